@@ -3,7 +3,7 @@
 on: C3 = configs[2], the Cornell box with the 819,212-triangle mesh at 1920 x 1080 x 1024 spp (the largest single-GPU
 configuration; configs[3] is the same scene across 2/4/8 GPUs).
 
-    python bench.py --gpus 1 --steps K --warmup W
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A *step* is one complete pass of the hot path over the workload: the whole image rendered into a film that is already
@@ -527,6 +527,39 @@ def timed_steps(wl, steps, warmup, seed, fence, dist, world_size):
     return elapsed * 1e3 / max(steps, 1), film, seeds_used
 
 
+DUMP_BYTES = 64_000_000  # all files of --dump-outputs together
+DUMP_SAMPLE_SEED = 20240607
+
+
+def dump_outputs(film, out_dir):
+    """What the last timed step handed its caller -- the film, [height, width, bins, 2] float32: per pixel and wavelength bin the
+    summed radiance and the exposure weight -- as .npy files under `out_dir`, so that two builds can be compared output for output:
+      film_pixels.npy        [n, bins, 2] float32, whole pixels of the film: all of them when they fit in 64 MB with their index,
+                             else a sample drawn with a fixed seed (the same pixels for every build and run of one workload)
+      film_pixel_index.npy   [n] float64, the row-major index y * width + x of each of those pixels (exact in float64)
+      film_bin_totals.npy    [bins, 2] float64, the film summed over ALL pixels, so that a difference outside the sample shows too
+    Returns the files' names and the pixel count. The film stays where it is; only the sampled rows are copied to the host."""
+    import numpy as np
+    import torch
+
+    height, width, bins, two = film.shape
+    pixels = height * width
+    flat = film.reshape(pixels, bins, two)
+    n = min(pixels, (DUMP_BYTES - 64_000) // (bins * two * 4 + 8))  # 64 kB left for the totals and the .npy headers
+    if n == pixels:
+        index = np.arange(pixels, dtype=np.int64)
+    else:
+        index = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(pixels, size=n, replace=False))
+    rows = flat.index_select(0, torch.from_numpy(index).to(film.device)).cpu().numpy()
+    totals = flat.sum(0, dtype=torch.float64).cpu().numpy()
+    os.makedirs(out_dir, exist_ok=True)
+    arrays = {"film_pixels": rows.astype(np.float32, copy=False), "film_pixel_index": index.astype(np.float64), "film_bin_totals": totals}
+    for name, array in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), array)
+    return {"dir": out_dir, "files": sorted(name + ".npy" for name in arrays), "pixels": int(n), "of_pixels": pixels,
+            "sample_seed": None if n == pixels else DUMP_SAMPLE_SEED}
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -543,7 +576,11 @@ def main():
     ap.add_argument("--no-c1", action="store_true", help="skip the extra C1 (configs[0]: GPU next to the oracle's full CPU render) measurement")
     ap.add_argument("--dev", default="", help="development overrides, e.g. spectrum_samples=1,light_samples=0,bounces=2 (marks the line reduced)")
     ap.add_argument("--seed", type=int, default=1)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the film of the last one to DIR/*.npy (rank 0; see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch
     import torch.distributed as dist
@@ -661,6 +698,8 @@ def main():
             "seeds": sorted(set(seeds_used)),
             "config": config,
         }
+        if args.dump_outputs:
+            line["outputs"] = dump_outputs(film, args.dump_outputs)
     del film
 
     if rank == 0:

@@ -61,9 +61,30 @@ def texture_fixtures():
         reemit_obj(os.path.join(src, name), os.path.join(out_dir, name), "test/textures " + name)
 
 
+def project_fixtures():
+    """test/spheres/spheres.lua and test/diamonds/diamonds.lua as the loader reads them (pyrite_amd/lua_project.py): the
+    flattened scene, camera, renderer parameters and film size of each, kept in reference_projects.json for
+    tests/test_lua_project.py to hold the scenes pyrite_amd/scenes.py restates against."""
+    import json
+
+    sys.path.insert(0, os.path.join(ROOT, "tests"))
+    from pyrite_amd import lua_project, scenes
+    from test_lua_project import scene_record
+
+    out = {}
+    for name in ("spheres", "diamonds"):
+        project, base_dir = lua_project.load_project(os.path.join(REFERENCE, name, name + ".lua"))
+        out[name] = scene_record(*scenes.build(project, seed=1, base_dir=base_dir))
+    with open(os.path.join(HERE, "reference_projects.json"), "w") as f:
+        json.dump(out, f, sort_keys=True)
+        f.write("\n")
+    print("reference_projects.json", sorted(out))
+
+
 def main():
     out = {}
     texture_fixtures()
+    project_fixtures()
     for name in ("spheres", "diamonds", "textures"):
         img = images.read_png(os.path.join(REFERENCE, name, "hq_example.png"))
         out[name] = block_means(img)

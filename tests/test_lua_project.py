@@ -1,6 +1,7 @@
 """The project-file loader (next row f2): the declarative Lua subset project files are written in, evaluated against the
 prelude's names, must build the same typed tree -- and so the same flattened scene -- as the Python surface does."""
 import ctypes as C
+import json
 import os
 
 import numpy as np
@@ -149,31 +150,29 @@ def test_gpu_renders_a_project_file(gpu_lib):
     assert_parity(film, cpu)
 
 
-REFERENCE_TESTS = "/root/reference/pyrite/test"
+REFERENCE_PROJECTS = os.path.join(HERE, "golden", "reference_projects.json")
+RENDERER_KEYS = ("pixel_samples", "bounces", "light_samples", "spectrum_samples", "spectrum_bins", "tile_size")
 
 
-@pytest.mark.skipif(not os.path.isdir(REFERENCE_TESTS), reason="the reference checkout only exists in the build container")
+def scene_record(world, cam, r, film):
+    """What the restated-scene check compares -- flattened world, camera, renderer parameters, film size -- in the form JSON keeps
+    exactly (floats by repr, bytes as hex); tests/golden/make_reference_fixtures.py stores it for the reference's project files."""
+    record = {"scene": desc_bytes(world), "camera": bytes(cam.c).hex(), "renderer": {key: getattr(r, key) for key in RENDERER_KEYS},
+              "film": [film.width, film.height, film.bins]}
+    return json.loads(json.dumps(record, default=bytes.hex))
+
+
 @pytest.mark.parametrize("name,restated", [("spheres", lambda: scenes.spheres_example(512, 256, 600)),
                                            ("diamonds", lambda: scenes.diamonds_example(512, 300, 200, bounces=256))])
 def test_the_reference_projects_load_and_equal_the_restated_scenes(name, restated):
-    """pyrite/test/<name>/<name>.lua read by the loader == the scene pyrite_amd/scenes.py restates by hand (the one the
-    reference-image tests render): same camera, renderer parameters and flattened world."""
-    project, base_dir = lua_project.load_project(os.path.join(REFERENCE_TESTS, name, name + ".lua"))
-    lua_world, lua_cam, lua_r, lua_film = scenes.build(project, seed=1, base_dir=base_dir)
-    py_world, py_cam, py_r, py_film = scenes.build(restated(), seed=1)
-    assert desc_bytes(lua_world) == desc_bytes(py_world)
-    assert bytes(lua_cam.c) == bytes(py_cam.c)
-    for key in ("pixel_samples", "bounces", "light_samples", "spectrum_samples", "spectrum_bins", "tile_size"):
-        assert getattr(lua_r, key) == getattr(py_r, key), key
-    assert (lua_film.width, lua_film.height, lua_film.bins) == (py_film.width, py_film.height, py_film.bins)
+    """pyrite/test/<name>/<name>.lua read by the loader (kept in golden/reference_projects.json) == the scene pyrite_amd/scenes.py
+    restates by hand (the one the reference-image tests render): same camera, renderer parameters and flattened world."""
+    with open(REFERENCE_PROJECTS) as f:
+        want = json.load(f)[name]
+    got = scene_record(*scenes.build(restated(), seed=1))
+    assert got["scene"] == want["scene"]
+    assert got["camera"] == want["camera"]
+    for key in RENDERER_KEYS:
+        assert got["renderer"][key] == want["renderer"][key], key
+    assert got["film"] == want["film"]
 
-
-@pytest.mark.skipif(not os.path.isdir(REFERENCE_TESTS), reason="the reference checkout only exists in the build container")
-def test_every_reference_project_file_parses():
-    import glob
-
-    for path in sorted(glob.glob(os.path.join(REFERENCE_TESTS, "*", "*.lua"))):
-        if os.path.basename(path) in ("materials.lua", "lamp.lua") or path.endswith("cornell/colors.lua"):
-            continue  # modules that other projects `require`
-        project, _ = lua_project.load_project(path)
-        assert project["renderer"].type in ("simple", "bidirectional", "photon_mapping") and len(project["world"]["objects"]) >= 1, path
