@@ -3,7 +3,7 @@
 on: C3 = configs[2], the Cornell box with the 819,212-triangle mesh at 1920 x 1080 x 1024 spp (the largest single-GPU
 configuration; configs[3] is the same scene across 2/4/8 GPUs).
 
-    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps K --warmup W [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
 A *step* is one complete pass of the hot path over the workload: the whole image rendered into a film that is already
@@ -14,7 +14,12 @@ assembly are inside the step (pyr_render_simple_sharded; see pyrite_amd/distribu
 both sides of exactly K steps, max over ranks, rank 0 prints one JSON line. `--workload C2|C1|C5` runs another BASELINE
 config instead.
 
-Extra objects on the line:
+A plain run does only what the headline needs: set-up, W warm-up steps, the K timed steps, the film-weight check of the last
+step, --dump-outputs, the line. Everything else takes runs of its own (instrumented launches, PMC child passes, other
+configurations, the CPU oracle: about two minutes on C3) and is measured only with `--full`, after the timed steps; the
+`--no-*` options leave parts of it out.
+
+Extra objects on the line (with --full):
   roofline      the dominant kernel of the workload. `achieved` = ALGORITHMIC bytes per launch (32 B
                 per box test, 36 B per triangle test, 16 B per sphere / plane test, 52 B per shaded hit, 16 B per film
                 exposure; counts from instrumented runs of the same launches -- same seeds -- outside the timed region) over
@@ -273,8 +278,7 @@ def pmc_pass(workload, seed, kernel_part, counters, extra_args=(), pass_seconds=
         return None, "this run is itself being profiled"
     out = tempfile.mkdtemp(prefix="pyr_pmc_", dir="/tmp")
     cmd = [rocprof, "--pmc", *counters, "--output-format", "csv", "-d", out, "-o", "pmc", "--", sys.executable, os.path.abspath(__file__),
-           "--workload", workload, "--steps", "1", "--warmup", "0", "--seed", str(seed), "--no-cpu-baseline", "--no-traversal", "--no-c2", "--no-c5",
-           "--no-c1", "--no-live-traffic", *extra_args]
+           "--workload", workload, "--steps", "1", "--warmup", "0", "--seed", str(seed), *extra_args]
     try:
         child = subprocess.Popen(cmd, cwd="/tmp", env=dict(os.environ, TMPDIR="/tmp"), stdout=subprocess.PIPE, stderr=subprocess.STDOUT, start_new_session=True)
         try:
@@ -567,13 +571,15 @@ def main():
     ap.add_argument("--warmup", type=int, default=1)
     ap.add_argument("--workload", default="C3", choices=sorted(WORKLOADS))
     ap.add_argument("--spp", type=int, default=None, help="override samples per pixel (development only: the line is then marked reduced)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-traversal", action="store_true", help="skip the BVH-traversal roofline measurement on the C3 scene")
-    ap.add_argument("--no-c2", action="store_true", help="skip the extra C2 (configs[1]) measurement")
-    ap.add_argument("--no-c5", action="store_true", help="skip the extra C5 (configs[4]'s workload on one GPU) measurement")
-    ap.add_argument("--no-live-traffic", action="store_true", help="skip the two rocprofv3 --pmc child passes (N = 1, full workload) that measure `roofline.traffic` "
-                                                                  "on this box; the line then carries the committed passes' figure")
-    ap.add_argument("--no-c1", action="store_true", help="skip the extra C1 (configs[0]: GPU next to the oracle's full CPU render) measurement")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also measure `roofline`, `issue`, `traversal_roofline`, `c2`, `c5`, "
+                                                       "`c1` and `cpu_baseline` (see the docstring); a plain run prints the headline alone")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU oracle's measurements (`cpu_baseline`, `c1`)")
+    ap.add_argument("--no-traversal", action="store_true", help="with --full: skip the BVH-traversal roofline measurement on the C3 scene")
+    ap.add_argument("--no-c2", action="store_true", help="with --full: skip the extra C2 (configs[1]) measurement")
+    ap.add_argument("--no-c5", action="store_true", help="with --full: skip the extra C5 (configs[4]'s workload on one GPU) measurement")
+    ap.add_argument("--no-live-traffic", action="store_true", help="with --full: skip the two rocprofv3 --pmc child passes (N = 1, full workload) that measure "
+                                                                  "`roofline.traffic` on this box; the line then carries the committed passes' figure")
+    ap.add_argument("--no-c1", action="store_true", help="with --full: skip the extra C1 (configs[0]: GPU next to the oracle's full CPU render) measurement")
     ap.add_argument("--dev", default="", help="development overrides, e.g. spectrum_samples=1,light_samples=0,bounces=2 (marks the line reduced)")
     ap.add_argument("--seed", type=int, default=1)
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
@@ -702,7 +708,7 @@ def main():
             line["outputs"] = dump_outputs(film, args.dump_outputs)
     del film
 
-    if rank == 0:
+    if rank == 0 and args.full:
         # kernel duration from HIP events on the launch stream: one launch per step and rank (the figure is rank 0's kernel
         # time and rank 0's algorithmic bytes, i.e. per GPU)
         launches = len(wl.launch_events)
@@ -768,9 +774,10 @@ def main():
             c1.world.close()
         if world_size == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(wl.world, wl.cam, wl.renderer, wl.width, wl.height)
+    if rank == 0:
         print(json.dumps(line), flush=True)
     if world_size > 1:
-        dist.barrier()  # rank 0 ran the instrumented pass above: leave together
+        dist.barrier()  # with --full, rank 0 ran the instrumented pass above: leave together
         dist.destroy_process_group()
     elif force_native:
         dist.destroy_process_group()

@@ -7,7 +7,7 @@ What lands in profiles/ (per round tag, e.g. r02):
   <tag>_<cfg>_pmc_fetch_size.csv / _write_size.csv   the raw counter rows of our kernels (separate --pmc passes)
   <tag>_<cfg>_sq_counters.txt         SQ counter sums of the dominant kernel + the derived lane occupancy
   <tag>_intersect16m_*.csv / .txt     the same for World::intersect on the 16 M-ray batch bench.py quotes
-  <tag>_c3_bench_full.json            the bench line of the driver's command (`bench.py --gpus 1 --steps 20 --warmup 5`)
+  <tag>_c3_bench_full.json            the bench line of `bench.py --gpus 1 --steps 20 --warmup 5 --full`
   traffic.json                        HBM bytes per launch (2 * FETCH_SIZE + WRITE_SIZE, MI355X_MICROARCH.md "HBM") and the
                                       rocprof average duration of the same kernel, read by bench.py"""
 import collections

@@ -8,7 +8,7 @@
 R=${GRAFT_REPO_ROOT:-$PWD}
 OUT=$1; shift
 mkdir -p "$OUT"
-ARGS=${PMC_BENCH_ARGS:---workload C3 --spp 32 --steps 1 --warmup 0 --no-cpu-baseline --no-c2 --no-c5}
+ARGS=${PMC_BENCH_ARGS:---workload C3 --spp 32 --steps 1 --warmup 0 --full --no-cpu-baseline --no-c2 --no-c5}
 LIMIT=${PMC_PASS_SECONDS:-240}
 cd /tmp && export TMPDIR=/tmp
 n=0

@@ -19,7 +19,7 @@ C3="--workload C3 --no-cpu-baseline --no-traversal --no-c2 --no-c5 --no-c1 --no-
 PMC="--pmc"
 if [ "${ONLY:-all}" = "all" ] || [ "$ONLY" = "bench" ]; then
   T0=$(date +%s.%N)
-  timeout -k 10 900 python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 > $OUT/c3_bench.json 2> $OUT/c3_bench.err; rc=$?
+  timeout -k 10 900 python3 $R/bench.py --gpus 1 --steps 20 --warmup 5 --full > $OUT/c3_bench.json 2> $OUT/c3_bench.err; rc=$?
   python3 -c "import time,sys; print(\"%.1f s wall\" % (time.time() - float(sys.argv[1])))" $T0 > $OUT/c3_bench.wall; echo "[bench C3 driver args] rc=$rc $(cat $OUT/c3_bench.wall)"
 fi
 if [ "${ONLY:-all}" = "all" ] || [ "$ONLY" = "c3" ]; then
@@ -38,7 +38,7 @@ if [ "${ONLY:-all}" = "all" ] || [ "$ONLY" = "isect" ]; then
   step isect_tcp 300 rocprofv3 $PMC TCP_TCC_READ_REQ_sum TCP_TOTAL_CACHE_ACCESSES_sum --output-format csv -d $OUT/isect_tcp -o tcp -- python3 $R/tools/prof_intersect_c3.py
 fi
 if [ "${ONLY:-all}" = "all" ] || [ "$ONLY" = "c5" ]; then
-  step c5_bench 600 python3 $R/bench.py --workload C5 --steps 1 --warmup 0 --no-cpu-baseline --no-traversal --no-live-traffic
+  step c5_bench 600 python3 $R/bench.py --workload C5 --steps 1 --warmup 0 --full --no-cpu-baseline --no-traversal --no-live-traffic
   step c5_trace 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/c5_trace -o c5 -- python3 $R/bench.py --workload C5 --spp 256 --steps 2 --warmup 0 --no-cpu-baseline --no-traversal --no-live-traffic
   step c5_fetch 300 rocprofv3 $PMC FETCH_SIZE --output-format csv -d $OUT/c5_fetch -o fetch -- python3 $R/bench.py --workload C5 --steps 1 --warmup 0 --no-cpu-baseline --no-traversal --no-live-traffic
   step c5_write 300 rocprofv3 $PMC WRITE_SIZE --output-format csv -d $OUT/c5_write -o write -- python3 $R/bench.py --workload C5 --steps 1 --warmup 0 --no-cpu-baseline --no-traversal --no-live-traffic

@@ -30,7 +30,7 @@ for spec in args:
     for pair in filter(None, envs.split(",")):
         k, v = pair.split("=")
         env[k] = v
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--spp", spp, "--steps", steps, "--warmup", "1", "--no-cpu-baseline",
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--workload", workload, "--spp", spp, "--steps", steps, "--warmup", "1", "--full", "--no-cpu-baseline",
            "--no-traversal", "--no-c2"]
     try:
         out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=400)
