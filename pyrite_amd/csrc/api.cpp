@@ -436,8 +436,16 @@ int pack_and_upload(const PyrSceneDesc* d, PyrScene* s) {
     const char* wide_switch = std::getenv("PYRITE_WIDE_BVH");
     const char* pair_switch = std::getenv("PYRITE_PAIR_PRIMS");
     const bool pair_tree_expected = d->num_spheres == 0 && bounds.size() * 48 > 8 * 1024 && !(wide_switch && wide_switch[0] == '0') && !(pair_switch && pair_switch[0] == '0');
-    BuiltBvh bvh = build_bvh(bounds, pair_tree_expected);
+    // The pair tree may also split space (PYRITE_SPATIAL_SPLITS, bvh.h) and is collapsed by cost (PYRITE_WIDE_COLLAPSE); every
+    // other tree is built and collapsed as before, byte for byte.
+    const bool spatial = pair_tree_expected && spatial_splits_wanted();
+    const bool cost_driven_collapse = pair_tree_expected && cost_driven_collapse_wanted();
+    SpatialSplits spatial_params;
+    spatial_params.tri_positions = d->tri_positions;
+    BuiltBvh bvh = spatial ? build_bvh_spatial(bounds, spatial_params) : build_bvh(bounds, pair_tree_expected);
     if (bvh.max_depth > 96) return fail(PYR_ERR_UNSUPPORTED, "BVH deeper than the LDS traversal stack allows");
+    // spatial splits repeat triangles in prim_order (and so in `prims` and the pair records): a leaf code keeps `first` in 28 bits
+    if (bvh.prim_order.size() >= (1ull << 28)) return fail(PYR_ERR_UNSUPPORTED, "scene too large: 2^28 primitive references or more");
 
     std::vector<DevPrim> prims(bvh.prim_order.size());
     for (size_t k = 0; k < prims.size(); ++k) {
@@ -598,7 +606,7 @@ int pack_and_upload(const PyrSceneDesc* d, PyrScene* s) {
     const char* wide_env = std::getenv("PYRITE_WIDE_BVH");
     const bool want_wide = (size_t)bvh.nodes.size() * 64 + prims.size() * 48 > 8 * 1024 && !(wide_env && wide_env[0] == '0');
     if (want_wide) {
-        wide = collapse_to_wide(bvh);
+        wide = cost_driven_collapse ? collapse_to_wide_sah(bvh) : collapse_to_wide(bvh);
         if (wide.stack_need > kMaxStackDepth || wide.nodes.size() >= (1ull << 25)) wide = WideBvh{}; // too deep, or past 4 GB: the binary tree
     }
     // Triangle pairs for the wide tree's leaves (device_scene.h DevPrimPair): every leaf gets ceil(n / 2) records of its own and
@@ -764,7 +772,7 @@ int pack_and_upload(const PyrSceneDesc* d, PyrScene* s) {
     s->info.num_nodes = (uint32_t)bvh.nodes.size();
     s->info.num_leaves = bvh.num_leaves;
     s->info.max_depth = bvh.max_depth;
-    s->info.num_primitives = (uint32_t)prims.size();
+    s->info.num_primitives = (uint32_t)bounds.size(); // the scene's primitives; `prims` and the pair records may repeat some (spatial splits)
     s->info.node_bytes = bvh.nodes.size() * sizeof(Node64);
     s->info.primitive_bytes = prims.size() * sizeof(DevPrim);
     s->info.num_wide_nodes = (uint32_t)wide.nodes.size();

@@ -2,7 +2,10 @@
 #include "bvh.h"
 
 #include <algorithm>
+#include <array>
 #include <cmath>
+#include <cstdlib>
+#include <cstring>
 #include <limits>
 
 namespace pyr {
@@ -228,6 +231,327 @@ BuiltBvh build_bvh(const std::vector<PrimBounds>& prims, bool leaves_tested_in_p
     return out;
 }
 
+namespace {
+
+struct SRef {
+    Box box; // the part of the triangle this reference stands for (its whole box unless it was clipped)
+    uint32_t shape;
+    float c(int a) const { return 0.5f * box.lo[a] + 0.5f * box.hi[a]; }
+};
+
+bool box_valid(const Box& b) { return b.lo[0] <= b.hi[0] && b.lo[1] <= b.hi[1] && b.lo[2] <= b.hi[2]; }
+
+Box box_and(const Box& x, const Box& y) {
+    Box r;
+    for (int a = 0; a < 3; ++a) r.lo[a] = std::max(x.lo[a], y.lo[a]), r.hi[a] = std::min(x.hi[a], y.hi[a]);
+    return r;
+}
+
+// Bounds of the part of triangle `v` whose coordinate `axis` lies in [a, b], intersected with `clip`; an invalid box when that part
+// is empty. The polygon's corners are the triangle's corners inside the slab and the edges' crossings of its two planes; the
+// crossings are computed in double and rounded outward (with a margin far above the double rounding error), and on `axis` the
+// bounds are the float corners and planes themselves, so the box contains every point of the part.
+Box clip_triangle(const float* v, int axis, float a, float b, const Box& clip) {
+    double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY};
+    double mag = 0.0;
+    for (int k = 0; k < 9; ++k) mag = std::max(mag, (double)std::fabs(v[k]));
+    auto add = [&](const double* p) {
+        for (int k = 0; k < 3; ++k) lo[k] = std::min(lo[k], p[k]), hi[k] = std::max(hi[k], p[k]);
+    };
+    for (int e = 0; e < 3; ++e) {
+        const float* p = v + 3 * e;
+        const float* q = v + 3 * ((e + 1) % 3);
+        const double P[3] = {p[0], p[1], p[2]}, Q[3] = {q[0], q[1], q[2]};
+        if (P[axis] >= a && P[axis] <= b) add(P);
+        for (const float plane : {a, b}) {
+            if ((P[axis] < plane && Q[axis] > plane) || (P[axis] > plane && Q[axis] < plane)) {
+                const double t = ((double)plane - P[axis]) / (Q[axis] - P[axis]);
+                double X[3];
+                for (int k = 0; k < 3; ++k) X[k] = P[k] + t * (Q[k] - P[k]);
+                X[axis] = plane;
+                add(X);
+            }
+        }
+    }
+    Box r;
+    if (!(lo[0] <= hi[0])) return r;
+    const double slack = 1.0e-12 * mag;
+    for (int k = 0; k < 3; ++k) {
+        if (k == axis) { // corners and planes: float values already
+            r.lo[k] = (float)lo[k], r.hi[k] = (float)hi[k];
+            continue;
+        }
+        const double l = lo[k] - slack, h = hi[k] + slack;
+        float fl = (float)l, fh = (float)h;
+        if ((double)fl > l) fl = std::nextafter(fl, -kInf);
+        if ((double)fh < h) fh = std::nextafter(fh, kInf);
+        r.lo[k] = fl, r.hi[k] = fh;
+    }
+    return box_and(r, clip);
+}
+
+} // namespace
+
+bool spatial_splits_wanted() {
+    const char* e = std::getenv("PYRITE_SPATIAL_SPLITS");
+    return e && e[0] == '1';
+}
+
+bool cost_driven_collapse_wanted() {
+    const char* e = std::getenv("PYRITE_WIDE_COLLAPSE");
+    return !(e && std::strcmp(e, "greedy") == 0);
+}
+
+BuiltBvh build_bvh_spatial(const std::vector<PrimBounds>& prims, const SpatialSplits& spatial) {
+    BuiltBvh out;
+    const uint32_t n = (uint32_t)prims.size();
+    const float* tri = spatial.tri_positions;
+    std::vector<SRef> refs(n);
+    for (uint32_t i = 0; i < n; ++i) {
+        for (int a = 0; a < 3; ++a) refs[i].box.lo[a] = prims[i].lo[a], refs[i].box.hi[a] = prims[i].hi[a];
+        refs[i].shape = prims[i].shape;
+    }
+    // the same padding as build_bvh: clipped boxes lie inside the triangles' own boxes, so the largest coordinate is the same
+    float max_abs = 0.0f;
+    for (uint32_t i = 0; i < n; ++i)
+        for (int a = 0; a < 3; ++a) max_abs = std::max(max_abs, std::max(std::fabs(prims[i].lo[a]), std::fabs(prims[i].hi[a])));
+    const float pad = 16.0f * 1.1920929e-7f * max_abs;
+
+    auto set_child = [&](int32_t parent, int slot, int32_t code, const Box& box) {
+        Node64& p = out.nodes[parent];
+        p.child[slot] = code;
+        p.lo_x[slot] = box.lo[0] - pad, p.lo_y[slot] = box.lo[1] - pad, p.lo_z[slot] = box.lo[2] - pad;
+        p.hi_x[slot] = box.hi[0] + pad, p.hi_y[slot] = box.hi[1] + pad, p.hi_z[slot] = box.hi[2] + pad;
+    };
+    auto empty_node = []() {
+        Node64 nd{};
+        for (int c = 0; c < 2; ++c) {
+            nd.lo_x[c] = nd.lo_y[c] = nd.lo_z[c] = kInf;
+            nd.hi_x[c] = nd.hi_y[c] = nd.hi_z[c] = -kInf;
+            nd.child[c] = encode_leaf(0, 0);
+        }
+        return nd;
+    };
+    out.nodes.push_back(empty_node());
+    if (n == 0) return out;
+
+    const bool in_pairs = PYR_SAH_PAIRS != 0;
+    auto leaf_tests = [in_pairs](uint32_t count) { return in_pairs ? (float)((count + 1u) & ~1u) : (float)count; };
+    Box root_box;
+    for (const SRef& r : refs) root_box.grow(r.box);
+    const float min_overlap = spatial.alpha * root_box.half_area();
+    const uint64_t budget = (uint64_t)std::max(0.0, std::floor((double)spatial.max_duplication * n) - n);
+
+    auto make_leaf = [&](const std::vector<SRef>& rs, uint32_t depth, int32_t parent, int slot, const Box& box) {
+        const uint32_t first = (uint32_t)out.prim_order.size();
+        for (const SRef& r : rs) out.prim_order.push_back(r.shape);
+        set_child(parent, slot, encode_leaf(first, (uint32_t)rs.size()), box);
+        out.num_leaves++;
+        out.max_depth = std::max(out.max_depth, depth);
+    };
+
+    // Builds the subtree of `rs` as child `slot` of `parent` (depth counts edges from the root; the root's own range is split
+    // into its two children at depth 1, as in build_bvh). `extra`: references this subtree may add by splitting.
+    auto build = [&](auto&& self, std::vector<SRef>& rs, uint32_t depth, int32_t parent, int slot, uint64_t extra) -> void {
+        const uint32_t count = (uint32_t)rs.size();
+        Box box, cbox;
+        for (const SRef& r : rs) {
+            box.grow(r.box);
+            float c[3] = {r.c(0), r.c(1), r.c(2)};
+            cbox.grow_point(c);
+        }
+        const bool is_root = parent < 0;
+        if (!is_root && count <= 1) return make_leaf(rs, depth, parent, slot, box);
+        const bool force_median = depth + ceil_log2((count + kMaxLeafPrims - 1) / kMaxLeafPrims) + 1 >= kMaxBvhDepth;
+
+        // binned object split over the references' centroids (build_bvh's rule)
+        float obj_cost = kInf;
+        int obj_axis = -1, obj_bin = -1;
+        Box obj_left, obj_right;
+        if (!force_median) {
+            for (int a = 0; a < 3; ++a) {
+                const float extent = cbox.hi[a] - cbox.lo[a];
+                if (!(extent > 0.0f)) continue;
+                Box bin_box[kBins];
+                uint32_t bin_count[kBins] = {0};
+                const float scale = (float)kBins / extent;
+                for (const SRef& r : rs) {
+                    const int b = std::min(kBins - 1, std::max(0, (int)((r.c(a) - cbox.lo[a]) * scale)));
+                    bin_box[b].grow(r.box);
+                    bin_count[b]++;
+                }
+                Box right_box[kBins];
+                uint32_t right_count[kBins];
+                Box acc;
+                uint32_t cnt = 0;
+                for (int b = kBins - 1; b > 0; --b) {
+                    acc.grow(bin_box[b]);
+                    cnt += bin_count[b];
+                    right_box[b] = acc;
+                    right_count[b] = cnt;
+                }
+                Box left;
+                uint32_t lcnt = 0;
+                for (int b = 0; b < kBins - 1; ++b) {
+                    left.grow(bin_box[b]);
+                    lcnt += bin_count[b];
+                    if (lcnt == 0 || right_count[b + 1] == 0) continue;
+                    const float cost = left.half_area() * leaf_tests(lcnt) + right_box[b + 1].half_area() * leaf_tests(right_count[b + 1]);
+                    if (cost < obj_cost) obj_cost = cost, obj_axis = a, obj_bin = b, obj_left = left, obj_right = right_box[b + 1];
+                }
+            }
+        }
+        // binned spatial split, where the object split's children overlap
+        float sp_cost = kInf;
+        int sp_axis = -1;
+        uint32_t sp_left_n = 0, sp_right_n = 0;
+        Box sp_left, sp_right;
+        float sp_plane = 0.0f;
+        const Box overlap = box_and(obj_left, obj_right);
+        if (obj_axis >= 0 && extra > 0 && box_valid(overlap) && overlap.half_area() > min_overlap) {
+            for (int a = 0; a < 3; ++a) {
+                const float extent = box.hi[a] - box.lo[a];
+                if (!(extent > 0.0f)) continue;
+                float plane[kSpatialBins + 1];
+                for (int b = 0; b <= kSpatialBins; ++b) plane[b] = box.lo[a] + extent * ((float)b / (float)kSpatialBins);
+                plane[kSpatialBins] = box.hi[a];
+                const float scale = (float)kSpatialBins / extent;
+                auto bin_of = [&](float x) {
+                    int b = std::min(kSpatialBins - 1, std::max(0, (int)((x - box.lo[a]) * scale)));
+                    while (b > 0 && x < plane[b]) --b;
+                    while (b < kSpatialBins - 1 && x >= plane[b + 1]) ++b;
+                    return b;
+                };
+                Box bin_box[kSpatialBins];
+                uint32_t entry[kSpatialBins] = {0}, exit[kSpatialBins] = {0};
+                for (const SRef& r : rs) {
+                    const int b0 = bin_of(r.box.lo[a]);
+                    int b1 = bin_of(r.box.hi[a]);
+                    while (b1 > b0 && r.box.hi[a] <= plane[b1]) --b1;
+                    entry[b0]++, exit[b1]++;
+                    if (b0 == b1) {
+                        bin_box[b0].grow(r.box);
+                        continue;
+                    }
+                    const float* v = tri + 9 * (size_t)(r.shape & 0x3FFFFFFFu);
+                    for (int b = b0; b <= b1; ++b) {
+                        const Box part = clip_triangle(v, a, plane[b], plane[b + 1], r.box);
+                        if (box_valid(part)) bin_box[b].grow(part);
+                    }
+                }
+                Box right_box[kSpatialBins];
+                uint32_t right_count[kSpatialBins];
+                Box acc;
+                uint32_t cnt = 0;
+                for (int b = kSpatialBins - 1; b > 0; --b) {
+                    acc.grow(bin_box[b]);
+                    cnt += exit[b];
+                    right_box[b] = acc;
+                    right_count[b] = cnt;
+                }
+                Box left;
+                uint32_t lcnt = 0;
+                for (int b = 0; b < kSpatialBins - 1; ++b) {
+                    left.grow(bin_box[b]);
+                    lcnt += entry[b];
+                    const uint32_t rcnt = right_count[b + 1];
+                    if (lcnt == 0 || rcnt == 0 || lcnt >= count || rcnt >= count || lcnt + rcnt - count > extra) continue;
+                    const float cost = left.half_area() * leaf_tests(lcnt) + right_box[b + 1].half_area() * leaf_tests(rcnt);
+                    if (cost < sp_cost)
+                        sp_cost = cost, sp_axis = a, sp_left = left, sp_right = right_box[b + 1], sp_left_n = lcnt, sp_right_n = rcnt,
+                        sp_plane = plane[b + 1];
+                }
+            }
+        }
+        const bool use_spatial = sp_axis >= 0 && sp_cost < obj_cost;
+        const float best_cost = use_spatial ? sp_cost : obj_cost;
+        if (!is_root && (obj_axis >= 0 || use_spatial)) {
+            const float parent_area = box.half_area();
+            const float split_cost = kSahNodeCost + (parent_area > 0.0f ? best_cost / parent_area : kInf);
+            if (count <= kMaxLeafPrims && leaf_tests(count) <= split_cost) return make_leaf(rs, depth, parent, slot, box);
+        }
+        std::vector<SRef> left, right;
+        if (use_spatial) {
+            // references that straddle the plane are clipped to both sides, or kept whole on one side where that is cheaper
+            // (the "unsplitting" of the SBVH paper, judged against the binned children)
+            Box bl = sp_left, br = sp_right;
+            uint32_t nl = sp_left_n, nr = sp_right_n;
+            const int a = sp_axis;
+            for (const SRef& r : rs) {
+                if (r.box.hi[a] <= sp_plane) {
+                    left.push_back(r);
+                    continue;
+                }
+                if (r.box.lo[a] >= sp_plane) {
+                    right.push_back(r);
+                    continue;
+                }
+                const float* v = tri + 9 * (size_t)(r.shape & 0x3FFFFFFFu);
+                const Box lb = clip_triangle(v, a, -kInf, sp_plane, r.box), rb = clip_triangle(v, a, sp_plane, kInf, r.box);
+                if (!box_valid(lb) || !box_valid(rb)) {
+                    (box_valid(lb) ? left : right).push_back(SRef{box_valid(lb) ? lb : rb, r.shape});
+                    continue;
+                }
+                Box bl_whole = bl, br_whole = br;
+                bl_whole.grow(r.box), br_whole.grow(r.box);
+                const float c_split = bl.half_area() * (float)nl + br.half_area() * (float)nr;
+                const float c_left = bl_whole.half_area() * (float)nl + br.half_area() * (float)(nr - 1);
+                const float c_right = bl.half_area() * (float)(nl - 1) + br_whole.half_area() * (float)nr;
+                if (c_left < c_split && c_left <= c_right) {
+                    left.push_back(r), bl = bl_whole, nr--;
+                } else if (c_right < c_split) {
+                    right.push_back(r), br = br_whole, nl--;
+                } else {
+                    left.push_back(SRef{lb, r.shape});
+                    right.push_back(SRef{rb, r.shape});
+                }
+            }
+        } else {
+            uint32_t mid = 0;
+            if (obj_axis >= 0) {
+                const float scale = (float)kBins / (cbox.hi[obj_axis] - cbox.lo[obj_axis]);
+                const float lo = cbox.lo[obj_axis];
+                auto it = std::partition(rs.begin(), rs.end(), [&](const SRef& r) {
+                    const int b = std::min(kBins - 1, std::max(0, (int)((r.c(obj_axis) - lo) * scale)));
+                    return b <= obj_bin;
+                });
+                mid = (uint32_t)(it - rs.begin());
+            }
+            if (mid == 0 || mid == count) {
+                if (!is_root && count <= kMaxLeafPrims) return make_leaf(rs, depth, parent, slot, box);
+                int a = 0;
+                float w = -1.0f;
+                for (int k = 0; k < 3; ++k)
+                    if (cbox.hi[k] - cbox.lo[k] > w) w = cbox.hi[k] - cbox.lo[k], a = k;
+                mid = count / 2;
+                std::nth_element(rs.begin(), rs.begin() + mid, rs.end(), [a](const SRef& x, const SRef& y) { return x.c(a) < y.c(a); });
+            }
+            left.assign(rs.begin(), rs.begin() + mid);
+            right.assign(rs.begin() + mid, rs.end());
+        }
+        std::vector<SRef>().swap(rs);
+        const uint64_t added = left.size() + right.size() - count;
+        const uint64_t rest = extra - std::min(extra, added);
+        const uint64_t rest_left = rest * left.size() / (left.size() + right.size());
+        int32_t id = 0;
+        if (!is_root) {
+            id = (int32_t)out.nodes.size();
+            out.nodes.push_back(empty_node());
+            set_child(parent, slot, id, box);
+        }
+        self(self, left, depth + 1, id, 0, rest_left);
+        self(self, right, depth + 1, id, 1, rest - rest_left);
+    };
+    if (n <= kMaxLeafPrims) {
+        Box box;
+        for (const SRef& r : refs) box.grow(r.box);
+        make_leaf(refs, 1, 0, 0, box);
+        return out;
+    }
+    build(build, refs, 0, -1, 0, budget);
+    return out;
+}
+
 WideBvh collapse_to_wide(const BuiltBvh& bvh) {
     WideBvh out;
     struct Child {
@@ -292,6 +616,145 @@ WideBvh collapse_to_wide(const BuiltBvh& bvh) {
                 todo.push_back(Task{real[k].code, index, t.depth + 1, t.stack_before + pushes});
             } else {
                 node.child[k] = real[k].code;
+            }
+        }
+        out.nodes[t.wide_index] = node;
+    }
+    return out;
+}
+
+WideBvh collapse_to_wide_sah(const BuiltBvh& bvh) {
+    WideBvh out;
+    const size_t nn = bvh.nodes.size();
+    struct Slot {
+        float lo[3], hi[3];
+        int32_t code; // Node64 child code
+    };
+    auto slot_of = [&](int32_t node, int k) {
+        const Node64& n = bvh.nodes[node];
+        return Slot{{n.lo_x[k], n.lo_y[k], n.lo_z[k]}, {n.hi_x[k], n.hi_y[k], n.hi_z[k]}, n.child[k]};
+    };
+    auto area = [](const Slot& c) {
+        const float dx = c.hi[0] - c.lo[0], dy = c.hi[1] - c.lo[1], dz = c.hi[2] - c.lo[2];
+        return dx >= 0 && dy >= 0 && dz >= 0 ? dx * dy + dy * dz + dz * dx : 0.0f;
+    };
+    auto leaf_count = [](int32_t code) { return (uint32_t)(-1 - code) & 7u; };
+    auto leaf_first = [](int32_t code) { return (uint32_t)(-1 - code) >> 3; };
+    auto leaf_cost = [](uint32_t count) { return kWidePairCost * (float)((count + 1u) / 2u); };
+
+    // Per binary node, bottom-up (a child's index is always larger than its parent's): the references under it -- contiguous in
+    // prim_order, the builder emits leaves depth first -- and cost[n][i], the least cost of its subtree when it may take up i
+    // slots of the wide node above it: i = 1 is one wide node or one leaf, i > 1 also spreads its children over the slots.
+    std::vector<uint32_t> total(nn, 0), first(nn, UINT32_MAX);
+    std::vector<float> node_area(nn, 0.0f);
+    std::vector<std::array<float, 5>> cost(nn);
+    std::vector<std::array<int8_t, 5>> pick(nn); // i >= 2: k slots to child 0 (0: child 0 is empty), -1: use i - 1 slots; i = 1: 1 leaf, 0 node
+    auto slot_cost = [&](const Slot& c, int i) -> float {
+        if (c.code >= 0) return cost[c.code][i];
+        const uint32_t cnt = leaf_count(c.code);
+        return cnt ? area(c) * leaf_cost(cnt) : 0.0f;
+    };
+    auto real = [&](const Slot& c) { return c.code >= 0 || leaf_count(c.code) != 0; };
+    // least cost of node n's two children spread over exactly up to j slots, and how many of them go to child 0
+    auto distribute = [&](size_t n, int j, int& k_best) {
+        const Slot c0 = slot_of((int32_t)n, 0), c1 = slot_of((int32_t)n, 1);
+        const bool r0 = real(c0), r1 = real(c1);
+        k_best = -1;
+        if (!r0 && !r1) return k_best = 0, 0.0f;
+        if (!r1) return k_best = j, slot_cost(c0, j);
+        if (!r0) return k_best = 0, slot_cost(c1, j);
+        float best = kInf;
+        for (int k = 1; k < j; ++k) {
+            const float c = slot_cost(c0, k) + slot_cost(c1, j - k);
+            if (c < best) best = c, k_best = k;
+        }
+        return best;
+    };
+    for (size_t n = 0; n < nn; ++n)
+        for (int k = 0; k < 2; ++k)
+            if (bvh.nodes[n].child[k] >= 0) node_area[bvh.nodes[n].child[k]] = area(slot_of((int32_t)n, k));
+    for (size_t n = nn; n-- > 0;) {
+        for (int k = 0; k < 2; ++k) {
+            const Slot c = slot_of((int32_t)n, k);
+            if (c.code >= 0) {
+                total[n] += total[c.code];
+                first[n] = std::min(first[n], first[c.code]);
+            } else if (leaf_count(c.code)) {
+                total[n] += leaf_count(c.code);
+                first[n] = std::min(first[n], leaf_first(c.code));
+            }
+        }
+        int k4;
+        const float as_node = node_area[n] * kWideNodeCost + distribute(n, 4, k4);
+        const float as_leaf = total[n] <= kMaxLeafPrims ? node_area[n] * leaf_cost(total[n]) : kInf;
+        cost[n][0] = kInf;
+        cost[n][1] = as_leaf < as_node ? as_leaf : as_node;
+        pick[n][1] = as_leaf < as_node ? 1 : 0;
+        for (int i = 2; i <= 4; ++i) {
+            int k;
+            const float spread = distribute(n, i, k);
+            if (spread < cost[n][i - 1]) {
+                cost[n][i] = spread, pick[n][i] = (int8_t)k;
+            } else {
+                cost[n][i] = cost[n][i - 1], pick[n][i] = -1;
+            }
+        }
+    }
+    // the slots a wide node gets for binary node n's children, spread over at most j of them
+    auto gather = [&](auto&& self, int32_t n, int j, std::vector<Slot>& kids) -> void {
+        int k;
+        distribute((size_t)n, j, k);
+        for (int side = 0; side < 2; ++side) {
+            const Slot c = slot_of(n, side);
+            int i = side == 0 ? k : j - k;
+            if (!real(c) || i <= 0) continue;
+            if (c.code < 0) {
+                kids.push_back(c);
+                continue;
+            }
+            while (i > 1 && pick[c.code][i] < 0) --i;
+            if (i > 1) {
+                self(self, c.code, i, kids);
+            } else if (pick[c.code][1] == 1) {
+                Slot leaf = c;
+                leaf.code = encode_leaf(first[c.code], total[c.code]);
+                kids.push_back(leaf);
+            } else {
+                kids.push_back(c);
+            }
+        }
+    };
+    struct Task {
+        int32_t binary_node; // Node64 index this wide node stands for
+        int32_t wide_index;
+        uint32_t depth, stack_before;
+    };
+    out.nodes.emplace_back();
+    std::vector<Task> todo{{0, 0, 1, 0}};
+    while (!todo.empty()) {
+        Task t = todo.back();
+        todo.pop_back();
+        std::vector<Slot> kids;
+        gather(gather, t.binary_node, 4, kids);
+        Node128 node{};
+        for (int k = 0; k < 4; ++k) { // unused slots: NaN boxes, as in collapse_to_wide
+            node.lo_x[k] = node.lo_y[k] = node.lo_z[k] = std::numeric_limits<float>::quiet_NaN();
+            node.hi_x[k] = node.hi_y[k] = node.hi_z[k] = std::numeric_limits<float>::quiet_NaN();
+            node.child[k] = kEmptyChild;
+        }
+        const uint32_t pushes = kids.empty() ? 0u : (uint32_t)kids.size() - 1u;
+        out.max_depth = std::max(out.max_depth, t.depth);
+        out.stack_need = std::max(out.stack_need, t.stack_before + pushes);
+        for (size_t k = 0; k < kids.size(); ++k) {
+            node.lo_x[k] = kids[k].lo[0], node.lo_y[k] = kids[k].lo[1], node.lo_z[k] = kids[k].lo[2];
+            node.hi_x[k] = kids[k].hi[0], node.hi_y[k] = kids[k].hi[1], node.hi_z[k] = kids[k].hi[2];
+            if (kids[k].code >= 0) {
+                const int32_t index = (int32_t)out.nodes.size();
+                out.nodes.emplace_back();
+                node.child[k] = index;
+                todo.push_back(Task{kids[k].code, index, t.depth + 1, t.stack_before + pushes});
+            } else {
+                node.child[k] = kids[k].code;
             }
         }
         out.nodes[t.wide_index] = node;

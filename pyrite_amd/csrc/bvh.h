@@ -62,10 +62,30 @@ inline int32_t encode_leaf(uint32_t first, uint32_t count) { return -1 - (int32_
 // when PYR_SAH_PAIRS is on; everything else (sphere scenes, LDS-resident scenes, the binary walk) counts singly.
 BuiltBvh build_bvh(const std::vector<PrimBounds>& prims, bool leaves_tested_in_pairs = false);
 
+// Spatial splits (SBVH, Stich et al. 2009) for a triangle-only pair tree: at every node where the best object split's two
+// children overlap by more than `alpha` x the root's area, a binned split of space (kSpatialBins planes per axis) competes
+// with it; a triangle that straddles the chosen plane is clipped against it -- the triangle itself, not its box -- and goes
+// to both sides, unless keeping it whole on one side is cheaper. The references may then repeat a triangle (never twice in
+// one leaf), at most `max_duplication` x the triangles in all: each node passes the budget it has left on to its children in
+// proportion to their references, so the tree is the same whatever order it were built in. Clipped boxes are rounded
+// outward and never leave the triangle's own box, so build_bvh's padding argument holds for them unchanged.
+struct SpatialSplits {
+    const float* tri_positions = nullptr; // 9 floats per triangle, indexed by the shape code's index
+    float alpha = 1.0e-5f;
+    float max_duplication = 1.4f;
+};
+constexpr int kSpatialBins = 32;
+BuiltBvh build_bvh_spatial(const std::vector<PrimBounds>& prims, const SpatialSplits& spatial);
+// PYRITE_SPATIAL_SPLITS=1 (read at scene creation) builds the pair tree with spatial splits; unset or "0", with build_bvh's
+// object splits. Off by default: on C3's mesh they raise the tree's SAH cost instead of lowering it (DESIGN §8b,
+// profiles/r05_bvh_quality.txt) and take 10x as long to build.
+bool spatial_splits_wanted();
+
 // Four-child node, 128 bytes = one L2 line, read as eight float4: lo.x[4] lo.y[4] lo.z[4] hi.x[4] hi.y[4] hi.z[4] child[4]
-// pad[4]. Built by collapsing the binary tree (the child with the largest surface area is replaced by its own two children
-// until the node has four): a ray then makes about half as many dependent node fetches. Used by the resumable traversal
-// on scenes that do not live in LDS, where the walk is latency bound; unused slots hold kEmptyChild and are never entered.
+// pad[4]. Built by collapsing the binary tree (collapse_to_wide: the child with the largest surface area is replaced by its own
+// two children until the node has four; the pair tree: collapse_to_wide_sah below): a ray then makes about half as many dependent
+// node fetches. Used by the resumable traversal on scenes that do not live in LDS, where the walk is latency bound; unused slots
+// hold kEmptyChild and are never entered.
 struct alignas(128) Node128 {
     float lo_x[4], lo_y[4], lo_z[4], hi_x[4], hi_y[4], hi_z[4];
     int32_t child[4]; // >= 0: Node128 index; < 0: leaf code as in Node64; kEmptyChild: nothing
@@ -80,5 +100,18 @@ struct WideBvh {
     uint32_t stack_need = 0;    // entries an ordered traversal can hold at once: max over paths of sum(children - 1)
 };
 WideBvh collapse_to_wide(const BuiltBvh& bvh);
+// The cost-driven collapse (Ylitie et al. 2017, for four-child nodes): dynamic programming over the binary tree decides for
+// every subtree whether it becomes a wide node, a leaf (at most kMaxLeafPrims references, tested two per step) or is spread
+// over up to four slots of its parent, by surface area x (kWideNodeCost per visit, kWidePairCost per pair step). Unlike
+// the greedy rule above it weighs opening a node against stopping, and may turn a small subtree into one leaf. A pair step is
+// weighed at 1.5 node visits: at 1.0 the collapse merges leaves freely (two leaves of two triangles into one of four: the same
+// pair records, but all four triangles are tested whenever the merged box is hit) -- C3 +16 % triangle tests for -8 % box tests;
+// from 1.2 on the steps per ray are the same (tools/bvh_quality.cpp) and the triangle tests within 3 % of the greedy tree's.
+constexpr float kWideNodeCost = 1.0f;
+constexpr float kWidePairCost = 1.5f;
+WideBvh collapse_to_wide_sah(const BuiltBvh& bvh);
+// PYRITE_WIDE_COLLAPSE (read at scene creation): "greedy" collapses the pair tree by the greedy rule (A/B); anything else,
+// or unset, by cost
+bool cost_driven_collapse_wanted();
 
 } // namespace pyr
