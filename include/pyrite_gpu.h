@@ -167,9 +167,18 @@ typedef struct PyrInstr {
     PyrOperand x, y, z, w;
 } PyrInstr; /* 64 bytes */
 
+/* The size of the interpreter's in-register file, not a limit on programs. pyr_scene_create renumbers the registers of a program
+ * that declares more (pyr_program_allocate_registers); a program that still needs more after that runs on the wide interpreter
+ * build, whose file holds PYR_WIDE_*_REGISTERS, and one that needs more than that is refused with
+ * PYR_ERR_UNSUPPORTED. A program may declare at most PYR_MAX_DECLARED_REGISTERS registers of each file (both front ends keep that
+ * bound; pyr_scene_create and pyr_program_allocate_registers refuse more with PYR_ERR_UNSUPPORTED). */
 #define PYR_MAX_NUMBER_REGISTERS 16
 #define PYR_MAX_VECTOR_REGISTERS 8
 #define PYR_MAX_RGB_REGISTERS 8
+#define PYR_WIDE_NUMBER_REGISTERS 64
+#define PYR_WIDE_VECTOR_REGISTERS 32
+#define PYR_WIDE_RGB_REGISTERS 32
+#define PYR_MAX_DECLARED_REGISTERS 65536
 
 /* ProgramType (program/mod.rs:61-73): Constant short-circuits, Instructions reads one output register. */
 typedef enum PyrProgramKind { PYR_PROGRAM_CONSTANT = 0, PYR_PROGRAM_INSTRUCTIONS = 1 } PyrProgramKind;
@@ -415,6 +424,32 @@ typedef struct PyrPathInfo {
     uint32_t reserved[3];
 } PyrPathInfo;
 int pyr_scene_path_info(PyrScene* scene, const PyrRenderParams* params, PyrPathInfo* out);
+
+/* The register files of a scene's programs (what pyr_scene_create made of them; nothing is launched). Largest counts over every
+ * PYR_PROGRAM_INSTRUCTIONS program, as declared and after pyr_program_allocate_registers: */
+typedef struct PyrProgramInfo {
+    uint32_t declared_numbers, declared_vectors, declared_rgbs;
+    uint32_t allocated_numbers, allocated_vectors, allocated_rgbs;
+    uint32_t wide;     /* 1: some program needs more than the in-register file even after allocation: the scene runs the wide
+                          interpreter build (PYR_WIDE_*_REGISTERS), without a tape (PyrPathInfo::tape 0) */
+    uint32_t reserved;
+} PyrProgramInfo;
+int pyr_scene_program_info(PyrScene* scene, PyrProgramInfo* out);
+
+/* Register allocation of one program, host only (no device needed): exactly the pass pyr_scene_create applies to every
+ * PYR_PROGRAM_INSTRUCTIONS program that declares more than PYR_MAX_NUMBER_REGISTERS / PYR_MAX_VECTOR_REGISTERS /
+ * PYR_MAX_RGB_REGISTERS. `instrs` and `instrs_out` are indexed like PyrSceneDesc::instrs: the pass reads
+ * instrs[program->first_instr, + num_instrs) and writes the same range of instrs_out (which may be `instrs`); *program_out is
+ * *program with output_reg and the three counts renumbered. Only register indices change -- the same instructions in the same
+ * order, ops, deps, constants and inputs -- and the counts never grow. Linear scan, one pool per file; a value that does not
+ * depend on the wavelength but is read by an instruction that does, and such a program output, keep a register of their own for
+ * the whole program (the kernels re-run only the PYR_DEP_WAVELENGTH instructions for the companion wavelengths). A program that
+ * fits the in-register file, a constant program and one the pass cannot follow (a register written twice, or read before it is
+ * written or beyond its declared count) are copied unchanged. Deterministic. PYR_OK; PYR_ERR_INVALID_ARGUMENT for null pointers;
+ * PYR_ERR_UNSUPPORTED (nothing written) for a program that declares more than PYR_MAX_DECLARED_REGISTERS registers of a file.
+ * pyr_scene_create reads every program from the caller's instructions and gives a renumbered one a copy of its own, so programs
+ * may share instruction ranges. */
+int pyr_program_allocate_registers(const PyrInstr* instrs, const PyrProgram* program, PyrInstr* instrs_out, PyrProgram* program_out);
 
 /* ---------------------------------------------------------------- multi-GPU -----------
  * The reference is one process with shared memory; its unit of parallel work is the tile (renderer/simple.rs:36-55: every

@@ -32,6 +32,8 @@ SHAPE_SPHERE, SHAPE_TRIANGLE, SHAPE_PLANE = 0, 1, 2
 HIT_NONE = 0xFFFFFFFF
 
 MAX_NUMBER_REGISTERS, MAX_VECTOR_REGISTERS, MAX_RGB_REGISTERS = 16, 8, 8
+WIDE_NUMBER_REGISTERS, WIDE_VECTOR_REGISTERS, WIDE_RGB_REGISTERS = 64, 32, 32
+MAX_DECLARED_REGISTERS = 65536
 
 
 class PyrGrain(C.Structure):
@@ -236,6 +238,19 @@ class PyrPathInfo(C.Structure):
     ]
 
 
+class PyrProgramInfo(C.Structure):
+    _fields_ = [
+        ("declared_numbers", C.c_uint32),
+        ("declared_vectors", C.c_uint32),
+        ("declared_rgbs", C.c_uint32),
+        ("allocated_numbers", C.c_uint32),
+        ("allocated_vectors", C.c_uint32),
+        ("allocated_rgbs", C.c_uint32),
+        ("wide", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 class PyrDevelopParams(C.Structure):
     _fields_ = [
         ("step_size", C.c_float),
@@ -273,6 +288,8 @@ ENTRY_POINTS = {
     "pyr_scene_intersect_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "pyr_scene_bvh_info": (C.c_int, [C.c_void_p, C.POINTER(PyrBvhInfo)]),
     "pyr_scene_path_info": (C.c_int, [C.c_void_p, C.POINTER(PyrRenderParams), C.POINTER(PyrPathInfo)]),
+    "pyr_scene_program_info": (C.c_int, [C.c_void_p, C.POINTER(PyrProgramInfo)]),
+    "pyr_program_allocate_registers": (C.c_int, [C.POINTER(PyrInstr), C.POINTER(PyrProgram), C.POINTER(PyrInstr), C.POINTER(PyrProgram)]),
     "pyr_film_blocks_grains": (C.c_uint64, [C.POINTER(PyrFilmDesc), C.POINTER(PyrRenderParams)]),
     "pyr_film_blocks_assemble_device": (C.c_int, [C.POINTER(PyrFilmDesc), C.POINTER(PyrRenderParams), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]),
     "pyr_comm_unique_id": (C.c_int, [C.c_void_p]),

@@ -9,8 +9,8 @@ import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 OUT = os.path.join(CSRC, "libpyrite_gpu.so")
-SOURCES = ["kernels.hip", "api.cpp", "multi.cpp", "bvh.cpp"]
-HEADERS = ["bvh.h", "device_scene.h", "api_internal.h", "exact_math.h", os.path.join("..", "..", "include", "pyrite_gpu.h")]
+SOURCES = ["kernels.hip", "api.cpp", "multi.cpp", "bvh.cpp", "program_regs.cpp"]
+HEADERS = ["bvh.h", "device_scene.h", "api_internal.h", "exact_math.h", "program_regs.h", os.path.join("..", "..", "include", "pyrite_gpu.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = [
     "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-shared",
@@ -91,14 +91,16 @@ def build_host(force=False, verbose=False):
 
 
 def compile_library(out, extra_flags=(), verbose=False):
-    """The four sources -> objects in parallel -> one shared library. kernels.hip is compiled three times (-DPYR_TU=0: everything but
-    the interpreter builds of the stage scheduler; -DPYR_TU=1: only those, the heaviest kernels; -DPYR_TU=2: their PRODUCT forms) so that
-    the parts build side by side: 120 s -> ~50 s. -DPYR_PHASE_PROFILE builds keep one translation unit (their device-side counters are one variable)."""
+    """The sources -> objects in parallel -> one shared library. kernels.hip is compiled four times (-DPYR_TU=0: everything but
+    the interpreter builds of the stage scheduler; -DPYR_TU=1: only those, the heaviest kernels; -DPYR_TU=2: their PRODUCT forms;
+    -DPYR_TU=3: the wide interpreter build, for programs that need more registers than the in-register file) so that the parts build
+    side by side: 120 s -> ~50 s. -DPYR_PHASE_PROFILE builds keep one translation unit (their device-side counters are one variable)
+    and have no wide interpreter build: a scene that needs it is refused there."""
     import tempfile
 
     flags = [f for f in FLAGS if f != "-shared"] + list(extra_flags)
     split = not any("PYR_PHASE_PROFILE" in f or "PYR_DEV_ONLY" in f for f in extra_flags)
-    units = [("kernels.hip", ["-DPYR_TU=0"]), ("kernels.hip", ["-DPYR_TU=1"]), ("kernels.hip", ["-DPYR_TU=2"])] if split else [("kernels.hip", [])]
+    units = [("kernels.hip", ["-DPYR_TU=%d" % tu]) for tu in range(4)] if split else [("kernels.hip", [])]
     units += [(src, []) for src in SOURCES if src != "kernels.hip"]
     with tempfile.TemporaryDirectory(prefix="pyrite_build_") as tmp:
         jobs = []

@@ -233,6 +233,9 @@ class _Pending(Exception):
         self.child = child
 
 
+PROGRAM_REGISTER_BOUND = abi.MAX_DECLARED_REGISTERS  # registers of one file a compiled program may declare (PYR_MAX_DECLARED_REGISTERS)
+
+
 class FlatScene:
     """Arrays of include/pyrite_gpu.h's PyrSceneDesc, plus the builders that fill them."""
 
@@ -524,8 +527,10 @@ class FlatScene:
             elif kind == "c":
                 reg = rgb_register_to_vector(reg, deps)
             output_kind = abi.OUTPUT_VECTOR
-        if counts["n"] > abi.MAX_NUMBER_REGISTERS or counts["v"] > abi.MAX_VECTOR_REGISTERS or counts["c"] > abi.MAX_RGB_REGISTERS:
-            raise ProjectError("program needs more registers than the GPU VM provides")
+        # a sanity bound only (the same in pyrite_host.cpp): pyr_scene_create renumbers the registers of a program that declares more
+        # than the interpreter's in-register file and refuses one that does not fit its wide build even then
+        if max(counts.values()) > PROGRAM_REGISTER_BOUND:
+            raise ProjectError("program needs more than %d registers of one kind" % PROGRAM_REGISTER_BOUND)
         first = len(self.instrs)
         self.instrs.extend(instructions)
         self.programs.append(dict(kind=abi.PROGRAM_INSTRUCTIONS, constant=0.0, first=first, n=len(instructions), output_kind=output_kind,

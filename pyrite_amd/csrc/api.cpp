@@ -8,12 +8,14 @@
 #include <cstdlib>
 #include <cstring>
 #include <memory>
+#include <new>
 #include <string>
 #include <vector>
 
 #include "api_internal.h"
 #include "bvh.h"
 #include "device_scene.h"
+#include "program_regs.h"
 
 using namespace pyr;
 
@@ -96,8 +98,6 @@ int validate(const PyrSceneDesc* d) {
         const PyrProgram& p = d->programs[i];
         if (p.kind == PYR_PROGRAM_INSTRUCTIONS) {
             if ((uint64_t)p.first_instr + p.num_instrs > d->num_instrs) return fail(PYR_ERR_INVALID_ARGUMENT, "program instruction range out of bounds");
-            if (p.num_numbers > PYR_MAX_NUMBER_REGISTERS || p.num_vectors > PYR_MAX_VECTOR_REGISTERS || p.num_rgbs > PYR_MAX_RGB_REGISTERS)
-                return fail(PYR_ERR_UNSUPPORTED, "program needs more registers than the GPU VM provides");
         }
     }
     for (uint32_t i = 0; i < d->num_materials; ++i) {
@@ -274,6 +274,7 @@ bool split_product(std::vector<PyrInstr>& instrs, const PyrProgram& p, PyrProgra
     }
     if (written_once_more(instrs[(size_t)lambda_writer].output, (size_t)lambda_writer)) return false;
     std::vector<PyrInstr> hit_list, lambda_list;
+    std::vector<bool> on_lambda(p.num_instrs, false); // the instructions of lambda_list, by position in the program
     for (size_t k = first; k < end; ++k) {
         const PyrInstr& ins = instrs[k];
         if (on_chain[k - first]) continue;
@@ -281,24 +282,29 @@ bool split_product(std::vector<PyrInstr>& instrs, const PyrProgram& p, PyrProgra
             const bool number_op = ins.op == PYR_OP_SPECTRUM || ins.op == PYR_OP_BLACKBODY || ins.op == PYR_OP_CLAMP || ((ins.op == PYR_OP_BINARY || ins.op == PYR_OP_MIX) && ins.value_type == PYR_VT_NUMBER);
             if (!number_op || hit_deps(ins) || k > (size_t)lambda_writer) return false; // a second factor that reads the wavelength, or one that reads the hit too
             lambda_list.push_back(ins);
+            on_lambda[k - first] = true;
         } else {
             hit_list.push_back(ins);
-            if (ins.op == PYR_OP_NUMBER && k < (size_t)lambda_writer) lambda_list.push_back(ins); // a constant either side may read
+            if (ins.op == PYR_OP_NUMBER && k < (size_t)lambda_writer) lambda_list.push_back(ins), on_lambda[k - first] = true; // a constant either side may read
         }
     }
     if (hit_list.empty() || lambda_list.empty()) return false;
-    // the wavelength side must be closed: every number register it reads was written by one of its own instructions (a constant that
-    // is not a NumberValue -- 2 * 3 left unfolded -- stands on the hit side only, and the program keeps the online form)
+    // the wavelength side must be closed: the value every number register it reads holds there in the whole program was written by one
+    // of its own instructions -- the LAST writer before the read, in program order (a hit-side instruction may write a register between
+    // a constant's write and the read: the registers of an allocated program are reused). A constant that is not a NumberValue -- 2 * 3
+    // left unfolded -- stands on the hit side only, and the program keeps the online form.
     {
-        bool written[PYR_MAX_NUMBER_REGISTERS] = {};
         bool closed = true;
-        auto reads = [&](const PyrOperand& o) {
-            if (o.kind == PYR_OPERAND_REGISTER && !(o.bits < PYR_MAX_NUMBER_REGISTERS && written[o.bits])) closed = false;
-        };
-        auto reads_register = [&](uint32_t r) {
-            if (!(r < PYR_MAX_NUMBER_REGISTERS && written[r])) closed = false;
-        };
-        for (const PyrInstr& ins : lambda_list) {
+        for (size_t k = first; k < end && closed; ++k) {
+            if (!on_lambda[k - first]) continue;
+            const PyrInstr& ins = instrs[k];
+            auto reads_register = [&](uint32_t r) {
+                const long w = writer_before(r, k);
+                if (!(r < PYR_MAX_NUMBER_REGISTERS && w >= 0 && on_lambda[(size_t)w - first])) closed = false;
+            };
+            auto reads = [&](const PyrOperand& o) {
+                if (o.kind == PYR_OPERAND_REGISTER) reads_register(o.bits);
+            };
             switch (ins.op) {
             case PYR_OP_SPECTRUM: reads(ins.x); break;
             case PYR_OP_BLACKBODY: reads(ins.x), reads(ins.y); break;
@@ -307,7 +313,7 @@ bool split_product(std::vector<PyrInstr>& instrs, const PyrProgram& p, PyrProgra
             case PYR_OP_MIX: reads(ins.x), reads_register(ins.a), reads_register(ins.b); break;
             default: break; // NumberValue
             }
-            if (ins.output < PYR_MAX_NUMBER_REGISTERS) written[ins.output] = true;
+            if (ins.output >= PYR_MAX_NUMBER_REGISTERS) closed = false;
         }
         if (!closed) return false;
     }
@@ -337,6 +343,7 @@ struct PyrScene {
         spectrum_data, rgb_basis, counters, tri_tex, sphere_tex_scale, plane_frames, textures, texture_data;
     PyrCounters last_counters{};
     bool have_counters = false;
+    PyrProgramInfo program_info{}; // pyr_scene_program_info; program_info.wide: the kernels are the wide interpreter build (kernels.hip PYR_TU 3)
     uint32_t* tail_count = nullptr; // device, kFeedBytes: the work-feed cursors of the intersect kernel
     DeviceBuffer tape; // spectral tape of the stage-scheduled kernel (grown on demand, kept between renders)
     DeviceBuffer tape_overflow; // one word the kernels set when a path outgrew the tape (checked after blocking renders and by pyr_scene_counters)
@@ -400,6 +407,10 @@ void plane_frame_from_normal(const float n[3], float q[4]) {
 }
 
 int pack_and_upload(const PyrSceneDesc* d, PyrScene* s) {
+    const bool wide_vm = s->program_info.wide != 0;
+    for (uint32_t i = 0; i < d->num_programs; ++i) // (the allocated description: the kernels read every range from the uploaded array)
+        if (d->programs[i].kind == PYR_PROGRAM_INSTRUCTIONS && (uint64_t)d->programs[i].first_instr + d->programs[i].num_instrs > d->num_instrs)
+            return fail(PYR_ERR_INVALID_ARGUMENT, "program instruction range out of bounds after register allocation");
     // ---- primitives + BVH
     std::vector<PrimBounds> bounds;
     bounds.reserve((size_t)d->num_spheres + d->num_triangles);
@@ -529,7 +540,7 @@ int pack_and_upload(const PyrSceneDesc* d, PyrScene* s) {
     // programs without a tape form that factor into a hit side and a wavelength side get both as programs of their own, behind the
     // caller's (TAPE_FORM_PRODUCT); the instruction array grows by their instructions
     std::vector<PyrInstr> instrs(d->instrs, d->instrs + d->num_instrs);
-    for (uint32_t i = 0; i < d->num_programs; ++i) {
+    for (uint32_t i = 0; i < d->num_programs && !wide_vm; ++i) { // (the wide build has no tape)
         if (programs[i].kind != PYR_PROGRAM_INSTRUCTIONS || programs[i].tape_form != TAPE_FORM_NONE || programs.size() + 2 > 128) continue; // (a hit tape takes at most 128 programs)
         const size_t instrs_before = instrs.size();
         PyrProgram hit, lambda;
@@ -751,6 +762,7 @@ int pack_and_upload(const PyrSceneDesc* d, PyrScene* s) {
         if (tape_rows_needed(fast_programs, v.rgb_records != 0) > kTapeMaxValueRows) ok = false; // (counted here without LAMBDA's hit-tape condition: never fewer than the kernel finds)
         const char* off = std::getenv("PYRITE_HIT_TAPE"); // A/B and tests: PYRITE_HIT_TAPE=0 keeps the online form (read at scene creation)
         if (off && off[0] == '0') ok = false;
+        if (wide_vm) ok = false; // the wide interpreter build keeps every wavelength online (kernels.hip pick_wide_kernel)
         v.hit_tape = ok ? 1u : 0u;
         if (!ok) v.rgb_records = v.micro_records = v.product_records = 0u;
     }
@@ -892,7 +904,7 @@ int render_batches(PyrScene* scene, RenderLaunch L, bool count, hipStream_t stre
         int rc = reserve_tape(scene, L, stream);
         if (rc != PYR_OK) return rc;
     }
-    int rc = launch_render(scene->dev, L, count, stream, scene->num_cus);
+    int rc = launch_render(scene->dev, L, count, stream, scene->num_cus, scene->program_info.wide != 0);
     if (rc != PYR_OK) return fail(rc, kernels_last_error());
     return PYR_OK;
 }
@@ -943,6 +955,51 @@ RenderLaunch make_launch(const PyrCamera* camera, const PyrFilmDesc* film, const
     return L;
 }
 
+// pyr_scene_create's register allocation (program_regs.h) of every program that declares more than the in-register file. Each program
+// is read from the caller's instructions, never from a copy an earlier program's allocation rewrote -- two programs may name the same
+// or overlapping ranges -- and a program the pass renumbered gets its instructions of its own, appended to `instrs` (which starts as
+// the caller's array, so every other program keeps its range). Fails with PYR_ERR_UNSUPPORTED for a program that declares more than
+// PYR_MAX_DECLARED_REGISTERS registers of a file or still needs more than the wide interpreter build's file after allocation.
+int allocate_scene_registers(const PyrSceneDesc* desc, std::vector<PyrProgram>& programs, std::vector<PyrInstr>& instrs, PyrProgramInfo& info) {
+    try {
+        programs.assign(desc->programs, desc->programs + desc->num_programs);
+        instrs.assign(desc->instrs, desc->instrs + desc->num_instrs);
+        info = PyrProgramInfo{};
+        std::vector<PyrInstr> code;
+        for (uint32_t i = 0; i < desc->num_programs; ++i) {
+            const PyrProgram& p = desc->programs[i];
+            if (p.kind != PYR_PROGRAM_INSTRUCTIONS) continue;
+            PyrProgram& q = programs[i];
+            if (!program_fits_registers(p)) {
+                code.resize(p.num_instrs);
+                if (allocate_program_registers(desc->instrs + p.first_instr, p, code.data(), q) != PYR_OK)
+                    return fail(PYR_ERR_UNSUPPORTED, "program " + std::to_string(i) + " declares more than " + std::to_string(PYR_MAX_DECLARED_REGISTERS) +
+                                                         " registers of one kind");
+                if (std::memcmp(&q, &p, sizeof(PyrProgram)) != 0) { // renumbered: its own copy of the instructions
+                    if ((uint64_t)instrs.size() + code.size() >= 0xFFFFFFFFull) return fail(PYR_ERR_UNSUPPORTED, "too many program instructions");
+                    q.first_instr = (uint32_t)instrs.size();
+                    instrs.insert(instrs.end(), code.begin(), code.end());
+                }
+            }
+            info.declared_numbers = std::max(info.declared_numbers, p.num_numbers);
+            info.declared_vectors = std::max(info.declared_vectors, p.num_vectors);
+            info.declared_rgbs = std::max(info.declared_rgbs, p.num_rgbs);
+            info.allocated_numbers = std::max(info.allocated_numbers, q.num_numbers);
+            info.allocated_vectors = std::max(info.allocated_vectors, q.num_vectors);
+            info.allocated_rgbs = std::max(info.allocated_rgbs, q.num_rgbs);
+            if (!program_fits_wide_registers(q))
+                return fail(PYR_ERR_UNSUPPORTED, "program " + std::to_string(i) + " needs " + std::to_string(q.num_numbers) + " number, " + std::to_string(q.num_vectors) +
+                                                     " vector and " + std::to_string(q.num_rgbs) + " RGB registers after register allocation; the wide interpreter build holds " +
+                                                     std::to_string(PYR_WIDE_NUMBER_REGISTERS) + ", " + std::to_string(PYR_WIDE_VECTOR_REGISTERS) + " and " +
+                                                     std::to_string(PYR_WIDE_RGB_REGISTERS));
+            if (!program_fits_registers(q)) info.wide = 1u;
+        }
+    } catch (const std::bad_alloc&) {
+        return fail(PYR_ERR_OUT_OF_MEMORY, "out of host memory while allocating program registers");
+    }
+    return PYR_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -962,6 +1019,17 @@ int pyr_scene_create(const PyrSceneDesc* desc, int device, PyrScene** out_scene)
     *out_scene = nullptr;
     int rc = validate(desc);
     if (rc != PYR_OK) return rc;
+    // programs that declare more registers than the interpreter's in-register file get theirs renumbered (program_regs.h) before
+    // anything else looks at them: the fast shapes, the tape forms and the kernels all see the allocated programs
+    PyrSceneDesc allocated = *desc;
+    std::vector<PyrProgram> programs;
+    std::vector<PyrInstr> instrs;
+    PyrProgramInfo info{};
+    rc = allocate_scene_registers(desc, programs, instrs, info);
+    if (rc != PYR_OK) return rc;
+    allocated.programs = programs.data();
+    allocated.instrs = instrs.data();
+    allocated.num_instrs = (uint32_t)instrs.size(); // the caller's instructions and the renumbered programs' copies behind them
     int n = pyr_device_count();
     if (n <= 0) return fail(PYR_ERR_DEVICE, "no HIP device is visible; pyrite_gpu has no CPU path");
     if (device < 0 || device >= n) return fail(PYR_ERR_INVALID_ARGUMENT, "device index out of range");
@@ -971,7 +1039,8 @@ int pyr_scene_create(const PyrSceneDesc* desc, int device, PyrScene** out_scene)
     std::unique_ptr<PyrScene> s(new PyrScene());
     s->device = device;
     s->num_cus = prop.multiProcessorCount;
-    rc = pack_and_upload(desc, s.get());
+    s->program_info = info;
+    rc = pack_and_upload(&allocated, s.get());
     if (rc != PYR_OK) return rc;
     *out_scene = s.release();
     return PYR_OK;
@@ -1219,6 +1288,12 @@ int pyr_scene_path_info(PyrScene* scene, const PyrRenderParams* params, PyrPathI
     out->scene_in_lds = scene_is_lds_resident(scene->dev) ? 1u : 0u;
     out->tape = L.scheduler == 0 ? 0u : scene->dev.needs_interpreter == 0 ? 1u : uses_hit_tape(scene->dev, L) ? 2u : 0u;
     out->phase_lanes = L.scheduler != 0 ? L.sm_phase_lanes : 0u;
+    return PYR_OK;
+}
+
+int pyr_scene_program_info(PyrScene* scene, PyrProgramInfo* out) {
+    if (!scene || !out) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+    *out = scene->program_info;
     return PYR_OK;
 }
 

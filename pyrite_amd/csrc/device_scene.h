@@ -242,7 +242,8 @@ struct AssembleLaunch {
 int launch_assemble(const AssembleLaunch& launch, void* stream);
 
 // launchers (kernels.hip)
-int launch_render(const DevScene& scene, const RenderLaunch& launch, bool with_counters, void* stream, int num_cus);
+// wide_vm: the scene has a program that only the wide interpreter build (kernels.hip PYR_TU 3) holds
+int launch_render(const DevScene& scene, const RenderLaunch& launch, bool with_counters, void* stream, int num_cus, bool wide_vm = false);
 uint32_t tape_ops_bound(const DevScene& scene, const RenderLaunch& launch); // records per path the stage-scheduled kernel may append to its spectral tape
 bool uses_hit_tape(const DevScene& scene, const RenderLaunch& launch); // an interpreter scene that records a tape in this launch
 uint32_t tape_lanes_bound(int num_cus);              // lanes (tape columns) of the largest grid launch_render starts

@@ -706,8 +706,11 @@ uint32_t FlatScene::compile(const Expression& expression, bool allow_wavelength,
             reg = rgb_register_to_vector(reg, st.deps);
         output_kind = PYR_OUTPUT_VECTOR;
     }
-    if (counts[RN] > PYR_MAX_NUMBER_REGISTERS || counts[RV] > PYR_MAX_VECTOR_REGISTERS || counts[RC] > PYR_MAX_RGB_REGISTERS)
-        throw ProjectError("program needs more registers than the GPU VM provides");
+    // a sanity bound only (the same in compiler.py): pyr_scene_create renumbers the registers of a program that declares more than the
+    // interpreter's in-register file and refuses one that does not fit its wide build even then
+    constexpr uint32_t kProgramRegisterBound = PYR_MAX_DECLARED_REGISTERS;
+    if (counts[RN] > kProgramRegisterBound || counts[RV] > kProgramRegisterBound || counts[RC] > kProgramRegisterBound)
+        throw ProjectError("program needs more than " + std::to_string(kProgramRegisterBound) + " registers of one kind");
     PyrProgram p{};
     p.kind = PYR_PROGRAM_INSTRUCTIONS;
     p.first_instr = (uint32_t)S.instrs.size();

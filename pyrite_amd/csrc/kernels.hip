@@ -39,8 +39,27 @@
 #define PYR_TU_MAIN (PYR_TU == 0 || PYR_TU == -1)
 #define PYR_TU_INTERP (PYR_TU == 1 || PYR_TU == -1)
 #define PYR_TU_PRODUCT (PYR_TU == 2 || PYR_TU == -1)
+// -DPYR_TU=3: the wide interpreter build -- the online interpreter builds of render_kernel_sm (no tape) whose register files (struct
+// Vm) hold PYR_WIDE_*_REGISTERS, for scenes with a program that needs more than the in-register file even after api.cpp's register
+// allocation (program_regs.h). Everything of that unit lives in a namespace of its own, pyr::wide: the same templates with another
+// Vm under the same names would break the one-definition rule. The one-unit builds (-1) have no wide build and refuse such scenes.
+#define PYR_TU_WIDE (PYR_TU == 3)
+#if PYR_TU_WIDE
+#define PYR_VM_NUMBERS PYR_WIDE_NUMBER_REGISTERS
+#define PYR_VM_VECTORS PYR_WIDE_VECTOR_REGISTERS
+#define PYR_VM_RGBS PYR_WIDE_RGB_REGISTERS
+#else
+#define PYR_VM_NUMBERS PYR_MAX_NUMBER_REGISTERS
+#define PYR_VM_VECTORS PYR_MAX_VECTOR_REGISTERS
+#define PYR_VM_RGBS PYR_MAX_RGB_REGISTERS
+#endif
+static_assert((PYR_VM_NUMBERS & (PYR_VM_NUMBERS - 1)) == 0 && (PYR_VM_VECTORS & (PYR_VM_VECTORS - 1)) == 0 && (PYR_VM_RGBS & (PYR_VM_RGBS - 1)) == 0,
+              "the interpreter masks register indices: its files are powers of two");
 
 namespace pyr {
+#if PYR_TU_WIDE
+namespace wide {
+#endif
 
 #if PYR_TU_MAIN
 namespace {
@@ -378,11 +397,11 @@ DEV void texture_get(const DevScene& S, uint32_t id, float px, float py, float o
 // wavelength, only the instructions that depend on the wavelength (PyrInstr::deps) -- the reference's memoised re-run
 // (program/memoized.rs:22-39, execution_context.rs:311-342): a texture is sampled once per hit, not once per wavelength.
 struct Vm {
-    float num[PYR_MAX_NUMBER_REGISTERS];
-    float vec[PYR_MAX_VECTOR_REGISTERS][4];
-    float rgb[PYR_MAX_RGB_REGISTERS][4];
+    float num[PYR_VM_NUMBERS];
+    float vec[PYR_VM_VECTORS][4];
+    float rgb[PYR_VM_RGBS][4];
     DEV void step(const DevScene& S, const PyrInstr& ins, const VmInput& in);
-    DEV float number(const DevProgram& p) const { return p.output_kind == PYR_OUTPUT_NUMBER ? num[p.output_reg & (PYR_MAX_NUMBER_REGISTERS - 1)] : vec[p.output_reg & (PYR_MAX_VECTOR_REGISTERS - 1)][0]; }
+    DEV float number(const DevProgram& p) const { return p.output_kind == PYR_OUTPUT_NUMBER ? num[p.output_reg & (PYR_VM_NUMBERS - 1)] : vec[p.output_reg & (PYR_VM_VECTORS - 1)][0]; }
 };
 
 // Vm::step: one instruction of the register interpreter (program/execution_context.rs:69-283).
@@ -390,7 +409,7 @@ DEV void Vm::step(const DevScene& S, const PyrInstr& ins, const VmInput& in) {
     auto value = [&](const PyrOperand& o) -> float {
         if (o.kind == PYR_OPERAND_CONSTANT) return __uint_as_float(o.bits);
         if (o.kind == PYR_OPERAND_INPUT) return in.wavelength;
-        return num[o.bits & (PYR_MAX_NUMBER_REGISTERS - 1)];
+        return num[o.bits & (PYR_VM_NUMBERS - 1)];
     };
     auto vinput = [&](uint32_t which, float out[4]) {
         f3 v = which == PYR_INPUT_NORMAL ? in.normal : (which == PYR_INPUT_INCIDENT ? in.incident : mk(in.tx, in.ty, 0.0f));
@@ -409,26 +428,26 @@ DEV void Vm::step(const DevScene& S, const PyrInstr& ins, const VmInput& in) {
     };
     const uint32_t out = ins.output;
     switch (ins.op) {
-    case PYR_OP_NUMBER: num[out & (PYR_MAX_NUMBER_REGISTERS - 1)] = __uint_as_float(ins.x.bits); break;
+    case PYR_OP_NUMBER: num[out & (PYR_VM_NUMBERS - 1)] = __uint_as_float(ins.x.bits); break;
     case PYR_OP_VECTOR: {
         float x = value(ins.x), y = value(ins.y), z = value(ins.z), w = value(ins.w);
-        float* v = vec[out & (PYR_MAX_VECTOR_REGISTERS - 1)];
+        float* v = vec[out & (PYR_VM_VECTORS - 1)];
         v[0] = x, v[1] = y, v[2] = z, v[3] = w;
         break;
     }
     case PYR_OP_RGB: {
         float r = value(ins.x), g = value(ins.y), b = value(ins.z);
-        float* v = rgb[out & (PYR_MAX_VECTOR_REGISTERS - 1)];
+        float* v = rgb[out & (PYR_VM_RGBS - 1)];
         v[0] = r, v[1] = g, v[2] = b, v[3] = 1.0f;
         break;
     }
-    case PYR_OP_SPECTRUM: num[out & (PYR_MAX_NUMBER_REGISTERS - 1)] = spectrum_get(S, ins.a, value(ins.x)); break;
+    case PYR_OP_SPECTRUM: num[out & (PYR_VM_NUMBERS - 1)] = spectrum_get(S, ins.a, value(ins.x)); break;
     case PYR_OP_COLOR_TEXTURE: { // execution_context.rs:114-126
         float pos[4];
         vinput(ins.b, pos);
         float c[4];
         texture_get(S, ins.a, pos[0], pos[1], c);
-        float* v = rgb[out & (PYR_MAX_VECTOR_REGISTERS - 1)];
+        float* v = rgb[out & (PYR_VM_RGBS - 1)];
         for (int j = 0; j < 4; ++j) v[j] = c[j];
         break;
     }
@@ -437,12 +456,12 @@ DEV void Vm::step(const DevScene& S, const PyrInstr& ins, const VmInput& in) {
         vinput(ins.b, pos);
         float c[4];
         texture_get(S, ins.a, pos[0], pos[1], c);
-        num[out & (PYR_MAX_NUMBER_REGISTERS - 1)] = c[0];
+        num[out & (PYR_VM_NUMBERS - 1)] = c[0];
         break;
     }
     case PYR_OP_RGB_SPECTRUM: {
         float wl = value(ins.x);
-        const float* c = rgb[ins.a & (PYR_MAX_VECTOR_REGISTERS - 1)];
+        const float* c = rgb[ins.a & (PYR_VM_RGBS - 1)];
         float resp[3] = {0, 0, 0};
         uint32_t count = S.rgb_count;
         if (count > 0) {
@@ -460,7 +479,7 @@ DEV void Vm::step(const DevScene& S, const PyrInstr& ins, const VmInput& in) {
                 for (int j = 0; j < 3; ++j) resp[j] = d[3 * i0 + j] * (1.0f - mix) + d[3 * (i0 + 1) + j] * mix;
             }
         }
-        num[out & (PYR_MAX_NUMBER_REGISTERS - 1)] = c[0] * resp[0] + c[1] * resp[1] + c[2] * resp[2];
+        num[out & (PYR_VM_NUMBERS - 1)] = c[0] * resp[0] + c[1] * resp[1] + c[2] * resp[2];
         break;
     }
     case PYR_OP_FRESNEL: {
@@ -468,29 +487,29 @@ DEV void Vm::step(const DevScene& S, const PyrInstr& ins, const VmInput& in) {
         float nn[4], ii[4];
         vinput(ins.a, nn);
         vinput(ins.b, ii);
-        num[out & (PYR_MAX_NUMBER_REGISTERS - 1)] = fresnel(ior, env, mk(nn[0], nn[1], nn[2]), mk(ii[0], ii[1], ii[2]));
+        num[out & (PYR_VM_NUMBERS - 1)] = fresnel(ior, env, mk(nn[0], nn[1], nn[2]), mk(ii[0], ii[1], ii[2]));
         break;
     }
     case PYR_OP_BLACKBODY: {
         float wl = value(ins.x), temp = value(ins.y);
-        num[out & (PYR_MAX_NUMBER_REGISTERS - 1)] = blackbody(wl, temp);
+        num[out & (PYR_VM_NUMBERS - 1)] = blackbody(wl, temp);
         break;
     }
     case PYR_OP_RGB_TO_VECTOR: {
-        const float* c = rgb[ins.a & (PYR_MAX_VECTOR_REGISTERS - 1)];
-        float* v = vec[out & (PYR_MAX_VECTOR_REGISTERS - 1)];
+        const float* c = rgb[ins.a & (PYR_VM_RGBS - 1)];
+        float* v = vec[out & (PYR_VM_VECTORS - 1)];
         for (int j = 0; j < 4; ++j) v[j] = (c[j] * 2.0f) - 1.0f;
         break;
     }
     case PYR_OP_MIX: {
         float amount = fmaxf(fminf(value(ins.x), 1.0f), 0.0f);
         if (ins.value_type == PYR_VT_NUMBER) {
-            float l = num[ins.a & (PYR_MAX_NUMBER_REGISTERS - 1)], r = num[ins.b & (PYR_MAX_NUMBER_REGISTERS - 1)];
-            num[out & (PYR_MAX_NUMBER_REGISTERS - 1)] = l * (1.0f - amount) + r * amount;
+            float l = num[ins.a & (PYR_VM_NUMBERS - 1)], r = num[ins.b & (PYR_VM_NUMBERS - 1)];
+            num[out & (PYR_VM_NUMBERS - 1)] = l * (1.0f - amount) + r * amount;
         } else {
-            float* l = ins.value_type == PYR_VT_VECTOR ? vec[ins.a & (PYR_MAX_VECTOR_REGISTERS - 1)] : rgb[ins.a & (PYR_MAX_VECTOR_REGISTERS - 1)];
-            float* r = ins.value_type == PYR_VT_VECTOR ? vec[ins.b & (PYR_MAX_VECTOR_REGISTERS - 1)] : rgb[ins.b & (PYR_MAX_VECTOR_REGISTERS - 1)];
-            float* o = ins.value_type == PYR_VT_VECTOR ? vec[out & (PYR_MAX_VECTOR_REGISTERS - 1)] : rgb[out & (PYR_MAX_VECTOR_REGISTERS - 1)];
+            float* l = ins.value_type == PYR_VT_VECTOR ? vec[ins.a & (PYR_VM_VECTORS - 1)] : rgb[ins.a & (PYR_VM_RGBS - 1)];
+            float* r = ins.value_type == PYR_VT_VECTOR ? vec[ins.b & (PYR_VM_VECTORS - 1)] : rgb[ins.b & (PYR_VM_RGBS - 1)];
+            float* o = ins.value_type == PYR_VT_VECTOR ? vec[out & (PYR_VM_VECTORS - 1)] : rgb[out & (PYR_VM_RGBS - 1)];
             float t[4];
             for (int j = 0; j < 4; ++j) t[j] = l[j] + (r[j] - l[j]) * amount;
             for (int j = 0; j < 4; ++j) o[j] = t[j];
@@ -499,11 +518,11 @@ DEV void Vm::step(const DevScene& S, const PyrInstr& ins, const VmInput& in) {
     }
     case PYR_OP_BINARY: {
         if (ins.value_type == PYR_VT_NUMBER) {
-            num[out & (PYR_MAX_NUMBER_REGISTERS - 1)] = binop(ins.operator_, num[ins.a & (PYR_MAX_NUMBER_REGISTERS - 1)], num[ins.b & (PYR_MAX_NUMBER_REGISTERS - 1)]);
+            num[out & (PYR_VM_NUMBERS - 1)] = binop(ins.operator_, num[ins.a & (PYR_VM_NUMBERS - 1)], num[ins.b & (PYR_VM_NUMBERS - 1)]);
         } else {
-            float* l = ins.value_type == PYR_VT_VECTOR ? vec[ins.a & (PYR_MAX_VECTOR_REGISTERS - 1)] : rgb[ins.a & (PYR_MAX_VECTOR_REGISTERS - 1)];
-            float* r = ins.value_type == PYR_VT_VECTOR ? vec[ins.b & (PYR_MAX_VECTOR_REGISTERS - 1)] : rgb[ins.b & (PYR_MAX_VECTOR_REGISTERS - 1)];
-            float* o = ins.value_type == PYR_VT_VECTOR ? vec[out & (PYR_MAX_VECTOR_REGISTERS - 1)] : rgb[out & (PYR_MAX_VECTOR_REGISTERS - 1)];
+            float* l = ins.value_type == PYR_VT_VECTOR ? vec[ins.a & (PYR_VM_VECTORS - 1)] : rgb[ins.a & (PYR_VM_RGBS - 1)];
+            float* r = ins.value_type == PYR_VT_VECTOR ? vec[ins.b & (PYR_VM_VECTORS - 1)] : rgb[ins.b & (PYR_VM_RGBS - 1)];
+            float* o = ins.value_type == PYR_VT_VECTOR ? vec[out & (PYR_VM_VECTORS - 1)] : rgb[out & (PYR_VM_RGBS - 1)];
             float t[4];
             for (int j = 0; j < 4; ++j) t[j] = binop(ins.operator_, l[j], r[j]);
             for (int j = 0; j < 4; ++j) o[j] = t[j];
@@ -512,7 +531,7 @@ DEV void Vm::step(const DevScene& S, const PyrInstr& ins, const VmInput& in) {
     }
     case PYR_OP_CLAMP: {
         float v = value(ins.x), mn = value(ins.y), mx = value(ins.z);
-        num[out & (PYR_MAX_NUMBER_REGISTERS - 1)] = fmaxf(fminf(v, mx), mn);
+        num[out & (PYR_VM_NUMBERS - 1)] = fmaxf(fminf(v, mx), mn);
         break;
     }
     default: break;
@@ -524,13 +543,13 @@ __device__ __noinline__ float run_interpreter(const DevScene& S, const DevProgra
     Vm vm;
     for (uint32_t k = 0; k < p.num_instrs; ++k) vm.step(S, S.instrs[p.first_instr + k], in);
     if (p.output_kind == PYR_OUTPUT_NUMBER) {
-        const float n = vm.num[p.output_reg & (PYR_MAX_NUMBER_REGISTERS - 1)];
+        const float n = vm.num[p.output_reg & (PYR_VM_NUMBERS - 1)];
         if (vector_out) vector_out[0] = vector_out[1] = vector_out[2] = vector_out[3] = n;
         return n;
     }
     if (vector_out)
-        for (int j = 0; j < 4; ++j) vector_out[j] = vm.vec[p.output_reg & (PYR_MAX_VECTOR_REGISTERS - 1)][j];
-    return vm.vec[p.output_reg & (PYR_MAX_VECTOR_REGISTERS - 1)][0];
+        for (int j = 0; j < 4; ++j) vector_out[j] = vm.vec[p.output_reg & (PYR_VM_VECTORS - 1)][j];
+    return vm.vec[p.output_reg & (PYR_VM_VECTORS - 1)][0];
 }
 
 // ExecutionContext::run (execution_context.rs:29-56) with the three shapes every Cornell-family program has short-cut.
@@ -1065,9 +1084,9 @@ DEV void surface_textured(const DevScene& S, const Hit& hit, f3 o, f3 d, f3& pos
             Vm vm;
             for (uint32_t k = 0; k < prog.num_instrs; ++k) vm.step(S, S.instrs[prog.first_instr + k], in);
             if (prog.output_kind == PYR_OUTPUT_NUMBER)
-                v[0] = v[1] = v[2] = v[3] = vm.num[prog.output_reg & (PYR_MAX_NUMBER_REGISTERS - 1)];
+                v[0] = v[1] = v[2] = v[3] = vm.num[prog.output_reg & (PYR_VM_NUMBERS - 1)];
             else
-                for (int j = 0; j < 4; ++j) v[j] = vm.vec[prog.output_reg & (PYR_MAX_VECTOR_REGISTERS - 1)][j];
+                for (int j = 0; j < 4; ++j) v[j] = vm.vec[prog.output_reg & (PYR_VM_VECTORS - 1)][j];
         }
         normal = normalize(quat_rotate(frame, mk(v[0], v[1], v[2])));
     }
@@ -2469,7 +2488,7 @@ struct Walker {
                         tape_push_raw(L, hero | TAPE_RGB_TIMES | (kTapeOneSlot << TAPE_EAGER_SLOT_SHIFT), vm.num[(packed >> (20u + 4u * k)) & 15u]);
                     tape_push_raw(L, flags | TAPE_RGB_APPLY | (kTapeOneSlot << TAPE_EAGER_SLOT_SHIFT), factor);
                 } else { // HIT_RGB: c0 * basis_r + c1 * basis_g + c2 * basis_b (execution_context.rs:140-152), then times the factor
-                    const float* c = vm.rgb[colour.tape_rgb_reg & (PYR_MAX_VECTOR_REGISTERS - 1)];
+                    const float* c = vm.rgb[colour.tape_rgb_reg & (PYR_VM_RGBS - 1)];
                     const uint32_t hero = c_companions ? 0u : TAPE_HERO_ONLY;
                     tape_push_raw(L, hero | TAPE_RGB_FIRST | ((rgb_slot + 0u) << TAPE_EAGER_SLOT_SHIFT), c[0]);
                     tape_push_raw(L, hero | TAPE_RGB_NEXT | ((rgb_slot + 1u) << TAPE_EAGER_SLOT_SHIFT), c[1]);
@@ -3605,14 +3624,20 @@ RenderKernel pick_interp_kernel(bool with_counters, bool lds_scene, bool lds_tab
 RenderKernel pick_interp_kernel(bool with_counters, bool lds_scene, bool lds_tables, bool hit_tape, bool product);
 #endif
 
+#if !PYR_TU_WIDE
+// The wide interpreter build (defined at the end of this file in the -DPYR_TU=3 unit; nullptr in the one-unit builds).
+RenderKernel pick_wide_kernel(bool with_counters, bool lds_scene, bool lds_tables);
+#endif
+
 #if PYR_TU_MAIN
-static RenderKernel pick_kernel(bool sm, bool with_counters, bool interp, bool lds_scene, bool lds_tables, bool hit_tape, bool product) {
+static RenderKernel pick_kernel(bool sm, bool with_counters, bool interp, bool lds_scene, bool lds_tables, bool hit_tape, bool product, bool wide_vm) {
 #ifdef PYR_DEV_ONLY_SM // developer builds for reading the ISA (tools/asm_sm.sh): only the kernel the BASELINE meshes run is instantiated
     return render_kernel_sm<false, false, false, true>;
 #endif
 #ifdef PYR_DEV_ONLY_SM_INTERP // ... or only the interpreter build the reference's textures example runs
     return render_kernel_sm<false, true, true, false, true>;
 #endif
+    if (interp && wide_vm) return pick_wide_kernel(with_counters, lds_scene, lds_tables);
     if (interp) return pick_interp_kernel(with_counters, lds_scene, lds_tables, hit_tape, product);
     auto pick = [&](auto counters) -> RenderKernel {
         constexpr bool C = decltype(counters)::value;
@@ -3625,10 +3650,14 @@ static RenderKernel pick_kernel(bool sm, bool with_counters, bool interp, bool l
 
 bool scene_is_lds_resident(const DevScene& scene) { return scene_fits_lds(scene); }
 
-int launch_render(const DevScene& scene, const RenderLaunch& launch_in, bool with_counters, void* stream, int num_cus) {
+int launch_render(const DevScene& scene, const RenderLaunch& launch_in, bool with_counters, void* stream, int num_cus, bool wide_vm) {
     if (scene.stack_depth > kMaxStackDepth) {
         g_kernel_error = "BVH deeper than kMaxStackDepth";
         return PYR_ERR_UNSUPPORTED;
+    }
+    if (wide_vm && (launch_in.scheduler != 1 || scene.needs_interpreter == 0 || uses_tape(scene, launch_in))) {
+        g_kernel_error = "the wide interpreter build runs the stage scheduler's online form only";
+        return PYR_ERR_INVALID_ARGUMENT;
     }
     RenderLaunch launch = launch_in;
     launch.stack_lds = 0;
@@ -3648,7 +3677,11 @@ int launch_render(const DevScene& scene, const RenderLaunch& launch_in, bool wit
     const uint32_t chunks = launch.chunk_end - launch.chunk_begin;
     if (chunks == 0) return PYR_OK;
     RenderKernel kernel = pick_kernel(launch.scheduler == 1, with_counters, scene.needs_interpreter != 0, scene_fits_lds(scene), scene.lds_table_floats != 0,
-                                      launch.scheduler == 1 && uses_hit_tape(scene, launch), scene.product_records != 0);
+                                      launch.scheduler == 1 && uses_hit_tape(scene, launch), scene.product_records != 0, wide_vm);
+    if (kernel == nullptr) {
+        g_kernel_error = "a program of this scene needs the wide interpreter build, which this one-unit build of the kernels does not hold";
+        return PYR_ERR_UNSUPPORTED;
+    }
     hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     if (err != hipSuccess) {
         g_kernel_error = std::string("hipFuncSetAttribute: ") + hipGetErrorString(err);
@@ -3717,6 +3750,23 @@ int launch_intersect(const DevScene& scene, const IntersectLaunch& launch, bool 
 }
 
 #endif // PYR_TU_MAIN
+
+#if PYR_TU_WIDE
+} // namespace wide
+
+// The wide interpreter build: the three layouts of the online form, with and without counters. Waves per SIMD as every interpreter
+// build (sm_waves); the register files live in scratch.
+wide::RenderKernel pick_wide_kernel(bool with_counters, bool lds_scene, bool lds_tables) {
+    auto pick = [&](auto counters) -> wide::RenderKernel {
+        constexpr bool C = decltype(counters)::value;
+        if (lds_scene) return wide::render_kernel_sm<C, true, true, false>;
+        return lds_tables ? wide::render_kernel_sm<C, true, false, true> : wide::render_kernel_sm<C, true, false, false>;
+    };
+    return with_counters ? pick(std::true_type{}) : pick(std::false_type{});
+}
+#elif PYR_TU == -1
+RenderKernel pick_wide_kernel(bool, bool, bool) { return nullptr; }
+#endif
 
 } // namespace pyr
 

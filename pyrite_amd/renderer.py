@@ -119,6 +119,13 @@ class Renderer:
         check(lib().pyr_scene_path_info(world.scene(device), C.byref(params), C.byref(info)))
         return {name: int(getattr(info, name)) for name, _ in info._fields_ if name != "reserved"}
 
+    def program_info(self, world: World, device=0):
+        """The register files of `world`'s programs (pyr_scene_program_info): largest declared and allocated counts, and whether the
+        scene runs the wide interpreter build. A dict of PyrProgramInfo's fields."""
+        info = abi.PyrProgramInfo()
+        check(lib().pyr_scene_program_info(world.scene(device), C.byref(info)))
+        return {name: int(getattr(info, name)) for name, _ in info._fields_ if name != "reserved"}
+
     def render(self, film: Film, camera: Camera, world: World, on_status=None, device=0, counters=False, tile_range=None, film_rows=None,
                window=None, share=None):
         """Blocking render into a host Film (adds to it). Returns the PyrCounters dict when counters=True.

@@ -393,3 +393,65 @@ def textures_reference_example(texture_dir, width=1024, height=512, pixel_sample
         "camera": camera.perspective(fov=53, transform=transform.look_at(**{"from": vector(0, 2, 12), "to": vector(0, 2, 0)})),
         "world": {"objects": objects},
     }
+
+
+# ---------------------------------------------------------------- programs larger than the interpreter's register file
+def textured_spectra(n, seed=3):
+    """A colour: n colour textures, each times a spectrum of its own, summed and scaled. Every texture value is read by a
+    wavelength-dependent product, so each keeps an RGB register through the memoised re-run: n + 3 RGBs after allocation."""
+    from .project import texture
+
+    tex = _generated_textures(seed=seed, size=8)
+    images = [tex["checker"], tex["rgba"], tex["normal_map"]]
+    rng = np.random.default_rng(seed)
+    colour = None
+    for k in range(n):
+        s = spectrum(format="array", min=400.0, max=700.0, points=[float(x) for x in rng.uniform(0.1, 0.9, 5)])
+        term = (texture(images[k % 3], "linear") if k % 2 else texture(images[k % 3])) * s
+        colour = term if colour is None else colour + term
+    return colour * (1.0 / n)
+
+
+def layered_normal_map(seed=3, layers=10):
+    """A normal map whose vector values are all live at once (a right-nested sum: layers + 2 vectors after allocation)."""
+    from .project import texture
+
+    t = texture(_generated_textures(seed=seed, size=8)["normal_map"], "linear")
+    terms = [t * vector(1, 0.9 + 0.02 * k, 1) for k in range(layers)]
+    e = terms[-1]
+    for x in reversed(terms[:-1]):
+        e = x + e
+    return e * vector(0.1, 0.1, 0.1)
+
+
+def wide_program_project(mesh, textures=9, width=40, height=28, pixel_samples=3, spectrum_samples=5, layered=True):
+    """A plane under textured_spectra(textures) and, with `layered`, layered_normal_map(); spheres (a scene in LDS) or, with `mesh`, a
+    torus knot that does not fit LDS under a fresnel mix of another textured_spectra. Nine textures and the layered map need the wide
+    interpreter build (12 RGBs, 12 vectors); five textures and a plain map fit the in-register file after allocation."""
+    from .project import fresnel, light, light_source, mix, rgb, texture
+
+    tex = _generated_textures(seed=3, size=8)
+    normal_map = layered_normal_map() if layered else texture(tex["normal_map"], "linear") * vector(1, -1, 1)
+    objects = [shape.plane(origin=vector(0, 0, 0), normal=vector(0, 0, 1), texture_scale=vector(2, 2),
+                           material={"surface": material.diffuse(color=textured_spectra(textures)), "normal_map": normal_map})]
+    if mesh:
+        tri, nrm = torus_knot_mesh(segments=60, sides=14, noise_seed=5, fit_min=(-2.5, -2.0, 0.2), fit_max=(2.5, 2.0, 3.2))
+        n = len(tri)
+        uv = (tri.reshape(-1, 3)[:, :2] * f32(0.7) + tri.reshape(-1, 3)[:, 2:3] * f32(0.3)).astype(f32)
+        corner = np.arange(3 * n).reshape(n, 3)
+        knot = {"position": tri.reshape(-1, 3), "texture": uv, "normal": nrm.reshape(-1, 3),
+                "objects": [{"name": "knot", "polys": [[(int(a), int(a), int(a)), (int(b), int(b), int(b)), (int(c), int(c), int(c))] for a, b, c in corner]}]}
+        surface = mix(material.diffuse(color=textured_spectra(textures, seed=4)), material.mirror(color=0.8), fresnel(1.5))
+        objects.append(shape.mesh(file=knot, materials={"knot": {"surface": surface}}))
+    else:
+        objects.append(shape.sphere(position=vector(-1, 0, 1), radius=1.0, material={"surface": material.diffuse(color=textured_spectra(textures, seed=4))},
+                                    texture_scale=vector(0.5, 0.5)))
+        objects.append(shape.sphere(position=vector(1.2, 0.5, 0.6), radius=0.6, material={"surface": material.mirror(color=rgb(0.9, 0.8, 0.7))}))
+    objects.append(light.point(position=vector(1, -2, 4), color=light_source.a * 15))
+    objects.append(shape.sphere(position=vector(-2, 1, 3.5), radius=0.4, material={"surface": material.emissive(color=light_source.d65 * 6)}))
+    return {
+        "image": {"width": width, "height": height},
+        "renderer": renderer.simple(pixel_samples=pixel_samples, bounces=5, light_samples=2, spectrum_samples=spectrum_samples, tile_size=16),
+        "camera": camera.perspective(fov=55, transform=transform.look_at(**{"from": vector(0.3, -7, 2.5), "to": vector(0, 0, 1), "up": vector(z=1)})),
+        "world": {"sky": light_source.d65 * 0.1, "objects": objects},
+    }
