@@ -9,8 +9,11 @@ import sys
 
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 OUT = os.path.join(CSRC, "libpyrite_gpu.so")
-SOURCES = ["kernels.hip", "api.cpp", "multi.cpp", "bvh.cpp", "program_regs.cpp"]
-HEADERS = ["bvh.h", "device_scene.h", "api_internal.h", "exact_math.h", "program_regs.h", os.path.join("..", "..", "include", "pyrite_gpu.h")]
+KERNELS = os.path.join(CSRC, "kernels")  # the units that instantiate the kernels of kernels.hip
+KERNEL_UNITS = ["main.hip", "interp.hip", "product.hip", "wide.hip"]
+PROFILE_UNIT = "profile.hip"  # -DPYR_PHASE_PROFILE builds: main, interp and product in one unit, no wide build
+SOURCES = ["api.cpp", "multi.cpp", "bvh.cpp", "program_regs.cpp"]
+HEADERS = ["kernels.hip", "bvh.h", "device_scene.h", "api_internal.h", "exact_math.h", "program_regs.h", os.path.join("..", "..", "include", "pyrite_gpu.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = [
     "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-shared",
@@ -37,7 +40,8 @@ def stale():
     if not os.path.exists(OUT):
         return True
     t = os.path.getmtime(OUT)
-    return os.path.getmtime(os.path.abspath(__file__)) > t or any(os.path.getmtime(os.path.join(CSRC, f)) > t for f in SOURCES + HEADERS)
+    files = [os.path.join(CSRC, f) for f in SOURCES + HEADERS] + [os.path.join(KERNELS, f) for f in os.listdir(KERNELS)]
+    return os.path.getmtime(os.path.abspath(__file__)) > t or any(os.path.getmtime(f) > t for f in files)
 
 
 IMAGES_OUT = os.path.join(CSRC, "libpyrite_images.so")
@@ -91,22 +95,21 @@ def build_host(force=False, verbose=False):
 
 
 def compile_library(out, extra_flags=(), verbose=False):
-    """The sources -> objects in parallel -> one shared library. kernels.hip is compiled four times (-DPYR_TU=0: everything but
-    the interpreter builds of the stage scheduler; -DPYR_TU=1: only those, the heaviest kernels; -DPYR_TU=2: their PRODUCT forms;
-    -DPYR_TU=3: the wide interpreter build, for programs that need more registers than the in-register file) so that the parts build
+    """The sources -> objects in parallel -> one shared library. The kernels of kernels.hip are instantiated by four units (kernels/main.hip: everything but
+    the interpreter builds of the stage scheduler; interp.hip: only those, the heaviest kernels; product.hip: their PRODUCT forms;
+    wide.hip: the wide interpreter build, for programs that need more registers than the in-register file) so that the parts build
     side by side: 120 s -> ~50 s. -DPYR_PHASE_PROFILE builds keep one translation unit (their device-side counters are one variable)
     and have no wide interpreter build: a scene that needs it is refused there."""
     import tempfile
 
     flags = [f for f in FLAGS if f != "-shared"] + list(extra_flags)
-    split = not any("PYR_PHASE_PROFILE" in f or "PYR_DEV_ONLY" in f for f in extra_flags)
-    units = [("kernels.hip", ["-DPYR_TU=%d" % tu]) for tu in range(4)] if split else [("kernels.hip", [])]
-    units += [(src, []) for src in SOURCES if src != "kernels.hip"]
+    kernel_units = [PROFILE_UNIT] if any("PYR_PHASE_PROFILE" in f for f in extra_flags) else KERNEL_UNITS
+    units = [os.path.join("kernels", unit) for unit in kernel_units] + SOURCES
     with tempfile.TemporaryDirectory(prefix="pyrite_build_") as tmp:
         jobs = []
-        for k, (src, unit_flags) in enumerate(units):
-            obj = os.path.join(tmp, "%d_%s.o" % (k, os.path.splitext(src)[0]))
-            cmd = [HIPCC] + flags + unit_flags + ["-c", src, "-o", obj]
+        for src in units:
+            obj = os.path.join(tmp, os.path.splitext(os.path.basename(src))[0] + ".o")
+            cmd = [HIPCC] + flags + ["-c", src, "-o", obj]
             if verbose:
                 print(" ".join(cmd))
             jobs.append((subprocess.Popen(cmd, cwd=CSRC), cmd, obj))

@@ -343,7 +343,7 @@ struct PyrScene {
         spectrum_data, rgb_basis, counters, tri_tex, sphere_tex_scale, plane_frames, textures, texture_data;
     PyrCounters last_counters{};
     bool have_counters = false;
-    PyrProgramInfo program_info{}; // pyr_scene_program_info; program_info.wide: the kernels are the wide interpreter build (kernels.hip PYR_TU 3)
+    PyrProgramInfo program_info{}; // pyr_scene_program_info; program_info.wide: the kernels are the wide interpreter build (kernels/wide.hip)
     uint32_t* tail_count = nullptr; // device, kFeedBytes: the work-feed cursors of the intersect kernel
     DeviceBuffer tape; // spectral tape of the stage-scheduled kernel (grown on demand, kept between renders)
     DeviceBuffer tape_overflow; // one word the kernels set when a path outgrew the tape (checked after blocking renders and by pyr_scene_counters)
@@ -762,7 +762,7 @@ int pack_and_upload(const PyrSceneDesc* d, PyrScene* s) {
         if (tape_rows_needed(fast_programs, v.rgb_records != 0) > kTapeMaxValueRows) ok = false; // (counted here without LAMBDA's hit-tape condition: never fewer than the kernel finds)
         const char* off = std::getenv("PYRITE_HIT_TAPE"); // A/B and tests: PYRITE_HIT_TAPE=0 keeps the online form (read at scene creation)
         if (off && off[0] == '0') ok = false;
-        if (wide_vm) ok = false; // the wide interpreter build keeps every wavelength online (kernels.hip pick_wide_kernel)
+        if (wide_vm) ok = false; // the wide interpreter build keeps every wavelength online (kernels/wide.hip pick_wide_kernel)
         v.hit_tape = ok ? 1u : 0u;
         if (!ok) v.rgb_records = v.micro_records = v.product_records = 0u;
     }

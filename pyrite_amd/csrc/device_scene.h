@@ -241,8 +241,8 @@ struct AssembleLaunch {
 };
 int launch_assemble(const AssembleLaunch& launch, void* stream);
 
-// launchers (kernels.hip)
-// wide_vm: the scene has a program that only the wide interpreter build (kernels.hip PYR_TU 3) holds
+// launchers (kernels/main.hip)
+// wide_vm: the scene has a program that only the wide interpreter build (kernels/wide.hip) holds
 int launch_render(const DevScene& scene, const RenderLaunch& launch, bool with_counters, void* stream, int num_cus, bool wide_vm = false);
 uint32_t tape_ops_bound(const DevScene& scene, const RenderLaunch& launch); // records per path the stage-scheduled kernel may append to its spectral tape
 bool uses_hit_tape(const DevScene& scene, const RenderLaunch& launch); // an interpreter scene that records a tape in this launch
@@ -250,5 +250,11 @@ uint32_t tape_lanes_bound(int num_cus);              // lanes (tape columns) of 
 int launch_intersect(const DevScene& scene, const IntersectLaunch& launch, bool with_counters, void* stream);
 const char* kernels_last_error();
 bool scene_is_lds_resident(const DevScene& scene);
+// Which unit under kernels/ holds which build of render_kernel_sm: main.hip's pick_kernel asks these, each defined by the unit it is
+// named after (pick_wide_kernel: nullptr in the one-unit build, kernels/profile.hip).
+using RenderKernel = void (*)(DevScene, RenderLaunch);
+RenderKernel pick_interp_kernel(bool with_counters, bool lds_scene, bool lds_tables, bool hit_tape, bool product);
+RenderKernel pick_product_kernel(bool with_counters, bool lds_scene, bool lds_tables);
+RenderKernel pick_wide_kernel(bool with_counters, bool lds_scene, bool lds_tables);
 
 } // namespace pyr

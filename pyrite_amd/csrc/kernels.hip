@@ -9,14 +9,14 @@
 //                      the 64 paths advance bounce by bounce (scenes that fit in LDS: C1, C2)
 //   render_kernel_sm   every lane runs its path as a state machine (Walker) and refills itself; the wave votes on which
 //                      phase code runs next; traversal is resumable (big scenes: C3-C5, textured scenes)
-//   wf_logic_kernel +  the same state machine split at the ray, path state in a pool in HBM (optional)
-//   wf_trav_kernel
 //   intersect_kernel   World::intersect for ray batches: persistent waves with a segmented work feed
 //   develop_kernel     film -> 8-bit sRGB
 // Per lane: path state in VGPRs, the S - 1 spectral companions (wavelength / brightness / reflectance) and the traversal
 // stack in LDS laid out [entry][lane] (bank-conflict free), BVH nodes fetched as 4 x dwordx4 (64 B, both children's boxes,
 // tested with packed fp32), leaf primitives as 3 x dwordx4, one primitive per step. Film exposure is two no-return
 // global_atomic_add_f32 per exposure.
+#ifndef PYRITE_KERNELS_HIP
+#define PYRITE_KERNELS_HIP
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -28,23 +28,16 @@
 #include "device_scene.h"
 #include "exact_math.h"
 
-// This file is compiled three times and in parallel by pyrite_amd/build.py: -DPYR_TU=0 holds every kernel and launcher but the
-// interpreter builds of render_kernel_sm, -DPYR_TU=1 holds only those (the heaviest kernels to compile: the interpreter in line)
-// behind pick_interp_kernel(), -DPYR_TU=2 their PRODUCT forms behind pick_product_kernel(). Without the macro (-1: tools that compile
-// kernels.hip by themselves, and the -DPYR_PHASE_PROFILE builds, whose device-side counters must live in one translation unit)
-// everything is in one piece.
-#ifndef PYR_TU
-#define PYR_TU -1
-#endif
-#define PYR_TU_MAIN (PYR_TU == 0 || PYR_TU == -1)
-#define PYR_TU_INTERP (PYR_TU == 1 || PYR_TU == -1)
-#define PYR_TU_PRODUCT (PYR_TU == 2 || PYR_TU == -1)
-// -DPYR_TU=3: the wide interpreter build -- the online interpreter builds of render_kernel_sm (no tape) whose register files (struct
-// Vm) hold PYR_WIDE_*_REGISTERS, for scenes with a program that needs more than the in-register file even after api.cpp's register
-// allocation (program_regs.h). Everything of that unit lives in a namespace of its own, pyr::wide: the same templates with another
-// Vm under the same names would break the one-definition rule. The one-unit builds (-1) have no wide build and refuse such scenes.
-#define PYR_TU_WIDE (PYR_TU == 3)
-#if PYR_TU_WIDE
+// This file holds every device function and kernel template and is not compiled by itself: the units under kernels/ include it and
+// instantiate their kernels from it (main.hip: everything but the interpreter builds of render_kernel_sm, and every launcher;
+// interp.hip: those builds, the heaviest kernels to compile, behind pick_interp_kernel(); product.hip: their PRODUCT forms behind
+// pick_product_kernel(); wide.hip: the wide interpreter build; profile.hip: the first three in one piece for -DPYR_PHASE_PROFILE
+// builds, whose device-side counters must live in one translation unit). pyrite_amd/build.py compiles the four side by side.
+// Its one parameter is PYR_WIDE_VM, which wide.hip defines: the online interpreter builds of render_kernel_sm (no tape) whose register
+// files (struct Vm) hold PYR_WIDE_*_REGISTERS, for scenes with a program that needs more than the in-register file even after api.cpp's
+// register allocation (program_regs.h). Everything of that unit lives in a namespace of its own, pyr::wide: the same templates with
+// another Vm under the same names would break the one-definition rule.
+#ifdef PYR_WIDE_VM
 #define PYR_VM_NUMBERS PYR_WIDE_NUMBER_REGISTERS
 #define PYR_VM_VECTORS PYR_WIDE_VECTOR_REGISTERS
 #define PYR_VM_RGBS PYR_WIDE_RGB_REGISTERS
@@ -57,15 +50,8 @@ static_assert((PYR_VM_NUMBERS & (PYR_VM_NUMBERS - 1)) == 0 && (PYR_VM_VECTORS & 
               "the interpreter masks register indices: its files are powers of two");
 
 namespace pyr {
-#if PYR_TU_WIDE
+#ifdef PYR_WIDE_VM
 namespace wide {
-#endif
-
-#if PYR_TU_MAIN
-namespace {
-thread_local std::string g_kernel_error;
-}
-const char* kernels_last_error() { return g_kernel_error.c_str(); }
 #endif
 
 #define DEV __device__ __forceinline__
@@ -1357,10 +1343,6 @@ DEV DevScene stage_tables(const DevScene& S, float* lds, uint32_t lds_floats_bef
         };
         local.spectra = reinterpret_cast<const PyrSpectrum*>(stage(S.spectra, S.num_spectra * (uint32_t)(sizeof(PyrSpectrum) / sizeof(float))));
         local.spectrum_data = stage(S.spectrum_data, S.num_spectrum_floats);
-#ifndef PYR_LDS_SMALL_TABLES
-#define PYR_LDS_SMALL_TABLES 1
-#endif
-#if PYR_LDS_SMALL_TABLES
         // The records a bounce walks through one after the other -- material -> component -> program, and the lamp of a
         // next-event estimation -- are a few hundred bytes per scene, but every step of that chain was an L2 round trip (the
         // BVH traffic keeps evicting them from L1) in phases that run at a third of the wave's width: staged with the spectra.
@@ -1368,7 +1350,6 @@ DEV DevScene stage_tables(const DevScene& S, float* lds, uint32_t lds_floats_bef
         local.components = reinterpret_cast<const PyrComponent*>(stage(S.components, S.num_components * (uint32_t)(sizeof(PyrComponent) / sizeof(float))));
         local.programs = reinterpret_cast<const DevProgram*>(stage(S.programs, S.num_programs * (uint32_t)(sizeof(DevProgram) / sizeof(float))));
         local.lamps = reinterpret_cast<const DevLamp*>(stage(S.lamps, S.num_lamps * (uint32_t)(sizeof(DevLamp) / sizeof(float))));
-#endif
         if (COPY) __syncthreads();
     }
     return local;
@@ -1445,7 +1426,7 @@ struct SyncProf {
     unsigned long long section[8] = {0, 0, 0, 0, 0, 0, 0, 0}, last = 0;
 };
 #ifdef PYR_PHASE_PROFILE
-__device__ unsigned long long g_phase_prof[32]; // [0..15] as tools/phase_profile.py reads them; [16..31] render_kernel_px seat census
+__device__ unsigned long long g_phase_prof[16]; // as tools/phase_profile.py reads them
 #define SLAP(sp, i)                                 \
     {                                               \
         const unsigned long long now_ = clock64();  \
@@ -1458,35 +1439,20 @@ __device__ unsigned long long g_phase_prof[32]; // [0..15] as tools/phase_profil
 
 // Wave priority per section of the synchronous walk (s_setprio; see PYR_PRIO_* of the stage scheduler for why): traversal on
 // top, the next-event estimation's own arithmetic below it, shading below that, exposure and sample start at the bottom.
-// C2 803 -> 827 Msamples/s. All four equal = no instruction emitted.
-#ifndef PYR_SYNC_PRIO_T
-#define PYR_SYNC_PRIO_T 3
-#endif
-#ifndef PYR_SYNC_PRIO_N
-#define PYR_SYNC_PRIO_N 2
-#endif
-#ifndef PYR_SYNC_PRIO_S
-#define PYR_SYNC_PRIO_S 1
-#endif
-#ifndef PYR_SYNC_PRIO_E
-#define PYR_SYNC_PRIO_E 0
-#endif
-#if PYR_SYNC_PRIO_T != PYR_SYNC_PRIO_N || PYR_SYNC_PRIO_N != PYR_SYNC_PRIO_S || PYR_SYNC_PRIO_S != PYR_SYNC_PRIO_E
+// C2 803 -> 827 Msamples/s.
+constexpr int SYNC_PRIO_T = 3, SYNC_PRIO_N = 2, SYNC_PRIO_S = 1, SYNC_PRIO_E = 0; // traversal, next-event estimation, shading, exposure
 #define SYNC_PRIO(x) __builtin_amdgcn_s_setprio(x)
-#else
-#define SYNC_PRIO(x)
-#endif
 // One iteration of tracer::trace's loop (tracer.rs:221-344) with `contribute` (renderer/algorithm.rs:14-100) applied online.
 // Returns true when the path has ended (emission, miss). Does not touch p.bounce.
-template <bool COUNT, bool INTERP>
+template <bool COUNT>
 DEV bool bounce_step(const DevScene& S, const RenderLaunch& L, const SceneView& view, Path& p, Spectral& spec, int* stack, Counters& cnt, SyncProf& sp) {
     const uint32_t n_add = L.spectrum_samples - 1;
     Hit hit;
     if (COUNT) cnt.extension_rays++;
     const f3 ray_o = p.o, ray_d = p.d;
-    SYNC_PRIO(PYR_SYNC_PRIO_T);
+    SYNC_PRIO(SYNC_PRIO_T);
     const bool found = traverse<COUNT, false>(S, view.nodes, view.prims, ray_o, ray_d, 0.0f, hit, stack, cnt);
-    SYNC_PRIO(PYR_SYNC_PRIO_S);
+    SYNC_PRIO(SYNC_PRIO_S);
     SLAP(sp, 1);
     if (!found) {
         // miss: first matching directional lamp (trace_directional, tracer.rs:444-459) or the sky; dispersed = false
@@ -1500,13 +1466,13 @@ DEV bool bounce_step(const DevScene& S, const RenderLaunch& L, const SceneView& 
                 }
             }
         }
-        const Prepared q_prog = prepare_program<INTERP>(S, color);
+        const Prepared q_prog = prepare_program<false>(S, color);
         VmInput in{p.wl, -ray_d, ray_d};
-        p.bright += eval_prepared<INTERP>(S, q_prog, in) * 1.0f * p.refl;
+        p.bright += eval_prepared<false>(S, q_prog, in) * 1.0f * p.refl;
         if (p.use_additional)
             for (uint32_t k = 0; k < n_add; ++k) {
                 in.wavelength = spec.wl(k);
-                spec.bright(k) += eval_prepared<INTERP>(S, q_prog, in) * 1.0f * spec.refl(k);
+                spec.bright(k) += eval_prepared<false>(S, q_prog, in) * 1.0f * spec.refl(k);
             }
         return true;
     }
@@ -1522,20 +1488,20 @@ DEV bool bounce_step(const DevScene& S, const RenderLaunch& L, const SceneView& 
     bool normal_dispersed = false;
     if (comp.probability_program >= 0) {
         VmInput pin{p.wl, normal, ray_d};
-        component_probability = run_program<INTERP>(S, (uint32_t)comp.probability_program, pin) * comp.selection_compensation;
+        component_probability = run_program<false>(S, (uint32_t)comp.probability_program, pin) * comp.selection_compensation;
         normal_dispersed = S.programs[comp.probability_program].reads_wavelength != 0;
     }
 
     if (comp.bsdf == PYR_BSDF_EMISSIVE) { // Scattering::Emitted, tracer.rs:303-318
         if (p.sample_light) {
             p.use_additional = !normal_dispersed && p.use_additional;
-            const Prepared q_prog = prepare_program<INTERP>(S, comp.color_program);
+            const Prepared q_prog = prepare_program<false>(S, comp.color_program);
             VmInput in{p.wl, normal, ray_d};
-            p.bright += eval_prepared<INTERP>(S, q_prog, in) * component_probability * p.refl;
+            p.bright += eval_prepared<false>(S, q_prog, in) * component_probability * p.refl;
             if (p.use_additional)
                 for (uint32_t k = 0; k < n_add; ++k) {
                     in.wavelength = spec.wl(k);
-                    spec.bright(k) += eval_prepared<INTERP>(S, q_prog, in) * component_probability * spec.refl(k);
+                    spec.bright(k) += eval_prepared<false>(S, q_prog, in) * component_probability * spec.refl(k);
                 }
         }
         return true;
@@ -1568,18 +1534,18 @@ DEV bool bounce_step(const DevScene& S, const RenderLaunch& L, const SceneView& 
     const float bounce_probability = scatter_probability * component_probability; // tracer.rs:296
     p.use_additional = !(dispersed || normal_dispersed) && p.use_additional;       // simple.rs:122-123, tracer.rs:290
     {
-        const Prepared q_prog = prepare_program<INTERP>(S, comp.color_program);
+        const Prepared q_prog = prepare_program<false>(S, comp.color_program);
         VmInput in{p.wl, normal, ray_d};
-        p.refl *= eval_prepared<INTERP>(S, q_prog, in) * bounce_probability;
+        p.refl *= eval_prepared<false>(S, q_prog, in) * bounce_probability;
         if (p.use_additional)
             for (uint32_t k = 0; k < n_add; ++k) {
                 in.wavelength = spec.wl(k);
-                spec.refl(k) *= eval_prepared<INTERP>(S, q_prog, in) * bounce_probability;
+                spec.refl(k) *= eval_prepared<false>(S, q_prog, in) * bounce_probability;
             }
     }
 
     SLAP(sp, 2);
-    SYNC_PRIO(PYR_SYNC_PRIO_N);
+    SYNC_PRIO(SYNC_PRIO_N);
     // next-event estimation gate, tracer.rs:257-280
     if (p.events < 2) {
         p.sample_light = !has_brdf || L.light_samples == 0;
@@ -1601,11 +1567,11 @@ DEV bool bounce_step(const DevScene& S, const RenderLaunch& L, const SceneView& 
                 uint32_t parked = 0, parked_color = 0;
                 auto flush_parked = [&]() {
                     if (parked == 0) return;
-                    const Prepared q_prog = prepare_program<INTERP>(S, parked_color);
+                    const Prepared q_prog = prepare_program<false>(S, parked_color);
                     VmInput in{0.0f, mk(0, 0, 0), mk(0, 0, 0)};
                     for (uint32_t k = 0; k < n_add; ++k) {
                         in.wavelength = spec.wl(k);
-                        const float color = eval_prepared<INTERP>(S, q_prog, in);
+                        const float color = eval_prepared<false>(S, q_prog, in);
                         const float refl = spec.refl(k);
                         float b = spec.bright(k);
                         b += color * parked0 * refl;
@@ -1624,9 +1590,9 @@ DEV bool bounce_step(const DevScene& S, const RenderLaunch& L, const SceneView& 
                     const float limit = ls.sq_distance >= 0.0f ? ls.sq_distance - DIST_EPSILON : PYR_INF;
                     Hit shadow_hit;
                     SLAP(sp, 3);
-                    SYNC_PRIO(PYR_SYNC_PRIO_T);
+                    SYNC_PRIO(SYNC_PRIO_T);
                     const bool is_blocked = traverse<COUNT, true>(S, view.nodes, view.prims, position, ls.direction, limit, shadow_hit, stack, cnt);
-                    SYNC_PRIO(PYR_SYNC_PRIO_N);
+                    SYNC_PRIO(SYNC_PRIO_N);
                     SLAP(sp, 4);
                     if (is_blocked) continue;
                     uint32_t l_color = ls.color;
@@ -1640,7 +1606,7 @@ DEV bool bounce_step(const DevScene& S, const RenderLaunch& L, const SceneView& 
                         material_probability = ec.selection_compensation;
                         if (ec.probability_program >= 0) {
                             VmInput pin{p.wl, ls.normal, ls.direction};
-                            material_probability = run_program<INTERP>(S, (uint32_t)ec.probability_program, pin) * ec.selection_compensation;
+                            material_probability = run_program<false>(S, (uint32_t)ec.probability_program, pin) * ec.selection_compensation;
                             l_dispersed = S.programs[ec.probability_program].reads_wavelength != 0;
                         }
                         l_color = ec.color_program;
@@ -1649,24 +1615,17 @@ DEV bool bounce_step(const DevScene& S, const RenderLaunch& L, const SceneView& 
                     const float scale = ls.weight * probability * (2.0f * fabsf(dot(ls.direction, nff))); // lambertian, diffuse.rs:27-29
                     const float l_probability = scale * material_probability;
                     // contribute, direct light (algorithm.rs:65-90)
-                    const Prepared q_prog = prepare_program<INTERP>(S, l_color);
+                    const Prepared q_prog = prepare_program<false>(S, l_color);
                     VmInput in{p.wl, target_normal, ls.direction};
-                    p.bright += eval_prepared<INTERP>(S, q_prog, in) * l_probability * p.refl;
+                    p.bright += eval_prepared<false>(S, q_prog, in) * l_probability * p.refl;
                     if (p.use_additional && !l_dispersed) {
-                        if constexpr (INTERP) {
-                            for (uint32_t k = 0; k < n_add; ++k) {
-                                in.wavelength = spec.wl(k);
-                                spec.bright(k) += eval_prepared<INTERP>(S, q_prog, in) * l_probability * spec.refl(k);
-                            }
-                        } else {
-                            if (parked != 0 && (parked == 4 || parked_color != l_color)) flush_parked();
-                            parked_color = l_color;
-                            if (parked == 0) parked0 = l_probability;
-                            if (parked == 1) parked1 = l_probability;
-                            if (parked == 2) parked2 = l_probability;
-                            if (parked == 3) parked3 = l_probability;
-                            parked++;
-                        }
+                        if (parked != 0 && (parked == 4 || parked_color != l_color)) flush_parked();
+                        parked_color = l_color;
+                        if (parked == 0) parked0 = l_probability;
+                        if (parked == 1) parked1 = l_probability;
+                        if (parked == 2) parked2 = l_probability;
+                        if (parked == 3) parked3 = l_probability;
+                        parked++;
                     }
                 }
                 flush_parked();
@@ -1698,37 +1657,32 @@ DEV void finish_path(const RenderLaunch& L, const Path& p, Spectral& spec, Count
         for (uint32_t k = 0; k + 1 < L.spectrum_samples; ++k) expose_grain<COUNT>(L, p.pixel, spec.wl(k), spec.bright(k), cnt);
 }
 
+// The launch record as the kernel-argument segment holds it, behind a pointer the compiler cannot see through. The stage
+// loop keeps ~100 uniform scene / launch values alive; there are 104 scalar registers, so the allocator parks the rest in
+// lanes of a VGPR and fetches them back with v_readlane -- vector instructions, sixteen in a row where a phase wants the
+// camera -- in a kernel that is bound by vector issue. Read through this reference at the head of a phase the fields are
+// s_load'ed from the (scalar-cached) argument segment where they are used and die with the phase.
+typedef __attribute__((address_space(4))) const RenderLaunch* kernarg_launch_ptr;
+constexpr size_t kLaunchKernargOffset = (sizeof(DevScene) + alignof(RenderLaunch) - 1) / alignof(RenderLaunch) * alignof(RenderLaunch);
+typedef __attribute__((address_space(4))) const DevScene* kernarg_scene_ptr;
+DEV const DevScene& scene_from_kernarg(const DevScene& /*by_value*/) { // the scene record: the first kernel argument (the by-value copy is named, not read)
+    unsigned long long at = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
+    asm volatile("" : "+s"(at));
+    return *(const DevScene*)(kernarg_scene_ptr)at;
+}
+DEV const RenderLaunch& launch_from_kernarg(const RenderLaunch& /*by_value*/) {
+    unsigned long long at = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr() + kLaunchKernargOffset;
+    asm volatile("" : "+s"(at));
+    return *(const RenderLaunch*)(kernarg_launch_ptr)at;
+}
+
 // Bounce-synchronous integrator: a wave takes a chunk of 64 samples and walks the 64 paths bounce by bounce. Next-event
 // estimation happens in the first two diffuse events of a path (tracer.rs:257), i.e. at the same time for all 64 lanes
 // of a diffuse scene, which is why this plain walk beats per-lane refill on C2:
 //   * refilling a lane as soon as its path ends (one bounce per loop turn)                         0.60x
 //   * parking survivors of the first two bounces in a ballot-compacted HBM queue for a tail kernel  0.93x
 // (MI355X, C2, 64 spp; both were built and measured, see DESIGN.md "Scheduling experiments").
-// The launch record as the kernel-argument segment holds it, behind a pointer the compiler cannot see through. The stage
-// loop keeps ~100 uniform scene / launch values alive; there are 104 scalar registers, so the allocator parks the rest in
-// lanes of a VGPR and fetches them back with v_readlane -- vector instructions, sixteen in a row where a phase wants the
-// camera -- in a kernel that is bound by vector issue. Read through this reference at the head of a phase the fields are
-// s_load'ed from the (scalar-cached) argument segment where they are used and die with the phase.
-#ifndef PYR_RELOAD_LAUNCH
-#define PYR_RELOAD_LAUNCH 1
-#endif
-typedef __attribute__((address_space(4))) const RenderLaunch* kernarg_launch_ptr;
-constexpr size_t kLaunchKernargOffset = (sizeof(DevScene) + alignof(RenderLaunch) - 1) / alignof(RenderLaunch) * alignof(RenderLaunch);
-typedef __attribute__((address_space(4))) const DevScene* kernarg_scene_ptr;
-DEV const DevScene& scene_from_kernarg(const DevScene& by_value) { // the scene record: the first kernel argument
-    if (!PYR_RELOAD_LAUNCH) return by_value;
-    unsigned long long at = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr();
-    asm volatile("" : "+s"(at));
-    return *(const DevScene*)(kernarg_scene_ptr)at;
-}
-DEV const RenderLaunch& launch_from_kernarg(const RenderLaunch& by_value) {
-    if (!PYR_RELOAD_LAUNCH) return by_value;
-    unsigned long long at = (unsigned long long)__builtin_amdgcn_kernarg_segment_ptr() + kLaunchKernargOffset;
-    asm volatile("" : "+s"(at));
-    return *(const RenderLaunch*)(kernarg_launch_ptr)at;
-}
-
-template <bool COUNT, bool INTERP, bool LDS_SCENE, bool LDS_TABLES>
+template <bool COUNT, bool LDS_SCENE, bool LDS_TABLES>
 __global__ __launch_bounds__(BLOCK, 4) void render_kernel(DevScene S0, RenderLaunch L) {
     extern __shared__ float lds[];
     const uint32_t SS = L.spectrum_samples;
@@ -1758,12 +1712,12 @@ __global__ __launch_bounds__(BLOCK, 4) void render_kernel(DevScene S0, RenderLau
         if (COUNT) cnt.samples++;
         SLAP(sp, 0);
         while (p.bounce < L.bounces) {
-            const bool ended = bounce_step<COUNT, INTERP>(S, launch_from_kernarg(L), view, p, spec, stack, cnt, sp);
+            const bool ended = bounce_step<COUNT>(S, launch_from_kernarg(L), view, p, spec, stack, cnt, sp);
             p.bounce++;
             if (ended) break;
         }
         SLAP(sp, 6);
-        SYNC_PRIO(PYR_SYNC_PRIO_E);
+        SYNC_PRIO(SYNC_PRIO_E);
         finish_path<COUNT>(launch_from_kernarg(L), p, spec, cnt);
         SLAP(sp, 7);
     }
@@ -1836,9 +1790,9 @@ DEV void trav_ray_signs(Trav& t) {
     t.ny = (__float_as_uint(t.d.y) >> 31) * 48u;
     t.nz = (__float_as_uint(t.d.z) >> 31) * 48u;
 }
-// Puts a query whose ray, limit and plane results are set at the root of the tree.
 // v_sqrt_f32 alone: the ulp it may be off by is far inside the margin (0.1 % at least). +inf stays +inf; a negative limit gives NaN: nothing passes
 DEV float shadow_cutoff(float limit, float margin) { return __builtin_amdgcn_sqrtf(limit * margin + 1.0e-3f); }
+// Puts a query whose ray, limit and plane results are set at the root of the tree.
 // (t.inv is NOT set here: the kernels compute it where a ray is about to be stepped -- the stage scheduler at every entry of
 // its traversal phase -- so that the three registers are free while the other phases run.)
 DEV void trav_restart(Trav& t, float shadow_margin) {
@@ -1898,10 +1852,6 @@ struct TravStack {
     DEV int pop(int sp) const { return sp < lds_entries ? lds[sp * BLOCK] : deep[sp - lds_entries]; }
 };
 
-// One node visit or one leaf. Returns true when the traversal has finished. Same tests, same order as traverse<>.
-// One visit of a four-child node (bvh.h Node128). The twelve plane distances of two children at a time are v_pk_fma_f32;
-// the children that are hit are ordered by entry distance with a five-comparator network, the nearest is entered and the
-// others are pushed far to near, so they pop nearest first. Returns true when the traversal has finished.
 // The four box tests of a node and the order of its children: c[] = the children that are hit, nearest first (entry distance
 // e[]), the others INT32_MIN at the end.
 // SIGNED: the first three vectors are the planes the ray meets first on each axis and the other three the ones it meets last
@@ -1992,6 +1942,9 @@ DEV void wide_children(const float4* wide_nodes, const Trav& t, Counters& cnt, f
     const WidePlanes pl = load_wide_planes(wide_nodes, t); // near / far planes picked by the ray's signs (trav_ray_signs)
     wide_node_children<COUNT, true>(pl.nx, pl.ny, pl.nz, pl.fx, pl.fy, pl.fz, pl.ch, t, cnt, e, c);
 }
+// One visit of a four-child node (bvh.h Node128). The twelve plane distances of two children at a time are v_pk_fma_f32;
+// the children that are hit are ordered by entry distance with a five-comparator network, the nearest is entered and the
+// others are pushed far to near, so they pop nearest first. Returns true when the traversal has finished.
 template <bool COUNT, bool GLOBAL = true>
 DEV bool trav_step_wide(const SceneView& view, Trav& t, TravStack& stack, Counters& cnt) {
     float e[4];
@@ -2010,8 +1963,6 @@ DEV bool trav_step_wide(const SceneView& view, Trav& t, TravStack& stack, Counte
     return false;
 }
 
-// One primitive of a leaf, its record already loaded (a, b, c = the three vectors of a DevPrim): the tests and the
-// bookkeeping of trav_step's leaf part. `first` / `count` are the leaf code's fields. Returns true when the traversal has finished.
 // The test and the verdict; true when the primitive blocks a shadow ray.
 template <bool COUNT>
 DEV bool leaf_prim_test(const float4 a, const float4 b, const float4 c, Trav& t, Counters& cnt) {
@@ -2040,6 +1991,8 @@ DEV bool leaf_prim_test(const float4 a, const float4 b, const float4 c, Trav& t,
     t.v = closer ? v : t.v;
     return blocks;
 }
+// One primitive of a leaf, its record already loaded (a, b, c = the three vectors of a DevPrim): the tests and the
+// bookkeeping of trav_step's leaf part. `first` / `count` are the leaf code's fields. Returns true when the traversal has finished.
 template <bool COUNT>
 DEV bool leaf_prim_visit(const float4 a, const float4 b, const float4 c, uint32_t first, uint32_t count, Trav& t, TravStack& stack, Counters& cnt) {
     if (leaf_prim_test<COUNT>(a, b, c, t, cnt)) return true;
@@ -2078,9 +2031,6 @@ DEV bool trav_node_step(const SceneView& view, Trav& t, TravStack& stack, Counte
     }
     return false;
 }
-// One primitive of the leaf a lane stands in (t.node < 0). A leaf is walked one primitive per step (the code in t.node shrinks:
-// first + 1, count - 1), in leaf order. Looping over the whole leaf here made every wave pay for its fullest leaf (4
-// primitives) at each step while most lanes were at inner nodes: 17 % VALU lane occupancy in the traversal kernel.
 // Two triangles of a leaf in one step, both Moeller-Trumbore tests in packed f32 (DevPrimPair): the operations of
 // triangle_test, component pairs side by side, and the verdicts applied in leaf order -- triangle A, then triangle B against
 // the closest distance A left -- so the outcome is the one two single steps give. A ray makes 3.3 primitive steps on C3
@@ -2134,6 +2084,9 @@ DEV bool leaf_pair_visit(const float4 q0, const float4 q1, const float4 q2, cons
     return false;
 }
 
+// One primitive of the leaf a lane stands in (t.node < 0). A leaf is walked one primitive per step (the code in t.node shrinks:
+// first + 1, count - 1), in leaf order. Looping over the whole leaf here made every wave pay for its fullest leaf (4
+// primitives) at each step while most lanes were at inner nodes: 17 % VALU lane occupancy in the traversal kernel.
 template <bool COUNT, bool GLOBAL = true>
 DEV bool trav_leaf_step(const SceneView& view, Trav& t, TravStack& stack, Counters& cnt) {
     const uint32_t code = (uint32_t)(-1 - t.node);
@@ -2151,6 +2104,20 @@ DEV bool trav_leaf_step(const SceneView& view, Trav& t, TravStack& stack, Counte
     t.node = stack.pop(t.sp);
     return false;
 }
+// One step for the lanes of a wave that have a ray in flight (`active`), with a vote: a step is an inner-node visit or a
+// primitive test, two different pieces of code, and a wave whose lanes want both runs both at partial occupancy. Only the
+// kind most lanes wait for runs this turn; the minority keeps its place (rays are independent; a later turn serves them).
+// Must be called by every lane of the wave. Measured on C3 (intersect Mrays/s | stage-scheduled render Msamples/s): both kinds
+// every turn 5774 | 210; minority too when it has >= 16 / 32 lanes 5899 | 225, 5882 | 228; majority only 6087 | 236.
+template <bool COUNT, bool GLOBAL = true>
+DEV bool trav_step_voted(const SceneView& view, Trav& t, TravStack& stack, Counters& cnt, bool active) {
+    const bool at_node = t.node >= 0;
+    const unsigned long long nodes = ballot64(active && at_node), leaves = ballot64(active && !at_node);
+    // the choice is wave-uniform, so it is a scalar branch to ONE of the two bodies, not two masked regions
+    if (__popcll(nodes) >= __popcll(leaves)) return (active && at_node) ? trav_node_step<COUNT, GLOBAL>(view, t, stack, cnt) : false;
+    return (active && !at_node) ? trav_leaf_step<COUNT, GLOBAL>(view, t, stack, cnt) : false;
+}
+
 // The step of trav_step_voted (majority kind only) for the tree the big scenes walk -- four-child nodes whose leaves index
 // triangle pairs -- as straight-line code. What the generic step spends around the tests is control flow: three conditional
 // pushes, each an LDS-or-scratch choice (two saved exec masks and their branches per push), the same again around the pop, and
@@ -2161,46 +2128,6 @@ DEV bool trav_leaf_step(const SceneView& view, Trav& t, TravStack& stack, Counte
 //     hit is stored too -- at level sp + n, above the new top, where nothing lives;
 //   - node, stack pointer and the verdict are selects.
 // Same tests, same order of visits, same stack contents below the top as the generic step.
-template <bool COUNT>
-DEV bool trav_step_lean(const SceneView& view, Trav& t, TravStack& stack, Counters& cnt, bool active);
-// One step for the lanes of a wave that have a ray in flight (`active`), with a vote: a step is an inner-node visit or a
-// primitive test, two different pieces of code, and a wave whose lanes want both runs both at partial occupancy. Only the
-// kind most lanes wait for runs this turn; the minority keeps its place (rays are independent; a later turn serves them).
-// Must be called by every lane of the wave. Measured on C3 (intersect Mrays/s | stage-scheduled render Msamples/s): both kinds
-// every turn 5774 | 210; minority too when it has >= 16 / 32 lanes 5899 | 225, 5882 | 228; majority only 6087 | 236.
-// Wave priority per phase of the stage scheduler (s_setprio, 0-3: a SIMD issues from the ready wave with the highest priority).
-// With equal priorities the arbiter interleaves a wave that walks the tree with one that replays tapes instruction by
-// instruction and both chains stretch; with the traversal on top, the replay (full width, no dependent fetches, the longest
-// phase) at the bottom and SHADE / NEE between them, every phase runs close to its own speed whenever it is ready and the
-// lower ones fill its waits: C3 533 -> 579 Msamples/s, C5 464 -> 507 (128 / 256 spp). Any split between traversal and the rest
-// gives +6 % -- in EITHER direction --, four distinct levels +8.5 %; the same priority per WAVE instead of per phase gives nothing.
-#ifndef PYR_PRIO_E
-#define PYR_PRIO_E 0
-#endif
-#ifndef PYR_PRIO_S
-#define PYR_PRIO_S 1
-#endif
-#ifndef PYR_PRIO_N
-#define PYR_PRIO_N 2
-#endif
-#ifndef PYR_PRIO_T
-#define PYR_PRIO_T 3
-#endif
-#define PYR_PRIO_ANY (PYR_PRIO_E != PYR_PRIO_S || PYR_PRIO_S != PYR_PRIO_N || PYR_PRIO_N != PYR_PRIO_T)
-#if PYR_PRIO_ANY
-#define PHASE_PRIO(x) __builtin_amdgcn_s_setprio(x)
-#else
-#define PHASE_PRIO(x)
-#endif
-template <bool COUNT, bool GLOBAL = true>
-DEV bool trav_step_voted(const SceneView& view, Trav& t, TravStack& stack, Counters& cnt, bool active) {
-    const bool at_node = t.node >= 0;
-    const unsigned long long nodes = ballot64(active && at_node), leaves = ballot64(active && !at_node);
-    // the choice is wave-uniform, so it is a scalar branch to ONE of the two bodies, not two masked regions
-    if (__popcll(nodes) >= __popcll(leaves)) return (active && at_node) ? trav_node_step<COUNT, GLOBAL>(view, t, stack, cnt) : false;
-    return (active && !at_node) ? trav_leaf_step<COUNT, GLOBAL>(view, t, stack, cnt) : false;
-}
-
 template <bool COUNT>
 DEV bool trav_step_lean(const SceneView& view, Trav& t, TravStack& stack, Counters& cnt, bool active) {
     const bool at_node = t.node >= 0;
@@ -2248,7 +2175,31 @@ DEV bool trav_step_lean(const SceneView& view, Trav& t, TravStack& stack, Counte
     return done;
 }
 
-// Per-path state of the resumable integrator and the code of its phases (the stage-scheduled kernel keeps it in registers).
+// Wave priority per phase of the stage scheduler (s_setprio, 0-3: a SIMD issues from the ready wave with the highest priority).
+// With equal priorities the arbiter interleaves a wave that walks the tree with one that replays tapes instruction by
+// instruction and both chains stretch; with the traversal on top, the replay (full width, no dependent fetches, the longest
+// phase) at the bottom and SHADE / NEE between them, every phase runs close to its own speed whenever it is ready and the
+// lower ones fill its waits: C3 533 -> 579 Msamples/s, C5 464 -> 507 (128 / 256 spp). Any split between traversal and the rest
+// gives +6 % -- in EITHER direction --, four distinct levels +8.5 %; the same priority per WAVE instead of per phase gives nothing.
+#ifndef PYR_PRIO_E
+#define PYR_PRIO_E 0
+#endif
+#ifndef PYR_PRIO_S
+#define PYR_PRIO_S 1
+#endif
+#ifndef PYR_PRIO_N
+#define PYR_PRIO_N 2
+#endif
+#ifndef PYR_PRIO_T
+#define PYR_PRIO_T 3
+#endif
+#define PYR_PRIO_ANY (PYR_PRIO_E != PYR_PRIO_S || PYR_PRIO_S != PYR_PRIO_N || PYR_PRIO_N != PYR_PRIO_T)
+#if PYR_PRIO_ANY
+#define PHASE_PRIO(x) __builtin_amdgcn_s_setprio(x)
+#else
+#define PHASE_PRIO(x)
+#endif
+
 // Spectral tape (TAPE builds: the stage-scheduled kernel on scenes without interpreter programs, i.e. every BASELINE
 // config; since round 4 also on scenes WITH interpreter programs whose colour programs have a tape form, see tape_pending). Without the interpreter a colour program is a function of the wavelength alone, and nothing a path decides
 // depends on its brightness or reflectance (the reference has no Russian roulette; only the hero wavelength's value enters
@@ -2261,9 +2212,6 @@ DEV bool trav_step_lean(const SceneView& view, Trav& t, TravStack& stack, Counte
 // its finished lanes with one (path, wavelength) pair per lane, at full width: the same f32 operations in the same order for
 // every wavelength, so the film is bit-identical. The S wavelengths stay in LDS; the per-lane brightness / reflectance arrays
 // ([2 (S - 1)][256] floats of LDS) are gone, which lets the traversal stack live in LDS down to 16 levels.
-// Developer builds that time the parts of this scheme by leaving one out (the FILM IS WRONG under each of them; DESIGN.md 3.2
-// quotes the numbers): -DPYR_TAPE_NOSTORE (no records written), -DPYR_TAPE_NOREPLAY (no replay), -DPYR_REPLAY_NOEVAL (record
-// by record path: programs evaluate to 1), -DPYR_REPLAY_NOEXPOSE (no film atomics).
 constexpr uint32_t kTapeEagerSlots = 8; // LDS rows for the values of the programs that read a spectrum (replay_tapes)
 constexpr uint32_t TAPE_MUL = 0u, TAPE_ADD = 1u, TAPE_SCALE = 2u, TAPE_HERO_ONLY = 1u << 29, TAPE_PROGRAM_MASK = (1u << 28) - 1u;
 // Records of the eager replay (the scene's spectrum-reading programs fit the LDS value rows): every record is "m = value[slot] * s;
@@ -2287,6 +2235,7 @@ static_assert(BLOCK == 1u << TAPE_EAGER_SLOT_SHIFT, "an eager record's slot fiel
 // the 8-byte stores do NOT merge in L2 before they are written back, the neighbouring lanes' records no longer share a sector
 // either, and the fabric saw 85 GB instead of 68 GB per 32-spp frame: C3 -3.5 %, profiles/r04_write_traffic_split.txt.)
 DEV size_t tape_index(uint32_t op, uint32_t lanes, uint32_t column) { return (size_t)op * lanes + column; }
+// Per-path state of the resumable integrator and the code of its phases (the stage-scheduled kernel keeps it in registers).
 template <bool COUNT, bool INTERP, bool TAPE = false, bool PRODUCT = false> // PRODUCT: the scene has TAPE_FORM_PRODUCT colour programs (device_scene.h)
 struct Walker {
     uint32_t stage = ST_NEW;
@@ -2294,12 +2243,7 @@ struct Walker {
     uint32_t tape_column = 0; // TAPE: this path's column of the tape (the lane of the persistent grid, or the pool slot)
     const uint32_t* tape_prepared = nullptr; // TAPE, eager replay: the kernel's LDS table of prepared programs, else nullptr
     DEV void tape_push(const RenderLaunch& L, uint32_t kind, uint32_t program, float s, bool hero_only = false) {
-#ifndef PYR_TAPE_NOSTORE
-        if (n_ops < L.tape_max_ops)
-#else
-        if (n_ops > 1000000u)
-#endif
-        {
+        if (n_ops < L.tape_max_ops) {
             uint32_t word = (kind << 30) | (hero_only ? TAPE_HERO_ONLY : 0u) | (program & TAPE_PROGRAM_MASK);
             if (tape_prepared != nullptr) {
                 // eager replay: the record names the LDS slot of the program's value; a constant program is folded into the
@@ -2315,14 +2259,11 @@ struct Walker {
                 word = (kind == TAPE_ADD ? TAPE_EAGER_ADD : 0u) | (hero_only ? TAPE_HERO_ONLY : 0u) | (slot << TAPE_EAGER_SLOT_SHIFT);
             }
             L.tape[tape_index(n_ops, L.tape_lanes, tape_column)] = (unsigned long long)word | ((unsigned long long)__float_as_uint(s) << 32);
-        }
-#ifndef PYR_TAPE_NOSTORE
-        else {
+        } else {
             // more records than tape_ops_bound() allows for: the bound was derived by hand from trace / trace_direct, so a change
             // there that outgrows it must not pass as a slightly wrong film -- the host turns this word into PYR_ERR_DEVICE
             *L.tape_overflow = 1u;
         }
-#endif
         n_ops++;
     }
     // One eager record as it stands (HIT_VALUE / HIT_RGB contributions: Walker::tape_pending).
@@ -2832,9 +2773,6 @@ DEV void replay_tapes(const DevScene& S, const RenderLaunch& L, bool exposing, u
     const unsigned long long mask = ballot64(exposing);
     const uint32_t n = (uint32_t)__popcll(mask);
     if (n == 0) return;
-#ifdef PYR_TAPE_NOREPLAY
-    if (n_ops < 1000000u) return;
-#endif
     // The finished lanes are listed with the paths that keep their companions first, the dispersed ones behind them: a
     // dispersed path exposes its hero wavelength only (simple.rs:133-139), so it is ONE item, not S of which S - 1 idle --
     // on C5 a third of the paths disperse and a turn's items drop from 10 n to ~7 n, often a whole pass of 64 less.
@@ -2884,8 +2822,7 @@ DEV void replay_tapes(const DevScene& S, const RenderLaunch& L, bool exposing, u
         const float hero_wl = __shfl(p.wl, (int)src);
         const bool hero = k == SS - 1;
         const bool run = active;
-        // the companions' wavelengths live in the LDS column of the path's home (the lane itself in render_kernel_sm; wherever the
-        // path's sample sequence belongs in render_kernel_px, whose paths move between lanes)
+        // the companions' wavelengths live in the LDS column of the path's home (the lane itself in render_kernel_sm)
         const uint32_t src_column = (uint32_t)__shfl((int)wl_column, (int)src);
         const float wl = hero ? hero_wl : wl_rows[k * BLOCK + src_column];
         float refl = 1.0f, bright = 0.0f, value = 0.0f;
@@ -2909,9 +2846,6 @@ DEV void replay_tapes(const DevScene& S, const RenderLaunch& L, bool exposing, u
                 const float c = __uint_as_float(e[1]);
                 const float* data = S.spectrum_data + e[5];
                 float v;
-#ifdef PYR_REPLAY_NOEAGER_EVAL // timing ablation (the film is wrong): what the per-item look-ups of the spectrum-reading programs cost
-                v = wl * 1.0e-3f;
-#else
                 if (RGB && mode == 0xFFu) { // (uniform) a LAMBDA program: interpreted once per item (hit-tape scenes only)
                     v = lambda_eval(S, S.programs[slot_program[slot]], wl);
                 } else if (format == PYR_SPECTRUM_ARRAY && count != 0u) {
@@ -2933,7 +2867,6 @@ DEV void replay_tapes(const DevScene& S, const RenderLaunch& L, bool exposing, u
                     sp.format = format, sp.min = __uint_as_float(e[3]), sp.max = __uint_as_float(e[4]), sp.offset = e[5], sp.count = count;
                     v = spectrum_eval(sp, data, wl);
                 }
-#endif
                 spectral_values[tape_row(slot) * BLOCK] = (mode == FAST_SPECTRUM || mode == 0xFFu) ? v : v * c; // FAST_SPECTRUM_MUL and FAST_MUL_SPECTRUM: v * c is c * v
             }
             if (RGB && S.rgb_records != 0) { // (uniform) the RGB basis at this item's wavelength: RgbSpectrumValue's look-up, execution_context.rs:140-152
@@ -3028,9 +2961,6 @@ DEV void replay_tapes(const DevScene& S, const RenderLaunch& L, bool exposing, u
                 if ((word & TAPE_HERO_ONLY) && !hero) continue;
                 const uint32_t program = word & TAPE_PROGRAM_MASK;
                 if (program != value_of) {
-#ifdef PYR_REPLAY_NOEVAL
-                    value = 1.0f;
-#else
                     // the prepared form of a program: from the LDS table when the kernel staged one (a replay item changes
                     // program with nearly every record; fetching the program record from HBM each time was 16 % of the render)
                     Prepared q_prog;
@@ -3050,7 +2980,6 @@ DEV void replay_tapes(const DevScene& S, const RenderLaunch& L, bool exposing, u
                     }
                     VmInput in{wl, mk(0, 0, 0), mk(0, 0, 0)};
                     value = eval_prepared<false>(S, q_prog, in);
-#endif
                     value_of = program;
                 }
                 if (kind == TAPE_MUL)
@@ -3059,11 +2988,7 @@ DEV void replay_tapes(const DevScene& S, const RenderLaunch& L, bool exposing, u
                     bright += value * s * refl;
             }
         }
-#ifdef PYR_REPLAY_NOEXPOSE
-        if (run && bright == 123.456f) expose_grain<COUNT>(L, pixel, wl, bright, cnt);
-#else
         if (run) expose_grain<COUNT>(L, pixel, wl, bright, cnt);
-#endif
     }
     __builtin_amdgcn_wave_barrier();
 }
@@ -3122,9 +3047,9 @@ DEV uint32_t prepare_tape_tables(const DevScene& S0, const DevScene& S, const Re
 #ifndef PYR_SM_WAVES_INTERP
 #define PYR_SM_WAVES_INTERP 3
 #endif
-constexpr int sm_waves(bool interp, bool /*lds_scene*/, bool /*hit_tape*/) { return interp ? PYR_SM_WAVES_INTERP : PYR_SM_WAVES; }
+constexpr int sm_waves(bool interp) { return interp ? PYR_SM_WAVES_INTERP : PYR_SM_WAVES; }
 template <bool COUNT, bool INTERP, bool LDS_SCENE, bool LDS_TABLES, bool HIT_TAPE = false, bool PRODUCT = false>
-__global__ __launch_bounds__(BLOCK, sm_waves(INTERP, LDS_SCENE, HIT_TAPE)) void render_kernel_sm(DevScene S0, RenderLaunch L) {
+__global__ __launch_bounds__(BLOCK, sm_waves(INTERP)) void render_kernel_sm(DevScene S0, RenderLaunch L) {
     extern __shared__ float lds[];
     static_assert(INTERP || !HIT_TAPE, "HIT_TAPE is a form of the interpreter build");
     static_assert(HIT_TAPE || !PRODUCT, "PRODUCT is a form of the hit tape (device_scene.h TapeForm)");
@@ -3172,7 +3097,7 @@ __global__ __launch_bounds__(BLOCK, sm_waves(INTERP, LDS_SCENE, HIT_TAPE)) void 
 
     // the scene record as the phases see it (table pointers at the staged copies), rebuilt where a phase starts
     auto scene_view = [&](const RenderLaunch& Lp) {
-        if (!PYR_RELOAD_LAUNCH || LDS_SCENE || INTERP) return S; // interpreter builds hand the record to run_interpreter by address: one copy in scratch, made once
+        if (LDS_SCENE || INTERP) return S; // interpreter builds hand the record to run_interpreter by address: one copy in scratch, made once
         const uint32_t rows = (TAPE ? Lp.spectrum_samples + 1 + S0.tape_value_rows : 3 * Lp.spectrum_samples) + Lp.stack_lds;
         return stage_tables<LDS_TABLES ? 1 : 0, false>(scene_from_kernarg(S0), lds, rows * BLOCK);
     };
@@ -3382,411 +3307,9 @@ __global__ __launch_bounds__(BLOCK, PYR_INTERSECT_WAVES) void intersect_kernel(D
     flush_counters<COUNT>(cnt, L.counters);
 }
 
-#if PYR_TU_MAIN
-// ------------------------------------------------------------------------------------------------ film development
-// main.rs:315-327: every pixel spectrum -> spectrum_to_xyz (main.rs:352-418, trapezoid rule against the CIE observer
-// tables) -> linear sRGB -> sRGB u8. One thread per pixel; the film is read once (bins * 8 B per pixel), HBM-bound.
-// The last pixel is skipped as in DevelopedPixels::next (film.rs:299).
-__global__ __launch_bounds__(BLOCK) void develop_kernel(DevelopLaunch D) {
-    const size_t pixels = (size_t)D.film.width * D.film.height;
-    const uint32_t bins = D.film.bins;
-    const float min = D.film.wl_start, max = D.film.wl_start + D.film.wl_width;
-    for (size_t px = (size_t)blockIdx.x * BLOCK + threadIdx.x; px < pixels; px += (size_t)gridDim.x * BLOCK) {
-        uint8_t out[3] = {0, 0, 0};
-        if ((px + 1) * bins < pixels * bins) {
-            const PyrGrain* g = D.grains + px * bins;
-            auto xyz_get = [&](int channel, float w) {
-                const float* d = D.xyz_table;
-                const uint32_t n = D.xyz_count;
-                if (w <= D.xyz_min) return d[channel];
-                if (w >= D.xyz_max) return d[3 * (n - 1) + channel];
-                float normalized = (w - D.xyz_min) / (D.xyz_max - D.xyz_min);
-                float fi = normalized * ((float)n - 1.0f);
-                float fmin_ = truncf(fi);
-                uint32_t i0 = (uint32_t)fmin_;
-                float mix = fi - fmin_;
-                return d[3 * i0 + channel] * (1.0f - mix) + d[3 * (i0 + 1) + channel] * mix;
-            };
-            auto sample = [&](float w, uint32_t i) {
-                float intensity;
-                if (w < min || w > max) {
-                    intensity = 0.0f;
-                } else {
-                    float normalized = (w - min) / (max - min);
-                    float float_index = normalized * (float)bins;
-                    uint32_t index = (uint32_t)fminf(floorf(float_index), (float)(bins - 1));
-                    const PyrGrain gr = g[index];
-                    intensity = gr.weight > 0.0f ? gr.acc / gr.weight : 0.0f; // Grain::develop, film.rs:132-143
-                }
-                if (D.filter) intensity = intensity * D.filter[i];
-                if (D.white_div) intensity = (intensity / D.white_div[i]) * D.white_mul[i];
-                return intensity;
-            };
-            float sum[3] = {0, 0, 0}, weight = 0.0f;
-            float wl_min = min;
-            uint32_t i = 0;
-            float spectrum_min = sample(wl_min, i);
-            float start[3] = {xyz_get(0, wl_min), xyz_get(1, wl_min), xyz_get(2, wl_min)};
-            while (wl_min < max) {
-                float wl_max = wl_min + D.step_size;
-                i += 1;
-                float spectrum_max = sample(wl_max, i < D.sample_count ? i : D.sample_count - 1);
-                float end[3] = {xyz_get(0, wl_max), xyz_get(1, wl_max), xyz_get(2, wl_max)};
-                float w = wl_max - wl_min;
-                for (int c = 0; c < 3; ++c) sum[c] += (start[c] * spectrum_min + end[c] * spectrum_max) * 0.5f * w;
-                weight += w;
-                wl_min = wl_max;
-                spectrum_min = spectrum_max;
-                for (int c = 0; c < 3; ++c) start[c] = end[c];
-            }
-            float xyz[3];
-            for (int c = 0; c < 3; ++c) xyz[c] = (weight == 0.0f ? sum[c] : sum[c] / weight) * D.xyz_scale;
-            const float rgb[3] = {3.2404542f * xyz[0] + -1.5371385f * xyz[1] + -0.4985314f * xyz[2],
-                                  -0.9692660f * xyz[0] + 1.8760108f * xyz[1] + 0.0415560f * xyz[2],
-                                  0.0556434f * xyz[0] + -0.2040259f * xyz[1] + 1.0572252f * xyz[2]};
-            for (int c = 0; c < 3; ++c) {
-                float v = fminf(fmaxf(rgb[c], 0.0f), 1.0f);
-                float e = v <= 0.0031308f ? 12.92f * v : 1.055f * (float)pow((double)v, 1.0 / 2.4) - 0.055f;
-                e = fminf(fmaxf(e, 0.0f), 1.0f);
-                out[c] = (uint8_t)(e * 255.0f + 0.5f);
-            }
-        }
-        D.rgb_out[3 * px + 0] = out[0];
-        D.rgb_out[3 * px + 1] = out[1];
-        D.rgb_out[3 * px + 2] = out[2];
-    }
-}
-
-int launch_develop(const DevelopLaunch& launch, void* stream) {
-    const size_t pixels = (size_t)launch.film.width * launch.film.height;
-    if (pixels == 0) return PYR_OK;
-    uint32_t grid = (uint32_t)std::min<size_t>((pixels + BLOCK - 1) / BLOCK, 256 * 16);
-    hipLaunchKernelGGL(develop_kernel, dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, launch);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        g_kernel_error = std::string("develop kernel launch: ") + hipGetErrorString(err);
-        return PYR_ERR_DEVICE;
-    }
-    return PYR_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ film blocks -> film
-// Rank 0's side of the multi-GPU gather: the blocks a rank rendered (PYR_FILM_TILE_BLOCKS: the tile's pixels plus a ring of
-// one pixel) are added into the whole-image film. The pixels of a tile belong to one block of the set only, so they are
-// plain read-modify-writes, one grain (8 bytes) per thread, contiguous along a pixel row in both buffers: HBM-bound, two
-// reads and one write of 8 B per grain. Ring pixels lie inside neighbouring tiles -- which may be in the same set -- so
-// they go second, as atomics, and only where something was exposed (about one sample in 1e6 lands there).
-__global__ __launch_bounds__(BLOCK) void assemble_interior_kernel(AssembleLaunch A) {
-    const uint32_t ts = A.tile_size, side = ts + 2u, bins = A.film.bins;
-    const uint64_t row_grains = (uint64_t)ts * bins, tile_grains = row_grains * ts, total = tile_grains * A.tile_count;
-    for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < total; i += (uint64_t)gridDim.x * BLOCK) {
-        const uint32_t k = (uint32_t)(i / tile_grains);
-        const uint64_t r = i - (uint64_t)k * tile_grains;
-        const uint32_t row = (uint32_t)(r / row_grains), in_row = (uint32_t)(r - (uint64_t)row * row_grains);
-        const uint32_t col = in_row / bins, bin = in_row - col * bins;
-        const uint32_t tile = A.tile_begin + k * A.tile_stride;
-        const uint32_t ty = tile / A.tiles_x, tx = tile - ty * A.tiles_x;
-        const uint32_t x = tx * ts + col, y = ty * ts + row;
-        if (x >= A.film.width || y >= A.film.height) continue; // a tile cut by the image border
-        const PyrGrain g = A.blocks[(((size_t)k * side + row + 1u) * side + col + 1u) * bins + bin];
-        PyrGrain* out = A.film_out + ((size_t)x + (size_t)y * A.film.width) * bins + bin;
-        PyrGrain f = *out;
-        f.acc += g.acc;
-        f.weight += g.weight;
-        *out = f;
-    }
-}
-__global__ __launch_bounds__(BLOCK) void assemble_ring_kernel(AssembleLaunch A) {
-    const uint32_t ts = A.tile_size, side = ts + 2u, bins = A.film.bins;
-    const uint32_t ring = 4u * (ts + 1u); // pixels of the ring
-    const uint64_t tile_grains = (uint64_t)ring * bins, total = tile_grains * A.tile_count;
-    for (uint64_t i = (uint64_t)blockIdx.x * BLOCK + threadIdx.x; i < total; i += (uint64_t)gridDim.x * BLOCK) {
-        const uint32_t k = (uint32_t)(i / tile_grains);
-        const uint32_t r = (uint32_t)(i - (uint64_t)k * tile_grains);
-        const uint32_t q = r / bins, bin = r - q * bins;
-        // ring pixel q: top row (side pixels), bottom row (side), then the left and right columns without their corners
-        uint32_t bx, by;
-        if (q < side)
-            bx = q, by = 0u;
-        else if (q < 2u * side)
-            bx = q - side, by = side - 1u;
-        else if (q < 2u * side + ts)
-            bx = 0u, by = q - 2u * side + 1u;
-        else
-            bx = side - 1u, by = q - 2u * side - ts + 1u;
-        const PyrGrain g = A.blocks[(((size_t)k * side + by) * side + bx) * bins + bin];
-        if (g.acc == 0.0f && g.weight == 0.0f) continue;
-        const uint32_t tile = A.tile_begin + k * A.tile_stride;
-        const uint32_t ty = tile / A.tiles_x, tx = tile - ty * A.tiles_x;
-        const uint32_t x = tx * ts + bx - 1u, y = ty * ts + by - 1u; // wraps for the ring left of / above the image
-        if (x >= A.film.width || y >= A.film.height) continue;
-        float* out = reinterpret_cast<float*>(A.film_out + ((size_t)x + (size_t)y * A.film.width) * bins + bin);
-        atomicAdd(out, g.acc);
-        atomicAdd(out + 1, g.weight);
-    }
-}
-
-int launch_assemble(const AssembleLaunch& launch, void* stream) {
-    if (launch.tile_count == 0) return PYR_OK;
-    const uint64_t interior = (uint64_t)launch.tile_size * launch.tile_size * launch.film.bins * launch.tile_count;
-    const uint64_t ring = (uint64_t)4 * (launch.tile_size + 1) * launch.film.bins * launch.tile_count;
-    const uint32_t grid_i = (uint32_t)std::min<uint64_t>((interior + BLOCK - 1) / BLOCK, 256 * 32);
-    const uint32_t grid_r = (uint32_t)std::min<uint64_t>((ring + BLOCK - 1) / BLOCK, 256 * 32);
-    hipLaunchKernelGGL(assemble_interior_kernel, dim3(grid_i), dim3(BLOCK), 0, (hipStream_t)stream, launch);
-    hipLaunchKernelGGL(assemble_ring_kernel, dim3(grid_r), dim3(BLOCK), 0, (hipStream_t)stream, launch);
-    hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        g_kernel_error = std::string("assemble kernel launch: ") + hipGetErrorString(err);
-        return PYR_ERR_DEVICE;
-    }
-    return PYR_OK;
-}
-
-// ------------------------------------------------------------------------------------------------ launchers
-constexpr size_t kLdsSceneBytes = 8 * 1024; // nodes + primitives staged in LDS when they fit (C1, C2: < 3 KB)
-static bool scene_fits_lds(const DevScene& scene) { return (size_t)scene.num_nodes * 64 + (size_t)scene.num_prims * 48 <= kLdsSceneBytes; }
-// Levels of the traversal stack kept in LDS. The synchronous walk keeps the whole stack there (its scenes are shallow). The
-// resumable walk spills deeper levels to scratch (TravStack) and keeps as many levels in LDS as still let `workgroups`
-// workgroups share a CU's 160 KB next to `other_bytes` of LDS each -- on C3 the render runs at 103 / 135 / 160 Msamples/s
-// with 2 / 3 / 4 workgroups per CU and does not care whether 4 or 12 levels are in LDS. PYRITE_LDS_STACK overrides.
-constexpr uint32_t kShortStackMax = 16;
-static uint32_t short_stack_levels(const DevScene& scene, size_t other_bytes, uint32_t workgroups) {
-    const char* e = std::getenv("PYRITE_LDS_STACK");
-    uint32_t levels;
-    if (e && *e) {
-        levels = (uint32_t)std::strtoul(e, nullptr, 10);
-    } else {
-        const size_t budget = (160 * 1024) / std::max(workgroups, 1u);
-        levels = budget > other_bytes ? (uint32_t)((budget - other_bytes) / (BLOCK * sizeof(int))) : 0u;
-        levels = std::min(levels, kShortStackMax);
-    }
-    return std::max(1u, std::min(levels, scene.wide_nodes ? scene.wide_stack_depth : scene.stack_depth));
-}
-// Records a path can append: one MUL and one SCALE per bounce, light_samples ADDs in each of the two next-event estimations
-// (tracer.rs:257), one closing ADD (emission or sky).
-// A contribution whose colour program is HIT_RGB is four records (three coefficients and the factor).
-uint32_t tape_ops_bound(const DevScene& scene, const RenderLaunch& launch) {
-    return (launch.bounces + 2u * launch.light_samples + 1u) * (scene.micro_records ? 4u : 1u) + launch.bounces; // HIT_RGB: four records a contribution; PRODUCT: two to four
-}
-uint32_t tape_lanes_bound(int num_cus) { return (uint32_t)num_cus * 8u * BLOCK; } // launch_render never starts more than 8 blocks per CU
-constexpr uint32_t kTapeProgramsLds = 128; // prepared programs kept in LDS for the replay (4 KB); scenes with more use the HBM records
-static uint32_t tape_programs_in_lds(const DevScene& scene) { return scene.num_programs <= kTapeProgramsLds ? scene.num_programs : 0u; }
-// Interpreter scenes record a tape when their colour programs allow it (DevScene::hit_tape) and there are wavelengths to share a
-// hit's work among: with one or two per sample the online form wins (diamonds.lua, one wavelength, 256 bounces: 538 against 486).
-bool uses_hit_tape(const DevScene& scene, const RenderLaunch& launch) {
-    static const char* const least = std::getenv("PYRITE_HIT_TAPE_WAVELENGTHS"); // development: the fewest wavelengths per sample a hit tape is recorded for
-    return scene.needs_interpreter != 0 && scene.hit_tape != 0 && launch.spectrum_samples >= (least && *least ? (uint32_t)std::strtoul(least, nullptr, 10) : 4u);
-}
-static bool uses_tape(const DevScene& scene, const RenderLaunch& launch) {
-    return launch.scheduler == 1 && (scene.needs_interpreter == 0 || uses_hit_tape(scene, launch));
-}
-static size_t render_lds_bytes(const DevScene& scene, const RenderLaunch& launch) {
-    const size_t spectral_rows = uses_tape(scene, launch) ? launch.spectrum_samples + 1 + scene.tape_value_rows : 3 * launch.spectrum_samples;
-    size_t bytes = (spectral_rows + launch.stack_lds) * BLOCK * sizeof(float);
-    if (scene_fits_lds(scene)) bytes += (size_t)scene.num_nodes * 64 + (size_t)scene.num_prims * 48;
-    bytes += (size_t)scene.lds_table_floats * sizeof(float);
-    if (uses_tape(scene, launch)) bytes += ((size_t)tape_programs_in_lds(scene) * 8 + kTapeMaxValueRows) * sizeof(uint32_t);
-    return bytes;
-}
-
-#endif // PYR_TU_MAIN
-
-using RenderKernel = void (*)(DevScene, RenderLaunch);
-// A scene staged in LDS never has its tables staged too (api.cpp: lds_table_floats is only set for scenes that do not live in
-// LDS), so that combination is never instantiated.
-#if PYR_TU_PRODUCT
-// The hit-tape interpreter builds for scenes with TAPE_FORM_PRODUCT colour programs: builds of their own (Walker::tape_pending says why)
-RenderKernel pick_product_kernel(bool with_counters, bool lds_scene, bool lds_tables) {
-    auto pick = [&](auto counters) -> RenderKernel {
-        constexpr bool C = decltype(counters)::value;
-        if (lds_scene) return render_kernel_sm<C, true, true, false, true, true>;
-        return lds_tables ? render_kernel_sm<C, true, false, true, true, true> : render_kernel_sm<C, true, false, false, true, true>;
-    };
-    return with_counters ? pick(std::true_type{}) : pick(std::false_type{});
-}
-#else
-RenderKernel pick_product_kernel(bool with_counters, bool lds_scene, bool lds_tables);
-#endif
-#if PYR_TU_INTERP
-// The interpreter builds of the stage scheduler (the synchronous walk is built without the interpreter: a scene with interpreter
-// programs always runs on the stage scheduler, which keeps the interpreter in line). HIT_TAPE: see device_scene.h TapeForm.
-RenderKernel pick_interp_kernel(bool with_counters, bool lds_scene, bool lds_tables, bool hit_tape, bool product) {
-    auto pick = [&](auto counters) -> RenderKernel {
-        constexpr bool C = decltype(counters)::value;
-        if (hit_tape && product) return pick_product_kernel(C, lds_scene, lds_tables);
-        if (lds_scene) return hit_tape ? render_kernel_sm<C, true, true, false, true> : render_kernel_sm<C, true, true, false>;
-        if (hit_tape) return lds_tables ? render_kernel_sm<C, true, false, true, true> : render_kernel_sm<C, true, false, false, true>;
-        return lds_tables ? render_kernel_sm<C, true, false, true> : render_kernel_sm<C, true, false, false>;
-    };
-    return with_counters ? pick(std::true_type{}) : pick(std::false_type{});
-}
-#else
-RenderKernel pick_interp_kernel(bool with_counters, bool lds_scene, bool lds_tables, bool hit_tape, bool product);
-#endif
-
-#if !PYR_TU_WIDE
-// The wide interpreter build (defined at the end of this file in the -DPYR_TU=3 unit; nullptr in the one-unit builds).
-RenderKernel pick_wide_kernel(bool with_counters, bool lds_scene, bool lds_tables);
-#endif
-
-#if PYR_TU_MAIN
-static RenderKernel pick_kernel(bool sm, bool with_counters, bool interp, bool lds_scene, bool lds_tables, bool hit_tape, bool product, bool wide_vm) {
-#ifdef PYR_DEV_ONLY_SM // developer builds for reading the ISA (tools/asm_sm.sh): only the kernel the BASELINE meshes run is instantiated
-    return render_kernel_sm<false, false, false, true>;
-#endif
-#ifdef PYR_DEV_ONLY_SM_INTERP // ... or only the interpreter build the reference's textures example runs
-    return render_kernel_sm<false, true, true, false, true>;
-#endif
-    if (interp && wide_vm) return pick_wide_kernel(with_counters, lds_scene, lds_tables);
-    if (interp) return pick_interp_kernel(with_counters, lds_scene, lds_tables, hit_tape, product);
-    auto pick = [&](auto counters) -> RenderKernel {
-        constexpr bool C = decltype(counters)::value;
-        if (lds_scene) return sm ? render_kernel_sm<C, false, true, false> : render_kernel<C, false, true, false>;
-        if (sm) return lds_tables ? render_kernel_sm<C, false, false, true> : render_kernel_sm<C, false, false, false>;
-        return lds_tables ? render_kernel<C, false, false, true> : render_kernel<C, false, false, false>;
-    };
-    return with_counters ? pick(std::true_type{}) : pick(std::false_type{});
-}
-
-bool scene_is_lds_resident(const DevScene& scene) { return scene_fits_lds(scene); }
-
-int launch_render(const DevScene& scene, const RenderLaunch& launch_in, bool with_counters, void* stream, int num_cus, bool wide_vm) {
-    if (scene.stack_depth > kMaxStackDepth) {
-        g_kernel_error = "BVH deeper than kMaxStackDepth";
-        return PYR_ERR_UNSUPPORTED;
-    }
-    if (wide_vm && (launch_in.scheduler != 1 || scene.needs_interpreter == 0 || uses_tape(scene, launch_in))) {
-        g_kernel_error = "the wide interpreter build runs the stage scheduler's online form only";
-        return PYR_ERR_INVALID_ARGUMENT;
-    }
-    RenderLaunch launch = launch_in;
-    launch.stack_lds = 0;
-    launch.tape_programs_lds = uses_tape(scene, launch) ? tape_programs_in_lds(scene) : 0u;
-    // the stage-scheduled kernels are built for 4 waves per SIMD (__launch_bounds__(BLOCK, 4))
-    launch.tape_programs_lds = uses_tape(scene, launch) ? tape_programs_in_lds(scene) : 0u;
-    launch.stack_lds = launch.scheduler == 1 ? short_stack_levels(scene, render_lds_bytes(scene, launch), (uint32_t)sm_waves(scene.needs_interpreter != 0, scene_fits_lds(scene), uses_hit_tape(scene, launch)))
-                                             : scene.stack_depth;
-    // a scene staged in LDS is a few dozen nodes: its whole stack is kept in LDS (the kernels built for such scenes have no
-    // scratch part: TravStack::deep is one entry), whatever the budget or PYRITE_LDS_STACK say; the 160 KB check below applies
-    if (scene_fits_lds(scene)) launch.stack_lds = std::max(launch.stack_lds, scene.stack_depth);
-    const size_t lds = render_lds_bytes(scene, launch);
-    if (lds > 160 * 1024) {
-        g_kernel_error = "spectrum_samples + BVH depth need more than 160 KB of LDS per workgroup";
-        return PYR_ERR_UNSUPPORTED;
-    }
-    const uint32_t chunks = launch.chunk_end - launch.chunk_begin;
-    if (chunks == 0) return PYR_OK;
-    RenderKernel kernel = pick_kernel(launch.scheduler == 1, with_counters, scene.needs_interpreter != 0, scene_fits_lds(scene), scene.lds_table_floats != 0,
-                                      launch.scheduler == 1 && uses_hit_tape(scene, launch), scene.product_records != 0, wide_vm);
-    if (kernel == nullptr) {
-        g_kernel_error = "a program of this scene needs the wide interpreter build, which this one-unit build of the kernels does not hold";
-        return PYR_ERR_UNSUPPORTED;
-    }
-    hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (err != hipSuccess) {
-        g_kernel_error = std::string("hipFuncSetAttribute: ") + hipGetErrorString(err);
-        return PYR_ERR_DEVICE;
-    }
-    // Residency of a 256-thread block (one wave per SIMD): waves per SIMD allowed by the 512-entry register file
-    // (8-register granules, MI355X_MICROARCH.md "Register files") and by the 160 KB of LDS. The grid is persistent but needs
-    // no co-residency (no inter-block hand-off), so an over-estimate only queues blocks.
-    hipFuncAttributes attr{};
-    int blocks_per_cu = 4;
-    if (hipFuncGetAttributes(&attr, reinterpret_cast<const void*>(kernel)) == hipSuccess && attr.numRegs > 0) {
-        int regs = ((attr.numRegs + 7) / 8) * 8;
-        blocks_per_cu = std::min(8, 512 / regs);
-    }
-    blocks_per_cu = std::max(1, std::min<int>(blocks_per_cu, (int)((160 * 1024) / std::max<size_t>(lds, 1))));
-    uint32_t grid = (uint32_t)num_cus * (uint32_t)blocks_per_cu;
-    const uint32_t path_waves = BLOCK / 64; // waves of a workgroup that take chunks
-    uint32_t blocks_needed = (chunks + path_waves - 1) / path_waves;
-    if (grid > blocks_needed) grid = blocks_needed;
-    if (uses_tape(scene, launch) && (launch.tape == nullptr || (size_t)grid * BLOCK > launch.tape_lanes || launch.tape_max_ops < tape_ops_bound(scene, launch))) {
-        g_kernel_error = "the spectral tape is missing or too small for this launch";
-        return PYR_ERR_INVALID_ARGUMENT;
-    }
-    if (const char* cut = std::getenv("PYRITE_TEST_TAPE_OPS")) // test switch: pretend the bound were smaller, to see the overflow word work
-        if (uses_tape(scene, launch) && *cut) launch.tape_max_ops = std::min<uint32_t>(launch.tape_max_ops, (uint32_t)std::strtoul(cut, nullptr, 10));
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), lds, (hipStream_t)stream, scene, launch);
-    err = hipGetLastError();
-    if (err != hipSuccess) {
-        g_kernel_error = std::string("render kernel launch: ") + hipGetErrorString(err);
-        return PYR_ERR_DEVICE;
-    }
-    return PYR_OK;
-}
-
-int launch_intersect(const DevScene& scene, const IntersectLaunch& launch, bool with_counters, void* stream) {
-    if (launch.n == 0) return PYR_OK;
-    if (scene.stack_depth > kMaxStackDepth) {
-        g_kernel_error = "BVH deeper than kMaxStackDepth";
-        return PYR_ERR_UNSUPPORTED;
-    }
-    const uint32_t stack_lds = short_stack_levels(scene, 0, 8);
-    const size_t lds = (size_t)stack_lds * BLOCK * sizeof(int);
-    auto kernel = with_counters ? intersect_kernel<true> : intersect_kernel<false>;
-    hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (err != hipSuccess) {
-        g_kernel_error = std::string("hipFuncSetAttribute: ") + hipGetErrorString(err);
-        return PYR_ERR_DEVICE;
-    }
-    // persistent grid: as many workgroups as the registers and the LDS stack let a CU hold (no co-residency is required)
-    int blocks_per_cu = std::max(1, std::min<int>(8, (int)((160 * 1024) / std::max<size_t>(lds, 1))));
-    uint32_t grid = (uint32_t)launch.num_cus * (uint32_t)blocks_per_cu;
-    uint32_t needed = (launch.n + BLOCK - 1) / BLOCK;
-    if (grid > needed) grid = needed;
-    IntersectLaunch sized = launch;
-    sized.stack_lds = stack_lds;
-    // reservation per atomic: about a quarter of a wave's share of the batch, a multiple of 64, at most 2048
-    const uint32_t waves = grid * (BLOCK / 64);
-    sized.reserve = std::max<uint32_t>(64, std::min<uint32_t>(2048, (launch.n / std::max<uint32_t>(waves * 4, 1)) & ~63u));
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), lds, (hipStream_t)stream, scene, sized);
-    err = hipGetLastError();
-    if (err != hipSuccess) {
-        g_kernel_error = std::string("intersect kernel launch: ") + hipGetErrorString(err);
-        return PYR_ERR_DEVICE;
-    }
-    return PYR_OK;
-}
-
-#endif // PYR_TU_MAIN
-
-#if PYR_TU_WIDE
+#ifdef PYR_WIDE_VM
 } // namespace wide
-
-// The wide interpreter build: the three layouts of the online form, with and without counters. Waves per SIMD as every interpreter
-// build (sm_waves); the register files live in scratch.
-wide::RenderKernel pick_wide_kernel(bool with_counters, bool lds_scene, bool lds_tables) {
-    auto pick = [&](auto counters) -> wide::RenderKernel {
-        constexpr bool C = decltype(counters)::value;
-        if (lds_scene) return wide::render_kernel_sm<C, true, true, false>;
-        return lds_tables ? wide::render_kernel_sm<C, true, false, true> : wide::render_kernel_sm<C, true, false, false>;
-    };
-    return with_counters ? pick(std::true_type{}) : pick(std::false_type{});
-}
-#elif PYR_TU == -1
-RenderKernel pick_wide_kernel(bool, bool, bool) { return nullptr; }
 #endif
-
 } // namespace pyr
 
-#if defined(PYR_PHASE_PROFILE) && PYR_TU_MAIN
-extern "C" int pyr_debug_phase_profile32(unsigned long long* out32, int reset) {
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(out32, HIP_SYMBOL(pyr::g_phase_prof), 32 * sizeof(unsigned long long)) != hipSuccess) return -1;
-    if (reset) {
-        unsigned long long zero[32] = {};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(pyr::g_phase_prof), zero, sizeof(zero)) != hipSuccess) return -1;
-    }
-    return 0;
-}
-extern "C" int pyr_debug_phase_profile(unsigned long long* out16, int reset) {
-    if (hipDeviceSynchronize() != hipSuccess) return -1;
-    if (hipMemcpyFromSymbol(out16, HIP_SYMBOL(pyr::g_phase_prof), 16 * sizeof(unsigned long long)) != hipSuccess) return -1;
-    if (reset) {
-        unsigned long long zero[16] = {};
-        if (hipMemcpyToSymbol(HIP_SYMBOL(pyr::g_phase_prof), zero, sizeof(zero)) != hipSuccess) return -1;
-    }
-    return 0;
-}
 #endif

@@ -18,7 +18,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_the_baseline_kernel_keeps_its_registers(tmp_path):
     flags = [f for f in build.FLAGS if f not in ("-shared", "-fPIC")]
     out = tmp_path / "sm.s"
-    subprocess.check_call([build.HIPCC] + flags + ["--cuda-device-only", "-DPYR_DEV_ONLY_SM", "-S", "kernels.hip", "-o", str(out)], cwd=build.CSRC,
+    subprocess.check_call([build.HIPCC] + flags + ["--cuda-device-only", "-S", "kernels/main.hip", "-o", str(out)], cwd=build.CSRC,
                           stderr=subprocess.DEVNULL)
     text = out.read_text()
     start = re.search(r"^_ZN3pyr16render_kernel_smILb0ELb0ELb0ELb1E\w*:", text, re.M)

@@ -537,7 +537,7 @@ WIDE_SCRATCH = {  # render_kernel_sm<COUNT, true, LDS_SCENE, LDS_TABLES>: bytes 
 def test_the_wide_build_keeps_its_resources(tmp_path):
     flags = [f for f in gpu_build.FLAGS if f not in ("-shared", "-fPIC")]
     out = tmp_path / "wide.s"
-    subprocess.check_call([gpu_build.HIPCC] + flags + ["--cuda-device-only", "-DPYR_TU=3", "-S", "kernels.hip", "-o", str(out)], cwd=gpu_build.CSRC,
+    subprocess.check_call([gpu_build.HIPCC] + flags + ["--cuda-device-only", "-S", "kernels/wide.hip", "-o", str(out)], cwd=gpu_build.CSRC,
                           stderr=subprocess.DEVNULL)
     text = out.read_text()
     kernels = re.findall(r"^\s*\.amdhsa_kernel (\S+)", text, re.M)

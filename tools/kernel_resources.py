@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Developer tool: registers / scratch / occupancy of every kernel in kernels.hip, from hipcc's
+"""Developer tool: registers / scratch / occupancy of every kernel of the four units under csrc/kernels/, from hipcc's
 -Rpass-analysis=kernel-resource-usage remarks.   python tools/kernel_resources.py [extra -D flags]"""
 import os
 import re
@@ -11,8 +11,10 @@ sys.path.insert(0, ROOT)
 from pyrite_amd import build  # noqa: E402
 
 flags = [f for f in build.FLAGS if f != "-shared"] + sys.argv[1:]
-cmd = [build.HIPCC] + flags + ["-Rpass-analysis=kernel-resource-usage", "-c", "kernels.hip", "-o", "/dev/null"]
-text = subprocess.run(cmd, cwd=build.CSRC, capture_output=True, text=True).stderr
+text = ""
+for unit in build.KERNEL_UNITS:
+    cmd = [build.HIPCC] + flags + ["-Rpass-analysis=kernel-resource-usage", "-c", os.path.join("kernels", unit), "-o", "/dev/null"]
+    text += subprocess.run(cmd, cwd=build.CSRC, capture_output=True, text=True).stderr
 for block in re.split(r"remark: Function Name: ", text)[1:]:
     name = block.split(" ")[0]
 
