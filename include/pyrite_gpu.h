@@ -32,12 +32,13 @@
 extern "C" {
 #endif
 
-#define PYR_ABI_VERSION 4
+#define PYR_ABI_VERSION 5
 
 typedef enum PyrStatus {
     PYR_OK = 0,
     PYR_ERR_INVALID_ARGUMENT = -1,
-    PYR_ERR_UNSUPPORTED = -2, /* texture / normal-map opcodes, ray-marched shapes: SURVEY.md section 8 "out" rows */
+    PYR_ERR_UNSUPPORTED = -2, /* outside what the library renders: ray-marched shapes (SURVEY.md section 8 "out" rows), a program beyond the
+                                 wide register file, sizes beyond the bounds stated at pyr_scene_create */
     PYR_ERR_DEVICE = -3,      /* a HIP call failed or no gfx950 device is present */
     PYR_ERR_OUT_OF_MEMORY = -4
 } PyrStatus;
@@ -78,6 +79,12 @@ typedef struct PyrFilmDesc {
  * Tiles are independent units in the reference too: each has its own RNG and writes its own pixels
  * (renderer/simple.rs:36-55).
  *
+ * Sample windows (ABI 5): a tile of w x h pixels (clipped to the image) runs w*h*pixel_samples iterations of the simple.rs:78 loop;
+ * with sample_begin = b the call runs the iterations [w*h*b, w*h*(b + pixel_samples)) of every tile instead of the first
+ * w*h*pixel_samples. The RNG key stays (seed, tile, iteration), so the windows [0,n), [n,2n), ... of k calls are together exactly the
+ * samples of one call with k*n samples per pixel: added into one film they give that call's film up to the order of the float
+ * additions. sample_begin = 0 is a plain render. A window whose end a single call could not reach (2^32 chunks) is PYR_ERR_UNSUPPORTED.
+ *
  * film_layout says what the film buffer handed to the call holds:
  *   PYR_FILM_ROWS         pixel rows [film_row_begin, film_row_begin + film_row_count) of the image in the film.rs:56 layout
  *                         (film_row_count == 0 means the whole image);
@@ -105,6 +112,7 @@ typedef struct PyrRenderParams {
     uint32_t film_row_count;
     uint32_t tile_stride; /* 0 and 1 both mean every tile of the range */
     uint32_t film_layout; /* PYR_FILM_ROWS | PYR_FILM_TILE_BLOCKS */
+    uint32_t sample_begin; /* ABI 5: the call renders samples [sample_begin, sample_begin + pixel_samples) of every pixel's budget */
 } PyrRenderParams;
 
 /* == Camera::Perspective {transform, view_plane, focus_distance, aperture}: cameras.rs:20-27.
@@ -373,7 +381,8 @@ int pyr_render_simple(PyrScene* scene, const PyrCamera* camera, const PyrFilmDes
 /* Same, but `film_device` is DEVICE memory on the scene's device and the work is enqueued on `hip_stream`
  * (a hipStream_t, NULL = default stream) without synchronising: the caller synchronises the stream.
  * A PyrScene owns device-side working memory (counters, the spectral tape) that serves one render at a
- * time: renders of ONE scene must be issued on one stream (or otherwise ordered); different scenes are independent. */
+ * time: renders of ONE scene must be issued on one stream (or otherwise ordered); different scenes are independent. A scene serves
+ * one PyrSession or one plain render at a time (see "progressive sessions"). */
 int pyr_render_simple_device(PyrScene* scene, const PyrCamera* camera, const PyrFilmDesc* film,
                              const PyrRenderParams* params, PyrGrain* film_device, void* hip_stream);
 
@@ -542,6 +551,68 @@ int pyr_film_develop(const PyrFilmDesc* film, const PyrGrain* grains, const PyrD
  * call); enqueued on `hip_stream`. */
 int pyr_film_develop_device(const PyrFilmDesc* film, const PyrGrain* grains_device, const PyrDevelopParams* params, uint8_t* rgb_device,
                             int device, void* hip_stream);
+
+/* ---------------------------------------------------------------- progressive sessions (ABI 5) ----------------
+ * main.rs:243-305 renders while a status closure rewrites a preview image from the live film every 20 s or more
+ * (main.rs:261-299, developed with step_size = 30). pyr_render_simple is one call whose film is valid when it returns; a
+ * PyrSession is the same render cut into passes: pass j renders the sample window [done, done + n) of every pixel's budget
+ * (PyrRenderParams::sample_begin), so every pass covers the whole image and after the last one the film is the one-shot film up to
+ * the order of the float additions. The session owns the film ON THE SCENE'S DEVICE, a stream of its own, the camera, the film
+ * description and the renderer parameters; a preview develops the film there and brings only width*height*3 bytes to the host.
+ *   A PyrScene serves ONE session or ONE plain render at a time (its working memory is one render's): do not render the
+ * scene by other means, or through a second session, between a session's first pyr_session_render and the pyr_session_sync (or
+ * preview / film / noise call, which all wait) that follows its last. The scene must outlive the session. One GPU: the
+ * multi-GPU entries have no session form.
+ *   PYR_SESSION_HALVES keeps two films A and B: pass number j (from 0) exposes into A when j is even and into B when j is odd. The
+ * film of the session is then A + B (accs added, weights added), and pyr_session_noise compares the two. */
+#define PYR_SESSION_HALVES 1u
+typedef struct PyrSession PyrSession;
+
+/* `params->pixel_samples` is the whole budget; sample_begin must be 0, the film layout PYR_FILM_ROWS over the whole image, flags
+ * without PYR_FLAG_COUNTERS. The film starts zeroed; if `film_host` (HOST, height*width*bins grains) is not NULL it is uploaded and
+ * the session adds to it (into A when there are halves). Blocking. */
+int pyr_session_create(PyrScene* scene, const PyrCamera* camera, const PyrFilmDesc* film, const PyrRenderParams* params, uint32_t flags,
+                       const PyrGrain* film_host, PyrSession** out_session);
+/* Waits for the session's stream first. NULL is a no-op. */
+void pyr_session_destroy(PyrSession* session);
+/* Enqueues one pass -- the next `samples` (> 0) samples of every pixel, clipped to the budget -- on the session's stream and
+ * returns without waiting. PYR_OK and nothing done when the budget is spent. */
+int pyr_session_render(PyrSession* session, uint32_t samples);
+/* Waits for every pass enqueued so far; reports, as pyr_render_simple does, a render that flagged its own film invalid. */
+int pyr_session_sync(PyrSession* session);
+/* Samples per pixel of the passes enqueued so far (never more than the budget). */
+int pyr_session_samples_done(PyrSession* session, uint32_t* out_samples);
+/* The film as it stands after every pass enqueued so far, developed on the device (pyr_film_develop's arithmetic and bytes; with
+ * halves, of A + B): rgb_out = HOST, height*width*3 bytes. Blocking; the film itself does not cross the bus. */
+int pyr_session_preview(PyrSession* session, const PyrDevelopParams* develop_params, uint8_t* rgb_out);
+/* The film after every pass enqueued so far, in the film.rs:56 layout (A + B with halves): HOST / DEVICE memory (the scene's
+ * device) of height*width*bins grains. Both block. */
+int pyr_session_film(PyrSession* session, PyrGrain* film_out);
+int pyr_session_film_device(PyrSession* session, PyrGrain* film_out_device);
+/* The two half films (PYR_SESSION_HALVES only), HOST memory of height*width*bins grains each. Blocking. */
+int pyr_session_halves(PyrSession* session, PyrGrain* film_a_out, PyrGrain* film_b_out);
+/* Noise estimate per tile of the make_tiles grid (renderer/algorithm.rs:152-188), raster order: out_per_tile = HOST,
+ * tiles_x*tiles_y floats. Needs PYR_SESSION_HALVES and at least two passes (else PYR_ERR_INVALID_ARGUMENT). With a, b the f32
+ * quotients acc/weight of a grain in A and in B (0 where the weight is 0), over every (pixel, bin) of the tile and summed in f64:
+ *     value = sqrt( sum (a - b)^2 / sum ((a + b)/2)^2 ),   0 when the denominator is 0.
+ * It is the relative RMS difference of the two halves. HALF of it estimates the relative error of the summed film: the
+ * difference of two independent halves has four times the variance of their mean. It weighs every grain alike, so paths that
+ * dispersed (one wavelength per sample) and paths that did not (every wavelength of the sample) count alike, and it is only
+ * as good as the halves are equal: render passes of one size, an even number of them. A film passed to pyr_session_create
+ * sits in A alone and counts as difference. Deterministic: no atomics, the same bits on every call. Nothing here stops a
+ * render by this number. Blocking. */
+int pyr_session_noise(PyrSession* session, float* out_per_tile);
+
+/* The drop-in for main.rs:243-305, blocking: renders `params->pixel_samples` samples per pixel in passes of `pass_samples`,
+ * calls `on_status` (may be NULL) after every pass with percent = samples_done*100/budget, and -- when `on_preview` is not NULL --
+ * develops the film with `preview_develop_params` after a pass once `preview_min_interval_s` seconds (>= 0; main.rs:261 uses 20)
+ * have gone by since the last preview (since the start, for the first), and hands it over: rgb = height*width*3 bytes, valid
+ * during the callback only. Both callbacks run on the calling thread. At the end `film_inout` (HOST) holds what it held
+ * plus the render's exposures, as with pyr_render_simple. */
+typedef void (*PyrPreviewFn)(void* user, const uint8_t* rgb, uint32_t width, uint32_t height, uint32_t samples_done);
+int pyr_render_simple_progressive(PyrScene* scene, const PyrCamera* camera, const PyrFilmDesc* film, const PyrRenderParams* params,
+                                  PyrGrain* film_inout, uint32_t pass_samples, PyrProgressFn on_status, PyrPreviewFn on_preview,
+                                  double preview_min_interval_s, const PyrDevelopParams* preview_develop_params, void* user);
 
 #ifdef __cplusplus
 }

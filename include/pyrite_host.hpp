@@ -305,7 +305,39 @@ class Renderer { // renderer/mod.rs:18-28, Algorithm::Simple
     // devices[0]. What the reference does with its worker threads (renderer/mod.rs:125-189) a host does with its GPUs.
     // A device listed twice is the one-GPU test rig (pyrite_gpu.h).
     void render(Film& film, const Camera& camera, World& world, const std::vector<int>& devices, const std::function<void(Progress)>& on_status = nullptr) const;
+    PyrRenderParams params(uint32_t sample_begin = 0) const; // this renderer as the ABI's parameter block
 };
+
+// A render cut into passes over the whole image (pyrite_gpu.h "progressive sessions"): the film lives on the GPU, render()
+// enqueues the next samples of every pixel and returns at once, preview() develops the live film there and fetches the 8-bit image
+// alone. The world's scene on that device serves this session alone while it renders. pyrite_amd/renderer.py Session is the same.
+class Session {
+  public:
+    Session(const Renderer& renderer, uint32_t width, uint32_t height, const Camera& camera, World& world, bool halves = false, int device = 0,
+            const Film* start = nullptr);
+    ~Session();
+    Session(const Session&) = delete;
+    Session& operator=(const Session&) = delete;
+    void render(uint32_t samples);
+    void sync();
+    uint32_t samples_done() const;
+    // main.rs:261-299: [height][width][3] sRGB of the film as it stands, with the image's filter / white programs
+    std::vector<uint8_t> preview(float step_size = 30.0f, const std::optional<Expression>& filter = std::nullopt, const std::optional<Expression>& white = std::nullopt);
+    Film film();
+    std::vector<float> noise(); // per tile of the make_tiles grid, raster order (pyr_session_noise): needs halves and two passes
+    uint32_t tiles_x() const { return (width_ + tile_size_ - 1) / tile_size_; }
+    uint32_t tiles_y() const { return (height_ + tile_size_ - 1) / tile_size_; }
+
+  private:
+    PyrSession* handle_ = nullptr;
+    Film shape_; // the film's description (no grains are kept here)
+    uint32_t width_, height_, tile_size_;
+};
+
+// What is wrong with the flags of a progressive render (--pass-samples, --preview-every, --noise without --preview), in the words
+// both front ends print, or "" (pyrite_amd/__main__.py progressive_flag_problem).
+std::string progressive_flag_problem(const std::optional<long>& pass_samples, bool preview, double preview_every, bool noise);
+constexpr uint32_t kDefaultPassSamples = 256; // passes of a render with a preview when --pass-samples is not given: the smallest that cost nothing on C3
 
 // ------------------------------------------------------------------------------------------------ project files
 // Reads a project file (*.lua): the declarative subset of Lua project files are written in, evaluated against the prelude

@@ -2,11 +2,55 @@
 (pyrite/src/main.rs:46-330): load the project file, render it on the GPU, develop the film with the project's `image.filter`
 / `image.white`, and write `render.png` next to the project file (main.rs:180-184).
 
-    python -m pyrite_amd path/to/project.lua [-o out.png] [--seed N] [--device D] [--spp N] [--size WxH]"""
+    python -m pyrite_amd path/to/project.lua [-o out.png] [--seed N] [--device D] [--spp N] [--size WxH]
+                         [--pass-samples N] [--preview PATH] [--preview-every SECONDS] [--noise]
+
+With --pass-samples, --preview or --noise the render runs as a progressive session (pyr_session_*): passes of N samples per pixel
+over the whole image, the preview image rewritten from the live film every SECONDS or more (main.rs:261-299; developed on the GPU
+with step 30, main.rs:270), and with --noise the largest and the median per-tile noise estimate printed after each preview. The
+final image is the one the plain render writes."""
 import argparse
 import os
 import sys
 import time
+
+
+DEFAULT_PASS_SAMPLES = 256  # passes of a render with a preview when --pass-samples is not given: the smallest that cost nothing on C3 (DESIGN.md section 9a)
+
+
+def progressive_flag_problem(pass_samples, preview, preview_every, noise):
+    """What is wrong with the progressive flags, in the words pyrite_host_tool uses too, or None."""
+    if pass_samples is not None and pass_samples < 1:
+        return "--pass-samples must be at least 1"
+    if not preview_every >= 0:
+        return "--preview-every must not be negative"
+    if noise and not preview:
+        return "--noise needs --preview"
+    return None
+
+
+def render_progressive(r, cam, world, film, args, image, on_status):
+    """The render as a session: passes, previews, noise. Returns the final host Film."""
+    import numpy as np
+
+    from .develop import save_png
+
+    pass_samples = args.pass_samples or DEFAULT_PASS_SAMPLES
+    with r.session((film.width, film.height), cam, world, halves=args.noise, device=args.device) as s:
+        on_status(0, "Rendering")
+        last_image = time.monotonic()  # main.rs:241
+        while s.samples_done < r.pixel_samples:
+            s.render(pass_samples)
+            s.sync()
+            on_status(s.samples_done * 100 // r.pixel_samples, "Rendering")
+            if args.preview and time.monotonic() - last_image >= args.preview_every:
+                save_png(args.preview, s.preview(30.0, filter=image.get("filter"), white=image.get("white")))
+                print("\nPreview updated (%d samples per pixel)" % s.samples_done)
+                if args.noise and s.samples_done >= 2 * pass_samples:
+                    noise = s.noise()
+                    print("noise: largest tile %.4g, median tile %.4g" % (float(noise.max()), float(np.median(noise))))
+                last_image = time.monotonic()
+        return s.film()
 
 
 def main(argv=None):
@@ -17,7 +61,15 @@ def main(argv=None):
     ap.add_argument("--device", type=int, default=0)
     ap.add_argument("--spp", type=int, default=None, help="override renderer.pixel_samples")
     ap.add_argument("--size", default=None, help="override image size, WIDTHxHEIGHT")
+    ap.add_argument("--pass-samples", type=int, default=None, help="render in passes of N samples per pixel (default with --preview: %d)" % DEFAULT_PASS_SAMPLES)
+    ap.add_argument("--preview", default=None, metavar="PATH", help="image to rewrite from the live film while rendering")
+    ap.add_argument("--preview-every", type=float, default=20.0, metavar="SECONDS", help="least time between two previews (default 20, main.rs:262)")
+    ap.add_argument("--noise", action="store_true", help="print the largest and median per-tile noise estimate after each preview")
     args = ap.parse_args(argv)
+    problem = progressive_flag_problem(args.pass_samples, args.preview, args.preview_every, args.noise)
+    if problem:
+        print("error: " + problem, file=sys.stderr)
+        return 2
 
     from . import lua_project, scenes
     from .develop import develop, save_png
@@ -36,10 +88,13 @@ def main(argv=None):
         print("\r%s... %3d %%" % (message, percent), end="", flush=True)
 
     t = time.time()
-    r.render(film, cam, world, on_status=on_status, device=args.device)
+    image = project.get("image") or {}
+    if args.pass_samples is not None or args.preview or args.noise:
+        film = render_progressive(r, cam, world, film, args, image, on_status)
+    else:
+        r.render(film, cam, world, on_status=on_status, device=args.device)
     print("\rRendering... done in %.2f s (%.1f Msamples/s)" % (time.time() - t, film.width * film.height * r.pixel_samples / (time.time() - t) / 1e6))
     print("Saving final result...")  # main.rs:313
-    image = project.get("image") or {}
     rgb = develop(film, filter=image.get("filter"), white=image.get("white"), device=args.device)
     out = args.output or os.path.join(base_dir, "render.png")
     save_png(out, rgb)

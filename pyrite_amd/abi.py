@@ -2,7 +2,7 @@
 tests/test_abi.py checks sizes and that every declared symbol is exported."""
 import ctypes as C
 
-PYR_ABI_VERSION = 4
+PYR_ABI_VERSION = 5
 
 PYR_OK = 0
 PYR_ERR_INVALID_ARGUMENT = -1
@@ -12,6 +12,7 @@ PYR_ERR_OUT_OF_MEMORY = -4
 
 PYR_FLAG_COUNTERS = 1
 PYR_FILM_ROWS, PYR_FILM_TILE_BLOCKS = 0, 1
+PYR_SESSION_HALVES = 1
 PYR_COMM_ID_BYTES = 128
 
 # PyrOp
@@ -59,6 +60,7 @@ class PyrRenderParams(C.Structure):
         ("film_row_count", C.c_uint32),
         ("tile_stride", C.c_uint32),
         ("film_layout", C.c_uint32),
+        ("sample_begin", C.c_uint32),
     ]
 
 
@@ -267,6 +269,7 @@ class PyrDevelopParams(C.Structure):
 
 
 PyrProgressFn = C.CFUNCTYPE(None, C.c_void_p, C.c_uint8, C.c_char_p)
+PyrPreviewFn = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, C.c_uint32)
 
 # Every entry point include/pyrite_gpu.h declares: name -> (restype, argtypes)
 ENTRY_POINTS = {
@@ -307,6 +310,24 @@ ENTRY_POINTS = {
     ),
     "pyr_film_develop": (C.c_int, [C.POINTER(PyrFilmDesc), C.c_void_p, C.POINTER(PyrDevelopParams), C.c_void_p, C.c_int]),
     "pyr_film_develop_device": (C.c_int, [C.POINTER(PyrFilmDesc), C.c_void_p, C.POINTER(PyrDevelopParams), C.c_void_p, C.c_int, C.c_void_p]),
+    "pyr_session_create": (
+        C.c_int,
+        [C.c_void_p, C.POINTER(PyrCamera), C.POINTER(PyrFilmDesc), C.POINTER(PyrRenderParams), C.c_uint32, C.c_void_p, C.POINTER(C.c_void_p)],
+    ),
+    "pyr_session_destroy": (None, [C.c_void_p]),
+    "pyr_session_render": (C.c_int, [C.c_void_p, C.c_uint32]),
+    "pyr_session_sync": (C.c_int, [C.c_void_p]),
+    "pyr_session_samples_done": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32)]),
+    "pyr_session_preview": (C.c_int, [C.c_void_p, C.POINTER(PyrDevelopParams), C.c_void_p]),
+    "pyr_session_film": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pyr_session_film_device": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pyr_session_halves": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pyr_session_noise": (C.c_int, [C.c_void_p, C.c_void_p]),
+    "pyr_render_simple_progressive": (
+        C.c_int,
+        [C.c_void_p, C.POINTER(PyrCamera), C.POINTER(PyrFilmDesc), C.POINTER(PyrRenderParams), C.c_void_p, C.c_uint32, PyrProgressFn, PyrPreviewFn,
+         C.c_double, C.POINTER(PyrDevelopParams), C.c_void_p],
+    ),
 }
 
 

@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
+#include <chrono>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
@@ -814,6 +815,10 @@ int plan_tiles(const PyrFilmDesc* film, const PyrRenderParams* p, TilePlan& plan
     plan.tile_count = (uint32_t)((end - begin + plan.tile_stride - 1) / plan.tile_stride);
     const uint64_t per_tile = ((uint64_t)ts * ts * p->pixel_samples + 63) / 64; // iterations of a full tile: simple.rs:73
     if (per_tile * plan.tile_count >= 0xFFFFFFFFull) return fail(PYR_ERR_UNSUPPORTED, "too many samples for one call: more than 2^32 chunks");
+    // a window [sample_begin, sample_begin + pixel_samples) must end where a one-shot call of that many samples could: same bound
+    const uint64_t window_end = (uint64_t)p->sample_begin + p->pixel_samples;
+    if (p->sample_begin != 0 && (window_end > 0xFFFFFFFFull || (((uint64_t)ts * ts * window_end + 63) / 64) * plan.tile_count >= 0xFFFFFFFFull))
+        return fail(PYR_ERR_UNSUPPORTED, "sample window ends beyond what one call can render: more than 2^32 chunks");
     plan.chunks_per_tile = (uint32_t)std::max<uint64_t>(per_tile, 1); // pixel_samples == 0: no chunk at all
     plan.chunk_begin = 0;
     plan.chunk_end = (uint32_t)(per_tile * plan.tile_count);
@@ -939,6 +944,7 @@ RenderLaunch make_launch(const PyrCamera* camera, const PyrFilmDesc* film, const
     L.spectrum_samples = p->spectrum_samples;
     L.tile_size = p->tile_size;
     L.pixel_samples = p->pixel_samples;
+    L.sample_begin = p->sample_begin;
     L.tiles_x = plan.tiles_x;
     L.tiles_y = plan.tiles_y;
     L.tile_begin = plan.tile_begin;
@@ -1210,32 +1216,34 @@ int pyr_scene_intersect(PyrScene* scene, const float* rays, uint32_t n, PyrHit* 
     return PYR_OK;
 }
 
-static int develop_common(const PyrFilmDesc* film, const PyrGrain* grains_device, const PyrDevelopParams* p, uint8_t* rgb_device, hipStream_t stream,
-                          bool blocking) {
-    if (!(p->step_size > 0.0f) || p->sample_count == 0 || p->xyz_count < 2) return fail(PYR_ERR_INVALID_ARGUMENT, "bad development parameters");
-    if ((p->white_div == nullptr) != (p->white_mul == nullptr)) return fail(PYR_ERR_INVALID_ARGUMENT, "white_div and white_mul go together");
-    // the small per-wavelength tables are copied for the call (stream-ordered allocation, freed after the kernel)
+// Which develop kernel a launch runs. Both write the same bytes (tests/test_gpu_session.py); the choice is the measured one (DESIGN.md
+// section 9a, C3-sized film): develop_wave_kernel (kernels/film.hip: one wave per run of pixels, the whole film read in full lines) when
+// the trapezoid walk touches most bins -- step 2: 2.90 against 4.85 ms -- and develop_kernel (kernels/main.hip: one thread per pixel,
+// reads only the bins it samples) when it touches fewer than half of them -- step 30, 15 of 64 bins: 0.44 against 0.65 ms. Two half films
+// are developed by the wave kernel, which adds them as it reads; films of more bins than its LDS rows hold by develop_kernel.
+// PYRITE_DEVELOP_KERNEL=pixel|wave overrides (development: tools/bench_session.py times one against the other).
+static bool develop_uses_wave(const DevelopLaunch& D) {
+    if (!develop_wave_serves(D)) return false;
+    if (D.grains_b) return true;
+    const char* e = std::getenv("PYRITE_DEVELOP_KERNEL");
+    if (e && std::string(e) == "pixel") return false;
+    if (e && std::string(e) == "wave") return true;
+    return 2ull * D.sample_count > D.film.bins;
+}
+
+// The launch record of a development with the per-wavelength tables at `tables` (device: filter, white_div, white_mul -- sample_count
+// floats each -- then the observer table); `host` receives the same floats for the caller to copy there.
+static DevelopLaunch develop_launch(const PyrFilmDesc* film, const PyrDevelopParams* p, float* tables, std::vector<float>& host) {
     const size_t n = p->sample_count;
-    float* tables = nullptr;
-    const size_t floats = 3 * n + 3 * (size_t)p->xyz_count;
-    HIP_TRY(hipMallocAsync((void**)&tables, floats * sizeof(float), stream));
-    std::vector<float> host(floats, 0.0f);
+    host.assign(3 * n + 3 * (size_t)p->xyz_count, 0.0f);
     if (p->filter) std::memcpy(host.data(), p->filter, n * 4);
     if (p->white_div) {
         std::memcpy(host.data() + n, p->white_div, n * 4);
         std::memcpy(host.data() + 2 * n, p->white_mul, n * 4);
     }
     std::memcpy(host.data() + 3 * n, p->xyz_table, 3 * (size_t)p->xyz_count * 4);
-    {
-        const hipError_t copied = hipMemcpy(tables, host.data(), floats * sizeof(float), hipMemcpyHostToDevice); // synchronous: `host` dies with this frame
-        if (copied != hipSuccess) {
-            (void)hipFreeAsync(tables, stream);
-            return hip_fail(copied, "hipMemcpy(development tables)");
-        }
-    }
     DevelopLaunch D{};
     D.film = *film;
-    D.grains = grains_device;
     D.step_size = p->step_size;
     D.xyz_scale = p->xyz_scale;
     D.sample_count = p->sample_count;
@@ -1246,10 +1254,36 @@ static int develop_common(const PyrFilmDesc* film, const PyrGrain* grains_device
     D.xyz_count = p->xyz_count;
     D.xyz_min = p->xyz_min;
     D.xyz_max = p->xyz_max;
+    return D;
+}
+static int check_develop_params(const PyrDevelopParams* p) {
+    if (!(p->step_size > 0.0f) || p->sample_count == 0 || p->xyz_count < 2) return fail(PYR_ERR_INVALID_ARGUMENT, "bad development parameters");
+    if ((p->white_div == nullptr) != (p->white_mul == nullptr)) return fail(PYR_ERR_INVALID_ARGUMENT, "white_div and white_mul go together");
+    return PYR_OK;
+}
+
+static int develop_common(const PyrFilmDesc* film, const PyrGrain* grains_device, const PyrDevelopParams* p, uint8_t* rgb_device, hipStream_t stream,
+                          bool blocking) {
+    if (int bad = check_develop_params(p)) return bad;
+    // the small per-wavelength tables are copied for the call (stream-ordered allocation, freed after the kernel)
+    float* tables = nullptr;
+    const size_t floats = 3 * (size_t)p->sample_count + 3 * (size_t)p->xyz_count;
+    HIP_TRY(hipMallocAsync((void**)&tables, floats * sizeof(float), stream));
+    std::vector<float> host;
+    DevelopLaunch D = develop_launch(film, p, tables, host);
+    {
+        const hipError_t copied = hipMemcpy(tables, host.data(), floats * sizeof(float), hipMemcpyHostToDevice); // synchronous: `host` dies with this frame
+        if (copied != hipSuccess) {
+            (void)hipFreeAsync(tables, stream);
+            return hip_fail(copied, "hipMemcpy(development tables)");
+        }
+    }
+    D.grains = grains_device;
     D.rgb_out = rgb_device;
-    int rc = launch_develop(D, stream);
+    const bool wave = develop_uses_wave(D);
+    int rc = wave ? launch_develop_wave(D, stream) : launch_develop(D, stream);
     hipError_t e = hipFreeAsync(tables, stream);
-    if (rc != PYR_OK) return fail(rc, kernels_last_error());
+    if (rc != PYR_OK) return fail(rc, wave ? film_kernels_last_error() : kernels_last_error());
     if (e != hipSuccess) return hip_fail(e, "hipFreeAsync");
     if (blocking) HIP_TRY(hipStreamSynchronize(stream));
     return PYR_OK;
@@ -1301,6 +1335,268 @@ int pyr_scene_bvh_info(PyrScene* scene, PyrBvhInfo* out) {
     if (!scene || !out) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
     *out = scene->info;
     return PYR_OK;
+}
+
+
+// ------------------------------------------------------------------------------------------------ progressive sessions
+} // extern "C"
+
+struct PyrSession {
+    PyrScene* scene = nullptr;
+    PyrCamera camera{};
+    PyrFilmDesc film{};
+    PyrRenderParams params{}; // pixel_samples = the whole budget
+    bool halves = false;
+    hipStream_t stream = nullptr;
+    DeviceBuffer film_a, film_b, sum, rgb, tables, noise;
+    std::vector<float> host_tables;
+    size_t grains = 0;
+    uint32_t samples_done = 0, passes = 0;
+    uint32_t tiles_x = 0, tiles_y = 0;
+    ~PyrSession() {
+        if (stream) (void)hipStreamDestroy(stream);
+    }
+};
+
+namespace {
+
+int session_ready(PyrSession* s) {
+    if (!s) return fail(PYR_ERR_INVALID_ARGUMENT, "null session");
+    HIP_TRY(hipSetDevice(s->scene->device));
+    return PYR_OK;
+}
+
+// The film of the session on its device, valid in stream order: A, or A + B in the session's sum buffer.
+int session_film(PyrSession* s, const PyrGrain** out) {
+    *out = (const PyrGrain*)s->film_a.ptr;
+    if (!s->halves) return PYR_OK;
+    if (!s->sum.ptr) {
+        int rc = s->sum.alloc(s->grains * sizeof(PyrGrain));
+        if (rc != PYR_OK) return rc;
+    }
+    int rc = launch_film_sum((const PyrGrain*)s->film_a.ptr, (const PyrGrain*)s->film_b.ptr, (PyrGrain*)s->sum.ptr, s->grains, s->stream);
+    if (rc != PYR_OK) return fail(rc, film_kernels_last_error());
+    *out = (const PyrGrain*)s->sum.ptr;
+    return PYR_OK;
+}
+
+int session_sync(PyrSession* s) {
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    return check_tape_overflow(s->scene);
+}
+
+// What pyr_session_create and pyr_render_simple_progressive refuse before anything runs.
+int check_session_args(PyrScene* scene, const PyrCamera* camera, const PyrFilmDesc* film, const PyrRenderParams* p) {
+    if (!scene || !camera || !film || !p) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+    if (film->width == 0 || film->height == 0 || film->bins == 0 || p->tile_size == 0 || p->spectrum_samples == 0 || p->pixel_samples == 0)
+        return fail(PYR_ERR_INVALID_ARGUMENT, "zero-sized parameter");
+    if (p->sample_begin != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "a session starts its own sample windows: sample_begin must be 0");
+    if (p->film_layout != PYR_FILM_ROWS || p->film_row_begin != 0 || (p->film_row_count != 0 && p->film_row_count != film->height))
+        return fail(PYR_ERR_INVALID_ARGUMENT, "a session holds the whole image in the film.rs:56 layout");
+    if (p->flags & PYR_FLAG_COUNTERS) return fail(PYR_ERR_INVALID_ARGUMENT, "a session keeps no counters");
+    if (pyr_device_count() <= 0) return fail(PYR_ERR_DEVICE, "no HIP device is visible; pyrite_gpu has no CPU path");
+    return PYR_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int pyr_session_create(PyrScene* scene, const PyrCamera* camera, const PyrFilmDesc* film, const PyrRenderParams* params, uint32_t flags,
+                       const PyrGrain* film_host, PyrSession** out_session) {
+    if (!out_session) return fail(PYR_ERR_INVALID_ARGUMENT, "null out pointer");
+    *out_session = nullptr;
+    int rc = check_session_args(scene, camera, film, params);
+    if (rc != PYR_OK) return rc;
+    if (flags & ~PYR_SESSION_HALVES) return fail(PYR_ERR_INVALID_ARGUMENT, "unknown session flag");
+    if ((rc = check_render_args(scene, camera, film, params, scene)) != PYR_OK) return rc;
+    TilePlan plan;
+    if ((rc = plan_tiles(film, params, plan)) != PYR_OK) return rc; // the whole budget must be one a single call could render
+    HIP_TRY(hipSetDevice(scene->device));
+    std::unique_ptr<PyrSession> s(new (std::nothrow) PyrSession());
+    if (!s) return fail(PYR_ERR_OUT_OF_MEMORY, "out of host memory");
+    s->scene = scene;
+    s->camera = *camera;
+    s->film = *film;
+    s->params = *params;
+    s->halves = (flags & PYR_SESSION_HALVES) != 0;
+    s->tiles_x = plan.tiles_x, s->tiles_y = plan.tiles_y;
+    s->grains = (size_t)film->width * film->height * film->bins;
+    const size_t bytes = s->grains * sizeof(PyrGrain);
+    HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
+    if (film_host) {
+        if ((rc = s->film_a.upload(film_host, bytes)) != PYR_OK) return rc;
+    } else {
+        if ((rc = s->film_a.alloc(bytes)) != PYR_OK) return rc;
+        HIP_TRY(hipMemsetAsync(s->film_a.ptr, 0, bytes, s->stream));
+    }
+    if (s->halves) {
+        if ((rc = s->film_b.alloc(bytes)) != PYR_OK) return rc;
+        HIP_TRY(hipMemsetAsync(s->film_b.ptr, 0, bytes, s->stream));
+    }
+    if ((rc = s->rgb.alloc((size_t)film->width * film->height * 3)) != PYR_OK) return rc;
+    HIP_TRY(hipStreamSynchronize(s->stream));
+    *out_session = s.release();
+    return PYR_OK;
+}
+
+void pyr_session_destroy(PyrSession* session) {
+    if (!session) return;
+    (void)hipSetDevice(session->scene->device);
+    (void)hipStreamSynchronize(session->stream); // a pass may still be writing the films
+    delete session;
+}
+
+int pyr_session_render(PyrSession* session, uint32_t samples) {
+    int rc = session_ready(session);
+    if (rc != PYR_OK) return rc;
+    if (samples == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "zero-sized parameter");
+    const uint32_t left = session->params.pixel_samples - session->samples_done;
+    if (left == 0) return PYR_OK; // the budget is spent
+    PyrRenderParams p = session->params;
+    p.sample_begin = session->samples_done;
+    p.pixel_samples = std::min(samples, left);
+    TilePlan plan;
+    if ((rc = plan_tiles(&session->film, &p, plan)) != PYR_OK) return rc;
+    RenderLaunch L = make_launch(&session->camera, &session->film, &p, plan);
+    L.film_out = (PyrGrain*)((session->halves && (session->passes & 1u)) ? session->film_b.ptr : session->film_a.ptr);
+    if ((rc = render_batches(session->scene, L, false, session->stream)) != PYR_OK) return rc;
+    session->samples_done += p.pixel_samples;
+    session->passes += 1;
+    return PYR_OK;
+}
+
+int pyr_session_sync(PyrSession* session) {
+    int rc = session_ready(session);
+    if (rc != PYR_OK) return rc;
+    return session_sync(session);
+}
+
+int pyr_session_samples_done(PyrSession* session, uint32_t* out_samples) {
+    if (!session || !out_samples) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+    *out_samples = session->samples_done;
+    return PYR_OK;
+}
+
+int pyr_session_preview(PyrSession* session, const PyrDevelopParams* develop_params, uint8_t* rgb_out) {
+    if (!session || !develop_params || !rgb_out || !develop_params->xyz_table) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = session_ready(session);
+    if (rc != PYR_OK) return rc;
+    if ((rc = check_develop_params(develop_params)) != PYR_OK) return rc;
+    PyrSession* s = session;
+    const size_t floats = 3 * (size_t)develop_params->sample_count + 3 * (size_t)develop_params->xyz_count;
+    if (floats * sizeof(float) > s->tables.bytes || !s->tables.ptr) {
+        HIP_TRY(hipStreamSynchronize(s->stream)); // an earlier preview may still read the old tables
+        s->tables.release();
+        if ((rc = s->tables.alloc(floats * sizeof(float))) != PYR_OK) return rc;
+    }
+    DevelopLaunch D = develop_launch(&s->film, develop_params, (float*)s->tables.ptr, s->host_tables);
+    HIP_TRY(hipMemcpyAsync(s->tables.ptr, s->host_tables.data(), floats * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    D.grains = (const PyrGrain*)s->film_a.ptr;
+    D.grains_b = s->halves ? (const PyrGrain*)s->film_b.ptr : nullptr;
+    D.rgb_out = (uint8_t*)s->rgb.ptr;
+    const PyrGrain* summed = nullptr;
+    if (!develop_uses_wave(D)) { // the per-pixel kernel (of A + B where there are halves and the film has more bins than the wave kernel's rows)
+        if ((rc = session_film(s, &summed)) != PYR_OK) return rc;
+        D.grains = summed, D.grains_b = nullptr;
+        rc = launch_develop(D, s->stream);
+        if (rc != PYR_OK) return fail(rc, kernels_last_error());
+    } else {
+        rc = launch_develop_wave(D, s->stream);
+        if (rc != PYR_OK) return fail(rc, film_kernels_last_error());
+    }
+    HIP_TRY(hipMemcpyAsync(rgb_out, s->rgb.ptr, (size_t)s->film.width * s->film.height * 3, hipMemcpyDeviceToHost, s->stream));
+    return session_sync(s);
+}
+
+int pyr_session_film_device(PyrSession* session, PyrGrain* film_out_device) {
+    if (!session || !film_out_device) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = session_ready(session);
+    if (rc != PYR_OK) return rc;
+    if (session->halves) {
+        rc = launch_film_sum((const PyrGrain*)session->film_a.ptr, (const PyrGrain*)session->film_b.ptr, film_out_device, session->grains, session->stream);
+        if (rc != PYR_OK) return fail(rc, film_kernels_last_error());
+    } else {
+        HIP_TRY(hipMemcpyAsync(film_out_device, session->film_a.ptr, session->grains * sizeof(PyrGrain), hipMemcpyDeviceToDevice, session->stream));
+    }
+    return session_sync(session);
+}
+
+int pyr_session_film(PyrSession* session, PyrGrain* film_out) {
+    if (!session || !film_out) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = session_ready(session);
+    if (rc != PYR_OK) return rc;
+    const PyrGrain* film = nullptr;
+    if ((rc = session_film(session, &film)) != PYR_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(film_out, film, session->grains * sizeof(PyrGrain), hipMemcpyDeviceToHost, session->stream));
+    return session_sync(session);
+}
+
+int pyr_session_halves(PyrSession* session, PyrGrain* film_a_out, PyrGrain* film_b_out) {
+    if (!session || !film_a_out || !film_b_out) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = session_ready(session);
+    if (rc != PYR_OK) return rc;
+    if (!session->halves) return fail(PYR_ERR_INVALID_ARGUMENT, "the session was created without PYR_SESSION_HALVES");
+    HIP_TRY(hipMemcpyAsync(film_a_out, session->film_a.ptr, session->grains * sizeof(PyrGrain), hipMemcpyDeviceToHost, session->stream));
+    HIP_TRY(hipMemcpyAsync(film_b_out, session->film_b.ptr, session->grains * sizeof(PyrGrain), hipMemcpyDeviceToHost, session->stream));
+    return session_sync(session);
+}
+
+int pyr_session_noise(PyrSession* session, float* out_per_tile) {
+    if (!session || !out_per_tile) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = session_ready(session);
+    if (rc != PYR_OK) return rc;
+    if (!session->halves) return fail(PYR_ERR_INVALID_ARGUMENT, "the noise estimate needs the two half films: create the session with PYR_SESSION_HALVES");
+    if (session->passes < 2) return fail(PYR_ERR_INVALID_ARGUMENT, "the noise estimate needs at least two passes: one half film is still empty");
+    const size_t tiles = (size_t)session->tiles_x * session->tiles_y;
+    if (!session->noise.ptr && (rc = session->noise.alloc(tiles * sizeof(float))) != PYR_OK) return rc;
+    NoiseLaunch N{};
+    N.film = session->film;
+    N.tile_size = session->params.tile_size;
+    N.tiles_x = session->tiles_x, N.tiles_y = session->tiles_y;
+    N.a = (const PyrGrain*)session->film_a.ptr;
+    N.b = (const PyrGrain*)session->film_b.ptr;
+    N.out = (float*)session->noise.ptr;
+    rc = launch_noise(N, session->stream);
+    if (rc != PYR_OK) return fail(rc, film_kernels_last_error());
+    HIP_TRY(hipMemcpyAsync(out_per_tile, session->noise.ptr, tiles * sizeof(float), hipMemcpyDeviceToHost, session->stream));
+    return session_sync(session);
+}
+
+int pyr_render_simple_progressive(PyrScene* scene, const PyrCamera* camera, const PyrFilmDesc* film, const PyrRenderParams* params, PyrGrain* film_inout,
+                                  uint32_t pass_samples, PyrProgressFn on_status, PyrPreviewFn on_preview, double preview_min_interval_s,
+                                  const PyrDevelopParams* preview_develop_params, void* user) {
+    if (!film_inout) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+    if (on_preview && (!preview_develop_params || !preview_develop_params->xyz_table)) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: a preview needs development parameters");
+    if (!scene || !camera || !film || !params) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+    if (pass_samples == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "zero-sized parameter: pass_samples");
+    if (!(preview_min_interval_s >= 0.0)) return fail(PYR_ERR_INVALID_ARGUMENT, "negative preview interval");
+    int rc = check_session_args(scene, camera, film, params);
+    if (rc != PYR_OK) return rc;
+    PyrSession* raw = nullptr;
+    if ((rc = pyr_session_create(scene, camera, film, params, 0u, film_inout, &raw)) != PYR_OK) return rc;
+    struct Closer {
+        PyrSession* s;
+        ~Closer() { pyr_session_destroy(s); }
+    } closer{raw};
+    const char* message = "Rendering"; // simple.rs:30
+    if (on_status) on_status(user, 0, message);
+    std::vector<uint8_t> rgb;
+    if (on_preview) rgb.resize((size_t)film->width * film->height * 3);
+    const uint32_t budget = params->pixel_samples;
+    auto last_preview = std::chrono::steady_clock::now(); // main.rs:261: the first preview comes one interval into the render
+    while (raw->samples_done < budget) {
+        if ((rc = pyr_session_render(raw, pass_samples)) != PYR_OK) return rc;
+        if ((rc = session_sync(raw)) != PYR_OK) return rc;
+        if (on_status) on_status(user, (uint8_t)((uint64_t)raw->samples_done * 100u / budget), message);
+        const auto now = std::chrono::steady_clock::now();
+        if (on_preview && std::chrono::duration<double>(now - last_preview).count() >= preview_min_interval_s) {
+            if ((rc = pyr_session_preview(raw, preview_develop_params, rgb.data())) != PYR_OK) return rc;
+            on_preview(user, rgb.data(), film->width, film->height, raw->samples_done);
+            last_preview = std::chrono::steady_clock::now();
+        }
+    }
+    return pyr_session_film(raw, film_inout);
 }
 
 } // extern "C"

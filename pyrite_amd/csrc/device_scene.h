@@ -1,5 +1,6 @@
 // device_scene.h -- layout of the frozen scene in HBM, shared by the host packer (api.cpp) and the kernels.
 #pragma once
+#include <cstddef>
 #include <cstdint>
 
 #include "../../include/pyrite_gpu.h"
@@ -199,6 +200,7 @@ struct RenderLaunch {
     uint32_t tape_lanes, tape_max_ops;
     uint32_t* tape_overflow; // device word, set when a path wanted to append more than tape_max_ops records
     uint32_t tape_programs_lds; // programs whose prepared form the kernel keeps in LDS for the replay (set by launch_render; 0 = none)
+    uint32_t sample_begin; // first sample of every pixel's budget this launch renders (PyrRenderParams::sample_begin); only locate_chunk reads it
 };
 
 // Work feed of the persistent traversal kernels: kFeedSegments cursor words, kFeedCursorStride words apart (kernels.hip WorkFeed).
@@ -228,8 +230,26 @@ struct DevelopLaunch {
     uint32_t xyz_count;
     float xyz_min, xyz_max;
     uint8_t* rgb_out; // device
+    const PyrGrain* grains_b; // device or nullptr: a second half film, developed as grains + grains_b (develop_wave_kernel only)
 };
-int launch_develop(const DevelopLaunch& launch, void* stream);
+int launch_develop(const DevelopLaunch& launch, void* stream); // develop_kernel: one thread per pixel (kernels/main.hip)
+
+// kernels/film.hip: the kernels of a progressive session's film
+// develop_wave_kernel: one wave per run of 64 pixels, the same bytes as develop_kernel. Its LDS rows hold films of up to
+// kWaveDevelopMaxBins bins (64 KB a wave); develop_wave_serves says whether a launch fits, launch_develop_wave refuses one that does not.
+constexpr uint32_t kWaveDevelopMaxBins = 255;
+bool develop_wave_serves(const DevelopLaunch& launch);
+int launch_develop_wave(const DevelopLaunch& launch, void* stream);
+int launch_film_sum(const PyrGrain* a, const PyrGrain* b, PyrGrain* out, size_t grains, void* stream); // out = a + b (out may be a or b)
+struct NoiseLaunch {
+    PyrFilmDesc film;
+    uint32_t tile_size, tiles_x, tiles_y;
+    const PyrGrain* a; // device, whole image: the two half films
+    const PyrGrain* b;
+    float* out; // device, tiles_x * tiles_y
+};
+int launch_noise(const NoiseLaunch& launch, void* stream);
+const char* film_kernels_last_error();
 
 // Adds the PYR_FILM_TILE_BLOCKS buffer of the tiles tile_begin + k * tile_stride (k < tile_count) into a whole-image film.
 struct AssembleLaunch {

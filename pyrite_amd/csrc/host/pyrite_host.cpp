@@ -1094,11 +1094,17 @@ void on_status_trampoline(void* user, uint8_t percent, const char* message) {
 }
 } // namespace
 
-void Renderer::render(Film& film, const Camera& camera, World& world, const std::function<void(Progress)>& on_status, int device, PyrCounters* counters) const {
+PyrRenderParams Renderer::params(uint32_t sample_begin) const {
     PyrRenderParams p{};
     p.bounces = bounces, p.pixel_samples = pixel_samples, p.light_samples = light_samples, p.spectrum_samples = spectrum_samples, p.tile_size = tile_size;
-    p.flags = counters != nullptr ? PYR_FLAG_COUNTERS : 0u;
     p.seed = seed;
+    p.sample_begin = sample_begin;
+    return p;
+}
+
+void Renderer::render(Film& film, const Camera& camera, World& world, const std::function<void(Progress)>& on_status, int device, PyrCounters* counters) const {
+    PyrRenderParams p = params();
+    p.flags = counters != nullptr ? PYR_FLAG_COUNTERS : 0u;
     const PyrFilmDesc desc = film.desc();
     Trampoline t{&on_status};
     check_status(pyr_render_simple(world.scene(device), &camera.c, &desc, &p, film.grains.data(), on_status ? on_status_trampoline : nullptr, on_status ? &t : nullptr));
@@ -1107,9 +1113,7 @@ void Renderer::render(Film& film, const Camera& camera, World& world, const std:
 
 void Renderer::render(Film& film, const Camera& camera, World& world, const std::vector<int>& devices, const std::function<void(Progress)>& on_status) const {
     if (devices.empty()) throw ProjectError("render: no device given");
-    PyrRenderParams p{};
-    p.bounces = bounces, p.pixel_samples = pixel_samples, p.light_samples = light_samples, p.spectrum_samples = spectrum_samples, p.tile_size = tile_size;
-    p.seed = seed;
+    const PyrRenderParams p = params();
     std::vector<PyrScene*> scenes;
     std::map<int, int> seen;
     for (int device : devices) scenes.push_back(world.scene(device, seen[device]++));
@@ -1203,36 +1207,87 @@ float evaluate_at(const Expression& e, float w) {
     }
 }
 
-std::vector<uint8_t> Film::develop(const std::optional<Expression>& filter, const std::optional<Expression>& white, float step_size, int device) const {
-    // wl_i of spectrum_to_tristimulus (main.rs:393-411): start at the span's minimum, add step_size in f32 while below the maximum
-    const float lo = wavelength_start, hi = wavelength_start + wavelength_width;
-    std::vector<float> wl{lo};
-    while (wl.back() < hi) wl.push_back(wl.back() + step_size);
-    static const std::vector<float> xyz_table = table(k_xyz_bits, (size_t)k_xyz_rows * 3);
+namespace {
+// PyrDevelopParams of a film with the image's filter / white programs, and the arrays it borrows.
+struct DevelopSetup {
     PyrDevelopParams p{};
-    p.step_size = step_size, p.xyz_scale = 3.444f, p.sample_count = (uint32_t)wl.size();
-    p.xyz_table = xyz_table.data(), p.xyz_count = k_xyz_rows, p.xyz_min = k_xyz_min, p.xyz_max = k_xyz_max;
     std::vector<float> filter_values, white_div, white_mul;
-    if (filter) { // main.rs:197-202
-        for (float w : wl) filter_values.push_back(evaluate_at(*filter, w));
-        p.filter = filter_values.data();
-    }
-    if (white) { // main.rs:204-222
-        float mx = 0.0f, d65_mx = 0.0f;
-        for (float w = lo; w < hi; w = w + 1.0f) {
-            mx = std::max(mx, evaluate_at(*white, w));
-            d65_mx = std::max(d65_mx, d65_at(w));
+    DevelopSetup(const Film& film, const std::optional<Expression>& filter, const std::optional<Expression>& white, float step_size) {
+        // wl_i of spectrum_to_tristimulus (main.rs:393-411): start at the span's minimum, add step_size in f32 while below the maximum
+        const float lo = film.wavelength_start, hi = film.wavelength_start + film.wavelength_width;
+        std::vector<float> wl{lo};
+        while (wl.back() < hi) wl.push_back(wl.back() + step_size);
+        static const std::vector<float> xyz_table = table(k_xyz_bits, (size_t)k_xyz_rows * 3);
+        p.step_size = step_size, p.xyz_scale = 3.444f, p.sample_count = (uint32_t)wl.size();
+        p.xyz_table = xyz_table.data(), p.xyz_count = k_xyz_rows, p.xyz_min = k_xyz_min, p.xyz_max = k_xyz_max;
+        if (filter) { // main.rs:197-202
+            for (float w : wl) filter_values.push_back(evaluate_at(*filter, w));
+            p.filter = filter_values.data();
         }
-        for (float w : wl) {
-            white_div.push_back(std::max(evaluate_at(*white, w) / mx, 0.000001f));
-            white_mul.push_back(d65_at(w) / d65_mx);
+        if (white) { // main.rs:204-222
+            float mx = 0.0f, d65_mx = 0.0f;
+            for (float w = lo; w < hi; w = w + 1.0f) {
+                mx = std::max(mx, evaluate_at(*white, w));
+                d65_mx = std::max(d65_mx, d65_at(w));
+            }
+            for (float w : wl) {
+                white_div.push_back(std::max(evaluate_at(*white, w) / mx, 0.000001f));
+                white_mul.push_back(d65_at(w) / d65_mx);
+            }
+            p.white_div = white_div.data(), p.white_mul = white_mul.data();
         }
-        p.white_div = white_div.data(), p.white_mul = white_mul.data();
     }
+    DevelopSetup(const DevelopSetup&) = delete;
+};
+} // namespace
+
+std::vector<uint8_t> Film::develop(const std::optional<Expression>& filter, const std::optional<Expression>& white, float step_size, int device) const {
+    const DevelopSetup setup(*this, filter, white, step_size);
     std::vector<uint8_t> out((size_t)width * height * 3, 0);
     const PyrFilmDesc d = desc();
-    check_status(pyr_film_develop(&d, grains.data(), &p, out.data(), device));
+    check_status(pyr_film_develop(&d, grains.data(), &setup.p, out.data(), device));
     return out;
+}
+
+// ---- progressive sessions ------------------------------------------------------------------------------------------------------
+Session::Session(const Renderer& renderer, uint32_t width, uint32_t height, const Camera& camera, World& world, bool halves, int device, const Film* start)
+    : shape_(0, 0, renderer.spectrum_bins, renderer.spectrum_span[0], renderer.spectrum_span[1]), width_(width), height_(height), tile_size_(renderer.tile_size) {
+    shape_.width = width, shape_.height = height;
+    if (start && (start->width != width || start->height != height || start->bins != shape_.bins)) throw ProjectError("session: the film to continue from has another shape");
+    const PyrRenderParams p = renderer.params();
+    const PyrFilmDesc d = shape_.desc();
+    check_status(pyr_session_create(world.scene(device), &camera.c, &d, &p, halves ? PYR_SESSION_HALVES : 0u, start ? start->grains.data() : nullptr, &handle_));
+}
+Session::~Session() { pyr_session_destroy(handle_); }
+void Session::render(uint32_t samples) { check_status(pyr_session_render(handle_, samples)); }
+void Session::sync() { check_status(pyr_session_sync(handle_)); }
+uint32_t Session::samples_done() const {
+    uint32_t n = 0;
+    check_status(pyr_session_samples_done(handle_, &n));
+    return n;
+}
+std::vector<uint8_t> Session::preview(float step_size, const std::optional<Expression>& filter, const std::optional<Expression>& white) {
+    const DevelopSetup setup(shape_, filter, white, step_size);
+    std::vector<uint8_t> out((size_t)width_ * height_ * 3, 0);
+    check_status(pyr_session_preview(handle_, &setup.p, out.data()));
+    return out;
+}
+Film Session::film() {
+    Film out(width_, height_, shape_.bins, shape_.wavelength_start, shape_.wavelength_start + shape_.wavelength_width);
+    check_status(pyr_session_film(handle_, out.grains.data()));
+    return out;
+}
+std::vector<float> Session::noise() {
+    std::vector<float> out((size_t)tiles_x() * tiles_y(), 0.0f);
+    check_status(pyr_session_noise(handle_, out.data()));
+    return out;
+}
+
+std::string progressive_flag_problem(const std::optional<long>& pass_samples, bool preview, double preview_every, bool noise) {
+    if (pass_samples && *pass_samples < 1) return "--pass-samples must be at least 1";
+    if (!(preview_every >= 0.0)) return "--preview-every must not be negative";
+    if (noise && !preview) return "--noise needs --preview";
+    return "";
 }
 
 // Minimal PNG writer (8-bit RGB, stored deflate blocks) -- the image::save of main.rs:327.

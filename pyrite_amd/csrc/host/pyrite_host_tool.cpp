@@ -8,11 +8,14 @@
 //   pyrite_host_tool render <scene> <data_dir> <w> <h> <spp> <seed> <film.bin> [out.png]
 //                                                                             Renderer::render on device 0; film as raw {acc, weight} f32
 // scenes: c1 c2 spheres diamonds lamps textures      data_dir: pyrite_amd/data (cornell_spectra.json, cornell_box.obj, diamonds.obj)
+#include <algorithm>
+#include <chrono>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <iostream>
+#include <optional>
 #include <sstream>
 
 #include "pyrite_host.hpp"
@@ -235,7 +238,36 @@ int main(int argc, char** argv) {
             write_dump(argv[4], flat, loaded.project);
             return 0;
         }
-        if (argc >= 6 && std::string(argv[1]) == "render-project") { // render-project <project.lua> <texel dir | -> <seed> <out.png> [film.bin]
+        if (argc >= 6 && std::string(argv[1]) == "render-project") { // render-project <project.lua> <texel dir | -> <seed> <out.png> [film.bin] [--pass-samples N] [--preview PATH] [--preview-every SECONDS] [--noise]
+            // the flags of python -m pyrite_amd: a progressive session with previews (main.rs:261-299) instead of one blocking call
+            std::optional<long> pass_samples;
+            std::string preview_path, film_path;
+            double preview_every = 20.0; // main.rs:262
+            bool noise = false;
+            for (int i = 6; i < argc; ++i) {
+                const std::string a = argv[i];
+                auto value = [&]() -> const char* {
+                    if (i + 1 >= argc) throw ProjectError(a + " needs a value");
+                    return argv[++i];
+                };
+                if (a == "--pass-samples")
+                    pass_samples = std::strtol(value(), nullptr, 10);
+                else if (a == "--preview")
+                    preview_path = value();
+                else if (a == "--preview-every")
+                    preview_every = std::strtod(value(), nullptr);
+                else if (a == "--noise")
+                    noise = true;
+                else if (a.rfind("--", 0) == 0)
+                    throw ProjectError("unknown flag " + a);
+                else
+                    film_path = a;
+            }
+            const std::string problem = progressive_flag_problem(pass_samples, !preview_path.empty(), preview_every, noise);
+            if (!problem.empty()) {
+                std::fprintf(stderr, "error: %s\n", problem.c_str());
+                return 2;
+            }
             const LoadedProject loaded = load_project(argv[2], std::string(argv[3]) == "-" ? TextureLoader() : texel_files(argv[3]));
             const Project& project = loaded.project;
             std::unique_ptr<World> world = World::from_project(project.world, loaded.base_dir);
@@ -244,11 +276,35 @@ int main(int argc, char** argv) {
             r.seed = std::strtoull(argv[4], nullptr, 10);
             Film film = r.new_film(project.image.width, project.image.height);
             std::printf("The scene contains %zu objects.\n", world->num_objects()); // world.rs:251-254
-            r.render(film, cam, *world);
+            if (pass_samples || !preview_path.empty() || noise) {
+                const uint32_t per_pass = pass_samples ? (uint32_t)*pass_samples : kDefaultPassSamples;
+                Session session(r, film.width, film.height, cam, *world, noise);
+                auto last_image = std::chrono::steady_clock::now(); // main.rs:241
+                while (session.samples_done() < r.pixel_samples) {
+                    session.render(per_pass);
+                    session.sync();
+                    std::printf("Rendering... %3d %%\n", (int)((uint64_t)session.samples_done() * 100u / r.pixel_samples));
+                    if (!preview_path.empty() && std::chrono::duration<double>(std::chrono::steady_clock::now() - last_image).count() >= preview_every) {
+                        save_png(preview_path, session.preview(30.0f, project.image.filter, project.image.white), film.width, film.height);
+                        std::printf("Preview updated (%u samples per pixel)\n", session.samples_done());
+                        if (noise && session.samples_done() >= 2 * per_pass) {
+                            std::vector<float> tiles = session.noise();
+                            std::sort(tiles.begin(), tiles.end());
+                            const size_t n = tiles.size();
+                            const float median = n % 2 ? tiles[n / 2] : 0.5f * (tiles[n / 2 - 1] + tiles[n / 2]);
+                            std::printf("noise: largest tile %.4g, median tile %.4g\n", tiles.back(), median);
+                        }
+                        last_image = std::chrono::steady_clock::now();
+                    }
+                }
+                film = session.film();
+            } else {
+                r.render(film, cam, *world);
+            }
             std::printf("Saving final result...\n"); // main.rs:313
             save_png(argv[5], film.develop(project.image.filter, project.image.white), film.width, film.height);
-            if (argc >= 7) {
-                std::ofstream f(argv[6], std::ios::binary);
+            if (!film_path.empty()) {
+                std::ofstream f(film_path, std::ios::binary);
                 f.write(reinterpret_cast<const char*>(film.grains.data()), (std::streamsize)(film.grains.size() * sizeof(PyrGrain)));
             }
             return 0;

@@ -1406,7 +1406,8 @@ DEV void start_sample(const RenderLaunch& L, uint32_t tile, uint64_t iteration, 
 }
 
 // Maps a chunk number of the launch to (tile, first iteration, tile rectangle): chunk c belongs to the launch's
-// (c / chunks_per_tile)-th tile. Returns false when the lane's iteration lies beyond the tile's iteration count (the last
+// (c / chunks_per_tile)-th tile, whose iterations [w * h * sample_begin, w * h * (sample_begin + pixel_samples)) the launch renders
+// (w x h the tile's clipped size). Returns false when the lane's iteration lies beyond the tile's iteration count (the last
 // chunk of a tile, and the empty chunk numbers of a tile cut by the image border).
 DEV bool locate_chunk(const RenderLaunch& L, uint32_t chunk, uint32_t lane, uint32_t& tile, uint64_t& iteration, TileArea& area) {
     const uint32_t k = chunk / L.chunks_per_tile, within = chunk - k * L.chunks_per_tile;
@@ -1414,9 +1415,10 @@ DEV bool locate_chunk(const RenderLaunch& L, uint32_t chunk, uint32_t lane, uint
     const uint32_t ty = tile / L.tiles_x, tx = tile - ty * L.tiles_x;
     const uint32_t sx = tx * L.tile_size, sy = ty * L.tile_size;
     const uint32_t w = min(L.film.width - sx, L.tile_size), h = min(L.film.height - sy, L.tile_size);
-    const uint64_t iterations = (uint64_t)w * h * L.pixel_samples;
+    const uint64_t area_px = (uint64_t)w * h, iterations = area_px * L.pixel_samples;
     iteration = (uint64_t)within * 64u + lane;
     if (iteration >= iterations) return false;
+    iteration += area_px * L.sample_begin; // the call's window of the pixel budget: the RNG key stays (seed, tile, iteration)
     area = to_view_area(sx, sy, w, h, L.film.width, L.film.height);
     return true;
 }

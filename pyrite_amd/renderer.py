@@ -99,9 +99,10 @@ class Renderer:
         ts = self.tile_size
         return ((width + ts - 1) // ts) * ((height + ts - 1) // ts)
 
-    def params(self, flags=0, tile_range=None, film_rows=None, share=None):
+    def params(self, flags=0, tile_range=None, film_rows=None, share=None, sample_begin=0):
         """PyrRenderParams of this renderer. `tile_range` / `film_rows` restrict the call to raster tiles [a, b) and to a window of
-        pixel rows; `share` (pyrite_amd.distributed.Share) sets tiles, stride and film layout at once."""
+        pixel rows; `share` (pyrite_amd.distributed.Share) sets tiles, stride and film layout at once; `sample_begin` makes the call
+        render the samples [sample_begin, sample_begin + pixel_samples) of every pixel's budget."""
         p = abi.PyrRenderParams()
         p.bounces, p.pixel_samples, p.light_samples = self.bounces, self.pixel_samples, self.light_samples
         p.spectrum_samples, p.tile_size, p.flags, p.seed = self.spectrum_samples, self.tile_size, flags, self.seed
@@ -111,7 +112,13 @@ class Renderer:
             p.film_row_begin, p.film_row_count = int(film_rows[0]), int(film_rows[1])
         if share is not None:
             share.apply(p)
+        p.sample_begin = int(sample_begin)
         return p
+
+    def session(self, film_size, camera: Camera, world: World, halves=False, device=0, film: Film = None):
+        """A progressive render of this renderer's whole budget (pyr_session_*): `film_size` = (width, height). The film lives on
+        the GPU; with `film` the session continues from that host Film. See Session."""
+        return Session(self, film_size, camera, world, halves=halves, device=device, film=film)
 
     def path_info(self, world: World, device=0):
         """Which kernel a render of `world` with this renderer would run (pyr_scene_path_info): a dict of PyrPathInfo's fields."""
@@ -127,11 +134,11 @@ class Renderer:
         return {name: int(getattr(info, name)) for name, _ in info._fields_ if name != "reserved"}
 
     def render(self, film: Film, camera: Camera, world: World, on_status=None, device=0, counters=False, tile_range=None, film_rows=None,
-               window=None, share=None):
+               window=None, share=None, sample_begin=0):
         """Blocking render into a host Film (adds to it). Returns the PyrCounters dict when counters=True.
         `tile_range` restricts the call to raster tiles [a, b); with film_rows=(first_row, rows) the exposures go to `window`,
         a float32 [rows, width, bins, 2] array covering only those rows of the image `film` describes."""
-        params = self.params(abi.PYR_FLAG_COUNTERS if counters else 0, tile_range, film_rows, share)
+        params = self.params(abi.PYR_FLAG_COUNTERS if counters else 0, tile_range, film_rows, share, sample_begin)
         desc = film.desc()
         if window is not None:
             assert window.flags["C_CONTIGUOUS"] and window.dtype == np.float32
@@ -180,3 +187,89 @@ class Renderer:
         out = abi.PyrCounters()
         check(lib().pyr_scene_counters(world.scene(device), C.byref(out)))
         return out.as_dict()
+
+
+class Session:
+    """A render cut into passes over the whole image (include/pyrite_gpu.h "progressive sessions"): `render(n)` enqueues the next
+    n samples of every pixel and returns at once, `preview()` develops the live film on the GPU and fetches the 8-bit image alone,
+    `film()` fetches the film, `noise()` the per-tile noise estimate of a session with `halves`. The world's scene on that device
+    serves this session alone until it is closed or synced."""
+
+    def __init__(self, renderer: Renderer, film_size, camera: Camera, world: World, halves=False, device=0, film: Film = None):
+        self.renderer, self.world, self.device, self.halves = renderer, world, int(device), bool(halves)
+        self.width, self.height = int(film_size[0]), int(film_size[1])
+        self._film = renderer.new_film(self.width, self.height) if film is None else film
+        assert (self._film.width, self._film.height) == (self.width, self.height)
+        self._shape = (self.height, self.width, self._film.bins, 2)
+        desc, params = self._film.desc(), renderer.params()
+        start = None
+        if film is not None:
+            start = np.ascontiguousarray(film.grains)
+        self.handle = C.c_void_p()
+        check(lib().pyr_session_create(world.scene(self.device), C.byref(camera.c), C.byref(desc), C.byref(params),
+                                       abi.PYR_SESSION_HALVES if halves else 0, start.ctypes.data if start is not None else None, C.byref(self.handle)))
+
+    @property
+    def samples_done(self):
+        n = C.c_uint32(0)
+        check(lib().pyr_session_samples_done(self.handle, C.byref(n)))
+        return int(n.value)
+
+    @property
+    def tiles(self):
+        """(tiles_x, tiles_y) of the make_tiles grid: the shape of noise()."""
+        ts = self.renderer.tile_size
+        return (self.width + ts - 1) // ts, (self.height + ts - 1) // ts
+
+    def render(self, samples):
+        check(lib().pyr_session_render(self.handle, int(samples)))
+
+    def sync(self):
+        check(lib().pyr_session_sync(self.handle))
+
+    def preview(self, step=30.0, filter=None, white=None):
+        """uint8 [height, width, 3]: the film as it stands, developed on the GPU (main.rs:270 uses step 30 for previews)."""
+        from .develop import develop_params
+
+        p, keep = develop_params(self._film, step, filter, white)
+        out = np.zeros((self.height, self.width, 3), dtype=np.uint8)
+        check(lib().pyr_session_preview(self.handle, C.byref(p), out.ctypes.data))
+        del keep
+        return out
+
+    def film(self):
+        """The film so far as a host Film (the sum of the halves when there are two)."""
+        out = Film(self.width, self.height, self._film.bins, (self._film.wavelength_start, self._film.wavelength_start + self._film.wavelength_width))
+        check(lib().pyr_session_film(self.handle, out.grains.ctypes.data))
+        return out
+
+    def half_films(self):
+        """The two half films of a session with `halves`, float32 [height, width, bins, 2] each."""
+        a, b = np.zeros(self._shape, dtype=np.float32), np.zeros(self._shape, dtype=np.float32)
+        check(lib().pyr_session_halves(self.handle, a.ctypes.data, b.ctypes.data))
+        return a, b
+
+    def noise(self):
+        """float32 [tiles_y, tiles_x]: relative RMS difference of the half films per tile; half of it estimates the relative
+        error of the film (pyr_session_noise). Needs `halves` and two passes."""
+        tx, ty = self.tiles
+        out = np.zeros((ty, tx), dtype=np.float32)
+        check(lib().pyr_session_noise(self.handle, out.ctypes.data))
+        return out
+
+    def close(self):
+        if self.handle:
+            lib().pyr_session_destroy(self.handle)
+            self.handle = C.c_void_p()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
