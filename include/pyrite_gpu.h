@@ -614,6 +614,59 @@ int pyr_render_simple_progressive(PyrScene* scene, const PyrCamera* camera, cons
                                   PyrGrain* film_inout, uint32_t pass_samples, PyrProgressFn on_status, PyrPreviewFn on_preview,
                                   double preview_min_interval_s, const PyrDevelopParams* preview_develop_params, void* user);
 
+/* ---------------------------------------------------------------- first-hit feature images ---------------------
+ * The noise-free description of what the camera sees, one record and one albedo spectrum per pixel: what a denoiser, a stopping
+ * rule or a user who checks a scene before a long render reads. The reference has no such output; every step is one of its own:
+ *   - pixel (x, y) takes grid x grid sub-samples; sub-sample j = jy*grid + jx sits at fx = (jx + 0.5f) / grid, fy = (jy + 0.5f) / grid
+ *     of the pixel's view-plane rectangle (from, size) = Camera::to_view_area(x, y, 1, 1) (cameras.rs:57-68): px = from.x + size.x*fx,
+ *     py = from.y + size.y*fy, unfused f32;
+ *   - the ray is Camera::ray_towards(px, py) (cameras.rs:70-97) with `aperture` read as 0: the lens is its centre, nothing is drawn
+ *     from an RNG, the pass is a pure function of its arguments (lens blur is not reproduced);
+ *   - the hit is World::intersect (world.rs:273-299), the hit pyr_scene_intersect reports for that ray; surface data is
+ *     SurfacePoint::get_surface_data (shapes/mod.rs:484-494), the shading normal Material::apply_normal_map (materials/mod.rs:68-80)
+ *     run at the wavelength wl_start + wl_width * 0.5f with incident = the ray's direction;
+ *   - albedo: bin b of fp->albedo_bins stands for wl_b = wl_start + ((float)b + 0.5f) * (wl_width / (float)albedo_bins). With N =
+ *     the hit material's num_components, a = (sum over the components whose bsdf is not PYR_BSDF_EMISSIVE, in list order, of
+ *     get_probability(c) * color_c) / (float)N, both programs run on {wl_b, shading normal, ray direction, texture coordinates};
+ *     get_probability = probability_program * selection_compensation, or selection_compensation alone (materials/mod.rs:238-248).
+ *     Every sub-sample adds a (0 on a miss) to the grain's acc and 1 to its weight, in sub-sample order: the developed albedo is
+ *     anti-aliased against black. Emission and the sky have no channel;
+ *   - the record: `normal` = the sum of the shading normals of the sub-samples that hit, in sub-sample order, divided by their
+ *     number (not renormalised; 0 without a hit); `depth` = the mean PyrHit::distance of those; `coverage` = hits / grid^2; `shape` =
+ *     PyrHit::shape of sub-sample grid*grid/2 (PYR_HIT_NONE on a miss) and `material` that hit's material index (0xFFFFFFFF).
+ * Deterministic: a pixel is summed by one lane in a fixed order and written with plain stores, no float atomics; two calls write
+ * the same bytes. One GPU; scenes that need the wide interpreter build are served. */
+typedef struct PyrFeatureParams {
+    uint32_t grid;        /* 1..8: grid x grid sub-samples per pixel */
+    uint32_t albedo_bins; /* 1..64; read only when an albedo buffer is given */
+    uint32_t reserved[2];
+} PyrFeatureParams;
+typedef struct PyrFeaturePixel {
+    float normal[3];
+    float depth;
+    float coverage;
+    uint32_t shape;
+    uint32_t material;
+    uint32_t reserved; /* 0 */
+} PyrFeaturePixel; /* 32 bytes */
+
+/* HOST buffers; blocking. film->bins is ignored: the albedo film has fp->albedo_bins bins over film's wavelength span.
+ * albedo_inout (height*width*albedo_bins grains in the film.rs:56 layout, added into) and pixels_out (height*width records,
+ * row-major, overwritten) may each be NULL, not both. Arguments are checked before a device is looked for: PYR_ERR_INVALID_ARGUMENT
+ * for a null pointer, a grid outside 1..8, albedo_bins outside 1..64 with an albedo buffer, an empty image or wavelength span, or
+ * 2^32 pixels or more (pyr_last_error names the argument). */
+int pyr_render_features(PyrScene* scene, const PyrCamera* camera, const PyrFilmDesc* film, const PyrFeatureParams* fp,
+                        PyrGrain* albedo_inout, PyrFeaturePixel* pixels_out);
+/* Same with DEVICE buffers on the scene's device, enqueued on `hip_stream` without synchronising. The pass uses the scene's
+ * working memory: the one-render-at-a-time rule of pyr_render_simple_device holds for it too. pixels_device must be 16-byte
+ * aligned (hipMalloc's memory is; PYR_ERR_INVALID_ARGUMENT otherwise). */
+int pyr_render_features_device(PyrScene* scene, const PyrCamera* camera, const PyrFilmDesc* film, const PyrFeatureParams* fp,
+                               PyrGrain* albedo_device, PyrFeaturePixel* pixels_device, void* hip_stream);
+/* The session's camera and image size, on the session's stream, ordered after the passes enqueued so far; blocking. HOST outputs,
+ * each may be NULL (not both); here the albedo is OVERWRITTEN: the pass runs into a zeroed film. The session's own film is not
+ * touched, and further passes may follow. */
+int pyr_session_features(PyrSession* session, const PyrFeatureParams* fp, PyrGrain* albedo_out, PyrFeaturePixel* pixels_out);
+
 #ifdef __cplusplus
 }
 #endif

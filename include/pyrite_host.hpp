@@ -306,7 +306,26 @@ class Renderer { // renderer/mod.rs:18-28, Algorithm::Simple
     // A device listed twice is the one-GPU test rig (pyrite_gpu.h).
     void render(Film& film, const Camera& camera, World& world, const std::vector<int>& devices, const std::function<void(Progress)>& on_status = nullptr) const;
     PyrRenderParams params(uint32_t sample_begin = 0) const; // this renderer as the ABI's parameter block
+    // The first-hit feature images (pyr_render_features; pyrite_amd/renderer.py Renderer.features): no noise, no random numbers.
+    struct Features features(uint32_t width, uint32_t height, const Camera& camera, World& world, uint32_t grid = 1, uint32_t albedo_bins = 16, int device = 0) const;
 };
+
+// What Renderer::features and Session::features return: the albedo film (albedo_bins bins over the renderer's span; develop and
+// save_png apply) and one PyrFeaturePixel per pixel, row-major (pyrite_gpu.h "first-hit feature images").
+struct Features {
+    Film albedo;
+    std::vector<PyrFeaturePixel> pixels;
+};
+// The 8-bit images of the records, [height][width][3], pure functions (pyrite_amd/features.py encode_normal / encode_depth write
+// the same bytes): normal = (uint8)(255 * (0.5 * n + 0.5) + 0.5) per channel in f32; depth = grey, linear between the smallest and
+// the largest depth over the pixels with coverage > 0, near is white. Pixels with coverage 0 are black in both.
+std::vector<uint8_t> encode_normal_image(const std::vector<PyrFeaturePixel>& pixels);
+std::vector<uint8_t> encode_depth_image(const std::vector<PyrFeaturePixel>& pixels);
+// PREFIX_albedo.png (developed with the image's filter / white programs, step 2), PREFIX_normal.png, PREFIX_depth.png
+void write_feature_images(const std::string& prefix, const Features& features, const std::optional<Expression>& filter = std::nullopt,
+                          const std::optional<Expression>& white = std::nullopt, int device = 0);
+// What is wrong with --features / --features-grid, in the words both front ends print, or "" (pyrite_amd/features.py features_flag_problem).
+std::string features_flag_problem(bool features, const std::optional<long>& features_grid);
 
 // A render cut into passes over the whole image (pyrite_gpu.h "progressive sessions"): the film lives on the GPU, render()
 // enqueues the next samples of every pixel and returns at once, preview() develops the live film there and fetches the 8-bit image
@@ -325,6 +344,7 @@ class Session {
     std::vector<uint8_t> preview(float step_size = 30.0f, const std::optional<Expression>& filter = std::nullopt, const std::optional<Expression>& white = std::nullopt);
     Film film();
     std::vector<float> noise(); // per tile of the make_tiles grid, raster order (pyr_session_noise): needs halves and two passes
+    Features features(uint32_t grid = 1, uint32_t albedo_bins = 16); // pyr_session_features: after the passes enqueued so far; the film is not touched
     uint32_t tiles_x() const { return (width_ + tile_size_ - 1) / tile_size_; }
     uint32_t tiles_y() const { return (height_ + tile_size_ - 1) / tile_size_; }
 

@@ -4,11 +4,15 @@
 
     python -m pyrite_amd path/to/project.lua [-o out.png] [--seed N] [--device D] [--spp N] [--size WxH]
                          [--pass-samples N] [--preview PATH] [--preview-every SECONDS] [--noise]
+                         [--features PREFIX] [--features-grid N]
 
 With --pass-samples, --preview or --noise the render runs as a progressive session (pyr_session_*): passes of N samples per pixel
 over the whole image, the preview image rewritten from the live film every SECONDS or more (main.rs:261-299; developed on the GPU
 with step 30, main.rs:270), and with --noise the largest and the median per-tile noise estimate printed after each preview. The
-final image is the one the plain render writes."""
+final image is the one the plain render writes.
+
+With --features the first-hit feature pass (pyr_render_features, N x N sub-samples per pixel, default 1) runs after the render and
+writes PREFIX_albedo.png, PREFIX_normal.png and PREFIX_depth.png."""
 import argparse
 import os
 import sys
@@ -65,8 +69,12 @@ def main(argv=None):
     ap.add_argument("--preview", default=None, metavar="PATH", help="image to rewrite from the live film while rendering")
     ap.add_argument("--preview-every", type=float, default=20.0, metavar="SECONDS", help="least time between two previews (default 20, main.rs:262)")
     ap.add_argument("--noise", action="store_true", help="print the largest and median per-tile noise estimate after each preview")
+    ap.add_argument("--features", default=None, metavar="PREFIX", help="write PREFIX_albedo.png, PREFIX_normal.png and PREFIX_depth.png of the first hits")
+    ap.add_argument("--features-grid", type=int, default=None, metavar="N", help="N x N sub-samples per pixel for --features (1 to 8, default 1)")
     args = ap.parse_args(argv)
-    problem = progressive_flag_problem(args.pass_samples, args.preview, args.preview_every, args.noise)
+    from .features import features_flag_problem
+
+    problem = progressive_flag_problem(args.pass_samples, args.preview, args.preview_every, args.noise) or features_flag_problem(args.features, args.features_grid)
     if problem:
         print("error: " + problem, file=sys.stderr)
         return 2
@@ -99,6 +107,12 @@ def main(argv=None):
     out = args.output or os.path.join(base_dir, "render.png")
     save_png(out, rgb)
     print("wrote", out)
+    if args.features:
+        from .features import write_feature_images
+
+        write_feature_images(args.features, r.features((film.width, film.height), cam, world, grid=args.features_grid or 1, device=args.device),
+                             filter=image.get("filter"), white=image.get("white"), device=args.device)
+        print("wrote %s_albedo.png, %s_normal.png, %s_depth.png" % (args.features, args.features, args.features))
     return 0
 
 

@@ -268,6 +268,21 @@ class PyrDevelopParams(C.Structure):
     ]
 
 
+class PyrFeatureParams(C.Structure):
+    _fields_ = [("grid", C.c_uint32), ("albedo_bins", C.c_uint32), ("reserved", C.c_uint32 * 2)]
+
+
+class PyrFeaturePixel(C.Structure):
+    _fields_ = [
+        ("normal", C.c_float * 3),
+        ("depth", C.c_float),
+        ("coverage", C.c_float),
+        ("shape", C.c_uint32),
+        ("material", C.c_uint32),
+        ("reserved", C.c_uint32),
+    ]
+
+
 PyrProgressFn = C.CFUNCTYPE(None, C.c_void_p, C.c_uint8, C.c_char_p)
 PyrPreviewFn = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, C.c_uint32)
 
@@ -328,6 +343,12 @@ ENTRY_POINTS = {
         [C.c_void_p, C.POINTER(PyrCamera), C.POINTER(PyrFilmDesc), C.POINTER(PyrRenderParams), C.c_void_p, C.c_uint32, PyrProgressFn, PyrPreviewFn,
          C.c_double, C.POINTER(PyrDevelopParams), C.c_void_p],
     ),
+    "pyr_render_features": (C.c_int, [C.c_void_p, C.POINTER(PyrCamera), C.POINTER(PyrFilmDesc), C.POINTER(PyrFeatureParams), C.c_void_p, C.c_void_p]),
+    "pyr_render_features_device": (
+        C.c_int,
+        [C.c_void_p, C.POINTER(PyrCamera), C.POINTER(PyrFilmDesc), C.POINTER(PyrFeatureParams), C.c_void_p, C.c_void_p, C.c_void_p],
+    ),
+    "pyr_session_features": (C.c_int, [C.c_void_p, C.POINTER(PyrFeatureParams), C.c_void_p, C.c_void_p]),
 }
 
 

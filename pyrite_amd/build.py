@@ -10,8 +10,9 @@ import sys
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 OUT = os.path.join(CSRC, "libpyrite_gpu.so")
 KERNELS = os.path.join(CSRC, "kernels")  # the units that instantiate the kernels of kernels.hip
-KERNEL_UNITS = ["main.hip", "interp.hip", "product.hip", "wide.hip", "film.hip"]
+KERNEL_UNITS = ["main.hip", "interp.hip", "product.hip", "wide.hip", "film.hip", "features.hip", "features_wide.hip"]
 PROFILE_UNIT = "profile.hip"  # -DPYR_PHASE_PROFILE builds: main, interp and product in one unit, no wide build
+PLAIN_UNITS = ["film.hip", "features.hip", "features_wide.hip"]  # units without phase counters: every build has them
 SOURCES = ["api.cpp", "multi.cpp", "bvh.cpp", "program_regs.cpp"]
 HEADERS = ["kernels.hip", "bvh.h", "device_scene.h", "api_internal.h", "exact_math.h", "program_regs.h", os.path.join("..", "..", "include", "pyrite_gpu.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -95,7 +96,8 @@ def build_host(force=False, verbose=False):
 
 
 def compile_library(out, extra_flags=(), verbose=False):
-    """The sources -> objects in parallel -> one shared library. The kernels of kernels.hip are instantiated by four units, and kernels/film.hip holds the session's film kernels (kernels/main.hip: everything but
+    """The sources -> objects in parallel -> one shared library. The kernels of kernels.hip are instantiated by four units, and kernels/film.hip holds the session's film kernels and kernels/features.hip
+    (+ features_wide.hip) the feature pass (kernels/main.hip: everything but
     the interpreter builds of the stage scheduler; interp.hip: only those, the heaviest kernels; product.hip: their PRODUCT forms;
     wide.hip: the wide interpreter build, for programs that need more registers than the in-register file) so that the parts build
     side by side: 120 s -> ~50 s. -DPYR_PHASE_PROFILE builds keep one translation unit (their device-side counters are one variable)
@@ -103,7 +105,7 @@ def compile_library(out, extra_flags=(), verbose=False):
     import tempfile
 
     flags = [f for f in FLAGS if f != "-shared"] + list(extra_flags)
-    kernel_units = [PROFILE_UNIT, "film.hip"] if any("PYR_PHASE_PROFILE" in f for f in extra_flags) else KERNEL_UNITS
+    kernel_units = [PROFILE_UNIT] + PLAIN_UNITS if any("PYR_PHASE_PROFILE" in f for f in extra_flags) else KERNEL_UNITS
     units = [os.path.join("kernels", unit) for unit in kernel_units] + SOURCES
     with tempfile.TemporaryDirectory(prefix="pyrite_build_") as tmp:
         jobs = []

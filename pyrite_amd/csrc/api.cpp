@@ -1599,4 +1599,95 @@ int pyr_render_simple_progressive(PyrScene* scene, const PyrCamera* camera, cons
     return pyr_session_film(raw, film_inout);
 }
 
+// ------------------------------------------------------------------------------------------------ first-hit feature images
+} // extern "C"
+
+namespace {
+
+// What the three feature entries refuse before a device is looked for. `what` names the scene or session argument.
+int check_feature_args(const void* owner, const char* what, const PyrCamera* camera, bool need_camera, const PyrFilmDesc* film, const PyrFeatureParams* fp,
+                       const void* albedo, const void* pixels) {
+    if (!owner) return fail(PYR_ERR_INVALID_ARGUMENT, std::string("null argument: ") + what);
+    if (need_camera && !camera) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: camera");
+    if (!film) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: film");
+    if (!fp) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: fp");
+    if (!albedo && !pixels) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: the albedo and the pixel buffer are both null");
+    if (fp->grid < 1 || fp->grid > 8) return fail(PYR_ERR_INVALID_ARGUMENT, "fp->grid must be 1..8");
+    if (albedo && (fp->albedo_bins < 1 || fp->albedo_bins > 64)) return fail(PYR_ERR_INVALID_ARGUMENT, "fp->albedo_bins must be 1..64");
+    if (film->width == 0 || film->height == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "film: zero-sized image");
+    if (albedo && !(film->wl_width > 0.0f)) return fail(PYR_ERR_INVALID_ARGUMENT, "film: empty wavelength span");
+    if ((uint64_t)film->width * film->height >= 0xFFFFFFFFull) return fail(PYR_ERR_INVALID_ARGUMENT, "film: 2^32 pixels or more");
+    if (pyr_device_count() <= 0) return fail(PYR_ERR_DEVICE, "no HIP device is visible; pyrite_gpu has no CPU path");
+    return PYR_OK;
+}
+
+// Enqueues the pass on `stream`; the buffers are on the scene's device (either may be null).
+int enqueue_features(PyrScene* scene, const PyrCamera* camera, const PyrFilmDesc* film, const PyrFeatureParams* fp, PyrGrain* albedo, PyrFeaturePixel* pixels,
+                     hipStream_t stream) {
+    if (!scene->tail_count) HIP_TRY(hipMalloc((void**)&scene->tail_count, kFeedBytes));
+    HIP_TRY(hipMemsetAsync(scene->tail_count, 0, kFeedBytes, stream));
+    FeatureLaunch L{};
+    L.camera = *camera;
+    L.film = *film;
+    L.grid = fp->grid;
+    L.albedo_bins = albedo ? fp->albedo_bins : 0u;
+    L.albedo = albedo;
+    L.pixels = pixels;
+    L.next = scene->tail_count;
+    int rc = launch_features(scene->dev, L, stream, scene->num_cus, scene->program_info.wide != 0);
+    if (rc != PYR_OK) return fail(rc, feature_kernels_last_error());
+    return PYR_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int pyr_render_features_device(PyrScene* scene, const PyrCamera* camera, const PyrFilmDesc* film, const PyrFeatureParams* fp, PyrGrain* albedo_device,
+                               PyrFeaturePixel* pixels_device, void* hip_stream) {
+    if (((uintptr_t)pixels_device & 15u) != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "pixels_device must be 16-byte aligned"); // records are written as 16-byte vectors
+    int rc = check_feature_args(scene, "scene", camera, true, film, fp, albedo_device, pixels_device);
+    if (rc != PYR_OK) return rc;
+    HIP_TRY(hipSetDevice(scene->device));
+    return enqueue_features(scene, camera, film, fp, albedo_device, pixels_device, (hipStream_t)hip_stream);
+}
+
+int pyr_render_features(PyrScene* scene, const PyrCamera* camera, const PyrFilmDesc* film, const PyrFeatureParams* fp, PyrGrain* albedo_inout,
+                        PyrFeaturePixel* pixels_out) {
+    int rc = check_feature_args(scene, "scene", camera, true, film, fp, albedo_inout, pixels_out);
+    if (rc != PYR_OK) return rc;
+    HIP_TRY(hipSetDevice(scene->device));
+    const size_t pixels = (size_t)film->width * film->height;
+    const size_t albedo_bytes = albedo_inout ? pixels * fp->albedo_bins * sizeof(PyrGrain) : 0, pixel_bytes = pixels_out ? pixels * sizeof(PyrFeaturePixel) : 0;
+    DeviceBuffer albedo_dev, pixels_dev;
+    if (albedo_inout && (rc = albedo_dev.upload(albedo_inout, albedo_bytes)) != PYR_OK) return rc;
+    if (pixels_out && (rc = pixels_dev.alloc(pixel_bytes)) != PYR_OK) return rc;
+    if ((rc = enqueue_features(scene, camera, film, fp, (PyrGrain*)albedo_dev.ptr, (PyrFeaturePixel*)pixels_dev.ptr, nullptr)) != PYR_OK) return rc;
+    HIP_TRY(hipDeviceSynchronize());
+    if (albedo_inout) HIP_TRY(hipMemcpy(albedo_inout, albedo_dev.ptr, albedo_bytes, hipMemcpyDeviceToHost));
+    if (pixels_out) HIP_TRY(hipMemcpy(pixels_out, pixels_dev.ptr, pixel_bytes, hipMemcpyDeviceToHost));
+    return PYR_OK;
+}
+
+int pyr_session_features(PyrSession* session, const PyrFeatureParams* fp, PyrGrain* albedo_out, PyrFeaturePixel* pixels_out) {
+    int rc = check_feature_args(session, "session", nullptr, false, session ? &session->film : nullptr, fp, albedo_out, pixels_out);
+    if (rc != PYR_OK) return rc;
+    if ((rc = session_ready(session)) != PYR_OK) return rc;
+    const size_t pixels = (size_t)session->film.width * session->film.height;
+    const size_t albedo_bytes = albedo_out ? pixels * fp->albedo_bins * sizeof(PyrGrain) : 0, pixel_bytes = pixels_out ? pixels * sizeof(PyrFeaturePixel) : 0;
+    DeviceBuffer albedo_dev, pixels_dev;
+    if (albedo_out) {
+        if ((rc = albedo_dev.alloc(albedo_bytes)) != PYR_OK) return rc;
+        HIP_TRY(hipMemsetAsync(albedo_dev.ptr, 0, albedo_bytes, session->stream));
+    }
+    if (pixels_out && (rc = pixels_dev.alloc(pixel_bytes)) != PYR_OK) return rc;
+    rc = enqueue_features(session->scene, &session->camera, &session->film, fp, (PyrGrain*)albedo_dev.ptr, (PyrFeaturePixel*)pixels_dev.ptr, session->stream);
+    if (rc == PYR_OK && albedo_out && hipMemcpyAsync(albedo_out, albedo_dev.ptr, albedo_bytes, hipMemcpyDeviceToHost, session->stream) != hipSuccess)
+        rc = fail(PYR_ERR_DEVICE, "hipMemcpyAsync of the albedo film failed");
+    if (rc == PYR_OK && pixels_out && hipMemcpyAsync(pixels_out, pixels_dev.ptr, pixel_bytes, hipMemcpyDeviceToHost, session->stream) != hipSuccess)
+        rc = fail(PYR_ERR_DEVICE, "hipMemcpyAsync of the feature records failed");
+    const int synced = session_sync(session); // before the buffers above are freed, whatever happened
+    return rc != PYR_OK ? rc : synced;
+}
+
 } // extern "C"

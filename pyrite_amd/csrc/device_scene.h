@@ -261,6 +261,22 @@ struct AssembleLaunch {
 };
 int launch_assemble(const AssembleLaunch& launch, void* stream);
 
+// kernels/features.hip: the first-hit feature pass. An item is a pixel; 64 consecutive items are an 8 x 8
+// pixel square (the launcher numbers them and sets `n`, `squares_x`, `reserve` and `stack_lds`).
+struct FeatureLaunch {
+    PyrCamera camera; // aperture is not read: the lens is its centre
+    PyrFilmDesc film; // width, height and the wavelength span; bins is not read
+    uint32_t grid, albedo_bins;
+    PyrGrain* albedo;        // device, height * width * albedo_bins grains, added into; or nullptr
+    PyrFeaturePixel* pixels; // device, height * width records, overwritten; or nullptr
+    uint32_t* next;          // device, kFeedBytes, zero at launch: the work-feed cursors
+    uint32_t n, squares_x, reserve, stack_lds;
+};
+using FeatureKernel = void (*)(DevScene, FeatureLaunch);
+FeatureKernel pick_wide_features_kernel(); // kernels/features_wide.hip: the build whose interpreter holds the wide register file
+int launch_features(const DevScene& scene, const FeatureLaunch& launch, void* stream, int num_cus, bool wide_vm);
+const char* feature_kernels_last_error();
+
 // launchers (kernels/main.hip)
 // wide_vm: the scene has a program that only the wide interpreter build (kernels/wide.hip) holds
 int launch_render(const DevScene& scene, const RenderLaunch& launch, bool with_counters, void* stream, int num_cus, bool wide_vm = false);

@@ -1283,6 +1283,63 @@ std::vector<float> Session::noise() {
     return out;
 }
 
+// ---- first-hit feature images --------------------------------------------------------------------------------------------------
+Features Renderer::features(uint32_t width, uint32_t height, const Camera& camera, World& world, uint32_t grid, uint32_t albedo_bins, int device) const {
+    Features out{Film(width, height, albedo_bins, spectrum_span[0], spectrum_span[1]), std::vector<PyrFeaturePixel>((size_t)width * height)};
+    const PyrFilmDesc d = out.albedo.desc();
+    const PyrFeatureParams fp{grid, albedo_bins, {0, 0}};
+    check_status(pyr_render_features(world.scene(device), &camera.c, &d, &fp, out.albedo.grains.data(), out.pixels.data()));
+    return out;
+}
+Features Session::features(uint32_t grid, uint32_t albedo_bins) {
+    Features out{Film(width_, height_, albedo_bins, shape_.wavelength_start, shape_.wavelength_start + shape_.wavelength_width), std::vector<PyrFeaturePixel>((size_t)width_ * height_)};
+    const PyrFeatureParams fp{grid, albedo_bins, {0, 0}};
+    check_status(pyr_session_features(handle_, &fp, out.albedo.grains.data(), out.pixels.data()));
+    return out;
+}
+namespace {
+uint8_t unit_to_byte(float v) { // pyrite_amd/features.py _to_byte: NaN and anything below 0 give 0, anything above 1 gives 255
+    v = v > 0.0f ? v : 0.0f;
+    v = v < 1.0f ? v : 1.0f;
+    return (uint8_t)(v * 255.0f + 0.5f);
+}
+} // namespace
+std::vector<uint8_t> encode_normal_image(const std::vector<PyrFeaturePixel>& pixels) {
+    std::vector<uint8_t> rgb(pixels.size() * 3, 0);
+    for (size_t i = 0; i < pixels.size(); ++i)
+        if (pixels[i].coverage > 0.0f)
+            for (int c = 0; c < 3; ++c) rgb[3 * i + c] = unit_to_byte(0.5f * pixels[i].normal[c] + 0.5f);
+    return rgb;
+}
+std::vector<uint8_t> encode_depth_image(const std::vector<PyrFeaturePixel>& pixels) {
+    std::vector<uint8_t> rgb(pixels.size() * 3, 0);
+    bool any = false;
+    float lo = 0.0f, hi = 0.0f;
+    for (const PyrFeaturePixel& p : pixels)
+        if (p.coverage > 0.0f) {
+            lo = any ? std::min(lo, p.depth) : p.depth;
+            hi = any ? std::max(hi, p.depth) : p.depth;
+            any = true;
+        }
+    for (size_t i = 0; i < pixels.size(); ++i)
+        if (pixels[i].coverage > 0.0f) {
+            const uint8_t grey = unit_to_byte(hi > lo ? (hi - pixels[i].depth) / (hi - lo) : 1.0f);
+            rgb[3 * i] = rgb[3 * i + 1] = rgb[3 * i + 2] = grey;
+        }
+    return rgb;
+}
+void write_feature_images(const std::string& prefix, const Features& features, const std::optional<Expression>& filter, const std::optional<Expression>& white, int device) {
+    const uint32_t w = features.albedo.width, h = features.albedo.height;
+    save_png(prefix + "_albedo.png", features.albedo.develop(filter, white, 2.0f, device), w, h);
+    save_png(prefix + "_normal.png", encode_normal_image(features.pixels), w, h);
+    save_png(prefix + "_depth.png", encode_depth_image(features.pixels), w, h);
+}
+std::string features_flag_problem(bool features, const std::optional<long>& features_grid) {
+    if (features_grid && !features) return "--features-grid needs --features";
+    if (features_grid && (*features_grid < 1 || *features_grid > 8)) return "--features-grid must be 1 to 8";
+    return "";
+}
+
 std::string progressive_flag_problem(const std::optional<long>& pass_samples, bool preview, double preview_every, bool noise) {
     if (pass_samples && *pass_samples < 1) return "--pass-samples must be at least 1";
     if (!(preview_every >= 0.0)) return "--preview-every must not be negative";

@@ -4,6 +4,8 @@
 //   pyrite_host_tool dump   <scene> <data_dir> <out.bin>                      flatten only (no GPU): canonical scene bytes + camera + renderer
 //   pyrite_host_tool dump-project   <project.lua> <texel dir | -> <out.bin>    the same for a project file (lua_project.cpp)
 //   pyrite_host_tool render-project <project.lua> <texel dir | -> <seed> <out.png> [film.bin]   what `pyrite project.lua` does (main.rs:46-330)
+//                                   [--size WxH] [--spp N] [--features PREFIX] [--features-grid N] and the progressive flags of python -m pyrite_amd
+//   pyrite_host_tool encode-features <records.bin> <normal.rgb> <depth.rgb>    PyrFeaturePixel[n] -> the 8-bit normal and depth images, raw RGB (no GPU)
 //   pyrite_host_tool intersect <scene> <data_dir> <rays.f32> <hits.bin>       World::intersect for a ray batch ([n][6] f32 -> PyrHit[n])
 //   pyrite_host_tool render <scene> <data_dir> <w> <h> <spp> <seed> <film.bin> [out.png]
 //                                                                             Renderer::render on device 0; film as raw {acc, weight} f32
@@ -244,6 +246,8 @@ int main(int argc, char** argv) {
             std::string preview_path, film_path;
             double preview_every = 20.0; // main.rs:262
             bool noise = false;
+            std::string features_prefix, size;
+            std::optional<long> features_grid, spp;
             for (int i = 6; i < argc; ++i) {
                 const std::string a = argv[i];
                 auto value = [&]() -> const char* {
@@ -258,17 +262,32 @@ int main(int argc, char** argv) {
                     preview_every = std::strtod(value(), nullptr);
                 else if (a == "--noise")
                     noise = true;
+                else if (a == "--features")
+                    features_prefix = value();
+                else if (a == "--features-grid")
+                    features_grid = std::strtol(value(), nullptr, 10);
+                else if (a == "--size")
+                    size = value();
+                else if (a == "--spp")
+                    spp = std::strtol(value(), nullptr, 10);
                 else if (a.rfind("--", 0) == 0)
                     throw ProjectError("unknown flag " + a);
                 else
                     film_path = a;
             }
-            const std::string problem = progressive_flag_problem(pass_samples, !preview_path.empty(), preview_every, noise);
+            std::string problem = progressive_flag_problem(pass_samples, !preview_path.empty(), preview_every, noise);
+            if (problem.empty()) problem = features_flag_problem(!features_prefix.empty(), features_grid);
             if (!problem.empty()) {
                 std::fprintf(stderr, "error: %s\n", problem.c_str());
                 return 2;
             }
-            const LoadedProject loaded = load_project(argv[2], std::string(argv[3]) == "-" ? TextureLoader() : texel_files(argv[3]));
+            LoadedProject loaded = load_project(argv[2], std::string(argv[3]) == "-" ? TextureLoader() : texel_files(argv[3]));
+            if (!size.empty()) { // WIDTHxHEIGHT, as python -m pyrite_amd --size
+                char* rest = nullptr;
+                loaded.project.image.width = (uint32_t)std::strtoul(size.c_str(), &rest, 10);
+                loaded.project.image.height = (uint32_t)std::strtoul(rest && *rest ? rest + 1 : "0", nullptr, 10);
+            }
+            if (spp && *spp > 0) loaded.project.renderer.pixel_samples = (uint32_t)*spp;
             const Project& project = loaded.project;
             std::unique_ptr<World> world = World::from_project(project.world, loaded.base_dir);
             const Camera cam = Camera::from_project(project.camera);
@@ -307,6 +326,21 @@ int main(int argc, char** argv) {
                 std::ofstream f(film_path, std::ios::binary);
                 f.write(reinterpret_cast<const char*>(film.grains.data()), (std::streamsize)(film.grains.size() * sizeof(PyrGrain)));
             }
+            if (!features_prefix.empty()) {
+                write_feature_images(features_prefix, r.features(film.width, film.height, cam, *world, features_grid ? (uint32_t)*features_grid : 1u), project.image.filter,
+                                     project.image.white);
+                std::printf("wrote %s_albedo.png, %s_normal.png, %s_depth.png\n", features_prefix.c_str(), features_prefix.c_str(), features_prefix.c_str());
+            }
+            return 0;
+        }
+        if (argc >= 5 && std::string(argv[1]) == "encode-features") { // encode-features <records.bin> <normal.rgb> <depth.rgb>
+            std::ifstream in(argv[2], std::ios::binary);
+            std::vector<char> bytes((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+            std::vector<PyrFeaturePixel> pixels(bytes.size() / sizeof(PyrFeaturePixel));
+            std::memcpy(pixels.data(), bytes.data(), pixels.size() * sizeof(PyrFeaturePixel));
+            const std::vector<uint8_t> normal = encode_normal_image(pixels), depth = encode_depth_image(pixels);
+            std::ofstream(argv[3], std::ios::binary).write(reinterpret_cast<const char*>(normal.data()), (std::streamsize)normal.size());
+            std::ofstream(argv[4], std::ios::binary).write(reinterpret_cast<const char*>(depth.data()), (std::streamsize)depth.size());
             return 0;
         }
         if (argc >= 5 && std::string(argv[1]) == "dump") {

@@ -1009,8 +1009,10 @@ DEV void sphere_texture(f3 normal, float scale_x, float scale_y, float& latitude
 
 // SurfacePoint::get_surface_data with texture coordinates (shapes/mod.rs:346-385, :454-469, :484-494) followed by
 // Material::apply_normal_map (materials/mod.rs:68-80, tracer.rs:227-232): the shading normal, the material, the texture
-// coordinates. The tangent frame is only built for materials that have a normal map.
-DEV void surface_textured(const DevScene& S, const Hit& hit, f3 o, f3 d, f3& position, f3& normal, uint32_t& material, float& tx, float& ty) {
+// coordinates. The tangent frame is only built for materials that have a normal map. `normal_map_wavelength` is the wavelength the
+// normal map's program sees (the render kernels leave it 0; the feature pass, kernels/features.hip, states one).
+DEV void surface_textured(const DevScene& S, const Hit& hit, f3 o, f3 d, f3& position, f3& normal, uint32_t& material, float& tx, float& ty,
+                          float normal_map_wavelength = 0.0f) {
     const uint32_t kind = hit.shape >> 30, index = hit.shape & 0x3FFFFFFFu;
     Quat frame{1.0f, 0.0f, 0.0f, 0.0f};
     if (kind == PYR_SHAPE_TRIANGLE) {
@@ -1066,7 +1068,7 @@ DEV void surface_textured(const DevScene& S, const Hit& hit, f3 o, f3 d, f3& pos
         const DevProgram prog = S.programs[normal_map];
         float v[4] = {prog.constant, prog.constant, prog.constant, prog.constant};
         if (prog.kind != PYR_PROGRAM_CONSTANT) { // in line: an out-of-line call here spills the walker around itself
-            const VmInput in{0.0f, normal, d, tx, ty};
+            const VmInput in{normal_map_wavelength, normal, d, tx, ty};
             Vm vm;
             for (uint32_t k = 0; k < prog.num_instrs; ++k) vm.step(S, S.instrs[prog.first_instr + k], in);
             if (prog.output_kind == PYR_OUTPUT_NUMBER)

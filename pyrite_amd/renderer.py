@@ -120,6 +120,16 @@ class Renderer:
         the GPU; with `film` the session continues from that host Film. See Session."""
         return Session(self, film_size, camera, world, halves=halves, device=device, film=film)
 
+    def features(self, film_size, camera: Camera, world: World, grid=1, albedo_bins=16, device=0):
+        """The first-hit feature images of `film_size` = (width, height) (pyr_render_features): albedo film, shading normal,
+        depth, coverage, shape and material id per pixel, from grid x grid sub-samples, without noise. See features.Features."""
+        from .features import Features
+
+        out = Features(film_size[0], film_size[1], albedo_bins, self.spectrum_span)
+        desc, fp = out.albedo.desc(), abi.PyrFeatureParams(int(grid), int(albedo_bins))
+        check(lib().pyr_render_features(world.scene(device), C.byref(camera.c), C.byref(desc), C.byref(fp), out.albedo.grains.ctypes.data, out.records.ctypes.data))
+        return out
+
     def path_info(self, world: World, device=0):
         """Which kernel a render of `world` with this renderer would run (pyr_scene_path_info): a dict of PyrPathInfo's fields."""
         info, params = abi.PyrPathInfo(), self.params()
@@ -241,6 +251,16 @@ class Session:
         """The film so far as a host Film (the sum of the halves when there are two)."""
         out = Film(self.width, self.height, self._film.bins, (self._film.wavelength_start, self._film.wavelength_start + self._film.wavelength_width))
         check(lib().pyr_session_film(self.handle, out.grains.ctypes.data))
+        return out
+
+    def features(self, grid=1, albedo_bins=16):
+        """Renderer.features for the session's camera and image size, on the session's stream after the passes enqueued so far
+        (pyr_session_features). The session's film is not touched."""
+        from .features import Features
+
+        out = Features(self.width, self.height, albedo_bins, (self._film.wavelength_start, self._film.wavelength_start + self._film.wavelength_width))
+        fp = abi.PyrFeatureParams(int(grid), int(albedo_bins))
+        check(lib().pyr_session_features(self.handle, C.byref(fp), out.albedo.grains.ctypes.data, out.records.ctypes.data))
         return out
 
     def half_films(self):
