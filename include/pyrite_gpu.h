@@ -667,6 +667,84 @@ int pyr_render_features_device(PyrScene* scene, const PyrCamera* camera, const P
  * touched, and further passes may follow. */
 int pyr_session_features(PyrSession* session, const PyrFeatureParams* fp, PyrGrain* albedo_out, PyrFeaturePixel* pixels_out);
 
+/* ---------------------------------------------------------------- linear images and tone mapping ---------------
+ * pyr_film_develop ends in 8 bits behind a hard clamp (main.rs:315-327). These entries stop one step earlier and hand out the image
+ * in linear light, three f32 per pixel, row-major: PYR_LINEAR_XYZ is spectrum_to_xyz's result after `xyz_scale`, PYR_LINEAR_SRGB
+ * the linear sRGB triple the 8-bit path clamps and encodes -- the same operations in the same order, so the floats are the very
+ * values pyr_film_develop encodes. The last pixel of the film is 0, 0, 0, as it is black there (film.rs:299). A second film
+ * `grains_b` (NULL: none) is developed as grains + grains_b, accs added and weights added, the sum a session with halves holds.
+ *
+ * Statistics (of a linear sRGB image). Per pixel, in f32 and unfused:  Y = (0.2126f*R + 0.7152f*G) + 0.0722f*B.  A pixel is LIT
+ * when Y > 0 and DARK otherwise (zero, negative, NaN). Lit pixels fill a histogram of 256 bins, 8 per octave over [2^-16, 2^16),
+ * read off the bits of Y:  bin = clamp((int)(bits(Y) >> 20) - 888, 0, 255)  -- 888 = 111 << 3 is the biased exponent of 2^-16 with
+ * three mantissa bits below it; smaller values (denormals too) fall into bin 0, larger ones and +inf into bin 255. Bin k ends below
+ * upper_edge(k) = float_of_bits((k + 889) << 20). min_lit / max_lit are the extremes of Y over the lit pixels (0 when none is).
+ * All counters are integers: the result does not depend on the order of the pixels and two calls give the same bits.
+ *
+ * Tone mapping (linear sRGB -> 8-bit sRGB), f32 and unfused, clamp(x) = fminf(fmaxf(x, 0), 1) (a NaN becomes 0):
+ *   PYR_TONE_CLIP      v_c = clamp(exposure * c)                                   with exposure 1: pyr_film_develop to the byte
+ *   PYR_TONE_REINHARD  a pixel that is not lit is black; else  L = exposure * Y,  Ld = (L * (1.0f + L / (white*white))) / (1.0f + L),
+ *                      s = Ld / L,  v_c = clamp((exposure * c) * s)                extended Reinhard on luminance: L = white -> 1
+ *   byte_c = (uint8)(e * 255.0f + 0.5f),  e = clamp(v <= 0.0031308f ? 12.92f*v : 1.055f*(float)pow((double)v, 1.0/2.4) - 0.055f)
+ *
+ * The automatic rule (pyr_tone_resolve, host arithmetic only). With target(p) = ceil((double)p * lit) clipped to 1..lit and
+ * bin(p) = the first bin whose cumulative count reaches target(p):
+ *   exposure <= 0:  exposure = key / upper_edge(bin(percentile))   -- the median luminance lands on `key`; 1 when nothing is lit
+ *   white <= 0 (PYR_TONE_REINHARD only; PYR_TONE_CLIP does not read it and gets 1):
+ *                   white = exposure * upper_edge(bin(white_percentile));           1 when nothing is lit
+ * The usual values are key 0.18, percentile 0.5, white_percentile 0.99 (PYR_TONE_KEY, PYR_TONE_PERCENTILE, PYR_TONE_WHITE_PERCENTILE). */
+#define PYR_LINEAR_XYZ 0u
+#define PYR_LINEAR_SRGB 1u
+#define PYR_TONE_CLIP 0u
+#define PYR_TONE_REINHARD 1u
+#define PYR_TONE_KEY 0.18f
+#define PYR_TONE_PERCENTILE 0.5f
+#define PYR_TONE_WHITE_PERCENTILE 0.99f
+typedef struct PyrImageStats {
+    uint32_t histogram[256];
+    uint32_t lit, dark;
+    float min_lit, max_lit;
+} PyrImageStats; /* 1040 bytes */
+typedef struct PyrToneParams {
+    uint32_t op;            /* PYR_TONE_CLIP or PYR_TONE_REINHARD */
+    float exposure;         /* a factor on the linear values; <= 0: automatic */
+    float white;            /* the exposed luminance that becomes 1 (PYR_TONE_REINHARD); <= 0: automatic */
+    float key;              /* > 0, read when the exposure is automatic */
+    float percentile;       /* in (0, 1] */
+    float white_percentile; /* in (0, 1] */
+} PyrToneParams;
+
+/* Every entry below checks its arguments before it looks for a device: PYR_ERR_INVALID_ARGUMENT for a null pointer, an unknown
+ * `space` or `op`, bad development parameters, a percentile outside (0, 1], a key that is not positive; PYR_ERR_UNSUPPORTED for an
+ * image of more than 2^32 - 1 pixels (the counters are 32 bits wide); then PYR_ERR_DEVICE when there is no such device. */
+
+/* HOST grains (grains_b may be NULL) -> HOST out, height*width*3 floats. Blocking. */
+int pyr_film_develop_linear(const PyrFilmDesc* film, const PyrGrain* grains, const PyrGrain* grains_b, const PyrDevelopParams* params, uint32_t space,
+                            float* out, int device);
+/* Same with the films and the output resident on `device`, enqueued on `hip_stream` (the PyrDevelopParams arrays stay HOST pointers). */
+int pyr_film_develop_linear_device(const PyrFilmDesc* film, const PyrGrain* grains_device, const PyrGrain* grains_b_device, const PyrDevelopParams* params,
+                                   uint32_t space, float* out_device, int device, void* hip_stream);
+/* linear_srgb: HOST, height*width*3 floats; out: HOST. Blocking. */
+int pyr_image_stats(const float* linear_srgb, uint32_t width, uint32_t height, PyrImageStats* out, int device);
+/* Both buffers on `device`; enqueued on `hip_stream`, `out_device` is valid in stream order. */
+int pyr_image_stats_device(const float* linear_srgb_device, uint32_t width, uint32_t height, PyrImageStats* out_device, int device, void* hip_stream);
+/* The automatic rule above; no device is touched. `stats` may be NULL when nothing is automatic. Writes the exposure and the white
+ * point pyr_image_tonemap is to be called with. */
+int pyr_tone_resolve(const PyrImageStats* stats, const PyrToneParams* tone, float* exposure_out, float* white_out);
+/* `resolved`: exposure > 0 and, for PYR_TONE_REINHARD, white > 0 (else PYR_ERR_INVALID_ARGUMENT); key and the percentiles are not
+ * read. HOST buffers, rgb_out = height*width*3 bytes. Blocking. */
+int pyr_image_tonemap(const float* linear_srgb, uint32_t width, uint32_t height, const PyrToneParams* resolved, uint8_t* rgb_out, int device);
+int pyr_image_tonemap_device(const float* linear_srgb_device, uint32_t width, uint32_t height, const PyrToneParams* resolved, uint8_t* rgb_device, int device,
+                             void* hip_stream);
+/* The session's film as it stands after every pass enqueued so far (A + B with halves), developed to a linear image on the session's
+ * stream: out = HOST, height*width*3 floats. Blocking. */
+int pyr_session_linear(PyrSession* session, const PyrDevelopParams* develop_params, uint32_t space, float* out);
+/* pyr_session_preview with a tone curve: linear sRGB development, statistics (only when something is automatic or they are asked
+ * for), pyr_tone_resolve, tone mapping -- all on the session's stream and device. rgb_out = HOST, height*width*3 bytes; stats_out
+ * (HOST) may be NULL. The linear image does not cross the bus. Blocking. */
+int pyr_session_preview_tone(PyrSession* session, const PyrDevelopParams* develop_params, const PyrToneParams* tone, uint8_t* rgb_out,
+                             PyrImageStats* stats_out);
+
 #ifdef __cplusplus
 }
 #endif

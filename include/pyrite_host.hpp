@@ -285,6 +285,30 @@ class Film { // film.rs:9-18
 };
 void save_png(const std::string& path, const std::vector<uint8_t>& rgb, uint32_t width, uint32_t height);
 
+// ---- linear images and tone mapping (pyrite_gpu.h "linear images and tone mapping"; pyrite_amd/develop.py has the same surface) ----
+// [height][width][3] f32 of `film` (+ `film_b`, grain by grain) on the GPU: CIE XYZ or the linear sRGB triple Film::develop clamps and encodes.
+std::vector<float> develop_linear(const Film& film, uint32_t space = PYR_LINEAR_SRGB, const std::optional<Expression>& filter = std::nullopt,
+                                  const std::optional<Expression>& white = std::nullopt, float step_size = 2.0f, int device = 0, const Film* film_b = nullptr);
+PyrImageStats image_stats(const std::vector<float>& linear_srgb, uint32_t width, uint32_t height, int device = 0);
+// exposure / white <= 0: automatic (pyr_tone_resolve)
+PyrToneParams tone_params(uint32_t op = PYR_TONE_CLIP, float exposure = 0.0f, float white = 0.0f);
+// 8-bit sRGB of a linear sRGB image; what `tone` leaves automatic is resolved from the image's statistics, taken here.
+std::vector<uint8_t> tonemap(const std::vector<float>& linear_srgb, uint32_t width, uint32_t height, const PyrToneParams& tone, int device = 0);
+// The bytes of a Radiance RGBE picture (flat scanlines) and of a colour PFM file (little-endian, rows bottom to top) of a linear
+// image, pure functions (csrc/host/images.cpp; pyrite_amd/develop.py encode_hdr / encode_pfm write the same bytes). RGBE is Ward's
+// mapping in f64: a channel that is not positive is 0, one above kRgbeMax (+inf too) is kRgbeMax; m = the largest channel;
+// m < 1e-32: four zero bytes; else m = f * 2^e, f in [0.5, 1): mantissa bytes (uint8)(c * (f * 256 / m)), exponent byte e + 128.
+constexpr double kRgbeMax = 255.0 * 0x1p119; // the largest value a pixel holds: mantissa 255, exponent byte 255
+std::vector<uint8_t> encode_hdr(const std::vector<float>& rgb, uint32_t width, uint32_t height);
+std::vector<uint8_t> encode_pfm(const std::vector<float>& rgb, uint32_t width, uint32_t height);
+void write_hdr(const std::string& path, const std::vector<float>& rgb, uint32_t width, uint32_t height);
+void write_pfm(const std::string& path, const std::vector<float>& rgb, uint32_t width, uint32_t height);
+void write_linear(const std::string& path, const std::vector<float>& rgb, uint32_t width, uint32_t height); // --hdr PATH: .hdr or .pfm by the extension
+// What is wrong with --hdr / --exposure / --tone, in the words both front ends print, or "" (pyrite_amd/develop.py tone_flag_problem).
+std::string tone_flag_problem(const std::optional<std::string>& hdr, const std::optional<std::string>& exposure, const std::optional<std::string>& tone);
+// The tone parameters of --exposure EV|auto and --tone clip|reinhard, or nothing when neither is given (pyrite_amd/develop.py tone_from_flags).
+std::optional<PyrToneParams> tone_from_flags(const std::optional<std::string>& exposure, const std::optional<std::string>& tone);
+
 struct Progress { // renderer/mod.rs:229-232
     uint8_t progress;
     const char* message;
@@ -342,6 +366,12 @@ class Session {
     uint32_t samples_done() const;
     // main.rs:261-299: [height][width][3] sRGB of the film as it stands, with the image's filter / white programs
     std::vector<uint8_t> preview(float step_size = 30.0f, const std::optional<Expression>& filter = std::nullopt, const std::optional<Expression>& white = std::nullopt);
+    // pyr_session_preview_tone: the preview through a tone curve; `stats`, when given, receives the linear image's statistics
+    std::vector<uint8_t> preview_tone(const PyrToneParams& tone, float step_size = 30.0f, const std::optional<Expression>& filter = std::nullopt,
+                                      const std::optional<Expression>& white = std::nullopt, PyrImageStats* stats = nullptr);
+    // pyr_session_linear: [height][width][3] f32, the film as it stands in linear light
+    std::vector<float> linear(uint32_t space = PYR_LINEAR_SRGB, float step_size = 2.0f, const std::optional<Expression>& filter = std::nullopt,
+                              const std::optional<Expression>& white = std::nullopt);
     Film film();
     std::vector<float> noise(); // per tile of the make_tiles grid, raster order (pyr_session_noise): needs halves and two passes
     Features features(uint32_t grid = 1, uint32_t albedo_bins = 16); // pyr_session_features: after the passes enqueued so far; the film is not touched
@@ -386,5 +416,7 @@ extern "C" uint64_t pyrh_serialize_desc(const PyrSceneDesc* desc, uint8_t* out, 
 // pyrite::save_png through a C entry point (tests). Returns 0 on success.
 extern "C" int64_t pyrh_test_load_texture(const char* path, int linear, int mono, float* out, uint64_t capacity, uint32_t* width, uint32_t* height);
 extern "C" int pyrh_test_png(const char* path, const uint8_t* rgb, uint32_t width, uint32_t height);
+// pyrite::write_hdr (pfm == 0) / write_pfm through a C entry point (tests). Returns 0 on success.
+extern "C" int pyrh_test_linear_image(const char* path, const float* rgb, uint32_t width, uint32_t height, int pfm);
 
 #endif // PYRITE_HOST_HPP

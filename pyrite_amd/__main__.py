@@ -4,7 +4,7 @@
 
     python -m pyrite_amd path/to/project.lua [-o out.png] [--seed N] [--device D] [--spp N] [--size WxH]
                          [--pass-samples N] [--preview PATH] [--preview-every SECONDS] [--noise]
-                         [--features PREFIX] [--features-grid N]
+                         [--features PREFIX] [--features-grid N] [--hdr PATH] [--exposure EV|auto] [--tone clip|reinhard]
 
 With --pass-samples, --preview or --noise the render runs as a progressive session (pyr_session_*): passes of N samples per pixel
 over the whole image, the preview image rewritten from the live film every SECONDS or more (main.rs:261-299; developed on the GPU
@@ -12,7 +12,12 @@ with step 30, main.rs:270), and with --noise the largest and the median per-tile
 final image is the one the plain render writes.
 
 With --features the first-hit feature pass (pyr_render_features, N x N sub-samples per pixel, default 1) runs after the render and
-writes PREFIX_albedo.png, PREFIX_normal.png and PREFIX_depth.png."""
+writes PREFIX_albedo.png, PREFIX_normal.png and PREFIX_depth.png.
+
+With --hdr the final film is also written in linear light (linear sRGB, step 2, the project's filter and white): Radiance RGBE for
+PATH.hdr, PFM for PATH.pfm. --exposure (stops, or auto: the median luminance to 0.18) and --tone (clip, or reinhard: the extended
+Reinhard curve on luminance; alone it means --exposure auto) apply to the final PNG and to the previews. Without them the PNG is
+the reference's hard clamp, byte for byte."""
 import argparse
 import os
 import sys
@@ -48,7 +53,7 @@ def render_progressive(r, cam, world, film, args, image, on_status):
             s.sync()
             on_status(s.samples_done * 100 // r.pixel_samples, "Rendering")
             if args.preview and time.monotonic() - last_image >= args.preview_every:
-                save_png(args.preview, s.preview(30.0, filter=image.get("filter"), white=image.get("white")))
+                save_png(args.preview, s.preview(30.0, filter=image.get("filter"), white=image.get("white"), tone=args.tone_params))
                 print("\nPreview updated (%d samples per pixel)" % s.samples_done)
                 if args.noise and s.samples_done >= 2 * pass_samples:
                     noise = s.noise()
@@ -71,16 +76,23 @@ def main(argv=None):
     ap.add_argument("--noise", action="store_true", help="print the largest and median per-tile noise estimate after each preview")
     ap.add_argument("--features", default=None, metavar="PREFIX", help="write PREFIX_albedo.png, PREFIX_normal.png and PREFIX_depth.png of the first hits")
     ap.add_argument("--features-grid", type=int, default=None, metavar="N", help="N x N sub-samples per pixel for --features (1 to 8, default 1)")
+    ap.add_argument("--hdr", default=None, metavar="PATH", help="also write the image in linear light: PATH.hdr (Radiance RGBE) or PATH.pfm")
+    ap.add_argument("--exposure", default=None, metavar="EV|auto", help="exposure of the PNG and the previews in stops, or auto")
+    ap.add_argument("--tone", default=None, metavar="clip|reinhard", help="tone curve of the PNG and the previews (reinhard alone means --exposure auto)")
     args = ap.parse_args(argv)
+    from .develop import tone_flag_problem, tone_from_flags
     from .features import features_flag_problem
 
-    problem = progressive_flag_problem(args.pass_samples, args.preview, args.preview_every, args.noise) or features_flag_problem(args.features, args.features_grid)
+    problem = (progressive_flag_problem(args.pass_samples, args.preview, args.preview_every, args.noise) or features_flag_problem(args.features, args.features_grid)
+               or tone_flag_problem(args.hdr, args.exposure, args.tone))
     if problem:
         print("error: " + problem, file=sys.stderr)
         return 2
 
+    args.tone_params = tone_from_flags(args.exposure, args.tone)
+
     from . import lua_project, scenes
-    from .develop import develop, save_png
+    from .develop import develop, develop_linear, save_linear, save_png, tonemap
 
     project, base_dir = lua_project.load_project(args.project)
     if args.size:
@@ -103,10 +115,19 @@ def main(argv=None):
         r.render(film, cam, world, on_status=on_status, device=args.device)
     print("\rRendering... done in %.2f s (%.1f Msamples/s)" % (time.time() - t, film.width * film.height * r.pixel_samples / (time.time() - t) / 1e6))
     print("Saving final result...")  # main.rs:313
-    rgb = develop(film, filter=image.get("filter"), white=image.get("white"), device=args.device)
+    linear = None
+    if args.hdr or args.tone_params is not None:
+        linear = develop_linear(film, "srgb", filter=image.get("filter"), white=image.get("white"), device=args.device)
+    if args.tone_params is not None:
+        rgb = tonemap(linear, args.tone_params, device=args.device)
+    else:
+        rgb = develop(film, filter=image.get("filter"), white=image.get("white"), device=args.device)
     out = args.output or os.path.join(base_dir, "render.png")
     save_png(out, rgb)
     print("wrote", out)
+    if args.hdr:
+        save_linear(args.hdr, linear)
+        print("wrote", args.hdr)
     if args.features:
         from .features import write_feature_images
 

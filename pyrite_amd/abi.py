@@ -283,6 +283,29 @@ class PyrFeaturePixel(C.Structure):
     ]
 
 
+PYR_LINEAR_XYZ, PYR_LINEAR_SRGB = 0, 1
+PYR_TONE_CLIP, PYR_TONE_REINHARD = 0, 1
+PYR_TONE_KEY, PYR_TONE_PERCENTILE, PYR_TONE_WHITE_PERCENTILE = 0.18, 0.5, 0.99
+
+
+class PyrImageStats(C.Structure):
+    _fields_ = [("histogram", C.c_uint32 * 256), ("lit", C.c_uint32), ("dark", C.c_uint32), ("min_lit", C.c_float), ("max_lit", C.c_float)]
+
+    def as_dict(self):
+        return {"histogram": list(self.histogram), "lit": int(self.lit), "dark": int(self.dark), "min_lit": float(self.min_lit), "max_lit": float(self.max_lit)}
+
+
+class PyrToneParams(C.Structure):
+    _fields_ = [
+        ("op", C.c_uint32),
+        ("exposure", C.c_float),
+        ("white", C.c_float),
+        ("key", C.c_float),
+        ("percentile", C.c_float),
+        ("white_percentile", C.c_float),
+    ]
+
+
 PyrProgressFn = C.CFUNCTYPE(None, C.c_void_p, C.c_uint8, C.c_char_p)
 PyrPreviewFn = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, C.c_uint32)
 
@@ -349,6 +372,18 @@ ENTRY_POINTS = {
         [C.c_void_p, C.POINTER(PyrCamera), C.POINTER(PyrFilmDesc), C.POINTER(PyrFeatureParams), C.c_void_p, C.c_void_p, C.c_void_p],
     ),
     "pyr_session_features": (C.c_int, [C.c_void_p, C.POINTER(PyrFeatureParams), C.c_void_p, C.c_void_p]),
+    "pyr_film_develop_linear": (C.c_int, [C.POINTER(PyrFilmDesc), C.c_void_p, C.c_void_p, C.POINTER(PyrDevelopParams), C.c_uint32, C.c_void_p, C.c_int]),
+    "pyr_film_develop_linear_device": (
+        C.c_int,
+        [C.POINTER(PyrFilmDesc), C.c_void_p, C.c_void_p, C.POINTER(PyrDevelopParams), C.c_uint32, C.c_void_p, C.c_int, C.c_void_p],
+    ),
+    "pyr_image_stats": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PyrImageStats), C.c_int]),
+    "pyr_image_stats_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.c_void_p, C.c_int, C.c_void_p]),
+    "pyr_tone_resolve": (C.c_int, [C.POINTER(PyrImageStats), C.POINTER(PyrToneParams), C.POINTER(C.c_float), C.POINTER(C.c_float)]),
+    "pyr_image_tonemap": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PyrToneParams), C.c_void_p, C.c_int]),
+    "pyr_image_tonemap_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PyrToneParams), C.c_void_p, C.c_int, C.c_void_p]),
+    "pyr_session_linear": (C.c_int, [C.c_void_p, C.POINTER(PyrDevelopParams), C.c_uint32, C.c_void_p]),
+    "pyr_session_preview_tone": (C.c_int, [C.c_void_p, C.POINTER(PyrDevelopParams), C.POINTER(PyrToneParams), C.c_void_p, C.POINTER(PyrImageStats)]),
 }
 
 

@@ -1348,7 +1348,7 @@ struct PyrSession {
     PyrRenderParams params{}; // pixel_samples = the whole budget
     bool halves = false;
     hipStream_t stream = nullptr;
-    DeviceBuffer film_a, film_b, sum, rgb, tables, noise;
+    DeviceBuffer film_a, film_b, sum, rgb, tables, noise, linear, stats;
     std::vector<float> host_tables;
     size_t grains = 0;
     uint32_t samples_done = 0, passes = 0;
@@ -1383,6 +1383,21 @@ int session_film(PyrSession* s, const PyrGrain** out) {
 int session_sync(PyrSession* s) {
     HIP_TRY(hipStreamSynchronize(s->stream));
     return check_tape_overflow(s->scene);
+}
+
+// The session's development tables on its device, in stream order, and the launch record that reads them (grains: A, and B with halves).
+int session_develop_launch(PyrSession* s, const PyrDevelopParams* p, DevelopLaunch& D) {
+    const size_t floats = 3 * (size_t)p->sample_count + 3 * (size_t)p->xyz_count;
+    if (floats * sizeof(float) > s->tables.bytes || !s->tables.ptr) {
+        HIP_TRY(hipStreamSynchronize(s->stream)); // an earlier preview may still read the old tables
+        s->tables.release();
+        if (int rc = s->tables.alloc(floats * sizeof(float))) return rc;
+    }
+    D = develop_launch(&s->film, p, (float*)s->tables.ptr, s->host_tables);
+    HIP_TRY(hipMemcpyAsync(s->tables.ptr, s->host_tables.data(), floats * sizeof(float), hipMemcpyHostToDevice, s->stream));
+    D.grains = (const PyrGrain*)s->film_a.ptr;
+    D.grains_b = s->halves ? (const PyrGrain*)s->film_b.ptr : nullptr;
+    return PYR_OK;
 }
 
 // What pyr_session_create and pyr_render_simple_progressive refuse before anything runs.
@@ -1484,16 +1499,8 @@ int pyr_session_preview(PyrSession* session, const PyrDevelopParams* develop_par
     if (rc != PYR_OK) return rc;
     if ((rc = check_develop_params(develop_params)) != PYR_OK) return rc;
     PyrSession* s = session;
-    const size_t floats = 3 * (size_t)develop_params->sample_count + 3 * (size_t)develop_params->xyz_count;
-    if (floats * sizeof(float) > s->tables.bytes || !s->tables.ptr) {
-        HIP_TRY(hipStreamSynchronize(s->stream)); // an earlier preview may still read the old tables
-        s->tables.release();
-        if ((rc = s->tables.alloc(floats * sizeof(float))) != PYR_OK) return rc;
-    }
-    DevelopLaunch D = develop_launch(&s->film, develop_params, (float*)s->tables.ptr, s->host_tables);
-    HIP_TRY(hipMemcpyAsync(s->tables.ptr, s->host_tables.data(), floats * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    D.grains = (const PyrGrain*)s->film_a.ptr;
-    D.grains_b = s->halves ? (const PyrGrain*)s->film_b.ptr : nullptr;
+    DevelopLaunch D{};
+    if ((rc = session_develop_launch(s, develop_params, D)) != PYR_OK) return rc;
     D.rgb_out = (uint8_t*)s->rgb.ptr;
     const PyrGrain* summed = nullptr;
     if (!develop_uses_wave(D)) { // the per-pixel kernel (of A + B where there are halves and the film has more bins than the wave kernel's rows)
@@ -1688,6 +1695,227 @@ int pyr_session_features(PyrSession* session, const PyrFeatureParams* fp, PyrGra
         rc = fail(PYR_ERR_DEVICE, "hipMemcpyAsync of the feature records failed");
     const int synced = session_sync(session); // before the buffers above are freed, whatever happened
     return rc != PYR_OK ? rc : synced;
+}
+
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------ linear images and tone mapping
+namespace {
+
+constexpr uint64_t kMaxImagePixels = 0xFFFFFFFFull; // PyrImageStats counts in 32 bits
+
+int check_image_size(uint32_t width, uint32_t height) {
+    if ((uint64_t)width * height > kMaxImagePixels) return fail(PYR_ERR_UNSUPPORTED, "an image of more than 2^32 - 1 pixels");
+    return PYR_OK;
+}
+int check_device(int device) {
+    if (pyr_device_count() <= device || device < 0) return fail(PYR_ERR_DEVICE, "no such HIP device; pyrite_gpu has no CPU path");
+    return PYR_OK;
+}
+int check_linear_args(const PyrFilmDesc* film, const void* grains, const PyrDevelopParams* p, uint32_t space, const void* out) {
+    if (!film || !grains || !p || !out || !p->xyz_table) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+    if (space != PYR_LINEAR_XYZ && space != PYR_LINEAR_SRGB) return fail(PYR_ERR_INVALID_ARGUMENT, "unknown space: PYR_LINEAR_XYZ or PYR_LINEAR_SRGB");
+    if (int bad = check_develop_params(p)) return bad;
+    if (film->bins == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "film: no bins");
+    return check_image_size(film->width, film->height);
+}
+bool percentile_ok(float p) { return p > 0.0f && p <= 1.0f; }
+// What pyr_tone_resolve refuses.
+int check_tone_params(const PyrToneParams* t) {
+    if (t->op != PYR_TONE_CLIP && t->op != PYR_TONE_REINHARD) return fail(PYR_ERR_INVALID_ARGUMENT, "unknown tone operator: PYR_TONE_CLIP or PYR_TONE_REINHARD");
+    if (!percentile_ok(t->percentile) || !percentile_ok(t->white_percentile)) return fail(PYR_ERR_INVALID_ARGUMENT, "a percentile outside (0, 1]");
+    if (!(t->exposure > 0.0f) && !(t->key > 0.0f)) return fail(PYR_ERR_INVALID_ARGUMENT, "an automatic exposure needs a positive key");
+    return PYR_OK;
+}
+bool tone_needs_stats(const PyrToneParams* t) { return !(t->exposure > 0.0f) || (t->op == PYR_TONE_REINHARD && !(t->white > 0.0f)); }
+// What pyr_image_tonemap refuses.
+int check_resolved_tone(const PyrToneParams* t) {
+    if (t->op != PYR_TONE_CLIP && t->op != PYR_TONE_REINHARD) return fail(PYR_ERR_INVALID_ARGUMENT, "unknown tone operator: PYR_TONE_CLIP or PYR_TONE_REINHARD");
+    if (!(t->exposure > 0.0f) || (t->op == PYR_TONE_REINHARD && !(t->white > 0.0f)))
+        return fail(PYR_ERR_INVALID_ARGUMENT, "unresolved tone parameters: pyr_tone_resolve gives the exposure and the white point");
+    return PYR_OK;
+}
+
+float upper_edge(uint32_t bin) {
+    const uint32_t bits = (bin + 889u) << 20;
+    float f;
+    std::memcpy(&f, &bits, sizeof(f));
+    return f;
+}
+uint32_t percentile_bin(const PyrImageStats* s, float percentile) {
+    uint64_t target = (uint64_t)std::ceil((double)percentile * (double)s->lit);
+    target = std::min<uint64_t>(std::max<uint64_t>(target, 1), s->lit);
+    uint64_t seen = 0;
+    for (uint32_t k = 0; k < 256; ++k) {
+        seen += s->histogram[k];
+        if (seen >= target) return k;
+    }
+    return 255; // a histogram that holds fewer than `lit` pixels
+}
+
+// Development to a linear image with the tables copied for the call, as develop_common does for the 8-bit image.
+int develop_linear_common(const PyrFilmDesc* film, const PyrGrain* grains_device, const PyrGrain* grains_b_device, const PyrDevelopParams* p, uint32_t space,
+                          float* out_device, hipStream_t stream, bool blocking) {
+    float* tables = nullptr;
+    const size_t floats = 3 * (size_t)p->sample_count + 3 * (size_t)p->xyz_count;
+    HIP_TRY(hipMallocAsync((void**)&tables, floats * sizeof(float), stream));
+    std::vector<float> host;
+    LinearLaunch L{};
+    L.develop = develop_launch(film, p, tables, host);
+    const hipError_t copied = hipMemcpy(tables, host.data(), floats * sizeof(float), hipMemcpyHostToDevice); // synchronous: `host` dies with this frame
+    if (copied != hipSuccess) {
+        (void)hipFreeAsync(tables, stream);
+        return hip_fail(copied, "hipMemcpy(development tables)");
+    }
+    L.develop.grains = grains_device;
+    L.develop.grains_b = grains_b_device;
+    L.out = out_device;
+    L.space = space;
+    const int rc = launch_develop_linear(L, stream);
+    const hipError_t e = hipFreeAsync(tables, stream);
+    if (rc != PYR_OK) return fail(rc, tone_kernels_last_error());
+    if (e != hipSuccess) return hip_fail(e, "hipFreeAsync");
+    if (blocking) HIP_TRY(hipStreamSynchronize(stream));
+    return PYR_OK;
+}
+
+// The session's film developed into its linear image buffer, enqueued on its stream.
+int session_linear(PyrSession* s, const PyrDevelopParams* p, uint32_t space) {
+    int rc;
+    const size_t bytes = (size_t)s->film.width * s->film.height * 3 * sizeof(float);
+    if (!s->linear.ptr && (rc = s->linear.alloc(bytes)) != PYR_OK) return rc;
+    LinearLaunch L{};
+    if ((rc = session_develop_launch(s, p, L.develop)) != PYR_OK) return rc;
+    L.out = (float*)s->linear.ptr;
+    L.space = space;
+    if ((rc = launch_develop_linear(L, s->stream)) != PYR_OK) return fail(rc, tone_kernels_last_error());
+    return PYR_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int pyr_film_develop_linear_device(const PyrFilmDesc* film, const PyrGrain* grains_device, const PyrGrain* grains_b_device, const PyrDevelopParams* params,
+                                   uint32_t space, float* out_device, int device, void* hip_stream) {
+    int rc = check_linear_args(film, grains_device, params, space, out_device);
+    if (rc != PYR_OK || (rc = check_device(device)) != PYR_OK) return rc;
+    HIP_TRY(hipSetDevice(device));
+    return develop_linear_common(film, grains_device, grains_b_device, params, space, out_device, (hipStream_t)hip_stream, false);
+}
+
+int pyr_film_develop_linear(const PyrFilmDesc* film, const PyrGrain* grains, const PyrGrain* grains_b, const PyrDevelopParams* params, uint32_t space, float* out,
+                            int device) {
+    int rc = check_linear_args(film, grains, params, space, out);
+    if (rc != PYR_OK || (rc = check_device(device)) != PYR_OK) return rc;
+    HIP_TRY(hipSetDevice(device));
+    const size_t pixels = (size_t)film->width * film->height;
+    DeviceBuffer a_dev, b_dev, out_dev;
+    if ((rc = a_dev.upload(grains, pixels * film->bins * sizeof(PyrGrain))) != PYR_OK) return rc;
+    if (grains_b && (rc = b_dev.upload(grains_b, pixels * film->bins * sizeof(PyrGrain))) != PYR_OK) return rc;
+    if ((rc = out_dev.alloc(pixels * 3 * sizeof(float))) != PYR_OK) return rc;
+    rc = develop_linear_common(film, (const PyrGrain*)a_dev.ptr, grains_b ? (const PyrGrain*)b_dev.ptr : nullptr, params, space, (float*)out_dev.ptr, nullptr, true);
+    if (rc != PYR_OK) return rc;
+    HIP_TRY(hipMemcpy(out, out_dev.ptr, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
+    return PYR_OK;
+}
+
+int pyr_image_stats_device(const float* linear_srgb_device, uint32_t width, uint32_t height, PyrImageStats* out_device, int device, void* hip_stream) {
+    if (!linear_srgb_device || !out_device) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = check_image_size(width, height);
+    if (rc != PYR_OK || (rc = check_device(device)) != PYR_OK) return rc;
+    HIP_TRY(hipSetDevice(device));
+    if ((rc = launch_image_stats(linear_srgb_device, (size_t)width * height, out_device, hip_stream)) != PYR_OK) return fail(rc, tone_kernels_last_error());
+    return PYR_OK;
+}
+
+int pyr_image_stats(const float* linear_srgb, uint32_t width, uint32_t height, PyrImageStats* out, int device) {
+    if (!linear_srgb || !out) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = check_image_size(width, height);
+    if (rc != PYR_OK || (rc = check_device(device)) != PYR_OK) return rc;
+    HIP_TRY(hipSetDevice(device));
+    const size_t pixels = (size_t)width * height;
+    DeviceBuffer image_dev, stats_dev;
+    if ((rc = image_dev.upload(linear_srgb, pixels * 3 * sizeof(float))) != PYR_OK) return rc;
+    if ((rc = stats_dev.alloc(sizeof(PyrImageStats))) != PYR_OK) return rc;
+    if ((rc = launch_image_stats((const float*)image_dev.ptr, pixels, (PyrImageStats*)stats_dev.ptr, nullptr)) != PYR_OK) return fail(rc, tone_kernels_last_error());
+    HIP_TRY(hipMemcpy(out, stats_dev.ptr, sizeof(PyrImageStats), hipMemcpyDeviceToHost));
+    return PYR_OK;
+}
+
+int pyr_tone_resolve(const PyrImageStats* stats, const PyrToneParams* tone, float* exposure_out, float* white_out) {
+    if (!tone || !exposure_out || !white_out) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+    if (int bad = check_tone_params(tone)) return bad;
+    if (tone_needs_stats(tone) && !stats) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: an automatic exposure or white point needs the statistics");
+    float exposure = tone->exposure;
+    if (!(exposure > 0.0f)) exposure = stats->lit ? tone->key / upper_edge(percentile_bin(stats, tone->percentile)) : 1.0f;
+    float white = 1.0f;
+    if (tone->op == PYR_TONE_REINHARD) {
+        if (tone->white > 0.0f)
+            white = tone->white;
+        else if (stats->lit)
+            white = exposure * upper_edge(percentile_bin(stats, tone->white_percentile));
+    }
+    *exposure_out = exposure;
+    *white_out = white;
+    return PYR_OK;
+}
+
+int pyr_image_tonemap_device(const float* linear_srgb_device, uint32_t width, uint32_t height, const PyrToneParams* resolved, uint8_t* rgb_device, int device,
+                             void* hip_stream) {
+    if (!linear_srgb_device || !resolved || !rgb_device) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = check_resolved_tone(resolved);
+    if (rc != PYR_OK || (rc = check_image_size(width, height)) != PYR_OK || (rc = check_device(device)) != PYR_OK) return rc;
+    HIP_TRY(hipSetDevice(device));
+    const ToneLaunch T{linear_srgb_device, rgb_device, (size_t)width * height, resolved->op, resolved->exposure, resolved->white};
+    if ((rc = launch_tonemap(T, hip_stream)) != PYR_OK) return fail(rc, tone_kernels_last_error());
+    return PYR_OK;
+}
+
+int pyr_image_tonemap(const float* linear_srgb, uint32_t width, uint32_t height, const PyrToneParams* resolved, uint8_t* rgb_out, int device) {
+    if (!linear_srgb || !resolved || !rgb_out) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = check_resolved_tone(resolved);
+    if (rc != PYR_OK || (rc = check_image_size(width, height)) != PYR_OK || (rc = check_device(device)) != PYR_OK) return rc;
+    HIP_TRY(hipSetDevice(device));
+    const size_t pixels = (size_t)width * height;
+    DeviceBuffer image_dev, rgb_dev;
+    if ((rc = image_dev.upload(linear_srgb, pixels * 3 * sizeof(float))) != PYR_OK) return rc;
+    if ((rc = rgb_dev.alloc(pixels * 3)) != PYR_OK) return rc;
+    const ToneLaunch T{(const float*)image_dev.ptr, (uint8_t*)rgb_dev.ptr, pixels, resolved->op, resolved->exposure, resolved->white};
+    if ((rc = launch_tonemap(T, nullptr)) != PYR_OK) return fail(rc, tone_kernels_last_error());
+    HIP_TRY(hipMemcpy(rgb_out, rgb_dev.ptr, pixels * 3, hipMemcpyDeviceToHost));
+    return PYR_OK;
+}
+
+int pyr_session_linear(PyrSession* session, const PyrDevelopParams* develop_params, uint32_t space, float* out) {
+    if (!session) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = check_linear_args(&session->film, session, develop_params, space, out);
+    if (rc != PYR_OK || (rc = session_ready(session)) != PYR_OK) return rc;
+    if ((rc = session_linear(session, develop_params, space)) != PYR_OK) return rc;
+    HIP_TRY(hipMemcpyAsync(out, session->linear.ptr, (size_t)session->film.width * session->film.height * 3 * sizeof(float), hipMemcpyDeviceToHost, session->stream));
+    return session_sync(session);
+}
+
+int pyr_session_preview_tone(PyrSession* session, const PyrDevelopParams* develop_params, const PyrToneParams* tone, uint8_t* rgb_out, PyrImageStats* stats_out) {
+    if (!session || !tone) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+    int rc = check_tone_params(tone);
+    if (rc != PYR_OK || (rc = check_linear_args(&session->film, session, develop_params, PYR_LINEAR_SRGB, rgb_out)) != PYR_OK || (rc = session_ready(session)) != PYR_OK) return rc;
+    PyrSession* s = session;
+    const size_t pixels = (size_t)s->film.width * s->film.height;
+    if ((rc = session_linear(s, develop_params, PYR_LINEAR_SRGB)) != PYR_OK) return rc;
+    PyrImageStats stats{};
+    if (tone_needs_stats(tone) || stats_out) {
+        if (!s->stats.ptr && (rc = s->stats.alloc(sizeof(PyrImageStats))) != PYR_OK) return rc;
+        if ((rc = launch_image_stats((const float*)s->linear.ptr, pixels, (PyrImageStats*)s->stats.ptr, s->stream)) != PYR_OK) return fail(rc, tone_kernels_last_error());
+        HIP_TRY(hipMemcpyAsync(&stats, s->stats.ptr, sizeof(PyrImageStats), hipMemcpyDeviceToHost, s->stream));
+        HIP_TRY(hipStreamSynchronize(s->stream)); // the rule is host arithmetic on 1 KB
+        if (stats_out) *stats_out = stats;
+    }
+    ToneLaunch T{(const float*)s->linear.ptr, (uint8_t*)s->rgb.ptr, pixels, tone->op, 0.0f, 0.0f};
+    if ((rc = pyr_tone_resolve(&stats, tone, &T.exposure, &T.white)) != PYR_OK) return rc;
+    if ((rc = launch_tonemap(T, s->stream)) != PYR_OK) return fail(rc, tone_kernels_last_error());
+    HIP_TRY(hipMemcpyAsync(rgb_out, s->rgb.ptr, pixels * 3, hipMemcpyDeviceToHost, s->stream));
+    return session_sync(s);
 }
 
 } // extern "C"

@@ -251,6 +251,26 @@ struct NoiseLaunch {
 int launch_noise(const NoiseLaunch& launch, void* stream);
 const char* film_kernels_last_error();
 
+// kernels/tone.hip: the film as an image in linear light, its luminance statistics, its tone mapping
+struct LinearLaunch {
+    DevelopLaunch develop; // rgb_out is not read; grains_b is served by both forms
+    float* out;            // device, height * width * 3 floats
+    uint32_t space;        // PYR_LINEAR_XYZ or PYR_LINEAR_SRGB
+};
+// develop_linear_kernel (a wave per run of 64 pixels) up to kWaveDevelopMaxBins bins, develop_linear_pixel_kernel beyond
+int launch_develop_linear(const LinearLaunch& launch, void* stream);
+// Zeroes `out` (device) and fills it from `image` (device, pixels * 3 floats, linear sRGB), all on `stream`.
+int launch_image_stats(const float* image, size_t pixels, PyrImageStats* out, void* stream);
+struct ToneLaunch {
+    const float* image; // device, pixels * 3 floats, linear sRGB
+    uint8_t* rgb_out;   // device, pixels * 3 bytes
+    size_t pixels;
+    uint32_t op; // PYR_TONE_CLIP or PYR_TONE_REINHARD
+    float exposure, white;
+};
+int launch_tonemap(const ToneLaunch& launch, void* stream);
+const char* tone_kernels_last_error();
+
 // Adds the PYR_FILM_TILE_BLOCKS buffer of the tiles tile_begin + k * tile_stride (k < tile_count) into a whole-image film.
 struct AssembleLaunch {
     PyrFilmDesc film;

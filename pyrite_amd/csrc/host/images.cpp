@@ -323,4 +323,42 @@ std::vector<float> load_texture_file(const std::string& path, bool linear, bool 
     return out;
 }
 
+// ---- linear images out: Radiance RGBE and PFM (pyrite_host.hpp; pyrite_amd/develop.py encode_hdr / encode_pfm) --------------------
+namespace {
+std::vector<uint8_t> header_bytes(const std::string& text) { return std::vector<uint8_t>(text.begin(), text.end()); }
+} // namespace
+
+std::vector<uint8_t> encode_hdr(const std::vector<float>& rgb, uint32_t width, uint32_t height) {
+    if (rgb.size() != (size_t)width * height * 3) throw ProjectError("encode_hdr: buffer size does not match the image size");
+    std::vector<uint8_t> file = header_bytes("#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n-Y " + std::to_string(height) + " +X " + std::to_string(width) + "\n");
+    file.reserve(file.size() + (size_t)width * height * 4);
+    for (size_t px = 0; px < (size_t)width * height; ++px) {
+        double c[3], m = 0.0;
+        for (int k = 0; k < 3; ++k) {
+            const float v = rgb[3 * px + k];
+            c[k] = v > 0.0f ? std::min((double)v, kRgbeMax) : 0.0; // NaN and anything negative: 0
+            m = std::max(m, c[k]);
+        }
+        uint8_t out[4] = {0, 0, 0, 0};
+        if (m >= 1e-32) {
+            int e = 0;
+            const double scale = std::frexp(m, &e) * 256.0 / m;
+            for (int k = 0; k < 3; ++k) out[k] = (uint8_t)(c[k] * scale);
+            out[3] = (uint8_t)(e + 128);
+        }
+        file.insert(file.end(), out, out + 4);
+    }
+    return file;
+}
+
+std::vector<uint8_t> encode_pfm(const std::vector<float>& rgb, uint32_t width, uint32_t height) {
+    if (rgb.size() != (size_t)width * height * 3) throw ProjectError("encode_pfm: buffer size does not match the image size");
+    std::vector<uint8_t> file = header_bytes("PF\n" + std::to_string(width) + " " + std::to_string(height) + "\n-1.0\n");
+    const size_t row = (size_t)width * 3, at = file.size();
+    file.resize(at + row * height * 4);
+    for (uint32_t y = 0; y < height; ++y) // bottom to top; the bytes of an f32 as this little-endian host holds them
+        std::memcpy(file.data() + at + (size_t)y * row * 4, rgb.data() + (size_t)(height - 1 - y) * row, row * 4);
+    return file;
+}
+
 } // namespace pyrite

@@ -5,7 +5,9 @@
 #include "pyrite_host.hpp"
 
 #include <algorithm>
+#include <cctype>
 #include <cmath>
+#include <cstdlib>
 #include <cstring>
 #include <fstream>
 #include <sstream>
@@ -1249,6 +1251,68 @@ std::vector<uint8_t> Film::develop(const std::optional<Expression>& filter, cons
     return out;
 }
 
+// ---- linear images and tone mapping --------------------------------------------------------------------------------------------
+std::vector<float> develop_linear(const Film& film, uint32_t space, const std::optional<Expression>& filter, const std::optional<Expression>& white, float step_size,
+                                  int device, const Film* film_b) {
+    if (film_b && (film_b->width != film.width || film_b->height != film.height || film_b->bins != film.bins)) throw ProjectError("develop_linear: the second film has another shape");
+    const DevelopSetup setup(film, filter, white, step_size);
+    std::vector<float> out((size_t)film.width * film.height * 3, 0.0f);
+    const PyrFilmDesc d = film.desc();
+    check_status(pyr_film_develop_linear(&d, film.grains.data(), film_b ? film_b->grains.data() : nullptr, &setup.p, space, out.data(), device));
+    return out;
+}
+PyrImageStats image_stats(const std::vector<float>& linear_srgb, uint32_t width, uint32_t height, int device) {
+    if (linear_srgb.size() != (size_t)width * height * 3) throw ProjectError("image_stats: buffer size does not match the image size");
+    PyrImageStats out{};
+    check_status(pyr_image_stats(linear_srgb.data(), width, height, &out, device));
+    return out;
+}
+PyrToneParams tone_params(uint32_t op, float exposure, float white) { return PyrToneParams{op, exposure, white, PYR_TONE_KEY, PYR_TONE_PERCENTILE, PYR_TONE_WHITE_PERCENTILE}; }
+std::vector<uint8_t> tonemap(const std::vector<float>& linear_srgb, uint32_t width, uint32_t height, const PyrToneParams& tone, int device) {
+    if (linear_srgb.size() != (size_t)width * height * 3) throw ProjectError("tonemap: buffer size does not match the image size");
+    PyrToneParams resolved = tone;
+    const bool needs_stats = !(tone.exposure > 0.0f) || (tone.op == PYR_TONE_REINHARD && !(tone.white > 0.0f));
+    PyrImageStats stats{};
+    if (needs_stats) stats = image_stats(linear_srgb, width, height, device);
+    check_status(pyr_tone_resolve(&stats, &tone, &resolved.exposure, &resolved.white));
+    std::vector<uint8_t> out((size_t)width * height * 3, 0);
+    check_status(pyr_image_tonemap(linear_srgb.data(), width, height, &resolved, out.data(), device));
+    return out;
+}
+namespace {
+bool ends_with(std::string s, const char* tail) {
+    for (char& c : s) c = (char)std::tolower((unsigned char)c);
+    const size_t n = std::strlen(tail);
+    return s.size() >= n && s.compare(s.size() - n, n, tail) == 0;
+}
+void write_bytes(const std::string& path, const std::vector<uint8_t>& bytes) {
+    std::ofstream f(path, std::ios::binary);
+    if (!f) throw ProjectError("could not write " + path);
+    f.write(reinterpret_cast<const char*>(bytes.data()), (std::streamsize)bytes.size());
+}
+} // namespace
+void write_hdr(const std::string& path, const std::vector<float>& rgb, uint32_t width, uint32_t height) { write_bytes(path, encode_hdr(rgb, width, height)); }
+void write_pfm(const std::string& path, const std::vector<float>& rgb, uint32_t width, uint32_t height) { write_bytes(path, encode_pfm(rgb, width, height)); }
+void write_linear(const std::string& path, const std::vector<float>& rgb, uint32_t width, uint32_t height) {
+    ends_with(path, ".pfm") ? write_pfm(path, rgb, width, height) : write_hdr(path, rgb, width, height);
+}
+std::string tone_flag_problem(const std::optional<std::string>& hdr, const std::optional<std::string>& exposure, const std::optional<std::string>& tone) {
+    if (hdr && !ends_with(*hdr, ".hdr") && !ends_with(*hdr, ".pfm")) return "--hdr must end in .hdr or .pfm";
+    if (exposure && *exposure != "auto") {
+        char* end = nullptr;
+        const double ev = std::strtod(exposure->c_str(), &end);
+        if (exposure->empty() || *end != 0 || !std::isfinite(ev)) return "--exposure must be a number of stops or auto";
+    }
+    if (tone && *tone != "clip" && *tone != "reinhard") return "--tone must be clip or reinhard";
+    return "";
+}
+std::optional<PyrToneParams> tone_from_flags(const std::optional<std::string>& exposure, const std::optional<std::string>& tone) {
+    if (!exposure && !tone) return std::nullopt;
+    const uint32_t op = tone && *tone == "reinhard" ? PYR_TONE_REINHARD : PYR_TONE_CLIP;
+    const std::string ev = exposure ? *exposure : op == PYR_TONE_REINHARD ? "auto" : "0";
+    return tone_params(op, ev == "auto" ? 0.0f : (float)std::pow(2.0, std::strtod(ev.c_str(), nullptr)));
+}
+
 // ---- progressive sessions ------------------------------------------------------------------------------------------------------
 Session::Session(const Renderer& renderer, uint32_t width, uint32_t height, const Camera& camera, World& world, bool halves, int device, const Film* start)
     : shape_(0, 0, renderer.spectrum_bins, renderer.spectrum_span[0], renderer.spectrum_span[1]), width_(width), height_(height), tile_size_(renderer.tile_size) {
@@ -1270,6 +1334,19 @@ std::vector<uint8_t> Session::preview(float step_size, const std::optional<Expre
     const DevelopSetup setup(shape_, filter, white, step_size);
     std::vector<uint8_t> out((size_t)width_ * height_ * 3, 0);
     check_status(pyr_session_preview(handle_, &setup.p, out.data()));
+    return out;
+}
+std::vector<uint8_t> Session::preview_tone(const PyrToneParams& tone, float step_size, const std::optional<Expression>& filter, const std::optional<Expression>& white,
+                                           PyrImageStats* stats) {
+    const DevelopSetup setup(shape_, filter, white, step_size);
+    std::vector<uint8_t> out((size_t)width_ * height_ * 3, 0);
+    check_status(pyr_session_preview_tone(handle_, &setup.p, &tone, out.data(), stats));
+    return out;
+}
+std::vector<float> Session::linear(uint32_t space, float step_size, const std::optional<Expression>& filter, const std::optional<Expression>& white) {
+    const DevelopSetup setup(shape_, filter, white, step_size);
+    std::vector<float> out((size_t)width_ * height_ * 3, 0.0f);
+    check_status(pyr_session_linear(handle_, &setup.p, space, out.data()));
     return out;
 }
 Film Session::film() {
@@ -1413,6 +1490,16 @@ void save_png(const std::string& path, const std::vector<uint8_t>& rgb, uint32_t
 extern "C" int pyrh_test_png(const char* path, const uint8_t* rgb, uint32_t width, uint32_t height) {
     try {
         pyrite::save_png(path, std::vector<uint8_t>(rgb, rgb + (size_t)width * height * 3), width, height);
+        return 0;
+    } catch (const std::exception&) {
+        return 1;
+    }
+}
+
+extern "C" int pyrh_test_linear_image(const char* path, const float* rgb, uint32_t width, uint32_t height, int pfm) {
+    try {
+        const std::vector<float> image(rgb, rgb + (size_t)width * height * 3);
+        pfm ? pyrite::write_pfm(path, image, width, height) : pyrite::write_hdr(path, image, width, height);
         return 0;
     } catch (const std::exception&) {
         return 1;

@@ -4,7 +4,8 @@
 //   pyrite_host_tool dump   <scene> <data_dir> <out.bin>                      flatten only (no GPU): canonical scene bytes + camera + renderer
 //   pyrite_host_tool dump-project   <project.lua> <texel dir | -> <out.bin>    the same for a project file (lua_project.cpp)
 //   pyrite_host_tool render-project <project.lua> <texel dir | -> <seed> <out.png> [film.bin]   what `pyrite project.lua` does (main.rs:46-330)
-//                                   [--size WxH] [--spp N] [--features PREFIX] [--features-grid N] and the progressive flags of python -m pyrite_amd
+//                                   [--size WxH] [--spp N] [--features PREFIX] [--features-grid N] [--hdr PATH] [--exposure EV|auto] [--tone clip|reinhard]
+//                                   and the progressive flags of python -m pyrite_amd
 //   pyrite_host_tool encode-features <records.bin> <normal.rgb> <depth.rgb>    PyrFeaturePixel[n] -> the 8-bit normal and depth images, raw RGB (no GPU)
 //   pyrite_host_tool intersect <scene> <data_dir> <rays.f32> <hits.bin>       World::intersect for a ray batch ([n][6] f32 -> PyrHit[n])
 //   pyrite_host_tool render <scene> <data_dir> <w> <h> <spp> <seed> <film.bin> [out.png]
@@ -248,6 +249,7 @@ int main(int argc, char** argv) {
             bool noise = false;
             std::string features_prefix, size;
             std::optional<long> features_grid, spp;
+            std::optional<std::string> hdr, exposure, tone_name;
             for (int i = 6; i < argc; ++i) {
                 const std::string a = argv[i];
                 auto value = [&]() -> const char* {
@@ -266,6 +268,12 @@ int main(int argc, char** argv) {
                     features_prefix = value();
                 else if (a == "--features-grid")
                     features_grid = std::strtol(value(), nullptr, 10);
+                else if (a == "--hdr")
+                    hdr = value();
+                else if (a == "--exposure")
+                    exposure = value();
+                else if (a == "--tone")
+                    tone_name = value();
                 else if (a == "--size")
                     size = value();
                 else if (a == "--spp")
@@ -277,10 +285,12 @@ int main(int argc, char** argv) {
             }
             std::string problem = progressive_flag_problem(pass_samples, !preview_path.empty(), preview_every, noise);
             if (problem.empty()) problem = features_flag_problem(!features_prefix.empty(), features_grid);
+            if (problem.empty()) problem = tone_flag_problem(hdr, exposure, tone_name);
             if (!problem.empty()) {
                 std::fprintf(stderr, "error: %s\n", problem.c_str());
                 return 2;
             }
+            const std::optional<PyrToneParams> tone = tone_from_flags(exposure, tone_name);
             LoadedProject loaded = load_project(argv[2], std::string(argv[3]) == "-" ? TextureLoader() : texel_files(argv[3]));
             if (!size.empty()) { // WIDTHxHEIGHT, as python -m pyrite_amd --size
                 char* rest = nullptr;
@@ -304,7 +314,9 @@ int main(int argc, char** argv) {
                     session.sync();
                     std::printf("Rendering... %3d %%\n", (int)((uint64_t)session.samples_done() * 100u / r.pixel_samples));
                     if (!preview_path.empty() && std::chrono::duration<double>(std::chrono::steady_clock::now() - last_image).count() >= preview_every) {
-                        save_png(preview_path, session.preview(30.0f, project.image.filter, project.image.white), film.width, film.height);
+                        save_png(preview_path,
+                                 tone ? session.preview_tone(*tone, 30.0f, project.image.filter, project.image.white) : session.preview(30.0f, project.image.filter, project.image.white),
+                                 film.width, film.height);
                         std::printf("Preview updated (%u samples per pixel)\n", session.samples_done());
                         if (noise && session.samples_done() >= 2 * per_pass) {
                             std::vector<float> tiles = session.noise();
@@ -321,7 +333,13 @@ int main(int argc, char** argv) {
                 r.render(film, cam, *world);
             }
             std::printf("Saving final result...\n"); // main.rs:313
-            save_png(argv[5], film.develop(project.image.filter, project.image.white), film.width, film.height);
+            std::vector<float> linear;
+            if (hdr || tone) linear = develop_linear(film, PYR_LINEAR_SRGB, project.image.filter, project.image.white);
+            save_png(argv[5], tone ? tonemap(linear, film.width, film.height, *tone) : film.develop(project.image.filter, project.image.white), film.width, film.height);
+            if (hdr) {
+                write_linear(*hdr, linear, film.width, film.height);
+                std::printf("wrote %s\n", hdr->c_str());
+            }
             if (!film_path.empty()) {
                 std::ofstream f(film_path, std::ios::binary);
                 f.write(reinterpret_cast<const char*>(film.grains.data()), (std::streamsize)(film.grains.size() * sizeof(PyrGrain)));

@@ -146,3 +146,142 @@ def save_png(path, rgb):
 
     with open(path, "wb") as f:
         f.write(b"\x89PNG\r\n\x1a\n" + chunk(b"IHDR", struct.pack(">IIBBBBB", w, h, 8, 2, 0, 0, 0)) + chunk(b"IDAT", zlib.compress(raw, 6)) + chunk(b"IEND", b""))
+
+
+# ---------------------------------------------------------------------------------------------- linear images and tone mapping
+SPACES = {"xyz": abi.PYR_LINEAR_XYZ, "srgb": abi.PYR_LINEAR_SRGB}
+TONE_OPS = {"clip": abi.PYR_TONE_CLIP, "reinhard": abi.PYR_TONE_REINHARD}
+
+
+def develop_linear(film: Film, space="srgb", film_b: Film = None, step_size=2.0, filter=None, white=None, device=0):
+    """float32 [height, width, 3]: `film` (plus `film_b`, grain by grain, when given) developed on the GPU to CIE XYZ or to the
+    linear sRGB triple that `develop` clamps and encodes (pyr_film_develop_linear)."""
+    p, keep = develop_params(film, step_size, filter, white)
+    desc = film.desc()
+    grains = np.ascontiguousarray(film.grains)
+    grains_b = None
+    if film_b is not None:
+        assert film_b.grains.shape == film.grains.shape
+        grains_b = np.ascontiguousarray(film_b.grains)
+    out = np.zeros((film.height, film.width, 3), dtype=np.float32)
+    check(lib().pyr_film_develop_linear(C.byref(desc), grains.ctypes.data, grains_b.ctypes.data if grains_b is not None else None, C.byref(p),
+                                        SPACES[space], out.ctypes.data, int(device)))
+    del keep
+    return out
+
+
+def _linear_image(rgb):
+    rgb = np.ascontiguousarray(rgb, dtype=np.float32)
+    assert rgb.ndim == 3 and rgb.shape[2] == 3
+    return rgb
+
+
+def image_stats(rgb, device=0):
+    """abi.PyrImageStats of a linear sRGB image: the luminance histogram (8 bins per octave over 2^-16 .. 2^16), the lit and dark
+    pixel counts, the extremes of the lit luminance (pyr_image_stats). Integer counters: the same bits on every call."""
+    rgb = _linear_image(rgb)
+    out = abi.PyrImageStats()
+    check(lib().pyr_image_stats(rgb.ctypes.data, rgb.shape[1], rgb.shape[0], C.byref(out), int(device)))
+    return out
+
+
+def tone_params(op="clip", exposure=None, white=None, key=abi.PYR_TONE_KEY, percentile=abi.PYR_TONE_PERCENTILE, white_percentile=abi.PYR_TONE_WHITE_PERCENTILE):
+    """abi.PyrToneParams: `exposure` is a factor on the linear values, `white` the exposed luminance that Reinhard's curve takes to
+    1; None or "auto" leaves either to the image's statistics."""
+    automatic = (None, "auto")
+    return abi.PyrToneParams(TONE_OPS[op] if isinstance(op, str) else int(op), 0.0 if exposure in automatic else float(exposure),
+                             0.0 if white in automatic else float(white), float(key), float(percentile), float(white_percentile))
+
+
+def tone_resolve(stats, tone):
+    """(exposure, white) that `tone` stands for on an image with these statistics (pyr_tone_resolve: host arithmetic, no device)."""
+    exposure, white = C.c_float(0), C.c_float(0)
+    check(lib().pyr_tone_resolve(C.byref(stats) if stats is not None else None, C.byref(tone), C.byref(exposure), C.byref(white)))
+    return float(exposure.value), float(white.value)
+
+
+def tonemap(rgb, tone=None, stats=None, device=0):
+    """uint8 [height, width, 3] sRGB of a linear sRGB image under `tone` (tone_params; default: the clip at exposure 1, which is
+    `develop`'s image). What `tone` leaves automatic is resolved from `stats`, taken on the GPU here when not given."""
+    rgb = _linear_image(rgb)
+    tone = tone_params(exposure=1.0) if tone is None else tone
+    needs_stats = not tone.exposure > 0 or (tone.op == abi.PYR_TONE_REINHARD and not tone.white > 0)
+    if needs_stats and stats is None:
+        stats = image_stats(rgb, device)
+    exposure, white = tone_resolve(stats, tone)
+    resolved = abi.PyrToneParams(tone.op, exposure, white, tone.key, tone.percentile, tone.white_percentile)
+    out = np.zeros(rgb.shape, dtype=np.uint8)
+    check(lib().pyr_image_tonemap(rgb.ctypes.data, rgb.shape[1], rgb.shape[0], C.byref(resolved), out.ctypes.data, int(device)))
+    return out
+
+
+RGBE_MAX = 255.0 * 2.0 ** 119  # the largest value a Radiance pixel holds: mantissa 255, exponent byte 255
+
+
+def encode_hdr(rgb):
+    """The bytes of a Radiance picture of a linear image: flat scanlines of RGBE pixels, no run-length coding. Ward's mapping, in
+    f64 (pyrite_host.hpp encode_hdr writes the same bytes): a channel that is not positive (negative, NaN) is 0, one above RGBE_MAX
+    (+inf too) is RGBE_MAX; m = the largest channel; m < 1e-32: four zero bytes; else m = f * 2^e with f in [0.5, 1), the mantissa
+    bytes are (uint8)(c * (f * 256 / m)) and the exponent byte is e + 128."""
+    rgb = _linear_image(rgb)
+    h, w, _ = rgb.shape
+    with np.errstate(all="ignore"):
+        c = np.where(rgb > 0, rgb, np.float32(0)).astype(np.float64)
+        c = np.minimum(c, RGBE_MAX)
+        m = c.max(axis=2)
+        some = m >= 1e-32
+        f, e = np.frexp(np.where(some, m, 1.0))
+        scale = f * 256.0 / np.where(some, m, 1.0)
+        pixels = np.zeros((h, w, 4), dtype=np.uint8)
+        pixels[..., :3] = np.where(some[..., None], c * scale[..., None], 0.0).astype(np.uint8)
+        pixels[..., 3] = np.where(some, e + 128, 0).astype(np.uint8)
+    return b"#?RADIANCE\nFORMAT=32-bit_rle_rgbe\n\n-Y %d +X %d\n" % (h, w) + pixels.tobytes()
+
+
+def encode_pfm(rgb):
+    """The bytes of a colour PFM file: little-endian f32 as they are, rows bottom to top."""
+    rgb = _linear_image(rgb)
+    h, w, _ = rgb.shape
+    return b"PF\n%d %d\n-1.0\n" % (w, h) + rgb[::-1].astype("<f4").tobytes()
+
+
+def save_hdr(path, rgb):
+    with open(path, "wb") as f:
+        f.write(encode_hdr(rgb))
+
+
+def save_pfm(path, rgb):
+    with open(path, "wb") as f:
+        f.write(encode_pfm(rgb))
+
+
+def tone_flag_problem(hdr, exposure, tone):
+    """What is wrong with --hdr / --exposure / --tone, in the words pyrite_host_tool uses too, or None."""
+    if hdr is not None and not hdr.lower().endswith((".hdr", ".pfm")):
+        return "--hdr must end in .hdr or .pfm"
+    if exposure is not None and exposure != "auto":
+        try:
+            ok = np.isfinite(float(exposure))
+        except ValueError:
+            ok = False
+        if not ok:
+            return "--exposure must be a number of stops or auto"
+    if tone is not None and tone not in TONE_OPS:
+        return "--tone must be clip or reinhard"
+    return None
+
+
+def tone_from_flags(exposure, tone):
+    """The PyrToneParams of --exposure EV|auto and --tone clip|reinhard, or None when neither is given: EV is stops (a factor of
+    2^EV), --tone reinhard alone means --exposure auto, --exposure alone means --tone clip."""
+    if exposure is None and tone is None:
+        return None
+    op = tone or "clip"
+    if exposure is None:
+        exposure = "auto" if op == "reinhard" else "0"
+    return tone_params(op, None if exposure == "auto" else f32(2.0 ** float(exposure)))
+
+
+def save_linear(path, rgb):
+    """--hdr PATH: .hdr or .pfm by the extension."""
+    (save_pfm if path.lower().endswith(".pfm") else save_hdr)(path, rgb)

@@ -237,13 +237,30 @@ class Session:
     def sync(self):
         check(lib().pyr_session_sync(self.handle))
 
-    def preview(self, step=30.0, filter=None, white=None):
-        """uint8 [height, width, 3]: the film as it stands, developed on the GPU (main.rs:270 uses step 30 for previews)."""
+    def preview(self, step=30.0, filter=None, white=None, tone=None, stats=None):
+        """uint8 [height, width, 3]: the film as it stands, developed on the GPU (main.rs:270 uses step 30 for previews). With `tone`
+        (develop.tone_params) the film is developed to linear light, measured and tone mapped there (pyr_session_preview_tone) and
+        `stats`, an abi.PyrImageStats, is filled when given; without it this is pyr_session_preview's hard clamp."""
         from .develop import develop_params
 
         p, keep = develop_params(self._film, step, filter, white)
         out = np.zeros((self.height, self.width, 3), dtype=np.uint8)
-        check(lib().pyr_session_preview(self.handle, C.byref(p), out.ctypes.data))
+        if tone is None:
+            assert stats is None, "the statistics belong to a tone mapped preview"
+            check(lib().pyr_session_preview(self.handle, C.byref(p), out.ctypes.data))
+        else:
+            check(lib().pyr_session_preview_tone(self.handle, C.byref(p), C.byref(tone), out.ctypes.data, C.byref(stats) if stats is not None else None))
+        del keep
+        return out
+
+    def linear(self, step=2.0, space="srgb", filter=None, white=None):
+        """float32 [height, width, 3]: the film as it stands (A + B with halves) developed to CIE XYZ or linear sRGB on the GPU
+        (pyr_session_linear; develop.develop_linear of film() gives the same floats)."""
+        from .develop import SPACES, develop_params
+
+        p, keep = develop_params(self._film, step, filter, white)
+        out = np.zeros((self.height, self.width, 3), dtype=np.float32)
+        check(lib().pyr_session_linear(self.handle, C.byref(p), SPACES[space], out.ctypes.data))
         del keep
         return out
 
