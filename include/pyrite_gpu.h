@@ -745,6 +745,85 @@ int pyr_session_linear(PyrSession* session, const PyrDevelopParams* develop_para
 int pyr_session_preview_tone(PyrSession* session, const PyrDevelopParams* develop_params, const PyrToneParams* tone, uint8_t* rgb_out,
                              PyrImageStats* stats_out);
 
+/* ---------------------------------------------------------------- denoising a linear image from two halves -------
+ * A session with PYR_SESSION_HALVES holds two films of independent samples, and development is linear in the grain quotients: the
+ * two developed halves are two independent estimates of one image. These entries filter such a pair -- three f32 per pixel, never
+ * the film -- with a non-local-means cross filter: the weights that average half `a` are read from half `b` and the other way
+ * round, so the noise of a pixel never votes for itself. The reference has no such step.
+ *   Inputs: `a`, `b`: width*height*3 f32, row-major, the halves. Optional guides, NULL = absent: `albedo`, width*height*3 f32 (the
+ * albedo film of the feature pass developed to linear sRGB), and `pixels`, width*height PyrFeaturePixel records (normal, depth).
+ *   All arithmetic is f32 and unfused, one rounding per operation, sums in the order written and started from 0.0f. p, q are
+ * pixels, c a channel (0, 1, 2 in this order wherever channels are summed), "inside" means inside the image.
+ *
+ * Variance of one half:  s_c(p) = (a_c(p) - b_c(p))^2;  V_c(p) = 0.5f * (sum / (float)count), the sum of s_c over p's 3 x 3
+ * neighbourhood clipped to the image in raster order (rows outer), count the pixels summed (4, 6 or 9; 1, 2 or 3 on a thin image).
+ * Where that value is +inf, V_c(p) is NaN: an infinite pixel then poisons every term it enters, as a NaN one does by itself.
+ *
+ * Colour distance of p and q = p + o read from half H: t runs over the (2*patch+1)^2 patch offsets in raster order, dy outer, dx
+ * inner, channel innermost. An offset t is skipped when p + t or q + t is not inside; n counts the offsets kept (t = 0 always is).
+ *     S = sum ((H_c(p+t) - H_c(q+t))^2 - (V_c(p+t) + fminf(V_c(p+t), V_c(q+t)))) / (epsilon + (k*k) * (V_c(p+t) + V_c(q+t)))
+ *     D = fmaxf(S / (3.0f * (float)n), 0.0f)
+ * (the difference is squared as d*d, k*k is one product formed once). Guides, each only when its buffer is given and its sigma is
+ * positive, in this order, with g the guide's term:  D = fmaxf(D, g),
+ *     albedo: g = (sum_c (alb_c(p) - alb_c(q))^2) / (2.0f * (sigma_albedo * sigma_albedo))
+ *     normal: the same form with PyrFeaturePixel::normal and sigma_normal
+ *     depth:  z = PyrFeaturePixel::depth, m = fmaxf(fmaxf(z_p, z_q), 1e-30f), r = (z_p - z_q) / m,
+ *             g = (r*r) / (2.0f * (sigma_depth * sigma_depth))
+ * A pixel without coverage has normal 0 and depth 0 and needs no special case.
+ *
+ * Weight:  w(p, q) = expf(-D).  NaN: C's fmaxf drops a NaN operand, so the rule is explicit: w = 0 when S / (3.0f * (float)n) or a
+ * guide term that applies is NaN. w(p, p) = 1 by definition, nothing is computed for o = 0. An offset whose q is not inside is
+ * skipped, and an offset whose weight is 0 adds nothing to either sum below (0 * NaN would be NaN). Together: a NaN or infinite
+ * pixel of either half makes V NaN in its 3 x 3 neighbourhood, every pair that touches it gets weight 0, the pixel keeps its own
+ * value and gives it to nobody, and the pixels within patch + 1 of it come back as (a + b) * 0.5f, unfiltered.
+ *
+ * Cross filtering, o over the (2*radius+1)^2 window in raster order (oy outer), w_B the weights read from H = b:
+ *     FA_c(p) = (sum_o w_B(p, p+o) * a_c(p+o)) / (sum_o w_B(p, p+o));   FB the same with the halves exchanged.
+ * Outputs:  out = (FA + FB) * 0.5f;  error_out (optional) = fabsf(FA - FB) * 0.5f, the noise that is left, per pixel and channel.
+ * Only expf is not pinned to the bit here. Deterministic: one lane owns a pixel, there are no float atomics, two calls write
+ * the same bytes.
+ *   The variance assumes halves of equal sample counts: as with pyr_session_noise, render passes of one size and an even number
+ * of them. Halves of unequal size bias V -- the noisier half is under-estimated, the other over-estimated -- and with it every
+ * weight. Nothing is filtered per wavelength bin, across GPUs, over time or twice. */
+#define PYR_DENOISE_RADIUS 5u
+#define PYR_DENOISE_PATCH 1u
+#define PYR_DENOISE_K 0.45f
+#define PYR_DENOISE_EPSILON 1e-10f
+#define PYR_DENOISE_SIGMA_ALBEDO 0.02f
+#define PYR_DENOISE_SIGMA_NORMAL 0.1f
+#define PYR_DENOISE_SIGMA_DEPTH 0.02f
+#define PYR_DENOISE_MAX_RADIUS 10u
+#define PYR_DENOISE_MAX_PATCH 3u
+typedef struct PyrDenoiseParams {
+    uint32_t radius;      /* 1..PYR_DENOISE_MAX_RADIUS: the window is (2*radius+1)^2 pixels */
+    uint32_t patch;       /* 0..PYR_DENOISE_MAX_PATCH: the patch is (2*patch+1)^2 pixels */
+    float k;              /* > 0: smaller keeps more detail and more noise */
+    float epsilon;        /* > 0 */
+    float sigma_albedo;   /* <= 0 turns that guide off */
+    float sigma_normal;
+    float sigma_depth;
+    uint32_t reserved;    /* 0 */
+} PyrDenoiseParams; /* 32 bytes */
+
+/* Arguments are checked before a device is looked for: PYR_ERR_INVALID_ARGUMENT, with the argument named in pyr_last_error, for a
+ * null a, b, params or out, an empty image, radius, patch, k or epsilon out of range (a NaN is out of range), a non-zero reserved
+ * word; PYR_ERR_UNSUPPORTED for more than 2^32 - 1 pixels; only then PYR_ERR_DEVICE when there is no such device.
+ * HOST buffers; albedo, pixels and error_out may be NULL. Blocking. */
+int pyr_image_denoise(const float* a, const float* b, const float* albedo, const PyrFeaturePixel* pixels, uint32_t width, uint32_t height,
+                      const PyrDenoiseParams* params, float* out, float* error_out, int device);
+/* The same with every buffer resident on `device`, enqueued on `hip_stream`; out and error_out may not overlap the inputs. The
+ * working memory (three images of width*height*3 floats) is allocated and freed in stream order. */
+int pyr_image_denoise_device(const float* a_device, const float* b_device, const float* albedo_device, const PyrFeaturePixel* pixels_device, uint32_t width,
+                             uint32_t height, const PyrDenoiseParams* params, float* out_device, float* error_out_device, int device, void* hip_stream);
+/* The session's two half films, each developed to linear sRGB with `develop_params` (pyr_film_develop_linear of A alone and of B
+ * alone), then denoised, all on the session's stream and device: out = HOST, height*width*3 floats; error_out (HOST) may be NULL.
+ * With `feature_params` (NULL: no guides) the feature pass runs first into a zeroed albedo film of feature_params->albedo_bins bins,
+ * that film is developed with the same `develop_params`, and it and the feature records guide the filter. Needs PYR_SESSION_HALVES
+ * and at least two passes (else PYR_ERR_INVALID_ARGUMENT, as pyr_session_noise); the remark on halves of unequal size above holds.
+ * The session's films are not touched, and further passes may follow. Blocking. */
+int pyr_session_denoised(PyrSession* session, const PyrDevelopParams* develop_params, const PyrFeatureParams* feature_params,
+                         const PyrDenoiseParams* denoise_params, float* out, float* error_out);
+
 #ifdef __cplusplus
 }
 #endif

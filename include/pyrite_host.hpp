@@ -309,6 +309,22 @@ std::string tone_flag_problem(const std::optional<std::string>& hdr, const std::
 // The tone parameters of --exposure EV|auto and --tone clip|reinhard, or nothing when neither is given (pyrite_amd/develop.py tone_from_flags).
 std::optional<PyrToneParams> tone_from_flags(const std::optional<std::string>& exposure, const std::optional<std::string>& tone);
 
+// ---- denoising (pyrite_gpu.h "denoising a linear image from two halves"; pyrite_amd/develop.py denoise has the same surface) ----
+// The defaults: PYR_DENOISE_RADIUS, PYR_DENOISE_PATCH, PYR_DENOISE_K, PYR_DENOISE_EPSILON and the three guide sigmas.
+PyrDenoiseParams denoise_params(uint32_t radius = PYR_DENOISE_RADIUS, uint32_t patch = PYR_DENOISE_PATCH);
+// What denoise and Session::denoised return: the filtered image and the noise that is left, [height][width][3] f32 each.
+struct Denoised {
+    std::vector<float> image, error;
+};
+// The two half images `a` and `b` (linear light, independent samples of one picture) cross filtered on the GPU (pyr_image_denoise).
+// Guides, either may be null: `albedo`, a linear image, and `pixels`, the records of the feature pass.
+Denoised denoise(const std::vector<float>& a, const std::vector<float>& b, uint32_t width, uint32_t height, const PyrDenoiseParams& params = denoise_params(),
+                 const std::vector<float>* albedo = nullptr, const std::vector<PyrFeaturePixel>* pixels = nullptr, int device = 0);
+// What is wrong with --denoise / --denoise-radius, in the words both front ends print, or "" (pyrite_amd/develop.py
+// denoise_flag_problem). `pixel_samples`: the render's budget once the project is loaded; `pass_samples`: --pass-samples, when given.
+std::string denoise_flag_problem(bool denoise, const std::optional<long>& denoise_radius, const std::optional<uint32_t>& pixel_samples = std::nullopt,
+                                 const std::optional<long>& pass_samples = std::nullopt);
+
 struct Progress { // renderer/mod.rs:229-232
     uint8_t progress;
     const char* message;
@@ -375,6 +391,10 @@ class Session {
     Film film();
     std::vector<float> noise(); // per tile of the make_tiles grid, raster order (pyr_session_noise): needs halves and two passes
     Features features(uint32_t grid = 1, uint32_t albedo_bins = 16); // pyr_session_features: after the passes enqueued so far; the film is not touched
+    // pyr_session_denoised: the two half films developed to linear sRGB and cross filtered on the session's device; with `guides` the
+    // feature pass (grid, albedo_bins) runs first and steers the filter. Needs halves and two passes; the films are not touched.
+    Denoised denoised(const PyrDenoiseParams& params = denoise_params(), bool guides = true, float step_size = 2.0f, const std::optional<Expression>& filter = std::nullopt,
+                      const std::optional<Expression>& white = std::nullopt, uint32_t grid = 1, uint32_t albedo_bins = 16);
     uint32_t tiles_x() const { return (width_ + tile_size_ - 1) / tile_size_; }
     uint32_t tiles_y() const { return (height_ + tile_size_ - 1) / tile_size_; }
 

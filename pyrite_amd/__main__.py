@@ -5,6 +5,7 @@
     python -m pyrite_amd path/to/project.lua [-o out.png] [--seed N] [--device D] [--spp N] [--size WxH]
                          [--pass-samples N] [--preview PATH] [--preview-every SECONDS] [--noise]
                          [--features PREFIX] [--features-grid N] [--hdr PATH] [--exposure EV|auto] [--tone clip|reinhard]
+                         [--denoise] [--denoise-radius N]
 
 With --pass-samples, --preview or --noise the render runs as a progressive session (pyr_session_*): passes of N samples per pixel
 over the whole image, the preview image rewritten from the live film every SECONDS or more (main.rs:261-299; developed on the GPU
@@ -17,7 +18,12 @@ writes PREFIX_albedo.png, PREFIX_normal.png and PREFIX_depth.png.
 With --hdr the final film is also written in linear light (linear sRGB, step 2, the project's filter and white): Radiance RGBE for
 PATH.hdr, PFM for PATH.pfm. --exposure (stops, or auto: the median luminance to 0.18) and --tone (clip, or reinhard: the extended
 Reinhard curve on luminance; alone it means --exposure auto) apply to the final PNG and to the previews. Without them the PNG is
-the reference's hard clamp, byte for byte."""
+the reference's hard clamp, byte for byte.
+
+With --denoise the render runs as a session with two half films, in an even number of equal passes (two of half the samples when
+--pass-samples is not given; an odd number of samples per pixel is refused), and the final PNG and the --hdr image are written
+from the denoised linear image (pyr_session_denoised with the feature pass as its guide; window radius N, default 5): the PNG
+through the tone curve, which without --exposure / --tone is the clip at exposure 1, the encoder of the plain PNG."""
 import argparse
 import os
 import sys
@@ -44,8 +50,8 @@ def render_progressive(r, cam, world, film, args, image, on_status):
 
     from .develop import save_png
 
-    pass_samples = args.pass_samples or DEFAULT_PASS_SAMPLES
-    with r.session((film.width, film.height), cam, world, halves=args.noise, device=args.device) as s:
+    pass_samples = args.pass_samples or (r.pixel_samples // 2 if args.denoise else DEFAULT_PASS_SAMPLES)
+    with r.session((film.width, film.height), cam, world, halves=args.noise or args.denoise, device=args.device) as s:
         on_status(0, "Rendering")
         last_image = time.monotonic()  # main.rs:241
         while s.samples_done < r.pixel_samples:
@@ -59,6 +65,9 @@ def render_progressive(r, cam, world, film, args, image, on_status):
                     noise = s.noise()
                     print("noise: largest tile %.4g, median tile %.4g" % (float(noise.max()), float(np.median(noise))))
                 last_image = time.monotonic()
+        if args.denoise:
+            params = {} if args.denoise_radius is None else {"radius": args.denoise_radius}
+            args.denoised = s.denoised(2.0, filter=image.get("filter"), white=image.get("white"), **params)[0]
         return s.film()
 
 
@@ -79,12 +88,14 @@ def main(argv=None):
     ap.add_argument("--hdr", default=None, metavar="PATH", help="also write the image in linear light: PATH.hdr (Radiance RGBE) or PATH.pfm")
     ap.add_argument("--exposure", default=None, metavar="EV|auto", help="exposure of the PNG and the previews in stops, or auto")
     ap.add_argument("--tone", default=None, metavar="clip|reinhard", help="tone curve of the PNG and the previews (reinhard alone means --exposure auto)")
+    ap.add_argument("--denoise", action="store_true", help="write the PNG and the --hdr image from the denoised linear image of two half films")
+    ap.add_argument("--denoise-radius", type=int, default=None, metavar="N", help="window radius of --denoise (1 to 10, default 5)")
     args = ap.parse_args(argv)
-    from .develop import tone_flag_problem, tone_from_flags
+    from .develop import denoise_flag_problem, tone_flag_problem, tone_from_flags
     from .features import features_flag_problem
 
     problem = (progressive_flag_problem(args.pass_samples, args.preview, args.preview_every, args.noise) or features_flag_problem(args.features, args.features_grid)
-               or tone_flag_problem(args.hdr, args.exposure, args.tone))
+               or tone_flag_problem(args.hdr, args.exposure, args.tone) or denoise_flag_problem(args.denoise, args.denoise_radius))
     if problem:
         print("error: " + problem, file=sys.stderr)
         return 2
@@ -100,6 +111,10 @@ def main(argv=None):
         project.setdefault("image", {}).update(width=w, height=h)
     if args.spp:
         project["renderer"] = project["renderer"].with_(pixel_samples=args.spp)
+    problem = denoise_flag_problem(args.denoise, args.denoise_radius, int(project["renderer"].pixel_samples), args.pass_samples)
+    if problem:
+        print("error: " + problem, file=sys.stderr)
+        return 2
     seed = args.seed if args.seed is not None else int(time.time_ns() & 0x7FFFFFFFFFFFFFFF)
     world, cam, r, film = scenes.build(project, seed=seed, base_dir=base_dir)
     print("The scene contains %d objects." % (len(world.flat.tri_material) + len(world.flat.spheres) + len(world.flat.planes)))  # world.rs:251-254
@@ -109,16 +124,18 @@ def main(argv=None):
 
     t = time.time()
     image = project.get("image") or {}
-    if args.pass_samples is not None or args.preview or args.noise:
+    if args.pass_samples is not None or args.preview or args.noise or args.denoise:
         film = render_progressive(r, cam, world, film, args, image, on_status)
     else:
         r.render(film, cam, world, on_status=on_status, device=args.device)
     print("\rRendering... done in %.2f s (%.1f Msamples/s)" % (time.time() - t, film.width * film.height * r.pixel_samples / (time.time() - t) / 1e6))
     print("Saving final result...")  # main.rs:313
     linear = None
-    if args.hdr or args.tone_params is not None:
+    if args.denoise:
+        linear = args.denoised
+    elif args.hdr or args.tone_params is not None:
         linear = develop_linear(film, "srgb", filter=image.get("filter"), white=image.get("white"), device=args.device)
-    if args.tone_params is not None:
+    if args.tone_params is not None or args.denoise:
         rgb = tonemap(linear, args.tone_params, device=args.device)
     else:
         rgb = develop(film, filter=image.get("filter"), white=image.get("white"), device=args.device)

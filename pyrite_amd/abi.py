@@ -306,6 +306,24 @@ class PyrToneParams(C.Structure):
     ]
 
 
+PYR_DENOISE_RADIUS, PYR_DENOISE_PATCH, PYR_DENOISE_K, PYR_DENOISE_EPSILON = 5, 1, 0.45, 1e-10
+PYR_DENOISE_SIGMA_ALBEDO, PYR_DENOISE_SIGMA_NORMAL, PYR_DENOISE_SIGMA_DEPTH = 0.02, 0.1, 0.02
+PYR_DENOISE_MAX_RADIUS, PYR_DENOISE_MAX_PATCH = 10, 3
+
+
+class PyrDenoiseParams(C.Structure):
+    _fields_ = [
+        ("radius", C.c_uint32),
+        ("patch", C.c_uint32),
+        ("k", C.c_float),
+        ("epsilon", C.c_float),
+        ("sigma_albedo", C.c_float),
+        ("sigma_normal", C.c_float),
+        ("sigma_depth", C.c_float),
+        ("reserved", C.c_uint32),
+    ]
+
+
 PyrProgressFn = C.CFUNCTYPE(None, C.c_void_p, C.c_uint8, C.c_char_p)
 PyrPreviewFn = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, C.c_uint32)
 
@@ -384,6 +402,12 @@ ENTRY_POINTS = {
     "pyr_image_tonemap_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PyrToneParams), C.c_void_p, C.c_int, C.c_void_p]),
     "pyr_session_linear": (C.c_int, [C.c_void_p, C.POINTER(PyrDevelopParams), C.c_uint32, C.c_void_p]),
     "pyr_session_preview_tone": (C.c_int, [C.c_void_p, C.POINTER(PyrDevelopParams), C.POINTER(PyrToneParams), C.c_void_p, C.POINTER(PyrImageStats)]),
+    "pyr_image_denoise": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PyrDenoiseParams), C.c_void_p, C.c_void_p, C.c_int]),
+    "pyr_image_denoise_device": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PyrDenoiseParams), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    ),
+    "pyr_session_denoised": (C.c_int, [C.c_void_p, C.POINTER(PyrDevelopParams), C.POINTER(PyrFeatureParams), C.POINTER(PyrDenoiseParams), C.c_void_p, C.c_void_p]),
 }
 
 

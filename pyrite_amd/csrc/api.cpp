@@ -1919,3 +1919,140 @@ int pyr_session_preview_tone(PyrSession* session, const PyrDevelopParams* develo
 }
 
 } // extern "C"
+
+// ------------------------------------------------------------------------------------------------ denoising a linear image from two halves
+namespace {
+
+// What the three denoise entries refuse before a device is looked for.
+int check_denoise_params(const PyrDenoiseParams* p) {
+    if (!p) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: params");
+    if (p->radius < 1 || p->radius > PYR_DENOISE_MAX_RADIUS) return fail(PYR_ERR_INVALID_ARGUMENT, "params->radius must be 1..10");
+    if (p->patch > PYR_DENOISE_MAX_PATCH) return fail(PYR_ERR_INVALID_ARGUMENT, "params->patch must be 0..3");
+    if (!(p->k > 0.0f)) return fail(PYR_ERR_INVALID_ARGUMENT, "params->k must be positive");
+    if (!(p->epsilon > 0.0f)) return fail(PYR_ERR_INVALID_ARGUMENT, "params->epsilon must be positive");
+    if (p->reserved != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "params->reserved must be 0");
+    return PYR_OK;
+}
+int check_denoise_args(const void* a, const void* b, uint32_t width, uint32_t height, const PyrDenoiseParams* p, const void* out) {
+    if (!a) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: a");
+    if (!b) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: b");
+    if (!out) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: out");
+    if (int bad = check_denoise_params(p)) return bad;
+    if (width == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "width: an empty image");
+    if (height == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "height: an empty image");
+    return check_image_size(width, height);
+}
+
+// Variance, the two filter launches with the halves exchanged, the combine: everything on `stream`, every buffer on the current
+// device; `work` holds three images of width * height * 3 floats (V, FA, FB).
+int enqueue_denoise(const float* a, const float* b, const float* albedo, const PyrFeaturePixel* pixels, uint32_t width, uint32_t height, const PyrDenoiseParams* p,
+                    float* work, float* out, float* error_out, hipStream_t stream) {
+    const size_t floats = (size_t)width * height * 3;
+    float *variance = work, *fa = work + floats, *fb = work + 2 * floats;
+    int rc;
+    if ((rc = launch_denoise_variance(a, b, width, height, variance, stream)) != PYR_OK) return fail(rc, denoise_kernels_last_error());
+    DenoiseLaunch L{};
+    L.variance = variance;
+    L.albedo = albedo, L.pixels = pixels;
+    L.width = width, L.height = height, L.radius = p->radius, L.patch = p->patch;
+    L.kk = p->k * p->k, L.epsilon = p->epsilon;
+    L.albedo_div = 2.0f * (p->sigma_albedo * p->sigma_albedo), L.normal_div = 2.0f * (p->sigma_normal * p->sigma_normal), L.depth_div = 2.0f * (p->sigma_depth * p->sigma_depth);
+    if (!(p->sigma_albedo > 0.0f)) L.albedo_div = 0.0f;
+    if (!(p->sigma_normal > 0.0f)) L.normal_div = 0.0f;
+    if (!(p->sigma_depth > 0.0f)) L.depth_div = 0.0f;
+    L.weights_from = b, L.averaged = a, L.out = fa; // FA: a under the weights of b
+    if ((rc = launch_denoise_filter(L, stream)) != PYR_OK) return fail(rc, denoise_kernels_last_error());
+    L.weights_from = a, L.averaged = b, L.out = fb;
+    if ((rc = launch_denoise_filter(L, stream)) != PYR_OK) return fail(rc, denoise_kernels_last_error());
+    if ((rc = launch_denoise_combine(fa, fb, (size_t)width * height, out, error_out, stream)) != PYR_OK) return fail(rc, denoise_kernels_last_error());
+    return PYR_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int pyr_image_denoise_device(const float* a_device, const float* b_device, const float* albedo_device, const PyrFeaturePixel* pixels_device, uint32_t width,
+                             uint32_t height, const PyrDenoiseParams* params, float* out_device, float* error_out_device, int device, void* hip_stream) {
+    int rc = check_denoise_args(a_device, b_device, width, height, params, out_device);
+    if (rc != PYR_OK || (rc = check_device(device)) != PYR_OK) return rc;
+    HIP_TRY(hipSetDevice(device));
+    hipStream_t stream = (hipStream_t)hip_stream;
+    float* work = nullptr;
+    HIP_TRY(hipMallocAsync((void**)&work, (size_t)width * height * 9 * sizeof(float), stream));
+    rc = enqueue_denoise(a_device, b_device, albedo_device, pixels_device, width, height, params, work, out_device, error_out_device, stream);
+    const hipError_t e = hipFreeAsync(work, stream);
+    if (rc != PYR_OK) return rc;
+    if (e != hipSuccess) return hip_fail(e, "hipFreeAsync");
+    return PYR_OK;
+}
+
+int pyr_image_denoise(const float* a, const float* b, const float* albedo, const PyrFeaturePixel* pixels, uint32_t width, uint32_t height,
+                      const PyrDenoiseParams* params, float* out, float* error_out, int device) {
+    int rc = check_denoise_args(a, b, width, height, params, out);
+    if (rc != PYR_OK || (rc = check_device(device)) != PYR_OK) return rc;
+    HIP_TRY(hipSetDevice(device));
+    const size_t count = (size_t)width * height, image_bytes = count * 3 * sizeof(float);
+    DeviceBuffer a_dev, b_dev, albedo_dev, pixels_dev, work_dev, out_dev, error_dev;
+    if ((rc = a_dev.upload(a, image_bytes)) != PYR_OK || (rc = b_dev.upload(b, image_bytes)) != PYR_OK) return rc;
+    if (albedo && (rc = albedo_dev.upload(albedo, image_bytes)) != PYR_OK) return rc;
+    if (pixels && (rc = pixels_dev.upload(pixels, count * sizeof(PyrFeaturePixel))) != PYR_OK) return rc;
+    if ((rc = work_dev.alloc(3 * image_bytes)) != PYR_OK || (rc = out_dev.alloc(image_bytes)) != PYR_OK) return rc;
+    if (error_out && (rc = error_dev.alloc(image_bytes)) != PYR_OK) return rc;
+    rc = enqueue_denoise((const float*)a_dev.ptr, (const float*)b_dev.ptr, albedo ? (const float*)albedo_dev.ptr : nullptr,
+                         pixels ? (const PyrFeaturePixel*)pixels_dev.ptr : nullptr, width, height, params, (float*)work_dev.ptr, (float*)out_dev.ptr,
+                         error_out ? (float*)error_dev.ptr : nullptr, nullptr);
+    HIP_TRY(hipDeviceSynchronize()); // before the buffers above are freed, whatever happened
+    if (rc != PYR_OK) return rc;
+    HIP_TRY(hipMemcpy(out, out_dev.ptr, image_bytes, hipMemcpyDeviceToHost));
+    if (error_out) HIP_TRY(hipMemcpy(error_out, error_dev.ptr, image_bytes, hipMemcpyDeviceToHost));
+    return PYR_OK;
+}
+
+int pyr_session_denoised(PyrSession* session, const PyrDevelopParams* develop_params, const PyrFeatureParams* feature_params, const PyrDenoiseParams* denoise_params,
+                         float* out, float* error_out) {
+    if (!session) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: session");
+    PyrSession* s = session;
+    int rc = check_linear_args(&s->film, s, develop_params, PYR_LINEAR_SRGB, out);
+    if (rc != PYR_OK || (rc = check_denoise_params(denoise_params)) != PYR_OK) return rc;
+    if (feature_params && (rc = check_feature_args(s, "session", nullptr, false, &s->film, feature_params, s, s)) != PYR_OK) return rc;
+    if ((rc = session_ready(s)) != PYR_OK) return rc;
+    if (!s->halves) return fail(PYR_ERR_INVALID_ARGUMENT, "denoising needs the two half films: create the session with PYR_SESSION_HALVES");
+    if (s->passes < 2) return fail(PYR_ERR_INVALID_ARGUMENT, "denoising needs at least two passes: one half film is still empty");
+    const size_t count = (size_t)s->film.width * s->film.height, image_bytes = count * 3 * sizeof(float);
+    // a, b, the developed albedo, the filter's three working images, out, error_out: one allocation of eight images
+    DeviceBuffer images, albedo_film, records;
+    if ((rc = images.alloc(8 * image_bytes)) != PYR_OK) return rc;
+    float* image = (float*)images.ptr;
+    auto at = [&](size_t i) { return image + i * count * 3; };
+    auto enqueue = [&]() -> int {
+        int rc;
+        LinearLaunch L{};
+        if ((rc = session_develop_launch(s, develop_params, L.develop)) != PYR_OK) return rc;
+        L.space = PYR_LINEAR_SRGB;
+        L.develop.grains = (const PyrGrain*)s->film_a.ptr, L.develop.grains_b = nullptr, L.out = at(0);
+        if ((rc = launch_develop_linear(L, s->stream)) != PYR_OK) return fail(rc, tone_kernels_last_error());
+        L.develop.grains = (const PyrGrain*)s->film_b.ptr, L.out = at(1);
+        if ((rc = launch_develop_linear(L, s->stream)) != PYR_OK) return fail(rc, tone_kernels_last_error());
+        if (feature_params) {
+            const size_t albedo_bytes = count * feature_params->albedo_bins * sizeof(PyrGrain);
+            if ((rc = albedo_film.alloc(albedo_bytes)) != PYR_OK || (rc = records.alloc(count * sizeof(PyrFeaturePixel))) != PYR_OK) return rc;
+            HIP_TRY(hipMemsetAsync(albedo_film.ptr, 0, albedo_bytes, s->stream));
+            if ((rc = enqueue_features(s->scene, &s->camera, &s->film, feature_params, (PyrGrain*)albedo_film.ptr, (PyrFeaturePixel*)records.ptr, s->stream)) != PYR_OK) return rc;
+            L.develop.film.bins = feature_params->albedo_bins; // the same span, tables and parameters
+            L.develop.grains = (const PyrGrain*)albedo_film.ptr, L.out = at(2);
+            if ((rc = launch_develop_linear(L, s->stream)) != PYR_OK) return fail(rc, tone_kernels_last_error());
+        }
+        rc = enqueue_denoise(at(0), at(1), feature_params ? at(2) : nullptr, feature_params ? (const PyrFeaturePixel*)records.ptr : nullptr, s->film.width, s->film.height,
+                             denoise_params, at(3), at(6), error_out ? at(7) : nullptr, s->stream);
+        if (rc != PYR_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(out, at(6), image_bytes, hipMemcpyDeviceToHost, s->stream));
+        if (error_out) HIP_TRY(hipMemcpyAsync(error_out, at(7), image_bytes, hipMemcpyDeviceToHost, s->stream));
+        return PYR_OK;
+    };
+    rc = enqueue();
+    const int synced = session_sync(s); // before the buffers above are freed, whatever happened
+    return rc != PYR_OK ? rc : synced;
+}
+
+} // extern "C"

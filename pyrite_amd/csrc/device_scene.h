@@ -271,6 +271,26 @@ struct ToneLaunch {
 int launch_tonemap(const ToneLaunch& launch, void* stream);
 const char* tone_kernels_last_error();
 
+// kernels/denoise.hip: the cross filter of two developed half images. One launch filters `averaged` with
+// the weights read from `weights_from`; the caller launches it twice with the halves exchanged and combines the two results.
+struct DenoiseLaunch {
+    const float* weights_from; // device, height * width * 3 floats: the half H of the colour distance
+    const float* averaged;     // device, the other half
+    const float* variance;     // device, height * width * 3 floats (launch_denoise_variance)
+    const float* albedo;             // device, height * width * 3 floats, or nullptr
+    const PyrFeaturePixel* pixels;   // device, height * width records, or nullptr
+    uint32_t width, height, radius, patch;
+    float kk, epsilon;                         // k * k
+    float albedo_div, normal_div, depth_div;   // 2.0f * (sigma * sigma); <= 0: that guide is off
+    float* out;       // device, height * width * 3 floats
+    uint32_t tiles_x; // set by the launcher
+};
+int launch_denoise_variance(const float* a, const float* b, uint32_t width, uint32_t height, float* variance, void* stream);
+int launch_denoise_filter(const DenoiseLaunch& launch, void* stream);
+// out = (fa + fb) * 0.5f and, unless it is nullptr, error_out = fabsf(fa - fb) * 0.5f
+int launch_denoise_combine(const float* fa, const float* fb, size_t pixels, float* out, float* error_out, void* stream);
+const char* denoise_kernels_last_error();
+
 // Adds the PYR_FILM_TILE_BLOCKS buffer of the tiles tile_begin + k * tile_stride (k < tile_count) into a whole-image film.
 struct AssembleLaunch {
     PyrFilmDesc film;

@@ -1360,6 +1360,38 @@ std::vector<float> Session::noise() {
     return out;
 }
 
+Denoised Session::denoised(const PyrDenoiseParams& params, bool guides, float step_size, const std::optional<Expression>& filter, const std::optional<Expression>& white,
+                           uint32_t grid, uint32_t albedo_bins) {
+    const DevelopSetup setup(shape_, filter, white, step_size);
+    const PyrFeatureParams fp{grid, albedo_bins, {0, 0}};
+    Denoised out{std::vector<float>((size_t)width_ * height_ * 3, 0.0f), std::vector<float>((size_t)width_ * height_ * 3, 0.0f)};
+    check_status(pyr_session_denoised(handle_, &setup.p, guides ? &fp : nullptr, &params, out.image.data(), out.error.data()));
+    return out;
+}
+
+// ---- denoising -----------------------------------------------------------------------------------------------------------------
+PyrDenoiseParams denoise_params(uint32_t radius, uint32_t patch) {
+    return PyrDenoiseParams{radius, patch, PYR_DENOISE_K, PYR_DENOISE_EPSILON, PYR_DENOISE_SIGMA_ALBEDO, PYR_DENOISE_SIGMA_NORMAL, PYR_DENOISE_SIGMA_DEPTH, 0u};
+}
+Denoised denoise(const std::vector<float>& a, const std::vector<float>& b, uint32_t width, uint32_t height, const PyrDenoiseParams& params, const std::vector<float>* albedo,
+                 const std::vector<PyrFeaturePixel>* pixels, int device) {
+    const size_t count = (size_t)width * height;
+    if (a.size() != count * 3 || b.size() != count * 3 || (albedo && albedo->size() != count * 3) || (pixels && pixels->size() != count))
+        throw ProjectError("denoise: buffer size does not match the image size");
+    Denoised out{std::vector<float>(count * 3, 0.0f), std::vector<float>(count * 3, 0.0f)};
+    check_status(pyr_image_denoise(a.data(), b.data(), albedo ? albedo->data() : nullptr, pixels ? pixels->data() : nullptr, width, height, &params, out.image.data(),
+                                   out.error.data(), device));
+    return out;
+}
+std::string denoise_flag_problem(bool denoise, const std::optional<long>& denoise_radius, const std::optional<uint32_t>& pixel_samples, const std::optional<long>& pass_samples) {
+    if (denoise_radius && !denoise) return "--denoise-radius needs --denoise";
+    if (denoise_radius && (*denoise_radius < 1 || *denoise_radius > (long)PYR_DENOISE_MAX_RADIUS)) return "--denoise-radius must be 1 to " + std::to_string(PYR_DENOISE_MAX_RADIUS);
+    if (denoise && pixel_samples && *pixel_samples % 2u) return "--denoise needs an even number of samples per pixel: the two half films must be equal";
+    if (denoise && pixel_samples && pass_samples && *pass_samples > 0 && *pixel_samples % (2u * (uint64_t)*pass_samples))
+        return "--denoise needs an even number of equal passes: the samples per pixel must be a multiple of twice --pass-samples";
+    return "";
+}
+
 // ---- first-hit feature images --------------------------------------------------------------------------------------------------
 Features Renderer::features(uint32_t width, uint32_t height, const Camera& camera, World& world, uint32_t grid, uint32_t albedo_bins, int device) const {
     Features out{Film(width, height, albedo_bins, spectrum_span[0], spectrum_span[1]), std::vector<PyrFeaturePixel>((size_t)width * height)};

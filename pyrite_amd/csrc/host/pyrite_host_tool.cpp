@@ -241,7 +241,7 @@ int main(int argc, char** argv) {
             write_dump(argv[4], flat, loaded.project);
             return 0;
         }
-        if (argc >= 6 && std::string(argv[1]) == "render-project") { // render-project <project.lua> <texel dir | -> <seed> <out.png> [film.bin] [--pass-samples N] [--preview PATH] [--preview-every SECONDS] [--noise]
+        if (argc >= 6 && std::string(argv[1]) == "render-project") { // render-project <project.lua> <texel dir | -> <seed> <out.png> [film.bin] [--pass-samples N] [--preview PATH] [--preview-every SECONDS] [--noise] [--denoise] [--denoise-radius N]
             // the flags of python -m pyrite_amd: a progressive session with previews (main.rs:261-299) instead of one blocking call
             std::optional<long> pass_samples;
             std::string preview_path, film_path;
@@ -250,6 +250,8 @@ int main(int argc, char** argv) {
             std::string features_prefix, size;
             std::optional<long> features_grid, spp;
             std::optional<std::string> hdr, exposure, tone_name;
+            bool denoise_flag = false;
+            std::optional<long> denoise_radius;
             for (int i = 6; i < argc; ++i) {
                 const std::string a = argv[i];
                 auto value = [&]() -> const char* {
@@ -274,6 +276,10 @@ int main(int argc, char** argv) {
                     exposure = value();
                 else if (a == "--tone")
                     tone_name = value();
+                else if (a == "--denoise")
+                    denoise_flag = true;
+                else if (a == "--denoise-radius")
+                    denoise_radius = std::strtol(value(), nullptr, 10);
                 else if (a == "--size")
                     size = value();
                 else if (a == "--spp")
@@ -286,6 +292,7 @@ int main(int argc, char** argv) {
             std::string problem = progressive_flag_problem(pass_samples, !preview_path.empty(), preview_every, noise);
             if (problem.empty()) problem = features_flag_problem(!features_prefix.empty(), features_grid);
             if (problem.empty()) problem = tone_flag_problem(hdr, exposure, tone_name);
+            if (problem.empty()) problem = denoise_flag_problem(denoise_flag, denoise_radius);
             if (!problem.empty()) {
                 std::fprintf(stderr, "error: %s\n", problem.c_str());
                 return 2;
@@ -299,15 +306,21 @@ int main(int argc, char** argv) {
             }
             if (spp && *spp > 0) loaded.project.renderer.pixel_samples = (uint32_t)*spp;
             const Project& project = loaded.project;
+            problem = denoise_flag_problem(denoise_flag, denoise_radius, project.renderer.pixel_samples, pass_samples);
+            if (!problem.empty()) {
+                std::fprintf(stderr, "error: %s\n", problem.c_str());
+                return 2;
+            }
             std::unique_ptr<World> world = World::from_project(project.world, loaded.base_dir);
             const Camera cam = Camera::from_project(project.camera);
             Renderer r = Renderer::from_project(project.renderer);
             r.seed = std::strtoull(argv[4], nullptr, 10);
             Film film = r.new_film(project.image.width, project.image.height);
             std::printf("The scene contains %zu objects.\n", world->num_objects()); // world.rs:251-254
-            if (pass_samples || !preview_path.empty() || noise) {
-                const uint32_t per_pass = pass_samples ? (uint32_t)*pass_samples : kDefaultPassSamples;
-                Session session(r, film.width, film.height, cam, *world, noise);
+            std::vector<float> linear;
+            if (pass_samples || !preview_path.empty() || noise || denoise_flag) {
+                const uint32_t per_pass = pass_samples ? (uint32_t)*pass_samples : denoise_flag ? r.pixel_samples / 2u : kDefaultPassSamples;
+                Session session(r, film.width, film.height, cam, *world, noise || denoise_flag);
                 auto last_image = std::chrono::steady_clock::now(); // main.rs:241
                 while (session.samples_done() < r.pixel_samples) {
                     session.render(per_pass);
@@ -328,14 +341,18 @@ int main(int argc, char** argv) {
                         last_image = std::chrono::steady_clock::now();
                     }
                 }
+                if (denoise_flag)
+                    linear = session.denoised(denoise_params(denoise_radius ? (uint32_t)*denoise_radius : PYR_DENOISE_RADIUS), true, 2.0f, project.image.filter, project.image.white).image;
                 film = session.film();
             } else {
                 r.render(film, cam, *world);
             }
             std::printf("Saving final result...\n"); // main.rs:313
-            std::vector<float> linear;
-            if (hdr || tone) linear = develop_linear(film, PYR_LINEAR_SRGB, project.image.filter, project.image.white);
-            save_png(argv[5], tone ? tonemap(linear, film.width, film.height, *tone) : film.develop(project.image.filter, project.image.white), film.width, film.height);
+            if (!denoise_flag && (hdr || tone)) linear = develop_linear(film, PYR_LINEAR_SRGB, project.image.filter, project.image.white);
+            save_png(argv[5],
+                     tone || denoise_flag ? tonemap(linear, film.width, film.height, tone ? *tone : tone_params(PYR_TONE_CLIP, 1.0f))
+                                          : film.develop(project.image.filter, project.image.white),
+                     film.width, film.height);
             if (hdr) {
                 write_linear(*hdr, linear, film.width, film.height);
                 std::printf("wrote %s\n", hdr->c_str());

@@ -215,6 +215,47 @@ def tonemap(rgb, tone=None, stats=None, device=0):
     return out
 
 
+# ---------------------------------------------------------------------------------------------- denoising
+def denoise_params(radius=abi.PYR_DENOISE_RADIUS, patch=abi.PYR_DENOISE_PATCH, k=abi.PYR_DENOISE_K, epsilon=abi.PYR_DENOISE_EPSILON,
+                   sigma_albedo=abi.PYR_DENOISE_SIGMA_ALBEDO, sigma_normal=abi.PYR_DENOISE_SIGMA_NORMAL, sigma_depth=abi.PYR_DENOISE_SIGMA_DEPTH):
+    """abi.PyrDenoiseParams: the window is (2*radius+1)^2 pixels, the patch (2*patch+1)^2; a sigma <= 0 turns that guide off."""
+    return abi.PyrDenoiseParams(int(radius), int(patch), float(k), float(epsilon), float(sigma_albedo), float(sigma_normal), float(sigma_depth), 0)
+
+
+def denoise(a, b, albedo=None, pixels=None, device=0, **params):
+    """(image, error), float32 [height, width, 3] each: the two half images `a` and `b` (linear light, independent samples of one
+    picture) cross filtered on the GPU (pyr_image_denoise; include/pyrite_gpu.h has the arithmetic) and the noise that is left.
+    Guides: `albedo`, a linear image, and `pixels`, the records of the feature pass (Features.records). `params`: denoise_params."""
+    a, b = _linear_image(a), _linear_image(b)
+    assert a.shape == b.shape
+    h, w, _ = a.shape
+    if albedo is not None:
+        albedo = _linear_image(albedo)
+        assert albedo.shape == a.shape
+    if pixels is not None:
+        pixels = np.ascontiguousarray(pixels)
+        assert pixels.nbytes == h * w * C.sizeof(abi.PyrFeaturePixel)
+    p = denoise_params(**params)
+    out, error = np.zeros(a.shape, dtype=np.float32), np.zeros(a.shape, dtype=np.float32)
+    check(lib().pyr_image_denoise(a.ctypes.data, b.ctypes.data, albedo.ctypes.data if albedo is not None else None, pixels.ctypes.data if pixels is not None else None,
+                                  w, h, C.byref(p), out.ctypes.data, error.ctypes.data, int(device)))
+    return out, error
+
+
+def denoise_flag_problem(denoise, denoise_radius, pixel_samples=None, pass_samples=None):
+    """What is wrong with --denoise / --denoise-radius, in the words pyrite_host_tool uses too, or None. `pixel_samples`: the
+    render's budget once the project is loaded; `pass_samples`: --pass-samples, when given."""
+    if denoise_radius is not None and not denoise:
+        return "--denoise-radius needs --denoise"
+    if denoise_radius is not None and not 1 <= denoise_radius <= abi.PYR_DENOISE_MAX_RADIUS:
+        return "--denoise-radius must be 1 to %d" % abi.PYR_DENOISE_MAX_RADIUS
+    if denoise and pixel_samples is not None and pixel_samples % 2:
+        return "--denoise needs an even number of samples per pixel: the two half films must be equal"
+    if denoise and pixel_samples is not None and pass_samples and pixel_samples % (2 * pass_samples):
+        return "--denoise needs an even number of equal passes: the samples per pixel must be a multiple of twice --pass-samples"
+    return None
+
+
 RGBE_MAX = 255.0 * 2.0 ** 119  # the largest value a Radiance pixel holds: mantissa 255, exponent byte 255
 
 

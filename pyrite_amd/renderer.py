@@ -294,6 +294,21 @@ class Session:
         check(lib().pyr_session_noise(self.handle, out.ctypes.data))
         return out
 
+    def denoised(self, step=2.0, filter=None, white=None, guides=True, grid=1, albedo_bins=16, **params):
+        """(image, error), float32 [height, width, 3] each: the two half films developed to linear sRGB and cross filtered on the
+        session's device (pyr_session_denoised; develop.denoise of the developed half_films() gives the same floats). With `guides`
+        the feature pass (features(grid, albedo_bins)) runs first and its albedo, normals and depths steer the filter. `params`:
+        develop.denoise_params. Needs `halves` and two passes, best an even number of equal ones. The films are not touched."""
+        from .develop import denoise_params, develop_params
+
+        p, keep = develop_params(self._film, step, filter, white)
+        dp = denoise_params(**params)
+        fp = abi.PyrFeatureParams(int(grid), int(albedo_bins)) if guides else None
+        out, error = np.zeros((self.height, self.width, 3), dtype=np.float32), np.zeros((self.height, self.width, 3), dtype=np.float32)
+        check(lib().pyr_session_denoised(self.handle, C.byref(p), C.byref(fp) if fp is not None else None, C.byref(dp), out.ctypes.data, error.ctypes.data))
+        del keep
+        return out, error
+
     def close(self):
         if self.handle:
             lib().pyr_session_destroy(self.handle)
