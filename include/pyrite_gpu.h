@@ -167,7 +167,9 @@ typedef struct PyrInstr {
     uint32_t op;         /* PyrOp */
     uint32_t value_type; /* PyrValueType, BINARY / MIX only */
     uint32_t operator_;  /* PyrBinaryOperator, BINARY only */
-    uint32_t deps;       /* Instruction::dependencies (instruction.rs:15) */
+    uint32_t deps;       /* Instruction::dependencies (instruction.rs:15): the inputs the instruction depends on, through the registers it reads
+                          * too. For a path's further wavelengths only the PYR_DEP_WAVELENGTH instructions run again, over the registers the
+                          * first run left (program/memoized.rs): a caller's program must compute the same value under both runs. */
     uint32_t output;     /* register index; the register file follows from op / value_type */
     uint32_t a;
     uint32_t b;

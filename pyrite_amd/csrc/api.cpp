@@ -758,7 +758,9 @@ int pack_and_upload(const PyrSceneDesc* d, PyrScene* s) {
             if (pr.tape_form == TAPE_FORM_PRODUCT) v.product_records = 1u;
         };
         for (uint32_t i = 0; i < d->num_components; ++i) colour(d->components[i].color_program);
-        for (const DevLamp& l : lamps) colour(l.color_program);
+        // (a shape lamp shines with its material's emissive components, counted above: its color_program is not read)
+        for (const DevLamp& l : lamps)
+            if (l.kind != PYR_LAMP_SHAPE) colour(l.color_program);
         colour(d->sky_program);
         if (tape_rows_needed(fast_programs, v.rgb_records != 0) > kTapeMaxValueRows) ok = false; // (counted here without LAMBDA's hit-tape condition: never fewer than the kernel finds)
         const char* off = std::getenv("PYRITE_HIT_TAPE"); // A/B and tests: PYRITE_HIT_TAPE=0 keeps the online form (read at scene creation)

@@ -14,6 +14,7 @@ import oracle
 from pyrite_amd import abi, build as gpu_build, lua_project, scenes
 from pyrite_amd.compiler import FlatScene, ProjectError
 from pyrite_amd.project import blackbody, material, renderer, rgb, shape, spectrum, texture, vector
+from program_gen import Gen
 from test_host_cpp import check_project_file, host  # noqa: F401 (fixture)
 
 PROJECTS = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "projects")
@@ -92,98 +93,6 @@ def test_the_front_ends_keep_a_sanity_bound():
 
 
 # ------------------------------------------------------------------------------------------------ 2. the pass on random programs
-class Gen:
-    """Well-typed single-assignment programs over every opcode, with shared subexpressions and every kind of dependency."""
-
-    def __init__(self, rng, num_spectra, colour_textures, mono_textures, wide=False):
-        self.rng, self.num_spectra, self.colour_textures, self.mono_textures = rng, num_spectra, colour_textures, mono_textures
-        self.wide = wide
-
-    def program(self, allow_wavelength=True, output="number"):
-        rng = self.rng
-        instrs, vals = [], {"n": [], "v": [], "c": []}  # (register, deps)
-        counts = {"n": 0, "v": 0, "c": 0}
-
-        def emit(file, deps, **kw):
-            ins = abi.PyrInstr()
-            for k, v in kw.items():
-                setattr(ins, k, v)
-            ins.deps, ins.output = deps, counts[file]
-            counts[file] += 1
-            instrs.append(ins)
-            vals[file].append((ins.output, deps))
-            return ins.output, deps
-
-        def number_operand():
-            r = rng.random()
-            if r < 0.25 or not vals["n"]:
-                if allow_wavelength and r < 0.12:
-                    return abi.PyrOperand(abi.OPERAND_INPUT, abi.INPUT_WAVELENGTH), WL
-                return abi.PyrOperand(abi.OPERAND_CONSTANT, int(np.float32(rng.uniform(0.05, 2.0)).view(np.uint32))), 0
-            reg, deps = vals["n"][rng.integers(len(vals["n"]))]
-            return abi.PyrOperand(abi.OPERAND_REGISTER, reg), deps
-
-        def pick(file):
-            return vals[file][rng.integers(len(vals[file]))]
-
-        def f32bits(v):
-            return abi.PyrOperand(abi.OPERAND_CONSTANT, int(np.float32(v).view(np.uint32)))
-
-        length = int(rng.integers(12, 90 if self.wide else 60))
-        for _ in range(length):
-            choice = rng.integers(0, 14)
-            if choice == 0 or not vals["n"]:
-                emit("n", 0, op=abi.OP_NUMBER, x=f32bits(rng.uniform(0.1, 1.5)))
-            elif choice == 1 and allow_wavelength:
-                x, d = number_operand()
-                if x.kind == abi.OPERAND_CONSTANT:
-                    x, d = abi.PyrOperand(abi.OPERAND_INPUT, abi.INPUT_WAVELENGTH), WL
-                emit("n", d, op=abi.OP_SPECTRUM, x=x, a=int(rng.integers(self.num_spectra)))
-            elif choice == 2 and allow_wavelength:
-                emit("n", WL, op=abi.OP_BLACKBODY, x=abi.PyrOperand(abi.OPERAND_INPUT, abi.INPUT_WAVELENGTH), y=f32bits(rng.uniform(2000, 8000)))
-            elif choice == 3:
-                (x, dx), (y, dy), (z, dz) = number_operand(), number_operand(), number_operand()
-                emit("n", dx | dy | dz, op=abi.OP_CLAMP, x=x, y=y, z=z)
-            elif choice == 4:
-                emit("n", abi.DEP_TEXTURE, op=abi.OP_MONO_TEXTURE, a=self.mono_textures[rng.integers(len(self.mono_textures))], b=abi.INPUT_TEXTURE)
-            elif choice == 5:
-                emit("c", abi.DEP_TEXTURE, op=abi.OP_COLOR_TEXTURE, a=self.colour_textures[rng.integers(len(self.colour_textures))], b=abi.INPUT_TEXTURE)
-            elif choice == 6:
-                (x, dx), (y, dy) = number_operand(), number_operand()
-                emit("n", dx | dy | abi.DEP_NORMAL | abi.DEP_INCIDENT, op=abi.OP_FRESNEL, x=x, y=y, a=abi.INPUT_NORMAL, b=abi.INPUT_INCIDENT)
-            elif choice == 7:
-                (x, dx), (y, dy), (z, dz) = number_operand(), number_operand(), number_operand()
-                emit("c", dx | dy | dz, op=abi.OP_RGB, x=x, y=y, z=z)
-            elif choice == 8:
-                ops = [number_operand() for _ in range(4)]
-                emit("v", ops[0][1] | ops[1][1] | ops[2][1] | ops[3][1], op=abi.OP_VECTOR, x=ops[0][0], y=ops[1][0], z=ops[2][0], w=ops[3][0])
-            elif choice == 9 and vals["c"] and allow_wavelength:
-                reg, d = pick("c")
-                emit("n", d | WL, op=abi.OP_RGB_SPECTRUM, x=abi.PyrOperand(abi.OPERAND_INPUT, abi.INPUT_WAVELENGTH), a=reg)
-            elif choice == 10 and vals["c"]:
-                reg, d = pick("c")
-                emit("v", d, op=abi.OP_RGB_TO_VECTOR, a=reg)
-            else:
-                file = ["n", "v", "c"][rng.integers(3)]
-                if not vals[file]:
-                    file = "n"
-                (ra, da), (rb, db) = pick(file), pick(file)
-                vt = {"n": abi.VT_NUMBER, "v": abi.VT_VECTOR, "c": abi.VT_RGB}[file]
-                if rng.random() < 0.3:
-                    x, dx = number_operand()
-                    emit(file, da | db | dx, op=abi.OP_MIX, value_type=vt, a=ra, b=rb, x=x)
-                else:
-                    emit(file, da | db, op=abi.OP_BINARY, value_type=vt, operator_=int(rng.integers(4)), a=ra, b=rb)
-        out_file = "n" if output == "number" else "v"
-        if output == "vector" and not vals["v"]:
-            emit("v", 0, op=abi.OP_VECTOR, x=f32bits(0.0), y=f32bits(0.0), z=f32bits(1.0), w=f32bits(0.0))
-        # the output: the last value of its file, most of the time a late one
-        reg = vals[out_file][-1][0] if rng.random() < 0.8 else pick(out_file)[0]
-        p = abi.PyrProgram(abi.PROGRAM_INSTRUCTIONS, 0.0, 0, len(instrs), abi.OUTPUT_NUMBER if output == "number" else abi.OUTPUT_VECTOR, reg,
-                           counts["n"], counts["v"], counts["c"])
-        return instrs, p
-
-
 def memoised_runs(instrs, p, wavelengths, texture=(0.3, 0.7)):
     """A small interpreter with the kernels' memoised re-run: a full run at wavelengths[0], then only the PYR_DEP_WAVELENGTH
     instructions at each further wavelength; the register files persist (filled with a marker first). Returns the outputs' bits."""
