@@ -418,6 +418,51 @@ typedef struct PyrBvhInfo {
 } PyrBvhInfo;
 int pyr_scene_bvh_info(PyrScene* scene, PyrBvhInfo* out);
 
+/* ---- who builds the acceleration structure. pyr_scene_create builds the binary tree on one host thread (binned SAH, 16 bins on
+ * three axes). pyr_scene_create_with may ask for the same tree from the device instead: level-synchronous binned SAH with the host
+ * builder's rules, expression for expression, so that where no node needs the median fallback (median_splits == 0 below) the
+ * tree is the host's -- the same nodes in the same order, the same PyrBvhInfo, the same hits and the same traversal counts; the
+ * order of the up to four primitives inside a leaf is the only freedom (the device builder stores them ascending by shape code).
+ * A node whose centroids cannot be separated by bins (coincident centroids, or the depth rule) is split at the median: the device
+ * gives slot 0 the count / 2 references smallest by (centroid on the widest axis, shape code), which is deterministic but may
+ * break ties differently from the host builder -- a valid tree of the same shape, possibly other leaves.
+ *   The collapse to four-child nodes, the pair records and the upload are the host's in both cases. The device builder steps
+ * aside, and the host builds, when spatial splits are asked for (PYRITE_SPATIAL_SPLITS=1) or when the scene is beyond what it
+ * handles; PyrBuildInfo says so. Two builds of one scene give the same bytes, whoever builds. */
+#define PYR_BUILD_HOST 0u
+#define PYR_BUILD_DEVICE 1u
+typedef struct PyrBuildParams {
+    uint32_t builder;     /* PYR_BUILD_HOST or PYR_BUILD_DEVICE */
+    uint32_t reserved[7]; /* zero */
+} PyrBuildParams;
+/* pyr_scene_create with a choice of builder. `build` NULL: exactly pyr_scene_create. An unknown `builder` or a non-zero reserved
+ * word is PYR_ERR_INVALID_ARGUMENT, reported before the description is looked at and before any device is touched. */
+int pyr_scene_create_with(const PyrSceneDesc* desc, int device, const PyrBuildParams* build, PyrScene** out_scene);
+
+#define PYR_BUILD_FALLBACK_NONE 0u
+#define PYR_BUILD_FALLBACK_SPATIAL_SPLITS 1u    /* PYRITE_SPATIAL_SPLITS=1 and the scene gets a pair tree: only the host splits space */
+#define PYR_BUILD_FALLBACK_MEDIAN_TOO_LARGE 2u  /* a node of more than 2048 references needed the median rule */
+#define PYR_BUILD_FALLBACK_INTERNAL 3u          /* the device's result did not pass the host's validation, or nodes were left after the
+                                                   last level the depth rule allows (never expected) */
+/* How a scene's acceleration structure was built, for host-built scenes too. Times are host wall-clock milliseconds of the
+ * stages of scene creation: the primitives' bounds; the binary tree (device builder: upload, every level, download; when it
+ * stepped aside, its attempt and the host build); its finishing pass (device builder only: renumbering into the host builder's
+ * layout); the collapse to four-child nodes; everything else (packing, pair records, upload); and all of scene creation. `reserved`
+ * is always 0. The digest is no part of scene creation: the first pyr_scene_build_info of a scene walks the binary tree, which the
+ * scene keeps on the host until then (64 bytes per node and 4 per primitive) and frees afterwards; later calls return the same value.
+ * `tree_digest`: a pre-order walk of the binary tree hashing each child's stored box (-0.0f read as +0.0f), depth and slot, and a
+ * leaf's shape codes sorted -- node numbers and the order inside a leaf do not enter, so equal digests mean the same tree. */
+typedef struct PyrBuildInfo {
+    uint32_t builder_asked, builder_used; /* differ when the device builder stepped aside */
+    uint32_t fallback_reason;             /* PYR_BUILD_FALLBACK_* */
+    uint32_t levels;                      /* iterations of the device builder's level loop (0: built on the host) */
+    uint32_t median_splits;               /* nodes split by the median rule: 0 means the tree is tie-free */
+    uint32_t reserved;
+    uint64_t tree_digest;
+    float bounds_ms, tree_ms, finish_ms, collapse_ms, pack_upload_ms, total_ms;
+} PyrBuildInfo;
+int pyr_scene_build_info(PyrScene* scene, PyrBuildInfo* out);
+
 /* Introspection of the kernel a render of `scene` with `params` would run (nothing is launched; only spectrum_samples is read
  * today). Results never depend on it -- every schedule is the same per-sample arithmetic as tracer.rs:208-345 -- but throughput
  * does, and a maintainer wants to see why a scene is slow: */

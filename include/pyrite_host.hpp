@@ -254,7 +254,12 @@ class World { // world.rs:31-36
   public:
     static std::unique_ptr<World> from_project(const WorldProject& world, const std::string& base_dir = ".");
     ~World();
-    PyrScene* scene(int device = 0, int copy = 0); // created on first use (BVH build + upload); `copy` > 0: a further scene on the same device
+    // Who builds the acceleration structure (pyr_scene_create_with): one host thread, or the device with the same rules and, where
+    // no node needs the median fallback, the same tree. The builder is chosen when a scene is first used (none given: the host);
+    // later calls get that scene, and naming another builder for it then is a ProjectError, as in the Python layer.
+    enum class Build { Host, Device };
+    PyrScene* scene(int device = 0, int copy = 0, std::optional<Build> build = std::nullopt); // created on first use (BVH build + upload); `copy` > 0: a further scene on the same device
+    PyrBuildInfo build_info(int device = 0, int copy = 0); // pyr_scene_build_info: the builder used, why if not the one asked for, stage times, tree digest
     // World::intersect (world.rs:273-299) for a batch of rays, [n][6] = origin, direction: closest hits, on the GPU
     std::vector<PyrHit> intersect(const std::vector<float>& rays, int device = 0, PyrCounters* counters = nullptr);
     FlatScene& flat() { return flat_; }
@@ -264,6 +269,7 @@ class World { // world.rs:31-36
     World() = default;
     FlatScene flat_;
     std::map<std::pair<int, int>, PyrScene*> scenes_;
+    std::map<std::pair<int, int>, Build> builders_; // what each scene was asked to be built by
 };
 
 struct Camera { // cameras.rs:20-27

@@ -5,7 +5,7 @@
     python -m pyrite_amd path/to/project.lua [-o out.png] [--seed N] [--device D] [--spp N] [--size WxH]
                          [--pass-samples N] [--preview PATH] [--preview-every SECONDS] [--noise]
                          [--features PREFIX] [--features-grid N] [--hdr PATH] [--exposure EV|auto] [--tone clip|reinhard]
-                         [--denoise] [--denoise-radius N]
+                         [--denoise] [--denoise-radius N] [--build host|device]
 
 With --pass-samples, --preview or --noise the render runs as a progressive session (pyr_session_*): passes of N samples per pixel
 over the whole image, the preview image rewritten from the live film every SECONDS or more (main.rs:261-299; developed on the GPU
@@ -23,7 +23,10 @@ the reference's hard clamp, byte for byte.
 With --denoise the render runs as a session with two half films, in an even number of equal passes (two of half the samples when
 --pass-samples is not given; an odd number of samples per pixel is refused), and the final PNG and the --hdr image are written
 from the denoised linear image (pyr_session_denoised with the feature pass as its guide; window radius N, default 5): the PNG
-through the tone curve, which without --exposure / --tone is the clip at exposure 1, the encoder of the plain PNG."""
+through the tone curve, which without --exposure / --tone is the clip at exposure 1, the encoder of the plain PNG.
+
+With --build the acceleration structure is built by the named builder (host: one CPU thread, the default; device: the same tree from
+the GPU, pyr_scene_create_with) and one line with the builder used and the stage times of scene creation goes to stderr."""
 import argparse
 import os
 import sys
@@ -90,6 +93,7 @@ def main(argv=None):
     ap.add_argument("--tone", default=None, metavar="clip|reinhard", help="tone curve of the PNG and the previews (reinhard alone means --exposure auto)")
     ap.add_argument("--denoise", action="store_true", help="write the PNG and the --hdr image from the denoised linear image of two half films")
     ap.add_argument("--denoise-radius", type=int, default=None, metavar="N", help="window radius of --denoise (1 to 10, default 5)")
+    ap.add_argument("--build", default=None, choices=["host", "device"], help="who builds the BVH (default host); given, the stage times of scene creation go to stderr")
     args = ap.parse_args(argv)
     from .develop import denoise_flag_problem, tone_flag_problem, tone_from_flags
     from .features import features_flag_problem
@@ -118,6 +122,13 @@ def main(argv=None):
     seed = args.seed if args.seed is not None else int(time.time_ns() & 0x7FFFFFFFFFFFFFFF)
     world, cam, r, film = scenes.build(project, seed=seed, base_dir=base_dir)
     print("The scene contains %d objects." % (len(world.flat.tri_material) + len(world.flat.spheres) + len(world.flat.planes)))  # world.rs:251-254
+
+    if args.build:
+        world.scene(args.device, build=args.build)
+        b = world.build_info(args.device)
+        print("build: asked %s, used %s (fallback %d), %d levels, %d median splits, digest %016x; bounds %.2f tree %.2f finish %.2f collapse %.2f pack+upload %.2f total %.2f ms"
+              % (args.build, "device" if b["builder_used"] == 1 else "host", b["fallback_reason"], b["levels"], b["median_splits"], b["tree_digest"],
+                 b["bounds_ms"], b["tree_ms"], b["finish_ms"], b["collapse_ms"], b["pack_upload_ms"], b["total_ms"]), file=sys.stderr)
 
     def on_status(percent, message):
         print("\r%s... %3d %%" % (message, percent), end="", flush=True)

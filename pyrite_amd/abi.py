@@ -229,6 +229,39 @@ class PyrBvhInfo(C.Structure):
     ]
 
 
+PYR_BUILD_HOST = 0
+PYR_BUILD_DEVICE = 1
+PYR_BUILD_FALLBACK_NONE = 0
+PYR_BUILD_FALLBACK_SPATIAL_SPLITS = 1
+PYR_BUILD_FALLBACK_MEDIAN_TOO_LARGE = 2
+PYR_BUILD_FALLBACK_INTERNAL = 3
+
+
+class PyrBuildParams(C.Structure):
+    _fields_ = [
+        ("builder", C.c_uint32),
+        ("reserved", C.c_uint32 * 7),
+    ]
+
+
+class PyrBuildInfo(C.Structure):
+    _fields_ = [
+        ("builder_asked", C.c_uint32),
+        ("builder_used", C.c_uint32),
+        ("fallback_reason", C.c_uint32),
+        ("levels", C.c_uint32),
+        ("median_splits", C.c_uint32),
+        ("reserved", C.c_uint32),
+        ("tree_digest", C.c_uint64),
+        ("bounds_ms", C.c_float),
+        ("tree_ms", C.c_float),
+        ("finish_ms", C.c_float),
+        ("collapse_ms", C.c_float),
+        ("pack_upload_ms", C.c_float),
+        ("total_ms", C.c_float),
+    ]
+
+
 class PyrPathInfo(C.Structure):
     _fields_ = [
         ("stage_scheduler", C.c_uint32),
@@ -346,6 +379,8 @@ ENTRY_POINTS = {
     "pyr_scene_intersect": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.POINTER(C.c_float), C.POINTER(PyrCounters)]),
     "pyr_scene_intersect_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_void_p, C.c_void_p]),
     "pyr_scene_bvh_info": (C.c_int, [C.c_void_p, C.POINTER(PyrBvhInfo)]),
+    "pyr_scene_create_with": (C.c_int, [C.POINTER(PyrSceneDesc), C.c_int, C.POINTER(PyrBuildParams), C.POINTER(C.c_void_p)]),
+    "pyr_scene_build_info": (C.c_int, [C.c_void_p, C.POINTER(PyrBuildInfo)]),
     "pyr_scene_path_info": (C.c_int, [C.c_void_p, C.POINTER(PyrRenderParams), C.POINTER(PyrPathInfo)]),
     "pyr_scene_program_info": (C.c_int, [C.c_void_p, C.POINTER(PyrProgramInfo)]),
     "pyr_program_allocate_registers": (C.c_int, [C.POINTER(PyrInstr), C.POINTER(PyrProgram), C.POINTER(PyrInstr), C.POINTER(PyrProgram)]),

@@ -15,6 +15,7 @@
 
 #include "api_internal.h"
 #include "bvh.h"
+#include "bvh_device.h"
 #include "device_scene.h"
 #include "program_regs.h"
 
@@ -340,6 +341,8 @@ struct PyrScene {
     int num_cus = 0;
     DevScene dev{};
     PyrBvhInfo info{};
+    PyrBuildInfo build_info{}; // pyr_scene_build_info
+    std::unique_ptr<pyr::BuiltBvh> digest_source; // the binary tree, kept until the first pyr_scene_build_info has hashed it (tree_digest walks the whole tree: not on every scene creation's bill)
     DeviceBuffer wide_nodes, wide_pair_nodes, pair_prims, nodes, prims, tri_shade, spheres, sphere_material, planes, plane_material, lamps, materials, components, programs, instrs, spectra,
         spectrum_data, rgb_basis, counters, tri_tex, sphere_tex_scale, plane_frames, textures, texture_data;
     PyrCounters last_counters{};
@@ -407,7 +410,14 @@ void plane_frame_from_normal(const float n[3], float q[4]) {
     }
 }
 
-int pack_and_upload(const PyrSceneDesc* d, PyrScene* s) {
+double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
+
+int pack_and_upload(const PyrSceneDesc* d, PyrScene* s, uint32_t builder) {
+    const auto t_start = std::chrono::steady_clock::now();
+    PyrBuildInfo& build_info = s->build_info;
+    build_info = PyrBuildInfo{};
+    build_info.builder_asked = builder;
+    build_info.builder_used = PYR_BUILD_HOST;
     const bool wide_vm = s->program_info.wide != 0;
     for (uint32_t i = 0; i < d->num_programs; ++i) // (the allocated description: the kernels read every range from the uploaded array)
         if (d->programs[i].kind == PYR_PROGRAM_INSTRUCTIONS && (uint64_t)d->programs[i].first_instr + d->programs[i].num_instrs > d->num_instrs)
@@ -454,7 +464,32 @@ int pack_and_upload(const PyrSceneDesc* d, PyrScene* s) {
     const bool cost_driven_collapse = pair_tree_expected && cost_driven_collapse_wanted();
     SpatialSplits spatial_params;
     spatial_params.tri_positions = d->tri_positions;
-    BuiltBvh bvh = spatial ? build_bvh_spatial(bounds, spatial_params) : build_bvh(bounds, pair_tree_expected);
+    const auto t_bounds = std::chrono::steady_clock::now();
+    BuiltBvh bvh;
+    bool built = false;
+    if (builder == PYR_BUILD_DEVICE && spatial) build_info.fallback_reason = PYR_BUILD_FALLBACK_SPATIAL_SPLITS; // only the host splits space
+    if (builder == PYR_BUILD_DEVICE && !spatial) {
+        DeviceBuildReport report;
+        std::string error;
+        if (!build_bvh_device(bounds, pair_tree_expected, bvh, report, error)) return fail(PYR_ERR_DEVICE, error);
+        build_info.fallback_reason = report.fallback_reason;
+        build_info.finish_ms = (float)report.finish_ms;
+        if (report.fallback_reason == PYR_BUILD_FALLBACK_NONE) {
+            built = true;
+            build_info.builder_used = PYR_BUILD_DEVICE;
+            build_info.levels = report.levels;
+            build_info.median_splits = report.median_splits;
+        }
+    }
+    if (!built) {
+        uint32_t medians = 0;
+        bvh = spatial ? build_bvh_spatial(bounds, spatial_params) : build_bvh(bounds, pair_tree_expected, &medians);
+        build_info.median_splits = medians; // (the spatial builder does not count its own)
+    }
+    const auto t_tree = std::chrono::steady_clock::now();
+    build_info.bounds_ms = (float)ms_between(t_start, t_bounds);
+    build_info.tree_ms = (float)ms_between(t_bounds, t_tree) - build_info.finish_ms;
+    double collapse_ms = 0.0;
     if (bvh.max_depth > 96) return fail(PYR_ERR_UNSUPPORTED, "BVH deeper than the LDS traversal stack allows");
     // spatial splits repeat triangles in prim_order (and so in `prims` and the pair records): a leaf code keeps `first` in 28 bits
     if (bvh.prim_order.size() >= (1ull << 28)) return fail(PYR_ERR_UNSUPPORTED, "scene too large: 2^28 primitive references or more");
@@ -618,7 +653,9 @@ int pack_and_upload(const PyrSceneDesc* d, PyrScene* s) {
     const char* wide_env = std::getenv("PYRITE_WIDE_BVH");
     const bool want_wide = (size_t)bvh.nodes.size() * 64 + prims.size() * 48 > 8 * 1024 && !(wide_env && wide_env[0] == '0');
     if (want_wide) {
+        const auto t_collapse = std::chrono::steady_clock::now();
         wide = cost_driven_collapse ? collapse_to_wide_sah(bvh) : collapse_to_wide(bvh);
+        collapse_ms = ms_between(t_collapse, std::chrono::steady_clock::now());
         if (wide.stack_need > kMaxStackDepth || wide.nodes.size() >= (1ull << 25)) wide = WideBvh{}; // too deep, or past 4 GB: the binary tree
     }
     // Triangle pairs for the wide tree's leaves (device_scene.h DevPrimPair): every leaf gets ceil(n / 2) records of its own and
@@ -794,6 +831,10 @@ int pack_and_upload(const PyrSceneDesc* d, PyrScene* s) {
     s->info.num_pair_records = (uint32_t)pairs.size();
     s->info.wide_node_bytes = wide.nodes.size() * sizeof(Node128);
     s->info.pair_record_bytes = pairs.size() * sizeof(DevPrimPair);
+    build_info.collapse_ms = (float)collapse_ms;
+    build_info.total_ms = (float)ms_between(t_start, std::chrono::steady_clock::now());
+    build_info.pack_upload_ms = build_info.total_ms - build_info.bounds_ms - build_info.tree_ms - build_info.finish_ms - build_info.collapse_ms;
+    s->digest_source.reset(new BuiltBvh(std::move(bvh)));
     return PYR_OK;
 }
 
@@ -1022,9 +1063,18 @@ int pyr_device_count(void) {
 
 const char* pyr_last_error(void) { return g_error.c_str(); }
 
-int pyr_scene_create(const PyrSceneDesc* desc, int device, PyrScene** out_scene) {
+int pyr_scene_create(const PyrSceneDesc* desc, int device, PyrScene** out_scene) { return pyr_scene_create_with(desc, device, nullptr, out_scene); }
+
+int pyr_scene_create_with(const PyrSceneDesc* desc, int device, const PyrBuildParams* build, PyrScene** out_scene) {
     if (!out_scene) return fail(PYR_ERR_INVALID_ARGUMENT, "null out pointer");
     *out_scene = nullptr;
+    uint32_t builder = PYR_BUILD_HOST;
+    if (build) { // checked before the description and before any device is looked for
+        if (build->builder != PYR_BUILD_HOST && build->builder != PYR_BUILD_DEVICE) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrBuildParams.builder is neither PYR_BUILD_HOST nor PYR_BUILD_DEVICE");
+        for (uint32_t word : build->reserved)
+            if (word != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrBuildParams.reserved must be zero");
+        builder = build->builder;
+    }
     int rc = validate(desc);
     if (rc != PYR_OK) return rc;
     // programs that declare more registers than the interpreter's in-register file get theirs renumbered (program_regs.h) before
@@ -1048,7 +1098,7 @@ int pyr_scene_create(const PyrSceneDesc* desc, int device, PyrScene** out_scene)
     s->device = device;
     s->num_cus = prop.multiProcessorCount;
     s->program_info = info;
-    rc = pack_and_upload(&allocated, s.get());
+    rc = pack_and_upload(&allocated, s.get(), builder);
     if (rc != PYR_OK) return rc;
     *out_scene = s.release();
     return PYR_OK;
@@ -1330,6 +1380,16 @@ int pyr_scene_path_info(PyrScene* scene, const PyrRenderParams* params, PyrPathI
 int pyr_scene_program_info(PyrScene* scene, PyrProgramInfo* out) {
     if (!scene || !out) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
     *out = scene->program_info;
+    return PYR_OK;
+}
+
+int pyr_scene_build_info(PyrScene* scene, PyrBuildInfo* out) {
+    if (!scene || !out) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+    if (scene->digest_source) { // first call: hash the tree, then let it go
+        scene->build_info.tree_digest = pyr::tree_digest(*scene->digest_source);
+        scene->digest_source.reset();
+    }
+    *out = scene->build_info;
     return PYR_OK;
 }
 

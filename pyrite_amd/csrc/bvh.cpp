@@ -1,5 +1,6 @@
 // bvh.cpp -- binned-SAH builder for the 64-byte two-child node layout (see bvh.h).
 #include "bvh.h"
+#include "bvh_level.h"
 
 #include <algorithm>
 #include <array>
@@ -54,8 +55,9 @@ inline uint32_t ceil_log2(uint32_t n) {
 
 } // namespace
 
-BuiltBvh build_bvh(const std::vector<PrimBounds>& prims, bool leaves_tested_in_pairs) {
+BuiltBvh build_bvh(const std::vector<PrimBounds>& prims, bool leaves_tested_in_pairs, uint32_t* median_splits) {
     BuiltBvh out;
+    if (median_splits) *median_splits = 0;
     const uint32_t n = (uint32_t)prims.size();
     std::vector<Ref> refs(n);
     for (uint32_t i = 0; i < n; ++i) {
@@ -194,6 +196,7 @@ BuiltBvh build_bvh(const std::vector<PrimBounds>& prims, bool leaves_tested_in_p
             }
         }
         mid = begin + count / 2;
+        if (median_splits) ++*median_splits;
         std::nth_element(refs.begin() + begin, refs.begin() + mid, refs.begin() + end, [a](const Ref& x, const Ref& y) { return x.c[a] < y.c[a]; });
         return true;
     };
@@ -760,6 +763,243 @@ WideBvh collapse_to_wide_sah(const BuiltBvh& bvh) {
         out.nodes[t.wide_index] = node;
     }
     return out;
+}
+
+// ------------------------------------------------------------------------------------------------ level-wise build
+static_assert(lvl::kBins == kBins && lvl::kLeafMax == kMaxLeafPrims && lvl::kDepthMax == kMaxBvhDepth && lvl::kNodeCost == kSahNodeCost,
+              "bvh_level.h restates bvh.h's constants");
+
+float bvh_padding(const std::vector<PrimBounds>& prims) {
+    float max_abs = 0.0f;
+    for (const PrimBounds& p : prims)
+        for (int a = 0; a < 3; ++a) max_abs = std::max(max_abs, std::max(std::fabs(p.lo[a]), std::fabs(p.hi[a])));
+    return 16.0f * 1.1920929e-7f * max_abs;
+}
+
+namespace {
+
+Node64 empty_node64() {
+    Node64 nd{};
+    for (int c = 0; c < 2; ++c) {
+        nd.lo_x[c] = nd.lo_y[c] = nd.lo_z[c] = kInf;
+        nd.hi_x[c] = nd.hi_y[c] = nd.hi_z[c] = -kInf;
+        nd.child[c] = encode_leaf(0, 0);
+    }
+    return nd;
+}
+
+void set_child64(Node64& p, int slot, int32_t code, const lvl::Box3& box, float pad) {
+    p.child[slot] = code;
+    p.lo_x[slot] = box.lo[0] - pad, p.lo_y[slot] = box.lo[1] - pad, p.lo_z[slot] = box.lo[2] - pad;
+    p.hi_x[slot] = box.hi[0] + pad, p.hi_y[slot] = box.hi[1] + pad, p.hi_z[slot] = box.hi[2] + pad;
+}
+
+void grow_keys(uint32_t* box, uint32_t* cbox, const PrimBounds& r) {
+    for (int a = 0; a < 3; ++a) {
+        box[a] = std::min(box[a], lvl::key_of(r.lo[a]));
+        box[3 + a] = std::max(box[3 + a], lvl::key_of(r.hi[a]));
+        const uint32_t c = lvl::key_of(lvl::centroid(r.lo[a], r.hi[a]));
+        cbox[a] = std::min(cbox[a], c);
+        cbox[3 + a] = std::max(cbox[3 + a], c);
+    }
+}
+
+} // namespace
+
+BuiltBvh single_leaf_bvh(const std::vector<PrimBounds>& prims) {
+    BuiltBvh out;
+    out.nodes.push_back(empty_node64());
+    if (prims.empty()) return out;
+    lvl::Box3 box = lvl::empty_box();
+    for (const PrimBounds& p : prims) {
+        lvl::grow(box, p.lo, p.hi);
+        out.prim_order.push_back(p.shape);
+    }
+    std::sort(out.prim_order.begin(), out.prim_order.end());
+    set_child64(out.nodes[0], 0, encode_leaf(0, (uint32_t)prims.size()), box, bvh_padding(prims));
+    out.num_leaves = 1;
+    out.max_depth = 1;
+    return out;
+}
+
+bool finish_levelwise(const std::vector<lvl::Task>& tasks, const std::vector<uint32_t>& leaf_shapes, float pad, BuiltBvh& out, LevelBuildStats* stats) {
+    out = BuiltBvh{};
+    out.nodes.push_back(empty_node64());
+    const size_t nt = tasks.size();
+    if (nt == 0 || tasks[0].kind < lvl::KIND_SPLIT || (size_t)tasks[0].child0 + 1 >= nt) return false;
+    out.nodes.reserve(nt / 2 + 1); // every inner task is a node, every other one a leaf
+    out.prim_order.reserve(leaf_shapes.size());
+    uint32_t medians = 0;
+    struct Item {
+        uint32_t task;
+        int32_t node;
+    };
+    std::vector<Item> stack{{tasks[0].child0 + 1, 0}, {tasks[0].child0, 0}};
+    medians += tasks[0].kind == lvl::KIND_MEDIAN;
+    size_t visited = 1;
+    while (!stack.empty()) {
+        const Item it = stack.back();
+        stack.pop_back();
+        const lvl::Task& t = tasks[it.task];
+        if (++visited > nt || t.slot > 1) return false; // (a cycle would visit more tasks than there are)
+        const lvl::Box3 box = lvl::box_of_keys(t.box);
+        if (t.kind == lvl::KIND_LEAF) {
+            if (t.end < t.begin || t.end > leaf_shapes.size() || t.end - t.begin > kMaxLeafPrims) return false;
+            const uint32_t first = (uint32_t)out.prim_order.size();
+            out.prim_order.insert(out.prim_order.end(), leaf_shapes.begin() + t.begin, leaf_shapes.begin() + t.end);
+            std::sort(out.prim_order.begin() + first, out.prim_order.end());
+            set_child64(out.nodes[it.node], (int)t.slot, encode_leaf(first, t.end - t.begin), box, pad);
+            out.num_leaves++;
+            out.max_depth = std::max(out.max_depth, t.depth);
+        } else if (t.kind == lvl::KIND_SPLIT || t.kind == lvl::KIND_MEDIAN) {
+            if ((size_t)t.child0 + 1 >= nt || t.child0 <= it.task) return false;
+            medians += t.kind == lvl::KIND_MEDIAN;
+            const int32_t id = (int32_t)out.nodes.size();
+            out.nodes.push_back(empty_node64());
+            set_child64(out.nodes[it.node], (int)t.slot, id, box, pad);
+            stack.push_back(Item{t.child0 + 1, id});
+            stack.push_back(Item{t.child0, id});
+        } else {
+            return false;
+        }
+    }
+    if (out.prim_order.size() != leaf_shapes.size()) return false;
+    if (stats) stats->median_splits = medians;
+    return true;
+}
+
+BuiltBvh build_bvh_levelwise(const std::vector<PrimBounds>& prims, bool leaves_tested_in_pairs, uint32_t depth_bound, LevelBuildStats* stats) {
+    const uint32_t n = (uint32_t)prims.size();
+    if (stats) *stats = LevelBuildStats{};
+    if (n <= kMaxLeafPrims) return single_leaf_bvh(prims);
+    const bool in_pairs = PYR_SAH_PAIRS && leaves_tested_in_pairs;
+    std::vector<PrimBounds> cur = prims, next(n);
+    std::vector<uint32_t> leaf_shapes(n, 0);
+    std::vector<lvl::Task> tasks(1);
+    std::memset(&tasks[0], 0, sizeof(lvl::Task));
+    tasks[0].end = n, tasks[0].parent = -1;
+    lvl::empty_keys(tasks[0].box), lvl::empty_keys(tasks[0].cbox);
+    for (const PrimBounds& r : cur) grow_keys(tasks[0].box, tasks[0].cbox, r);
+
+    struct Bins {
+        lvl::Box3 b[3][kBins];
+        uint32_t c[3][kBins];
+        const lvl::Box3& box(int a, int k) const { return b[a][k]; }
+        uint32_t count(int a, int k) const { return c[a][k]; }
+    };
+    std::vector<uint32_t> level{0}, following;
+    uint32_t levels = 0;
+    while (!level.empty()) {
+        ++levels;
+        following.clear();
+        for (const uint32_t ti : level) {
+            lvl::Task t = tasks[ti];
+            const uint32_t count = t.end - t.begin;
+            const lvl::Box3 box = lvl::box_of_keys(t.box), cbox = lvl::box_of_keys(t.cbox);
+            // bin phase
+            Bins bins;
+            for (int a = 0; a < 3; ++a) {
+                for (int k = 0; k < kBins; ++k) bins.b[a][k] = lvl::empty_box(), bins.c[a][k] = 0;
+                const float extent = cbox.hi[a] - cbox.lo[a];
+                if (!(extent > 0.0f)) continue;
+                const float scale = lvl::bin_scale(extent);
+                for (uint32_t i = t.begin; i < t.end; ++i) {
+                    const int k = lvl::bin_index(lvl::centroid(cur[i].lo[a], cur[i].hi[a]), cbox.lo[a], scale);
+                    lvl::grow(bins.b[a][k], cur[i].lo, cur[i].hi);
+                    bins.c[a][k]++;
+                }
+            }
+            // choose phase
+            const lvl::Decision d = lvl::choose_split(count, t.depth, box, cbox, bins, in_pairs, depth_bound);
+            t.kind = d.kind, t.axis = d.axis, t.bin = d.bin, t.lo = d.lo, t.scale = d.scale;
+            if (d.kind == lvl::KIND_LEAF) {
+                for (uint32_t i = t.begin; i < t.end; ++i) leaf_shapes[i] = cur[i].shape;
+                tasks[ti] = t;
+                continue;
+            }
+            // partition phase
+            t.child0 = (uint32_t)tasks.size();
+            tasks[ti] = t;
+            lvl::Task kids[2];
+            for (uint32_t s = 0; s < 2; ++s) {
+                std::memset(&kids[s], 0, sizeof(lvl::Task));
+                kids[s].begin = s == 0 ? t.begin : t.begin + d.left_count;
+                kids[s].end = s == 0 ? t.begin + d.left_count : t.end;
+                kids[s].parent = (int32_t)ti, kids[s].slot = s, kids[s].depth = t.depth + 1;
+                lvl::empty_keys(kids[s].box), lvl::empty_keys(kids[s].cbox);
+            }
+            uint32_t cursor[2] = {kids[0].begin, kids[1].begin};
+            for (uint32_t i = t.begin; i < t.end; ++i) {
+                const PrimBounds& r = cur[i];
+                const float c = lvl::centroid(r.lo[d.axis], r.hi[d.axis]);
+                uint32_t side;
+                if (d.kind == lvl::KIND_SPLIT) {
+                    side = lvl::bin_index(c, d.lo, d.scale) <= d.bin ? 0u : 1u;
+                } else {
+                    uint32_t rank = 0;
+                    for (uint32_t j = t.begin; j < t.end; ++j)
+                        rank += lvl::median_before(lvl::centroid(cur[j].lo[d.axis], cur[j].hi[d.axis]), cur[j].shape, c, r.shape) ? 1u : 0u;
+                    side = rank < d.left_count ? 0u : 1u;
+                }
+                next[cursor[side]++] = r;
+                grow_keys(kids[side].box, kids[side].cbox, r);
+            }
+            tasks.push_back(kids[0]);
+            tasks.push_back(kids[1]);
+            following.push_back(t.child0), following.push_back(t.child0 + 1);
+        }
+        cur.swap(next);
+        level.swap(following);
+    }
+    BuiltBvh out;
+    LevelBuildStats st;
+    if (!finish_levelwise(tasks, leaf_shapes, bvh_padding(prims), out, &st)) return BuiltBvh{};
+    st.levels = levels;
+    if (stats) *stats = st;
+    return out;
+}
+
+uint64_t tree_digest(const BuiltBvh& bvh) {
+    uint64_t h = 1469598103934665603ull;
+    auto mix = [&h](const void* p, size_t bytes) { // FNV-1a over 32-bit words (every item hashed is a whole number of them)
+        uint32_t w;
+        for (size_t i = 0; i < bytes; i += 4) {
+            std::memcpy(&w, (const unsigned char*)p + i, 4);
+            h = (h ^ w) * 1099511628211ull;
+        }
+    };
+    struct Item {
+        int32_t node;
+        uint32_t slot, depth;
+    };
+    if (bvh.nodes.empty()) return h;
+    std::vector<Item> stack{{0, 1, 1}, {0, 0, 1}};
+    while (!stack.empty()) {
+        const Item it = stack.back();
+        stack.pop_back();
+        const Node64& n = bvh.nodes[it.node];
+        const uint32_t k = it.slot;
+        float box[6] = {n.lo_x[k], n.lo_y[k], n.lo_z[k], n.hi_x[k], n.hi_y[k], n.hi_z[k]};
+        for (float& f : box)
+            if (f == 0.0f) f = 0.0f; // -0.0f reads as +0.0f
+        mix(box, sizeof(box));
+        mix(&it.depth, 4), mix(&it.slot, 4);
+        const int32_t code = n.child[k];
+        if (code >= 0) {
+            const uint32_t inner = 0xFFFFFFFFu;
+            mix(&inner, 4);
+            stack.push_back(Item{code, 1, it.depth + 1});
+            stack.push_back(Item{code, 0, it.depth + 1});
+        } else {
+            const uint32_t first = (uint32_t)(-1 - code) >> 3, count = (uint32_t)(-1 - code) & 7u;
+            uint32_t shapes[8] = {0};
+            for (uint32_t j = 0; j < count; ++j) shapes[j] = bvh.prim_order[first + j];
+            std::sort(shapes, shapes + count);
+            mix(&count, 4);
+            mix(shapes, 4 * count);
+        }
+    }
+    return h;
 }
 
 } // namespace pyr

@@ -60,7 +60,35 @@ inline int32_t encode_leaf(uint32_t first, uint32_t count) { return -1 - (int32_
 // `leaves_tested_in_pairs`: the tree's leaves will be tested two triangles per step (the four-child pair tree of a
 // triangle-only scene that does not live in LDS), so the SAH counts a leaf of n primitives as n rounded up to even -- only
 // when PYR_SAH_PAIRS is on; everything else (sphere scenes, LDS-resident scenes, the binary walk) counts singly.
-BuiltBvh build_bvh(const std::vector<PrimBounds>& prims, bool leaves_tested_in_pairs = false);
+// `median_splits`, if given, receives how many nodes were split by the median fallback (coincident centroids, or the depth rule).
+BuiltBvh build_bvh(const std::vector<PrimBounds>& prims, bool leaves_tested_in_pairs = false, uint32_t* median_splits = nullptr);
+
+// The same tree built level by level: the sequential rehearsal of the device builder (kernels/build.hip),
+// calling the per-reference and per-node functions of bvh_level.h it calls. Where no node needs the median fallback the tree is
+// build_bvh's (tree_digest below is equal); where one does, the count / 2 references smallest by (centroid, shape code) go to
+// slot 0, which may break ties differently from build_bvh's nth_element. `depth_bound` stands in for kMaxBvhDepth in the depth
+// rule (tests lower it to reach the forced median on small inputs).
+struct LevelBuildStats {
+    uint32_t levels = 0;        // iterations of the level loop
+    uint32_t median_splits = 0; // nodes split by the median rule
+};
+BuiltBvh build_bvh_levelwise(const std::vector<PrimBounds>& prims, bool leaves_tested_in_pairs = false, uint32_t depth_bound = kMaxBvhDepth,
+                             LevelBuildStats* stats = nullptr);
+namespace lvl {
+struct Task;
+}
+// The padding build_bvh gives every stored box: 16 ulps of the largest coordinate.
+float bvh_padding(const std::vector<PrimBounds>& prims);
+// A scene of at most kMaxLeafPrims primitives: one leaf under the root, as build_bvh makes it (shape codes ascending).
+BuiltBvh single_leaf_bvh(const std::vector<PrimBounds>& prims);
+// The tasks of a level-wise build (host rehearsal or device) -> build_bvh's layout: nodes numbered in pre-order, slot 0 first;
+// prim_order in the same leaf order, each leaf's shape codes ascending (`leaf_shapes[i]`: the shape code at reference position
+// i of the leaf that covers it). False when the tasks do not describe a tree over `leaf_shapes` (nothing is trusted blindly:
+// the device builder's output passes through here).
+bool finish_levelwise(const std::vector<lvl::Task>& tasks, const std::vector<uint32_t>& leaf_shapes, float pad, BuiltBvh& out, LevelBuildStats* stats);
+// Pre-order walk of the binary tree: every child's stored box (-0.0f read as +0.0f), depth and slot, and a leaf's shape codes
+// sorted. Node numbers and the order inside a leaf do not enter, so equal digests mean the same tree.
+uint64_t tree_digest(const BuiltBvh& bvh);
 
 // Spatial splits (SBVH, Stich et al. 2009) for a triangle-only pair tree: at every node where the best object split's two
 // children overlap by more than `alpha` x the root's area, a binned split of space (kSpatialBins planes per axis) competes

@@ -1,0 +1,204 @@
+// bvh_level.h -- build_bvh's rules (bvh.cpp) as functions of one reference or one node, for builders that work level by level:
+// the device builder (kernels/build.hip) and its sequential rehearsal on the host (build_bvh_levelwise, bvh.cpp) call the same
+// functions, so what the two decide can differ only in what is not in here -- atomics and scans.
+//
+// Every quantity a node accumulates is a min, a max or a count, so a node's bins and its children's boxes do not depend on the
+// order its references arrive in, and the split is a pure function of the bins (choose_split). Each expression below restates
+// the one in build_bvh; units that include this header are built with -ffp-contract=off and IEEE division.
+#pragma once
+#include <cstdint>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+#define PYR_HD __host__ __device__ __forceinline__
+#else
+#define PYR_HD inline
+#endif
+
+namespace pyr {
+namespace lvl {
+
+constexpr int kBins = 16; // PYR_SAH_BINS of bvh.cpp
+constexpr uint32_t kLeafMax = 4;  // kMaxLeafPrims (bvh.h; checked there)
+constexpr uint32_t kDepthMax = 40; // kMaxBvhDepth
+constexpr float kNodeCost = 1.0f; // kSahNodeCost
+
+PYR_HD float pos_inf() { return __builtin_inff(); }
+
+struct Box3 {
+    float lo[3], hi[3];
+};
+PYR_HD Box3 empty_box() {
+    Box3 b;
+    for (int a = 0; a < 3; ++a) b.lo[a] = pos_inf(), b.hi[a] = -pos_inf();
+    return b;
+}
+// std::min / std::max of Box::grow: the second argument wins only when it is strictly smaller (larger)
+PYR_HD void grow(Box3& b, const float* l, const float* h) {
+    for (int a = 0; a < 3; ++a) {
+        b.lo[a] = l[a] < b.lo[a] ? l[a] : b.lo[a];
+        b.hi[a] = b.hi[a] < h[a] ? h[a] : b.hi[a];
+    }
+}
+PYR_HD float half_area(const Box3& b) {
+    float dx = b.hi[0] - b.lo[0], dy = b.hi[1] - b.lo[1], dz = b.hi[2] - b.lo[2];
+    if (dx < 0 || dy < 0 || dz < 0) return 0.0f;
+    return dx * dy + dx * dz + dy * dz;
+}
+
+// Floats as unsigned keys of the same order (-inf lowest, -0 just below +0), so that integer atomicMin / atomicMax accumulate
+// float bounds. No NaN reaches a builder (pyr_scene_create refuses coordinates that are not finite).
+PYR_HD uint32_t float_bits(float f) {
+    union {
+        float f;
+        uint32_t u;
+    } v;
+    v.f = f;
+    return v.u;
+}
+PYR_HD float bits_float(uint32_t u) {
+    union {
+        float f;
+        uint32_t u;
+    } v;
+    v.u = u;
+    return v.f;
+}
+PYR_HD uint32_t key_of(float f) {
+    const uint32_t u = float_bits(f);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+PYR_HD float float_of(uint32_t k) { return bits_float((k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k); }
+constexpr uint32_t kKeyPosInf = 0xFF800000u; // key_of(+inf): an empty lower bound
+constexpr uint32_t kKeyNegInf = 0x007FFFFFu; // key_of(-inf): an empty upper bound
+
+PYR_HD float centroid(float lo, float hi) { return 0.5f * lo + 0.5f * hi; }
+
+// (int)x as the host builder's compiler converts it (x86 cvttss2si: what does not fit an int becomes INT_MIN), spelled out so
+// that the device agrees where a degenerate extent makes `scale` infinite
+PYR_HD int to_int(float x) { return (x >= -2147483648.0f && x < 2147483648.0f) ? (int)x : (-2147483647 - 1); }
+PYR_HD float bin_scale(float extent) { return (float)kBins / extent; }
+PYR_HD int bin_index(float c, float cbox_lo, float scale) {
+    const int b = to_int((c - cbox_lo) * scale);
+    const int clamped = b > 0 ? b : 0;
+    return clamped < kBins - 1 ? clamped : kBins - 1;
+}
+
+PYR_HD uint32_t ceil_log2(uint32_t n) {
+    uint32_t l = 0;
+    while ((1u << l) < n) ++l;
+    return l;
+}
+PYR_HD float leaf_tests(uint32_t count, bool in_pairs) { return in_pairs ? (float)((count + 1u) & ~1u) : (float)count; }
+PYR_HD bool force_median(uint32_t count, uint32_t depth, uint32_t depth_bound) {
+    return depth + ceil_log2((count + kLeafMax - 1) / kLeafMax) + 1 >= depth_bound;
+}
+
+enum : uint32_t { KIND_PENDING = 0, KIND_LEAF = 1, KIND_SPLIT = 2, KIND_MEDIAN = 3 };
+
+struct Decision {
+    uint32_t kind; // KIND_LEAF, KIND_SPLIT (bins <= `bin` on `axis` go to slot 0), KIND_MEDIAN (count / 2 smallest on `axis`)
+    int axis, bin;
+    float lo, scale;     // KIND_SPLIT: bin_index(c, lo, scale)
+    uint32_t left_count; // references of slot 0
+};
+
+// build_bvh's `split` for one node, from its bins. `bins.box(axis, bin)` / `bins.count(axis, bin)` are read only for axes whose
+// centroid extent is positive, and not at all when the depth rule forces the median. The candidates of a SAH split have
+// references on both sides by the same bin_index the partition uses, so a chosen split never leaves a side empty.
+template <class Bins>
+PYR_HD Decision choose_split(uint32_t count, uint32_t depth, const Box3& box, const Box3& cbox, const Bins& bins, bool in_pairs, uint32_t depth_bound) {
+    Decision d;
+    d.kind = KIND_LEAF, d.axis = 0, d.bin = -1, d.lo = 0.0f, d.scale = 0.0f, d.left_count = 0;
+    if (count <= 1) return d;
+    float best_cost = pos_inf();
+    int best_axis = -1, best_bin = -1;
+    uint32_t best_left = 0;
+    if (!force_median(count, depth, depth_bound)) {
+        for (int a = 0; a < 3; ++a) {
+            float extent = cbox.hi[a] - cbox.lo[a];
+            if (!(extent > 0.0f)) continue;
+            float right_area[kBins];
+            uint32_t right_count[kBins];
+            Box3 acc = empty_box();
+            uint32_t cnt = 0;
+            for (int b = kBins - 1; b > 0; --b) {
+                const Box3 bb = bins.box(a, b);
+                grow(acc, bb.lo, bb.hi);
+                cnt += bins.count(a, b);
+                right_area[b] = half_area(acc);
+                right_count[b] = cnt;
+            }
+            Box3 left = empty_box();
+            uint32_t lcnt = 0;
+            for (int b = 0; b < kBins - 1; ++b) {
+                const Box3 bb = bins.box(a, b);
+                grow(left, bb.lo, bb.hi);
+                lcnt += bins.count(a, b);
+                if (lcnt == 0 || right_count[b + 1] == 0) continue;
+                float cost = half_area(left) * leaf_tests(lcnt, in_pairs) + right_area[b + 1] * leaf_tests(right_count[b + 1], in_pairs);
+                if (cost < best_cost) {
+                    best_cost = cost;
+                    best_axis = a;
+                    best_bin = b;
+                    best_left = lcnt;
+                }
+            }
+        }
+    }
+    if (best_axis >= 0) {
+        float parent_area = half_area(box);
+        float split_cost = kNodeCost + (parent_area > 0.0f ? best_cost / parent_area : pos_inf());
+        if (count <= kLeafMax && leaf_tests(count, in_pairs) <= split_cost) return d;
+        float extent = cbox.hi[best_axis] - cbox.lo[best_axis];
+        d.kind = KIND_SPLIT, d.axis = best_axis, d.bin = best_bin;
+        d.lo = cbox.lo[best_axis], d.scale = bin_scale(extent), d.left_count = best_left;
+        return d;
+    }
+    if (count <= kLeafMax) return d;
+    // median split on the widest centroid axis (coincident centroids, or depth budget exhausted)
+    int a = 0;
+    float w = -1.0f;
+    for (int k = 0; k < 3; ++k) {
+        float e = cbox.hi[k] - cbox.lo[k];
+        if (e > w) {
+            w = e;
+            a = k;
+        }
+    }
+    d.kind = KIND_MEDIAN, d.axis = a, d.left_count = count / 2;
+    return d;
+}
+
+// The median rule's order: by centroid on the axis, then by shape code. Shape codes are distinct within a tree without spatial
+// splits, so this is a strict total order and the count / 2 smallest are the same set whatever order the references are held in.
+PYR_HD bool median_before(float c, uint32_t shape, float other_c, uint32_t other_shape) { return c < other_c || (c == other_c && shape < other_shape); }
+
+// One node of a level-wise build, in the order the builders made them (task 0 is the root's range; its children are the two
+// slots of node 0). What the finishing pass (finish_levelwise, bvh.cpp) turns into a BuiltBvh.
+struct Task {
+    uint32_t begin, end;  // references [begin, end) of the level's reference array
+    int32_t parent;       // task whose node holds this one as a child, -1 for the root's range
+    uint32_t slot;        // which child of it
+    uint32_t depth;       // edges from the root node
+    uint32_t kind;        // KIND_*
+    uint32_t child0;      // KIND_SPLIT / KIND_MEDIAN: the task of slot 0; slot 1 is child0 + 1
+    int32_t axis, bin;    // the decision, for the partition
+    float lo, scale;
+    uint32_t cursor[2];   // device: references placed so far on each side
+    uint32_t box[6];      // lo xyz, hi xyz as keys (key_of)
+    uint32_t cbox[6];     // centroid bounds, likewise
+};
+static_assert(sizeof(Task) == 100, "Task is shared with the device as 25 words");
+
+PYR_HD Box3 box_of_keys(const uint32_t* k) {
+    Box3 b;
+    for (int a = 0; a < 3; ++a) b.lo[a] = float_of(k[a]), b.hi[a] = float_of(k[3 + a]);
+    return b;
+}
+PYR_HD void empty_keys(uint32_t* k) {
+    for (int a = 0; a < 3; ++a) k[a] = kKeyPosInf, k[3 + a] = kKeyNegInf;
+}
+
+} // namespace lvl
+} // namespace pyr

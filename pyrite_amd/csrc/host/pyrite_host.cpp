@@ -1046,13 +1046,24 @@ std::unique_ptr<World> World::from_project(const WorldProject& world, const std:
 World::~World() {
     for (auto& kv : scenes_) pyr_scene_destroy(kv.second);
 }
-PyrScene* World::scene(int device, int copy) {
+PyrScene* World::scene(int device, int copy, std::optional<Build> build) {
     auto it = scenes_.find({device, copy});
-    if (it != scenes_.end()) return it->second;
+    if (it != scenes_.end()) {
+        if (build && *build != builders_[{device, copy}]) throw ProjectError("the scene on this device was created with the other BVH builder");
+        return it->second;
+    }
     PyrScene* handle = nullptr;
-    check_status(pyr_scene_create(&flat_.desc(), device, &handle));
+    PyrBuildParams params{};
+    params.builder = build && *build == Build::Device ? PYR_BUILD_DEVICE : PYR_BUILD_HOST;
+    check_status(pyr_scene_create_with(&flat_.desc(), device, build ? &params : nullptr, &handle));
     scenes_[{device, copy}] = handle;
+    builders_[{device, copy}] = build.value_or(Build::Host);
     return handle;
+}
+PyrBuildInfo World::build_info(int device, int copy) {
+    PyrBuildInfo info{};
+    check_status(pyr_scene_build_info(scene(device, copy), &info));
+    return info;
 }
 
 std::vector<PyrHit> World::intersect(const std::vector<float>& rays, int device, PyrCounters* counters) {

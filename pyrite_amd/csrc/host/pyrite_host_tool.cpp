@@ -5,7 +5,7 @@
 //   pyrite_host_tool dump-project   <project.lua> <texel dir | -> <out.bin>    the same for a project file (lua_project.cpp)
 //   pyrite_host_tool render-project <project.lua> <texel dir | -> <seed> <out.png> [film.bin]   what `pyrite project.lua` does (main.rs:46-330)
 //                                   [--size WxH] [--spp N] [--features PREFIX] [--features-grid N] [--hdr PATH] [--exposure EV|auto] [--tone clip|reinhard]
-//                                   and the progressive flags of python -m pyrite_amd
+//                                   [--build host|device] and the progressive flags of python -m pyrite_amd
 //   pyrite_host_tool encode-features <records.bin> <normal.rgb> <depth.rgb>    PyrFeaturePixel[n] -> the 8-bit normal and depth images, raw RGB (no GPU)
 //   pyrite_host_tool intersect <scene> <data_dir> <rays.f32> <hits.bin>       World::intersect for a ray batch ([n][6] f32 -> PyrHit[n])
 //   pyrite_host_tool render <scene> <data_dir> <w> <h> <spp> <seed> <film.bin> [out.png]
@@ -241,7 +241,7 @@ int main(int argc, char** argv) {
             write_dump(argv[4], flat, loaded.project);
             return 0;
         }
-        if (argc >= 6 && std::string(argv[1]) == "render-project") { // render-project <project.lua> <texel dir | -> <seed> <out.png> [film.bin] [--pass-samples N] [--preview PATH] [--preview-every SECONDS] [--noise] [--denoise] [--denoise-radius N]
+        if (argc >= 6 && std::string(argv[1]) == "render-project") { // render-project <project.lua> <texel dir | -> <seed> <out.png> [film.bin] [--pass-samples N] [--preview PATH] [--preview-every SECONDS] [--noise] [--denoise] [--denoise-radius N] [--build host|device]
             // the flags of python -m pyrite_amd: a progressive session with previews (main.rs:261-299) instead of one blocking call
             std::optional<long> pass_samples;
             std::string preview_path, film_path;
@@ -252,6 +252,7 @@ int main(int argc, char** argv) {
             std::optional<std::string> hdr, exposure, tone_name;
             bool denoise_flag = false;
             std::optional<long> denoise_radius;
+            std::optional<std::string> build_name; // --build host|device: who builds the BVH; given, the stage times go to stderr
             for (int i = 6; i < argc; ++i) {
                 const std::string a = argv[i];
                 auto value = [&]() -> const char* {
@@ -280,6 +281,8 @@ int main(int argc, char** argv) {
                     denoise_flag = true;
                 else if (a == "--denoise-radius")
                     denoise_radius = std::strtol(value(), nullptr, 10);
+                else if (a == "--build")
+                    build_name = value();
                 else if (a == "--size")
                     size = value();
                 else if (a == "--spp")
@@ -293,6 +296,7 @@ int main(int argc, char** argv) {
             if (problem.empty()) problem = features_flag_problem(!features_prefix.empty(), features_grid);
             if (problem.empty()) problem = tone_flag_problem(hdr, exposure, tone_name);
             if (problem.empty()) problem = denoise_flag_problem(denoise_flag, denoise_radius);
+            if (problem.empty() && build_name && *build_name != "host" && *build_name != "device") problem = "--build takes host or device";
             if (!problem.empty()) {
                 std::fprintf(stderr, "error: %s\n", problem.c_str());
                 return 2;
@@ -317,6 +321,13 @@ int main(int argc, char** argv) {
             r.seed = std::strtoull(argv[4], nullptr, 10);
             Film film = r.new_film(project.image.width, project.image.height);
             std::printf("The scene contains %zu objects.\n", world->num_objects()); // world.rs:251-254
+            if (build_name) {
+                world->scene(0, 0, *build_name == "device" ? World::Build::Device : World::Build::Host);
+                const PyrBuildInfo b = world->build_info(0);
+                std::fprintf(stderr, "build: asked %s, used %s (fallback %u), %u levels, %u median splits, digest %016llx; bounds %.2f tree %.2f finish %.2f collapse %.2f pack+upload %.2f total %.2f ms\n",
+                             build_name->c_str(), b.builder_used == PYR_BUILD_DEVICE ? "device" : "host", b.fallback_reason, b.levels, b.median_splits, (unsigned long long)b.tree_digest,
+                             b.bounds_ms, b.tree_ms, b.finish_ms, b.collapse_ms, b.pack_upload_ms, b.total_ms);
+            }
             std::vector<float> linear;
             if (pass_samples || !preview_path.empty() || noise || denoise_flag) {
                 const uint32_t per_pass = pass_samples ? (uint32_t)*pass_samples : denoise_flag ? r.pixel_samples / 2u : kDefaultPassSamples;

@@ -24,6 +24,7 @@ class World:
         self.flat = flat
         self._desc = flat.desc()
         self._scenes = {}
+        self._builders = {}
 
     @classmethod
     def from_project(cls, world, base_dir="."):
@@ -33,14 +34,35 @@ class World:
     def desc(self):
         return self._desc
 
-    def scene(self, device=0, slot=0):
-        """The PyrScene on `device` (`slot` > 0: a further copy on the same device, for the one-GPU multi-rank test rig)."""
+    BUILDERS = {"host": abi.PYR_BUILD_HOST, "device": abi.PYR_BUILD_DEVICE}
+
+    def scene(self, device=0, slot=0, build=None):
+        """The PyrScene on `device` (`slot` > 0: a further copy on the same device, for the one-GPU multi-rank test rig).
+        `build`: who builds the acceleration structure when the scene is created here, "host" (one CPU thread; the default) or
+        "device" (pyr_scene_create_with: the same rules on the GPU and, where no node needs the median fallback, the same tree).
+        A scene that exists already is returned as it was built; asking for another builder then is an error."""
+        if build is not None and build not in self.BUILDERS:
+            raise ValueError("build must be 'host' or 'device', not %r" % (build,))
         key = device if slot == 0 else (device, slot)
         if key not in self._scenes:
             handle = C.c_void_p()
-            check(lib().pyr_scene_create(C.byref(self._desc), int(device), C.byref(handle)))
+            if build is None:
+                check(lib().pyr_scene_create(C.byref(self._desc), int(device), C.byref(handle)))
+            else:
+                params = abi.PyrBuildParams(builder=self.BUILDERS[build])
+                check(lib().pyr_scene_create_with(C.byref(self._desc), int(device), C.byref(params), C.byref(handle)))
             self._scenes[key] = handle
+            self._builders[key] = build or "host"
+        elif build is not None and build != self._builders[key]:
+            raise ValueError("the scene on device %r was created with build=%r" % (device, self._builders[key]))
         return self._scenes[key]
+
+    def build_info(self, device=0, slot=0):
+        """pyr_scene_build_info as a dict: the builder asked for and used, why they differ, levels, median splits, the tree's
+        digest and the stage times of scene creation in milliseconds."""
+        info = abi.PyrBuildInfo()
+        check(lib().pyr_scene_build_info(self.scene(device, slot), C.byref(info)))
+        return {name: getattr(info, name) for name, _ in info._fields_ if name != "reserved"}
 
     def bvh_info(self, device=0):
         info = abi.PyrBvhInfo()
@@ -61,6 +83,7 @@ class World:
         for handle in self._scenes.values():
             lib().pyr_scene_destroy(handle)
         self._scenes = {}
+        self._builders = {}
 
     def __del__(self):
         try:

@@ -9,7 +9,12 @@
 //                                          against brute force (tests/test_bvh_build.py)
 //   bvh_quality hash TRIS                  hashes of the tree PYRITE_SPATIAL_SPLITS / PYRITE_WIDE_COLLAPSE select and of the
 //                                          old, the cost-collapsed and the spatial-split trees
+//   bvh_quality level PRIMS RAYS|- [DEPTH_BOUND]
+//                                          the level-wise builder (build_bvh_levelwise, the device builder's rehearsal) next to
+//                                          the recursive one: both trees' digests and median splits, then the invariants of the
+//                                          level-wise tree and its walk against brute force (tests/test_bvh_device_cpu.py)
 //
+// PRIMS: uint32 count, then count x 10 float32: kind (0 sphere: centre, radius; 1 triangle: three vertices), nine values.
 // TRIS: uint32 count, then count x 9 float32 (three vertices). RAYS: uint32 count, then count x 8 float32: origin, direction,
 // limit (the shadow ray's squared blocking distance, or -1 for a closest-hit ray), unused. tools/bvh_quality.py writes both.
 #include "../pyrite_amd/csrc/bvh.h"
@@ -130,7 +135,8 @@ struct Hit {
 };
 
 // One ray through the wide tree, as the kernels walk it (trav_step_wide, the pair steps of trav_step_lean).
-Hit walk(const Trees& t, const std::vector<Tri>& tris, const Ray& r, Counts& cnt) {
+template <class HitShape> // hit(shape code, ray, distance)
+Hit walk(const Trees& t, const HitShape& hit_shape, const Ray& r, Counts& cnt) {
     const bool shadow = r.limit >= 0.0f;
     Hit h;
     double closest = shadow ? std::sqrt((double)r.limit) * 1.001 + 1.0e-3 : INFINITY; // shadow_cutoff
@@ -176,9 +182,9 @@ Hit walk(const Trees& t, const std::vector<Tri>& tris, const Ray& r, Counts& cnt
             cnt.pair_steps++;
             for (uint32_t k = j; k < std::min(count, j + 2); ++k) {
                 cnt.tri_tests++;
-                const uint32_t tri = t.bvh.prim_order[first + k] & 0x3FFFFFFFu;
+                const uint32_t shape = t.bvh.prim_order[first + k], tri = shape & 0x3FFFFFFFu;
                 double dist;
-                if (!hit_triangle(tris[tri].v, r, dist)) continue;
+                if (!hit_shape(shape, r, dist)) continue;
                 if (shadow && dist * dist < r.limit) h.blocked = done = true;
                 if (!shadow && dist < closest) closest = h.dist = dist, h.tri = tri;
             }
@@ -188,6 +194,10 @@ Hit walk(const Trees& t, const std::vector<Tri>& tris, const Ray& r, Counts& cnt
         stack.pop_back();
     }
     return h;
+}
+
+Hit walk(const Trees& t, const std::vector<Tri>& tris, const Ray& r, Counts& cnt) {
+    return walk(t, [&tris](uint32_t shape, const Ray& ray, double& dist) { return hit_triangle(tris[shape & 0x3FFFFFFFu].v, ray, dist); }, r, cnt);
 }
 
 Hit brute(const std::vector<Tri>& tris, const Ray& r) {
@@ -361,6 +371,131 @@ int check(int, char** argv) {
     return 0;
 }
 
+// ---- level-wise builder: spheres and triangles
+struct Prim {
+    float kind, v[9];
+};
+
+bool hit_sphere(const float* s, const Ray& r, double& dist) { // centre, radius; nearest root beyond DIST_EPSILON
+    const double oc[3] = {(double)r.o[0] - s[0], (double)r.o[1] - s[1], (double)r.o[2] - s[2]};
+    const double d[3] = {r.d[0], r.d[1], r.d[2]};
+    const double a = d[0] * d[0] + d[1] * d[1] + d[2] * d[2], b = oc[0] * d[0] + oc[1] * d[1] + oc[2] * d[2];
+    const double c = oc[0] * oc[0] + oc[1] * oc[1] + oc[2] * oc[2] - (double)s[3] * s[3];
+    const double disc = b * b - a * c;
+    if (disc < 0.0 || a == 0.0) return false;
+    const double q = std::sqrt(disc), t0 = (-b - q) / a, t1 = (-b + q) / a;
+    dist = t0 > 1.0e-4 ? t0 : t1;
+    return dist > 1.0e-4;
+}
+
+struct LevelScene {
+    std::vector<Prim> prims;
+    std::vector<PrimBounds> bounds;
+    std::vector<uint32_t> prim_of_sphere, prim_of_triangle; // shape index -> record
+    const Prim* find(uint32_t shape) const {
+        const uint32_t index = shape & 0x3FFFFFFFu;
+        const std::vector<uint32_t>& table = (shape >> 30) == 1 ? prim_of_triangle : prim_of_sphere;
+        return (shape >> 30) <= 1 && index < table.size() ? &prims[table[index]] : nullptr;
+    }
+    bool hit(uint32_t shape, const Ray& r, double& dist) const {
+        const Prim* p = find(shape);
+        return (shape >> 30) == 1 ? hit_triangle(p->v, r, dist) : hit_sphere(p->v, r, dist);
+    }
+};
+
+LevelScene read_prims(const char* path) {
+    LevelScene sc;
+    sc.prims = read_file<Prim>(path);
+    for (size_t i = 0; i < sc.prims.size(); ++i) {
+        const float* p = sc.prims[i].v;
+        PrimBounds b;
+        if (sc.prims[i].kind == 1.0f) {
+            for (int a = 0; a < 3; ++a) {
+                b.lo[a] = std::min(p[a], std::min(p[3 + a], p[6 + a]));
+                b.hi[a] = std::max(p[a], std::max(p[3 + a], p[6 + a]));
+            }
+            b.shape = (1u << 30) | (uint32_t)sc.prim_of_triangle.size();
+            sc.prim_of_triangle.push_back((uint32_t)i);
+        } else {
+            for (int a = 0; a < 3; ++a) b.lo[a] = p[a] - p[3], b.hi[a] = p[a] + p[3]; // pack_and_upload's sphere bounds
+            b.shape = (uint32_t)sc.prim_of_sphere.size();
+            sc.prim_of_sphere.push_back((uint32_t)i);
+        }
+        sc.bounds.push_back(b);
+    }
+    return sc;
+}
+
+int level(int argc, char** argv) {
+    const LevelScene sc = read_prims(argv[2]);
+    const std::vector<Ray> rays = std::strcmp(argv[3], "-") ? read_file<Ray>(argv[3]) : std::vector<Ray>();
+    const uint32_t depth_bound = argc > 4 ? (uint32_t)std::atoi(argv[4]) : kMaxBvhDepth;
+    // as pack_and_upload decides it: leaves are tested in pairs in a triangle-only scene too big to live in LDS
+    const bool in_pairs = sc.prim_of_sphere.empty() && sc.bounds.size() * 48 > 8 * 1024;
+    uint32_t recursive_medians = 0;
+    const BuiltBvh recursive = build_bvh(sc.bounds, in_pairs, &recursive_medians);
+    LevelBuildStats stats, stats_again;
+    Trees t, again;
+    t.bvh = build_bvh_levelwise(sc.bounds, in_pairs, depth_bound, &stats);
+    again.bvh = build_bvh_levelwise(sc.bounds, in_pairs, depth_bound, &stats_again);
+    std::printf("recursive %016llx median_splits %u\n", (unsigned long long)tree_digest(recursive), recursive_medians);
+    std::printf("levelwise %016llx median_splits %u levels %u nodes %zu leaves %u depth %u\n", (unsigned long long)tree_digest(t.bvh), stats.median_splits,
+                stats.levels, t.bvh.nodes.size(), t.bvh.num_leaves, t.bvh.max_depth);
+    if (recursive_medians == 0 && depth_bound == kMaxBvhDepth) { // the same tree in the same layout, up to the order inside a leaf
+        if (recursive.nodes.size() != t.bvh.nodes.size() || recursive.num_leaves != t.bvh.num_leaves || recursive.max_depth != t.bvh.max_depth) return fail("layout differs from the recursive builder's");
+        for (size_t i = 0; i < recursive.nodes.size(); ++i)
+            if (std::memcmp(recursive.nodes[i].child, t.bvh.nodes[i].child, sizeof(recursive.nodes[i].child))) return fail("node numbering differs from the recursive builder's");
+    }
+    if (t.bvh.nodes.empty()) return fail("the level-wise tasks are no tree");
+    t.wide = in_pairs ? collapse_to_wide_sah(t.bvh) : collapse_to_wide(t.bvh);
+    again.wide = in_pairs ? collapse_to_wide_sah(again.bvh) : collapse_to_wide(again.bvh);
+    if (hash_of(t) != hash_of(again)) return fail("two builds differ");
+    if (t.bvh.max_depth > kMaxBvhDepth) return fail("binary depth");
+    if (t.wide.stack_need > 64) return fail("stack need");
+    if (t.bvh.prim_order.size() != sc.bounds.size()) return fail("reference count");
+    // every primitive is named by exactly one leaf, whose (padded) box holds its bounds
+    std::vector<uint32_t> named(sc.prims.size(), 0);
+    for (const Node128& n : t.wide.nodes)
+        for (int k = 0; k < 4; ++k) {
+            const int32_t code = n.child[k];
+            if (code >= 0 || code == kEmptyChild) continue;
+            const uint32_t first = (uint32_t)(-1 - code) >> 3, count = (uint32_t)(-1 - code) & 7u;
+            if (count > kMaxLeafPrims || first + count > t.bvh.prim_order.size()) return fail("leaf code out of range");
+            for (uint32_t j = 0; j < count; ++j) {
+                const Prim* p = sc.find(t.bvh.prim_order[first + j]);
+                if (!p) return fail("leaf reference is not a primitive of the scene");
+                const PrimBounds& b = sc.bounds[(size_t)(p - sc.prims.data())];
+                named[(size_t)(p - sc.prims.data())]++;
+                if (!(b.lo[0] >= n.lo_x[k] && b.lo[1] >= n.lo_y[k] && b.lo[2] >= n.lo_z[k] && b.hi[0] <= n.hi_x[k] && b.hi[1] <= n.hi_y[k] && b.hi[2] <= n.hi_z[k]))
+                    return fail("coverage");
+            }
+        }
+    for (const uint32_t c : named)
+        if (c != 1) return fail("a primitive is not named exactly once");
+    size_t hits = 0, blocked = 0;
+    auto hit = [&](uint32_t shape, const Ray& r, double& dist) { return sc.hit(shape, r, dist); };
+    for (const Ray& r : rays) {
+        Counts c;
+        const Hit a = walk(t, hit, r, c);
+        Hit b;
+        for (const PrimBounds& pb : sc.bounds) {
+            double dist;
+            if (!sc.hit(pb.shape, r, dist)) continue;
+            if (r.limit >= 0.0f && dist * dist < r.limit) b.blocked = true;
+            if (dist < b.dist) b.dist = dist, b.tri = pb.shape;
+        }
+        if (r.limit >= 0.0f) {
+            if (a.blocked != b.blocked) return fail("any-hit differs from brute force");
+            blocked += b.blocked;
+        } else {
+            if (a.dist != b.dist) return fail("closest hit differs from brute force");
+            hits += b.tri >= 0;
+        }
+    }
+    std::printf("OK %zu primitives, depth %u, stack %u, %zu rays (%zu closest hits, %zu blocked)\n", sc.prims.size(), t.bvh.max_depth, t.wide.stack_need, rays.size(), hits, blocked);
+    return 0;
+}
+
 int hash(int, char** argv) {
     const std::vector<Tri> tris = read_file<Tri>(argv[2]);
     std::printf("selected %016llx\n", (unsigned long long)hash_of(build(tris, spatial_splits_wanted(), cost_driven_collapse_wanted())));
@@ -376,6 +511,7 @@ int main(int argc, char** argv) {
     if (argc >= 3 && !std::strcmp(argv[1], "report")) return report(argc, argv);
     if (argc == 5 && !std::strcmp(argv[1], "check")) return check(argc, argv);
     if (argc == 3 && !std::strcmp(argv[1], "hash")) return hash(argc, argv);
-    std::fprintf(stderr, "usage: bvh_quality report TRIS NAME:RAYS... | check TRIS RAYS object|spatial | hash TRIS\n");
+    if ((argc == 4 || argc == 5) && !std::strcmp(argv[1], "level")) return level(argc, argv);
+    std::fprintf(stderr, "usage: bvh_quality report TRIS NAME:RAYS... | check TRIS RAYS object|spatial | hash TRIS | level PRIMS RAYS|- [DEPTH_BOUND]\n");
     return 2;
 }

@@ -34,6 +34,19 @@ def write_triangles(path, tris):
         f.write(tris.tobytes())
 
 
+def write_prims(path, spheres, tris):
+    """PRIMS of the tool's `level` mode: spheres [n,4] (centre, radius) first, then triangles [m,9], as pyr_scene_create orders them."""
+    spheres = np.asarray(spheres, dtype="<f4").reshape(-1, 4)
+    tris = np.asarray(tris, dtype="<f4").reshape(-1, 9)
+    rec = np.zeros((len(spheres) + len(tris), 10), dtype="<f4")
+    rec[:len(spheres), 1:5] = spheres
+    rec[len(spheres):, 0] = 1.0
+    rec[len(spheres):, 1:] = tris
+    with open(path, "wb") as f:
+        f.write(np.uint32(len(rec)).tobytes())
+        f.write(rec.tobytes())
+
+
 def write_rays(path, origins, dirs, limits=None):
     n = len(origins)
     rec = np.zeros((n, 8), dtype="<f4")
