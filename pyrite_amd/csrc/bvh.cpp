@@ -1,61 +1,80 @@
-// bvh.cpp -- binned-SAH builder for the 64-byte two-child node layout (see bvh.h).
+// bvh.cpp -- binned-SAH builders for the 64-byte two-child node layout (see bvh.h). The SAH rules are bvh_level.h's.
 #include "bvh.h"
-#include "bvh_level.h"
 
 #include <algorithm>
 #include <array>
 #include <cmath>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <limits>
 
 namespace pyr {
 namespace {
 
-#ifndef PYR_SAH_BINS
-#define PYR_SAH_BINS 16
-#endif
-constexpr int kBins = PYR_SAH_BINS;
+constexpr int kBins = lvl::kBins;
 constexpr float kInf = std::numeric_limits<float>::infinity();
 
-struct Box {
-    float lo[3] = {kInf, kInf, kInf};
-    float hi[3] = {-kInf, -kInf, -kInf};
-    void grow(const float* l, const float* h) {
-        for (int a = 0; a < 3; ++a) {
-            lo[a] = std::min(lo[a], l[a]);
-            hi[a] = std::max(hi[a], h[a]);
-        }
+// lvl::Box3 that starts empty; the arithmetic is bvh_level.h's
+struct Box : lvl::Box3 {
+    Box() : lvl::Box3(lvl::empty_box()) {}
+    void grow(const float* l, const float* h) { lvl::grow(*this, l, h); }
+    void grow(const lvl::Box3& b) { lvl::grow(*this, b.lo, b.hi); }
+    float half_area() const { return lvl::half_area(*this); }
+};
+
+// The object split's bins of one node on the host: what lvl::best_candidate and lvl::choose_split read
+struct Bins {
+    Box b[3][kBins];
+    uint32_t c[3][kBins] = {};
+    void add(int a, int k, const float* lo, const float* hi) {
+        b[a][k].grow(lo, hi);
+        c[a][k]++;
     }
-    void grow(const Box& b) { grow(b.lo, b.hi); }
-    void grow_point(const float* p) { grow(p, p); }
-    float half_area() const {
-        float dx = hi[0] - lo[0], dy = hi[1] - lo[1], dz = hi[2] - lo[2];
-        if (dx < 0 || dy < 0 || dz < 0) return 0.0f;
-        return dx * dy + dx * dz + dy * dz;
+    const lvl::Box3& box(int a, int k) const { return b[a][k]; }
+    uint32_t count(int a, int k) const { return c[a][k]; }
+};
+
+Node64 empty_node64() {
+    Node64 nd{};
+    for (int c = 0; c < 2; ++c) {
+        nd.lo_x[c] = nd.lo_y[c] = nd.lo_z[c] = kInf; // an empty child leads to an empty leaf at worst
+        nd.hi_x[c] = nd.hi_y[c] = nd.hi_z[c] = -kInf;
+        nd.child[c] = encode_leaf(0, 0);
     }
-};
+    return nd;
+}
 
-struct Ref {
-    float lo[3], hi[3], c[3];
-    uint32_t shape;
-};
-
-struct Task {
-    uint32_t begin, end, depth;
-    int32_t parent; // node that receives this subtree, -1 for the root
-    int slot;       // which child of `parent`
-};
-
-inline uint32_t ceil_log2(uint32_t n) {
-    uint32_t l = 0;
-    while ((1u << l) < n) ++l;
-    return l;
+void set_child64(Node64& p, int slot, int32_t code, const lvl::Box3& box, float pad) {
+    p.child[slot] = code;
+    p.lo_x[slot] = box.lo[0] - pad, p.lo_y[slot] = box.lo[1] - pad, p.lo_z[slot] = box.lo[2] - pad;
+    p.hi_x[slot] = box.hi[0] + pad, p.hi_y[slot] = box.hi[1] + pad, p.hi_z[slot] = box.hi[2] + pad;
 }
 
 } // namespace
 
+// Padding of every stored box: 16 ulps of the largest coordinate in the scene. The kernels compute slab distances as
+// fma(bound, 1/d, -(o * 1/d)), whose error is half an ulp of |o / d| -- in world units half an ulp of the ray origin,
+// which lies inside the scene -- so a padded box is never missed by a ray that hits something inside the exact box.
+float bvh_padding(const std::vector<PrimBounds>& prims) {
+    float max_abs = 0.0f;
+    for (const PrimBounds& p : prims)
+        for (int a = 0; a < 3; ++a) max_abs = std::max(max_abs, std::max(std::fabs(p.lo[a]), std::fabs(p.hi[a])));
+    return 16.0f * 1.1920929e-7f * max_abs;
+}
+
 BuiltBvh build_bvh(const std::vector<PrimBounds>& prims, bool leaves_tested_in_pairs, uint32_t* median_splits) {
+    struct Ref {
+        float lo[3], hi[3], c[3];
+        uint32_t shape;
+    };
+    // Build the subtree of [begin, end) and store it as child `slot` of node `parent`; parent < 0: the range of the root, whose two
+    // halves become the children of node 0. Depth counts edges from the root node: its children sit at depth 1.
+    struct Task {
+        uint32_t begin, end, depth;
+        int32_t parent;
+        int slot;
+    };
     BuiltBvh out;
     if (median_splits) *median_splits = 0;
     const uint32_t n = (uint32_t)prims.size();
@@ -64,170 +83,65 @@ BuiltBvh build_bvh(const std::vector<PrimBounds>& prims, bool leaves_tested_in_p
         for (int a = 0; a < 3; ++a) {
             refs[i].lo[a] = prims[i].lo[a];
             refs[i].hi[a] = prims[i].hi[a];
-            refs[i].c[a] = 0.5f * prims[i].lo[a] + 0.5f * prims[i].hi[a];
+            refs[i].c[a] = lvl::centroid(prims[i].lo[a], prims[i].hi[a]);
         }
         refs[i].shape = prims[i].shape;
     }
-
-    // Padding of every stored box: 16 ulps of the largest coordinate in the scene. The kernels compute slab distances as
-    // fma(bound, 1/d, -(o * 1/d)), whose error is half an ulp of |o / d| -- in world units half an ulp of the ray origin,
-    // which lies inside the scene -- so a padded box is never missed by a ray that hits something inside the exact box.
-    float max_abs = 0.0f;
-    for (uint32_t i = 0; i < n; ++i)
-        for (int a = 0; a < 3; ++a) max_abs = std::max(max_abs, std::max(std::fabs(prims[i].lo[a]), std::fabs(prims[i].hi[a])));
-    const float pad = 16.0f * 1.1920929e-7f * max_abs;
-
-    auto set_child = [&](int32_t parent, int slot, int32_t code, const Box& box) {
-        Node64& p = out.nodes[parent];
-        p.child[slot] = code;
-        p.lo_x[slot] = box.lo[0] - pad, p.lo_y[slot] = box.lo[1] - pad, p.lo_z[slot] = box.lo[2] - pad;
-        p.hi_x[slot] = box.hi[0] + pad, p.hi_y[slot] = box.hi[1] + pad, p.hi_z[slot] = box.hi[2] + pad;
-    };
-    auto empty_node = []() {
-        Node64 nd{};
-        for (int c = 0; c < 2; ++c) {
-            nd.lo_x[c] = nd.lo_y[c] = nd.lo_z[c] = kInf; // an empty child leads to an empty leaf at worst
-            nd.hi_x[c] = nd.hi_y[c] = nd.hi_z[c] = -kInf;
-            nd.child[c] = encode_leaf(0, 0);
-        }
-        return nd;
-    };
-
+    const float pad = bvh_padding(prims);
     // The root is always a node; a scene with <= kMaxLeafPrims primitives hangs one leaf under it.
-    out.nodes.push_back(empty_node());
+    out.nodes.push_back(empty_node64());
     if (n == 0) return out;
 
+    // PYR_SAH_PAIRS=1: the render kernels test a leaf's triangles two per step (DevPrimPair), so an odd triangle costs a whole step.
+    const bool in_pairs = PYR_SAH_PAIRS && leaves_tested_in_pairs;
     auto make_leaf = [&](const Task& t, const Box& box) {
-        uint32_t first = (uint32_t)out.prim_order.size();
+        const uint32_t first = (uint32_t)out.prim_order.size();
         for (uint32_t i = t.begin; i < t.end; ++i) out.prim_order.push_back(refs[i].shape);
-        set_child(t.parent, t.slot, encode_leaf(first, t.end - t.begin), box);
+        set_child64(out.nodes[t.parent], t.slot, encode_leaf(first, t.end - t.begin), box, pad);
         out.num_leaves++;
         out.max_depth = std::max(out.max_depth, t.depth);
     };
-
-    std::vector<Task> stack;
-    // Root split: children of node 0. Handle it by treating the whole range as a task whose result is written
-    // into a virtual parent; simpler: split the root range here, in the same code path as every other inner node.
-    struct Pending {
-        Task task;
-    };
-    // Task semantics: build the subtree for [begin,end) and store it as child `slot` of `parent`.
-    // Depth counts edges from the root node; children of the root sit at depth 1.
-    auto bounds_of = [&](uint32_t b, uint32_t e, Box& box, Box& cbox) {
-        for (uint32_t i = b; i < e; ++i) {
-            box.grow(refs[i].lo, refs[i].hi);
-            cbox.grow_point(refs[i].c);
-        }
-    };
-
-    // What testing n primitives of one leaf costs, in primitive tests. PYR_SAH_PAIRS=1: the render kernels test a leaf's
-    // triangles two per step (DevPrimPair), so an odd triangle costs a whole step.
-    const bool in_pairs = PYR_SAH_PAIRS && leaves_tested_in_pairs;
-    auto leaf_tests = [in_pairs](uint32_t count) { return in_pairs ? (float)((count + 1u) & ~1u) : (float)count; };
-    // Splits [begin,end) and returns mid; false when the range should become a leaf.
-    auto split = [&](uint32_t begin, uint32_t end, uint32_t depth, const Box& box, const Box& cbox, uint32_t& mid) -> bool {
-        uint32_t count = end - begin;
-        if (count <= 1) return false;
-        // Depth bound: once the remaining budget only just fits a balanced tree, split at the median.
-        bool force_median = depth + ceil_log2((count + kMaxLeafPrims - 1) / kMaxLeafPrims) + 1 >= kMaxBvhDepth;
-        float best_cost = kInf;
-        int best_axis = -1, best_bin = -1;
-        if (!force_median) {
-            for (int a = 0; a < 3; ++a) {
-                float extent = cbox.hi[a] - cbox.lo[a];
-                if (!(extent > 0.0f)) continue;
-                Box bin_box[kBins];
-                uint32_t bin_count[kBins] = {0};
-                float scale = (float)kBins / extent;
-                for (uint32_t i = begin; i < end; ++i) {
-                    int b = std::min(kBins - 1, std::max(0, (int)((refs[i].c[a] - cbox.lo[a]) * scale)));
-                    bin_box[b].grow(refs[i].lo, refs[i].hi);
-                    bin_count[b]++;
-                }
-                float right_area[kBins];
-                uint32_t right_count[kBins];
-                Box acc;
-                uint32_t cnt = 0;
-                for (int b = kBins - 1; b > 0; --b) {
-                    acc.grow(bin_box[b]);
-                    cnt += bin_count[b];
-                    right_area[b] = acc.half_area();
-                    right_count[b] = cnt;
-                }
-                Box left;
-                uint32_t lcnt = 0;
-                for (int b = 0; b < kBins - 1; ++b) {
-                    left.grow(bin_box[b]);
-                    lcnt += bin_count[b];
-                    if (lcnt == 0 || right_count[b + 1] == 0) continue;
-                    float cost = left.half_area() * leaf_tests(lcnt) + right_area[b + 1] * leaf_tests(right_count[b + 1]);
-                    if (cost < best_cost) {
-                        best_cost = cost;
-                        best_axis = a;
-                        best_bin = b;
-                    }
-                }
-            }
-        }
-        if (best_axis >= 0) {
-            // SAH termination: a leaf costs `count` primitive tests, a split costs one node visit plus the children.
-            float parent_area = box.half_area();
-            float split_cost = kSahNodeCost + (parent_area > 0.0f ? best_cost / parent_area : kInf);
-            if (count <= kMaxLeafPrims && leaf_tests(count) <= split_cost) return false;
-            float extent = cbox.hi[best_axis] - cbox.lo[best_axis];
-            float scale = (float)kBins / extent;
-            float lo = cbox.lo[best_axis];
-            auto it = std::partition(refs.begin() + begin, refs.begin() + end, [&](const Ref& r) {
-                int b = std::min(kBins - 1, std::max(0, (int)((r.c[best_axis] - lo) * scale)));
-                return b <= best_bin;
-            });
-            mid = (uint32_t)(it - refs.begin());
-            if (mid > begin && mid < end) return true;
-        }
-        if (count <= kMaxLeafPrims) return false;
-        // Median split on the widest centroid axis (coincident centroids, or depth budget exhausted).
-        int a = 0;
-        float w = -1.0f;
-        for (int k = 0; k < 3; ++k) {
-            float e = cbox.hi[k] - cbox.lo[k];
-            if (e > w) {
-                w = e;
-                a = k;
-            }
-        }
-        mid = begin + count / 2;
-        if (median_splits) ++*median_splits;
-        std::nth_element(refs.begin() + begin, refs.begin() + mid, refs.begin() + end, [a](const Ref& x, const Ref& y) { return x.c[a] < y.c[a]; });
-        return true;
-    };
-
     if (n <= kMaxLeafPrims) {
-        Box box, cbox;
-        bounds_of(0, n, box, cbox);
+        Box box;
+        for (const Ref& r : refs) box.grow(r.lo, r.hi);
         make_leaf(Task{0, n, 1, 0, 0}, box);
         return out;
     }
-    {
-        Box box, cbox;
-        bounds_of(0, n, box, cbox);
-        uint32_t mid = 0;
-        split(0, n, 0, box, cbox, mid); // n > kMaxLeafPrims: always splits
-        stack.push_back(Task{mid, n, 1, 0, 1});
-        stack.push_back(Task{0, mid, 1, 0, 0});
-    }
+    std::vector<Task> stack{Task{0, n, 0, -1, 0}}; // more than kMaxLeafPrims references: choose_split never makes this one a leaf
     while (!stack.empty()) {
-        Task t = stack.back();
+        const Task t = stack.back();
         stack.pop_back();
         Box box, cbox;
-        bounds_of(t.begin, t.end, box, cbox);
-        uint32_t mid = 0;
-        if (!split(t.begin, t.end, t.depth, box, cbox, mid)) {
+        for (uint32_t i = t.begin; i < t.end; ++i) {
+            box.grow(refs[i].lo, refs[i].hi);
+            cbox.grow(refs[i].c, refs[i].c);
+        }
+        Bins bins;
+        for (int a = 0; a < 3; ++a) {
+            const float extent = cbox.hi[a] - cbox.lo[a];
+            if (!(extent > 0.0f)) continue;
+            const float scale = lvl::bin_scale(extent);
+            for (uint32_t i = t.begin; i < t.end; ++i) bins.add(a, lvl::bin_index(refs[i].c[a], cbox.lo[a], scale), refs[i].lo, refs[i].hi);
+        }
+        const lvl::Decision d = lvl::choose_split(t.end - t.begin, t.depth, box, cbox, bins, in_pairs, kMaxBvhDepth);
+        if (d.kind == lvl::KIND_LEAF) {
             make_leaf(t, box);
             continue;
         }
-        int32_t id = (int32_t)out.nodes.size();
-        out.nodes.push_back(empty_node());
-        set_child(t.parent, t.slot, id, box);
+        const uint32_t mid = t.begin + d.left_count;
+        const int a = d.axis;
+        if (d.kind == lvl::KIND_SPLIT) { // both sides have references: the candidates were counted by this very bin_index
+            std::partition(refs.begin() + t.begin, refs.begin() + t.end, [&](const Ref& r) { return lvl::bin_index(r.c[a], d.lo, d.scale) <= d.bin; });
+        } else {
+            if (median_splits) ++*median_splits;
+            std::nth_element(refs.begin() + t.begin, refs.begin() + mid, refs.begin() + t.end, [a](const Ref& x, const Ref& y) { return x.c[a] < y.c[a]; });
+        }
+        int32_t id = 0;
+        if (t.parent >= 0) {
+            id = (int32_t)out.nodes.size();
+            out.nodes.push_back(empty_node64());
+            set_child64(out.nodes[t.parent], t.slot, id, box, pad);
+        }
         stack.push_back(Task{mid, t.end, t.depth + 1, id, 1});
         stack.push_back(Task{t.begin, mid, t.depth + 1, id, 0});
     }
@@ -239,7 +153,7 @@ namespace {
 struct SRef {
     Box box; // the part of the triangle this reference stands for (its whole box unless it was clipped)
     uint32_t shape;
-    float c(int a) const { return 0.5f * box.lo[a] + 0.5f * box.hi[a]; }
+    float c(int a) const { return lvl::centroid(box.lo[a], box.hi[a]); }
 };
 
 bool box_valid(const Box& b) { return b.lo[0] <= b.hi[0] && b.lo[1] <= b.hi[1] && b.lo[2] <= b.hi[2]; }
@@ -314,32 +228,12 @@ BuiltBvh build_bvh_spatial(const std::vector<PrimBounds>& prims, const SpatialSp
         for (int a = 0; a < 3; ++a) refs[i].box.lo[a] = prims[i].lo[a], refs[i].box.hi[a] = prims[i].hi[a];
         refs[i].shape = prims[i].shape;
     }
-    // the same padding as build_bvh: clipped boxes lie inside the triangles' own boxes, so the largest coordinate is the same
-    float max_abs = 0.0f;
-    for (uint32_t i = 0; i < n; ++i)
-        for (int a = 0; a < 3; ++a) max_abs = std::max(max_abs, std::max(std::fabs(prims[i].lo[a]), std::fabs(prims[i].hi[a])));
-    const float pad = 16.0f * 1.1920929e-7f * max_abs;
-
-    auto set_child = [&](int32_t parent, int slot, int32_t code, const Box& box) {
-        Node64& p = out.nodes[parent];
-        p.child[slot] = code;
-        p.lo_x[slot] = box.lo[0] - pad, p.lo_y[slot] = box.lo[1] - pad, p.lo_z[slot] = box.lo[2] - pad;
-        p.hi_x[slot] = box.hi[0] + pad, p.hi_y[slot] = box.hi[1] + pad, p.hi_z[slot] = box.hi[2] + pad;
-    };
-    auto empty_node = []() {
-        Node64 nd{};
-        for (int c = 0; c < 2; ++c) {
-            nd.lo_x[c] = nd.lo_y[c] = nd.lo_z[c] = kInf;
-            nd.hi_x[c] = nd.hi_y[c] = nd.hi_z[c] = -kInf;
-            nd.child[c] = encode_leaf(0, 0);
-        }
-        return nd;
-    };
-    out.nodes.push_back(empty_node());
+    const float pad = bvh_padding(prims); // clipped boxes lie inside the triangles' own boxes, so the largest coordinate is the same
+    out.nodes.push_back(empty_node64());
     if (n == 0) return out;
 
     const bool in_pairs = PYR_SAH_PAIRS != 0;
-    auto leaf_tests = [in_pairs](uint32_t count) { return in_pairs ? (float)((count + 1u) & ~1u) : (float)count; };
+    auto leaf_tests = [in_pairs](uint32_t count) { return lvl::leaf_tests(count, in_pairs); };
     Box root_box;
     for (const SRef& r : refs) root_box.grow(r.box);
     const float min_overlap = spatial.alpha * root_box.half_area();
@@ -348,7 +242,7 @@ BuiltBvh build_bvh_spatial(const std::vector<PrimBounds>& prims, const SpatialSp
     auto make_leaf = [&](const std::vector<SRef>& rs, uint32_t depth, int32_t parent, int slot, const Box& box) {
         const uint32_t first = (uint32_t)out.prim_order.size();
         for (const SRef& r : rs) out.prim_order.push_back(r.shape);
-        set_child(parent, slot, encode_leaf(first, (uint32_t)rs.size()), box);
+        set_child64(out.nodes[parent], slot, encode_leaf(first, (uint32_t)rs.size()), box, pad);
         out.num_leaves++;
         out.max_depth = std::max(out.max_depth, depth);
     };
@@ -360,48 +254,27 @@ BuiltBvh build_bvh_spatial(const std::vector<PrimBounds>& prims, const SpatialSp
         Box box, cbox;
         for (const SRef& r : rs) {
             box.grow(r.box);
-            float c[3] = {r.c(0), r.c(1), r.c(2)};
-            cbox.grow_point(c);
+            const float c[3] = {r.c(0), r.c(1), r.c(2)};
+            cbox.grow(c, c);
         }
         const bool is_root = parent < 0;
         if (!is_root && count <= 1) return make_leaf(rs, depth, parent, slot, box);
-        const bool force_median = depth + ceil_log2((count + kMaxLeafPrims - 1) / kMaxLeafPrims) + 1 >= kMaxBvhDepth;
-
-        // binned object split over the references' centroids (build_bvh's rule)
-        float obj_cost = kInf;
-        int obj_axis = -1, obj_bin = -1;
+        // the binned object split over the references' centroids, by build_bvh's rules
+        lvl::Candidate obj;
+        obj.cost = kInf, obj.axis = -1, obj.bin = -1, obj.left_count = 0;
         Box obj_left, obj_right;
-        if (!force_median) {
+        if (!lvl::force_median(count, depth, kMaxBvhDepth)) {
+            Bins bins;
             for (int a = 0; a < 3; ++a) {
                 const float extent = cbox.hi[a] - cbox.lo[a];
                 if (!(extent > 0.0f)) continue;
-                Box bin_box[kBins];
-                uint32_t bin_count[kBins] = {0};
-                const float scale = (float)kBins / extent;
-                for (const SRef& r : rs) {
-                    const int b = std::min(kBins - 1, std::max(0, (int)((r.c(a) - cbox.lo[a]) * scale)));
-                    bin_box[b].grow(r.box);
-                    bin_count[b]++;
-                }
-                Box right_box[kBins];
-                uint32_t right_count[kBins];
-                Box acc;
-                uint32_t cnt = 0;
-                for (int b = kBins - 1; b > 0; --b) {
-                    acc.grow(bin_box[b]);
-                    cnt += bin_count[b];
-                    right_box[b] = acc;
-                    right_count[b] = cnt;
-                }
-                Box left;
-                uint32_t lcnt = 0;
-                for (int b = 0; b < kBins - 1; ++b) {
-                    left.grow(bin_box[b]);
-                    lcnt += bin_count[b];
-                    if (lcnt == 0 || right_count[b + 1] == 0) continue;
-                    const float cost = left.half_area() * leaf_tests(lcnt) + right_box[b + 1].half_area() * leaf_tests(right_count[b + 1]);
-                    if (cost < obj_cost) obj_cost = cost, obj_axis = a, obj_bin = b, obj_left = left, obj_right = right_box[b + 1];
-                }
+                const float scale = lvl::bin_scale(extent);
+                for (const SRef& r : rs) bins.add(a, lvl::bin_index(r.c(a), cbox.lo[a], scale), r.box.lo, r.box.hi);
+            }
+            obj = lvl::best_candidate(cbox, bins, in_pairs);
+            if (obj.axis >= 0) { // its two children's boxes, grown in the candidate loop's order
+                for (int b = 0; b <= obj.bin; ++b) obj_left.grow(bins.box(obj.axis, b));
+                for (int b = kBins - 1; b > obj.bin; --b) obj_right.grow(bins.box(obj.axis, b));
             }
         }
         // binned spatial split, where the object split's children overlap
@@ -411,7 +284,7 @@ BuiltBvh build_bvh_spatial(const std::vector<PrimBounds>& prims, const SpatialSp
         Box sp_left, sp_right;
         float sp_plane = 0.0f;
         const Box overlap = box_and(obj_left, obj_right);
-        if (obj_axis >= 0 && extra > 0 && box_valid(overlap) && overlap.half_area() > min_overlap) {
+        if (obj.axis >= 0 && extra > 0 && box_valid(overlap) && overlap.half_area() > min_overlap) {
             for (int a = 0; a < 3; ++a) {
                 const float extent = box.hi[a] - box.lo[a];
                 if (!(extent > 0.0f)) continue;
@@ -466,13 +339,11 @@ BuiltBvh build_bvh_spatial(const std::vector<PrimBounds>& prims, const SpatialSp
                 }
             }
         }
-        const bool use_spatial = sp_axis >= 0 && sp_cost < obj_cost;
-        const float best_cost = use_spatial ? sp_cost : obj_cost;
-        if (!is_root && (obj_axis >= 0 || use_spatial)) {
-            const float parent_area = box.half_area();
-            const float split_cost = kSahNodeCost + (parent_area > 0.0f ? best_cost / parent_area : kInf);
-            if (count <= kMaxLeafPrims && leaf_tests(count) <= split_cost) return make_leaf(rs, depth, parent, slot, box);
-        }
+        // this builder's own termination: the better of the two splits decides, and the root always splits
+        const bool use_spatial = sp_axis >= 0 && sp_cost < obj.cost;
+        if (!is_root && (obj.axis >= 0 || use_spatial) && count <= kMaxLeafPrims &&
+            leaf_tests(count) <= lvl::split_cost(use_spatial ? sp_cost : obj.cost, box))
+            return make_leaf(rs, depth, parent, slot, box);
         std::vector<SRef> left, right;
         if (use_spatial) {
             // references that straddle the plane are clipped to both sides, or kept whole on one side where that is cheaper
@@ -510,22 +381,14 @@ BuiltBvh build_bvh_spatial(const std::vector<PrimBounds>& prims, const SpatialSp
                 }
             }
         } else {
-            uint32_t mid = 0;
-            if (obj_axis >= 0) {
-                const float scale = (float)kBins / (cbox.hi[obj_axis] - cbox.lo[obj_axis]);
-                const float lo = cbox.lo[obj_axis];
-                auto it = std::partition(rs.begin(), rs.end(), [&](const SRef& r) {
-                    const int b = std::min(kBins - 1, std::max(0, (int)((r.c(obj_axis) - lo) * scale)));
-                    return b <= obj_bin;
-                });
-                mid = (uint32_t)(it - rs.begin());
-            }
-            if (mid == 0 || mid == count) {
+            uint32_t mid = obj.left_count;
+            if (obj.axis >= 0) { // both sides have references: the candidates were counted by this very bin_index
+                const int a = obj.axis;
+                const float lo = cbox.lo[a], scale = lvl::bin_scale(cbox.hi[a] - cbox.lo[a]);
+                std::partition(rs.begin(), rs.end(), [&](const SRef& r) { return lvl::bin_index(r.c(a), lo, scale) <= obj.bin; });
+            } else { // coincident centroids, or the depth rule: the median on the widest centroid axis
                 if (!is_root && count <= kMaxLeafPrims) return make_leaf(rs, depth, parent, slot, box);
-                int a = 0;
-                float w = -1.0f;
-                for (int k = 0; k < 3; ++k)
-                    if (cbox.hi[k] - cbox.lo[k] > w) w = cbox.hi[k] - cbox.lo[k], a = k;
+                const int a = lvl::widest_axis(cbox);
                 mid = count / 2;
                 std::nth_element(rs.begin(), rs.begin() + mid, rs.end(), [a](const SRef& x, const SRef& y) { return x.c(a) < y.c(a); });
             }
@@ -539,8 +402,8 @@ BuiltBvh build_bvh_spatial(const std::vector<PrimBounds>& prims, const SpatialSp
         int32_t id = 0;
         if (!is_root) {
             id = (int32_t)out.nodes.size();
-            out.nodes.push_back(empty_node());
-            set_child(parent, slot, id, box);
+            out.nodes.push_back(empty_node64());
+            set_child64(out.nodes[parent], slot, id, box, pad);
         }
         self(self, left, depth + 1, id, 0, rest_left);
         self(self, right, depth + 1, id, 1, rest - rest_left);
@@ -555,23 +418,23 @@ BuiltBvh build_bvh_spatial(const std::vector<PrimBounds>& prims, const SpatialSp
     return out;
 }
 
-WideBvh collapse_to_wide(const BuiltBvh& bvh) {
+namespace {
+
+// One child of a binary node, as a candidate for a slot of a wide node
+struct Slot {
+    float lo[3], hi[3];
+    int32_t code; // Node64 child code
+};
+Slot slot_of(const BuiltBvh& bvh, int32_t node, int k) {
+    const Node64& n = bvh.nodes[node];
+    return Slot{{n.lo_x[k], n.lo_y[k], n.lo_z[k]}, {n.hi_x[k], n.hi_y[k], n.hi_z[k]}, n.child[k]};
+}
+uint32_t leaf_count(int32_t code) { return (uint32_t)(-1 - code) & 7u; }
+
+// The wide tree whose node for binary node n holds the (at most four) slots `slots_of(n)` gives it -- the rule of a collapse --
+// numbered in the order a depth-first walk, last inner slot first, reaches them.
+WideBvh emit_wide(const std::function<void(int32_t, std::vector<Slot>&)>& slots_of) {
     WideBvh out;
-    struct Child {
-        float lo[3], hi[3];
-        int32_t code; // Node64 child code
-    };
-    auto child_of = [&](const Node64& n, int k) {
-        Child c;
-        c.lo[0] = n.lo_x[k], c.lo[1] = n.lo_y[k], c.lo[2] = n.lo_z[k];
-        c.hi[0] = n.hi_x[k], c.hi[1] = n.hi_y[k], c.hi[2] = n.hi_z[k];
-        c.code = n.child[k];
-        return c;
-    };
-    auto area = [](const Child& c) {
-        float dx = c.hi[0] - c.lo[0], dy = c.hi[1] - c.lo[1], dz = c.hi[2] - c.lo[2];
-        return (dx > 0 && dy >= 0 && dz >= 0) || (dy > 0 && dx >= 0 && dz >= 0) || (dz > 0 && dx >= 0 && dy >= 0) ? dx * dy + dy * dz + dz * dx : 0.0f;
-    };
     struct Task {
         int32_t binary_node; // Node64 index this wide node stands for
         int32_t wide_index;
@@ -579,25 +442,12 @@ WideBvh collapse_to_wide(const BuiltBvh& bvh) {
     };
     out.nodes.emplace_back();
     std::vector<Task> todo{{0, 0, 1, 0}};
+    std::vector<Slot> kids;
     while (!todo.empty()) {
-        Task t = todo.back();
+        const Task t = todo.back();
         todo.pop_back();
-        std::vector<Child> kids{child_of(bvh.nodes[t.binary_node], 0), child_of(bvh.nodes[t.binary_node], 1)};
-        for (;;) {
-            if (kids.size() >= 4) break;
-            int best = -1;
-            float best_area = -1.0f;
-            for (size_t i = 0; i < kids.size(); ++i)
-                if (kids[i].code >= 0 && area(kids[i]) > best_area) best_area = area(kids[i]), best = (int)i;
-            if (best < 0) break;
-            const Node64& inner = bvh.nodes[kids[best].code];
-            kids[best] = child_of(inner, 0);
-            kids.push_back(child_of(inner, 1));
-        }
-        // drop empty leaves (a binary node with fewer than two real children)
-        std::vector<Child> real;
-        for (const Child& c : kids)
-            if (c.code >= 0 || ((uint32_t)(-1 - c.code) & 7u) != 0) real.push_back(c);
+        kids.clear();
+        slots_of(t.binary_node, kids);
         Node128 node{};
         for (int k = 0; k < 4; ++k) {
             // an unused slot's box is NaN: every comparison of the slab test fails on it, so the traversal needs no "is there a
@@ -606,19 +456,19 @@ WideBvh collapse_to_wide(const BuiltBvh& bvh) {
             node.hi_x[k] = node.hi_y[k] = node.hi_z[k] = std::numeric_limits<float>::quiet_NaN();
             node.child[k] = kEmptyChild;
         }
-        const uint32_t pushes = real.empty() ? 0u : (uint32_t)real.size() - 1u;
+        const uint32_t pushes = kids.empty() ? 0u : (uint32_t)kids.size() - 1u;
         out.max_depth = std::max(out.max_depth, t.depth);
         out.stack_need = std::max(out.stack_need, t.stack_before + pushes);
-        for (size_t k = 0; k < real.size(); ++k) {
-            node.lo_x[k] = real[k].lo[0], node.lo_y[k] = real[k].lo[1], node.lo_z[k] = real[k].lo[2];
-            node.hi_x[k] = real[k].hi[0], node.hi_y[k] = real[k].hi[1], node.hi_z[k] = real[k].hi[2];
-            if (real[k].code >= 0) {
+        for (size_t k = 0; k < kids.size(); ++k) {
+            node.lo_x[k] = kids[k].lo[0], node.lo_y[k] = kids[k].lo[1], node.lo_z[k] = kids[k].lo[2];
+            node.hi_x[k] = kids[k].hi[0], node.hi_y[k] = kids[k].hi[1], node.hi_z[k] = kids[k].hi[2];
+            if (kids[k].code >= 0) {
                 const int32_t index = (int32_t)out.nodes.size();
                 out.nodes.emplace_back();
                 node.child[k] = index;
-                todo.push_back(Task{real[k].code, index, t.depth + 1, t.stack_before + pushes});
+                todo.push_back(Task{kids[k].code, index, t.depth + 1, t.stack_before + pushes});
             } else {
-                node.child[k] = real[k].code;
+                node.child[k] = kids[k].code;
             }
         }
         out.nodes[t.wide_index] = node;
@@ -626,22 +476,38 @@ WideBvh collapse_to_wide(const BuiltBvh& bvh) {
     return out;
 }
 
+} // namespace
+
+WideBvh collapse_to_wide(const BuiltBvh& bvh) {
+    auto area = [](const Slot& c) { // (0 for a box that is flat on all axes but one)
+        float dx = c.hi[0] - c.lo[0], dy = c.hi[1] - c.lo[1], dz = c.hi[2] - c.lo[2];
+        return (dx > 0 && dy >= 0 && dz >= 0) || (dy > 0 && dx >= 0 && dz >= 0) || (dz > 0 && dx >= 0 && dy >= 0) ? dx * dy + dy * dz + dz * dx : 0.0f;
+    };
+    // the inner child with the largest surface area is replaced by its own two children until the node has four
+    return emit_wide([&](int32_t n, std::vector<Slot>& real) {
+        std::vector<Slot> kids{slot_of(bvh, n, 0), slot_of(bvh, n, 1)};
+        while (kids.size() < 4) {
+            int best = -1;
+            float best_area = -1.0f;
+            for (size_t i = 0; i < kids.size(); ++i)
+                if (kids[i].code >= 0 && area(kids[i]) > best_area) best_area = area(kids[i]), best = (int)i;
+            if (best < 0) break;
+            const int32_t inner = kids[best].code;
+            kids[best] = slot_of(bvh, inner, 0);
+            kids.push_back(slot_of(bvh, inner, 1));
+        }
+        // drop empty leaves (a binary node with fewer than two real children)
+        for (const Slot& c : kids)
+            if (c.code >= 0 || leaf_count(c.code) != 0) real.push_back(c);
+    });
+}
+
 WideBvh collapse_to_wide_sah(const BuiltBvh& bvh) {
-    WideBvh out;
     const size_t nn = bvh.nodes.size();
-    struct Slot {
-        float lo[3], hi[3];
-        int32_t code; // Node64 child code
-    };
-    auto slot_of = [&](int32_t node, int k) {
-        const Node64& n = bvh.nodes[node];
-        return Slot{{n.lo_x[k], n.lo_y[k], n.lo_z[k]}, {n.hi_x[k], n.hi_y[k], n.hi_z[k]}, n.child[k]};
-    };
     auto area = [](const Slot& c) {
         const float dx = c.hi[0] - c.lo[0], dy = c.hi[1] - c.lo[1], dz = c.hi[2] - c.lo[2];
         return dx >= 0 && dy >= 0 && dz >= 0 ? dx * dy + dy * dz + dz * dx : 0.0f;
     };
-    auto leaf_count = [](int32_t code) { return (uint32_t)(-1 - code) & 7u; };
     auto leaf_first = [](int32_t code) { return (uint32_t)(-1 - code) >> 3; };
     auto leaf_cost = [](uint32_t count) { return kWidePairCost * (float)((count + 1u) / 2u); };
 
@@ -660,7 +526,7 @@ WideBvh collapse_to_wide_sah(const BuiltBvh& bvh) {
     auto real = [&](const Slot& c) { return c.code >= 0 || leaf_count(c.code) != 0; };
     // least cost of node n's two children spread over exactly up to j slots, and how many of them go to child 0
     auto distribute = [&](size_t n, int j, int& k_best) {
-        const Slot c0 = slot_of((int32_t)n, 0), c1 = slot_of((int32_t)n, 1);
+        const Slot c0 = slot_of(bvh, (int32_t)n, 0), c1 = slot_of(bvh, (int32_t)n, 1);
         const bool r0 = real(c0), r1 = real(c1);
         k_best = -1;
         if (!r0 && !r1) return k_best = 0, 0.0f;
@@ -675,10 +541,10 @@ WideBvh collapse_to_wide_sah(const BuiltBvh& bvh) {
     };
     for (size_t n = 0; n < nn; ++n)
         for (int k = 0; k < 2; ++k)
-            if (bvh.nodes[n].child[k] >= 0) node_area[bvh.nodes[n].child[k]] = area(slot_of((int32_t)n, k));
+            if (bvh.nodes[n].child[k] >= 0) node_area[bvh.nodes[n].child[k]] = area(slot_of(bvh, (int32_t)n, k));
     for (size_t n = nn; n-- > 0;) {
         for (int k = 0; k < 2; ++k) {
-            const Slot c = slot_of((int32_t)n, k);
+            const Slot c = slot_of(bvh, (int32_t)n, k);
             if (c.code >= 0) {
                 total[n] += total[c.code];
                 first[n] = std::min(first[n], first[c.code]);
@@ -708,7 +574,7 @@ WideBvh collapse_to_wide_sah(const BuiltBvh& bvh) {
         int k;
         distribute((size_t)n, j, k);
         for (int side = 0; side < 2; ++side) {
-            const Slot c = slot_of(n, side);
+            const Slot c = slot_of(bvh, n, side);
             int i = side == 0 ? k : j - k;
             if (!real(c) || i <= 0) continue;
             if (c.code < 0) {
@@ -727,72 +593,11 @@ WideBvh collapse_to_wide_sah(const BuiltBvh& bvh) {
             }
         }
     };
-    struct Task {
-        int32_t binary_node; // Node64 index this wide node stands for
-        int32_t wide_index;
-        uint32_t depth, stack_before;
-    };
-    out.nodes.emplace_back();
-    std::vector<Task> todo{{0, 0, 1, 0}};
-    while (!todo.empty()) {
-        Task t = todo.back();
-        todo.pop_back();
-        std::vector<Slot> kids;
-        gather(gather, t.binary_node, 4, kids);
-        Node128 node{};
-        for (int k = 0; k < 4; ++k) { // unused slots: NaN boxes, as in collapse_to_wide
-            node.lo_x[k] = node.lo_y[k] = node.lo_z[k] = std::numeric_limits<float>::quiet_NaN();
-            node.hi_x[k] = node.hi_y[k] = node.hi_z[k] = std::numeric_limits<float>::quiet_NaN();
-            node.child[k] = kEmptyChild;
-        }
-        const uint32_t pushes = kids.empty() ? 0u : (uint32_t)kids.size() - 1u;
-        out.max_depth = std::max(out.max_depth, t.depth);
-        out.stack_need = std::max(out.stack_need, t.stack_before + pushes);
-        for (size_t k = 0; k < kids.size(); ++k) {
-            node.lo_x[k] = kids[k].lo[0], node.lo_y[k] = kids[k].lo[1], node.lo_z[k] = kids[k].lo[2];
-            node.hi_x[k] = kids[k].hi[0], node.hi_y[k] = kids[k].hi[1], node.hi_z[k] = kids[k].hi[2];
-            if (kids[k].code >= 0) {
-                const int32_t index = (int32_t)out.nodes.size();
-                out.nodes.emplace_back();
-                node.child[k] = index;
-                todo.push_back(Task{kids[k].code, index, t.depth + 1, t.stack_before + pushes});
-            } else {
-                node.child[k] = kids[k].code;
-            }
-        }
-        out.nodes[t.wide_index] = node;
-    }
-    return out;
+    return emit_wide([&](int32_t n, std::vector<Slot>& kids) { gather(gather, n, 4, kids); });
 }
 
 // ------------------------------------------------------------------------------------------------ level-wise build
-static_assert(lvl::kBins == kBins && lvl::kLeafMax == kMaxLeafPrims && lvl::kDepthMax == kMaxBvhDepth && lvl::kNodeCost == kSahNodeCost,
-              "bvh_level.h restates bvh.h's constants");
-
-float bvh_padding(const std::vector<PrimBounds>& prims) {
-    float max_abs = 0.0f;
-    for (const PrimBounds& p : prims)
-        for (int a = 0; a < 3; ++a) max_abs = std::max(max_abs, std::max(std::fabs(p.lo[a]), std::fabs(p.hi[a])));
-    return 16.0f * 1.1920929e-7f * max_abs;
-}
-
 namespace {
-
-Node64 empty_node64() {
-    Node64 nd{};
-    for (int c = 0; c < 2; ++c) {
-        nd.lo_x[c] = nd.lo_y[c] = nd.lo_z[c] = kInf;
-        nd.hi_x[c] = nd.hi_y[c] = nd.hi_z[c] = -kInf;
-        nd.child[c] = encode_leaf(0, 0);
-    }
-    return nd;
-}
-
-void set_child64(Node64& p, int slot, int32_t code, const lvl::Box3& box, float pad) {
-    p.child[slot] = code;
-    p.lo_x[slot] = box.lo[0] - pad, p.lo_y[slot] = box.lo[1] - pad, p.lo_z[slot] = box.lo[2] - pad;
-    p.hi_x[slot] = box.hi[0] + pad, p.hi_y[slot] = box.hi[1] + pad, p.hi_z[slot] = box.hi[2] + pad;
-}
 
 void grow_keys(uint32_t* box, uint32_t* cbox, const PrimBounds& r) {
     for (int a = 0; a < 3; ++a) {
@@ -881,12 +686,6 @@ BuiltBvh build_bvh_levelwise(const std::vector<PrimBounds>& prims, bool leaves_t
     lvl::empty_keys(tasks[0].box), lvl::empty_keys(tasks[0].cbox);
     for (const PrimBounds& r : cur) grow_keys(tasks[0].box, tasks[0].cbox, r);
 
-    struct Bins {
-        lvl::Box3 b[3][kBins];
-        uint32_t c[3][kBins];
-        const lvl::Box3& box(int a, int k) const { return b[a][k]; }
-        uint32_t count(int a, int k) const { return c[a][k]; }
-    };
     std::vector<uint32_t> level{0}, following;
     uint32_t levels = 0;
     while (!level.empty()) {
@@ -899,15 +698,10 @@ BuiltBvh build_bvh_levelwise(const std::vector<PrimBounds>& prims, bool leaves_t
             // bin phase
             Bins bins;
             for (int a = 0; a < 3; ++a) {
-                for (int k = 0; k < kBins; ++k) bins.b[a][k] = lvl::empty_box(), bins.c[a][k] = 0;
                 const float extent = cbox.hi[a] - cbox.lo[a];
                 if (!(extent > 0.0f)) continue;
                 const float scale = lvl::bin_scale(extent);
-                for (uint32_t i = t.begin; i < t.end; ++i) {
-                    const int k = lvl::bin_index(lvl::centroid(cur[i].lo[a], cur[i].hi[a]), cbox.lo[a], scale);
-                    lvl::grow(bins.b[a][k], cur[i].lo, cur[i].hi);
-                    bins.c[a][k]++;
-                }
+                for (uint32_t i = t.begin; i < t.end; ++i) bins.add(a, lvl::bin_index(lvl::centroid(cur[i].lo[a], cur[i].hi[a]), cbox.lo[a], scale), cur[i].lo, cur[i].hi);
             }
             // choose phase
             const lvl::Decision d = lvl::choose_split(count, t.depth, box, cbox, bins, in_pairs, depth_bound);

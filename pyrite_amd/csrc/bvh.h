@@ -12,6 +12,8 @@
 #include <climits>
 #include <vector>
 
+#include "bvh_level.h"
+
 namespace pyr {
 
 struct PrimBounds {
@@ -39,21 +41,16 @@ struct BuiltBvh {
     uint32_t num_leaves = 0;
 };
 
-#ifndef PYR_MAX_LEAF
-#define PYR_MAX_LEAF 4
-#endif
-constexpr uint32_t kMaxLeafPrims = PYR_MAX_LEAF; // <= 7: the leaf code keeps the count in 3 bits
-constexpr uint32_t kMaxBvhDepth = 40;
+// The builders' constants are defined in bvh_level.h (with their -D knobs), which the device builder compiles too
+constexpr uint32_t kMaxLeafPrims = lvl::kLeafMax; // <= 7: the leaf code keeps the count in 3 bits
+constexpr uint32_t kMaxBvhDepth = lvl::kDepthMax;
 // The SAH counts a leaf's primitives in pairs (an odd one costs a whole test): the render kernels test the triangles of a
 // leaf two per step (device_scene.h DevPrimPair). Measured against counting singly: C3 451 -> 457, C5 393 -> 397 Msamples/s
 // with the same number of triangle tests (fewer steps); C2's 71-node tree does not change.
 #ifndef PYR_SAH_PAIRS
 #define PYR_SAH_PAIRS 1
 #endif
-#ifndef PYR_SAH_NODE_COST
-#define PYR_SAH_NODE_COST 1.0f
-#endif
-constexpr float kSahNodeCost = PYR_SAH_NODE_COST; // cost of one node visit in units of one primitive test (SAH termination)
+constexpr float kSahNodeCost = lvl::kNodeCost; // cost of one node visit in units of one primitive test (SAH termination)
 
 inline int32_t encode_leaf(uint32_t first, uint32_t count) { return -1 - (int32_t)((first << 3) | count); }
 
@@ -63,8 +60,8 @@ inline int32_t encode_leaf(uint32_t first, uint32_t count) { return -1 - (int32_
 // `median_splits`, if given, receives how many nodes were split by the median fallback (coincident centroids, or the depth rule).
 BuiltBvh build_bvh(const std::vector<PrimBounds>& prims, bool leaves_tested_in_pairs = false, uint32_t* median_splits = nullptr);
 
-// The same tree built level by level: the sequential rehearsal of the device builder (kernels/build.hip),
-// calling the per-reference and per-node functions of bvh_level.h it calls. Where no node needs the median fallback the tree is
+// The same tree built level by level: the sequential rehearsal of the device builder (kernels/build.hip).
+// Both, like build_bvh, decide by the functions of bvh_level.h. Where no node needs the median fallback the tree is
 // build_bvh's (tree_digest below is equal); where one does, the count / 2 references smallest by (centroid, shape code) go to
 // slot 0, which may break ties differently from build_bvh's nth_element. `depth_bound` stands in for kMaxBvhDepth in the depth
 // rule (tests lower it to reach the forced median on small inputs).
@@ -74,9 +71,6 @@ struct LevelBuildStats {
 };
 BuiltBvh build_bvh_levelwise(const std::vector<PrimBounds>& prims, bool leaves_tested_in_pairs = false, uint32_t depth_bound = kMaxBvhDepth,
                              LevelBuildStats* stats = nullptr);
-namespace lvl {
-struct Task;
-}
 // The padding build_bvh gives every stored box: 16 ulps of the largest coordinate.
 float bvh_padding(const std::vector<PrimBounds>& prims);
 // A scene of at most kMaxLeafPrims primitives: one leaf under the root, as build_bvh makes it (shape codes ascending).

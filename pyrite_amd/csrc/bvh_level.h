@@ -1,10 +1,11 @@
-// bvh_level.h -- build_bvh's rules (bvh.cpp) as functions of one reference or one node, for builders that work level by level:
-// the device builder (kernels/build.hip) and its sequential rehearsal on the host (build_bvh_levelwise, bvh.cpp) call the same
-// functions, so what the two decide can differ only in what is not in here -- atomics and scans.
+// bvh_level.h -- the binned-SAH rules of every BVH builder, as functions of one reference or one node: build_bvh, the object split
+// of build_bvh_spatial and build_bvh_levelwise (bvh.cpp) and the device builder (kernels/build.hip) all call these, so what they
+// decide can differ only in what is not in here -- how a builder walks its nodes and holds its references, atomics and scans, and
+// the median rule's tie-breaking (build_bvh's nth_element against median_before below).
 //
 // Every quantity a node accumulates is a min, a max or a count, so a node's bins and its children's boxes do not depend on the
-// order its references arrive in, and the split is a pure function of the bins (choose_split). Each expression below restates
-// the one in build_bvh; units that include this header are built with -ffp-contract=off and IEEE division.
+// order its references arrive in, and the split is a pure function of the bins (choose_split). Units that include this header are
+// built with -ffp-contract=off and IEEE division. It is compiled for the device too: no standard container in here.
 #pragma once
 #include <cstdint>
 
@@ -18,10 +19,20 @@
 namespace pyr {
 namespace lvl {
 
-constexpr int kBins = 16; // PYR_SAH_BINS of bvh.cpp
-constexpr uint32_t kLeafMax = 4;  // kMaxLeafPrims (bvh.h; checked there)
-constexpr uint32_t kDepthMax = 40; // kMaxBvhDepth
-constexpr float kNodeCost = 1.0f; // kSahNodeCost
+// The builders' constants, defined here once (bvh.h names the last three kMaxLeafPrims, kMaxBvhDepth and kSahNodeCost).
+#ifndef PYR_SAH_BINS
+#define PYR_SAH_BINS 16
+#endif
+#ifndef PYR_MAX_LEAF
+#define PYR_MAX_LEAF 4
+#endif
+#ifndef PYR_SAH_NODE_COST
+#define PYR_SAH_NODE_COST 1.0f
+#endif
+constexpr int kBins = PYR_SAH_BINS;             // bins per axis of the object split
+constexpr uint32_t kLeafMax = PYR_MAX_LEAF;     // primitives of a leaf; <= 7: the leaf code keeps the count in 3 bits
+constexpr uint32_t kDepthMax = 40;              // edges from the root to a leaf, at most
+constexpr float kNodeCost = PYR_SAH_NODE_COST;  // one node visit in units of one primitive test (SAH termination)
 
 PYR_HD float pos_inf() { return __builtin_inff(); }
 
@@ -33,7 +44,7 @@ PYR_HD Box3 empty_box() {
     for (int a = 0; a < 3; ++a) b.lo[a] = pos_inf(), b.hi[a] = -pos_inf();
     return b;
 }
-// std::min / std::max of Box::grow: the second argument wins only when it is strictly smaller (larger)
+// as std::min / std::max would: the new bound wins only when it is strictly smaller (larger), so of -0 and +0 the first one stays
 PYR_HD void grow(Box3& b, const float* l, const float* h) {
     for (int a = 0; a < 3; ++a) {
         b.lo[a] = l[a] < b.lo[a] ? l[a] : b.lo[a];
@@ -103,60 +114,58 @@ struct Decision {
     uint32_t left_count; // references of slot 0
 };
 
-// build_bvh's `split` for one node, from its bins. `bins.box(axis, bin)` / `bins.count(axis, bin)` are read only for axes whose
-// centroid extent is positive, and not at all when the depth rule forces the median. The candidates of a SAH split have
-// references on both sides by the same bin_index the partition uses, so a chosen split never leaves a side empty.
+// The candidate loop of the object split: the cheapest of the (kBins - 1) x 3 planes between bins that have references on both
+// sides -- axis 0..2, bins ascending, the first of equal costs. `bins.box(axis, bin)` / `bins.count(axis, bin)` are read only for
+// axes whose centroid extent is positive. axis < 0: no such plane (every centroid extent is zero).
+struct Candidate {
+    float cost; // left area x left tests + right area x right tests
+    int axis, bin;
+    uint32_t left_count; // references in bins <= `bin`
+};
 template <class Bins>
-PYR_HD Decision choose_split(uint32_t count, uint32_t depth, const Box3& box, const Box3& cbox, const Bins& bins, bool in_pairs, uint32_t depth_bound) {
-    Decision d;
-    d.kind = KIND_LEAF, d.axis = 0, d.bin = -1, d.lo = 0.0f, d.scale = 0.0f, d.left_count = 0;
-    if (count <= 1) return d;
-    float best_cost = pos_inf();
-    int best_axis = -1, best_bin = -1;
-    uint32_t best_left = 0;
-    if (!force_median(count, depth, depth_bound)) {
-        for (int a = 0; a < 3; ++a) {
-            float extent = cbox.hi[a] - cbox.lo[a];
-            if (!(extent > 0.0f)) continue;
-            float right_area[kBins];
-            uint32_t right_count[kBins];
-            Box3 acc = empty_box();
-            uint32_t cnt = 0;
-            for (int b = kBins - 1; b > 0; --b) {
-                const Box3 bb = bins.box(a, b);
-                grow(acc, bb.lo, bb.hi);
-                cnt += bins.count(a, b);
-                right_area[b] = half_area(acc);
-                right_count[b] = cnt;
-            }
-            Box3 left = empty_box();
-            uint32_t lcnt = 0;
-            for (int b = 0; b < kBins - 1; ++b) {
-                const Box3 bb = bins.box(a, b);
-                grow(left, bb.lo, bb.hi);
-                lcnt += bins.count(a, b);
-                if (lcnt == 0 || right_count[b + 1] == 0) continue;
-                float cost = half_area(left) * leaf_tests(lcnt, in_pairs) + right_area[b + 1] * leaf_tests(right_count[b + 1], in_pairs);
-                if (cost < best_cost) {
-                    best_cost = cost;
-                    best_axis = a;
-                    best_bin = b;
-                    best_left = lcnt;
-                }
+PYR_HD Candidate best_candidate(const Box3& cbox, const Bins& bins, bool in_pairs) {
+    Candidate best;
+    best.cost = pos_inf(), best.axis = -1, best.bin = -1, best.left_count = 0;
+    for (int a = 0; a < 3; ++a) {
+        float extent = cbox.hi[a] - cbox.lo[a];
+        if (!(extent > 0.0f)) continue;
+        float right_area[kBins];
+        uint32_t right_count[kBins];
+        Box3 acc = empty_box();
+        uint32_t cnt = 0;
+        for (int b = kBins - 1; b > 0; --b) {
+            const Box3 bb = bins.box(a, b);
+            grow(acc, bb.lo, bb.hi);
+            cnt += bins.count(a, b);
+            right_area[b] = half_area(acc);
+            right_count[b] = cnt;
+        }
+        Box3 left = empty_box();
+        uint32_t lcnt = 0;
+        for (int b = 0; b < kBins - 1; ++b) {
+            const Box3 bb = bins.box(a, b);
+            grow(left, bb.lo, bb.hi);
+            lcnt += bins.count(a, b);
+            if (lcnt == 0 || right_count[b + 1] == 0) continue;
+            float cost = half_area(left) * leaf_tests(lcnt, in_pairs) + right_area[b + 1] * leaf_tests(right_count[b + 1], in_pairs);
+            if (cost < best.cost) {
+                best.cost = cost;
+                best.axis = a;
+                best.bin = b;
+                best.left_count = lcnt;
             }
         }
     }
-    if (best_axis >= 0) {
-        float parent_area = half_area(box);
-        float split_cost = kNodeCost + (parent_area > 0.0f ? best_cost / parent_area : pos_inf());
-        if (count <= kLeafMax && leaf_tests(count, in_pairs) <= split_cost) return d;
-        float extent = cbox.hi[best_axis] - cbox.lo[best_axis];
-        d.kind = KIND_SPLIT, d.axis = best_axis, d.bin = best_bin;
-        d.lo = cbox.lo[best_axis], d.scale = bin_scale(extent), d.left_count = best_left;
-        return d;
-    }
-    if (count <= kLeafMax) return d;
-    // median split on the widest centroid axis (coincident centroids, or depth budget exhausted)
+    return best;
+}
+
+// SAH termination: a leaf costs its primitive tests, a split one node visit plus the children's share of the parent's area
+PYR_HD float split_cost(float children_cost, const Box3& box) {
+    float parent_area = half_area(box);
+    return kNodeCost + (parent_area > 0.0f ? children_cost / parent_area : pos_inf());
+}
+// the median rule's axis: the widest centroid extent, the first of equals
+PYR_HD int widest_axis(const Box3& cbox) {
     int a = 0;
     float w = -1.0f;
     for (int k = 0; k < 3; ++k) {
@@ -166,7 +175,29 @@ PYR_HD Decision choose_split(uint32_t count, uint32_t depth, const Box3& box, co
             a = k;
         }
     }
-    d.kind = KIND_MEDIAN, d.axis = a, d.left_count = count / 2;
+    return a;
+}
+
+// What becomes of one node, from its bins (not read when the depth rule forces the median): a leaf, a SAH split, or the median
+// split (coincident centroids, or depth budget exhausted). The candidates of a SAH split have references on both sides by the
+// same bin_index the partition uses, so a chosen split never leaves a side empty.
+template <class Bins>
+PYR_HD Decision choose_split(uint32_t count, uint32_t depth, const Box3& box, const Box3& cbox, const Bins& bins, bool in_pairs, uint32_t depth_bound) {
+    Decision d;
+    d.kind = KIND_LEAF, d.axis = 0, d.bin = -1, d.lo = 0.0f, d.scale = 0.0f, d.left_count = 0;
+    if (count <= 1) return d;
+    if (!force_median(count, depth, depth_bound)) {
+        const Candidate best = best_candidate(cbox, bins, in_pairs);
+        if (best.axis >= 0) {
+            if (count <= kLeafMax && leaf_tests(count, in_pairs) <= split_cost(best.cost, box)) return d;
+            float extent = cbox.hi[best.axis] - cbox.lo[best.axis];
+            d.kind = KIND_SPLIT, d.axis = best.axis, d.bin = best.bin;
+            d.lo = cbox.lo[best.axis], d.scale = bin_scale(extent), d.left_count = best.left_count;
+            return d;
+        }
+    }
+    if (count <= kLeafMax) return d;
+    d.kind = KIND_MEDIAN, d.axis = widest_axis(cbox), d.left_count = count / 2;
     return d;
 }
 

@@ -1,8 +1,9 @@
-// Stand-alone host program (no GPU): runs the level-wise BVH builder -- build_bvh_levelwise of pyrite_amd/csrc/bvh.cpp, which
-// calls the per-reference and per-node functions of bvh_level.h that the device builder's kernels compile -- on the primitive
-// files given on the command line (tools/bvh_quality.py write_prims), with the depth bound of the scene builder and lowered to 8,
-// twice each, next to the recursive builder, and collapses every tree both ways. Built with -fsanitize=address,undefined together
-// with bvh.cpp, an index out of range or an undefined conversion in any of them stops the program where it happens.
+// Stand-alone host program (no GPU): runs every BVH builder of pyrite_amd/csrc/bvh.cpp -- all of them decide by the functions of
+// bvh_level.h, which the device builder's kernels compile too -- on the primitive files given on the command line
+// (tools/bvh_quality.py write_prims): the recursive builder; the level-wise one with the depth bound of the scene builder and lowered
+// to 8, twice each; on inputs without spheres the spatial-split builder, twice; and collapses every tree both ways. Built with
+// -fsanitize=address,undefined together with bvh.cpp, an index out of range or an undefined conversion in any of them stops the
+// program where it happens.
 // Exit status 0: every build gave a tree over all its primitives, twice the same digest.
 #include <algorithm>
 #include <cstdio>
@@ -19,7 +20,8 @@ struct Prim {
     float kind, v[9];
 };
 
-bool read_prims(const char* path, std::vector<PrimBounds>& bounds) {
+// `tri_positions`: nine floats per triangle, in the order of the triangles' shape codes
+bool read_prims(const char* path, std::vector<PrimBounds>& bounds, std::vector<float>& tri_positions) {
     FILE* f = std::fopen(path, "rb");
     if (!f) return false;
     uint32_t n = 0;
@@ -36,6 +38,7 @@ bool read_prims(const char* path, std::vector<PrimBounds>& bounds) {
                 b.hi[a] = std::max(p.v[a], std::max(p.v[3 + a], p.v[6 + a]));
             }
             b.shape = (1u << 30) | triangles++;
+            tri_positions.insert(tri_positions.end(), p.v, p.v + 9);
         } else {
             for (int a = 0; a < 3; ++a) b.lo[a] = p.v[a] - p.v[3], b.hi[a] = p.v[a] + p.v[3];
             b.shape = spheres++;
@@ -45,19 +48,30 @@ bool read_prims(const char* path, std::vector<PrimBounds>& bounds) {
     return true;
 }
 
+bool collapses(const BuiltBvh& tree) {
+    const WideBvh greedy = collapse_to_wide(tree), by_cost = collapse_to_wide_sah(tree);
+    return !greedy.nodes.empty() && !by_cost.nodes.empty();
+}
+
 } // namespace
 
 int main(int argc, char** argv) {
     size_t builds = 0;
     for (int i = 1; i < argc; ++i) {
         std::vector<PrimBounds> bounds;
-        if (!read_prims(argv[i], bounds)) {
+        std::vector<float> tri_positions;
+        if (!read_prims(argv[i], bounds, tri_positions)) {
             std::fprintf(stderr, "cannot read %s\n", argv[i]);
             return 2;
         }
         for (const bool in_pairs : {false, true}) {
             uint32_t medians = 0;
             const BuiltBvh recursive = build_bvh(bounds, in_pairs, &medians);
+            if (recursive.nodes.empty() || recursive.prim_order.size() != bounds.size() || recursive.max_depth > kMaxBvhDepth || !collapses(recursive)) {
+                std::fprintf(stderr, "%s: pairs %d: the recursive builder gave no tree over every primitive\n", argv[i], (int)in_pairs);
+                return 1;
+            }
+            builds += 1;
             for (const uint32_t depth_bound : {kMaxBvhDepth, 8u}) {
                 LevelBuildStats stats, again_stats;
                 const BuiltBvh tree = build_bvh_levelwise(bounds, in_pairs, depth_bound, &stats);
@@ -70,12 +84,22 @@ int main(int argc, char** argv) {
                     std::fprintf(stderr, "%s: pairs %d: the level-wise tree is not the recursive builder's\n", argv[i], (int)in_pairs);
                     return 1;
                 }
-                const WideBvh greedy = collapse_to_wide(tree), by_cost = collapse_to_wide_sah(tree);
-                if (greedy.nodes.empty() || by_cost.nodes.empty()) return 1;
+                if (!collapses(tree)) return 1;
                 builds += 2;
             }
         }
+        if (!bounds.empty() && tri_positions.size() == 9 * bounds.size()) { // triangles only: what spatial splits are for
+            SpatialSplits sp;
+            sp.tri_positions = tri_positions.data();
+            const BuiltBvh tree = build_bvh_spatial(bounds, sp), again = build_bvh_spatial(bounds, sp);
+            if (tree.nodes.empty() || tree.prim_order.size() < bounds.size() || tree.prim_order.size() > (size_t)(1.4 * bounds.size()) + 1 ||
+                tree.max_depth > kMaxBvhDepth || tree_digest(tree) != tree_digest(again) || !collapses(tree)) {
+                std::fprintf(stderr, "%s: spatial splits: no tree within the duplication budget, or two builds differ\n", argv[i]);
+                return 1;
+            }
+            builds += 2;
+        }
     }
-    std::printf("ok: %zu level-wise builds of %d inputs\n", builds, argc - 1);
+    std::printf("ok: %zu builds of %d inputs\n", builds, argc - 1);
     return 0;
 }

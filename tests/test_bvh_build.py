@@ -4,7 +4,8 @@ the spatial-split build of the four-child pair tree. No GPU: the tool walks the 
 On a small sliver mesh (a coarse torus knot, scenes.torus_knot_mesh, in a box of large walls) every tree: covers each triangle
 with the leaf boxes that name it, names only real triangles, keeps the depth and stack bounds, builds to the same bytes twice,
 and finds the same closest hits and the same blocked shadow rays as brute force. PYRITE_SPATIAL_SPLITS / PYRITE_WIDE_COLLAPSE
-select the trees they say."""
+select the trees they say, and the three trees of the sliver mesh are the ones tests/golden/bvh_digests.json pins."""
+import json
 import os
 import subprocess
 import sys
@@ -92,3 +93,10 @@ def test_builds_are_deterministic_and_the_switches_select_the_trees(tool, mesh_f
     assert hashes(tool, tri_path, PYRITE_SPATIAL_SPLITS="0")["selected"] == default["cost"]
     assert hashes(tool, tri_path, PYRITE_WIDE_COLLAPSE="greedy")["selected"] == default["old"]
     assert hashes(tool, tri_path, PYRITE_SPATIAL_SPLITS="1")["selected"] == default["spatial"]
+
+
+def test_the_three_trees_of_the_sliver_mesh_are_the_pinned_ones(tool, mesh_files):
+    with open(os.path.join(ROOT, "tests", "golden", "bvh_digests.json")) as f:
+        pinned = json.load(f)["hash_sliver_mesh"]
+    built = hashes(tool, mesh_files[0])
+    assert {k: built[k] for k in ("old", "cost", "spatial")} == pinned

@@ -3,10 +3,13 @@ by level with the per-reference and per-node functions of bvh_level.h -- the one
 tools/bvh_quality.cpp's `level` mode. No GPU.
 
 Where the recursive builder needs no median fallback, the level-wise tree is its tree: equal digests, equal node numbering.
+All builders decide by the same functions, so a wrong edit there moves them together: tests/golden/bvh_digests.json pins the trees.
 Where it does (or the depth bound is lowered to 8), the tree keeps the tool's invariants: every primitive named once by a leaf
 whose box holds it, depth and stack bounds, the same closest hits and blocked shadow rays as brute force, the same bytes twice.
 The argument checks of pyr_scene_create_with come before any device is looked for."""
 import ctypes as C
+import functools
+import json
 import os
 import subprocess
 import sys
@@ -24,6 +27,8 @@ from pyrite_amd import abi  # noqa: E402
 from pyrite_amd import build as gpu_build  # noqa: E402
 
 SOURCES = [os.path.join(ROOT, "tools", "bvh_quality.cpp"), os.path.join(ROOT, "pyrite_amd", "csrc", "bvh.cpp")]
+with open(os.path.join(ROOT, "tests", "golden", "bvh_digests.json")) as f:
+    PINS = json.load(f)
 
 
 @pytest.fixture(scope="module")
@@ -47,6 +52,7 @@ def files(tmp_path_factory):
     return out
 
 
+@functools.lru_cache(maxsize=None)
 def run_level(tool, prims, rays, *extra):
     run = subprocess.run([tool, "level", prims, rays] + list(extra), capture_output=True, text=True)
     assert run.returncode == 0, run.stdout + run.stderr
@@ -73,6 +79,34 @@ def test_tie_free_inputs_give_the_recursive_builders_tree(tool, files, name):
 def test_fallback_inputs_keep_the_invariants(tool, files, name):
     r = run_level(tool, *files[name])  # exit status 0: coverage, real primitives, depth and stack, brute force, the same bytes twice
     assert r["recursive_medians"] > 0 and r["medians"] > 0
+
+
+def test_every_input_is_pinned():
+    assert sorted(PINS["level_tie_free"]) == sorted(inputs.TIE_FREE)
+    assert sorted(PINS["level_fallback"]) == sorted(list(inputs.FALLBACK) + list(inputs.TOO_LARGE))
+
+
+@pytest.mark.parametrize("name", sorted(inputs.TIE_FREE))
+def test_tie_free_inputs_give_the_pinned_trees(tool, files, name):
+    r = run_level(tool, *files[name])
+    assert {"recursive": r["recursive"], "levelwise": r["levelwise"]} == PINS["level_tie_free"][name]
+
+
+@pytest.mark.parametrize("name", sorted(inputs.FALLBACK) + sorted(inputs.TOO_LARGE))
+def test_fallback_inputs_give_the_pinned_level_wise_trees(tool, files, name):
+    """(the recursive builder's tree of these depends on the C++ library's nth_element and is not pinned)"""
+    assert run_level(tool, *files[name])["levelwise"] == PINS["level_fallback"][name]["levelwise"]
+
+
+def test_the_c3_mesh_gives_the_pinned_tree_with_both_builders(tool, tmp_path):
+    """819,212 triangles, no rays: the tree DESIGN.md section 9e and profiles/r10_build.txt report, a few seconds."""
+    tris = bvh_quality.c3_triangles()
+    assert len(tris) == PINS["level_c3_mesh"]["triangles"]
+    prims = str(tmp_path / "c3.prims")
+    bvh_quality.write_prims(prims, inputs.NO_SPHERES, tris)
+    r = run_level(tool, prims, "-")
+    assert r["recursive_medians"] == 0 and r["medians"] == 0
+    assert (r["recursive"], r["levelwise"]) == (PINS["level_c3_mesh"]["recursive"], PINS["level_c3_mesh"]["levelwise"])
 
 
 @pytest.mark.parametrize("name", ["sliver_mesh", "mixed", "tri257"])

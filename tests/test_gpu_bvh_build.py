@@ -1,11 +1,12 @@
 """The BVH built on the device (pyr_scene_create_with, PYR_BUILD_DEVICE) against the host builder's -- run
 with `-m gpu` on an MI355X. The inputs are those of tests/test_bvh_device_cpu.py (tests/bvh_build_inputs.py).
 
-Tie-free inputs: the device builds the host's tree -- equal digest, equal PyrBvhInfo, hits equal bit for bit, equal traversal
+Tie-free inputs: the device builds the host's tree -- equal digest (the one tests/golden/bvh_digests.json pins), equal PyrBvhInfo, hits equal bit for bit, equal traversal
 counts. Fallback inputs (a node needs the median rule, where the two builders may break ties differently): equal hit distances bit
 for bit, and equal shapes except where the oracle's own intersection routine says both primitives are hit at that very distance.
 The command lines compare PNG files byte for byte: the 8-bit image of a fixed seed does not move with the order of the film's
 float atomics in any test of this suite (tests/test_gpu_session.py compares the same way), and here the trees are equal too."""
+import json
 import os
 import subprocess
 import sys
@@ -25,6 +26,8 @@ from pyrite_amd.renderer import World  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+with open(os.path.join(ROOT, "tests", "golden", "bvh_digests.json")) as f:
+    PINS = json.load(f)
 
 
 def world_of(spheres, tris):
@@ -62,6 +65,7 @@ def test_tie_free_inputs_get_the_host_builders_tree(gpu_lib, name):
     assert h["builder_asked"] == h["builder_used"] == abi.PYR_BUILD_HOST and h["fallback_reason"] == 0 and h["median_splits"] == 0
     assert d["builder_asked"] == d["builder_used"] == abi.PYR_BUILD_DEVICE and d["fallback_reason"] == 0 and d["median_splits"] == 0
     assert d["tree_digest"] == h["tree_digest"]
+    assert "%016x" % d["tree_digest"] == PINS["level_tie_free"][name]["levelwise"]
     assert device.bvh_info() == host.bvh_info()
     rays = rays_into(spheres, tris, 20000)
     hh, _, hc = host.intersect(rays, want_counters=True)
