@@ -463,6 +463,59 @@ typedef struct PyrBuildInfo {
 } PyrBuildInfo;
 int pyr_scene_build_info(PyrScene* scene, PyrBuildInfo* out);
 
+/* ---- moving a live scene's geometry. A PyrScene is no longer frozen where its primitives are: pyr_scene_update takes new
+ * positions for the SAME primitives and leaves the scene ready to render again, without repeating register allocation, the
+ * product split, the texture upload or -- for a refit -- the tree build.
+ *   What may change: where things are. Counts, materials, uvs, planes, programs, textures and the lamp list do not change; an
+ * array left NULL stays as the scene holds it (positions without normals: a pure translation).
+ *   Argument checks and atomicity: a NULL update, an unknown mode, a non-zero reserved word, an array given for a count of zero,
+ * a NULL scene and counts that are not the scene's are PYR_ERR_INVALID_ARGUMENT, in that order, before any device is looked for;
+ * pyr_last_error names the argument. The new arrays pass the coordinate check of scene creation ("Coordinates": 1e15 units,
+ * finite; PYR_ERR_UNSUPPORTED) before anything of the scene is written, so a refused update leaves the scene as it was.
+ *   Live sessions: a scene counts its PyrSessions and refuses an update while there is one (PYR_ERR_INVALID_ARGUMENT): a session
+ * renders from the scene whenever it is asked to. The one-render-at-a-time rule of the _device entry points covers
+ * pyr_scene_update_device too: the caller orders it against this scene's other work on other streams.
+ *   PYR_UPDATE_REBUILD builds a new tree with the scene's builder (host or device, as at creation): afterwards the scene is in
+ * every observable respect the scene pyr_scene_create_with makes from the same description with the new arrays -- PyrBuildInfo
+ * (digest included; its times are those of the rebuild), PyrBvhInfo, hits, traversal counters and films -- because it runs the
+ * geometry part of scene creation again. Programs, materials, spectra and textures are neither touched nor uploaded again.
+ *   PYR_UPDATE_REFIT keeps the topology: primitive order, leaf sizes and every count are those of the last build, and everything
+ * derived from positions is new -- the primitive and pair records, the triangles' shading normals and texture frames, the sphere
+ * table, the records of shape lamps (the arithmetic of scene creation, on the host) and every stored box of the binary, the
+ * four-child and the pair tree. A leaf's box is the exact min / max of its primitives, moved outward by the padding of the NEW
+ * bounds (16 ulps of the largest coordinate); an inner child's box is the union of that child's stored boxes, which is the padded
+ * union because x - pad is monotone. So a refit with unchanged arrays reproduces the bytes creation uploaded, and two updates
+ * with the same arrays write the same bytes. Empty slots and empty leaves keep their boxes. A scene built with
+ * PYRITE_SPATIAL_SPLITS=1 holds clipped boxes: PYR_UPDATE_REFIT refuses it with PYR_ERR_UNSUPPORTED, PYR_UPDATE_REBUILD serves it.
+ *   A refit never rebuilds by itself. PyrUpdateInfo::area_ratio is the caller's signal for when to ask for a rebuild.
+ *   pyr_scene_build_info keeps describing the last build (creation or rebuild).
+ *   pyr_scene_update reads HOST arrays and returns when the scene is ready. pyr_scene_update_device reads DEVICE arrays on the
+ * scene's device (16-byte aligned) and enqueues its kernels on `hip_stream`; it copies the arrays to the host first (the
+ * coordinate check, the lamp records and the description a later rebuild starts from live there), which waits for the stream. */
+#define PYR_UPDATE_REFIT   0u  /* keep the tree's topology, recompute every box bottom-up */
+#define PYR_UPDATE_REBUILD 1u  /* build a new tree with the scene's builder (host or device, as at creation) */
+typedef struct PyrGeometryUpdate {
+    uint32_t mode;
+    uint32_t num_triangles, num_spheres;   /* must equal the scene's */
+    const float* tri_positions;  /* [n][3][3] or NULL: triangles stay */
+    const float* tri_normals;    /* [n][3][3] or NULL: normals stay (a pure translation) */
+    const float* tri_frames;     /* [n][3][4] or NULL: frames stay */
+    const float* spheres;        /* [n][4] or NULL */
+    uint32_t reserved[4];
+} PyrGeometryUpdate;
+int pyr_scene_update(PyrScene*, const PyrGeometryUpdate*);                            /* HOST arrays, blocking */
+int pyr_scene_update_device(PyrScene*, const PyrGeometryUpdate*, void* hip_stream);   /* DEVICE arrays on the scene's device */
+/* The last update of a scene (all zero, area_ratio 1, before the first): the mode it ran, the launches of its longest refit
+ * schedule (the binary tree's heights; 0 for a rebuild), how many updates the scene has taken since the last build, and host
+ * wall-clock milliseconds -- new arrays to where the kernels read them (pyr_scene_update_device: to the host), the records,
+ * the boxes, and the whole call. pyr_scene_update waits between the stages, so its times are the device's too;
+ * pyr_scene_update_device's last two are the time to enqueue. A rebuild's bill is PyrBuildInfo's; here it is total_ms.
+ * `area_ratio`: the sum of the half areas of every stored child box of the binary tree, now, over the same sum at the last
+ * build, in f64 in node order -- 1.0 for a tree as built, larger as a refit loosens it. Computed on this call (it fetches the
+ * binary tree), never on an update's bill. */
+typedef struct PyrUpdateInfo { uint32_t mode_used, levels, updates; float upload_ms, prims_ms, refit_ms, total_ms; double area_ratio; uint32_t reserved[4]; } PyrUpdateInfo;
+int pyr_scene_update_info(PyrScene*, PyrUpdateInfo* out);
+
 /* Introspection of the kernel a render of `scene` with `params` would run (nothing is launched; only spectrum_samples is read
  * today). Results never depend on it -- every schedule is the same per-sample arithmetic as tracer.rs:208-345 -- but throughput
  * does, and a maintainer wants to see why a scene is slow: */

@@ -241,6 +241,9 @@ class FlatScene {
     void add_triangle(const float positions[9], const float normals[9], const float uvs[6], uint32_t material, const float frames[12] = nullptr);
 
     const PyrSceneDesc& desc(); // borrows this object's arrays
+    // New places for the same primitives (World::update): [n][3][3] positions and normals, [n][3][4] frames, [n][4] spheres; an
+    // empty vector leaves that array as it is, any other size than the scene's is a ProjectError
+    void move_geometry(const std::vector<float>& positions, const std::vector<float>& normals, const std::vector<float>& frames, const std::vector<float>& spheres);
     size_t num_triangles() const;
     size_t num_spheres() const;
     size_t num_planes() const;
@@ -260,6 +263,14 @@ class World { // world.rs:31-36
     enum class Build { Host, Device };
     PyrScene* scene(int device = 0, int copy = 0, std::optional<Build> build = std::nullopt); // created on first use (BVH build + upload); `copy` > 0: a further scene on the same device
     PyrBuildInfo build_info(int device = 0, int copy = 0); // pyr_scene_build_info: the builder used, why if not the one asked for, stage times, tree digest
+    // Moves the geometry of the scene on `device` (pyr_scene_update, host arrays, blocking): new positions [n][3][3], normals
+    // [n][3][3] and frames [n][3][4] for the same triangles, spheres [n][4] for the same spheres; an empty vector stays. Refit keeps
+    // the tree's topology and recomputes every box on the device, Rebuild builds a new tree with the scene's builder. flat()
+    // follows, so the description and the device agree.
+    enum class Update { Refit, Rebuild };
+    void update(const std::vector<float>& positions, const std::vector<float>& normals = {}, const std::vector<float>& frames = {},
+                const std::vector<float>& spheres = {}, Update mode = Update::Refit, int device = 0);
+    PyrUpdateInfo update_info(int device = 0); // pyr_scene_update_info: the last update's stages and the tree's area ratio
     // World::intersect (world.rs:273-299) for a batch of rays, [n][6] = origin, direction: closest hits, on the GPU
     std::vector<PyrHit> intersect(const std::vector<float>& rays, int device = 0, PyrCounters* counters = nullptr);
     FlatScene& flat() { return flat_; }

@@ -262,6 +262,37 @@ class PyrBuildInfo(C.Structure):
     ]
 
 
+PYR_UPDATE_REFIT = 0
+PYR_UPDATE_REBUILD = 1
+
+
+class PyrGeometryUpdate(C.Structure):
+    _fields_ = [
+        ("mode", C.c_uint32),
+        ("num_triangles", C.c_uint32),
+        ("num_spheres", C.c_uint32),
+        ("tri_positions", C.c_void_p),
+        ("tri_normals", C.c_void_p),
+        ("tri_frames", C.c_void_p),
+        ("spheres", C.c_void_p),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
+class PyrUpdateInfo(C.Structure):
+    _fields_ = [
+        ("mode_used", C.c_uint32),
+        ("levels", C.c_uint32),
+        ("updates", C.c_uint32),
+        ("upload_ms", C.c_float),
+        ("prims_ms", C.c_float),
+        ("refit_ms", C.c_float),
+        ("total_ms", C.c_float),
+        ("area_ratio", C.c_double),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
 class PyrPathInfo(C.Structure):
     _fields_ = [
         ("stage_scheduler", C.c_uint32),
@@ -381,6 +412,9 @@ ENTRY_POINTS = {
     "pyr_scene_bvh_info": (C.c_int, [C.c_void_p, C.POINTER(PyrBvhInfo)]),
     "pyr_scene_create_with": (C.c_int, [C.POINTER(PyrSceneDesc), C.c_int, C.POINTER(PyrBuildParams), C.POINTER(C.c_void_p)]),
     "pyr_scene_build_info": (C.c_int, [C.c_void_p, C.POINTER(PyrBuildInfo)]),
+    "pyr_scene_update": (C.c_int, [C.c_void_p, C.POINTER(PyrGeometryUpdate)]),
+    "pyr_scene_update_device": (C.c_int, [C.c_void_p, C.POINTER(PyrGeometryUpdate), C.c_void_p]),
+    "pyr_scene_update_info": (C.c_int, [C.c_void_p, C.POINTER(PyrUpdateInfo)]),
     "pyr_scene_path_info": (C.c_int, [C.c_void_p, C.POINTER(PyrRenderParams), C.POINTER(PyrPathInfo)]),
     "pyr_scene_program_info": (C.c_int, [C.c_void_p, C.POINTER(PyrProgramInfo)]),
     "pyr_program_allocate_registers": (C.c_int, [C.POINTER(PyrInstr), C.POINTER(PyrProgram), C.POINTER(PyrInstr), C.POINTER(PyrProgram)]),

@@ -17,6 +17,7 @@
 #include "bvh.h"
 #include "bvh_device.h"
 #include "device_scene.h"
+#include "kernels/refit_launch.h"
 #include "program_regs.h"
 
 using namespace pyr;
@@ -45,7 +46,8 @@ struct DeviceBuffer {
         ptr = nullptr;
         bytes = 0;
     }
-    int upload(const void* src, size_t n) {
+    int upload(const void* src, size_t n) { // (over an earlier allocation: that one is freed -- a rebuild uploads into the scene's buffers again)
+        release();
         bytes = n;
         if (n == 0) n = 16; // keep pointers non-null
         HIP_TRY(hipMalloc(&ptr, n));
@@ -53,6 +55,7 @@ struct DeviceBuffer {
         return PYR_OK;
     }
     int alloc(size_t n) {
+        release();
         bytes = n;
         HIP_TRY(hipMalloc(&ptr, n ? n : 16));
         return PYR_OK;
@@ -351,6 +354,53 @@ struct PyrScene {
     uint32_t* tail_count = nullptr; // device, kFeedBytes: the work-feed cursors of the intersect kernel
     DeviceBuffer tape; // spectral tape of the stage-scheduled kernel (grown on demand, kept between renders)
     DeviceBuffer tape_overflow; // one word the kernels set when a path outgrew the tape (checked after blocking renders and by pyr_scene_counters)
+    // ---- pyr_scene_update: what of the description says where things are, kept on the host (a rebuild packs the geometry from it
+    // again, a refit its lamps; the arrays an update leaves out stay as they are here), and the state of the refit
+    struct Geometry {
+        std::vector<float> tri_positions, tri_normals, tri_uvs, tri_frames, spheres, sphere_tex_scale;
+        std::vector<uint32_t> tri_material, sphere_material;
+        std::vector<PyrLamp> lamps;
+        bool has_uvs = false, has_frames = false, has_tex_scale = false;
+        uint32_t num_triangles = 0, num_spheres = 0;
+        PyrSceneDesc view() const { // a description with the fields pack_geometry and pack_lamp read
+            PyrSceneDesc d{};
+            d.num_triangles = num_triangles, d.num_spheres = num_spheres, d.num_lamps = (uint32_t)lamps.size();
+            d.tri_positions = tri_positions.data(), d.tri_normals = tri_normals.data(), d.tri_material = tri_material.data();
+            d.tri_uvs = has_uvs ? tri_uvs.data() : nullptr, d.tri_frames = has_frames ? tri_frames.data() : nullptr;
+            d.spheres = spheres.data(), d.sphere_material = sphere_material.data();
+            d.sphere_tex_scale = has_tex_scale ? sphere_tex_scale.data() : nullptr;
+            d.lamps = lamps.data();
+            return d;
+        }
+    } geometry;
+    void keep_geometry(const PyrSceneDesc* d) {
+        Geometry& g = geometry;
+        const size_t nt = d->num_triangles, ns = d->num_spheres;
+        g.num_triangles = d->num_triangles, g.num_spheres = d->num_spheres;
+        g.tri_positions.assign(d->tri_positions, d->tri_positions + (nt ? 9 * nt : 0));
+        g.tri_normals.assign(d->tri_normals, d->tri_normals + (nt ? 9 * nt : 0));
+        g.tri_material.assign(d->tri_material, d->tri_material + nt);
+        g.has_uvs = d->tri_uvs != nullptr, g.has_frames = d->tri_frames != nullptr, g.has_tex_scale = d->sphere_tex_scale != nullptr;
+        if (g.has_uvs) g.tri_uvs.assign(d->tri_uvs, d->tri_uvs + 6 * nt);
+        if (g.has_frames) g.tri_frames.assign(d->tri_frames, d->tri_frames + 12 * nt);
+        g.spheres.assign(d->spheres, d->spheres + (ns ? 4 * ns : 0));
+        g.sphere_material.assign(d->sphere_material, d->sphere_material + ns);
+        if (g.has_tex_scale) g.sphere_tex_scale.assign(d->sphere_tex_scale, d->sphere_tex_scale + 2 * ns);
+        g.lamps.assign(d->lamps, d->lamps + d->num_lamps);
+    }
+    uint32_t builder = PYR_BUILD_HOST; // who builds this scene's trees: at creation, and at every PYR_UPDATE_REBUILD
+    bool spatial_splits = false;       // the last build split space: its leaves hold clipped boxes, which a refit cannot recompute
+    uint64_t table_floats = 0;         // floats of the small tables a big scene stages into LDS (DevScene::lds_table_floats)
+    uint32_t live_sessions = 0;        // PyrSessions on this scene: an update is refused while there is one
+    DeviceBuffer upd_positions, upd_normals, upd_frames, upd_spheres; // the host form's new arrays on the device
+    bool upd_positions_current = false; // upd_positions holds geometry.tri_positions
+    DeviceBuffer upd_bounds, upd_max_abs, upd_order_binary, upd_order_wide; // the refit's scratch and its schedules (made at the first refit after a build)
+    std::vector<uint32_t> sched_binary, sched_wide; // RefitSchedule::begin of either tree
+    bool have_schedule = false;
+    std::vector<DevLamp> upd_lamps; // the lamp records of the last update (the copy to the device may still read them)
+    double built_area = 0.0; // child_area_sum at the last build; < 0: not computed yet
+    bool have_built_area = false;
+    PyrUpdateInfo update_info{};
     ~PyrScene() {
         if (tail_count) (void)hipFree(tail_count);
     }
@@ -412,47 +462,97 @@ void plane_frame_from_normal(const float n[3], float q[4]) {
 
 double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
 
-int pack_and_upload(const PyrSceneDesc* d, PyrScene* s, uint32_t builder) {
+// pyrite_gpu.h "Coordinates": what pack_geometry and pyr_scene_update refuse, in the same words
+constexpr float kMaxCoordinate = 1.0e15f;
+const char* const kCoordinateRangeMessage =
+    "a primitive lies beyond 1e15 units from the origin (or is not finite): outside the range the kernels' arithmetic is verified for";
+bool within_coordinate_range(const PrimBounds& b) {
+    for (int a = 0; a < 3; ++a)
+        if (!(std::fabs(b.lo[a]) <= kMaxCoordinate && std::fabs(b.hi[a]) <= kMaxCoordinate)) return false;
+    return true;
+}
+
+// One DevLamp from the description: a shape lamp gathers its shape's vertices, normals, area and material (Lamp::sample touches
+// nothing else). Scene creation and pyr_scene_update both pack lamps here, so a moved lamp gets creation's arithmetic.
+DevLamp pack_lamp(const PyrSceneDesc* d, uint32_t i) {
+    DevLamp o;
+    const PyrLamp& l = d->lamps[i];
+    std::memset(&o, 0, sizeof(o));
+    o.kind = l.kind;
+    o.shape_kind = l.shape_kind;
+    o.shape_index = l.shape_index;
+    o.color_program = l.color_program;
+    for (int a = 0; a < 3; ++a) o.v[a] = l.v[a];
+    o.width = l.width;
+    if (l.kind == PYR_LAMP_SHAPE && l.shape_kind == PYR_SHAPE_SPHERE) {
+        const float* p = d->spheres + 4 * (size_t)l.shape_index;
+        for (int a = 0; a < 3; ++a) o.v[a] = p[a];
+        o.width = p[3];
+        o.area = p[3] * p[3] * 4.0f * 3.14159265358979323846f; // Shape::surface_area, shapes/mod.rs:275
+        o.material = d->sphere_material[l.shape_index];
+        o.t1[0] = d->sphere_tex_scale ? d->sphere_tex_scale[2 * (size_t)l.shape_index] : 1.0f;
+        o.t1[1] = d->sphere_tex_scale ? d->sphere_tex_scale[2 * (size_t)l.shape_index + 1] : 1.0f;
+    } else if (l.kind == PYR_LAMP_SHAPE) {
+        const float* p = d->tri_positions + 9 * (size_t)l.shape_index;
+        const float* n = d->tri_normals + 9 * (size_t)l.shape_index;
+        for (int a = 0; a < 3; ++a) {
+            o.p1[a] = p[a];
+            o.p2[a] = p[3 + a];
+            o.p3[a] = p[6 + a];
+            o.n1[a] = n[a];
+            o.n2[a] = n[3 + a];
+            o.n3[a] = n[6 + a];
+        }
+        // 0.5 * |a x b| (shapes/mod.rs:276-285), evaluated in f32 without fusing
+        volatile float ax = p[3] - p[0], ay = p[4] - p[1], az = p[5] - p[2];
+        volatile float bx = p[6] - p[0], by = p[7] - p[1], bz = p[8] - p[2];
+        volatile float m1 = ay * bz, m2 = az * by, m3 = az * bx, m4 = ax * bz, m5 = ax * by, m6 = ay * bx;
+        volatile float cx = m1 - m2, cy = m3 - m4, cz = m5 - m6;
+        volatile float xx = cx * cx, yy = cy * cy, zz = cz * cz;
+        volatile float s1 = xx + yy;
+        volatile float s2 = s1 + zz;
+        o.area = 0.5f * std::sqrt(s2);
+        o.material = d->tri_material[l.shape_index];
+        if (d->tri_uvs) {
+            const float* uv = d->tri_uvs + 6 * (size_t)l.shape_index;
+            o.t1[0] = uv[0], o.t1[1] = uv[1], o.t2[0] = uv[2], o.t2[1] = uv[3], o.t3[0] = uv[4], o.t3[1] = uv[5];
+        }
+    }
+    return o;
+}
+
+// The geometry part of scene creation: everything that depends on where the primitives are -- their bounds, the trees, the
+// records in leaf order, the shading and texture-space records, the lamp records -- packed and uploaded, and the DevScene fields,
+// PyrBvhInfo and PyrBuildInfo that follow from them. pack_and_upload runs it once; pyr_scene_update(PYR_UPDATE_REBUILD) runs it
+// again on the same description with the new arrays, which is why a rebuilt scene is the scene creation makes. `d` needs its
+// geometry fields and lamps only. Nothing of the scene is written before the coordinate range is checked.
+int pack_geometry(const PyrSceneDesc* d, PyrScene* s, uint32_t builder) {
     const auto t_start = std::chrono::steady_clock::now();
     PyrBuildInfo& build_info = s->build_info;
     build_info = PyrBuildInfo{};
     build_info.builder_asked = builder;
     build_info.builder_used = PYR_BUILD_HOST;
-    const bool wide_vm = s->program_info.wide != 0;
-    for (uint32_t i = 0; i < d->num_programs; ++i) // (the allocated description: the kernels read every range from the uploaded array)
-        if (d->programs[i].kind == PYR_PROGRAM_INSTRUCTIONS && (uint64_t)d->programs[i].first_instr + d->programs[i].num_instrs > d->num_instrs)
-            return fail(PYR_ERR_INVALID_ARGUMENT, "program instruction range out of bounds after register allocation");
+    const bool needs_interpreter = s->dev.needs_interpreter != 0;
     // ---- primitives + BVH
     std::vector<PrimBounds> bounds;
     bounds.reserve((size_t)d->num_spheres + d->num_triangles);
     for (uint32_t i = 0; i < d->num_spheres; ++i) { // Bounded::aabb, shapes/mod.rs:411-416
-        const float* p = d->spheres + 4 * (size_t)i;
         PrimBounds b;
-        for (int a = 0; a < 3; ++a) {
-            b.lo[a] = p[a] - p[3];
-            b.hi[a] = p[a] + p[3];
-        }
+        lvl::sphere_bounds(d->spheres + 4 * (size_t)i, b.lo, b.hi);
         b.shape = ((uint32_t)PYR_SHAPE_SPHERE << 30) | i;
         bounds.push_back(b);
     }
     for (uint32_t i = 0; i < d->num_triangles; ++i) { // shapes/mod.rs:417-428
-        const float* p = d->tri_positions + 9 * (size_t)i;
         PrimBounds b;
-        for (int a = 0; a < 3; ++a) {
-            b.lo[a] = std::min(p[a], std::min(p[3 + a], p[6 + a]));
-            b.hi[a] = std::max(p[a], std::max(p[3 + a], p[6 + a]));
-        }
+        lvl::triangle_bounds(d->tri_positions + 9 * (size_t)i, b.lo, b.hi);
         b.shape = ((uint32_t)PYR_SHAPE_TRIANGLE << 30) | i;
         bounds.push_back(b);
     }
     // exact_math.h: `normalize` multiplies by rcp32(sqrt32(|v|^2)), which is the correctly rounded IEEE result (what the reference
     // computes) only while lengths and squared lengths stay normal f32 numbers. Coordinates are the user's units, so a scene whose
     // extent leaves the verified range is refused instead of rendered differently from the reference (pyrite_gpu.h "Coordinates").
-    constexpr float kMaxCoordinate = 1.0e15f;
     for (const PrimBounds& b : bounds)
-        for (int a = 0; a < 3; ++a)
-            if (!(std::fabs(b.lo[a]) <= kMaxCoordinate && std::fabs(b.hi[a]) <= kMaxCoordinate))
-                return fail(PYR_ERR_UNSUPPORTED, "a primitive lies beyond 1e15 units from the origin (or is not finite): outside the range the kernels' arithmetic is verified for");
+        if (!within_coordinate_range(b)) return fail(PYR_ERR_UNSUPPORTED, kCoordinateRangeMessage);
     // Leaves are tested in pairs only by the four-child pair tree: a triangle-only scene too big to live in LDS (its
     // primitives alone outgrow the 8 KB the LDS-resident walk allows) with neither tree switched off.
     const char* wide_switch = std::getenv("PYRITE_WIDE_BVH");
@@ -493,6 +593,9 @@ int pack_and_upload(const PyrSceneDesc* d, PyrScene* s, uint32_t builder) {
     if (bvh.max_depth > 96) return fail(PYR_ERR_UNSUPPORTED, "BVH deeper than the LDS traversal stack allows");
     // spatial splits repeat triangles in prim_order (and so in `prims` and the pair records): a leaf code keeps `first` in 28 bits
     if (bvh.prim_order.size() >= (1ull << 28)) return fail(PYR_ERR_UNSUPPORTED, "scene too large: 2^28 primitive references or more");
+    // the traversal addresses a node by a 32-bit byte offset from the tree's base (one SGPR pair + one VGPR per load): 4 GB of 64-byte
+    // binary nodes, 4 GB of 128-byte wide nodes -- about 200 M triangles, beyond which the call says so instead of wrapping around
+    if (bvh.nodes.size() >= (1ull << 26)) return fail(PYR_ERR_UNSUPPORTED, "scene too large: the acceleration structure has 2^26 nodes or more (4 GB)");
 
     std::vector<DevPrim> prims(bvh.prim_order.size());
     for (size_t k = 0; k < prims.size(); ++k) {
@@ -526,87 +629,9 @@ int pack_and_upload(const PyrSceneDesc* d, PyrScene* s, uint32_t builder) {
         o.n1[3] = bits_to_float(d->tri_material[i]);
     }
     std::vector<DevLamp> lamps(d->num_lamps);
-    for (uint32_t i = 0; i < d->num_lamps; ++i) {
-        const PyrLamp& l = d->lamps[i];
-        DevLamp& o = lamps[i];
-        std::memset(&o, 0, sizeof(o));
-        o.kind = l.kind;
-        o.shape_kind = l.shape_kind;
-        o.shape_index = l.shape_index;
-        o.color_program = l.color_program;
-        for (int a = 0; a < 3; ++a) o.v[a] = l.v[a];
-        o.width = l.width;
-        if (l.kind == PYR_LAMP_SHAPE && l.shape_kind == PYR_SHAPE_SPHERE) {
-            const float* p = d->spheres + 4 * (size_t)l.shape_index;
-            for (int a = 0; a < 3; ++a) o.v[a] = p[a];
-            o.width = p[3];
-            o.area = p[3] * p[3] * 4.0f * 3.14159265358979323846f; // Shape::surface_area, shapes/mod.rs:275
-            o.material = d->sphere_material[l.shape_index];
-            o.t1[0] = d->sphere_tex_scale ? d->sphere_tex_scale[2 * (size_t)l.shape_index] : 1.0f;
-            o.t1[1] = d->sphere_tex_scale ? d->sphere_tex_scale[2 * (size_t)l.shape_index + 1] : 1.0f;
-        } else if (l.kind == PYR_LAMP_SHAPE) {
-            const float* p = d->tri_positions + 9 * (size_t)l.shape_index;
-            const float* n = d->tri_normals + 9 * (size_t)l.shape_index;
-            for (int a = 0; a < 3; ++a) {
-                o.p1[a] = p[a];
-                o.p2[a] = p[3 + a];
-                o.p3[a] = p[6 + a];
-                o.n1[a] = n[a];
-                o.n2[a] = n[3 + a];
-                o.n3[a] = n[6 + a];
-            }
-            // 0.5 * |a x b| (shapes/mod.rs:276-285), evaluated in f32 without fusing
-            volatile float ax = p[3] - p[0], ay = p[4] - p[1], az = p[5] - p[2];
-            volatile float bx = p[6] - p[0], by = p[7] - p[1], bz = p[8] - p[2];
-            volatile float m1 = ay * bz, m2 = az * by, m3 = az * bx, m4 = ax * bz, m5 = ax * by, m6 = ay * bx;
-            volatile float cx = m1 - m2, cy = m3 - m4, cz = m5 - m6;
-            volatile float xx = cx * cx, yy = cy * cy, zz = cz * cz;
-            volatile float s1 = xx + yy;
-            volatile float s2 = s1 + zz;
-            o.area = 0.5f * std::sqrt(s2);
-            o.material = d->tri_material[l.shape_index];
-            if (d->tri_uvs) {
-                const float* uv = d->tri_uvs + 6 * (size_t)l.shape_index;
-                o.t1[0] = uv[0], o.t1[1] = uv[1], o.t2[0] = uv[2], o.t2[1] = uv[3], o.t3[0] = uv[4], o.t3[1] = uv[5];
-            }
-        }
-    }
-    std::vector<DevProgram> programs(d->num_programs);
-    for (uint32_t i = 0; i < d->num_programs; ++i) programs[i] = pack_program(d->instrs, d->programs[i]);
-    // programs without a tape form that factor into a hit side and a wavelength side get both as programs of their own, behind the
-    // caller's (TAPE_FORM_PRODUCT); the instruction array grows by their instructions
-    std::vector<PyrInstr> instrs(d->instrs, d->instrs + d->num_instrs);
-    for (uint32_t i = 0; i < d->num_programs && !wide_vm; ++i) { // (the wide build has no tape)
-        if (programs[i].kind != PYR_PROGRAM_INSTRUCTIONS || programs[i].tape_form != TAPE_FORM_NONE || programs.size() + 2 > 128) continue; // (a hit tape takes at most 128 programs)
-        const size_t instrs_before = instrs.size();
-        PyrProgram hit, lambda;
-        std::vector<uint32_t> chain;
-        if (!split_product(instrs, d->programs[i], hit, lambda, chain)) continue;
-        const DevProgram dev_hit = pack_program(instrs.data(), hit), dev_lambda = pack_program(instrs.data(), lambda);
-        if (dev_hit.tape_form != TAPE_FORM_HIT_VALUE || !(dev_lambda.tape_form == TAPE_FORM_LAMBDA || dev_lambda.fast != FAST_NONE)) {
-            instrs.resize(instrs_before);
-            continue;
-        }
-        programs[i].tape_form = TAPE_FORM_PRODUCT;
-        uint32_t packed = (uint32_t)programs.size() | (((uint32_t)programs.size() + 1u) << 8) | ((uint32_t)chain.size() << 16); // device_scene.h DevProgram::tape_rgb_reg
-        for (size_t c = 0; c < chain.size(); ++c) packed |= chain[c] << (20u + 4u * (uint32_t)c); // PYR_MAX_NUMBER_REGISTERS == 16
-        programs[i].tape_rgb_reg = packed;
-        programs.push_back(dev_hit);
-        programs.push_back(dev_lambda);
-    }
-
-    bool needs_interpreter = false, uses_textures = false;
-    for (const DevProgram& pr : programs)
-        if (pr.kind == PYR_PROGRAM_INSTRUCTIONS && pr.fast == FAST_NONE) needs_interpreter = true;
-    for (uint32_t i = 0; i < d->num_instrs; ++i)
-        if (d->instrs[i].op == PYR_OP_COLOR_TEXTURE || d->instrs[i].op == PYR_OP_MONO_TEXTURE) uses_textures = true;
-    for (uint32_t i = 0; i < d->num_materials; ++i)
-        if (d->materials[i].normal_map_program >= 0) uses_textures = needs_interpreter = true;
-
+    for (uint32_t i = 0; i < d->num_lamps; ++i) lamps[i] = pack_lamp(d, i);
     // texture space: only the interpreter builds of the kernels read it
     std::vector<DevTriTex> tri_tex;
-    std::vector<float> sphere_scale, plane_frames;
-    std::vector<DevTexture> textures(d->num_textures);
     if (needs_interpreter) {
         tri_tex.resize(d->num_triangles);
         for (uint32_t i = 0; i < d->num_triangles; ++i) {
@@ -623,29 +648,9 @@ int pack_and_upload(const PyrSceneDesc* d, PyrScene* s, uint32_t builder) {
                 for (int a = 0; a < 4; ++a) o.f1[a] = f[a], o.f2[a] = f[4 + a], o.f3[a] = f[8 + a];
             }
         }
-        sphere_scale.assign(2 * (size_t)d->num_spheres, 1.0f);
-        if (d->sphere_tex_scale) sphere_scale.assign(d->sphere_tex_scale, d->sphere_tex_scale + 2 * (size_t)d->num_spheres);
-        plane_frames.resize(4 * (size_t)d->num_planes);
-        for (uint32_t i = 0; i < d->num_planes; ++i) {
-            if (d->plane_frames) {
-                for (int a = 0; a < 4; ++a) plane_frames[4 * (size_t)i + a] = d->plane_frames[4 * (size_t)i + a];
-            } else {
-                plane_frame_from_normal(d->planes + 8 * (size_t)i + 3, &plane_frames[4 * (size_t)i]);
-            }
-        }
     }
-    for (uint32_t i = 0; i < d->num_textures; ++i)
-        textures[i] = DevTexture{d->textures[i].format == PYR_TEXTURE_COLOR ? 4u : 1u, d->textures[i].width, d->textures[i].height, 0u, d->textures[i].offset};
-
     int rc;
     if ((rc = s->tri_tex.upload(tri_tex.data(), tri_tex.size() * sizeof(DevTriTex)))) return rc;
-    if ((rc = s->sphere_tex_scale.upload(sphere_scale.data(), sphere_scale.size() * 4))) return rc;
-    if ((rc = s->plane_frames.upload(plane_frames.data(), plane_frames.size() * 4))) return rc;
-    if ((rc = s->textures.upload(textures.data(), textures.size() * sizeof(DevTexture)))) return rc;
-    if ((rc = s->texture_data.upload(d->texture_data, d->num_textures ? (size_t)d->num_texture_floats * 4 : 0))) return rc;
-    // the traversal addresses a node by a 32-bit byte offset from the tree's base (one SGPR pair + one VGPR per load): 4 GB of 64-byte
-    // binary nodes, 4 GB of 128-byte wide nodes -- about 200 M triangles, beyond which the call says so instead of wrapping around
-    if (bvh.nodes.size() >= (1ull << 26)) return fail(PYR_ERR_UNSUPPORTED, "scene too large: the acceleration structure has 2^26 nodes or more (4 GB)");
     if ((rc = s->nodes.upload(bvh.nodes.data(), bvh.nodes.size() * sizeof(Node64)))) return rc;
     // scenes that do not live in LDS also get the 4-wide tree for the resumable traversal (latency bound there);
     // PYRITE_WIDE_BVH=0 keeps the binary tree (A/B)
@@ -700,19 +705,7 @@ int pack_and_upload(const PyrSceneDesc* d, PyrScene* s, uint32_t builder) {
     if ((rc = s->prims.upload(prims.data(), prims.size() * sizeof(DevPrim)))) return rc;
     if ((rc = s->tri_shade.upload(shade.data(), shade.size() * sizeof(DevTriShade)))) return rc;
     if ((rc = s->spheres.upload(d->spheres, (size_t)d->num_spheres * 16))) return rc;
-    if ((rc = s->sphere_material.upload(d->sphere_material, (size_t)d->num_spheres * 4))) return rc;
-    if ((rc = s->planes.upload(d->planes, (size_t)d->num_planes * 32))) return rc;
-    if ((rc = s->plane_material.upload(d->plane_material, (size_t)d->num_planes * 4))) return rc;
     if ((rc = s->lamps.upload(lamps.data(), lamps.size() * sizeof(DevLamp)))) return rc;
-    if ((rc = s->materials.upload(d->materials, (size_t)d->num_materials * sizeof(PyrMaterial)))) return rc;
-    if ((rc = s->components.upload(d->components, (size_t)d->num_components * sizeof(PyrComponent)))) return rc;
-    if ((rc = s->programs.upload(programs.data(), programs.size() * sizeof(DevProgram)))) return rc;
-    if ((rc = s->instrs.upload(instrs.data(), instrs.size() * sizeof(PyrInstr)))) return rc;
-    if ((rc = s->spectra.upload(d->spectra, (size_t)d->num_spectra * sizeof(PyrSpectrum)))) return rc;
-    if ((rc = s->spectrum_data.upload(d->spectrum_data, (size_t)d->num_spectrum_floats * 4))) return rc;
-    if ((rc = s->rgb_basis.upload(d->rgb_basis, d->rgb_basis ? (size_t)d->rgb_basis_count * 12 : 0))) return rc;
-    if ((rc = s->counters.alloc(sizeof(PyrCounters)))) return rc;
-
     DevScene& v = s->dev;
     v.nodes = (const float*)s->nodes.ptr;
     v.wide_nodes = wide.nodes.empty() ? nullptr : (const float*)s->wide_nodes.ptr;
@@ -722,10 +715,115 @@ int pack_and_upload(const PyrSceneDesc* d, PyrScene* s, uint32_t builder) {
     v.prims = (const float*)s->prims.ptr;
     v.tri_shade = (const float*)s->tri_shade.ptr;
     v.spheres = (const float*)s->spheres.ptr;
+    v.lamps = (const DevLamp*)s->lamps.ptr;
+    v.tri_tex = (const float*)s->tri_tex.ptr;
+    v.stack_depth = std::max(1u, bvh.max_depth);
+    v.num_nodes = (uint32_t)bvh.nodes.size();
+    v.num_prims = (uint32_t)prims.size();
+    {
+        // the small tables the kernels stage into LDS (kernels.hip stage_tables): spectra + the material / component / program /
+        // lamp records. <= 16 KB, and only for scenes too big to live in LDS themselves: a small scene leaves L1 to the tables
+        // (C2: staging the spectra costs a workgroup per CU and is 0.9x), a big one evicts them all the time (C3: 1.33x)
+        const bool big_scene = (size_t)bvh.nodes.size() * 64 + prims.size() * 48 > 8 * 1024;
+        v.lds_table_floats = (s->table_floats <= 4096 && big_scene) ? (uint32_t)s->table_floats : 0;
+    }
+    s->info.num_nodes = (uint32_t)bvh.nodes.size();
+    s->info.num_leaves = bvh.num_leaves;
+    s->info.max_depth = bvh.max_depth;
+    s->info.num_primitives = (uint32_t)bounds.size(); // the scene's primitives; `prims` and the pair records may repeat some (spatial splits)
+    s->info.node_bytes = bvh.nodes.size() * sizeof(Node64);
+    s->info.primitive_bytes = prims.size() * sizeof(DevPrim);
+    s->info.num_wide_nodes = (uint32_t)wide.nodes.size();
+    s->info.num_pair_records = (uint32_t)pairs.size();
+    s->info.wide_node_bytes = wide.nodes.size() * sizeof(Node128);
+    s->info.pair_record_bytes = pairs.size() * sizeof(DevPrimPair);
+    build_info.collapse_ms = (float)collapse_ms;
+    build_info.total_ms = (float)ms_between(t_start, std::chrono::steady_clock::now());
+    build_info.pack_upload_ms = build_info.total_ms - build_info.bounds_ms - build_info.tree_ms - build_info.finish_ms - build_info.collapse_ms;
+    s->spatial_splits = spatial;
+    s->digest_source.reset(new BuiltBvh(std::move(bvh)));
+    return PYR_OK;
+}
+
+int pack_and_upload(const PyrSceneDesc* d, PyrScene* s, uint32_t builder) {
+    const auto t_start = std::chrono::steady_clock::now();
+    const bool wide_vm = s->program_info.wide != 0;
+    for (uint32_t i = 0; i < d->num_programs; ++i) // (the allocated description: the kernels read every range from the uploaded array)
+        if (d->programs[i].kind == PYR_PROGRAM_INSTRUCTIONS && (uint64_t)d->programs[i].first_instr + d->programs[i].num_instrs > d->num_instrs)
+            return fail(PYR_ERR_INVALID_ARGUMENT, "program instruction range out of bounds after register allocation");
+    std::vector<DevProgram> programs(d->num_programs);
+    for (uint32_t i = 0; i < d->num_programs; ++i) programs[i] = pack_program(d->instrs, d->programs[i]);
+    // programs without a tape form that factor into a hit side and a wavelength side get both as programs of their own, behind the
+    // caller's (TAPE_FORM_PRODUCT); the instruction array grows by their instructions
+    std::vector<PyrInstr> instrs(d->instrs, d->instrs + d->num_instrs);
+    for (uint32_t i = 0; i < d->num_programs && !wide_vm; ++i) { // (the wide build has no tape)
+        if (programs[i].kind != PYR_PROGRAM_INSTRUCTIONS || programs[i].tape_form != TAPE_FORM_NONE || programs.size() + 2 > 128) continue; // (a hit tape takes at most 128 programs)
+        const size_t instrs_before = instrs.size();
+        PyrProgram hit, lambda;
+        std::vector<uint32_t> chain;
+        if (!split_product(instrs, d->programs[i], hit, lambda, chain)) continue;
+        const DevProgram dev_hit = pack_program(instrs.data(), hit), dev_lambda = pack_program(instrs.data(), lambda);
+        if (dev_hit.tape_form != TAPE_FORM_HIT_VALUE || !(dev_lambda.tape_form == TAPE_FORM_LAMBDA || dev_lambda.fast != FAST_NONE)) {
+            instrs.resize(instrs_before);
+            continue;
+        }
+        programs[i].tape_form = TAPE_FORM_PRODUCT;
+        uint32_t packed = (uint32_t)programs.size() | (((uint32_t)programs.size() + 1u) << 8) | ((uint32_t)chain.size() << 16); // device_scene.h DevProgram::tape_rgb_reg
+        for (size_t c = 0; c < chain.size(); ++c) packed |= chain[c] << (20u + 4u * (uint32_t)c); // PYR_MAX_NUMBER_REGISTERS == 16
+        programs[i].tape_rgb_reg = packed;
+        programs.push_back(dev_hit);
+        programs.push_back(dev_lambda);
+    }
+
+    bool needs_interpreter = false, uses_textures = false;
+    for (const DevProgram& pr : programs)
+        if (pr.kind == PYR_PROGRAM_INSTRUCTIONS && pr.fast == FAST_NONE) needs_interpreter = true;
+    for (uint32_t i = 0; i < d->num_instrs; ++i)
+        if (d->instrs[i].op == PYR_OP_COLOR_TEXTURE || d->instrs[i].op == PYR_OP_MONO_TEXTURE) uses_textures = true;
+    for (uint32_t i = 0; i < d->num_materials; ++i)
+        if (d->materials[i].normal_map_program >= 0) uses_textures = needs_interpreter = true;
+    std::vector<float> sphere_scale, plane_frames;
+    std::vector<DevTexture> textures(d->num_textures);
+    if (needs_interpreter) {
+        sphere_scale.assign(2 * (size_t)d->num_spheres, 1.0f);
+        if (d->sphere_tex_scale) sphere_scale.assign(d->sphere_tex_scale, d->sphere_tex_scale + 2 * (size_t)d->num_spheres);
+        plane_frames.resize(4 * (size_t)d->num_planes);
+        for (uint32_t i = 0; i < d->num_planes; ++i) {
+            if (d->plane_frames) {
+                for (int a = 0; a < 4; ++a) plane_frames[4 * (size_t)i + a] = d->plane_frames[4 * (size_t)i + a];
+            } else {
+                plane_frame_from_normal(d->planes + 8 * (size_t)i + 3, &plane_frames[4 * (size_t)i]);
+            }
+        }
+    }
+    for (uint32_t i = 0; i < d->num_textures; ++i)
+        textures[i] = DevTexture{d->textures[i].format == PYR_TEXTURE_COLOR ? 4u : 1u, d->textures[i].width, d->textures[i].height, 0u, d->textures[i].offset};
+
+    int rc;
+    if ((rc = s->sphere_tex_scale.upload(sphere_scale.data(), sphere_scale.size() * 4))) return rc;
+    if ((rc = s->plane_frames.upload(plane_frames.data(), plane_frames.size() * 4))) return rc;
+    if ((rc = s->textures.upload(textures.data(), textures.size() * sizeof(DevTexture)))) return rc;
+    if ((rc = s->texture_data.upload(d->texture_data, d->num_textures ? (size_t)d->num_texture_floats * 4 : 0))) return rc;
+    if ((rc = s->sphere_material.upload(d->sphere_material, (size_t)d->num_spheres * 4))) return rc;
+    if ((rc = s->planes.upload(d->planes, (size_t)d->num_planes * 32))) return rc;
+    if ((rc = s->plane_material.upload(d->plane_material, (size_t)d->num_planes * 4))) return rc;
+    if ((rc = s->materials.upload(d->materials, (size_t)d->num_materials * sizeof(PyrMaterial)))) return rc;
+    if ((rc = s->components.upload(d->components, (size_t)d->num_components * sizeof(PyrComponent)))) return rc;
+    if ((rc = s->programs.upload(programs.data(), programs.size() * sizeof(DevProgram)))) return rc;
+    if ((rc = s->instrs.upload(instrs.data(), instrs.size() * sizeof(PyrInstr)))) return rc;
+    if ((rc = s->spectra.upload(d->spectra, (size_t)d->num_spectra * sizeof(PyrSpectrum)))) return rc;
+    if ((rc = s->spectrum_data.upload(d->spectrum_data, (size_t)d->num_spectrum_floats * 4))) return rc;
+    if ((rc = s->rgb_basis.upload(d->rgb_basis, d->rgb_basis ? (size_t)d->rgb_basis_count * 12 : 0))) return rc;
+    if ((rc = s->counters.alloc(sizeof(PyrCounters)))) return rc;
+    // the small tables the kernels stage into LDS, in floats (pack_geometry decides whether the scene is big enough to stage them)
+    s->table_floats = (uint64_t)d->num_spectra * (sizeof(PyrSpectrum) / 4) + d->num_spectrum_floats + (uint64_t)d->num_materials * (sizeof(PyrMaterial) / 4) +
+                      (uint64_t)d->num_components * (sizeof(PyrComponent) / 4) + (uint64_t)programs.size() * (sizeof(DevProgram) / 4) +
+                      (uint64_t)d->num_lamps * (sizeof(DevLamp) / 4);
+
+    DevScene& v = s->dev;
     v.sphere_material = (const uint32_t*)s->sphere_material.ptr;
     v.planes = (const float*)s->planes.ptr;
     v.plane_material = (const uint32_t*)s->plane_material.ptr;
-    v.lamps = (const DevLamp*)s->lamps.ptr;
     v.materials = (const PyrMaterial*)s->materials.ptr;
     v.components = (const PyrComponent*)s->components.ptr;
     v.programs = (const DevProgram*)s->programs.ptr;
@@ -739,24 +837,11 @@ int pack_and_upload(const PyrSceneDesc* d, PyrScene* s, uint32_t builder) {
     v.rgb_min = d->rgb_basis_min;
     v.rgb_max = d->rgb_basis_max;
     v.sky_program = d->sky_program;
-    v.stack_depth = std::max(1u, bvh.max_depth);
-    v.num_nodes = (uint32_t)bvh.nodes.size();
-    v.num_prims = (uint32_t)prims.size();
     v.num_spectra = d->num_spectra;
     v.num_programs = (uint32_t)programs.size();
     v.num_spectrum_floats = d->num_spectrum_floats;
     v.num_materials = d->num_materials;
     v.num_components = d->num_components;
-    {
-        // the small tables the kernels stage into LDS (kernels.hip stage_tables): spectra + the material / component / program /
-        // lamp records. <= 16 KB, and only for scenes too big to live in LDS themselves: a small scene leaves L1 to the tables
-        // (C2: staging the spectra costs a workgroup per CU and is 0.9x), a big one evicts them all the time (C3: 1.33x)
-        const uint64_t floats = (uint64_t)d->num_spectra * (sizeof(PyrSpectrum) / 4) + d->num_spectrum_floats + (uint64_t)d->num_materials * (sizeof(PyrMaterial) / 4) +
-                                (uint64_t)d->num_components * (sizeof(PyrComponent) / 4) + (uint64_t)programs.size() * (sizeof(DevProgram) / 4) +
-                                (uint64_t)d->num_lamps * (sizeof(DevLamp) / 4);
-        const bool big_scene = (size_t)bvh.nodes.size() * 64 + prims.size() * 48 > 8 * 1024;
-        v.lds_table_floats = (floats <= 4096 && big_scene) ? (uint32_t)floats : 0;
-    }
     v.needs_interpreter = needs_interpreter ? 1u : 0u;
     v.uses_textures = uses_textures ? 1u : 0u;
     // Round 4: the spectral tape for scenes WITH interpreter programs (device_scene.h TapeForm). Every colour program -- of a
@@ -796,8 +881,8 @@ int pack_and_upload(const PyrSceneDesc* d, PyrScene* s, uint32_t builder) {
         };
         for (uint32_t i = 0; i < d->num_components; ++i) colour(d->components[i].color_program);
         // (a shape lamp shines with its material's emissive components, counted above: its color_program is not read)
-        for (const DevLamp& l : lamps)
-            if (l.kind != PYR_LAMP_SHAPE) colour(l.color_program);
+        for (uint32_t i = 0; i < d->num_lamps; ++i)
+            if (d->lamps[i].kind != PYR_LAMP_SHAPE) colour(d->lamps[i].color_program);
         colour(d->sky_program);
         if (tape_rows_needed(fast_programs, v.rgb_records != 0) > kTapeMaxValueRows) ok = false; // (counted here without LAMBDA's hit-tape condition: never fewer than the kernel finds)
         const char* off = std::getenv("PYRITE_HIT_TAPE"); // A/B and tests: PYRITE_HIT_TAPE=0 keeps the online form (read at scene creation)
@@ -815,26 +900,17 @@ int pack_and_upload(const PyrSceneDesc* d, PyrScene* s, uint32_t builder) {
             const int probability = d->components[d->materials[i].first_emissive + k].probability_program;
             if (probability >= 0 && programs[(size_t)probability].reads_wavelength) v.hero_only_records = 1u;
         }
-    v.tri_tex = (const float*)s->tri_tex.ptr;
     v.sphere_tex_scale = (const float*)s->sphere_tex_scale.ptr;
     v.plane_frames = (const float*)s->plane_frames.ptr;
     v.textures = (const DevTexture*)s->textures.ptr;
     v.texture_data = (const float*)s->texture_data.ptr;
 
-    s->info.num_nodes = (uint32_t)bvh.nodes.size();
-    s->info.num_leaves = bvh.num_leaves;
-    s->info.max_depth = bvh.max_depth;
-    s->info.num_primitives = (uint32_t)bounds.size(); // the scene's primitives; `prims` and the pair records may repeat some (spatial splits)
-    s->info.node_bytes = bvh.nodes.size() * sizeof(Node64);
-    s->info.primitive_bytes = prims.size() * sizeof(DevPrim);
-    s->info.num_wide_nodes = (uint32_t)wide.nodes.size();
-    s->info.num_pair_records = (uint32_t)pairs.size();
-    s->info.wide_node_bytes = wide.nodes.size() * sizeof(Node128);
-    s->info.pair_record_bytes = pairs.size() * sizeof(DevPrimPair);
-    build_info.collapse_ms = (float)collapse_ms;
+    // the geometry part last: it reads what the programs decided (needs_interpreter, the staged tables' size) and nothing else
+    if ((rc = pack_geometry(d, s, builder)) != PYR_OK) return rc;
+    s->keep_geometry(d);
+    PyrBuildInfo& build_info = s->build_info; // all of scene creation, not the geometry part alone
     build_info.total_ms = (float)ms_between(t_start, std::chrono::steady_clock::now());
     build_info.pack_upload_ms = build_info.total_ms - build_info.bounds_ms - build_info.tree_ms - build_info.finish_ms - build_info.collapse_ms;
-    s->digest_source.reset(new BuiltBvh(std::move(bvh)));
     return PYR_OK;
 }
 
@@ -1098,6 +1174,7 @@ int pyr_scene_create_with(const PyrSceneDesc* desc, int device, const PyrBuildPa
     s->device = device;
     s->num_cus = prop.multiProcessorCount;
     s->program_info = info;
+    s->builder = builder;
     rc = pack_and_upload(&allocated, s.get(), builder);
     if (rc != PYR_OK) return rc;
     *out_scene = s.release();
@@ -1399,6 +1476,235 @@ int pyr_scene_bvh_info(PyrScene* scene, PyrBvhInfo* out) {
     return PYR_OK;
 }
 
+} // extern "C"
+
+// ------------------------------------------------------------------------------------------------ pyr_scene_update
+namespace {
+
+// What both forms refuse before any device is looked for, in the order pyrite_gpu.h gives.
+int check_update_args(const PyrScene* scene, const PyrGeometryUpdate* u) {
+    if (!u) return fail(PYR_ERR_INVALID_ARGUMENT, "null update");
+    if (u->mode != PYR_UPDATE_REFIT && u->mode != PYR_UPDATE_REBUILD) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrGeometryUpdate.mode is neither PYR_UPDATE_REFIT nor PYR_UPDATE_REBUILD");
+    for (uint32_t word : u->reserved)
+        if (word != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrGeometryUpdate.reserved must be zero");
+    if (u->num_triangles == 0 && (u->tri_positions || u->tri_normals || u->tri_frames)) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrGeometryUpdate.num_triangles is 0 but a triangle array is given");
+    if (u->num_spheres == 0 && u->spheres) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrGeometryUpdate.num_spheres is 0 but spheres are given");
+    if (!scene) return fail(PYR_ERR_INVALID_ARGUMENT, "null scene");
+    if (u->num_triangles != scene->geometry.num_triangles) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrGeometryUpdate.num_triangles is not the scene's");
+    if (u->num_spheres != scene->geometry.num_spheres) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrGeometryUpdate.num_spheres is not the scene's");
+    if (scene->live_sessions != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "the scene has a live PyrSession: destroy it before the update");
+    if (u->mode == PYR_UPDATE_REFIT && scene->spatial_splits)
+        return fail(PYR_ERR_UNSUPPORTED, "the scene's tree was built with spatial splits (PYRITE_SPATIAL_SPLITS=1): its leaves hold clipped boxes, ask for PYR_UPDATE_REBUILD");
+    return PYR_OK;
+}
+
+// The refit's schedules and scratch, made from the trees on the device at the first refit after a build -- scene creation pays
+// nothing for them. The binary tree is fetched for it anyway, so its area sum at the build is taken here too.
+int prepare_refit(PyrScene* s) {
+    if (s->have_schedule) return PYR_OK;
+    std::vector<Node64> nodes(s->info.num_nodes);
+    HIP_TRY(hipMemcpy(nodes.data(), s->nodes.ptr, nodes.size() * sizeof(Node64), hipMemcpyDeviceToHost));
+    if (!s->have_built_area) s->built_area = child_area_sum(nodes.data(), nodes.size()), s->have_built_area = true;
+    const RefitSchedule binary = refit_schedule(nodes.data(), nodes.size());
+    int rc;
+    if ((rc = s->upd_order_binary.upload(binary.order.data(), binary.order.size() * 4)) != PYR_OK) return rc;
+    s->sched_binary = binary.begin;
+    s->sched_wide.clear();
+    if (s->info.num_wide_nodes) {
+        std::vector<Node128> wide(s->info.num_wide_nodes);
+        HIP_TRY(hipMemcpy(wide.data(), s->wide_nodes.ptr, wide.size() * sizeof(Node128), hipMemcpyDeviceToHost));
+        const RefitSchedule sched = refit_schedule(wide.data(), wide.size());
+        if ((rc = s->upd_order_wide.upload(sched.order.data(), sched.order.size() * 4)) != PYR_OK) return rc;
+        s->sched_wide = sched.begin;
+    }
+    if ((rc = s->upd_bounds.alloc((size_t)s->dev.num_prims * 32)) != PYR_OK) return rc;
+    if ((rc = s->upd_max_abs.alloc(4)) != PYR_OK) return rc;
+    s->have_schedule = true;
+    return PYR_OK;
+}
+
+// a buffer of the scene that holds `bytes` (allocated once, kept)
+int reserve(DeviceBuffer& b, size_t bytes) {
+    if (b.ptr && b.bytes >= bytes) return PYR_OK;
+    return b.alloc(bytes);
+}
+
+int scene_update(PyrScene* s, const PyrGeometryUpdate* u, bool device_arrays, hipStream_t stream) {
+    const auto t_start = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(s->device));
+    PyrScene::Geometry& g = s->geometry;
+    const size_t nt = g.num_triangles, ns = g.num_spheres;
+    // ---- the new arrays on the host: the caller's own, or copies of the device arrays
+    std::vector<float> fetched[4];
+    const float* given[4] = {u->tri_positions, u->tri_normals, u->tri_frames, u->spheres};
+    const size_t floats[4] = {9 * nt, 9 * nt, 12 * nt, 4 * ns};
+    const float* host[4] = {given[0], given[1], given[2], given[3]};
+    if (device_arrays) {
+        for (int k = 0; k < 4; ++k) {
+            if (!given[k]) continue;
+            fetched[k].resize(floats[k]);
+            HIP_TRY(hipMemcpyAsync(fetched[k].data(), given[k], floats[k] * 4, hipMemcpyDeviceToHost, stream));
+            host[k] = fetched[k].data();
+        }
+        HIP_TRY(hipStreamSynchronize(stream));
+    }
+    // ---- the coordinate check of scene creation, on the bounds of what moved, before anything of the scene is written
+    if (host[3])
+        for (size_t i = 0; i < ns; ++i) {
+            PrimBounds b;
+            lvl::sphere_bounds(host[3] + 4 * i, b.lo, b.hi);
+            if (!within_coordinate_range(b)) return fail(PYR_ERR_UNSUPPORTED, kCoordinateRangeMessage);
+        }
+    if (host[0])
+        for (size_t i = 0; i < nt; ++i) {
+            PrimBounds b;
+            lvl::triangle_bounds(host[0] + 9 * i, b.lo, b.hi);
+            if (!within_coordinate_range(b)) return fail(PYR_ERR_UNSUPPORTED, kCoordinateRangeMessage);
+        }
+    PyrUpdateInfo info{};
+    info.mode_used = u->mode;
+    info.area_ratio = 1.0;
+    auto commit = [&]() { // the description the scene keeps follows the device
+        if (host[0]) g.tri_positions.assign(host[0], host[0] + floats[0]);
+        if (host[1]) g.tri_normals.assign(host[1], host[1] + floats[1]);
+        if (host[2]) g.tri_frames.assign(host[2], host[2] + floats[2]), g.has_frames = true;
+        if (host[3]) g.spheres.assign(host[3], host[3] + floats[3]);
+    };
+
+    if (u->mode == PYR_UPDATE_REBUILD) {
+        // the geometry part of scene creation over the description with the new arrays; every buffer it uploads is replaced, so
+        // nothing of this scene may be in flight
+        HIP_TRY(hipDeviceSynchronize());
+        PyrSceneDesc d = g.view();
+        if (host[0]) d.tri_positions = host[0];
+        if (host[1]) d.tri_normals = host[1];
+        if (host[2]) d.tri_frames = host[2];
+        if (host[3]) d.spheres = host[3];
+        const PyrBuildInfo build_before = s->build_info;
+        const int rc = pack_geometry(&d, s, s->builder);
+        if (rc != PYR_OK) {
+            s->build_info = build_before;
+            return rc;
+        }
+        commit();
+        s->have_schedule = s->have_built_area = s->upd_positions_current = false;
+        info.updates = 0;
+        info.total_ms = (float)ms_between(t_start, std::chrono::steady_clock::now());
+        s->update_info = info;
+        return PYR_OK;
+    }
+
+    // ---- refit
+    int rc = prepare_refit(s);
+    if (rc != PYR_OK) return rc;
+    devrefit::Ctx c{};
+    c.prims = (float*)s->prims.ptr, c.num_prims = s->dev.num_prims;
+    c.pair_prims = s->info.num_pair_records ? (float*)s->pair_prims.ptr : nullptr, c.num_pairs = s->info.num_pair_records;
+    c.tri_shade = (float*)s->tri_shade.ptr;
+    c.tri_tex = s->tri_tex.bytes ? (float*)s->tri_tex.ptr : nullptr;
+    c.sphere_table = (float*)s->spheres.ptr;
+    c.num_triangles = g.num_triangles, c.num_spheres = g.num_spheres;
+    c.write_triangles = given[0] ? 1u : 0u, c.write_spheres = given[3] ? 1u : 0u;
+    c.bounds = (float*)s->upd_bounds.ptr, c.max_abs_bits = (uint32_t*)s->upd_max_abs.ptr;
+    c.nodes = (Node64*)s->nodes.ptr, c.num_nodes = s->info.num_nodes;
+    c.wide_nodes = s->info.num_wide_nodes ? (Node128*)s->wide_nodes.ptr : nullptr, c.num_wide_nodes = s->info.num_wide_nodes;
+    c.wide_pair_nodes = s->info.num_pair_records ? (Node128*)s->wide_pair_nodes.ptr : nullptr;
+    // where the kernels read the arrays: the caller's device arrays, or the scene's own copies of the host arrays. The bounds of
+    // every leaf need the triangles as they are now, moved or not.
+    DeviceBuffer* own[4] = {&s->upd_positions, &s->upd_normals, &s->upd_frames, &s->upd_spheres};
+    const float* source[4] = {nullptr, nullptr, nullptr, nullptr};
+    for (int k = 0; k < 4; ++k) {
+        if (!given[k]) continue;
+        if (device_arrays) {
+            source[k] = given[k];
+        } else {
+            if ((rc = reserve(*own[k], floats[k] * 4)) != PYR_OK) return rc;
+            HIP_TRY(hipMemcpyAsync(own[k]->ptr, given[k], floats[k] * 4, hipMemcpyHostToDevice, stream));
+            source[k] = (const float*)own[k]->ptr;
+        }
+    }
+    if (given[0]) s->upd_positions_current = !device_arrays;
+    if (!given[0] && nt) { // the triangles stay: their positions as the scene keeps them
+        if (!s->upd_positions_current) {
+            if ((rc = reserve(s->upd_positions, floats[0] * 4)) != PYR_OK) return rc;
+            HIP_TRY(hipMemcpyAsync(s->upd_positions.ptr, g.tri_positions.data(), floats[0] * 4, hipMemcpyHostToDevice, stream));
+            s->upd_positions_current = true;
+        }
+        source[0] = (const float*)s->upd_positions.ptr;
+    }
+    c.tri_positions = source[0], c.tri_normals = source[1], c.tri_frames = source[2];
+    c.spheres = source[3] ? source[3] : (const float*)s->spheres.ptr;
+    commit();
+    // the lamp records, on the host with creation's arithmetic (lamps are few)
+    bool shape_lamps = false;
+    for (const PyrLamp& l : g.lamps) shape_lamps = shape_lamps || l.kind == PYR_LAMP_SHAPE;
+    if (shape_lamps) {
+        HIP_TRY(hipStreamSynchronize(stream)); // an earlier update's copy may still read upd_lamps
+        const PyrSceneDesc d = g.view();
+        s->upd_lamps.resize(g.lamps.size());
+        for (uint32_t i = 0; i < (uint32_t)g.lamps.size(); ++i) s->upd_lamps[i] = pack_lamp(&d, i);
+        HIP_TRY(hipMemcpyAsync(s->lamps.ptr, s->upd_lamps.data(), s->upd_lamps.size() * sizeof(DevLamp), hipMemcpyHostToDevice, stream));
+    }
+    HIP_TRY(hipMemsetAsync(s->upd_max_abs.ptr, 0, 4, stream));
+    if (!device_arrays) HIP_TRY(hipStreamSynchronize(stream));
+    const auto t_uploaded = std::chrono::steady_clock::now();
+    hipError_t e = devrefit::launch_repack(c, stream);
+    if (e != hipSuccess) return hip_fail(e, "refit: repack kernels");
+    if (!device_arrays) HIP_TRY(hipStreamSynchronize(stream));
+    const auto t_prims = std::chrono::steady_clock::now();
+    // one launch per height and tree, deepest nodes first
+    for (size_t h = 0; h + 1 < s->sched_binary.size(); ++h) {
+        e = devrefit::launch_refit_binary(c, (const uint32_t*)s->upd_order_binary.ptr + s->sched_binary[h], s->sched_binary[h + 1] - s->sched_binary[h], stream);
+        if (e != hipSuccess) return hip_fail(e, "refit: binary tree");
+    }
+    for (size_t h = 0; h + 1 < s->sched_wide.size(); ++h) {
+        e = devrefit::launch_refit_wide(c, (const uint32_t*)s->upd_order_wide.ptr + s->sched_wide[h], s->sched_wide[h + 1] - s->sched_wide[h], stream);
+        if (e != hipSuccess) return hip_fail(e, "refit: four-child tree");
+    }
+    if (!device_arrays) HIP_TRY(hipStreamSynchronize(stream));
+    const auto t_end = std::chrono::steady_clock::now();
+    info.levels = s->sched_binary.empty() ? 0u : (uint32_t)s->sched_binary.size() - 1u;
+    info.updates = s->update_info.updates + 1u;
+    info.upload_ms = (float)ms_between(t_start, t_uploaded);
+    info.prims_ms = (float)ms_between(t_uploaded, t_prims);
+    info.refit_ms = (float)ms_between(t_prims, t_end);
+    info.total_ms = (float)ms_between(t_start, t_end);
+    s->update_info = info;
+    return PYR_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int pyr_scene_update(PyrScene* scene, const PyrGeometryUpdate* update) {
+    int rc = check_update_args(scene, update);
+    if (rc != PYR_OK) return rc;
+    HIP_TRY(hipSetDevice(scene->device));
+    HIP_TRY(hipDeviceSynchronize()); // blocking: nothing of this scene is in flight while its records change
+    return scene_update(scene, update, false, nullptr);
+}
+
+int pyr_scene_update_device(PyrScene* scene, const PyrGeometryUpdate* update, void* hip_stream) {
+    int rc = check_update_args(scene, update);
+    if (rc != PYR_OK) return rc;
+    return scene_update(scene, update, true, (hipStream_t)hip_stream);
+}
+
+int pyr_scene_update_info(PyrScene* scene, PyrUpdateInfo* out) {
+    if (!scene || !out) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+    HIP_TRY(hipSetDevice(scene->device));
+    HIP_TRY(hipDeviceSynchronize());
+    std::vector<Node64> nodes(scene->info.num_nodes);
+    HIP_TRY(hipMemcpy(nodes.data(), scene->nodes.ptr, nodes.size() * sizeof(Node64), hipMemcpyDeviceToHost));
+    const double now = child_area_sum(nodes.data(), nodes.size());
+    if (!scene->have_built_area) scene->built_area = now, scene->have_built_area = true; // no refit since the build: this is the built tree
+    *out = scene->update_info;
+    out->area_ratio = scene->built_area > 0.0 ? now / scene->built_area : 1.0;
+    return PYR_OK;
+}
+
+
 
 // ------------------------------------------------------------------------------------------------ progressive sessions
 } // extern "C"
@@ -1416,6 +1722,7 @@ struct PyrSession {
     uint32_t samples_done = 0, passes = 0;
     uint32_t tiles_x = 0, tiles_y = 0;
     ~PyrSession() {
+        if (scene) scene->live_sessions--; // (pyr_scene_update refuses a scene that has one)
         if (stream) (void)hipStreamDestroy(stream);
     }
 };
@@ -1493,6 +1800,7 @@ int pyr_session_create(PyrScene* scene, const PyrCamera* camera, const PyrFilmDe
     std::unique_ptr<PyrSession> s(new (std::nothrow) PyrSession());
     if (!s) return fail(PYR_ERR_OUT_OF_MEMORY, "out of host memory");
     s->scene = scene;
+    scene->live_sessions++;
     s->camera = *camera;
     s->film = *film;
     s->params = *params;

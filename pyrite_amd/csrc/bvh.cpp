@@ -46,9 +46,10 @@ Node64 empty_node64() {
 }
 
 void set_child64(Node64& p, int slot, int32_t code, const lvl::Box3& box, float pad) {
+    const lvl::Box3 stored = lvl::padded(box, pad);
     p.child[slot] = code;
-    p.lo_x[slot] = box.lo[0] - pad, p.lo_y[slot] = box.lo[1] - pad, p.lo_z[slot] = box.lo[2] - pad;
-    p.hi_x[slot] = box.hi[0] + pad, p.hi_y[slot] = box.hi[1] + pad, p.hi_z[slot] = box.hi[2] + pad;
+    p.lo_x[slot] = stored.lo[0], p.lo_y[slot] = stored.lo[1], p.lo_z[slot] = stored.lo[2];
+    p.hi_x[slot] = stored.hi[0], p.hi_y[slot] = stored.hi[1], p.hi_z[slot] = stored.hi[2];
 }
 
 } // namespace
@@ -58,9 +59,8 @@ void set_child64(Node64& p, int slot, int32_t code, const lvl::Box3& box, float 
 // which lies inside the scene -- so a padded box is never missed by a ray that hits something inside the exact box.
 float bvh_padding(const std::vector<PrimBounds>& prims) {
     float max_abs = 0.0f;
-    for (const PrimBounds& p : prims)
-        for (int a = 0; a < 3; ++a) max_abs = std::max(max_abs, std::max(std::fabs(p.lo[a]), std::fabs(p.hi[a])));
-    return 16.0f * 1.1920929e-7f * max_abs;
+    for (const PrimBounds& p : prims) max_abs = lvl::grow_max_abs(max_abs, p.lo, p.hi);
+    return lvl::padding_of(max_abs);
 }
 
 BuiltBvh build_bvh(const std::vector<PrimBounds>& prims, bool leaves_tested_in_pairs, uint32_t* median_splits) {
@@ -751,6 +751,75 @@ BuiltBvh build_bvh_levelwise(const std::vector<PrimBounds>& prims, bool leaves_t
     st.levels = levels;
     if (stats) *stats = st;
     return out;
+}
+
+// ---------------------------------------------------------------------------------------------------------------- refit
+namespace {
+
+// the primitives' bounds by leaf-order position, as lvl::refit_leaf_box reads them
+struct OrderedBounds {
+    const std::vector<PrimBounds>& prims;
+    const std::vector<uint32_t>& order;
+    size_t first_of_kind[4] = {0, 0, 0, 0}; // where a kind's index 0 sits in `prims` (pack order: each kind by index)
+    OrderedBounds(const std::vector<PrimBounds>& p, const std::vector<uint32_t>& o) : prims(p), order(o) {
+        bool seen[4] = {false, false, false, false};
+        for (size_t i = 0; i < p.size(); ++i) {
+            const uint32_t kind = p[i].shape >> 30;
+            if (!seen[kind]) seen[kind] = true, first_of_kind[kind] = i - (p[i].shape & 0x3FFFFFFFu);
+        }
+    }
+    const PrimBounds& at(uint32_t i) const { return prims[first_of_kind[order[i] >> 30] + (order[i] & 0x3FFFFFFFu)]; }
+    void get(uint32_t i, float* lo, float* hi) const {
+        const PrimBounds& b = at(i);
+        for (int a = 0; a < 3; ++a) lo[a] = b.lo[a], hi[a] = b.hi[a];
+    }
+};
+
+template <class Node>
+RefitSchedule schedule_of(const Node* nodes, size_t count, int slots) {
+    RefitSchedule s;
+    std::vector<uint32_t> height(count, 0);
+    uint32_t top = 0;
+    for (size_t n = count; n-- > 0;) { // a child's index is larger than its parent's in both trees
+        height[n] = lvl::refit_height(nodes[n], slots, height.data());
+        top = std::max(top, height[n]);
+    }
+    s.begin.assign(count ? top + 2 : 1, 0);
+    for (size_t n = 0; n < count; ++n) s.begin[height[n] + 1]++;
+    for (size_t h = 1; h < s.begin.size(); ++h) s.begin[h] += s.begin[h - 1];
+    s.order.resize(count);
+    std::vector<uint32_t> cursor(s.begin.begin(), s.begin.end());
+    for (size_t n = 0; n < count; ++n) s.order[cursor[height[n]]++] = (uint32_t)n;
+    return s;
+}
+
+template <class Node>
+void refit_nodes(std::vector<Node>& nodes, int slots, const OrderedBounds& bounds, float pad) {
+    const RefitSchedule s = schedule_of(nodes.data(), nodes.size(), slots);
+    for (const uint32_t n : s.order) lvl::refit_node(nodes[n], slots, nodes.data(), bounds, pad);
+}
+
+} // namespace
+
+RefitSchedule refit_schedule(const Node64* nodes, size_t count) { return schedule_of(nodes, count, 2); }
+RefitSchedule refit_schedule(const Node128* nodes, size_t count) { return schedule_of(nodes, count, 4); }
+
+void refit_bvh(BuiltBvh& bvh, const std::vector<PrimBounds>& prims) { refit_nodes(bvh.nodes, 2, OrderedBounds(prims, bvh.prim_order), bvh_padding(prims)); }
+
+void refit_wide(WideBvh& wide, const BuiltBvh& bvh, const std::vector<PrimBounds>& prims) {
+    refit_nodes(wide.nodes, 4, OrderedBounds(prims, bvh.prim_order), bvh_padding(prims));
+}
+
+double child_area_sum(const Node64* nodes, size_t count) {
+    double sum = 0.0;
+    for (size_t n = 0; n < count; ++n)
+        for (int k = 0; k < 2; ++k) {
+            lvl::Box3 b;
+            b.lo[0] = nodes[n].lo_x[k], b.lo[1] = nodes[n].lo_y[k], b.lo[2] = nodes[n].lo_z[k];
+            b.hi[0] = nodes[n].hi_x[k], b.hi[1] = nodes[n].hi_y[k], b.hi[2] = nodes[n].hi_z[k];
+            sum += (double)lvl::half_area(b);
+        }
+    return sum;
 }
 
 uint64_t tree_digest(const BuiltBvh& bvh) {

@@ -10,6 +10,7 @@
 #pragma once
 #include <cstdint>
 #include <climits>
+#include <cstddef>
 #include <vector>
 
 #include "bvh_level.h"
@@ -135,5 +136,24 @@ WideBvh collapse_to_wide_sah(const BuiltBvh& bvh);
 // PYRITE_WIDE_COLLAPSE (read at scene creation): "greedy" collapses the pair tree by the greedy rule (A/B); anything else,
 // or unset, by cost
 bool cost_driven_collapse_wanted();
+
+// ---- refit: new boxes for a tree whose topology, prim_order and leaf sizes stay. `prims` are the scene's
+// primitives in pack order (spheres, then triangles, each kind by index: what the tree was built from), with their new bounds.
+// Sequential rehearsals of kernels/refit.hip on bvh_level.h's refit rules: a leaf's box is the exact box of its primitives,
+// padded by bvh_padding(prims); an inner child's the union of that child's stored boxes. With unchanged bounds the nodes come
+// out byte for byte as the builder stored them. Not for trees with spatial splits, whose leaves hold clipped boxes.
+void refit_bvh(BuiltBvh& bvh, const std::vector<PrimBounds>& prims);
+// The four-child tree collapsed from `bvh` (its leaf codes index bvh.prim_order), likewise.
+void refit_wide(WideBvh& wide, const BuiltBvh& bvh, const std::vector<PrimBounds>& prims);
+// The order a refit visits a tree's nodes in: grouped by height (lvl::refit_height), nodes whose children are all leaves first.
+// order[begin[h] .. begin[h + 1]) are the nodes of height h; a node's inner children all have smaller heights.
+struct RefitSchedule {
+    std::vector<uint32_t> order, begin;
+};
+RefitSchedule refit_schedule(const Node64* nodes, size_t count);
+RefitSchedule refit_schedule(const Node128* nodes, size_t count);
+// Sum of lvl::half_area over every stored child box of the binary tree, in f64 in node order: the SAH's measure of what a
+// refit has done to the tree (PyrUpdateInfo::area_ratio is this now over this at the last build).
+double child_area_sum(const Node64* nodes, size_t count);
 
 } // namespace pyr

@@ -231,5 +231,87 @@ PYR_HD void empty_keys(uint32_t* k) {
     for (int a = 0; a < 3; ++a) k[a] = kKeyPosInf, k[3 + a] = kKeyNegInf;
 }
 
+// ---------------------------------------------------------------------------------------------------------------- refit
+// The rules of a refit: the boxes of a tree whose topology stays, from primitives that moved. The host
+// rehearsal (refit_bvh / refit_wide, bvh.cpp) and the device kernels (kernels/refit.hip) call these and nothing else, and scene
+// creation takes its primitive bounds, its padding and a stored box's padding from here too.
+
+// Bounded::aabb of a triangle [3][3] and of a sphere (centre, radius), as std::min / std::max nest them at scene creation
+PYR_HD void triangle_bounds(const float* p, float* lo, float* hi) {
+    for (int a = 0; a < 3; ++a) {
+        const float l = p[6 + a] < p[3 + a] ? p[6 + a] : p[3 + a], h = p[3 + a] < p[6 + a] ? p[6 + a] : p[3 + a];
+        lo[a] = l < p[a] ? l : p[a];
+        hi[a] = p[a] < h ? h : p[a];
+    }
+}
+PYR_HD void sphere_bounds(const float* s, float* lo, float* hi) {
+    for (int a = 0; a < 3; ++a) lo[a] = s[a] - s[3], hi[a] = s[a] + s[3];
+}
+// the largest coordinate of a set of boxes, one box at a time (never negative, so its bits order like the floats do)
+PYR_HD float grow_max_abs(float m, const float* lo, const float* hi) {
+    for (int a = 0; a < 3; ++a) {
+        const float l = lo[a] < 0.0f ? -lo[a] : lo[a], h = hi[a] < 0.0f ? -hi[a] : hi[a];
+        const float w = l < h ? h : l;
+        m = m < w ? w : m;
+    }
+    return m;
+}
+// the padding of every stored box: 16 ulps of the largest coordinate (bvh.cpp bvh_padding says why)
+PYR_HD float padding_of(float max_abs) { return 16.0f * 1.1920929e-7f * max_abs; }
+// a stored box: the exact box moved outward by the padding. x - pad and x + pad are monotone in x, so the union of padded boxes
+// is the padded union, bit for bit
+PYR_HD Box3 padded(const Box3& b, float pad) {
+    Box3 r;
+    for (int a = 0; a < 3; ++a) r.lo[a] = b.lo[a] - pad, r.hi[a] = b.hi[a] + pad;
+    return r;
+}
+// a leaf's stored box: the exact min / max of its primitives' bounds, padded. `bounds.get(i, lo, hi)`: the bounds of the
+// primitive at leaf-order position i
+template <class Bounds>
+PYR_HD Box3 refit_leaf_box(const Bounds& bounds, uint32_t first, uint32_t count, float pad) {
+    Box3 b = empty_box();
+    for (uint32_t i = 0; i < count; ++i) {
+        float lo[3], hi[3];
+        bounds.get(first + i, lo, hi);
+        grow(b, lo, hi);
+    }
+    return padded(b, pad);
+}
+constexpr int32_t kNoChild = -2147483647 - 1; // bvh.h kEmptyChild: a slot of a four-child node that holds nothing (its box is NaN)
+PYR_HD uint32_t leaf_first(int32_t code) { return (uint32_t)(-1 - code) >> 3; }
+PYR_HD uint32_t leaf_count(int32_t code) { return (uint32_t)(-1 - code) & 7u; }
+// an inner child's stored box: the union of the boxes that child stores (Node64: two slots, Node128: four). An empty slot of a
+// four-child node is skipped; an empty leaf of a two-child node holds the empty box, which grows nothing
+template <class Node>
+PYR_HD Box3 refit_inner_box(const Node& child, int slots) {
+    Box3 b = empty_box();
+    for (int k = 0; k < slots; ++k) {
+        if (child.child[k] == kNoChild) continue;
+        const float lo[3] = {child.lo_x[k], child.lo_y[k], child.lo_z[k]}, hi[3] = {child.hi_x[k], child.hi_y[k], child.hi_z[k]};
+        grow(b, lo, hi);
+    }
+    return b;
+}
+// One node of a refit: every slot's box anew -- a leaf's from the primitives, an inner child's from that child's node, which a
+// bottom-up order has finished already. Empty slots and empty leaves keep their boxes.
+template <class Node, class Bounds>
+PYR_HD void refit_node(Node& node, int slots, const Node* nodes, const Bounds& bounds, float pad) {
+    for (int k = 0; k < slots; ++k) {
+        const int32_t code = node.child[k];
+        if (code == kNoChild || (code < 0 && leaf_count(code) == 0)) continue;
+        const Box3 b = code >= 0 ? refit_inner_box(nodes[code], slots) : refit_leaf_box(bounds, leaf_first(code), leaf_count(code), pad);
+        node.lo_x[k] = b.lo[0], node.lo_y[k] = b.lo[1], node.lo_z[k] = b.lo[2];
+        node.hi_x[k] = b.hi[0], node.hi_y[k] = b.hi[1], node.hi_z[k] = b.hi[2];
+    }
+}
+// a node's height in the refit schedule: 0 when every child is a leaf, else one more than its highest inner child's
+template <class Node>
+PYR_HD uint32_t refit_height(const Node& node, int slots, const uint32_t* heights) {
+    uint32_t h = 0;
+    for (int k = 0; k < slots; ++k)
+        if (node.child[k] >= 0 && heights[node.child[k]] + 1 > h) h = heights[node.child[k]] + 1;
+    return h;
+}
+
 } // namespace lvl
 } // namespace pyr

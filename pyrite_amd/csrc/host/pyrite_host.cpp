@@ -940,6 +940,19 @@ void FlatScene::add_world(const WorldProject& world, const std::string& base_dir
     }
 }
 
+void FlatScene::move_geometry(const std::vector<float>& positions, const std::vector<float>& normals, const std::vector<float>& frames, const std::vector<float>& spheres) {
+    Impl& S = *impl_;
+    auto move = [](std::vector<float>& kept, const std::vector<float>& given, size_t floats, const char* what) {
+        if (given.empty()) return;
+        if (given.size() != floats) throw ProjectError(std::string("update: ") + what + " must hold the scene's own count");
+        kept = given;
+    };
+    move(S.tri_positions, positions, 9 * S.tri_material.size(), "positions");
+    move(S.tri_normals, normals, 9 * S.tri_material.size(), "normals");
+    move(S.tri_frames, frames, 12 * S.tri_material.size(), "frames");
+    move(S.spheres, spheres, 4 * S.sphere_material.size(), "spheres");
+}
+
 const PyrSceneDesc& FlatScene::desc() {
     Impl& S = *impl_;
     PyrSceneDesc& d = S.desc;
@@ -1063,6 +1076,28 @@ PyrScene* World::scene(int device, int copy, std::optional<Build> build) {
 PyrBuildInfo World::build_info(int device, int copy) {
     PyrBuildInfo info{};
     check_status(pyr_scene_build_info(scene(device, copy), &info));
+    return info;
+}
+void World::update(const std::vector<float>& positions, const std::vector<float>& normals, const std::vector<float>& frames, const std::vector<float>& spheres, Update mode,
+                   int device) {
+    PyrScene* handle = scene(device);
+    const PyrSceneDesc& d = flat_.desc();
+    if ((!positions.empty() && positions.size() != 9 * (size_t)d.num_triangles) || (!normals.empty() && normals.size() != 9 * (size_t)d.num_triangles) ||
+        (!frames.empty() && frames.size() != 12 * (size_t)d.num_triangles) || (!spheres.empty() && spheres.size() != 4 * (size_t)d.num_spheres))
+        throw ProjectError("update: an array does not hold the scene's own count");
+    PyrGeometryUpdate u{};
+    u.mode = mode == Update::Rebuild ? PYR_UPDATE_REBUILD : PYR_UPDATE_REFIT;
+    u.num_triangles = d.num_triangles, u.num_spheres = d.num_spheres;
+    u.tri_positions = positions.empty() ? nullptr : positions.data();
+    u.tri_normals = normals.empty() ? nullptr : normals.data();
+    u.tri_frames = frames.empty() || !d.tri_frames ? nullptr : frames.data(); // (the description passes frames only for normal maps)
+    u.spheres = spheres.empty() ? nullptr : spheres.data();
+    check_status(pyr_scene_update(handle, &u));
+    flat_.move_geometry(positions, normals, frames, spheres);
+}
+PyrUpdateInfo World::update_info(int device) {
+    PyrUpdateInfo info{};
+    check_status(pyr_scene_update_info(scene(device), &info));
     return info;
 }
 

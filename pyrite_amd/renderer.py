@@ -69,6 +69,62 @@ class World:
         check(lib().pyr_scene_bvh_info(self.scene(device), C.byref(info)))
         return {name: int(getattr(info, name)) for name, _ in info._fields_}
 
+    UPDATE_MODES = {"refit": abi.PYR_UPDATE_REFIT, "rebuild": abi.PYR_UPDATE_REBUILD}
+
+    def update(self, positions=None, normals=None, frames=None, spheres=None, mode="refit", device=0, stream=0):
+        """Moves the geometry of the scene on `device` (pyr_scene_update): new `positions` [n,3,3], `normals` [n,3,3], `frames`
+        [n,3,4] for the same triangles and `spheres` [n,4] for the same spheres; what is None stays. mode="refit" keeps the
+        tree's topology and recomputes every box; "rebuild" builds a new tree with the scene's builder. Arrays that are torch
+        tensors on the GPU go through pyr_scene_update_device on `stream` (all of them must be, then); anything else is taken
+        as host data. `World.flat` and the description follow, so a scene created later elsewhere is the moved one."""
+        if mode not in self.UPDATE_MODES:
+            raise ValueError("mode must be 'refit' or 'rebuild', not %r" % (mode,))
+        given = {"positions": (positions, 9), "normals": (normals, 9), "frames": (frames, 12), "spheres": (spheres, 4)}
+        on_device = [a is not None and hasattr(a, "data_ptr") and getattr(a, "is_cuda", False) for a, _ in given.values()]
+        some = [a is not None for a, _ in given.values()]
+        if any(on_device) and on_device != some:
+            raise ValueError("the arrays of one update are all host arrays or all device tensors")
+        u = abi.PyrGeometryUpdate(mode=self.UPDATE_MODES[mode], num_triangles=self._desc.num_triangles, num_spheres=self._desc.num_spheres)
+        host, keep = {}, []
+        for name, (a, width) in given.items():
+            if a is None:
+                continue
+            count = self._desc.num_spheres if name == "spheres" else self._desc.num_triangles
+            if any(on_device):
+                import torch
+
+                t = a.to(torch.float32).contiguous()
+                if t.numel() != count * width:
+                    raise ValueError("%s holds %d floats, the scene needs %d" % (name, t.numel(), count * width))
+                keep.append(t)
+                host[name] = t.detach().cpu().numpy().reshape(count, width)
+                pointer = t.data_ptr()
+            else:
+                h = np.ascontiguousarray(a, dtype=np.float32)
+                if h.size != count * width:
+                    raise ValueError("%s holds %d floats, the scene needs %d" % (name, h.size, count * width))
+                host[name] = h.reshape(count, width)
+                pointer = host[name].ctypes.data
+            if name == "frames" and not self.flat.uses_normal_maps:
+                continue  # the description passes frames only for normal maps (FlatScene.desc): the device keeps none to move
+            setattr(u, {"positions": "tri_positions", "normals": "tri_normals", "frames": "tri_frames", "spheres": "spheres"}[name], pointer)
+        if any(on_device):
+            check(lib().pyr_scene_update_device(self.scene(device), C.byref(u), C.c_void_p(int(stream))))
+        else:
+            check(lib().pyr_scene_update(self.scene(device), C.byref(u)))
+        del keep
+        for name, attr in (("positions", "tri_positions"), ("normals", "tri_normals"), ("frames", "tri_frames"), ("spheres", "spheres")):
+            if name in host:
+                setattr(self.flat, attr, [host[name].copy()])
+        self._desc = self.flat.desc()
+
+    def update_info(self, device=0):
+        """pyr_scene_update_info as a dict: the last update's mode, schedule length, updates since the last build, stage times in
+        milliseconds, and area_ratio -- the binary tree's summed child box areas now over those at the last build."""
+        info = abi.PyrUpdateInfo()
+        check(lib().pyr_scene_update_info(self.scene(device), C.byref(info)))
+        return {name: getattr(info, name) for name, _ in info._fields_ if name != "reserved"}
+
     def intersect(self, rays, device=0, want_counters=False):
         """World::intersect (world.rs:273-299) for float32 rays [n,6] -> (structured hits, kernel ms, counters|None)."""
         rays = np.ascontiguousarray(rays, dtype=np.float32).reshape(-1, 6)

@@ -1,0 +1,337 @@
+"""Moving a live scene's geometry (pyr_scene_update) -- run with `-m gpu` on an MI355X.
+
+A refit with the scene's own arrays changes nothing a ray can see; a refit to moved arrays answers like a scene created from them
+(distances bit for bit, shapes up to proven ties); a rebuild IS that scene (digest, PyrBvhInfo, hits, traversal counters); films of
+refitted scenes match the oracle's render of a world created from the moved description; refused updates leave the scene alone."""
+import os
+import subprocess
+import sys
+
+import numpy as np
+import pytest
+
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import bvh_build_inputs as inputs  # noqa: E402
+import oracle  # noqa: E402
+from test_gpu_bvh_build import assert_shapes_equal_up_to_ties, rays_into, world_of  # noqa: E402
+from test_gpu_parity import TOL, assert_parity, rel_l2  # noqa: E402
+
+from pyrite_amd import abi, scenes  # noqa: E402
+from pyrite_amd._lib import PyriteGpuError  # noqa: E402
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+FIELDS = ("distance", "shape", "u", "v")
+MOVED_INPUTS = ("mixed", "tri65", "sliver_mesh")
+
+
+def same_bits(a, b, fields=FIELDS):
+    return all(np.array_equal(a[f].view(np.uint32), b[f].view(np.uint32)) for f in fields)
+
+
+def counts_of(counters):
+    return counters["box_tests"], counters["triangle_tests"], counters["sphere_tests"]
+
+
+def normals_of(tris):
+    t = tris.reshape(-1, 3, 3)
+    n = np.cross(t[:, 1] - t[:, 0], t[:, 2] - t[:, 0])
+    n /= np.maximum(np.linalg.norm(n, axis=1, keepdims=True), 1e-30)
+    return np.repeat(n[:, None, :], 3, axis=1).astype(np.float32)
+
+
+def rotation(axis, angle):
+    axis = np.asarray(axis, dtype=np.float64) / np.linalg.norm(axis)
+    k = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+    return np.eye(3) + np.sin(angle) * k + (1 - np.cos(angle)) * (k @ k)
+
+
+def moved(spheres, tris, move):
+    """"rigid": a rotation plus a translation of everything; "shaken": every vertex and centre displaced by up to a tenth of the extent, seeded."""
+    points = np.concatenate([tris.reshape(-1, 3), spheres[:, :3]]).astype(np.float64)
+    if move == "rigid":
+        r, t = rotation((1, 2, 3), 0.7), np.array([1.5, -0.75, 2.25])
+        new_tris = (tris.reshape(-1, 3).astype(np.float64) @ r.T + t).astype(np.float32).reshape(-1, 9)
+        new_spheres = spheres.copy()
+        new_spheres[:, :3] = (spheres[:, :3].astype(np.float64) @ r.T + t).astype(np.float32)
+        return new_spheres, new_tris
+    rng = np.random.RandomState(77)
+    amplitude = 0.1 * float((points.max(axis=0) - points.min(axis=0)).max())
+    new_spheres = spheres.copy()
+    new_spheres[:, :3] += rng.uniform(-amplitude, amplitude, size=(len(spheres), 3)).astype(np.float32)
+    return new_spheres, (tris + rng.uniform(-amplitude, amplitude, size=tris.shape).astype(np.float32)).astype(np.float32)
+
+
+def aimed_rays(spheres, tris, n, seed=3):
+    """rays_for's set and as many rays aimed at primitives from points around them, so that small inputs are hit often too."""
+    centres = np.concatenate([tris.reshape(-1, 3, 3).mean(axis=1), spheres[:, :3]]).astype(np.float64)
+    rng = np.random.RandomState(seed)
+    target = centres[rng.randint(len(centres), size=n // 2)]
+    origin = target + rng.normal(size=target.shape) * 6.0
+    d = target - origin
+    d /= np.linalg.norm(d, axis=1, keepdims=True)
+    return np.concatenate([rays_into(spheres, tris, n - n // 2), np.concatenate([origin, d], axis=1).astype(np.float32)])
+
+
+def update_world(world, spheres, tris, mode="refit", form="host"):
+    args = {}
+    if len(tris):
+        args["positions"], args["normals"] = tris, normals_of(tris)
+    if len(spheres):
+        args["spheres"] = spheres
+    if form == "device":
+        import torch
+
+        args = {k: torch.from_numpy(np.ascontiguousarray(v, dtype=np.float32)).to("cuda:0") for k, v in args.items()}
+    world.update(mode=mode, **args)
+
+
+# ---------------------------------------------------------------------------------------------------------------- 1. identity
+@pytest.mark.parametrize("form", ["host", "device"])
+@pytest.mark.parametrize("name", sorted(inputs.TIE_FREE))
+def test_a_refit_with_the_scenes_own_arrays_changes_nothing(gpu_lib, name, form):
+    """Single-leaf and LDS-resident binary trees, spheres, a mix, and sliver_mesh's wide and pair trees over several levels: the
+    boxes a refit computes from unchanged arrays are the boxes creation uploaded, so hits and traversal counts are the same."""
+    spheres, tris = inputs.TIE_FREE[name]()
+    world = world_of(spheres, tris)
+    rays = rays_into(spheres, tris, 20000)
+    h0, _, c0 = world.intersect(rays, want_counters=True)
+    update_world(world, spheres, tris, form=form)
+    h1, _, c1 = world.intersect(rays, want_counters=True)
+    assert same_bits(h0, h1)
+    assert counts_of(c0) == counts_of(c1)
+    info = world.update_info()
+    assert info["mode_used"] == abi.PYR_UPDATE_REFIT and info["updates"] == 1 and info["area_ratio"] == 1.0
+    update_world(world, spheres, tris, form=form)  # and once more: the same bytes again
+    h2, _, c2 = world.intersect(rays, want_counters=True)
+    assert same_bits(h0, h2) and counts_of(c0) == counts_of(c2) and world.update_info()["updates"] == 2
+    world.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------- 2. moved, refit
+@pytest.mark.parametrize("move", ["rigid", "shaken"])
+@pytest.mark.parametrize("name", MOVED_INPUTS)
+def test_a_refitted_scene_answers_like_a_scene_created_from_the_moved_arrays(gpu_lib, name, move):
+    spheres, tris = inputs.TIE_FREE[name]()
+    new_spheres, new_tris = moved(spheres, tris, move)
+    a, b = world_of(spheres, tris), world_of(new_spheres, new_tris)
+    old_rays = rays_into(spheres, tris, 20000)
+    h_old, _, c_old = a.intersect(old_rays, want_counters=True)
+    before = a.bvh_info()
+    update_world(a, new_spheres, new_tris)
+    assert a.bvh_info() == before  # topology, counts and sizes are the last build's
+    rays = aimed_rays(new_spheres, new_tris, 20000)
+    ha, _, _ = a.intersect(rays)
+    hb, _, _ = b.intersect(rays)
+    print("%s %s: %d rays hit, %d shapes differ, area_ratio %.4g" % (name, move, (hb["shape"] != 0xFFFFFFFF).sum(), (ha["shape"] != hb["shape"]).sum(), a.update_info()["area_ratio"]))
+    assert np.array_equal(ha["distance"].view(np.uint32), hb["distance"].view(np.uint32))
+    assert (hb["shape"] != 0xFFFFFFFF).sum() > 1000
+    assert_shapes_equal_up_to_ties(b, hb, ha, rays)
+    ratio = a.update_info()["area_ratio"]
+    assert np.isfinite(ratio) and ratio > 0.0
+    # and back: the scene creation made
+    update_world(a, spheres, tris)
+    h_back, _, c_back = a.intersect(old_rays, want_counters=True)
+    assert same_bits(h_old, h_back) and counts_of(c_old) == counts_of(c_back)
+    assert a.update_info()["area_ratio"] == 1.0
+    a.close(), b.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------- 3. moved, rebuild
+@pytest.mark.parametrize("build", ["host", "device"])
+@pytest.mark.parametrize("move", ["rigid", "shaken"])
+@pytest.mark.parametrize("name", MOVED_INPUTS)
+def test_a_rebuilt_scene_is_the_scene_created_from_the_moved_arrays(gpu_lib, name, move, build):
+    spheres, tris = inputs.TIE_FREE[name]()
+    new_spheres, new_tris = moved(spheres, tris, move)
+    a, b = world_of(spheres, tris), world_of(new_spheres, new_tris)
+    a.scene(0, build=build), b.scene(0, build=build)
+    update_world(a, new_spheres, new_tris, mode="rebuild")
+    ia, ib = a.build_info(), b.build_info()
+    for key in ("builder_asked", "builder_used", "fallback_reason", "levels", "median_splits", "tree_digest"):
+        assert ia[key] == ib[key], key
+    assert a.bvh_info() == b.bvh_info()
+    rays = aimed_rays(new_spheres, new_tris, 20000)
+    ha, _, ca = a.intersect(rays, want_counters=True)
+    hb, _, cb = b.intersect(rays, want_counters=True)
+    assert same_bits(ha, hb) and counts_of(ca) == counts_of(cb)  # the same builder on the same arrays: the same tree, ties included
+    assert (hb["shape"] != 0xFFFFFFFF).sum() > 1000
+    info = a.update_info()
+    assert info["mode_used"] == abi.PYR_UPDATE_REBUILD and info["updates"] == 0 and info["area_ratio"] == 1.0
+    a.close(), b.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------- 4. films
+def flat_arrays(world):
+    f = world.flat
+    cat = lambda rows, width: np.concatenate([np.asarray(r, dtype=np.float32).reshape(-1, width) for r in rows]) if len(rows) else np.zeros((0, width), dtype=np.float32)  # noqa: E731
+    return {"positions": cat(f.tri_positions, 9), "normals": cat(f.tri_normals, 9), "frames": cat(f.tri_frames, 12), "spheres": cat(f.spheres, 4)}
+
+
+def rotate_triangles(arrays, which, axis, angle, with_frames=False):
+    """The triangles `which` rotated about their common centre: positions, normals and (asked for) the tangent frames, quaternions (s, x, y, z)."""
+    r = rotation(axis, angle)
+    p = arrays["positions"].reshape(-1, 3, 3).astype(np.float64)
+    n = arrays["normals"].reshape(-1, 3, 3).astype(np.float64)
+    centre = p[which].reshape(-1, 3).mean(axis=0)
+    p[which] = (p[which] - centre) @ r.T + centre
+    n[which] = n[which] @ r.T
+    out = {"positions": p.astype(np.float32).reshape(-1, 9), "normals": n.astype(np.float32).reshape(-1, 9)}
+    if with_frames:
+        ax = np.asarray(axis, dtype=np.float64) / np.linalg.norm(axis)
+        q = np.concatenate([[np.cos(angle / 2)], np.sin(angle / 2) * ax])
+        f = arrays["frames"].reshape(-1, 3, 4).astype(np.float64)
+        s, v = f[which][..., :1], f[which][..., 1:]
+        f[which] = np.concatenate([q[0] * s - (v * q[1:]).sum(-1, keepdims=True), q[0] * v + s * q[1:] + np.cross(np.broadcast_to(q[1:], v.shape), v)], axis=-1)
+        out["frames"] = f.astype(np.float32).reshape(-1, 12)
+    return out
+
+
+def cornell_short_box(arrays, world):
+    p = arrays["positions"].reshape(-1, 3, 3)
+    which = np.arange(12, 24)
+    assert len(p) == 36 and p[which][..., 2].max() == np.float32(1.65) and p[which][..., 0].min() == np.float32(-2.9)  # the short box of cornell_box.obj
+    return rotate_triangles(arrays, which, (0, 0, 1), 0.5)
+
+
+def cornell_light_lowered(arrays, world):
+    lamp = [l["shape_index"] for l in world.flat.lamps]
+    assert len(lamp) == 2
+    p = arrays["positions"].reshape(-1, 3, 3).copy()
+    p[lamp, :, 2] -= np.float32(1.25)
+    return {"positions": p.reshape(-1, 9)}
+
+
+def spheres_moved(arrays, world):
+    s = arrays["spheres"].copy()
+    assert len(s) == 8 and world.flat.lamps[0]["shape_index"] == 7
+    s[5, :3] += np.float32([0.6, -0.5, 0.3])
+    s[6, :3] += np.float32([-0.7, 0.4, 0.5])
+    s[7, :3] += np.float32([0.8, 0.3, -0.9])  # the lamp sphere
+    return {"spheres": s}
+
+
+def knot_rotated(arrays, world):
+    n = len(arrays["positions"])
+    assert n == 12 + 24 * 16 * 2
+    return rotate_triangles(arrays, np.arange(12, n), (1, 1, 0.5), 0.6)
+
+
+def cube_rotated(arrays, world):
+    assert world.flat.uses_normal_maps and len(arrays["positions"]) >= 1
+    return rotate_triangles(arrays, np.arange(len(arrays["positions"])), (0.2, 0.3, 1.0), 0.4, with_frames=True)
+
+
+FILM_CASES = {
+    "cornell_short_box_rotated": (lambda: scenes.c2_cornell(64, 64, 16), cornell_short_box),
+    "cornell_light_lowered": (lambda: scenes.c2_cornell(64, 64, 16), cornell_light_lowered),
+    "c1_spheres_and_lamp_moved": (lambda: scenes.c1_spheres(64, 64, 16), spheres_moved),
+    "c3_knot_rotated": (lambda: scenes.c3_mesh_in_box(64, 36, 8, segments=24, sides=16), knot_rotated),
+    "textures_cube_rotated": (lambda: scenes.textures_example(64, 48, 8), cube_rotated),
+}
+
+
+@pytest.mark.parametrize("name", sorted(FILM_CASES))
+def test_films_of_refitted_scenes_match_the_oracle(gpu_lib, name):
+    """The oracle renders a world created from the moved description; the GPU renders the scene created from the old one and
+    refitted. Weights exact, every pixel within TOL, path counters equal."""
+    make, mover = FILM_CASES[name]
+    world, cam, r, gfilm = scenes.build(make(), seed=5)
+    arrays = flat_arrays(world)
+    new = mover(arrays, world)
+    fresh, _, _, _ = scenes.build(make(), seed=5)  # the moved description, never on the GPU
+    for key, attr in (("positions", "tri_positions"), ("normals", "tri_normals"), ("frames", "tri_frames"), ("spheres", "spheres")):
+        if key in new:
+            setattr(fresh.flat, attr, [new[key].copy()])
+    fresh._desc = fresh.flat.desc()
+    cfilm = r.new_film(gfilm.width, gfilm.height)
+    ccount = oracle.OracleScene(fresh).render(r, cam, cfilm, threads=8)
+    world.scene(0)
+    if name == "c3_knot_rotated":
+        assert world.bvh_info()["num_pair_records"] > 0  # the pair tree
+    world.update(mode="refit", **new)
+    gcount = r.render(gfilm, cam, world, counters=True)
+    assert_parity(gfilm, cfilm)
+    for key in ("samples", "extension_rays", "shadow_rays", "shaded_hits", "exposures"):
+        assert gcount[key] == ccount[key], key
+    assert cfilm.grains[..., 1].sum() > 0
+    world.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------- 5. refusals
+def test_an_update_under_a_live_session_is_refused_and_the_session_goes_on(gpu_lib):
+    films = []
+    for disturb in (False, True):
+        world, cam, r, film = scenes.build(scenes.c2_cornell(48, 48, 8), seed=3)
+        with r.session((48, 48), cam, world) as session:
+            session.render(4)
+            if disturb:
+                new = cornell_short_box(flat_arrays(world), world)
+                with pytest.raises(PyriteGpuError) as err:
+                    world.update(mode="refit", **new)
+                assert err.value.status == abi.PYR_ERR_INVALID_ARGUMENT and "PyrSession" in str(err.value)
+                with pytest.raises(PyriteGpuError):
+                    world.update(mode="rebuild", **new)
+            session.render(4)
+            session.sync()
+            films.append(session.film())
+        if disturb:  # the session is gone: the update goes through now
+            world.update(mode="refit", **cornell_short_box(flat_arrays(world), world))
+        world.close()
+    assert np.array_equal(films[0].grains[..., 1], films[1].grains[..., 1]) and films[0].grains[..., 1].sum() > 0
+    assert float(rel_l2(films[1], films[0]).max()) <= TOL
+
+
+@pytest.mark.parametrize("mode", ["refit", "rebuild"])
+def test_a_coordinate_beyond_the_range_is_refused_and_the_scene_stays(gpu_lib, mode):
+    spheres, tris = inputs.TIE_FREE["mixed"]()
+    world = world_of(spheres, tris)
+    rays = rays_into(spheres, tris, 20000)
+    h0, _, c0 = world.intersect(rays, want_counters=True)
+    build = world.build_info()
+    for bad_spheres, bad_tris in ((spheres, np.where(np.arange(tris.size).reshape(tris.shape) == 1234, np.float32(1e16), tris)),
+                                  (np.where(np.arange(spheres.size).reshape(spheres.shape) == 9, np.float32(-1e16), spheres), tris)):
+        with pytest.raises(PyriteGpuError) as err:
+            update_world(world, bad_spheres.astype(np.float32), bad_tris.astype(np.float32), mode=mode)
+        assert err.value.status == abi.PYR_ERR_UNSUPPORTED and "1e15" in str(err.value)
+    h1, _, c1 = world.intersect(rays, want_counters=True)
+    assert same_bits(h0, h1) and counts_of(c0) == counts_of(c1)
+    assert world.build_info() == build and world.update_info()["updates"] == 0
+    got = flat_arrays(world)
+    assert np.array_equal(got["positions"], tris) and np.array_equal(got["spheres"], spheres)  # the description did not move either
+    world.close()
+
+
+CHILD = """
+import sys
+sys.path.insert(0, %r); sys.path.insert(0, %r)
+import numpy as np
+import bvh_build_inputs as inputs
+from test_gpu_bvh_build import world_of, rays_into
+from test_gpu_scene_update import moved, update_world, same_bits
+from pyrite_amd._lib import PyriteGpuError
+spheres, tris = inputs.TIE_FREE["sliver_mesh"]()
+new_spheres, new_tris = moved(spheres, tris, "rigid")
+a, b = world_of(spheres, tris), world_of(new_spheres, new_tris)
+a.scene(0), b.scene(0)
+try:
+    update_world(a, new_spheres, new_tris, mode="refit")
+    print("REFIT went through")
+except PyriteGpuError as e:
+    print("REFIT", e.status)
+update_world(a, new_spheres, new_tris, mode="rebuild")
+rays = rays_into(new_spheres, new_tris, 20000)
+ha, hb = a.intersect(rays)[0], b.intersect(rays)[0]
+print("REBUILD", int(a.build_info()["tree_digest"] == b.build_info()["tree_digest"]), int(a.bvh_info() == b.bvh_info()), int(same_bits(ha, hb)), int((hb["shape"] != 0xFFFFFFFF).sum()))
+"""
+
+
+def test_a_tree_with_spatial_splits_refuses_the_refit_and_takes_the_rebuild(gpu_lib):
+    """PYRITE_SPATIAL_SPLITS is read when a tree is built: a fresh child process, so that nothing else in this one sees it."""
+    run = subprocess.run([sys.executable, "-c", CHILD % (ROOT, os.path.join(ROOT, "tests"))], env=dict(os.environ, PYRITE_SPATIAL_SPLITS="1", PYTHONPATH=ROOT),
+                         capture_output=True, text=True, timeout=300)
+    assert run.returncode == 0, run.stdout + run.stderr
+    lines = run.stdout.splitlines()
+    assert "REFIT %d" % abi.PYR_ERR_UNSUPPORTED in lines, run.stdout
+    rebuilt = [l.split() for l in lines if l.startswith("REBUILD")][0]
+    assert rebuilt[1:4] == ["1", "1", "1"] and int(rebuilt[4]) > 1000, run.stdout
