@@ -353,6 +353,7 @@ struct PyrScene {
     PyrProgramInfo program_info{}; // pyr_scene_program_info; program_info.wide: the kernels are the wide interpreter build (kernels/wide.hip)
     uint32_t* tail_count = nullptr; // device, kFeedBytes: the work-feed cursors of the intersect kernel
     DeviceBuffer tape; // spectral tape of the stage-scheduled kernel (grown on demand, kept between renders)
+    DeviceBuffer start_queue; // the waves' rings of ready sample starts (RenderLaunch::start_queue; scenes without interpreter programs), kept like the tape
     DeviceBuffer tape_overflow; // one word the kernels set when a path outgrew the tape (checked after blocking renders and by pyr_scene_counters)
     // ---- pyr_scene_update: what of the description says where things are, kept on the host (a rebuild packs the geometry from it
     // again, a refit its lamps; the arrays an update leaves out stay as they are here), and the state of the refit
@@ -974,7 +975,7 @@ int check_render_args(PyrScene* scene, const PyrCamera* camera, const PyrFilmDes
 // (C2: 573 vs 300 Msamples/s); the stage scheduler wins when traversal lengths are heavy tailed (C3: 110 vs 91).
 // PYRITE_SCHEDULER=sync|sm overrides; PYRITE_SM_LANES / PYRITE_SM_STEPS tune the stage scheduler.
 
-// The spectral tape ([tape_max_ops][tape_lanes] 8-byte records) and the overflow word, kept on the scene between renders.
+// The spectral tape ([tape_max_ops][tape_lanes] 8-byte records), the queues of ready sample starts and the overflow word, kept on the scene between renders.
 int reserve_tape(PyrScene* scene, RenderLaunch& L, hipStream_t stream) {
     const size_t bytes = (size_t)L.tape_lanes * L.tape_max_ops * sizeof(unsigned long long);
     if (bytes > scene->tape.bytes) {
@@ -984,6 +985,17 @@ int reserve_tape(PyrScene* scene, RenderLaunch& L, hipStream_t stream) {
         if (rc != PYR_OK) return rc;
     }
     L.tape = (unsigned long long*)scene->tape.ptr;
+    if (scene->dev.needs_interpreter == 0) { // a ring of ready starts for every wave the tape has columns for (tape_lanes_bound)
+        L.start_queue_stride = start_queue_words(L.spectrum_samples) * kStartQueueEntries;
+        const size_t queue_bytes = (size_t)(L.tape_lanes / 64u) * L.start_queue_stride * sizeof(uint32_t);
+        if (queue_bytes > scene->start_queue.bytes) {
+            HIP_TRY(hipStreamSynchronize(stream));
+            scene->start_queue.release();
+            int rc = scene->start_queue.alloc(queue_bytes);
+            if (rc != PYR_OK) return rc;
+        }
+        L.start_queue = (uint32_t*)scene->start_queue.ptr;
+    }
     if (!scene->tape_overflow.ptr) {
         int rc = scene->tape_overflow.alloc(sizeof(uint32_t));
         if (rc != PYR_OK) return rc;

@@ -180,7 +180,10 @@ struct RenderLaunch {
     // The launch renders the tiles tile_begin + k * tile_stride (k = 0 .. tile_count - 1) of the raster grid. A chunk is 64
     // consecutive iterations of one tile; every tile owns chunks_per_tile chunk numbers (the count a full tile_size^2 tile
     // needs: tiles cut by the image border leave their last ones empty), so chunk c belongs to the launch's tile
-    // c / chunks_per_tile. [chunk_begin, chunk_end) is the range this launch renders (progress slices cut it).
+    // c / chunks_per_tile. [chunk_begin, chunk_end) is the range this launch renders (progress slices cut it). Wave w of the
+    // persistent grid takes the chunks chunk_begin + w, + total_waves, ...: the stage scheduler's builds without interpreter programs
+    // start a chunk's 64 samples at once, at full width, into the wave's start_queue and any lane of the wave may render them; in every
+    // other build lane l of the wave renders iteration 64 * within + l of each of those chunks.
     uint32_t tile_begin, tile_stride, tile_count;
     uint32_t chunks_per_tile;
     uint32_t chunk_begin, chunk_end;
@@ -201,7 +204,21 @@ struct RenderLaunch {
     uint32_t* tape_overflow; // device word, set when a path wanted to append more than tape_max_ops records
     uint32_t tape_programs_lds; // programs whose prepared form the kernel keeps in LDS for the replay (set by launch_render; 0 = none)
     uint32_t sample_begin; // first sample of every pixel's budget this launch renders (PyrRenderParams::sample_begin); only locate_chunk reads it
+    // Ready sample starts of the stage scheduler's builds without interpreter programs (kernels.hip Walker::expose_and_restart): one
+    // slab of start_queue_stride words per wave of the persistent grid (tape_lanes / 64 of them), a ring laid out
+    // [start_queue_words][kStartQueueEntries]. Empty at the start and at the end of every launch.
+    uint32_t* start_queue;
+    uint32_t start_queue_stride;
 };
+
+// PYR_SAMPLE_QUEUE=0 builds (A/B, tools/ab.sh) start every sample in the lane that renders it, as the interpreter builds do.
+#ifndef PYR_SAMPLE_QUEUE
+#define PYR_SAMPLE_QUEUE 1
+#endif
+// A ready start: the RNG state behind the start's draws (4 words), the film pixel, the camera ray (6), the S - 1 companion
+// wavelengths and the hero wavelength. A wave fills at most 64 entries, and only while fewer than 64 are ready.
+constexpr uint32_t kStartQueueEntries = 128, kStartQueueFixedWords = 11;
+constexpr uint32_t start_queue_words(uint32_t spectrum_samples) { return kStartQueueFixedWords + spectrum_samples; }
 
 // Work feed of the persistent traversal kernels: kFeedSegments cursor words, kFeedCursorStride words apart (kernels.hip WorkFeed).
 constexpr uint32_t kFeedSegments = 8, kFeedCursorStride = 64;

@@ -930,6 +930,14 @@ struct Spectral {
     DEV float& refl(uint32_t k) { return base[(2 * s + k) * BLOCK]; }
 };
 
+// The wavelength rows of one entry of a wave's queue of ready starts (device_scene.h RenderLaunch::start_queue), for start_sample.
+typedef __attribute__((address_space(1))) uint32_t global_u32;
+typedef __attribute__((address_space(1))) float global_f32;
+struct StartQueueRows {
+    global_f32* base;
+    DEV global_f32& wl(uint32_t k) { return base[k * kStartQueueEntries]; }
+};
+
 // Surface normal at a hit (SurfacePoint::get_surface_data, shapes/mod.rs:484-494) and the material id.
 DEV void surface_at(const DevScene& S, const Hit& hit, f3 o, f3 d, f3& position, f3& normal, uint32_t& material) {
     const uint32_t kind = hit.shape >> 30, index = hit.shape & 0x3FFFFFFFu;
@@ -1281,6 +1289,12 @@ DEV const T* own_scalar(const T* p) {
     return reinterpret_cast<const T*>(out);
 }
 
+DEV uint32_t own_scalar(uint32_t v) { // the same for one word of a kernel-argument tuple
+    uint32_t out;
+    asm volatile("s_mov_b32 %0, %1" : "=s"(out) : "s"(v));
+    return out;
+}
+
 DEV SceneView wide_or_binary_view(const DevScene& S) {
     SceneView v{reinterpret_cast<const float4*>(S.nodes), reinterpret_cast<const float4*>(S.prims), false, nullptr};
     if (S.wide_nodes != nullptr) {
@@ -1358,8 +1372,10 @@ DEV DevScene stage_tables(const DevScene& S, float* lds, uint32_t lds_floats_bef
 }
 
 // Start of render_tile's loop body (simple.rs:78-107) for iteration `iteration` of raster tile `tile`.
-template <bool COMPANION_STATE = true>
-DEV void start_sample(const RenderLaunch& L, uint32_t tile, uint64_t iteration, const TileArea& area, Path& p, Spectral& spec) {
+// ROWS: where the sample's wavelengths go -- the lane's LDS rows (Spectral), or the rows of a ready start in the wave's queue
+// (StartQueueRows): slot S-1 is scratch during sample generation in both.
+template <bool COMPANION_STATE = true, class ROWS = Spectral>
+DEV void start_sample(const RenderLaunch& L, uint32_t tile, uint64_t iteration, const TileArea& area, Path& p, ROWS& spec) {
     const uint32_t SS = L.spectrum_samples;
     p.rng = rng_seed(L.seed, tile, iteration);
     // Tile::sample_point, renderer/algorithm.rs:113-119 (unfused: decides the pixel)
@@ -1744,7 +1760,7 @@ __global__ __launch_bounds__(BLOCK, 4) void render_kernel(DevScene S0, RenderLau
 // it, or when it is the most wanted one. Traversal is resumable (node index, stack pointer and closest hit stay in
 // registers, the stack in LDS) and advances sm_trav_steps node/leaf steps per turn, so a lane that finishes a short ray goes
 // on to shading while its neighbours keep walking the tree, and a lane whose path ends refills itself with the next
-// sample. Results are those of the synchronous walk bit for bit: per-path order of operations and RNG draws is unchanged.
+// sample (builds without interpreter programs: from the wave's queue of ready starts, Walker::expose_and_restart). Results are those of the synchronous walk bit for bit: per-path order of operations and RNG draws is unchanged.
 // =================================================================================================
 // Developer build only (-DPYR_PHASE_PROFILE, tools/phase_profile.py): per-phase wave cycles / active lanes / turns.
 #ifdef PYR_PHASE_PROFILE
@@ -1754,6 +1770,7 @@ __global__ __launch_bounds__(BLOCK, 4) void render_kernel(DevScene S0, RenderLau
 #define PROF_LANES(ph, cond) prof_l[ph] += __popcll(ballot64(cond)); prof_n[ph]++
 #define PROF_NOW() clock64()
 #define PROF_EXTRA(idx, cycles) if ((threadIdx.x & 63u) == 0) atomicAdd(&g_phase_prof[idx], (unsigned long long)(cycles))
+#define PROF_ADD(acc, v) (acc) += (v) /* a probe summed in registers and written once per wave (one atomic per turn and wave on one word would be the slowest thing in the kernel) */
 #define PROF_FLUSH()                                                                                  \
     if ((threadIdx.x & 63u) == 0)                                                                     \
         for (int i = 0; i < 4; ++i) {                                                                 \
@@ -1768,6 +1785,7 @@ __global__ __launch_bounds__(BLOCK, 4) void render_kernel(DevScene S0, RenderLau
 #define PROF_LANES(ph, cond)
 #define PROF_NOW() 0ull
 #define PROF_EXTRA(idx, cycles)
+#define PROF_ADD(acc, v)
 #define PROF_FLUSH()
 #endif
 
@@ -1843,6 +1861,7 @@ DEV bool trav_begin(const DevScene& S, Trav& t, f3 o, f3 d, bool shadow, float l
 // dozen pending subtrees, so a short LDS part keeps the LDS footprint (and with it the waves per CU) independent of the
 // tree's worst-case depth while the deep end is touched by a few rays only.
 typedef __attribute__((address_space(3))) int lds_int;
+typedef __attribute__((address_space(3))) uint32_t lds_u32;
 struct TravStack {
     lds_int* lds; // + threadIdx.x; an LDS pointer by type: a generic one makes every push and pop a flat_ access that drains both counters
     int lds_entries;
@@ -2279,7 +2298,17 @@ struct Walker {
         n_ops++;
     }
     uint32_t rgb_slot = 0; // eager replay of a scene with HIT_RGB programs: the value slot of the red basis (green and blue follow)
-    uint32_t chunk = 0; // next chunk of this lane's sample sequence (chunk_begin + wave, + total_waves, ...)
+    // QUEUE: the builds that start their samples 64 at a time (expose_and_restart) -- the tape builds without interpreter programs.
+    static constexpr bool QUEUE = PYR_SAMPLE_QUEUE != 0 && TAPE && !INTERP;
+    // The next chunk of the sample sequence chunk_begin + wave, + total_waves, ... QUEUE: the WAVE's sequence, the same value in every
+    // lane (a lane renders whichever ready start it pops); else this lane's own, lane l rendering iteration 64 * within + l of each chunk.
+    uint32_t chunk = 0;
+    // QUEUE: the first ready start of the wave's ring (bits 0-6) and how many are ready (from bit 8). The same in every lane, but kept
+    // in a vector register on purpose (expose_and_restart): the stage loop has no scalar register to spare.
+    uint32_t q_state = 0;
+#ifdef PYR_PHASE_PROFILE
+    unsigned long long prof_start[4] = {0, 0, 0, 0}; // builds without interpreter programs: cycles of the sample start (QUEUE: of the fills), fills, cycles of the pops; [3] the replay's (the kernel's)
+#endif
     Path p{};
     Trav t{};
     // context of the bounce in flight (between SHADE and the end of its next-event estimation)
@@ -2476,22 +2505,82 @@ struct Walker {
         }
     }
 
-    // EXPOSE / NEW: finish the path (simple.rs:133-139) and start the next sample of this lane's sequence (simple.rs:78-107)
+    // EXPOSE / NEW: finish the path (simple.rs:133-139) and start the next sample (simple.rs:78-107).
+    // A sample's start is a function of (seed, tile, iteration) alone, and this phase runs at a quarter of the wave's width, so the
+    // QUEUE builds do not start a sample in the lane that will render it: when more lanes want a sample than starts are ready, the
+    // whole wave runs locate_chunk and start_sample once for the 64 iterations of its next chunk and appends those that exist to a
+    // ring of ready starts in global memory (RenderLaunch::start_queue, [word][entry]: a fill is coalesced dword stores); a lane in
+    // ST_NEW then pops one -- 11 + S loads. A fill happens only while fewer than 64 starts are ready, so its up to 64 entries always
+    // fit the 128 of the ring and no lane waits a turn. Which lane renders which sample does not enter the film (a sum of atomics).
+    // The ring is read by other lanes of the SAME wave than wrote it: a release fence behind the fill and an acquire fence ahead of
+    // the pop, both at workgroup scope (the waves of a CU share its vector L1: a wait for the stores, no cache maintenance).
     DEV void expose_and_restart(const DevScene& S, const RenderLaunch& L, Spectral& spec, Counters& cnt, uint32_t lane, uint32_t total_waves) {
         if (stage == ST_EXPOSE) {
             if constexpr (!TAPE) finish_path<COUNT>(L, p, spec, cnt); // TAPE: the wave has replayed this lane's tape (replay_tapes)
             stage = ST_NEW;
         }
-        if (stage == ST_NEW) {
-            stage = ST_DONE;
-            while (chunk < L.chunk_end) {
+        if constexpr (QUEUE) {
+            [[maybe_unused]] const unsigned long long prof_q0 = PROF_NOW();
+            const unsigned long long starting = ballot64(stage == ST_NEW);
+            uint32_t wanted = (uint32_t)__popcll(starting);
+            asm volatile("" : "+v"(wanted)); // in a vector register, like q_state
+            const unsigned long long below = (1ull << lane) - 1ull;
+            global_u32* slab = (global_u32*)(L.start_queue + (size_t)(tape_column >> 6) * L.start_queue_stride);
+            const uint32_t q_head = q_state & (kStartQueueEntries - 1u);
+            uint32_t q_count = q_state >> 8;
+            bool filled = false;
+            while (q_count < wanted && chunk < L.chunk_end) { // the same in every lane
                 uint32_t tile;
                 uint64_t iteration;
                 TileArea area;
                 const bool ok = locate_chunk(L, chunk, lane, tile, iteration, area);
                 chunk += total_waves;
+                const unsigned long long exist = ballot64(ok);
+                const uint32_t at = q_head + q_count + (uint32_t)__popcll(exist & below);
+                q_count += (uint32_t)__popcll(exist); // (here: the mask is not carried across the start)
                 if (ok) {
-                    start_sample<!TAPE>(L, tile, iteration, area, p, spec);
+                    global_u32* e = slab + (at & (kStartQueueEntries - 1u));
+                    Path s;
+                    StartQueueRows rows{(global_f32*)(e + kStartQueueFixedWords * kStartQueueEntries)};
+                    start_sample<false>(L, tile, iteration, area, s, rows);
+                    rows.wl(L.spectrum_samples - 1u) = s.wl; // behind the companions, in the slot the hero pick has emptied
+                    e[0 * kStartQueueEntries] = s.rng.x, e[1 * kStartQueueEntries] = s.rng.y, e[2 * kStartQueueEntries] = s.rng.z, e[3 * kStartQueueEntries] = s.rng.w;
+                    e[4 * kStartQueueEntries] = s.pixel;
+                    e[5 * kStartQueueEntries] = __float_as_uint(s.o.x), e[6 * kStartQueueEntries] = __float_as_uint(s.o.y), e[7 * kStartQueueEntries] = __float_as_uint(s.o.z);
+                    e[8 * kStartQueueEntries] = __float_as_uint(s.d.x), e[9 * kStartQueueEntries] = __float_as_uint(s.d.y), e[10 * kStartQueueEntries] = __float_as_uint(s.d.z);
+                }
+                filled = true;
+            }
+            if (filled) __builtin_amdgcn_fence(__ATOMIC_RELEASE, "workgroup");
+            [[maybe_unused]] const unsigned long long prof_q1 = PROF_NOW();
+            PROF_ADD(prof_start[0], prof_q1 - prof_q0); // sample start: the fills (with PYR_SAMPLE_QUEUE=0: the starts, below)
+            PROF_ADD(prof_start[1], filled ? 1 : 0);
+            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+            if (stage == ST_NEW) {
+                const uint32_t rank = (uint32_t)__popcll(ballot64(stage == ST_NEW) & below);
+                stage = ST_DONE; // no chunks remain and the ring is empty: the launch's tail
+                if (rank < q_count) {
+                    const global_u32* e = slab + ((q_head + rank) & (kStartQueueEntries - 1u));
+                    // The companions go from the ring straight into this lane's wavelength rows (a load that writes LDS at the
+                    // wave's row + 4 * lane: where Spectral keeps them), all in flight at once beside the eleven words below: one
+                    // round trip for the whole entry. (A loop of load, wait, ds_write took nine of them in a row, 20,000 cycles a turn.)
+                    const uint32_t n_add = L.spectrum_samples - 1u;
+                    lds_u32* rows = (lds_u32*)(reinterpret_cast<uint32_t*>(spec.base) - lane);
+                    for (uint32_t k = 0; k < n_add; ++k)
+                        __builtin_amdgcn_global_load_lds(e + (kStartQueueFixedWords + k) * kStartQueueEntries, rows + k * BLOCK, 4, 0, 0);
+                    p.rng = Rng{e[0 * kStartQueueEntries], e[1 * kStartQueueEntries], e[2 * kStartQueueEntries], e[3 * kStartQueueEntries]};
+                    p.pixel = e[4 * kStartQueueEntries];
+                    p.o = mk(__uint_as_float(e[5 * kStartQueueEntries]), __uint_as_float(e[6 * kStartQueueEntries]), __uint_as_float(e[7 * kStartQueueEntries]));
+                    p.d = mk(__uint_as_float(e[8 * kStartQueueEntries]), __uint_as_float(e[9 * kStartQueueEntries]), __uint_as_float(e[10 * kStartQueueEntries]));
+                    p.wl = __uint_as_float(e[(kStartQueueFixedWords + n_add) * kStartQueueEntries]);
+                    asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // the rows are read as plain LDS from here on
+                    // what start_sample sets to constants
+                    p.bright = 0.0f;
+                    p.refl = 1.0f;
+                    p.use_additional = true;
+                    p.sample_light = true;
+                    p.events = 0;
+                    p.bounce = 0;
                     n_ops = 0;
                     if (COUNT) cnt.samples++;
                     if (L.bounces == 0) {
@@ -2500,9 +2589,37 @@ struct Walker {
                         if (COUNT) cnt.extension_rays++;
                         stage = trav_begin<COUNT>(S, t, p.o, p.d, false, 0.0f, cnt) ? ST_SHADE : ST_TRAV;
                     }
-                    break;
                 }
             }
+            const uint32_t popped = min(wanted, q_count);
+            q_state = ((q_head + popped) & (kStartQueueEntries - 1u)) | ((q_count - popped) << 8);
+            asm volatile("" : "+v"(q_state)); // a popcount's difference: the compiler would carry it across the stage loop as one more scalar
+            PROF_ADD(prof_start[2], PROF_NOW() - prof_q1); // the pops
+        } else {
+            [[maybe_unused]] const unsigned long long prof_q0 = PROF_NOW();
+            if (stage == ST_NEW) {
+                stage = ST_DONE;
+                while (chunk < L.chunk_end) {
+                    uint32_t tile;
+                    uint64_t iteration;
+                    TileArea area;
+                    const bool ok = locate_chunk(L, chunk, lane, tile, iteration, area);
+                    chunk += total_waves;
+                    if (ok) {
+                        start_sample<!TAPE>(L, tile, iteration, area, p, spec);
+                        n_ops = 0;
+                        if (COUNT) cnt.samples++;
+                        if (L.bounces == 0) {
+                            stage = ST_EXPOSE;
+                        } else {
+                            if (COUNT) cnt.extension_rays++;
+                            stage = trav_begin<COUNT>(S, t, p.o, p.d, false, 0.0f, cnt) ? ST_SHADE : ST_TRAV;
+                        }
+                        break;
+                    }
+                }
+            }
+            PROF_ADD(prof_start[0], PROF_NOW() - prof_q0); // sample start
         }
     }
 
@@ -3066,7 +3183,10 @@ __global__ __launch_bounds__(BLOCK, sm_waves(INTERP)) void render_kernel_sm(DevS
     int deep_levels[LDS_SCENE ? 1 : kMaxStackDepth]; // a scene that lives in LDS has its whole stack there (launch_render)
     stack.deep = deep_levels;
     stack.lds = (lds_int*)(reinterpret_cast<int*>(lds + spectral_rows * BLOCK) + threadIdx.x);
-    stack.lds_entries = (int)L.stack_lds;
+    // (QUEUE builds: the four schedule words arrive as one s_load_dwordx4, and with the queue's code in the EXPOSE phase the allocator
+    // parked that tuple whole and fetched all four back -- four v_readlane -- at every stack push of the traversal step; each word a value of its own)
+    constexpr bool QUEUE = Walker<COUNT, INTERP, TAPE, PRODUCT>::QUEUE;
+    stack.lds_entries = QUEUE ? (int)own_scalar(L.stack_lds) : (int)L.stack_lds;
     Counters cnt{};
     const uint32_t lds_base_floats = (spectral_rows + L.stack_lds) * BLOCK;
     const SceneView view = stage_scene<LDS_SCENE>(S0, lds, lds_base_floats, true);
@@ -3075,8 +3195,8 @@ __global__ __launch_bounds__(BLOCK, sm_waves(INTERP)) void render_kernel_sm(DevS
     const uint32_t lane = threadIdx.x & 63u;
     const uint32_t waves_per_block = BLOCK / 64;
     const uint32_t total_waves = gridDim.x * waves_per_block;
-    const int phase_lanes = (int)L.sm_phase_lanes, trav_steps = (int)L.sm_trav_steps;
-    const int expose_lanes = TAPE ? (int)L.sm_expose_lanes : phase_lanes; // the replay works at full width whatever the count, but has a fixed cost per turn
+    const int phase_lanes = QUEUE ? (int)own_scalar(L.sm_phase_lanes) : (int)L.sm_phase_lanes, trav_steps = QUEUE ? (int)own_scalar(L.sm_trav_steps) : (int)L.sm_trav_steps;
+    const int expose_lanes = TAPE ? (QUEUE ? (int)own_scalar(L.sm_expose_lanes) : (int)L.sm_expose_lanes) : phase_lanes; // the replay works at full width whatever the count, but has a fixed cost per turn
     Walker<COUNT, INTERP, TAPE, PRODUCT> w;
     w.chunk = L.chunk_begin + blockIdx.x * waves_per_block + (threadIdx.x >> 6);
     w.tape_prepared = nullptr;
@@ -3121,9 +3241,12 @@ __global__ __launch_bounds__(BLOCK, sm_waves(INTERP)) void render_kernel_sm(DevS
             const RenderLaunch& Lp = launch_from_kernarg(L);
             const DevScene Sp = scene_view(Lp);
             // (without hit-tape forms the replay is eager exactly when it has value slots: one uniform less to keep across the loop)
-            if constexpr (TAPE)
+            if constexpr (TAPE) {
+                [[maybe_unused]] const unsigned long long t_r0 = PROF_NOW();
                 replay_tapes<COUNT, HIT_TAPE, PRODUCT>(Sp, Lp, w.stage == ST_EXPOSE, w.n_ops, w.tape_column, w.p, lds, threadIdx.x, wave_list, prepared_lds, spectral_values, n_spectral,
                                               HIT_TAPE ? eager : n_spectral != 0, cnt);
+                PROF_ADD(w.prof_start[3], PROF_NOW() - t_r0); // the replay with its exposures; the rest of the phase is the sample start
+            }
             w.expose_and_restart(Sp, Lp, spec, cnt, lane, total_waves);
             PROF_END(0);
             nT = __popcll(ballot64(w.stage == ST_TRAV));
@@ -3189,6 +3312,10 @@ __global__ __launch_bounds__(BLOCK, sm_waves(INTERP)) void render_kernel_sm(DevS
         }
     }
     PROF_FLUSH();
+#ifdef PYR_PHASE_PROFILE
+    if constexpr (!INTERP) // (slots 12-14 are the interpreter builds' contribute probe)
+        for (int i = 0; i < 4; ++i) PROF_EXTRA(12 + i, w.prof_start[i]);
+#endif
     flush_counters<COUNT>(cnt, L.counters);
 }
 

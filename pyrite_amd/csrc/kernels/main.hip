@@ -284,6 +284,11 @@ int launch_render(const DevScene& scene, const RenderLaunch& launch_in, bool wit
         g_kernel_error = "the spectral tape is missing or too small for this launch";
         return PYR_ERR_INVALID_ARGUMENT;
     }
+    if (PYR_SAMPLE_QUEUE != 0 && uses_tape(scene, launch) && scene.needs_interpreter == 0 &&
+        (launch.start_queue == nullptr || launch.start_queue_stride < start_queue_words(launch.spectrum_samples) * kStartQueueEntries)) {
+        g_kernel_error = "the queue of ready sample starts is missing or too small for this launch"; // one slab per wave the tape has columns for: checked above
+        return PYR_ERR_INVALID_ARGUMENT;
+    }
     if (const char* cut = std::getenv("PYRITE_TEST_TAPE_OPS")) // test switch: pretend the bound were smaller, to see the overflow word work
         if (uses_tape(scene, launch) && *cut) launch.tape_max_ops = std::min<uint32_t>(launch.tape_max_ops, (uint32_t)std::strtoul(cut, nullptr, 10));
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), lds, (hipStream_t)stream, scene, launch);

@@ -3,7 +3,8 @@
 
 Needs the -DPYR_PHASE_PROFILE build of the library (csrc/variants/lib_prof.so):
     PYRITE_GPU_LIB=pyrite_amd/csrc/variants/lib_prof.so python tools/phase_profile.py [C3|C2|C5] [w h spp]
-Prints per phase: share of wave cycles, mean active lanes while the phase code runs, cycles per turn."""
+Prints per phase: share of wave cycles, mean active lanes while the phase code runs, cycles per turn; for C3 / C5 also EXPOSE/NEW
+split into the tape replay and the sample start (a -DPYR_SAMPLE_QUEUE=0 variant shows the start without the queue of ready starts)."""
 import ctypes as C
 import os
 import sys
@@ -54,6 +55,18 @@ for i, name in enumerate(["EXPOSE/NEW", "SHADE", "NEE", "TRAV"]):
     per_turn = cyc[i] / (n / (int(os.environ.get("PYRITE_SM_STEPS", "8")) if i == 3 else 1))
     print("%-11s %5.1f %% of wave cycles | mean active lanes %5.1f / 64 | %8.0f cycles per turn | %.2f turns per sample"
           % (name, 100.0 * cyc[i] / total, lanes[i] / n, per_turn, turns[i] * 64.0 / samples / (8 if i == 3 else 1)))
-if out[14]:  # interpreter builds: contribute_pending behind the phases
+if which in ("C3", "C5"):  # builds without interpreter programs: EXPOSE/NEW split into the tape replay (with its exposures) and the sample start
+    phase = float(cyc[0]) or 1.0
+    replay, start, fills, pops = out[15], out[12], out[13], out[14]
+    print("  of EXPOSE/NEW: replay + exposure %5.1f %% of wave cycles (%4.1f %% of the phase, full width: one (path, wavelength) pair per lane)"
+          % (100.0 * replay / total, 100.0 * replay / phase))
+    if fills:  # PYR_SAMPLE_QUEUE builds: the starts of a chunk at full width, then one pop per lane in ST_NEW
+        print("  of EXPOSE/NEW: sample start      %5.1f %% of wave cycles = fills %4.1f %% (64 lanes, %.3f fills per 64 samples, %6.0f cycles per fill) + pops %4.1f %% (mean lanes %4.1f, %5.0f cycles per turn)"
+              % (100.0 * (start + pops) / total, 100.0 * start / total, fills * 64.0 / samples, start / float(fills), 100.0 * pops / total, lanes[0] / max(turns[0], 1),
+                 pops / float(max(turns[0], 1))))
+    else:  # every lane starts its own sample: locate_chunk .. trav_begin at the phase's width
+        print("  of EXPOSE/NEW: sample start      %5.1f %% of wave cycles (%4.1f %% of the phase, mean lanes %4.1f, %5.0f cycles per turn)"
+              % (100.0 * start / total, 100.0 * start / phase, lanes[0] / max(turns[0], 1), start / float(max(turns[0], 1))))
+elif out[14]:  # interpreter builds: contribute_pending behind the phases
     print("contribute (interpreter) %5.1f %% of wave cycles (not in the phases above) | mean lanes with something to apply %5.1f / 64 | %8.0f cycles per turn | %.2f turns per sample"
           % (100.0 * out[12] / (total + out[12]), out[13] / float(out[14]), out[12] / float(out[14]), out[14] * 64.0 / samples))
