@@ -516,6 +516,55 @@ int pyr_scene_update_device(PyrScene*, const PyrGeometryUpdate*, void* hip_strea
 typedef struct PyrUpdateInfo { uint32_t mode_used, levels, updates; float upload_ms, prims_ms, refit_ms, total_ms; double area_ratio; uint32_t reserved[4]; } PyrUpdateInfo;
 int pyr_scene_update_info(PyrScene*, PyrUpdateInfo* out);
 
+/* ---- posing a live scene's objects. pyr_scene_update takes whole new arrays; most callers know less and more: WHICH object moves
+ * and by WHAT matrix. pyr_scene_set_objects names contiguous primitive ranges as objects and keeps the scene's geometry at that
+ * call on the device as the REST POSE; pyr_scene_pose takes one transform per object, computes every primitive of every object
+ * from the rest pose on the device, and runs the refit (or the rebuild) of pyr_scene_update from there: 80 bytes per object
+ * cross the bus instead of 120 bytes per triangle.
+ *   pyr_scene_set_objects: the ranges must lie inside the scene's counts and be pairwise disjoint (PYR_ERR_INVALID_ARGUMENT
+ * otherwise, as are a NULL scene and NULL ranges with a count); primitives in no range never move. Calling it again replaces the
+ * ranges and captures the rest pose again (the geometry as it is then, posed or not); num_objects == 0 forgets the objects and
+ * frees the rest pose. A pyr_scene_update[_device] that carries any array forgets them too -- those arrays are a new geometry,
+ * not a pose of the old one -- and pyr_scene_pose is PYR_ERR_INVALID_ARGUMENT until objects are set again.
+ *   pyr_scene_pose leaves the scene, in every observable respect, as pyr_scene_update (host arrays, the same mode) leaves it when
+ * given the arrays P(rest, poses). P is the reference's Shape::scale, then Shape::transform with Normal::transform, applied to the
+ * REST pose, never to the previous pose, all in f32 and unfused:
+ *     triangles  position *= scale; every vertex normal n and frame q become n' = normalize(M3 n),
+ *                q' = quat_from_cols(normalize(M3 (q * ex)), normalize(M3 (q * ey)), n'); then position = M position
+ *                (normalize(v) = v * (1 / |v|), |v| = sqrt((x*x + y*y) + z*z); M3 = the upper 3x3 of `transform`)
+ *     spheres    radius *= scale; centre *= scale; centre = M centre
+ * The last row of `transform` must be exactly 0,0,0,1, so the reference's division by w is by exactly 1. An object whose pose is
+ * exactly the identity matrix with scale 1.0f is COPIED from rest bit for bit (Normal::transform by the identity is not the
+ * identity on bits).
+ *   Argument checks, in this order, before any device is looked for (pyr_last_error names the argument): a NULL scene or update;
+ * an unknown mode; a non-zero reserved word, in the update or in any pose; num_objects that is not the scene's, or no objects set;
+ * NULL poses; a matrix entry or scale that is not finite; a last row that is not 0,0,0,1 -- all PYR_ERR_INVALID_ARGUMENT. A live
+ * PyrSession and a refit of a spatial-split tree are refused as pyr_scene_update refuses them.
+ *   Atomicity: the kernels write the posed arrays into the scene's staging arrays and touch no record; a bound of a moved primitive
+ * that fails the coordinate check of scene creation ("Coordinates") sets one word, which the call reads back -- its only wait on
+ * `hip_stream` before the refit is enqueued. Then the call returns PYR_ERR_UNSUPPORTED and the scene renders as before.
+ *   Shape lamps get their records from the posed arrays on the device, with the arithmetic of scene creation.
+ *   PYR_UPDATE_REBUILD poses on the device, fetches the posed arrays and runs the geometry part of scene creation, as
+ * pyr_scene_update does; it serves spatial-split scenes. pyr_scene_update_info describes a pose too: upload_ms is the pose kernels
+ * and the read-back of the word.
+ *   pyr_scene_geometry copies the scene's geometry as it is now to HOST arrays ([n][3][3], [n][3][3], [n][3][4], [n][4]); a NULL
+ * array is skipped, and tri_frames must be NULL for a scene created without frames. It waits for the device. */
+typedef struct PyrObjectRange { uint32_t first_triangle, num_triangles, first_sphere, num_spheres; } PyrObjectRange;
+int pyr_scene_set_objects(PyrScene*, const PyrObjectRange* ranges, uint32_t num_objects);
+typedef struct PyrObjectPose {
+    float transform[16];   /* column-major like PyrCamera::cam_to_world; last row 0,0,0,1 */
+    float scale;           /* uniform, applied before the transform */
+    uint32_t reserved[3];
+} PyrObjectPose;
+typedef struct PyrPoseUpdate {
+    uint32_t mode;               /* PYR_UPDATE_REFIT | PYR_UPDATE_REBUILD */
+    uint32_t num_objects;        /* must equal the scene's */
+    const PyrObjectPose* poses;  /* HOST, [num_objects] */
+    uint32_t reserved[4];
+} PyrPoseUpdate;
+int pyr_scene_pose(PyrScene*, const PyrPoseUpdate*, void* hip_stream);
+int pyr_scene_geometry(PyrScene*, float* tri_positions, float* tri_normals, float* tri_frames, float* spheres);
+
 /* Introspection of the kernel a render of `scene` with `params` would run (nothing is launched; only spectrum_samples is read
  * today). Results never depend on it -- every schedule is the same per-sample arithmetic as tracer.rs:208-345 -- but throughput
  * does, and a maintainer wants to see why a scene is slow: */

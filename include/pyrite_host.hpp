@@ -247,6 +247,12 @@ class FlatScene {
     size_t num_triangles() const;
     size_t num_spheres() const;
     size_t num_planes() const;
+    // What moves together (World::pose): one record per project object that has geometry -- a sphere; a mesh -- in project order.
+    struct Object {
+        std::string name; // "objects[i]"
+        PyrObjectRange range;
+    };
+    const std::vector<Object>& objects() const;
 
   private:
     struct Impl;
@@ -271,6 +277,24 @@ class World { // world.rs:31-36
     void update(const std::vector<float>& positions, const std::vector<float>& normals = {}, const std::vector<float>& frames = {},
                 const std::vector<float>& spheres = {}, Update mode = Update::Refit, int device = 0);
     PyrUpdateInfo update_info(int device = 0); // pyr_scene_update_info: the last update's stages and the tree's area ratio
+    // Poses the objects of the scene on `device` (pyr_scene_set_objects when the scene is made, pyr_scene_pose here): `poses` maps an
+    // object's index in objects() to a column-major matrix (last row 0,0,0,1) and the uniform scale that comes first; objects it
+    // does not name keep the identity -- every pose is from the rest pose, never from the previous one. The primitives are computed
+    // on the GPU. flat() stays the rest pose; the world remembers the poses and a scene it makes later is built for them.
+    struct ObjectPose {
+        float transform[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+        float scale = 1.0f;
+    };
+    const std::vector<FlatScene::Object>& objects() const { return flat_.objects(); }
+    void pose(const std::map<size_t, ObjectPose>& poses, Update mode = Update::Refit, int device = 0, void* hip_stream = nullptr);
+    // Names the description's objects again on every scene of this world (pyr_scene_set_objects): the geometry as it is now is the
+    // rest pose, every pose the identity. An update() that carried arrays makes the scene forget its objects until this is called.
+    void set_objects();
+    // pyr_scene_geometry: the geometry of the scene on `device` as it is now (frames empty unless the scene keeps them)
+    struct Geometry {
+        std::vector<float> positions, normals, frames, spheres;
+    };
+    Geometry geometry(int device = 0);
     // World::intersect (world.rs:273-299) for a batch of rays, [n][6] = origin, direction: closest hits, on the GPU
     std::vector<PyrHit> intersect(const std::vector<float>& rays, int device = 0, PyrCounters* counters = nullptr);
     FlatScene& flat() { return flat_; }
@@ -281,6 +305,8 @@ class World { // world.rs:31-36
     FlatScene flat_;
     std::map<std::pair<int, int>, PyrScene*> scenes_;
     std::map<std::pair<int, int>, Build> builders_; // what each scene was asked to be built by
+    std::map<size_t, ObjectPose> poses_;            // the poses the scenes are in; identity where absent
+    void pose_scene(PyrScene* handle, const std::map<size_t, ObjectPose>& poses, Update mode, void* hip_stream);
 };
 
 struct Camera { // cameras.rs:20-27

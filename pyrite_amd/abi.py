@@ -293,6 +293,32 @@ class PyrUpdateInfo(C.Structure):
     ]
 
 
+class PyrObjectRange(C.Structure):
+    _fields_ = [
+        ("first_triangle", C.c_uint32),
+        ("num_triangles", C.c_uint32),
+        ("first_sphere", C.c_uint32),
+        ("num_spheres", C.c_uint32),
+    ]
+
+
+class PyrObjectPose(C.Structure):
+    _fields_ = [
+        ("transform", C.c_float * 16),
+        ("scale", C.c_float),
+        ("reserved", C.c_uint32 * 3),
+    ]
+
+
+class PyrPoseUpdate(C.Structure):
+    _fields_ = [
+        ("mode", C.c_uint32),
+        ("num_objects", C.c_uint32),
+        ("poses", C.POINTER(PyrObjectPose)),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
 class PyrPathInfo(C.Structure):
     _fields_ = [
         ("stage_scheduler", C.c_uint32),
@@ -415,6 +441,9 @@ ENTRY_POINTS = {
     "pyr_scene_update": (C.c_int, [C.c_void_p, C.POINTER(PyrGeometryUpdate)]),
     "pyr_scene_update_device": (C.c_int, [C.c_void_p, C.POINTER(PyrGeometryUpdate), C.c_void_p]),
     "pyr_scene_update_info": (C.c_int, [C.c_void_p, C.POINTER(PyrUpdateInfo)]),
+    "pyr_scene_set_objects": (C.c_int, [C.c_void_p, C.POINTER(PyrObjectRange), C.c_uint32]),
+    "pyr_scene_pose": (C.c_int, [C.c_void_p, C.POINTER(PyrPoseUpdate), C.c_void_p]),
+    "pyr_scene_geometry": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pyr_scene_path_info": (C.c_int, [C.c_void_p, C.POINTER(PyrRenderParams), C.POINTER(PyrPathInfo)]),
     "pyr_scene_program_info": (C.c_int, [C.c_void_p, C.POINTER(PyrProgramInfo)]),
     "pyr_program_allocate_registers": (C.c_int, [C.POINTER(PyrInstr), C.POINTER(PyrProgram), C.POINTER(PyrInstr), C.POINTER(PyrProgram)]),

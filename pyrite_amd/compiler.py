@@ -252,6 +252,17 @@ class FlatScene:
         self.uses_rgb_basis = False
         self.sky_program = 0
         self._keep = None
+        # what moves together (World.pose): one record per project object that has geometry and per add_triangles call
+        self.objects = []
+
+    def _mark(self):
+        return len(self.tri_material), len(self.spheres)
+
+    def _record_object(self, name, mark):
+        first_triangle, first_sphere = mark
+        triangles, spheres = len(self.tri_material) - first_triangle, len(self.spheres) - first_sphere
+        if triangles or spheres:
+            self.objects.append(dict(name=name, first_triangle=first_triangle, num_triangles=triangles, first_sphere=first_sphere, num_spheres=spheres))
 
     # ---- spectra (SpectrumId::from_lua, project/spectra.rs:116-145: one id per Lua table) ----
     def spectrum_id(self, e):
@@ -596,6 +607,7 @@ class FlatScene:
         objects = world["objects"] if isinstance(world, dict) else world.objects
         for i, obj in enumerate(objects):
             t = obj.type
+            mark = self._mark()
             if t == "sphere":
                 m, emissive = self.add_material(obj.material)
                 position = eval_vector(obj.position)[:3]
@@ -627,6 +639,7 @@ class FlatScene:
                 raise ProjectError("ray-marched shapes are out of scope for the GPU path (SURVEY.md section 8)")
             else:
                 raise ProjectError("objects[%d]: unknown object type %s" % (i, t))
+            self._record_object("objects[%d]" % i, mark)
         return self
 
     def _add_mesh(self, i, obj, base_dir):  # world.rs:184-236
@@ -686,6 +699,7 @@ class FlatScene:
         positions = np.ascontiguousarray(positions, dtype=f32).reshape(-1, 9)
         normals = np.ascontiguousarray(normals, dtype=f32).reshape(-1, 9)
         base = len(self.tri_material)
+        mark = self._mark()
         self.tri_positions.append(positions)
         self.tri_normals.append(normals)
         self.tri_uvs.append(np.zeros((len(positions), 6), dtype=f32))
@@ -694,6 +708,7 @@ class FlatScene:
         if emissive:
             for k in range(len(positions)):
                 self.lamps.append(dict(kind=abi.LAMP_SHAPE, shape_kind=abi.SHAPE_TRIANGLE, shape_index=base + k))
+        self._record_object("triangles[%d]" % base, mark)
 
     # ---- ctypes view ----
     def desc(self):

@@ -17,6 +17,7 @@
 #include "bvh.h"
 #include "bvh_device.h"
 #include "device_scene.h"
+#include "kernels/pose_launch.h"
 #include "kernels/refit_launch.h"
 #include "program_regs.h"
 
@@ -402,6 +403,13 @@ struct PyrScene {
     double built_area = 0.0; // child_area_sum at the last build; < 0: not computed yet
     bool have_built_area = false;
     PyrUpdateInfo update_info{};
+    // ---- pyr_scene_set_objects / pyr_scene_pose: the objects with the poses the scene is in (identity when they are set), the rest
+    // pose on the device, and whether the host description above lags behind the staging arrays (a pose leaves it so; whoever
+    // reads it fetches first)
+    std::vector<devpose::DevObject> pose_table;
+    uint32_t posed_triangles = 0, posed_spheres = 0;
+    DeviceBuffer rest_positions, rest_normals, rest_frames, rest_spheres, pose_objects, pose_flag;
+    bool geometry_stale = false;
     ~PyrScene() {
         if (tail_count) (void)hipFree(tail_count);
     }
@@ -1541,11 +1549,81 @@ int reserve(DeviceBuffer& b, size_t bytes) {
     return b.alloc(bytes);
 }
 
+// The scene's records, trees and refit scratch as the refit kernels take them; the caller adds where the arrays are read and
+// which records the call rewrites.
+devrefit::Ctx refit_context(PyrScene* s) {
+    devrefit::Ctx c{};
+    c.prims = (float*)s->prims.ptr, c.num_prims = s->dev.num_prims;
+    c.pair_prims = s->info.num_pair_records ? (float*)s->pair_prims.ptr : nullptr, c.num_pairs = s->info.num_pair_records;
+    c.tri_shade = (float*)s->tri_shade.ptr;
+    c.tri_tex = s->tri_tex.bytes ? (float*)s->tri_tex.ptr : nullptr;
+    c.sphere_table = (float*)s->spheres.ptr;
+    c.num_triangles = s->geometry.num_triangles, c.num_spheres = s->geometry.num_spheres;
+    c.bounds = (float*)s->upd_bounds.ptr, c.max_abs_bits = (uint32_t*)s->upd_max_abs.ptr;
+    c.nodes = (Node64*)s->nodes.ptr, c.num_nodes = s->info.num_nodes;
+    c.wide_nodes = s->info.num_wide_nodes ? (Node128*)s->wide_nodes.ptr : nullptr, c.num_wide_nodes = s->info.num_wide_nodes;
+    c.wide_pair_nodes = s->info.num_pair_records ? (Node128*)s->wide_pair_nodes.ptr : nullptr;
+    return c;
+}
+
+// The records, then every box: one launch per height and tree, deepest nodes first. `waits`: the blocking form, whose stage times
+// are the device's. Fills the rest of `info` and makes it the scene's.
+int enqueue_refit(PyrScene* s, const devrefit::Ctx& c, bool waits, hipStream_t stream, std::chrono::steady_clock::time_point t_start,
+                  std::chrono::steady_clock::time_point t_uploaded, PyrUpdateInfo info) {
+    hipError_t e = devrefit::launch_repack(c, stream);
+    if (e != hipSuccess) return hip_fail(e, "refit: repack kernels");
+    if (waits) HIP_TRY(hipStreamSynchronize(stream));
+    const auto t_prims = std::chrono::steady_clock::now();
+    for (size_t h = 0; h + 1 < s->sched_binary.size(); ++h) {
+        e = devrefit::launch_refit_binary(c, (const uint32_t*)s->upd_order_binary.ptr + s->sched_binary[h], s->sched_binary[h + 1] - s->sched_binary[h], stream);
+        if (e != hipSuccess) return hip_fail(e, "refit: binary tree");
+    }
+    for (size_t h = 0; h + 1 < s->sched_wide.size(); ++h) {
+        e = devrefit::launch_refit_wide(c, (const uint32_t*)s->upd_order_wide.ptr + s->sched_wide[h], s->sched_wide[h + 1] - s->sched_wide[h], stream);
+        if (e != hipSuccess) return hip_fail(e, "refit: four-child tree");
+    }
+    if (waits) HIP_TRY(hipStreamSynchronize(stream));
+    const auto t_end = std::chrono::steady_clock::now();
+    info.levels = s->sched_binary.empty() ? 0u : (uint32_t)s->sched_binary.size() - 1u;
+    info.updates = s->update_info.updates + 1u;
+    info.upload_ms = (float)ms_between(t_start, t_uploaded);
+    info.prims_ms = (float)ms_between(t_uploaded, t_prims);
+    info.refit_ms = (float)ms_between(t_prims, t_end);
+    info.total_ms = (float)ms_between(t_start, t_end);
+    s->update_info = info;
+    return PYR_OK;
+}
+
+// The host description follows the staging arrays a pose wrote (nothing else leaves it behind).
+int fetch_geometry(PyrScene* s) {
+    if (!s->geometry_stale) return PYR_OK;
+    PyrScene::Geometry& g = s->geometry;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize());
+    if (g.num_triangles) {
+        HIP_TRY(hipMemcpy(g.tri_positions.data(), s->upd_positions.ptr, g.tri_positions.size() * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(g.tri_normals.data(), s->upd_normals.ptr, g.tri_normals.size() * 4, hipMemcpyDeviceToHost));
+        if (g.has_frames) HIP_TRY(hipMemcpy(g.tri_frames.data(), s->upd_frames.ptr, g.tri_frames.size() * 4, hipMemcpyDeviceToHost));
+    }
+    if (g.num_spheres) HIP_TRY(hipMemcpy(g.spheres.data(), s->upd_spheres.ptr, g.spheres.size() * 4, hipMemcpyDeviceToHost));
+    s->geometry_stale = false;
+    return PYR_OK;
+}
+
+// (the description is current: whoever forgets the objects has fetched it)
+void forget_objects(PyrScene* s) {
+    s->pose_table.clear();
+    s->posed_triangles = s->posed_spheres = 0;
+    for (DeviceBuffer* b : {&s->rest_positions, &s->rest_normals, &s->rest_frames, &s->rest_spheres, &s->pose_objects}) b->release();
+}
+
 int scene_update(PyrScene* s, const PyrGeometryUpdate* u, bool device_arrays, hipStream_t stream) {
     const auto t_start = std::chrono::steady_clock::now();
     HIP_TRY(hipSetDevice(s->device));
     PyrScene::Geometry& g = s->geometry;
     const size_t nt = g.num_triangles, ns = g.num_spheres;
+    int rc = fetch_geometry(s); // a pose left the description behind: what stays comes from it
+    if (rc != PYR_OK) return rc;
     // ---- the new arrays on the host: the caller's own, or copies of the device arrays
     std::vector<float> fetched[4];
     const float* given[4] = {u->tri_positions, u->tri_normals, u->tri_frames, u->spheres};
@@ -1577,6 +1655,7 @@ int scene_update(PyrScene* s, const PyrGeometryUpdate* u, bool device_arrays, hi
     info.mode_used = u->mode;
     info.area_ratio = 1.0;
     auto commit = [&]() { // the description the scene keeps follows the device
+        if (host[0] || host[1] || host[2] || host[3]) forget_objects(s); // new arrays are a new geometry, not a pose of the old one
         if (host[0]) g.tri_positions.assign(host[0], host[0] + floats[0]);
         if (host[1]) g.tri_normals.assign(host[1], host[1] + floats[1]);
         if (host[2]) g.tri_frames.assign(host[2], host[2] + floats[2]), g.has_frames = true;
@@ -1593,7 +1672,7 @@ int scene_update(PyrScene* s, const PyrGeometryUpdate* u, bool device_arrays, hi
         if (host[2]) d.tri_frames = host[2];
         if (host[3]) d.spheres = host[3];
         const PyrBuildInfo build_before = s->build_info;
-        const int rc = pack_geometry(&d, s, s->builder);
+        rc = pack_geometry(&d, s, s->builder);
         if (rc != PYR_OK) {
             s->build_info = build_before;
             return rc;
@@ -1607,20 +1686,10 @@ int scene_update(PyrScene* s, const PyrGeometryUpdate* u, bool device_arrays, hi
     }
 
     // ---- refit
-    int rc = prepare_refit(s);
+    rc = prepare_refit(s);
     if (rc != PYR_OK) return rc;
-    devrefit::Ctx c{};
-    c.prims = (float*)s->prims.ptr, c.num_prims = s->dev.num_prims;
-    c.pair_prims = s->info.num_pair_records ? (float*)s->pair_prims.ptr : nullptr, c.num_pairs = s->info.num_pair_records;
-    c.tri_shade = (float*)s->tri_shade.ptr;
-    c.tri_tex = s->tri_tex.bytes ? (float*)s->tri_tex.ptr : nullptr;
-    c.sphere_table = (float*)s->spheres.ptr;
-    c.num_triangles = g.num_triangles, c.num_spheres = g.num_spheres;
+    devrefit::Ctx c = refit_context(s);
     c.write_triangles = given[0] ? 1u : 0u, c.write_spheres = given[3] ? 1u : 0u;
-    c.bounds = (float*)s->upd_bounds.ptr, c.max_abs_bits = (uint32_t*)s->upd_max_abs.ptr;
-    c.nodes = (Node64*)s->nodes.ptr, c.num_nodes = s->info.num_nodes;
-    c.wide_nodes = s->info.num_wide_nodes ? (Node128*)s->wide_nodes.ptr : nullptr, c.num_wide_nodes = s->info.num_wide_nodes;
-    c.wide_pair_nodes = s->info.num_pair_records ? (Node128*)s->wide_pair_nodes.ptr : nullptr;
     // where the kernels read the arrays: the caller's device arrays, or the scene's own copies of the host arrays. The bounds of
     // every leaf need the triangles as they are now, moved or not.
     DeviceBuffer* own[4] = {&s->upd_positions, &s->upd_normals, &s->upd_frames, &s->upd_spheres};
@@ -1660,34 +1729,223 @@ int scene_update(PyrScene* s, const PyrGeometryUpdate* u, bool device_arrays, hi
     HIP_TRY(hipMemsetAsync(s->upd_max_abs.ptr, 0, 4, stream));
     if (!device_arrays) HIP_TRY(hipStreamSynchronize(stream));
     const auto t_uploaded = std::chrono::steady_clock::now();
-    hipError_t e = devrefit::launch_repack(c, stream);
-    if (e != hipSuccess) return hip_fail(e, "refit: repack kernels");
-    if (!device_arrays) HIP_TRY(hipStreamSynchronize(stream));
-    const auto t_prims = std::chrono::steady_clock::now();
-    // one launch per height and tree, deepest nodes first
-    for (size_t h = 0; h + 1 < s->sched_binary.size(); ++h) {
-        e = devrefit::launch_refit_binary(c, (const uint32_t*)s->upd_order_binary.ptr + s->sched_binary[h], s->sched_binary[h + 1] - s->sched_binary[h], stream);
-        if (e != hipSuccess) return hip_fail(e, "refit: binary tree");
+    return enqueue_refit(s, c, !device_arrays, stream, t_start, t_uploaded, info);
+}
+
+// ------------------------------------------------------------------------------------------------ pyr_scene_pose
+// What pyr_scene_pose refuses before any device is looked for, in the order pyrite_gpu.h gives.
+int check_pose_args(const PyrScene* scene, const PyrPoseUpdate* u) {
+    if (!u) return fail(PYR_ERR_INVALID_ARGUMENT, "null update");
+    if (!scene) return fail(PYR_ERR_INVALID_ARGUMENT, "null scene");
+    if (u->mode != PYR_UPDATE_REFIT && u->mode != PYR_UPDATE_REBUILD) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrPoseUpdate.mode is neither PYR_UPDATE_REFIT nor PYR_UPDATE_REBUILD");
+    for (uint32_t word : u->reserved)
+        if (word != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrPoseUpdate.reserved must be zero");
+    if (u->poses)
+        for (uint32_t i = 0; i < u->num_objects; ++i)
+            for (uint32_t word : u->poses[i].reserved)
+                if (word != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectPose.reserved must be zero");
+    if (scene->pose_table.empty()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrPoseUpdate.num_objects: the scene has no objects (pyr_scene_set_objects names them)");
+    if (u->num_objects != scene->pose_table.size()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrPoseUpdate.num_objects is not the scene's");
+    if (!u->poses) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrPoseUpdate.poses is null");
+    for (uint32_t i = 0; i < u->num_objects; ++i) {
+        const PyrObjectPose& p = u->poses[i];
+        for (float x : p.transform)
+            if (!std::isfinite(x)) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectPose.transform has an entry that is not finite");
+        if (!std::isfinite(p.scale)) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectPose.scale is not finite");
     }
-    for (size_t h = 0; h + 1 < s->sched_wide.size(); ++h) {
-        e = devrefit::launch_refit_wide(c, (const uint32_t*)s->upd_order_wide.ptr + s->sched_wide[h], s->sched_wide[h + 1] - s->sched_wide[h], stream);
-        if (e != hipSuccess) return hip_fail(e, "refit: four-child tree");
+    for (uint32_t i = 0; i < u->num_objects; ++i) {
+        const float* m = u->poses[i].transform;
+        if (!(m[3] == 0.0f && m[7] == 0.0f && m[11] == 0.0f && m[15] == 1.0f)) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectPose.transform: the last row must be 0, 0, 0, 1");
     }
-    if (!device_arrays) HIP_TRY(hipStreamSynchronize(stream));
-    const auto t_end = std::chrono::steady_clock::now();
-    info.levels = s->sched_binary.empty() ? 0u : (uint32_t)s->sched_binary.size() - 1u;
-    info.updates = s->update_info.updates + 1u;
-    info.upload_ms = (float)ms_between(t_start, t_uploaded);
-    info.prims_ms = (float)ms_between(t_uploaded, t_prims);
-    info.refit_ms = (float)ms_between(t_prims, t_end);
-    info.total_ms = (float)ms_between(t_start, t_end);
-    s->update_info = info;
+    if (scene->live_sessions != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "the scene has a live PyrSession: destroy it before the pose");
+    if (u->mode == PYR_UPDATE_REFIT && scene->spatial_splits)
+        return fail(PYR_ERR_UNSUPPORTED, "the scene's tree was built with spatial splits (PYRITE_SPATIAL_SPLITS=1): its leaves hold clipped boxes, ask for PYR_UPDATE_REBUILD");
+    return PYR_OK;
+}
+
+void set_pose(devpose::DevObject& o, const float* transform, float scale) {
+    static const float identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    bool same = scale == 1.0f;
+    for (int k = 0; k < 16; ++k) o.pose.m[k] = transform[k], same = same && transform[k] == identity[k];
+    o.pose.scale = scale;
+    o.pose.identity = same ? 1u : 0u;
+}
+
+devpose::Ctx pose_context(PyrScene* s) {
+    devpose::Ctx c{};
+    c.rest_positions = (const float*)s->rest_positions.ptr, c.rest_normals = (const float*)s->rest_normals.ptr;
+    c.rest_frames = s->geometry.has_frames ? (const float*)s->rest_frames.ptr : nullptr;
+    c.rest_spheres = (const float*)s->rest_spheres.ptr;
+    c.positions = (float*)s->upd_positions.ptr, c.normals = (float*)s->upd_normals.ptr, c.frames = (float*)s->upd_frames.ptr, c.spheres = (float*)s->upd_spheres.ptr;
+    c.objects = (const devpose::DevObject*)s->pose_objects.ptr, c.num_objects = (uint32_t)s->pose_table.size();
+    c.num_triangles = s->geometry.num_triangles, c.num_spheres = s->geometry.num_spheres;
+    c.posed_triangles = s->posed_triangles, c.posed_spheres = s->posed_spheres;
+    c.beyond_range = (uint32_t*)s->pose_flag.ptr;
+    c.lamps = (DevLamp*)s->lamps.ptr, c.num_lamps = (uint32_t)s->geometry.lamps.size();
+    return c;
+}
+
+// Every object's primitives from the rest pose into the staging arrays under `table`, and the flag back: the one wait.
+int run_pose(PyrScene* s, const std::vector<devpose::DevObject>& table, hipStream_t stream, uint32_t& beyond_range) {
+    HIP_TRY(hipMemcpyAsync(s->pose_objects.ptr, table.data(), table.size() * sizeof(devpose::DevObject), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemsetAsync(s->pose_flag.ptr, 0, 4, stream));
+    const hipError_t e = devpose::launch_pose(pose_context(s), stream);
+    if (e != hipSuccess) return hip_fail(e, "pose kernels");
+    HIP_TRY(hipMemcpyAsync(&beyond_range, s->pose_flag.ptr, 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return PYR_OK;
+}
+
+int scene_pose(PyrScene* s, const PyrPoseUpdate* u, hipStream_t stream) {
+    const auto t_start = std::chrono::steady_clock::now();
+    HIP_TRY(hipSetDevice(s->device));
+    PyrScene::Geometry& g = s->geometry;
+    int rc;
+    if (u->mode == PYR_UPDATE_REFIT && (rc = prepare_refit(s)) != PYR_OK) return rc;
+    std::vector<devpose::DevObject> table = s->pose_table;
+    for (uint32_t i = 0; i < u->num_objects; ++i) set_pose(table[i], u->poses[i].transform, u->poses[i].scale);
+    uint32_t beyond_range = 0;
+    if ((rc = run_pose(s, table, stream, beyond_range)) != PYR_OK) return rc;
+    if (beyond_range != 0) { // no record has been touched: the staging arrays go back to the poses the scene is in
+        if ((rc = run_pose(s, s->pose_table, stream, beyond_range)) != PYR_OK) return rc;
+        return fail(PYR_ERR_UNSUPPORTED, kCoordinateRangeMessage);
+    }
+    PyrUpdateInfo info{};
+    info.mode_used = u->mode;
+    info.area_ratio = 1.0;
+    const auto t_posed = std::chrono::steady_clock::now();
+
+    if (u->mode == PYR_UPDATE_REBUILD) {
+        // the posed arrays to the host, then the geometry part of scene creation over them, as pyr_scene_update does
+        std::vector<float> posed[4];
+        const DeviceBuffer* from[4] = {&s->upd_positions, &s->upd_normals, &s->upd_frames, &s->upd_spheres};
+        const size_t floats[4] = {g.tri_positions.size(), g.tri_normals.size(), g.has_frames ? g.tri_frames.size() : 0, g.spheres.size()};
+        HIP_TRY(hipDeviceSynchronize());
+        for (int k = 0; k < 4; ++k) {
+            posed[k].resize(floats[k]);
+            if (floats[k]) HIP_TRY(hipMemcpy(posed[k].data(), from[k]->ptr, floats[k] * 4, hipMemcpyDeviceToHost));
+        }
+        PyrSceneDesc d = g.view();
+        d.tri_positions = posed[0].data(), d.tri_normals = posed[1].data(), d.spheres = posed[3].data();
+        if (g.has_frames) d.tri_frames = posed[2].data();
+        const PyrBuildInfo build_before = s->build_info;
+        rc = pack_geometry(&d, s, s->builder);
+        if (rc != PYR_OK) {
+            s->build_info = build_before;
+            uint32_t ignored = 0;
+            const int back = run_pose(s, s->pose_table, stream, ignored);
+            return back != PYR_OK ? back : rc;
+        }
+        g.tri_positions.swap(posed[0]), g.tri_normals.swap(posed[1]), g.spheres.swap(posed[3]);
+        if (g.has_frames) g.tri_frames.swap(posed[2]);
+        s->geometry_stale = false;
+        s->pose_table.swap(table);
+        s->have_schedule = s->have_built_area = false;
+        info.updates = 0;
+        info.upload_ms = (float)ms_between(t_start, t_posed);
+        info.total_ms = (float)ms_between(t_start, std::chrono::steady_clock::now());
+        s->update_info = info;
+        return PYR_OK;
+    }
+
+    // ---- refit: every record and box from the staging arrays, as the host form of pyr_scene_update given all four arrays
+    s->pose_table.swap(table);
+    s->geometry_stale = true;
+    devrefit::Ctx c = refit_context(s);
+    c.write_triangles = g.num_triangles ? 1u : 0u, c.write_spheres = g.num_spheres ? 1u : 0u;
+    c.tri_positions = g.num_triangles ? (const float*)s->upd_positions.ptr : nullptr;
+    c.tri_normals = g.num_triangles ? (const float*)s->upd_normals.ptr : nullptr;
+    c.tri_frames = g.num_triangles && g.has_frames ? (const float*)s->upd_frames.ptr : nullptr;
+    c.spheres = (const float*)s->upd_spheres.ptr;
+    const hipError_t e = devpose::launch_lamps(pose_context(s), stream);
+    if (e != hipSuccess) return hip_fail(e, "pose: lamp records");
+    HIP_TRY(hipMemsetAsync(s->upd_max_abs.ptr, 0, 4, stream));
+    return enqueue_refit(s, c, false, stream, t_start, t_posed, info);
+}
+
+// ranges inside the counts and pairwise disjoint, triangles and spheres each
+int check_ranges(const PyrScene* scene, const PyrObjectRange* ranges, uint32_t n) {
+    std::vector<std::pair<uint64_t, uint64_t>> tri, sph;
+    for (uint32_t i = 0; i < n; ++i) {
+        const PyrObjectRange& r = ranges[i];
+        if ((uint64_t)r.first_triangle + r.num_triangles > scene->geometry.num_triangles) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectRange: a triangle range reaches past the scene's triangles");
+        if ((uint64_t)r.first_sphere + r.num_spheres > scene->geometry.num_spheres) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectRange: a sphere range reaches past the scene's spheres");
+        if (r.num_triangles) tri.emplace_back(r.first_triangle, (uint64_t)r.first_triangle + r.num_triangles);
+        if (r.num_spheres) sph.emplace_back(r.first_sphere, (uint64_t)r.first_sphere + r.num_spheres);
+    }
+    for (auto* list : {&tri, &sph}) {
+        std::sort(list->begin(), list->end());
+        for (size_t k = 1; k < list->size(); ++k)
+            if ((*list)[k].first < (*list)[k - 1].second) return fail(PYR_ERR_INVALID_ARGUMENT, list == &tri ? "PyrObjectRange: two triangle ranges overlap" : "PyrObjectRange: two sphere ranges overlap");
+    }
+    return PYR_OK;
+}
+
+// a staging array that holds a copy of `rest` (which holds `floats` floats of the description)
+int capture(DeviceBuffer& rest, DeviceBuffer& staging, const std::vector<float>& from, size_t floats) {
+    int rc;
+    if ((rc = rest.upload(from.data(), floats * 4)) != PYR_OK) return rc;
+    if ((rc = reserve(staging, floats * 4)) != PYR_OK) return rc;
+    if (floats) HIP_TRY(hipMemcpy(staging.ptr, rest.ptr, floats * 4, hipMemcpyDeviceToDevice));
     return PYR_OK;
 }
 
 } // namespace
 
 extern "C" {
+
+int pyr_scene_set_objects(PyrScene* scene, const PyrObjectRange* ranges, uint32_t num_objects) {
+    if (num_objects != 0 && !ranges) return fail(PYR_ERR_INVALID_ARGUMENT, "null ranges with a non-zero num_objects");
+    if (!scene) return fail(PYR_ERR_INVALID_ARGUMENT, "null scene");
+    int rc = check_ranges(scene, ranges, num_objects);
+    if (rc != PYR_OK) return rc;
+    if (num_objects == 0 && scene->pose_table.empty()) return PYR_OK;
+    HIP_TRY(hipSetDevice(scene->device));
+    HIP_TRY(hipDeviceSynchronize());
+    if ((rc = fetch_geometry(scene)) != PYR_OK) return rc; // the rest pose is the geometry as it is now
+    forget_objects(scene);
+    if (num_objects == 0) return PYR_OK;
+    PyrScene::Geometry& g = scene->geometry;
+    if ((rc = capture(scene->rest_positions, scene->upd_positions, g.tri_positions, g.tri_positions.size())) != PYR_OK) return rc;
+    if ((rc = capture(scene->rest_normals, scene->upd_normals, g.tri_normals, g.tri_normals.size())) != PYR_OK) return rc;
+    if ((rc = capture(scene->rest_frames, scene->upd_frames, g.tri_frames, g.has_frames ? g.tri_frames.size() : 0)) != PYR_OK) return rc;
+    if ((rc = capture(scene->rest_spheres, scene->upd_spheres, g.spheres, g.spheres.size())) != PYR_OK) return rc;
+    scene->upd_positions_current = true;
+    if ((rc = scene->pose_objects.alloc((size_t)num_objects * sizeof(devpose::DevObject))) != PYR_OK) return rc;
+    if (!scene->pose_flag.ptr && (rc = scene->pose_flag.alloc(4)) != PYR_OK) return rc;
+    static const float identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    scene->pose_table.resize(num_objects);
+    uint32_t triangle_lane = 0, sphere_lane = 0;
+    for (uint32_t i = 0; i < num_objects; ++i) {
+        devpose::DevObject& o = scene->pose_table[i];
+        set_pose(o, identity, 1.0f);
+        o.first_triangle = ranges[i].first_triangle, o.num_triangles = ranges[i].num_triangles;
+        o.first_sphere = ranges[i].first_sphere, o.num_spheres = ranges[i].num_spheres;
+        o.triangle_lane = triangle_lane, o.sphere_lane = sphere_lane;
+        triangle_lane += o.num_triangles, sphere_lane += o.num_spheres; // disjoint ranges inside the counts: below 2^28 in all
+    }
+    scene->posed_triangles = triangle_lane, scene->posed_spheres = sphere_lane;
+    return PYR_OK;
+}
+
+int pyr_scene_pose(PyrScene* scene, const PyrPoseUpdate* update, void* hip_stream) {
+    int rc = check_pose_args(scene, update);
+    if (rc != PYR_OK) return rc;
+    return scene_pose(scene, update, (hipStream_t)hip_stream);
+}
+
+int pyr_scene_geometry(PyrScene* scene, float* tri_positions, float* tri_normals, float* tri_frames, float* spheres) {
+    if (!scene) return fail(PYR_ERR_INVALID_ARGUMENT, "null scene");
+    const PyrScene::Geometry& g = scene->geometry;
+    if (tri_frames && !g.has_frames) return fail(PYR_ERR_INVALID_ARGUMENT, "tri_frames: the scene was created without frames and keeps none");
+    int rc = fetch_geometry(scene);
+    if (rc != PYR_OK) return rc;
+    if (tri_positions && !g.tri_positions.empty()) std::memcpy(tri_positions, g.tri_positions.data(), g.tri_positions.size() * 4);
+    if (tri_normals && !g.tri_normals.empty()) std::memcpy(tri_normals, g.tri_normals.data(), g.tri_normals.size() * 4);
+    if (tri_frames && !g.tri_frames.empty()) std::memcpy(tri_frames, g.tri_frames.data(), g.tri_frames.size() * 4);
+    if (spheres && !g.spheres.empty()) std::memcpy(spheres, g.spheres.data(), g.spheres.size() * 4);
+    return PYR_OK;
+}
 
 int pyr_scene_update(PyrScene* scene, const PyrGeometryUpdate* update) {
     int rc = check_update_args(scene, update);

@@ -339,6 +339,7 @@ struct FlatScene::Impl {
     std::vector<float> planes, plane_frames;
     std::vector<uint32_t> plane_material;
     std::vector<PyrLamp> lamps;
+    std::vector<FlatScene::Object> objects;
     std::vector<PyrMaterial> materials;
     std::vector<PyrComponent> components;
     std::vector<PyrProgram> programs;
@@ -887,6 +888,7 @@ void FlatScene::add_world(const WorldProject& world, const std::string& base_dir
     S.sky_program = compile(world.sky ? *world.sky : Expression(0.0));
     for (size_t i = 0; i < world.objects.size(); ++i) {
         const WorldObject& obj = world.objects[i];
+        const uint32_t first_triangle = (uint32_t)S.tri_material.size(), first_sphere = (uint32_t)S.sphere_material.size();
         switch (obj.kind) {
         case WorldObject::Kind::Sphere: {
             const auto added = add_material(obj.sphere.material);
@@ -937,8 +939,11 @@ void FlatScene::add_world(const WorldProject& world, const std::string& base_dir
             break;
         }
         }
+        const uint32_t triangles = (uint32_t)S.tri_material.size() - first_triangle, spheres = (uint32_t)S.sphere_material.size() - first_sphere;
+        if (triangles || spheres) S.objects.push_back(Object{"objects[" + std::to_string(i) + "]", PyrObjectRange{first_triangle, triangles, first_sphere, spheres}});
     }
 }
+const std::vector<FlatScene::Object>& FlatScene::objects() const { return impl_->objects; }
 
 void FlatScene::move_geometry(const std::vector<float>& positions, const std::vector<float>& normals, const std::vector<float>& frames, const std::vector<float>& spheres) {
     Impl& S = *impl_;
@@ -1071,6 +1076,12 @@ PyrScene* World::scene(int device, int copy, std::optional<Build> build) {
     check_status(pyr_scene_create_with(&flat_.desc(), device, build ? &params : nullptr, &handle));
     scenes_[{device, copy}] = handle;
     builders_[{device, copy}] = build.value_or(Build::Host);
+    if (!flat_.objects().empty()) { // the rest pose is the description; a scene made after a pose is built for the pose it is in
+        std::vector<PyrObjectRange> ranges;
+        for (const FlatScene::Object& o : flat_.objects()) ranges.push_back(o.range);
+        check_status(pyr_scene_set_objects(handle, ranges.data(), (uint32_t)ranges.size()));
+        if (!poses_.empty()) pose_scene(handle, poses_, Update::Rebuild, nullptr);
+    }
     return handle;
 }
 PyrBuildInfo World::build_info(int device, int copy) {
@@ -1094,6 +1105,48 @@ void World::update(const std::vector<float>& positions, const std::vector<float>
     u.spheres = spheres.empty() ? nullptr : spheres.data();
     check_status(pyr_scene_update(handle, &u));
     flat_.move_geometry(positions, normals, frames, spheres);
+    if (u.tri_positions || u.tri_normals || u.tri_frames || u.spheres) poses_.clear(); // a new geometry, not a pose of the old one: the scene forgot its objects (set_objects names them again)
+}
+void World::set_objects() {
+    if (!poses_.empty() && !scenes_.empty()) { // every scene of this world is in the same pose: flat() follows the first
+        const Geometry g = geometry(scenes_.begin()->first.first);
+        flat_.move_geometry(g.positions, g.normals, g.frames, g.spheres);
+    }
+    std::vector<PyrObjectRange> ranges;
+    for (const FlatScene::Object& o : flat_.objects()) ranges.push_back(o.range);
+    for (auto& kv : scenes_) check_status(pyr_scene_set_objects(kv.second, ranges.data(), (uint32_t)ranges.size()));
+    poses_.clear();
+}
+void World::pose_scene(PyrScene* handle, const std::map<size_t, ObjectPose>& poses, Update mode, void* hip_stream) {
+    std::vector<PyrObjectPose> records(flat_.objects().size());
+    for (size_t k = 0; k < records.size(); ++k) {
+        const auto it = poses.find(k);
+        const ObjectPose pose = it == poses.end() ? ObjectPose{} : it->second;
+        std::memset(&records[k], 0, sizeof(PyrObjectPose));
+        std::memcpy(records[k].transform, pose.transform, sizeof(pose.transform));
+        records[k].scale = pose.scale;
+    }
+    PyrPoseUpdate u{};
+    u.mode = mode == Update::Rebuild ? PYR_UPDATE_REBUILD : PYR_UPDATE_REFIT;
+    u.num_objects = (uint32_t)records.size();
+    u.poses = records.data();
+    check_status(pyr_scene_pose(handle, &u, hip_stream));
+}
+void World::pose(const std::map<size_t, ObjectPose>& poses, Update mode, int device, void* hip_stream) {
+    for (const auto& kv : poses)
+        if (kv.first >= flat_.objects().size()) throw ProjectError("pose: no object " + std::to_string(kv.first));
+    pose_scene(scene(device), poses, mode, hip_stream);
+    poses_ = poses;
+}
+World::Geometry World::geometry(int device) {
+    PyrScene* handle = scene(device);
+    const PyrSceneDesc& d = flat_.desc();
+    Geometry g;
+    g.positions.resize(9 * (size_t)d.num_triangles), g.normals.resize(9 * (size_t)d.num_triangles), g.spheres.resize(4 * (size_t)d.num_spheres);
+    if (d.tri_frames) g.frames.resize(12 * (size_t)d.num_triangles);
+    check_status(pyr_scene_geometry(handle, g.positions.empty() ? nullptr : g.positions.data(), g.normals.empty() ? nullptr : g.normals.data(),
+                                    g.frames.empty() ? nullptr : g.frames.data(), g.spheres.empty() ? nullptr : g.spheres.data()));
+    return g;
 }
 PyrUpdateInfo World::update_info(int device) {
     PyrUpdateInfo info{};

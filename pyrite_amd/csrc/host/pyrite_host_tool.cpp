@@ -397,6 +397,33 @@ int main(int argc, char** argv) {
             write_dump(argv[4], flat, project);
             return 0;
         }
+        if (argc >= 4 && std::string(argv[1]) == "objects") { // objects <scene> <data_dir>: what moves together (tests)
+            Project project = make_scene(argv[2], argv[3]);
+            std::unique_ptr<World> world = World::from_project(project.world, argv[3]);
+            for (const FlatScene::Object& o : world->objects())
+                std::printf("%s %u %u %u %u\n", o.name.c_str(), o.range.first_triangle, o.range.num_triangles, o.range.first_sphere, o.range.num_spheres);
+            return 0;
+        }
+        if (argc >= 6 && std::string(argv[1]) == "pose") { // pose <scene> <data_dir> <poses.f32: 17 floats an object> <geometry.f32> [rebuild] (tests)
+            Project project = make_scene(argv[2], argv[3]);
+            std::unique_ptr<World> world = World::from_project(project.world, argv[3]);
+            std::ifstream in(argv[4], std::ios::binary);
+            std::vector<char> bytes((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+            if (bytes.size() != world->objects().size() * 17 * 4) throw ProjectError("pose: the file does not hold 17 floats for each of the scene's objects");
+            std::map<size_t, World::ObjectPose> poses;
+            for (size_t k = 0; k < world->objects().size(); ++k) {
+                World::ObjectPose pose;
+                std::memcpy(pose.transform, bytes.data() + k * 68, 64);
+                std::memcpy(&pose.scale, bytes.data() + k * 68 + 64, 4);
+                poses[k] = pose;
+            }
+            world->pose(poses, argc >= 7 && std::string(argv[6]) == "rebuild" ? World::Update::Rebuild : World::Update::Refit);
+            const World::Geometry g = world->geometry();
+            std::ofstream out(argv[5], std::ios::binary);
+            for (const std::vector<float>* a : {&g.positions, &g.normals, &g.frames, &g.spheres}) out.write(reinterpret_cast<const char*>(a->data()), (std::streamsize)(a->size() * 4));
+            std::printf("%zu objects posed\n", poses.size());
+            return 0;
+        }
         if (argc >= 6 && std::string(argv[1]) == "intersect") { // intersect <scene> <data_dir> <rays.f32> <hits.bin>
             Project project = make_scene(argv[2], argv[3]);
             std::unique_ptr<World> world = World::from_project(project.world, argv[3]);

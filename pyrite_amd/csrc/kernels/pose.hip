@@ -1,0 +1,172 @@
+// pose.hip -- posing a live scene's objects on the device, a unit of its own: every primitive of an object
+// is computed from the rest pose by pose_rules.h and written to the scene's staging arrays, from where the refit of section 9f
+// (kernels/refit.hip) rewrites the records and the boxes; the records of shape lamps follow from the staging arrays too. Nothing
+// here touches a record the render kernels read except the lamp records, and those only after the host has seen the flag clear.
+//
+// One lane per primitive of an object, each lane stores to its own primitive only; the only word two lanes share is the flag,
+// which is an OR. No kernel waits for another workgroup.
+#include "pose_launch.h"
+
+#include "../bvh_level.h"
+#include "../device_scene.h"
+
+namespace pyr {
+namespace devpose {
+
+namespace {
+
+typedef float float4_t __attribute__((ext_vector_type(4)));
+
+__device__ __forceinline__ float4_t load4(const float* p) { return *(const float4_t*)p; }
+__device__ __forceinline__ void store4(float* p, float4_t v) { *(float4_t*)p = v; }
+
+// the object whose lanes hold `lane`: the last one that begins at or before it (an object without lanes begins where the next
+// one does, so it is never the last such one unless it is the last object, which begins at the lane count)
+template <uint32_t DevObject::*kBegin>
+__device__ __forceinline__ uint32_t object_of(const DevObject* objects, uint32_t num_objects, uint32_t lane) {
+    uint32_t lo = 0, hi = num_objects;
+    while (hi - lo > 1) {
+        const uint32_t mid = lo + (hi - lo) / 2;
+        if (objects[mid].*kBegin <= lane)
+            lo = mid;
+        else
+            hi = mid;
+    }
+    return lo;
+}
+
+__device__ __forceinline__ pose::Pose load_pose(const DevObject& o) {
+    pose::Pose p;
+    const float4_t c0 = load4(o.pose.m), c1 = load4(o.pose.m + 4), c2 = load4(o.pose.m + 8), c3 = load4(o.pose.m + 12);
+    p.m[0] = c0.x, p.m[1] = c0.y, p.m[2] = c0.z, p.m[3] = c0.w;
+    p.m[4] = c1.x, p.m[5] = c1.y, p.m[6] = c1.z, p.m[7] = c1.w;
+    p.m[8] = c2.x, p.m[9] = c2.y, p.m[10] = c2.z, p.m[11] = c2.w;
+    p.m[12] = c3.x, p.m[13] = c3.y, p.m[14] = c3.z, p.m[15] = c3.w;
+    p.scale = o.pose.scale;
+    p.identity = o.pose.identity;
+    return p;
+}
+
+__device__ __forceinline__ bool box_beyond_range(const float* lo, const float* hi) {
+    bool bad = false;
+    for (int a = 0; a < 3; ++a) bad = bad || pose::beyond_range(lo[a]) || pose::beyond_range(hi[a]);
+    return bad;
+}
+
+// the workgroup's OR in LDS, then one atomic of the workgroup on the scene's word (every lane of the workgroup arrives here)
+__device__ __forceinline__ void raise_flag(bool mine, uint32_t* block_flag, uint32_t* flag) {
+    if (mine) atomicOr(block_flag, 1u);
+    __syncthreads();
+    if (threadIdx.x == 0 && *block_flag != 0u) atomicOr(flag, 1u);
+}
+
+// ---- one lane per triangle of an object. 36 bytes a triangle, so only every fourth starts on a 16-byte boundary: dword loads
+// and stores for positions and normals; a triangle's frames are 48 bytes: 16-byte loads and stores.
+__global__ __launch_bounds__(kBlock) void pose_triangles_kernel(Ctx c) {
+    __shared__ uint32_t block_flag;
+    if (threadIdx.x == 0) block_flag = 0u;
+    __syncthreads();
+    const uint32_t lane = blockIdx.x * kBlock + threadIdx.x;
+    bool bad = false;
+    if (lane < c.posed_triangles && c.num_objects != 0u) {
+        const DevObject& object = c.objects[object_of<&DevObject::triangle_lane>(c.objects, c.num_objects, lane)];
+        const uint32_t within = lane - object.triangle_lane, index = object.first_triangle + within;
+        if (within < object.num_triangles && index >= object.first_triangle && index < c.num_triangles) {
+            const pose::Pose pose = load_pose(object);
+            const float* rest_p = c.rest_positions + 9 * (size_t)index;
+            const float* rest_n = c.rest_normals + 9 * (size_t)index;
+            float* out_p = c.positions + 9 * (size_t)index;
+            float* out_n = c.normals + 9 * (size_t)index;
+            float p[9];
+            for (int k = 0; k < 9; ++k) p[k] = rest_p[k];
+            if (!pose.identity)
+                for (int v = 0; v < 3; ++v) pose::pose_point(pose, p + 3 * v);
+            for (int k = 0; k < 9; ++k) out_p[k] = p[k];
+            float lo[3], hi[3];
+            lvl::triangle_bounds(p, lo, hi);
+            bad = box_beyond_range(lo, hi);
+            for (int v = 0; v < 3; ++v) { // a vertex at a time: its normal and, where the scene keeps them, its frame
+                float n[3] = {rest_n[3 * v], rest_n[3 * v + 1], rest_n[3 * v + 2]};
+                if (c.rest_frames) {
+                    const float4_t f = load4(c.rest_frames + 12 * (size_t)index + 4 * v);
+                    float q[4] = {f.x, f.y, f.z, f.w};
+                    if (!pose.identity) pose::pose_normal_frame(pose, n, q);
+                    store4(c.frames + 12 * (size_t)index + 4 * v, float4_t{q[0], q[1], q[2], q[3]});
+                } else if (!pose.identity) {
+                    pose::pose_normal(pose, n);
+                }
+                out_n[3 * v] = n[0], out_n[3 * v + 1] = n[1], out_n[3 * v + 2] = n[2];
+            }
+        }
+    }
+    raise_flag(bad, &block_flag, c.beyond_range);
+}
+
+// ---- one lane per sphere of an object
+__global__ __launch_bounds__(kBlock) void pose_spheres_kernel(Ctx c) {
+    __shared__ uint32_t block_flag;
+    if (threadIdx.x == 0) block_flag = 0u;
+    __syncthreads();
+    const uint32_t lane = blockIdx.x * kBlock + threadIdx.x;
+    bool bad = false;
+    if (lane < c.posed_spheres && c.num_objects != 0u) {
+        const DevObject& object = c.objects[object_of<&DevObject::sphere_lane>(c.objects, c.num_objects, lane)];
+        const uint32_t within = lane - object.sphere_lane, index = object.first_sphere + within;
+        if (within < object.num_spheres && index >= object.first_sphere && index < c.num_spheres) {
+            const pose::Pose pose = load_pose(object);
+            const float4_t r = load4(c.rest_spheres + 4 * (size_t)index);
+            float s[4] = {r.x, r.y, r.z, r.w};
+            if (!pose.identity) pose::pose_sphere(pose, s);
+            store4(c.spheres + 4 * (size_t)index, float4_t{s[0], s[1], s[2], s[3]});
+            float lo[3], hi[3];
+            lvl::sphere_bounds(s, lo, hi);
+            bad = box_beyond_range(lo, hi);
+        }
+    }
+    raise_flag(bad, &block_flag, c.beyond_range);
+}
+
+// ---- one lane per lamp: a shape lamp's record takes its shape from the staging arrays; directional and point lamps stay
+__global__ __launch_bounds__(kBlock) void pose_lamps_kernel(Ctx c) {
+    const uint32_t i = blockIdx.x * kBlock + threadIdx.x;
+    if (i >= c.num_lamps) return;
+    DevLamp& lamp = c.lamps[i];
+    if (lamp.kind != PYR_LAMP_SHAPE) return;
+    const uint32_t index = lamp.shape_index;
+    pose::LampShape shape;
+    if (lamp.shape_kind == PYR_SHAPE_SPHERE && index < c.num_spheres) {
+        const float4_t r = load4(c.spheres + 4 * (size_t)index);
+        const float s[4] = {r.x, r.y, r.z, r.w};
+        pose::lamp_of_sphere(s, shape);
+        for (int a = 0; a < 3; ++a) lamp.v[a] = shape.v[a];
+        lamp.width = shape.width;
+        lamp.area = shape.area;
+    } else if (lamp.shape_kind == PYR_SHAPE_TRIANGLE && index < c.num_triangles) {
+        float p[9], n[9];
+        for (int k = 0; k < 9; ++k) p[k] = c.positions[9 * (size_t)index + k], n[k] = c.normals[9 * (size_t)index + k];
+        pose::lamp_of_triangle(p, n, shape);
+        for (int a = 0; a < 3; ++a) {
+            lamp.p1[a] = shape.p[a], lamp.p2[a] = shape.p[3 + a], lamp.p3[a] = shape.p[6 + a];
+            lamp.n1[a] = shape.n[a], lamp.n2[a] = shape.n[3 + a], lamp.n3[a] = shape.n[6 + a];
+        }
+        lamp.area = shape.area;
+    }
+}
+
+uint32_t blocks_for(uint32_t n) { return (n + kBlock - 1) / kBlock; }
+
+} // namespace
+
+hipError_t launch_pose(const Ctx& c, hipStream_t stream) {
+    if (c.posed_triangles) hipLaunchKernelGGL(pose_triangles_kernel, dim3(blocks_for(c.posed_triangles)), dim3(kBlock), 0, stream, c);
+    if (c.posed_spheres) hipLaunchKernelGGL(pose_spheres_kernel, dim3(blocks_for(c.posed_spheres)), dim3(kBlock), 0, stream, c);
+    return hipGetLastError();
+}
+
+hipError_t launch_lamps(const Ctx& c, hipStream_t stream) {
+    if (c.num_lamps) hipLaunchKernelGGL(pose_lamps_kernel, dim3(blocks_for(c.num_lamps)), dim3(kBlock), 0, stream, c);
+    return hipGetLastError();
+}
+
+} // namespace devpose
+} // namespace pyr

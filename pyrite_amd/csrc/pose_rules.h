@@ -1,0 +1,165 @@
+// pose_rules.h -- what a pose does to one vertex, one sphere and one lamp, as functions of one record: the
+// pose kernels (kernels/pose.hip) and the host rehearsal (tests/probes/pose_check.cpp) both compile these, so what they compute
+// can differ only in the square root and the reciprocal -- sqrt32 / rcp32 of exact_math.h on the device, std::sqrt and 1.0f / x on
+// the host, bit-identical in the ranges exact_math.h names.
+//
+// The rule is the reference's Shape::scale and Shape::transform (shapes/mod.rs:290-344) with Normal::transform (shapes/mod.rs:
+// 572-583), in f32 and in the operation order of compiler.py's _transform_point, _transform_vector, _quat_rotate, _normalize and
+// _quat_from_cols. Units that include this header are built with -ffp-contract=off. A pose's last row is 0,0,0,1 (pyr_scene_pose
+// refuses any other), so transform_point's division by w is a division by exactly 1 and is left out. It is compiled for the
+// device too: no standard container in here.
+#pragma once
+#include <cstdint>
+
+#if defined(__HIPCC__)
+#include <hip/hip_runtime.h>
+
+#include "exact_math.h"
+#define PYR_POSE_HD __host__ __device__ __forceinline__
+#else
+#define PYR_POSE_HD inline
+#endif
+#if !defined(__HIP_DEVICE_COMPILE__)
+#include <cmath>
+#endif
+
+namespace pyr {
+namespace pose {
+
+// One object's pose as the kernels read it: the matrix column-major like PyrCamera::cam_to_world, the uniform scale that comes
+// first, and whether the pose is exactly the identity with scale 1 (such an object is copied from rest bit for bit:
+// Normal::transform by the identity is not the identity on bits).
+struct Pose {
+    float m[16];
+    float scale;
+    uint32_t identity;
+};
+
+PYR_POSE_HD float root(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return sqrt32(x);
+#else
+    return std::sqrt(x);
+#endif
+}
+PYR_POSE_HD float reciprocal(float x) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return rcp32(x);
+#else
+    return 1.0f / x;
+#endif
+}
+PYR_POSE_HD float magnitude(float x) { return x < 0.0f ? -x : x; } // fabs for everything the check below looks at (NaN stays NaN)
+
+// creation's coordinate check on one bound (pyrite_gpu.h "Coordinates")
+PYR_POSE_HD bool beyond_range(float x) { return !(magnitude(x) <= 1.0e15f); }
+
+// cgmath normalize: v * (1 / |v|) with |v| = sqrt((x*x + y*y) + z*z)
+PYR_POSE_HD void normalize(float* v) {
+    const float mag = root((v[0] * v[0] + v[1] * v[1]) + v[2] * v[2]);
+    const float k = reciprocal(mag);
+    v[0] = v[0] * k, v[1] = v[1] * k, v[2] = v[2] * k;
+}
+PYR_POSE_HD void cross(const float* a, const float* b, float* o) {
+    o[0] = a[1] * b[2] - a[2] * b[1];
+    o[1] = a[2] * b[0] - a[0] * b[2];
+    o[2] = a[0] * b[1] - a[1] * b[0];
+}
+PYR_POSE_HD void transform_vector(const float* m, const float* v, float* o) {
+    o[0] = m[0] * v[0] + m[4] * v[1] + m[8] * v[2];
+    o[1] = m[1] * v[0] + m[5] * v[1] + m[9] * v[2];
+    o[2] = m[2] * v[0] + m[6] * v[1] + m[10] * v[2];
+}
+PYR_POSE_HD void transform_point(const float* m, const float* p, float* o) { // (then / w, which is 1)
+    o[0] = m[0] * p[0] + m[4] * p[1] + m[8] * p[2] + m[12];
+    o[1] = m[1] * p[0] + m[5] * p[1] + m[9] * p[2] + m[13];
+    o[2] = m[2] * p[0] + m[6] * p[1] + m[10] * p[2] + m[14];
+}
+// Quaternion (s, x, y, z) * Vector3
+PYR_POSE_HD void quat_rotate(const float* q, const float* vec, float* o) {
+    float c[3], tmp[3], d[3];
+    cross(q + 1, vec, c);
+    tmp[0] = c[0] + vec[0] * q[0], tmp[1] = c[1] + vec[1] * q[0], tmp[2] = c[2] + vec[2] * q[0];
+    cross(q + 1, tmp, d);
+    o[0] = d[0] * 2.0f + vec[0], o[1] = d[1] * 2.0f + vec[1], o[2] = d[2] * 2.0f + vec[2];
+}
+// Quaternion::from(Matrix3::from_cols(c0, c1, c2)), kernels.hip's quat_from_cols
+PYR_POSE_HD void quat_from_cols(const float* c0, const float* c1, const float* c2, float* q) {
+    const float m00 = c0[0], m01 = c0[1], m02 = c0[2], m10 = c1[0], m11 = c1[1], m12 = c1[2], m20 = c2[0], m21 = c2[1], m22 = c2[2];
+    const float trace = m00 + m11 + m22;
+    if (trace >= 0.0f) {
+        float s = root(1.0f + trace);
+        const float w = 0.5f * s;
+        s = 0.5f / s;
+        q[0] = w, q[1] = (m12 - m21) * s, q[2] = (m20 - m02) * s, q[3] = (m01 - m10) * s;
+    } else if (m00 > m11 && m00 > m22) {
+        float s = root((m00 - m11 - m22) + 1.0f);
+        const float x = 0.5f * s;
+        s = 0.5f / s;
+        q[0] = (m12 - m21) * s, q[1] = x, q[2] = (m10 + m01) * s, q[3] = (m02 + m20) * s;
+    } else if (m11 > m22) {
+        float s = root((m11 - m00 - m22) + 1.0f);
+        const float y = 0.5f * s;
+        s = 0.5f / s;
+        q[0] = (m20 - m02) * s, q[1] = (m10 + m01) * s, q[2] = y, q[3] = (m21 + m12) * s;
+    } else {
+        float s = root((m22 - m00 - m11) + 1.0f);
+        const float z = 0.5f * s;
+        s = 0.5f / s;
+        q[0] = (m01 - m10) * s, q[1] = (m02 + m20) * s, q[2] = (m21 + m12) * s, q[3] = z;
+    }
+}
+
+// ---- the per-vertex rule
+// Shape::scale, then Shape::transform, on a vertex position
+PYR_POSE_HD void pose_point(const Pose& pose, float* p) {
+    const float s[3] = {p[0] * pose.scale, p[1] * pose.scale, p[2] * pose.scale};
+    transform_point(pose.m, s, p);
+}
+// Normal::transform on a vertex normal alone (a scene that keeps no frames)
+PYR_POSE_HD void pose_normal(const Pose& pose, float* n) {
+    float t[3];
+    transform_vector(pose.m, n, t);
+    normalize(t);
+    n[0] = t[0], n[1] = t[1], n[2] = t[2];
+}
+// Normal::transform on a vertex normal and its tangent frame
+PYR_POSE_HD void pose_normal_frame(const Pose& pose, float* n, float* frame) {
+    const float ex[3] = {1.0f, 0.0f, 0.0f}, ey[3] = {0.0f, 1.0f, 0.0f};
+    float rx[3], ry[3], x[3], y[3];
+    pose_normal(pose, n);
+    quat_rotate(frame, ex, rx);
+    transform_vector(pose.m, rx, x);
+    normalize(x);
+    quat_rotate(frame, ey, ry);
+    transform_vector(pose.m, ry, y);
+    normalize(y);
+    quat_from_cols(x, y, n, frame);
+}
+// ---- the per-sphere rule: radius *= scale; centre *= scale; centre = transform_point(centre)
+PYR_POSE_HD void pose_sphere(const Pose& pose, float* s) {
+    s[3] = s[3] * pose.scale;
+    pose_point(pose, s);
+}
+
+// ---- the lamp rule: what a shape lamp's record takes from its shape, with pack_lamp's arithmetic (api.cpp)
+struct LampShape {
+    float v[3], width; // sphere: centre and radius
+    float p[9], n[9];  // triangle: vertices and vertex normals
+    float area;        // Shape::surface_area, unfused f32
+};
+PYR_POSE_HD void lamp_of_sphere(const float* s, LampShape& o) {
+    o.v[0] = s[0], o.v[1] = s[1], o.v[2] = s[2];
+    o.width = s[3];
+    o.area = s[3] * s[3] * 4.0f * 3.14159265358979323846f;
+}
+PYR_POSE_HD void lamp_of_triangle(const float* p, const float* n, LampShape& o) {
+    for (int k = 0; k < 9; ++k) o.p[k] = p[k], o.n[k] = n[k];
+    const float a[3] = {p[3] - p[0], p[4] - p[1], p[5] - p[2]}, b[3] = {p[6] - p[0], p[7] - p[1], p[8] - p[2]};
+    float c[3];
+    cross(a, b, c); // 0.5 * |a x b|
+    o.area = 0.5f * root((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]);
+}
+
+} // namespace pose
+} // namespace pyr

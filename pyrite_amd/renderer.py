@@ -25,6 +25,8 @@ class World:
         self._desc = flat.desc()
         self._scenes = {}
         self._builders = {}
+        self._objects = [dict(o) for o in flat.objects]  # what moves together (World.pose)
+        self._poses = {}  # object index -> (float32[16] column-major, scale): the poses the scenes are in; identity where absent
 
     @classmethod
     def from_project(cls, world, base_dir="."):
@@ -53,6 +55,10 @@ class World:
                 check(lib().pyr_scene_create_with(C.byref(self._desc), int(device), C.byref(params), C.byref(handle)))
             self._scenes[key] = handle
             self._builders[key] = build or "host"
+            if self._objects:  # the rest pose is the description; a scene made after a pose is built for the pose it is in
+                self._set_objects(handle)
+                if self._poses:
+                    self._pose(handle, self._poses, "rebuild", 0)
         elif build is not None and build != self._builders[key]:
             raise ValueError("the scene on device %r was created with build=%r" % (device, self._builders[key]))
         return self._scenes[key]
@@ -70,13 +76,87 @@ class World:
         return {name: int(getattr(info, name)) for name, _ in info._fields_}
 
     UPDATE_MODES = {"refit": abi.PYR_UPDATE_REFIT, "rebuild": abi.PYR_UPDATE_REBUILD}
+    IDENTITY = np.array([1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1], dtype=np.float32)
+
+    @property
+    def objects(self):
+        """What moves together: one record per project object that has geometry (a sphere; a mesh) and per add_triangles call,
+        or what set_objects named -- `name`, `first_triangle`, `num_triangles`, `first_sphere`, `num_spheres`."""
+        return [dict(o) for o in self._objects]
+
+    def _set_objects(self, handle, objects=None):
+        objects = self._objects if objects is None else objects
+        ranges = (abi.PyrObjectRange * max(1, len(objects)))()
+        for k, o in enumerate(objects):
+            ranges[k] = abi.PyrObjectRange(o.get("first_triangle", 0), o.get("num_triangles", 0), o.get("first_sphere", 0), o.get("num_spheres", 0))
+        check(lib().pyr_scene_set_objects(handle, ranges, len(objects)))
+
+    def set_objects(self, objects=None):
+        """Names other primitive ranges as the objects (pyr_scene_set_objects on every scene of this world; None: the records of
+        the description again). The geometry as it is now becomes the rest pose, and every pose is the identity again."""
+        if self._poses and self._scenes:  # every scene of this world is in the same pose: `flat` follows the first
+            self._follow(self._geometry(next(iter(self._scenes.values()))))
+        objects = [dict(o) for o in (self.flat.objects if objects is None else objects)]
+        for handle in self._scenes.values():
+            self._set_objects(handle, objects)
+        self._objects, self._poses = objects, {}
+
+    def _follow(self, arrays):
+        for name, attr in (("positions", "tri_positions"), ("normals", "tri_normals"), ("frames", "tri_frames"), ("spheres", "spheres")):
+            if arrays.get(name) is not None and len(arrays[name]):
+                setattr(self.flat, attr, [np.array(arrays[name], dtype=np.float32).reshape(len(arrays[name]), -1)])
+        self._desc = self.flat.desc()
+
+    def _pose(self, handle, poses, mode, stream):
+        records = (abi.PyrObjectPose * max(1, len(self._objects)))()
+        for k in range(len(self._objects)):
+            matrix, scale = poses.get(k, (None, 1.0))
+            m = self.IDENTITY if matrix is None else np.asarray(matrix, dtype=np.float32)
+            if m.shape == (4, 4):
+                m = m.T  # rows of a 4x4 array -> column-major
+            m = np.ascontiguousarray(m, dtype=np.float32).reshape(-1)
+            if m.size != 16:
+                raise ValueError("the pose of object %d is not a 4x4 matrix" % k)
+            records[k].transform = (C.c_float * 16)(*[float(x) for x in m])
+            records[k].scale = float(scale)
+        u = abi.PyrPoseUpdate(mode=self.UPDATE_MODES[mode], num_objects=len(self._objects), poses=records)
+        check(lib().pyr_scene_pose(handle, C.byref(u), C.c_void_p(int(stream))))
+
+    def pose(self, poses, mode="refit", device=0, stream=0):
+        """Poses the objects of the scene on `device` (pyr_scene_pose): `poses` maps an object's index in `World.objects` to
+        (matrix, scale) -- a 4x4 array as written on paper (translation in the last column), or 16 floats column-major, or None
+        for no transform; the uniform scale comes first. Objects it does not name keep the identity: every pose is from the
+        rest pose, never from the previous one. The primitives are computed on the GPU; mode as for `update`. `World.flat`
+        stays the rest pose, and the world remembers the poses for scenes it creates later."""
+        if mode not in self.UPDATE_MODES:
+            raise ValueError("mode must be 'refit' or 'rebuild', not %r" % (mode,))
+        for k in poses:
+            if not 0 <= int(k) < len(self._objects):
+                raise ValueError("no object %r: the world has %d" % (k, len(self._objects)))
+        named = {int(k): (None if v[0] is None else np.array(v[0], dtype=np.float32), float(v[1])) for k, v in poses.items()}
+        self._pose(self.scene(device), named, mode, stream)
+        self._poses = named
+
+    def geometry(self, device=0):
+        """The geometry of the scene on `device` as it is now (pyr_scene_geometry): a dict of float32 arrays `positions` [n,9],
+        `normals` [n,9], `frames` [n,12] (None unless the scene keeps frames) and `spheres` [n,4]."""
+        return self._geometry(self.scene(device))
+
+    def _geometry(self, handle):
+        nt, ns = self._desc.num_triangles, self._desc.num_spheres
+        out = {"positions": np.zeros((nt, 9), dtype=np.float32), "normals": np.zeros((nt, 9), dtype=np.float32),
+               "frames": np.zeros((nt, 12), dtype=np.float32) if self.flat.uses_normal_maps and nt else None, "spheres": np.zeros((ns, 4), dtype=np.float32)}
+        pointer = lambda a: None if a is None or a.size == 0 else a.ctypes.data  # noqa: E731
+        check(lib().pyr_scene_geometry(handle, pointer(out["positions"]), pointer(out["normals"]), pointer(out["frames"]), pointer(out["spheres"])))
+        return out
 
     def update(self, positions=None, normals=None, frames=None, spheres=None, mode="refit", device=0, stream=0):
         """Moves the geometry of the scene on `device` (pyr_scene_update): new `positions` [n,3,3], `normals` [n,3,3], `frames`
         [n,3,4] for the same triangles and `spheres` [n,4] for the same spheres; what is None stays. mode="refit" keeps the
         tree's topology and recomputes every box; "rebuild" builds a new tree with the scene's builder. Arrays that are torch
         tensors on the GPU go through pyr_scene_update_device on `stream` (all of them must be, then); anything else is taken
-        as host data. `World.flat` and the description follow, so a scene created later elsewhere is the moved one."""
+        as host data. `World.flat` and the description follow, so a scene created later elsewhere is the moved one. New arrays are
+        a new geometry, not a pose of the old one: the scene forgets its objects, and `set_objects()` names them again."""
         if mode not in self.UPDATE_MODES:
             raise ValueError("mode must be 'refit' or 'rebuild', not %r" % (mode,))
         given = {"positions": (positions, 9), "normals": (normals, 9), "frames": (frames, 12), "spheres": (spheres, 4)}
@@ -113,6 +193,8 @@ class World:
         else:
             check(lib().pyr_scene_update(self.scene(device), C.byref(u)))
         del keep
+        if u.tri_positions or u.tri_normals or u.tri_frames or u.spheres:
+            self._poses = {}  # new arrays are a new geometry, not a pose of the old one: the scene forgot its objects (set_objects names them again)
         for name, attr in (("positions", "tri_positions"), ("normals", "tri_normals"), ("frames", "tri_frames"), ("spheres", "spheres")):
             if name in host:
                 setattr(self.flat, attr, [host[name].copy()])
