@@ -1,6 +1,6 @@
 // api.cpp -- host side of the C ABI declared in include/pyrite_gpu.h: scene validation and packing, BVH build,
 // upload, launch orchestration. No radiance is ever computed on the host; without a gfx950 device every render /
-// intersect entry point fails with PYR_ERR_DEVICE.
+// intersect entry point fails with PYR_ERR_DEVICE. What moves a scene after creation is live_scene.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -17,13 +17,12 @@
 #include "bvh.h"
 #include "bvh_device.h"
 #include "device_scene.h"
-#include "kernels/pose_launch.h"
-#include "kernels/refit_launch.h"
 #include "program_regs.h"
+#include "scene_internal.h"
 
 using namespace pyr;
 
-namespace {
+namespace pyr {
 
 thread_local std::string g_error;
 int fail(int code, const std::string& message) {
@@ -31,37 +30,35 @@ int fail(int code, const std::string& message) {
     return code;
 }
 int hip_fail(hipError_t e, const char* what) { return fail(PYR_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); }
+int api_fail(int code, const std::string& message) { return fail(code, message); }
 
-#define HIP_TRY(expr)                                  \
-    do {                                               \
-        hipError_t e_ = (expr);                        \
-        if (e_ != hipSuccess) return hip_fail(e_, #expr); \
-    } while (0)
+void DeviceBuffer::release() {
+    if (ptr) (void)hipFree(ptr);
+    ptr = nullptr;
+    bytes = 0;
+}
+int DeviceBuffer::upload(const void* src, size_t n) {
+    release();
+    bytes = n;
+    if (n == 0) n = 16; // keep pointers non-null
+    HIP_TRY(hipMalloc(&ptr, n));
+    if (bytes) HIP_TRY(hipMemcpy(ptr, src, bytes, hipMemcpyHostToDevice));
+    return PYR_OK;
+}
+int DeviceBuffer::alloc(size_t n) {
+    release();
+    bytes = n;
+    HIP_TRY(hipMalloc(&ptr, n ? n : 16));
+    return PYR_OK;
+}
+int DeviceBuffer::reserve(size_t n) {
+    if (ptr && bytes >= n) return PYR_OK;
+    return alloc(n);
+}
 
-struct DeviceBuffer {
-    void* ptr = nullptr;
-    size_t bytes = 0;
-    ~DeviceBuffer() { release(); }
-    void release() {
-        if (ptr) (void)hipFree(ptr);
-        ptr = nullptr;
-        bytes = 0;
-    }
-    int upload(const void* src, size_t n) { // (over an earlier allocation: that one is freed -- a rebuild uploads into the scene's buffers again)
-        release();
-        bytes = n;
-        if (n == 0) n = 16; // keep pointers non-null
-        HIP_TRY(hipMalloc(&ptr, n));
-        if (bytes) HIP_TRY(hipMemcpy(ptr, src, bytes, hipMemcpyHostToDevice));
-        return PYR_OK;
-    }
-    int alloc(size_t n) {
-        release();
-        bytes = n;
-        HIP_TRY(hipMalloc(&ptr, n ? n : 16));
-        return PYR_OK;
-    }
-};
+} // namespace pyr
+
+namespace {
 
 int validate(const PyrSceneDesc* d) {
     if (!d) return fail(PYR_ERR_INVALID_ARGUMENT, "null scene description");
@@ -340,83 +337,11 @@ bool split_product(std::vector<PyrInstr>& instrs, const PyrProgram& p, PyrProgra
 
 } // namespace
 
-struct PyrScene {
-    int device = 0;
-    int num_cus = 0;
-    DevScene dev{};
-    PyrBvhInfo info{};
-    PyrBuildInfo build_info{}; // pyr_scene_build_info
-    std::unique_ptr<pyr::BuiltBvh> digest_source; // the binary tree, kept until the first pyr_scene_build_info has hashed it (tree_digest walks the whole tree: not on every scene creation's bill)
-    DeviceBuffer wide_nodes, wide_pair_nodes, pair_prims, nodes, prims, tri_shade, spheres, sphere_material, planes, plane_material, lamps, materials, components, programs, instrs, spectra,
-        spectrum_data, rgb_basis, counters, tri_tex, sphere_tex_scale, plane_frames, textures, texture_data;
-    PyrCounters last_counters{};
-    bool have_counters = false;
-    PyrProgramInfo program_info{}; // pyr_scene_program_info; program_info.wide: the kernels are the wide interpreter build (kernels/wide.hip)
-    uint32_t* tail_count = nullptr; // device, kFeedBytes: the work-feed cursors of the intersect kernel
-    DeviceBuffer tape; // spectral tape of the stage-scheduled kernel (grown on demand, kept between renders)
-    DeviceBuffer start_queue; // the waves' rings of ready sample starts (RenderLaunch::start_queue; scenes without interpreter programs), kept like the tape
-    DeviceBuffer tape_overflow; // one word the kernels set when a path outgrew the tape (checked after blocking renders and by pyr_scene_counters)
-    // ---- pyr_scene_update: what of the description says where things are, kept on the host (a rebuild packs the geometry from it
-    // again, a refit its lamps; the arrays an update leaves out stay as they are here), and the state of the refit
-    struct Geometry {
-        std::vector<float> tri_positions, tri_normals, tri_uvs, tri_frames, spheres, sphere_tex_scale;
-        std::vector<uint32_t> tri_material, sphere_material;
-        std::vector<PyrLamp> lamps;
-        bool has_uvs = false, has_frames = false, has_tex_scale = false;
-        uint32_t num_triangles = 0, num_spheres = 0;
-        PyrSceneDesc view() const { // a description with the fields pack_geometry and pack_lamp read
-            PyrSceneDesc d{};
-            d.num_triangles = num_triangles, d.num_spheres = num_spheres, d.num_lamps = (uint32_t)lamps.size();
-            d.tri_positions = tri_positions.data(), d.tri_normals = tri_normals.data(), d.tri_material = tri_material.data();
-            d.tri_uvs = has_uvs ? tri_uvs.data() : nullptr, d.tri_frames = has_frames ? tri_frames.data() : nullptr;
-            d.spheres = spheres.data(), d.sphere_material = sphere_material.data();
-            d.sphere_tex_scale = has_tex_scale ? sphere_tex_scale.data() : nullptr;
-            d.lamps = lamps.data();
-            return d;
-        }
-    } geometry;
-    void keep_geometry(const PyrSceneDesc* d) {
-        Geometry& g = geometry;
-        const size_t nt = d->num_triangles, ns = d->num_spheres;
-        g.num_triangles = d->num_triangles, g.num_spheres = d->num_spheres;
-        g.tri_positions.assign(d->tri_positions, d->tri_positions + (nt ? 9 * nt : 0));
-        g.tri_normals.assign(d->tri_normals, d->tri_normals + (nt ? 9 * nt : 0));
-        g.tri_material.assign(d->tri_material, d->tri_material + nt);
-        g.has_uvs = d->tri_uvs != nullptr, g.has_frames = d->tri_frames != nullptr, g.has_tex_scale = d->sphere_tex_scale != nullptr;
-        if (g.has_uvs) g.tri_uvs.assign(d->tri_uvs, d->tri_uvs + 6 * nt);
-        if (g.has_frames) g.tri_frames.assign(d->tri_frames, d->tri_frames + 12 * nt);
-        g.spheres.assign(d->spheres, d->spheres + (ns ? 4 * ns : 0));
-        g.sphere_material.assign(d->sphere_material, d->sphere_material + ns);
-        if (g.has_tex_scale) g.sphere_tex_scale.assign(d->sphere_tex_scale, d->sphere_tex_scale + 2 * ns);
-        g.lamps.assign(d->lamps, d->lamps + d->num_lamps);
-    }
-    uint32_t builder = PYR_BUILD_HOST; // who builds this scene's trees: at creation, and at every PYR_UPDATE_REBUILD
-    bool spatial_splits = false;       // the last build split space: its leaves hold clipped boxes, which a refit cannot recompute
-    uint64_t table_floats = 0;         // floats of the small tables a big scene stages into LDS (DevScene::lds_table_floats)
-    uint32_t live_sessions = 0;        // PyrSessions on this scene: an update is refused while there is one
-    DeviceBuffer upd_positions, upd_normals, upd_frames, upd_spheres; // the host form's new arrays on the device
-    bool upd_positions_current = false; // upd_positions holds geometry.tri_positions
-    DeviceBuffer upd_bounds, upd_max_abs, upd_order_binary, upd_order_wide; // the refit's scratch and its schedules (made at the first refit after a build)
-    std::vector<uint32_t> sched_binary, sched_wide; // RefitSchedule::begin of either tree
-    bool have_schedule = false;
-    std::vector<DevLamp> upd_lamps; // the lamp records of the last update (the copy to the device may still read them)
-    double built_area = 0.0; // child_area_sum at the last build; < 0: not computed yet
-    bool have_built_area = false;
-    PyrUpdateInfo update_info{};
-    // ---- pyr_scene_set_objects / pyr_scene_pose: the objects with the poses the scene is in (identity when they are set), the rest
-    // pose on the device, and whether the host description above lags behind the staging arrays (a pose leaves it so; whoever
-    // reads it fetches first)
-    std::vector<devpose::DevObject> pose_table;
-    uint32_t posed_triangles = 0, posed_spheres = 0;
-    DeviceBuffer rest_positions, rest_normals, rest_frames, rest_spheres, pose_objects, pose_flag;
-    bool geometry_stale = false;
-    ~PyrScene() {
-        if (tail_count) (void)hipFree(tail_count);
-    }
-};
+PyrScene::~PyrScene() {
+    if (tail_count) (void)hipFree(tail_count);
+}
 
 namespace pyr {
-int api_fail(int code, const std::string& message) { return fail(code, message); }
 int scene_device(const PyrScene* scene) { return scene->device; }
 } // namespace pyr
 
@@ -469,17 +394,14 @@ void plane_frame_from_normal(const float n[3], float q[4]) {
     }
 }
 
+} // namespace
+
+namespace pyr {
+
 double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b) { return std::chrono::duration<double, std::milli>(b - a).count(); }
 
-// pyrite_gpu.h "Coordinates": what pack_geometry and pyr_scene_update refuse, in the same words
-constexpr float kMaxCoordinate = 1.0e15f;
 const char* const kCoordinateRangeMessage =
     "a primitive lies beyond 1e15 units from the origin (or is not finite): outside the range the kernels' arithmetic is verified for";
-bool within_coordinate_range(const PrimBounds& b) {
-    for (int a = 0; a < 3; ++a)
-        if (!(std::fabs(b.lo[a]) <= kMaxCoordinate && std::fabs(b.hi[a]) <= kMaxCoordinate)) return false;
-    return true;
-}
 
 // One DevLamp from the description: a shape lamp gathers its shape's vertices, normals, area and material (Lamp::sample touches
 // nothing else). Scene creation and pyr_scene_update both pack lamps here, so a moved lamp gets creation's arithmetic.
@@ -754,6 +676,10 @@ int pack_geometry(const PyrSceneDesc* d, PyrScene* s, uint32_t builder) {
     return PYR_OK;
 }
 
+} // namespace pyr
+
+namespace {
+
 int pack_and_upload(const PyrSceneDesc* d, PyrScene* s, uint32_t builder) {
     const auto t_start = std::chrono::steady_clock::now();
     const bool wide_vm = s->program_info.wide != 0;
@@ -916,7 +842,7 @@ int pack_and_upload(const PyrSceneDesc* d, PyrScene* s, uint32_t builder) {
 
     // the geometry part last: it reads what the programs decided (needs_interpreter, the staged tables' size) and nothing else
     if ((rc = pack_geometry(d, s, builder)) != PYR_OK) return rc;
-    s->keep_geometry(d);
+    s->live.keep(d);
     PyrBuildInfo& build_info = s->build_info; // all of scene creation, not the geometry part alone
     build_info.total_ms = (float)ms_between(t_start, std::chrono::steady_clock::now());
     build_info.pack_upload_ms = build_info.total_ms - build_info.bounds_ms - build_info.tree_ms - build_info.finish_ms - build_info.collapse_ms;
@@ -1498,487 +1424,7 @@ int pyr_scene_bvh_info(PyrScene* scene, PyrBvhInfo* out) {
 
 } // extern "C"
 
-// ------------------------------------------------------------------------------------------------ pyr_scene_update
-namespace {
-
-// What both forms refuse before any device is looked for, in the order pyrite_gpu.h gives.
-int check_update_args(const PyrScene* scene, const PyrGeometryUpdate* u) {
-    if (!u) return fail(PYR_ERR_INVALID_ARGUMENT, "null update");
-    if (u->mode != PYR_UPDATE_REFIT && u->mode != PYR_UPDATE_REBUILD) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrGeometryUpdate.mode is neither PYR_UPDATE_REFIT nor PYR_UPDATE_REBUILD");
-    for (uint32_t word : u->reserved)
-        if (word != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrGeometryUpdate.reserved must be zero");
-    if (u->num_triangles == 0 && (u->tri_positions || u->tri_normals || u->tri_frames)) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrGeometryUpdate.num_triangles is 0 but a triangle array is given");
-    if (u->num_spheres == 0 && u->spheres) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrGeometryUpdate.num_spheres is 0 but spheres are given");
-    if (!scene) return fail(PYR_ERR_INVALID_ARGUMENT, "null scene");
-    if (u->num_triangles != scene->geometry.num_triangles) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrGeometryUpdate.num_triangles is not the scene's");
-    if (u->num_spheres != scene->geometry.num_spheres) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrGeometryUpdate.num_spheres is not the scene's");
-    if (scene->live_sessions != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "the scene has a live PyrSession: destroy it before the update");
-    if (u->mode == PYR_UPDATE_REFIT && scene->spatial_splits)
-        return fail(PYR_ERR_UNSUPPORTED, "the scene's tree was built with spatial splits (PYRITE_SPATIAL_SPLITS=1): its leaves hold clipped boxes, ask for PYR_UPDATE_REBUILD");
-    return PYR_OK;
-}
-
-// The refit's schedules and scratch, made from the trees on the device at the first refit after a build -- scene creation pays
-// nothing for them. The binary tree is fetched for it anyway, so its area sum at the build is taken here too.
-int prepare_refit(PyrScene* s) {
-    if (s->have_schedule) return PYR_OK;
-    std::vector<Node64> nodes(s->info.num_nodes);
-    HIP_TRY(hipMemcpy(nodes.data(), s->nodes.ptr, nodes.size() * sizeof(Node64), hipMemcpyDeviceToHost));
-    if (!s->have_built_area) s->built_area = child_area_sum(nodes.data(), nodes.size()), s->have_built_area = true;
-    const RefitSchedule binary = refit_schedule(nodes.data(), nodes.size());
-    int rc;
-    if ((rc = s->upd_order_binary.upload(binary.order.data(), binary.order.size() * 4)) != PYR_OK) return rc;
-    s->sched_binary = binary.begin;
-    s->sched_wide.clear();
-    if (s->info.num_wide_nodes) {
-        std::vector<Node128> wide(s->info.num_wide_nodes);
-        HIP_TRY(hipMemcpy(wide.data(), s->wide_nodes.ptr, wide.size() * sizeof(Node128), hipMemcpyDeviceToHost));
-        const RefitSchedule sched = refit_schedule(wide.data(), wide.size());
-        if ((rc = s->upd_order_wide.upload(sched.order.data(), sched.order.size() * 4)) != PYR_OK) return rc;
-        s->sched_wide = sched.begin;
-    }
-    if ((rc = s->upd_bounds.alloc((size_t)s->dev.num_prims * 32)) != PYR_OK) return rc;
-    if ((rc = s->upd_max_abs.alloc(4)) != PYR_OK) return rc;
-    s->have_schedule = true;
-    return PYR_OK;
-}
-
-// a buffer of the scene that holds `bytes` (allocated once, kept)
-int reserve(DeviceBuffer& b, size_t bytes) {
-    if (b.ptr && b.bytes >= bytes) return PYR_OK;
-    return b.alloc(bytes);
-}
-
-// The scene's records, trees and refit scratch as the refit kernels take them; the caller adds where the arrays are read and
-// which records the call rewrites.
-devrefit::Ctx refit_context(PyrScene* s) {
-    devrefit::Ctx c{};
-    c.prims = (float*)s->prims.ptr, c.num_prims = s->dev.num_prims;
-    c.pair_prims = s->info.num_pair_records ? (float*)s->pair_prims.ptr : nullptr, c.num_pairs = s->info.num_pair_records;
-    c.tri_shade = (float*)s->tri_shade.ptr;
-    c.tri_tex = s->tri_tex.bytes ? (float*)s->tri_tex.ptr : nullptr;
-    c.sphere_table = (float*)s->spheres.ptr;
-    c.num_triangles = s->geometry.num_triangles, c.num_spheres = s->geometry.num_spheres;
-    c.bounds = (float*)s->upd_bounds.ptr, c.max_abs_bits = (uint32_t*)s->upd_max_abs.ptr;
-    c.nodes = (Node64*)s->nodes.ptr, c.num_nodes = s->info.num_nodes;
-    c.wide_nodes = s->info.num_wide_nodes ? (Node128*)s->wide_nodes.ptr : nullptr, c.num_wide_nodes = s->info.num_wide_nodes;
-    c.wide_pair_nodes = s->info.num_pair_records ? (Node128*)s->wide_pair_nodes.ptr : nullptr;
-    return c;
-}
-
-// The records, then every box: one launch per height and tree, deepest nodes first. `waits`: the blocking form, whose stage times
-// are the device's. Fills the rest of `info` and makes it the scene's.
-int enqueue_refit(PyrScene* s, const devrefit::Ctx& c, bool waits, hipStream_t stream, std::chrono::steady_clock::time_point t_start,
-                  std::chrono::steady_clock::time_point t_uploaded, PyrUpdateInfo info) {
-    hipError_t e = devrefit::launch_repack(c, stream);
-    if (e != hipSuccess) return hip_fail(e, "refit: repack kernels");
-    if (waits) HIP_TRY(hipStreamSynchronize(stream));
-    const auto t_prims = std::chrono::steady_clock::now();
-    for (size_t h = 0; h + 1 < s->sched_binary.size(); ++h) {
-        e = devrefit::launch_refit_binary(c, (const uint32_t*)s->upd_order_binary.ptr + s->sched_binary[h], s->sched_binary[h + 1] - s->sched_binary[h], stream);
-        if (e != hipSuccess) return hip_fail(e, "refit: binary tree");
-    }
-    for (size_t h = 0; h + 1 < s->sched_wide.size(); ++h) {
-        e = devrefit::launch_refit_wide(c, (const uint32_t*)s->upd_order_wide.ptr + s->sched_wide[h], s->sched_wide[h + 1] - s->sched_wide[h], stream);
-        if (e != hipSuccess) return hip_fail(e, "refit: four-child tree");
-    }
-    if (waits) HIP_TRY(hipStreamSynchronize(stream));
-    const auto t_end = std::chrono::steady_clock::now();
-    info.levels = s->sched_binary.empty() ? 0u : (uint32_t)s->sched_binary.size() - 1u;
-    info.updates = s->update_info.updates + 1u;
-    info.upload_ms = (float)ms_between(t_start, t_uploaded);
-    info.prims_ms = (float)ms_between(t_uploaded, t_prims);
-    info.refit_ms = (float)ms_between(t_prims, t_end);
-    info.total_ms = (float)ms_between(t_start, t_end);
-    s->update_info = info;
-    return PYR_OK;
-}
-
-// The host description follows the staging arrays a pose wrote (nothing else leaves it behind).
-int fetch_geometry(PyrScene* s) {
-    if (!s->geometry_stale) return PYR_OK;
-    PyrScene::Geometry& g = s->geometry;
-    HIP_TRY(hipSetDevice(s->device));
-    HIP_TRY(hipDeviceSynchronize());
-    if (g.num_triangles) {
-        HIP_TRY(hipMemcpy(g.tri_positions.data(), s->upd_positions.ptr, g.tri_positions.size() * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(g.tri_normals.data(), s->upd_normals.ptr, g.tri_normals.size() * 4, hipMemcpyDeviceToHost));
-        if (g.has_frames) HIP_TRY(hipMemcpy(g.tri_frames.data(), s->upd_frames.ptr, g.tri_frames.size() * 4, hipMemcpyDeviceToHost));
-    }
-    if (g.num_spheres) HIP_TRY(hipMemcpy(g.spheres.data(), s->upd_spheres.ptr, g.spheres.size() * 4, hipMemcpyDeviceToHost));
-    s->geometry_stale = false;
-    return PYR_OK;
-}
-
-// (the description is current: whoever forgets the objects has fetched it)
-void forget_objects(PyrScene* s) {
-    s->pose_table.clear();
-    s->posed_triangles = s->posed_spheres = 0;
-    for (DeviceBuffer* b : {&s->rest_positions, &s->rest_normals, &s->rest_frames, &s->rest_spheres, &s->pose_objects}) b->release();
-}
-
-int scene_update(PyrScene* s, const PyrGeometryUpdate* u, bool device_arrays, hipStream_t stream) {
-    const auto t_start = std::chrono::steady_clock::now();
-    HIP_TRY(hipSetDevice(s->device));
-    PyrScene::Geometry& g = s->geometry;
-    const size_t nt = g.num_triangles, ns = g.num_spheres;
-    int rc = fetch_geometry(s); // a pose left the description behind: what stays comes from it
-    if (rc != PYR_OK) return rc;
-    // ---- the new arrays on the host: the caller's own, or copies of the device arrays
-    std::vector<float> fetched[4];
-    const float* given[4] = {u->tri_positions, u->tri_normals, u->tri_frames, u->spheres};
-    const size_t floats[4] = {9 * nt, 9 * nt, 12 * nt, 4 * ns};
-    const float* host[4] = {given[0], given[1], given[2], given[3]};
-    if (device_arrays) {
-        for (int k = 0; k < 4; ++k) {
-            if (!given[k]) continue;
-            fetched[k].resize(floats[k]);
-            HIP_TRY(hipMemcpyAsync(fetched[k].data(), given[k], floats[k] * 4, hipMemcpyDeviceToHost, stream));
-            host[k] = fetched[k].data();
-        }
-        HIP_TRY(hipStreamSynchronize(stream));
-    }
-    // ---- the coordinate check of scene creation, on the bounds of what moved, before anything of the scene is written
-    if (host[3])
-        for (size_t i = 0; i < ns; ++i) {
-            PrimBounds b;
-            lvl::sphere_bounds(host[3] + 4 * i, b.lo, b.hi);
-            if (!within_coordinate_range(b)) return fail(PYR_ERR_UNSUPPORTED, kCoordinateRangeMessage);
-        }
-    if (host[0])
-        for (size_t i = 0; i < nt; ++i) {
-            PrimBounds b;
-            lvl::triangle_bounds(host[0] + 9 * i, b.lo, b.hi);
-            if (!within_coordinate_range(b)) return fail(PYR_ERR_UNSUPPORTED, kCoordinateRangeMessage);
-        }
-    PyrUpdateInfo info{};
-    info.mode_used = u->mode;
-    info.area_ratio = 1.0;
-    auto commit = [&]() { // the description the scene keeps follows the device
-        if (host[0] || host[1] || host[2] || host[3]) forget_objects(s); // new arrays are a new geometry, not a pose of the old one
-        if (host[0]) g.tri_positions.assign(host[0], host[0] + floats[0]);
-        if (host[1]) g.tri_normals.assign(host[1], host[1] + floats[1]);
-        if (host[2]) g.tri_frames.assign(host[2], host[2] + floats[2]), g.has_frames = true;
-        if (host[3]) g.spheres.assign(host[3], host[3] + floats[3]);
-    };
-
-    if (u->mode == PYR_UPDATE_REBUILD) {
-        // the geometry part of scene creation over the description with the new arrays; every buffer it uploads is replaced, so
-        // nothing of this scene may be in flight
-        HIP_TRY(hipDeviceSynchronize());
-        PyrSceneDesc d = g.view();
-        if (host[0]) d.tri_positions = host[0];
-        if (host[1]) d.tri_normals = host[1];
-        if (host[2]) d.tri_frames = host[2];
-        if (host[3]) d.spheres = host[3];
-        const PyrBuildInfo build_before = s->build_info;
-        rc = pack_geometry(&d, s, s->builder);
-        if (rc != PYR_OK) {
-            s->build_info = build_before;
-            return rc;
-        }
-        commit();
-        s->have_schedule = s->have_built_area = s->upd_positions_current = false;
-        info.updates = 0;
-        info.total_ms = (float)ms_between(t_start, std::chrono::steady_clock::now());
-        s->update_info = info;
-        return PYR_OK;
-    }
-
-    // ---- refit
-    rc = prepare_refit(s);
-    if (rc != PYR_OK) return rc;
-    devrefit::Ctx c = refit_context(s);
-    c.write_triangles = given[0] ? 1u : 0u, c.write_spheres = given[3] ? 1u : 0u;
-    // where the kernels read the arrays: the caller's device arrays, or the scene's own copies of the host arrays. The bounds of
-    // every leaf need the triangles as they are now, moved or not.
-    DeviceBuffer* own[4] = {&s->upd_positions, &s->upd_normals, &s->upd_frames, &s->upd_spheres};
-    const float* source[4] = {nullptr, nullptr, nullptr, nullptr};
-    for (int k = 0; k < 4; ++k) {
-        if (!given[k]) continue;
-        if (device_arrays) {
-            source[k] = given[k];
-        } else {
-            if ((rc = reserve(*own[k], floats[k] * 4)) != PYR_OK) return rc;
-            HIP_TRY(hipMemcpyAsync(own[k]->ptr, given[k], floats[k] * 4, hipMemcpyHostToDevice, stream));
-            source[k] = (const float*)own[k]->ptr;
-        }
-    }
-    if (given[0]) s->upd_positions_current = !device_arrays;
-    if (!given[0] && nt) { // the triangles stay: their positions as the scene keeps them
-        if (!s->upd_positions_current) {
-            if ((rc = reserve(s->upd_positions, floats[0] * 4)) != PYR_OK) return rc;
-            HIP_TRY(hipMemcpyAsync(s->upd_positions.ptr, g.tri_positions.data(), floats[0] * 4, hipMemcpyHostToDevice, stream));
-            s->upd_positions_current = true;
-        }
-        source[0] = (const float*)s->upd_positions.ptr;
-    }
-    c.tri_positions = source[0], c.tri_normals = source[1], c.tri_frames = source[2];
-    c.spheres = source[3] ? source[3] : (const float*)s->spheres.ptr;
-    commit();
-    // the lamp records, on the host with creation's arithmetic (lamps are few)
-    bool shape_lamps = false;
-    for (const PyrLamp& l : g.lamps) shape_lamps = shape_lamps || l.kind == PYR_LAMP_SHAPE;
-    if (shape_lamps) {
-        HIP_TRY(hipStreamSynchronize(stream)); // an earlier update's copy may still read upd_lamps
-        const PyrSceneDesc d = g.view();
-        s->upd_lamps.resize(g.lamps.size());
-        for (uint32_t i = 0; i < (uint32_t)g.lamps.size(); ++i) s->upd_lamps[i] = pack_lamp(&d, i);
-        HIP_TRY(hipMemcpyAsync(s->lamps.ptr, s->upd_lamps.data(), s->upd_lamps.size() * sizeof(DevLamp), hipMemcpyHostToDevice, stream));
-    }
-    HIP_TRY(hipMemsetAsync(s->upd_max_abs.ptr, 0, 4, stream));
-    if (!device_arrays) HIP_TRY(hipStreamSynchronize(stream));
-    const auto t_uploaded = std::chrono::steady_clock::now();
-    return enqueue_refit(s, c, !device_arrays, stream, t_start, t_uploaded, info);
-}
-
-// ------------------------------------------------------------------------------------------------ pyr_scene_pose
-// What pyr_scene_pose refuses before any device is looked for, in the order pyrite_gpu.h gives.
-int check_pose_args(const PyrScene* scene, const PyrPoseUpdate* u) {
-    if (!u) return fail(PYR_ERR_INVALID_ARGUMENT, "null update");
-    if (!scene) return fail(PYR_ERR_INVALID_ARGUMENT, "null scene");
-    if (u->mode != PYR_UPDATE_REFIT && u->mode != PYR_UPDATE_REBUILD) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrPoseUpdate.mode is neither PYR_UPDATE_REFIT nor PYR_UPDATE_REBUILD");
-    for (uint32_t word : u->reserved)
-        if (word != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrPoseUpdate.reserved must be zero");
-    if (u->poses)
-        for (uint32_t i = 0; i < u->num_objects; ++i)
-            for (uint32_t word : u->poses[i].reserved)
-                if (word != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectPose.reserved must be zero");
-    if (scene->pose_table.empty()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrPoseUpdate.num_objects: the scene has no objects (pyr_scene_set_objects names them)");
-    if (u->num_objects != scene->pose_table.size()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrPoseUpdate.num_objects is not the scene's");
-    if (!u->poses) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrPoseUpdate.poses is null");
-    for (uint32_t i = 0; i < u->num_objects; ++i) {
-        const PyrObjectPose& p = u->poses[i];
-        for (float x : p.transform)
-            if (!std::isfinite(x)) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectPose.transform has an entry that is not finite");
-        if (!std::isfinite(p.scale)) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectPose.scale is not finite");
-    }
-    for (uint32_t i = 0; i < u->num_objects; ++i) {
-        const float* m = u->poses[i].transform;
-        if (!(m[3] == 0.0f && m[7] == 0.0f && m[11] == 0.0f && m[15] == 1.0f)) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectPose.transform: the last row must be 0, 0, 0, 1");
-    }
-    if (scene->live_sessions != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "the scene has a live PyrSession: destroy it before the pose");
-    if (u->mode == PYR_UPDATE_REFIT && scene->spatial_splits)
-        return fail(PYR_ERR_UNSUPPORTED, "the scene's tree was built with spatial splits (PYRITE_SPATIAL_SPLITS=1): its leaves hold clipped boxes, ask for PYR_UPDATE_REBUILD");
-    return PYR_OK;
-}
-
-void set_pose(devpose::DevObject& o, const float* transform, float scale) {
-    static const float identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    bool same = scale == 1.0f;
-    for (int k = 0; k < 16; ++k) o.pose.m[k] = transform[k], same = same && transform[k] == identity[k];
-    o.pose.scale = scale;
-    o.pose.identity = same ? 1u : 0u;
-}
-
-devpose::Ctx pose_context(PyrScene* s) {
-    devpose::Ctx c{};
-    c.rest_positions = (const float*)s->rest_positions.ptr, c.rest_normals = (const float*)s->rest_normals.ptr;
-    c.rest_frames = s->geometry.has_frames ? (const float*)s->rest_frames.ptr : nullptr;
-    c.rest_spheres = (const float*)s->rest_spheres.ptr;
-    c.positions = (float*)s->upd_positions.ptr, c.normals = (float*)s->upd_normals.ptr, c.frames = (float*)s->upd_frames.ptr, c.spheres = (float*)s->upd_spheres.ptr;
-    c.objects = (const devpose::DevObject*)s->pose_objects.ptr, c.num_objects = (uint32_t)s->pose_table.size();
-    c.num_triangles = s->geometry.num_triangles, c.num_spheres = s->geometry.num_spheres;
-    c.posed_triangles = s->posed_triangles, c.posed_spheres = s->posed_spheres;
-    c.beyond_range = (uint32_t*)s->pose_flag.ptr;
-    c.lamps = (DevLamp*)s->lamps.ptr, c.num_lamps = (uint32_t)s->geometry.lamps.size();
-    return c;
-}
-
-// Every object's primitives from the rest pose into the staging arrays under `table`, and the flag back: the one wait.
-int run_pose(PyrScene* s, const std::vector<devpose::DevObject>& table, hipStream_t stream, uint32_t& beyond_range) {
-    HIP_TRY(hipMemcpyAsync(s->pose_objects.ptr, table.data(), table.size() * sizeof(devpose::DevObject), hipMemcpyHostToDevice, stream));
-    HIP_TRY(hipMemsetAsync(s->pose_flag.ptr, 0, 4, stream));
-    const hipError_t e = devpose::launch_pose(pose_context(s), stream);
-    if (e != hipSuccess) return hip_fail(e, "pose kernels");
-    HIP_TRY(hipMemcpyAsync(&beyond_range, s->pose_flag.ptr, 4, hipMemcpyDeviceToHost, stream));
-    HIP_TRY(hipStreamSynchronize(stream));
-    return PYR_OK;
-}
-
-int scene_pose(PyrScene* s, const PyrPoseUpdate* u, hipStream_t stream) {
-    const auto t_start = std::chrono::steady_clock::now();
-    HIP_TRY(hipSetDevice(s->device));
-    PyrScene::Geometry& g = s->geometry;
-    int rc;
-    if (u->mode == PYR_UPDATE_REFIT && (rc = prepare_refit(s)) != PYR_OK) return rc;
-    std::vector<devpose::DevObject> table = s->pose_table;
-    for (uint32_t i = 0; i < u->num_objects; ++i) set_pose(table[i], u->poses[i].transform, u->poses[i].scale);
-    uint32_t beyond_range = 0;
-    if ((rc = run_pose(s, table, stream, beyond_range)) != PYR_OK) return rc;
-    if (beyond_range != 0) { // no record has been touched: the staging arrays go back to the poses the scene is in
-        if ((rc = run_pose(s, s->pose_table, stream, beyond_range)) != PYR_OK) return rc;
-        return fail(PYR_ERR_UNSUPPORTED, kCoordinateRangeMessage);
-    }
-    PyrUpdateInfo info{};
-    info.mode_used = u->mode;
-    info.area_ratio = 1.0;
-    const auto t_posed = std::chrono::steady_clock::now();
-
-    if (u->mode == PYR_UPDATE_REBUILD) {
-        // the posed arrays to the host, then the geometry part of scene creation over them, as pyr_scene_update does
-        std::vector<float> posed[4];
-        const DeviceBuffer* from[4] = {&s->upd_positions, &s->upd_normals, &s->upd_frames, &s->upd_spheres};
-        const size_t floats[4] = {g.tri_positions.size(), g.tri_normals.size(), g.has_frames ? g.tri_frames.size() : 0, g.spheres.size()};
-        HIP_TRY(hipDeviceSynchronize());
-        for (int k = 0; k < 4; ++k) {
-            posed[k].resize(floats[k]);
-            if (floats[k]) HIP_TRY(hipMemcpy(posed[k].data(), from[k]->ptr, floats[k] * 4, hipMemcpyDeviceToHost));
-        }
-        PyrSceneDesc d = g.view();
-        d.tri_positions = posed[0].data(), d.tri_normals = posed[1].data(), d.spheres = posed[3].data();
-        if (g.has_frames) d.tri_frames = posed[2].data();
-        const PyrBuildInfo build_before = s->build_info;
-        rc = pack_geometry(&d, s, s->builder);
-        if (rc != PYR_OK) {
-            s->build_info = build_before;
-            uint32_t ignored = 0;
-            const int back = run_pose(s, s->pose_table, stream, ignored);
-            return back != PYR_OK ? back : rc;
-        }
-        g.tri_positions.swap(posed[0]), g.tri_normals.swap(posed[1]), g.spheres.swap(posed[3]);
-        if (g.has_frames) g.tri_frames.swap(posed[2]);
-        s->geometry_stale = false;
-        s->pose_table.swap(table);
-        s->have_schedule = s->have_built_area = false;
-        info.updates = 0;
-        info.upload_ms = (float)ms_between(t_start, t_posed);
-        info.total_ms = (float)ms_between(t_start, std::chrono::steady_clock::now());
-        s->update_info = info;
-        return PYR_OK;
-    }
-
-    // ---- refit: every record and box from the staging arrays, as the host form of pyr_scene_update given all four arrays
-    s->pose_table.swap(table);
-    s->geometry_stale = true;
-    devrefit::Ctx c = refit_context(s);
-    c.write_triangles = g.num_triangles ? 1u : 0u, c.write_spheres = g.num_spheres ? 1u : 0u;
-    c.tri_positions = g.num_triangles ? (const float*)s->upd_positions.ptr : nullptr;
-    c.tri_normals = g.num_triangles ? (const float*)s->upd_normals.ptr : nullptr;
-    c.tri_frames = g.num_triangles && g.has_frames ? (const float*)s->upd_frames.ptr : nullptr;
-    c.spheres = (const float*)s->upd_spheres.ptr;
-    const hipError_t e = devpose::launch_lamps(pose_context(s), stream);
-    if (e != hipSuccess) return hip_fail(e, "pose: lamp records");
-    HIP_TRY(hipMemsetAsync(s->upd_max_abs.ptr, 0, 4, stream));
-    return enqueue_refit(s, c, false, stream, t_start, t_posed, info);
-}
-
-// ranges inside the counts and pairwise disjoint, triangles and spheres each
-int check_ranges(const PyrScene* scene, const PyrObjectRange* ranges, uint32_t n) {
-    std::vector<std::pair<uint64_t, uint64_t>> tri, sph;
-    for (uint32_t i = 0; i < n; ++i) {
-        const PyrObjectRange& r = ranges[i];
-        if ((uint64_t)r.first_triangle + r.num_triangles > scene->geometry.num_triangles) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectRange: a triangle range reaches past the scene's triangles");
-        if ((uint64_t)r.first_sphere + r.num_spheres > scene->geometry.num_spheres) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectRange: a sphere range reaches past the scene's spheres");
-        if (r.num_triangles) tri.emplace_back(r.first_triangle, (uint64_t)r.first_triangle + r.num_triangles);
-        if (r.num_spheres) sph.emplace_back(r.first_sphere, (uint64_t)r.first_sphere + r.num_spheres);
-    }
-    for (auto* list : {&tri, &sph}) {
-        std::sort(list->begin(), list->end());
-        for (size_t k = 1; k < list->size(); ++k)
-            if ((*list)[k].first < (*list)[k - 1].second) return fail(PYR_ERR_INVALID_ARGUMENT, list == &tri ? "PyrObjectRange: two triangle ranges overlap" : "PyrObjectRange: two sphere ranges overlap");
-    }
-    return PYR_OK;
-}
-
-// a staging array that holds a copy of `rest` (which holds `floats` floats of the description)
-int capture(DeviceBuffer& rest, DeviceBuffer& staging, const std::vector<float>& from, size_t floats) {
-    int rc;
-    if ((rc = rest.upload(from.data(), floats * 4)) != PYR_OK) return rc;
-    if ((rc = reserve(staging, floats * 4)) != PYR_OK) return rc;
-    if (floats) HIP_TRY(hipMemcpy(staging.ptr, rest.ptr, floats * 4, hipMemcpyDeviceToDevice));
-    return PYR_OK;
-}
-
-} // namespace
-
-extern "C" {
-
-int pyr_scene_set_objects(PyrScene* scene, const PyrObjectRange* ranges, uint32_t num_objects) {
-    if (num_objects != 0 && !ranges) return fail(PYR_ERR_INVALID_ARGUMENT, "null ranges with a non-zero num_objects");
-    if (!scene) return fail(PYR_ERR_INVALID_ARGUMENT, "null scene");
-    int rc = check_ranges(scene, ranges, num_objects);
-    if (rc != PYR_OK) return rc;
-    if (num_objects == 0 && scene->pose_table.empty()) return PYR_OK;
-    HIP_TRY(hipSetDevice(scene->device));
-    HIP_TRY(hipDeviceSynchronize());
-    if ((rc = fetch_geometry(scene)) != PYR_OK) return rc; // the rest pose is the geometry as it is now
-    forget_objects(scene);
-    if (num_objects == 0) return PYR_OK;
-    PyrScene::Geometry& g = scene->geometry;
-    if ((rc = capture(scene->rest_positions, scene->upd_positions, g.tri_positions, g.tri_positions.size())) != PYR_OK) return rc;
-    if ((rc = capture(scene->rest_normals, scene->upd_normals, g.tri_normals, g.tri_normals.size())) != PYR_OK) return rc;
-    if ((rc = capture(scene->rest_frames, scene->upd_frames, g.tri_frames, g.has_frames ? g.tri_frames.size() : 0)) != PYR_OK) return rc;
-    if ((rc = capture(scene->rest_spheres, scene->upd_spheres, g.spheres, g.spheres.size())) != PYR_OK) return rc;
-    scene->upd_positions_current = true;
-    if ((rc = scene->pose_objects.alloc((size_t)num_objects * sizeof(devpose::DevObject))) != PYR_OK) return rc;
-    if (!scene->pose_flag.ptr && (rc = scene->pose_flag.alloc(4)) != PYR_OK) return rc;
-    static const float identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
-    scene->pose_table.resize(num_objects);
-    uint32_t triangle_lane = 0, sphere_lane = 0;
-    for (uint32_t i = 0; i < num_objects; ++i) {
-        devpose::DevObject& o = scene->pose_table[i];
-        set_pose(o, identity, 1.0f);
-        o.first_triangle = ranges[i].first_triangle, o.num_triangles = ranges[i].num_triangles;
-        o.first_sphere = ranges[i].first_sphere, o.num_spheres = ranges[i].num_spheres;
-        o.triangle_lane = triangle_lane, o.sphere_lane = sphere_lane;
-        triangle_lane += o.num_triangles, sphere_lane += o.num_spheres; // disjoint ranges inside the counts: below 2^28 in all
-    }
-    scene->posed_triangles = triangle_lane, scene->posed_spheres = sphere_lane;
-    return PYR_OK;
-}
-
-int pyr_scene_pose(PyrScene* scene, const PyrPoseUpdate* update, void* hip_stream) {
-    int rc = check_pose_args(scene, update);
-    if (rc != PYR_OK) return rc;
-    return scene_pose(scene, update, (hipStream_t)hip_stream);
-}
-
-int pyr_scene_geometry(PyrScene* scene, float* tri_positions, float* tri_normals, float* tri_frames, float* spheres) {
-    if (!scene) return fail(PYR_ERR_INVALID_ARGUMENT, "null scene");
-    const PyrScene::Geometry& g = scene->geometry;
-    if (tri_frames && !g.has_frames) return fail(PYR_ERR_INVALID_ARGUMENT, "tri_frames: the scene was created without frames and keeps none");
-    int rc = fetch_geometry(scene);
-    if (rc != PYR_OK) return rc;
-    if (tri_positions && !g.tri_positions.empty()) std::memcpy(tri_positions, g.tri_positions.data(), g.tri_positions.size() * 4);
-    if (tri_normals && !g.tri_normals.empty()) std::memcpy(tri_normals, g.tri_normals.data(), g.tri_normals.size() * 4);
-    if (tri_frames && !g.tri_frames.empty()) std::memcpy(tri_frames, g.tri_frames.data(), g.tri_frames.size() * 4);
-    if (spheres && !g.spheres.empty()) std::memcpy(spheres, g.spheres.data(), g.spheres.size() * 4);
-    return PYR_OK;
-}
-
-int pyr_scene_update(PyrScene* scene, const PyrGeometryUpdate* update) {
-    int rc = check_update_args(scene, update);
-    if (rc != PYR_OK) return rc;
-    HIP_TRY(hipSetDevice(scene->device));
-    HIP_TRY(hipDeviceSynchronize()); // blocking: nothing of this scene is in flight while its records change
-    return scene_update(scene, update, false, nullptr);
-}
-
-int pyr_scene_update_device(PyrScene* scene, const PyrGeometryUpdate* update, void* hip_stream) {
-    int rc = check_update_args(scene, update);
-    if (rc != PYR_OK) return rc;
-    return scene_update(scene, update, true, (hipStream_t)hip_stream);
-}
-
-int pyr_scene_update_info(PyrScene* scene, PyrUpdateInfo* out) {
-    if (!scene || !out) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
-    HIP_TRY(hipSetDevice(scene->device));
-    HIP_TRY(hipDeviceSynchronize());
-    std::vector<Node64> nodes(scene->info.num_nodes);
-    HIP_TRY(hipMemcpy(nodes.data(), scene->nodes.ptr, nodes.size() * sizeof(Node64), hipMemcpyDeviceToHost));
-    const double now = child_area_sum(nodes.data(), nodes.size());
-    if (!scene->have_built_area) scene->built_area = now, scene->have_built_area = true; // no refit since the build: this is the built tree
-    *out = scene->update_info;
-    out->area_ratio = scene->built_area > 0.0 ? now / scene->built_area : 1.0;
-    return PYR_OK;
-}
-
-
-
 // ------------------------------------------------------------------------------------------------ progressive sessions
-} // extern "C"
-
 struct PyrSession {
     PyrScene* scene = nullptr;
     PyrCamera camera{};

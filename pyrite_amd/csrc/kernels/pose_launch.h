@@ -1,4 +1,4 @@
-// pose_launch.h -- what the pose kernels (kernels/pose.hip) and their host driver (api.cpp pyr_scene_pose) share.
+// pose_launch.h -- what the pose kernels (kernels/pose.hip) and their host driver (live_scene.cpp pyr_scene_pose) share.
 #pragma once
 #include <hip/hip_runtime.h>
 

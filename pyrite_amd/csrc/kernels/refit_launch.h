@@ -1,4 +1,4 @@
-// refit_launch.h -- what the refit kernels (kernels/refit.hip) and their host driver (api.cpp pyr_scene_update) share.
+// refit_launch.h -- what the refit kernels (kernels/refit.hip) and their host driver (live_scene.cpp pyr_scene_update) share.
 #pragma once
 #include <hip/hip_runtime.h>
 

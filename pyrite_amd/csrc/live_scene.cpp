@@ -1,0 +1,479 @@
+// live_scene.cpp -- everything that moves a scene after creation: pyr_scene_update[_device], pyr_scene_set_objects,
+// pyr_scene_pose, pyr_scene_geometry, pyr_scene_update_info. LiveGeometry (scene_internal.h) says where the geometry is and
+// which copies are valid; rebuild_from and refit_from are the two ways new arrays reach the records and trees on the device.
+#include <algorithm>
+#include <cmath>
+#include <cstring>
+
+#include "bvh_level.h"
+#include "kernels/refit_launch.h"
+#include "scene_internal.h"
+
+using namespace pyr;
+
+// ------------------------------------------------------------------------------------------------ the live state
+void LiveGeometry::keep(const PyrSceneDesc* d) {
+    num_triangles = d->num_triangles, num_spheres = d->num_spheres;
+    const float* const from[NUM_ARRAYS] = {d->tri_positions, d->tri_normals, d->tri_frames, d->spheres};
+    arrays[FRAMES].kept = d->tri_frames != nullptr;
+    for (int k = 0; k < NUM_ARRAYS; ++k)
+        if (arrays[k].kept) arrays[k].host.assign(from[k], from[k] + floats(k));
+    tri_material.assign(d->tri_material, d->tri_material + num_triangles);
+    has_uvs = d->tri_uvs != nullptr, has_tex_scale = d->sphere_tex_scale != nullptr;
+    if (has_uvs) tri_uvs.assign(d->tri_uvs, d->tri_uvs + 6 * (size_t)num_triangles);
+    sphere_material.assign(d->sphere_material, d->sphere_material + num_spheres);
+    if (has_tex_scale) sphere_tex_scale.assign(d->sphere_tex_scale, d->sphere_tex_scale + 2 * (size_t)num_spheres);
+    lamps.assign(d->lamps, d->lamps + d->num_lamps);
+}
+
+PyrSceneDesc LiveGeometry::view(const float* const with[NUM_ARRAYS]) const {
+    const float* a[NUM_ARRAYS];
+    for (int k = 0; k < NUM_ARRAYS; ++k) a[k] = with && with[k] ? with[k] : arrays[k].kept ? arrays[k].host.data() : nullptr;
+    PyrSceneDesc d{};
+    d.num_triangles = num_triangles, d.num_spheres = num_spheres, d.num_lamps = (uint32_t)lamps.size();
+    d.tri_positions = a[POSITIONS], d.tri_normals = a[NORMALS], d.tri_frames = a[FRAMES], d.spheres = a[SPHERES];
+    d.tri_material = tri_material.data(), d.sphere_material = sphere_material.data();
+    d.tri_uvs = has_uvs ? tri_uvs.data() : nullptr;
+    d.sphere_tex_scale = has_tex_scale ? sphere_tex_scale.data() : nullptr;
+    d.lamps = lamps.data();
+    return d;
+}
+
+// (the description is current: whoever forgets the objects has fetched it)
+void LiveGeometry::forget_objects() {
+    pose_table.clear();
+    posed_triangles = posed_spheres = 0;
+    for (LiveArray& a : arrays) a.rest.release();
+    pose_objects.release();
+}
+
+void LiveGeometry::adopted(const float* const given[NUM_ARRAYS], bool staged) {
+    if (given[POSITIONS] || given[NORMALS] || given[FRAMES] || given[SPHERES]) forget_objects(); // new arrays are a new geometry, not a pose of the old one
+    for (int k = 0; k < NUM_ARRAYS; ++k)
+        if (given[k]) arrays[k].host.assign(given[k], given[k] + floats(k)), arrays[k].kept = true;
+    if (given[POSITIONS]) positions_staged_ = staged;
+}
+
+namespace {
+
+using Clock = std::chrono::steady_clock;
+const float kIdentity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+enum { POSITIONS = LiveGeometry::POSITIONS, NORMALS = LiveGeometry::NORMALS, FRAMES = LiveGeometry::FRAMES, SPHERES = LiveGeometry::SPHERES, NUM_ARRAYS = LiveGeometry::NUM_ARRAYS };
+
+// What every way of moving a scene refuses, around what only one of them does (`specific`, which also refuses a null scene where
+// its entry point has not done so before): an unknown mode and a reserved word first; a live session and the refit of a
+// split-space tree last. `name`: the update's struct; `noun`: what the session's message calls the call.
+template <class Update, class Specific>
+int check_move(const PyrScene* scene, const Update* u, const std::string& name, const char* noun, Specific specific) {
+    if (u->mode != PYR_UPDATE_REFIT && u->mode != PYR_UPDATE_REBUILD) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".mode is neither PYR_UPDATE_REFIT nor PYR_UPDATE_REBUILD");
+    for (uint32_t word : u->reserved)
+        if (word != 0) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".reserved must be zero");
+    const int rc = specific();
+    if (rc != PYR_OK) return rc;
+    if (scene->live_sessions != 0) return fail(PYR_ERR_INVALID_ARGUMENT, std::string("the scene has a live PyrSession: destroy it before the ") + noun);
+    if (u->mode == PYR_UPDATE_REFIT && scene->spatial_splits)
+        return fail(PYR_ERR_UNSUPPORTED, "the scene's tree was built with spatial splits (PYRITE_SPATIAL_SPLITS=1): its leaves hold clipped boxes, ask for PYR_UPDATE_REBUILD");
+    return PYR_OK;
+}
+
+// What both forms of pyr_scene_update refuse before any device is looked for, in the order pyrite_gpu.h gives.
+int check_update_args(const PyrScene* scene, const PyrGeometryUpdate* u) {
+    if (!u) return fail(PYR_ERR_INVALID_ARGUMENT, "null update");
+    return check_move(scene, u, "PyrGeometryUpdate", "update", [&]() {
+        if (u->num_triangles == 0 && (u->tri_positions || u->tri_normals || u->tri_frames)) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrGeometryUpdate.num_triangles is 0 but a triangle array is given");
+        if (u->num_spheres == 0 && u->spheres) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrGeometryUpdate.num_spheres is 0 but spheres are given");
+        if (!scene) return fail(PYR_ERR_INVALID_ARGUMENT, "null scene");
+        if (u->num_triangles != scene->live.num_triangles) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrGeometryUpdate.num_triangles is not the scene's");
+        if (u->num_spheres != scene->live.num_spheres) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrGeometryUpdate.num_spheres is not the scene's");
+        return (int)PYR_OK;
+    });
+}
+
+// What pyr_scene_pose refuses before any device is looked for, in the order pyrite_gpu.h gives.
+int check_pose_args(const PyrScene* scene, const PyrPoseUpdate* u) {
+    if (!u) return fail(PYR_ERR_INVALID_ARGUMENT, "null update");
+    if (!scene) return fail(PYR_ERR_INVALID_ARGUMENT, "null scene");
+    return check_move(scene, u, "PyrPoseUpdate", "pose", [&]() {
+        if (u->poses)
+            for (uint32_t i = 0; i < u->num_objects; ++i)
+                for (uint32_t word : u->poses[i].reserved)
+                    if (word != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectPose.reserved must be zero");
+        if (scene->live.pose_table.empty()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrPoseUpdate.num_objects: the scene has no objects (pyr_scene_set_objects names them)");
+        if (u->num_objects != scene->live.pose_table.size()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrPoseUpdate.num_objects is not the scene's");
+        if (!u->poses) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrPoseUpdate.poses is null");
+        for (uint32_t i = 0; i < u->num_objects; ++i) {
+            const PyrObjectPose& p = u->poses[i];
+            for (float x : p.transform)
+                if (!std::isfinite(x)) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectPose.transform has an entry that is not finite");
+            if (!std::isfinite(p.scale)) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectPose.scale is not finite");
+        }
+        for (uint32_t i = 0; i < u->num_objects; ++i) {
+            const float* m = u->poses[i].transform;
+            if (!(m[3] == 0.0f && m[7] == 0.0f && m[11] == 0.0f && m[15] == 1.0f)) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectPose.transform: the last row must be 0, 0, 0, 1");
+        }
+        return (int)PYR_OK;
+    });
+}
+
+// The refit's schedules and scratch, made from the trees on the device at the first refit after a build -- scene creation pays
+// nothing for them. The binary tree is fetched for it anyway, so its area sum at the build is taken here too.
+int prepare_refit(PyrScene* s) {
+    LiveGeometry& live = s->live;
+    if (live.schedule_current()) return PYR_OK;
+    std::vector<Node64> nodes(s->info.num_nodes);
+    HIP_TRY(hipMemcpy(nodes.data(), s->nodes.ptr, nodes.size() * sizeof(Node64), hipMemcpyDeviceToHost));
+    if (!live.area_known()) live.area_at_build(child_area_sum(nodes.data(), nodes.size()));
+    const RefitSchedule binary = refit_schedule(nodes.data(), nodes.size());
+    int rc;
+    if ((rc = live.order_binary.upload(binary.order.data(), binary.order.size() * 4)) != PYR_OK) return rc;
+    live.sched_binary = binary.begin;
+    live.sched_wide.clear();
+    if (s->info.num_wide_nodes) {
+        std::vector<Node128> wide(s->info.num_wide_nodes);
+        HIP_TRY(hipMemcpy(wide.data(), s->wide_nodes.ptr, wide.size() * sizeof(Node128), hipMemcpyDeviceToHost));
+        const RefitSchedule sched = refit_schedule(wide.data(), wide.size());
+        if ((rc = live.order_wide.upload(sched.order.data(), sched.order.size() * 4)) != PYR_OK) return rc;
+        live.sched_wide = sched.begin;
+    }
+    if ((rc = live.bounds.alloc((size_t)s->dev.num_prims * 32)) != PYR_OK) return rc;
+    if ((rc = live.max_abs.alloc(4)) != PYR_OK) return rc;
+    live.scheduled();
+    return PYR_OK;
+}
+
+// Every record and every box from `sources` on the device (nullptr: that array stays; the positions are the triangles as they are
+// NOW, moved or not: the bounds of every leaf need them). The records first, then one launch per height and tree, deepest nodes
+// first. `waits`: the blocking form, whose stage times are the device's. `uploaded_at`: when the sources were complete, or nullptr:
+// now, once the uploads enqueued on `stream` are in. Fills the rest of `info` and makes it the scene's.
+int refit_from(PyrScene* s, const float* const sources[NUM_ARRAYS], bool write_triangles, bool write_spheres, bool waits, hipStream_t stream, Clock::time_point t_start,
+               const Clock::time_point* uploaded_at, PyrUpdateInfo info) {
+    LiveGeometry& live = s->live;
+    devrefit::Ctx c{};
+    c.prims = (float*)s->prims.ptr, c.num_prims = s->dev.num_prims;
+    c.pair_prims = s->info.num_pair_records ? (float*)s->pair_prims.ptr : nullptr, c.num_pairs = s->info.num_pair_records;
+    c.tri_shade = (float*)s->tri_shade.ptr;
+    c.tri_tex = s->tri_tex.bytes ? (float*)s->tri_tex.ptr : nullptr;
+    c.sphere_table = (float*)s->spheres.ptr;
+    c.num_triangles = live.num_triangles, c.num_spheres = live.num_spheres;
+    c.bounds = (float*)live.bounds.ptr, c.max_abs_bits = (uint32_t*)live.max_abs.ptr;
+    c.nodes = (Node64*)s->nodes.ptr, c.num_nodes = s->info.num_nodes;
+    c.wide_nodes = s->info.num_wide_nodes ? (Node128*)s->wide_nodes.ptr : nullptr, c.num_wide_nodes = s->info.num_wide_nodes;
+    c.wide_pair_nodes = s->info.num_pair_records ? (Node128*)s->wide_pair_nodes.ptr : nullptr;
+    c.write_triangles = write_triangles ? 1u : 0u, c.write_spheres = write_spheres ? 1u : 0u;
+    c.tri_positions = sources[POSITIONS], c.tri_normals = sources[NORMALS], c.tri_frames = sources[FRAMES];
+    c.spheres = sources[SPHERES] ? sources[SPHERES] : (const float*)s->spheres.ptr;
+    HIP_TRY(hipMemsetAsync(live.max_abs.ptr, 0, 4, stream));
+    if (waits) HIP_TRY(hipStreamSynchronize(stream));
+    const auto t_uploaded = uploaded_at ? *uploaded_at : Clock::now();
+    hipError_t e = devrefit::launch_repack(c, stream);
+    if (e != hipSuccess) return hip_fail(e, "refit: repack kernels");
+    if (waits) HIP_TRY(hipStreamSynchronize(stream));
+    const auto t_prims = Clock::now();
+    for (size_t h = 0; h + 1 < live.sched_binary.size(); ++h) {
+        e = devrefit::launch_refit_binary(c, (const uint32_t*)live.order_binary.ptr + live.sched_binary[h], live.sched_binary[h + 1] - live.sched_binary[h], stream);
+        if (e != hipSuccess) return hip_fail(e, "refit: binary tree");
+    }
+    for (size_t h = 0; h + 1 < live.sched_wide.size(); ++h) {
+        e = devrefit::launch_refit_wide(c, (const uint32_t*)live.order_wide.ptr + live.sched_wide[h], live.sched_wide[h + 1] - live.sched_wide[h], stream);
+        if (e != hipSuccess) return hip_fail(e, "refit: four-child tree");
+    }
+    if (waits) HIP_TRY(hipStreamSynchronize(stream));
+    const auto t_end = Clock::now();
+    info.levels = live.sched_binary.empty() ? 0u : (uint32_t)live.sched_binary.size() - 1u;
+    info.updates = live.update_info.updates + 1u;
+    info.upload_ms = (float)ms_between(t_start, t_uploaded);
+    info.prims_ms = (float)ms_between(t_uploaded, t_prims);
+    info.refit_ms = (float)ms_between(t_prims, t_end);
+    info.total_ms = (float)ms_between(t_start, t_end);
+    live.update_info = info;
+    return PYR_OK;
+}
+
+// The geometry part of scene creation over the description with `arrays` on the host in place of its own (nullptr: that array
+// stays) and the scene's builder: the only call of pack_geometry after creation. Every buffer it uploads is replaced, so the caller
+// has waited for whatever of this scene was in flight. A refusal leaves the scene as it was; otherwise the description adopts the
+// arrays (and so forgets the objects, if there is one), the refit starts over, and `info` becomes the scene's.
+int rebuild_from(PyrScene* s, const float* const arrays[NUM_ARRAYS], Clock::time_point t_start, PyrUpdateInfo info) {
+    const PyrSceneDesc d = s->live.view(arrays);
+    const PyrBuildInfo build_before = s->build_info;
+    const int rc = pack_geometry(&d, s, s->builder);
+    if (rc != PYR_OK) {
+        s->build_info = build_before;
+        return rc;
+    }
+    s->live.adopted(arrays, false);
+    s->live.built();
+    info.updates = 0;
+    info.total_ms = (float)ms_between(t_start, Clock::now());
+    s->live.update_info = info;
+    return PYR_OK;
+}
+
+// The host description follows the staging arrays a pose wrote (nothing else leaves it behind).
+int fetch_live_geometry(PyrScene* s) {
+    LiveGeometry& live = s->live;
+    if (live.host_current()) return PYR_OK;
+    HIP_TRY(hipSetDevice(s->device));
+    HIP_TRY(hipDeviceSynchronize());
+    for (int k = 0; k < NUM_ARRAYS; ++k)
+        if (const size_t n = live.kept_floats(k)) HIP_TRY(hipMemcpy(live.arrays[k].host.data(), live.arrays[k].staging.ptr, n * 4, hipMemcpyDeviceToHost));
+    live.fetched();
+    return PYR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ pyr_scene_update
+int scene_update(PyrScene* s, const PyrGeometryUpdate* u, bool device_arrays, hipStream_t stream) {
+    const auto t_start = Clock::now();
+    HIP_TRY(hipSetDevice(s->device));
+    LiveGeometry& live = s->live;
+    int rc = fetch_live_geometry(s); // a pose left the description behind: what stays comes from it
+    if (rc != PYR_OK) return rc;
+    // ---- the new arrays on the host: the caller's own, or copies of the device arrays
+    const float* const given[NUM_ARRAYS] = {u->tri_positions, u->tri_normals, u->tri_frames, u->spheres};
+    const float* host[NUM_ARRAYS] = {given[0], given[1], given[2], given[3]};
+    std::vector<float> fetched[NUM_ARRAYS];
+    if (device_arrays) {
+        for (int k = 0; k < NUM_ARRAYS; ++k) {
+            if (!given[k]) continue;
+            fetched[k].resize(live.floats(k));
+            HIP_TRY(hipMemcpyAsync(fetched[k].data(), given[k], live.floats(k) * 4, hipMemcpyDeviceToHost, stream));
+            host[k] = fetched[k].data();
+        }
+        HIP_TRY(hipStreamSynchronize(stream));
+    }
+    // ---- the coordinate check of scene creation, on the bounds of what moved, before anything of the scene is written
+    for (int k : {(int)SPHERES, (int)POSITIONS}) {
+        if (!host[k]) continue;
+        for (const float *p = host[k], *end = p + live.floats(k); p != end; p += live.arrays[k].width) {
+            PrimBounds b;
+            k == SPHERES ? lvl::sphere_bounds(p, b.lo, b.hi) : lvl::triangle_bounds(p, b.lo, b.hi);
+            if (!within_coordinate_range(b)) return fail(PYR_ERR_UNSUPPORTED, kCoordinateRangeMessage);
+        }
+    }
+    PyrUpdateInfo info{};
+    info.mode_used = u->mode;
+    info.area_ratio = 1.0;
+
+    if (u->mode == PYR_UPDATE_REBUILD) {
+        HIP_TRY(hipDeviceSynchronize());
+        return rebuild_from(s, host, t_start, info);
+    }
+
+    // ---- refit: where the kernels read the arrays -- the caller's device arrays, or the scene's own copies of the host arrays
+    if ((rc = prepare_refit(s)) != PYR_OK) return rc;
+    const float* source[NUM_ARRAYS] = {nullptr, nullptr, nullptr, nullptr};
+    for (int k = 0; k < NUM_ARRAYS; ++k) {
+        if (!given[k]) continue;
+        if (device_arrays) {
+            source[k] = given[k];
+        } else {
+            DeviceBuffer& own = live.arrays[k].staging;
+            if ((rc = own.reserve(live.floats(k) * 4)) != PYR_OK) return rc;
+            HIP_TRY(hipMemcpyAsync(own.ptr, given[k], live.floats(k) * 4, hipMemcpyHostToDevice, stream));
+            source[k] = (const float*)own.ptr;
+        }
+    }
+    if (!given[POSITIONS] && live.num_triangles) { // the triangles stay: their positions as the scene keeps them
+        LiveArray& positions = live.arrays[POSITIONS];
+        if (!live.positions_staged()) {
+            if ((rc = positions.staging.reserve(live.floats(POSITIONS) * 4)) != PYR_OK) return rc;
+            HIP_TRY(hipMemcpyAsync(positions.staging.ptr, positions.host.data(), live.floats(POSITIONS) * 4, hipMemcpyHostToDevice, stream));
+            live.staged_positions();
+        }
+        source[POSITIONS] = (const float*)positions.staging.ptr;
+    }
+    live.adopted(host, !device_arrays); // the description the scene keeps follows the device
+    // the lamp records, on the host with creation's arithmetic (lamps are few)
+    bool shape_lamps = false;
+    for (const PyrLamp& l : live.lamps) shape_lamps = shape_lamps || l.kind == PYR_LAMP_SHAPE;
+    if (shape_lamps) {
+        HIP_TRY(hipStreamSynchronize(stream)); // an earlier update's copy may still read lamp_records
+        const PyrSceneDesc d = live.view();
+        live.lamp_records.resize(live.lamps.size());
+        for (uint32_t i = 0; i < (uint32_t)live.lamps.size(); ++i) live.lamp_records[i] = pack_lamp(&d, i);
+        HIP_TRY(hipMemcpyAsync(s->lamps.ptr, live.lamp_records.data(), live.lamp_records.size() * sizeof(DevLamp), hipMemcpyHostToDevice, stream));
+    }
+    return refit_from(s, source, given[POSITIONS] != nullptr, given[SPHERES] != nullptr, !device_arrays, stream, t_start, nullptr, info);
+}
+
+// ------------------------------------------------------------------------------------------------ pyr_scene_pose
+void set_pose(devpose::DevObject& o, const float* transform, float scale) {
+    bool same = scale == 1.0f;
+    for (int k = 0; k < 16; ++k) o.pose.m[k] = transform[k], same = same && transform[k] == kIdentity[k];
+    o.pose.scale = scale;
+    o.pose.identity = same ? 1u : 0u;
+}
+
+devpose::Ctx pose_context(PyrScene* s) {
+    const LiveGeometry& live = s->live;
+    const auto rest = [&](int k) { return live.arrays[k].kept ? (const float*)live.arrays[k].rest.ptr : nullptr; };
+    const auto staging = [&](int k) { return (float*)live.arrays[k].staging.ptr; };
+    devpose::Ctx c{};
+    c.rest_positions = rest(POSITIONS), c.rest_normals = rest(NORMALS), c.rest_frames = rest(FRAMES), c.rest_spheres = rest(SPHERES);
+    c.positions = staging(POSITIONS), c.normals = staging(NORMALS), c.frames = staging(FRAMES), c.spheres = staging(SPHERES);
+    c.objects = (const devpose::DevObject*)live.pose_objects.ptr, c.num_objects = (uint32_t)live.pose_table.size();
+    c.num_triangles = live.num_triangles, c.num_spheres = live.num_spheres;
+    c.posed_triangles = live.posed_triangles, c.posed_spheres = live.posed_spheres;
+    c.beyond_range = (uint32_t*)live.pose_flag.ptr;
+    c.lamps = (DevLamp*)s->lamps.ptr, c.num_lamps = (uint32_t)live.lamps.size();
+    return c;
+}
+
+// Every object's primitives from the rest pose into the staging arrays under `table`, and the flag back: the one wait.
+int run_pose(PyrScene* s, const std::vector<devpose::DevObject>& table, hipStream_t stream, uint32_t& beyond_range) {
+    HIP_TRY(hipMemcpyAsync(s->live.pose_objects.ptr, table.data(), table.size() * sizeof(devpose::DevObject), hipMemcpyHostToDevice, stream));
+    HIP_TRY(hipMemsetAsync(s->live.pose_flag.ptr, 0, 4, stream));
+    const hipError_t e = devpose::launch_pose(pose_context(s), stream);
+    if (e != hipSuccess) return hip_fail(e, "pose kernels");
+    HIP_TRY(hipMemcpyAsync(&beyond_range, s->live.pose_flag.ptr, 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipStreamSynchronize(stream));
+    return PYR_OK;
+}
+
+int scene_pose(PyrScene* s, const PyrPoseUpdate* u, hipStream_t stream) {
+    const auto t_start = Clock::now();
+    HIP_TRY(hipSetDevice(s->device));
+    LiveGeometry& live = s->live;
+    int rc;
+    if (u->mode == PYR_UPDATE_REFIT && (rc = prepare_refit(s)) != PYR_OK) return rc;
+    std::vector<devpose::DevObject> table = live.pose_table;
+    for (uint32_t i = 0; i < u->num_objects; ++i) set_pose(table[i], u->poses[i].transform, u->poses[i].scale);
+    uint32_t beyond_range = 0;
+    if ((rc = run_pose(s, table, stream, beyond_range)) != PYR_OK) return rc;
+    const auto refused = [&](int why) { // no record has been touched: the staging arrays go back to the poses the scene is in
+        const int back = run_pose(s, live.pose_table, stream, beyond_range);
+        return back != PYR_OK ? back : why;
+    };
+    if (beyond_range != 0) return refused(fail(PYR_ERR_UNSUPPORTED, kCoordinateRangeMessage));
+    PyrUpdateInfo info{};
+    info.mode_used = u->mode;
+    info.area_ratio = 1.0;
+    const auto t_posed = Clock::now();
+
+    if (u->mode == PYR_UPDATE_REBUILD) { // the staging arrays are the geometry now: the description follows them, then a rebuild over it
+        const float* const none[NUM_ARRAYS] = {nullptr, nullptr, nullptr, nullptr};
+        info.upload_ms = (float)ms_between(t_start, t_posed);
+        live.posed();
+        if ((rc = fetch_live_geometry(s)) == PYR_OK) rc = rebuild_from(s, none, t_start, info);
+        if (rc != PYR_OK) { // (and the description follows them again when it is next read)
+            live.posed();
+            return refused(rc);
+        }
+        live.pose_table.swap(table);
+        return PYR_OK;
+    }
+
+    // ---- refit: every record and box from the staging arrays, as the host form of pyr_scene_update given all four arrays
+    live.pose_table.swap(table);
+    live.posed();
+    const float* source[NUM_ARRAYS];
+    for (int k = 0; k < NUM_ARRAYS; ++k) source[k] = live.kept_floats(k) ? (const float*)live.arrays[k].staging.ptr : nullptr;
+    const hipError_t e = devpose::launch_lamps(pose_context(s), stream);
+    if (e != hipSuccess) return hip_fail(e, "pose: lamp records");
+    return refit_from(s, source, live.num_triangles != 0, live.num_spheres != 0, false, stream, t_start, &t_posed, info);
+}
+
+// ranges inside the counts and pairwise disjoint, triangles and spheres each
+int check_ranges(const PyrScene* scene, const PyrObjectRange* ranges, uint32_t n) {
+    std::vector<std::pair<uint64_t, uint64_t>> tri, sph;
+    for (uint32_t i = 0; i < n; ++i) {
+        const PyrObjectRange& r = ranges[i];
+        if ((uint64_t)r.first_triangle + r.num_triangles > scene->live.num_triangles) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectRange: a triangle range reaches past the scene's triangles");
+        if ((uint64_t)r.first_sphere + r.num_spheres > scene->live.num_spheres) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectRange: a sphere range reaches past the scene's spheres");
+        if (r.num_triangles) tri.emplace_back(r.first_triangle, (uint64_t)r.first_triangle + r.num_triangles);
+        if (r.num_spheres) sph.emplace_back(r.first_sphere, (uint64_t)r.first_sphere + r.num_spheres);
+    }
+    for (auto* list : {&tri, &sph}) {
+        std::sort(list->begin(), list->end());
+        for (size_t k = 1; k < list->size(); ++k)
+            if ((*list)[k].first < (*list)[k - 1].second) return fail(PYR_ERR_INVALID_ARGUMENT, list == &tri ? "PyrObjectRange: two triangle ranges overlap" : "PyrObjectRange: two sphere ranges overlap");
+    }
+    return PYR_OK;
+}
+
+} // namespace
+
+extern "C" {
+
+int pyr_scene_set_objects(PyrScene* scene, const PyrObjectRange* ranges, uint32_t num_objects) {
+    if (num_objects != 0 && !ranges) return fail(PYR_ERR_INVALID_ARGUMENT, "null ranges with a non-zero num_objects");
+    if (!scene) return fail(PYR_ERR_INVALID_ARGUMENT, "null scene");
+    int rc = check_ranges(scene, ranges, num_objects);
+    if (rc != PYR_OK) return rc;
+    LiveGeometry& live = scene->live;
+    if (num_objects == 0 && live.pose_table.empty()) return PYR_OK;
+    HIP_TRY(hipSetDevice(scene->device));
+    HIP_TRY(hipDeviceSynchronize());
+    if ((rc = fetch_live_geometry(scene)) != PYR_OK) return rc; // the rest pose is the geometry as it is now
+    live.forget_objects();
+    if (num_objects == 0) return PYR_OK;
+    for (int k = 0; k < NUM_ARRAYS; ++k) { // the rest pose, and a staging array that holds a copy of it
+        LiveArray& a = live.arrays[k];
+        const size_t bytes = live.kept_floats(k) * 4;
+        if ((rc = a.rest.upload(a.host.data(), bytes)) != PYR_OK) return rc;
+        if ((rc = a.staging.reserve(bytes)) != PYR_OK) return rc;
+        if (bytes) HIP_TRY(hipMemcpy(a.staging.ptr, a.rest.ptr, bytes, hipMemcpyDeviceToDevice));
+    }
+    live.staged_positions();
+    if ((rc = live.pose_objects.alloc((size_t)num_objects * sizeof(devpose::DevObject))) != PYR_OK) return rc;
+    if (!live.pose_flag.ptr && (rc = live.pose_flag.alloc(4)) != PYR_OK) return rc;
+    live.pose_table.resize(num_objects);
+    uint32_t triangle_lane = 0, sphere_lane = 0;
+    for (uint32_t i = 0; i < num_objects; ++i) {
+        devpose::DevObject& o = live.pose_table[i];
+        set_pose(o, kIdentity, 1.0f);
+        o.first_triangle = ranges[i].first_triangle, o.num_triangles = ranges[i].num_triangles;
+        o.first_sphere = ranges[i].first_sphere, o.num_spheres = ranges[i].num_spheres;
+        o.triangle_lane = triangle_lane, o.sphere_lane = sphere_lane;
+        triangle_lane += o.num_triangles, sphere_lane += o.num_spheres; // disjoint ranges inside the counts: below 2^28 in all
+    }
+    live.posed_triangles = triangle_lane, live.posed_spheres = sphere_lane;
+    return PYR_OK;
+}
+
+int pyr_scene_pose(PyrScene* scene, const PyrPoseUpdate* update, void* hip_stream) {
+    int rc = check_pose_args(scene, update);
+    if (rc != PYR_OK) return rc;
+    return scene_pose(scene, update, (hipStream_t)hip_stream);
+}
+
+int pyr_scene_geometry(PyrScene* scene, float* tri_positions, float* tri_normals, float* tri_frames, float* spheres) {
+    if (!scene) return fail(PYR_ERR_INVALID_ARGUMENT, "null scene");
+    const LiveGeometry& live = scene->live;
+    if (tri_frames && !live.arrays[FRAMES].kept) return fail(PYR_ERR_INVALID_ARGUMENT, "tri_frames: the scene was created without frames and keeps none");
+    int rc = fetch_live_geometry(scene);
+    if (rc != PYR_OK) return rc;
+    float* const out[NUM_ARRAYS] = {tri_positions, tri_normals, tri_frames, spheres};
+    for (int k = 0; k < NUM_ARRAYS; ++k)
+        if (out[k] && live.kept_floats(k)) std::memcpy(out[k], live.arrays[k].host.data(), live.kept_floats(k) * 4);
+    return PYR_OK;
+}
+
+int pyr_scene_update(PyrScene* scene, const PyrGeometryUpdate* update) {
+    int rc = check_update_args(scene, update);
+    if (rc != PYR_OK) return rc;
+    HIP_TRY(hipSetDevice(scene->device));
+    HIP_TRY(hipDeviceSynchronize()); // blocking: nothing of this scene is in flight while its records change
+    return scene_update(scene, update, false, nullptr);
+}
+
+int pyr_scene_update_device(PyrScene* scene, const PyrGeometryUpdate* update, void* hip_stream) {
+    int rc = check_update_args(scene, update);
+    if (rc != PYR_OK) return rc;
+    return scene_update(scene, update, true, (hipStream_t)hip_stream);
+}
+
+int pyr_scene_update_info(PyrScene* scene, PyrUpdateInfo* out) {
+    if (!scene || !out) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+    HIP_TRY(hipSetDevice(scene->device));
+    HIP_TRY(hipDeviceSynchronize());
+    std::vector<Node64> nodes(scene->info.num_nodes);
+    HIP_TRY(hipMemcpy(nodes.data(), scene->nodes.ptr, nodes.size() * sizeof(Node64), hipMemcpyDeviceToHost));
+    const double now = child_area_sum(nodes.data(), nodes.size());
+    if (!scene->live.area_known()) scene->live.area_at_build(now); // no refit since the build: this is the built tree
+    *out = scene->live.update_info;
+    out->area_ratio = scene->live.built_area > 0.0 ? now / scene->live.built_area : 1.0;
+    return PYR_OK;
+}
+
+} // extern "C"

@@ -1,0 +1,144 @@
+// scene_internal.h -- what api.cpp (creation, renders, sessions, images) and live_scene.cpp (everything that moves a scene after
+// creation) both see of a PyrScene. Declarations, but for the coordinate test: api.cpp defines what is not said to live elsewhere.
+#pragma once
+#include <hip/hip_runtime.h>
+
+#include <chrono>
+#include <cmath>
+#include <memory>
+#include <string>
+#include <vector>
+
+#include "api_internal.h"
+#include "bvh.h"
+#include "device_scene.h"
+#include "kernels/pose_launch.h"
+
+namespace pyr {
+
+// Records the thread-local message pyr_last_error() returns and hands `code` back (api_fail is the same function under the
+// name the other units know).
+int fail(int code, const std::string& message);
+int hip_fail(hipError_t e, const char* what);
+
+#define HIP_TRY(expr)                                          \
+    do {                                                       \
+        hipError_t e_ = (expr);                                \
+        if (e_ != hipSuccess) return pyr::hip_fail(e_, #expr); \
+    } while (0)
+
+struct DeviceBuffer {
+    void* ptr = nullptr;
+    size_t bytes = 0;
+    ~DeviceBuffer() { release(); }
+    void release();
+    int upload(const void* src, size_t n); // (over an earlier allocation: that one is freed -- a rebuild uploads into the scene's buffers again)
+    int alloc(size_t n);
+    int reserve(size_t n); // holds `n` bytes afterwards: allocated once, kept while it is large enough
+};
+
+double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b);
+
+// pyrite_gpu.h "Coordinates": what pack_geometry, pyr_scene_update and pyr_scene_pose refuse, in the same words. The test runs
+// once per primitive of every creation and update, so it is the one body here: a call into another unit costs a millisecond
+// per million triangles.
+constexpr float kMaxCoordinate = 1.0e15f;
+extern const char* const kCoordinateRangeMessage;
+inline bool within_coordinate_range(const PrimBounds& b) {
+    for (int a = 0; a < 3; ++a)
+        if (!(std::fabs(b.lo[a]) <= kMaxCoordinate && std::fabs(b.hi[a]) <= kMaxCoordinate)) return false;
+    return true;
+}
+
+// One DevLamp from the description, and the geometry part of scene creation (api.cpp): `d` needs its geometry fields and lamps.
+DevLamp pack_lamp(const PyrSceneDesc* d, uint32_t i);
+int pack_geometry(const PyrSceneDesc* d, PyrScene* s, uint32_t builder);
+
+struct LiveArray {       // one of the arrays that move, and its homes
+    uint32_t width;      // floats per primitive
+    bool per_sphere;     // scales with num_spheres, not num_triangles
+    bool kept = true;    // the scene keeps it (frames: only a description that has them, or an update that brought them)
+    std::vector<float> host;
+    DeviceBuffer staging, rest;
+};
+
+// Where a scene's geometry is now, and which of its copies are valid (live_scene.cpp). Four arrays move -- positions, normals,
+// frames, spheres -- and each has up to three homes in the scene: `host`, the description a rebuild packs from and a refit's
+// lamp records need; `staging`, the device array a host update uploads into, the pose kernels write and the refit reads; `rest`,
+// the device copy taken when objects were named, which every pose starts from. What never moves (uvs, materials, the lamp
+// list) are plain members.
+//
+// What holds between the copies, and the only methods that change it:
+//  - host_current: `host` is the geometry the records on the device were made from. Only a refit pose leaves it behind
+//    (posed()): the staging arrays are the truth then, and whoever reads `host` calls fetch_live_geometry first (fetched()).
+//  - positions_staged: staging positions equal host positions, so a refit that moves no triangle reads them without an upload.
+//    True after they were uploaded or captured from `host` (staged_positions(), adopted() of host arrays); false after
+//    device arrays were adopted and after every build (built(): conservative, costs one upload at most).
+//  - schedule_current: the refit schedules and scratch belong to the trees on the device (scheduled(); built() ends it).
+//  - area_known: built_area is the binary tree's child_area_sum at the last build (area_at_build(); built() ends it).
+//  - While host_current is false, objects are set and every kept array's staging buffer holds the whole array.
+struct LiveGeometry {
+    enum { POSITIONS, NORMALS, FRAMES, SPHERES, NUM_ARRAYS };
+    LiveArray arrays[NUM_ARRAYS] = {{9, false}, {9, false}, {12, false}, {4, true}}; // the one table of what moves
+    uint32_t num_triangles = 0, num_spheres = 0;
+    std::vector<float> tri_uvs, sphere_tex_scale;
+    std::vector<uint32_t> tri_material, sphere_material;
+    std::vector<PyrLamp> lamps;
+    bool has_uvs = false, has_tex_scale = false;
+    // the refit's scratch and its schedules (made at the first refit after a build): RefitSchedule::order and ::begin of either tree
+    DeviceBuffer bounds, max_abs, order_binary, order_wide;
+    std::vector<uint32_t> sched_binary, sched_wide;
+    std::vector<DevLamp> lamp_records; // of the last host update (the copy to the device may still read them)
+    double built_area = 0.0;
+    PyrUpdateInfo update_info{};
+    // the objects with the poses the scene is in (identity when they are set)
+    std::vector<devpose::DevObject> pose_table;
+    uint32_t posed_triangles = 0, posed_spheres = 0;
+    DeviceBuffer pose_objects, pose_flag;
+
+    size_t floats(int k) const { return (size_t)arrays[k].width * (arrays[k].per_sphere ? num_spheres : num_triangles); } // of array k in full, kept or not
+    size_t kept_floats(int k) const { return arrays[k].kept ? floats(k) : 0; }
+    void keep(const PyrSceneDesc* d); // scene creation: the description's geometry
+    PyrSceneDesc view(const float* const with[NUM_ARRAYS] = nullptr) const; // what pack_geometry and pack_lamp read; `with`: arrays in place of the scene's own
+    void forget_objects(); // (adopted() does it: new arrays are a new geometry, not a pose of the old one)
+    bool host_current() const { return host_current_; }
+    bool positions_staged() const { return positions_staged_; }
+    bool schedule_current() const { return schedule_current_; }
+    bool area_known() const { return area_known_; }
+    void built() { host_current_ = true, positions_staged_ = schedule_current_ = area_known_ = false; } // pack_geometry made new trees from `host`
+    void adopted(const float* const given[NUM_ARRAYS], bool staged); // `host` takes the arrays an update gave; staged: they are in staging too
+    void staged_positions() { positions_staged_ = true; }
+    void posed() { host_current_ = false; }
+    void fetched() { host_current_ = true; }
+    void scheduled() { schedule_current_ = true; }
+    void area_at_build(double area) { built_area = area, area_known_ = true; }
+
+private:
+    bool host_current_ = true, positions_staged_ = false, schedule_current_ = false, area_known_ = false;
+};
+
+} // namespace pyr
+
+struct PyrScene {
+    int device = 0;
+    int num_cus = 0;
+    pyr::DevScene dev{};
+    PyrBvhInfo info{};
+    PyrBuildInfo build_info{}; // pyr_scene_build_info
+    std::unique_ptr<pyr::BuiltBvh> digest_source; // the binary tree, kept until the first pyr_scene_build_info has hashed it (tree_digest walks the whole tree: not on every scene creation's bill)
+    pyr::DeviceBuffer wide_nodes, wide_pair_nodes, pair_prims, nodes, prims, tri_shade, spheres, sphere_material, planes, plane_material, lamps, materials, components, programs, instrs, spectra,
+        spectrum_data, rgb_basis, counters, tri_tex, sphere_tex_scale, plane_frames, textures, texture_data;
+    PyrCounters last_counters{};
+    bool have_counters = false;
+    PyrProgramInfo program_info{}; // pyr_scene_program_info; program_info.wide: the kernels are the wide interpreter build (kernels/wide.hip)
+    uint32_t* tail_count = nullptr; // device, kFeedBytes: the work-feed cursors of the intersect kernel
+    pyr::DeviceBuffer tape; // spectral tape of the stage-scheduled kernel (grown on demand, kept between renders)
+    pyr::DeviceBuffer start_queue; // the waves' rings of ready sample starts (RenderLaunch::start_queue; scenes without interpreter programs), kept like the tape
+    pyr::DeviceBuffer tape_overflow; // one word the kernels set when a path outgrew the tape (checked after blocking renders and by pyr_scene_counters)
+    uint32_t builder = PYR_BUILD_HOST; // who builds this scene's trees: at creation, and at every PYR_UPDATE_REBUILD
+    bool spatial_splits = false;       // the last build split space: its leaves hold clipped boxes, which a refit cannot recompute
+    uint64_t table_floats = 0;         // floats of the small tables a big scene stages into LDS (DevScene::lds_table_floats)
+    uint32_t live_sessions = 0;        // PyrSessions on this scene: an update is refused while there is one
+    pyr::LiveGeometry live;            // where the geometry is now (pyr_scene_update, pyr_scene_set_objects / pyr_scene_pose)
+    ~PyrScene();
+};

@@ -347,6 +347,70 @@ def test_an_update_with_arrays_forgets_the_objects(gpu_lib):
     world.close()
 
 
+@pytest.mark.parametrize("shape", ["knot", "textures"])
+def test_a_walk_through_every_way_to_move_a_scene(gpu_lib, shape):
+    """One world through poses, updates from the host and from the device, rebuilds and set_objects in a row: after every step
+    World.geometry() is the numpy expectation bit for bit, and at the end the scene answers like one created from the final arrays."""
+    import torch
+
+    world, _, _, _, ranges = cases.build(shape)
+    rest = cases.rest_of(world)
+    p1, p2 = cases.poses_for("rotated_and_translated", len(ranges)), cases.poses_for("scaled_and_rotated", len(ranges))
+
+    def at(step, want, mode, updates):
+        assert_geometry_bits(world.geometry(), want, "%s step %d" % (shape, step))
+        info = world.update_info()
+        assert (info["mode_used"], info["updates"]) == (mode, updates), (step, info)
+
+    def the_objects_are_forgotten():
+        with pytest.raises(PyriteGpuError) as err:
+            world.pose(p1)
+        assert err.value.status == abi.PYR_ERR_INVALID_ARGUMENT and "no objects" in str(err.value)
+
+    world.pose(p1)  # 1
+    g1 = restatement.pose_arrays(rest, ranges, p1)
+    at(1, g1, abi.PYR_UPDATE_REFIT, 1)
+    world.update(mode="rebuild")  # 2: no array -- the geometry and the objects stay, the tree is new
+    at(2, g1, abi.PYR_UPDATE_REBUILD, 0)
+    world.pose(p2)  # 3: from rest, on the rebuilt tree (its schedule is made again)
+    g3 = restatement.pose_arrays(rest, ranges, p2)
+    at(3, g3, abi.PYR_UPDATE_REFIT, 1)
+    normals = restatement.pose_arrays(rest, ranges, cases.poses_for("non_uniform", len(ranges)))["normals"]
+    world.update(normals=normals, mode="refit")  # 4: from the host -- the positions the pose left stay
+    g4 = dict(g3, normals=normals)
+    at(4, g4, abi.PYR_UPDATE_REFIT, 2)
+    the_objects_are_forgotten()
+    world.update(mode="refit")  # 5: no array -- the positions are staged from the description
+    at(5, g4, abi.PYR_UPDATE_REFIT, 3)
+    world.set_objects(ranges)  # 6: the rest pose is the geometry as it is now
+    world.pose(p1, mode="rebuild")
+    g6 = restatement.pose_arrays(g4, ranges, p1)
+    at(6, g6, abi.PYR_UPDATE_REBUILD, 0)
+    positions = restatement.pose_arrays(g6, ranges, p2)["positions"]
+    world.update(positions=torch.from_numpy(positions).to("cuda:0"), mode="refit")  # 7: the device form
+    final = dict(g6, positions=positions)
+    at(7, final, abi.PYR_UPDATE_REFIT, 1)
+    the_objects_are_forgotten()
+    world.set_objects([])  # 8
+    at(8, final, abi.PYR_UPDATE_REFIT, 1)
+
+    fresh, _, _, _, _ = cases.build(shape)
+    for key, attr in (("positions", "tri_positions"), ("normals", "tri_normals"), ("frames", "tri_frames"), ("spheres", "spheres")):
+        if final[key] is not None and len(final[key]):
+            setattr(fresh.flat, attr, [final[key].copy()])
+    fresh._desc = fresh.flat.desc()
+    rays = rays_at(final)
+    hf = fresh.intersect(rays)[0]
+    hits = int((hf["shape"] != 0xFFFFFFFF).sum())
+    print("%s: %d of %d rays hit the scene created from the final arrays" % (shape, hits, len(rays)))
+    assert hits > 1000
+    hw = world.intersect(rays)[0]
+    assert np.array_equal(hw["distance"].view(np.uint32), hf["distance"].view(np.uint32))
+    assert int((hw["shape"] != 0xFFFFFFFF).sum()) == hits
+    assert_shapes_equal_up_to_ties(fresh, hf, hw, rays)
+    world.close(), fresh.close()
+
+
 @pytest.mark.parametrize("mode", ["refit", "rebuild"])
 def test_the_cpp_world_poses_like_the_restatement(gpu_lib, tmp_path, mode):
     """pyrite::World::pose and geometry() through pyrite_host_tool on the textures scene (frames, spheres, a lamp sphere)."""
