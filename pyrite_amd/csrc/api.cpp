@@ -1,6 +1,7 @@
-// api.cpp -- host side of the C ABI declared in include/pyrite_gpu.h: scene validation and packing, BVH build,
-// upload, launch orchestration. No radiance is ever computed on the host; without a gfx950 device every render /
-// intersect entry point fails with PYR_ERR_DEVICE. What moves a scene after creation is live_scene.cpp.
+// api.cpp -- the scene's side of the C ABI declared in include/pyrite_gpu.h: scene validation and packing, BVH build, upload, and
+// the entries that render, intersect or look at a scene. No radiance is ever computed on the host; without a gfx950 device every
+// render / intersect entry point fails with PYR_ERR_DEVICE. What moves a scene after creation is live_scene.cpp, progressive
+// sessions are session.cpp, and what develops, tone-maps or denoises an image without a scene is image_ops.cpp.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -30,7 +31,6 @@ int fail(int code, const std::string& message) {
     return code;
 }
 int hip_fail(hipError_t e, const char* what) { return fail(PYR_ERR_DEVICE, std::string(what) + ": " + hipGetErrorString(e)); }
-int api_fail(int code, const std::string& message) { return fail(code, message); }
 
 void DeviceBuffer::release() {
     if (ptr) (void)hipFree(ptr);
@@ -849,60 +849,10 @@ int pack_and_upload(const PyrSceneDesc* d, PyrScene* s, uint32_t builder) {
     return PYR_OK;
 }
 
-struct TilePlan {
-    uint32_t tiles_x = 0, tiles_y = 0;
-    uint32_t tile_begin = 0, tile_stride = 1, tile_count = 0;
-    uint32_t chunks_per_tile = 0;
-    uint32_t chunk_begin = 0, chunk_end = 0; // chunk numbers of the call's tiles (device_scene.h RenderLaunch)
-};
-
-int plan_tiles(const PyrFilmDesc* film, const PyrRenderParams* p, TilePlan& plan) {
-    // make_tiles, renderer/algorithm.rs:158-166
-    const uint32_t ts = p->tile_size;
-    plan.tiles_x = (film->width + ts - 1) / ts;
-    plan.tiles_y = (film->height + ts - 1) / ts;
-    const uint64_t total = (uint64_t)plan.tiles_x * plan.tiles_y;
-    const uint64_t begin = p->tile_begin, end = p->tile_end ? p->tile_end : total;
-    if (total >= 0xFFFFFFFFull || begin > end || end > total) return fail(PYR_ERR_INVALID_ARGUMENT, "tile range out of bounds");
-    plan.tile_begin = (uint32_t)begin;
-    plan.tile_stride = std::max(1u, p->tile_stride);
-    plan.tile_count = (uint32_t)((end - begin + plan.tile_stride - 1) / plan.tile_stride);
-    const uint64_t per_tile = ((uint64_t)ts * ts * p->pixel_samples + 63) / 64; // iterations of a full tile: simple.rs:73
-    if (per_tile * plan.tile_count >= 0xFFFFFFFFull) return fail(PYR_ERR_UNSUPPORTED, "too many samples for one call: more than 2^32 chunks");
-    // a window [sample_begin, sample_begin + pixel_samples) must end where a one-shot call of that many samples could: same bound
-    const uint64_t window_end = (uint64_t)p->sample_begin + p->pixel_samples;
-    if (p->sample_begin != 0 && (window_end > 0xFFFFFFFFull || (((uint64_t)ts * ts * window_end + 63) / 64) * plan.tile_count >= 0xFFFFFFFFull))
-        return fail(PYR_ERR_UNSUPPORTED, "sample window ends beyond what one call can render: more than 2^32 chunks");
-    plan.chunks_per_tile = (uint32_t)std::max<uint64_t>(per_tile, 1); // pixel_samples == 0: no chunk at all
-    plan.chunk_begin = 0;
-    plan.chunk_end = (uint32_t)(per_tile * plan.tile_count);
-    return PYR_OK;
-}
-
 uint64_t film_buffer_grains(const PyrFilmDesc* film, const PyrRenderParams* p, const TilePlan& plan) {
     if (p->film_layout == PYR_FILM_TILE_BLOCKS) return (uint64_t)plan.tile_count * (p->tile_size + 2ull) * (p->tile_size + 2ull) * film->bins;
     const uint32_t rows = p->film_row_count ? p->film_row_count : film->height;
     return (uint64_t)rows * film->width * film->bins;
-}
-
-int check_render_args(PyrScene* scene, const PyrCamera* camera, const PyrFilmDesc* film, const PyrRenderParams* p, const void* film_ptr) {
-    if (!scene || !camera || !film || !p || !film_ptr) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
-    if (film->width == 0 || film->height == 0 || film->bins == 0 || p->tile_size == 0 || p->spectrum_samples == 0)
-        return fail(PYR_ERR_INVALID_ARGUMENT, "zero-sized parameter");
-    if (!(film->wl_width > 0.0f)) return fail(PYR_ERR_INVALID_ARGUMENT, "empty wavelength span");
-    uint32_t rows = p->film_row_count ? p->film_row_count : film->height;
-    if ((uint64_t)p->film_row_begin + rows > film->height) return fail(PYR_ERR_INVALID_ARGUMENT, "film window exceeds the image");
-    if (p->spectrum_samples > 64) return fail(PYR_ERR_UNSUPPORTED, "spectrum_samples > 64");
-    // a pixel is a 32-bit index into the call's film buffer (0xFFFFFFFF stands for "none"): 65,535 x 65,535 still fits
-    if ((uint64_t)film->width * film->height >= 0xFFFFFFFFull) return fail(PYR_ERR_UNSUPPORTED, "image too large: 2^32 pixels or more");
-    if (p->film_layout == PYR_FILM_TILE_BLOCKS) {
-        const uint64_t tiles = (uint64_t)((film->width + p->tile_size - 1) / p->tile_size) * ((film->height + p->tile_size - 1) / p->tile_size);
-        if (tiles * (p->tile_size + 2ull) * (p->tile_size + 2ull) >= 0xFFFFFFFFull) return fail(PYR_ERR_UNSUPPORTED, "image too large for a film of tile blocks");
-    }
-    if (p->film_layout > PYR_FILM_TILE_BLOCKS) return fail(PYR_ERR_INVALID_ARGUMENT, "unknown film layout");
-    if (p->film_layout == PYR_FILM_TILE_BLOCKS && (p->film_row_begin || p->film_row_count))
-        return fail(PYR_ERR_INVALID_ARGUMENT, "a film of tile blocks has no row window");
-    return PYR_OK;
 }
 
 // Scheduler choice (kernels.hip): the bounce-synchronous walk wins when the scene lives in LDS and traversal is cheap
@@ -965,67 +915,6 @@ void choose_schedule(const PyrScene* scene, RenderLaunch& L) {
     L.sm_expose_lanes = expose && *expose ? (uint32_t)std::strtoul(expose, nullptr, 10) : L.sm_phase_lanes;
 }
 
-int render_batches(PyrScene* scene, RenderLaunch L, bool count, hipStream_t stream) {
-    if (L.chunk_end == L.chunk_begin) return PYR_OK;
-    choose_schedule(scene, L);
-    if (L.scheduler != 0 && (scene->dev.needs_interpreter == 0 || uses_hit_tape(scene->dev, L))) {
-        L.tape_lanes = tape_lanes_bound(scene->num_cus);
-        L.tape_max_ops = tape_ops_bound(scene->dev, L);
-        int rc = reserve_tape(scene, L, stream);
-        if (rc != PYR_OK) return rc;
-    }
-    int rc = launch_render(scene->dev, L, count, stream, scene->num_cus, scene->program_info.wide != 0);
-    if (rc != PYR_OK) return fail(rc, kernels_last_error());
-    return PYR_OK;
-}
-
-// After a render has been waited for: did a path outgrow the spectral tape (kernels.hip tape_push)? The film is wrong then.
-int check_tape_overflow(PyrScene* scene) {
-    if (!scene->tape_overflow.ptr) return PYR_OK;
-    uint32_t word = 0;
-    HIP_TRY(hipMemcpy(&word, scene->tape_overflow.ptr, sizeof(word), hipMemcpyDeviceToHost));
-    if (word == 0) return PYR_OK;
-    HIP_TRY(hipMemset(scene->tape_overflow.ptr, 0, sizeof(uint32_t)));
-    if (word == 2) return fail(PYR_ERR_DEVICE, "a wave gave up waiting on its workgroup's LDS queues (spin limit): the film of that render is invalid");
-    return fail(PYR_ERR_DEVICE, "a path appended more records than the spectral tape's bound allows: the film of that render is invalid");
-}
-
-} // namespace
-
-namespace pyr {
-// For the translation units that enqueue renders without waiting for them (multi.cpp): the word itself, and its check.
-uint32_t* scene_overflow_word(PyrScene* scene) { return scene ? (uint32_t*)scene->tape_overflow.ptr : nullptr; }
-int scene_check_overflow(PyrScene* scene) { return check_tape_overflow(scene); }
-} // namespace pyr
-
-namespace {
-
-RenderLaunch make_launch(const PyrCamera* camera, const PyrFilmDesc* film, const PyrRenderParams* p, const TilePlan& plan) {
-    RenderLaunch L{};
-    L.camera = *camera;
-    L.film = *film;
-    L.bounces = p->bounces;
-    L.light_samples = p->light_samples;
-    L.spectrum_samples = p->spectrum_samples;
-    L.tile_size = p->tile_size;
-    L.pixel_samples = p->pixel_samples;
-    L.sample_begin = p->sample_begin;
-    L.tiles_x = plan.tiles_x;
-    L.tiles_y = plan.tiles_y;
-    L.tile_begin = plan.tile_begin;
-    L.tile_stride = plan.tile_stride;
-    L.tile_count = plan.tile_count;
-    L.chunks_per_tile = plan.chunks_per_tile;
-    L.chunk_begin = plan.chunk_begin;
-    L.chunk_end = plan.chunk_end;
-    L.film_layout = p->film_layout;
-    L.film_row_begin = p->film_row_begin;
-    L.film_row_count = p->film_row_count ? p->film_row_count : film->height;
-    L.seed = p->seed;
-    L.grains_per_wavelength = (float)film->bins / film->wl_width; // film.rs:38
-    return L;
-}
-
 // pyr_scene_create's register allocation (program_regs.h) of every program that declares more than the in-register file. Each program
 // is read from the caller's instructions, never from a copy an earlier program's allocation rewrote -- two programs may name the same
 // or overlapping ranges -- and a program the pass renumbered gets its instructions of its own, appended to `instrs` (which starts as
@@ -1072,6 +961,139 @@ int allocate_scene_registers(const PyrSceneDesc* desc, std::vector<PyrProgram>& 
 }
 
 } // namespace
+
+namespace pyr {
+
+int plan_tiles(const PyrFilmDesc* film, const PyrRenderParams* p, TilePlan& plan) {
+    // make_tiles, renderer/algorithm.rs:158-166
+    const uint32_t ts = p->tile_size;
+    plan.tiles_x = (film->width + ts - 1) / ts;
+    plan.tiles_y = (film->height + ts - 1) / ts;
+    const uint64_t total = (uint64_t)plan.tiles_x * plan.tiles_y;
+    const uint64_t begin = p->tile_begin, end = p->tile_end ? p->tile_end : total;
+    if (total >= 0xFFFFFFFFull || begin > end || end > total) return fail(PYR_ERR_INVALID_ARGUMENT, "tile range out of bounds");
+    plan.tile_begin = (uint32_t)begin;
+    plan.tile_stride = std::max(1u, p->tile_stride);
+    plan.tile_count = (uint32_t)((end - begin + plan.tile_stride - 1) / plan.tile_stride);
+    const uint64_t per_tile = ((uint64_t)ts * ts * p->pixel_samples + 63) / 64; // iterations of a full tile: simple.rs:73
+    if (per_tile * plan.tile_count >= 0xFFFFFFFFull) return fail(PYR_ERR_UNSUPPORTED, "too many samples for one call: more than 2^32 chunks");
+    // a window [sample_begin, sample_begin + pixel_samples) must end where a one-shot call of that many samples could: same bound
+    const uint64_t window_end = (uint64_t)p->sample_begin + p->pixel_samples;
+    if (p->sample_begin != 0 && (window_end > 0xFFFFFFFFull || (((uint64_t)ts * ts * window_end + 63) / 64) * plan.tile_count >= 0xFFFFFFFFull))
+        return fail(PYR_ERR_UNSUPPORTED, "sample window ends beyond what one call can render: more than 2^32 chunks");
+    plan.chunks_per_tile = (uint32_t)std::max<uint64_t>(per_tile, 1); // pixel_samples == 0: no chunk at all
+    plan.chunk_begin = 0;
+    plan.chunk_end = (uint32_t)(per_tile * plan.tile_count);
+    return PYR_OK;
+}
+
+int check_render_args(PyrScene* scene, const PyrCamera* camera, const PyrFilmDesc* film, const PyrRenderParams* p, const void* film_ptr) {
+    if (!scene || !camera || !film || !p || !film_ptr) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+    if (film->width == 0 || film->height == 0 || film->bins == 0 || p->tile_size == 0 || p->spectrum_samples == 0)
+        return fail(PYR_ERR_INVALID_ARGUMENT, "zero-sized parameter");
+    if (!(film->wl_width > 0.0f)) return fail(PYR_ERR_INVALID_ARGUMENT, "empty wavelength span");
+    uint32_t rows = p->film_row_count ? p->film_row_count : film->height;
+    if ((uint64_t)p->film_row_begin + rows > film->height) return fail(PYR_ERR_INVALID_ARGUMENT, "film window exceeds the image");
+    if (p->spectrum_samples > 64) return fail(PYR_ERR_UNSUPPORTED, "spectrum_samples > 64");
+    // a pixel is a 32-bit index into the call's film buffer (0xFFFFFFFF stands for "none"): 65,535 x 65,535 still fits
+    if ((uint64_t)film->width * film->height >= 0xFFFFFFFFull) return fail(PYR_ERR_UNSUPPORTED, "image too large: 2^32 pixels or more");
+    if (p->film_layout == PYR_FILM_TILE_BLOCKS) {
+        const uint64_t tiles = (uint64_t)((film->width + p->tile_size - 1) / p->tile_size) * ((film->height + p->tile_size - 1) / p->tile_size);
+        if (tiles * (p->tile_size + 2ull) * (p->tile_size + 2ull) >= 0xFFFFFFFFull) return fail(PYR_ERR_UNSUPPORTED, "image too large for a film of tile blocks");
+    }
+    if (p->film_layout > PYR_FILM_TILE_BLOCKS) return fail(PYR_ERR_INVALID_ARGUMENT, "unknown film layout");
+    if (p->film_layout == PYR_FILM_TILE_BLOCKS && (p->film_row_begin || p->film_row_count))
+        return fail(PYR_ERR_INVALID_ARGUMENT, "a film of tile blocks has no row window");
+    return PYR_OK;
+}
+
+int render_batches(PyrScene* scene, RenderLaunch L, bool count, hipStream_t stream) {
+    if (L.chunk_end == L.chunk_begin) return PYR_OK;
+    choose_schedule(scene, L);
+    if (launch_tape(scene->dev, L) != 0u) {
+        L.tape_lanes = tape_lanes_bound(scene->num_cus);
+        L.tape_max_ops = tape_ops_bound(scene->dev, L);
+        int rc = reserve_tape(scene, L, stream);
+        if (rc != PYR_OK) return rc;
+    }
+    return launch_render(scene->dev, L, count, stream, scene->num_cus, scene->program_info.wide != 0);
+}
+
+// After a render has been waited for: did a path outgrow the spectral tape (kernels.hip tape_push)? The film is wrong then.
+int check_tape_overflow(PyrScene* scene) {
+    if (!scene->tape_overflow.ptr) return PYR_OK;
+    uint32_t word = 0;
+    HIP_TRY(hipMemcpy(&word, scene->tape_overflow.ptr, sizeof(word), hipMemcpyDeviceToHost));
+    if (word == 0) return PYR_OK;
+    HIP_TRY(hipMemset(scene->tape_overflow.ptr, 0, sizeof(uint32_t)));
+    if (word == 2) return fail(PYR_ERR_DEVICE, "a wave gave up waiting on its workgroup's LDS queues (spin limit): the film of that render is invalid");
+    return fail(PYR_ERR_DEVICE, "a path appended more records than the spectral tape's bound allows: the film of that render is invalid");
+}
+
+// For the translation units that enqueue renders without waiting for them (multi.cpp): the word itself, and its check.
+uint32_t* scene_overflow_word(PyrScene* scene) { return scene ? (uint32_t*)scene->tape_overflow.ptr : nullptr; }
+int scene_check_overflow(PyrScene* scene) { return check_tape_overflow(scene); }
+
+RenderLaunch make_launch(const PyrCamera* camera, const PyrFilmDesc* film, const PyrRenderParams* p, const TilePlan& plan) {
+    RenderLaunch L{};
+    L.camera = *camera;
+    L.film = *film;
+    L.bounces = p->bounces;
+    L.light_samples = p->light_samples;
+    L.spectrum_samples = p->spectrum_samples;
+    L.tile_size = p->tile_size;
+    L.pixel_samples = p->pixel_samples;
+    L.sample_begin = p->sample_begin;
+    L.tiles_x = plan.tiles_x;
+    L.tiles_y = plan.tiles_y;
+    L.tile_begin = plan.tile_begin;
+    L.tile_stride = plan.tile_stride;
+    L.tile_count = plan.tile_count;
+    L.chunks_per_tile = plan.chunks_per_tile;
+    L.chunk_begin = plan.chunk_begin;
+    L.chunk_end = plan.chunk_end;
+    L.film_layout = p->film_layout;
+    L.film_row_begin = p->film_row_begin;
+    L.film_row_count = p->film_row_count ? p->film_row_count : film->height;
+    L.seed = p->seed;
+    L.grains_per_wavelength = (float)film->bins / film->wl_width; // film.rs:38
+    return L;
+}
+
+// What the three feature entries refuse before a device is looked for. `what` names the scene or session argument.
+int check_feature_args(const void* owner, const char* what, const PyrCamera* camera, bool need_camera, const PyrFilmDesc* film, const PyrFeatureParams* fp,
+                       const void* albedo, const void* pixels) {
+    if (!owner) return fail(PYR_ERR_INVALID_ARGUMENT, std::string("null argument: ") + what);
+    if (need_camera && !camera) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: camera");
+    if (!film) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: film");
+    if (!fp) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: fp");
+    if (!albedo && !pixels) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: the albedo and the pixel buffer are both null");
+    if (fp->grid < 1 || fp->grid > 8) return fail(PYR_ERR_INVALID_ARGUMENT, "fp->grid must be 1..8");
+    if (albedo && (fp->albedo_bins < 1 || fp->albedo_bins > 64)) return fail(PYR_ERR_INVALID_ARGUMENT, "fp->albedo_bins must be 1..64");
+    if (film->width == 0 || film->height == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "film: zero-sized image");
+    if (albedo && !(film->wl_width > 0.0f)) return fail(PYR_ERR_INVALID_ARGUMENT, "film: empty wavelength span");
+    if ((uint64_t)film->width * film->height >= 0xFFFFFFFFull) return fail(PYR_ERR_INVALID_ARGUMENT, "film: 2^32 pixels or more");
+    if (pyr_device_count() <= 0) return fail(PYR_ERR_DEVICE, "no HIP device is visible; pyrite_gpu has no CPU path");
+    return PYR_OK;
+}
+
+// Enqueues the pass on `stream`; the buffers are on the scene's device (either may be null).
+int enqueue_features(PyrScene* scene, const PyrCamera* camera, const PyrFilmDesc* film, const PyrFeatureParams* fp, PyrGrain* albedo, PyrFeaturePixel* pixels,
+                     hipStream_t stream) {
+    if (!scene->tail_count) HIP_TRY(hipMalloc((void**)&scene->tail_count, kFeedBytes));
+    HIP_TRY(hipMemsetAsync(scene->tail_count, 0, kFeedBytes, stream));
+    FeatureLaunch L{};
+    L.camera = *camera;
+    L.film = *film;
+    L.grid = fp->grid;
+    L.albedo_bins = albedo ? fp->albedo_bins : 0u;
+    L.albedo = albedo;
+    L.pixels = pixels;
+    L.next = scene->tail_count;
+    return launch_features(scene->dev, L, stream, scene->num_cus, scene->program_info.wide != 0);
+}
+
+} // namespace pyr
 
 extern "C" {
 
@@ -1224,9 +1246,7 @@ int pyr_film_blocks_assemble_device(const PyrFilmDesc* film, const PyrRenderPara
     A.tile_count = plan.tile_count;
     A.blocks = blocks_device;
     A.film_out = film_device;
-    rc = launch_assemble(A, hip_stream);
-    if (rc != PYR_OK) return fail(rc, kernels_last_error());
-    return PYR_OK;
+    return launch_assemble(A, hip_stream);
 }
 
 int pyr_scene_counters(PyrScene* scene, PyrCounters* out) {
@@ -1246,9 +1266,7 @@ int pyr_scene_intersect_device(PyrScene* scene, const float* rays_device, uint32
     if (!scene->tail_count) HIP_TRY(hipMalloc((void**)&scene->tail_count, kFeedBytes));
     HIP_TRY(hipMemsetAsync(scene->tail_count, 0, kFeedBytes, (hipStream_t)hip_stream));
     IntersectLaunch L{rays_device, hits_device, n, nullptr, scene->tail_count, (uint32_t)scene->num_cus};
-    int rc = launch_intersect(scene->dev, L, false, hip_stream);
-    if (rc != PYR_OK) return fail(rc, kernels_last_error());
-    return PYR_OK;
+    return launch_intersect(scene->dev, L, false, hip_stream);
 }
 
 int pyr_scene_intersect(PyrScene* scene, const float* rays, uint32_t n, PyrHit* hits, float* elapsed_ms, PyrCounters* counters) {
@@ -1267,8 +1285,7 @@ int pyr_scene_intersect(PyrScene* scene, const float* rays, uint32_t n, PyrHit* 
         HIP_TRY(hipMemset(scene->tail_count, 0, kFeedBytes));
         HIP_TRY(hipMemset(scene->counters.ptr, 0, sizeof(PyrCounters)));
         L.counters = (unsigned long long*)scene->counters.ptr;
-        rc = launch_intersect(scene->dev, L, true, nullptr);
-        if (rc != PYR_OK) return fail(rc, kernels_last_error());
+        if ((rc = launch_intersect(scene->dev, L, true, nullptr)) != PYR_OK) return rc;
         HIP_TRY(hipDeviceSynchronize());
         HIP_TRY(hipMemcpy(counters, scene->counters.ptr, sizeof(PyrCounters), hipMemcpyDeviceToHost));
         L.counters = nullptr;
@@ -1278,8 +1295,7 @@ int pyr_scene_intersect(PyrScene* scene, const float* rays, uint32_t n, PyrHit* 
     HIP_TRY(hipEventCreate(&stop));
     HIP_TRY(hipMemset(scene->tail_count, 0, kFeedBytes));
     HIP_TRY(hipEventRecord(start, nullptr));
-    rc = launch_intersect(scene->dev, L, false, nullptr);
-    if (rc != PYR_OK) return fail(rc, kernels_last_error());
+    if ((rc = launch_intersect(scene->dev, L, false, nullptr)) != PYR_OK) return rc;
     HIP_TRY(hipEventRecord(stop, nullptr));
     HIP_TRY(hipEventSynchronize(stop));
     float ms = 0.0f;
@@ -1288,101 +1304,6 @@ int pyr_scene_intersect(PyrScene* scene, const float* rays, uint32_t n, PyrHit* 
     (void)hipEventDestroy(stop);
     if (elapsed_ms) *elapsed_ms = ms;
     HIP_TRY(hipMemcpy(hits, hits_dev.ptr, (size_t)n * sizeof(PyrHit), hipMemcpyDeviceToHost));
-    return PYR_OK;
-}
-
-// Which develop kernel a launch runs. Both write the same bytes (tests/test_gpu_session.py); the choice is the measured one (DESIGN.md
-// section 9a, C3-sized film): develop_wave_kernel (kernels/film.hip: one wave per run of pixels, the whole film read in full lines) when
-// the trapezoid walk touches most bins -- step 2: 2.90 against 4.85 ms -- and develop_kernel (kernels/main.hip: one thread per pixel,
-// reads only the bins it samples) when it touches fewer than half of them -- step 30, 15 of 64 bins: 0.44 against 0.65 ms. Two half films
-// are developed by the wave kernel, which adds them as it reads; films of more bins than its LDS rows hold by develop_kernel.
-// PYRITE_DEVELOP_KERNEL=pixel|wave overrides (development: tools/bench_session.py times one against the other).
-static bool develop_uses_wave(const DevelopLaunch& D) {
-    if (!develop_wave_serves(D)) return false;
-    if (D.grains_b) return true;
-    const char* e = std::getenv("PYRITE_DEVELOP_KERNEL");
-    if (e && std::string(e) == "pixel") return false;
-    if (e && std::string(e) == "wave") return true;
-    return 2ull * D.sample_count > D.film.bins;
-}
-
-// The launch record of a development with the per-wavelength tables at `tables` (device: filter, white_div, white_mul -- sample_count
-// floats each -- then the observer table); `host` receives the same floats for the caller to copy there.
-static DevelopLaunch develop_launch(const PyrFilmDesc* film, const PyrDevelopParams* p, float* tables, std::vector<float>& host) {
-    const size_t n = p->sample_count;
-    host.assign(3 * n + 3 * (size_t)p->xyz_count, 0.0f);
-    if (p->filter) std::memcpy(host.data(), p->filter, n * 4);
-    if (p->white_div) {
-        std::memcpy(host.data() + n, p->white_div, n * 4);
-        std::memcpy(host.data() + 2 * n, p->white_mul, n * 4);
-    }
-    std::memcpy(host.data() + 3 * n, p->xyz_table, 3 * (size_t)p->xyz_count * 4);
-    DevelopLaunch D{};
-    D.film = *film;
-    D.step_size = p->step_size;
-    D.xyz_scale = p->xyz_scale;
-    D.sample_count = p->sample_count;
-    D.filter = p->filter ? tables : nullptr;
-    D.white_div = p->white_div ? tables + n : nullptr;
-    D.white_mul = p->white_div ? tables + 2 * n : nullptr;
-    D.xyz_table = tables + 3 * n;
-    D.xyz_count = p->xyz_count;
-    D.xyz_min = p->xyz_min;
-    D.xyz_max = p->xyz_max;
-    return D;
-}
-static int check_develop_params(const PyrDevelopParams* p) {
-    if (!(p->step_size > 0.0f) || p->sample_count == 0 || p->xyz_count < 2) return fail(PYR_ERR_INVALID_ARGUMENT, "bad development parameters");
-    if ((p->white_div == nullptr) != (p->white_mul == nullptr)) return fail(PYR_ERR_INVALID_ARGUMENT, "white_div and white_mul go together");
-    return PYR_OK;
-}
-
-static int develop_common(const PyrFilmDesc* film, const PyrGrain* grains_device, const PyrDevelopParams* p, uint8_t* rgb_device, hipStream_t stream,
-                          bool blocking) {
-    if (int bad = check_develop_params(p)) return bad;
-    // the small per-wavelength tables are copied for the call (stream-ordered allocation, freed after the kernel)
-    float* tables = nullptr;
-    const size_t floats = 3 * (size_t)p->sample_count + 3 * (size_t)p->xyz_count;
-    HIP_TRY(hipMallocAsync((void**)&tables, floats * sizeof(float), stream));
-    std::vector<float> host;
-    DevelopLaunch D = develop_launch(film, p, tables, host);
-    {
-        const hipError_t copied = hipMemcpy(tables, host.data(), floats * sizeof(float), hipMemcpyHostToDevice); // synchronous: `host` dies with this frame
-        if (copied != hipSuccess) {
-            (void)hipFreeAsync(tables, stream);
-            return hip_fail(copied, "hipMemcpy(development tables)");
-        }
-    }
-    D.grains = grains_device;
-    D.rgb_out = rgb_device;
-    const bool wave = develop_uses_wave(D);
-    int rc = wave ? launch_develop_wave(D, stream) : launch_develop(D, stream);
-    hipError_t e = hipFreeAsync(tables, stream);
-    if (rc != PYR_OK) return fail(rc, wave ? film_kernels_last_error() : kernels_last_error());
-    if (e != hipSuccess) return hip_fail(e, "hipFreeAsync");
-    if (blocking) HIP_TRY(hipStreamSynchronize(stream));
-    return PYR_OK;
-}
-
-int pyr_film_develop_device(const PyrFilmDesc* film, const PyrGrain* grains_device, const PyrDevelopParams* params, uint8_t* rgb_device, int device,
-                            void* hip_stream) {
-    if (!film || !grains_device || !params || !rgb_device || !params->xyz_table) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
-    if (pyr_device_count() <= device || device < 0) return fail(PYR_ERR_DEVICE, "no such HIP device; pyrite_gpu has no CPU path");
-    HIP_TRY(hipSetDevice(device));
-    return develop_common(film, grains_device, params, rgb_device, (hipStream_t)hip_stream, false);
-}
-
-int pyr_film_develop(const PyrFilmDesc* film, const PyrGrain* grains, const PyrDevelopParams* params, uint8_t* rgb_out, int device) {
-    if (!film || !grains || !params || !rgb_out || !params->xyz_table) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
-    if (pyr_device_count() <= device || device < 0) return fail(PYR_ERR_DEVICE, "no such HIP device; pyrite_gpu has no CPU path");
-    HIP_TRY(hipSetDevice(device));
-    const size_t pixels = (size_t)film->width * film->height;
-    DeviceBuffer film_dev, rgb_dev;
-    int rc;
-    if ((rc = film_dev.upload(grains, pixels * film->bins * sizeof(PyrGrain))) != PYR_OK) return rc;
-    if ((rc = rgb_dev.alloc(pixels * 3)) != PYR_OK) return rc;
-    if ((rc = develop_common(film, (const PyrGrain*)film_dev.ptr, params, (uint8_t*)rgb_dev.ptr, nullptr, true)) != PYR_OK) return rc;
-    HIP_TRY(hipMemcpy(rgb_out, rgb_dev.ptr, pixels * 3, hipMemcpyDeviceToHost));
     return PYR_OK;
 }
 
@@ -1395,7 +1316,7 @@ int pyr_scene_path_info(PyrScene* scene, const PyrRenderParams* params, PyrPathI
     out->stage_scheduler = L.scheduler;
     out->interpreter = scene->dev.needs_interpreter;
     out->scene_in_lds = scene_is_lds_resident(scene->dev) ? 1u : 0u;
-    out->tape = L.scheduler == 0 ? 0u : scene->dev.needs_interpreter == 0 ? 1u : uses_hit_tape(scene->dev, L) ? 2u : 0u;
+    out->tape = launch_tape(scene->dev, L);
     out->phase_lanes = L.scheduler != 0 ? L.sm_phase_lanes : 0u;
     return PYR_OK;
 }
@@ -1422,320 +1343,7 @@ int pyr_scene_bvh_info(PyrScene* scene, PyrBvhInfo* out) {
     return PYR_OK;
 }
 
-} // extern "C"
-
-// ------------------------------------------------------------------------------------------------ progressive sessions
-struct PyrSession {
-    PyrScene* scene = nullptr;
-    PyrCamera camera{};
-    PyrFilmDesc film{};
-    PyrRenderParams params{}; // pixel_samples = the whole budget
-    bool halves = false;
-    hipStream_t stream = nullptr;
-    DeviceBuffer film_a, film_b, sum, rgb, tables, noise, linear, stats;
-    std::vector<float> host_tables;
-    size_t grains = 0;
-    uint32_t samples_done = 0, passes = 0;
-    uint32_t tiles_x = 0, tiles_y = 0;
-    ~PyrSession() {
-        if (scene) scene->live_sessions--; // (pyr_scene_update refuses a scene that has one)
-        if (stream) (void)hipStreamDestroy(stream);
-    }
-};
-
-namespace {
-
-int session_ready(PyrSession* s) {
-    if (!s) return fail(PYR_ERR_INVALID_ARGUMENT, "null session");
-    HIP_TRY(hipSetDevice(s->scene->device));
-    return PYR_OK;
-}
-
-// The film of the session on its device, valid in stream order: A, or A + B in the session's sum buffer.
-int session_film(PyrSession* s, const PyrGrain** out) {
-    *out = (const PyrGrain*)s->film_a.ptr;
-    if (!s->halves) return PYR_OK;
-    if (!s->sum.ptr) {
-        int rc = s->sum.alloc(s->grains * sizeof(PyrGrain));
-        if (rc != PYR_OK) return rc;
-    }
-    int rc = launch_film_sum((const PyrGrain*)s->film_a.ptr, (const PyrGrain*)s->film_b.ptr, (PyrGrain*)s->sum.ptr, s->grains, s->stream);
-    if (rc != PYR_OK) return fail(rc, film_kernels_last_error());
-    *out = (const PyrGrain*)s->sum.ptr;
-    return PYR_OK;
-}
-
-int session_sync(PyrSession* s) {
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    return check_tape_overflow(s->scene);
-}
-
-// The session's development tables on its device, in stream order, and the launch record that reads them (grains: A, and B with halves).
-int session_develop_launch(PyrSession* s, const PyrDevelopParams* p, DevelopLaunch& D) {
-    const size_t floats = 3 * (size_t)p->sample_count + 3 * (size_t)p->xyz_count;
-    if (floats * sizeof(float) > s->tables.bytes || !s->tables.ptr) {
-        HIP_TRY(hipStreamSynchronize(s->stream)); // an earlier preview may still read the old tables
-        s->tables.release();
-        if (int rc = s->tables.alloc(floats * sizeof(float))) return rc;
-    }
-    D = develop_launch(&s->film, p, (float*)s->tables.ptr, s->host_tables);
-    HIP_TRY(hipMemcpyAsync(s->tables.ptr, s->host_tables.data(), floats * sizeof(float), hipMemcpyHostToDevice, s->stream));
-    D.grains = (const PyrGrain*)s->film_a.ptr;
-    D.grains_b = s->halves ? (const PyrGrain*)s->film_b.ptr : nullptr;
-    return PYR_OK;
-}
-
-// What pyr_session_create and pyr_render_simple_progressive refuse before anything runs.
-int check_session_args(PyrScene* scene, const PyrCamera* camera, const PyrFilmDesc* film, const PyrRenderParams* p) {
-    if (!scene || !camera || !film || !p) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
-    if (film->width == 0 || film->height == 0 || film->bins == 0 || p->tile_size == 0 || p->spectrum_samples == 0 || p->pixel_samples == 0)
-        return fail(PYR_ERR_INVALID_ARGUMENT, "zero-sized parameter");
-    if (p->sample_begin != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "a session starts its own sample windows: sample_begin must be 0");
-    if (p->film_layout != PYR_FILM_ROWS || p->film_row_begin != 0 || (p->film_row_count != 0 && p->film_row_count != film->height))
-        return fail(PYR_ERR_INVALID_ARGUMENT, "a session holds the whole image in the film.rs:56 layout");
-    if (p->flags & PYR_FLAG_COUNTERS) return fail(PYR_ERR_INVALID_ARGUMENT, "a session keeps no counters");
-    if (pyr_device_count() <= 0) return fail(PYR_ERR_DEVICE, "no HIP device is visible; pyrite_gpu has no CPU path");
-    return PYR_OK;
-}
-
-} // namespace
-
-extern "C" {
-
-int pyr_session_create(PyrScene* scene, const PyrCamera* camera, const PyrFilmDesc* film, const PyrRenderParams* params, uint32_t flags,
-                       const PyrGrain* film_host, PyrSession** out_session) {
-    if (!out_session) return fail(PYR_ERR_INVALID_ARGUMENT, "null out pointer");
-    *out_session = nullptr;
-    int rc = check_session_args(scene, camera, film, params);
-    if (rc != PYR_OK) return rc;
-    if (flags & ~PYR_SESSION_HALVES) return fail(PYR_ERR_INVALID_ARGUMENT, "unknown session flag");
-    if ((rc = check_render_args(scene, camera, film, params, scene)) != PYR_OK) return rc;
-    TilePlan plan;
-    if ((rc = plan_tiles(film, params, plan)) != PYR_OK) return rc; // the whole budget must be one a single call could render
-    HIP_TRY(hipSetDevice(scene->device));
-    std::unique_ptr<PyrSession> s(new (std::nothrow) PyrSession());
-    if (!s) return fail(PYR_ERR_OUT_OF_MEMORY, "out of host memory");
-    s->scene = scene;
-    scene->live_sessions++;
-    s->camera = *camera;
-    s->film = *film;
-    s->params = *params;
-    s->halves = (flags & PYR_SESSION_HALVES) != 0;
-    s->tiles_x = plan.tiles_x, s->tiles_y = plan.tiles_y;
-    s->grains = (size_t)film->width * film->height * film->bins;
-    const size_t bytes = s->grains * sizeof(PyrGrain);
-    HIP_TRY(hipStreamCreateWithFlags(&s->stream, hipStreamNonBlocking));
-    if (film_host) {
-        if ((rc = s->film_a.upload(film_host, bytes)) != PYR_OK) return rc;
-    } else {
-        if ((rc = s->film_a.alloc(bytes)) != PYR_OK) return rc;
-        HIP_TRY(hipMemsetAsync(s->film_a.ptr, 0, bytes, s->stream));
-    }
-    if (s->halves) {
-        if ((rc = s->film_b.alloc(bytes)) != PYR_OK) return rc;
-        HIP_TRY(hipMemsetAsync(s->film_b.ptr, 0, bytes, s->stream));
-    }
-    if ((rc = s->rgb.alloc((size_t)film->width * film->height * 3)) != PYR_OK) return rc;
-    HIP_TRY(hipStreamSynchronize(s->stream));
-    *out_session = s.release();
-    return PYR_OK;
-}
-
-void pyr_session_destroy(PyrSession* session) {
-    if (!session) return;
-    (void)hipSetDevice(session->scene->device);
-    (void)hipStreamSynchronize(session->stream); // a pass may still be writing the films
-    delete session;
-}
-
-int pyr_session_render(PyrSession* session, uint32_t samples) {
-    int rc = session_ready(session);
-    if (rc != PYR_OK) return rc;
-    if (samples == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "zero-sized parameter");
-    const uint32_t left = session->params.pixel_samples - session->samples_done;
-    if (left == 0) return PYR_OK; // the budget is spent
-    PyrRenderParams p = session->params;
-    p.sample_begin = session->samples_done;
-    p.pixel_samples = std::min(samples, left);
-    TilePlan plan;
-    if ((rc = plan_tiles(&session->film, &p, plan)) != PYR_OK) return rc;
-    RenderLaunch L = make_launch(&session->camera, &session->film, &p, plan);
-    L.film_out = (PyrGrain*)((session->halves && (session->passes & 1u)) ? session->film_b.ptr : session->film_a.ptr);
-    if ((rc = render_batches(session->scene, L, false, session->stream)) != PYR_OK) return rc;
-    session->samples_done += p.pixel_samples;
-    session->passes += 1;
-    return PYR_OK;
-}
-
-int pyr_session_sync(PyrSession* session) {
-    int rc = session_ready(session);
-    if (rc != PYR_OK) return rc;
-    return session_sync(session);
-}
-
-int pyr_session_samples_done(PyrSession* session, uint32_t* out_samples) {
-    if (!session || !out_samples) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
-    *out_samples = session->samples_done;
-    return PYR_OK;
-}
-
-int pyr_session_preview(PyrSession* session, const PyrDevelopParams* develop_params, uint8_t* rgb_out) {
-    if (!session || !develop_params || !rgb_out || !develop_params->xyz_table) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
-    int rc = session_ready(session);
-    if (rc != PYR_OK) return rc;
-    if ((rc = check_develop_params(develop_params)) != PYR_OK) return rc;
-    PyrSession* s = session;
-    DevelopLaunch D{};
-    if ((rc = session_develop_launch(s, develop_params, D)) != PYR_OK) return rc;
-    D.rgb_out = (uint8_t*)s->rgb.ptr;
-    const PyrGrain* summed = nullptr;
-    if (!develop_uses_wave(D)) { // the per-pixel kernel (of A + B where there are halves and the film has more bins than the wave kernel's rows)
-        if ((rc = session_film(s, &summed)) != PYR_OK) return rc;
-        D.grains = summed, D.grains_b = nullptr;
-        rc = launch_develop(D, s->stream);
-        if (rc != PYR_OK) return fail(rc, kernels_last_error());
-    } else {
-        rc = launch_develop_wave(D, s->stream);
-        if (rc != PYR_OK) return fail(rc, film_kernels_last_error());
-    }
-    HIP_TRY(hipMemcpyAsync(rgb_out, s->rgb.ptr, (size_t)s->film.width * s->film.height * 3, hipMemcpyDeviceToHost, s->stream));
-    return session_sync(s);
-}
-
-int pyr_session_film_device(PyrSession* session, PyrGrain* film_out_device) {
-    if (!session || !film_out_device) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
-    int rc = session_ready(session);
-    if (rc != PYR_OK) return rc;
-    if (session->halves) {
-        rc = launch_film_sum((const PyrGrain*)session->film_a.ptr, (const PyrGrain*)session->film_b.ptr, film_out_device, session->grains, session->stream);
-        if (rc != PYR_OK) return fail(rc, film_kernels_last_error());
-    } else {
-        HIP_TRY(hipMemcpyAsync(film_out_device, session->film_a.ptr, session->grains * sizeof(PyrGrain), hipMemcpyDeviceToDevice, session->stream));
-    }
-    return session_sync(session);
-}
-
-int pyr_session_film(PyrSession* session, PyrGrain* film_out) {
-    if (!session || !film_out) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
-    int rc = session_ready(session);
-    if (rc != PYR_OK) return rc;
-    const PyrGrain* film = nullptr;
-    if ((rc = session_film(session, &film)) != PYR_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(film_out, film, session->grains * sizeof(PyrGrain), hipMemcpyDeviceToHost, session->stream));
-    return session_sync(session);
-}
-
-int pyr_session_halves(PyrSession* session, PyrGrain* film_a_out, PyrGrain* film_b_out) {
-    if (!session || !film_a_out || !film_b_out) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
-    int rc = session_ready(session);
-    if (rc != PYR_OK) return rc;
-    if (!session->halves) return fail(PYR_ERR_INVALID_ARGUMENT, "the session was created without PYR_SESSION_HALVES");
-    HIP_TRY(hipMemcpyAsync(film_a_out, session->film_a.ptr, session->grains * sizeof(PyrGrain), hipMemcpyDeviceToHost, session->stream));
-    HIP_TRY(hipMemcpyAsync(film_b_out, session->film_b.ptr, session->grains * sizeof(PyrGrain), hipMemcpyDeviceToHost, session->stream));
-    return session_sync(session);
-}
-
-int pyr_session_noise(PyrSession* session, float* out_per_tile) {
-    if (!session || !out_per_tile) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
-    int rc = session_ready(session);
-    if (rc != PYR_OK) return rc;
-    if (!session->halves) return fail(PYR_ERR_INVALID_ARGUMENT, "the noise estimate needs the two half films: create the session with PYR_SESSION_HALVES");
-    if (session->passes < 2) return fail(PYR_ERR_INVALID_ARGUMENT, "the noise estimate needs at least two passes: one half film is still empty");
-    const size_t tiles = (size_t)session->tiles_x * session->tiles_y;
-    if (!session->noise.ptr && (rc = session->noise.alloc(tiles * sizeof(float))) != PYR_OK) return rc;
-    NoiseLaunch N{};
-    N.film = session->film;
-    N.tile_size = session->params.tile_size;
-    N.tiles_x = session->tiles_x, N.tiles_y = session->tiles_y;
-    N.a = (const PyrGrain*)session->film_a.ptr;
-    N.b = (const PyrGrain*)session->film_b.ptr;
-    N.out = (float*)session->noise.ptr;
-    rc = launch_noise(N, session->stream);
-    if (rc != PYR_OK) return fail(rc, film_kernels_last_error());
-    HIP_TRY(hipMemcpyAsync(out_per_tile, session->noise.ptr, tiles * sizeof(float), hipMemcpyDeviceToHost, session->stream));
-    return session_sync(session);
-}
-
-int pyr_render_simple_progressive(PyrScene* scene, const PyrCamera* camera, const PyrFilmDesc* film, const PyrRenderParams* params, PyrGrain* film_inout,
-                                  uint32_t pass_samples, PyrProgressFn on_status, PyrPreviewFn on_preview, double preview_min_interval_s,
-                                  const PyrDevelopParams* preview_develop_params, void* user) {
-    if (!film_inout) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
-    if (on_preview && (!preview_develop_params || !preview_develop_params->xyz_table)) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: a preview needs development parameters");
-    if (!scene || !camera || !film || !params) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
-    if (pass_samples == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "zero-sized parameter: pass_samples");
-    if (!(preview_min_interval_s >= 0.0)) return fail(PYR_ERR_INVALID_ARGUMENT, "negative preview interval");
-    int rc = check_session_args(scene, camera, film, params);
-    if (rc != PYR_OK) return rc;
-    PyrSession* raw = nullptr;
-    if ((rc = pyr_session_create(scene, camera, film, params, 0u, film_inout, &raw)) != PYR_OK) return rc;
-    struct Closer {
-        PyrSession* s;
-        ~Closer() { pyr_session_destroy(s); }
-    } closer{raw};
-    const char* message = "Rendering"; // simple.rs:30
-    if (on_status) on_status(user, 0, message);
-    std::vector<uint8_t> rgb;
-    if (on_preview) rgb.resize((size_t)film->width * film->height * 3);
-    const uint32_t budget = params->pixel_samples;
-    auto last_preview = std::chrono::steady_clock::now(); // main.rs:261: the first preview comes one interval into the render
-    while (raw->samples_done < budget) {
-        if ((rc = pyr_session_render(raw, pass_samples)) != PYR_OK) return rc;
-        if ((rc = session_sync(raw)) != PYR_OK) return rc;
-        if (on_status) on_status(user, (uint8_t)((uint64_t)raw->samples_done * 100u / budget), message);
-        const auto now = std::chrono::steady_clock::now();
-        if (on_preview && std::chrono::duration<double>(now - last_preview).count() >= preview_min_interval_s) {
-            if ((rc = pyr_session_preview(raw, preview_develop_params, rgb.data())) != PYR_OK) return rc;
-            on_preview(user, rgb.data(), film->width, film->height, raw->samples_done);
-            last_preview = std::chrono::steady_clock::now();
-        }
-    }
-    return pyr_session_film(raw, film_inout);
-}
-
 // ------------------------------------------------------------------------------------------------ first-hit feature images
-} // extern "C"
-
-namespace {
-
-// What the three feature entries refuse before a device is looked for. `what` names the scene or session argument.
-int check_feature_args(const void* owner, const char* what, const PyrCamera* camera, bool need_camera, const PyrFilmDesc* film, const PyrFeatureParams* fp,
-                       const void* albedo, const void* pixels) {
-    if (!owner) return fail(PYR_ERR_INVALID_ARGUMENT, std::string("null argument: ") + what);
-    if (need_camera && !camera) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: camera");
-    if (!film) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: film");
-    if (!fp) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: fp");
-    if (!albedo && !pixels) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: the albedo and the pixel buffer are both null");
-    if (fp->grid < 1 || fp->grid > 8) return fail(PYR_ERR_INVALID_ARGUMENT, "fp->grid must be 1..8");
-    if (albedo && (fp->albedo_bins < 1 || fp->albedo_bins > 64)) return fail(PYR_ERR_INVALID_ARGUMENT, "fp->albedo_bins must be 1..64");
-    if (film->width == 0 || film->height == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "film: zero-sized image");
-    if (albedo && !(film->wl_width > 0.0f)) return fail(PYR_ERR_INVALID_ARGUMENT, "film: empty wavelength span");
-    if ((uint64_t)film->width * film->height >= 0xFFFFFFFFull) return fail(PYR_ERR_INVALID_ARGUMENT, "film: 2^32 pixels or more");
-    if (pyr_device_count() <= 0) return fail(PYR_ERR_DEVICE, "no HIP device is visible; pyrite_gpu has no CPU path");
-    return PYR_OK;
-}
-
-// Enqueues the pass on `stream`; the buffers are on the scene's device (either may be null).
-int enqueue_features(PyrScene* scene, const PyrCamera* camera, const PyrFilmDesc* film, const PyrFeatureParams* fp, PyrGrain* albedo, PyrFeaturePixel* pixels,
-                     hipStream_t stream) {
-    if (!scene->tail_count) HIP_TRY(hipMalloc((void**)&scene->tail_count, kFeedBytes));
-    HIP_TRY(hipMemsetAsync(scene->tail_count, 0, kFeedBytes, stream));
-    FeatureLaunch L{};
-    L.camera = *camera;
-    L.film = *film;
-    L.grid = fp->grid;
-    L.albedo_bins = albedo ? fp->albedo_bins : 0u;
-    L.albedo = albedo;
-    L.pixels = pixels;
-    L.next = scene->tail_count;
-    int rc = launch_features(scene->dev, L, stream, scene->num_cus, scene->program_info.wide != 0);
-    if (rc != PYR_OK) return fail(rc, feature_kernels_last_error());
-    return PYR_OK;
-}
-
-} // namespace
-
-extern "C" {
-
 int pyr_render_features_device(PyrScene* scene, const PyrCamera* camera, const PyrFilmDesc* film, const PyrFeatureParams* fp, PyrGrain* albedo_device,
                                PyrFeaturePixel* pixels_device, void* hip_stream) {
     if (((uintptr_t)pixels_device & 15u) != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "pixels_device must be 16-byte aligned"); // records are written as 16-byte vectors
@@ -1760,385 +1368,6 @@ int pyr_render_features(PyrScene* scene, const PyrCamera* camera, const PyrFilmD
     if (albedo_inout) HIP_TRY(hipMemcpy(albedo_inout, albedo_dev.ptr, albedo_bytes, hipMemcpyDeviceToHost));
     if (pixels_out) HIP_TRY(hipMemcpy(pixels_out, pixels_dev.ptr, pixel_bytes, hipMemcpyDeviceToHost));
     return PYR_OK;
-}
-
-int pyr_session_features(PyrSession* session, const PyrFeatureParams* fp, PyrGrain* albedo_out, PyrFeaturePixel* pixels_out) {
-    int rc = check_feature_args(session, "session", nullptr, false, session ? &session->film : nullptr, fp, albedo_out, pixels_out);
-    if (rc != PYR_OK) return rc;
-    if ((rc = session_ready(session)) != PYR_OK) return rc;
-    const size_t pixels = (size_t)session->film.width * session->film.height;
-    const size_t albedo_bytes = albedo_out ? pixels * fp->albedo_bins * sizeof(PyrGrain) : 0, pixel_bytes = pixels_out ? pixels * sizeof(PyrFeaturePixel) : 0;
-    DeviceBuffer albedo_dev, pixels_dev;
-    if (albedo_out) {
-        if ((rc = albedo_dev.alloc(albedo_bytes)) != PYR_OK) return rc;
-        HIP_TRY(hipMemsetAsync(albedo_dev.ptr, 0, albedo_bytes, session->stream));
-    }
-    if (pixels_out && (rc = pixels_dev.alloc(pixel_bytes)) != PYR_OK) return rc;
-    rc = enqueue_features(session->scene, &session->camera, &session->film, fp, (PyrGrain*)albedo_dev.ptr, (PyrFeaturePixel*)pixels_dev.ptr, session->stream);
-    if (rc == PYR_OK && albedo_out && hipMemcpyAsync(albedo_out, albedo_dev.ptr, albedo_bytes, hipMemcpyDeviceToHost, session->stream) != hipSuccess)
-        rc = fail(PYR_ERR_DEVICE, "hipMemcpyAsync of the albedo film failed");
-    if (rc == PYR_OK && pixels_out && hipMemcpyAsync(pixels_out, pixels_dev.ptr, pixel_bytes, hipMemcpyDeviceToHost, session->stream) != hipSuccess)
-        rc = fail(PYR_ERR_DEVICE, "hipMemcpyAsync of the feature records failed");
-    const int synced = session_sync(session); // before the buffers above are freed, whatever happened
-    return rc != PYR_OK ? rc : synced;
-}
-
-} // extern "C"
-
-// ------------------------------------------------------------------------------------------------ linear images and tone mapping
-namespace {
-
-constexpr uint64_t kMaxImagePixels = 0xFFFFFFFFull; // PyrImageStats counts in 32 bits
-
-int check_image_size(uint32_t width, uint32_t height) {
-    if ((uint64_t)width * height > kMaxImagePixels) return fail(PYR_ERR_UNSUPPORTED, "an image of more than 2^32 - 1 pixels");
-    return PYR_OK;
-}
-int check_device(int device) {
-    if (pyr_device_count() <= device || device < 0) return fail(PYR_ERR_DEVICE, "no such HIP device; pyrite_gpu has no CPU path");
-    return PYR_OK;
-}
-int check_linear_args(const PyrFilmDesc* film, const void* grains, const PyrDevelopParams* p, uint32_t space, const void* out) {
-    if (!film || !grains || !p || !out || !p->xyz_table) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
-    if (space != PYR_LINEAR_XYZ && space != PYR_LINEAR_SRGB) return fail(PYR_ERR_INVALID_ARGUMENT, "unknown space: PYR_LINEAR_XYZ or PYR_LINEAR_SRGB");
-    if (int bad = check_develop_params(p)) return bad;
-    if (film->bins == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "film: no bins");
-    return check_image_size(film->width, film->height);
-}
-bool percentile_ok(float p) { return p > 0.0f && p <= 1.0f; }
-// What pyr_tone_resolve refuses.
-int check_tone_params(const PyrToneParams* t) {
-    if (t->op != PYR_TONE_CLIP && t->op != PYR_TONE_REINHARD) return fail(PYR_ERR_INVALID_ARGUMENT, "unknown tone operator: PYR_TONE_CLIP or PYR_TONE_REINHARD");
-    if (!percentile_ok(t->percentile) || !percentile_ok(t->white_percentile)) return fail(PYR_ERR_INVALID_ARGUMENT, "a percentile outside (0, 1]");
-    if (!(t->exposure > 0.0f) && !(t->key > 0.0f)) return fail(PYR_ERR_INVALID_ARGUMENT, "an automatic exposure needs a positive key");
-    return PYR_OK;
-}
-bool tone_needs_stats(const PyrToneParams* t) { return !(t->exposure > 0.0f) || (t->op == PYR_TONE_REINHARD && !(t->white > 0.0f)); }
-// What pyr_image_tonemap refuses.
-int check_resolved_tone(const PyrToneParams* t) {
-    if (t->op != PYR_TONE_CLIP && t->op != PYR_TONE_REINHARD) return fail(PYR_ERR_INVALID_ARGUMENT, "unknown tone operator: PYR_TONE_CLIP or PYR_TONE_REINHARD");
-    if (!(t->exposure > 0.0f) || (t->op == PYR_TONE_REINHARD && !(t->white > 0.0f)))
-        return fail(PYR_ERR_INVALID_ARGUMENT, "unresolved tone parameters: pyr_tone_resolve gives the exposure and the white point");
-    return PYR_OK;
-}
-
-float upper_edge(uint32_t bin) {
-    const uint32_t bits = (bin + 889u) << 20;
-    float f;
-    std::memcpy(&f, &bits, sizeof(f));
-    return f;
-}
-uint32_t percentile_bin(const PyrImageStats* s, float percentile) {
-    uint64_t target = (uint64_t)std::ceil((double)percentile * (double)s->lit);
-    target = std::min<uint64_t>(std::max<uint64_t>(target, 1), s->lit);
-    uint64_t seen = 0;
-    for (uint32_t k = 0; k < 256; ++k) {
-        seen += s->histogram[k];
-        if (seen >= target) return k;
-    }
-    return 255; // a histogram that holds fewer than `lit` pixels
-}
-
-// Development to a linear image with the tables copied for the call, as develop_common does for the 8-bit image.
-int develop_linear_common(const PyrFilmDesc* film, const PyrGrain* grains_device, const PyrGrain* grains_b_device, const PyrDevelopParams* p, uint32_t space,
-                          float* out_device, hipStream_t stream, bool blocking) {
-    float* tables = nullptr;
-    const size_t floats = 3 * (size_t)p->sample_count + 3 * (size_t)p->xyz_count;
-    HIP_TRY(hipMallocAsync((void**)&tables, floats * sizeof(float), stream));
-    std::vector<float> host;
-    LinearLaunch L{};
-    L.develop = develop_launch(film, p, tables, host);
-    const hipError_t copied = hipMemcpy(tables, host.data(), floats * sizeof(float), hipMemcpyHostToDevice); // synchronous: `host` dies with this frame
-    if (copied != hipSuccess) {
-        (void)hipFreeAsync(tables, stream);
-        return hip_fail(copied, "hipMemcpy(development tables)");
-    }
-    L.develop.grains = grains_device;
-    L.develop.grains_b = grains_b_device;
-    L.out = out_device;
-    L.space = space;
-    const int rc = launch_develop_linear(L, stream);
-    const hipError_t e = hipFreeAsync(tables, stream);
-    if (rc != PYR_OK) return fail(rc, tone_kernels_last_error());
-    if (e != hipSuccess) return hip_fail(e, "hipFreeAsync");
-    if (blocking) HIP_TRY(hipStreamSynchronize(stream));
-    return PYR_OK;
-}
-
-// The session's film developed into its linear image buffer, enqueued on its stream.
-int session_linear(PyrSession* s, const PyrDevelopParams* p, uint32_t space) {
-    int rc;
-    const size_t bytes = (size_t)s->film.width * s->film.height * 3 * sizeof(float);
-    if (!s->linear.ptr && (rc = s->linear.alloc(bytes)) != PYR_OK) return rc;
-    LinearLaunch L{};
-    if ((rc = session_develop_launch(s, p, L.develop)) != PYR_OK) return rc;
-    L.out = (float*)s->linear.ptr;
-    L.space = space;
-    if ((rc = launch_develop_linear(L, s->stream)) != PYR_OK) return fail(rc, tone_kernels_last_error());
-    return PYR_OK;
-}
-
-} // namespace
-
-extern "C" {
-
-int pyr_film_develop_linear_device(const PyrFilmDesc* film, const PyrGrain* grains_device, const PyrGrain* grains_b_device, const PyrDevelopParams* params,
-                                   uint32_t space, float* out_device, int device, void* hip_stream) {
-    int rc = check_linear_args(film, grains_device, params, space, out_device);
-    if (rc != PYR_OK || (rc = check_device(device)) != PYR_OK) return rc;
-    HIP_TRY(hipSetDevice(device));
-    return develop_linear_common(film, grains_device, grains_b_device, params, space, out_device, (hipStream_t)hip_stream, false);
-}
-
-int pyr_film_develop_linear(const PyrFilmDesc* film, const PyrGrain* grains, const PyrGrain* grains_b, const PyrDevelopParams* params, uint32_t space, float* out,
-                            int device) {
-    int rc = check_linear_args(film, grains, params, space, out);
-    if (rc != PYR_OK || (rc = check_device(device)) != PYR_OK) return rc;
-    HIP_TRY(hipSetDevice(device));
-    const size_t pixels = (size_t)film->width * film->height;
-    DeviceBuffer a_dev, b_dev, out_dev;
-    if ((rc = a_dev.upload(grains, pixels * film->bins * sizeof(PyrGrain))) != PYR_OK) return rc;
-    if (grains_b && (rc = b_dev.upload(grains_b, pixels * film->bins * sizeof(PyrGrain))) != PYR_OK) return rc;
-    if ((rc = out_dev.alloc(pixels * 3 * sizeof(float))) != PYR_OK) return rc;
-    rc = develop_linear_common(film, (const PyrGrain*)a_dev.ptr, grains_b ? (const PyrGrain*)b_dev.ptr : nullptr, params, space, (float*)out_dev.ptr, nullptr, true);
-    if (rc != PYR_OK) return rc;
-    HIP_TRY(hipMemcpy(out, out_dev.ptr, pixels * 3 * sizeof(float), hipMemcpyDeviceToHost));
-    return PYR_OK;
-}
-
-int pyr_image_stats_device(const float* linear_srgb_device, uint32_t width, uint32_t height, PyrImageStats* out_device, int device, void* hip_stream) {
-    if (!linear_srgb_device || !out_device) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
-    int rc = check_image_size(width, height);
-    if (rc != PYR_OK || (rc = check_device(device)) != PYR_OK) return rc;
-    HIP_TRY(hipSetDevice(device));
-    if ((rc = launch_image_stats(linear_srgb_device, (size_t)width * height, out_device, hip_stream)) != PYR_OK) return fail(rc, tone_kernels_last_error());
-    return PYR_OK;
-}
-
-int pyr_image_stats(const float* linear_srgb, uint32_t width, uint32_t height, PyrImageStats* out, int device) {
-    if (!linear_srgb || !out) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
-    int rc = check_image_size(width, height);
-    if (rc != PYR_OK || (rc = check_device(device)) != PYR_OK) return rc;
-    HIP_TRY(hipSetDevice(device));
-    const size_t pixels = (size_t)width * height;
-    DeviceBuffer image_dev, stats_dev;
-    if ((rc = image_dev.upload(linear_srgb, pixels * 3 * sizeof(float))) != PYR_OK) return rc;
-    if ((rc = stats_dev.alloc(sizeof(PyrImageStats))) != PYR_OK) return rc;
-    if ((rc = launch_image_stats((const float*)image_dev.ptr, pixels, (PyrImageStats*)stats_dev.ptr, nullptr)) != PYR_OK) return fail(rc, tone_kernels_last_error());
-    HIP_TRY(hipMemcpy(out, stats_dev.ptr, sizeof(PyrImageStats), hipMemcpyDeviceToHost));
-    return PYR_OK;
-}
-
-int pyr_tone_resolve(const PyrImageStats* stats, const PyrToneParams* tone, float* exposure_out, float* white_out) {
-    if (!tone || !exposure_out || !white_out) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
-    if (int bad = check_tone_params(tone)) return bad;
-    if (tone_needs_stats(tone) && !stats) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: an automatic exposure or white point needs the statistics");
-    float exposure = tone->exposure;
-    if (!(exposure > 0.0f)) exposure = stats->lit ? tone->key / upper_edge(percentile_bin(stats, tone->percentile)) : 1.0f;
-    float white = 1.0f;
-    if (tone->op == PYR_TONE_REINHARD) {
-        if (tone->white > 0.0f)
-            white = tone->white;
-        else if (stats->lit)
-            white = exposure * upper_edge(percentile_bin(stats, tone->white_percentile));
-    }
-    *exposure_out = exposure;
-    *white_out = white;
-    return PYR_OK;
-}
-
-int pyr_image_tonemap_device(const float* linear_srgb_device, uint32_t width, uint32_t height, const PyrToneParams* resolved, uint8_t* rgb_device, int device,
-                             void* hip_stream) {
-    if (!linear_srgb_device || !resolved || !rgb_device) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
-    int rc = check_resolved_tone(resolved);
-    if (rc != PYR_OK || (rc = check_image_size(width, height)) != PYR_OK || (rc = check_device(device)) != PYR_OK) return rc;
-    HIP_TRY(hipSetDevice(device));
-    const ToneLaunch T{linear_srgb_device, rgb_device, (size_t)width * height, resolved->op, resolved->exposure, resolved->white};
-    if ((rc = launch_tonemap(T, hip_stream)) != PYR_OK) return fail(rc, tone_kernels_last_error());
-    return PYR_OK;
-}
-
-int pyr_image_tonemap(const float* linear_srgb, uint32_t width, uint32_t height, const PyrToneParams* resolved, uint8_t* rgb_out, int device) {
-    if (!linear_srgb || !resolved || !rgb_out) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
-    int rc = check_resolved_tone(resolved);
-    if (rc != PYR_OK || (rc = check_image_size(width, height)) != PYR_OK || (rc = check_device(device)) != PYR_OK) return rc;
-    HIP_TRY(hipSetDevice(device));
-    const size_t pixels = (size_t)width * height;
-    DeviceBuffer image_dev, rgb_dev;
-    if ((rc = image_dev.upload(linear_srgb, pixels * 3 * sizeof(float))) != PYR_OK) return rc;
-    if ((rc = rgb_dev.alloc(pixels * 3)) != PYR_OK) return rc;
-    const ToneLaunch T{(const float*)image_dev.ptr, (uint8_t*)rgb_dev.ptr, pixels, resolved->op, resolved->exposure, resolved->white};
-    if ((rc = launch_tonemap(T, nullptr)) != PYR_OK) return fail(rc, tone_kernels_last_error());
-    HIP_TRY(hipMemcpy(rgb_out, rgb_dev.ptr, pixels * 3, hipMemcpyDeviceToHost));
-    return PYR_OK;
-}
-
-int pyr_session_linear(PyrSession* session, const PyrDevelopParams* develop_params, uint32_t space, float* out) {
-    if (!session) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
-    int rc = check_linear_args(&session->film, session, develop_params, space, out);
-    if (rc != PYR_OK || (rc = session_ready(session)) != PYR_OK) return rc;
-    if ((rc = session_linear(session, develop_params, space)) != PYR_OK) return rc;
-    HIP_TRY(hipMemcpyAsync(out, session->linear.ptr, (size_t)session->film.width * session->film.height * 3 * sizeof(float), hipMemcpyDeviceToHost, session->stream));
-    return session_sync(session);
-}
-
-int pyr_session_preview_tone(PyrSession* session, const PyrDevelopParams* develop_params, const PyrToneParams* tone, uint8_t* rgb_out, PyrImageStats* stats_out) {
-    if (!session || !tone) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
-    int rc = check_tone_params(tone);
-    if (rc != PYR_OK || (rc = check_linear_args(&session->film, session, develop_params, PYR_LINEAR_SRGB, rgb_out)) != PYR_OK || (rc = session_ready(session)) != PYR_OK) return rc;
-    PyrSession* s = session;
-    const size_t pixels = (size_t)s->film.width * s->film.height;
-    if ((rc = session_linear(s, develop_params, PYR_LINEAR_SRGB)) != PYR_OK) return rc;
-    PyrImageStats stats{};
-    if (tone_needs_stats(tone) || stats_out) {
-        if (!s->stats.ptr && (rc = s->stats.alloc(sizeof(PyrImageStats))) != PYR_OK) return rc;
-        if ((rc = launch_image_stats((const float*)s->linear.ptr, pixels, (PyrImageStats*)s->stats.ptr, s->stream)) != PYR_OK) return fail(rc, tone_kernels_last_error());
-        HIP_TRY(hipMemcpyAsync(&stats, s->stats.ptr, sizeof(PyrImageStats), hipMemcpyDeviceToHost, s->stream));
-        HIP_TRY(hipStreamSynchronize(s->stream)); // the rule is host arithmetic on 1 KB
-        if (stats_out) *stats_out = stats;
-    }
-    ToneLaunch T{(const float*)s->linear.ptr, (uint8_t*)s->rgb.ptr, pixels, tone->op, 0.0f, 0.0f};
-    if ((rc = pyr_tone_resolve(&stats, tone, &T.exposure, &T.white)) != PYR_OK) return rc;
-    if ((rc = launch_tonemap(T, s->stream)) != PYR_OK) return fail(rc, tone_kernels_last_error());
-    HIP_TRY(hipMemcpyAsync(rgb_out, s->rgb.ptr, pixels * 3, hipMemcpyDeviceToHost, s->stream));
-    return session_sync(s);
-}
-
-} // extern "C"
-
-// ------------------------------------------------------------------------------------------------ denoising a linear image from two halves
-namespace {
-
-// What the three denoise entries refuse before a device is looked for.
-int check_denoise_params(const PyrDenoiseParams* p) {
-    if (!p) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: params");
-    if (p->radius < 1 || p->radius > PYR_DENOISE_MAX_RADIUS) return fail(PYR_ERR_INVALID_ARGUMENT, "params->radius must be 1..10");
-    if (p->patch > PYR_DENOISE_MAX_PATCH) return fail(PYR_ERR_INVALID_ARGUMENT, "params->patch must be 0..3");
-    if (!(p->k > 0.0f)) return fail(PYR_ERR_INVALID_ARGUMENT, "params->k must be positive");
-    if (!(p->epsilon > 0.0f)) return fail(PYR_ERR_INVALID_ARGUMENT, "params->epsilon must be positive");
-    if (p->reserved != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "params->reserved must be 0");
-    return PYR_OK;
-}
-int check_denoise_args(const void* a, const void* b, uint32_t width, uint32_t height, const PyrDenoiseParams* p, const void* out) {
-    if (!a) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: a");
-    if (!b) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: b");
-    if (!out) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: out");
-    if (int bad = check_denoise_params(p)) return bad;
-    if (width == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "width: an empty image");
-    if (height == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "height: an empty image");
-    return check_image_size(width, height);
-}
-
-// Variance, the two filter launches with the halves exchanged, the combine: everything on `stream`, every buffer on the current
-// device; `work` holds three images of width * height * 3 floats (V, FA, FB).
-int enqueue_denoise(const float* a, const float* b, const float* albedo, const PyrFeaturePixel* pixels, uint32_t width, uint32_t height, const PyrDenoiseParams* p,
-                    float* work, float* out, float* error_out, hipStream_t stream) {
-    const size_t floats = (size_t)width * height * 3;
-    float *variance = work, *fa = work + floats, *fb = work + 2 * floats;
-    int rc;
-    if ((rc = launch_denoise_variance(a, b, width, height, variance, stream)) != PYR_OK) return fail(rc, denoise_kernels_last_error());
-    DenoiseLaunch L{};
-    L.variance = variance;
-    L.albedo = albedo, L.pixels = pixels;
-    L.width = width, L.height = height, L.radius = p->radius, L.patch = p->patch;
-    L.kk = p->k * p->k, L.epsilon = p->epsilon;
-    L.albedo_div = 2.0f * (p->sigma_albedo * p->sigma_albedo), L.normal_div = 2.0f * (p->sigma_normal * p->sigma_normal), L.depth_div = 2.0f * (p->sigma_depth * p->sigma_depth);
-    if (!(p->sigma_albedo > 0.0f)) L.albedo_div = 0.0f;
-    if (!(p->sigma_normal > 0.0f)) L.normal_div = 0.0f;
-    if (!(p->sigma_depth > 0.0f)) L.depth_div = 0.0f;
-    L.weights_from = b, L.averaged = a, L.out = fa; // FA: a under the weights of b
-    if ((rc = launch_denoise_filter(L, stream)) != PYR_OK) return fail(rc, denoise_kernels_last_error());
-    L.weights_from = a, L.averaged = b, L.out = fb;
-    if ((rc = launch_denoise_filter(L, stream)) != PYR_OK) return fail(rc, denoise_kernels_last_error());
-    if ((rc = launch_denoise_combine(fa, fb, (size_t)width * height, out, error_out, stream)) != PYR_OK) return fail(rc, denoise_kernels_last_error());
-    return PYR_OK;
-}
-
-} // namespace
-
-extern "C" {
-
-int pyr_image_denoise_device(const float* a_device, const float* b_device, const float* albedo_device, const PyrFeaturePixel* pixels_device, uint32_t width,
-                             uint32_t height, const PyrDenoiseParams* params, float* out_device, float* error_out_device, int device, void* hip_stream) {
-    int rc = check_denoise_args(a_device, b_device, width, height, params, out_device);
-    if (rc != PYR_OK || (rc = check_device(device)) != PYR_OK) return rc;
-    HIP_TRY(hipSetDevice(device));
-    hipStream_t stream = (hipStream_t)hip_stream;
-    float* work = nullptr;
-    HIP_TRY(hipMallocAsync((void**)&work, (size_t)width * height * 9 * sizeof(float), stream));
-    rc = enqueue_denoise(a_device, b_device, albedo_device, pixels_device, width, height, params, work, out_device, error_out_device, stream);
-    const hipError_t e = hipFreeAsync(work, stream);
-    if (rc != PYR_OK) return rc;
-    if (e != hipSuccess) return hip_fail(e, "hipFreeAsync");
-    return PYR_OK;
-}
-
-int pyr_image_denoise(const float* a, const float* b, const float* albedo, const PyrFeaturePixel* pixels, uint32_t width, uint32_t height,
-                      const PyrDenoiseParams* params, float* out, float* error_out, int device) {
-    int rc = check_denoise_args(a, b, width, height, params, out);
-    if (rc != PYR_OK || (rc = check_device(device)) != PYR_OK) return rc;
-    HIP_TRY(hipSetDevice(device));
-    const size_t count = (size_t)width * height, image_bytes = count * 3 * sizeof(float);
-    DeviceBuffer a_dev, b_dev, albedo_dev, pixels_dev, work_dev, out_dev, error_dev;
-    if ((rc = a_dev.upload(a, image_bytes)) != PYR_OK || (rc = b_dev.upload(b, image_bytes)) != PYR_OK) return rc;
-    if (albedo && (rc = albedo_dev.upload(albedo, image_bytes)) != PYR_OK) return rc;
-    if (pixels && (rc = pixels_dev.upload(pixels, count * sizeof(PyrFeaturePixel))) != PYR_OK) return rc;
-    if ((rc = work_dev.alloc(3 * image_bytes)) != PYR_OK || (rc = out_dev.alloc(image_bytes)) != PYR_OK) return rc;
-    if (error_out && (rc = error_dev.alloc(image_bytes)) != PYR_OK) return rc;
-    rc = enqueue_denoise((const float*)a_dev.ptr, (const float*)b_dev.ptr, albedo ? (const float*)albedo_dev.ptr : nullptr,
-                         pixels ? (const PyrFeaturePixel*)pixels_dev.ptr : nullptr, width, height, params, (float*)work_dev.ptr, (float*)out_dev.ptr,
-                         error_out ? (float*)error_dev.ptr : nullptr, nullptr);
-    HIP_TRY(hipDeviceSynchronize()); // before the buffers above are freed, whatever happened
-    if (rc != PYR_OK) return rc;
-    HIP_TRY(hipMemcpy(out, out_dev.ptr, image_bytes, hipMemcpyDeviceToHost));
-    if (error_out) HIP_TRY(hipMemcpy(error_out, error_dev.ptr, image_bytes, hipMemcpyDeviceToHost));
-    return PYR_OK;
-}
-
-int pyr_session_denoised(PyrSession* session, const PyrDevelopParams* develop_params, const PyrFeatureParams* feature_params, const PyrDenoiseParams* denoise_params,
-                         float* out, float* error_out) {
-    if (!session) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: session");
-    PyrSession* s = session;
-    int rc = check_linear_args(&s->film, s, develop_params, PYR_LINEAR_SRGB, out);
-    if (rc != PYR_OK || (rc = check_denoise_params(denoise_params)) != PYR_OK) return rc;
-    if (feature_params && (rc = check_feature_args(s, "session", nullptr, false, &s->film, feature_params, s, s)) != PYR_OK) return rc;
-    if ((rc = session_ready(s)) != PYR_OK) return rc;
-    if (!s->halves) return fail(PYR_ERR_INVALID_ARGUMENT, "denoising needs the two half films: create the session with PYR_SESSION_HALVES");
-    if (s->passes < 2) return fail(PYR_ERR_INVALID_ARGUMENT, "denoising needs at least two passes: one half film is still empty");
-    const size_t count = (size_t)s->film.width * s->film.height, image_bytes = count * 3 * sizeof(float);
-    // a, b, the developed albedo, the filter's three working images, out, error_out: one allocation of eight images
-    DeviceBuffer images, albedo_film, records;
-    if ((rc = images.alloc(8 * image_bytes)) != PYR_OK) return rc;
-    float* image = (float*)images.ptr;
-    auto at = [&](size_t i) { return image + i * count * 3; };
-    auto enqueue = [&]() -> int {
-        int rc;
-        LinearLaunch L{};
-        if ((rc = session_develop_launch(s, develop_params, L.develop)) != PYR_OK) return rc;
-        L.space = PYR_LINEAR_SRGB;
-        L.develop.grains = (const PyrGrain*)s->film_a.ptr, L.develop.grains_b = nullptr, L.out = at(0);
-        if ((rc = launch_develop_linear(L, s->stream)) != PYR_OK) return fail(rc, tone_kernels_last_error());
-        L.develop.grains = (const PyrGrain*)s->film_b.ptr, L.out = at(1);
-        if ((rc = launch_develop_linear(L, s->stream)) != PYR_OK) return fail(rc, tone_kernels_last_error());
-        if (feature_params) {
-            const size_t albedo_bytes = count * feature_params->albedo_bins * sizeof(PyrGrain);
-            if ((rc = albedo_film.alloc(albedo_bytes)) != PYR_OK || (rc = records.alloc(count * sizeof(PyrFeaturePixel))) != PYR_OK) return rc;
-            HIP_TRY(hipMemsetAsync(albedo_film.ptr, 0, albedo_bytes, s->stream));
-            if ((rc = enqueue_features(s->scene, &s->camera, &s->film, feature_params, (PyrGrain*)albedo_film.ptr, (PyrFeaturePixel*)records.ptr, s->stream)) != PYR_OK) return rc;
-            L.develop.film.bins = feature_params->albedo_bins; // the same span, tables and parameters
-            L.develop.grains = (const PyrGrain*)albedo_film.ptr, L.out = at(2);
-            if ((rc = launch_develop_linear(L, s->stream)) != PYR_OK) return fail(rc, tone_kernels_last_error());
-        }
-        rc = enqueue_denoise(at(0), at(1), feature_params ? at(2) : nullptr, feature_params ? (const PyrFeaturePixel*)records.ptr : nullptr, s->film.width, s->film.height,
-                             denoise_params, at(3), at(6), error_out ? at(7) : nullptr, s->stream);
-        if (rc != PYR_OK) return rc;
-        HIP_TRY(hipMemcpyAsync(out, at(6), image_bytes, hipMemcpyDeviceToHost, s->stream));
-        if (error_out) HIP_TRY(hipMemcpyAsync(error_out, at(7), image_bytes, hipMemcpyDeviceToHost, s->stream));
-        return PYR_OK;
-    };
-    rc = enqueue();
-    const int synced = session_sync(s); // before the buffers above are freed, whatever happened
-    return rc != PYR_OK ? rc : synced;
 }
 
 } // extern "C"

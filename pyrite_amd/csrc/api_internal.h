@@ -1,13 +1,35 @@
-// api_internal.h -- what the host-side translation units of libpyrite_gpu.so share besides the public ABI.
+// api_internal.h -- what the host-side translation units of libpyrite_gpu.so and the launchers under kernels/ share besides the
+// public ABI: the one error channel, and a device allocation that frees itself.
 #pragma once
+#include <hip/hip_runtime.h>
+
 #include <string>
 
 #include "../../include/pyrite_gpu.h"
 
 namespace pyr {
 
-// Records the thread-local message pyr_last_error() returns and hands `code` back.
-int api_fail(int code, const std::string& message);
+// Records the thread-local message pyr_last_error() returns and hands `code` back. Everything that refuses or fails reports
+// here -- entry points, checks, the kernels' launchers -- so whoever gets a code back passes it on and the message is the failure's.
+int fail(int code, const std::string& message);
+int hip_fail(hipError_t e, const char* what);
+
+#define HIP_TRY(expr)                                          \
+    do {                                                       \
+        hipError_t e_ = (expr);                                \
+        if (e_ != hipSuccess) return pyr::hip_fail(e_, #expr); \
+    } while (0)
+
+struct DeviceBuffer {
+    void* ptr = nullptr;
+    size_t bytes = 0;
+    ~DeviceBuffer() { release(); }
+    void release();
+    int upload(const void* src, size_t n); // (over an earlier allocation: that one is freed -- a rebuild uploads into the scene's buffers again)
+    int alloc(size_t n);
+    int reserve(size_t n); // holds `n` bytes afterwards: allocated once, kept while it is large enough
+};
+
 // Device a scene was created on.
 int scene_device(const PyrScene* scene);
 // The device word the kernels set when a render's film is invalid (a path outgrew the spectral tape: 1; a wave

@@ -249,6 +249,7 @@ struct DevelopLaunch {
     uint8_t* rgb_out; // device
     const PyrGrain* grains_b; // device or nullptr: a second half film, developed as grains + grains_b (develop_wave_kernel only)
 };
+// A launcher that refuses a launch, or whose launch fails, says why through fail() (api_internal.h) and returns that code.
 int launch_develop(const DevelopLaunch& launch, void* stream); // develop_kernel: one thread per pixel (kernels/main.hip)
 
 // kernels/film.hip: the kernels of a progressive session's film
@@ -266,7 +267,6 @@ struct NoiseLaunch {
     float* out; // device, tiles_x * tiles_y
 };
 int launch_noise(const NoiseLaunch& launch, void* stream);
-const char* film_kernels_last_error();
 
 // kernels/tone.hip: the film as an image in linear light, its luminance statistics, its tone mapping
 struct LinearLaunch {
@@ -286,7 +286,6 @@ struct ToneLaunch {
     float exposure, white;
 };
 int launch_tonemap(const ToneLaunch& launch, void* stream);
-const char* tone_kernels_last_error();
 
 // kernels/denoise.hip: the cross filter of two developed half images. One launch filters `averaged` with
 // the weights read from `weights_from`; the caller launches it twice with the halves exchanged and combines the two results.
@@ -306,7 +305,6 @@ int launch_denoise_variance(const float* a, const float* b, uint32_t width, uint
 int launch_denoise_filter(const DenoiseLaunch& launch, void* stream);
 // out = (fa + fb) * 0.5f and, unless it is nullptr, error_out = fabsf(fa - fb) * 0.5f
 int launch_denoise_combine(const float* fa, const float* fb, size_t pixels, float* out, float* error_out, void* stream);
-const char* denoise_kernels_last_error();
 
 // Adds the PYR_FILM_TILE_BLOCKS buffer of the tiles tile_begin + k * tile_stride (k < tile_count) into a whole-image film.
 struct AssembleLaunch {
@@ -332,16 +330,14 @@ struct FeatureLaunch {
 using FeatureKernel = void (*)(DevScene, FeatureLaunch);
 FeatureKernel pick_wide_features_kernel(); // kernels/features_wide.hip: the build whose interpreter holds the wide register file
 int launch_features(const DevScene& scene, const FeatureLaunch& launch, void* stream, int num_cus, bool wide_vm);
-const char* feature_kernels_last_error();
 
 // launchers (kernels/main.hip)
 // wide_vm: the scene has a program that only the wide interpreter build (kernels/wide.hip) holds
 int launch_render(const DevScene& scene, const RenderLaunch& launch, bool with_counters, void* stream, int num_cus, bool wide_vm = false);
 uint32_t tape_ops_bound(const DevScene& scene, const RenderLaunch& launch); // records per path the stage-scheduled kernel may append to its spectral tape
-bool uses_hit_tape(const DevScene& scene, const RenderLaunch& launch); // an interpreter scene that records a tape in this launch
+uint32_t launch_tape(const DevScene& scene, const RenderLaunch& launch); // the tape this launch records, as PyrPathInfo::tape counts: 0 none, 1 spectral, 2 hit tape
 uint32_t tape_lanes_bound(int num_cus);              // lanes (tape columns) of the largest grid launch_render starts
 int launch_intersect(const DevScene& scene, const IntersectLaunch& launch, bool with_counters, void* stream);
-const char* kernels_last_error();
 bool scene_is_lds_resident(const DevScene& scene);
 // Which unit under kernels/ holds which build of render_kernel_sm: main.hip's pick_kernel asks these, each defined by the unit it is
 // named after (pick_wide_kernel: nullptr in the one-unit build, kernels/profile.hip).

@@ -1,0 +1,32 @@
+// image_internal.h -- what image_ops.cpp (film development, linear images, tone mapping and denoising without a scene) lets
+// session.cpp use on a session's own buffers and stream. Declarations only: image_ops.cpp defines them all.
+#pragma once
+#include <vector>
+
+#include "api_internal.h"
+#include "device_scene.h"
+
+namespace pyr {
+
+// What every entry that takes them refuses: the size of an image, the device number, the parameter blocks.
+int check_image_size(uint32_t width, uint32_t height);
+int check_device(int device);
+int check_develop_params(const PyrDevelopParams* p);
+int check_linear_args(const PyrFilmDesc* film, const void* grains, const PyrDevelopParams* p, uint32_t space, const void* out);
+int check_tone_params(const PyrToneParams* t); // what pyr_tone_resolve refuses
+bool tone_needs_stats(const PyrToneParams* t);
+int check_denoise_params(const PyrDenoiseParams* p);
+
+// The per-wavelength tables of a development -- filter, white_div, white_mul, sample_count floats each, then the observer table --
+// are develop_table_floats(p) floats. develop_launch makes the launch record that reads them at `tables` (device); `host` receives
+// the same floats for the caller to copy there.
+size_t develop_table_floats(const PyrDevelopParams* p);
+DevelopLaunch develop_launch(const PyrFilmDesc* film, const PyrDevelopParams* p, float* tables, std::vector<float>& host);
+bool develop_uses_wave(const DevelopLaunch& D); // launch_develop_wave, not launch_develop: read at every call (PYRITE_DEVELOP_KERNEL)
+
+// Variance, the two filter launches with the halves exchanged, the combine: everything on `stream`, every buffer on the current
+// device; `work` holds three images of width * height * 3 floats (V, FA, FB).
+int enqueue_denoise(const float* a, const float* b, const float* albedo, const PyrFeaturePixel* pixels, uint32_t width, uint32_t height, const PyrDenoiseParams* p,
+                    float* work, float* out, float* error_out, hipStream_t stream);
+
+} // namespace pyr

@@ -6,24 +6,22 @@
 #include <cmath>
 #include <string>
 
+#include "../api_internal.h"
 #include "../device_scene.h"
 #include "denoise_tile.h"
 
 namespace pyr {
 
 namespace {
-thread_local std::string g_denoise_error;
 constexpr uint32_t PIXEL_BLOCK = 256;
 constexpr uint32_t TILE_BLOCK = kDenoiseTile * kDenoiseTile;
 
 int launched(const char* what) {
     const hipError_t err = hipGetLastError();
     if (err == hipSuccess) return PYR_OK;
-    g_denoise_error = std::string(what) + " kernel launch: " + hipGetErrorString(err);
-    return PYR_ERR_DEVICE;
+    return fail(PYR_ERR_DEVICE, std::string(what) + " kernel launch: " + hipGetErrorString(err));
 }
 } // namespace
-const char* denoise_kernels_last_error() { return g_denoise_error.c_str(); }
 
 // ------------------------------------------------------------------------------------------------ the variance of one half
 // V_c(p) = 0.5f * (sum of (a_c - b_c)^2 over p's 3 x 3 neighbourhood clipped to the image, raster order, / the pixels summed); NaN
@@ -165,16 +163,11 @@ int launch_denoise_variance(const float* a, const float* b, uint32_t width, uint
 int launch_denoise_filter(const DenoiseLaunch& launch, void* stream) {
     DenoiseLaunch L = launch;
     if (L.width == 0 || L.height == 0) return PYR_OK;
-    if (L.radius < 1 || L.radius > kDenoiseMaxRadius || L.patch > kDenoiseMaxPatch) { // the LDS tile is sized by these
-        g_denoise_error = "denoise filter: radius or patch out of range";
-        return PYR_ERR_INVALID_ARGUMENT;
-    }
+    if (L.radius < 1 || L.radius > kDenoiseMaxRadius || L.patch > kDenoiseMaxPatch) // the LDS tile is sized by these
+        return fail(PYR_ERR_INVALID_ARGUMENT, "denoise filter: radius or patch out of range");
     L.tiles_x = (L.width + kDenoiseTile - 1) / kDenoiseTile;
     const uint64_t tiles = (uint64_t)L.tiles_x * ((L.height + kDenoiseTile - 1) / kDenoiseTile);
-    if (tiles > 0x7FFFFFFFull) {
-        g_denoise_error = "denoise filter: more tiles than a grid holds";
-        return PYR_ERR_UNSUPPORTED;
-    }
+    if (tiles > 0x7FFFFFFFull) return fail(PYR_ERR_UNSUPPORTED, "denoise filter: more tiles than a grid holds");
     const size_t lds = (size_t)3 * denoise_plane_cells(L.radius + L.patch) * sizeof(float2);
     hipLaunchKernelGGL(denoise_filter_kernel, dim3((uint32_t)tiles), dim3(TILE_BLOCK), lds, (hipStream_t)stream, L);
     return launched("denoise filter");

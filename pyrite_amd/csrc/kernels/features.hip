@@ -6,6 +6,8 @@
 #endif
 #include "../kernels.hip"
 
+#include "../api_internal.h"
+
 namespace pyr {
 #ifdef PYR_WIDE_VM
 namespace wide {
@@ -199,16 +201,8 @@ __global__ __launch_bounds__(BLOCK, INTERP ? 3 : 4) void features_kernel(DevScen
 FeatureKernel pick_wide_features_kernel() { return wide::features_kernel<true>; }
 #else
 
-namespace {
-thread_local std::string g_feature_error;
-}
-const char* feature_kernels_last_error() { return g_feature_error.c_str(); }
-
 int launch_features(const DevScene& scene, const FeatureLaunch& launch, void* stream, int num_cus, bool wide_vm) {
-    if (scene.stack_depth > kMaxStackDepth) {
-        g_feature_error = "BVH deeper than kMaxStackDepth";
-        return PYR_ERR_UNSUPPORTED;
-    }
+    if (scene.stack_depth > kMaxStackDepth) return fail(PYR_ERR_UNSUPPORTED, "BVH deeper than kMaxStackDepth");
     FeatureLaunch sized = launch;
 #ifdef PYR_FEATURES_ROW_MAJOR
     const uint64_t items = (uint64_t)launch.film.width * launch.film.height;
@@ -217,10 +211,7 @@ int launch_features(const DevScene& scene, const FeatureLaunch& launch, void* st
     sized.squares_x = (launch.film.width + 7u) / 8u;
     const uint64_t items = (uint64_t)sized.squares_x * ((launch.film.height + 7u) / 8u) * 64u;
 #endif
-    if (items >= 0xFFFFFFFFull) {
-        g_feature_error = "film: 2^32 pixels or more (counted in 8 x 8 squares)";
-        return PYR_ERR_INVALID_ARGUMENT;
-    }
+    if (items >= 0xFFFFFFFFull) return fail(PYR_ERR_INVALID_ARGUMENT, "film: 2^32 pixels or more (counted in 8 x 8 squares)");
     if (items == 0) return PYR_OK;
     sized.n = (uint32_t)items;
     // traversal stack levels in LDS: at most 16 (16 KB a workgroup, eight workgroups a CU), the rest in the lane's scratch
@@ -228,10 +219,7 @@ int launch_features(const DevScene& scene, const FeatureLaunch& launch, void* st
     const size_t lds = (size_t)sized.stack_lds * BLOCK * sizeof(int);
     FeatureKernel kernel = wide_vm ? pick_wide_features_kernel() : (scene.needs_interpreter != 0 ? features_kernel<true> : features_kernel<false>);
     hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (err != hipSuccess) {
-        g_feature_error = std::string("hipFuncSetAttribute: ") + hipGetErrorString(err);
-        return PYR_ERR_DEVICE;
-    }
+    if (err != hipSuccess) return fail(PYR_ERR_DEVICE, std::string("hipFuncSetAttribute: ") + hipGetErrorString(err));
     // persistent grid: the workgroups the registers and the LDS stack let a CU hold (no co-residency is required)
     hipFuncAttributes attr{};
     int blocks_per_cu = 4;
@@ -243,10 +231,7 @@ int launch_features(const DevScene& scene, const FeatureLaunch& launch, void* st
     sized.reserve = std::max<uint32_t>(64, std::min<uint32_t>(1024, (sized.n / std::max<uint32_t>(waves * 4, 1)) & ~63u));
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), lds, (hipStream_t)stream, scene, sized);
     err = hipGetLastError();
-    if (err != hipSuccess) {
-        g_feature_error = std::string("feature kernel launch: ") + hipGetErrorString(err);
-        return PYR_ERR_DEVICE;
-    }
+    if (err != hipSuccess) return fail(PYR_ERR_DEVICE, std::string("feature kernel launch: ") + hipGetErrorString(err));
     return PYR_OK;
 }
 #endif

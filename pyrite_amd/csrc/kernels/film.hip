@@ -5,18 +5,17 @@
 #include <algorithm>
 #include <string>
 
+#include "../api_internal.h"
 #include "../device_scene.h"
 
 namespace pyr {
 
 namespace {
-thread_local std::string g_film_error;
 constexpr uint32_t WAVE = 64;
 constexpr uint32_t NOISE_BLOCK = 256;
 
 __device__ __forceinline__ float develop_grain(float acc, float weight) { return weight > 0.0f ? acc / weight : 0.0f; } // Grain::develop, film.rs:132-143
 } // namespace
-const char* film_kernels_last_error() { return g_film_error.c_str(); }
 
 // ------------------------------------------------------------------------------------------------ film development, wave per pixel run
 // The film is pixel-major, `bins` grains of 8 B per pixel. A workgroup is ONE wave and takes runs of 64 consecutive pixels:
@@ -137,18 +136,12 @@ bool develop_wave_serves(const DevelopLaunch& launch) { return launch.film.bins 
 int launch_develop_wave(const DevelopLaunch& launch, void* stream) {
     const size_t pixels = (size_t)launch.film.width * launch.film.height;
     if (pixels == 0) return PYR_OK;
-    if (!develop_wave_serves(launch)) {
-        g_film_error = "develop_wave_kernel: more bins than its LDS rows hold";
-        return PYR_ERR_UNSUPPORTED;
-    }
+    if (!develop_wave_serves(launch)) return fail(PYR_ERR_UNSUPPORTED, "develop_wave_kernel: more bins than its LDS rows hold");
     const size_t lds = (size_t)WAVE * (launch.film.bins + 1u) * sizeof(float);
     const uint32_t grid = (uint32_t)std::min<size_t>((pixels + WAVE - 1) / WAVE, 256 * 32);
     hipLaunchKernelGGL(develop_wave_kernel, dim3(grid), dim3(WAVE), lds, (hipStream_t)stream, launch);
     hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        g_film_error = std::string("develop kernel launch: ") + hipGetErrorString(err);
-        return PYR_ERR_DEVICE;
-    }
+    if (err != hipSuccess) return fail(PYR_ERR_DEVICE, std::string("develop kernel launch: ") + hipGetErrorString(err));
     return PYR_OK;
 }
 
@@ -167,10 +160,7 @@ int launch_film_sum(const PyrGrain* a, const PyrGrain* b, PyrGrain* out, size_t 
     hipLaunchKernelGGL(film_sum_kernel, dim3(grid), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<const float2*>(a), reinterpret_cast<const float2*>(b),
                        reinterpret_cast<float2*>(out), grains);
     hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        g_film_error = std::string("film sum kernel launch: ") + hipGetErrorString(err);
-        return PYR_ERR_DEVICE;
-    }
+    if (err != hipSuccess) return fail(PYR_ERR_DEVICE, std::string("film sum kernel launch: ") + hipGetErrorString(err));
     return PYR_OK;
 }
 
@@ -221,10 +211,7 @@ int launch_noise(const NoiseLaunch& launch, void* stream) {
     if (tiles == 0) return PYR_OK;
     hipLaunchKernelGGL(noise_kernel, dim3(tiles), dim3(NOISE_BLOCK), 0, (hipStream_t)stream, launch);
     hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        g_film_error = std::string("noise kernel launch: ") + hipGetErrorString(err);
-        return PYR_ERR_DEVICE;
-    }
+    if (err != hipSuccess) return fail(PYR_ERR_DEVICE, std::string("noise kernel launch: ") + hipGetErrorString(err));
     return PYR_OK;
 }
 

@@ -1,12 +1,9 @@
 // main.hip -- the unit of every kernel but the interpreter builds of render_kernel_sm, and of every launcher.
 #include "../kernels.hip"
 
-namespace pyr {
+#include "../api_internal.h"
 
-namespace {
-thread_local std::string g_kernel_error;
-}
-const char* kernels_last_error() { return g_kernel_error.c_str(); }
+namespace pyr {
 
 // ------------------------------------------------------------------------------------------------ film development
 // main.rs:315-327: every pixel spectrum -> spectrum_to_xyz (main.rs:352-418, trapezoid rule against the CIE observer
@@ -88,10 +85,7 @@ int launch_develop(const DevelopLaunch& launch, void* stream) {
     uint32_t grid = (uint32_t)std::min<size_t>((pixels + BLOCK - 1) / BLOCK, 256 * 16);
     hipLaunchKernelGGL(develop_kernel, dim3(grid), dim3(BLOCK), 0, (hipStream_t)stream, launch);
     hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        g_kernel_error = std::string("develop kernel launch: ") + hipGetErrorString(err);
-        return PYR_ERR_DEVICE;
-    }
+    if (err != hipSuccess) return fail(PYR_ERR_DEVICE, std::string("develop kernel launch: ") + hipGetErrorString(err));
     return PYR_OK;
 }
 
@@ -160,10 +154,7 @@ int launch_assemble(const AssembleLaunch& launch, void* stream) {
     hipLaunchKernelGGL(assemble_interior_kernel, dim3(grid_i), dim3(BLOCK), 0, (hipStream_t)stream, launch);
     hipLaunchKernelGGL(assemble_ring_kernel, dim3(grid_r), dim3(BLOCK), 0, (hipStream_t)stream, launch);
     hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        g_kernel_error = std::string("assemble kernel launch: ") + hipGetErrorString(err);
-        return PYR_ERR_DEVICE;
-    }
+    if (err != hipSuccess) return fail(PYR_ERR_DEVICE, std::string("assemble kernel launch: ") + hipGetErrorString(err));
     return PYR_OK;
 }
 
@@ -198,13 +189,16 @@ constexpr uint32_t kTapeProgramsLds = 128; // prepared programs kept in LDS for 
 static uint32_t tape_programs_in_lds(const DevScene& scene) { return scene.num_programs <= kTapeProgramsLds ? scene.num_programs : 0u; }
 // Interpreter scenes record a tape when their colour programs allow it (DevScene::hit_tape) and there are wavelengths to share a
 // hit's work among: with one or two per sample the online form wins (diamonds.lua, one wavelength, 256 bounces: 538 against 486).
-bool uses_hit_tape(const DevScene& scene, const RenderLaunch& launch) {
+static bool uses_hit_tape(const DevScene& scene, const RenderLaunch& launch) {
     static const char* const least = std::getenv("PYRITE_HIT_TAPE_WAVELENGTHS"); // development: the fewest wavelengths per sample a hit tape is recorded for
     return scene.needs_interpreter != 0 && scene.hit_tape != 0 && launch.spectrum_samples >= (least && *least ? (uint32_t)std::strtoul(least, nullptr, 10) : 4u);
 }
-static bool uses_tape(const DevScene& scene, const RenderLaunch& launch) {
-    return launch.scheduler == 1 && (scene.needs_interpreter == 0 || uses_hit_tape(scene, launch));
+// The tape a launch records, as PyrPathInfo::tape counts: 0 none, 1 the spectral tape of a scene without interpreter programs, 2 a hit tape.
+uint32_t launch_tape(const DevScene& scene, const RenderLaunch& launch) {
+    if (launch.scheduler != 1) return 0u;
+    return scene.needs_interpreter == 0 ? 1u : uses_hit_tape(scene, launch) ? 2u : 0u;
 }
+static bool uses_tape(const DevScene& scene, const RenderLaunch& launch) { return launch_tape(scene, launch) != 0u; }
 static size_t render_lds_bytes(const DevScene& scene, const RenderLaunch& launch) {
     const size_t spectral_rows = uses_tape(scene, launch) ? launch.spectrum_samples + 1 + scene.tape_value_rows : 3 * launch.spectrum_samples;
     size_t bytes = (spectral_rows + launch.stack_lds) * BLOCK * sizeof(float);
@@ -232,14 +226,9 @@ static RenderKernel pick_kernel(bool sm, bool with_counters, bool interp, bool l
 bool scene_is_lds_resident(const DevScene& scene) { return scene_fits_lds(scene); }
 
 int launch_render(const DevScene& scene, const RenderLaunch& launch_in, bool with_counters, void* stream, int num_cus, bool wide_vm) {
-    if (scene.stack_depth > kMaxStackDepth) {
-        g_kernel_error = "BVH deeper than kMaxStackDepth";
-        return PYR_ERR_UNSUPPORTED;
-    }
-    if (wide_vm && (launch_in.scheduler != 1 || scene.needs_interpreter == 0 || uses_tape(scene, launch_in))) {
-        g_kernel_error = "the wide interpreter build runs the stage scheduler's online form only";
-        return PYR_ERR_INVALID_ARGUMENT;
-    }
+    if (scene.stack_depth > kMaxStackDepth) return fail(PYR_ERR_UNSUPPORTED, "BVH deeper than kMaxStackDepth");
+    if (wide_vm && (launch_in.scheduler != 1 || scene.needs_interpreter == 0 || uses_tape(scene, launch_in)))
+        return fail(PYR_ERR_INVALID_ARGUMENT, "the wide interpreter build runs the stage scheduler's online form only");
     RenderLaunch launch = launch_in;
     launch.stack_lds = 0;
     launch.tape_programs_lds = uses_tape(scene, launch) ? tape_programs_in_lds(scene) : 0u;
@@ -249,23 +238,14 @@ int launch_render(const DevScene& scene, const RenderLaunch& launch_in, bool wit
     // scratch part: TravStack::deep is one entry), whatever the budget or PYRITE_LDS_STACK say; the 160 KB check below applies
     if (scene_fits_lds(scene)) launch.stack_lds = std::max(launch.stack_lds, scene.stack_depth);
     const size_t lds = render_lds_bytes(scene, launch);
-    if (lds > 160 * 1024) {
-        g_kernel_error = "spectrum_samples + BVH depth need more than 160 KB of LDS per workgroup";
-        return PYR_ERR_UNSUPPORTED;
-    }
+    if (lds > 160 * 1024) return fail(PYR_ERR_UNSUPPORTED, "spectrum_samples + BVH depth need more than 160 KB of LDS per workgroup");
     const uint32_t chunks = launch.chunk_end - launch.chunk_begin;
     if (chunks == 0) return PYR_OK;
     RenderKernel kernel = pick_kernel(launch.scheduler == 1, with_counters, scene.needs_interpreter != 0, scene_fits_lds(scene), scene.lds_table_floats != 0,
                                       launch.scheduler == 1 && uses_hit_tape(scene, launch), scene.product_records != 0, wide_vm);
-    if (kernel == nullptr) {
-        g_kernel_error = "a program of this scene needs the wide interpreter build, which this one-unit build of the kernels does not hold";
-        return PYR_ERR_UNSUPPORTED;
-    }
+    if (kernel == nullptr) return fail(PYR_ERR_UNSUPPORTED, "a program of this scene needs the wide interpreter build, which this one-unit build of the kernels does not hold");
     hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (err != hipSuccess) {
-        g_kernel_error = std::string("hipFuncSetAttribute: ") + hipGetErrorString(err);
-        return PYR_ERR_DEVICE;
-    }
+    if (err != hipSuccess) return fail(PYR_ERR_DEVICE, std::string("hipFuncSetAttribute: ") + hipGetErrorString(err));
     // Residency of a 256-thread block (one wave per SIMD): waves per SIMD allowed by the 512-entry register file
     // (8-register granules, MI355X_MICROARCH.md "Register files") and by the 160 KB of LDS. The grid is persistent but needs
     // no co-residency (no inter-block hand-off), so an over-estimate only queues blocks.
@@ -280,40 +260,27 @@ int launch_render(const DevScene& scene, const RenderLaunch& launch_in, bool wit
     const uint32_t path_waves = BLOCK / 64; // waves of a workgroup that take chunks
     uint32_t blocks_needed = (chunks + path_waves - 1) / path_waves;
     if (grid > blocks_needed) grid = blocks_needed;
-    if (uses_tape(scene, launch) && (launch.tape == nullptr || (size_t)grid * BLOCK > launch.tape_lanes || launch.tape_max_ops < tape_ops_bound(scene, launch))) {
-        g_kernel_error = "the spectral tape is missing or too small for this launch";
-        return PYR_ERR_INVALID_ARGUMENT;
-    }
+    if (uses_tape(scene, launch) && (launch.tape == nullptr || (size_t)grid * BLOCK > launch.tape_lanes || launch.tape_max_ops < tape_ops_bound(scene, launch)))
+        return fail(PYR_ERR_INVALID_ARGUMENT, "the spectral tape is missing or too small for this launch");
     if (PYR_SAMPLE_QUEUE != 0 && uses_tape(scene, launch) && scene.needs_interpreter == 0 &&
-        (launch.start_queue == nullptr || launch.start_queue_stride < start_queue_words(launch.spectrum_samples) * kStartQueueEntries)) {
-        g_kernel_error = "the queue of ready sample starts is missing or too small for this launch"; // one slab per wave the tape has columns for: checked above
-        return PYR_ERR_INVALID_ARGUMENT;
-    }
+        (launch.start_queue == nullptr || launch.start_queue_stride < start_queue_words(launch.spectrum_samples) * kStartQueueEntries))
+        return fail(PYR_ERR_INVALID_ARGUMENT, "the queue of ready sample starts is missing or too small for this launch"); // one slab per wave the tape has columns for: checked above
     if (const char* cut = std::getenv("PYRITE_TEST_TAPE_OPS")) // test switch: pretend the bound were smaller, to see the overflow word work
         if (uses_tape(scene, launch) && *cut) launch.tape_max_ops = std::min<uint32_t>(launch.tape_max_ops, (uint32_t)std::strtoul(cut, nullptr, 10));
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), lds, (hipStream_t)stream, scene, launch);
     err = hipGetLastError();
-    if (err != hipSuccess) {
-        g_kernel_error = std::string("render kernel launch: ") + hipGetErrorString(err);
-        return PYR_ERR_DEVICE;
-    }
+    if (err != hipSuccess) return fail(PYR_ERR_DEVICE, std::string("render kernel launch: ") + hipGetErrorString(err));
     return PYR_OK;
 }
 
 int launch_intersect(const DevScene& scene, const IntersectLaunch& launch, bool with_counters, void* stream) {
     if (launch.n == 0) return PYR_OK;
-    if (scene.stack_depth > kMaxStackDepth) {
-        g_kernel_error = "BVH deeper than kMaxStackDepth";
-        return PYR_ERR_UNSUPPORTED;
-    }
+    if (scene.stack_depth > kMaxStackDepth) return fail(PYR_ERR_UNSUPPORTED, "BVH deeper than kMaxStackDepth");
     const uint32_t stack_lds = short_stack_levels(scene, 0, 8);
     const size_t lds = (size_t)stack_lds * BLOCK * sizeof(int);
     auto kernel = with_counters ? intersect_kernel<true> : intersect_kernel<false>;
     hipError_t err = hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (err != hipSuccess) {
-        g_kernel_error = std::string("hipFuncSetAttribute: ") + hipGetErrorString(err);
-        return PYR_ERR_DEVICE;
-    }
+    if (err != hipSuccess) return fail(PYR_ERR_DEVICE, std::string("hipFuncSetAttribute: ") + hipGetErrorString(err));
     // persistent grid: as many workgroups as the registers and the LDS stack let a CU hold (no co-residency is required)
     int blocks_per_cu = std::max(1, std::min<int>(8, (int)((160 * 1024) / std::max<size_t>(lds, 1))));
     uint32_t grid = (uint32_t)launch.num_cus * (uint32_t)blocks_per_cu;
@@ -326,10 +293,7 @@ int launch_intersect(const DevScene& scene, const IntersectLaunch& launch, bool 
     sized.reserve = std::max<uint32_t>(64, std::min<uint32_t>(2048, (launch.n / std::max<uint32_t>(waves * 4, 1)) & ~63u));
     hipLaunchKernelGGL(kernel, dim3(grid), dim3(BLOCK), lds, (hipStream_t)stream, scene, sized);
     err = hipGetLastError();
-    if (err != hipSuccess) {
-        g_kernel_error = std::string("intersect kernel launch: ") + hipGetErrorString(err);
-        return PYR_ERR_DEVICE;
-    }
+    if (err != hipSuccess) return fail(PYR_ERR_DEVICE, std::string("intersect kernel launch: ") + hipGetErrorString(err));
     return PYR_OK;
 }
 

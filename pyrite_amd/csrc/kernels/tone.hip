@@ -6,12 +6,12 @@
 #include <algorithm>
 #include <string>
 
+#include "../api_internal.h"
 #include "../device_scene.h"
 
 namespace pyr {
 
 namespace {
-thread_local std::string g_tone_error;
 constexpr uint32_t WAVE = 64;
 constexpr uint32_t PIXEL_BLOCK = 256;
 constexpr uint32_t STATS_BLOCK = 256;
@@ -83,7 +83,6 @@ __device__ __forceinline__ uint8_t encode_srgb(float v) {
 
 __device__ __forceinline__ float luminance(float r, float g, float b) { return (0.2126f * r + 0.7152f * g) + 0.0722f * b; }
 } // namespace
-const char* tone_kernels_last_error() { return g_tone_error.c_str(); }
 
 // ------------------------------------------------------------------------------------------------ linear development, wave per pixel run
 // develop_wave_kernel's shape (kernels/film.hip): a workgroup is ONE wave and takes runs of 64 consecutive pixels, the run's grains
@@ -188,10 +187,7 @@ int launch_develop_linear(const LinearLaunch& launch, void* stream) {
         hipLaunchKernelGGL(develop_linear_pixel_kernel, dim3(grid), dim3(PIXEL_BLOCK), 0, (hipStream_t)stream, launch);
     }
     hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        g_tone_error = std::string("linear develop kernel launch: ") + hipGetErrorString(err);
-        return PYR_ERR_DEVICE;
-    }
+    if (err != hipSuccess) return fail(PYR_ERR_DEVICE, std::string("linear develop kernel launch: ") + hipGetErrorString(err));
     return PYR_OK;
 }
 
@@ -268,10 +264,7 @@ int launch_image_stats(const float* image, size_t pixels, PyrImageStats* out, vo
         hipLaunchKernelGGL(image_stats_finish_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, out);
         err = hipGetLastError();
     }
-    if (err != hipSuccess) {
-        g_tone_error = std::string("image stats kernel launch: ") + hipGetErrorString(err);
-        return PYR_ERR_DEVICE;
-    }
+    if (err != hipSuccess) return fail(PYR_ERR_DEVICE, std::string("image stats kernel launch: ") + hipGetErrorString(err));
     return PYR_OK;
 }
 
@@ -322,10 +315,7 @@ int launch_tonemap(const ToneLaunch& launch, void* stream) {
     const uint32_t grid = (uint32_t)std::min<size_t>((launch.pixels + 4 * TONE_BLOCK - 1) / (4 * TONE_BLOCK), 256 * 16);
     hipLaunchKernelGGL(tonemap_kernel, dim3(grid), dim3(TONE_BLOCK), 0, (hipStream_t)stream, launch);
     hipError_t err = hipGetLastError();
-    if (err != hipSuccess) {
-        g_tone_error = std::string("tonemap kernel launch: ") + hipGetErrorString(err);
-        return PYR_ERR_DEVICE;
-    }
+    if (err != hipSuccess) return fail(PYR_ERR_DEVICE, std::string("tonemap kernel launch: ") + hipGetErrorString(err));
     return PYR_OK;
 }
 

@@ -57,12 +57,6 @@ using namespace pyr;
 
 namespace {
 
-#define HIP_TRY(expr)                                                                                      \
-    do {                                                                                                   \
-        hipError_t e_ = (expr);                                                                            \
-        if (e_ != hipSuccess) return api_fail(PYR_ERR_DEVICE, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 struct Rccl {
     void* handle = nullptr;
     ncclResult_t (*GetUniqueId)(ncclUniqueId*) = nullptr;
@@ -124,7 +118,7 @@ Rccl* rccl() {
 
 int rccl_ready(Rccl*& out) {
     out = rccl();
-    if (!out->error.empty()) return api_fail(PYR_ERR_DEVICE, out->error);
+    if (!out->error.empty()) return fail(PYR_ERR_DEVICE, out->error);
     return PYR_OK;
 }
 
@@ -215,22 +209,22 @@ extern "C" {
 
 int pyr_comm_unique_id(uint8_t id_out[PYR_COMM_ID_BYTES]) {
     static_assert(PYR_COMM_ID_BYTES == NCCL_UNIQUE_ID_BYTES, "id size");
-    if (!id_out) return api_fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+    if (!id_out) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
     Rccl* lib;
     int rc = rccl_ready(lib);
     if (rc != PYR_OK) return rc;
     ncclUniqueId id;
     ncclResult_t r = lib->GetUniqueId(&id);
-    if (r != ncclSuccess) return api_fail(PYR_ERR_DEVICE, nccl_message(lib, "ncclGetUniqueId", r));
+    if (r != ncclSuccess) return fail(PYR_ERR_DEVICE, nccl_message(lib, "ncclGetUniqueId", r));
     std::memcpy(id_out, id.internal, PYR_COMM_ID_BYTES);
     return PYR_OK;
 }
 
 int pyr_comm_create(const uint8_t id_in[PYR_COMM_ID_BYTES], int rank, int num_ranks, int device, PyrComm** out_comm) {
-    if (!out_comm) return api_fail(PYR_ERR_INVALID_ARGUMENT, "null out pointer");
+    if (!out_comm) return fail(PYR_ERR_INVALID_ARGUMENT, "null out pointer");
     *out_comm = nullptr;
-    if (num_ranks < 1 || rank < 0 || rank >= num_ranks) return api_fail(PYR_ERR_INVALID_ARGUMENT, "rank out of range");
-    if (device < 0 || device >= pyr_device_count()) return api_fail(PYR_ERR_DEVICE, "no such HIP device; pyrite_gpu has no CPU path");
+    if (num_ranks < 1 || rank < 0 || rank >= num_ranks) return fail(PYR_ERR_INVALID_ARGUMENT, "rank out of range");
+    if (device < 0 || device >= pyr_device_count()) return fail(PYR_ERR_DEVICE, "no such HIP device; pyrite_gpu has no CPU path");
     HIP_TRY(hipSetDevice(device));
     // A world of one needs no communicator -- unless PYRITE_FORCE_RCCL=1 asks for a real one-rank RCCL communicator: the
     // rank's blocks then travel through a grouped self ncclSend / ncclRecv (and the agreement through ncclAllReduce), i.e. the
@@ -242,7 +236,7 @@ int pyr_comm_create(const uint8_t id_in[PYR_COMM_ID_BYTES], int rank, int num_ra
     if (real) {
         if (!id_in) {
             delete c;
-            return api_fail(PYR_ERR_INVALID_ARGUMENT, "null communicator id");
+            return fail(PYR_ERR_INVALID_ARGUMENT, "null communicator id");
         }
         Rccl* lib;
         int rc = rccl_ready(lib);
@@ -255,7 +249,7 @@ int pyr_comm_create(const uint8_t id_in[PYR_COMM_ID_BYTES], int rank, int num_ra
         ncclResult_t r = lib->CommInitRank(&c->comm, num_ranks, id, rank);
         if (r != ncclSuccess) {
             delete c;
-            return api_fail(PYR_ERR_DEVICE, nccl_message(lib, "ncclCommInitRank", r));
+            return fail(PYR_ERR_DEVICE, nccl_message(lib, "ncclCommInitRank", r));
         }
     }
     *out_comm = c;
@@ -273,25 +267,25 @@ void pyr_comm_destroy(PyrComm* comm) {
 int pyr_comm_uses_rccl(const PyrComm* comm) { return comm && comm->comm != nullptr ? 1 : 0; }
 
 int pyr_comm_status(PyrComm* comm) {
-    if (!comm) return api_fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
-    if (comm->dead) return api_fail(PYR_ERR_DEVICE, "the communicator was aborted after an error inside a collective");
+    if (!comm) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+    if (comm->dead) return fail(PYR_ERR_DEVICE, "the communicator was aborted after an error inside a collective");
     if (!comm->pending || !comm->host_words) return PYR_OK;
     comm->pending = false;
     for (int r = 0; r < comm->num_ranks; ++r) {
         const uint32_t word = comm->host_words[2 + r];
         if (word == 0) continue;
         const std::string who = "rank " + std::to_string(r);
-        if (word == kTrailerLaunchFailed) return api_fail(PYR_ERR_DEVICE, who + " could not launch its render: the gathered film is invalid");
-        if (word == 2) return api_fail(PYR_ERR_DEVICE, who + ": a wave gave up waiting on its workgroup's LDS queues: the gathered film is invalid");
-        return api_fail(PYR_ERR_DEVICE, who + ": a path appended more records than the spectral tape's bound allows: the gathered film is invalid");
+        if (word == kTrailerLaunchFailed) return fail(PYR_ERR_DEVICE, who + " could not launch its render: the gathered film is invalid");
+        if (word == 2) return fail(PYR_ERR_DEVICE, who + ": a wave gave up waiting on its workgroup's LDS queues: the gathered film is invalid");
+        return fail(PYR_ERR_DEVICE, who + ": a path appended more records than the spectral tape's bound allows: the gathered film is invalid");
     }
     return PYR_OK;
 }
 
 int pyr_render_simple_sharded(PyrComm* comm, PyrScene* scene, const PyrCamera* camera, const PyrFilmDesc* film, const PyrRenderParams* params,
                               PyrGrain* film_device_rank0, void* hip_stream) {
-    if (!comm) return api_fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
-    if (comm->dead) return api_fail(PYR_ERR_DEVICE, "the communicator was aborted after an error inside a collective");
+    if (!comm) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+    if (comm->dead) return fail(PYR_ERR_DEVICE, "the communicator was aborted after an error inside a collective");
     HIP_TRY(hipSetDevice(comm->device));
     hipStream_t stream = (hipStream_t)hip_stream;
     const uint32_t n = (uint32_t)comm->num_ranks, me = (uint32_t)comm->rank;
@@ -307,18 +301,18 @@ int pyr_render_simple_sharded(PyrComm* comm, PyrScene* scene, const PyrCamera* c
         int rc = comm->host_reserve();
         if (rc != PYR_OK) return rc;
         if (travels && (rc = comm->agree.reserve(2 * sizeof(uint32_t), stream)) != PYR_OK) return rc;
-        if (!scene || !camera || !film || !params) return api_fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
-        if (me == 0 && !film_device_rank0) return api_fail(PYR_ERR_INVALID_ARGUMENT, "rank 0 needs the film");
-        if (scene_device(scene) != comm->device) return api_fail(PYR_ERR_INVALID_ARGUMENT, "the scene lives on another device than the communicator");
+        if (!scene || !camera || !film || !params) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+        if (me == 0 && !film_device_rank0) return fail(PYR_ERR_INVALID_ARGUMENT, "rank 0 needs the film");
+        if (scene_device(scene) != comm->device) return fail(PYR_ERR_INVALID_ARGUMENT, "the scene lives on another device than the communicator");
         if (params->film_layout != PYR_FILM_ROWS || params->film_row_begin || params->film_row_count)
-            return api_fail(PYR_ERR_INVALID_ARGUMENT, "a sharded render adds into the whole-image film on rank 0");
-        if (params->tile_size == 0 || film->width == 0 || film->height == 0 || film->bins == 0) return api_fail(PYR_ERR_INVALID_ARGUMENT, "zero-sized parameter");
+            return fail(PYR_ERR_INVALID_ARGUMENT, "a sharded render adds into the whole-image film on rank 0");
+        if (params->tile_size == 0 || film->width == 0 || film->height == 0 || film->bins == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "zero-sized parameter");
         for (uint32_t r = 0; r < n; ++r) {
             share[r] = rank_share(film, params, r, n);
             grains[r] = share[r].tile_begin < share[r].tile_end ? pyr_film_blocks_grains(film, &share[r]) : 0;
             if (share[r].tile_begin < share[r].tile_end && grains[r] == 0) return PYR_ERR_INVALID_ARGUMENT; // message set by the callee
         }
-        if (test_switch_names("PYRITE_TEST_FAIL_RANK", (int)me)) return api_fail(PYR_ERR_DEVICE, "test switch: this rank's buffers could not be grown");
+        if (test_switch_names("PYRITE_TEST_FAIL_RANK", (int)me)) return fail(PYR_ERR_DEVICE, "test switch: this rank's buffers could not be grown");
         if (grains[me] && (rc = comm->window.reserve((grains[me] + 1) * sizeof(PyrGrain), stream)) != PYR_OK) return rc;
         if (travels && me == 0) {
             uint64_t incoming = 0;
@@ -334,7 +328,7 @@ int pyr_render_simple_sharded(PyrComm* comm, PyrScene* scene, const PyrCamera* c
     if (travels) {
         if (!comm->agree.ptr || !comm->host_words) { // not even the status word could be set up: peers cannot be told
             comm->abort_comm();
-            return api_fail(local != PYR_OK ? local : PYR_ERR_DEVICE, local_message.empty() ? "no memory for the status exchange" : local_message);
+            return fail(local != PYR_OK ? local : PYR_ERR_DEVICE, local_message.empty() ? "no memory for the status exchange" : local_message);
         }
         uint32_t* words = (uint32_t*)comm->agree.ptr;
         comm->host_words[0] = 1u;
@@ -346,14 +340,14 @@ int pyr_render_simple_sharded(PyrComm* comm, PyrScene* scene, const PyrCamera* c
         ok = ok && hipStreamSynchronize(stream) == hipSuccess;
         if (!ok) {
             comm->abort_comm();
-            return api_fail(PYR_ERR_DEVICE, r != ncclSuccess ? nccl_message(lib, "ncclAllReduce (status agreement)", r) : std::string("the status agreement failed on the device"));
+            return fail(PYR_ERR_DEVICE, r != ncclSuccess ? nccl_message(lib, "ncclAllReduce (status agreement)", r) : std::string("the status agreement failed on the device"));
         }
         if (comm->host_words[0] != 0u) {
-            if (local != PYR_OK) return api_fail(local, local_message);
-            return api_fail(PYR_ERR_DEVICE, "another rank failed before the gather; nothing was rendered");
+            if (local != PYR_OK) return fail(local, local_message);
+            return fail(PYR_ERR_DEVICE, "another rank failed before the gather; nothing was rendered");
         }
     } else if (local != PYR_OK) {
-        return api_fail(local, local_message);
+        return fail(local, local_message);
     }
 
     // ---- 3. the render; its outcome goes into the trailer grain behind the blocks
@@ -408,7 +402,7 @@ int pyr_render_simple_sharded(PyrComm* comm, PyrScene* scene, const PyrCamera* c
         }
         if (first != ncclSuccess) {
             comm->abort_comm();
-            return api_fail(PYR_ERR_DEVICE, nccl_message(lib, where, first));
+            return fail(PYR_ERR_DEVICE, nccl_message(lib, where, first));
         }
     }
 
@@ -433,14 +427,14 @@ int pyr_render_simple_sharded(PyrComm* comm, PyrScene* scene, const PyrCamera* c
 
 int pyr_render_simple_multi(PyrScene* const* scenes, uint32_t num_devices, const PyrCamera* camera, const PyrFilmDesc* film, const PyrRenderParams* params,
                             PyrGrain* film_inout, PyrProgressFn on_status, void* user) {
-    if (!scenes || num_devices == 0 || !camera || !film || !params || !film_inout) return api_fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+    if (!scenes || num_devices == 0 || !camera || !film || !params || !film_inout) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
     if (params->film_layout != PYR_FILM_ROWS || params->film_row_begin || params->film_row_count)
-        return api_fail(PYR_ERR_INVALID_ARGUMENT, "a multi-device render adds into a whole-image film");
-    if (params->tile_size == 0 || film->width == 0 || film->height == 0 || film->bins == 0) return api_fail(PYR_ERR_INVALID_ARGUMENT, "zero-sized parameter");
+        return fail(PYR_ERR_INVALID_ARGUMENT, "a multi-device render adds into a whole-image film");
+    if (params->tile_size == 0 || film->width == 0 || film->height == 0 || film->bins == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "zero-sized parameter");
     std::vector<int> devices(num_devices);
     bool distinct = true;
     for (uint32_t i = 0; i < num_devices; ++i) {
-        if (!scenes[i]) return api_fail(PYR_ERR_INVALID_ARGUMENT, "null scene");
+        if (!scenes[i]) return fail(PYR_ERR_INVALID_ARGUMENT, "null scene");
         devices[i] = scene_device(scenes[i]);
         for (uint32_t j = 0; j < i; ++j) distinct = distinct && devices[j] != devices[i];
     }
@@ -470,7 +464,7 @@ int pyr_render_simple_multi(PyrScene* const* scenes, uint32_t num_devices, const
         if (it == cache.end()) {
             std::vector<ncclComm_t> made(num_devices);
             ncclResult_t r = lib->CommInitAll(made.data(), (int)num_devices, devices.data());
-            if (r != ncclSuccess) return api_fail(PYR_ERR_DEVICE, nccl_message(lib, "ncclCommInitAll", r));
+            if (r != ncclSuccess) return fail(PYR_ERR_DEVICE, nccl_message(lib, "ncclCommInitAll", r));
             it = cache.emplace(devices, made).first;
         }
         for (uint32_t i = 0; i < num_devices; ++i) comms[i].comm = it->second[i];
@@ -548,27 +542,27 @@ int pyr_render_simple_multi(PyrScene* const* scenes, uint32_t num_devices, const
             const uint64_t grains = pyr_film_blocks_grains(film, &mine);
             int rc = PYR_OK;
             if (hipSetDevice(devices[i]) != hipSuccess || (i > 0 && hipStreamCreateWithFlags(&streams[i], hipStreamNonBlocking) != hipSuccess))
-                rc = api_fail(PYR_ERR_DEVICE, "hipStreamCreate failed");
+                rc = fail(PYR_ERR_DEVICE, "hipStreamCreate failed");
             hipStream_t s = streams[i];
             if (rc == PYR_OK) rc = comms[i].window.reserve(grains * sizeof(PyrGrain), s);
-            if (rc == PYR_OK && hipMemsetAsync(comms[i].window.ptr, 0, grains * sizeof(PyrGrain), s) != hipSuccess) rc = api_fail(PYR_ERR_DEVICE, "hipMemsetAsync failed");
+            if (rc == PYR_OK && hipMemsetAsync(comms[i].window.ptr, 0, grains * sizeof(PyrGrain), s) != hipSuccess) rc = fail(PYR_ERR_DEVICE, "hipMemsetAsync failed");
             if (rc == PYR_OK) rc = pyr_render_simple_device(scenes[i], camera, film, &mine, (PyrGrain*)comms[i].window.ptr, s);
-            if (rc == PYR_OK && hipStreamSynchronize(s) != hipSuccess) rc = api_fail(PYR_ERR_DEVICE, "hipStreamSynchronize failed");
+            if (rc == PYR_OK && hipStreamSynchronize(s) != hipSuccess) rc = fail(PYR_ERR_DEVICE, "hipStreamSynchronize failed");
             if (rc == PYR_OK) rc = scene_check_overflow(scenes[i]); // the kernels' verdict on the film they just wrote
             if (rc == PYR_OK) {
                 (void)hipSetDevice(devices[0]);
                 rc = staged.reserve(grains * sizeof(PyrGrain), streams[0]);
                 if (rc == PYR_OK && hipMemcpyPeerAsync(staged.ptr, devices[0], comms[i].window.ptr, devices[i], grains * sizeof(PyrGrain), streams[0]) != hipSuccess)
-                    rc = api_fail(PYR_ERR_DEVICE, "hipMemcpyPeerAsync failed");
+                    rc = fail(PYR_ERR_DEVICE, "hipMemcpyPeerAsync failed");
                 if (rc == PYR_OK) rc = pyr_film_blocks_assemble_device(film, &mine, (const PyrGrain*)staged.ptr, film_dev, devices[0], streams[0]);
-                if (rc == PYR_OK && hipStreamSynchronize(streams[0]) != hipSuccess) rc = api_fail(PYR_ERR_DEVICE, "hipStreamSynchronize failed");
+                if (rc == PYR_OK && hipStreamSynchronize(streams[0]) != hipSuccess) rc = fail(PYR_ERR_DEVICE, "hipStreamSynchronize failed");
             }
             if (rc != PYR_OK) result = rc, result_message = pyr_last_error();
         }
         (void)hipSetDevice(devices[0]);
         staged.release();
     }
-    if (result != PYR_OK) return api_fail(result, result_message);
+    if (result != PYR_OK) return fail(result, result_message);
     HIP_TRY(hipSetDevice(devices[0]));
     HIP_TRY(hipMemcpy(film_inout, film_dev, film_bytes, hipMemcpyDeviceToHost));
     if (on_status) on_status(user, 100, message);

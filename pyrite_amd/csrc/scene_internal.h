@@ -1,5 +1,6 @@
-// scene_internal.h -- what api.cpp (creation, renders, sessions, images) and live_scene.cpp (everything that moves a scene after
-// creation) both see of a PyrScene. Declarations, but for the coordinate test: api.cpp defines what is not said to live elsewhere.
+// scene_internal.h -- what api.cpp (creation, renders, feature passes), live_scene.cpp (everything that moves a scene after
+// creation) and session.cpp (progressive sessions) all see of a PyrScene. Declarations, but for the coordinate test: api.cpp
+// defines what is not said to live elsewhere.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -15,27 +16,6 @@
 #include "kernels/pose_launch.h"
 
 namespace pyr {
-
-// Records the thread-local message pyr_last_error() returns and hands `code` back (api_fail is the same function under the
-// name the other units know).
-int fail(int code, const std::string& message);
-int hip_fail(hipError_t e, const char* what);
-
-#define HIP_TRY(expr)                                          \
-    do {                                                       \
-        hipError_t e_ = (expr);                                \
-        if (e_ != hipSuccess) return pyr::hip_fail(e_, #expr); \
-    } while (0)
-
-struct DeviceBuffer {
-    void* ptr = nullptr;
-    size_t bytes = 0;
-    ~DeviceBuffer() { release(); }
-    void release();
-    int upload(const void* src, size_t n); // (over an earlier allocation: that one is freed -- a rebuild uploads into the scene's buffers again)
-    int alloc(size_t n);
-    int reserve(size_t n); // holds `n` bytes afterwards: allocated once, kept while it is large enough
-};
 
 double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b);
 
@@ -53,6 +33,25 @@ inline bool within_coordinate_range(const PrimBounds& b) {
 // One DevLamp from the description, and the geometry part of scene creation (api.cpp): `d` needs its geometry fields and lamps.
 DevLamp pack_lamp(const PyrSceneDesc* d, uint32_t i);
 int pack_geometry(const PyrSceneDesc* d, PyrScene* s, uint32_t builder);
+
+// The render side, for the units that enqueue renders and feature passes of a scene (api.cpp defines it, session.cpp calls it).
+struct TilePlan {
+    uint32_t tiles_x = 0, tiles_y = 0;
+    uint32_t tile_begin = 0, tile_stride = 1, tile_count = 0;
+    uint32_t chunks_per_tile = 0;
+    uint32_t chunk_begin = 0, chunk_end = 0; // chunk numbers of the call's tiles (device_scene.h RenderLaunch)
+};
+int plan_tiles(const PyrFilmDesc* film, const PyrRenderParams* p, TilePlan& plan);
+int check_render_args(PyrScene* scene, const PyrCamera* camera, const PyrFilmDesc* film, const PyrRenderParams* p, const void* film_ptr);
+RenderLaunch make_launch(const PyrCamera* camera, const PyrFilmDesc* film, const PyrRenderParams* p, const TilePlan& plan);
+int render_batches(PyrScene* scene, RenderLaunch L, bool count, hipStream_t stream); // picks the schedule, reserves the tape, launches
+int check_tape_overflow(PyrScene* scene); // after a render has been waited for: PYR_ERR_DEVICE if a path outgrew the spectral tape
+// What the feature entries refuse before a device is looked for (`what` names the scene or session argument), and the pass
+// enqueued on `stream`: the buffers are on the scene's device, either may be null.
+int check_feature_args(const void* owner, const char* what, const PyrCamera* camera, bool need_camera, const PyrFilmDesc* film, const PyrFeatureParams* fp,
+                       const void* albedo, const void* pixels);
+int enqueue_features(PyrScene* scene, const PyrCamera* camera, const PyrFilmDesc* film, const PyrFeatureParams* fp, PyrGrain* albedo, PyrFeaturePixel* pixels,
+                     hipStream_t stream);
 
 struct LiveArray {       // one of the arrays that move, and its homes
     uint32_t width;      // floats per primitive

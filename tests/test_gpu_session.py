@@ -372,3 +372,34 @@ def test_command_line_writes_previews_and_the_same_final_image(gpu_lib, tmp_path
     assert read_png(preview).shape == (64, 96, 3)
     assert "noise" in out
     assert open(plain, "rb").read() == open(passes, "rb").read()
+
+
+LDS_REFUSAL = "spectrum_samples + BVH depth need more than 160 KB of LDS per workgroup"
+
+
+def test_a_launcher_refusal_reaches_both_callers_with_its_own_words(gpu_lib, monkeypatch):
+    """The one refusal of a launcher that a caller reaches without anything being launched: the synchronous walk of a scene that
+    lives in LDS keeps 3 * spectrum_samples rows of 1 KB next to its stack, so 64 wavelengths need more than a workgroup's
+    160 KB and launch_render says so. The code and the text arrive through pyr_render_simple and through a session's pass alike,
+    nothing is rendered, and the scene renders afterwards."""
+    monkeypatch.delenv("PYRITE_SCHEDULER", raising=False)
+    world, cam, r, film = scenes.build(scenes.c1_spheres(8, 8, 4), seed=5)
+    r.spectrum_samples = 64
+    info = r.path_info(world)
+    assert info["scene_in_lds"] == 1 and info["stage_scheduler"] == 0, info
+    refused = "pyrite_gpu error %d: %s" % (abi.PYR_ERR_UNSUPPORTED, LDS_REFUSAL)
+    with pytest.raises(PyriteGpuError) as e:
+        r.render(film, cam, world)
+    print("pyr_render_simple: %s" % e.value)
+    assert e.value.status == abi.PYR_ERR_UNSUPPORTED and str(e.value) == refused
+    assert film.total_weight() == 0
+    with r.session((8, 8), cam, world) as s:
+        with pytest.raises(PyriteGpuError) as e:
+            s.render(4)
+        print("pyr_session_render: %s" % e.value)
+        assert e.value.status == abi.PYR_ERR_UNSUPPORTED and str(e.value) == refused
+        assert s.samples_done == 0
+    r.spectrum_samples = 4
+    r.render(film, cam, world)
+    assert film.total_weight() > 0 and not np.isnan(film.grains).any()
+    world.close()
