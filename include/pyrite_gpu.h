@@ -565,6 +565,54 @@ typedef struct PyrPoseUpdate {
 int pyr_scene_pose(PyrScene*, const PyrPoseUpdate*, void* hip_stream);
 int pyr_scene_geometry(PyrScene*, float* tri_positions, float* tri_normals, float* tri_frames, float* spheres);
 
+/* ---- skinning a live scene's meshes. A pose moves an object as one rigid piece; a mesh that bends -- a figure on a skeleton, a
+ * cable, a flag -- has a matrix per VERTEX, blended from a few joint matrices by weights that never change (linear blend skinning).
+ * pyr_scene_set_skins takes those bindings once, 72 bytes per skinned triangle; pyr_scene_skin takes one small table of joint
+ * matrices per frame (and, if wanted, the objects' poses), computes every triangle from the rest pose on the device and runs the
+ * refit or the rebuild of pyr_scene_pose from there.
+ *   A skin belongs to one object of pyr_scene_set_objects and covers all of that object's triangles, in their order; the object's
+ * spheres are not skinned. For every vertex it names four joints j0..j3 (relative to the skin's first joint) and four weights
+ * w0..w3. A frame supplies the skin's joint matrices J[0..num_joints), column-major like PyrObjectPose::transform, last row exactly
+ * 0,0,0,1. The vertex's matrix B is blended per entry e of the upper three rows, unfused f32 in this order:
+ *     B[e] = ((w0*J[j0][e] + w1*J[j1][e]) + w2*J[j2][e]) + w3*J[j3][e]          last row 0,0,0,1
+ * and the vertex takes the per-vertex rule of pyr_scene_pose with transform B and scale 1.0f: position = B position,
+ * n' = normalize(B3 n) (NOT an inverse transpose), frames as there. The object's own pose is then applied to the skinned vertex by
+ * the same rule (skipped bit for bit when it is exactly the identity): the geometry is P_object(S(rest, bindings, J)), always from
+ * rest, never from the previous frame. A skin whose joint matrices are ALL exactly the identity is copied from rest bit for bit,
+ * the same convention as an identity pose (decided per skin on the host). Weights are not renormalised.
+ *   pyr_scene_set_skins needs objects to be set. It copies the bindings to the device and sets every joint to the identity; the
+ * geometry does not change at this call. num_skins == 0 forgets the skins. Every pyr_scene_set_objects call forgets them, and so
+ * does every pyr_scene_update[_device] that carries an array: skins hang on objects, objects on the rest pose. Refused with
+ * PYR_ERR_INVALID_ARGUMENT, in this order, before any device is looked for (pyr_last_error names the argument): NULL skins with a
+ * non-zero count; a NULL scene; no objects set; a non-zero reserved word; an object index out of range; an object without
+ * triangles; two skins on one object; num_joints 0 or above 65,536; NULL joints or weights; a joint index >= num_joints, even
+ * under a zero weight; a weight that is not finite or is negative; a vertex whose weights, summed left to right in f32, are
+ * further than 1e-3 from 1. A refused call leaves the previous skins in place.
+ *   pyr_scene_skin is one call, one pose-and-skin pass, one read-back of the flag and one refit or rebuild; its contract is
+ * pyr_scene_pose's: it leaves the scene as pyr_scene_update (host arrays, the same mode) leaves it when given the arrays above; a
+ * bound beyond 1e15 is PYR_ERR_UNSUPPORTED and the scene renders as before; a live PyrSession and a refit of a spatial-split tree
+ * are refused; shape lamps get their records from the staged arrays on the device; pyr_scene_update_info describes the call.
+ * `poses` NULL: the objects keep the poses they are in (num_objects must still be the scene's). To pyr_scene_pose's argument
+ * checks, in its order, it adds: no skins set; num_joints that is not the scene's (the skins' counts summed); NULL joints; an entry
+ * that is not finite; a last row that is not 0,0,0,1. pyr_scene_pose on a scene with skins keeps the joints that scene is in. */
+typedef struct PyrSkin {
+    uint32_t object;          /* index into the ranges of pyr_scene_set_objects */
+    uint32_t num_joints;      /* 1 .. 65,536 */
+    const uint16_t* joints;   /* HOST, [object's num_triangles][3][4] */
+    const float* weights;     /* HOST, [object's num_triangles][3][4] */
+    uint32_t reserved[4];
+} PyrSkin;
+int pyr_scene_set_skins(PyrScene*, const PyrSkin* skins, uint32_t num_skins);
+typedef struct PyrSkinUpdate {
+    uint32_t mode;               /* PYR_UPDATE_REFIT | PYR_UPDATE_REBUILD */
+    uint32_t num_objects;        /* must equal the scene's */
+    const PyrObjectPose* poses;  /* HOST, [num_objects], or NULL: the objects keep the poses they are in */
+    const float* joints;         /* HOST, [num_joints][16], the skins' tables one after the other in skin order */
+    uint32_t num_joints;         /* must equal the scene's: the skins' num_joints summed */
+    uint32_t reserved[4];
+} PyrSkinUpdate;
+int pyr_scene_skin(PyrScene*, const PyrSkinUpdate*, void* hip_stream);
+
 /* Introspection of the kernel a render of `scene` with `params` would run (nothing is launched; only spectrum_samples is read
  * today). Results never depend on it -- every schedule is the same per-sample arithmetic as tracer.rs:208-345 -- but throughput
  * does, and a maintainer wants to see why a scene is slow: */

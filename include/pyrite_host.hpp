@@ -290,6 +290,23 @@ class World { // world.rs:31-36
     // Names the description's objects again on every scene of this world (pyr_scene_set_objects): the geometry as it is now is the
     // rest pose, every pose the identity. An update() that carried arrays makes the scene forget its objects until this is called.
     void set_objects();
+    // Binds meshes to joints (pyr_scene_set_skins on every scene of this world): `skins` maps an object's index in objects() to its
+    // bindings -- four joint indices below num_joints and four weights for each of the three vertices of each of the object's
+    // triangles ([T][3][4] each). Skins are in the order of their object indices. Every joint is the identity afterwards and the
+    // geometry does not change; an empty map forgets the skins, and so do set_objects() and an update() that carries arrays.
+    struct Skin {
+        uint32_t num_joints = 0;
+        std::vector<uint16_t> joints;
+        std::vector<float> weights;
+    };
+    void set_skins(const std::map<size_t, Skin>& skins);
+    // One frame of the skinned meshes of the scene on `device` (pyr_scene_skin): `joints` maps a skinned object's index to its joint
+    // matrices, 16 floats each, column-major with last row 0,0,0,1; a skin it does not name is at the identity. Every vertex takes
+    // the matrix blended from its four joints by its weights, then the object's pose: `poses` as for pose(), nullptr keeps the
+    // poses the world is in. Everything is computed from the rest pose on the GPU. flat() stays the rest pose; the world remembers
+    // joints and poses and a scene it makes later is built for them.
+    void skin(const std::map<size_t, std::vector<float>>& joints, const std::map<size_t, ObjectPose>* poses = nullptr, Update mode = Update::Refit, int device = 0,
+              void* hip_stream = nullptr);
     // pyr_scene_geometry: the geometry of the scene on `device` as it is now (frames empty unless the scene keeps them)
     struct Geometry {
         std::vector<float> positions, normals, frames, spheres;
@@ -306,7 +323,12 @@ class World { // world.rs:31-36
     std::map<std::pair<int, int>, PyrScene*> scenes_;
     std::map<std::pair<int, int>, Build> builders_; // what each scene was asked to be built by
     std::map<size_t, ObjectPose> poses_;            // the poses the scenes are in; identity where absent
+    std::map<size_t, Skin> skins_;                  // the bindings (set_skins)
+    std::map<size_t, std::vector<float>> joints_;   // the joints the scenes are in; identity where absent
+    std::vector<PyrObjectPose> pose_records(const std::map<size_t, ObjectPose>& poses) const;
     void pose_scene(PyrScene* handle, const std::map<size_t, ObjectPose>& poses, Update mode, void* hip_stream);
+    void set_skins_on(PyrScene* handle, const std::map<size_t, Skin>& skins);
+    void skin_scene(PyrScene* handle, const std::map<size_t, std::vector<float>>& joints, const std::map<size_t, ObjectPose>& poses, Update mode, void* hip_stream);
 };
 
 struct Camera { // cameras.rs:20-27

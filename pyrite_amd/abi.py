@@ -319,6 +319,27 @@ class PyrPoseUpdate(C.Structure):
     ]
 
 
+class PyrSkin(C.Structure):
+    _fields_ = [
+        ("object", C.c_uint32),
+        ("num_joints", C.c_uint32),
+        ("joints", C.c_void_p),
+        ("weights", C.c_void_p),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
+class PyrSkinUpdate(C.Structure):
+    _fields_ = [
+        ("mode", C.c_uint32),
+        ("num_objects", C.c_uint32),
+        ("poses", C.POINTER(PyrObjectPose)),
+        ("joints", C.c_void_p),
+        ("num_joints", C.c_uint32),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
 class PyrPathInfo(C.Structure):
     _fields_ = [
         ("stage_scheduler", C.c_uint32),
@@ -444,6 +465,8 @@ ENTRY_POINTS = {
     "pyr_scene_set_objects": (C.c_int, [C.c_void_p, C.POINTER(PyrObjectRange), C.c_uint32]),
     "pyr_scene_pose": (C.c_int, [C.c_void_p, C.POINTER(PyrPoseUpdate), C.c_void_p]),
     "pyr_scene_geometry": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "pyr_scene_set_skins": (C.c_int, [C.c_void_p, C.POINTER(PyrSkin), C.c_uint32]),
+    "pyr_scene_skin": (C.c_int, [C.c_void_p, C.POINTER(PyrSkinUpdate), C.c_void_p]),
     "pyr_scene_path_info": (C.c_int, [C.c_void_p, C.POINTER(PyrRenderParams), C.POINTER(PyrPathInfo)]),
     "pyr_scene_program_info": (C.c_int, [C.c_void_p, C.POINTER(PyrProgramInfo)]),
     "pyr_program_allocate_registers": (C.c_int, [C.POINTER(PyrInstr), C.POINTER(PyrProgram), C.POINTER(PyrInstr), C.POINTER(PyrProgram)]),

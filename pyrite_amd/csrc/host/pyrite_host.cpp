@@ -1080,7 +1080,11 @@ PyrScene* World::scene(int device, int copy, std::optional<Build> build) {
         std::vector<PyrObjectRange> ranges;
         for (const FlatScene::Object& o : flat_.objects()) ranges.push_back(o.range);
         check_status(pyr_scene_set_objects(handle, ranges.data(), (uint32_t)ranges.size()));
-        if (!poses_.empty()) pose_scene(handle, poses_, Update::Rebuild, nullptr);
+        if (!skins_.empty()) set_skins_on(handle, skins_);
+        if (!joints_.empty())
+            skin_scene(handle, joints_, poses_, Update::Rebuild, nullptr);
+        else if (!poses_.empty())
+            pose_scene(handle, poses_, Update::Rebuild, nullptr);
     }
     return handle;
 }
@@ -1105,19 +1109,19 @@ void World::update(const std::vector<float>& positions, const std::vector<float>
     u.spheres = spheres.empty() ? nullptr : spheres.data();
     check_status(pyr_scene_update(handle, &u));
     flat_.move_geometry(positions, normals, frames, spheres);
-    if (u.tri_positions || u.tri_normals || u.tri_frames || u.spheres) poses_.clear(); // a new geometry, not a pose of the old one: the scene forgot its objects (set_objects names them again)
+    if (u.tri_positions || u.tri_normals || u.tri_frames || u.spheres) poses_.clear(), skins_.clear(), joints_.clear(); // a new geometry, not a pose of the old one: the scene forgot its objects (set_objects names them again)
 }
 void World::set_objects() {
-    if (!poses_.empty() && !scenes_.empty()) { // every scene of this world is in the same pose: flat() follows the first
+    if ((!poses_.empty() || !joints_.empty()) && !scenes_.empty()) { // every scene of this world is in the same pose: flat() follows the first
         const Geometry g = geometry(scenes_.begin()->first.first);
         flat_.move_geometry(g.positions, g.normals, g.frames, g.spheres);
     }
     std::vector<PyrObjectRange> ranges;
     for (const FlatScene::Object& o : flat_.objects()) ranges.push_back(o.range);
     for (auto& kv : scenes_) check_status(pyr_scene_set_objects(kv.second, ranges.data(), (uint32_t)ranges.size()));
-    poses_.clear();
+    poses_.clear(), skins_.clear(), joints_.clear(); // skins hang on objects: pyr_scene_set_objects forgot them
 }
-void World::pose_scene(PyrScene* handle, const std::map<size_t, ObjectPose>& poses, Update mode, void* hip_stream) {
+std::vector<PyrObjectPose> World::pose_records(const std::map<size_t, ObjectPose>& poses) const {
     std::vector<PyrObjectPose> records(flat_.objects().size());
     for (size_t k = 0; k < records.size(); ++k) {
         const auto it = poses.find(k);
@@ -1126,6 +1130,10 @@ void World::pose_scene(PyrScene* handle, const std::map<size_t, ObjectPose>& pos
         std::memcpy(records[k].transform, pose.transform, sizeof(pose.transform));
         records[k].scale = pose.scale;
     }
+    return records;
+}
+void World::pose_scene(PyrScene* handle, const std::map<size_t, ObjectPose>& poses, Update mode, void* hip_stream) {
+    const std::vector<PyrObjectPose> records = pose_records(poses);
     PyrPoseUpdate u{};
     u.mode = mode == Update::Rebuild ? PYR_UPDATE_REBUILD : PYR_UPDATE_REFIT;
     u.num_objects = (uint32_t)records.size();
@@ -1137,6 +1145,59 @@ void World::pose(const std::map<size_t, ObjectPose>& poses, Update mode, int dev
         if (kv.first >= flat_.objects().size()) throw ProjectError("pose: no object " + std::to_string(kv.first));
     pose_scene(scene(device), poses, mode, hip_stream);
     poses_ = poses;
+}
+void World::set_skins_on(PyrScene* handle, const std::map<size_t, Skin>& skins) {
+    std::vector<PyrSkin> records;
+    for (const auto& kv : skins) {
+        PyrSkin s{};
+        s.object = (uint32_t)kv.first, s.num_joints = kv.second.num_joints;
+        s.joints = kv.second.joints.data(), s.weights = kv.second.weights.data();
+        records.push_back(s);
+    }
+    check_status(pyr_scene_set_skins(handle, records.data(), (uint32_t)records.size()));
+}
+void World::set_skins(const std::map<size_t, Skin>& skins) {
+    for (const auto& kv : skins) {
+        if (kv.first >= flat_.objects().size()) throw ProjectError("set_skins: no object " + std::to_string(kv.first));
+        const size_t words = 12 * (size_t)flat_.objects()[kv.first].range.num_triangles;
+        if (kv.second.joints.size() != words || kv.second.weights.size() != words)
+            throw ProjectError("set_skins: object " + std::to_string(kv.first) + " needs four joints and four weights for each vertex of each of its triangles");
+    }
+    for (auto& kv : scenes_) set_skins_on(kv.second, skins);
+    skins_ = skins;
+    joints_.clear();
+}
+void World::skin_scene(PyrScene* handle, const std::map<size_t, std::vector<float>>& joints, const std::map<size_t, ObjectPose>& poses, Update mode, void* hip_stream) {
+    static const float identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
+    std::vector<float> table;
+    for (const auto& kv : skins_) {
+        const auto it = joints.find(kv.first);
+        if (it != joints.end())
+            table.insert(table.end(), it->second.begin(), it->second.end());
+        else
+            for (uint32_t j = 0; j < kv.second.num_joints; ++j) table.insert(table.end(), identity, identity + 16);
+    }
+    const std::vector<PyrObjectPose> records = pose_records(poses);
+    PyrSkinUpdate u{};
+    u.mode = mode == Update::Rebuild ? PYR_UPDATE_REBUILD : PYR_UPDATE_REFIT;
+    u.num_objects = (uint32_t)records.size();
+    u.poses = records.data();
+    u.num_joints = (uint32_t)(table.size() / 16);
+    u.joints = table.data();
+    check_status(pyr_scene_skin(handle, &u, hip_stream));
+}
+void World::skin(const std::map<size_t, std::vector<float>>& joints, const std::map<size_t, ObjectPose>* poses, Update mode, int device, void* hip_stream) {
+    for (const auto& kv : joints) {
+        const auto it = skins_.find(kv.first);
+        if (it == skins_.end()) throw ProjectError("skin: no skin on object " + std::to_string(kv.first));
+        if (kv.second.size() != 16 * (size_t)it->second.num_joints) throw ProjectError("skin: object " + std::to_string(kv.first) + " needs 16 floats for each of its joints");
+    }
+    if (poses)
+        for (const auto& kv : *poses)
+            if (kv.first >= flat_.objects().size()) throw ProjectError("skin: no object " + std::to_string(kv.first));
+    const std::map<size_t, ObjectPose> named = poses ? *poses : poses_;
+    skin_scene(scene(device), joints, named, mode, hip_stream);
+    poses_ = named, joints_ = joints;
 }
 World::Geometry World::geometry(int device) {
     PyrScene* handle = scene(device);

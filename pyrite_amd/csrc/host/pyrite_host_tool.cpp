@@ -424,6 +424,36 @@ int main(int argc, char** argv) {
             std::printf("%zu objects posed\n", poses.size());
             return 0;
         }
+        if (argc >= 7 && std::string(argv[1]) == "skin") { // skin <scene> <data_dir> <bindings> <joints.f32> <geometry.f32> [rebuild] (tests)
+            // bindings: u32 object, num_joints; u16 joints[T][3][4]; f32 weights[T][3][4] for the object's T triangles. joints.f32: 16 floats a joint.
+            Project project = make_scene(argv[2], argv[3]);
+            std::unique_ptr<World> world = World::from_project(project.world, argv[3]);
+            const auto slurp = [](const char* path) {
+                std::ifstream in(path, std::ios::binary);
+                return std::vector<char>((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+            };
+            const std::vector<char> bindings = slurp(argv[4]), table = slurp(argv[5]);
+            uint32_t head[2] = {0, 0};
+            if (bindings.size() < 8) throw ProjectError("skin: the bindings file is too short");
+            std::memcpy(head, bindings.data(), 8);
+            if (head[0] >= world->objects().size()) throw ProjectError("skin: no such object");
+            const size_t words = 12 * (size_t)world->objects()[head[0]].range.num_triangles;
+            if (bindings.size() != 8 + words * 6) throw ProjectError("skin: the bindings file does not hold the object's triangles");
+            if (table.size() != (size_t)head[1] * 64) throw ProjectError("skin: the joints file does not hold 16 floats for each joint");
+            World::Skin skin;
+            skin.num_joints = head[1];
+            skin.joints.resize(words), skin.weights.resize(words);
+            if (words) std::memcpy(skin.joints.data(), bindings.data() + 8, words * 2), std::memcpy(skin.weights.data(), bindings.data() + 8 + words * 2, words * 4);
+            std::vector<float> joints(table.size() / 4);
+            if (!joints.empty()) std::memcpy(joints.data(), table.data(), table.size());
+            world->set_skins({{head[0], skin}});
+            world->skin({{head[0], joints}}, nullptr, argc >= 8 && std::string(argv[7]) == "rebuild" ? World::Update::Rebuild : World::Update::Refit);
+            const World::Geometry g = world->geometry();
+            std::ofstream out(argv[6], std::ios::binary);
+            for (const std::vector<float>* a : {&g.positions, &g.normals, &g.frames, &g.spheres}) out.write(reinterpret_cast<const char*>(a->data()), (std::streamsize)(a->size() * 4));
+            std::printf("object %u skinned to %u joints\n", head[0], head[1]);
+            return 0;
+        }
         if (argc >= 6 && std::string(argv[1]) == "intersect") { // intersect <scene> <data_dir> <rays.f32> <hits.bin>
             Project project = make_scene(argv[2], argv[3]);
             std::unique_ptr<World> world = World::from_project(project.world, argv[3]);

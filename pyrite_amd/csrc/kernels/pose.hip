@@ -1,4 +1,4 @@
-// pose.hip -- posing a live scene's objects on the device, a unit of its own: every primitive of an object
+// pose.hip -- posing a live scene's objects and skinning its meshes on the device (DESIGN.md sections 9g and 9h), a unit of its own: every primitive of an object
 // is computed from the rest pose by pose_rules.h and written to the scene's staging arrays, from where the refit of section 9f
 // (kernels/refit.hip) rewrites the records and the boxes; the records of shape lamps follow from the staging arrays too. Nothing
 // here touches a record the render kernels read except the lamp records, and those only after the host has seen the flag clear.
@@ -16,14 +16,15 @@ namespace devpose {
 namespace {
 
 typedef float float4_t __attribute__((ext_vector_type(4)));
+typedef uint32_t uint2_t __attribute__((ext_vector_type(2)));
 
 __device__ __forceinline__ float4_t load4(const float* p) { return *(const float4_t*)p; }
 __device__ __forceinline__ void store4(float* p, float4_t v) { *(float4_t*)p = v; }
 
 // the object whose lanes hold `lane`: the last one that begins at or before it (an object without lanes begins where the next
 // one does, so it is never the last such one unless it is the last object, which begins at the lane count)
-template <uint32_t DevObject::*kBegin>
-__device__ __forceinline__ uint32_t object_of(const DevObject* objects, uint32_t num_objects, uint32_t lane) {
+template <class Record, uint32_t Record::*kBegin>
+__device__ __forceinline__ uint32_t object_of(const Record* objects, uint32_t num_objects, uint32_t lane) {
     uint32_t lo = 0, hi = num_objects;
     while (hi - lo > 1) {
         const uint32_t mid = lo + (hi - lo) / 2;
@@ -35,15 +36,15 @@ __device__ __forceinline__ uint32_t object_of(const DevObject* objects, uint32_t
     return lo;
 }
 
-__device__ __forceinline__ pose::Pose load_pose(const DevObject& o) {
+__device__ __forceinline__ pose::Pose load_pose(const pose::Pose& from) {
     pose::Pose p;
-    const float4_t c0 = load4(o.pose.m), c1 = load4(o.pose.m + 4), c2 = load4(o.pose.m + 8), c3 = load4(o.pose.m + 12);
+    const float4_t c0 = load4(from.m), c1 = load4(from.m + 4), c2 = load4(from.m + 8), c3 = load4(from.m + 12);
     p.m[0] = c0.x, p.m[1] = c0.y, p.m[2] = c0.z, p.m[3] = c0.w;
     p.m[4] = c1.x, p.m[5] = c1.y, p.m[6] = c1.z, p.m[7] = c1.w;
     p.m[8] = c2.x, p.m[9] = c2.y, p.m[10] = c2.z, p.m[11] = c2.w;
     p.m[12] = c3.x, p.m[13] = c3.y, p.m[14] = c3.z, p.m[15] = c3.w;
-    p.scale = o.pose.scale;
-    p.identity = o.pose.identity;
+    p.scale = from.scale;
+    p.identity = from.identity;
     return p;
 }
 
@@ -69,10 +70,10 @@ __global__ __launch_bounds__(kBlock) void pose_triangles_kernel(Ctx c) {
     const uint32_t lane = blockIdx.x * kBlock + threadIdx.x;
     bool bad = false;
     if (lane < c.posed_triangles && c.num_objects != 0u) {
-        const DevObject& object = c.objects[object_of<&DevObject::triangle_lane>(c.objects, c.num_objects, lane)];
+        const DevObject& object = c.objects[object_of<DevObject, &DevObject::triangle_lane>(c.objects, c.num_objects, lane)];
         const uint32_t within = lane - object.triangle_lane, index = object.first_triangle + within;
         if (within < object.num_triangles && index >= object.first_triangle && index < c.num_triangles) {
-            const pose::Pose pose = load_pose(object);
+            const pose::Pose pose = load_pose(object.pose);
             const float* rest_p = c.rest_positions + 9 * (size_t)index;
             const float* rest_n = c.rest_normals + 9 * (size_t)index;
             float* out_p = c.positions + 9 * (size_t)index;
@@ -102,6 +103,71 @@ __global__ __launch_bounds__(kBlock) void pose_triangles_kernel(Ctx c) {
     raise_flag(bad, &block_flag, c.beyond_range);
 }
 
+// ---- one lane per triangle of a skin: a vertex at a time, its matrix blended from the joints its binding
+// names (pose_rules.h blend_joints), the per-vertex rule with that matrix, then the object's own pose as above. A triangle's
+// weights are 48 bytes: 16-byte loads; its joint indices are 24 bytes: 8-byte loads. The binding row is the lane. A joint index is
+// compared against the skin's count before it is used (pyr_scene_set_skins has refused such a binding: the flag, and joint 0).
+__global__ __launch_bounds__(kBlock) void skin_triangles_kernel(Ctx c) {
+    __shared__ uint32_t block_flag;
+    if (threadIdx.x == 0) block_flag = 0u;
+    __syncthreads();
+    const uint32_t lane = blockIdx.x * kBlock + threadIdx.x;
+    bool bad = false;
+    if (lane < c.skinned_triangles && c.num_skins != 0u) {
+        const DevSkin& skin = c.skins[object_of<DevSkin, &DevSkin::lane>(c.skins, c.num_skins, lane)];
+        const uint32_t within = lane - skin.lane, index = skin.first_triangle + within;
+        const bool joints_inside = skin.num_joints != 0u && skin.first_joint < c.num_joints && skin.num_joints <= c.num_joints - skin.first_joint;
+        if (within < skin.num_triangles && index >= skin.first_triangle && index < c.num_triangles && joints_inside) {
+            const pose::Pose pose = load_pose(skin.pose);
+            const uint32_t num_joints = skin.num_joints, rest_skin = skin.identity;
+            const float* joints = c.joints + 12 * (size_t)skin.first_joint;
+            const float* rest_p = c.rest_positions + 9 * (size_t)index;
+            const float* rest_n = c.rest_normals + 9 * (size_t)index;
+            float* out_p = c.positions + 9 * (size_t)index;
+            float* out_n = c.normals + 9 * (size_t)index;
+            float p[9];
+            for (int v = 0; v < 3; ++v) {
+                float n[3] = {rest_n[3 * v], rest_n[3 * v + 1], rest_n[3 * v + 2]};
+                float q[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                for (int a = 0; a < 3; ++a) p[3 * v + a] = rest_p[3 * v + a];
+                if (c.rest_frames) {
+                    const float4_t f = load4(c.rest_frames + 12 * (size_t)index + 4 * v);
+                    q[0] = f.x, q[1] = f.y, q[2] = f.z, q[3] = f.w;
+                }
+                if (!rest_skin) {
+                    const float4_t wv = load4(c.skin_weights + 12 * (size_t)lane + 4 * v);
+                    const uint2_t jv = *(const uint2_t*)(c.skin_joints + 12 * (size_t)lane + 4 * v);
+                    const float w[4] = {wv.x, wv.y, wv.z, wv.w};
+                    uint32_t j[4] = {jv.x & 0xFFFFu, jv.x >> 16, jv.y & 0xFFFFu, jv.y >> 16};
+                    for (int k = 0; k < 4; ++k)
+                        if (j[k] >= num_joints) j[k] = 0u, bad = true;
+                    pose::Pose blended;
+                    pose::blend_joints(joints, j, w, blended);
+                    pose::pose_point(blended, p + 3 * v);
+                    if (c.rest_frames)
+                        pose::pose_normal_frame(blended, n, q);
+                    else
+                        pose::pose_normal(blended, n);
+                }
+                if (!pose.identity) {
+                    pose::pose_point(pose, p + 3 * v);
+                    if (c.rest_frames)
+                        pose::pose_normal_frame(pose, n, q);
+                    else
+                        pose::pose_normal(pose, n);
+                }
+                if (c.rest_frames) store4(c.frames + 12 * (size_t)index + 4 * v, float4_t{q[0], q[1], q[2], q[3]});
+                out_n[3 * v] = n[0], out_n[3 * v + 1] = n[1], out_n[3 * v + 2] = n[2];
+            }
+            for (int k = 0; k < 9; ++k) out_p[k] = p[k];
+            float lo[3], hi[3];
+            lvl::triangle_bounds(p, lo, hi);
+            bad = bad || box_beyond_range(lo, hi);
+        }
+    }
+    raise_flag(bad, &block_flag, c.beyond_range);
+}
+
 // ---- one lane per sphere of an object
 __global__ __launch_bounds__(kBlock) void pose_spheres_kernel(Ctx c) {
     __shared__ uint32_t block_flag;
@@ -110,10 +176,10 @@ __global__ __launch_bounds__(kBlock) void pose_spheres_kernel(Ctx c) {
     const uint32_t lane = blockIdx.x * kBlock + threadIdx.x;
     bool bad = false;
     if (lane < c.posed_spheres && c.num_objects != 0u) {
-        const DevObject& object = c.objects[object_of<&DevObject::sphere_lane>(c.objects, c.num_objects, lane)];
+        const DevObject& object = c.objects[object_of<DevObject, &DevObject::sphere_lane>(c.objects, c.num_objects, lane)];
         const uint32_t within = lane - object.sphere_lane, index = object.first_sphere + within;
         if (within < object.num_spheres && index >= object.first_sphere && index < c.num_spheres) {
-            const pose::Pose pose = load_pose(object);
+            const pose::Pose pose = load_pose(object.pose);
             const float4_t r = load4(c.rest_spheres + 4 * (size_t)index);
             float s[4] = {r.x, r.y, r.z, r.w};
             if (!pose.identity) pose::pose_sphere(pose, s);
@@ -159,6 +225,7 @@ uint32_t blocks_for(uint32_t n) { return (n + kBlock - 1) / kBlock; }
 
 hipError_t launch_pose(const Ctx& c, hipStream_t stream) {
     if (c.posed_triangles) hipLaunchKernelGGL(pose_triangles_kernel, dim3(blocks_for(c.posed_triangles)), dim3(kBlock), 0, stream, c);
+    if (c.skinned_triangles) hipLaunchKernelGGL(skin_triangles_kernel, dim3(blocks_for(c.skinned_triangles)), dim3(kBlock), 0, stream, c);
     if (c.posed_spheres) hipLaunchKernelGGL(pose_spheres_kernel, dim3(blocks_for(c.posed_spheres)), dim3(kBlock), 0, stream, c);
     return hipGetLastError();
 }

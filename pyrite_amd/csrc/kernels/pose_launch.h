@@ -18,6 +18,16 @@ struct DevObject {
     uint32_t triangle_lane, sphere_lane;
 };
 
+// One skin on the device: its object's pose and triangles, where its lanes begin in the launch over all
+// skinned triangles -- which is also where its bindings begin, the skins' bindings lying one after the other in skin order -- its
+// rows of the joint table, and whether every one of them is exactly the identity (the host decides; such a skin is copied from
+// rest). 96 bytes. The launch over the objects' triangles leaves a skinned object's triangles out.
+struct DevSkin {
+    pose::Pose pose;
+    uint32_t first_triangle, num_triangles, lane;
+    uint32_t first_joint, num_joints, identity;
+};
+
 // The rest pose, the scene's staging arrays the posed geometry is written to (the ones pyr_scene_update's host form uploads
 // into and the refit reads), and the lamp records. Every count is the scene's own: the kernels index nothing they have not
 // compared against one of them.
@@ -37,10 +47,18 @@ struct Ctx {
     uint32_t* beyond_range; // one word, zeroed before the call: set when a bound of a moved primitive fails the coordinate check
     DevLamp* lamps;
     uint32_t num_lamps;
+    // the skins (none: num_skins 0 and the rest unused)
+    const DevSkin* skins;
+    uint32_t num_skins;
+    uint32_t skinned_triangles;   // lanes: the skins' triangle counts summed, and the rows of the two binding arrays
+    uint32_t num_joints;          // rows of `joints`: the skins' joint counts summed
+    const float* joints;          // [num_joints][12]: a joint's upper three rows, column by column
+    const float* skin_weights;    // [skinned_triangles][3][4]
+    const uint16_t* skin_joints;  // [skinned_triangles][3][4], relative to the skin's first joint
 };
 
 // Each enqueues on `stream` and returns hipGetLastError().
-hipError_t launch_pose(const Ctx& c, hipStream_t stream);  // triangles and spheres of every object into the staging arrays
+hipError_t launch_pose(const Ctx& c, hipStream_t stream);  // triangles and spheres of every object, skinned or posed, into the staging arrays
 hipError_t launch_lamps(const Ctx& c, hipStream_t stream); // the records of shape lamps from the staging arrays
 
 } // namespace devpose

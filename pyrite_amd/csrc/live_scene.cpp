@@ -1,6 +1,7 @@
 // live_scene.cpp -- everything that moves a scene after creation: pyr_scene_update[_device], pyr_scene_set_objects,
-// pyr_scene_pose, pyr_scene_geometry, pyr_scene_update_info. LiveGeometry (scene_internal.h) says where the geometry is and
-// which copies are valid; rebuild_from and refit_from are the two ways new arrays reach the records and trees on the device.
+// pyr_scene_pose, pyr_scene_set_skins, pyr_scene_skin, pyr_scene_geometry, pyr_scene_update_info. LiveGeometry
+// (scene_internal.h) says where the geometry is and which copies are valid; rebuild_from and refit_from are the two ways new
+// arrays reach the records and trees on the device.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -40,8 +41,17 @@ PyrSceneDesc LiveGeometry::view(const float* const with[NUM_ARRAYS]) const {
 }
 
 // (the description is current: whoever forgets the objects has fetched it)
+void LiveGeometry::forget_skins() {
+    skins.clear(), skin_joints.clear();
+    skinned_triangles = 0;
+    for (DeviceBuffer* b : {&skin_table, &skin_weights, &skin_indices, &joint_table}) b->release();
+    posed_triangles = 0; // the launch over the objects' triangles has every object's again
+    for (const devpose::DevObject& o : pose_table) posed_triangles += o.num_triangles;
+}
+
 void LiveGeometry::forget_objects() {
     pose_table.clear();
+    forget_skins();
     posed_triangles = posed_spheres = 0;
     for (LiveArray& a : arrays) a.rest.release();
     pose_objects.release();
@@ -89,27 +99,53 @@ int check_update_args(const PyrScene* scene, const PyrGeometryUpdate* u) {
     });
 }
 
+// What pyr_scene_pose and pyr_scene_skin refuse of the objects' poses (`name`: the update's struct; `may_keep`: NULL poses keep
+// the poses the scene is in), in the order pyrite_gpu.h gives.
+template <class Update>
+int check_poses(const PyrScene* scene, const Update* u, const std::string& name, bool may_keep) {
+    if (u->poses)
+        for (uint32_t i = 0; i < u->num_objects; ++i)
+            for (uint32_t word : u->poses[i].reserved)
+                if (word != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectPose.reserved must be zero");
+    if (scene->live.pose_table.empty()) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".num_objects: the scene has no objects (pyr_scene_set_objects names them)");
+    if (u->num_objects != scene->live.pose_table.size()) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".num_objects is not the scene's");
+    if (!u->poses) return may_keep ? (int)PYR_OK : fail(PYR_ERR_INVALID_ARGUMENT, name + ".poses is null");
+    for (uint32_t i = 0; i < u->num_objects; ++i) {
+        const PyrObjectPose& p = u->poses[i];
+        for (float x : p.transform)
+            if (!std::isfinite(x)) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectPose.transform has an entry that is not finite");
+        if (!std::isfinite(p.scale)) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectPose.scale is not finite");
+    }
+    for (uint32_t i = 0; i < u->num_objects; ++i) {
+        const float* m = u->poses[i].transform;
+        if (!(m[3] == 0.0f && m[7] == 0.0f && m[11] == 0.0f && m[15] == 1.0f)) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectPose.transform: the last row must be 0, 0, 0, 1");
+    }
+    return (int)PYR_OK;
+}
+
 // What pyr_scene_pose refuses before any device is looked for, in the order pyrite_gpu.h gives.
 int check_pose_args(const PyrScene* scene, const PyrPoseUpdate* u) {
     if (!u) return fail(PYR_ERR_INVALID_ARGUMENT, "null update");
     if (!scene) return fail(PYR_ERR_INVALID_ARGUMENT, "null scene");
-    return check_move(scene, u, "PyrPoseUpdate", "pose", [&]() {
-        if (u->poses)
-            for (uint32_t i = 0; i < u->num_objects; ++i)
-                for (uint32_t word : u->poses[i].reserved)
-                    if (word != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectPose.reserved must be zero");
-        if (scene->live.pose_table.empty()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrPoseUpdate.num_objects: the scene has no objects (pyr_scene_set_objects names them)");
-        if (u->num_objects != scene->live.pose_table.size()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrPoseUpdate.num_objects is not the scene's");
-        if (!u->poses) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrPoseUpdate.poses is null");
-        for (uint32_t i = 0; i < u->num_objects; ++i) {
-            const PyrObjectPose& p = u->poses[i];
-            for (float x : p.transform)
-                if (!std::isfinite(x)) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectPose.transform has an entry that is not finite");
-            if (!std::isfinite(p.scale)) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectPose.scale is not finite");
-        }
-        for (uint32_t i = 0; i < u->num_objects; ++i) {
-            const float* m = u->poses[i].transform;
-            if (!(m[3] == 0.0f && m[7] == 0.0f && m[11] == 0.0f && m[15] == 1.0f)) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectPose.transform: the last row must be 0, 0, 0, 1");
+    return check_move(scene, u, "PyrPoseUpdate", "pose", [&]() { return check_poses(scene, u, "PyrPoseUpdate", false); });
+}
+
+// What pyr_scene_skin adds to that: the joint table.
+int check_skin_args(const PyrScene* scene, const PyrSkinUpdate* u) {
+    if (!u) return fail(PYR_ERR_INVALID_ARGUMENT, "null update");
+    if (!scene) return fail(PYR_ERR_INVALID_ARGUMENT, "null scene");
+    return check_move(scene, u, "PyrSkinUpdate", "skin", [&]() {
+        const int rc = check_poses(scene, u, "PyrSkinUpdate", true);
+        if (rc != PYR_OK) return rc;
+        const LiveGeometry& live = scene->live;
+        if (live.skins.empty()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSkinUpdate.num_joints: the scene has no skins (pyr_scene_set_skins binds them)");
+        if ((size_t)u->num_joints * 16 != live.skin_joints.size()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSkinUpdate.num_joints is not the scene's");
+        if (!u->joints) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSkinUpdate.joints is null");
+        for (size_t k = 0; k < live.skin_joints.size(); ++k)
+            if (!std::isfinite(u->joints[k])) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSkinUpdate.joints has an entry that is not finite");
+        for (uint32_t j = 0; j < u->num_joints; ++j) {
+            const float* m = u->joints + 16 * (size_t)j;
+            if (!(m[3] == 0.0f && m[7] == 0.0f && m[11] == 0.0f && m[15] == 1.0f)) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSkinUpdate.joints: the last row must be 0, 0, 0, 1");
         }
         return (int)PYR_OK;
     });
@@ -316,12 +352,45 @@ devpose::Ctx pose_context(PyrScene* s) {
     c.posed_triangles = live.posed_triangles, c.posed_spheres = live.posed_spheres;
     c.beyond_range = (uint32_t*)live.pose_flag.ptr;
     c.lamps = (DevLamp*)s->lamps.ptr, c.num_lamps = (uint32_t)live.lamps.size();
+    c.skins = (const devpose::DevSkin*)live.skin_table.ptr, c.num_skins = (uint32_t)live.skins.size();
+    c.skinned_triangles = live.skinned_triangles, c.num_joints = (uint32_t)(live.skin_joints.size() / 16);
+    c.joints = (const float*)live.joint_table.ptr;
+    c.skin_weights = (const float*)live.skin_weights.ptr, c.skin_joints = (const uint16_t*)live.skin_indices.ptr;
     return c;
 }
 
-// Every object's primitives from the rest pose into the staging arrays under `table`, and the flag back: the one wait.
-int run_pose(PyrScene* s, const std::vector<devpose::DevObject>& table, hipStream_t stream, uint32_t& beyond_range) {
-    HIP_TRY(hipMemcpyAsync(s->live.pose_objects.ptr, table.data(), table.size() * sizeof(devpose::DevObject), hipMemcpyHostToDevice, stream));
+// Every object's primitives from the rest pose into the staging arrays under `table` and, where the scene has skins, under
+// `joints` ([joints][16]), and the flag back: the one wait. A skinned object's triangles have their lanes in the skin kernel's
+// launch, so the table the pose kernels read gives that object none.
+int run_pose(PyrScene* s, const std::vector<devpose::DevObject>& table, const std::vector<float>& joints, hipStream_t stream, uint32_t& beyond_range) {
+    const LiveGeometry& live = s->live;
+    std::vector<devpose::DevObject> unskinned; // (these three live until the wait below)
+    std::vector<devpose::DevSkin> skins(live.skins.size());
+    std::vector<float> rows(joints.size() / 16 * 12);
+    if (!live.skins.empty()) {
+        unskinned = table;
+        for (size_t k = 0; k < skins.size(); ++k) {
+            const LiveGeometry::Skin& from = live.skins[k];
+            devpose::DevSkin& to = skins[k];
+            to.pose = table[from.object].pose;
+            to.first_triangle = table[from.object].first_triangle, to.num_triangles = table[from.object].num_triangles, to.lane = from.lane;
+            to.first_joint = from.first_joint, to.num_joints = from.num_joints;
+            bool same = true;
+            for (size_t j = from.first_joint; j < (size_t)from.first_joint + from.num_joints; ++j)
+                for (int e = 0; e < 16; ++e) same = same && joints[16 * j + e] == kIdentity[e];
+            to.identity = same ? 1u : 0u;
+            unskinned[from.object].num_triangles = 0;
+        }
+        uint32_t lane = 0;
+        for (devpose::DevObject& o : unskinned) o.triangle_lane = lane, lane += o.num_triangles;
+        for (size_t j = 0; j < rows.size() / 12; ++j)
+            for (int col = 0; col < 4; ++col)
+                for (int row = 0; row < 3; ++row) rows[12 * j + 3 * col + row] = joints[16 * j + 4 * col + row];
+        HIP_TRY(hipMemcpyAsync(live.skin_table.ptr, skins.data(), skins.size() * sizeof(devpose::DevSkin), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(live.joint_table.ptr, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, stream));
+    }
+    const std::vector<devpose::DevObject>& objects = live.skins.empty() ? table : unskinned;
+    HIP_TRY(hipMemcpyAsync(s->live.pose_objects.ptr, objects.data(), objects.size() * sizeof(devpose::DevObject), hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemsetAsync(s->live.pose_flag.ptr, 0, 4, stream));
     const hipError_t e = devpose::launch_pose(pose_context(s), stream);
     if (e != hipSuccess) return hip_fail(e, "pose kernels");
@@ -330,27 +399,31 @@ int run_pose(PyrScene* s, const std::vector<devpose::DevObject>& table, hipStrea
     return PYR_OK;
 }
 
-int scene_pose(PyrScene* s, const PyrPoseUpdate* u, hipStream_t stream) {
+// pyr_scene_pose and pyr_scene_skin: `poses` nullptr keeps the poses the scene is in, `new_joints` nullptr its joints.
+int scene_pose(PyrScene* s, uint32_t mode, const PyrObjectPose* poses, const float* new_joints, hipStream_t stream) {
     const auto t_start = Clock::now();
     HIP_TRY(hipSetDevice(s->device));
     LiveGeometry& live = s->live;
     int rc;
-    if (u->mode == PYR_UPDATE_REFIT && (rc = prepare_refit(s)) != PYR_OK) return rc;
+    if (mode == PYR_UPDATE_REFIT && (rc = prepare_refit(s)) != PYR_OK) return rc;
     std::vector<devpose::DevObject> table = live.pose_table;
-    for (uint32_t i = 0; i < u->num_objects; ++i) set_pose(table[i], u->poses[i].transform, u->poses[i].scale);
+    if (poses)
+        for (size_t i = 0; i < table.size(); ++i) set_pose(table[i], poses[i].transform, poses[i].scale);
+    std::vector<float> joints = live.skin_joints;
+    if (new_joints) joints.assign(new_joints, new_joints + joints.size());
     uint32_t beyond_range = 0;
-    if ((rc = run_pose(s, table, stream, beyond_range)) != PYR_OK) return rc;
-    const auto refused = [&](int why) { // no record has been touched: the staging arrays go back to the poses the scene is in
-        const int back = run_pose(s, live.pose_table, stream, beyond_range);
+    if ((rc = run_pose(s, table, joints, stream, beyond_range)) != PYR_OK) return rc;
+    const auto refused = [&](int why) { // no record has been touched: the staging arrays go back to the poses and joints the scene is in
+        const int back = run_pose(s, live.pose_table, live.skin_joints, stream, beyond_range);
         return back != PYR_OK ? back : why;
     };
     if (beyond_range != 0) return refused(fail(PYR_ERR_UNSUPPORTED, kCoordinateRangeMessage));
     PyrUpdateInfo info{};
-    info.mode_used = u->mode;
+    info.mode_used = mode;
     info.area_ratio = 1.0;
     const auto t_posed = Clock::now();
 
-    if (u->mode == PYR_UPDATE_REBUILD) { // the staging arrays are the geometry now: the description follows them, then a rebuild over it
+    if (mode == PYR_UPDATE_REBUILD) { // the staging arrays are the geometry now: the description follows them, then a rebuild over it
         const float* const none[NUM_ARRAYS] = {nullptr, nullptr, nullptr, nullptr};
         info.upload_ms = (float)ms_between(t_start, t_posed);
         live.posed();
@@ -359,18 +432,53 @@ int scene_pose(PyrScene* s, const PyrPoseUpdate* u, hipStream_t stream) {
             live.posed();
             return refused(rc);
         }
-        live.pose_table.swap(table);
+        live.pose_table.swap(table), live.skin_joints.swap(joints);
         return PYR_OK;
     }
 
     // ---- refit: every record and box from the staging arrays, as the host form of pyr_scene_update given all four arrays
-    live.pose_table.swap(table);
+    live.pose_table.swap(table), live.skin_joints.swap(joints);
     live.posed();
     const float* source[NUM_ARRAYS];
     for (int k = 0; k < NUM_ARRAYS; ++k) source[k] = live.kept_floats(k) ? (const float*)live.arrays[k].staging.ptr : nullptr;
     const hipError_t e = devpose::launch_lamps(pose_context(s), stream);
     if (e != hipSuccess) return hip_fail(e, "pose: lamp records");
     return refit_from(s, source, live.num_triangles != 0, live.num_spheres != 0, false, stream, t_start, &t_posed, info);
+}
+
+// What pyr_scene_set_skins refuses of the skins themselves, in the order pyrite_gpu.h gives.
+int check_skins(const LiveGeometry& live, const PyrSkin* skins, uint32_t n) {
+    const auto triangles_of = [&](const PyrSkin& s) { return (size_t)live.pose_table[s.object].num_triangles; };
+    for (uint32_t k = 0; k < n; ++k)
+        for (uint32_t word : skins[k].reserved)
+            if (word != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSkin.reserved must be zero");
+    for (uint32_t k = 0; k < n; ++k)
+        if (skins[k].object >= live.pose_table.size()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSkin.object is not one of the scene's objects");
+    for (uint32_t k = 0; k < n; ++k)
+        if (triangles_of(skins[k]) == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSkin.object: the object has no triangles");
+    std::vector<uint32_t> taken;
+    for (uint32_t k = 0; k < n; ++k) taken.push_back(skins[k].object);
+    std::sort(taken.begin(), taken.end());
+    if (std::adjacent_find(taken.begin(), taken.end()) != taken.end()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSkin.object: two skins on one object");
+    for (uint32_t k = 0; k < n; ++k)
+        if (skins[k].num_joints == 0 || skins[k].num_joints > 65536u) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSkin.num_joints must be 1 to 65,536");
+    for (uint32_t k = 0; k < n; ++k) {
+        if (!skins[k].joints) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSkin.joints is null");
+        if (!skins[k].weights) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSkin.weights is null");
+    }
+    for (uint32_t k = 0; k < n; ++k)
+        for (size_t i = 0, end = 12 * triangles_of(skins[k]); i < end; ++i)
+            if (skins[k].joints[i] >= skins[k].num_joints) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSkin.joints names a joint index that is not below num_joints");
+    for (uint32_t k = 0; k < n; ++k)
+        for (size_t i = 0, end = 12 * triangles_of(skins[k]); i < end; ++i)
+            if (!std::isfinite(skins[k].weights[i]) || skins[k].weights[i] < 0.0f) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSkin.weights has a weight that is not finite or is negative");
+    for (uint32_t k = 0; k < n; ++k)
+        for (size_t i = 0, end = 12 * triangles_of(skins[k]); i < end; i += 4) {
+            const float* w = skins[k].weights + i;
+            const float sum = ((w[0] + w[1]) + w[2]) + w[3];
+            if (!(std::fabs(sum - 1.0f) <= 1.0e-3f)) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSkin.weights: a vertex's weights do not sum to 1 within 1e-3");
+        }
+    return PYR_OK;
 }
 
 // ranges inside the counts and pairwise disjoint, triangles and spheres each
@@ -434,7 +542,56 @@ int pyr_scene_set_objects(PyrScene* scene, const PyrObjectRange* ranges, uint32_
 int pyr_scene_pose(PyrScene* scene, const PyrPoseUpdate* update, void* hip_stream) {
     int rc = check_pose_args(scene, update);
     if (rc != PYR_OK) return rc;
-    return scene_pose(scene, update, (hipStream_t)hip_stream);
+    return scene_pose(scene, update->mode, update->poses, nullptr, (hipStream_t)hip_stream);
+}
+
+int pyr_scene_set_skins(PyrScene* scene, const PyrSkin* skins, uint32_t num_skins) {
+    if (num_skins != 0 && !skins) return fail(PYR_ERR_INVALID_ARGUMENT, "null skins with a non-zero num_skins");
+    if (!scene) return fail(PYR_ERR_INVALID_ARGUMENT, "null scene");
+    LiveGeometry& live = scene->live;
+    if (live.pose_table.empty()) return fail(PYR_ERR_INVALID_ARGUMENT, "pyr_scene_set_skins: the scene has no objects (pyr_scene_set_objects names them)");
+    int rc = check_skins(live, skins, num_skins);
+    if (rc != PYR_OK) return rc;
+    if (num_skins == 0 && live.skins.empty()) return PYR_OK;
+    HIP_TRY(hipSetDevice(scene->device));
+    HIP_TRY(hipDeviceSynchronize()); // an earlier call's kernels may still read the bindings
+    if (num_skins == 0) {
+        live.forget_skins();
+        return PYR_OK;
+    }
+    // the bindings one skin after the other, on the device before anything of the old skins is let go
+    std::vector<LiveGeometry::Skin> table(num_skins);
+    std::vector<float> weights;
+    std::vector<uint16_t> indices;
+    uint32_t lane = 0, joint = 0;
+    for (uint32_t k = 0; k < num_skins; ++k) {
+        const size_t words = 12 * (size_t)live.pose_table[skins[k].object].num_triangles;
+        table[k] = {skins[k].object, skins[k].num_joints, joint, lane};
+        weights.insert(weights.end(), skins[k].weights, skins[k].weights + words);
+        indices.insert(indices.end(), skins[k].joints, skins[k].joints + words);
+        lane += live.pose_table[skins[k].object].num_triangles, joint += skins[k].num_joints; // disjoint ranges: below 2^28; at most 2^16 a skin
+    }
+    DeviceBuffer fresh[4]; // weights, indices, DevSkin records, joint rows
+    if ((rc = fresh[0].upload(weights.data(), weights.size() * 4)) != PYR_OK) return rc;
+    if ((rc = fresh[1].upload(indices.data(), indices.size() * 2)) != PYR_OK) return rc;
+    if ((rc = fresh[2].alloc((size_t)num_skins * sizeof(devpose::DevSkin))) != PYR_OK) return rc;
+    if ((rc = fresh[3].alloc((size_t)joint * 48)) != PYR_OK) return rc;
+    DeviceBuffer* const own[4] = {&live.skin_weights, &live.skin_indices, &live.skin_table, &live.joint_table};
+    for (int k = 0; k < 4; ++k) std::swap(own[k]->ptr, fresh[k].ptr), std::swap(own[k]->bytes, fresh[k].bytes);
+    live.skins.swap(table);
+    live.skin_joints.clear();
+    for (uint32_t j = 0; j < joint; ++j) live.skin_joints.insert(live.skin_joints.end(), kIdentity, kIdentity + 16);
+    live.skinned_triangles = lane;
+    live.posed_triangles = 0;
+    for (const devpose::DevObject& o : live.pose_table) live.posed_triangles += o.num_triangles;
+    live.posed_triangles -= lane;
+    return PYR_OK;
+}
+
+int pyr_scene_skin(PyrScene* scene, const PyrSkinUpdate* update, void* hip_stream) {
+    int rc = check_skin_args(scene, update);
+    if (rc != PYR_OK) return rc;
+    return scene_pose(scene, update->mode, update->poses, update->joints, (hipStream_t)hip_stream);
 }
 
 int pyr_scene_geometry(PyrScene* scene, float* tri_positions, float* tri_normals, float* tri_frames, float* spheres) {

@@ -1,4 +1,5 @@
-// pose_rules.h -- what a pose does to one vertex, one sphere and one lamp, as functions of one record: the
+// pose_rules.h -- what a pose does to one vertex, one sphere and one lamp and how a skin blends a vertex's
+// matrix (section 9h), as functions of one record: the
 // pose kernels (kernels/pose.hip) and the host rehearsal (tests/probes/pose_check.cpp) both compile these, so what they compute
 // can differ only in the square root and the reciprocal -- sqrt32 / rcp32 of exact_math.h on the device, std::sqrt and 1.0f / x on
 // the host, bit-identical in the ranges exact_math.h names.
@@ -136,6 +137,23 @@ PYR_POSE_HD void pose_normal_frame(const Pose& pose, float* n, float* frame) {
     normalize(y);
     quat_from_cols(x, y, n, frame);
 }
+// ---- the skin rule: one vertex's matrix blended from four joints, `joints` holding twelve floats a joint
+// -- the upper three rows, column by column -- and j0..j3 already compared against the skin's joint count. Every entry is
+// ((w0*J0 + w1*J1) + w2*J2) + w3*J3, unfused; the last row is 0,0,0,1. The vertex then takes the per-vertex rule above with
+// Pose{B, 1.0f, not identity}.
+PYR_POSE_HD void blend_joints(const float* joints, const uint32_t* j, const float* w, Pose& b) {
+    const float *a0 = joints + 12 * (size_t)j[0], *a1 = joints + 12 * (size_t)j[1], *a2 = joints + 12 * (size_t)j[2], *a3 = joints + 12 * (size_t)j[3];
+    for (int col = 0; col < 4; ++col) {
+        for (int row = 0; row < 3; ++row) {
+            const int e = 3 * col + row;
+            b.m[4 * col + row] = ((w[0] * a0[e] + w[1] * a1[e]) + w[2] * a2[e]) + w[3] * a3[e];
+        }
+        b.m[4 * col + 3] = col == 3 ? 1.0f : 0.0f;
+    }
+    b.scale = 1.0f;
+    b.identity = 0u;
+}
+
 // ---- the per-sphere rule: radius *= scale; centre *= scale; centre = transform_point(centre)
 PYR_POSE_HD void pose_sphere(const Pose& pose, float* s) {
     s[3] = s[3] * pose.scale;

@@ -63,7 +63,7 @@ struct LiveArray {       // one of the arrays that move, and its homes
 
 // Where a scene's geometry is now, and which of its copies are valid (live_scene.cpp). Four arrays move -- positions, normals,
 // frames, spheres -- and each has up to three homes in the scene: `host`, the description a rebuild packs from and a refit's
-// lamp records need; `staging`, the device array a host update uploads into, the pose kernels write and the refit reads; `rest`,
+// lamp records need; `staging`, the device array a host update uploads into, the pose and skin kernels write and the refit reads; `rest`,
 // the device copy taken when objects were named, which every pose starts from. What never moves (uvs, materials, the lamp
 // list) are plain members.
 //
@@ -94,12 +94,22 @@ struct LiveGeometry {
     std::vector<devpose::DevObject> pose_table;
     uint32_t posed_triangles = 0, posed_spheres = 0;
     DeviceBuffer pose_objects, pose_flag;
+    // the skins in skin order (pyr_scene_set_skins): whose triangles, which rows of the joint table, where the lanes and bindings
+    // begin; and the joint matrices the scene is in, [joints][16] (identity when the skins are set)
+    struct Skin {
+        uint32_t object, num_joints, first_joint, lane;
+    };
+    std::vector<Skin> skins;
+    std::vector<float> skin_joints;
+    uint32_t skinned_triangles = 0;
+    DeviceBuffer skin_table, skin_weights, skin_indices, joint_table; // DevSkin records, the two binding arrays, twelve floats a joint
 
     size_t floats(int k) const { return (size_t)arrays[k].width * (arrays[k].per_sphere ? num_spheres : num_triangles); } // of array k in full, kept or not
     size_t kept_floats(int k) const { return arrays[k].kept ? floats(k) : 0; }
     void keep(const PyrSceneDesc* d); // scene creation: the description's geometry
     PyrSceneDesc view(const float* const with[NUM_ARRAYS] = nullptr) const; // what pack_geometry and pack_lamp read; `with`: arrays in place of the scene's own
-    void forget_objects(); // (adopted() does it: new arrays are a new geometry, not a pose of the old one)
+    void forget_objects(); // (adopted() does it: new arrays are a new geometry, not a pose of the old one); forgets the skins too
+    void forget_skins();
     bool host_current() const { return host_current_; }
     bool positions_staged() const { return positions_staged_; }
     bool schedule_current() const { return schedule_current_; }

@@ -27,6 +27,8 @@ class World:
         self._builders = {}
         self._objects = [dict(o) for o in flat.objects]  # what moves together (World.pose)
         self._poses = {}  # object index -> (float32[16] column-major, scale): the poses the scenes are in; identity where absent
+        self._skins = {}  # object index -> dict(joints uint16 [T,3,4], weights float32 [T,3,4], num_joints): the bindings (World.set_skins)
+        self._joints = {}  # object index -> float32 [J,16] column-major: the joints the scenes are in; identity where absent
 
     @classmethod
     def from_project(cls, world, base_dir="."):
@@ -57,7 +59,11 @@ class World:
             self._builders[key] = build or "host"
             if self._objects:  # the rest pose is the description; a scene made after a pose is built for the pose it is in
                 self._set_objects(handle)
-                if self._poses:
+                if self._skins:
+                    self._set_skins(handle, self._skins)
+                if self._joints:
+                    self._skin(handle, self._joints, self._poses, "rebuild", 0)
+                elif self._poses:
                     self._pose(handle, self._poses, "rebuild", 0)
         elif build is not None and build != self._builders[key]:
             raise ValueError("the scene on device %r was created with build=%r" % (device, self._builders[key]))
@@ -94,12 +100,13 @@ class World:
     def set_objects(self, objects=None):
         """Names other primitive ranges as the objects (pyr_scene_set_objects on every scene of this world; None: the records of
         the description again). The geometry as it is now becomes the rest pose, and every pose is the identity again."""
-        if self._poses and self._scenes:  # every scene of this world is in the same pose: `flat` follows the first
+        if (self._poses or self._joints) and self._scenes:  # every scene of this world is in the same pose: `flat` follows the first
             self._follow(self._geometry(next(iter(self._scenes.values()))))
         objects = [dict(o) for o in (self.flat.objects if objects is None else objects)]
         for handle in self._scenes.values():
             self._set_objects(handle, objects)
         self._objects, self._poses = objects, {}
+        self._skins, self._joints = {}, {}  # skins hang on objects: pyr_scene_set_objects forgot them
 
     def _follow(self, arrays):
         for name, attr in (("positions", "tri_positions"), ("normals", "tri_normals"), ("frames", "tri_frames"), ("spheres", "spheres")):
@@ -107,7 +114,7 @@ class World:
                 setattr(self.flat, attr, [np.array(arrays[name], dtype=np.float32).reshape(len(arrays[name]), -1)])
         self._desc = self.flat.desc()
 
-    def _pose(self, handle, poses, mode, stream):
+    def _pose_records(self, poses):
         records = (abi.PyrObjectPose * max(1, len(self._objects)))()
         for k in range(len(self._objects)):
             matrix, scale = poses.get(k, (None, 1.0))
@@ -119,6 +126,10 @@ class World:
                 raise ValueError("the pose of object %d is not a 4x4 matrix" % k)
             records[k].transform = (C.c_float * 16)(*[float(x) for x in m])
             records[k].scale = float(scale)
+        return records
+
+    def _pose(self, handle, poses, mode, stream):
+        records = self._pose_records(poses)
         u = abi.PyrPoseUpdate(mode=self.UPDATE_MODES[mode], num_objects=len(self._objects), poses=records)
         check(lib().pyr_scene_pose(handle, C.byref(u), C.c_void_p(int(stream))))
 
@@ -136,6 +147,72 @@ class World:
         named = {int(k): (None if v[0] is None else np.array(v[0], dtype=np.float32), float(v[1])) for k, v in poses.items()}
         self._pose(self.scene(device), named, mode, stream)
         self._poses = named
+
+    def _set_skins(self, handle, skins):
+        order = sorted(skins)
+        records = (abi.PyrSkin * max(1, len(order)))()
+        for k, index in enumerate(order):
+            s = skins[index]
+            records[k] = abi.PyrSkin(object=index, num_joints=s["num_joints"], joints=s["joints"].ctypes.data, weights=s["weights"].ctypes.data)
+        check(lib().pyr_scene_set_skins(handle, records, len(order)))
+
+    def set_skins(self, skins):
+        """Binds meshes to joints (pyr_scene_set_skins on every scene of this world): `skins` maps an object's index in
+        `World.objects` to dict(joints=uint16 [T,3,4], weights=float32 [T,3,4], num_joints=J) for that object's T triangles --
+        four joint indices below J and four weights per vertex. Skins are in the order of their object indices. Every joint is
+        the identity afterwards and the geometry does not change; an empty dict forgets the skins."""
+        bound = {}
+        for index, s in skins.items():
+            if not 0 <= int(index) < len(self._objects):
+                raise ValueError("no object %r: the world has %d" % (index, len(self._objects)))
+            shape = (self._objects[int(index)].get("num_triangles", 0), 3, 4)
+            joints, weights = np.asarray(s["joints"]), np.asarray(s["weights"])
+            if joints.shape != shape or weights.shape != shape:
+                raise ValueError("the skin of object %r needs joints and weights of shape %r, not %r and %r" % (index, shape, joints.shape, weights.shape))
+            if joints.size and (joints.min() < 0 or joints.max() > 0xFFFF):
+                raise ValueError("the skin of object %r names a joint index that is no uint16" % (index,))
+            bound[int(index)] = dict(joints=np.ascontiguousarray(joints, dtype=np.uint16), weights=np.ascontiguousarray(weights, dtype=np.float32), num_joints=int(s["num_joints"]))
+        for handle in self._scenes.values():
+            self._set_skins(handle, bound)
+        self._skins, self._joints = bound, {}
+
+    def _joint_tables(self, joints):
+        """{object: float32 [J,16] column-major} of `joints`, checked against the skins."""
+        tables = {}
+        for index, table in joints.items():
+            if int(index) not in self._skins:
+                raise ValueError("no skin on object %r" % (index,))
+            t = np.asarray(table, dtype=np.float32)
+            if t.ndim == 3 and t.shape[1:] == (4, 4):
+                t = t.transpose(0, 2, 1)  # rows of a 4x4 array -> column-major
+            t = np.ascontiguousarray(t, dtype=np.float32).reshape(len(t), -1)
+            if t.shape != (self._skins[int(index)]["num_joints"], 16):
+                raise ValueError("the joints of object %r are not %d 4x4 matrices" % (index, self._skins[int(index)]["num_joints"]))
+            tables[int(index)] = t
+        return tables
+
+    def _skin(self, handle, tables, poses, mode, stream):
+        rows = [tables[index] if index in tables else np.tile(self.IDENTITY, (self._skins[index]["num_joints"], 1)) for index in sorted(self._skins)]
+        table = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, 16)), dtype=np.float32)
+        records = self._pose_records(poses)
+        u = abi.PyrSkinUpdate(mode=self.UPDATE_MODES[mode], num_objects=len(self._objects), poses=records, joints=table.ctypes.data, num_joints=len(table))
+        check(lib().pyr_scene_skin(handle, C.byref(u), C.c_void_p(int(stream))))
+
+    def skin(self, joints, poses=None, mode="refit", device=0, stream=0):
+        """One frame of the skinned meshes of the scene on `device` (pyr_scene_skin): `joints` maps a skinned object's index to its
+        joint matrices, [J,4,4] as written on paper or [J,16] column-major; a skin it does not name is at the identity. Every
+        vertex takes the matrix blended from its four joints by its weights, then the object's pose: `poses` as for `pose`, None
+        keeps the poses the world is in. Everything is computed from the rest pose on the GPU; mode as for `update`. `World.flat`
+        stays the rest pose, and the world remembers joints and poses for scenes it creates later."""
+        if mode not in self.UPDATE_MODES:
+            raise ValueError("mode must be 'refit' or 'rebuild', not %r" % (mode,))
+        for k in ({} if poses is None else poses):
+            if not 0 <= int(k) < len(self._objects):
+                raise ValueError("no object %r: the world has %d" % (k, len(self._objects)))
+        tables = self._joint_tables(joints)
+        named = self._poses if poses is None else {int(k): (None if v[0] is None else np.array(v[0], dtype=np.float32), float(v[1])) for k, v in poses.items()}
+        self._skin(self.scene(device), tables, named, mode, stream)
+        self._poses, self._joints = named, tables
 
     def geometry(self, device=0):
         """The geometry of the scene on `device` as it is now (pyr_scene_geometry): a dict of float32 arrays `positions` [n,9],
@@ -195,6 +272,7 @@ class World:
         del keep
         if u.tri_positions or u.tri_normals or u.tri_frames or u.spheres:
             self._poses = {}  # new arrays are a new geometry, not a pose of the old one: the scene forgot its objects (set_objects names them again)
+            self._skins, self._joints = {}, {}
         for name, attr in (("positions", "tri_positions"), ("normals", "tri_normals"), ("frames", "tri_frames"), ("spheres", "spheres")):
             if name in host:
                 setattr(self.flat, attr, [host[name].copy()])
