@@ -4,13 +4,16 @@
 // calls: sample generation, tracer::trace (tracer.rs:208-345), trace_direct (:347-442), the spectral fold `contribute`
 // (renderer/algorithm.rs:14-100, applied online bounce by bounce) and Film::expose (film.rs:89-95).
 //
-// Execution models, all running the same per-path code and so producing the same film:
+// Execution models, both stating a path through the same rules ("the path's rules" below: the miss, the
+// component and its probability, scattering, the next-event gate, a light sample's acceptance, `contribute`) and so producing
+// the same film:
 //   render_kernel      one persistent launch; a wave walks a strided sequence of 64-iteration chunks, lane = iteration, and
 //                      the 64 paths advance bounce by bounce (scenes that fit in LDS: C1, C2)
 //   render_kernel_sm   every lane runs its path as a state machine (Walker) and refills itself; the wave votes on which
 //                      phase code runs next; traversal is resumable (big scenes: C3-C5, textured scenes)
+// and beside them
 //   intersect_kernel   World::intersect for ray batches: persistent waves with a segmented work feed
-//   develop_kernel     film -> 8-bit sRGB
+// (What becomes of a film -- develop_kernel, assemble_*_kernel, sessions, linear images -- lives in the units: kernels/main.hip, film.hip, tone.hip.)
 // Per lane: path state in VGPRs, the S - 1 spectral companions (wavelength / brightness / reflectance) and the traversal
 // stack in LDS laid out [entry][lane] (bank-conflict free), BVH nodes fetched as 4 x dwordx4 (64 B, both children's boxes,
 // tested with packed fp32), leaf primitives as 3 x dwordx4, one primitive per step. Film exposure is two no-return
@@ -1441,6 +1444,167 @@ DEV bool locate_chunk(const RenderLaunch& L, uint32_t chunk, uint32_t lane, uint
     return true;
 }
 
+// ================================================================================================= the path's rules
+// The reference's rules of a path (tracer.rs:208-459, materials/mod.rs, lamp.rs, renderer/algorithm.rs:14-100), each stated once
+// for the two integrators below (bounce_step; Walker::shade / next_event / finish_bounce) and the feature pass (kernels/features.hip).
+// The callers keep what is theirs: how a contribution is applied (online, noted for contribute_pending / tape_pending, or pushed
+// on the tape), the parked companions of the synchronous walk's light samples, stage transitions, profiling laps and wave priority.
+// A path's random draws and f32 operations happen in the order of this text; the oracle (oracle/oracle.cpp) states the same rules
+// independently, on purpose. How a caller holds a rule's result is not free: scatter()'s struct kept alive across Walker::shade cost
+// an interpreter build of the stage scheduler 135 v_readlane, get_probability()'s across bounce_step the C1 / C2 kernel 67, for the
+// same arithmetic -- both read the fields into locals at once. The listing decides (tests/test_kernel_isa.py).
+
+DEV f3 face_forward(f3 normal, f3 ray_d) { return dot(ray_d, normal) < 0.0f ? normal : -normal; }
+
+// miss: the colour program of the first matching directional lamp (trace_directional, tracer.rs:444-459) or the sky; dispersed = false
+DEV uint32_t miss_program(const DevScene& S, bool sample_light, f3 ray_d) {
+    uint32_t color = S.sky_program;
+    if (sample_light) {
+        for (uint32_t i = 0; i < S.num_lamps; ++i) {
+            const DevLamp& l = S.lamps[i];
+            if (l.kind == PYR_LAMP_DIRECTIONAL && dot(ld3(l.v), ray_d) >= l.width) {
+                color = l.color_program;
+                break;
+            }
+        }
+    }
+    return color;
+}
+
+// choose_component / choose_emissive, materials/mod.rs:48-62: one of `count` components from `first` on
+DEV PyrComponent choose_component(const DevScene& S, Rng& rng, uint32_t first, uint32_t count) { return S.components[first + rng_choose(rng, count)]; }
+
+// MaterialComponent::get_probability, materials/mod.rs:238-248; `dispersed`: the probability program reads the wavelength.
+// DEFER (the interpreter builds of the stage scheduler, which run the program beside the colour program: contribute_pending /
+// tape_pending): `value` is the compensation alone and `program` what is still to evaluate, the probability being its value * `value`.
+struct ComponentProbability {
+    float value;
+    int program;
+    bool dispersed;
+};
+template <bool DEFER, bool INTERP = false>
+DEV ComponentProbability get_probability(const DevScene& S, const PyrComponent& comp, const VmInput& in) {
+    ComponentProbability r{comp.selection_compensation, -1, false};
+    if (comp.probability_program >= 0) {
+        if constexpr (DEFER)
+            r.program = comp.probability_program;
+        else
+            r.value = run_program<INTERP>(S, (uint32_t)comp.probability_program, in) * comp.selection_compensation;
+        r.dispersed = S.programs[comp.probability_program].reads_wavelength != 0;
+    }
+    return r;
+}
+
+// What an unblocked light sample shows (tracer.rs:387-420): a lamp's own colour seen against the ray, or choose_emissive of a
+// physical light's material at the sampled point. `in`: the hero wavelength, the sampled point's normal, texture coordinates and the direction to it.
+struct LightEmission {
+    uint32_t color;
+    f3 normal;
+    ComponentProbability probability;
+};
+template <bool DEFER>
+DEV LightEmission light_emission(const DevScene& S, Rng& rng, bool physical, uint32_t material, uint32_t color, const VmInput& in) {
+    LightEmission e{color, -in.incident, {1.0f, -1, false}};
+    if (physical) {
+        const PyrMaterial lm = S.materials[material];
+        const PyrComponent ec = choose_component(S, rng, lm.first_emissive, lm.num_emissive);
+        e.probability = get_probability<DEFER>(S, ec, in);
+        e.color = ec.color_program;
+        e.normal = in.normal;
+    }
+    return e;
+}
+
+// SurfaceBsdfType::scatter, materials/mod.rs:344-359. `probability` is the scattering's own; has_brdf: the lambertian BRDF applies.
+struct Scatter {
+    f3 out;
+    float probability;
+    bool dispersed, has_brdf;
+};
+DEV Scatter scatter(const PyrComponent& comp, f3 ray_d, f3 normal, float hero_wavelength, Rng& rng) {
+    Scatter s{mk(0, 0, 0), 1.0f, false, false};
+    if (comp.bsdf == PYR_BSDF_DIFFUSE) { // diffuse.rs:8-25
+        s.out = sample_hemisphere(rng, face_forward(normal, ray_d));
+        s.has_brdf = true;
+    } else if (comp.bsdf == PYR_BSDF_MIRROR) { // mirror.rs:5-21
+        f3 n = face_forward(normal, ray_d);
+        float perp = dot(ray_d, n) * 2.0f;
+        s.out = ray_d - n * perp;
+    } else { // refractive.rs:6-37
+        s.dispersed = comp.dispersion != 0.0f || comp.env_dispersion != 0.0f;
+        float ior = comp.ior, env_ior = comp.env_ior;
+        if (s.dispersed) {
+            float wl = hero_wavelength * 0.001f;
+            ior = comp.ior + comp.dispersion / (wl * wl);
+            env_ior = comp.env_ior + comp.env_dispersion / (wl * wl);
+        }
+        refract(ior, env_ior, ray_d, normal, rng, s.out, s.probability);
+    }
+    return s;
+}
+
+// The next-event estimation gate (tracer.rs:257-280) with pick_lamp (world.rs:301-305): true when trace_direct (tracer.rs:347-442)
+// is to run for the bounce, towards `lamp`.
+DEV bool next_event_gate(const DevScene& S, const RenderLaunch& L, Path& p, bool has_brdf, uint32_t& lamp) {
+    if (p.events < 2) {
+        p.sample_light = !has_brdf || L.light_samples == 0;
+        if (has_brdf) {
+            p.events += 1;
+            if (S.num_lamps > 0) {
+                lamp = rng_range_usize(p.rng, S.num_lamps);
+                return true;
+            }
+        }
+    } else {
+        p.sample_light = true;
+    }
+    return false;
+}
+
+// A light sample's acceptance (tracer.rs:365-386). 1 / (samples * 2 pi * p_lamp), tracer.rs:365: a function of the launch alone.
+DEV float light_sample_probability(const DevScene& S, const RenderLaunch& L) {
+    const float lamp_probability = 1.0f / (float)S.num_lamps;
+    return 1.0f / ((float)L.light_samples * 2.0f * PI_F * lamp_probability);
+}
+// false: the sample lies behind the face-forwarded normal `nff` and casts no shadow ray
+DEV bool light_sample_faces(f3 nff, const LampSample& ls) {
+    const float cos_out = fmaxf(dot(nff, ls.direction), 0.0f);
+    return cos_out > 0.0f;
+}
+// where its shadow ray ends: short of the light, or nowhere (a directional lamp)
+DEV float shadow_limit(const LampSample& ls) { return ls.sq_distance >= 0.0f ? ls.sq_distance - DIST_EPSILON : PYR_INF; }
+// what the sample contributes with, apart from its material's probability: weight * probability * the lambertian BRDF (diffuse.rs:27-29)
+DEV float light_sample_scale(const LampSample& ls, float probability, f3 nff) { return ls.weight * probability * (2.0f * fabsf(dot(ls.direction, nff))); }
+
+// `contribute` (renderer/algorithm.rs:14-100) applied online to the hero wavelength and, if `companions`, to the others.
+// ADD: brightness += program(wl) * probability * reflectance -- emission, the sky, an unblocked light sample (:30-46, :65-90)
+DEV void contribute_add(const DevScene& S, Path& p, Spectral& spec, uint32_t n_add, uint32_t program, VmInput in, float probability, bool companions) {
+    const Prepared q_prog = prepare_program<false>(S, program);
+    p.bright += eval_prepared<false>(S, q_prog, in) * probability * p.refl;
+    if (companions)
+        for (uint32_t k = 0; k < n_add; ++k) {
+            in.wavelength = spec.wl(k);
+            spec.bright(k) += eval_prepared<false>(S, q_prog, in) * probability * spec.refl(k);
+        }
+}
+// MUL: reflectance *= program(wl) * probability -- a bounce, first half (:48-63)
+DEV void contribute_mul(const DevScene& S, Path& p, Spectral& spec, uint32_t n_add, uint32_t program, VmInput in, float probability, bool companions) {
+    const Prepared q_prog = prepare_program<false>(S, program);
+    p.refl *= eval_prepared<false>(S, q_prog, in) * probability;
+    if (companions)
+        for (uint32_t k = 0; k < n_add; ++k) {
+            in.wavelength = spec.wl(k);
+            spec.refl(k) *= eval_prepared<false>(S, q_prog, in) * probability;
+        }
+}
+// a bounce, second half (:92-98): reflectance *= brdf, 2|n.out| for diffuse (tracer.rs:175-183), on the hero and its companions
+DEV float brdf_factor(f3 out, f3 normal) { return 2.0f * fabsf(dot(out, normal)); }
+DEV void contribute_scale(Path& p, Spectral& spec, uint32_t n_add, float s) {
+    p.refl *= s;
+    if (p.use_additional)
+        for (uint32_t k = 0; k < n_add; ++k) spec.refl(k) *= s;
+}
+
 // Developer build only (-DPYR_PHASE_PROFILE, tools/phase_profile.py): lap timers of the synchronous walk's sections.
 struct SyncProf {
     unsigned long long section[8] = {0, 0, 0, 0, 0, 0, 0, 0}, last = 0;
@@ -1475,25 +1639,7 @@ DEV bool bounce_step(const DevScene& S, const RenderLaunch& L, const SceneView& 
     SYNC_PRIO(SYNC_PRIO_S);
     SLAP(sp, 1);
     if (!found) {
-        // miss: first matching directional lamp (trace_directional, tracer.rs:444-459) or the sky; dispersed = false
-        uint32_t color = S.sky_program;
-        if (p.sample_light) {
-            for (uint32_t i = 0; i < S.num_lamps; ++i) {
-                const DevLamp& l = S.lamps[i];
-                if (l.kind == PYR_LAMP_DIRECTIONAL && dot(ld3(l.v), ray_d) >= l.width) {
-                    color = l.color_program;
-                    break;
-                }
-            }
-        }
-        const Prepared q_prog = prepare_program<false>(S, color);
-        VmInput in{p.wl, -ray_d, ray_d};
-        p.bright += eval_prepared<false>(S, q_prog, in) * 1.0f * p.refl;
-        if (p.use_additional)
-            for (uint32_t k = 0; k < n_add; ++k) {
-                in.wavelength = spec.wl(k);
-                spec.bright(k) += eval_prepared<false>(S, q_prog, in) * 1.0f * spec.refl(k);
-            }
+        contribute_add(S, p, spec, n_add, miss_program(S, p.sample_light, ray_d), VmInput{p.wl, -ray_d, ray_d}, 1.0f, p.use_additional);
         return true;
     }
     if (COUNT) cnt.shaded_hits++;
@@ -1501,45 +1647,33 @@ DEV bool bounce_step(const DevScene& S, const RenderLaunch& L, const SceneView& 
     uint32_t material_id;
     surface_at(S, hit, ray_o, ray_d, position, normal, material_id);
     const PyrMaterial material = S.materials[material_id];
-    const uint32_t pick = rng_choose(p.rng, material.num_components); // choose_component, materials/mod.rs:48-54
-    const PyrComponent comp = S.components[material.first_component + pick];
-    // get_probability, materials/mod.rs:238-248
-    float component_probability = comp.selection_compensation;
-    bool normal_dispersed = false;
-    if (comp.probability_program >= 0) {
-        VmInput pin{p.wl, normal, ray_d};
-        component_probability = run_program<false>(S, (uint32_t)comp.probability_program, pin) * comp.selection_compensation;
-        normal_dispersed = S.programs[comp.probability_program].reads_wavelength != 0;
-    }
+    const PyrComponent comp = choose_component(S, p.rng, material.first_component, material.num_components);
+    const ComponentProbability component = get_probability<false>(S, comp, VmInput{p.wl, normal, ray_d});
+    const float component_probability = component.value; // read out at once (see the path's rules)
+    const bool normal_dispersed = component.dispersed;
 
     if (comp.bsdf == PYR_BSDF_EMISSIVE) { // Scattering::Emitted, tracer.rs:303-318
         if (p.sample_light) {
             p.use_additional = !normal_dispersed && p.use_additional;
-            const Prepared q_prog = prepare_program<false>(S, comp.color_program);
-            VmInput in{p.wl, normal, ray_d};
-            p.bright += eval_prepared<false>(S, q_prog, in) * component_probability * p.refl;
-            if (p.use_additional)
-                for (uint32_t k = 0; k < n_add; ++k) {
-                    in.wavelength = spec.wl(k);
-                    spec.bright(k) += eval_prepared<false>(S, q_prog, in) * component_probability * spec.refl(k);
-                }
+            contribute_add(S, p, spec, n_add, comp.color_program, VmInput{p.wl, normal, ray_d}, component_probability, p.use_additional);
         }
         return true;
     }
 
-    // SurfaceBsdfType::scatter, materials/mod.rs:344-359
+    // SurfaceBsdfType::scatter once more, the twin of scatter() among the path's rules -- the one rule this walk states for itself:
+    // called from here, however it hands its results over, scatter() leaves this kernel with 67 more v_readlane (139 -> 206 in
+    // render_kernel<false, true, false>, the C1 / C2 kernel; tests/test_kernel_isa.py). A change to one is a change to both.
     f3 out_direction;
     float scatter_probability = 1.0f;
     bool dispersed = false, has_brdf = false;
-    if (comp.bsdf == PYR_BSDF_DIFFUSE) { // diffuse.rs:8-25
-        f3 n = dot(ray_d, normal) < 0.0f ? normal : -normal;
-        out_direction = sample_hemisphere(p.rng, n);
+    if (comp.bsdf == PYR_BSDF_DIFFUSE) {
+        out_direction = sample_hemisphere(p.rng, face_forward(normal, ray_d));
         has_brdf = true;
-    } else if (comp.bsdf == PYR_BSDF_MIRROR) { // mirror.rs:5-21
-        f3 n = dot(ray_d, normal) < 0.0f ? normal : -normal;
+    } else if (comp.bsdf == PYR_BSDF_MIRROR) {
+        f3 n = face_forward(normal, ray_d);
         float perp = dot(ray_d, n) * 2.0f;
         out_direction = ray_d - n * perp;
-    } else { // refractive.rs:6-37
+    } else {
         dispersed = comp.dispersion != 0.0f || comp.env_dispersion != 0.0f;
         float ior = comp.ior, env_ior = comp.env_ior;
         if (dispersed) {
@@ -1549,120 +1683,72 @@ DEV bool bounce_step(const DevScene& S, const RenderLaunch& L, const SceneView& 
         }
         refract(ior, env_ior, ray_d, normal, p.rng, out_direction, scatter_probability);
     }
-
-    // contribute, non-emission bounce, first half (algorithm.rs:48-63): reflectance *= color * probability
-    const float bounce_probability = scatter_probability * component_probability; // tracer.rs:296
-    p.use_additional = !(dispersed || normal_dispersed) && p.use_additional;       // simple.rs:122-123, tracer.rs:290
-    {
-        const Prepared q_prog = prepare_program<false>(S, comp.color_program);
-        VmInput in{p.wl, normal, ray_d};
-        p.refl *= eval_prepared<false>(S, q_prog, in) * bounce_probability;
-        if (p.use_additional)
-            for (uint32_t k = 0; k < n_add; ++k) {
-                in.wavelength = spec.wl(k);
-                spec.refl(k) *= eval_prepared<false>(S, q_prog, in) * bounce_probability;
-            }
-    }
+    p.use_additional = !(dispersed || normal_dispersed) && p.use_additional; // simple.rs:122-123, tracer.rs:290
+    contribute_mul(S, p, spec, n_add, comp.color_program, VmInput{p.wl, normal, ray_d}, scatter_probability * component_probability, p.use_additional); // tracer.rs:296
 
     SLAP(sp, 2);
     SYNC_PRIO(SYNC_PRIO_N);
-    // next-event estimation gate, tracer.rs:257-280
-    if (p.events < 2) {
-        p.sample_light = !has_brdf || L.light_samples == 0;
-        if (has_brdf) {
-            p.events += 1;
-            if (S.num_lamps > 0) { // trace_direct, tracer.rs:347-442
-                const uint32_t lamp_index = rng_range_usize(p.rng, S.num_lamps); // pick_lamp, world.rs:301-305
-                const DevLamp& lamp = S.lamps[lamp_index];
-                const float lamp_probability = 1.0f / (float)S.num_lamps;
-                const f3 nff = dot(ray_d, normal) < 0.0f ? normal : -normal;
-                const float probability = 1.0f / ((float)L.light_samples * 2.0f * PI_F * lamp_probability);
-                // Companion wavelengths of the unblocked light samples. Without the interpreter a colour program is a function
-                // of the wavelength alone (a constant or spectrum [* c]), so consecutive samples that show the same program
-                // need its value at each companion wavelength only once: their probabilities are parked (up to four) and the
-                // companions are brought up to date in one pass -- each brightness still receives the same addends in the
-                // same order as in `contribute` (algorithm.rs:65-90), so the result is bit-identical, at a quarter of the
-                // spectrum look-ups.
-                float parked0 = 0.0f, parked1 = 0.0f, parked2 = 0.0f, parked3 = 0.0f;
-                uint32_t parked = 0, parked_color = 0;
-                auto flush_parked = [&]() {
-                    if (parked == 0) return;
-                    const Prepared q_prog = prepare_program<false>(S, parked_color);
-                    VmInput in{0.0f, mk(0, 0, 0), mk(0, 0, 0)};
-                    for (uint32_t k = 0; k < n_add; ++k) {
-                        in.wavelength = spec.wl(k);
-                        const float color = eval_prepared<false>(S, q_prog, in);
-                        const float refl = spec.refl(k);
-                        float b = spec.bright(k);
-                        b += color * parked0 * refl;
-                        if (parked > 1) b += color * parked1 * refl;
-                        if (parked > 2) b += color * parked2 * refl;
-                        if (parked > 3) b += color * parked3 * refl;
-                        spec.bright(k) = b;
-                    }
-                    parked = 0;
-                };
-                for (uint32_t ls_i = 0; ls_i < L.light_samples; ++ls_i) {
-                    const LampSample ls = lamp_sample(lamp, p.rng, position);
-                    const float cos_out = fmaxf(dot(nff, ls.direction), 0.0f);
-                    if (!(cos_out > 0.0f)) continue;
-                    if (COUNT) cnt.shadow_rays++;
-                    const float limit = ls.sq_distance >= 0.0f ? ls.sq_distance - DIST_EPSILON : PYR_INF;
-                    Hit shadow_hit;
-                    SLAP(sp, 3);
-                    SYNC_PRIO(SYNC_PRIO_T);
-                    const bool is_blocked = traverse<COUNT, true>(S, view.nodes, view.prims, position, ls.direction, limit, shadow_hit, stack, cnt);
-                    SYNC_PRIO(SYNC_PRIO_N);
-                    SLAP(sp, 4);
-                    if (is_blocked) continue;
-                    uint32_t l_color = ls.color;
-                    float material_probability = 1.0f;
-                    bool l_dispersed = false;
-                    f3 target_normal = -ls.direction;
-                    if (ls.physical) {
-                        const PyrMaterial lm = S.materials[ls.material];
-                        const uint32_t e_pick = rng_choose(p.rng, lm.num_emissive); // choose_emissive, materials/mod.rs:56-62
-                        const PyrComponent ec = S.components[lm.first_emissive + e_pick];
-                        material_probability = ec.selection_compensation;
-                        if (ec.probability_program >= 0) {
-                            VmInput pin{p.wl, ls.normal, ls.direction};
-                            material_probability = run_program<false>(S, (uint32_t)ec.probability_program, pin) * ec.selection_compensation;
-                            l_dispersed = S.programs[ec.probability_program].reads_wavelength != 0;
-                        }
-                        l_color = ec.color_program;
-                        target_normal = ls.normal;
-                    }
-                    const float scale = ls.weight * probability * (2.0f * fabsf(dot(ls.direction, nff))); // lambertian, diffuse.rs:27-29
-                    const float l_probability = scale * material_probability;
-                    // contribute, direct light (algorithm.rs:65-90)
-                    const Prepared q_prog = prepare_program<false>(S, l_color);
-                    VmInput in{p.wl, target_normal, ls.direction};
-                    p.bright += eval_prepared<false>(S, q_prog, in) * l_probability * p.refl;
-                    if (p.use_additional && !l_dispersed) {
-                        if (parked != 0 && (parked == 4 || parked_color != l_color)) flush_parked();
-                        parked_color = l_color;
-                        if (parked == 0) parked0 = l_probability;
-                        if (parked == 1) parked1 = l_probability;
-                        if (parked == 2) parked2 = l_probability;
-                        if (parked == 3) parked3 = l_probability;
-                        parked++;
-                    }
-                }
-                flush_parked();
-                SLAP(sp, 5);
+    uint32_t lamp_index;
+    if (next_event_gate(S, L, p, has_brdf, lamp_index)) { // trace_direct, tracer.rs:347-442
+        const DevLamp& lamp = S.lamps[lamp_index];
+        const f3 nff = face_forward(normal, ray_d);
+        const float probability = light_sample_probability(S, L);
+        // Companion wavelengths of the unblocked light samples. Without the interpreter a colour program is a function
+        // of the wavelength alone (a constant or spectrum [* c]), so consecutive samples that show the same program
+        // need its value at each companion wavelength only once: their probabilities are parked (up to four) and the
+        // companions are brought up to date in one pass -- each brightness still receives the same addends in the
+        // same order as in `contribute` (algorithm.rs:65-90), so the result is bit-identical, at a quarter of the
+        // spectrum look-ups.
+        float parked0 = 0.0f, parked1 = 0.0f, parked2 = 0.0f, parked3 = 0.0f;
+        uint32_t parked = 0, parked_color = 0;
+        auto flush_parked = [&]() {
+            if (parked == 0) return;
+            const Prepared q_prog = prepare_program<false>(S, parked_color);
+            VmInput in{0.0f, mk(0, 0, 0), mk(0, 0, 0)};
+            for (uint32_t k = 0; k < n_add; ++k) {
+                in.wavelength = spec.wl(k);
+                const float color = eval_prepared<false>(S, q_prog, in);
+                const float refl = spec.refl(k);
+                float b = spec.bright(k);
+                b += color * parked0 * refl;
+                if (parked > 1) b += color * parked1 * refl;
+                if (parked > 2) b += color * parked2 * refl;
+                if (parked > 3) b += color * parked3 * refl;
+                spec.bright(k) = b;
+            }
+            parked = 0;
+        };
+        for (uint32_t ls_i = 0; ls_i < L.light_samples; ++ls_i) {
+            const LampSample ls = lamp_sample(lamp, p.rng, position);
+            if (!light_sample_faces(nff, ls)) continue;
+            if (COUNT) cnt.shadow_rays++;
+            const float limit = shadow_limit(ls);
+            Hit shadow_hit;
+            SLAP(sp, 3);
+            SYNC_PRIO(SYNC_PRIO_T);
+            const bool is_blocked = traverse<COUNT, true>(S, view.nodes, view.prims, position, ls.direction, limit, shadow_hit, stack, cnt);
+            SYNC_PRIO(SYNC_PRIO_N);
+            SLAP(sp, 4);
+            if (is_blocked) continue;
+            const LightEmission e = light_emission<false>(S, p.rng, ls.physical, ls.material, ls.color, VmInput{p.wl, ls.normal, ls.direction});
+            const float l_probability = light_sample_scale(ls, probability, nff) * e.probability.value;
+            // the hero online; the companions parked (above)
+            contribute_add(S, p, spec, n_add, e.color, VmInput{p.wl, e.normal, ls.direction}, l_probability, false);
+            if (p.use_additional && !e.probability.dispersed) {
+                if (parked != 0 && (parked == 4 || parked_color != e.color)) flush_parked();
+                parked_color = e.color;
+                if (parked == 0) parked0 = l_probability;
+                if (parked == 1) parked1 = l_probability;
+                if (parked == 2) parked2 = l_probability;
+                if (parked == 3) parked3 = l_probability;
+                parked++;
             }
         }
-    } else {
-        p.sample_light = true;
+        flush_parked();
+        SLAP(sp, 5);
     }
 
-    // contribute, second half (algorithm.rs:92-98): reflectance *= brdf (2|n.out| for diffuse, tracer.rs:175-183)
-    if (has_brdf) {
-        const float brdf = 2.0f * fabsf(dot(out_direction, normal));
-        p.refl *= brdf;
-        if (p.use_additional)
-            for (uint32_t k = 0; k < n_add; ++k) spec.refl(k) *= brdf;
-    }
+    if (has_brdf) contribute_scale(p, spec, n_add, brdf_factor(out_direction, normal));
     p.o = position;
     p.d = out_direction;
     SLAP(sp, 6);
@@ -2317,11 +2403,6 @@ struct Walker {
     DEV f3 b_nff() const { return b_flip ? -b_normal : b_normal; }
     bool b_has_brdf = false;
     uint32_t nee_lamp = 0, nee_i = 0;
-    // 1 / (samples * 2 pi * p_lamp), tracer.rs:365: a function of the launch alone, formed where it is used
-    DEV static float nee_probability(const DevScene& S, const RenderLaunch& L) {
-        const float lamp_probability = 1.0f / (float)S.num_lamps;
-        return 1.0f / ((float)L.light_samples * 2.0f * PI_F * lamp_probability);
-    }
     // the light sample whose shadow ray is in flight
     bool ls_pending = false, ls_physical = false;
     uint32_t ls_material = 0, ls_color = 0;
@@ -2400,9 +2481,7 @@ struct Walker {
                 c_kind = CONTRIB_NONE;
             }
             if (c_has_scale) {
-                p.refl *= c_scale;
-                if (p.use_additional)
-                    for (uint32_t k = 0; k < n_add; ++k) spec.refl(k) *= c_scale;
+                contribute_scale(p, spec, n_add, c_scale);
                 c_has_scale = false;
             }
         }
@@ -2482,17 +2561,13 @@ struct Walker {
     DEV void finish_bounce(const DevScene& S, const RenderLaunch& L, Spectral& spec, Counters& cnt) {
         const uint32_t n_add = L.spectrum_samples - 1;
         if (b_has_brdf) {
-            const float brdf = 2.0f * fabsf(dot(b_out, b_normal));
-            if constexpr (TAPE && !INTERP) {
+            const float brdf = brdf_factor(b_out, b_normal);
+            if constexpr (TAPE && !INTERP)
                 tape_push(L, TAPE_SCALE, 0u, brdf);
-            } else if constexpr (INTERP) {
+            else if constexpr (INTERP)
                 c_scale = brdf, c_has_scale = true; // behind this turn's contribution (contribute_pending)
-            } else {
-                p.refl *= brdf;
-                if (p.use_additional) {
-                    for (uint32_t k = 0; k < n_add; ++k) spec.refl(k) *= brdf;
-                }
-            }
+            else
+                contribute_scale(p, spec, n_add, brdf);
         }
         p.o = b_position;
         p.d = b_out;
@@ -2629,30 +2704,13 @@ struct Walker {
         const uint32_t n_add = L.spectrum_samples - 1;
         const f3 ray_o = t.o, ray_d = t.d;
         if (t.shape == PYR_HIT_NONE) {
-            uint32_t color = S.sky_program;
-            if (p.sample_light) {
-                for (uint32_t i = 0; i < S.num_lamps; ++i) {
-                    const DevLamp& l = S.lamps[i];
-                    if (l.kind == PYR_LAMP_DIRECTIONAL && dot(ld3(l.v), ray_d) >= l.width) {
-                        color = l.color_program;
-                        break;
-                    }
-                }
-            }
-            if constexpr (TAPE && !INTERP) {
+            const uint32_t color = miss_program(S, p.sample_light, ray_d);
+            if constexpr (TAPE && !INTERP)
                 tape_push(L, TAPE_ADD, color, 1.0f);
-            } else if constexpr (INTERP) {
+            else if constexpr (INTERP)
                 contribution(CONTRIB_ADD, color, -1, 1.0f, false, 1.0f, p.use_additional, -ray_d, ray_d, 0.0f, 0.0f);
-            } else {
-                const Prepared q_prog = prepare_program<INTERP>(S, color);
-                VmInput in{p.wl, -ray_d, ray_d};
-                p.bright += eval_prepared<INTERP>(S, q_prog, in) * 1.0f * p.refl;
-                if (p.use_additional)
-                    for (uint32_t k = 0; k < n_add; ++k) {
-                        in.wavelength = spec.wl(k);
-                        spec.bright(k) += eval_prepared<INTERP>(S, q_prog, in) * 1.0f * spec.refl(k);
-                    }
-            }
+            else
+                contribute_add(S, p, spec, n_add, color, VmInput{p.wl, -ray_d, ray_d}, 1.0f, p.use_additional);
             stage = ST_EXPOSE;
             return;
         }
@@ -2666,104 +2724,46 @@ struct Walker {
         else
             surface_at(S, hit, ray_o, ray_d, position, normal, material_id);
         const PyrMaterial material = S.materials[material_id];
-        const uint32_t pick = rng_choose(p.rng, material.num_components);
-        const PyrComponent comp = S.components[material.first_component + pick];
-        float component_probability = comp.selection_compensation;
-        bool normal_dispersed = false;
-        int deferred_probability = -1; // interpreter builds evaluate it with the colour program (contribute_pending)
-        if (comp.probability_program >= 0) {
-            if constexpr (INTERP) {
-                deferred_probability = comp.probability_program;
-            } else {
-                VmInput pin{p.wl, normal, ray_d, tx, ty};
-                component_probability = run_program<INTERP>(S, (uint32_t)comp.probability_program, pin) * comp.selection_compensation;
-            }
-            normal_dispersed = S.programs[comp.probability_program].reads_wavelength != 0;
-        }
+        const PyrComponent comp = choose_component(S, p.rng, material.first_component, material.num_components);
+        // interpreter builds: the probability program is evaluated with the colour program (contribute_pending / tape_pending)
+        const ComponentProbability component = get_probability<INTERP>(S, comp, VmInput{p.wl, normal, ray_d, tx, ty});
         if (comp.bsdf == PYR_BSDF_EMISSIVE) {
             if (p.sample_light) {
-                p.use_additional = !normal_dispersed && p.use_additional;
-                if constexpr (TAPE && !INTERP) {
-                    tape_push(L, TAPE_ADD, comp.color_program, component_probability);
-                } else if constexpr (INTERP) {
-                    contribution(CONTRIB_ADD, comp.color_program, deferred_probability, comp.selection_compensation, false, 1.0f, p.use_additional, normal, ray_d, tx, ty);
-                } else {
-                    const Prepared q_prog = prepare_program<INTERP>(S, comp.color_program);
-                    VmInput in{p.wl, normal, ray_d, tx, ty};
-                    p.bright += eval_prepared<INTERP>(S, q_prog, in) * component_probability * p.refl;
-                    if (p.use_additional)
-                        for (uint32_t k = 0; k < n_add; ++k) {
-                            in.wavelength = spec.wl(k);
-                            spec.bright(k) += eval_prepared<INTERP>(S, q_prog, in) * component_probability * spec.refl(k);
-                        }
-                }
+                p.use_additional = !component.dispersed && p.use_additional;
+                if constexpr (TAPE && !INTERP)
+                    tape_push(L, TAPE_ADD, comp.color_program, component.value);
+                else if constexpr (INTERP)
+                    contribution(CONTRIB_ADD, comp.color_program, component.program, component.value, false, 1.0f, p.use_additional, normal, ray_d, tx, ty);
+                else
+                    contribute_add(S, p, spec, n_add, comp.color_program, VmInput{p.wl, normal, ray_d, tx, ty}, component.value, p.use_additional);
             }
             stage = ST_EXPOSE;
             return;
         }
-        f3 out_direction;
-        float scatter_probability = 1.0f;
-        bool dispersed = false, has_brdf = false;
-        if (comp.bsdf == PYR_BSDF_DIFFUSE) {
-            f3 n = dot(ray_d, normal) < 0.0f ? normal : -normal;
-            out_direction = sample_hemisphere(p.rng, n);
-            has_brdf = true;
-        } else if (comp.bsdf == PYR_BSDF_MIRROR) {
-            f3 n = dot(ray_d, normal) < 0.0f ? normal : -normal;
-            float perp = dot(ray_d, n) * 2.0f;
-            out_direction = ray_d - n * perp;
-        } else {
-            dispersed = comp.dispersion != 0.0f || comp.env_dispersion != 0.0f;
-            float ior = comp.ior, env_ior = comp.env_ior;
-            if (dispersed) {
-                float wl = p.wl * 0.001f;
-                ior = comp.ior + comp.dispersion / (wl * wl);
-                env_ior = comp.env_ior + comp.env_dispersion / (wl * wl);
-            }
-            refract(ior, env_ior, ray_d, normal, p.rng, out_direction, scatter_probability);
-        }
-        const float bounce_probability = scatter_probability * component_probability;
-        p.use_additional = !(dispersed || normal_dispersed) && p.use_additional;
-        if constexpr (TAPE && !INTERP) {
+        const Scatter sc = scatter(comp, ray_d, normal, p.wl, p.rng);
+        const f3 out_direction = sc.out; // read out at once (see the path's rules)
+        const float scatter_probability = sc.probability;
+        const bool dispersed = sc.dispersed, has_brdf = sc.has_brdf;
+        const float bounce_probability = scatter_probability * component.value;
+        p.use_additional = !(dispersed || component.dispersed) && p.use_additional;
+        if constexpr (TAPE && !INTERP)
             tape_push(L, TAPE_MUL, comp.color_program, bounce_probability);
-        } else if constexpr (INTERP) {
-            // bounce_probability = scatter_probability * (probability program's value * compensation), formed where the value is
-            contribution(CONTRIB_MUL, comp.color_program, deferred_probability, comp.selection_compensation, true, scatter_probability, p.use_additional, normal, ray_d, tx,
-                         ty);
-        } else {
-            const Prepared q_prog = prepare_program<INTERP>(S, comp.color_program);
-            VmInput in{p.wl, normal, ray_d, tx, ty};
-            p.refl *= eval_prepared<INTERP>(S, q_prog, in) * bounce_probability;
-            if (p.use_additional)
-                for (uint32_t k = 0; k < n_add; ++k) {
-                    in.wavelength = spec.wl(k);
-                    spec.refl(k) *= eval_prepared<INTERP>(S, q_prog, in) * bounce_probability;
-                }
-        }
+        else if constexpr (INTERP) // bounce_probability = scatter's * (probability program's value * compensation), formed where the value is
+            contribution(CONTRIB_MUL, comp.color_program, component.program, component.value, true, scatter_probability, p.use_additional, normal, ray_d, tx, ty);
+        else
+            contribute_mul(S, p, spec, n_add, comp.color_program, VmInput{p.wl, normal, ray_d, tx, ty}, bounce_probability, p.use_additional);
         b_position = position;
         b_normal = normal;
         b_out = out_direction;
         b_has_brdf = has_brdf;
-        bool nee = false;
-        if (p.events < 2) { // tracer.rs:257-280
-            p.sample_light = !has_brdf || L.light_samples == 0;
-            if (has_brdf) {
-                p.events += 1;
-                if (S.num_lamps > 0) {
-                    nee_lamp = rng_range_usize(p.rng, S.num_lamps); // pick_lamp, world.rs:301-305
-                    b_flip = !(dot(ray_d, normal) < 0.0f);
-                    nee_i = 0;
-                    ls_pending = false;
-                    nee = true;
-                }
-            }
-        } else {
-            p.sample_light = true;
-        }
-        if (nee)
+        if (next_event_gate(S, L, p, has_brdf, nee_lamp)) {
+            b_flip = !(dot(ray_d, normal) < 0.0f);
+            nee_i = 0;
+            ls_pending = false;
             stage = ST_NEE;
-        else
+        } else {
             finish_bounce(S, L, spec, cnt);
+        }
     }
 
     // NEE: trace_direct (tracer.rs:347-442), one light sample per visit: account for the shadow ray that came back, then
@@ -2774,56 +2774,25 @@ struct Walker {
         if (ls_pending) {
             ls_pending = false;
             if (!t.blocked) {
-                uint32_t l_color = ls_color;
-                float material_probability = 1.0f;
-                bool l_dispersed = false;
-                f3 target_normal = -t.d;
-                int deferred_probability = -1; // interpreter builds evaluate it with the colour program (contribute_pending)
-                if (ls_physical) {
-                    const PyrMaterial lm = S.materials[ls_material];
-                    const uint32_t e_pick = rng_choose(p.rng, lm.num_emissive);
-                    const PyrComponent ec = S.components[lm.first_emissive + e_pick];
-                    material_probability = ec.selection_compensation;
-                    if (ec.probability_program >= 0) {
-                        if constexpr (INTERP) {
-                            deferred_probability = ec.probability_program;
-                        } else {
-                            VmInput pin{p.wl, ls_normal, t.d, ls_tx, ls_ty};
-                            material_probability = run_program<INTERP>(S, (uint32_t)ec.probability_program, pin) * ec.selection_compensation;
-                        }
-                        l_dispersed = S.programs[ec.probability_program].reads_wavelength != 0;
-                    }
-                    l_color = ec.color_program;
-                    target_normal = ls_normal;
-                }
-                const float l_probability = ls_scale * material_probability;
-                if constexpr (TAPE && !INTERP) {
-                    tape_push(L, TAPE_ADD, l_color, l_probability, l_dispersed);
-                } else if constexpr (INTERP) {
-                    // l_probability = ls_scale * (probability program's value * compensation); the material's inputs are the light's
-                    contribution(CONTRIB_ADD, l_color, deferred_probability, material_probability, true, ls_scale, p.use_additional && !l_dispersed, target_normal, t.d,
-                                 ls_physical ? ls_tx : 0.0f, ls_physical ? ls_ty : 0.0f);
-                } else {
-                    const Prepared q_prog = prepare_program<INTERP>(S, l_color);
-                    VmInput in{p.wl, target_normal, t.d, ls_physical ? ls_tx : 0.0f, ls_physical ? ls_ty : 0.0f};
-                    p.bright += eval_prepared<INTERP>(S, q_prog, in) * l_probability * p.refl;
-                    if (p.use_additional && !l_dispersed)
-                        for (uint32_t k = 0; k < n_add; ++k) {
-                            in.wavelength = spec.wl(k);
-                            spec.bright(k) += eval_prepared<INTERP>(S, q_prog, in) * l_probability * spec.refl(k);
-                        }
-                }
+                const LightEmission e = light_emission<INTERP>(S, p.rng, ls_physical, ls_material, ls_color, VmInput{p.wl, ls_normal, t.d, ls_tx, ls_ty});
+                const float l_probability = ls_scale * e.probability.value;
+                const bool companions = p.use_additional && !e.probability.dispersed;
+                const float tx = ls_physical ? ls_tx : 0.0f, ty = ls_physical ? ls_ty : 0.0f; // the material's inputs are the light's
+                if constexpr (TAPE && !INTERP)
+                    tape_push(L, TAPE_ADD, e.color, l_probability, e.probability.dispersed);
+                else if constexpr (INTERP) // l_probability = ls_scale * (probability program's value * compensation)
+                    contribution(CONTRIB_ADD, e.color, e.probability.program, e.probability.value, true, ls_scale, companions, e.normal, t.d, tx, ty);
+                else
+                    contribute_add(S, p, spec, n_add, e.color, VmInput{p.wl, e.normal, t.d, tx, ty}, l_probability, companions);
             }
         }
         const DevLamp& lamp = S.lamps[nee_lamp];
         while (nee_i < L.light_samples) {
             const LampSample ls = lamp_sample<INTERP>(lamp, p.rng, b_position);
             nee_i++;
-            const float cos_out = fmaxf(dot(b_nff(), ls.direction), 0.0f);
-            if (!(cos_out > 0.0f)) continue;
+            if (!light_sample_faces(b_nff(), ls)) continue;
             if (COUNT) cnt.shadow_rays++;
-            const float limit = ls.sq_distance >= 0.0f ? ls.sq_distance - DIST_EPSILON : PYR_INF;
-            ls_scale = ls.weight * nee_probability(S, L) * (2.0f * fabsf(dot(ls.direction, b_nff())));
+            ls_scale = light_sample_scale(ls, light_sample_probability(S, L), b_nff());
             ls_physical = ls.physical;
             ls_material = ls.material;
             ls_color = ls.color;
@@ -2831,7 +2800,7 @@ struct Walker {
             ls_tx = ls.tx, ls_ty = ls.ty;
             ls_pending = true;
             // a shadow ray decided by a plane alone comes straight back to this phase
-            stage = trav_begin<COUNT>(S, t, b_position, ls.direction, true, limit, cnt) ? ST_NEE : ST_TRAV;
+            stage = trav_begin<COUNT>(S, t, b_position, ls.direction, true, shadow_limit(ls), cnt) ? ST_NEE : ST_TRAV;
             break;
         }
         if (stage == ST_NEE && !ls_pending) finish_bounce(S, L, spec, cnt);

@@ -90,8 +90,7 @@ DEV void feature_shade(const DevScene& S, const FeatureLaunch& L, const Trav& t,
             for (uint32_t c = 0; c < m.num_components; ++c) {
                 const PyrComponent comp = S.components[m.first_component + c];
                 if (comp.bsdf == PYR_BSDF_EMISSIVE) continue;
-                float probability = comp.selection_compensation; // MaterialComponent::get_probability, materials/mod.rs:238-248
-                if (comp.probability_program >= 0) probability = run_program<INTERP>(S, (uint32_t)comp.probability_program, in) * comp.selection_compensation;
+                const float probability = get_probability<false, INTERP>(S, comp, in).value;
                 sum += probability * run_program<INTERP>(S, comp.color_program, in);
             }
             a = sum / (float)m.num_components;
