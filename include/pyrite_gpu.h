@@ -1021,6 +1021,100 @@ int pyr_image_denoise_device(const float* a_device, const float* b_device, const
 int pyr_session_denoised(PyrSession* session, const PyrDevelopParams* develop_params, const PyrFeatureParams* feature_params,
                          const PyrDenoiseParams* denoise_params, float* out, float* error_out);
 
+/* ---------------------------------------------------------------- motion records and accumulation over frames ----
+ * A scene moves between frames (pyr_scene_update, pyr_scene_pose, pyr_scene_skin) and so may the camera. The motion pass answers,
+ * per pixel: where was the surface point this pixel sees one frame ago, and how far from the previous camera? pyr_image_reproject
+ * is the simplest consumer of the answer, a running mean of linear images that follows the surfaces. The reference has neither.
+ *
+ * The previous frame's geometry. pyr_scene_keep_previous(scene, keep != 0) copies the scene's triangle positions ([n][3][3]) and
+ * its sphere table ([n][4]) AS THEY ARE NOW into a snapshot on the scene's device: 36 bytes a triangle, 16 a sphere, both in the
+ * description's primitive order, the one PyrHit::shape indexes. Blocking. A second call replaces the snapshot, keep == 0 frees
+ * it, pyr_scene_destroy frees it. It survives every later pyr_scene_update / _pose / _skin in either mode: counts never change in
+ * a scene's life and the indices are the description's, so a rebuild does not invalidate it. The call only reads the scene: a
+ * live PyrSession does not forbid it. A NULL scene is PYR_ERR_INVALID_ARGUMENT, before a device is looked for.
+ *
+ * The pass takes one ray per pixel: sub-sample 0 of grid = 1 of the feature pass, the pixel centre through the centre of the lens.
+ * `shape` and `depth` are therefore, bit for bit, those of pyr_render_features with grid = 1. No material program runs.
+ *   All arithmetic is f32 and unfused, one rounding per operation, in the order written; sqrt is the correctly rounded one. The
+ * hit is (t, shape, u, v) = PyrHit of the ray (o, d), P the position the surface data of that hit has: o + d*t on a triangle, the
+ * point the sphere and the plane routine return otherwise. Q, where that material point was:
+ *   triangle i, snapshot rows a, b, c:   e1 = b - a, e2 = c - a, Q = (a + e1*u) + e2*v, per component
+ *   sphere i, now (c, r), snapshot (c', r'):   Q = c' + (P - c) * (r' / r)     -- a sphere's rotation is not tracked
+ *   plane:   Q = P (planes never move);   no snapshot kept:   Q = P for every shape (only the camera moved)
+ * Into the previous camera, W = pyr_camera_world_to_cam(previous_camera), column-major:
+ *   q.x = ((W[0]*Q.x + W[4]*Q.y) + W[8]*Q.z) + W[12], q.y and q.z from rows 1 and 2 alike.
+ * On a miss the direction d is a point at infinity: q.x = (W[0]*d.x + W[4]*d.y) + W[8]*d.z, depth = prev_depth = 0, HIT clear, and
+ * the projection below still applies, so a sky follows a turning camera.
+ *   zc = -q.z;  PYR_MOTION_IN_FRONT iff zc > 0, else prev_x = prev_y = 0 and INSIDE is clear. With vp = previous_camera->view_plane:
+ *   vx = (q.x / zc) * vp,  vy = (-q.y / zc) * vp                       (the inverse of Camera::ray_towards, cameras.rs:78-81)
+ *   m = fmaxf((float)width, (float)height) * 0.5f
+ *   prev_x = vx*m + (float)width*0.5f,  prev_y = vy*m + (float)height*0.5f          (the inverse of to_view_area, cameras.rs:57-68)
+ *   prev_depth = sqrt((q.x*q.x + q.y*q.y) + q.z*q.z) on a hit
+ * focus_distance and aperture of the previous camera are not read. Deterministic: a lane owns a pixel and writes its record with
+ * two 16-byte stores; two calls write the same bytes. One GPU. */
+#define PYR_MOTION_HIT 1u      /* the ray hit something */
+#define PYR_MOTION_IN_FRONT 2u /* the previous point lies in front of the previous camera */
+#define PYR_MOTION_INSIDE 4u   /* and 0 <= prev_x < width, 0 <= prev_y < height */
+typedef struct PyrMotionPixel {
+    float prev_x, prev_y; /* continuous pixel coordinates in the previous frame (pixel centres at +0.5) */
+    float prev_depth;     /* distance from the previous camera's origin to the previous point; 0 on a miss */
+    float depth;          /* PyrHit::distance of this frame's ray; 0 on a miss */
+    uint32_t shape;       /* PyrHit::shape, PYR_HIT_NONE on a miss */
+    uint32_t flags;
+    uint32_t reserved[2]; /* 0 */
+} PyrMotionPixel; /* 32 bytes */
+
+int pyr_scene_keep_previous(PyrScene* scene, int keep);
+/* world_to_cam of a camera, host arithmetic only: the affine inverse of cam_to_world in f64 by cofactors, each entry rounded once
+ * to f32, column-major, last row 0, 0, 0, 1. PYR_ERR_INVALID_ARGUMENT for a null pointer, an entry that is not finite, a last row
+ * that is not exactly 0, 0, 0, 1, or a 3 x 3 determinant that is 0 or not finite. The motion entries call it themselves. */
+int pyr_camera_world_to_cam(const PyrCamera* camera, float out[16]);
+/* HOST pixels_out, height*width records, row-major; blocking. Of `film` only width and height are read. Arguments are checked before
+ * a device is looked for: PYR_ERR_INVALID_ARGUMENT, with the argument named in pyr_last_error, for a null scene, camera,
+ * previous_camera, film or pixels_out, an empty image, 2^32 pixels or more, a previous camera pyr_camera_world_to_cam refuses. */
+int pyr_render_motion(PyrScene* scene, const PyrCamera* camera, const PyrCamera* previous_camera, const PyrFilmDesc* film, PyrMotionPixel* pixels_out);
+/* Same with pixels_device on the scene's device (16-byte aligned, else PYR_ERR_INVALID_ARGUMENT), enqueued on `hip_stream` without
+ * synchronising. The pass uses the scene's working memory: the one-render-at-a-time rule of pyr_render_simple_device holds. */
+int pyr_render_motion_device(PyrScene* scene, const PyrCamera* camera, const PyrCamera* previous_camera, const PyrFilmDesc* film, PyrMotionPixel* pixels_device,
+                             void* hip_stream);
+/* The session's camera as the current one and its image size, on the session's stream after the passes enqueued so far; HOST
+ * pixels_out; blocking. The session's film is not touched, and further passes may follow. */
+int pyr_session_motion(PyrSession* session, const PyrCamera* previous_camera, PyrMotionPixel* pixels_out);
+
+/* Accumulation over frames: out = the running mean of `current` and of the history fetched where each pixel's surface was.
+ * `current`, `history`, `out`: width*height*3 f32 in linear light; `history_count`, `count_out`: one f32 a pixel, the frames the
+ * pixel's mean holds; `motion`: this frame's records, `history_motion`: the records the history's frame was made with. The three
+ * history buffers are all NULL (a first frame) or all given. No scene is needed. Per pixel with record r, f32 and unfused:
+ *   No history -- out = current, count_out = 1 -- when there are no history buffers, PYR_MOTION_IN_FRONT is clear, or prev_x or
+ *   prev_y is not finite. Else gx = r.prev_x - 0.5f, x0 = floorf(gx), fx = gx - x0, the same in y; four taps (x0, y0), (x0 + 1.0f, y0),
+ *   (x0, y0 + 1.0f), (x0 + 1.0f, y0 + 1.0f) with weights (1.0f-fx)*(1.0f-fy), fx*(1.0f-fy), (1.0f-fx)*fy, fx*fy. A tap counts iff
+ *   it lies inside the image (decided on the floats, before any cast), history_motion[tap].shape == r.shape, where r has
+ *   PYR_MOTION_HIT  fabsf(h.depth - r.prev_depth) <= depth_tolerance * fmaxf(h.depth, r.prev_depth)  with h = history_motion[tap],
+ *   history_count[tap] > 0, and the tap's three history floats are finite. Wt, Hc (per channel) and N are the sums over the counting
+ *   taps, in tap order from 0.0f, of w, w * history_c and w * history_count. If Wt > 0 is false: no history, as above. Otherwise
+ *   H_c = Hc / Wt, n = fminf(N / Wt, max_history), out_c = H_c + (current_c - H_c) / (n + 1.0f), count_out = n + 1.0f.
+ * A surface that was hidden a frame ago finds no tap of its shape and depth and starts again at 1: the disocclusion rule. One lane
+ * owns a pixel, there are no atomics, two calls write the same bytes. Nothing clamps the history to the neighbourhood of `current`,
+ * nothing reads a variance, nothing jitters the pixel centre. */
+#define PYR_REPROJECT_DEPTH_TOLERANCE 0.02f /* = PYR_DENOISE_SIGMA_DEPTH */
+#define PYR_REPROJECT_MAX_HISTORY 32.0f
+typedef struct PyrReprojectParams {
+    float depth_tolerance; /* >= 0, finite */
+    float max_history;     /* >= 1, finite: the mean forgets older frames at the rate 1 / (max_history + 1) */
+    uint32_t reserved[2];  /* 0 */
+} PyrReprojectParams;
+/* Arguments are checked before a device is looked for: PYR_ERR_INVALID_ARGUMENT, with the argument named in pyr_last_error, for a
+ * null current, motion, params, out or count_out, history buffers of which some but not all are NULL, an empty image, parameters
+ * out of range (a NaN is), a non-zero reserved word; PYR_ERR_UNSUPPORTED for more than 2^32 - 1 pixels; only then PYR_ERR_DEVICE.
+ * HOST buffers. Blocking. */
+int pyr_image_reproject(const float* current, const PyrMotionPixel* motion, const float* history, const PyrMotionPixel* history_motion, const float* history_count,
+                        uint32_t width, uint32_t height, const PyrReprojectParams* params, float* out, float* count_out, int device);
+/* The same with every buffer resident on `device`, enqueued on `hip_stream`; out and count_out may not overlap an input. The two
+ * record arrays must be 16-byte aligned (hipMalloc's memory is; PYR_ERR_INVALID_ARGUMENT otherwise). */
+int pyr_image_reproject_device(const float* current_device, const PyrMotionPixel* motion_device, const float* history_device,
+                               const PyrMotionPixel* history_motion_device, const float* history_count_device, uint32_t width, uint32_t height,
+                               const PyrReprojectParams* params, float* out_device, float* count_out_device, int device, void* hip_stream);
+
 #ifdef __cplusplus
 }
 #endif

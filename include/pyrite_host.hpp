@@ -312,6 +312,9 @@ class World { // world.rs:31-36
         std::vector<float> positions, normals, frames, spheres;
     };
     Geometry geometry(int device = 0);
+    // pyr_scene_keep_previous: keeps the geometry of the scene on `device` as it is now as the previous frame's, for
+    // Renderer::motion; whatever update, pose or skin follows leaves it alone. `keep` false drops it.
+    void keep_previous(bool keep = true, int device = 0);
     // World::intersect (world.rs:273-299) for a batch of rays, [n][6] = origin, direction: closest hits, on the GPU
     std::vector<PyrHit> intersect(const std::vector<float>& rays, int device = 0, PyrCounters* counters = nullptr);
     FlatScene& flat() { return flat_; }
@@ -390,6 +393,17 @@ Denoised denoise(const std::vector<float>& a, const std::vector<float>& b, uint3
 std::string denoise_flag_problem(bool denoise, const std::optional<long>& denoise_radius, const std::optional<uint32_t>& pixel_samples = std::nullopt,
                                  const std::optional<long>& pass_samples = std::nullopt);
 
+// ---- accumulation over frames (pyrite_gpu.h "motion records and accumulation over frames"; pyrite_amd/develop.py reproject) ----
+// What reproject returns: the running mean, [height][width][3] f32, and the frames each pixel's mean holds, [height][width] f32.
+struct Accumulated {
+    std::vector<float> image, count;
+};
+PyrReprojectParams reproject_params(float depth_tolerance = PYR_REPROJECT_DEPTH_TOLERANCE, float max_history = PYR_REPROJECT_MAX_HISTORY);
+// `current` with the records of its frame (Renderer::motion), accumulated onto `history` -- the previous call's result and the
+// records of that frame; both null for a first frame (pyr_image_reproject).
+Accumulated reproject(const std::vector<float>& current, const std::vector<PyrMotionPixel>& motion, uint32_t width, uint32_t height, const Accumulated* history = nullptr,
+                      const std::vector<PyrMotionPixel>* history_motion = nullptr, const PyrReprojectParams& params = reproject_params(), int device = 0);
+
 struct Progress { // renderer/mod.rs:229-232
     uint8_t progress;
     const char* message;
@@ -413,6 +427,9 @@ class Renderer { // renderer/mod.rs:18-28, Algorithm::Simple
     PyrRenderParams params(uint32_t sample_begin = 0) const; // this renderer as the ABI's parameter block
     // The first-hit feature images (pyr_render_features; pyrite_amd/renderer.py Renderer.features): no noise, no random numbers.
     struct Features features(uint32_t width, uint32_t height, const Camera& camera, World& world, uint32_t grid = 1, uint32_t albedo_bins = 16, int device = 0) const;
+    // The motion records (pyr_render_motion; pyrite_amd/renderer.py Renderer.motion), one per pixel, row-major: where the surface
+    // point `camera` sees was for `previous_camera` in the geometry World::keep_previous kept (none kept: the geometry as it is).
+    std::vector<PyrMotionPixel> motion(uint32_t width, uint32_t height, const Camera& camera, World& world, const Camera& previous_camera, int device = 0) const;
 };
 
 // What Renderer::features and Session::features return: the albedo film (albedo_bins bins over the renderer's span; develop and
@@ -456,6 +473,7 @@ class Session {
     Film film();
     std::vector<float> noise(); // per tile of the make_tiles grid, raster order (pyr_session_noise): needs halves and two passes
     Features features(uint32_t grid = 1, uint32_t albedo_bins = 16); // pyr_session_features: after the passes enqueued so far; the film is not touched
+    std::vector<PyrMotionPixel> motion(const Camera& previous_camera); // pyr_session_motion: the session's camera against the previous one; the film is not touched
     // pyr_session_denoised: the two half films developed to linear sRGB and cross filtered on the session's device; with `guides` the
     // feature pass (grid, albedo_bins) runs first and steers the filter. Needs halves and two passes; the films are not touched.
     Denoised denoised(const PyrDenoiseParams& params = denoise_params(), bool guides = true, float step_size = 2.0f, const std::optional<Expression>& filter = std::nullopt,

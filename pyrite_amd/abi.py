@@ -435,6 +435,26 @@ class PyrDenoiseParams(C.Structure):
     ]
 
 
+PYR_MOTION_HIT, PYR_MOTION_IN_FRONT, PYR_MOTION_INSIDE = 1, 2, 4
+PYR_REPROJECT_DEPTH_TOLERANCE, PYR_REPROJECT_MAX_HISTORY = 0.02, 32.0
+
+
+class PyrMotionPixel(C.Structure):
+    _fields_ = [
+        ("prev_x", C.c_float),
+        ("prev_y", C.c_float),
+        ("prev_depth", C.c_float),
+        ("depth", C.c_float),
+        ("shape", C.c_uint32),
+        ("flags", C.c_uint32),
+        ("reserved", C.c_uint32 * 2),
+    ]
+
+
+class PyrReprojectParams(C.Structure):
+    _fields_ = [("depth_tolerance", C.c_float), ("max_history", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
 PyrProgressFn = C.CFUNCTYPE(None, C.c_void_p, C.c_uint8, C.c_char_p)
 PyrPreviewFn = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, C.c_uint32)
 
@@ -529,6 +549,19 @@ ENTRY_POINTS = {
         [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PyrDenoiseParams), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
     ),
     "pyr_session_denoised": (C.c_int, [C.c_void_p, C.POINTER(PyrDevelopParams), C.POINTER(PyrFeatureParams), C.POINTER(PyrDenoiseParams), C.c_void_p, C.c_void_p]),
+    "pyr_scene_keep_previous": (C.c_int, [C.c_void_p, C.c_int]),
+    "pyr_camera_world_to_cam": (C.c_int, [C.POINTER(PyrCamera), C.POINTER(C.c_float)]),
+    "pyr_render_motion": (C.c_int, [C.c_void_p, C.POINTER(PyrCamera), C.POINTER(PyrCamera), C.POINTER(PyrFilmDesc), C.c_void_p]),
+    "pyr_render_motion_device": (C.c_int, [C.c_void_p, C.POINTER(PyrCamera), C.POINTER(PyrCamera), C.POINTER(PyrFilmDesc), C.c_void_p, C.c_void_p]),
+    "pyr_session_motion": (C.c_int, [C.c_void_p, C.POINTER(PyrCamera), C.c_void_p]),
+    "pyr_image_reproject": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PyrReprojectParams), C.c_void_p, C.c_void_p, C.c_int],
+    ),
+    "pyr_image_reproject_device": (
+        C.c_int,
+        [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PyrReprojectParams), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    ),
 }
 
 

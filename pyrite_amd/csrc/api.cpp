@@ -1093,6 +1093,39 @@ int enqueue_features(PyrScene* scene, const PyrCamera* camera, const PyrFilmDesc
     return launch_features(scene->dev, L, stream, scene->num_cus, scene->program_info.wide != 0);
 }
 
+// What the three motion entries refuse before a device is looked for. `what` names the scene or session argument.
+int check_motion_args(const void* owner, const char* what, const PyrCamera* camera, bool need_camera, const PyrCamera* previous_camera, const PyrFilmDesc* film,
+                      const void* pixels, float previous_w[16]) {
+    if (!owner) return fail(PYR_ERR_INVALID_ARGUMENT, std::string("null argument: ") + what);
+    if (need_camera && !camera) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: camera");
+    if (!previous_camera) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: previous_camera");
+    if (!film) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: film");
+    if (!pixels) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: pixels");
+    if (film->width == 0 || film->height == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "film: zero-sized image");
+    if ((uint64_t)film->width * film->height >= 0xFFFFFFFFull) return fail(PYR_ERR_INVALID_ARGUMENT, "film: 2^32 pixels or more");
+    if (pyr_camera_world_to_cam(previous_camera, previous_w) != PYR_OK) return fail(PYR_ERR_INVALID_ARGUMENT, std::string("previous_camera: ") + pyr_last_error());
+    if (pyr_device_count() <= 0) return fail(PYR_ERR_DEVICE, "no HIP device is visible; pyrite_gpu has no CPU path");
+    return PYR_OK;
+}
+
+// Enqueues the pass on `stream`; `pixels` is on the scene's device.
+int enqueue_motion(PyrScene* scene, const PyrCamera* camera, const PyrCamera* previous_camera, const float previous_w[16], const PyrFilmDesc* film,
+                   PyrMotionPixel* pixels, hipStream_t stream) {
+    if (!scene->tail_count) HIP_TRY(hipMalloc((void**)&scene->tail_count, kFeedBytes));
+    HIP_TRY(hipMemsetAsync(scene->tail_count, 0, kFeedBytes, stream));
+    const LiveGeometry& live = scene->live;
+    MotionLaunch L{};
+    L.camera = *camera;
+    std::memcpy(L.previous_w, previous_w, sizeof(L.previous_w));
+    L.previous_view_plane = previous_camera->view_plane;
+    L.width = film->width, L.height = film->height;
+    L.previous_positions = live.previous_kept && live.num_triangles ? (const float*)live.previous_positions.ptr : nullptr;
+    L.previous_spheres = live.previous_kept && live.num_spheres ? (const float*)live.previous_spheres.ptr : nullptr;
+    L.pixels = pixels;
+    L.next = scene->tail_count;
+    return launch_motion(scene->dev, L, stream, scene->num_cus);
+}
+
 } // namespace pyr
 
 extern "C" {
@@ -1367,6 +1400,62 @@ int pyr_render_features(PyrScene* scene, const PyrCamera* camera, const PyrFilmD
     HIP_TRY(hipDeviceSynchronize());
     if (albedo_inout) HIP_TRY(hipMemcpy(albedo_inout, albedo_dev.ptr, albedo_bytes, hipMemcpyDeviceToHost));
     if (pixels_out) HIP_TRY(hipMemcpy(pixels_out, pixels_dev.ptr, pixel_bytes, hipMemcpyDeviceToHost));
+    return PYR_OK;
+}
+
+// ------------------------------------------------------------------------------------------------ motion records
+int pyr_camera_world_to_cam(const PyrCamera* camera, float out[16]) {
+    if (!camera || !out) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+    const float* m = camera->cam_to_world;
+    for (int k = 0; k < 16; ++k)
+        if (!std::isfinite(m[k])) return fail(PYR_ERR_INVALID_ARGUMENT, "cam_to_world has an entry that is not finite");
+    if (!(m[3] == 0.0f && m[7] == 0.0f && m[11] == 0.0f && m[15] == 1.0f)) return fail(PYR_ERR_INVALID_ARGUMENT, "cam_to_world: the last row must be 0, 0, 0, 1");
+    double a[3][3], t[3]; // a[row][column]
+    for (int r = 0; r < 3; ++r) {
+        for (int c = 0; c < 3; ++c) a[r][c] = (double)m[4 * c + r];
+        t[r] = (double)m[12 + r];
+    }
+    double cof[3][3]; // cof[r][c]: the cofactor of a[r][c]
+    for (int r = 0; r < 3; ++r)
+        for (int c = 0; c < 3; ++c) {
+            const int r1 = (r + 1) % 3, r2 = (r + 2) % 3, c1 = (c + 1) % 3, c2 = (c + 2) % 3;
+            cof[r][c] = a[r1][c1] * a[r2][c2] - a[r1][c2] * a[r2][c1];
+        }
+    const double det = a[0][0] * cof[0][0] + a[0][1] * cof[0][1] + a[0][2] * cof[0][2];
+    if (det == 0.0 || !std::isfinite(det)) return fail(PYR_ERR_INVALID_ARGUMENT, "cam_to_world: the determinant of its 3 x 3 part is 0 or not finite");
+    for (int r = 0; r < 3; ++r) {
+        double inv[3];
+        for (int c = 0; c < 3; ++c) inv[c] = cof[c][r] / det; // the inverse is the transposed cofactors over the determinant
+        for (int c = 0; c < 3; ++c) out[4 * c + r] = (float)inv[c];
+        out[12 + r] = (float)-(inv[0] * t[0] + inv[1] * t[1] + inv[2] * t[2]);
+    }
+    out[3] = out[7] = out[11] = 0.0f;
+    out[15] = 1.0f;
+    return PYR_OK;
+}
+
+int pyr_render_motion_device(PyrScene* scene, const PyrCamera* camera, const PyrCamera* previous_camera, const PyrFilmDesc* film, PyrMotionPixel* pixels_device,
+                             void* hip_stream) {
+    if (((uintptr_t)pixels_device & 15u) != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "pixels_device must be 16-byte aligned"); // records are written as 16-byte vectors
+    float w[16];
+    int rc = check_motion_args(scene, "scene", camera, true, previous_camera, film, pixels_device, w);
+    if (rc != PYR_OK) return rc;
+    HIP_TRY(hipSetDevice(scene->device));
+    return enqueue_motion(scene, camera, previous_camera, w, film, pixels_device, (hipStream_t)hip_stream);
+}
+
+int pyr_render_motion(PyrScene* scene, const PyrCamera* camera, const PyrCamera* previous_camera, const PyrFilmDesc* film, PyrMotionPixel* pixels_out) {
+    float w[16];
+    int rc = check_motion_args(scene, "scene", camera, true, previous_camera, film, pixels_out, w);
+    if (rc != PYR_OK) return rc;
+    HIP_TRY(hipSetDevice(scene->device));
+    const size_t bytes = (size_t)film->width * film->height * sizeof(PyrMotionPixel);
+    DeviceBuffer pixels_dev;
+    if ((rc = pixels_dev.alloc(bytes)) != PYR_OK) return rc;
+    rc = enqueue_motion(scene, camera, previous_camera, w, film, (PyrMotionPixel*)pixels_dev.ptr, nullptr);
+    HIP_TRY(hipDeviceSynchronize()); // before the buffer above is freed, whatever happened
+    if (rc != PYR_OK) return rc;
+    HIP_TRY(hipMemcpy(pixels_out, pixels_dev.ptr, bytes, hipMemcpyDeviceToHost));
     return PYR_OK;
 }
 

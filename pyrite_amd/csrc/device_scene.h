@@ -331,6 +331,36 @@ using FeatureKernel = void (*)(DevScene, FeatureLaunch);
 FeatureKernel pick_wide_features_kernel(); // kernels/features_wide.hip: the build whose interpreter holds the wide register file
 int launch_features(const DevScene& scene, const FeatureLaunch& launch, void* stream, int num_cus, bool wide_vm);
 
+// kernels/motion.hip: the motion pass. Items are the feature pass's: a pixel each, 64 consecutive ones an
+// 8 x 8 square (the launcher numbers them and sets `n`, `squares_x`, `reserve` and `stack_lds`). The snapshot of the previous
+// frame's geometry travels here, not in DevScene: the render kernels take that struct by value and know nothing of this pass.
+struct MotionLaunch {
+    PyrCamera camera;            // aperture is not read: the lens is its centre
+    float previous_w[16];        // pyr_camera_world_to_cam of the previous camera
+    float previous_view_plane;
+    uint32_t width, height;
+    const float* previous_positions; // device, [triangles][3][3] in the description's order, or nullptr: no snapshot
+    const float* previous_spheres;   // device, [spheres][4], or nullptr
+    PyrMotionPixel* pixels;          // device, height * width records, overwritten
+    uint32_t* next;                  // device, kFeedBytes, zero at launch: the work-feed cursors
+    uint32_t n, squares_x, reserve, stack_lds;
+};
+int launch_motion(const DevScene& scene, const MotionLaunch& launch, void* stream, int num_cus);
+
+// kernels/reproject.hip: accumulation over frames (pyrite_gpu.h "motion records and accumulation over frames")
+struct ReprojectLaunch {
+    const float* current;                 // device, height * width * 3 floats
+    const PyrMotionPixel* motion;         // device, height * width records
+    const float* history;                 // device, or all three nullptr: a first frame
+    const PyrMotionPixel* history_motion;
+    const float* history_count;
+    uint32_t width, height;
+    float depth_tolerance, max_history;
+    float* out;       // device, height * width * 3 floats
+    float* count_out; // device, height * width floats
+};
+int launch_reproject(const ReprojectLaunch& launch, void* stream);
+
 // launchers (kernels/main.hip)
 // wide_vm: the scene has a program that only the wide interpreter build (kernels/wide.hip) holds
 int launch_render(const DevScene& scene, const RenderLaunch& launch, bool with_counters, void* stream, int num_cus, bool wide_vm = false);

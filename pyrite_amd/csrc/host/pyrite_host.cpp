@@ -1209,6 +1209,7 @@ World::Geometry World::geometry(int device) {
                                     g.frames.empty() ? nullptr : g.frames.data(), g.spheres.empty() ? nullptr : g.spheres.data()));
     return g;
 }
+void World::keep_previous(bool keep, int device) { check_status(pyr_scene_keep_previous(scene(device), keep ? 1 : 0)); }
 PyrUpdateInfo World::update_info(int device) {
     PyrUpdateInfo info{};
     check_status(pyr_scene_update_info(scene(device), &info));
@@ -1550,6 +1551,32 @@ std::string denoise_flag_problem(bool denoise, const std::optional<long>& denois
     if (denoise && pixel_samples && pass_samples && *pass_samples > 0 && *pixel_samples % (2u * (uint64_t)*pass_samples))
         return "--denoise needs an even number of equal passes: the samples per pixel must be a multiple of twice --pass-samples";
     return "";
+}
+
+// ---- motion records and accumulation over frames -------------------------------------------------------------------------------
+std::vector<PyrMotionPixel> Renderer::motion(uint32_t width, uint32_t height, const Camera& camera, World& world, const Camera& previous_camera, int device) const {
+    std::vector<PyrMotionPixel> out((size_t)width * height);
+    PyrFilmDesc d{}; // only width and height are read
+    d.width = width, d.height = height, d.bins = spectrum_bins, d.wl_start = spectrum_span[0], d.wl_width = spectrum_span[1] - spectrum_span[0];
+    check_status(pyr_render_motion(world.scene(device), &camera.c, &previous_camera.c, &d, out.data()));
+    return out;
+}
+std::vector<PyrMotionPixel> Session::motion(const Camera& previous_camera) {
+    std::vector<PyrMotionPixel> out((size_t)width_ * height_);
+    check_status(pyr_session_motion(handle_, &previous_camera.c, out.data()));
+    return out;
+}
+PyrReprojectParams reproject_params(float depth_tolerance, float max_history) { return PyrReprojectParams{depth_tolerance, max_history, {0u, 0u}}; }
+Accumulated reproject(const std::vector<float>& current, const std::vector<PyrMotionPixel>& motion, uint32_t width, uint32_t height, const Accumulated* history,
+                      const std::vector<PyrMotionPixel>* history_motion, const PyrReprojectParams& params, int device) {
+    const size_t count = (size_t)width * height;
+    if ((history == nullptr) != (history_motion == nullptr)) throw ProjectError("reproject: the history and its motion records go together");
+    if (current.size() != count * 3 || motion.size() != count || (history && (history->image.size() != count * 3 || history->count.size() != count || history_motion->size() != count)))
+        throw ProjectError("reproject: buffer size does not match the image size");
+    Accumulated out{std::vector<float>(count * 3, 0.0f), std::vector<float>(count, 0.0f)};
+    check_status(pyr_image_reproject(current.data(), motion.data(), history ? history->image.data() : nullptr, history ? history_motion->data() : nullptr,
+                                     history ? history->count.data() : nullptr, width, height, &params, out.image.data(), out.count.data(), device));
+    return out;
 }
 
 // ---- first-hit feature images --------------------------------------------------------------------------------------------------

@@ -1,5 +1,6 @@
 // image_ops.cpp -- the entry points of include/pyrite_gpu.h that take a device number and never see a scene: a film developed to
-// an 8-bit or a linear image, an image's luminance statistics, its tone mapping, the denoising of two half images. What a
+// an 8-bit or a linear image, an image's luminance statistics, its tone mapping, the denoising of two half images, the
+// accumulation of linear images over frames along their motion records. What a
 // progressive session does with its own film through the same checks and launches (session.cpp) is declared in image_internal.h.
 #include <algorithm>
 #include <cmath>
@@ -209,9 +210,63 @@ int check_denoise_args(const void* a, const void* b, uint32_t width, uint32_t he
     return check_image_size(width, height);
 }
 
+// What both reproject entries refuse before a device is looked for.
+int check_reproject_args(const void* current, const void* motion, const void* history, const void* history_motion, const void* history_count, uint32_t width,
+                         uint32_t height, const PyrReprojectParams* p, const void* out, const void* count_out) {
+    if (!current) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: current");
+    if (!motion) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: motion");
+    if (!p) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: params");
+    if (!out) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: out");
+    if (!count_out) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: count_out");
+    const int given = (history != nullptr) + (history_motion != nullptr) + (history_count != nullptr);
+    if (given != 0 && given != 3) return fail(PYR_ERR_INVALID_ARGUMENT, "history, history_motion and history_count are all null or all given");
+    if (!(p->depth_tolerance >= 0.0f) || !std::isfinite(p->depth_tolerance)) return fail(PYR_ERR_INVALID_ARGUMENT, "params->depth_tolerance must be finite and not negative");
+    if (!(p->max_history >= 1.0f) || !std::isfinite(p->max_history)) return fail(PYR_ERR_INVALID_ARGUMENT, "params->max_history must be finite and at least 1");
+    if (p->reserved[0] != 0 || p->reserved[1] != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "params->reserved must be 0");
+    if (width == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "width: an empty image");
+    if (height == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "height: an empty image");
+    return check_image_size(width, height);
+}
+
 } // namespace
 
 extern "C" {
+
+int pyr_image_reproject_device(const float* current_device, const PyrMotionPixel* motion_device, const float* history_device,
+                               const PyrMotionPixel* history_motion_device, const float* history_count_device, uint32_t width, uint32_t height,
+                               const PyrReprojectParams* params, float* out_device, float* count_out_device, int device, void* hip_stream) {
+    if ((((uintptr_t)motion_device | (uintptr_t)history_motion_device) & 15u) != 0) // records are read as 16-byte vectors
+        return fail(PYR_ERR_INVALID_ARGUMENT, "motion_device and history_motion_device must be 16-byte aligned");
+    int rc = check_reproject_args(current_device, motion_device, history_device, history_motion_device, history_count_device, width, height, params, out_device, count_out_device);
+    if (rc != PYR_OK || (rc = check_device(device)) != PYR_OK) return rc;
+    HIP_TRY(hipSetDevice(device));
+    const ReprojectLaunch L{current_device, motion_device, history_device, history_motion_device, history_count_device, width, height,
+                            params->depth_tolerance, params->max_history, out_device, count_out_device};
+    return launch_reproject(L, hip_stream);
+}
+
+int pyr_image_reproject(const float* current, const PyrMotionPixel* motion, const float* history, const PyrMotionPixel* history_motion, const float* history_count,
+                        uint32_t width, uint32_t height, const PyrReprojectParams* params, float* out, float* count_out, int device) {
+    int rc = check_reproject_args(current, motion, history, history_motion, history_count, width, height, params, out, count_out);
+    if (rc != PYR_OK || (rc = check_device(device)) != PYR_OK) return rc;
+    HIP_TRY(hipSetDevice(device));
+    const size_t count = (size_t)width * height, image_bytes = count * 3 * sizeof(float), record_bytes = count * sizeof(PyrMotionPixel);
+    DeviceBuffer current_dev, motion_dev, history_dev, history_motion_dev, history_count_dev, out_dev, count_dev;
+    if ((rc = current_dev.upload(current, image_bytes)) != PYR_OK || (rc = motion_dev.upload(motion, record_bytes)) != PYR_OK) return rc;
+    if (history && ((rc = history_dev.upload(history, image_bytes)) != PYR_OK || (rc = history_motion_dev.upload(history_motion, record_bytes)) != PYR_OK ||
+                    (rc = history_count_dev.upload(history_count, count * sizeof(float))) != PYR_OK))
+        return rc;
+    if ((rc = out_dev.alloc(image_bytes)) != PYR_OK || (rc = count_dev.alloc(count * sizeof(float))) != PYR_OK) return rc;
+    const ReprojectLaunch L{(const float*)current_dev.ptr, (const PyrMotionPixel*)motion_dev.ptr, history ? (const float*)history_dev.ptr : nullptr,
+                            history ? (const PyrMotionPixel*)history_motion_dev.ptr : nullptr, history ? (const float*)history_count_dev.ptr : nullptr, width, height,
+                            params->depth_tolerance, params->max_history, (float*)out_dev.ptr, (float*)count_dev.ptr};
+    rc = launch_reproject(L, nullptr);
+    HIP_TRY(hipDeviceSynchronize()); // before the buffers above are freed, whatever happened
+    if (rc != PYR_OK) return rc;
+    HIP_TRY(hipMemcpy(out, out_dev.ptr, image_bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(count_out, count_dev.ptr, count * sizeof(float), hipMemcpyDeviceToHost));
+    return PYR_OK;
+}
 
 int pyr_film_develop_device(const PyrFilmDesc* film, const PyrGrain* grains_device, const PyrDevelopParams* params, uint8_t* rgb_device, int device,
                             void* hip_stream) {

@@ -1,5 +1,6 @@
 // live_scene.cpp -- everything that moves a scene after creation: pyr_scene_update[_device], pyr_scene_set_objects,
-// pyr_scene_pose, pyr_scene_set_skins, pyr_scene_skin, pyr_scene_geometry, pyr_scene_update_info. LiveGeometry
+// pyr_scene_pose, pyr_scene_set_skins, pyr_scene_skin, pyr_scene_geometry, pyr_scene_update_info -- and pyr_scene_keep_previous,
+// which copies where the geometry is now for the motion pass (api.cpp enqueues that one). LiveGeometry
 // (scene_internal.h) says where the geometry is and which copies are valid; rebuild_from and refit_from are the two ways new
 // arrays reach the records and trees on the device.
 #include <algorithm>
@@ -603,6 +604,34 @@ int pyr_scene_geometry(PyrScene* scene, float* tri_positions, float* tri_normals
     float* const out[NUM_ARRAYS] = {tri_positions, tri_normals, tri_frames, spheres};
     for (int k = 0; k < NUM_ARRAYS; ++k)
         if (out[k] && live.kept_floats(k)) std::memcpy(out[k], live.arrays[k].host.data(), live.kept_floats(k) * 4);
+    return PYR_OK;
+}
+
+int pyr_scene_keep_previous(PyrScene* scene, int keep) {
+    if (!scene) return fail(PYR_ERR_INVALID_ARGUMENT, "null scene");
+    LiveGeometry& live = scene->live;
+    HIP_TRY(hipSetDevice(scene->device));
+    HIP_TRY(hipDeviceSynchronize()); // blocking: a motion pass in flight may read the old snapshot, a pose may still write the staging arrays
+    if (!keep) {
+        live.previous_positions.release(), live.previous_spheres.release();
+        live.previous_kept = false;
+        return PYR_OK;
+    }
+    // Positions and spheres are always kept. After a refit pose the staging arrays hold both in full and are the truth; otherwise
+    // the description is, and the staging arrays may hold an older update or nothing.
+    const std::pair<int, DeviceBuffer*> pairs[2] = {{POSITIONS, &live.previous_positions}, {SPHERES, &live.previous_spheres}};
+    live.previous_kept = false; // (a copy that fails leaves no snapshot, not half of one)
+    for (const auto& [k, to] : pairs) {
+        const size_t bytes = live.floats(k) * 4;
+        int rc;
+        if (live.host_current()) {
+            if ((rc = to->upload(live.arrays[k].host.data(), bytes)) != PYR_OK) return rc;
+        } else {
+            if ((rc = to->reserve(bytes)) != PYR_OK) return rc;
+            if (bytes) HIP_TRY(hipMemcpy(to->ptr, live.arrays[k].staging.ptr, bytes, hipMemcpyDeviceToDevice));
+        }
+    }
+    live.previous_kept = true;
     return PYR_OK;
 }
 

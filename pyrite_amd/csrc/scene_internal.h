@@ -52,6 +52,12 @@ int check_feature_args(const void* owner, const char* what, const PyrCamera* cam
                        const void* albedo, const void* pixels);
 int enqueue_features(PyrScene* scene, const PyrCamera* camera, const PyrFilmDesc* film, const PyrFeatureParams* fp, PyrGrain* albedo, PyrFeaturePixel* pixels,
                      hipStream_t stream);
+// The same for the motion entries: the checks (previous_w receives pyr_camera_world_to_cam of the previous camera), and the pass
+// enqueued on `stream` with `pixels` on the scene's device.
+int check_motion_args(const void* owner, const char* what, const PyrCamera* camera, bool need_camera, const PyrCamera* previous_camera, const PyrFilmDesc* film,
+                      const void* pixels, float previous_w[16]);
+int enqueue_motion(PyrScene* scene, const PyrCamera* camera, const PyrCamera* previous_camera, const float previous_w[16], const PyrFilmDesc* film,
+                   PyrMotionPixel* pixels, hipStream_t stream);
 
 struct LiveArray {       // one of the arrays that move, and its homes
     uint32_t width;      // floats per primitive
@@ -103,6 +109,10 @@ struct LiveGeometry {
     std::vector<float> skin_joints;
     uint32_t skinned_triangles = 0;
     DeviceBuffer skin_table, skin_weights, skin_indices, joint_table; // DevSkin records, the two binding arrays, twelve floats a joint
+    // the previous frame (pyr_scene_keep_previous): positions and spheres as they were when it was called, the description's order.
+    // Nothing that moves the scene touches them -- counts and indices never change -- and only the motion pass reads them.
+    DeviceBuffer previous_positions, previous_spheres;
+    bool previous_kept = false;
 
     size_t floats(int k) const { return (size_t)arrays[k].width * (arrays[k].per_sphere ? num_spheres : num_triangles); } // of array k in full, kept or not
     size_t kept_floats(int k) const { return arrays[k].kept ? floats(k) : 0; }

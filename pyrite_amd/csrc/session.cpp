@@ -321,6 +321,23 @@ int pyr_session_features(PyrSession* session, const PyrFeatureParams* fp, PyrGra
     });
 }
 
+int pyr_session_motion(PyrSession* session, const PyrCamera* previous_camera, PyrMotionPixel* pixels_out) {
+    float w[16];
+    int rc = check_motion_args(session, "session", nullptr, false, previous_camera, session ? &session->film : nullptr, pixels_out, w);
+    if (rc != PYR_OK) return rc;
+    if ((rc = session_ready(session)) != PYR_OK) return rc;
+    const size_t bytes = (size_t)session->film.width * session->film.height * sizeof(PyrMotionPixel);
+    DeviceBuffer pixels_dev;
+    if ((rc = pixels_dev.alloc(bytes)) != PYR_OK) return rc;
+    return enqueue_then_sync(session, [&]() -> int {
+        int rc = enqueue_motion(session->scene, &session->camera, previous_camera, w, &session->film, (PyrMotionPixel*)pixels_dev.ptr, session->stream);
+        if (rc != PYR_OK) return rc;
+        if (hipMemcpyAsync(pixels_out, pixels_dev.ptr, bytes, hipMemcpyDeviceToHost, session->stream) != hipSuccess)
+            return fail(PYR_ERR_DEVICE, "hipMemcpyAsync of the motion records failed");
+        return PYR_OK;
+    });
+}
+
 int pyr_session_linear(PyrSession* session, const PyrDevelopParams* develop_params, uint32_t space, float* out) {
     if (!session) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
     int rc = check_linear_args(&session->film, session, develop_params, space, out);

@@ -242,6 +242,33 @@ def denoise(a, b, albedo=None, pixels=None, device=0, **params):
     return out, error
 
 
+def reproject(current, motion, history=None, history_motion=None, history_count=None, depth_tolerance=abi.PYR_REPROJECT_DEPTH_TOLERANCE,
+              max_history=abi.PYR_REPROJECT_MAX_HISTORY, device=0):
+    """(out, count): the running mean of linear images over frames of a moving scene (pyr_image_reproject; include/pyrite_gpu.h has
+    the arithmetic). `current`: this frame, float32 [height, width, 3]; `motion`: its records (Renderer.motion, motion.RECORD
+    [height, width]). `history`, `history_motion`, `history_count`: the previous call's `out`, the records of that frame and its
+    `count` -- all None for a first frame. `count` [height, width] float32 is the number of frames a pixel's mean holds; a pixel
+    whose surface was hidden a frame ago starts again at 1."""
+    current = _linear_image(current)
+    h, w, _ = current.shape
+    records = C.sizeof(abi.PyrMotionPixel) * h * w
+    motion = np.ascontiguousarray(motion)
+    assert motion.nbytes == records
+    given = [x is not None for x in (history, history_motion, history_count)]
+    if any(given):
+        if not all(given):
+            raise ValueError("history, history_motion and history_count go together")
+        history, history_motion = _linear_image(history), np.ascontiguousarray(history_motion)
+        history_count = np.ascontiguousarray(history_count, dtype=np.float32)
+        assert history.shape == current.shape and history_motion.nbytes == records and history_count.shape == (h, w)
+    p = abi.PyrReprojectParams(float(depth_tolerance), float(max_history))
+    out, count = np.zeros(current.shape, dtype=np.float32), np.zeros((h, w), dtype=np.float32)
+    ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
+    check(lib().pyr_image_reproject(current.ctypes.data, motion.ctypes.data, ptr(history), ptr(history_motion), ptr(history_count), w, h, C.byref(p), out.ctypes.data,
+                                    count.ctypes.data, int(device)))
+    return out, count
+
+
 def denoise_flag_problem(denoise, denoise_radius, pixel_samples=None, pass_samples=None):
     """What is wrong with --denoise / --denoise-radius, in the words pyrite_host_tool uses too, or None. `pixel_samples`: the
     render's budget once the project is loaded; `pass_samples`: --pass-samples, when given."""

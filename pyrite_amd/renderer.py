@@ -148,6 +148,12 @@ class World:
         self._pose(self.scene(device), named, mode, stream)
         self._poses = named
 
+    def keep_previous(self, keep=True, device=0):
+        """Keeps the geometry of the scene on `device` as it is now as the previous frame's (pyr_scene_keep_previous): the
+        motion pass finds each hit's material point there, whatever update, pose or skin follows. Call it after a frame is
+        done and before the scene moves on; `keep=False` drops the snapshot."""
+        check(lib().pyr_scene_keep_previous(self.scene(device), 1 if keep else 0))
+
     def _set_skins(self, handle, skins):
         order = sorted(skins)
         records = (abi.PyrSkin * max(1, len(order)))()
@@ -369,6 +375,18 @@ class Renderer:
         check(lib().pyr_render_features(world.scene(device), C.byref(camera.c), C.byref(desc), C.byref(fp), out.albedo.grains.ctypes.data, out.records.ctypes.data))
         return out
 
+    def motion(self, film_size, camera: Camera, world: World, previous_camera: Camera = None, device=0):
+        """The motion records of `film_size` = (width, height) (pyr_render_motion), motion.RECORD [height, width]: per pixel, where
+        the surface point `camera` sees was for `previous_camera` (None: the same camera) in the geometry World.keep_previous
+        kept -- or in the geometry as it is when none was kept -- its depth there, this frame's depth and shape, and flags."""
+        from .motion import RECORD
+
+        out = np.zeros((int(film_size[1]), int(film_size[0])), dtype=RECORD)
+        desc = abi.PyrFilmDesc(int(film_size[0]), int(film_size[1]), self.spectrum_bins, self.spectrum_span[0], self.spectrum_span[1] - self.spectrum_span[0])
+        previous = camera if previous_camera is None else previous_camera
+        check(lib().pyr_render_motion(world.scene(device), C.byref(camera.c), C.byref(previous.c), C.byref(desc), out.ctypes.data))
+        return out
+
     def path_info(self, world: World, device=0):
         """Which kernel a render of `world` with this renderer would run (pyr_scene_path_info): a dict of PyrPathInfo's fields."""
         info, params = abi.PyrPathInfo(), self.params()
@@ -517,6 +535,15 @@ class Session:
         out = Features(self.width, self.height, albedo_bins, (self._film.wavelength_start, self._film.wavelength_start + self._film.wavelength_width))
         fp = abi.PyrFeatureParams(int(grid), int(albedo_bins))
         check(lib().pyr_session_features(self.handle, C.byref(fp), out.albedo.grains.ctypes.data, out.records.ctypes.data))
+        return out
+
+    def motion(self, previous_camera: Camera):
+        """Renderer.motion for the session's camera and image size against `previous_camera`, on the session's stream after the
+        passes enqueued so far (pyr_session_motion). The session's film is not touched."""
+        from .motion import RECORD
+
+        out = np.zeros((self.height, self.width), dtype=RECORD)
+        check(lib().pyr_session_motion(self.handle, C.byref(previous_camera.c), out.ctypes.data))
         return out
 
     def half_films(self):

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Developer tool: registers / scratch / occupancy of every kernel of the four units under csrc/kernels/, from hipcc's
+"""Developer tool: registers / scratch / occupancy / static LDS of every kernel of the units under csrc/kernels/, from hipcc's
 -Rpass-analysis=kernel-resource-usage remarks.   python tools/kernel_resources.py [extra -D flags]"""
 import os
 import re
@@ -24,5 +24,5 @@ for block in re.split(r"remark: Function Name: ", text)[1:]:
 
     demangled = subprocess.run(["c++filt", name], capture_output=True, text=True).stdout.strip()
     demangled = re.sub(r"\(pyr::DevScene.*", "", demangled).replace("void pyr::", "")
-    print("VGPR %3d  scratch %5d B  SGPR %3d  waves/SIMD %d  %s" % (field("VGPRs"), field(r"ScratchSize \[bytes/lane\]"), field("TotalSGPRs"),
-                                                                  field(r"Occupancy \[waves/SIMD\]"), demangled))
+    print("VGPR %3d  scratch %5d B  SGPR %3d  waves/SIMD %d  LDS %6d B  %s" % (field("VGPRs"), field(r"ScratchSize \[bytes/lane\]"), field("TotalSGPRs"),
+                                                                               field(r"Occupancy \[waves/SIMD\]"), field(r"LDS Size \[bytes/block\]"), demangled))
