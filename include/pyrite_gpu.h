@@ -1115,6 +1115,73 @@ int pyr_image_reproject_device(const float* current_device, const PyrMotionPixel
                                const PyrMotionPixel* history_motion_device, const float* history_count_device, uint32_t width, uint32_t height,
                                const PyrReprojectParams* params, float* out_device, float* count_out_device, int device, void* hip_stream);
 
+/* ---------------------------------------------------------------- motion blur over the motion records ----
+ * A frame is an instantaneous still; this post filter spreads every pixel along the way its surface point went while the shutter
+ * was open. It is the gather of McGuire, Hennessy, Bukowski and Osman, "A Reconstruction Filter for Plausible Motion Blur" (I3D
+ * 2012), restated for the records above. It needs no scene. `image`, `out`: width*height*3 f32 in linear light; `motion`: the
+ * records of the frame `image` shows. All arithmetic is f32 and unfused, one rounding per operation, in the order written; sqrt
+ * and / are the correctly rounded ones; clamp01(v) = fminf(fmaxf(v, 0.0f), 1.0f), so a NaN becomes 0. With R = (float)max_radius:
+ *   Half velocity of pixel (x, y), index p = y*width + x, record r:
+ *     dx = ((float)x + 0.5f) - r.prev_x,  dy = ((float)y + 0.5f) - r.prev_y,  s = 0.5f * shutter
+ *     hx = dx * s,  hy = dy * s,  len = sqrt(hx*hx + hy*hy)
+ *     hx = hy = len = 0 when PYR_MOTION_IN_FRONT is clear or prev_x, prev_y or len is not finite; otherwise, if len > R:
+ *     k = R / len, hx = hx * k, hy = hy * k, len = R.
+ *     The blur is centred on the frame: taps span X - n .. X + n, for linear motion the exposure [t - shutter/2, t + shutter/2].
+ *   Depth of a pixel: z = r.depth with PYR_MOTION_HIT, else FLT_MAX (a miss lies behind everything; nothing forms inf - inf).
+ *   Tile maximum: tiles are max_radius x max_radius pixels, tile (tx, ty) = (x / max_radius, y / max_radius), index ty*tiles_x + tx,
+ *     partial at the right and bottom edges. A tile's maximum is the (hx, hy, len) of its pixel of largest len; of equal ones,
+ *     the one of smallest p.
+ *   Neighbour maximum (nx, ny, ln) of a tile: the tile maximum of largest len among the up to nine tiles of its 3 x 3 block that
+ *     lie inside the tile grid; of equal ones, the one of smallest tile index.
+ *   Gather, per pixel X = (x, y) with its tile's neighbour maximum, colour C_X = image[p], (lenX, zX) from above:
+ *     If ln < 0.5f, or one of C_X's three floats is not finite: out[p] = image[p], bit for bit. Otherwise
+ *     lX = fmaxf(lenX, 0.5f),  w0 = 1.0f / lX,  W = w0,  S_c = w0 * C_X.c.
+ *     Jitter: k = p + seed * 0x9E3779B1u;  k ^= k >> 16;  k *= 0x7FEB352Du;  k ^= k >> 15;  k *= 0x846CA68Bu;  k ^= k >> 16  (uint32,
+ *     wrapping);  j = (float)(k >> 8) * 0x1p-24f - 0.5f,  in [-0.5, 0.5).
+ *     For i = 0 .. samples-1, in order:
+ *       t = ((((float)i + 0.5f) + j) / (float)samples) * 2.0f - 1.0f;   ox = nx * t,  oy = ny * t
+ *       ax = floorf(((float)x + 0.5f) + ox),  ay = floorf(((float)y + 0.5f) + oy);  the tap Y = (ax, ay) is skipped unless
+ *       0 <= ax < (float)width and 0 <= ay < (float)height (decided on the floats, before any cast), and skipped when one of the
+ *       three floats of C_Y is not finite. With (lenY, zY) of Y:
+ *       dist = sqrt(ox*ox + oy*oy),  lY = fmaxf(lenY, 0.5f),  e = depth_softness * fmaxf(zX, zY)
+ *       front(a, b) = clamp01(1.0f - (a - b) / e)                     -- 1 where a lies in front of b
+ *       cone(d, l) = clamp01(1.0f - d / l)
+ *       cyl(d, l):  lo = 0.95f * l,  hi = 1.05f * l,  u = clamp01((d - lo) / (hi - lo)),  cyl = 1.0f - (u*u) * (3.0f - 2.0f*u)
+ *       w = (front(zY, zX) * cone(dist, lY) + front(zX, zY) * cone(dist, lX)) + (cyl(dist, lY) * cyl(dist, lX)) * 2.0f
+ *       W = W + w,  S_c = S_c + w * C_Y.c
+ *     out[p].c = S_c / W.
+ * A moving pixel reads at most 1 + samples pixels, all inside the 3 x 3 block of tiles around its own. One lane owns a pixel, there
+ * are no atomics, two calls write the same bytes. The records describe first hits only: shadows and reflections do not blur, a
+ * sphere's rotation and lens blur are not tracked (as above), and one previous frame gives linear motion. One GPU. */
+#define PYR_MOTION_BLUR_SHUTTER 0.5f
+#define PYR_MOTION_BLUR_SAMPLES 15u
+#define PYR_MOTION_BLUR_MAX_RADIUS 16u
+#define PYR_MOTION_BLUR_DEPTH_SOFTNESS 0.02f /* relative, like PYR_REPROJECT_DEPTH_TOLERANCE */
+#define PYR_MOTION_BLUR_MOST_SAMPLES 64u
+#define PYR_MOTION_BLUR_MOST_RADIUS 64u
+typedef struct PyrMotionBlurParams {
+    float shutter;        /* the fraction of the frame interval the shutter is open: finite, in (0, 1] */
+    uint32_t samples;     /* taps per pixel, 1..64 */
+    uint32_t max_radius;  /* the largest half-length of a blur in pixels, and the tile edge: 1..64 */
+    float depth_softness; /* finite, > 0 */
+    uint32_t seed;        /* of the per-pixel jitter */
+    uint32_t reserved[3]; /* 0 */
+} PyrMotionBlurParams; /* 32 bytes */
+/* Arguments are checked before a device is looked for: PYR_ERR_INVALID_ARGUMENT, with the argument named in pyr_last_error, for a
+ * null image, motion, params or out, an empty image, a parameter out of range (a NaN is), a non-zero reserved word;
+ * PYR_ERR_UNSUPPORTED for more than 2^32 - 1 pixels; only then PYR_ERR_DEVICE. HOST buffers. Blocking. */
+int pyr_image_motion_blur(const float* image, const PyrMotionPixel* motion, uint32_t width, uint32_t height, const PyrMotionBlurParams* params, float* out, int device);
+/* The same with every buffer resident on `device`, enqueued on `hip_stream`. The records must be 16-byte aligned and out may not
+ * overlap image or motion (PYR_ERR_INVALID_ARGUMENT otherwise). Working memory -- 16 bytes a pixel and 32 a tile -- is allocated
+ * and freed in stream order. */
+int pyr_image_motion_blur_device(const float* image_device, const PyrMotionPixel* motion_device, uint32_t width, uint32_t height,
+                                 const PyrMotionBlurParams* params, float* out_device, int device, void* hip_stream);
+/* What pyr_session_linear (PYR_LINEAR_SRGB), pyr_session_motion and the blur do, composed on the session's stream and device:
+ * nothing but the result crosses to the host. out = HOST, height*width*3 floats. The session's film is not touched, and further
+ * passes may follow. Blocking. */
+int pyr_session_motion_blurred(PyrSession* session, const PyrCamera* previous_camera, const PyrDevelopParams* develop_params,
+                               const PyrMotionBlurParams* blur_params, float* out);
+
 #ifdef __cplusplus
 }
 #endif

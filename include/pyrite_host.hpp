@@ -404,6 +404,14 @@ PyrReprojectParams reproject_params(float depth_tolerance = PYR_REPROJECT_DEPTH_
 Accumulated reproject(const std::vector<float>& current, const std::vector<PyrMotionPixel>& motion, uint32_t width, uint32_t height, const Accumulated* history = nullptr,
                       const std::vector<PyrMotionPixel>* history_motion = nullptr, const PyrReprojectParams& params = reproject_params(), int device = 0);
 
+// ---- motion blur over the motion records (pyrite_gpu.h "motion blur over the motion records"; pyrite_amd/develop.py motion_blur) ----
+PyrMotionBlurParams motion_blur_params(float shutter = PYR_MOTION_BLUR_SHUTTER, uint32_t samples = PYR_MOTION_BLUR_SAMPLES, uint32_t max_radius = PYR_MOTION_BLUR_MAX_RADIUS,
+                                       float depth_softness = PYR_MOTION_BLUR_DEPTH_SOFTNESS, uint32_t seed = 0);
+// The linear image `image`, [height][width][3] f32, blurred along the records of its frame (Renderer::motion) on the GPU
+// (pyr_image_motion_blur). A buffer of another size than the image's is a ProjectError before the library is called.
+std::vector<float> motion_blur(const std::vector<float>& image, const std::vector<PyrMotionPixel>& motion, uint32_t width, uint32_t height,
+                               const PyrMotionBlurParams& params = motion_blur_params(), int device = 0);
+
 struct Progress { // renderer/mod.rs:229-232
     uint8_t progress;
     const char* message;
@@ -474,6 +482,9 @@ class Session {
     std::vector<float> noise(); // per tile of the make_tiles grid, raster order (pyr_session_noise): needs halves and two passes
     Features features(uint32_t grid = 1, uint32_t albedo_bins = 16); // pyr_session_features: after the passes enqueued so far; the film is not touched
     std::vector<PyrMotionPixel> motion(const Camera& previous_camera); // pyr_session_motion: the session's camera against the previous one; the film is not touched
+    // pyr_session_motion_blurred: the film as it stands in linear sRGB, blurred along the records against `previous_camera`, on the session's device
+    std::vector<float> motion_blurred(const Camera& previous_camera, const PyrMotionBlurParams& params = motion_blur_params(), float step_size = 2.0f,
+                                      const std::optional<Expression>& filter = std::nullopt, const std::optional<Expression>& white = std::nullopt);
     // pyr_session_denoised: the two half films developed to linear sRGB and cross filtered on the session's device; with `guides` the
     // feature pass (grid, albedo_bins) runs first and steers the filter. Needs halves and two passes; the films are not touched.
     Denoised denoised(const PyrDenoiseParams& params = denoise_params(), bool guides = true, float step_size = 2.0f, const std::optional<Expression>& filter = std::nullopt,

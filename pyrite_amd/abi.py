@@ -455,6 +455,14 @@ class PyrReprojectParams(C.Structure):
     _fields_ = [("depth_tolerance", C.c_float), ("max_history", C.c_float), ("reserved", C.c_uint32 * 2)]
 
 
+PYR_MOTION_BLUR_SHUTTER, PYR_MOTION_BLUR_SAMPLES, PYR_MOTION_BLUR_MAX_RADIUS, PYR_MOTION_BLUR_DEPTH_SOFTNESS = 0.5, 15, 16, 0.02
+PYR_MOTION_BLUR_MOST_SAMPLES, PYR_MOTION_BLUR_MOST_RADIUS = 64, 64
+
+
+class PyrMotionBlurParams(C.Structure):
+    _fields_ = [("shutter", C.c_float), ("samples", C.c_uint32), ("max_radius", C.c_uint32), ("depth_softness", C.c_float), ("seed", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
 PyrProgressFn = C.CFUNCTYPE(None, C.c_void_p, C.c_uint8, C.c_char_p)
 PyrPreviewFn = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, C.c_uint32)
 
@@ -562,6 +570,9 @@ ENTRY_POINTS = {
         C.c_int,
         [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PyrReprojectParams), C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
     ),
+    "pyr_image_motion_blur": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PyrMotionBlurParams), C.c_void_p, C.c_int]),
+    "pyr_image_motion_blur_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PyrMotionBlurParams), C.c_void_p, C.c_int, C.c_void_p]),
+    "pyr_session_motion_blurred": (C.c_int, [C.c_void_p, C.POINTER(PyrCamera), C.POINTER(PyrDevelopParams), C.POINTER(PyrMotionBlurParams), C.c_void_p]),
 }
 
 

@@ -361,6 +361,21 @@ struct ReprojectLaunch {
 };
 int launch_reproject(const ReprojectLaunch& launch, void* stream);
 
+// kernels/motion_blur.hip: motion blur over the motion records (pyrite_gpu.h "motion blur over the motion records", DESIGN.md
+// section 9j). `work` is motion_blur_work_bytes() of device memory, 16-byte aligned, overwritten: four floats a pixel (hx, hy, len, z)
+// and twice four a tile (the tile maxima, the neighbour maxima). Three launches on `stream`: velocity, neighbour maximum, gather.
+struct MotionBlurLaunch {
+    const float* image;           // device, height * width * 3 floats
+    const PyrMotionPixel* motion; // device, height * width records
+    uint32_t width, height;
+    float shutter, depth_softness;
+    uint32_t samples, max_radius, seed;
+    float* work;
+    float* out; // device, height * width * 3 floats; overlaps no input
+};
+size_t motion_blur_work_bytes(uint32_t width, uint32_t height, uint32_t max_radius);
+int launch_motion_blur(const MotionBlurLaunch& launch, void* stream);
+
 // launchers (kernels/main.hip)
 // wide_vm: the scene has a program that only the wide interpreter build (kernels/wide.hip) holds
 int launch_render(const DevScene& scene, const RenderLaunch& launch, bool with_counters, void* stream, int num_cus, bool wide_vm = false);

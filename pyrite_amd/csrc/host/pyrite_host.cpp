@@ -1579,6 +1579,26 @@ Accumulated reproject(const std::vector<float>& current, const std::vector<PyrMo
     return out;
 }
 
+// ---- motion blur over the motion records ---------------------------------------------------------------------------------------
+PyrMotionBlurParams motion_blur_params(float shutter, uint32_t samples, uint32_t max_radius, float depth_softness, uint32_t seed) {
+    return PyrMotionBlurParams{shutter, samples, max_radius, depth_softness, seed, {0u, 0u, 0u}};
+}
+std::vector<float> motion_blur(const std::vector<float>& image, const std::vector<PyrMotionPixel>& motion, uint32_t width, uint32_t height, const PyrMotionBlurParams& params,
+                               int device) {
+    const size_t count = (size_t)width * height;
+    if (image.size() != count * 3 || motion.size() != count) throw ProjectError("motion_blur: buffer size does not match the image size");
+    std::vector<float> out(count * 3, 0.0f);
+    check_status(pyr_image_motion_blur(image.data(), motion.data(), width, height, &params, out.data(), device));
+    return out;
+}
+std::vector<float> Session::motion_blurred(const Camera& previous_camera, const PyrMotionBlurParams& params, float step_size, const std::optional<Expression>& filter,
+                                           const std::optional<Expression>& white) {
+    const DevelopSetup setup(shape_, filter, white, step_size);
+    std::vector<float> out((size_t)width_ * height_ * 3, 0.0f);
+    check_status(pyr_session_motion_blurred(handle_, &previous_camera.c, &setup.p, &params, out.data()));
+    return out;
+}
+
 // ---- first-hit feature images --------------------------------------------------------------------------------------------------
 Features Renderer::features(uint32_t width, uint32_t height, const Camera& camera, World& world, uint32_t grid, uint32_t albedo_bins, int device) const {
     Features out{Film(width, height, albedo_bins, spectrum_span[0], spectrum_span[1]), std::vector<PyrFeaturePixel>((size_t)width * height)};

@@ -16,6 +16,7 @@ int check_linear_args(const PyrFilmDesc* film, const void* grains, const PyrDeve
 int check_tone_params(const PyrToneParams* t); // what pyr_tone_resolve refuses
 bool tone_needs_stats(const PyrToneParams* t);
 int check_denoise_params(const PyrDenoiseParams* p);
+int check_motion_blur_params(const PyrMotionBlurParams* p, const char* what); // `what` names the argument: params, blur_params
 
 // The per-wavelength tables of a development -- filter, white_div, white_mul, sample_count floats each, then the observer table --
 // are develop_table_floats(p) floats. develop_launch makes the launch record that reads them at `tables` (device); `host` receives
@@ -28,5 +29,9 @@ bool develop_uses_wave(const DevelopLaunch& D); // launch_develop_wave, not laun
 // device; `work` holds three images of width * height * 3 floats (V, FA, FB).
 int enqueue_denoise(const float* a, const float* b, const float* albedo, const PyrFeaturePixel* pixels, uint32_t width, uint32_t height, const PyrDenoiseParams* p,
                     float* work, float* out, float* error_out, hipStream_t stream);
+
+// The motion blur of `image` along `motion` into `out` (kernels/motion_blur.hip): every buffer on the current device, the working
+// memory allocated and freed in stream order on `stream`.
+int enqueue_motion_blur(const float* image, const PyrMotionPixel* motion, uint32_t width, uint32_t height, const PyrMotionBlurParams* p, float* out, hipStream_t stream);
 
 } // namespace pyr

@@ -1,6 +1,6 @@
 // image_ops.cpp -- the entry points of include/pyrite_gpu.h that take a device number and never see a scene: a film developed to
 // an 8-bit or a linear image, an image's luminance statistics, its tone mapping, the denoising of two half images, the
-// accumulation of linear images over frames along their motion records. What a
+// accumulation of linear images over frames along their motion records, the motion blur of one along them. What a
 // progressive session does with its own film through the same checks and launches (session.cpp) is declared in image_internal.h.
 #include <algorithm>
 #include <cmath>
@@ -230,7 +230,84 @@ int check_reproject_args(const void* current, const void* motion, const void* hi
 
 } // namespace
 
+namespace pyr {
+
+// What the three motion blur entries refuse of their parameters before a device is looked for (`what`: params or blur_params).
+int check_motion_blur_params(const PyrMotionBlurParams* p, const char* what) {
+    const std::string name = std::string(what) + "->";
+    if (!p) return fail(PYR_ERR_INVALID_ARGUMENT, std::string("null argument: ") + what);
+    if (!(p->shutter > 0.0f && p->shutter <= 1.0f)) return fail(PYR_ERR_INVALID_ARGUMENT, name + "shutter must be in (0, 1]");
+    if (p->samples < 1 || p->samples > PYR_MOTION_BLUR_MOST_SAMPLES) return fail(PYR_ERR_INVALID_ARGUMENT, name + "samples must be 1..64");
+    if (p->max_radius < 1 || p->max_radius > PYR_MOTION_BLUR_MOST_RADIUS) return fail(PYR_ERR_INVALID_ARGUMENT, name + "max_radius must be 1..64");
+    if (!(p->depth_softness > 0.0f) || !std::isfinite(p->depth_softness)) return fail(PYR_ERR_INVALID_ARGUMENT, name + "depth_softness must be finite and positive");
+    if (p->reserved[0] != 0 || p->reserved[1] != 0 || p->reserved[2] != 0) return fail(PYR_ERR_INVALID_ARGUMENT, name + "reserved must be 0");
+    return PYR_OK;
+}
+
+// The blur of `image` along `motion` into `out`, every buffer on the current device, enqueued on `stream`; the working memory is
+// allocated and freed in stream order around the three launches.
+int enqueue_motion_blur(const float* image, const PyrMotionPixel* motion, uint32_t width, uint32_t height, const PyrMotionBlurParams* p, float* out, hipStream_t stream) {
+    float* work = nullptr;
+    HIP_TRY(hipMallocAsync((void**)&work, motion_blur_work_bytes(width, height, p->max_radius), stream));
+    const MotionBlurLaunch L{image, motion, width, height, p->shutter, p->depth_softness, p->samples, p->max_radius, p->seed, work, out};
+    const int rc = launch_motion_blur(L, stream);
+    const hipError_t freed = hipFreeAsync(work, stream);
+    if (rc != PYR_OK) return rc;
+    if (freed != hipSuccess) return hip_fail(freed, "hipFreeAsync");
+    return PYR_OK;
+}
+
+} // namespace pyr
+
+namespace {
+
+// What both image entries of the motion blur refuse before a device is looked for.
+int check_motion_blur_args(const void* image, const void* motion, uint32_t width, uint32_t height, const PyrMotionBlurParams* p, const void* out) {
+    if (!image) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: image");
+    if (!motion) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: motion");
+    if (!out) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: out");
+    if (int bad = check_motion_blur_params(p, "params")) return bad;
+    if (width == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "width: an empty image");
+    if (height == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "height: an empty image");
+    return check_image_size(width, height);
+}
+
+bool ranges_overlap(const void* a, uint64_t a_bytes, const void* b, uint64_t b_bytes) {
+    const uint64_t a0 = (uint64_t)(uintptr_t)a, b0 = (uint64_t)(uintptr_t)b;
+    return a0 < b0 + b_bytes && b0 < a0 + a_bytes;
+}
+
+} // namespace
+
 extern "C" {
+
+int pyr_image_motion_blur_device(const float* image_device, const PyrMotionPixel* motion_device, uint32_t width, uint32_t height, const PyrMotionBlurParams* params,
+                                 float* out_device, int device, void* hip_stream) {
+    int rc = check_motion_blur_args(image_device, motion_device, width, height, params, out_device);
+    if (rc != PYR_OK) return rc;
+    if (((uintptr_t)motion_device & 15u) != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "motion_device must be 16-byte aligned"); // records are read as 16-byte vectors
+    const uint64_t pixels = (uint64_t)width * height;
+    if (ranges_overlap(out_device, pixels * 12, image_device, pixels * 12)) return fail(PYR_ERR_INVALID_ARGUMENT, "out_device overlaps image_device");
+    if (ranges_overlap(out_device, pixels * 12, motion_device, pixels * sizeof(PyrMotionPixel))) return fail(PYR_ERR_INVALID_ARGUMENT, "out_device overlaps motion_device");
+    if ((rc = check_device(device)) != PYR_OK) return rc;
+    HIP_TRY(hipSetDevice(device));
+    return enqueue_motion_blur(image_device, motion_device, width, height, params, out_device, (hipStream_t)hip_stream);
+}
+
+int pyr_image_motion_blur(const float* image, const PyrMotionPixel* motion, uint32_t width, uint32_t height, const PyrMotionBlurParams* params, float* out, int device) {
+    int rc = check_motion_blur_args(image, motion, width, height, params, out);
+    if (rc != PYR_OK || (rc = check_device(device)) != PYR_OK) return rc;
+    HIP_TRY(hipSetDevice(device));
+    const size_t count = (size_t)width * height, image_bytes = count * 3 * sizeof(float);
+    DeviceBuffer image_dev, motion_dev, out_dev;
+    if ((rc = image_dev.upload(image, image_bytes)) != PYR_OK || (rc = motion_dev.upload(motion, count * sizeof(PyrMotionPixel))) != PYR_OK) return rc;
+    if ((rc = out_dev.alloc(image_bytes)) != PYR_OK) return rc;
+    rc = enqueue_motion_blur((const float*)image_dev.ptr, (const PyrMotionPixel*)motion_dev.ptr, width, height, params, (float*)out_dev.ptr, nullptr);
+    HIP_TRY(hipDeviceSynchronize()); // before the buffers above are freed, whatever happened
+    if (rc != PYR_OK) return rc;
+    HIP_TRY(hipMemcpy(out, out_dev.ptr, image_bytes, hipMemcpyDeviceToHost));
+    return PYR_OK;
+}
 
 int pyr_image_reproject_device(const float* current_device, const PyrMotionPixel* motion_device, const float* history_device,
                                const PyrMotionPixel* history_motion_device, const float* history_count_device, uint32_t width, uint32_t height,

@@ -269,6 +269,27 @@ def reproject(current, motion, history=None, history_motion=None, history_count=
     return out, count
 
 
+def motion_blur_params(shutter=abi.PYR_MOTION_BLUR_SHUTTER, samples=abi.PYR_MOTION_BLUR_SAMPLES, max_radius=abi.PYR_MOTION_BLUR_MAX_RADIUS,
+                       depth_softness=abi.PYR_MOTION_BLUR_DEPTH_SOFTNESS, seed=0):
+    """abi.PyrMotionBlurParams: the shutter is open for `shutter` of the frame interval, a moving pixel takes `samples` taps along a
+    blur of at most `max_radius` pixels to either side, depths within `depth_softness` (relative) count as one surface."""
+    return abi.PyrMotionBlurParams(float(shutter), int(samples), int(max_radius), float(depth_softness), int(seed) & 0xFFFFFFFF)
+
+
+def motion_blur(image, motion, device=0, **params):
+    """float32 [height, width, 3]: the linear image `image` blurred along its motion records (pyr_image_motion_blur;
+    include/pyrite_gpu.h has the arithmetic). `motion`: the records of the frame the image shows (Renderer.motion, motion.RECORD
+    [height, width]) against the previous frame. `params`: motion_blur_params. Pixels that nothing moves near keep their bits."""
+    image = _linear_image(image)
+    h, w, _ = image.shape
+    motion = np.ascontiguousarray(motion)
+    assert motion.nbytes == C.sizeof(abi.PyrMotionPixel) * h * w
+    p = motion_blur_params(**params)
+    out = np.zeros(image.shape, dtype=np.float32)
+    check(lib().pyr_image_motion_blur(image.ctypes.data, motion.ctypes.data, w, h, C.byref(p), out.ctypes.data, int(device)))
+    return out
+
+
 def denoise_flag_problem(denoise, denoise_radius, pixel_samples=None, pass_samples=None):
     """What is wrong with --denoise / --denoise-radius, in the words pyrite_host_tool uses too, or None. `pixel_samples`: the
     render's budget once the project is loaded; `pass_samples`: --pass-samples, when given."""

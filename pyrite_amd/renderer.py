@@ -546,6 +546,19 @@ class Session:
         check(lib().pyr_session_motion(self.handle, C.byref(previous_camera.c), out.ctypes.data))
         return out
 
+    def motion_blurred(self, previous_camera: Camera, step=2.0, filter=None, white=None, **params):
+        """float32 [height, width, 3]: the film as it stands developed to linear sRGB and blurred along the motion records against
+        `previous_camera`, all on the session's device (pyr_session_motion_blurred; develop.motion_blur of linear() and
+        motion(previous_camera) gives the same floats). `params`: develop.motion_blur_params. The session's film is not touched."""
+        from .develop import develop_params, motion_blur_params
+
+        p, keep = develop_params(self._film, step, filter, white)
+        bp = motion_blur_params(**params)
+        out = np.zeros((self.height, self.width, 3), dtype=np.float32)
+        check(lib().pyr_session_motion_blurred(self.handle, C.byref(previous_camera.c), C.byref(p), C.byref(bp), out.ctypes.data))
+        del keep
+        return out
+
     def half_films(self):
         """The two half films of a session with `halves`, float32 [height, width, bins, 2] each."""
         a, b = np.zeros(self._shape, dtype=np.float32), np.zeros(self._shape, dtype=np.float32)
