@@ -1095,7 +1095,7 @@ int pyr_session_motion(PyrSession* session, const PyrCamera* previous_camera, Py
  *   H_c = Hc / Wt, n = fminf(N / Wt, max_history), out_c = H_c + (current_c - H_c) / (n + 1.0f), count_out = n + 1.0f.
  * A surface that was hidden a frame ago finds no tap of its shape and depth and starts again at 1: the disocclusion rule. One lane
  * owns a pixel, there are no atomics, two calls write the same bytes. Nothing clamps the history to the neighbourhood of `current`,
- * nothing reads a variance, nothing jitters the pixel centre. */
+ * nothing reads a variance, nothing jitters the pixel centre: pyr_image_temporal_resolve ("temporal resolve", below) does the first two. */
 #define PYR_REPROJECT_DEPTH_TOLERANCE 0.02f /* = PYR_DENOISE_SIGMA_DEPTH */
 #define PYR_REPROJECT_MAX_HISTORY 32.0f
 typedef struct PyrReprojectParams {
@@ -1181,6 +1181,68 @@ int pyr_image_motion_blur_device(const float* image_device, const PyrMotionPixel
  * passes may follow. Blocking. */
 int pyr_session_motion_blurred(PyrSession* session, const PyrCamera* previous_camera, const PyrDevelopParams* develop_params,
                                const PyrMotionBlurParams* blur_params, float* out);
+
+/* ---------------------------------------------------------------- temporal resolve ----
+ * pyr_image_reproject starts a pixel's mean again only when its surface was hidden a frame ago: it watches shape and depth. Light
+ * that changes on a surface that stays -- a shadow that moves off a floor, a lamp that changes colour, what a mirror shows -- is kept
+ * for up to max_history frames and trails behind everything that moves. The resolve fetches the history exactly as the
+ * reprojection does, then clips it to the box that the neighbourhood of `current` spans (Karis, "High Quality Temporal
+ * Supersampling", SIGGRAPH 2014 course; the variance box of Salvi, "An Excursion in Temporal Supersampling", GDC 2016) and lets a
+ * pixel whose history had to be clipped forget faster. It needs no scene.
+ *   `current`, `history`, `out`: width*height*3 f32 in linear light; `motion`, `history_motion`: the records; `history_count`,
+ * `count_out`: one f32 a pixel; the three history buffers are all NULL (a first frame) or all given. `noise`: optional (NULL =
+ * absent), width*height*3 f32, the error_out of pyr_image_denoise for the frame `current` shows, read as fabsf(noise): it widens the
+ * box by the noise the frame is known to have left. `clip_out`: optional (NULL = not wanted), one f32 a pixel.
+ *   All arithmetic is f32 and unfused, one rounding per operation, in the order written; sqrt and / are the correctly rounded ones;
+ * fminf and fmaxf drop a NaN operand as C's do. Per pixel p with record r:
+ *   1. Usable. A pixel q is usable iff the three floats of current[q] are finite and, when `noise` is given, those of noise[q] are
+ *      too. If p is not usable: out = current bit for bit, count_out = 1, clip_out = 0.
+ *   2. Moments. q runs over the (2*radius+1)^2 neighbourhood of p in raster order, dy outer, dx inner; pixels outside the image or
+ *      not usable are skipped; k is the number kept, as a float (p itself always is). Per channel c, each sum from 0.0f:
+ *        mean_c = (sum of current_c(q)) / k
+ *        in a second walk in the same order  d = current_c(q) - mean_c,  var_c = (sum of d*d) / k,  sigma_c = sqrt(var_c)
+ *        nbar_c = (sum of fabsf(noise_c(q))) / k, or 0.0f without a noise image
+ *      Two walks, not E[x^2] - E[x]^2: a lamp's pixels are in the hundreds, and the difference of squares loses there what the
+ *      clip needs.
+ *   3. History fetch: that of pyr_image_reproject, word for word -- the four taps, what makes a tap count, Wt, Hc, N. Where that
+ *      rule says "no history": out = current, count_out = 1, clip_out = 0. Otherwise H_c = Hc / Wt, n = fminf(N / Wt, max_history).
+ *   4. Clip.  e_c = gamma * sigma_c + noise_scale * nbar_c,  lo_c = mean_c - e_c,  hi_c = mean_c + e_c
+ *        H'_c = fminf(fmaxf(H_c, lo_c), hi_c)
+ *        q_c = fabsf(H_c - H'_c) / fmaxf(e_c, 1e-30f)              -- how far outside the box, in half-widths of the box
+ *        r = fminf(fmaxf(fmaxf(q_0, q_1), q_2), 1e30f)
+ *   5. Forget and blend.  n2 = n / (1.0f + response * r)
+ *        out_c = H'_c + (current_c - H'_c) / (n2 + 1.0f),  count_out = n2 + 1.0f,  clip_out = r
+ * A pixel whose history already lies in the box has r = 0, n2 = n and H' = H: it is, bit for bit, what pyr_image_reproject writes
+ * (a zero may differ in sign: fmaxf(-0, +0) is either). One lane owns a pixel, there are no atomics, two calls write the same
+ * bytes. The box is per channel in linear RGB and clamps, it does not clip towards the centre; the fetch is bilinear; no variance
+ * is carried across frames. One GPU. */
+#define PYR_TEMPORAL_RADIUS 1u
+#define PYR_TEMPORAL_GAMMA 1.0f
+#define PYR_TEMPORAL_NOISE_SCALE 1.0f
+#define PYR_TEMPORAL_RESPONSE 1.0f
+#define PYR_TEMPORAL_MOST_RADIUS 3u
+typedef struct PyrTemporalParams {
+    float depth_tolerance; /* >= 0, finite: as PyrReprojectParams; default PYR_REPROJECT_DEPTH_TOLERANCE */
+    float max_history;     /* >= 1, finite: as PyrReprojectParams; default PYR_REPROJECT_MAX_HISTORY */
+    uint32_t radius;       /* 1..PYR_TEMPORAL_MOST_RADIUS: the neighbourhood is (2*radius+1)^2 pixels */
+    float gamma;           /* >= 0, finite: the half-width of the box in standard deviations */
+    float noise_scale;     /* >= 0, finite: how far the noise image widens the box */
+    float response;        /* >= 0, finite: how fast a clipped pixel forgets; 0 = the reprojection's count */
+    uint32_t reserved[2];  /* 0 */
+} PyrTemporalParams; /* 32 bytes */
+/* Arguments are checked before a device is looked for: PYR_ERR_INVALID_ARGUMENT, with the argument named in pyr_last_error, for a
+ * null current, motion, params, out or count_out, history buffers of which some but not all are NULL, an empty image, a parameter
+ * out of range (a NaN is), a non-zero reserved word; PYR_ERR_UNSUPPORTED for more than 2^32 - 1 pixels; only then PYR_ERR_DEVICE.
+ * HOST buffers. Blocking. */
+int pyr_image_temporal_resolve(const float* current, const PyrMotionPixel* motion, const float* noise, const float* history, const PyrMotionPixel* history_motion,
+                               const float* history_count, uint32_t width, uint32_t height, const PyrTemporalParams* params, float* out, float* count_out,
+                               float* clip_out, int device);
+/* The same with every buffer resident on `device`, enqueued on `hip_stream`. The two record arrays must be 16-byte aligned, and no
+ * output may overlap an input or another output (PYR_ERR_INVALID_ARGUMENT otherwise). */
+int pyr_image_temporal_resolve_device(const float* current_device, const PyrMotionPixel* motion_device, const float* noise_device, const float* history_device,
+                                      const PyrMotionPixel* history_motion_device, const float* history_count_device, uint32_t width, uint32_t height,
+                                      const PyrTemporalParams* params, float* out_device, float* count_out_device, float* clip_out_device, int device,
+                                      void* hip_stream);
 
 #ifdef __cplusplus
 }

@@ -404,6 +404,21 @@ PyrReprojectParams reproject_params(float depth_tolerance = PYR_REPROJECT_DEPTH_
 Accumulated reproject(const std::vector<float>& current, const std::vector<PyrMotionPixel>& motion, uint32_t width, uint32_t height, const Accumulated* history = nullptr,
                       const std::vector<PyrMotionPixel>* history_motion = nullptr, const PyrReprojectParams& params = reproject_params(), int device = 0);
 
+// ---- temporal resolve (pyrite_gpu.h "temporal resolve"; pyrite_amd/develop.py resolve) ----
+// What resolve returns: reproject's image and count, and how far outside the clip box each pixel's history lay, [height][width] f32.
+struct Resolved {
+    std::vector<float> image, count, clip;
+};
+PyrTemporalParams temporal_params(float depth_tolerance = PYR_REPROJECT_DEPTH_TOLERANCE, float max_history = PYR_REPROJECT_MAX_HISTORY, uint32_t radius = PYR_TEMPORAL_RADIUS,
+                                  float gamma = PYR_TEMPORAL_GAMMA, float noise_scale = PYR_TEMPORAL_NOISE_SCALE, float response = PYR_TEMPORAL_RESPONSE);
+// reproject with the fetched history clipped to the neighbourhood of `current` (pyr_image_temporal_resolve). `history`: the image and
+// count of the previous call's result (a Resolved's image and count in an Accumulated), with the records of that frame; both null for a
+// first frame. `noise`: the error image of the denoiser for this frame, or null. A buffer of another size than the image's is a
+// ProjectError before the library is called.
+Resolved resolve(const std::vector<float>& current, const std::vector<PyrMotionPixel>& motion, uint32_t width, uint32_t height, const Accumulated* history = nullptr,
+                 const std::vector<PyrMotionPixel>* history_motion = nullptr, const std::vector<float>* noise = nullptr, const PyrTemporalParams& params = temporal_params(),
+                 int device = 0);
+
 // ---- motion blur over the motion records (pyrite_gpu.h "motion blur over the motion records"; pyrite_amd/develop.py motion_blur) ----
 PyrMotionBlurParams motion_blur_params(float shutter = PYR_MOTION_BLUR_SHUTTER, uint32_t samples = PYR_MOTION_BLUR_SAMPLES, uint32_t max_radius = PYR_MOTION_BLUR_MAX_RADIUS,
                                        float depth_softness = PYR_MOTION_BLUR_DEPTH_SOFTNESS, uint32_t seed = 0);

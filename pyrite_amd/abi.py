@@ -463,6 +463,14 @@ class PyrMotionBlurParams(C.Structure):
     _fields_ = [("shutter", C.c_float), ("samples", C.c_uint32), ("max_radius", C.c_uint32), ("depth_softness", C.c_float), ("seed", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
+PYR_TEMPORAL_RADIUS, PYR_TEMPORAL_GAMMA, PYR_TEMPORAL_NOISE_SCALE, PYR_TEMPORAL_RESPONSE, PYR_TEMPORAL_MOST_RADIUS = 1, 1.0, 1.0, 1.0, 3
+
+
+class PyrTemporalParams(C.Structure):
+    _fields_ = [("depth_tolerance", C.c_float), ("max_history", C.c_float), ("radius", C.c_uint32), ("gamma", C.c_float), ("noise_scale", C.c_float),
+                ("response", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
 PyrProgressFn = C.CFUNCTYPE(None, C.c_void_p, C.c_uint8, C.c_char_p)
 PyrPreviewFn = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, C.c_uint32)
 
@@ -573,6 +581,14 @@ ENTRY_POINTS = {
     "pyr_image_motion_blur": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PyrMotionBlurParams), C.c_void_p, C.c_int]),
     "pyr_image_motion_blur_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PyrMotionBlurParams), C.c_void_p, C.c_int, C.c_void_p]),
     "pyr_session_motion_blurred": (C.c_int, [C.c_void_p, C.POINTER(PyrCamera), C.POINTER(PyrDevelopParams), C.POINTER(PyrMotionBlurParams), C.c_void_p]),
+    "pyr_image_temporal_resolve": (
+        C.c_int,
+        [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.POINTER(PyrTemporalParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int],
+    ),
+    "pyr_image_temporal_resolve_device": (
+        C.c_int,
+        [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.POINTER(PyrTemporalParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
+    ),
 }
 
 

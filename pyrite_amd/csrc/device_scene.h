@@ -361,6 +361,25 @@ struct ReprojectLaunch {
 };
 int launch_reproject(const ReprojectLaunch& launch, void* stream);
 
+// kernels/temporal.hip: the temporal resolve (pyrite_gpu.h "temporal resolve"): the reprojection's fetch, the
+// history clipped to the neighbourhood of `current`
+struct TemporalLaunch {
+    const float* current;                 // device, height * width * 3 floats
+    const PyrMotionPixel* motion;         // device, height * width records
+    const float* noise;                   // device, height * width * 3 floats, or nullptr: the build that stages none
+    const float* history;                 // device, or all three nullptr: a first frame
+    const PyrMotionPixel* history_motion;
+    const float* history_count;
+    uint32_t width, height;
+    float depth_tolerance, max_history;
+    uint32_t radius; // 1..PYR_TEMPORAL_MOST_RADIUS
+    float gamma, noise_scale, response;
+    float* out;       // device, height * width * 3 floats
+    float* count_out; // device, height * width floats
+    float* clip_out;  // device, height * width floats, or nullptr
+};
+int launch_temporal(const TemporalLaunch& launch, void* stream);
+
 // kernels/motion_blur.hip: motion blur over the motion records (pyrite_gpu.h "motion blur over the motion records", DESIGN.md
 // section 9j). `work` is motion_blur_work_bytes() of device memory, 16-byte aligned, overwritten: four floats a pixel (hx, hy, len, z)
 // and twice four a tile (the tile maxima, the neighbour maxima). Three launches on `stream`: velocity, neighbour maximum, gather.

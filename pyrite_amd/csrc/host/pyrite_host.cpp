@@ -1579,6 +1579,24 @@ Accumulated reproject(const std::vector<float>& current, const std::vector<PyrMo
     return out;
 }
 
+// ---- temporal resolve ------------------------------------------------------------------------------------------------------------
+PyrTemporalParams temporal_params(float depth_tolerance, float max_history, uint32_t radius, float gamma, float noise_scale, float response) {
+    return PyrTemporalParams{depth_tolerance, max_history, radius, gamma, noise_scale, response, {0u, 0u}};
+}
+Resolved resolve(const std::vector<float>& current, const std::vector<PyrMotionPixel>& motion, uint32_t width, uint32_t height, const Accumulated* history,
+                 const std::vector<PyrMotionPixel>* history_motion, const std::vector<float>* noise, const PyrTemporalParams& params, int device) {
+    const size_t count = (size_t)width * height;
+    if ((history == nullptr) != (history_motion == nullptr)) throw ProjectError("resolve: the history and its motion records go together");
+    if (current.size() != count * 3 || motion.size() != count || (noise && noise->size() != count * 3) ||
+        (history && (history->image.size() != count * 3 || history->count.size() != count || history_motion->size() != count)))
+        throw ProjectError("resolve: buffer size does not match the image size");
+    Resolved out{std::vector<float>(count * 3, 0.0f), std::vector<float>(count, 0.0f), std::vector<float>(count, 0.0f)};
+    check_status(pyr_image_temporal_resolve(current.data(), motion.data(), noise ? noise->data() : nullptr, history ? history->image.data() : nullptr,
+                                            history ? history_motion->data() : nullptr, history ? history->count.data() : nullptr, width, height, &params,
+                                            out.image.data(), out.count.data(), out.clip.data(), device));
+    return out;
+}
+
 // ---- motion blur over the motion records ---------------------------------------------------------------------------------------
 PyrMotionBlurParams motion_blur_params(float shutter, uint32_t samples, uint32_t max_radius, float depth_softness, uint32_t seed) {
     return PyrMotionBlurParams{shutter, samples, max_radius, depth_softness, seed, {0u, 0u, 0u}};

@@ -1,6 +1,7 @@
 // image_ops.cpp -- the entry points of include/pyrite_gpu.h that take a device number and never see a scene: a film developed to
 // an 8-bit or a linear image, an image's luminance statistics, its tone mapping, the denoising of two half images, the
-// accumulation of linear images over frames along their motion records, the motion blur of one along them. What a
+// accumulation of linear images over frames along their motion records (plain, and with the history clipped to the current
+// frame's neighbourhood: the temporal resolve), the motion blur of one along them. What a
 // progressive session does with its own film through the same checks and launches (session.cpp) is declared in image_internal.h.
 #include <algorithm>
 #include <cmath>
@@ -228,6 +229,28 @@ int check_reproject_args(const void* current, const void* motion, const void* hi
     return check_image_size(width, height);
 }
 
+// What both temporal resolve entries refuse before a device is looked for.
+int check_temporal_args(const void* current, const void* motion, const void* history, const void* history_motion, const void* history_count, uint32_t width,
+                        uint32_t height, const PyrTemporalParams* p, const void* out, const void* count_out) {
+    if (!current) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: current");
+    if (!motion) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: motion");
+    if (!p) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: params");
+    if (!out) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: out");
+    if (!count_out) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: count_out");
+    const int given = (history != nullptr) + (history_motion != nullptr) + (history_count != nullptr);
+    if (given != 0 && given != 3) return fail(PYR_ERR_INVALID_ARGUMENT, "history, history_motion and history_count are all null or all given");
+    if (width == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "width: an empty image");
+    if (height == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "height: an empty image");
+    if (!(p->depth_tolerance >= 0.0f) || !std::isfinite(p->depth_tolerance)) return fail(PYR_ERR_INVALID_ARGUMENT, "params->depth_tolerance must be finite and not negative");
+    if (!(p->max_history >= 1.0f) || !std::isfinite(p->max_history)) return fail(PYR_ERR_INVALID_ARGUMENT, "params->max_history must be finite and at least 1");
+    if (p->radius < 1 || p->radius > PYR_TEMPORAL_MOST_RADIUS) return fail(PYR_ERR_INVALID_ARGUMENT, "params->radius must be 1..3");
+    if (!(p->gamma >= 0.0f) || !std::isfinite(p->gamma)) return fail(PYR_ERR_INVALID_ARGUMENT, "params->gamma must be finite and not negative");
+    if (!(p->noise_scale >= 0.0f) || !std::isfinite(p->noise_scale)) return fail(PYR_ERR_INVALID_ARGUMENT, "params->noise_scale must be finite and not negative");
+    if (!(p->response >= 0.0f) || !std::isfinite(p->response)) return fail(PYR_ERR_INVALID_ARGUMENT, "params->response must be finite and not negative");
+    if (p->reserved[0] != 0 || p->reserved[1] != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "params->reserved must be 0");
+    return PYR_OK;
+}
+
 } // namespace
 
 namespace pyr {
@@ -342,6 +365,69 @@ int pyr_image_reproject(const float* current, const PyrMotionPixel* motion, cons
     if (rc != PYR_OK) return rc;
     HIP_TRY(hipMemcpy(out, out_dev.ptr, image_bytes, hipMemcpyDeviceToHost));
     HIP_TRY(hipMemcpy(count_out, count_dev.ptr, count * sizeof(float), hipMemcpyDeviceToHost));
+    return PYR_OK;
+}
+
+int pyr_image_temporal_resolve_device(const float* current_device, const PyrMotionPixel* motion_device, const float* noise_device, const float* history_device,
+                                      const PyrMotionPixel* history_motion_device, const float* history_count_device, uint32_t width, uint32_t height,
+                                      const PyrTemporalParams* params, float* out_device, float* count_out_device, float* clip_out_device, int device,
+                                      void* hip_stream) {
+    int rc = check_temporal_args(current_device, motion_device, history_device, history_motion_device, history_count_device, width, height, params, out_device, count_out_device);
+    if (rc != PYR_OK) return rc;
+    if ((((uintptr_t)motion_device | (uintptr_t)history_motion_device) & 15u) != 0) // records are read as 16-byte vectors
+        return fail(PYR_ERR_INVALID_ARGUMENT, "motion_device and history_motion_device must be 16-byte aligned");
+    if ((rc = check_image_size(width, height)) != PYR_OK) return rc; // before the byte counts below are formed
+    const uint64_t pixels = (uint64_t)width * height;
+    const struct {
+        const void* at;
+        uint64_t bytes;
+        const char* name;
+    } outputs[3] = {{out_device, pixels * 12, "out_device"}, {count_out_device, pixels * 4, "count_out_device"}, {clip_out_device, pixels * 4, "clip_out_device"}},
+      inputs[6] = {{current_device, pixels * 12, "current_device"}, {motion_device, pixels * sizeof(PyrMotionPixel), "motion_device"},
+                   {noise_device, pixels * 12, "noise_device"},     {history_device, pixels * 12, "history_device"},
+                   {history_motion_device, pixels * sizeof(PyrMotionPixel), "history_motion_device"}, {history_count_device, pixels * 4, "history_count_device"}};
+    for (int a = 0; a < 3; ++a) {
+        if (!outputs[a].at) continue; // clip_out_device is optional
+        for (int b = 0; b < 6; ++b)
+            if (inputs[b].at && ranges_overlap(outputs[a].at, outputs[a].bytes, inputs[b].at, inputs[b].bytes))
+                return fail(PYR_ERR_INVALID_ARGUMENT, std::string(outputs[a].name) + " overlaps " + inputs[b].name);
+        for (int b = a + 1; b < 3; ++b)
+            if (outputs[b].at && ranges_overlap(outputs[a].at, outputs[a].bytes, outputs[b].at, outputs[b].bytes))
+                return fail(PYR_ERR_INVALID_ARGUMENT, std::string(outputs[a].name) + " overlaps " + outputs[b].name);
+    }
+    if ((rc = check_device(device)) != PYR_OK) return rc;
+    HIP_TRY(hipSetDevice(device));
+    const TemporalLaunch L{current_device, motion_device, noise_device, history_device, history_motion_device, history_count_device, width, height,
+                           params->depth_tolerance, params->max_history, params->radius, params->gamma, params->noise_scale, params->response,
+                           out_device, count_out_device, clip_out_device};
+    return launch_temporal(L, hip_stream);
+}
+
+int pyr_image_temporal_resolve(const float* current, const PyrMotionPixel* motion, const float* noise, const float* history, const PyrMotionPixel* history_motion,
+                               const float* history_count, uint32_t width, uint32_t height, const PyrTemporalParams* params, float* out, float* count_out,
+                               float* clip_out, int device) {
+    int rc = check_temporal_args(current, motion, history, history_motion, history_count, width, height, params, out, count_out);
+    if (rc != PYR_OK || (rc = check_image_size(width, height)) != PYR_OK || (rc = check_device(device)) != PYR_OK) return rc;
+    HIP_TRY(hipSetDevice(device));
+    const size_t count = (size_t)width * height, image_bytes = count * 3 * sizeof(float), record_bytes = count * sizeof(PyrMotionPixel);
+    DeviceBuffer current_dev, motion_dev, noise_dev, history_dev, history_motion_dev, history_count_dev, out_dev, count_dev, clip_dev;
+    if ((rc = current_dev.upload(current, image_bytes)) != PYR_OK || (rc = motion_dev.upload(motion, record_bytes)) != PYR_OK) return rc;
+    if (noise && (rc = noise_dev.upload(noise, image_bytes)) != PYR_OK) return rc;
+    if (history && ((rc = history_dev.upload(history, image_bytes)) != PYR_OK || (rc = history_motion_dev.upload(history_motion, record_bytes)) != PYR_OK ||
+                    (rc = history_count_dev.upload(history_count, count * sizeof(float))) != PYR_OK))
+        return rc;
+    if ((rc = out_dev.alloc(image_bytes)) != PYR_OK || (rc = count_dev.alloc(count * sizeof(float))) != PYR_OK) return rc;
+    if (clip_out && (rc = clip_dev.alloc(count * sizeof(float))) != PYR_OK) return rc;
+    const TemporalLaunch L{(const float*)current_dev.ptr, (const PyrMotionPixel*)motion_dev.ptr, noise ? (const float*)noise_dev.ptr : nullptr,
+                           history ? (const float*)history_dev.ptr : nullptr, history ? (const PyrMotionPixel*)history_motion_dev.ptr : nullptr,
+                           history ? (const float*)history_count_dev.ptr : nullptr, width, height, params->depth_tolerance, params->max_history, params->radius,
+                           params->gamma, params->noise_scale, params->response, (float*)out_dev.ptr, (float*)count_dev.ptr, clip_out ? (float*)clip_dev.ptr : nullptr};
+    rc = launch_temporal(L, nullptr);
+    HIP_TRY(hipDeviceSynchronize()); // before the buffers above are freed, whatever happened
+    if (rc != PYR_OK) return rc;
+    HIP_TRY(hipMemcpy(out, out_dev.ptr, image_bytes, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(count_out, count_dev.ptr, count * sizeof(float), hipMemcpyDeviceToHost));
+    if (clip_out) HIP_TRY(hipMemcpy(clip_out, clip_dev.ptr, count * sizeof(float), hipMemcpyDeviceToHost));
     return PYR_OK;
 }
 

@@ -269,6 +269,43 @@ def reproject(current, motion, history=None, history_motion=None, history_count=
     return out, count
 
 
+def temporal_params(depth_tolerance=abi.PYR_REPROJECT_DEPTH_TOLERANCE, max_history=abi.PYR_REPROJECT_MAX_HISTORY, radius=abi.PYR_TEMPORAL_RADIUS,
+                    gamma=abi.PYR_TEMPORAL_GAMMA, noise_scale=abi.PYR_TEMPORAL_NOISE_SCALE, response=abi.PYR_TEMPORAL_RESPONSE):
+    """abi.PyrTemporalParams: the reprojection's `depth_tolerance` and `max_history`; the history is clipped to mean +- (`gamma`
+    standard deviations + `noise_scale` times the noise image) of the (2 radius + 1)^2 neighbourhood of the current frame, and a
+    pixel clipped by r half-widths of that box keeps 1 / (1 + `response` r) of its count."""
+    return abi.PyrTemporalParams(float(depth_tolerance), float(max_history), int(radius), float(gamma), float(noise_scale), float(response))
+
+
+def resolve(current, motion, history=None, history_motion=None, history_count=None, noise=None, device=0, **params):
+    """(image, count, clip): reproject's running mean with the fetched history clipped to the neighbourhood of `current`, so that
+    light which changes on a surface that stays -- a shadow that moves on -- leaves no trail (pyr_image_temporal_resolve;
+    include/pyrite_gpu.h has the arithmetic). The arguments are reproject's; `noise`, optional, is the error image of `denoise` for
+    the frame `current` shows and widens the clip box. `params`: temporal_params. `clip` [height, width] float32 says how far
+    outside the box each pixel's history lay, 0 where it was kept as it was: there `image` and `count` are reproject's."""
+    current = _linear_image(current)
+    h, w, _ = current.shape
+    records = C.sizeof(abi.PyrMotionPixel) * h * w
+    motion = np.ascontiguousarray(motion)
+    assert motion.nbytes == records
+    given = [x is not None for x in (history, history_motion, history_count)]
+    if any(given):
+        if not all(given):
+            raise ValueError("history, history_motion and history_count go together")
+        history, history_motion = _linear_image(history), np.ascontiguousarray(history_motion)
+        history_count = np.ascontiguousarray(history_count, dtype=np.float32)
+        assert history.shape == current.shape and history_motion.nbytes == records and history_count.shape == (h, w)
+    if noise is not None:
+        noise = _linear_image(noise)
+        assert noise.shape == current.shape
+    p = temporal_params(**params)
+    out, count, clip = np.zeros(current.shape, dtype=np.float32), np.zeros((h, w), dtype=np.float32), np.zeros((h, w), dtype=np.float32)
+    ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
+    check(lib().pyr_image_temporal_resolve(current.ctypes.data, motion.ctypes.data, ptr(noise), ptr(history), ptr(history_motion), ptr(history_count), w, h, C.byref(p),
+                                           out.ctypes.data, count.ctypes.data, clip.ctypes.data, int(device)))
+    return out, count, clip
+
+
 def motion_blur_params(shutter=abi.PYR_MOTION_BLUR_SHUTTER, samples=abi.PYR_MOTION_BLUR_SAMPLES, max_radius=abi.PYR_MOTION_BLUR_MAX_RADIUS,
                        depth_softness=abi.PYR_MOTION_BLUR_DEPTH_SOFTNESS, seed=0):
     """abi.PyrMotionBlurParams: the shutter is open for `shutter` of the frame interval, a moving pixel takes `samples` taps along a
