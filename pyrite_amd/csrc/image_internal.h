@@ -1,5 +1,7 @@
-// image_internal.h -- what image_ops.cpp (film development, linear images, tone mapping and denoising without a scene) lets
-// session.cpp use on a session's own buffers and stream. Declarations only: image_ops.cpp defines them all.
+// image_internal.h -- what image_ops.cpp (film development, linear images, tone mapping, denoising and the filters over motion
+// records, without a scene) lets session.cpp use on a session's own buffers and stream: the checks of the parameter blocks, the
+// launch record of a development, and the enqueues that take a stream. Declarations only: image_ops.cpp defines them all; its
+// staging of host buffers and the pieces its entries' checks are composed from stay private to it.
 #pragma once
 #include <vector>
 

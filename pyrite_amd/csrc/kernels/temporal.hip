@@ -1,7 +1,8 @@
 // temporal.hip -- the temporal resolve (include/pyrite_gpu.h "temporal resolve"), a unit of its own: the
-// header spells the f32 operations and their order out, the kernel keeps both. The history fetch is reproject_kernel's
-// (kernels/reproject.hip), restated here so that neither unit reads the other; what is new is the neighbourhood of `current`,
-// (2*radius+1)^2 pixels read twice by every pixel, and that is staged: a workgroup owns a 16 x 16 tile and loads it with its
+// header spells the f32 operations and their order out, the kernel keeps both. The history fetch is the one reproject_kernel
+// calls (kernels/history_fetch.h): where nothing is clipped the two kernels write the same bits because they run the same
+// function, started here only for a usable pixel. What is new is the neighbourhood of `current`, (2*radius+1)^2 pixels read twice
+// by every pixel, and that is staged: a workgroup owns a 16 x 16 tile and loads it with its
 // radius-wide ring once into LDS, one 16-byte slot a pixel -- the three floats and the usable flag, decided at load time -- and a
 // second slot array for |noise| in the build that reads one. Both walks run from LDS.
 //   Layout. A wave is a strip of 4 rows x 16 pixels: the lanes of a row read consecutive slots, and a tile row is kPitch = 32
@@ -20,6 +21,7 @@
 
 #include "../api_internal.h"
 #include "../device_scene.h"
+#include "history_fetch.h"
 
 namespace pyr {
 
@@ -48,7 +50,6 @@ __global__ __launch_bounds__(kTile* kTile) void temporal_kernel(TemporalLaunch L
     const uint32_t tiles = tiles_x * tiles_y;
     const uint32_t radius = L.radius, span = kTile + 2 * radius, side = 2 * radius + 1;
     const uint32_t lx = threadIdx.x % kTile, ly = threadIdx.x / kTile;
-    const float width = (float)L.width, height = (float)L.height;
     for (uint32_t t = blockIdx.x; t < tiles; t += gridDim.x) {
         const uint32_t tile_y = t / tiles_x, tile_x = t - tile_y * tiles_x;
         const int64_t x_first = (int64_t)tile_x * kTile - radius, y_first = (int64_t)tile_y * kTile - radius;
@@ -78,36 +79,8 @@ __global__ __launch_bounds__(kTile* kTile) void temporal_kernel(TemporalLaunch L
             const float4* record = reinterpret_cast<const float4*>(L.motion + px);
             const float4 lo = record[0], hi = record[1]; // prev_x, prev_y, prev_depth, depth; shape, flags
             const uint32_t shape = __float_as_uint(hi.x), flags = __float_as_uint(hi.y);
-            float weight = 0.0f, sum[3] = {0.0f, 0.0f, 0.0f}, frames = 0.0f;
-            // the fetch of reproject_kernel, word for word
-            if (own.w != 0.0f && L.history != nullptr && (flags & PYR_MOTION_IN_FRONT) != 0u && isfinite(lo.x) && isfinite(lo.y)) {
-                const float gx = lo.x - 0.5f, gy = lo.y - 0.5f;
-                const float x0 = floorf(gx), y0 = floorf(gy);
-                const float fx = gx - x0, fy = gy - y0;
-                const float tap_x[4] = {x0, x0 + 1.0f, x0, x0 + 1.0f}, tap_y[4] = {y0, y0, y0 + 1.0f, y0 + 1.0f};
-                const float tap_w[4] = {(1.0f - fx) * (1.0f - fy), fx * (1.0f - fy), (1.0f - fx) * fy, fx * fy};
-                for (int k = 0; k < 4; ++k) {
-                    if (!(tap_x[k] >= 0.0f && tap_x[k] < width && tap_y[k] >= 0.0f && tap_y[k] < height)) continue; // in float: 1e30 never reaches a cast
-                    const uint32_t tx = (uint32_t)tap_x[k], ty = (uint32_t)tap_y[k];
-                    if (tx >= L.width || ty >= L.height) continue; // (float)width rounds up beyond 2^24: never an address outside the image
-                    const size_t tap = (size_t)ty * L.width + tx;
-                    const float4* theirs = reinterpret_cast<const float4*>(L.history_motion + tap);
-                    if (__float_as_uint(theirs[1].x) != shape) continue;
-                    if ((flags & PYR_MOTION_HIT) != 0u) {
-                        const float their_depth = theirs[0].w;
-                        if (!(fabsf(their_depth - lo.z) <= L.depth_tolerance * fmaxf(their_depth, lo.z))) continue;
-                    }
-                    const float count = L.history_count[tap];
-                    if (!(count > 0.0f)) continue;
-                    const float h[3] = {L.history[3 * tap], L.history[3 * tap + 1], L.history[3 * tap + 2]};
-                    if (!(isfinite(h[0]) && isfinite(h[1]) && isfinite(h[2]))) continue;
-                    const float w = tap_w[k];
-                    weight = weight + w;
-                    for (int c = 0; c < 3; ++c) sum[c] = sum[c] + w * h[c];
-                    frames = frames + w * count;
-                }
-            }
-            if (weight > 0.0f) { // usable, and a history to clip: only these pixels walk the neighbourhood
+            const HistoryFetch f = fetch_history(L.history, L.history_motion, L.history_count, L.width, L.height, L.depth_tolerance, lo, shape, flags, own.w != 0.0f);
+            if (f.weight > 0.0f) { // usable, and a history to clip: only these pixels walk the neighbourhood
                 const float current[3] = {own.x, own.y, own.z};
                 float total[3] = {0.0f, 0.0f, 0.0f}, total_noise[3] = {0.0f, 0.0f, 0.0f}, kept = 0.0f;
                 for (uint32_t dy = 0; dy < side; ++dy)
@@ -132,14 +105,14 @@ __global__ __launch_bounds__(kTile* kTile) void temporal_kernel(TemporalLaunch L
                         squares[1] = keep ? squares[1] + d1 * d1 : squares[1];
                         squares[2] = keep ? squares[2] + d2 * d2 : squares[2];
                     }
-                const float n = fminf(frames / weight, L.max_history);
+                const float n = fminf(f.frames / f.weight, L.max_history);
                 float clipped[3], r = 0.0f;
                 for (int c = 0; c < 3; ++c) {
                     const float sigma = sqrtf(squares[c] / kept);
                     const float nbar = NOISE ? total_noise[c] / kept : 0.0f;
                     const float e = L.gamma * sigma + L.noise_scale * nbar;
                     const float low = mean[c] - e, high = mean[c] + e;
-                    const float H = sum[c] / weight;
+                    const float H = f.sum[c] / f.weight;
                     clipped[c] = fminf(fmaxf(H, low), high);
                     const float q = fabsf(H - clipped[c]) / fmaxf(e, 1e-30f);
                     r = c == 0 ? q : fmaxf(r, q);

@@ -237,18 +237,17 @@ def denoise(a, b, albedo=None, pixels=None, device=0, **params):
         assert pixels.nbytes == h * w * C.sizeof(abi.PyrFeaturePixel)
     p = denoise_params(**params)
     out, error = np.zeros(a.shape, dtype=np.float32), np.zeros(a.shape, dtype=np.float32)
-    check(lib().pyr_image_denoise(a.ctypes.data, b.ctypes.data, albedo.ctypes.data if albedo is not None else None, pixels.ctypes.data if pixels is not None else None,
-                                  w, h, C.byref(p), out.ctypes.data, error.ctypes.data, int(device)))
+    check(lib().pyr_image_denoise(a.ctypes.data, b.ctypes.data, _ptr(albedo), _ptr(pixels), w, h, C.byref(p), out.ctypes.data, error.ctypes.data, int(device)))
     return out, error
 
 
-def reproject(current, motion, history=None, history_motion=None, history_count=None, depth_tolerance=abi.PYR_REPROJECT_DEPTH_TOLERANCE,
-              max_history=abi.PYR_REPROJECT_MAX_HISTORY, device=0):
-    """(out, count): the running mean of linear images over frames of a moving scene (pyr_image_reproject; include/pyrite_gpu.h has
-    the arithmetic). `current`: this frame, float32 [height, width, 3]; `motion`: its records (Renderer.motion, motion.RECORD
-    [height, width]). `history`, `history_motion`, `history_count`: the previous call's `out`, the records of that frame and its
-    `count` -- all None for a first frame. `count` [height, width] float32 is the number of frames a pixel's mean holds; a pixel
-    whose surface was hidden a frame ago starts again at 1."""
+def _ptr(a):
+    return a.ctypes.data if a is not None else None
+
+
+def _frame_and_history(current, motion, history, history_motion, history_count):
+    """What reproject and resolve are given, as the library reads it: (current, motion, history, history_motion, history_count,
+    height, width), contiguous, of the right types and sizes, the history all None or all given."""
     current = _linear_image(current)
     h, w, _ = current.shape
     records = C.sizeof(abi.PyrMotionPixel) * h * w
@@ -261,10 +260,20 @@ def reproject(current, motion, history=None, history_motion=None, history_count=
         history, history_motion = _linear_image(history), np.ascontiguousarray(history_motion)
         history_count = np.ascontiguousarray(history_count, dtype=np.float32)
         assert history.shape == current.shape and history_motion.nbytes == records and history_count.shape == (h, w)
+    return current, motion, history, history_motion, history_count, h, w
+
+
+def reproject(current, motion, history=None, history_motion=None, history_count=None, depth_tolerance=abi.PYR_REPROJECT_DEPTH_TOLERANCE,
+              max_history=abi.PYR_REPROJECT_MAX_HISTORY, device=0):
+    """(out, count): the running mean of linear images over frames of a moving scene (pyr_image_reproject; include/pyrite_gpu.h has
+    the arithmetic). `current`: this frame, float32 [height, width, 3]; `motion`: its records (Renderer.motion, motion.RECORD
+    [height, width]). `history`, `history_motion`, `history_count`: the previous call's `out`, the records of that frame and its
+    `count` -- all None for a first frame. `count` [height, width] float32 is the number of frames a pixel's mean holds; a pixel
+    whose surface was hidden a frame ago starts again at 1."""
+    current, motion, history, history_motion, history_count, h, w = _frame_and_history(current, motion, history, history_motion, history_count)
     p = abi.PyrReprojectParams(float(depth_tolerance), float(max_history))
     out, count = np.zeros(current.shape, dtype=np.float32), np.zeros((h, w), dtype=np.float32)
-    ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
-    check(lib().pyr_image_reproject(current.ctypes.data, motion.ctypes.data, ptr(history), ptr(history_motion), ptr(history_count), w, h, C.byref(p), out.ctypes.data,
+    check(lib().pyr_image_reproject(current.ctypes.data, motion.ctypes.data, _ptr(history), _ptr(history_motion), _ptr(history_count), w, h, C.byref(p), out.ctypes.data,
                                     count.ctypes.data, int(device)))
     return out, count
 
@@ -283,25 +292,13 @@ def resolve(current, motion, history=None, history_motion=None, history_count=No
     include/pyrite_gpu.h has the arithmetic). The arguments are reproject's; `noise`, optional, is the error image of `denoise` for
     the frame `current` shows and widens the clip box. `params`: temporal_params. `clip` [height, width] float32 says how far
     outside the box each pixel's history lay, 0 where it was kept as it was: there `image` and `count` are reproject's."""
-    current = _linear_image(current)
-    h, w, _ = current.shape
-    records = C.sizeof(abi.PyrMotionPixel) * h * w
-    motion = np.ascontiguousarray(motion)
-    assert motion.nbytes == records
-    given = [x is not None for x in (history, history_motion, history_count)]
-    if any(given):
-        if not all(given):
-            raise ValueError("history, history_motion and history_count go together")
-        history, history_motion = _linear_image(history), np.ascontiguousarray(history_motion)
-        history_count = np.ascontiguousarray(history_count, dtype=np.float32)
-        assert history.shape == current.shape and history_motion.nbytes == records and history_count.shape == (h, w)
+    current, motion, history, history_motion, history_count, h, w = _frame_and_history(current, motion, history, history_motion, history_count)
     if noise is not None:
         noise = _linear_image(noise)
         assert noise.shape == current.shape
     p = temporal_params(**params)
     out, count, clip = np.zeros(current.shape, dtype=np.float32), np.zeros((h, w), dtype=np.float32), np.zeros((h, w), dtype=np.float32)
-    ptr = lambda a: a.ctypes.data if a is not None else None  # noqa: E731
-    check(lib().pyr_image_temporal_resolve(current.ctypes.data, motion.ctypes.data, ptr(noise), ptr(history), ptr(history_motion), ptr(history_count), w, h, C.byref(p),
+    check(lib().pyr_image_temporal_resolve(current.ctypes.data, motion.ctypes.data, _ptr(noise), _ptr(history), _ptr(history_motion), _ptr(history_count), w, h, C.byref(p),
                                            out.ctypes.data, count.ctypes.data, clip.ctypes.data, int(device)))
     return out, count, clip
 

@@ -1,7 +1,8 @@
 """Linear images and tone mapping on the GPU (include/pyrite_gpu.h "linear images and tone mapping"): the linear sRGB image is what
 the 8-bit development encodes, byte for byte; XYZ and linear sRGB against a numpy f32 restatement of the trapezoid walk; two half
 films develop as their sum; the luminance statistics are exact; Reinhard's curve against its f32 restatement; a real picture that
-the 8-bit path clips; and the argument checks, none of which reaches a kernel."""
+the 8-bit path clips; the _device forms on tensors and a stream of the caller's against the host forms, byte for byte; and the
+argument checks, none of which reaches a kernel."""
 import ctypes as C
 import math
 import os
@@ -10,7 +11,7 @@ import numpy as np
 import pytest
 
 from pyrite_amd import abi, scenes
-from pyrite_amd._lib import lib
+from pyrite_amd._lib import check, lib
 from pyrite_amd.compiler import tables
 from pyrite_amd.develop import (_array_get, develop, develop_linear, develop_params, encode_hdr, image_stats, tone_params, tone_resolve, tonemap)
 from pyrite_amd.film import Film
@@ -350,7 +351,45 @@ def test_a_picture_the_8_bit_path_clips(gpu_lib, tmp_path):
     world.close()
 
 
-# ------------------------------------------------------------------------------------------------ 7. errors
+# ------------------------------------------------------------------------------------------------ 7. the _device forms
+def on_device(entry, *args):
+    """The bytes `entry`, a _device form, writes on device 0 and a stream of its own: every numpy array among `args` goes as a device
+    copy, the last of them is the output."""
+    import torch
+
+    side = torch.cuda.Stream()
+    held = [torch.from_numpy(a.view(np.uint8).reshape(-1).copy()).cuda() if isinstance(a, np.ndarray) else a for a in args]
+    side.wait_stream(torch.cuda.current_stream())  # the copies above
+    check(getattr(lib(), entry)(*[C.c_void_p(a.data_ptr()) if isinstance(a, torch.Tensor) else a for a in held], 0, C.c_void_p(side.cuda_stream)))
+    side.synchronize()
+    return [a for a in held if isinstance(a, torch.Tensor)][-1].cpu().numpy().tobytes()
+
+
+@pytest.mark.parametrize("shape", [FILMS[0], FILMS[3]], ids=lambda s: "%dx%dx%d" % s)
+def test_the_device_forms_write_the_bytes_the_host_forms_return(shape, gpu_lib):
+    """pyr_film_develop_device, pyr_film_develop_linear_device (one film and two), pyr_image_stats_device, pyr_image_tonemap_device:
+    the host forms run through the same enqueues, so on tensors and a stream of the caller's the bytes are the same, none excepted."""
+    film, film_b = random_film(*shape, seed=61), random_film(*shape, seed=62)
+    width, height, _ = shape
+    desc, grains, grains_b = film.desc(), np.ascontiguousarray(film.grains), np.ascontiguousarray(film_b.grains)
+    for step_size in (2.0, 30.0):  # the wave kernel, the thread-per-pixel kernel
+        p, keep = develop_params(film, step_size)
+        rgb8 = on_device("pyr_film_develop_device", C.byref(desc), grains, C.byref(p), np.zeros((height, width, 3), dtype=np.uint8))
+        assert rgb8 == develop(film, step_size).tobytes(), step_size
+        for halves in (None, film_b):
+            linear = on_device("pyr_film_develop_linear_device", C.byref(desc), grains, grains_b if halves is not None else None, C.byref(p), abi.PYR_LINEAR_SRGB,
+                               np.zeros((height, width, 3), dtype=f32))
+            image = develop_linear(film, "srgb", film_b=halves, step_size=step_size)
+            assert linear == image.tobytes(), (step_size, halves is not None)
+        del keep
+        stats = on_device("pyr_image_stats_device", image, width, height, np.zeros(C.sizeof(abi.PyrImageStats), dtype=np.uint8))
+        assert stats == bytes(image_stats(image)), step_size
+        tone = abi.PyrToneParams(abi.PYR_TONE_REINHARD, 0.37, 1.5, abi.PYR_TONE_KEY, abi.PYR_TONE_PERCENTILE, abi.PYR_TONE_WHITE_PERCENTILE)
+        mapped = on_device("pyr_image_tonemap_device", image, width, height, C.byref(tone), np.zeros((height, width, 3), dtype=np.uint8))
+        assert mapped == tonemap(image, tone).tobytes(), step_size
+
+
+# ------------------------------------------------------------------------------------------------ 8. errors
 def test_invalid_arguments_are_refused_before_any_kernel(gpu_lib):
     L = lib()
     INVALID, UNSUPPORTED, DEVICE = abi.PYR_ERR_INVALID_ARGUMENT, abi.PYR_ERR_UNSUPPORTED, abi.PYR_ERR_DEVICE
