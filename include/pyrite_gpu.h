@@ -1244,6 +1244,64 @@ int pyr_image_temporal_resolve_device(const float* current_device, const PyrMoti
                                       const PyrTemporalParams* params, float* out_device, float* count_out_device, float* clip_out_device, int device,
                                       void* hip_stream);
 
+/* ---------------------------------------------------------------- glare ----
+ * Both tone curves turn a pixel of 40 and one of 4000 into the same white with the same hard edge. The glare is what a lens or an
+ * eye adds: a little of every pixel's light scattered over its surroundings with a long tail, so that what is brighter than white
+ * shows by the glow around it. The point spread is the normalised sum of L blurs, each twice as wide as the one before, computed
+ * as a pyramid: L halvings of the source, then L doublings that add a level on the way up (the dual filtering used for bloom in
+ * real-time renderers, e.g. Jimenez, "Next Generation Post Processing in Call of Duty: Advanced Warfare", SIGGRAPH 2014 course).
+ * It needs no scene. `image`, `out`: width*height*3 f32 in linear light.
+ *   All arithmetic is f32 and unfused, one rounding per operation, in the order written; / is the correctly rounded one;
+ * clamp01(v) = fminf(fmaxf(v, 0.0f), 1.0f) as above, so a NaN becomes 0.
+ *   Kept pixels. A pixel p whose three floats are not all finite is not kept: out[p] = image[p] bit for bit, and its source is 0.
+ *   Source S0 of a kept pixel (R, G, B), with Y = (0.2126f*R + 0.7152f*G) + 0.0722f*B as in the statistics:
+ *     threshold == 0:  S0 = image, the same bits (no multiply).
+ *     otherwise:       k = clamp01((Y - threshold) / fmaxf(Y, 1e-30f)),  S0.c = image.c * k.
+ *   Level sizes. w_0 = width, h_0 = height, w_{l+1} = (w_l + 1) / 2, h likewise (integer division). L = min(levels, the number of
+ *     steps until a level is 1 x 1). L = 0 for a 1 x 1 image: out = image, bit for bit.
+ *   Down, S_{l+1} from S_l: separable, rows first, then columns. With the values a, b, c, d of the taps at 2x-1, 2x, 2x+1, 2x+2,
+ *     each tap clamped to [0, w_l - 1]:
+ *       (a + d) * 0.125f + (b + c) * 0.375f
+ *     The columns do the same to the row results (taps at 2y-1 .. 2y+2 clamped to [0, h_l - 1]); a row result is an f32.
+ *   Up, Up(T) from level l+1 to level l: separable, rows first, then columns. With i = x >> 1:
+ *       even x:  T[i] * 0.75f + T[max(i-1, 0)] * 0.25f
+ *       odd x:   T[i] * 0.75f + T[min(i+1, w_{l+1}-1)] * 0.25f
+ *     and the columns the same on the row results with j = y >> 1 and h_{l+1}.
+ *   Weights, on the host in f32:  g_1 = 1.0f,  g_{l+1} = g_l * falloff,  G = ((g_1 + g_2) + ...) + g_L,  inv = 1.0f / G.
+ *   Accumulate.  T_L = S_L * g_L;   T_l = S_l * g_l + Up(T_{l+1}) for l = L-1 .. 1;   B = Up(T_1) * inv.
+ *   Compose, per kept pixel:  out.c = (image.c - strength * S0.c) + strength * B.c.
+ * This is a convolution with (1 - strength) * delta + strength * PSF. Every stage's weights sum to 1, so a constant image stays
+ * constant; away from the border light is moved, not made. At the border the taps are clamped, not dropped and renormalised: that
+ * keeps a constant image constant and gives up conservation there -- the edge pixels count more than once, so a bright pixel at
+ * the border spreads a little more light than it loses. With falloff = 1 the response to an impulse falls roughly as r^-2.
+ *   One lane owns a pixel, there are no atomics, two calls write the same bytes. No streaks, stars or ghosts, no aperture-shaped or
+ * wavelength-dependent point spread. One GPU.
+ *   The defaults are a maintainer's choice of a plausible eye, not measured values. */
+#define PYR_GLARE_STRENGTH 0.1f
+#define PYR_GLARE_LEVELS 6u
+#define PYR_GLARE_THRESHOLD 0.0f
+#define PYR_GLARE_FALLOFF 1.0f
+#define PYR_GLARE_MOST_LEVELS 12u
+typedef struct PyrGlareParams {
+    float strength;       /* finite, in (0, 1]: the share of the source that is spread */
+    uint32_t levels;      /* 1..PYR_GLARE_MOST_LEVELS; more than the image has count as all it has */
+    float threshold;      /* finite, >= 0: luminance below which a pixel spreads nothing; 0 = every kept pixel spreads */
+    float falloff;        /* finite, in (0, 4]: the weight of a level over that of the level before it */
+    uint32_t reserved[4]; /* 0 */
+} PyrGlareParams; /* 32 bytes */
+/* Arguments are checked before a device is looked for: PYR_ERR_INVALID_ARGUMENT, with the argument named in pyr_last_error, for a
+ * null image, params or out, an empty image, a parameter out of range (a NaN is), a non-zero reserved word; PYR_ERR_UNSUPPORTED
+ * for more than 2^32 - 1 pixels; only then PYR_ERR_DEVICE. HOST buffers. Blocking. */
+int pyr_image_glare(const float* image, uint32_t width, uint32_t height, const PyrGlareParams* params, float* out, int device);
+/* The same with both buffers resident on `device`, enqueued on `hip_stream`. out may not overlap image (PYR_ERR_INVALID_ARGUMENT
+ * otherwise). Working memory -- levels 1..L, 16 bytes a pixel: fewer than width*height/3 + width + height + 12 pixels -- is
+ * allocated and freed in stream order. */
+int pyr_image_glare_device(const float* image_device, uint32_t width, uint32_t height, const PyrGlareParams* params, float* out_device, int device, void* hip_stream);
+/* What pyr_session_linear (PYR_LINEAR_SRGB) and the glare do, composed on the session's stream and device: nothing but the result
+ * crosses to the host. out = HOST, height*width*3 floats. The session's film is not touched, and further passes may follow.
+ * Blocking. */
+int pyr_session_glared(PyrSession* session, const PyrDevelopParams* develop_params, const PyrGlareParams* glare_params, float* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -427,6 +427,17 @@ PyrMotionBlurParams motion_blur_params(float shutter = PYR_MOTION_BLUR_SHUTTER, 
 std::vector<float> motion_blur(const std::vector<float>& image, const std::vector<PyrMotionPixel>& motion, uint32_t width, uint32_t height,
                                const PyrMotionBlurParams& params = motion_blur_params(), int device = 0);
 
+// ---- glare (pyrite_gpu.h "glare"; pyrite_amd/develop.py glare) ----
+PyrGlareParams glare_params(float strength = PYR_GLARE_STRENGTH, uint32_t levels = PYR_GLARE_LEVELS, float threshold = PYR_GLARE_THRESHOLD, float falloff = PYR_GLARE_FALLOFF);
+// The linear image `image`, [height][width][3] f32, with the glare of a lens or an eye added on the GPU (pyr_image_glare). A buffer
+// of another size than the image's is a ProjectError before the library is called.
+std::vector<float> glare(const std::vector<float>& image, uint32_t width, uint32_t height, const PyrGlareParams& params = glare_params(), int device = 0);
+// What is wrong with --glare / --glare-levels / --glare-threshold, in the words both front ends print, or "" (pyrite_amd/develop.py
+// glare_flag_problem). `glare`: the strength as it was given, or nothing without --glare.
+std::string glare_flag_problem(const std::optional<std::string>& glare, const std::optional<long>& glare_levels, const std::optional<double>& glare_threshold);
+// The parameters of --glare [STRENGTH] --glare-levels N --glare-threshold T, or nothing without --glare (pyrite_amd/develop.py glare_from_flags).
+std::optional<PyrGlareParams> glare_from_flags(const std::optional<std::string>& glare, const std::optional<long>& glare_levels, const std::optional<double>& glare_threshold);
+
 struct Progress { // renderer/mod.rs:229-232
     uint8_t progress;
     const char* message;
@@ -500,6 +511,9 @@ class Session {
     // pyr_session_motion_blurred: the film as it stands in linear sRGB, blurred along the records against `previous_camera`, on the session's device
     std::vector<float> motion_blurred(const Camera& previous_camera, const PyrMotionBlurParams& params = motion_blur_params(), float step_size = 2.0f,
                                       const std::optional<Expression>& filter = std::nullopt, const std::optional<Expression>& white = std::nullopt);
+    // pyr_session_glared: the film as it stands in linear sRGB with the glare added, on the session's device; the film is not touched
+    std::vector<float> glared(const PyrGlareParams& params = glare_params(), float step_size = 2.0f, const std::optional<Expression>& filter = std::nullopt,
+                              const std::optional<Expression>& white = std::nullopt);
     // pyr_session_denoised: the two half films developed to linear sRGB and cross filtered on the session's device; with `guides` the
     // feature pass (grid, albedo_bins) runs first and steers the filter. Needs halves and two passes; the films are not touched.
     Denoised denoised(const PyrDenoiseParams& params = denoise_params(), bool guides = true, float step_size = 2.0f, const std::optional<Expression>& filter = std::nullopt,

@@ -5,7 +5,8 @@
     python -m pyrite_amd path/to/project.lua [-o out.png] [--seed N] [--device D] [--spp N] [--size WxH]
                          [--pass-samples N] [--preview PATH] [--preview-every SECONDS] [--noise]
                          [--features PREFIX] [--features-grid N] [--hdr PATH] [--exposure EV|auto] [--tone clip|reinhard]
-                         [--denoise] [--denoise-radius N] [--build host|device]
+                         [--denoise] [--denoise-radius N] [--glare [STRENGTH]] [--glare-levels N] [--glare-threshold T]
+                         [--build host|device]
 
 With --pass-samples, --preview or --noise the render runs as a progressive session (pyr_session_*): passes of N samples per pixel
 over the whole image, the preview image rewritten from the live film every SECONDS or more (main.rs:261-299; developed on the GPU
@@ -24,6 +25,11 @@ With --denoise the render runs as a session with two half films, in an even numb
 --pass-samples is not given; an odd number of samples per pixel is refused), and the final PNG and the --hdr image are written
 from the denoised linear image (pyr_session_denoised with the feature pass as its guide; window radius N, default 5): the PNG
 through the tone curve, which without --exposure / --tone is the clip at exposure 1, the encoder of the plain PNG.
+
+With --glare the final image takes the linear path (the denoised image with --denoise) and the glare of a lens or an eye is added
+to it (pyr_image_glare: STRENGTH of every pixel's light, default 0.1, spread over N blurs of doubling width, default 6; with
+--glare-threshold T only what lies above the luminance T): before the statistics of an automatic exposure are taken and before the
+tone curve, which without --exposure / --tone is the clip at exposure 1. The --hdr image is the glared one. Previews have no glare.
 
 With --build the acceleration structure is built by the named builder (host: one CPU thread, the default; device: the same tree from
 the GPU, pyr_scene_create_with) and one line with the builder used and the stage times of scene creation goes to stderr."""
@@ -93,21 +99,26 @@ def main(argv=None):
     ap.add_argument("--tone", default=None, metavar="clip|reinhard", help="tone curve of the PNG and the previews (reinhard alone means --exposure auto)")
     ap.add_argument("--denoise", action="store_true", help="write the PNG and the --hdr image from the denoised linear image of two half films")
     ap.add_argument("--denoise-radius", type=int, default=None, metavar="N", help="window radius of --denoise (1 to 10, default 5)")
+    ap.add_argument("--glare", nargs="?", const=str(0.1), default=None, metavar="STRENGTH", help="add glare to the final image: the share of the light that is spread (above 0, at most 1; default 0.1)")
+    ap.add_argument("--glare-levels", type=int, default=None, metavar="N", help="blurs of doubling width the glare sums (1 to 12, default 6)")
+    ap.add_argument("--glare-threshold", type=float, default=None, metavar="T", help="luminance below which a pixel spreads nothing (default 0: every pixel spreads)")
     ap.add_argument("--build", default=None, choices=["host", "device"], help="who builds the BVH (default host); given, the stage times of scene creation go to stderr")
     args = ap.parse_args(argv)
-    from .develop import denoise_flag_problem, tone_flag_problem, tone_from_flags
+    from .develop import denoise_flag_problem, glare_flag_problem, glare_from_flags, tone_flag_problem, tone_from_flags
     from .features import features_flag_problem
 
     problem = (progressive_flag_problem(args.pass_samples, args.preview, args.preview_every, args.noise) or features_flag_problem(args.features, args.features_grid)
-               or tone_flag_problem(args.hdr, args.exposure, args.tone) or denoise_flag_problem(args.denoise, args.denoise_radius))
+               or tone_flag_problem(args.hdr, args.exposure, args.tone) or denoise_flag_problem(args.denoise, args.denoise_radius)
+               or glare_flag_problem(args.glare, args.glare_levels, args.glare_threshold))
     if problem:
         print("error: " + problem, file=sys.stderr)
         return 2
 
     args.tone_params = tone_from_flags(args.exposure, args.tone)
+    args.glare_params = glare_from_flags(args.glare, args.glare_levels, args.glare_threshold)
 
     from . import lua_project, scenes
-    from .develop import develop, develop_linear, save_linear, save_png, tonemap
+    from .develop import develop, develop_linear, glare, save_linear, save_png, tonemap
 
     project, base_dir = lua_project.load_project(args.project)
     if args.size:
@@ -144,9 +155,11 @@ def main(argv=None):
     linear = None
     if args.denoise:
         linear = args.denoised
-    elif args.hdr or args.tone_params is not None:
+    elif args.hdr or args.tone_params is not None or args.glare_params is not None:
         linear = develop_linear(film, "srgb", filter=image.get("filter"), white=image.get("white"), device=args.device)
-    if args.tone_params is not None or args.denoise:
+    if args.glare_params is not None:  # before the statistics of an automatic exposure, which tonemap takes
+        linear = glare(linear, device=args.device, **args.glare_params)
+    if args.tone_params is not None or args.denoise or args.glare_params is not None:
         rgb = tonemap(linear, args.tone_params, device=args.device)
     else:
         rgb = develop(film, filter=image.get("filter"), white=image.get("white"), device=args.device)

@@ -471,6 +471,13 @@ class PyrTemporalParams(C.Structure):
                 ("response", C.c_float), ("reserved", C.c_uint32 * 2)]
 
 
+PYR_GLARE_STRENGTH, PYR_GLARE_LEVELS, PYR_GLARE_THRESHOLD, PYR_GLARE_FALLOFF, PYR_GLARE_MOST_LEVELS = 0.1, 6, 0.0, 1.0, 12
+
+
+class PyrGlareParams(C.Structure):
+    _fields_ = [("strength", C.c_float), ("levels", C.c_uint32), ("threshold", C.c_float), ("falloff", C.c_float), ("reserved", C.c_uint32 * 4)]
+
+
 PyrProgressFn = C.CFUNCTYPE(None, C.c_void_p, C.c_uint8, C.c_char_p)
 PyrPreviewFn = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, C.c_uint32)
 
@@ -589,6 +596,9 @@ ENTRY_POINTS = {
         C.c_int,
         [C.c_void_p] * 6 + [C.c_uint32, C.c_uint32, C.POINTER(PyrTemporalParams), C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p],
     ),
+    "pyr_image_glare": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PyrGlareParams), C.c_void_p, C.c_int]),
+    "pyr_image_glare_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PyrGlareParams), C.c_void_p, C.c_int, C.c_void_p]),
+    "pyr_session_glared": (C.c_int, [C.c_void_p, C.POINTER(PyrDevelopParams), C.POINTER(PyrGlareParams), C.c_void_p]),
 }
 
 

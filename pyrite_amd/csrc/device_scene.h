@@ -395,6 +395,20 @@ struct MotionBlurLaunch {
 size_t motion_blur_work_bytes(uint32_t width, uint32_t height, uint32_t max_radius);
 int launch_motion_blur(const MotionBlurLaunch& launch, void* stream);
 
+// kernels/glare.hip: the glare of a linear image (pyrite_gpu.h "glare"). `work` is glare_work_bytes() of
+// device memory, 16-byte aligned, overwritten: levels 1..L of the pyramid, one after the other, four floats a pixel. L downs, L - 1
+// ups and the compose on `stream`, the steps of the small levels in one launch (the tail); a 1 x 1 image is copied.
+struct GlareLaunch {
+    const float* image; // device, height * width * 3 floats
+    uint32_t width, height;
+    float strength, threshold, falloff;
+    uint32_t levels; // as given: 1..PYR_GLARE_MOST_LEVELS; the launcher takes the smaller of it and what the image has
+    float* work;
+    float* out; // device, height * width * 3 floats; does not overlap image
+};
+size_t glare_work_bytes(uint32_t width, uint32_t height, uint32_t levels);
+int launch_glare(const GlareLaunch& launch, void* stream);
+
 // launchers (kernels/main.hip)
 // wide_vm: the scene has a program that only the wide interpreter build (kernels/wide.hip) holds
 int launch_render(const DevScene& scene, const RenderLaunch& launch, bool with_counters, void* stream, int num_cus, bool wide_vm = false);

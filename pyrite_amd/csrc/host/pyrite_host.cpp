@@ -1617,6 +1617,39 @@ std::vector<float> Session::motion_blurred(const Camera& previous_camera, const 
     return out;
 }
 
+// ---- glare ---------------------------------------------------------------------------------------------------------------------
+PyrGlareParams glare_params(float strength, uint32_t levels, float threshold, float falloff) { return PyrGlareParams{strength, levels, threshold, falloff, {0u, 0u, 0u, 0u}}; }
+std::vector<float> glare(const std::vector<float>& image, uint32_t width, uint32_t height, const PyrGlareParams& params, int device) {
+    if (image.size() != (size_t)width * height * 3) throw ProjectError("glare: buffer size does not match the image size");
+    std::vector<float> out(image.size(), 0.0f);
+    check_status(pyr_image_glare(image.data(), width, height, &params, out.data(), device));
+    return out;
+}
+std::vector<float> Session::glared(const PyrGlareParams& params, float step_size, const std::optional<Expression>& filter, const std::optional<Expression>& white) {
+    const DevelopSetup setup(shape_, filter, white, step_size);
+    std::vector<float> out((size_t)width_ * height_ * 3, 0.0f);
+    check_status(pyr_session_glared(handle_, &setup.p, &params, out.data()));
+    return out;
+}
+std::string glare_flag_problem(const std::optional<std::string>& glare, const std::optional<long>& glare_levels, const std::optional<double>& glare_threshold) {
+    if (!glare) {
+        if (glare_levels) return "--glare-levels needs --glare";
+        if (glare_threshold) return "--glare-threshold needs --glare";
+        return "";
+    }
+    char* end = nullptr;
+    const double strength = std::strtod(glare->c_str(), &end);
+    if (glare->empty() || *end != 0 || !(strength > 0.0 && strength <= 1.0)) return "--glare must be a strength above 0 and at most 1";
+    if (glare_levels && (*glare_levels < 1 || *glare_levels > (long)PYR_GLARE_MOST_LEVELS)) return "--glare-levels must be 1 to " + std::to_string(PYR_GLARE_MOST_LEVELS);
+    if (glare_threshold && !(std::isfinite(*glare_threshold) && *glare_threshold >= 0.0)) return "--glare-threshold must be a finite number that is not negative";
+    return "";
+}
+std::optional<PyrGlareParams> glare_from_flags(const std::optional<std::string>& glare, const std::optional<long>& glare_levels, const std::optional<double>& glare_threshold) {
+    if (!glare) return std::nullopt;
+    return glare_params((float)std::strtod(glare->c_str(), nullptr), glare_levels ? (uint32_t)*glare_levels : PYR_GLARE_LEVELS,
+                        glare_threshold ? (float)*glare_threshold : PYR_GLARE_THRESHOLD);
+}
+
 // ---- first-hit feature images --------------------------------------------------------------------------------------------------
 Features Renderer::features(uint32_t width, uint32_t height, const Camera& camera, World& world, uint32_t grid, uint32_t albedo_bins, int device) const {
     Features out{Film(width, height, albedo_bins, spectrum_span[0], spectrum_span[1]), std::vector<PyrFeaturePixel>((size_t)width * height)};

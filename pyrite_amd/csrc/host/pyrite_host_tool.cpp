@@ -5,6 +5,7 @@
 //   pyrite_host_tool dump-project   <project.lua> <texel dir | -> <out.bin>    the same for a project file (lua_project.cpp)
 //   pyrite_host_tool render-project <project.lua> <texel dir | -> <seed> <out.png> [film.bin]   what `pyrite project.lua` does (main.rs:46-330)
 //                                   [--size WxH] [--spp N] [--features PREFIX] [--features-grid N] [--hdr PATH] [--exposure EV|auto] [--tone clip|reinhard]
+//                                   [--glare [STRENGTH]] [--glare-levels N] [--glare-threshold T]
 //                                   [--build host|device] and the progressive flags of python -m pyrite_amd
 //   pyrite_host_tool encode-features <records.bin> <normal.rgb> <depth.rgb>    PyrFeaturePixel[n] -> the 8-bit normal and depth images, raw RGB (no GPU)
 //   pyrite_host_tool intersect <scene> <data_dir> <rays.f32> <hits.bin>       World::intersect for a ray batch ([n][6] f32 -> PyrHit[n])
@@ -241,7 +242,7 @@ int main(int argc, char** argv) {
             write_dump(argv[4], flat, loaded.project);
             return 0;
         }
-        if (argc >= 6 && std::string(argv[1]) == "render-project") { // render-project <project.lua> <texel dir | -> <seed> <out.png> [film.bin] [--pass-samples N] [--preview PATH] [--preview-every SECONDS] [--noise] [--denoise] [--denoise-radius N] [--build host|device]
+        if (argc >= 6 && std::string(argv[1]) == "render-project") { // render-project <project.lua> <texel dir | -> <seed> <out.png> [film.bin] [--pass-samples N] [--preview PATH] [--preview-every SECONDS] [--noise] [--denoise] [--denoise-radius N] [--glare [STRENGTH]] [--glare-levels N] [--glare-threshold T] [--build host|device]
             // the flags of python -m pyrite_amd: a progressive session with previews (main.rs:261-299) instead of one blocking call
             std::optional<long> pass_samples;
             std::string preview_path, film_path;
@@ -252,6 +253,9 @@ int main(int argc, char** argv) {
             std::optional<std::string> hdr, exposure, tone_name;
             bool denoise_flag = false;
             std::optional<long> denoise_radius;
+            std::optional<std::string> glare_strength; // --glare [STRENGTH]: the next argument unless it is a flag, as argparse's nargs="?" reads it (a film path goes before it)
+            std::optional<long> glare_levels;
+            std::optional<double> glare_threshold;
             std::optional<std::string> build_name; // --build host|device: who builds the BVH; given, the stage times go to stderr
             for (int i = 6; i < argc; ++i) {
                 const std::string a = argv[i];
@@ -281,6 +285,12 @@ int main(int argc, char** argv) {
                     denoise_flag = true;
                 else if (a == "--denoise-radius")
                     denoise_radius = std::strtol(value(), nullptr, 10);
+                else if (a == "--glare")
+                    glare_strength = i + 1 < argc && std::string(argv[i + 1]).rfind("--", 0) != 0 ? argv[++i] : "0.1";
+                else if (a == "--glare-levels")
+                    glare_levels = std::strtol(value(), nullptr, 10);
+                else if (a == "--glare-threshold")
+                    glare_threshold = std::strtod(value(), nullptr);
                 else if (a == "--build")
                     build_name = value();
                 else if (a == "--size")
@@ -296,12 +306,14 @@ int main(int argc, char** argv) {
             if (problem.empty()) problem = features_flag_problem(!features_prefix.empty(), features_grid);
             if (problem.empty()) problem = tone_flag_problem(hdr, exposure, tone_name);
             if (problem.empty()) problem = denoise_flag_problem(denoise_flag, denoise_radius);
+            if (problem.empty()) problem = glare_flag_problem(glare_strength, glare_levels, glare_threshold);
             if (problem.empty() && build_name && *build_name != "host" && *build_name != "device") problem = "--build takes host or device";
             if (!problem.empty()) {
                 std::fprintf(stderr, "error: %s\n", problem.c_str());
                 return 2;
             }
             const std::optional<PyrToneParams> tone = tone_from_flags(exposure, tone_name);
+            const std::optional<PyrGlareParams> glare_p = glare_from_flags(glare_strength, glare_levels, glare_threshold);
             LoadedProject loaded = load_project(argv[2], std::string(argv[3]) == "-" ? TextureLoader() : texel_files(argv[3]));
             if (!size.empty()) { // WIDTHxHEIGHT, as python -m pyrite_amd --size
                 char* rest = nullptr;
@@ -359,9 +371,10 @@ int main(int argc, char** argv) {
                 r.render(film, cam, *world);
             }
             std::printf("Saving final result...\n"); // main.rs:313
-            if (!denoise_flag && (hdr || tone)) linear = develop_linear(film, PYR_LINEAR_SRGB, project.image.filter, project.image.white);
+            if (!denoise_flag && (hdr || tone || glare_p)) linear = develop_linear(film, PYR_LINEAR_SRGB, project.image.filter, project.image.white);
+            if (glare_p) linear = glare(linear, film.width, film.height, *glare_p); // before the statistics of an automatic exposure, which tonemap takes
             save_png(argv[5],
-                     tone || denoise_flag ? tonemap(linear, film.width, film.height, tone ? *tone : tone_params(PYR_TONE_CLIP, 1.0f))
+                     tone || denoise_flag || glare_p ? tonemap(linear, film.width, film.height, tone ? *tone : tone_params(PYR_TONE_CLIP, 1.0f))
                                           : film.develop(project.image.filter, project.image.white),
                      film.width, film.height);
             if (hdr) {

@@ -19,6 +19,7 @@ int check_tone_params(const PyrToneParams* t); // what pyr_tone_resolve refuses
 bool tone_needs_stats(const PyrToneParams* t);
 int check_denoise_params(const PyrDenoiseParams* p);
 int check_motion_blur_params(const PyrMotionBlurParams* p, const char* what); // `what` names the argument: params, blur_params
+int check_glare_params(const PyrGlareParams* p, const char* what);            // likewise: params, glare_params
 
 // The per-wavelength tables of a development -- filter, white_div, white_mul, sample_count floats each, then the observer table --
 // are develop_table_floats(p) floats. develop_launch makes the launch record that reads them at `tables` (device); `host` receives
@@ -35,5 +36,9 @@ int enqueue_denoise(const float* a, const float* b, const float* albedo, const P
 // The motion blur of `image` along `motion` into `out` (kernels/motion_blur.hip): every buffer on the current device, the working
 // memory allocated and freed in stream order on `stream`.
 int enqueue_motion_blur(const float* image, const PyrMotionPixel* motion, uint32_t width, uint32_t height, const PyrMotionBlurParams* p, float* out, hipStream_t stream);
+
+// The glare of `image` into `out` (kernels/glare.hip): both on the current device, the pyramid's levels allocated and freed in
+// stream order on `stream`.
+int enqueue_glare(const float* image, uint32_t width, uint32_t height, const PyrGlareParams* p, float* out, hipStream_t stream);
 
 } // namespace pyr

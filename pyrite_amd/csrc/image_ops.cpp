@@ -1,7 +1,7 @@
 // image_ops.cpp -- the entry points of include/pyrite_gpu.h that take a device number and never see a scene: a film developed to
 // an 8-bit or a linear image, an image's luminance statistics, its tone mapping, the denoising of two half images, the
 // accumulation of linear images over frames along their motion records (plain, and as the temporal resolve), the motion blur of
-// one along them. Every operation is stated in three parts, each once ("adding an image entry"):
+// one along them, the glare of one. Every operation is stated in three parts, each once ("adding an image entry"):
 //   its checks, composed from the pieces below in the order that entry refuses in (tests/golden/image_refusals.json pins it);
 //   one enqueue_... function: device pointers, the public parameter block, a stream -- the one place its launch record is built;
 //   two entries: the _device form is checks, use_device, enqueue; the host form is checks, use_device and Staging::finish, which
@@ -172,6 +172,18 @@ int check_motion_blur_params(const PyrMotionBlurParams* p, const char* what) {
     return PYR_OK;
 }
 
+// What the three glare entries refuse of their parameters before a device is looked for (`what`: params or glare_params).
+int check_glare_params(const PyrGlareParams* p, const char* what) {
+    const std::string name = std::string(what) + "->";
+    if (!p) return fail(PYR_ERR_INVALID_ARGUMENT, std::string("null argument: ") + what);
+    if (!(p->strength > 0.0f && p->strength <= 1.0f)) return fail(PYR_ERR_INVALID_ARGUMENT, name + "strength must be in (0, 1]");
+    if (p->levels < 1 || p->levels > PYR_GLARE_MOST_LEVELS) return fail(PYR_ERR_INVALID_ARGUMENT, name + "levels must be 1..12");
+    if (!(p->threshold >= 0.0f) || !std::isfinite(p->threshold)) return fail(PYR_ERR_INVALID_ARGUMENT, name + "threshold must be finite and not negative");
+    if (!(p->falloff > 0.0f && p->falloff <= 4.0f)) return fail(PYR_ERR_INVALID_ARGUMENT, name + "falloff must be in (0, 4]");
+    if (p->reserved[0] != 0 || p->reserved[1] != 0 || p->reserved[2] != 0 || p->reserved[3] != 0) return fail(PYR_ERR_INVALID_ARGUMENT, name + "reserved must be 0");
+    return PYR_OK;
+}
+
 // Variance, the two filter launches with the halves exchanged, the combine: everything on `stream`, every buffer on the current
 // device; `work` holds three images of width * height * 3 floats (V, FA, FB).
 int enqueue_denoise(const float* a, const float* b, const float* albedo, const PyrFeaturePixel* pixels, uint32_t width, uint32_t height, const PyrDenoiseParams* p,
@@ -202,6 +214,15 @@ int enqueue_motion_blur(const float* image, const PyrMotionPixel* motion, uint32
     return with_stream_memory(motion_blur_work_bytes(width, height, p->max_radius), stream, [&](void* work) {
         const MotionBlurLaunch L{image, motion, width, height, p->shutter, p->depth_softness, p->samples, p->max_radius, p->seed, (float*)work, out};
         return launch_motion_blur(L, stream);
+    });
+}
+
+// The glare of `image` into `out`, both on the current device, enqueued on `stream`; the pyramid's levels are allocated and freed
+// in stream order around the launches.
+int enqueue_glare(const float* image, uint32_t width, uint32_t height, const PyrGlareParams* p, float* out, hipStream_t stream) {
+    return with_stream_memory(glare_work_bytes(width, height, p->levels), stream, [&](void* work) {
+        const GlareLaunch L{image, width, height, p->strength, p->threshold, p->falloff, p->levels, (float*)work, out};
+        return launch_glare(L, stream);
     });
 }
 
@@ -328,6 +349,12 @@ int check_motion_blur_args(const void* image, const void* motion, uint32_t width
     if (int bad = check_given({{image, 0, "image"}, {motion, 0, "motion"}, {out, 0, "out"}})) return bad;
     if (int bad = check_motion_blur_params(p, "params")) return bad;
     return check_extent(width, height);
+}
+
+int check_glare_args(const void* image, uint32_t width, uint32_t height, const PyrGlareParams* p, const void* out) {
+    if (int bad = check_given({{image, 0, "image"}, {p, 0, "params"}, {out, 0, "out"}})) return bad;
+    if (int bad = check_not_empty(width, height)) return bad;
+    return check_glare_params(p, "params");
 }
 
 // A development with its small per-wavelength tables copied for the call: allocated in stream order, filled, handed to `launch`
@@ -563,6 +590,24 @@ int pyr_image_motion_blur(const float* image, const PyrMotionPixel* motion, uint
     const size_t count = (size_t)width * height, image_bytes = count * 3 * sizeof(float);
     Staging S;
     return S.finish(enqueue_motion_blur, S.in(image, image_bytes), S.in(motion, count * sizeof(PyrMotionPixel)), width, height, params, S.out(out, image_bytes), nullptr);
+}
+
+int pyr_image_glare_device(const float* image_device, uint32_t width, uint32_t height, const PyrGlareParams* params, float* out_device, int device, void* hip_stream) {
+    if (int bad = check_glare_args(image_device, width, height, params, out_device)) return bad;
+    // the overlap before the size; an image that is refused next for its size is taken as 2^32 pixels here, so that the byte counts fit 64 bits
+    const uint64_t pixels = std::min<uint64_t>((uint64_t)width * height, kMaxImagePixels + 1);
+    if (int bad = check_overlap({{out_device, pixels * 12, "out_device"}}, {{image_device, pixels * 12, "image_device"}})) return bad;
+    if (int bad = use_device(check_image_size(width, height), device)) return bad;
+    return enqueue_glare(image_device, width, height, params, out_device, (hipStream_t)hip_stream);
+}
+
+int pyr_image_glare(const float* image, uint32_t width, uint32_t height, const PyrGlareParams* params, float* out, int device) {
+    int rc = check_glare_args(image, width, height, params, out);
+    if (rc == PYR_OK) rc = check_image_size(width, height);
+    if (int bad = use_device(rc, device)) return bad;
+    const size_t image_bytes = (size_t)width * height * 3 * sizeof(float);
+    Staging S;
+    return S.finish(enqueue_glare, S.in(image, image_bytes), width, height, params, S.out(out, image_bytes), nullptr);
 }
 
 } // extern "C"

@@ -362,6 +362,25 @@ int pyr_session_motion_blurred(PyrSession* session, const PyrCamera* previous_ca
     });
 }
 
+int pyr_session_glared(PyrSession* session, const PyrDevelopParams* develop_params, const PyrGlareParams* glare_params, float* out) {
+    if (!session) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: session");
+    if (!develop_params) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: develop_params");
+    if (!out) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: out");
+    int rc = check_glare_params(glare_params, "glare_params"); // what needs no session comes first: before a device is looked for
+    if (rc != PYR_OK || (rc = check_linear_args(&session->film, session, develop_params, PYR_LINEAR_SRGB, out)) != PYR_OK || (rc = session_ready(session)) != PYR_OK) return rc;
+    PyrSession* s = session;
+    const size_t image_bytes = (size_t)s->film.width * s->film.height * 3 * sizeof(float);
+    DeviceBuffer out_dev;
+    if ((rc = out_dev.alloc(image_bytes)) != PYR_OK) return rc;
+    return enqueue_then_sync(s, [&]() -> int {
+        int rc = session_linear(s, develop_params, PYR_LINEAR_SRGB);
+        if (rc != PYR_OK) return rc;
+        if ((rc = enqueue_glare((const float*)s->linear.ptr, s->film.width, s->film.height, glare_params, (float*)out_dev.ptr, s->stream)) != PYR_OK) return rc;
+        if (hipMemcpyAsync(out, out_dev.ptr, image_bytes, hipMemcpyDeviceToHost, s->stream) != hipSuccess) return fail(PYR_ERR_DEVICE, "hipMemcpyAsync of the glared image failed");
+        return PYR_OK;
+    });
+}
+
 int pyr_session_linear(PyrSession* session, const PyrDevelopParams* develop_params, uint32_t space, float* out) {
     if (!session) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
     int rc = check_linear_args(&session->film, session, develop_params, space, out);

@@ -324,6 +324,58 @@ def motion_blur(image, motion, device=0, **params):
     return out
 
 
+def glare_params(strength=abi.PYR_GLARE_STRENGTH, levels=abi.PYR_GLARE_LEVELS, threshold=abi.PYR_GLARE_THRESHOLD, falloff=abi.PYR_GLARE_FALLOFF):
+    """abi.PyrGlareParams: `strength` of every pixel's light (of what lies above the luminance `threshold`, when that is not 0) is
+    spread over `levels` blurs, each twice as wide as the one before and weighted `falloff` times as much."""
+    return abi.PyrGlareParams(float(strength), int(levels), float(threshold), float(falloff))
+
+
+def glare(image, device=0, **params):
+    """float32 [height, width, 3]: the linear image `image` with the glare of a lens or an eye added -- a long-tailed point spread
+    that moves light from the bright pixels to their surroundings (pyr_image_glare; include/pyrite_gpu.h has the arithmetic).
+    `params`: glare_params. A pixel that is not finite keeps its bits and spreads nothing."""
+    image = _linear_image(image)
+    h, w, _ = image.shape
+    p = glare_params(**params)
+    out = np.zeros(image.shape, dtype=np.float32)
+    check(lib().pyr_image_glare(image.ctypes.data, w, h, C.byref(p), out.ctypes.data, int(device)))
+    return out
+
+
+def glare_flag_problem(glare, glare_levels, glare_threshold):
+    """What is wrong with --glare / --glare-levels / --glare-threshold, in the words pyrite_host_tool uses too, or None. `glare`:
+    the strength as given (a string or a number), or None without --glare."""
+    if glare is None:
+        if glare_levels is not None:
+            return "--glare-levels needs --glare"
+        if glare_threshold is not None:
+            return "--glare-threshold needs --glare"
+        return None
+    try:
+        strength = float(glare)
+    except ValueError:
+        strength = float("nan")
+    if not 0.0 < strength <= 1.0:
+        return "--glare must be a strength above 0 and at most 1"
+    if glare_levels is not None and not 1 <= glare_levels <= abi.PYR_GLARE_MOST_LEVELS:
+        return "--glare-levels must be 1 to %d" % abi.PYR_GLARE_MOST_LEVELS
+    if glare_threshold is not None and not (np.isfinite(glare_threshold) and glare_threshold >= 0.0):
+        return "--glare-threshold must be a finite number that is not negative"
+    return None
+
+
+def glare_from_flags(glare, glare_levels, glare_threshold):
+    """The glare_params keywords of --glare [STRENGTH] --glare-levels N --glare-threshold T, or None without --glare."""
+    if glare is None:
+        return None
+    params = {"strength": float(glare)}
+    if glare_levels is not None:
+        params["levels"] = glare_levels
+    if glare_threshold is not None:
+        params["threshold"] = glare_threshold
+    return params
+
+
 def denoise_flag_problem(denoise, denoise_radius, pixel_samples=None, pass_samples=None):
     """What is wrong with --denoise / --denoise-radius, in the words pyrite_host_tool uses too, or None. `pixel_samples`: the
     render's budget once the project is loaded; `pass_samples`: --pass-samples, when given."""

@@ -559,6 +559,19 @@ class Session:
         del keep
         return out
 
+    def glared(self, step=2.0, filter=None, white=None, **params):
+        """float32 [height, width, 3]: the film as it stands developed to linear sRGB with the glare added, all on the session's
+        device (pyr_session_glared; develop.glare of linear() gives the same floats). `params`: develop.glare_params. The session's
+        film is not touched."""
+        from .develop import develop_params, glare_params
+
+        p, keep = develop_params(self._film, step, filter, white)
+        gp = glare_params(**params)
+        out = np.zeros((self.height, self.width, 3), dtype=np.float32)
+        check(lib().pyr_session_glared(self.handle, C.byref(p), C.byref(gp), out.ctypes.data))
+        del keep
+        return out
+
     def half_films(self):
         """The two half films of a session with `halves`, float32 [height, width, bins, 2] each."""
         a, b = np.zeros(self._shape, dtype=np.float32), np.zeros(self._shape, dtype=np.float32)
