@@ -1302,6 +1302,81 @@ int pyr_image_glare_device(const float* image_device, uint32_t width, uint32_t h
  * Blocking. */
 int pyr_session_glared(PyrSession* session, const PyrDevelopParams* develop_params, const PyrGlareParams* glare_params, float* out);
 
+/* ------------------------------------------------------------- upsample ----
+ * Rendering dominates the cost of a frame, and the first-hit feature pass is noise-free, deterministic and cheap at any size. This
+ * joins the two: a joint bilateral upsampling (Kopf et al., "Joint Bilateral Upsampling", SIGGRAPH 2007) of a linear image rendered
+ * at low_width x low_height to W x H with W = scale*low_width, H = scale*low_height exactly, steered by full-size normals, depths
+ * and material ids so that it does not blur across an outline, and demodulated by albedo so that texture detail comes back at full
+ * size although the light was sampled at a fraction of it. It needs no scene.
+ *   `low`: low_width*low_height*3 f32 in linear light; `out`: W*H*3 f32. The albedo pair -- `low_albedo` at the low size, `albedo`
+ * at W x H, three floats a pixel -- is optional: both given or both NULL. So is the records pair `low_pixels`, `pixels`.
+ *   All arithmetic is f32 and unfused, one rounding per operation, in the order written; / is the correctly rounded one; sums start
+ * from 0.0f and run in the order written; the channel loop c = 0, 1, 2 is innermost. There is no expf: every bit is pinned.
+ *   Position. For the output pixel P = (X, Y):  lx = ((float)X + 0.5f) / (float)scale - 0.5f,  x0 = (int)floorf(lx);  ly, y0 alike.
+ *   Taps. q = (qx, qy) = (x0 - (radius-1) + i, y0 - (radius-1) + j) for j = 0 .. 2*radius-1 (outer), i = 0 .. 2*radius-1. A tap
+ *     outside the low image is skipped.  sx = fmaxf(1.0f - fabsf((float)qx - lx) / (float)radius, 0.0f),  sy alike,  sp = sy * sx.
+ *     A tap with sp == 0 is skipped. The taps that are left are the taps kept. With radius 1 and neither pair this is bilinear
+ *     interpolation, the edges clamped by renormalisation.
+ *   Guide weight gw, with the records pair (without it gw = 1). D = 0.0f. Each term applies only when its sigma is > 0, in this
+ *     order; a term g that is a NaN makes gw = 0 whatever else holds, any other sets D = fmaxf(D, g):
+ *       normal:  g = (((0.0f + e_0*e_0) + e_1*e_1) + e_2*e_2) / (2.0f * (sigma_normal*sigma_normal)),  e_c = normal_c(P) - normal_c(q)
+ *       depth:   m = fmaxf(fmaxf(z_P, z_q), 1e-30f),  r = (z_P - z_q) / m,  g = (r*r) / (2.0f * (sigma_depth*sigma_depth))
+ *     (the denoiser's distances). t = 1.0f - D;  gw = t*t when t > 0, else 0: the support is compact, a tap further than
+ *     sigma*sqrt(2) away weighs exactly 0. With PYR_UPSAMPLE_MATCH_MATERIAL gw = 0 when PyrFeaturePixel::material of q and of P
+ *     differ: that keeps a lamp set flush into a ceiling (same normal, same depth, no albedo channel) out of the ceiling's pixels.
+ *     w = sp * gw.
+ *   Demodulation, with the albedo pair (without it v_c = low_c(q)). Per low pixel and channel:
+ *       d_c(q) = 1.0f / (fmaxf(low_albedo_c(q), 0.0f) + albedo_floor)
+ *     per tap:  k_c = fminf((fmaxf(albedo_c(P), 0.0f) + albedo_floor) * d_c(q), max_gain), a NaN k_c counting as max_gain;
+ *     v_c = low_c(q) * k_c. The two fmaxf change nothing for an albedo that is not negative. A developed albedo can be: a saturated
+ *     colour lies outside linear sRGB, and without them low_albedo_c + albedo_floor would cross 0 and the gain have no bound (a NaN
+ *     albedo counts as 0). So 0 <= k_c <= max_gain always.
+ *   Sums over the taps kept, in tap order:  S += sp,  B_c += sp * low_c(q)  for every one of them;  W_ += w,  A_c += w * v_c  for
+ *     those with w > 0 only -- a tap of weight 0 adds nothing, so its NaN cannot leak.
+ *   Output.  out_c = A_c / W_ when W_ > 0, otherwise out_c = B_c / S: the raw tent, not demodulated, so that a pixel every guide
+ *     rejects never explodes. S > 0 always: the low pixel that contains P is inside and weighs more than 0.25.
+ * A tap that is not finite and has positive weight makes its output pixels not finite; which pixels and which of inf, -inf and NaN
+ * follows from the rule, the sign and payload bits of a NaN do not. One lane owns an output pixel, stores are plain, there are no
+ * float atomics: two calls write the same bytes. Integer scales only; nothing is reused over time. One GPU.
+ *   The defaults: the denoiser's sigmas; the floor and the gain are a maintainer's choice. */
+#define PYR_UPSAMPLE_RADIUS 1u
+#define PYR_UPSAMPLE_MOST_RADIUS 3u
+#define PYR_UPSAMPLE_MOST_SCALE 8u
+#define PYR_UPSAMPLE_SIGMA_NORMAL 0.1f /* = PYR_DENOISE_SIGMA_NORMAL */
+#define PYR_UPSAMPLE_SIGMA_DEPTH 0.02f /* = PYR_DENOISE_SIGMA_DEPTH */
+#define PYR_UPSAMPLE_ALBEDO_FLOOR 0.01f
+#define PYR_UPSAMPLE_MAX_GAIN 4.0f
+#define PYR_UPSAMPLE_MATCH_MATERIAL 1u
+typedef struct PyrUpsampleParams {
+    uint32_t radius;      /* 1..PYR_UPSAMPLE_MOST_RADIUS: 2*radius taps per axis */
+    uint32_t flags;       /* PYR_UPSAMPLE_MATCH_MATERIAL or 0; other bits are refused */
+    float sigma_normal;   /* <= 0 (or NaN) turns that guide off */
+    float sigma_depth;    /* likewise */
+    float albedo_floor;   /* > 0; read when the albedo pair is given */
+    float max_gain;       /* >= 1; likewise */
+    uint32_t reserved[2]; /* 0 */
+} PyrUpsampleParams; /* 32 bytes */
+/* Arguments are checked before a device is looked for: PYR_ERR_INVALID_ARGUMENT, with the argument named in pyr_last_error, for a
+ * null low, params or out, half a pair, an empty image (low_width, low_height), a scale outside 2..PYR_UPSAMPLE_MOST_SCALE, a
+ * radius outside 1..3, an unknown flag bit, with the albedo pair an albedo_floor that is not > 0 or a max_gain that is not >= 1 (a
+ * NaN is neither), a non-zero reserved word; PYR_ERR_UNSUPPORTED when W*H exceeds 2^32 - 1, or W or H 2^24, up to which (float)X
+ * is exact; only then PYR_ERR_DEVICE. HOST buffers. Blocking. */
+int pyr_image_upsample(const float* low, const float* low_albedo, const PyrFeaturePixel* low_pixels, uint32_t low_width, uint32_t low_height, uint32_t scale,
+                       const float* albedo, const PyrFeaturePixel* pixels, const PyrUpsampleParams* params, float* out, int device);
+/* The same with every buffer resident on `device`, enqueued on `hip_stream`. The records are read as 16-byte vectors: a records
+ * pointer that is not 16-byte aligned is PYR_ERR_INVALID_ARGUMENT, after the checks above and before the size. No working memory. */
+int pyr_image_upsample_device(const float* low_device, const float* low_albedo_device, const PyrFeaturePixel* low_pixels_device, uint32_t low_width,
+                              uint32_t low_height, uint32_t scale, const float* albedo_device, const PyrFeaturePixel* pixels_device, const PyrUpsampleParams* params,
+                              float* out_device, int device, void* hip_stream);
+/* The session's film, width x height, is the low image. On the session's stream and device: with `denoise_params` what
+ * pyr_session_denoised does (PYR_SESSION_HALVES and two passes, the same refusals; `feature_params` steers that filter too), without
+ * them what pyr_session_linear does in PYR_LINEAR_SRGB; with `feature_params` the feature pass at the session's size -- the one the
+ * denoiser ran, when it ran -- and once more with the session's camera and a film of scale*width x scale*height, both albedo
+ * films developed with `develop_params`; then the upsample, with both pairs or, without `feature_params`, with neither.
+ * out = HOST, scale*height * scale*width * 3 floats. The session's films are not touched, and further passes may follow. Blocking. */
+int pyr_session_upsampled(PyrSession* session, uint32_t scale, const PyrDevelopParams* develop_params, const PyrFeatureParams* feature_params,
+                          const PyrDenoiseParams* denoise_params, const PyrUpsampleParams* upsample_params, float* out);
+
 #ifdef __cplusplus
 }
 #endif

@@ -438,6 +438,22 @@ std::string glare_flag_problem(const std::optional<std::string>& glare, const st
 // The parameters of --glare [STRENGTH] --glare-levels N --glare-threshold T, or nothing without --glare (pyrite_amd/develop.py glare_from_flags).
 std::optional<PyrGlareParams> glare_from_flags(const std::optional<std::string>& glare, const std::optional<long>& glare_levels, const std::optional<double>& glare_threshold);
 
+// ---- guided upsampling (pyrite_gpu.h "upsample"; pyrite_amd/develop.py upsample) ----
+PyrUpsampleParams upsample_params(uint32_t radius = PYR_UPSAMPLE_RADIUS, bool match_material = true, float sigma_normal = PYR_UPSAMPLE_SIGMA_NORMAL,
+                                  float sigma_depth = PYR_UPSAMPLE_SIGMA_DEPTH, float albedo_floor = PYR_UPSAMPLE_ALBEDO_FLOOR, float max_gain = PYR_UPSAMPLE_MAX_GAIN);
+// The linear image `low`, [low_height][low_width][3] f32, upsampled `scale` times on the GPU (pyr_image_upsample). The albedo pair
+// (`low_albedo` of low's size, `albedo` of the result's) and the records pair (`low_pixels`, `pixels`) are each given whole or not at
+// all. A buffer of another size than its image's, or half a pair, is a ProjectError before the library is called.
+std::vector<float> upsample(const std::vector<float>& low, uint32_t low_width, uint32_t low_height, uint32_t scale, const PyrUpsampleParams& params = upsample_params(),
+                            const std::vector<float>* albedo = nullptr, const std::vector<PyrFeaturePixel>* pixels = nullptr, const std::vector<float>* low_albedo = nullptr,
+                            const std::vector<PyrFeaturePixel>* low_pixels = nullptr, int device = 0);
+// What is wrong with --upsample N / --upsample-radius R, in the words both front ends print, or "" (pyrite_amd/develop.py
+// upsample_flag_problem). `width`, `height`: the image's size once the project is loaded -- N must divide both.
+std::string upsample_flag_problem(const std::optional<long>& upsample, const std::optional<long>& upsample_radius, const std::optional<uint32_t>& width = std::nullopt,
+                                  const std::optional<uint32_t>& height = std::nullopt);
+// The parameters of --upsample N --upsample-radius R, or nothing without --upsample (pyrite_amd/develop.py upsample_from_flags).
+std::optional<PyrUpsampleParams> upsample_from_flags(const std::optional<long>& upsample, const std::optional<long>& upsample_radius);
+
 struct Progress { // renderer/mod.rs:229-232
     uint8_t progress;
     const char* message;
@@ -518,6 +534,12 @@ class Session {
     // feature pass (grid, albedo_bins) runs first and steers the filter. Needs halves and two passes; the films are not touched.
     Denoised denoised(const PyrDenoiseParams& params = denoise_params(), bool guides = true, float step_size = 2.0f, const std::optional<Expression>& filter = std::nullopt,
                       const std::optional<Expression>& white = std::nullopt, uint32_t grid = 1, uint32_t albedo_bins = 16);
+    // pyr_session_upsampled: the film, the low image, in linear sRGB -- with `denoise` what denoised() gives -- upsampled `scale`
+    // times under the guidance of the feature pass (grid, albedo_bins) at both sizes, on the session's device: [scale*height]
+    // [scale*width][3] f32. Without `guides` no feature pass runs: the plain tent. The films are not touched.
+    std::vector<float> upsampled(uint32_t scale, const PyrUpsampleParams& params = upsample_params(), bool guides = true, const std::optional<PyrDenoiseParams>& denoise = std::nullopt,
+                                 float step_size = 2.0f, const std::optional<Expression>& filter = std::nullopt, const std::optional<Expression>& white = std::nullopt,
+                                 uint32_t grid = 1, uint32_t albedo_bins = 16);
     uint32_t tiles_x() const { return (width_ + tile_size_ - 1) / tile_size_; }
     uint32_t tiles_y() const { return (height_ + tile_size_ - 1) / tile_size_; }
 

@@ -5,7 +5,8 @@
     python -m pyrite_amd path/to/project.lua [-o out.png] [--seed N] [--device D] [--spp N] [--size WxH]
                          [--pass-samples N] [--preview PATH] [--preview-every SECONDS] [--noise]
                          [--features PREFIX] [--features-grid N] [--hdr PATH] [--exposure EV|auto] [--tone clip|reinhard]
-                         [--denoise] [--denoise-radius N] [--glare [STRENGTH]] [--glare-levels N] [--glare-threshold T]
+                         [--denoise] [--denoise-radius N] [--upsample N] [--upsample-radius R]
+                         [--glare [STRENGTH]] [--glare-levels N] [--glare-threshold T]
                          [--build host|device]
 
 With --pass-samples, --preview or --noise the render runs as a progressive session (pyr_session_*): passes of N samples per pixel
@@ -25,6 +26,11 @@ With --denoise the render runs as a session with two half films, in an even numb
 --pass-samples is not given; an odd number of samples per pixel is refused), and the final PNG and the --hdr image are written
 from the denoised linear image (pyr_session_denoised with the feature pass as its guide; window radius N, default 5): the PNG
 through the tone curve, which without --exposure / --tone is the clip at exposure 1, the encoder of the plain PNG.
+
+With --upsample N the render runs at width/N x height/N with the project's camera -- N (2 to 8) must divide both -- and the final
+image, of the project's size, is its linear image (the denoised one with --denoise) upsampled under the guidance of the first-hit
+feature pass at both sizes (pyr_image_upsample: albedo, normals, depths and material ids; tent radius R, 1 to 3, default 1): after
+the denoiser, before the glare and the tone curve. The --hdr image is the upsampled one; previews keep the low size.
 
 With --glare the final image takes the linear path (the denoised image with --denoise) and the glare of a lens or an eye is added
 to it (pyr_image_glare: STRENGTH of every pixel's light, default 0.1, spread over N blurs of doubling width, default 6; with
@@ -99,26 +105,29 @@ def main(argv=None):
     ap.add_argument("--tone", default=None, metavar="clip|reinhard", help="tone curve of the PNG and the previews (reinhard alone means --exposure auto)")
     ap.add_argument("--denoise", action="store_true", help="write the PNG and the --hdr image from the denoised linear image of two half films")
     ap.add_argument("--denoise-radius", type=int, default=None, metavar="N", help="window radius of --denoise (1 to 10, default 5)")
+    ap.add_argument("--upsample", type=int, default=None, metavar="N", help="render at 1/N of the image size (2 to 8, N divides both sides) and upsample under the guidance of the feature pass")
+    ap.add_argument("--upsample-radius", type=int, default=None, metavar="R", help="tent radius of --upsample in low-resolution pixels (1 to 3, default 1)")
     ap.add_argument("--glare", nargs="?", const=str(0.1), default=None, metavar="STRENGTH", help="add glare to the final image: the share of the light that is spread (above 0, at most 1; default 0.1)")
     ap.add_argument("--glare-levels", type=int, default=None, metavar="N", help="blurs of doubling width the glare sums (1 to 12, default 6)")
     ap.add_argument("--glare-threshold", type=float, default=None, metavar="T", help="luminance below which a pixel spreads nothing (default 0: every pixel spreads)")
     ap.add_argument("--build", default=None, choices=["host", "device"], help="who builds the BVH (default host); given, the stage times of scene creation go to stderr")
     args = ap.parse_args(argv)
-    from .develop import denoise_flag_problem, glare_flag_problem, glare_from_flags, tone_flag_problem, tone_from_flags
+    from .develop import denoise_flag_problem, glare_flag_problem, glare_from_flags, tone_flag_problem, tone_from_flags, upsample_flag_problem, upsample_from_flags
     from .features import features_flag_problem
 
     problem = (progressive_flag_problem(args.pass_samples, args.preview, args.preview_every, args.noise) or features_flag_problem(args.features, args.features_grid)
                or tone_flag_problem(args.hdr, args.exposure, args.tone) or denoise_flag_problem(args.denoise, args.denoise_radius)
-               or glare_flag_problem(args.glare, args.glare_levels, args.glare_threshold))
+               or upsample_flag_problem(args.upsample, args.upsample_radius) or glare_flag_problem(args.glare, args.glare_levels, args.glare_threshold))
     if problem:
         print("error: " + problem, file=sys.stderr)
         return 2
 
     args.tone_params = tone_from_flags(args.exposure, args.tone)
     args.glare_params = glare_from_flags(args.glare, args.glare_levels, args.glare_threshold)
+    args.upsample_params = upsample_from_flags(args.upsample, args.upsample_radius)
 
     from . import lua_project, scenes
-    from .develop import develop, develop_linear, glare, save_linear, save_png, tonemap
+    from .develop import develop, develop_linear, glare, save_linear, save_png, tonemap, upsample
 
     project, base_dir = lua_project.load_project(args.project)
     if args.size:
@@ -127,9 +136,13 @@ def main(argv=None):
     if args.spp:
         project["renderer"] = project["renderer"].with_(pixel_samples=args.spp)
     problem = denoise_flag_problem(args.denoise, args.denoise_radius, int(project["renderer"].pixel_samples), args.pass_samples)
+    full_size = (int(project["image"]["width"]), int(project["image"]["height"]))
+    problem = problem or upsample_flag_problem(args.upsample, args.upsample_radius, full_size)
     if problem:
         print("error: " + problem, file=sys.stderr)
         return 2
+    if args.upsample:  # the render and everything before the upsample at 1/N of the size, under the same camera
+        project["image"].update(width=full_size[0] // args.upsample, height=full_size[1] // args.upsample)
     seed = args.seed if args.seed is not None else int(time.time_ns() & 0x7FFFFFFFFFFFFFFF)
     world, cam, r, film = scenes.build(project, seed=seed, base_dir=base_dir)
     print("The scene contains %d objects." % (len(world.flat.tri_material) + len(world.flat.spheres) + len(world.flat.planes)))  # world.rs:251-254
@@ -155,11 +168,16 @@ def main(argv=None):
     linear = None
     if args.denoise:
         linear = args.denoised
-    elif args.hdr or args.tone_params is not None or args.glare_params is not None:
+    elif args.hdr or args.tone_params is not None or args.glare_params is not None or args.upsample:
         linear = develop_linear(film, "srgb", filter=image.get("filter"), white=image.get("white"), device=args.device)
+    if args.upsample:  # after the denoiser, before the glare
+        guides = [r.features(size, cam, world, device=args.device) for size in ((film.width, film.height), full_size)]
+        low_albedo, albedo = (develop_linear(f.albedo, "srgb", filter=image.get("filter"), white=image.get("white"), device=args.device) for f in guides)
+        linear = upsample(linear, args.upsample, albedo=albedo, pixels=guides[1].records, low_albedo=low_albedo, low_pixels=guides[0].records, device=args.device,
+                          **args.upsample_params)
     if args.glare_params is not None:  # before the statistics of an automatic exposure, which tonemap takes
         linear = glare(linear, device=args.device, **args.glare_params)
-    if args.tone_params is not None or args.denoise or args.glare_params is not None:
+    if args.tone_params is not None or args.denoise or args.glare_params is not None or args.upsample:
         rgb = tonemap(linear, args.tone_params, device=args.device)
     else:
         rgb = develop(film, filter=image.get("filter"), white=image.get("white"), device=args.device)
@@ -172,7 +190,7 @@ def main(argv=None):
     if args.features:
         from .features import write_feature_images
 
-        write_feature_images(args.features, r.features((film.width, film.height), cam, world, grid=args.features_grid or 1, device=args.device),
+        write_feature_images(args.features, r.features(full_size, cam, world, grid=args.features_grid or 1, device=args.device),
                              filter=image.get("filter"), white=image.get("white"), device=args.device)
         print("wrote %s_albedo.png, %s_normal.png, %s_depth.png" % (args.features, args.features, args.features))
     return 0

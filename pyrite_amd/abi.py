@@ -478,6 +478,15 @@ class PyrGlareParams(C.Structure):
     _fields_ = [("strength", C.c_float), ("levels", C.c_uint32), ("threshold", C.c_float), ("falloff", C.c_float), ("reserved", C.c_uint32 * 4)]
 
 
+PYR_UPSAMPLE_RADIUS, PYR_UPSAMPLE_MOST_RADIUS, PYR_UPSAMPLE_MOST_SCALE, PYR_UPSAMPLE_MATCH_MATERIAL = 1, 3, 8, 1
+PYR_UPSAMPLE_SIGMA_NORMAL, PYR_UPSAMPLE_SIGMA_DEPTH, PYR_UPSAMPLE_ALBEDO_FLOOR, PYR_UPSAMPLE_MAX_GAIN = 0.1, 0.02, 0.01, 4.0
+
+
+class PyrUpsampleParams(C.Structure):
+    _fields_ = [("radius", C.c_uint32), ("flags", C.c_uint32), ("sigma_normal", C.c_float), ("sigma_depth", C.c_float), ("albedo_floor", C.c_float),
+                ("max_gain", C.c_float), ("reserved", C.c_uint32 * 2)]
+
+
 PyrProgressFn = C.CFUNCTYPE(None, C.c_void_p, C.c_uint8, C.c_char_p)
 PyrPreviewFn = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, C.c_uint32)
 
@@ -599,6 +608,12 @@ ENTRY_POINTS = {
     "pyr_image_glare": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PyrGlareParams), C.c_void_p, C.c_int]),
     "pyr_image_glare_device": (C.c_int, [C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PyrGlareParams), C.c_void_p, C.c_int, C.c_void_p]),
     "pyr_session_glared": (C.c_int, [C.c_void_p, C.POINTER(PyrDevelopParams), C.POINTER(PyrGlareParams), C.c_void_p]),
+    "pyr_image_upsample": (C.c_int, [C.c_void_p] * 3 + [C.c_uint32] * 3 + [C.c_void_p, C.c_void_p, C.POINTER(PyrUpsampleParams), C.c_void_p, C.c_int]),
+    "pyr_image_upsample_device": (C.c_int, [C.c_void_p] * 3 + [C.c_uint32] * 3 + [C.c_void_p, C.c_void_p, C.POINTER(PyrUpsampleParams), C.c_void_p, C.c_int, C.c_void_p]),
+    "pyr_session_upsampled": (
+        C.c_int,
+        [C.c_void_p, C.c_uint32, C.POINTER(PyrDevelopParams), C.POINTER(PyrFeatureParams), C.POINTER(PyrDenoiseParams), C.POINTER(PyrUpsampleParams), C.c_void_p],
+    ),
 }
 
 

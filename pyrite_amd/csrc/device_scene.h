@@ -409,6 +409,23 @@ struct GlareLaunch {
 size_t glare_work_bytes(uint32_t width, uint32_t height, uint32_t levels);
 int launch_glare(const GlareLaunch& launch, void* stream);
 
+// kernels/upsample.hip: the guided upsampling of a low-resolution linear image (pyrite_gpu.h "upsample").
+// One launch on `stream`, no working memory. Either pair is null or given whole.
+struct UpsampleLaunch {
+    const float* low;                  // device, low_height * low_width * 3 floats
+    const float* low_albedo;           // device, the same size, or null
+    const PyrFeaturePixel* low_pixels; // device, 16-byte aligned, or null
+    uint32_t low_width, low_height, scale;
+    const float* albedo;           // device, scale*low_height * scale*low_width * 3 floats, or null
+    const PyrFeaturePixel* pixels; // device, 16-byte aligned, or null
+    uint32_t radius;               // 1..PYR_UPSAMPLE_MOST_RADIUS
+    uint32_t use_normal, use_depth, match_material; // the guide switches: wave-uniform
+    float normal_div, depth_div;   // 2.0f * (sigma * sigma), formed on the host in f32
+    float albedo_floor, max_gain;
+    float* out; // device, scale*low_height * scale*low_width * 3 floats
+};
+int launch_upsample(const UpsampleLaunch& launch, void* stream);
+
 // launchers (kernels/main.hip)
 // wide_vm: the scene has a program that only the wide interpreter build (kernels/wide.hip) holds
 int launch_render(const DevScene& scene, const RenderLaunch& launch, bool with_counters, void* stream, int num_cus, bool wide_vm = false);

@@ -1650,6 +1650,48 @@ std::optional<PyrGlareParams> glare_from_flags(const std::optional<std::string>&
                         glare_threshold ? (float)*glare_threshold : PYR_GLARE_THRESHOLD);
 }
 
+// ---- guided upsampling ---------------------------------------------------------------------------------------------------------
+PyrUpsampleParams upsample_params(uint32_t radius, bool match_material, float sigma_normal, float sigma_depth, float albedo_floor, float max_gain) {
+    return PyrUpsampleParams{radius, match_material ? PYR_UPSAMPLE_MATCH_MATERIAL : 0u, sigma_normal, sigma_depth, albedo_floor, max_gain, {0u, 0u}};
+}
+std::vector<float> upsample(const std::vector<float>& low, uint32_t low_width, uint32_t low_height, uint32_t scale, const PyrUpsampleParams& params,
+                            const std::vector<float>* albedo, const std::vector<PyrFeaturePixel>* pixels, const std::vector<float>* low_albedo,
+                            const std::vector<PyrFeaturePixel>* low_pixels, int device) {
+    if ((albedo == nullptr) != (low_albedo == nullptr) || (pixels == nullptr) != (low_pixels == nullptr)) throw ProjectError("upsample: half a pair of guides");
+    const size_t low_count = (size_t)low_width * low_height;
+    const size_t sized = std::min<size_t>(std::max<size_t>(scale, 1), PYR_UPSAMPLE_MOST_SCALE); // a scale the library refuses never writes
+    const size_t count = low_count * sized * sized;
+    if (low.size() != low_count * 3 || (low_albedo && low_albedo->size() != low_count * 3) || (low_pixels && low_pixels->size() != low_count) ||
+        (albedo && albedo->size() != count * 3) || (pixels && pixels->size() != count))
+        throw ProjectError("upsample: buffer size does not match the image size");
+    std::vector<float> out(count * 3, 0.0f);
+    check_status(pyr_image_upsample(low.data(), low_albedo ? low_albedo->data() : nullptr, low_pixels ? low_pixels->data() : nullptr, low_width, low_height, scale,
+                                    albedo ? albedo->data() : nullptr, pixels ? pixels->data() : nullptr, &params, out.data(), device));
+    return out;
+}
+std::vector<float> Session::upsampled(uint32_t scale, const PyrUpsampleParams& params, bool guides, const std::optional<PyrDenoiseParams>& denoise, float step_size,
+                                      const std::optional<Expression>& filter, const std::optional<Expression>& white, uint32_t grid, uint32_t albedo_bins) {
+    const DevelopSetup setup(shape_, filter, white, step_size);
+    const PyrFeatureParams fp{grid, albedo_bins, {0, 0}};
+    const size_t sized = std::min<size_t>(std::max<size_t>(scale, 1), PYR_UPSAMPLE_MOST_SCALE);
+    std::vector<float> out((size_t)width_ * height_ * sized * sized * 3, 0.0f);
+    check_status(pyr_session_upsampled(handle_, scale, &setup.p, guides ? &fp : nullptr, denoise ? &*denoise : nullptr, &params, out.data()));
+    return out;
+}
+std::string upsample_flag_problem(const std::optional<long>& upsample, const std::optional<long>& upsample_radius, const std::optional<uint32_t>& width,
+                                  const std::optional<uint32_t>& height) {
+    if (!upsample) return upsample_radius ? "--upsample-radius needs --upsample" : "";
+    if (*upsample < 2 || *upsample > (long)PYR_UPSAMPLE_MOST_SCALE) return "--upsample must be 2 to " + std::to_string(PYR_UPSAMPLE_MOST_SCALE);
+    if (upsample_radius && (*upsample_radius < 1 || *upsample_radius > (long)PYR_UPSAMPLE_MOST_RADIUS)) return "--upsample-radius must be 1 to " + std::to_string(PYR_UPSAMPLE_MOST_RADIUS);
+    if (width && height && (*width % (uint32_t)*upsample || *height % (uint32_t)*upsample))
+        return "--upsample " + std::to_string(*upsample) + " does not divide the image size " + std::to_string(*width) + "x" + std::to_string(*height);
+    return "";
+}
+std::optional<PyrUpsampleParams> upsample_from_flags(const std::optional<long>& upsample, const std::optional<long>& upsample_radius) {
+    if (!upsample) return std::nullopt;
+    return upsample_params(upsample_radius ? (uint32_t)*upsample_radius : PYR_UPSAMPLE_RADIUS);
+}
+
 // ---- first-hit feature images --------------------------------------------------------------------------------------------------
 Features Renderer::features(uint32_t width, uint32_t height, const Camera& camera, World& world, uint32_t grid, uint32_t albedo_bins, int device) const {
     Features out{Film(width, height, albedo_bins, spectrum_span[0], spectrum_span[1]), std::vector<PyrFeaturePixel>((size_t)width * height)};

@@ -5,7 +5,7 @@
 //   pyrite_host_tool dump-project   <project.lua> <texel dir | -> <out.bin>    the same for a project file (lua_project.cpp)
 //   pyrite_host_tool render-project <project.lua> <texel dir | -> <seed> <out.png> [film.bin]   what `pyrite project.lua` does (main.rs:46-330)
 //                                   [--size WxH] [--spp N] [--features PREFIX] [--features-grid N] [--hdr PATH] [--exposure EV|auto] [--tone clip|reinhard]
-//                                   [--glare [STRENGTH]] [--glare-levels N] [--glare-threshold T]
+//                                   [--upsample N] [--upsample-radius R] [--glare [STRENGTH]] [--glare-levels N] [--glare-threshold T]
 //                                   [--build host|device] and the progressive flags of python -m pyrite_amd
 //   pyrite_host_tool encode-features <records.bin> <normal.rgb> <depth.rgb>    PyrFeaturePixel[n] -> the 8-bit normal and depth images, raw RGB (no GPU)
 //   pyrite_host_tool intersect <scene> <data_dir> <rays.f32> <hits.bin>       World::intersect for a ray batch ([n][6] f32 -> PyrHit[n])
@@ -242,7 +242,7 @@ int main(int argc, char** argv) {
             write_dump(argv[4], flat, loaded.project);
             return 0;
         }
-        if (argc >= 6 && std::string(argv[1]) == "render-project") { // render-project <project.lua> <texel dir | -> <seed> <out.png> [film.bin] [--pass-samples N] [--preview PATH] [--preview-every SECONDS] [--noise] [--denoise] [--denoise-radius N] [--glare [STRENGTH]] [--glare-levels N] [--glare-threshold T] [--build host|device]
+        if (argc >= 6 && std::string(argv[1]) == "render-project") { // render-project <project.lua> <texel dir | -> <seed> <out.png> [film.bin] [--pass-samples N] [--preview PATH] [--preview-every SECONDS] [--noise] [--denoise] [--denoise-radius N] [--upsample N] [--upsample-radius R] [--glare [STRENGTH]] [--glare-levels N] [--glare-threshold T] [--build host|device]
             // the flags of python -m pyrite_amd: a progressive session with previews (main.rs:261-299) instead of one blocking call
             std::optional<long> pass_samples;
             std::string preview_path, film_path;
@@ -253,6 +253,7 @@ int main(int argc, char** argv) {
             std::optional<std::string> hdr, exposure, tone_name;
             bool denoise_flag = false;
             std::optional<long> denoise_radius;
+            std::optional<long> upsample_scale, upsample_radius; // --upsample N: the render at 1/N of the image size, the final image upsampled to it
             std::optional<std::string> glare_strength; // --glare [STRENGTH]: the next argument unless it is a flag, as argparse's nargs="?" reads it (a film path goes before it)
             std::optional<long> glare_levels;
             std::optional<double> glare_threshold;
@@ -285,6 +286,10 @@ int main(int argc, char** argv) {
                     denoise_flag = true;
                 else if (a == "--denoise-radius")
                     denoise_radius = std::strtol(value(), nullptr, 10);
+                else if (a == "--upsample")
+                    upsample_scale = std::strtol(value(), nullptr, 10);
+                else if (a == "--upsample-radius")
+                    upsample_radius = std::strtol(value(), nullptr, 10);
                 else if (a == "--glare")
                     glare_strength = i + 1 < argc && std::string(argv[i + 1]).rfind("--", 0) != 0 ? argv[++i] : "0.1";
                 else if (a == "--glare-levels")
@@ -306,6 +311,7 @@ int main(int argc, char** argv) {
             if (problem.empty()) problem = features_flag_problem(!features_prefix.empty(), features_grid);
             if (problem.empty()) problem = tone_flag_problem(hdr, exposure, tone_name);
             if (problem.empty()) problem = denoise_flag_problem(denoise_flag, denoise_radius);
+            if (problem.empty()) problem = upsample_flag_problem(upsample_scale, upsample_radius);
             if (problem.empty()) problem = glare_flag_problem(glare_strength, glare_levels, glare_threshold);
             if (problem.empty() && build_name && *build_name != "host" && *build_name != "device") problem = "--build takes host or device";
             if (!problem.empty()) {
@@ -314,6 +320,7 @@ int main(int argc, char** argv) {
             }
             const std::optional<PyrToneParams> tone = tone_from_flags(exposure, tone_name);
             const std::optional<PyrGlareParams> glare_p = glare_from_flags(glare_strength, glare_levels, glare_threshold);
+            const std::optional<PyrUpsampleParams> upsample_p = upsample_from_flags(upsample_scale, upsample_radius);
             LoadedProject loaded = load_project(argv[2], std::string(argv[3]) == "-" ? TextureLoader() : texel_files(argv[3]));
             if (!size.empty()) { // WIDTHxHEIGHT, as python -m pyrite_amd --size
                 char* rest = nullptr;
@@ -321,12 +328,16 @@ int main(int argc, char** argv) {
                 loaded.project.image.height = (uint32_t)std::strtoul(rest && *rest ? rest + 1 : "0", nullptr, 10);
             }
             if (spp && *spp > 0) loaded.project.renderer.pixel_samples = (uint32_t)*spp;
-            const Project& project = loaded.project;
-            problem = denoise_flag_problem(denoise_flag, denoise_radius, project.renderer.pixel_samples, pass_samples);
+            problem = denoise_flag_problem(denoise_flag, denoise_radius, loaded.project.renderer.pixel_samples, pass_samples);
+            const uint32_t full_width = loaded.project.image.width, full_height = loaded.project.image.height;
+            if (problem.empty()) problem = upsample_flag_problem(upsample_scale, upsample_radius, full_width, full_height);
             if (!problem.empty()) {
                 std::fprintf(stderr, "error: %s\n", problem.c_str());
                 return 2;
             }
+            if (upsample_p) // the render and everything before the upsample at 1/N of the size, under the same camera
+                loaded.project.image.width = full_width / (uint32_t)*upsample_scale, loaded.project.image.height = full_height / (uint32_t)*upsample_scale;
+            const Project& project = loaded.project;
             std::unique_ptr<World> world = World::from_project(project.world, loaded.base_dir);
             const Camera cam = Camera::from_project(project.camera);
             Renderer r = Renderer::from_project(project.renderer);
@@ -371,14 +382,20 @@ int main(int argc, char** argv) {
                 r.render(film, cam, *world);
             }
             std::printf("Saving final result...\n"); // main.rs:313
-            if (!denoise_flag && (hdr || tone || glare_p)) linear = develop_linear(film, PYR_LINEAR_SRGB, project.image.filter, project.image.white);
-            if (glare_p) linear = glare(linear, film.width, film.height, *glare_p); // before the statistics of an automatic exposure, which tonemap takes
+            if (!denoise_flag && (hdr || tone || glare_p || upsample_p)) linear = develop_linear(film, PYR_LINEAR_SRGB, project.image.filter, project.image.white);
+            if (upsample_p) { // after the denoiser, before the glare
+                const Features low_guides = r.features(film.width, film.height, cam, *world), guides = r.features(full_width, full_height, cam, *world);
+                const std::vector<float> low_albedo = develop_linear(low_guides.albedo, PYR_LINEAR_SRGB, project.image.filter, project.image.white);
+                const std::vector<float> albedo = develop_linear(guides.albedo, PYR_LINEAR_SRGB, project.image.filter, project.image.white);
+                linear = upsample(linear, film.width, film.height, (uint32_t)*upsample_scale, *upsample_p, &albedo, &guides.pixels, &low_albedo, &low_guides.pixels);
+            }
+            if (glare_p) linear = glare(linear, full_width, full_height, *glare_p); // before the statistics of an automatic exposure, which tonemap takes
             save_png(argv[5],
-                     tone || denoise_flag || glare_p ? tonemap(linear, film.width, film.height, tone ? *tone : tone_params(PYR_TONE_CLIP, 1.0f))
-                                          : film.develop(project.image.filter, project.image.white),
-                     film.width, film.height);
+                     tone || denoise_flag || glare_p || upsample_p ? tonemap(linear, full_width, full_height, tone ? *tone : tone_params(PYR_TONE_CLIP, 1.0f))
+                                                                    : film.develop(project.image.filter, project.image.white),
+                     full_width, full_height);
             if (hdr) {
-                write_linear(*hdr, linear, film.width, film.height);
+                write_linear(*hdr, linear, full_width, full_height);
                 std::printf("wrote %s\n", hdr->c_str());
             }
             if (!film_path.empty()) {
@@ -386,7 +403,7 @@ int main(int argc, char** argv) {
                 f.write(reinterpret_cast<const char*>(film.grains.data()), (std::streamsize)(film.grains.size() * sizeof(PyrGrain)));
             }
             if (!features_prefix.empty()) {
-                write_feature_images(features_prefix, r.features(film.width, film.height, cam, *world, features_grid ? (uint32_t)*features_grid : 1u), project.image.filter,
+                write_feature_images(features_prefix, r.features(full_width, full_height, cam, *world, features_grid ? (uint32_t)*features_grid : 1u), project.image.filter,
                                      project.image.white);
                 std::printf("wrote %s_albedo.png, %s_normal.png, %s_depth.png\n", features_prefix.c_str(), features_prefix.c_str(), features_prefix.c_str());
             }

@@ -20,6 +20,9 @@ bool tone_needs_stats(const PyrToneParams* t);
 int check_denoise_params(const PyrDenoiseParams* p);
 int check_motion_blur_params(const PyrMotionBlurParams* p, const char* what); // `what` names the argument: params, blur_params
 int check_glare_params(const PyrGlareParams* p, const char* what);            // likewise: params, glare_params
+int check_upsample_params(const PyrUpsampleParams* p, const char* what, bool with_albedo); // likewise: params, upsample_params; the floor and the gain only with the albedo pair
+int check_upsample_scale(uint32_t scale);
+int check_upsample_size(uint32_t low_width, uint32_t low_height, uint32_t scale); // of the upsampled image
 
 // The per-wavelength tables of a development -- filter, white_div, white_mul, sample_count floats each, then the observer table --
 // are develop_table_floats(p) floats. develop_launch makes the launch record that reads them at `tables` (device); `host` receives
@@ -40,5 +43,10 @@ int enqueue_motion_blur(const float* image, const PyrMotionPixel* motion, uint32
 // The glare of `image` into `out` (kernels/glare.hip): both on the current device, the pyramid's levels allocated and freed in
 // stream order on `stream`.
 int enqueue_glare(const float* image, uint32_t width, uint32_t height, const PyrGlareParams* p, float* out, hipStream_t stream);
+
+// The upsampling of `low` to scale times its size into `out` (kernels/upsample.hip): every buffer on the current device, one
+// launch on `stream`. Either pair is null or given whole.
+int enqueue_upsample(const float* low, const float* low_albedo, const PyrFeaturePixel* low_pixels, uint32_t low_width, uint32_t low_height, uint32_t scale,
+                     const float* albedo, const PyrFeaturePixel* pixels, const PyrUpsampleParams* p, float* out, hipStream_t stream);
 
 } // namespace pyr

@@ -1,7 +1,7 @@
 // image_ops.cpp -- the entry points of include/pyrite_gpu.h that take a device number and never see a scene: a film developed to
 // an 8-bit or a linear image, an image's luminance statistics, its tone mapping, the denoising of two half images, the
 // accumulation of linear images over frames along their motion records (plain, and as the temporal resolve), the motion blur of
-// one along them, the glare of one. Every operation is stated in three parts, each once ("adding an image entry"):
+// one along them, the glare of one, the guided upsampling of one. Every operation is stated in three parts, each once ("adding an image entry"):
 //   its checks, composed from the pieces below in the order that entry refuses in (tests/golden/image_refusals.json pins it);
 //   one enqueue_... function: device pointers, the public parameter block, a stream -- the one place its launch record is built;
 //   two entries: the _device form is checks, use_device, enqueue; the host form is checks, use_device and Staging::finish, which
@@ -184,6 +184,30 @@ int check_glare_params(const PyrGlareParams* p, const char* what) {
     return PYR_OK;
 }
 
+// What the three upsample entries refuse of their parameters before a device is looked for (`what`: params or upsample_params).
+// The floor and the gain are read only with the albedo pair, so only then are they held to their ranges.
+int check_upsample_params(const PyrUpsampleParams* p, const char* what, bool with_albedo) {
+    const std::string name = std::string(what) + "->";
+    if (!p) return fail(PYR_ERR_INVALID_ARGUMENT, std::string("null argument: ") + what);
+    if (p->radius < 1 || p->radius > PYR_UPSAMPLE_MOST_RADIUS) return fail(PYR_ERR_INVALID_ARGUMENT, name + "radius must be 1..3");
+    if (p->flags & ~PYR_UPSAMPLE_MATCH_MATERIAL) return fail(PYR_ERR_INVALID_ARGUMENT, name + "flags has an unknown bit: PYR_UPSAMPLE_MATCH_MATERIAL or 0");
+    if (with_albedo && !(p->albedo_floor > 0.0f)) return fail(PYR_ERR_INVALID_ARGUMENT, name + "albedo_floor must be positive");
+    if (with_albedo && !(p->max_gain >= 1.0f)) return fail(PYR_ERR_INVALID_ARGUMENT, name + "max_gain must be at least 1");
+    if (p->reserved[0] != 0 || p->reserved[1] != 0) return fail(PYR_ERR_INVALID_ARGUMENT, name + "reserved must be 0");
+    return PYR_OK;
+}
+int check_upsample_scale(uint32_t scale) {
+    if (scale < 2 || scale > PYR_UPSAMPLE_MOST_SCALE) return fail(PYR_ERR_INVALID_ARGUMENT, "scale must be 2..8");
+    return PYR_OK;
+}
+// The size of the upsampled image: 2^32 - 1 pixels at the most, and neither side above 2^24, up to which the rule's f32 coordinates are exact.
+int check_upsample_size(uint32_t low_width, uint32_t low_height, uint32_t scale) {
+    const uint64_t width = (uint64_t)low_width * scale, height = (uint64_t)low_height * scale;
+    if (width * height > kMaxImagePixels) return fail(PYR_ERR_UNSUPPORTED, "an upsampled image of more than 2^32 - 1 pixels");
+    if (width > (1u << 24) || height > (1u << 24)) return fail(PYR_ERR_UNSUPPORTED, "an upsampled image with a side of more than 2^24 pixels");
+    return PYR_OK;
+}
+
 // Variance, the two filter launches with the halves exchanged, the combine: everything on `stream`, every buffer on the current
 // device; `work` holds three images of width * height * 3 floats (V, FA, FB).
 int enqueue_denoise(const float* a, const float* b, const float* albedo, const PyrFeaturePixel* pixels, uint32_t width, uint32_t height, const PyrDenoiseParams* p,
@@ -224,6 +248,22 @@ int enqueue_glare(const float* image, uint32_t width, uint32_t height, const Pyr
         const GlareLaunch L{image, width, height, p->strength, p->threshold, p->falloff, p->levels, (float*)work, out};
         return launch_glare(L, stream);
     });
+}
+
+// The upsampling of `low` to scale times its size into `out` (kernels/upsample.hip): every buffer on the current device, one launch
+// on `stream`, no working memory. Either pair is null or given whole.
+int enqueue_upsample(const float* low, const float* low_albedo, const PyrFeaturePixel* low_pixels, uint32_t low_width, uint32_t low_height, uint32_t scale,
+                     const float* albedo, const PyrFeaturePixel* pixels, const PyrUpsampleParams* p, float* out, hipStream_t stream) {
+    UpsampleLaunch L{};
+    L.low = low, L.low_albedo = low_albedo, L.low_pixels = low_pixels;
+    L.low_width = low_width, L.low_height = low_height, L.scale = scale;
+    L.albedo = albedo, L.pixels = pixels;
+    L.radius = p->radius;
+    L.use_normal = p->sigma_normal > 0.0f, L.use_depth = p->sigma_depth > 0.0f, L.match_material = (p->flags & PYR_UPSAMPLE_MATCH_MATERIAL) != 0;
+    L.normal_div = 2.0f * (p->sigma_normal * p->sigma_normal), L.depth_div = 2.0f * (p->sigma_depth * p->sigma_depth);
+    L.albedo_floor = p->albedo_floor, L.max_gain = p->max_gain;
+    L.out = out;
+    return launch_upsample(L, stream);
 }
 
 } // namespace pyr
@@ -355,6 +395,18 @@ int check_glare_args(const void* image, uint32_t width, uint32_t height, const P
     if (int bad = check_given({{image, 0, "image"}, {p, 0, "params"}, {out, 0, "out"}})) return bad;
     if (int bad = check_not_empty(width, height)) return bad;
     return check_glare_params(p, "params");
+}
+
+// Half a pair before the extent, the scale and the parameters; the size is left to the entries, which refuse it last.
+int check_upsample_args(const void* low, const void* low_albedo, const void* low_pixels, uint32_t low_width, uint32_t low_height, uint32_t scale, const void* albedo,
+                        const void* pixels, const PyrUpsampleParams* p, const void* out) {
+    if (int bad = check_given({{low, 0, "low"}, {p, 0, "params"}, {out, 0, "out"}})) return bad;
+    if ((low_albedo != nullptr) != (albedo != nullptr)) return fail(PYR_ERR_INVALID_ARGUMENT, "low_albedo and albedo are both null or both given");
+    if ((low_pixels != nullptr) != (pixels != nullptr)) return fail(PYR_ERR_INVALID_ARGUMENT, "low_pixels and pixels are both null or both given");
+    if (low_width == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "low_width: an empty image");
+    if (low_height == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "low_height: an empty image");
+    if (int bad = check_upsample_scale(scale)) return bad;
+    return check_upsample_params(p, "params", albedo != nullptr);
 }
 
 // A development with its small per-wavelength tables copied for the call: allocated in stream order, filled, handed to `launch`
@@ -608,6 +660,30 @@ int pyr_image_glare(const float* image, uint32_t width, uint32_t height, const P
     const size_t image_bytes = (size_t)width * height * 3 * sizeof(float);
     Staging S;
     return S.finish(enqueue_glare, S.in(image, image_bytes), width, height, params, S.out(out, image_bytes), nullptr);
+}
+
+int pyr_image_upsample_device(const float* low_device, const float* low_albedo_device, const PyrFeaturePixel* low_pixels_device, uint32_t low_width,
+                              uint32_t low_height, uint32_t scale, const float* albedo_device, const PyrFeaturePixel* pixels_device, const PyrUpsampleParams* params,
+                              float* out_device, int device, void* hip_stream) {
+    int rc = check_upsample_args(low_device, low_albedo_device, low_pixels_device, low_width, low_height, scale, albedo_device, pixels_device, params, out_device);
+    if (rc != PYR_OK) return rc;
+    if ((((uintptr_t)low_pixels_device | (uintptr_t)pixels_device) & 15u) != 0) // records are read as 16-byte vectors
+        return fail(PYR_ERR_INVALID_ARGUMENT, "low_pixels_device and pixels_device must be 16-byte aligned");
+    if (int bad = use_device(check_upsample_size(low_width, low_height, scale), device)) return bad;
+    return enqueue_upsample(low_device, low_albedo_device, low_pixels_device, low_width, low_height, scale, albedo_device, pixels_device, params, out_device,
+                            (hipStream_t)hip_stream);
+}
+
+int pyr_image_upsample(const float* low, const float* low_albedo, const PyrFeaturePixel* low_pixels, uint32_t low_width, uint32_t low_height, uint32_t scale,
+                       const float* albedo, const PyrFeaturePixel* pixels, const PyrUpsampleParams* params, float* out, int device) {
+    int rc = check_upsample_args(low, low_albedo, low_pixels, low_width, low_height, scale, albedo, pixels, params, out);
+    if (rc == PYR_OK) rc = check_upsample_size(low_width, low_height, scale);
+    if (int bad = use_device(rc, device)) return bad;
+    const size_t low_count = (size_t)low_width * low_height, count = low_count * scale * scale, pixel_bytes = 3 * sizeof(float);
+    Staging S;
+    return S.finish(enqueue_upsample, S.in(low, low_count * pixel_bytes), S.in(low_albedo, low_count * pixel_bytes), S.in(low_pixels, low_count * sizeof(PyrFeaturePixel)),
+                    low_width, low_height, scale, S.in(albedo, count * pixel_bytes), S.in(pixels, count * sizeof(PyrFeaturePixel)), params, S.out(out, count * pixel_bytes),
+                    nullptr);
 }
 
 } // extern "C"

@@ -106,6 +106,59 @@ int enqueue_then_sync(PyrSession* s, Enqueue enqueue) {
     return rc != PYR_OK ? rc : synced;
 }
 
+// What pyr_session_denoised refuses, pyr_session_upsampled with it: the arguments, then a session without halves or with one pass.
+int check_denoised_args(PyrSession* s, const PyrDevelopParams* develop_params, const PyrFeatureParams* feature_params, const PyrDenoiseParams* denoise_params,
+                        const void* out) {
+    int rc = check_linear_args(&s->film, s, develop_params, PYR_LINEAR_SRGB, out);
+    if (rc != PYR_OK || (rc = check_denoise_params(denoise_params)) != PYR_OK) return rc;
+    if (feature_params && (rc = check_feature_args(s, "session", nullptr, false, &s->film, feature_params, s, s)) != PYR_OK) return rc;
+    if ((rc = session_ready(s)) != PYR_OK) return rc;
+    if (!s->halves) return fail(PYR_ERR_INVALID_ARGUMENT, "denoising needs the two half films: create the session with PYR_SESSION_HALVES");
+    if (s->passes < 2) return fail(PYR_ERR_INVALID_ARGUMENT, "denoising needs at least two passes: one half film is still empty");
+    return PYR_OK;
+}
+
+// The feature pass with the session's camera over `film` -- the session's own, or one of more pixels over the same view -- and its
+// albedo film developed with `p` into `albedo_out`, on the session's stream. The two buffers are allocated here and belong to the
+// caller, who frees them after the wait.
+int session_feature_images(PyrSession* s, const PyrFilmDesc* film, const PyrDevelopParams* p, const PyrFeatureParams* fp, DeviceBuffer& albedo_film, DeviceBuffer& records,
+                           float* albedo_out) {
+    int rc;
+    const size_t count = (size_t)film->width * film->height, albedo_bytes = count * fp->albedo_bins * sizeof(PyrGrain);
+    if ((rc = albedo_film.alloc(albedo_bytes)) != PYR_OK || (rc = records.alloc(count * sizeof(PyrFeaturePixel))) != PYR_OK) return rc;
+    HIP_TRY(hipMemsetAsync(albedo_film.ptr, 0, albedo_bytes, s->stream));
+    if ((rc = enqueue_features(s->scene, &s->camera, film, fp, (PyrGrain*)albedo_film.ptr, (PyrFeaturePixel*)records.ptr, s->stream)) != PYR_OK) return rc;
+    LinearLaunch L{};
+    if ((rc = session_develop_launch(s, p, L.develop)) != PYR_OK) return rc;
+    L.space = PYR_LINEAR_SRGB;
+    L.develop.film = *film;
+    L.develop.film.bins = fp->albedo_bins; // the same span, tables and parameters
+    L.develop.grains = (const PyrGrain*)albedo_film.ptr, L.develop.grains_b = nullptr, L.out = albedo_out;
+    return launch_develop_linear(L, s->stream);
+}
+
+// The device side of pyr_session_denoised. `images`: eight images of the film's size in one allocation, made by the caller --
+// 0, 1: the halves developed; 2: the developed albedo (with features); 3..5: the filter's working images; 6: the result; 7: the
+// error image, when it is asked for.
+struct DenoisedImages {
+    DeviceBuffer images, albedo_film, records;
+    float* at(const PyrSession* s, size_t i) const { return (float*)images.ptr + i * (size_t)s->film.width * s->film.height * 3; }
+};
+int session_denoised(PyrSession* s, const PyrDevelopParams* develop_params, const PyrFeatureParams* feature_params, const PyrDenoiseParams* denoise_params, bool with_error,
+                     DenoisedImages& D) {
+    int rc;
+    LinearLaunch L{};
+    if ((rc = session_develop_launch(s, develop_params, L.develop)) != PYR_OK) return rc;
+    L.space = PYR_LINEAR_SRGB;
+    L.develop.grains = (const PyrGrain*)s->film_a.ptr, L.develop.grains_b = nullptr, L.out = D.at(s, 0);
+    if ((rc = launch_develop_linear(L, s->stream)) != PYR_OK) return rc;
+    L.develop.grains = (const PyrGrain*)s->film_b.ptr, L.out = D.at(s, 1);
+    if ((rc = launch_develop_linear(L, s->stream)) != PYR_OK) return rc;
+    if (feature_params && (rc = session_feature_images(s, &s->film, develop_params, feature_params, D.albedo_film, D.records, D.at(s, 2))) != PYR_OK) return rc;
+    return enqueue_denoise(D.at(s, 0), D.at(s, 1), feature_params ? D.at(s, 2) : nullptr, feature_params ? (const PyrFeaturePixel*)D.records.ptr : nullptr, s->film.width,
+                           s->film.height, denoise_params, D.at(s, 3), D.at(s, 6), with_error ? D.at(s, 7) : nullptr, s->stream);
+}
+
 } // namespace
 
 extern "C" {
@@ -416,41 +469,60 @@ int pyr_session_denoised(PyrSession* session, const PyrDevelopParams* develop_pa
                          float* out, float* error_out) {
     if (!session) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: session");
     PyrSession* s = session;
-    int rc = check_linear_args(&s->film, s, develop_params, PYR_LINEAR_SRGB, out);
-    if (rc != PYR_OK || (rc = check_denoise_params(denoise_params)) != PYR_OK) return rc;
-    if (feature_params && (rc = check_feature_args(s, "session", nullptr, false, &s->film, feature_params, s, s)) != PYR_OK) return rc;
-    if ((rc = session_ready(s)) != PYR_OK) return rc;
-    if (!s->halves) return fail(PYR_ERR_INVALID_ARGUMENT, "denoising needs the two half films: create the session with PYR_SESSION_HALVES");
-    if (s->passes < 2) return fail(PYR_ERR_INVALID_ARGUMENT, "denoising needs at least two passes: one half film is still empty");
-    const size_t count = (size_t)s->film.width * s->film.height, image_bytes = count * 3 * sizeof(float);
-    // a, b, the developed albedo, the filter's three working images, out, error_out: one allocation of eight images
-    DeviceBuffer images, albedo_film, records;
-    if ((rc = images.alloc(8 * image_bytes)) != PYR_OK) return rc;
-    float* image = (float*)images.ptr;
-    auto at = [&](size_t i) { return image + i * count * 3; };
+    int rc = check_denoised_args(s, develop_params, feature_params, denoise_params, out);
+    if (rc != PYR_OK) return rc;
+    const size_t image_bytes = (size_t)s->film.width * s->film.height * 3 * sizeof(float);
+    DenoisedImages D;
+    if ((rc = D.images.alloc(8 * image_bytes)) != PYR_OK) return rc;
+    return enqueue_then_sync(s, [&]() -> int {
+        int rc = session_denoised(s, develop_params, feature_params, denoise_params, error_out != nullptr, D);
+        if (rc != PYR_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(out, D.at(s, 6), image_bytes, hipMemcpyDeviceToHost, s->stream));
+        if (error_out) HIP_TRY(hipMemcpyAsync(error_out, D.at(s, 7), image_bytes, hipMemcpyDeviceToHost, s->stream));
+        return PYR_OK;
+    });
+}
+
+int pyr_session_upsampled(PyrSession* session, uint32_t scale, const PyrDevelopParams* develop_params, const PyrFeatureParams* feature_params,
+                          const PyrDenoiseParams* denoise_params, const PyrUpsampleParams* upsample_params, float* out) {
+    if (!session) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: session");
+    if (!develop_params) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: develop_params");
+    if (!out) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: out");
+    PyrSession* s = session;
+    int rc = check_upsample_scale(scale); // what needs no session comes first: before a device is looked for
+    if (rc != PYR_OK || (rc = check_upsample_params(upsample_params, "upsample_params", feature_params != nullptr)) != PYR_OK) return rc;
+    if ((rc = check_upsample_size(s->film.width, s->film.height, scale)) != PYR_OK) return rc;
+    PyrFilmDesc high = s->film; // the same camera over scale * scale as many pixels: Camera::to_view_area maps a block of them onto one of the film's
+    high.width *= scale, high.height *= scale;
+    if (denoise_params)
+        rc = check_denoised_args(s, develop_params, feature_params, denoise_params, out);
+    else if ((rc = check_linear_args(&s->film, s, develop_params, PYR_LINEAR_SRGB, out)) == PYR_OK && feature_params)
+        rc = check_feature_args(s, "session", nullptr, false, &s->film, feature_params, s, s);
+    if (rc == PYR_OK && feature_params) rc = check_feature_args(s, "session", nullptr, false, &high, feature_params, s, s);
+    if (rc != PYR_OK || (rc = session_ready(s)) != PYR_OK) return rc;
+    const size_t low_count = (size_t)s->film.width * s->film.height, count = low_count * scale * scale, low_bytes = low_count * 3 * sizeof(float), image_bytes = count * 3 * sizeof(float);
+    DenoisedImages D;
+    DeviceBuffer high_albedo_film, high_records, high_images; // high_images: the developed albedo (with features), then out
+    if (denoise_params && (rc = D.images.alloc(8 * low_bytes)) != PYR_OK) return rc;
+    if (!denoise_params && feature_params && (rc = D.images.alloc(3 * low_bytes)) != PYR_OK) return rc; // only image 2, the low albedo, is used
+    if ((rc = high_images.alloc(2 * image_bytes)) != PYR_OK) return rc;
+    float *albedo = (float*)high_images.ptr, *out_dev = albedo + count * 3;
     return enqueue_then_sync(s, [&]() -> int {
         int rc;
-        LinearLaunch L{};
-        if ((rc = session_develop_launch(s, develop_params, L.develop)) != PYR_OK) return rc;
-        L.space = PYR_LINEAR_SRGB;
-        L.develop.grains = (const PyrGrain*)s->film_a.ptr, L.develop.grains_b = nullptr, L.out = at(0);
-        if ((rc = launch_develop_linear(L, s->stream)) != PYR_OK) return rc;
-        L.develop.grains = (const PyrGrain*)s->film_b.ptr, L.out = at(1);
-        if ((rc = launch_develop_linear(L, s->stream)) != PYR_OK) return rc;
-        if (feature_params) {
-            const size_t albedo_bytes = count * feature_params->albedo_bins * sizeof(PyrGrain);
-            if ((rc = albedo_film.alloc(albedo_bytes)) != PYR_OK || (rc = records.alloc(count * sizeof(PyrFeaturePixel))) != PYR_OK) return rc;
-            HIP_TRY(hipMemsetAsync(albedo_film.ptr, 0, albedo_bytes, s->stream));
-            if ((rc = enqueue_features(s->scene, &s->camera, &s->film, feature_params, (PyrGrain*)albedo_film.ptr, (PyrFeaturePixel*)records.ptr, s->stream)) != PYR_OK) return rc;
-            L.develop.film.bins = feature_params->albedo_bins; // the same span, tables and parameters
-            L.develop.grains = (const PyrGrain*)albedo_film.ptr, L.out = at(2);
-            if ((rc = launch_develop_linear(L, s->stream)) != PYR_OK) return rc;
+        const float* low = nullptr;
+        if (denoise_params) {
+            if ((rc = session_denoised(s, develop_params, feature_params, denoise_params, false, D)) != PYR_OK) return rc;
+            low = D.at(s, 6);
+        } else {
+            if ((rc = session_linear(s, develop_params, PYR_LINEAR_SRGB)) != PYR_OK) return rc;
+            low = (const float*)s->linear.ptr;
+            if (feature_params && (rc = session_feature_images(s, &s->film, develop_params, feature_params, D.albedo_film, D.records, D.at(s, 2))) != PYR_OK) return rc;
         }
-        rc = enqueue_denoise(at(0), at(1), feature_params ? at(2) : nullptr, feature_params ? (const PyrFeaturePixel*)records.ptr : nullptr, s->film.width, s->film.height,
-                             denoise_params, at(3), at(6), error_out ? at(7) : nullptr, s->stream);
+        if (feature_params && (rc = session_feature_images(s, &high, develop_params, feature_params, high_albedo_film, high_records, albedo)) != PYR_OK) return rc;
+        rc = enqueue_upsample(low, feature_params ? D.at(s, 2) : nullptr, feature_params ? (const PyrFeaturePixel*)D.records.ptr : nullptr, s->film.width, s->film.height, scale,
+                              feature_params ? albedo : nullptr, feature_params ? (const PyrFeaturePixel*)high_records.ptr : nullptr, upsample_params, out_dev, s->stream);
         if (rc != PYR_OK) return rc;
-        HIP_TRY(hipMemcpyAsync(out, at(6), image_bytes, hipMemcpyDeviceToHost, s->stream));
-        if (error_out) HIP_TRY(hipMemcpyAsync(error_out, at(7), image_bytes, hipMemcpyDeviceToHost, s->stream));
+        if (hipMemcpyAsync(out, out_dev, image_bytes, hipMemcpyDeviceToHost, s->stream) != hipSuccess) return fail(PYR_ERR_DEVICE, "hipMemcpyAsync of the upsampled image failed");
         return PYR_OK;
     });
 }

@@ -376,6 +376,61 @@ def glare_from_flags(glare, glare_levels, glare_threshold):
     return params
 
 
+def upsample_params(radius=abi.PYR_UPSAMPLE_RADIUS, match_material=True, sigma_normal=abi.PYR_UPSAMPLE_SIGMA_NORMAL, sigma_depth=abi.PYR_UPSAMPLE_SIGMA_DEPTH,
+                    albedo_floor=abi.PYR_UPSAMPLE_ALBEDO_FLOOR, max_gain=abi.PYR_UPSAMPLE_MAX_GAIN, flags=None):
+    """abi.PyrUpsampleParams: (2*radius)^2 taps under a tent of that radius; a sigma <= 0 turns that guide off; `match_material`
+    sets PYR_UPSAMPLE_MATCH_MATERIAL (`flags`, when given, is the whole flag word instead)."""
+    word = (abi.PYR_UPSAMPLE_MATCH_MATERIAL if match_material else 0) if flags is None else int(flags)
+    return abi.PyrUpsampleParams(int(radius), word, float(sigma_normal), float(sigma_depth), float(albedo_floor), float(max_gain))
+
+
+def upsample(low, scale, albedo=None, pixels=None, low_albedo=None, low_pixels=None, device=0, **params):
+    """float32 [scale*height, scale*width, 3]: the linear image `low`, [height, width, 3], upsampled on the GPU under the guidance
+    of full-size feature images (pyr_image_upsample; include/pyrite_gpu.h has the arithmetic). The albedo pair -- `low_albedo` of
+    low's size, `albedo` of the result's, linear images -- demodulates, so that texture detail comes back at full size; the records
+    pair -- `low_pixels`, `pixels`, the records of the two feature passes (Features.records) -- keeps the taps on the pixel's own
+    surface. Each pair is given whole or not at all. `params`: upsample_params."""
+    low = _linear_image(low)
+    h, w, _ = low.shape
+    scale = int(scale)
+    if (albedo is None) != (low_albedo is None):
+        raise ValueError("albedo and low_albedo go together")
+    if (pixels is None) != (low_pixels is None):
+        raise ValueError("pixels and low_pixels go together")
+    if albedo is not None:
+        albedo, low_albedo = _linear_image(albedo), _linear_image(low_albedo)
+        assert low_albedo.shape == low.shape and albedo.shape == (h * scale, w * scale, 3)
+    if pixels is not None:
+        pixels, low_pixels = np.ascontiguousarray(pixels), np.ascontiguousarray(low_pixels)
+        assert low_pixels.nbytes == h * w * C.sizeof(abi.PyrFeaturePixel) and pixels.nbytes == low_pixels.nbytes * scale * scale
+    p = upsample_params(**params)
+    sized = min(max(scale, 1), abi.PYR_UPSAMPLE_MOST_SCALE)  # a scale the library refuses never writes
+    out = np.zeros((h * sized, w * sized, 3), dtype=np.float32)
+    check(lib().pyr_image_upsample(low.ctypes.data, _ptr(low_albedo), _ptr(low_pixels), w, h, scale, _ptr(albedo), _ptr(pixels), C.byref(p), out.ctypes.data, int(device)))
+    return out
+
+
+def upsample_flag_problem(upsample, upsample_radius, size=None):
+    """What is wrong with --upsample N / --upsample-radius R, in the words pyrite_host_tool uses too, or None. `size`: the image's
+    (width, height) once the project is loaded -- N must divide both."""
+    if upsample is None:
+        return "--upsample-radius needs --upsample" if upsample_radius is not None else None
+    if not 2 <= upsample <= abi.PYR_UPSAMPLE_MOST_SCALE:
+        return "--upsample must be 2 to %d" % abi.PYR_UPSAMPLE_MOST_SCALE
+    if upsample_radius is not None and not 1 <= upsample_radius <= abi.PYR_UPSAMPLE_MOST_RADIUS:
+        return "--upsample-radius must be 1 to %d" % abi.PYR_UPSAMPLE_MOST_RADIUS
+    if size is not None and (size[0] % upsample or size[1] % upsample):
+        return "--upsample %d does not divide the image size %dx%d" % (upsample, size[0], size[1])
+    return None
+
+
+def upsample_from_flags(upsample, upsample_radius):
+    """The upsample_params keywords of --upsample N --upsample-radius R, or None without --upsample."""
+    if upsample is None:
+        return None
+    return {"radius": upsample_radius} if upsample_radius is not None else {}
+
+
 def denoise_flag_problem(denoise, denoise_radius, pixel_samples=None, pass_samples=None):
     """What is wrong with --denoise / --denoise-radius, in the words pyrite_host_tool uses too, or None. `pixel_samples`: the
     render's budget once the project is loaded; `pass_samples`: --pass-samples, when given."""

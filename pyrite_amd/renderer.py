@@ -601,6 +601,25 @@ class Session:
         del keep
         return out, error
 
+    def upsampled(self, scale, step=2.0, filter=None, white=None, guides=True, grid=1, albedo_bins=16, denoise=None, **params):
+        """float32 [scale*height, scale*width, 3]: the film as it stands, the low image, developed to linear sRGB -- with `denoise`
+        (a dict of develop.denoise_params keywords, {} for the defaults) what denoised() gives instead -- and upsampled `scale` times
+        under the guidance of the feature pass at both sizes, all on the session's device (pyr_session_upsampled; develop.upsample of
+        linear() or denoised() and the two feature passes gives the same floats). Without `guides` no feature pass runs: the plain
+        tent. `params`: develop.upsample_params. The session's films are not touched."""
+        from .develop import denoise_params, develop_params, upsample_params
+
+        p, keep = develop_params(self._film, step, filter, white)
+        up = upsample_params(**params)
+        dp = denoise_params(**denoise) if denoise is not None else None
+        fp = abi.PyrFeatureParams(int(grid), int(albedo_bins)) if guides else None
+        sized = min(max(int(scale), 1), abi.PYR_UPSAMPLE_MOST_SCALE)  # a scale the library refuses never writes
+        out = np.zeros((self.height * sized, self.width * sized, 3), dtype=np.float32)
+        check(lib().pyr_session_upsampled(self.handle, int(scale), C.byref(p), C.byref(fp) if fp is not None else None, C.byref(dp) if dp is not None else None,
+                                          C.byref(up), out.ctypes.data))
+        del keep
+        return out
+
     def close(self):
         if self.handle:
             lib().pyr_session_destroy(self.handle)
