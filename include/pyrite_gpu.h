@@ -1377,6 +1377,75 @@ int pyr_image_upsample_device(const float* low_device, const float* low_albedo_d
 int pyr_session_upsampled(PyrSession* session, uint32_t scale, const PyrDevelopParams* develop_params, const PyrFeatureParams* feature_params,
                           const PyrDenoiseParams* denoise_params, const PyrUpsampleParams* upsample_params, float* out);
 
+/* ------------------------------------------------------------ despeckle ----
+ * Every image stage above assumes noise that behaves. A path tracer's does not: dispersive glass, small lamps and mirrors give, at
+ * preview sample counts, fireflies -- single pixels, in one half only, tens to thousands of times brighter than what surrounds them.
+ * The cross filter reads its weights from the other half, so it cannot see one and smears it over its window; the glare gives it a
+ * halo; the percentiles of the tone curve move. The two halves hold what tells a firefly from a highlight: a one-pixel lamp or
+ * glint is bright in both independent halves, a firefly in one. This clamps the second kind and keeps the first. It needs no scene.
+ *   `a`, `b`, `a_out`, `b_out`, `removed_out`: width*height*3 f32 in linear light. `b` and `b_out` are given together or both NULL;
+ * without them the filter works on one image, the agreement test below is dropped, and more is clamped along edges.
+ *   All arithmetic is f32 and unfused, one rounding per operation, in the order written; / is the correctly rounded one. "Finite"
+ * means neither an infinity nor a NaN.
+ *   Luminance, of every pixel of every given half:  Y = ((0.2126f*R + 0.7152f*G) + 0.0722f*B) + 0.0f  -- the statistics' expression;
+ *     the + 0.0f turns a -0 into +0, so that no -0 enters an ordering.
+ *   Sample set N(p): Y_H(q) for each given half H and each q of the (2*radius+1)^2 window around p clipped to the image, q = p
+ *     excluded (in both halves), finite values only. n = the number of them, at most 48. With n < PYR_DESPECKLE_LEAST_SAMPLES both
+ *     halves keep their bits at p.
+ *   Median and spread.  m = the lower median of N(p): element (n-1)/2 (integer division) of its ascending order.
+ *     s = the lower median, the same element, of fabsf(Y_i - m) over the same set.
+ *     spread = fmaxf(fmaxf(s * 1.4826f, relative * m), floor);   limit = m + k * spread.
+ *     Medians are selections, not sums: whatever algorithm selects, the bits are the same.
+ *   The firefly test. Half H holds a firefly at p when Y_H(p) is finite and Y_H(p) > limit and -- with the other half given -- it
+ *     is not the case that the other half's Y(p) is finite and > limit. The last clause keeps lamps, glints and the bright side of
+ *     an edge: what both halves saw.
+ *   The clamp.  g = limit / Y_H(p);  out_H(p).c = in_H(p).c * g: the hue is kept, the luminance lands on the limit. Every other
+ *     pixel of either half keeps its bits, the pixels that are not finite among them. (limit > 0 whenever m >= 0. A neighbourhood
+ *     whose median luminance is negative -- out-of-gamut colours throughout -- can make limit <= 0; g is then what the division gives.)
+ *   Reports, both optional.  d_H(p).c = in_H(p).c - out_H(p).c where H was clamped at p, 0.0f elsewhere.
+ *     removed_out(p).c = (d_a + d_b) * 0.5f with b, d_a without: the energy the mean of the halves lost, and where. For finite
+ *     pixels this is ((a - a_out) + (b - b_out)) * 0.5f bit for bit; at a pixel that is not finite it is 0.0f, not the NaN that
+ *     inf - inf would make, whose sign two IEEE machines need not agree on.
+ *     counts_out[0], counts_out[1]: the pixels clamped in a and in b (0 without b), summed by integer atomics.
+ * One lane owns a pixel, stores are plain, there is no float reduction: two calls write the same bytes. Outputs may not overlap
+ * inputs or each other: the rule reads neighbourhoods. No spectral form, no guides: the agreement of the halves does their job.
+ *   The defaults k = 6, relative = 0.1 come from a synthetic prototype (log-normal noise, planted outliers), not from renders. */
+#define PYR_DESPECKLE_RADIUS 2u
+#define PYR_DESPECKLE_MOST_RADIUS 2u
+#define PYR_DESPECKLE_K 6.0f
+#define PYR_DESPECKLE_RELATIVE 0.1f
+#define PYR_DESPECKLE_FLOOR 1e-4f
+#define PYR_DESPECKLE_LEAST_SAMPLES 5u
+typedef struct PyrDespeckleParams {
+    uint32_t radius;      /* 1..PYR_DESPECKLE_MOST_RADIUS: the window is (2*radius+1)^2 pixels */
+    float k;              /* finite, > 0: spreads above the median at which a pixel is a firefly */
+    float relative;       /* finite, >= 0: the spread is at least this share of the median */
+    float floor;          /* finite, > 0: and at least this much, which serves a black neighbourhood */
+    uint32_t flags;       /* none defined: any bit is refused */
+    uint32_t reserved[3]; /* 0 */
+} PyrDespeckleParams; /* 32 bytes */
+/* Arguments are checked before a device is looked for, in this order: PYR_ERR_INVALID_ARGUMENT, with the argument named in
+ * pyr_last_error, for a null a, params or a_out; for b without b_out or b_out without b; for an empty image (width, height);
+ * PYR_ERR_UNSUPPORTED for more than 2^32 - 1 pixels; PYR_ERR_INVALID_ARGUMENT again for a radius outside 1..2, a k or floor that is
+ * not finite and > 0, a relative that is not finite and >= 0, any flag bit, a non-zero reserved word, and for an output that
+ * overlaps an input or another output (the same pointer given twice does); only then PYR_ERR_DEVICE. counts_out: two uint32_t.
+ * HOST buffers. Blocking. */
+int pyr_image_despeckle(const float* a, const float* b, uint32_t width, uint32_t height, const PyrDespeckleParams* params, float* a_out, float* b_out,
+                        float* removed_out, uint32_t* counts_out, int device);
+/* The same with every buffer resident on `device`, enqueued on `hip_stream`. No output may overlap an input or another output
+ * (PYR_ERR_INVALID_ARGUMENT otherwise): a workgroup reads the neighbourhood of its tile while another writes. No working memory. */
+int pyr_image_despeckle_device(const float* a_device, const float* b_device, uint32_t width, uint32_t height, const PyrDespeckleParams* params, float* a_out_device,
+                               float* b_out_device, float* removed_out_device, uint32_t* counts_out_device, int device, void* hip_stream);
+/* On the session's stream and device (PYR_SESSION_HALVES and two passes, as pyr_session_denoised): half film A alone and half film
+ * B alone developed to linear sRGB, despeckled, and then, with `denoise_params`, cross filtered as pyr_session_denoised filters
+ * the raw halves (`feature_params`, optional, steers that filter and is not read without it); without `denoise_params`
+ * out = (a' + b') * 0.5f and error_out = fabsf(a' - b') * 0.5f of the cleaned halves a', b'. out = HOST, height*width*3 floats;
+ * error_out and removed_out likewise and optional; counts_out: two uint32_t, optional. The session's films are not touched, and
+ * further passes may follow. Blocking. */
+int pyr_session_despeckled(PyrSession* session, const PyrDevelopParams* develop_params, const PyrDespeckleParams* despeckle_params,
+                           const PyrFeatureParams* feature_params, const PyrDenoiseParams* denoise_params, float* out, float* error_out, float* removed_out,
+                           uint32_t* counts_out);
+
 #ifdef __cplusplus
 }
 #endif

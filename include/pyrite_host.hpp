@@ -454,6 +454,31 @@ std::string upsample_flag_problem(const std::optional<long>& upsample, const std
 // The parameters of --upsample N --upsample-radius R, or nothing without --upsample (pyrite_amd/develop.py upsample_from_flags).
 std::optional<PyrUpsampleParams> upsample_from_flags(const std::optional<long>& upsample, const std::optional<long>& upsample_radius);
 
+// ---- despeckle (pyrite_gpu.h "despeckle"; pyrite_amd/develop.py despeckle) ----
+PyrDespeckleParams despeckle_params(uint32_t radius = PYR_DESPECKLE_RADIUS, float k = PYR_DESPECKLE_K, float relative = PYR_DESPECKLE_RELATIVE, float floor = PYR_DESPECKLE_FLOOR);
+// What despeckle returns: the cleaned halves (b empty when none was given), what the mean of the halves lost, [height][width][3]
+// f32 each, and the pixels clamped in a and in b.
+struct Despeckled {
+    std::vector<float> a, b, removed;
+    uint32_t counts[2];
+};
+// The half images `a` and `b` (linear light, independent samples of one picture; `b` may be null: one image, no agreement test)
+// with their fireflies clamped on the GPU (pyr_image_despeckle). A buffer of another size than the image's is a ProjectError
+// before the library is called.
+Despeckled despeckle(const std::vector<float>& a, const std::vector<float>* b, uint32_t width, uint32_t height, const PyrDespeckleParams& params = despeckle_params(),
+                     int device = 0);
+// What is wrong with --despeckle [K] / --despeckle-radius R, in the words both front ends print, or "" (pyrite_amd/develop.py
+// despeckle_flag_problem). `despeckle`: K as it was given, or nothing without --despeckle.
+std::string despeckle_flag_problem(const std::optional<std::string>& despeckle, const std::optional<long>& despeckle_radius,
+                                   const std::optional<uint32_t>& pixel_samples = std::nullopt, const std::optional<long>& pass_samples = std::nullopt);
+// The parameters of --despeckle [K] --despeckle-radius R, or nothing without --despeckle (pyrite_amd/develop.py despeckle_from_flags).
+std::optional<PyrDespeckleParams> despeckle_from_flags(const std::optional<std::string>& despeckle, const std::optional<long>& despeckle_radius);
+// What Session::despeckled returns: the image, the noise left, what the clamp removed and the pixels clamped in either half.
+struct DespeckledImage {
+    std::vector<float> image, error, removed;
+    uint32_t counts[2];
+};
+
 struct Progress { // renderer/mod.rs:229-232
     uint8_t progress;
     const char* message;
@@ -540,6 +565,12 @@ class Session {
     std::vector<float> upsampled(uint32_t scale, const PyrUpsampleParams& params = upsample_params(), bool guides = true, const std::optional<PyrDenoiseParams>& denoise = std::nullopt,
                                  float step_size = 2.0f, const std::optional<Expression>& filter = std::nullopt, const std::optional<Expression>& white = std::nullopt,
                                  uint32_t grid = 1, uint32_t albedo_bins = 16);
+    // pyr_session_despeckled: the two half films developed to linear sRGB, their fireflies clamped, then cross filtered as denoised()
+    // filters the raw halves (`denoise`; `guides`, grid, albedo_bins: its feature pass) or, without `denoise`, their mean and half
+    // their difference, on the session's device. Needs halves and two passes; the films are not touched.
+    DespeckledImage despeckled(const PyrDespeckleParams& params = despeckle_params(), const std::optional<PyrDenoiseParams>& denoise = std::nullopt, bool guides = true,
+                               float step_size = 2.0f, const std::optional<Expression>& filter = std::nullopt, const std::optional<Expression>& white = std::nullopt,
+                               uint32_t grid = 1, uint32_t albedo_bins = 16);
     uint32_t tiles_x() const { return (width_ + tile_size_ - 1) / tile_size_; }
     uint32_t tiles_y() const { return (height_ + tile_size_ - 1) / tile_size_; }
 

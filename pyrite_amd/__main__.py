@@ -5,7 +5,7 @@
     python -m pyrite_amd path/to/project.lua [-o out.png] [--seed N] [--device D] [--spp N] [--size WxH]
                          [--pass-samples N] [--preview PATH] [--preview-every SECONDS] [--noise]
                          [--features PREFIX] [--features-grid N] [--hdr PATH] [--exposure EV|auto] [--tone clip|reinhard]
-                         [--denoise] [--denoise-radius N] [--upsample N] [--upsample-radius R]
+                         [--despeckle [K]] [--despeckle-radius R] [--denoise] [--denoise-radius N] [--upsample N] [--upsample-radius R]
                          [--glare [STRENGTH]] [--glare-levels N] [--glare-threshold T]
                          [--build host|device]
 
@@ -26,6 +26,12 @@ With --denoise the render runs as a session with two half films, in an even numb
 --pass-samples is not given; an odd number of samples per pixel is refused), and the final PNG and the --hdr image are written
 from the denoised linear image (pyr_session_denoised with the feature pass as its guide; window radius N, default 5): the PNG
 through the tone curve, which without --exposure / --tone is the clip at exposure 1, the encoder of the plain PNG.
+
+With --despeckle the render runs as a session with two half films, in an even number of equal passes as with --denoise, and the
+fireflies of the two developed halves are clamped before anything else reads them (pyr_session_despeckled: a pixel more than K
+spreads, default 6, above the median of its (2R+1)^2 window, R 1 or 2, default 2, in one half and not in the other): the order of
+the stages is develop the halves, despeckle, denoise (with --denoise) or the mean of the halves, upsample, glare, tone. One line
+with the pixels clamped in either half is printed. Previews are not despeckled.
 
 With --upsample N the render runs at width/N x height/N with the project's camera -- N (2 to 8) must divide both -- and the final
 image, of the project's size, is its linear image (the denoised one with --denoise) upsampled under the guidance of the first-hit
@@ -65,8 +71,8 @@ def render_progressive(r, cam, world, film, args, image, on_status):
 
     from .develop import save_png
 
-    pass_samples = args.pass_samples or (r.pixel_samples // 2 if args.denoise else DEFAULT_PASS_SAMPLES)
-    with r.session((film.width, film.height), cam, world, halves=args.noise or args.denoise, device=args.device) as s:
+    pass_samples = args.pass_samples or (r.pixel_samples // 2 if args.denoise or args.despeckle_params is not None else DEFAULT_PASS_SAMPLES)
+    with r.session((film.width, film.height), cam, world, halves=args.noise or args.denoise or args.despeckle_params is not None, device=args.device) as s:
         on_status(0, "Rendering")
         last_image = time.monotonic()  # main.rs:241
         while s.samples_done < r.pixel_samples:
@@ -80,7 +86,11 @@ def render_progressive(r, cam, world, film, args, image, on_status):
                     noise = s.noise()
                     print("noise: largest tile %.4g, median tile %.4g" % (float(noise.max()), float(np.median(noise))))
                 last_image = time.monotonic()
-        if args.denoise:
+        if args.despeckle_params is not None:  # the halves cleaned, then the denoiser or their mean
+            denoise = None if not args.denoise else {} if args.denoise_radius is None else {"radius": args.denoise_radius}
+            args.denoised, _, _, counts = s.despeckled(2.0, filter=image.get("filter"), white=image.get("white"), denoise=denoise, **args.despeckle_params)
+            print("\ndespeckle: %d pixels clamped in half A, %d in half B" % counts)
+        elif args.denoise:
             params = {} if args.denoise_radius is None else {"radius": args.denoise_radius}
             args.denoised = s.denoised(2.0, filter=image.get("filter"), white=image.get("white"), **params)[0]
         return s.film()
@@ -103,6 +113,8 @@ def main(argv=None):
     ap.add_argument("--hdr", default=None, metavar="PATH", help="also write the image in linear light: PATH.hdr (Radiance RGBE) or PATH.pfm")
     ap.add_argument("--exposure", default=None, metavar="EV|auto", help="exposure of the PNG and the previews in stops, or auto")
     ap.add_argument("--tone", default=None, metavar="clip|reinhard", help="tone curve of the PNG and the previews (reinhard alone means --exposure auto)")
+    ap.add_argument("--despeckle", nargs="?", const=str(6.0), default=None, metavar="K", help="clamp the fireflies of the two half images before they are denoised or averaged: spreads above the median at which a pixel is one (above 0, default 6)")
+    ap.add_argument("--despeckle-radius", type=int, default=None, metavar="R", help="window radius of --despeckle (1 or 2, default 2)")
     ap.add_argument("--denoise", action="store_true", help="write the PNG and the --hdr image from the denoised linear image of two half films")
     ap.add_argument("--denoise-radius", type=int, default=None, metavar="N", help="window radius of --denoise (1 to 10, default 5)")
     ap.add_argument("--upsample", type=int, default=None, metavar="N", help="render at 1/N of the image size (2 to 8, N divides both sides) and upsample under the guidance of the feature pass")
@@ -112,17 +124,19 @@ def main(argv=None):
     ap.add_argument("--glare-threshold", type=float, default=None, metavar="T", help="luminance below which a pixel spreads nothing (default 0: every pixel spreads)")
     ap.add_argument("--build", default=None, choices=["host", "device"], help="who builds the BVH (default host); given, the stage times of scene creation go to stderr")
     args = ap.parse_args(argv)
-    from .develop import denoise_flag_problem, glare_flag_problem, glare_from_flags, tone_flag_problem, tone_from_flags, upsample_flag_problem, upsample_from_flags
+    from .develop import denoise_flag_problem, despeckle_flag_problem, despeckle_from_flags, glare_flag_problem, glare_from_flags, tone_flag_problem, tone_from_flags, upsample_flag_problem, upsample_from_flags
     from .features import features_flag_problem
 
     problem = (progressive_flag_problem(args.pass_samples, args.preview, args.preview_every, args.noise) or features_flag_problem(args.features, args.features_grid)
-               or tone_flag_problem(args.hdr, args.exposure, args.tone) or denoise_flag_problem(args.denoise, args.denoise_radius)
+               or tone_flag_problem(args.hdr, args.exposure, args.tone) or despeckle_flag_problem(args.despeckle, args.despeckle_radius)
+               or denoise_flag_problem(args.denoise, args.denoise_radius)
                or upsample_flag_problem(args.upsample, args.upsample_radius) or glare_flag_problem(args.glare, args.glare_levels, args.glare_threshold))
     if problem:
         print("error: " + problem, file=sys.stderr)
         return 2
 
     args.tone_params = tone_from_flags(args.exposure, args.tone)
+    args.despeckle_params = despeckle_from_flags(args.despeckle, args.despeckle_radius)
     args.glare_params = glare_from_flags(args.glare, args.glare_levels, args.glare_threshold)
     args.upsample_params = upsample_from_flags(args.upsample, args.upsample_radius)
 
@@ -135,7 +149,8 @@ def main(argv=None):
         project.setdefault("image", {}).update(width=w, height=h)
     if args.spp:
         project["renderer"] = project["renderer"].with_(pixel_samples=args.spp)
-    problem = denoise_flag_problem(args.denoise, args.denoise_radius, int(project["renderer"].pixel_samples), args.pass_samples)
+    problem = despeckle_flag_problem(args.despeckle, args.despeckle_radius, int(project["renderer"].pixel_samples), args.pass_samples)
+    problem = problem or denoise_flag_problem(args.denoise, args.denoise_radius, int(project["renderer"].pixel_samples), args.pass_samples)
     full_size = (int(project["image"]["width"]), int(project["image"]["height"]))
     problem = problem or upsample_flag_problem(args.upsample, args.upsample_radius, full_size)
     if problem:
@@ -159,14 +174,14 @@ def main(argv=None):
 
     t = time.time()
     image = project.get("image") or {}
-    if args.pass_samples is not None or args.preview or args.noise or args.denoise:
+    if args.pass_samples is not None or args.preview or args.noise or args.denoise or args.despeckle_params is not None:
         film = render_progressive(r, cam, world, film, args, image, on_status)
     else:
         r.render(film, cam, world, on_status=on_status, device=args.device)
     print("\rRendering... done in %.2f s (%.1f Msamples/s)" % (time.time() - t, film.width * film.height * r.pixel_samples / (time.time() - t) / 1e6))
     print("Saving final result...")  # main.rs:313
     linear = None
-    if args.denoise:
+    if args.denoise or args.despeckle_params is not None:
         linear = args.denoised
     elif args.hdr or args.tone_params is not None or args.glare_params is not None or args.upsample:
         linear = develop_linear(film, "srgb", filter=image.get("filter"), white=image.get("white"), device=args.device)
@@ -177,7 +192,7 @@ def main(argv=None):
                           **args.upsample_params)
     if args.glare_params is not None:  # before the statistics of an automatic exposure, which tonemap takes
         linear = glare(linear, device=args.device, **args.glare_params)
-    if args.tone_params is not None or args.denoise or args.glare_params is not None or args.upsample:
+    if args.tone_params is not None or args.denoise or args.despeckle_params is not None or args.glare_params is not None or args.upsample:
         rgb = tonemap(linear, args.tone_params, device=args.device)
     else:
         rgb = develop(film, filter=image.get("filter"), white=image.get("white"), device=args.device)

@@ -487,6 +487,13 @@ class PyrUpsampleParams(C.Structure):
                 ("max_gain", C.c_float), ("reserved", C.c_uint32 * 2)]
 
 
+PYR_DESPECKLE_RADIUS, PYR_DESPECKLE_MOST_RADIUS, PYR_DESPECKLE_K, PYR_DESPECKLE_RELATIVE, PYR_DESPECKLE_FLOOR, PYR_DESPECKLE_LEAST_SAMPLES = 2, 2, 6.0, 0.1, 1e-4, 5
+
+
+class PyrDespeckleParams(C.Structure):
+    _fields_ = [("radius", C.c_uint32), ("k", C.c_float), ("relative", C.c_float), ("floor", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
+
+
 PyrProgressFn = C.CFUNCTYPE(None, C.c_void_p, C.c_uint8, C.c_char_p)
 PyrPreviewFn = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, C.c_uint32)
 
@@ -613,6 +620,12 @@ ENTRY_POINTS = {
     "pyr_session_upsampled": (
         C.c_int,
         [C.c_void_p, C.c_uint32, C.POINTER(PyrDevelopParams), C.POINTER(PyrFeatureParams), C.POINTER(PyrDenoiseParams), C.POINTER(PyrUpsampleParams), C.c_void_p],
+    ),
+    "pyr_image_despeckle": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PyrDespeckleParams)] + [C.c_void_p] * 4 + [C.c_int]),
+    "pyr_image_despeckle_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PyrDespeckleParams)] + [C.c_void_p] * 4 + [C.c_int, C.c_void_p]),
+    "pyr_session_despeckled": (
+        C.c_int,
+        [C.c_void_p, C.POINTER(PyrDevelopParams), C.POINTER(PyrDespeckleParams), C.POINTER(PyrFeatureParams), C.POINTER(PyrDenoiseParams)] + [C.c_void_p] * 4,
     ),
 }
 

@@ -426,6 +426,22 @@ struct UpsampleLaunch {
 };
 int launch_upsample(const UpsampleLaunch& launch, void* stream);
 
+// kernels/despeckle.hip: the firefly clamp of one or two half images (pyrite_gpu.h "despeckle"). The counts
+// are zeroed and one kernel is launched on `stream`; no working memory. No output overlaps an input or another output.
+struct DespeckleLaunch {
+    const float* a; // device, height * width * 3 floats
+    const float* b; // device, the same size, or null: one image, no agreement test
+    uint32_t width, height;
+    uint32_t radius; // 1..PYR_DESPECKLE_MOST_RADIUS
+    float k, relative, floor;
+    float* a_out;     // device, the size of a
+    float* b_out;     // device, given with b
+    float* removed;   // device, the size of a, or null
+    uint32_t* counts; // device, two words, or null
+    uint32_t tiles_x; // the launcher's
+};
+int launch_despeckle(const DespeckleLaunch& launch, void* stream);
+
 // launchers (kernels/main.hip)
 // wide_vm: the scene has a program that only the wide interpreter build (kernels/wide.hip) holds
 int launch_render(const DevScene& scene, const RenderLaunch& launch, bool with_counters, void* stream, int num_cus, bool wide_vm = false);

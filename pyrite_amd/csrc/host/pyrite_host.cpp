@@ -1692,6 +1692,42 @@ std::optional<PyrUpsampleParams> upsample_from_flags(const std::optional<long>& 
     return upsample_params(upsample_radius ? (uint32_t)*upsample_radius : PYR_UPSAMPLE_RADIUS);
 }
 
+// ---- despeckle -----------------------------------------------------------------------------------------------------------------
+PyrDespeckleParams despeckle_params(uint32_t radius, float k, float relative, float floor) { return PyrDespeckleParams{radius, k, relative, floor, 0u, {0u, 0u, 0u}}; }
+Despeckled despeckle(const std::vector<float>& a, const std::vector<float>* b, uint32_t width, uint32_t height, const PyrDespeckleParams& params, int device) {
+    const size_t floats = (size_t)width * height * 3;
+    if (a.size() != floats || (b && b->size() != floats)) throw ProjectError("despeckle: buffer size does not match the image size");
+    Despeckled out{std::vector<float>(floats, 0.0f), std::vector<float>(b ? floats : 0, 0.0f), std::vector<float>(floats, 0.0f), {0u, 0u}};
+    check_status(pyr_image_despeckle(a.data(), b ? b->data() : nullptr, width, height, &params, out.a.data(), b ? out.b.data() : nullptr, out.removed.data(), out.counts, device));
+    return out;
+}
+DespeckledImage Session::despeckled(const PyrDespeckleParams& params, const std::optional<PyrDenoiseParams>& denoise, bool guides, float step_size,
+                                    const std::optional<Expression>& filter, const std::optional<Expression>& white, uint32_t grid, uint32_t albedo_bins) {
+    const DevelopSetup setup(shape_, filter, white, step_size);
+    const PyrFeatureParams fp{grid, albedo_bins, {0, 0}};
+    const size_t floats = (size_t)width_ * height_ * 3;
+    DespeckledImage out{std::vector<float>(floats, 0.0f), std::vector<float>(floats, 0.0f), std::vector<float>(floats, 0.0f), {0u, 0u}};
+    check_status(pyr_session_despeckled(handle_, &setup.p, &params, guides && denoise ? &fp : nullptr, denoise ? &*denoise : nullptr, out.image.data(), out.error.data(),
+                                        out.removed.data(), out.counts));
+    return out;
+}
+std::string despeckle_flag_problem(const std::optional<std::string>& despeckle, const std::optional<long>& despeckle_radius, const std::optional<uint32_t>& pixel_samples,
+                                   const std::optional<long>& pass_samples) {
+    if (!despeckle) return despeckle_radius ? "--despeckle-radius needs --despeckle" : "";
+    char* end = nullptr;
+    const double k = std::strtod(despeckle->c_str(), &end);
+    if (despeckle->empty() || *end != 0 || !(std::isfinite(k) && k > 0.0)) return "--despeckle must be a finite number above 0";
+    if (despeckle_radius && (*despeckle_radius < 1 || *despeckle_radius > (long)PYR_DESPECKLE_MOST_RADIUS)) return "--despeckle-radius must be 1 to " + std::to_string(PYR_DESPECKLE_MOST_RADIUS);
+    if (pixel_samples && *pixel_samples % 2u) return "--despeckle needs an even number of samples per pixel: the two half films must be equal";
+    if (pixel_samples && pass_samples && *pass_samples > 0 && *pixel_samples % (2u * (uint64_t)*pass_samples))
+        return "--despeckle needs an even number of equal passes: the samples per pixel must be a multiple of twice --pass-samples";
+    return "";
+}
+std::optional<PyrDespeckleParams> despeckle_from_flags(const std::optional<std::string>& despeckle, const std::optional<long>& despeckle_radius) {
+    if (!despeckle) return std::nullopt;
+    return despeckle_params(despeckle_radius ? (uint32_t)*despeckle_radius : PYR_DESPECKLE_RADIUS, (float)std::strtod(despeckle->c_str(), nullptr));
+}
+
 // ---- first-hit feature images --------------------------------------------------------------------------------------------------
 Features Renderer::features(uint32_t width, uint32_t height, const Camera& camera, World& world, uint32_t grid, uint32_t albedo_bins, int device) const {
     Features out{Film(width, height, albedo_bins, spectrum_span[0], spectrum_span[1]), std::vector<PyrFeaturePixel>((size_t)width * height)};

@@ -5,7 +5,7 @@
 //   pyrite_host_tool dump-project   <project.lua> <texel dir | -> <out.bin>    the same for a project file (lua_project.cpp)
 //   pyrite_host_tool render-project <project.lua> <texel dir | -> <seed> <out.png> [film.bin]   what `pyrite project.lua` does (main.rs:46-330)
 //                                   [--size WxH] [--spp N] [--features PREFIX] [--features-grid N] [--hdr PATH] [--exposure EV|auto] [--tone clip|reinhard]
-//                                   [--upsample N] [--upsample-radius R] [--glare [STRENGTH]] [--glare-levels N] [--glare-threshold T]
+//                                   [--despeckle [K]] [--despeckle-radius R] [--upsample N] [--upsample-radius R] [--glare [STRENGTH]] [--glare-levels N] [--glare-threshold T]
 //                                   [--build host|device] and the progressive flags of python -m pyrite_amd
 //   pyrite_host_tool encode-features <records.bin> <normal.rgb> <depth.rgb>    PyrFeaturePixel[n] -> the 8-bit normal and depth images, raw RGB (no GPU)
 //   pyrite_host_tool intersect <scene> <data_dir> <rays.f32> <hits.bin>       World::intersect for a ray batch ([n][6] f32 -> PyrHit[n])
@@ -242,7 +242,7 @@ int main(int argc, char** argv) {
             write_dump(argv[4], flat, loaded.project);
             return 0;
         }
-        if (argc >= 6 && std::string(argv[1]) == "render-project") { // render-project <project.lua> <texel dir | -> <seed> <out.png> [film.bin] [--pass-samples N] [--preview PATH] [--preview-every SECONDS] [--noise] [--denoise] [--denoise-radius N] [--upsample N] [--upsample-radius R] [--glare [STRENGTH]] [--glare-levels N] [--glare-threshold T] [--build host|device]
+        if (argc >= 6 && std::string(argv[1]) == "render-project") { // render-project <project.lua> <texel dir | -> <seed> <out.png> [film.bin] [--pass-samples N] [--preview PATH] [--preview-every SECONDS] [--noise] [--despeckle [K]] [--despeckle-radius R] [--denoise] [--denoise-radius N] [--upsample N] [--upsample-radius R] [--glare [STRENGTH]] [--glare-levels N] [--glare-threshold T] [--build host|device]
             // the flags of python -m pyrite_amd: a progressive session with previews (main.rs:261-299) instead of one blocking call
             std::optional<long> pass_samples;
             std::string preview_path, film_path;
@@ -253,6 +253,8 @@ int main(int argc, char** argv) {
             std::optional<std::string> hdr, exposure, tone_name;
             bool denoise_flag = false;
             std::optional<long> denoise_radius;
+            std::optional<std::string> despeckle_k; // --despeckle [K]: the next argument unless it is a flag, as --glare reads its strength
+            std::optional<long> despeckle_radius;
             std::optional<long> upsample_scale, upsample_radius; // --upsample N: the render at 1/N of the image size, the final image upsampled to it
             std::optional<std::string> glare_strength; // --glare [STRENGTH]: the next argument unless it is a flag, as argparse's nargs="?" reads it (a film path goes before it)
             std::optional<long> glare_levels;
@@ -286,6 +288,10 @@ int main(int argc, char** argv) {
                     denoise_flag = true;
                 else if (a == "--denoise-radius")
                     denoise_radius = std::strtol(value(), nullptr, 10);
+                else if (a == "--despeckle")
+                    despeckle_k = i + 1 < argc && std::string(argv[i + 1]).rfind("--", 0) != 0 ? argv[++i] : "6.0";
+                else if (a == "--despeckle-radius")
+                    despeckle_radius = std::strtol(value(), nullptr, 10);
                 else if (a == "--upsample")
                     upsample_scale = std::strtol(value(), nullptr, 10);
                 else if (a == "--upsample-radius")
@@ -310,6 +316,7 @@ int main(int argc, char** argv) {
             std::string problem = progressive_flag_problem(pass_samples, !preview_path.empty(), preview_every, noise);
             if (problem.empty()) problem = features_flag_problem(!features_prefix.empty(), features_grid);
             if (problem.empty()) problem = tone_flag_problem(hdr, exposure, tone_name);
+            if (problem.empty()) problem = despeckle_flag_problem(despeckle_k, despeckle_radius);
             if (problem.empty()) problem = denoise_flag_problem(denoise_flag, denoise_radius);
             if (problem.empty()) problem = upsample_flag_problem(upsample_scale, upsample_radius);
             if (problem.empty()) problem = glare_flag_problem(glare_strength, glare_levels, glare_threshold);
@@ -320,6 +327,7 @@ int main(int argc, char** argv) {
             }
             const std::optional<PyrToneParams> tone = tone_from_flags(exposure, tone_name);
             const std::optional<PyrGlareParams> glare_p = glare_from_flags(glare_strength, glare_levels, glare_threshold);
+            const std::optional<PyrDespeckleParams> despeckle_p = despeckle_from_flags(despeckle_k, despeckle_radius);
             const std::optional<PyrUpsampleParams> upsample_p = upsample_from_flags(upsample_scale, upsample_radius);
             LoadedProject loaded = load_project(argv[2], std::string(argv[3]) == "-" ? TextureLoader() : texel_files(argv[3]));
             if (!size.empty()) { // WIDTHxHEIGHT, as python -m pyrite_amd --size
@@ -328,7 +336,8 @@ int main(int argc, char** argv) {
                 loaded.project.image.height = (uint32_t)std::strtoul(rest && *rest ? rest + 1 : "0", nullptr, 10);
             }
             if (spp && *spp > 0) loaded.project.renderer.pixel_samples = (uint32_t)*spp;
-            problem = denoise_flag_problem(denoise_flag, denoise_radius, loaded.project.renderer.pixel_samples, pass_samples);
+            problem = despeckle_flag_problem(despeckle_k, despeckle_radius, loaded.project.renderer.pixel_samples, pass_samples);
+            if (problem.empty()) problem = denoise_flag_problem(denoise_flag, denoise_radius, loaded.project.renderer.pixel_samples, pass_samples);
             const uint32_t full_width = loaded.project.image.width, full_height = loaded.project.image.height;
             if (problem.empty()) problem = upsample_flag_problem(upsample_scale, upsample_radius, full_width, full_height);
             if (!problem.empty()) {
@@ -352,9 +361,9 @@ int main(int argc, char** argv) {
                              b.bounds_ms, b.tree_ms, b.finish_ms, b.collapse_ms, b.pack_upload_ms, b.total_ms);
             }
             std::vector<float> linear;
-            if (pass_samples || !preview_path.empty() || noise || denoise_flag) {
-                const uint32_t per_pass = pass_samples ? (uint32_t)*pass_samples : denoise_flag ? r.pixel_samples / 2u : kDefaultPassSamples;
-                Session session(r, film.width, film.height, cam, *world, noise || denoise_flag);
+            if (pass_samples || !preview_path.empty() || noise || denoise_flag || despeckle_p) {
+                const uint32_t per_pass = pass_samples ? (uint32_t)*pass_samples : denoise_flag || despeckle_p ? r.pixel_samples / 2u : kDefaultPassSamples;
+                Session session(r, film.width, film.height, cam, *world, noise || denoise_flag || despeckle_p);
                 auto last_image = std::chrono::steady_clock::now(); // main.rs:241
                 while (session.samples_done() < r.pixel_samples) {
                     session.render(per_pass);
@@ -375,14 +384,19 @@ int main(int argc, char** argv) {
                         last_image = std::chrono::steady_clock::now();
                     }
                 }
-                if (denoise_flag)
+                if (despeckle_p) { // the halves cleaned, then the denoiser or their mean
+                    const std::optional<PyrDenoiseParams> denoise_p = denoise_flag ? std::optional<PyrDenoiseParams>(denoise_params(denoise_radius ? (uint32_t)*denoise_radius : PYR_DENOISE_RADIUS)) : std::nullopt;
+                    DespeckledImage cleaned = session.despeckled(*despeckle_p, denoise_p, true, 2.0f, project.image.filter, project.image.white);
+                    std::printf("despeckle: %u pixels clamped in half A, %u in half B\n", cleaned.counts[0], cleaned.counts[1]);
+                    linear = std::move(cleaned.image);
+                } else if (denoise_flag)
                     linear = session.denoised(denoise_params(denoise_radius ? (uint32_t)*denoise_radius : PYR_DENOISE_RADIUS), true, 2.0f, project.image.filter, project.image.white).image;
                 film = session.film();
             } else {
                 r.render(film, cam, *world);
             }
             std::printf("Saving final result...\n"); // main.rs:313
-            if (!denoise_flag && (hdr || tone || glare_p || upsample_p)) linear = develop_linear(film, PYR_LINEAR_SRGB, project.image.filter, project.image.white);
+            if (!denoise_flag && !despeckle_p && (hdr || tone || glare_p || upsample_p)) linear = develop_linear(film, PYR_LINEAR_SRGB, project.image.filter, project.image.white);
             if (upsample_p) { // after the denoiser, before the glare
                 const Features low_guides = r.features(film.width, film.height, cam, *world), guides = r.features(full_width, full_height, cam, *world);
                 const std::vector<float> low_albedo = develop_linear(low_guides.albedo, PYR_LINEAR_SRGB, project.image.filter, project.image.white);
@@ -391,7 +405,7 @@ int main(int argc, char** argv) {
             }
             if (glare_p) linear = glare(linear, full_width, full_height, *glare_p); // before the statistics of an automatic exposure, which tonemap takes
             save_png(argv[5],
-                     tone || denoise_flag || glare_p || upsample_p ? tonemap(linear, full_width, full_height, tone ? *tone : tone_params(PYR_TONE_CLIP, 1.0f))
+                     tone || denoise_flag || despeckle_p || glare_p || upsample_p ? tonemap(linear, full_width, full_height, tone ? *tone : tone_params(PYR_TONE_CLIP, 1.0f))
                                                                     : film.develop(project.image.filter, project.image.white),
                      full_width, full_height);
             if (hdr) {

@@ -20,6 +20,7 @@ bool tone_needs_stats(const PyrToneParams* t);
 int check_denoise_params(const PyrDenoiseParams* p);
 int check_motion_blur_params(const PyrMotionBlurParams* p, const char* what); // `what` names the argument: params, blur_params
 int check_glare_params(const PyrGlareParams* p, const char* what);            // likewise: params, glare_params
+int check_despeckle_params(const PyrDespeckleParams* p, const char* what);    // likewise: params, despeckle_params
 int check_upsample_params(const PyrUpsampleParams* p, const char* what, bool with_albedo); // likewise: params, upsample_params; the floor and the gain only with the albedo pair
 int check_upsample_scale(uint32_t scale);
 int check_upsample_size(uint32_t low_width, uint32_t low_height, uint32_t scale); // of the upsampled image
@@ -48,5 +49,10 @@ int enqueue_glare(const float* image, uint32_t width, uint32_t height, const Pyr
 // launch on `stream`. Either pair is null or given whole.
 int enqueue_upsample(const float* low, const float* low_albedo, const PyrFeaturePixel* low_pixels, uint32_t low_width, uint32_t low_height, uint32_t scale,
                      const float* albedo, const PyrFeaturePixel* pixels, const PyrUpsampleParams* p, float* out, hipStream_t stream);
+
+// The firefly clamp of `a` and, when given, `b` into `a_out` and `b_out` (kernels/despeckle.hip): every buffer on the current
+// device, one launch on `stream`, no working memory. `removed_out` and `counts_out` (two words, zeroed here) are optional.
+int enqueue_despeckle(const float* a, const float* b, uint32_t width, uint32_t height, const PyrDespeckleParams* p, float* a_out, float* b_out, float* removed_out,
+                      uint32_t* counts_out, hipStream_t stream);
 
 } // namespace pyr

@@ -1,7 +1,7 @@
 // image_ops.cpp -- the entry points of include/pyrite_gpu.h that take a device number and never see a scene: a film developed to
 // an 8-bit or a linear image, an image's luminance statistics, its tone mapping, the denoising of two half images, the
 // accumulation of linear images over frames along their motion records (plain, and as the temporal resolve), the motion blur of
-// one along them, the glare of one, the guided upsampling of one. Every operation is stated in three parts, each once ("adding an image entry"):
+// one along them, the glare of one, the guided upsampling of one, the firefly clamp of two halves. Every operation is stated in three parts, each once ("adding an image entry"):
 //   its checks, composed from the pieces below in the order that entry refuses in (tests/golden/image_refusals.json pins it);
 //   one enqueue_... function: device pointers, the public parameter block, a stream -- the one place its launch record is built;
 //   two entries: the _device form is checks, use_device, enqueue; the host form is checks, use_device and Staging::finish, which
@@ -196,6 +196,18 @@ int check_upsample_params(const PyrUpsampleParams* p, const char* what, bool wit
     if (p->reserved[0] != 0 || p->reserved[1] != 0) return fail(PYR_ERR_INVALID_ARGUMENT, name + "reserved must be 0");
     return PYR_OK;
 }
+// What the three despeckle entries refuse of their parameters before a device is looked for (`what`: params or despeckle_params).
+int check_despeckle_params(const PyrDespeckleParams* p, const char* what) {
+    const std::string name = std::string(what) + "->";
+    if (!p) return fail(PYR_ERR_INVALID_ARGUMENT, std::string("null argument: ") + what);
+    if (p->radius < 1 || p->radius > PYR_DESPECKLE_MOST_RADIUS) return fail(PYR_ERR_INVALID_ARGUMENT, name + "radius must be 1..2");
+    if (!(p->k > 0.0f) || !std::isfinite(p->k)) return fail(PYR_ERR_INVALID_ARGUMENT, name + "k must be finite and positive");
+    if (!(p->relative >= 0.0f) || !std::isfinite(p->relative)) return fail(PYR_ERR_INVALID_ARGUMENT, name + "relative must be finite and not negative");
+    if (!(p->floor > 0.0f) || !std::isfinite(p->floor)) return fail(PYR_ERR_INVALID_ARGUMENT, name + "floor must be finite and positive");
+    if (p->flags != 0) return fail(PYR_ERR_INVALID_ARGUMENT, name + "flags has an unknown bit: none is defined");
+    if (p->reserved[0] != 0 || p->reserved[1] != 0 || p->reserved[2] != 0) return fail(PYR_ERR_INVALID_ARGUMENT, name + "reserved must be 0");
+    return PYR_OK;
+}
 int check_upsample_scale(uint32_t scale) {
     if (scale < 2 || scale > PYR_UPSAMPLE_MOST_SCALE) return fail(PYR_ERR_INVALID_ARGUMENT, "scale must be 2..8");
     return PYR_OK;
@@ -264,6 +276,14 @@ int enqueue_upsample(const float* low, const float* low_albedo, const PyrFeature
     L.albedo_floor = p->albedo_floor, L.max_gain = p->max_gain;
     L.out = out;
     return launch_upsample(L, stream);
+}
+
+// The firefly clamp of `a` and, when given, `b` (kernels/despeckle.hip): every buffer on the current device, the counts zeroed and
+// one launch on `stream`, no working memory.
+int enqueue_despeckle(const float* a, const float* b, uint32_t width, uint32_t height, const PyrDespeckleParams* p, float* a_out, float* b_out, float* removed_out,
+                      uint32_t* counts_out, hipStream_t stream) {
+    const DespeckleLaunch L{a, b, width, height, p->radius, p->k, p->relative, p->floor, a_out, b_out, removed_out, counts_out, 0u};
+    return launch_despeckle(L, stream);
 }
 
 } // namespace pyr
@@ -407,6 +427,18 @@ int check_upsample_args(const void* low, const void* low_albedo, const void* low
     if (low_height == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "low_height: an empty image");
     if (int bad = check_upsample_scale(scale)) return bad;
     return check_upsample_params(p, "params", albedo != nullptr);
+}
+
+// Nulls, half a pair, the extent and its size, the parameters, then the overlaps: `names` are those of a, b, a_out, b_out,
+// removed_out and counts_out as the entry calls them.
+int check_despeckle_args(const void* a, const void* b, uint32_t width, uint32_t height, const PyrDespeckleParams* p, const void* a_out, const void* b_out,
+                         const void* removed_out, const void* counts_out, const char* const (&names)[6]) {
+    if (int bad = check_given({{a, 0, names[0]}, {p, 0, "params"}, {a_out, 0, names[2]}})) return bad;
+    if ((b != nullptr) != (b_out != nullptr)) return fail(PYR_ERR_INVALID_ARGUMENT, std::string(names[1]) + " and " + names[3] + " are both null or both given");
+    if (int bad = check_extent(width, height)) return bad;
+    if (int bad = check_despeckle_params(p, "params")) return bad;
+    const uint64_t bytes = (uint64_t)width * height * 12;
+    return check_overlap({{a_out, bytes, names[2]}, {b_out, bytes, names[3]}, {removed_out, bytes, names[4]}, {counts_out, 8, names[5]}}, {{a, bytes, names[0]}, {b, bytes, names[1]}});
 }
 
 // A development with its small per-wavelength tables copied for the call: allocated in stream order, filled, handed to `launch`
@@ -684,6 +716,24 @@ int pyr_image_upsample(const float* low, const float* low_albedo, const PyrFeatu
     return S.finish(enqueue_upsample, S.in(low, low_count * pixel_bytes), S.in(low_albedo, low_count * pixel_bytes), S.in(low_pixels, low_count * sizeof(PyrFeaturePixel)),
                     low_width, low_height, scale, S.in(albedo, count * pixel_bytes), S.in(pixels, count * sizeof(PyrFeaturePixel)), params, S.out(out, count * pixel_bytes),
                     nullptr);
+}
+
+int pyr_image_despeckle_device(const float* a_device, const float* b_device, uint32_t width, uint32_t height, const PyrDespeckleParams* params, float* a_out_device,
+                               float* b_out_device, float* removed_out_device, uint32_t* counts_out_device, int device, void* hip_stream) {
+    static const char* const names[6] = {"a_device", "b_device", "a_out_device", "b_out_device", "removed_out_device", "counts_out_device"};
+    const int rc = check_despeckle_args(a_device, b_device, width, height, params, a_out_device, b_out_device, removed_out_device, counts_out_device, names);
+    if (int bad = use_device(rc, device)) return bad;
+    return enqueue_despeckle(a_device, b_device, width, height, params, a_out_device, b_out_device, removed_out_device, counts_out_device, (hipStream_t)hip_stream);
+}
+
+int pyr_image_despeckle(const float* a, const float* b, uint32_t width, uint32_t height, const PyrDespeckleParams* params, float* a_out, float* b_out,
+                        float* removed_out, uint32_t* counts_out, int device) {
+    static const char* const names[6] = {"a", "b", "a_out", "b_out", "removed_out", "counts_out"};
+    if (int bad = use_device(check_despeckle_args(a, b, width, height, params, a_out, b_out, removed_out, counts_out, names), device)) return bad;
+    const size_t image_bytes = (size_t)width * height * 3 * sizeof(float);
+    Staging S;
+    return S.finish(enqueue_despeckle, S.in(a, image_bytes), S.in(b, image_bytes), width, height, params, S.out(a_out, image_bytes), S.out(b_out, image_bytes),
+                    S.out(removed_out, image_bytes), S.out(counts_out, 2 * sizeof(uint32_t)), nullptr);
 }
 
 } // extern "C"

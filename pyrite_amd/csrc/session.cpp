@@ -144,19 +144,29 @@ struct DenoisedImages {
     DeviceBuffer images, albedo_film, records;
     float* at(const PyrSession* s, size_t i) const { return (float*)images.ptr + i * (size_t)s->film.width * s->film.height * 3; }
 };
-int session_denoised(PyrSession* s, const PyrDevelopParams* develop_params, const PyrFeatureParams* feature_params, const PyrDenoiseParams* denoise_params, bool with_error,
-                     DenoisedImages& D) {
+// Half film A alone and half film B alone developed to linear sRGB into `a_out` and `b_out`, on the session's stream.
+int session_develop_halves(PyrSession* s, const PyrDevelopParams* develop_params, float* a_out, float* b_out) {
     int rc;
     LinearLaunch L{};
     if ((rc = session_develop_launch(s, develop_params, L.develop)) != PYR_OK) return rc;
     L.space = PYR_LINEAR_SRGB;
-    L.develop.grains = (const PyrGrain*)s->film_a.ptr, L.develop.grains_b = nullptr, L.out = D.at(s, 0);
+    L.develop.grains = (const PyrGrain*)s->film_a.ptr, L.develop.grains_b = nullptr, L.out = a_out;
     if ((rc = launch_develop_linear(L, s->stream)) != PYR_OK) return rc;
-    L.develop.grains = (const PyrGrain*)s->film_b.ptr, L.out = D.at(s, 1);
-    if ((rc = launch_develop_linear(L, s->stream)) != PYR_OK) return rc;
+    L.develop.grains = (const PyrGrain*)s->film_b.ptr, L.out = b_out;
+    return launch_develop_linear(L, s->stream);
+}
+// The cross filter of the half images at 0 and 1 of `D`, the feature pass before it when it steers.
+int session_denoise_halves(PyrSession* s, const PyrDevelopParams* develop_params, const PyrFeatureParams* feature_params, const PyrDenoiseParams* denoise_params,
+                           bool with_error, DenoisedImages& D) {
+    int rc;
     if (feature_params && (rc = session_feature_images(s, &s->film, develop_params, feature_params, D.albedo_film, D.records, D.at(s, 2))) != PYR_OK) return rc;
     return enqueue_denoise(D.at(s, 0), D.at(s, 1), feature_params ? D.at(s, 2) : nullptr, feature_params ? (const PyrFeaturePixel*)D.records.ptr : nullptr, s->film.width,
                            s->film.height, denoise_params, D.at(s, 3), D.at(s, 6), with_error ? D.at(s, 7) : nullptr, s->stream);
+}
+int session_denoised(PyrSession* s, const PyrDevelopParams* develop_params, const PyrFeatureParams* feature_params, const PyrDenoiseParams* denoise_params, bool with_error,
+                     DenoisedImages& D) {
+    if (int rc = session_develop_halves(s, develop_params, D.at(s, 0), D.at(s, 1))) return rc;
+    return session_denoise_halves(s, develop_params, feature_params, denoise_params, with_error, D);
 }
 
 } // namespace
@@ -523,6 +533,44 @@ int pyr_session_upsampled(PyrSession* session, uint32_t scale, const PyrDevelopP
                               feature_params ? albedo : nullptr, feature_params ? (const PyrFeaturePixel*)high_records.ptr : nullptr, upsample_params, out_dev, s->stream);
         if (rc != PYR_OK) return rc;
         if (hipMemcpyAsync(out, out_dev, image_bytes, hipMemcpyDeviceToHost, s->stream) != hipSuccess) return fail(PYR_ERR_DEVICE, "hipMemcpyAsync of the upsampled image failed");
+        return PYR_OK;
+    });
+}
+
+int pyr_session_despeckled(PyrSession* session, const PyrDevelopParams* develop_params, const PyrDespeckleParams* despeckle_params,
+                           const PyrFeatureParams* feature_params, const PyrDenoiseParams* denoise_params, float* out, float* error_out, float* removed_out,
+                           uint32_t* counts_out) {
+    if (!session) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: session");
+    if (!develop_params) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: develop_params");
+    if (!out) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: out");
+    PyrSession* s = session;
+    int rc = check_despeckle_params(despeckle_params, "despeckle_params"); // what needs no session comes first: before a device is looked for
+    if (rc != PYR_OK || (rc = check_linear_args(&s->film, s, develop_params, PYR_LINEAR_SRGB, out)) != PYR_OK) return rc;
+    if (denoise_params && (rc = check_denoise_params(denoise_params)) != PYR_OK) return rc;
+    if (denoise_params && feature_params && (rc = check_feature_args(s, "session", nullptr, false, &s->film, feature_params, s, s)) != PYR_OK) return rc;
+    if ((rc = session_ready(s)) != PYR_OK) return rc;
+    if (!s->halves) return fail(PYR_ERR_INVALID_ARGUMENT, "despeckling needs the two half films: create the session with PYR_SESSION_HALVES");
+    if (s->passes < 2) return fail(PYR_ERR_INVALID_ARGUMENT, "despeckling needs at least two passes: one half film is still empty");
+    const uint32_t width = s->film.width, height = s->film.height;
+    const size_t pixels = (size_t)width * height, image_bytes = pixels * 3 * sizeof(float);
+    DenoisedImages D; // 0, 1: the cleaned halves; 2..5: the denoiser's; 6: out; 7: the error image
+    DeviceBuffer raw, counts; // raw: the halves as developed, then what the clamp removed
+    if ((rc = D.images.alloc(8 * image_bytes)) != PYR_OK || (rc = raw.alloc(3 * image_bytes)) != PYR_OK || (rc = counts.alloc(2 * sizeof(uint32_t))) != PYR_OK) return rc;
+    float *raw_a = (float*)raw.ptr, *raw_b = raw_a + pixels * 3, *removed = raw_b + pixels * 3;
+    return enqueue_then_sync(s, [&]() -> int {
+        int rc = session_develop_halves(s, develop_params, raw_a, raw_b);
+        if (rc != PYR_OK) return rc;
+        rc = enqueue_despeckle(raw_a, raw_b, width, height, despeckle_params, D.at(s, 0), D.at(s, 1), removed_out ? removed : nullptr, (uint32_t*)counts.ptr, s->stream);
+        if (rc != PYR_OK) return rc;
+        if (denoise_params)
+            rc = session_denoise_halves(s, develop_params, feature_params, denoise_params, error_out != nullptr, D);
+        else
+            rc = launch_denoise_combine(D.at(s, 0), D.at(s, 1), pixels, D.at(s, 6), error_out ? D.at(s, 7) : nullptr, s->stream); // the mean and half the difference
+        if (rc != PYR_OK) return rc;
+        HIP_TRY(hipMemcpyAsync(out, D.at(s, 6), image_bytes, hipMemcpyDeviceToHost, s->stream));
+        if (error_out) HIP_TRY(hipMemcpyAsync(error_out, D.at(s, 7), image_bytes, hipMemcpyDeviceToHost, s->stream));
+        if (removed_out) HIP_TRY(hipMemcpyAsync(removed_out, removed, image_bytes, hipMemcpyDeviceToHost, s->stream));
+        if (counts_out) HIP_TRY(hipMemcpyAsync(counts_out, counts.ptr, 2 * sizeof(uint32_t), hipMemcpyDeviceToHost, s->stream));
         return PYR_OK;
     });
 }

@@ -431,6 +431,63 @@ def upsample_from_flags(upsample, upsample_radius):
     return {"radius": upsample_radius} if upsample_radius is not None else {}
 
 
+def despeckle_params(radius=abi.PYR_DESPECKLE_RADIUS, k=abi.PYR_DESPECKLE_K, relative=abi.PYR_DESPECKLE_RELATIVE, floor=abi.PYR_DESPECKLE_FLOOR, flags=0):
+    """abi.PyrDespeckleParams: a pixel is a firefly when it lies more than `k` spreads above the median of its (2*radius+1)^2
+    window; the spread is the scaled median deviation, at least `relative` times the median and at least `floor`."""
+    return abi.PyrDespeckleParams(int(radius), float(k), float(relative), float(floor), int(flags))
+
+
+def despeckle(a, b=None, device=0, **params):
+    """(a_out, b_out, removed, counts) -- or (a_out, removed, counts) without `b` -- the half images `a` and `b` (linear light,
+    independent samples of one picture) with their fireflies clamped on the GPU (pyr_image_despeckle; include/pyrite_gpu.h has the
+    arithmetic): a pixel far above the median of its neighbourhood in one half and not in the other lands on the limit, its hue
+    kept; everything else keeps its bits. `removed`: float32 [height, width, 3], what the mean of the halves lost; `counts`: the
+    pixels clamped in a and in b. Without `b` one image is filtered and bright edges lose pixels too. `params`: despeckle_params."""
+    a = _linear_image(a)
+    h, w, _ = a.shape
+    if b is not None:
+        b = _linear_image(b)
+        assert b.shape == a.shape
+    p = despeckle_params(**params)
+    a_out, removed = np.zeros(a.shape, dtype=np.float32), np.zeros(a.shape, dtype=np.float32)
+    b_out = np.zeros(a.shape, dtype=np.float32) if b is not None else None
+    counts = np.zeros(2, dtype=np.uint32)
+    check(lib().pyr_image_despeckle(a.ctypes.data, _ptr(b), w, h, C.byref(p), a_out.ctypes.data, _ptr(b_out), removed.ctypes.data, counts.ctypes.data, int(device)))
+    counts = (int(counts[0]), int(counts[1]))
+    return (a_out, b_out, removed, counts) if b is not None else (a_out, removed, counts)
+
+
+def despeckle_flag_problem(despeckle, despeckle_radius, pixel_samples=None, pass_samples=None):
+    """What is wrong with --despeckle [K] / --despeckle-radius R, in the words pyrite_host_tool uses too, or None. `despeckle`: K as
+    it was given (a string or a number), or None without --despeckle; `pixel_samples`: the render's budget once the project is
+    loaded; `pass_samples`: --pass-samples, when given."""
+    if despeckle is None:
+        return "--despeckle-radius needs --despeckle" if despeckle_radius is not None else None
+    try:
+        k = float(despeckle)
+    except ValueError:
+        k = float("nan")
+    if not (np.isfinite(k) and k > 0.0):
+        return "--despeckle must be a finite number above 0"
+    if despeckle_radius is not None and not 1 <= despeckle_radius <= abi.PYR_DESPECKLE_MOST_RADIUS:
+        return "--despeckle-radius must be 1 to %d" % abi.PYR_DESPECKLE_MOST_RADIUS
+    if pixel_samples is not None and pixel_samples % 2:
+        return "--despeckle needs an even number of samples per pixel: the two half films must be equal"
+    if pixel_samples is not None and pass_samples and pixel_samples % (2 * pass_samples):
+        return "--despeckle needs an even number of equal passes: the samples per pixel must be a multiple of twice --pass-samples"
+    return None
+
+
+def despeckle_from_flags(despeckle, despeckle_radius):
+    """The despeckle_params keywords of --despeckle [K] --despeckle-radius R, or None without --despeckle."""
+    if despeckle is None:
+        return None
+    params = {"k": float(despeckle)}
+    if despeckle_radius is not None:
+        params["radius"] = despeckle_radius
+    return params
+
+
 def denoise_flag_problem(denoise, denoise_radius, pixel_samples=None, pass_samples=None):
     """What is wrong with --denoise / --denoise-radius, in the words pyrite_host_tool uses too, or None. `pixel_samples`: the
     render's budget once the project is loaded; `pass_samples`: --pass-samples, when given."""

@@ -620,6 +620,26 @@ class Session:
         del keep
         return out
 
+    def despeckled(self, step=2.0, filter=None, white=None, denoise=None, guides=True, grid=1, albedo_bins=16, **params):
+        """(image, error, removed, counts): the two half films developed to linear sRGB, their fireflies clamped, and then -- with
+        `denoise`, a dict of develop.denoise_params keywords, {} for the defaults -- cross filtered as denoised() filters the raw
+        halves (`guides`, `grid`, `albedo_bins`: its feature pass), or without it their mean and half their difference, all on the
+        session's device (pyr_session_despeckled; develop.despeckle of the developed half_films(), then develop.denoise or the
+        mean, gives the same floats). `removed`, `counts`: as develop.despeckle. `params`: develop.despeckle_params. Needs `halves`
+        and two passes. The films are not touched."""
+        from .develop import denoise_params, despeckle_params, develop_params
+
+        p, keep = develop_params(self._film, step, filter, white)
+        sp = despeckle_params(**params)
+        dp = denoise_params(**denoise) if denoise is not None else None
+        fp = abi.PyrFeatureParams(int(grid), int(albedo_bins)) if guides and dp is not None else None
+        out, error, removed = (np.zeros((self.height, self.width, 3), dtype=np.float32) for _ in range(3))
+        counts = np.zeros(2, dtype=np.uint32)
+        check(lib().pyr_session_despeckled(self.handle, C.byref(p), C.byref(sp), C.byref(fp) if fp is not None else None, C.byref(dp) if dp is not None else None,
+                                           out.ctypes.data, error.ctypes.data, removed.ctypes.data, counts.ctypes.data))
+        del keep
+        return out, error, removed, (int(counts[0]), int(counts[1]))
+
     def close(self):
         if self.handle:
             lib().pyr_session_destroy(self.handle)
