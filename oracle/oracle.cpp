@@ -2294,10 +2294,11 @@ int oracle_surface_data(OracleScene* scene, const float ray6[6], float wavelengt
 // [3P] palette 0.7.2: Xyz(D65) -> linear sRGB with the sRGB/D65 matrix, clamp to [0,1] (FromColor), sRGB transfer function,
 // u8 = round(255 * v). The crate derives its matrix from the primaries at run time and converts to u8 through a lookup
 // table; both may differ from the textbook constants used here in the last bit (unverifiable offline).
-int oracle_film_develop(const PyrFilmDesc* film, const PyrGrain* grains, const PyrDevelopParams* p, uint8_t* rgb_out) {
-    if (!film || !grains || !p || !rgb_out || !p->xyz_table) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+// One walk for both entries: `xyz_out` and `rgb_out` (either may be null) take the pixel's XYZ and linear sRGB before the clamp.
+// `grains_b`, when given, is a second half film: accs added, weights added, grain by grain, before Grain::develop -- the sum
+// film of a session with halves (include/pyrite_gpu.h pyr_film_develop_linear).
+static void develop_pixel(const PyrFilmDesc* film, const PyrGrain* g, const PyrGrain* gb, const PyrDevelopParams* p, float* xyz_out, float* rgb_out) {
     const uint32_t bins = film->bins;
-    const size_t pixels = (size_t)film->width * film->height;
     const float min = film->wl_start, max = film->wl_start + film->wl_width;
     auto xyz_get = [&](int channel, float w) { // Spectrum::Array::get on the interleaved table
         const float* d = p->xyz_table;
@@ -2311,55 +2312,84 @@ int oracle_film_develop(const PyrFilmDesc* film, const PyrGrain* grains, const P
         float mix = fi - fmin_;
         return d[3 * i0 + channel] * (1.0f - mix) + d[3 * (i0 + 1) + channel] * mix;
     };
-    auto encode = [](float v) -> uint8_t { // sRGB transfer function, pow through f64
-        v = rmin(rmax(v, 0.0f), 1.0f);
-        float e = v <= 0.0031308f ? 12.92f * v : 1.055f * (float)std::pow((double)v, 1.0 / 2.4) - 0.055f;
-        e = rmin(rmax(e, 0.0f), 1.0f);
-        return (uint8_t)(e * 255.0f + 0.5f);
+    auto sample = [&](float w, uint32_t i) {
+        float intensity;
+        if (w < min || w > max) {
+            intensity = 0.0f;
+        } else {
+            float normalized = (w - min) / (max - min);
+            float float_index = normalized * (float)bins;
+            uint32_t index = (uint32_t)std::min<float>(std::floor(float_index), (float)(bins - 1));
+            float acc = g[index].acc, weight = g[index].weight;
+            if (gb) acc += gb[index].acc, weight += gb[index].weight;
+            intensity = weight > 0.0f ? acc / weight : 0.0f;
+        }
+        if (p->filter) intensity = intensity * p->filter[i];
+        if (p->white_div) intensity = (intensity / p->white_div[i]) * p->white_mul[i];
+        return intensity;
     };
+    float sum[3] = {0, 0, 0}, weight = 0.0f;
+    float wl_min = min;
+    uint32_t i = 0;
+    float spectrum_min = sample(wl_min, i);
+    float start[3] = {xyz_get(0, wl_min), xyz_get(1, wl_min), xyz_get(2, wl_min)};
+    while (wl_min < max) {
+        float wl_max = wl_min + p->step_size;
+        i += 1;
+        float spectrum_max = sample(wl_max, i < p->sample_count ? i : p->sample_count - 1);
+        float end[3] = {xyz_get(0, wl_max), xyz_get(1, wl_max), xyz_get(2, wl_max)};
+        float w = wl_max - wl_min;
+        for (int c = 0; c < 3; ++c) sum[c] += (start[c] * spectrum_min + end[c] * spectrum_max) * 0.5f * w;
+        weight += w;
+        wl_min = wl_max;
+        spectrum_min = spectrum_max;
+        for (int c = 0; c < 3; ++c) start[c] = end[c];
+    }
+    float xyz[3];
+    for (int c = 0; c < 3; ++c) xyz[c] = (weight == 0.0f ? sum[c] : sum[c] / weight) * p->xyz_scale;
+    if (xyz_out) xyz_out[0] = xyz[0], xyz_out[1] = xyz[1], xyz_out[2] = xyz[2];
+    if (rgb_out) {
+        rgb_out[0] = 3.2404542f * xyz[0] + -1.5371385f * xyz[1] + -0.4985314f * xyz[2];
+        rgb_out[1] = -0.9692660f * xyz[0] + 1.8760108f * xyz[1] + 0.0415560f * xyz[2];
+        rgb_out[2] = 0.0556434f * xyz[0] + -0.2040259f * xyz[1] + 1.0572252f * xyz[2];
+    }
+}
+
+static float encode255(float v) { // the clamp and the sRGB transfer function, pow through f64: 255 e, the number that is rounded to the byte
+    v = rmin(rmax(v, 0.0f), 1.0f);
+    float e = v <= 0.0031308f ? 12.92f * v : 1.055f * (float)std::pow((double)v, 1.0 / 2.4) - 0.055f;
+    e = rmin(rmax(e, 0.0f), 1.0f);
+    return e * 255.0f;
+}
+
+int oracle_film_develop(const PyrFilmDesc* film, const PyrGrain* grains, const PyrDevelopParams* p, uint8_t* rgb_out) {
+    if (!film || !grains || !p || !rgb_out || !p->xyz_table) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+    const uint32_t bins = film->bins;
+    const size_t pixels = (size_t)film->width * film->height;
     std::memset(rgb_out, 0, pixels * 3);
     for (size_t px = 0; px < pixels; ++px) {
         if ((px + 1) * bins >= pixels * bins) break; // DevelopedPixels::next stops when `end < len` fails: the last pixel is skipped
-        const PyrGrain* g = grains + px * bins;
-        auto sample = [&](float w, uint32_t i) {
-            float intensity;
-            if (w < min || w > max) {
-                intensity = 0.0f;
-            } else {
-                float normalized = (w - min) / (max - min);
-                float float_index = normalized * (float)bins;
-                uint32_t index = (uint32_t)std::min<float>(std::floor(float_index), (float)(bins - 1));
-                intensity = g[index].weight > 0.0f ? g[index].acc / g[index].weight : 0.0f;
-            }
-            if (p->filter) intensity = intensity * p->filter[i];
-            if (p->white_div) intensity = (intensity / p->white_div[i]) * p->white_mul[i];
-            return intensity;
-        };
-        float sum[3] = {0, 0, 0}, weight = 0.0f;
-        float wl_min = min;
-        uint32_t i = 0;
-        float spectrum_min = sample(wl_min, i);
-        float start[3] = {xyz_get(0, wl_min), xyz_get(1, wl_min), xyz_get(2, wl_min)};
-        while (wl_min < max) {
-            float wl_max = wl_min + p->step_size;
-            i += 1;
-            float spectrum_max = sample(wl_max, i < p->sample_count ? i : p->sample_count - 1);
-            float end[3] = {xyz_get(0, wl_max), xyz_get(1, wl_max), xyz_get(2, wl_max)};
-            float w = wl_max - wl_min;
-            for (int c = 0; c < 3; ++c) sum[c] += (start[c] * spectrum_min + end[c] * spectrum_max) * 0.5f * w;
-            weight += w;
-            wl_min = wl_max;
-            spectrum_min = spectrum_max;
-            for (int c = 0; c < 3; ++c) start[c] = end[c];
-        }
-        float xyz[3];
-        for (int c = 0; c < 3; ++c) xyz[c] = (weight == 0.0f ? sum[c] : sum[c] / weight) * p->xyz_scale;
-        float r = 3.2404542f * xyz[0] + -1.5371385f * xyz[1] + -0.4985314f * xyz[2];
-        float gg = -0.9692660f * xyz[0] + 1.8760108f * xyz[1] + 0.0415560f * xyz[2];
-        float b = 0.0556434f * xyz[0] + -0.2040259f * xyz[1] + 1.0572252f * xyz[2];
-        rgb_out[3 * px + 0] = encode(r);
-        rgb_out[3 * px + 1] = encode(gg);
-        rgb_out[3 * px + 2] = encode(b);
+        float rgb[3];
+        develop_pixel(film, grains + px * bins, nullptr, p, nullptr, rgb);
+        for (int c = 0; c < 3; ++c) rgb_out[3 * px + c] = (uint8_t)(encode255(rgb[c]) + 0.5f);
+    }
+    return PYR_OK;
+}
+
+// The same development stopped before the clamp: float [height][width][3], CIE XYZ (PYR_LINEAR_XYZ) or linear sRGB
+// (PYR_LINEAR_SRGB), of `grains` or of `grains` + `grains_b`; or stopped before the rounding (ORACLE_ENCODED_255): 255 e of each
+// channel, which oracle_film_develop rounds to the byte. The last pixel stays 0, as above.
+int oracle_film_develop_linear(const PyrFilmDesc* film, const PyrGrain* grains, const PyrGrain* grains_b, const PyrDevelopParams* p, uint32_t space, float* out) {
+    if (!film || !grains || !p || !out || !p->xyz_table) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
+    if (space != PYR_LINEAR_XYZ && space != PYR_LINEAR_SRGB && space != ORACLE_ENCODED_255) return fail(PYR_ERR_INVALID_ARGUMENT, "unknown space");
+    const uint32_t bins = film->bins;
+    const size_t pixels = (size_t)film->width * film->height;
+    std::memset(out, 0, pixels * 3 * sizeof(float));
+    for (size_t px = 0; px + 1 < pixels; ++px) {
+        develop_pixel(film, grains + px * bins, grains_b ? grains_b + px * bins : nullptr, p, space == PYR_LINEAR_XYZ ? out + 3 * px : nullptr,
+                      space != PYR_LINEAR_XYZ ? out + 3 * px : nullptr);
+        if (space == ORACLE_ENCODED_255)
+            for (int c = 0; c < 3; ++c) out[3 * px + c] = encode255(out[3 * px + c]);
     }
     return PYR_OK;
 }

@@ -112,6 +112,12 @@ int oracle_surface_data(OracleScene* scene, const float ray6[6], float wavelengt
 
 /* main.rs:315-327 + :352-418 + film.rs:282-337: develop a whole film into 8-bit sRGB ("next" row f1). */
 int oracle_film_develop(const PyrFilmDesc* film, const PyrGrain* grains, const PyrDevelopParams* params, uint8_t* rgb_out);
+/* The same walk stopped before the clamp: float [height][width][3], PYR_LINEAR_XYZ or PYR_LINEAR_SRGB; `grains_b` (optional) is a
+   second half film, added grain by grain (accs and weights) before the quotient. ORACLE_ENCODED_255 stops before the rounding
+   instead: 255 e per channel, the float that oracle_film_develop rounds to the byte. */
+#define ORACLE_ENCODED_255 2u
+int oracle_film_develop_linear(const PyrFilmDesc* film, const PyrGrain* grains, const PyrGrain* grains_b, const PyrDevelopParams* params, uint32_t space,
+                               float* out);
 
 #ifdef __cplusplus
 }

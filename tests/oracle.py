@@ -88,6 +88,7 @@ def lib():
         L.oracle_run_program.argtypes = [C.c_void_p, C.c_uint32, C.c_float, F3, F3, C.c_float * 2, C.POINTER(C.c_int)]
         L.oracle_run_program.restype = C.c_float
         L.oracle_film_develop.argtypes = [C.POINTER(abi.PyrFilmDesc), C.c_void_p, C.POINTER(abi.PyrDevelopParams), C.c_void_p]
+        L.oracle_film_develop_linear.argtypes = [C.POINTER(abi.PyrFilmDesc), C.c_void_p, C.c_void_p, C.POINTER(abi.PyrDevelopParams), C.c_uint32, C.c_void_p]
         L.oracle_texture_get.argtypes = [C.c_uint32, C.c_uint32, C.c_uint32, C.c_void_p, C.c_float, C.c_float, C.c_void_p]
         L.oracle_quat_from_cols.argtypes = [F3, F3, F3, C.c_float * 4]
         L.oracle_quat_rotate.argtypes = [C.c_float * 4, F3, F3]
@@ -105,6 +106,23 @@ def film_develop(film, step_size=2.0, filter=None, white=None):
     grains = np.ascontiguousarray(film.grains)
     out = np.zeros((film.height, film.width, 3), dtype=np.uint8)
     _check(lib().oracle_film_develop(C.byref(desc), grains.ctypes.data, C.byref(p), out.ctypes.data))
+    del keep
+    return out
+
+
+def film_develop_linear(film, space="srgb", film_b=None, step_size=2.0, filter=None, white=None):
+    """The same walk stopped before the clamp -> float32 [h, w, 3], CIE XYZ ("xyz") or linear sRGB ("srgb"), of `film` or of `film` +
+    `film_b`; "encoded" stops before the rounding instead: 255 e, the float that film_develop rounds to the byte."""
+    from pyrite_amd.develop import SPACES, develop_params
+
+    p, keep = develop_params(film, step_size, filter, white)
+    desc = film.desc()
+    grains = np.ascontiguousarray(film.grains)
+    grains_b = np.ascontiguousarray(film_b.grains) if film_b is not None else None
+    assert grains_b is None or grains_b.shape == grains.shape
+    out = np.zeros((film.height, film.width, 3), dtype=np.float32)
+    _check(lib().oracle_film_develop_linear(C.byref(desc), grains.ctypes.data, grains_b.ctypes.data if grains_b is not None else None, C.byref(p),
+                                            2 if space == "encoded" else SPACES[space], out.ctypes.data))
     del keep
     return out
 
