@@ -828,6 +828,8 @@ int pack_and_upload(const PyrSceneDesc* d, PyrScene* s, uint32_t builder) {
     }
     // the eager replay's value rows (device_scene.h): eight, or what the scene's programs need; past sixteen the replay looks values up record by record
     v.tape_value_rows = tape_rows_needed(fast_programs, v.rgb_records != 0) <= kTapeMaxValueRows ? tape_rows_needed(fast_programs, v.rgb_records != 0) : kTapeValueRows;
+    // builds that replay two wavelengths per lane: packed pairs of rows where pairs pay, packed single rows where they would cost LDS
+    if (tape_pairs(needs_interpreter)) v.tape_value_rows = tape_pair_build_rows(fast_programs);
     v.shadow_margin = d->num_spheres != 0 ? 1.01f : 1.001f; // device_scene.h
     v.hero_only_records = 0;
     for (uint32_t i = 0; i < d->num_materials; ++i)

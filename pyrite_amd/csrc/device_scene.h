@@ -151,7 +151,7 @@ struct DevScene {
     // sphere routine loses every digit of l.l - tca^2 for a ray that passes at a thousand radii or more and then reports hits up to a
     // radius NEARER than the sphere's own box, which the reference, walking with closest = inf, still counts as blockers.
     float shadow_margin;
-    uint32_t tape_value_rows; // LDS value rows of the eager replay (above): 8, or as many as the scene's spectrum-reading programs need, up to 16
+    uint32_t tape_value_rows; // LDS value rows of the eager replay (above): 8, or as many as the scene's spectrum-reading programs need, up to 16; scenes without interpreter programs: tape_pair_build_rows (below)
 };
 
 // Value rows of the eager replay (kernels.hip replay_tapes): rows of BLOCK floats in LDS, one per spectrum-reading program -- its value at the
@@ -168,6 +168,43 @@ constexpr uint32_t tape_rows_needed(uint32_t n_spectral, bool rgb) {
                ? (rgb ? tape_rgb_row(n_spectral) + 3u : tape_row(n_spectral - 1u) + 1u)
                : kTapeValueRows;
 }
+
+// The stage scheduler's builds without interpreter programs replay a path's tape for TWO wavelengths per lane (kernels.hip replay_tapes:
+// an item is a path and the halves k and k + (S + 1) / 2 of its wavelengths), in packed f32. Each value row then has a twin for the
+// second half right behind it, one ds_read2st64_b32 apart: the rows come in pairs, slot 0 in pair 0, 1.0 in pair 1, slot s >= 1 in pair
+// s + 1, and a record names twice its pair (up to 30: five bits of the word; bits 12-13 are the interpreter builds' alone). The pairs
+// are packed -- DevScene::tape_value_rows is 2 (n + 1) rows for n spectrum-reading programs there, 10 on C3 -- because the render pays
+// for every KB of LDS with a level of its traversal stack (C3: 660 Msamples/s at 14 levels, 635 at 12, profiles/r27_replay_pairs.txt).
+// For the same reason these builds have no row S and let the rows start at S - 1: that row of the wavelengths only holds a draw between
+// two statements of a sample's start (the hero moves to a register), and pair 0 is rewritten by every replay pass before it is read; the
+// lane lists of the replay are BLOCK bytes behind the prepared programs instead of a row.
+// Pairs take 2 (n + 1) rows where the layout above takes 8 (n <= 7) or n + 1, so a scene is replayed in pairs only where that costs no
+// KB the layout above would not take: up to four spectrum-reading programs (tape_pairs_pay; the replay's gain is about two stack levels'
+// worth). With more, these builds replay one wavelength per lane as the interpreter builds do, over single rows packed the same way
+// (slots 0 and 1 in rows 0 and 1, 1.0 in row 2 -- the word a record of 1.0 carries is 2 in both forms --, slot s >= 2 in row s + 1:
+// n + 1 rows, never more than the layout above). -DPYR_REPLAY_PAIRS=0 builds have the layout above throughout (A/B).
+#ifndef PYR_REPLAY_PAIRS
+#define PYR_REPLAY_PAIRS 1
+#endif
+constexpr bool tape_pairs(bool interpreter) { return PYR_REPLAY_PAIRS != 0 && !interpreter; }
+constexpr uint32_t kTapeOnePair = 1, kTapeMaxPairRows = 2u * kTapeMaxValueRows, kTapePackedOneRow = 2u * kTapeOnePair;
+constexpr uint32_t tape_pair(uint32_t slot) { return slot + (slot >= kTapeOnePair ? 1u : 0u); }
+constexpr uint32_t tape_pair_rows(uint32_t n_spectral) { return 2u * (n_spectral + 1u); }
+constexpr uint32_t tape_packed_row(uint32_t slot) { return slot + (slot >= kTapePackedOneRow ? 1u : 0u); }
+constexpr uint32_t tape_packed_rows(uint32_t n_spectral) { return n_spectral < kTapePackedOneRow ? kTapePackedOneRow + 1u : n_spectral + 1u; }
+constexpr bool tape_pairs_pay(uint32_t n_spectral) { return 2u * n_spectral <= tape_rows_needed(n_spectral, false); }
+// (the kernel counts the programs itself and may find fewer than the host: it pairs when pairs pay AND the rows the host reserved hold them)
+constexpr bool tape_replays_pairs(uint32_t n_spectral, uint32_t value_rows) { return tape_pairs_pay(n_spectral) && tape_pair_rows(n_spectral) <= value_rows; }
+// the value rows of a scene with n spectrum-reading programs in these builds (too many to fit: the replay looks values up record by
+// record, and row S - 1, which a sample's start draws into, is the only one: it must not be the traversal stack's)
+constexpr uint32_t tape_pair_build_rows(uint32_t n_spectral) {
+    return tape_pairs_pay(n_spectral) ? tape_pair_rows(n_spectral) : (tape_packed_rows(n_spectral) <= kTapeMaxValueRows ? tape_packed_rows(n_spectral) : 1u);
+}
+// LDS rows of a tape build in front of the traversal stack: the wavelengths, the lane lists' row (not with pairs) and the value rows;
+// and where the value rows start.
+constexpr uint32_t tape_first_value_row(uint32_t spectrum_samples, bool interpreter) { return tape_pairs(interpreter) ? spectrum_samples - 1u : spectrum_samples + 1u; }
+constexpr uint32_t tape_spectral_rows(uint32_t spectrum_samples, uint32_t value_rows, bool interpreter) { return tape_first_value_row(spectrum_samples, interpreter) + value_rows; }
+constexpr uint32_t tape_lane_list_bytes(bool interpreter) { return tape_pairs(interpreter) ? 256u : 0u; } // BLOCK lane numbers
 
 constexpr uint32_t kMaxStackDepth = 64; // >= kMaxBvhDepth (bvh.h) and >= the wide tree's stack need (else the binary tree is walked)
 

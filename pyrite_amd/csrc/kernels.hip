@@ -2328,6 +2328,9 @@ constexpr uint32_t TAPE_MUL = 0u, TAPE_ADD = 1u, TAPE_SCALE = 2u, TAPE_HERO_ONLY
 // rows: slot * BLOCK). A constant program's value was folded into s when the record was written, and the BRDF factor is a
 // plain factor: both name the slot that holds 1.0 (x * 1.0 is x, bit for bit), so the replay has one straight-line form.
 constexpr uint32_t TAPE_EAGER_ADD = 1u << 31, TAPE_EAGER_SLOT_SHIFT = 8, TAPE_EAGER_SLOT_MASK = 0xFu << TAPE_EAGER_SLOT_SHIFT;
+// Builds that replay two wavelengths per lane (device_scene.h tape_pairs): the field holds twice the row, in five bits.
+constexpr uint32_t TAPE_PAIR_SLOT_MASK = 0x1Fu << TAPE_EAGER_SLOT_SHIFT;
+static_assert(2u * (kTapeMaxValueRows - 1u) <= 0x1Fu, "a pair record's row field");
 constexpr uint32_t kTapeOneSlot = kTapeEagerSlots - 1; // the value row that holds 1.0
 static_assert(kTapeEagerSlots == kTapeValueRows && kTapeOneSlot == kTapeOneRow, "device_scene.h tape_row() and friends");
 // Eager records of a HIT_RGB contribution (device_scene.h TapeForm; scenes with S.rgb_records): bits 12-13 of the word say what the
@@ -2357,7 +2360,7 @@ struct Walker {
             if (tape_prepared != nullptr) {
                 // eager replay: the record names the LDS slot of the program's value; a constant program is folded into the
                 // factor -- c * s is the very product `contribute` forms (program value times probability)
-                uint32_t slot = kTapeOneSlot;
+                uint32_t slot = tape_pairs(INTERP) ? kTapePackedOneRow : kTapeOneSlot; // (the same word whether the scene is replayed in pairs or not)
                 if (kind != TAPE_SCALE) {
                     const uint32_t* e = tape_prepared + 8 * program;
                     if (e[0] == 0u)
@@ -2856,9 +2859,9 @@ DEV float lambda_eval(const DevScene& S, const DevProgram& p, float wavelength) 
 // exposes its hero only (simple.rs:133-139); a light sample whose material reads the wavelength is added for the hero only
 // (algorithm.rs:78). Consecutive records of one program (the light samples of one estimation) share one look-up, as in the
 // synchronous walk. Must be called by every lane of the wave.
-template <bool COUNT, bool RGB = false, bool TIMES = false> // RGB: the scene may hold HIT_RGB records (interpreter builds that record a tape); TIMES: and PRODUCT ones
+template <bool COUNT, bool RGB = false, bool TIMES = false, typename LaneNumber = uint32_t> // RGB: the scene may hold HIT_RGB records (interpreter builds that record a tape); TIMES: and PRODUCT ones
 DEV void replay_tapes(const DevScene& S, const RenderLaunch& L, bool exposing, uint32_t n_ops, uint32_t tape_column, const Path& p, const float* wl_rows,
-                      uint32_t wl_column, uint32_t* wave_list, const uint32_t* prepared_lds, float* spectral_values, uint32_t n_spectral, bool eager, Counters& cnt) {
+                      uint32_t wl_column, LaneNumber* wave_list, const uint32_t* prepared_lds, float* spectral_values, uint32_t n_spectral, bool eager, Counters& cnt) {
     const uint32_t lane = threadIdx.x & 63u;
     const unsigned long long mask = ballot64(exposing);
     const uint32_t n = (uint32_t)__popcll(mask);
@@ -2882,10 +2885,20 @@ DEV void replay_tapes(const DevScene& S, const RenderLaunch& L, bool exposing, u
         const unsigned long long mine = keeps ? (longest ? k0 : (shortest ? k2 : k1)) : (longest ? l0 : (shortest ? l2 : l1));
         uint32_t before = keeps ? 0u : n_full;
         before += (uint32_t)__builtin_popcountll(keeps ? ((longest ? 0ull : k0) | (shortest ? k1 : 0ull)) : ((longest ? 0ull : l0) | (shortest ? l1 : 0ull)));
-        wave_list[before + (uint32_t)__builtin_popcountll(mine & below)] = lane;
+        wave_list[before + (uint32_t)__builtin_popcountll(mine & below)] = (LaneNumber)lane;
     }
     __builtin_amdgcn_wave_barrier();
-    const uint32_t SS = L.spectrum_samples, full_items = n_full * SS, items = full_items + (n - n_full);
+    // PAIRS (builds without interpreter programs, device_scene.h tape_pairs): an item is a path and TWO of its wavelengths, the
+    // halves ka = i % P and kb = ka + P with P = (S + 1) / 2. What an item pays per record and per pass -- the row's load, the two
+    // cross-lane reads, the slot mask, the compare; the divisions, the butterfly, the grain address -- it pays once for both, and
+    // the three f32 operations of a record that differ between them are packed (v_pk_mul_f32 twice, v_pk_add_f32): each half makes
+    // exactly the single form's operations in its order. Half k is the hero iff k == S - 1; kb == S (odd S: a path's last item) and
+    // the second half of a dispersed path's one item are no wavelength: they replay the first half's again and expose nothing.
+    // A scene is replayed in pairs where that costs no LDS (device_scene.h tape_replays_pairs: up to four spectrum-reading programs);
+    // with more, and where values are looked up record by record, these builds replay one wavelength per item by the single form below.
+    constexpr bool PAIRS = tape_pairs(RGB);
+    const bool paired = PAIRS && eager && tape_replays_pairs(n_spectral, S.tape_value_rows);
+    const uint32_t SS = L.spectrum_samples, per_path = paired ? (SS + 1u) / 2u : SS, full_items = n_full * per_path, items = full_items + (n - n_full);
     // The wave reads the tape row by row: a row (one record index of all 64 lanes) is 512 contiguous bytes, so every finished
     // lane loads its own column's record -- one coalesced load per row, eight rows in flight -- and an item takes the record of
     // the lane it replays with a cross-lane read. (Reading record after record of one column from the item's lane was a chain
@@ -2893,15 +2906,135 @@ DEV void replay_tapes(const DevScene& S, const RenderLaunch& L, bool exposing, u
     // Rows past the end of a tape read as the identity record of the eager form -- "reflectance *= value[one] * 1.0", and
     // x * 1.0 is x bit for bit -- so the straight-line replay needs no "is this row still on my tape" test per record.
     const unsigned long long past_the_end =
-        eager ? ((unsigned long long)(kTapeOneSlot << TAPE_EAGER_SLOT_SHIFT) | ((unsigned long long)__float_as_uint(1.0f) << 32)) : 0ull;
-#ifndef PYR_REPLAY_ROWS
-#define PYR_REPLAY_ROWS 8
+        eager ? ((unsigned long long)((PAIRS ? kTapePackedOneRow : kTapeOneSlot) << TAPE_EAGER_SLOT_SHIFT) | ((unsigned long long)__float_as_uint(1.0f) << 32)) : 0ull;
+    // Records per batch: four pairs hold the registers eight singles do. The builds that hold both forms batch the single one by four
+    // too: with eight the kernel is past the bounds of tests/test_kernel_isa.py (8,763 vector instructions, 280 B of scratch).
+#ifndef PYR_REPLAY_PAIR_ROWS
+#define PYR_REPLAY_PAIR_ROWS 4
 #endif
-    constexpr uint32_t ROWS = PYR_REPLAY_ROWS;
+#ifdef PYR_REPLAY_ROWS
+    constexpr uint32_t ROWS = PYR_REPLAY_ROWS, PAIR_ROWS = PYR_REPLAY_PAIR_ROWS;
+#else
+    constexpr uint32_t ROWS = PAIRS ? 4 : 8, PAIR_ROWS = PYR_REPLAY_PAIR_ROWS;
+#endif
     for (uint32_t base = 0; base < items; base += 64) {
         const uint32_t i = base + lane;
         const bool active = i < items;
         const bool full = i < full_items; // an item of a path that kept its companions; else the hero of a dispersed path
+        if (paired) {
+            const uint32_t rank = !active ? 0u : (full ? i / per_path : n_full + (i - full_items)), ka = !active ? 0u : (full ? i - rank * per_path : SS - 1u), kb = ka + per_path;
+            const uint32_t src = wave_list[rank];
+            const uint32_t ops = (uint32_t)__shfl((int)n_ops, (int)src);
+            uint32_t pass_ops = active ? (ops < L.tape_max_ops ? ops : L.tape_max_ops) : 0u;
+            for (int off = 32; off > 0; off >>= 1) pass_ops = max(pass_ops, (uint32_t)__shfl_xor((int)pass_ops, off));
+            const uint32_t pixel = (uint32_t)__shfl((int)p.pixel, (int)src);
+            const float hero_wl = __shfl(p.wl, (int)src);
+            const bool hero_a = ka == SS - 1, hero_b = kb == SS - 1;
+            // (what the loops below ask of a half lives in vector registers -- the pixel a half exposes, PIXEL_NONE for none, and the
+            // record bit it skips -- not in lane masks: the stage loop has no scalar register to spare, tests/test_kernel_isa.py)
+            const uint32_t pixel_a = active ? pixel : PIXEL_NONE, pixel_b = active && kb < SS ? pixel : PIXEL_NONE;
+            const uint32_t not_for_a = hero_a ? 0u : TAPE_HERO_ONLY, not_for_b = hero_b ? 0u : TAPE_HERO_ONLY; // a hero-only record is skipped by the companions
+            const uint32_t src_column = (uint32_t)__shfl((int)wl_column, (int)src);
+            const float wl_a = hero_a ? hero_wl : wl_rows[ka * BLOCK + src_column];
+            const float wl_b = hero_b ? hero_wl : (kb < SS ? wl_rows[(kb < SS ? kb : ka) * BLOCK + src_column] : wl_a); // (no row past the wavelengths' is read)
+            const f2v wl = {wl_a, wl_b};
+            f2v refl = {1.0f, 1.0f}, bright = {0.0f, 0.0f};
+            { // the look-up of every slot, as in the single form below, at both wavelengths: half h of row r is LDS row 2 r + h
+                const uint32_t* slot_program = prepared_lds + 8 * L.tape_programs_lds;
+                uint32_t grid_min = 0, grid_max = 0, grid_count = 0;
+                uint32_t i0[2] = {0, 0}, i1[2] = {0, 0};
+                float mix[2] = {0.0f, 0.0f};
+                uint32_t edge[2] = {0, 0}; // 1: at or below the grid's first point, 2: at or above its last
+                for (uint32_t slot = 0; slot < n_spectral; ++slot) {
+                    const uint32_t* e = prepared_lds + 8 * slot_program[slot];
+                    const uint32_t mode = e[0], format = e[2], count = e[6];
+                    const float c = __uint_as_float(e[1]);
+                    const float* data = S.spectrum_data + e[5];
+                    float v[2] = {0.0f, 0.0f};
+                    if (format == PYR_SPECTRUM_ARRAY && count != 0u) {
+                        if (e[3] != grid_min || e[4] != grid_max || count != grid_count) { // (uniform) another grid than the previous slot's
+                            grid_min = e[3], grid_max = e[4], grid_count = count;
+                            const float lo = __uint_as_float(grid_min), hi = __uint_as_float(grid_max);
+#pragma unroll
+                            for (uint32_t h = 0; h < 2; ++h) {
+                                const bool under = wl[h] <= lo, above = wl[h] >= hi;
+                                edge[h] = under ? 1u : (above ? 2u : 0u);
+                                const float normalized = (wl[h] - lo) / (hi - lo);
+                                const float float_index = normalized * ((float)count - 1.0f);
+                                const float min_float_index = truncf(float_index);
+                                i0[h] = (under | above) ? 0u : (uint32_t)min_float_index;
+                                i1[h] = (under | above) ? 0u : i0[h] + 1u;
+                                mix[h] = float_index - min_float_index;
+                            }
+                        }
+#pragma unroll
+                        for (uint32_t h = 0; h < 2; ++h) {
+                            const float inside = data[i0[h]] * (1.0f - mix[h]) + data[i1[h]] * mix[h];
+                            v[h] = edge[h] == 1u ? data[0] : (edge[h] == 2u ? data[count - 1] : inside);
+                        }
+                    } else {
+                        PyrSpectrum sp;
+                        sp.format = format, sp.min = __uint_as_float(e[3]), sp.max = __uint_as_float(e[4]), sp.offset = e[5], sp.count = count;
+#pragma nounroll
+                        for (uint32_t h = 0; h < 2; ++h) {
+                            const float one = spectrum_eval(sp, data, h == 0u ? wl_a : wl_b);
+                            v[0] = h == 0u ? one : v[0], v[1] = one;
+                        }
+                    }
+#pragma unroll
+                    for (uint32_t h = 0; h < 2; ++h) spectral_values[(2u * tape_pair(slot) + h) * BLOCK] = mode == FAST_SPECTRUM ? v[h] : v[h] * c;
+                }
+            }
+            for (uint32_t r0 = 0; r0 < pass_ops; r0 += PAIR_ROWS) {
+                unsigned long long rows[PAIR_ROWS];
+#pragma unroll
+                for (uint32_t j = 0; j < PAIR_ROWS; ++j) rows[j] = r0 + j < my_ops ? L.tape[tape_index(r0 + j, L.tape_lanes, tape_column)] : past_the_end;
+                uint32_t words[PAIR_ROWS];
+                float factors[PAIR_ROWS];
+#pragma unroll
+                for (uint32_t j = 0; j < PAIR_ROWS; ++j) {
+                    words[j] = (uint32_t)__shfl((int)(uint32_t)rows[j], (int)src);
+                    factors[j] = __uint_as_float((uint32_t)__shfl((int)(uint32_t)(rows[j] >> 32), (int)src));
+                }
+                f2v values[PAIR_ROWS];
+#pragma unroll
+                for (uint32_t j = 0; j < PAIR_ROWS; ++j) {
+                    const float* row = spectral_values + (words[j] & TAPE_PAIR_SLOT_MASK); // (2 r) << 8 is 2 r * BLOCK: the first half's row, its twin one row on
+                    values[j] = f2v{row[0], row[BLOCK]};
+                }
+                if (S.hero_only_records == 0) { // (uniform) every record applies to both halves
+#pragma unroll
+                    for (uint32_t j = 0; j < PAIR_ROWS; ++j) {
+                        const f2v m = values[j] * factors[j];
+                        const bool adds = (int)words[j] < 0;
+                        const f2v multiplied = refl * m, added = bright + multiplied;
+                        bright.x = adds ? added.x : bright.x, bright.y = adds ? added.y : bright.y;
+                        refl.x = adds ? refl.x : multiplied.x, refl.y = adds ? refl.y : multiplied.y;
+                    }
+                    continue;
+                }
+#pragma unroll
+                for (uint32_t j = 0; j < PAIR_ROWS; ++j) {
+                    // a half the record is not for replays the identity record in its place -- "reflectance *= 1.0", as a row past the
+                    // end of a tape does -- chosen with bit operations: one lane mask per half and record, not three. So a skipped half
+                    // computes refl = refl * 1.0 where the single form leaves refl untouched: the same bits for every value but a
+                    // signalling NaN, which no operation here makes (f32 denormals are kept); tests/test_replay_identity_cpu.py
+                    const f2v product = values[j] * factors[j];
+                    const uint32_t skip_a = 0u - ((words[j] & not_for_a) >> 29), skip_b = 0u - ((words[j] & not_for_b) >> 29); // all ones: skipped
+                    static_assert(TAPE_HERO_ONLY == 1u << 29, "the shift above");
+                    const f2v m = {__uint_as_float((__float_as_uint(product.x) & ~skip_a) | (__float_as_uint(1.0f) & skip_a)),
+                                   __uint_as_float((__float_as_uint(product.y) & ~skip_b) | (__float_as_uint(1.0f) & skip_b))};
+                    const bool adds_a = (int)(words[j] & ~skip_a) < 0, adds_b = (int)(words[j] & ~skip_b) < 0;
+                    const f2v multiplied = refl * m, added = bright + multiplied;
+                    bright.x = adds_a ? added.x : bright.x, bright.y = adds_b ? added.y : bright.y;
+                    refl.x = adds_a ? refl.x : multiplied.x, refl.y = adds_b ? refl.y : multiplied.y;
+                }
+            }
+#pragma nounroll
+            for (uint32_t h = 0; h < 2; ++h)
+                expose_grain<COUNT>(L, h == 0u ? pixel_a : pixel_b, h == 0u ? wl_a : wl_b, h == 0u ? bright.x : bright.y, cnt);
+            continue;
+        }
         const uint32_t rank = !active ? 0u : (full ? i / SS : n_full + (i - full_items)), k = !active ? 0u : (full ? i - rank * SS : SS - 1u);
         const uint32_t src = wave_list[rank];
         const uint32_t ops = (uint32_t)__shfl((int)n_ops, (int)src);
@@ -2957,7 +3090,7 @@ DEV void replay_tapes(const DevScene& S, const RenderLaunch& L, bool exposing, u
                     sp.format = format, sp.min = __uint_as_float(e[3]), sp.max = __uint_as_float(e[4]), sp.offset = e[5], sp.count = count;
                     v = spectrum_eval(sp, data, wl);
                 }
-                spectral_values[tape_row(slot) * BLOCK] = (mode == FAST_SPECTRUM || mode == 0xFFu) ? v : v * c; // FAST_SPECTRUM_MUL and FAST_MUL_SPECTRUM: v * c is c * v
+                spectral_values[(PAIRS ? tape_packed_row(slot) : tape_row(slot)) * BLOCK] = (mode == FAST_SPECTRUM || mode == 0xFFu) ? v : v * c; // FAST_SPECTRUM_MUL and FAST_MUL_SPECTRUM: v * c is c * v
             }
             if (RGB && S.rgb_records != 0) { // (uniform) the RGB basis at this item's wavelength: RgbSpectrumValue's look-up, execution_context.rs:140-152
                 float resp[3] = {0.0f, 0.0f, 0.0f};
@@ -3087,6 +3220,7 @@ DEV void replay_tapes(const DevScene& S, const RenderLaunch& L, bool exposing, u
 // program's value among the programs that read a spectrum), followed by the slot -> program list. Returns the number of
 // spectrum-reading programs when they fit the kTapeEagerSlots value rows (the replay then looks each up once per item), else
 // 0 (looked up record by record). Called by every thread of the workgroup; ends with a barrier.
+template <bool PAIRS>
 DEV uint32_t prepare_tape_tables(const DevScene& S0, const DevScene& S, const RenderLaunch& L, uint32_t* prepared_lds, bool& eager) {
     // Programs that evaluate alike -- the same shape, factor and spectrum (a scene compiles one colour program per use: C3's
     // three white walls are three programs over one spectrum) -- share a value slot: the replay looks a slot up once per item.
@@ -3110,6 +3244,7 @@ DEV uint32_t prepare_tape_tables(const DevScene& S0, const DevScene& S, const Re
     };
     uint32_t n_spectral = 0;
     for (uint32_t i = 0; i < L.tape_programs_lds; ++i) n_spectral += (reads_spectrum(i) && first_alike(i) == i) ? 1u : 0u;
+    const bool paired = PAIRS && tape_replays_pairs(n_spectral, S0.tape_value_rows); // (device_scene.h: the scenes pairs cost no LDS)
     for (uint32_t i = threadIdx.x; i < L.tape_programs_lds; i += BLOCK) {
         const Prepared q = prepare_program<false>(S, i);
         const bool spectral = reads_spectrum(i);
@@ -3117,7 +3252,7 @@ DEV uint32_t prepare_tape_tables(const DevScene& S0, const DevScene& S, const Re
         const uint32_t slot = spectral ? slot_of(representative) : 0u;
         uint32_t* e = prepared_lds + 8 * i;
         e[0] = q.mode, e[1] = __float_as_uint(q.c), e[2] = q.sp.format, e[3] = __float_as_uint(q.sp.min), e[4] = __float_as_uint(q.sp.max);
-        e[5] = q.sp.offset, e[6] = q.sp.count, e[7] = tape_row(slot); // what a record carries: the value ROW
+        e[5] = q.sp.offset, e[6] = q.sp.count, e[7] = !PAIRS ? tape_row(slot) : (paired ? 2u * tape_pair(slot) : tape_packed_row(slot)); // what a record carries: the value ROW (pairs: of the first half)
         if (spectral && representative == i && slot < kTapeMaxValueRows - 1u) prepared_lds[8 * L.tape_programs_lds + slot] = i;
     }
     __syncthreads();
@@ -3125,7 +3260,8 @@ DEV uint32_t prepare_tape_tables(const DevScene& S0, const DevScene& S, const Re
     // programs' slots): too many spectrum-reading programs for them and the replay looks values up record by record. A scene
     // without any such program has nothing to look up eagerly -- unless it records hit-tape forms, which only the eager replay knows
     // (api.cpp makes sure they fit).
-    eager = L.tape_programs_lds != 0 && tape_rows_needed(n_spectral, S0.rgb_records != 0) <= S0.tape_value_rows && (n_spectral != 0 || S0.hit_tape != 0);
+    eager = L.tape_programs_lds != 0 && (paired || (PAIRS ? tape_packed_rows(n_spectral) : tape_rows_needed(n_spectral, S0.rgb_records != 0)) <= S0.tape_value_rows) &&
+            (n_spectral != 0 || S0.hit_tape != 0);
     return eager ? n_spectral : 0u;
 }
 
@@ -3147,7 +3283,8 @@ __global__ __launch_bounds__(BLOCK, sm_waves(INTERP)) void render_kernel_sm(DevS
     const uint32_t SS = L.spectrum_samples;
     Spectral spec{lds + threadIdx.x, SS};
     // LDS rows of 256 floats: TAPE: S wavelengths + one row of per-wave lane lists; else wavelengths / brightness / reflectance
-    const uint32_t spectral_rows = TAPE ? SS + 1 + S0.tape_value_rows : 3 * SS;
+    // (builds that replay two wavelengths per lane: no row of lists, and the value rows start at row S - 1: device_scene.h tape_pairs)
+    const uint32_t spectral_rows = TAPE ? tape_spectral_rows(SS, S0.tape_value_rows, INTERP) : 3 * SS;
     TravStack stack;
     int deep_levels[LDS_SCENE ? 1 : kMaxStackDepth]; // a scene that lives in LDS has its whole stack there (launch_render)
     stack.deep = deep_levels;
@@ -3169,19 +3306,27 @@ __global__ __launch_bounds__(BLOCK, sm_waves(INTERP)) void render_kernel_sm(DevS
     Walker<COUNT, INTERP, TAPE, PRODUCT> w;
     w.chunk = L.chunk_begin + blockIdx.x * waves_per_block + (threadIdx.x >> 6);
     w.tape_prepared = nullptr;
-    uint32_t* wave_list = reinterpret_cast<uint32_t*>(lds + SS * BLOCK) + (threadIdx.x & ~63u);
     // prepared programs for the replay: 8 words each, behind everything else in LDS
     uint32_t* prepared_lds = reinterpret_cast<uint32_t*>(lds + lds_base_floats + (LDS_SCENE ? (S0.num_nodes * 16 + S0.num_prims * 12) : 0) + (LDS_TABLES ? S0.lds_table_floats : 0));
+    // the replay's lists of finished lanes, one per wave: row S of words, or (pairs) BLOCK bytes behind the prepared programs and their slot list
+    typedef std::conditional_t<tape_pairs(INTERP), uint8_t, uint32_t> LaneNumber;
+    LaneNumber* wave_list = (tape_pairs(INTERP) ? reinterpret_cast<LaneNumber*>(prepared_lds + 8 * L.tape_programs_lds + kTapeMaxValueRows) : reinterpret_cast<LaneNumber*>(lds + SS * BLOCK)) +
+                            (threadIdx.x & ~63u);
     // programs that read a spectrum get a slot (their rank among such programs); the slot -> program list follows the table
     uint32_t n_spectral = 0;
     bool eager = false;
-    float* spectral_values = lds + (SS + 1) * BLOCK + threadIdx.x;
+    float* spectral_values = lds + tape_first_value_row(SS, INTERP) * BLOCK + threadIdx.x;
     if constexpr (TAPE) {
         // eager records of constant programs and BRDF factors (tape_push). TAPE builds only: without the tape these rows are not
         // reserved, and with few wavelengths the store landed in the staged scene (found by the fuzz campaign of round 3: two
         // wavelengths, a tree four levels deep -- row SS + 8 was the first KB of the LDS copy of the nodes)
-        spectral_values[kTapeOneSlot * BLOCK] = 1.0f;
-        n_spectral = prepare_tape_tables(S0, S, L, prepared_lds, eager);
+        if constexpr (!tape_pairs(INTERP)) spectral_values[kTapeOneSlot * BLOCK] = 1.0f;
+        n_spectral = prepare_tape_tables<tape_pairs(INTERP)>(S0, S, L, prepared_lds, eager);
+        // (pairs: a scene that is not replayed eagerly has pair 0 alone -- the row a sample's start draws into is never the stack's)
+        if (tape_pairs(INTERP) && eager) {
+            spectral_values[kTapePackedOneRow * BLOCK] = 1.0f;
+            if (tape_replays_pairs(n_spectral, S0.tape_value_rows)) spectral_values[(kTapePackedOneRow + 1u) * BLOCK] = 1.0f; // its twin
+        }
         if (eager) w.tape_prepared = prepared_lds;
         w.rgb_slot = tape_rgb_row(n_spectral);
         w.tape_column = blockIdx.x * BLOCK + threadIdx.x;
@@ -3191,7 +3336,7 @@ __global__ __launch_bounds__(BLOCK, sm_waves(INTERP)) void render_kernel_sm(DevS
     // the scene record as the phases see it (table pointers at the staged copies), rebuilt where a phase starts
     auto scene_view = [&](const RenderLaunch& Lp) {
         if (LDS_SCENE || INTERP) return S; // interpreter builds hand the record to run_interpreter by address: one copy in scratch, made once
-        const uint32_t rows = (TAPE ? Lp.spectrum_samples + 1 + S0.tape_value_rows : 3 * Lp.spectrum_samples) + Lp.stack_lds;
+        const uint32_t rows = (TAPE ? tape_spectral_rows(Lp.spectrum_samples, S0.tape_value_rows, INTERP) : 3 * Lp.spectrum_samples) + Lp.stack_lds;
         return stage_tables<LDS_TABLES ? 1 : 0, false>(scene_from_kernarg(S0), lds, rows * BLOCK);
     };
     PROF_DECL;

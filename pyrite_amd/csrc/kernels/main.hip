@@ -164,7 +164,8 @@ static bool scene_fits_lds(const DevScene& scene) { return (size_t)scene.num_nod
 // Levels of the traversal stack kept in LDS. The synchronous walk keeps the whole stack there (its scenes are shallow). The
 // resumable walk spills deeper levels to scratch (TravStack) and keeps as many levels in LDS as still let `workgroups`
 // workgroups share a CU's 160 KB next to `other_bytes` of LDS each -- on C3 the render runs at 103 / 135 / 160 Msamples/s
-// with 2 / 3 / 4 workgroups per CU and does not care whether 4 or 12 levels are in LDS. PYRITE_LDS_STACK overrides.
+// with 2 / 3 / 4 workgroups per CU and did not care whether 4 or 12 levels are in LDS (an early round; today it does: 660 / 635 / 611 /
+// 569 Msamples/s at 14 / 12 / 10 / 6 levels, profiles/r27_replay_pairs.txt -- a KB of LDS is a level). PYRITE_LDS_STACK overrides.
 constexpr uint32_t kShortStackMax = 16;
 static uint32_t short_stack_levels(const DevScene& scene, size_t other_bytes, uint32_t workgroups) {
     const char* e = std::getenv("PYRITE_LDS_STACK");
@@ -200,11 +201,11 @@ uint32_t launch_tape(const DevScene& scene, const RenderLaunch& launch) {
 }
 static bool uses_tape(const DevScene& scene, const RenderLaunch& launch) { return launch_tape(scene, launch) != 0u; }
 static size_t render_lds_bytes(const DevScene& scene, const RenderLaunch& launch) {
-    const size_t spectral_rows = uses_tape(scene, launch) ? launch.spectrum_samples + 1 + scene.tape_value_rows : 3 * launch.spectrum_samples;
+    const size_t spectral_rows = uses_tape(scene, launch) ? tape_spectral_rows(launch.spectrum_samples, scene.tape_value_rows, scene.needs_interpreter != 0) : 3 * launch.spectrum_samples;
     size_t bytes = (spectral_rows + launch.stack_lds) * BLOCK * sizeof(float);
     if (scene_fits_lds(scene)) bytes += (size_t)scene.num_nodes * 64 + (size_t)scene.num_prims * 48;
     bytes += (size_t)scene.lds_table_floats * sizeof(float);
-    if (uses_tape(scene, launch)) bytes += ((size_t)tape_programs_in_lds(scene) * 8 + kTapeMaxValueRows) * sizeof(uint32_t);
+    if (uses_tape(scene, launch)) bytes += ((size_t)tape_programs_in_lds(scene) * 8 + kTapeMaxValueRows) * sizeof(uint32_t) + tape_lane_list_bytes(scene.needs_interpreter != 0);
     return bytes;
 }
 

@@ -58,7 +58,7 @@ for i, name in enumerate(["EXPOSE/NEW", "SHADE", "NEE", "TRAV"]):
 if which in ("C3", "C5"):  # builds without interpreter programs: EXPOSE/NEW split into the tape replay (with its exposures) and the sample start
     phase = float(cyc[0]) or 1.0
     replay, start, fills, pops = out[15], out[12], out[13], out[14]
-    print("  of EXPOSE/NEW: replay + exposure %5.1f %% of wave cycles (%4.1f %% of the phase, full width: one (path, wavelength) pair per lane)"
+    print("  of EXPOSE/NEW: replay + exposure %5.1f %% of wave cycles (%4.1f %% of the phase, full width: one item per lane, a path and one or two of its wavelengths)"
           % (100.0 * replay / total, 100.0 * replay / phase))
     if fills:  # PYR_SAMPLE_QUEUE builds: the starts of a chunk at full width, then one pop per lane in ST_NEW
         print("  of EXPOSE/NEW: sample start      %5.1f %% of wave cycles = fills %4.1f %% (64 lanes, %.3f fills per 64 samples, %6.0f cycles per fill) + pops %4.1f %% (mean lanes %4.1f, %5.0f cycles per turn)"
