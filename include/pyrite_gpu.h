@@ -1446,6 +1446,73 @@ int pyr_session_despeckled(PyrSession* session, const PyrDevelopParams* develop_
                            const PyrFeatureParams* feature_params, const PyrDenoiseParams* denoise_params, float* out, float* error_out, float* removed_out,
                            uint32_t* counts_out);
 
+/* ------------------------------------------------------------ lens blur over the feature records ----
+ * The feature pass is a pinhole pass, and every image stage above is steered by it: a camera with aperture > 0 renders a blur
+ * whose guides are sharp. As with motion, the lens goes back in as a post filter: render the frame with aperture 0, run the
+ * guide-driven filters while image and guides agree, then spread every pixel over its circle of confusion, read from the depth of
+ * its record. It needs no scene. `image`, `out`: width*height*3 f32 in linear light; `pixels`: the PyrFeaturePixel records of the
+ * same camera at the same size. All arithmetic is f32 and unfused, one rounding per operation, in the order written; sqrt and / are
+ * the correctly rounded ones; clamp01(v) = fminf(fmaxf(v, 0.0f), 1.0f), so a NaN becomes 0; fminf and fmaxf return the other
+ * operand of a NaN. "Finite" means neither an infinity nor a NaN. PI_F = 3.14159265f (0x40490FDB).
+ *   The lens is the disc of radius sqrt(aperture) (cameras.rs:84). A point at axial depth z is spread on the focus plane over the
+ *   radius sqrt(aperture)*|1 - f/z|, and one unit of the focus plane is view_plane/f * max(W,H)/2 pixels (cameras.rs:57-68, 78-81):
+ *     m = (float)max(width, height) * 0.5f,  A = (sqrt(aperture) * (view_plane / focus_distance)) * m,  R = (float)max_radius.
+ *   Circle of confusion of pixel (x, y), index p = y*width + x, record r. The record is a miss when r.coverage == 0, or r.depth is
+ *   not finite, or r.depth <= 0. The pixel centre's view-plane coordinates are those of Camera::to_view_area (cameras.rs:57-68):
+ *     px = ((float)x + -((float)width * 0.5f)) / m + (1.0f / m) * 0.5f,   py likewise from y and height
+ *     t = (px*px + py*py) / (view_plane*view_plane)
+ *     z = r.depth / sqrt(1.0f + t)                                     -- r.depth runs along the ray, z along the axis
+ *     c = fminf(A * fabsf(1.0f - focus_distance / z), R)
+ *   For a miss z = FLT_MAX and c = fminf(A, R): the sky lies at infinity. For every pixel
+ *     inv = 1.0f / fmaxf(PI_F * ((c + 0.5f)*(c + 0.5f)), 1.0f)       -- one over the area of its disc, at most 1.
+ *   (Where focus_distance / z overflows -- a depth below focus_distance / FLT_MAX -- A * inf is inf, or NaN with A = 0, and c = R.)
+ *   Gather for pixel p with colour C_p = image[p] and (c_p, inv_p, z_p) from above. W_f = W_b = 0.0f, S_f = S_b = (0, 0, 0). The
+ *   window is the (2*max_radius+1)^2 offsets (ox, oy), oy outer from -max_radius, ox inner from -max_radius, p itself included. A
+ *   tap q = (x + ox, y + oy) is skipped when it lies outside the image or one of the three floats of C_q is not finite. Otherwise
+ *     d = sqrt((float)(ox*ox + oy*oy))
+ *     front = (z_p - z_q) > depth_tolerance * z_p                    -- q lies in front of p by more than the tolerance
+ *     front:      c_e = c_q,  inv_e = inv_q                          -- a front tap spreads by its own circle
+ *     otherwise:  c_e = fminf(c_q, c_p),  inv_e = inv_q when c_q < c_p, else inv_p
+ *                                                                    -- seen only through the smaller circle: a blurred
+ *                                                                       background does not bleed over a sharp foreground
+ *     w = clamp01((c_e - d) + 1.0f) * inv_e
+ *   A tap with w == 0 adds nothing. A front tap adds W_f = W_f + w, S_f.c = S_f.c + w * C_q.c; any other tap the same to W_b, S_b.
+ *   p itself always lands in W_b with w = inv_p > 0.
+ *   Result. out[p] = image[p], bit for bit, if one of C_p's three floats is not finite, or if no tap but p itself had w > 0: with
+ *   aperture == 0 the filter is the identity, and what is in focus and out of every neighbour's reach keeps its bits. Otherwise
+ *     B.c = S_b.c / W_b;   with W_f == 0: out[p].c = B.c;   else a = fminf(W_f, 1.0f),  F.c = S_f.c / W_f,
+ *     out[p].c = a * F.c + (1.0f - a) * B.c
+ *   W_f is the share of the pixel that the foreground's blur covers: a pixel wholly behind a blurred foreground shows the foreground.
+ * No tap with d >= c + 1 weighs, and c <= max_radius: a pixel reads only its window. One lane owns a pixel, there are no atomics,
+ * two calls write the same bytes. The limits: one layer is known per pixel, so what a wide lens sees round an edge is not
+ * recovered; c is clamped to max_radius; only first hits are refocused -- a mirror's image blurs at the mirror's depth, as do
+ * shadows and what glass shows. One GPU. */
+#define PYR_LENS_BLUR_MAX_RADIUS 8u
+#define PYR_LENS_BLUR_MOST_RADIUS 16u
+typedef struct PyrLensBlurParams {
+    float focus_distance;  /* PyrCamera::focus_distance: finite, > 0 */
+    float aperture;        /* PyrCamera::aperture: finite, >= 0; 0 is the identity */
+    float view_plane;      /* PyrCamera::view_plane: finite, > 0 */
+    uint32_t max_radius;   /* the largest circle of confusion in pixels, and the window's half side: 1..PYR_LENS_BLUR_MOST_RADIUS */
+    float depth_tolerance; /* relative: finite, in [0, 1); default PYR_REPROJECT_DEPTH_TOLERANCE */
+    uint32_t reserved[3];  /* 0 */
+} PyrLensBlurParams; /* 32 bytes */
+/* Arguments are checked before a device is looked for: PYR_ERR_INVALID_ARGUMENT, with the argument named in pyr_last_error, for a
+ * null image, pixels, params or out, a parameter out of range (a NaN is), a non-zero reserved word, an empty image;
+ * PYR_ERR_UNSUPPORTED for more than 2^32 - 1 pixels; only then PYR_ERR_DEVICE. HOST buffers. Blocking. */
+int pyr_image_lens_blur(const float* image, const PyrFeaturePixel* pixels, uint32_t width, uint32_t height, const PyrLensBlurParams* params, float* out, int device);
+/* The same with every buffer resident on `device`, enqueued on `hip_stream` without synchronising. The records must be 16-byte
+ * aligned and out may not overlap image or pixels (PYR_ERR_INVALID_ARGUMENT otherwise, after the checks above and before the
+ * device). No working memory. */
+int pyr_image_lens_blur_device(const float* image_device, const PyrFeaturePixel* pixels_device, uint32_t width, uint32_t height, const PyrLensBlurParams* params,
+                               float* out_device, int device, void* hip_stream);
+/* What pyr_session_linear (PYR_LINEAR_SRGB), the records of pyr_session_features (`feature_params`; no albedo is made) and the blur
+ * do, composed on the session's stream and device: nothing but the result crosses to the host. The lens is `blur_params`', not the
+ * session camera's: a session rendered with aperture 0 is the intended input. out = HOST, height*width*3 floats. The session's
+ * film is not touched, and further passes may follow. Blocking. */
+int pyr_session_lens_blurred(PyrSession* session, const PyrDevelopParams* develop_params, const PyrFeatureParams* feature_params,
+                             const PyrLensBlurParams* blur_params, float* out);
+
 #ifdef __cplusplus
 }
 #endif

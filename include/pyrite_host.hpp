@@ -427,6 +427,19 @@ PyrMotionBlurParams motion_blur_params(float shutter = PYR_MOTION_BLUR_SHUTTER, 
 std::vector<float> motion_blur(const std::vector<float>& image, const std::vector<PyrMotionPixel>& motion, uint32_t width, uint32_t height,
                                const PyrMotionBlurParams& params = motion_blur_params(), int device = 0);
 
+// ---- lens blur over the feature records (pyrite_gpu.h "lens blur over the feature records"; pyrite_amd/develop.py lens_blur) ----
+PyrLensBlurParams lens_blur_params(float focus_distance, float aperture, float view_plane, uint32_t max_radius = PYR_LENS_BLUR_MAX_RADIUS,
+                                   float depth_tolerance = PYR_REPROJECT_DEPTH_TOLERANCE);
+// The three lens numbers of `camera`.
+PyrLensBlurParams lens_blur_params(const Camera& camera, uint32_t max_radius = PYR_LENS_BLUR_MAX_RADIUS, float depth_tolerance = PYR_REPROJECT_DEPTH_TOLERANCE);
+// The linear image `image`, [height][width][3] f32, rendered through a pinhole, blurred as a thin lens would blur it, over the
+// feature records of the same camera at the same size (Renderer::features) on the GPU (pyr_image_lens_blur). A buffer of another
+// size than the image's is a ProjectError before the library is called.
+std::vector<float> lens_blur(const std::vector<float>& image, const std::vector<PyrFeaturePixel>& pixels, uint32_t width, uint32_t height, const PyrLensBlurParams& params,
+                             int device = 0);
+// What is wrong with --lens-blur / --lens-blur-radius R, in the words both front ends print, or "" (pyrite_amd/develop.py lens_blur_flag_problem).
+std::string lens_blur_flag_problem(bool lens_blur, const std::optional<long>& lens_blur_radius);
+
 // ---- glare (pyrite_gpu.h "glare"; pyrite_amd/develop.py glare) ----
 PyrGlareParams glare_params(float strength = PYR_GLARE_STRENGTH, uint32_t levels = PYR_GLARE_LEVELS, float threshold = PYR_GLARE_THRESHOLD, float falloff = PYR_GLARE_FALLOFF);
 // The linear image `image`, [height][width][3] f32, with the glare of a lens or an eye added on the GPU (pyr_image_glare). A buffer
@@ -552,6 +565,10 @@ class Session {
     // pyr_session_motion_blurred: the film as it stands in linear sRGB, blurred along the records against `previous_camera`, on the session's device
     std::vector<float> motion_blurred(const Camera& previous_camera, const PyrMotionBlurParams& params = motion_blur_params(), float step_size = 2.0f,
                                       const std::optional<Expression>& filter = std::nullopt, const std::optional<Expression>& white = std::nullopt);
+    // pyr_session_lens_blurred: the film as it stands in linear sRGB, blurred by the lens of `params` over the records of the feature
+    // pass (grid x grid sub-samples), on the session's device; the film is not touched
+    std::vector<float> lens_blurred(const PyrLensBlurParams& params, uint32_t grid = 1, float step_size = 2.0f, const std::optional<Expression>& filter = std::nullopt,
+                                    const std::optional<Expression>& white = std::nullopt);
     // pyr_session_glared: the film as it stands in linear sRGB with the glare added, on the session's device; the film is not touched
     std::vector<float> glared(const PyrGlareParams& params = glare_params(), float step_size = 2.0f, const std::optional<Expression>& filter = std::nullopt,
                               const std::optional<Expression>& white = std::nullopt);

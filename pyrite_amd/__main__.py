@@ -6,7 +6,7 @@
                          [--pass-samples N] [--preview PATH] [--preview-every SECONDS] [--noise]
                          [--features PREFIX] [--features-grid N] [--hdr PATH] [--exposure EV|auto] [--tone clip|reinhard]
                          [--despeckle [K]] [--despeckle-radius R] [--denoise] [--denoise-radius N] [--upsample N] [--upsample-radius R]
-                         [--glare [STRENGTH]] [--glare-levels N] [--glare-threshold T]
+                         [--glare [STRENGTH]] [--glare-levels N] [--glare-threshold T] [--lens-blur] [--lens-blur-radius R]
                          [--build host|device]
 
 With --pass-samples, --preview or --noise the render runs as a progressive session (pyr_session_*): passes of N samples per pixel
@@ -42,6 +42,12 @@ With --glare the final image takes the linear path (the denoised image with --de
 to it (pyr_image_glare: STRENGTH of every pixel's light, default 0.1, spread over N blurs of doubling width, default 6; with
 --glare-threshold T only what lies above the luminance T): before the statistics of an automatic exposure are taken and before the
 tone curve, which without --exposure / --tone is the clip at exposure 1. The --hdr image is the glared one. Previews have no glare.
+
+With --lens-blur the frame is rendered with the project camera's aperture set to 0 -- a pinhole, so that the image agrees with the
+feature pass that steers --denoise and --upsample -- and the camera's own focus_distance and aperture are applied afterwards by a
+filter that reads the depth of the full-size feature records (pyr_image_lens_blur; circles of confusion of at most R pixels, 1 to
+16, default 8): after --despeckle, --denoise and --upsample, before --glare and the tone curve. What is in focus and out of every
+blur's reach keeps the pinhole frame's values. The --hdr image is the blurred one; previews show the pinhole.
 
 With --build the acceleration structure is built by the named builder (host: one CPU thread, the default; device: the same tree from
 the GPU, pyr_scene_create_with) and one line with the builder used and the stage times of scene creation goes to stderr."""
@@ -122,15 +128,18 @@ def main(argv=None):
     ap.add_argument("--glare", nargs="?", const=str(0.1), default=None, metavar="STRENGTH", help="add glare to the final image: the share of the light that is spread (above 0, at most 1; default 0.1)")
     ap.add_argument("--glare-levels", type=int, default=None, metavar="N", help="blurs of doubling width the glare sums (1 to 12, default 6)")
     ap.add_argument("--glare-threshold", type=float, default=None, metavar="T", help="luminance below which a pixel spreads nothing (default 0: every pixel spreads)")
+    ap.add_argument("--lens-blur", action="store_true", help="render through a pinhole and apply the project camera's focus_distance and aperture as a filter over the feature records")
+    ap.add_argument("--lens-blur-radius", type=int, default=None, metavar="R", help="largest circle of confusion of --lens-blur in pixels (1 to 16, default 8)")
     ap.add_argument("--build", default=None, choices=["host", "device"], help="who builds the BVH (default host); given, the stage times of scene creation go to stderr")
     args = ap.parse_args(argv)
-    from .develop import denoise_flag_problem, despeckle_flag_problem, despeckle_from_flags, glare_flag_problem, glare_from_flags, tone_flag_problem, tone_from_flags, upsample_flag_problem, upsample_from_flags
+    from .develop import denoise_flag_problem, despeckle_flag_problem, despeckle_from_flags, glare_flag_problem, glare_from_flags, lens_blur_flag_problem, tone_flag_problem, tone_from_flags, upsample_flag_problem, upsample_from_flags
     from .features import features_flag_problem
 
     problem = (progressive_flag_problem(args.pass_samples, args.preview, args.preview_every, args.noise) or features_flag_problem(args.features, args.features_grid)
                or tone_flag_problem(args.hdr, args.exposure, args.tone) or despeckle_flag_problem(args.despeckle, args.despeckle_radius)
                or denoise_flag_problem(args.denoise, args.denoise_radius)
-               or upsample_flag_problem(args.upsample, args.upsample_radius) or glare_flag_problem(args.glare, args.glare_levels, args.glare_threshold))
+               or upsample_flag_problem(args.upsample, args.upsample_radius) or glare_flag_problem(args.glare, args.glare_levels, args.glare_threshold)
+               or lens_blur_flag_problem(args.lens_blur, args.lens_blur_radius))
     if problem:
         print("error: " + problem, file=sys.stderr)
         return 2
@@ -141,7 +150,7 @@ def main(argv=None):
     args.upsample_params = upsample_from_flags(args.upsample, args.upsample_radius)
 
     from . import lua_project, scenes
-    from .develop import develop, develop_linear, glare, save_linear, save_png, tonemap, upsample
+    from .develop import develop, develop_linear, glare, lens_blur, save_linear, save_png, tonemap, upsample
 
     project, base_dir = lua_project.load_project(args.project)
     if args.size:
@@ -160,6 +169,13 @@ def main(argv=None):
         project["image"].update(width=full_size[0] // args.upsample, height=full_size[1] // args.upsample)
     seed = args.seed if args.seed is not None else int(time.time_ns() & 0x7FFFFFFFFFFFFFFF)
     world, cam, r, film = scenes.build(project, seed=seed, base_dir=base_dir)
+    lens_cam = cam
+    if args.lens_blur:  # the render, its guides and every filter before the lens see a pinhole
+        from . import abi
+        from .renderer import Camera
+
+        cam = Camera(abi.PyrCamera.from_buffer_copy(lens_cam.c))
+        cam.c.aperture = 0.0
     print("The scene contains %d objects." % (len(world.flat.tri_material) + len(world.flat.spheres) + len(world.flat.planes)))  # world.rs:251-254
 
     if args.build:
@@ -183,16 +199,19 @@ def main(argv=None):
     linear = None
     if args.denoise or args.despeckle_params is not None:
         linear = args.denoised
-    elif args.hdr or args.tone_params is not None or args.glare_params is not None or args.upsample:
+    elif args.hdr or args.tone_params is not None or args.glare_params is not None or args.upsample or args.lens_blur:
         linear = develop_linear(film, "srgb", filter=image.get("filter"), white=image.get("white"), device=args.device)
     if args.upsample:  # after the denoiser, before the glare
         guides = [r.features(size, cam, world, device=args.device) for size in ((film.width, film.height), full_size)]
         low_albedo, albedo = (develop_linear(f.albedo, "srgb", filter=image.get("filter"), white=image.get("white"), device=args.device) for f in guides)
         linear = upsample(linear, args.upsample, albedo=albedo, pixels=guides[1].records, low_albedo=low_albedo, low_pixels=guides[0].records, device=args.device,
                           **args.upsample_params)
+    if args.lens_blur:  # after the filters that read the guides, before the glare and the tone curve; the full-size records
+        radius = {} if args.lens_blur_radius is None else {"max_radius": args.lens_blur_radius}
+        linear = lens_blur(linear, r.features(full_size, cam, world, device=args.device).records, device=args.device, camera=lens_cam, **radius)
     if args.glare_params is not None:  # before the statistics of an automatic exposure, which tonemap takes
         linear = glare(linear, device=args.device, **args.glare_params)
-    if args.tone_params is not None or args.denoise or args.despeckle_params is not None or args.glare_params is not None or args.upsample:
+    if args.tone_params is not None or args.denoise or args.despeckle_params is not None or args.glare_params is not None or args.upsample or args.lens_blur:
         rgb = tonemap(linear, args.tone_params, device=args.device)
     else:
         rgb = develop(film, filter=image.get("filter"), white=image.get("white"), device=args.device)

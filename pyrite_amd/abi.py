@@ -494,6 +494,14 @@ class PyrDespeckleParams(C.Structure):
     _fields_ = [("radius", C.c_uint32), ("k", C.c_float), ("relative", C.c_float), ("floor", C.c_float), ("flags", C.c_uint32), ("reserved", C.c_uint32 * 3)]
 
 
+PYR_LENS_BLUR_MAX_RADIUS, PYR_LENS_BLUR_MOST_RADIUS = 8, 16
+
+
+class PyrLensBlurParams(C.Structure):
+    _fields_ = [("focus_distance", C.c_float), ("aperture", C.c_float), ("view_plane", C.c_float), ("max_radius", C.c_uint32), ("depth_tolerance", C.c_float),
+                ("reserved", C.c_uint32 * 3)]
+
+
 PyrProgressFn = C.CFUNCTYPE(None, C.c_void_p, C.c_uint8, C.c_char_p)
 PyrPreviewFn = C.CFUNCTYPE(None, C.c_void_p, C.POINTER(C.c_uint8), C.c_uint32, C.c_uint32, C.c_uint32)
 
@@ -627,6 +635,9 @@ ENTRY_POINTS = {
         C.c_int,
         [C.c_void_p, C.POINTER(PyrDevelopParams), C.POINTER(PyrDespeckleParams), C.POINTER(PyrFeatureParams), C.POINTER(PyrDenoiseParams)] + [C.c_void_p] * 4,
     ),
+    "pyr_image_lens_blur": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PyrLensBlurParams), C.c_void_p, C.c_int]),
+    "pyr_image_lens_blur_device": (C.c_int, [C.c_void_p, C.c_void_p, C.c_uint32, C.c_uint32, C.POINTER(PyrLensBlurParams), C.c_void_p, C.c_int, C.c_void_p]),
+    "pyr_session_lens_blurred": (C.c_int, [C.c_void_p, C.POINTER(PyrDevelopParams), C.POINTER(PyrFeatureParams), C.POINTER(PyrLensBlurParams), C.c_void_p]),
 }
 
 

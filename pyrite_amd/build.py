@@ -10,9 +10,9 @@ import sys
 CSRC = os.path.join(os.path.dirname(os.path.abspath(__file__)), "csrc")
 OUT = os.path.join(CSRC, "libpyrite_gpu.so")
 KERNELS = os.path.join(CSRC, "kernels")  # the units that instantiate the kernels of kernels.hip
-KERNEL_UNITS = ["main.hip", "interp.hip", "product.hip", "wide.hip", "film.hip", "features.hip", "features_wide.hip", "tone.hip", "denoise.hip", "build.hip", "refit.hip", "pose.hip", "motion.hip", "reproject.hip", "motion_blur.hip", "temporal.hip", "glare.hip", "upsample.hip", "despeckle.hip"]
+KERNEL_UNITS = ["main.hip", "interp.hip", "product.hip", "wide.hip", "film.hip", "features.hip", "features_wide.hip", "tone.hip", "denoise.hip", "build.hip", "refit.hip", "pose.hip", "motion.hip", "reproject.hip", "motion_blur.hip", "temporal.hip", "glare.hip", "upsample.hip", "despeckle.hip", "lens_blur.hip"]
 PROFILE_UNIT = "profile.hip"  # -DPYR_PHASE_PROFILE builds: main, interp and product in one unit, no wide build
-PLAIN_UNITS = ["film.hip", "features.hip", "features_wide.hip", "tone.hip", "denoise.hip", "build.hip", "refit.hip", "pose.hip", "motion.hip", "reproject.hip", "motion_blur.hip", "temporal.hip", "glare.hip", "upsample.hip", "despeckle.hip"]  # units without phase counters: every build has them
+PLAIN_UNITS = ["film.hip", "features.hip", "features_wide.hip", "tone.hip", "denoise.hip", "build.hip", "refit.hip", "pose.hip", "motion.hip", "reproject.hip", "motion_blur.hip", "temporal.hip", "glare.hip", "upsample.hip", "despeckle.hip", "lens_blur.hip"]  # units without phase counters: every build has them
 SOURCES = ["api.cpp", "live_scene.cpp", "session.cpp", "image_ops.cpp", "multi.cpp", "bvh.cpp", "bvh_device.cpp", "program_regs.cpp"]
 HEADERS = ["kernels.hip", "bvh.h", "bvh_level.h", "bvh_device.h", "device_scene.h", "api_internal.h", "scene_internal.h", "image_internal.h", "exact_math.h", "pose_rules.h", "program_regs.h", os.path.join("..", "..", "include", "pyrite_gpu.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
@@ -97,7 +97,7 @@ def build_host(force=False, verbose=False):
 
 def compile_library(out, extra_flags=(), verbose=False):
     """The sources -> objects in parallel -> one shared library. The kernels of kernels.hip are instantiated by four units, and kernels/film.hip holds the session's film kernels, kernels/tone.hip
-    the linear images and their tone mapping, kernels/denoise.hip the cross filter of two half images and kernels/features.hip (+ features_wide.hip) the feature pass, kernels/motion.hip the motion pass and kernels/reproject.hip the accumulation over frames, kernels/motion_blur.hip the motion blur along the records, kernels/temporal.hip the temporal resolve, kernels/glare.hip the glare, kernels/upsample.hip the guided upsampling, kernels/despeckle.hip the firefly clamp (kernels/main.hip: everything but
+    the linear images and their tone mapping, kernels/denoise.hip the cross filter of two half images and kernels/features.hip (+ features_wide.hip) the feature pass, kernels/motion.hip the motion pass and kernels/reproject.hip the accumulation over frames, kernels/motion_blur.hip the motion blur along the records, kernels/temporal.hip the temporal resolve, kernels/glare.hip the glare, kernels/upsample.hip the guided upsampling, kernels/despeckle.hip the firefly clamp, kernels/lens_blur.hip the lens blur over the feature records (kernels/main.hip: everything but
     the interpreter builds of the stage scheduler; interp.hip: only those, the heaviest kernels; product.hip: their PRODUCT forms;
     wide.hip: the wide interpreter build, for programs that need more registers than the in-register file) so that the parts build
     side by side: 120 s -> ~50 s. -DPYR_PHASE_PROFILE builds keep one translation unit (their device-side counters are one variable)

@@ -479,6 +479,18 @@ struct DespeckleLaunch {
 };
 int launch_despeckle(const DespeckleLaunch& launch, void* stream);
 
+// kernels/lens_blur.hip: lens blur over the feature records (pyrite_gpu.h "lens blur over the feature records", DESIGN.md section
+// 9o). One launch on `stream`, no working memory.
+struct LensBlurLaunch {
+    const float* image;            // device, height * width * 3 floats
+    const PyrFeaturePixel* pixels; // device, height * width records, 16-byte aligned
+    uint32_t width, height;
+    float focus_distance, aperture, view_plane, depth_tolerance;
+    uint32_t max_radius; // 1..PYR_LENS_BLUR_MOST_RADIUS
+    float* out;          // device, height * width * 3 floats; overlaps no input
+};
+int launch_lens_blur(const LensBlurLaunch& launch, void* stream);
+
 // launchers (kernels/main.hip)
 // wide_vm: the scene has a program that only the wide interpreter build (kernels/wide.hip) holds
 int launch_render(const DevScene& scene, const RenderLaunch& launch, bool with_counters, void* stream, int num_cus, bool wide_vm = false);

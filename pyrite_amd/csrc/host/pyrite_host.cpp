@@ -1617,6 +1617,35 @@ std::vector<float> Session::motion_blurred(const Camera& previous_camera, const 
     return out;
 }
 
+// ---- lens blur over the feature records ----------------------------------------------------------------------------------------
+PyrLensBlurParams lens_blur_params(float focus_distance, float aperture, float view_plane, uint32_t max_radius, float depth_tolerance) {
+    return PyrLensBlurParams{focus_distance, aperture, view_plane, max_radius, depth_tolerance, {0u, 0u, 0u}};
+}
+PyrLensBlurParams lens_blur_params(const Camera& camera, uint32_t max_radius, float depth_tolerance) {
+    return lens_blur_params(camera.c.focus_distance, camera.c.aperture, camera.c.view_plane, max_radius, depth_tolerance);
+}
+std::vector<float> lens_blur(const std::vector<float>& image, const std::vector<PyrFeaturePixel>& pixels, uint32_t width, uint32_t height, const PyrLensBlurParams& params,
+                             int device) {
+    const size_t count = (size_t)width * height;
+    if (image.size() != count * 3 || pixels.size() != count) throw ProjectError("lens_blur: buffer size does not match the image size");
+    std::vector<float> out(count * 3, 0.0f);
+    check_status(pyr_image_lens_blur(image.data(), pixels.data(), width, height, &params, out.data(), device));
+    return out;
+}
+std::vector<float> Session::lens_blurred(const PyrLensBlurParams& params, uint32_t grid, float step_size, const std::optional<Expression>& filter,
+                                         const std::optional<Expression>& white) {
+    const DevelopSetup setup(shape_, filter, white, step_size);
+    const PyrFeatureParams fp{grid, 1u, {0u, 0u}};
+    std::vector<float> out((size_t)width_ * height_ * 3, 0.0f);
+    check_status(pyr_session_lens_blurred(handle_, &setup.p, &fp, &params, out.data()));
+    return out;
+}
+std::string lens_blur_flag_problem(bool lens_blur, const std::optional<long>& lens_blur_radius) {
+    if (!lens_blur) return lens_blur_radius ? "--lens-blur-radius needs --lens-blur" : "";
+    if (lens_blur_radius && (*lens_blur_radius < 1 || *lens_blur_radius > (long)PYR_LENS_BLUR_MOST_RADIUS)) return "--lens-blur-radius must be 1 to " + std::to_string(PYR_LENS_BLUR_MOST_RADIUS);
+    return "";
+}
+
 // ---- glare ---------------------------------------------------------------------------------------------------------------------
 PyrGlareParams glare_params(float strength, uint32_t levels, float threshold, float falloff) { return PyrGlareParams{strength, levels, threshold, falloff, {0u, 0u, 0u, 0u}}; }
 std::vector<float> glare(const std::vector<float>& image, uint32_t width, uint32_t height, const PyrGlareParams& params, int device) {

@@ -6,7 +6,7 @@
 //   pyrite_host_tool render-project <project.lua> <texel dir | -> <seed> <out.png> [film.bin]   what `pyrite project.lua` does (main.rs:46-330)
 //                                   [--size WxH] [--spp N] [--features PREFIX] [--features-grid N] [--hdr PATH] [--exposure EV|auto] [--tone clip|reinhard]
 //                                   [--despeckle [K]] [--despeckle-radius R] [--upsample N] [--upsample-radius R] [--glare [STRENGTH]] [--glare-levels N] [--glare-threshold T]
-//                                   [--build host|device] and the progressive flags of python -m pyrite_amd
+//                                   [--lens-blur] [--lens-blur-radius R] [--build host|device] and the progressive flags of python -m pyrite_amd
 //   pyrite_host_tool encode-features <records.bin> <normal.rgb> <depth.rgb>    PyrFeaturePixel[n] -> the 8-bit normal and depth images, raw RGB (no GPU)
 //   pyrite_host_tool intersect <scene> <data_dir> <rays.f32> <hits.bin>       World::intersect for a ray batch ([n][6] f32 -> PyrHit[n])
 //   pyrite_host_tool render <scene> <data_dir> <w> <h> <spp> <seed> <film.bin> [out.png]
@@ -242,7 +242,7 @@ int main(int argc, char** argv) {
             write_dump(argv[4], flat, loaded.project);
             return 0;
         }
-        if (argc >= 6 && std::string(argv[1]) == "render-project") { // render-project <project.lua> <texel dir | -> <seed> <out.png> [film.bin] [--pass-samples N] [--preview PATH] [--preview-every SECONDS] [--noise] [--despeckle [K]] [--despeckle-radius R] [--denoise] [--denoise-radius N] [--upsample N] [--upsample-radius R] [--glare [STRENGTH]] [--glare-levels N] [--glare-threshold T] [--build host|device]
+        if (argc >= 6 && std::string(argv[1]) == "render-project") { // render-project <project.lua> <texel dir | -> <seed> <out.png> [film.bin] [--pass-samples N] [--preview PATH] [--preview-every SECONDS] [--noise] [--despeckle [K]] [--despeckle-radius R] [--denoise] [--denoise-radius N] [--upsample N] [--upsample-radius R] [--glare [STRENGTH]] [--glare-levels N] [--glare-threshold T] [--lens-blur] [--lens-blur-radius R] [--build host|device]
             // the flags of python -m pyrite_amd: a progressive session with previews (main.rs:261-299) instead of one blocking call
             std::optional<long> pass_samples;
             std::string preview_path, film_path;
@@ -259,6 +259,8 @@ int main(int argc, char** argv) {
             std::optional<std::string> glare_strength; // --glare [STRENGTH]: the next argument unless it is a flag, as argparse's nargs="?" reads it (a film path goes before it)
             std::optional<long> glare_levels;
             std::optional<double> glare_threshold;
+            bool lens_blur_flag = false; // --lens-blur: the frame through a pinhole, the project camera's lens applied by the filter over the feature records
+            std::optional<long> lens_blur_radius;
             std::optional<std::string> build_name; // --build host|device: who builds the BVH; given, the stage times go to stderr
             for (int i = 6; i < argc; ++i) {
                 const std::string a = argv[i];
@@ -302,6 +304,10 @@ int main(int argc, char** argv) {
                     glare_levels = std::strtol(value(), nullptr, 10);
                 else if (a == "--glare-threshold")
                     glare_threshold = std::strtod(value(), nullptr);
+                else if (a == "--lens-blur")
+                    lens_blur_flag = true;
+                else if (a == "--lens-blur-radius")
+                    lens_blur_radius = std::strtol(value(), nullptr, 10);
                 else if (a == "--build")
                     build_name = value();
                 else if (a == "--size")
@@ -320,6 +326,7 @@ int main(int argc, char** argv) {
             if (problem.empty()) problem = denoise_flag_problem(denoise_flag, denoise_radius);
             if (problem.empty()) problem = upsample_flag_problem(upsample_scale, upsample_radius);
             if (problem.empty()) problem = glare_flag_problem(glare_strength, glare_levels, glare_threshold);
+            if (problem.empty()) problem = lens_blur_flag_problem(lens_blur_flag, lens_blur_radius);
             if (problem.empty() && build_name && *build_name != "host" && *build_name != "device") problem = "--build takes host or device";
             if (!problem.empty()) {
                 std::fprintf(stderr, "error: %s\n", problem.c_str());
@@ -348,7 +355,9 @@ int main(int argc, char** argv) {
                 loaded.project.image.width = full_width / (uint32_t)*upsample_scale, loaded.project.image.height = full_height / (uint32_t)*upsample_scale;
             const Project& project = loaded.project;
             std::unique_ptr<World> world = World::from_project(project.world, loaded.base_dir);
-            const Camera cam = Camera::from_project(project.camera);
+            const Camera lens_cam = Camera::from_project(project.camera);
+            Camera cam = lens_cam;
+            if (lens_blur_flag) cam.c.aperture = 0.0f; // the render, its guides and every filter before the lens see a pinhole
             Renderer r = Renderer::from_project(project.renderer);
             r.seed = std::strtoull(argv[4], nullptr, 10);
             Film film = r.new_film(project.image.width, project.image.height);
@@ -396,16 +405,19 @@ int main(int argc, char** argv) {
                 r.render(film, cam, *world);
             }
             std::printf("Saving final result...\n"); // main.rs:313
-            if (!denoise_flag && !despeckle_p && (hdr || tone || glare_p || upsample_p)) linear = develop_linear(film, PYR_LINEAR_SRGB, project.image.filter, project.image.white);
+            if (!denoise_flag && !despeckle_p && (hdr || tone || glare_p || upsample_p || lens_blur_flag)) linear = develop_linear(film, PYR_LINEAR_SRGB, project.image.filter, project.image.white);
             if (upsample_p) { // after the denoiser, before the glare
                 const Features low_guides = r.features(film.width, film.height, cam, *world), guides = r.features(full_width, full_height, cam, *world);
                 const std::vector<float> low_albedo = develop_linear(low_guides.albedo, PYR_LINEAR_SRGB, project.image.filter, project.image.white);
                 const std::vector<float> albedo = develop_linear(guides.albedo, PYR_LINEAR_SRGB, project.image.filter, project.image.white);
                 linear = upsample(linear, film.width, film.height, (uint32_t)*upsample_scale, *upsample_p, &albedo, &guides.pixels, &low_albedo, &low_guides.pixels);
             }
+            if (lens_blur_flag) // after the filters that read the guides, before the glare and the tone curve; the full-size records
+                linear = lens_blur(linear, r.features(full_width, full_height, cam, *world).pixels, full_width, full_height,
+                                   lens_blur_params(lens_cam, lens_blur_radius ? (uint32_t)*lens_blur_radius : PYR_LENS_BLUR_MAX_RADIUS));
             if (glare_p) linear = glare(linear, full_width, full_height, *glare_p); // before the statistics of an automatic exposure, which tonemap takes
             save_png(argv[5],
-                     tone || denoise_flag || despeckle_p || glare_p || upsample_p ? tonemap(linear, full_width, full_height, tone ? *tone : tone_params(PYR_TONE_CLIP, 1.0f))
+                     tone || denoise_flag || despeckle_p || glare_p || upsample_p || lens_blur_flag ? tonemap(linear, full_width, full_height, tone ? *tone : tone_params(PYR_TONE_CLIP, 1.0f))
                                                                     : film.develop(project.image.filter, project.image.white),
                      full_width, full_height);
             if (hdr) {

@@ -20,6 +20,7 @@ bool tone_needs_stats(const PyrToneParams* t);
 int check_denoise_params(const PyrDenoiseParams* p);
 int check_motion_blur_params(const PyrMotionBlurParams* p, const char* what); // `what` names the argument: params, blur_params
 int check_glare_params(const PyrGlareParams* p, const char* what);            // likewise: params, glare_params
+int check_lens_blur_params(const PyrLensBlurParams* p, const char* what);     // likewise: params, blur_params
 int check_despeckle_params(const PyrDespeckleParams* p, const char* what);    // likewise: params, despeckle_params
 int check_upsample_params(const PyrUpsampleParams* p, const char* what, bool with_albedo); // likewise: params, upsample_params; the floor and the gain only with the albedo pair
 int check_upsample_scale(uint32_t scale);
@@ -44,6 +45,10 @@ int enqueue_motion_blur(const float* image, const PyrMotionPixel* motion, uint32
 // The glare of `image` into `out` (kernels/glare.hip): both on the current device, the pyramid's levels allocated and freed in
 // stream order on `stream`.
 int enqueue_glare(const float* image, uint32_t width, uint32_t height, const PyrGlareParams* p, float* out, hipStream_t stream);
+
+// The lens blur of `image` over the feature records `pixels` into `out` (kernels/lens_blur.hip): every buffer on the current
+// device, one launch on `stream`, no working memory.
+int enqueue_lens_blur(const float* image, const PyrFeaturePixel* pixels, uint32_t width, uint32_t height, const PyrLensBlurParams* p, float* out, hipStream_t stream);
 
 // The upsampling of `low` to scale times its size into `out` (kernels/upsample.hip): every buffer on the current device, one
 // launch on `stream`. Either pair is null or given whole.

@@ -1,7 +1,8 @@
 // image_ops.cpp -- the entry points of include/pyrite_gpu.h that take a device number and never see a scene: a film developed to
 // an 8-bit or a linear image, an image's luminance statistics, its tone mapping, the denoising of two half images, the
 // accumulation of linear images over frames along their motion records (plain, and as the temporal resolve), the motion blur of
-// one along them, the glare of one, the guided upsampling of one, the firefly clamp of two halves. Every operation is stated in three parts, each once ("adding an image entry"):
+// one along them, the glare of one, the guided upsampling of one, the firefly clamp of two halves, the lens blur of one over its
+// feature records. Every operation is stated in three parts, each once ("adding an image entry"):
 //   its checks, composed from the pieces below in the order that entry refuses in (tests/golden/image_refusals.json pins it);
 //   one enqueue_... function: device pointers, the public parameter block, a stream -- the one place its launch record is built;
 //   two entries: the _device form is checks, use_device, enqueue; the host form is checks, use_device and Staging::finish, which
@@ -172,6 +173,19 @@ int check_motion_blur_params(const PyrMotionBlurParams* p, const char* what) {
     return PYR_OK;
 }
 
+// What the three lens blur entries refuse of their parameters before a device is looked for (`what`: params or blur_params).
+int check_lens_blur_params(const PyrLensBlurParams* p, const char* what) {
+    const std::string name = std::string(what) + "->";
+    if (!p) return fail(PYR_ERR_INVALID_ARGUMENT, std::string("null argument: ") + what);
+    if (!(p->focus_distance > 0.0f) || !std::isfinite(p->focus_distance)) return fail(PYR_ERR_INVALID_ARGUMENT, name + "focus_distance must be finite and positive");
+    if (!(p->aperture >= 0.0f) || !std::isfinite(p->aperture)) return fail(PYR_ERR_INVALID_ARGUMENT, name + "aperture must be finite and not negative");
+    if (!(p->view_plane > 0.0f) || !std::isfinite(p->view_plane)) return fail(PYR_ERR_INVALID_ARGUMENT, name + "view_plane must be finite and positive");
+    if (p->max_radius < 1 || p->max_radius > PYR_LENS_BLUR_MOST_RADIUS) return fail(PYR_ERR_INVALID_ARGUMENT, name + "max_radius must be 1..16");
+    if (!(p->depth_tolerance >= 0.0f && p->depth_tolerance < 1.0f)) return fail(PYR_ERR_INVALID_ARGUMENT, name + "depth_tolerance must be in [0, 1)");
+    if (p->reserved[0] != 0 || p->reserved[1] != 0 || p->reserved[2] != 0) return fail(PYR_ERR_INVALID_ARGUMENT, name + "reserved must be 0");
+    return PYR_OK;
+}
+
 // What the three glare entries refuse of their parameters before a device is looked for (`what`: params or glare_params).
 int check_glare_params(const PyrGlareParams* p, const char* what) {
     const std::string name = std::string(what) + "->";
@@ -260,6 +274,13 @@ int enqueue_glare(const float* image, uint32_t width, uint32_t height, const Pyr
         const GlareLaunch L{image, width, height, p->strength, p->threshold, p->falloff, p->levels, (float*)work, out};
         return launch_glare(L, stream);
     });
+}
+
+// The lens blur of `image` over the records `pixels` into `out` (kernels/lens_blur.hip): every buffer on the current device, one
+// launch on `stream`, no working memory.
+int enqueue_lens_blur(const float* image, const PyrFeaturePixel* pixels, uint32_t width, uint32_t height, const PyrLensBlurParams* p, float* out, hipStream_t stream) {
+    const LensBlurLaunch L{image, pixels, width, height, p->focus_distance, p->aperture, p->view_plane, p->depth_tolerance, p->max_radius, out};
+    return launch_lens_blur(L, stream);
 }
 
 // The upsampling of `low` to scale times its size into `out` (kernels/upsample.hip): every buffer on the current device, one launch
@@ -408,6 +429,11 @@ int check_temporal_args(const void* current, const void* motion, const void* his
 int check_motion_blur_args(const void* image, const void* motion, uint32_t width, uint32_t height, const PyrMotionBlurParams* p, const void* out) {
     if (int bad = check_given({{image, 0, "image"}, {motion, 0, "motion"}, {out, 0, "out"}})) return bad;
     if (int bad = check_motion_blur_params(p, "params")) return bad;
+    return check_extent(width, height);
+}
+int check_lens_blur_args(const void* image, const void* pixels, uint32_t width, uint32_t height, const PyrLensBlurParams* p, const void* out) {
+    if (int bad = check_given({{image, 0, "image"}, {pixels, 0, "pixels"}, {out, 0, "out"}})) return bad;
+    if (int bad = check_lens_blur_params(p, "params")) return bad;
     return check_extent(width, height);
 }
 
@@ -674,6 +700,24 @@ int pyr_image_motion_blur(const float* image, const PyrMotionPixel* motion, uint
     const size_t count = (size_t)width * height, image_bytes = count * 3 * sizeof(float);
     Staging S;
     return S.finish(enqueue_motion_blur, S.in(image, image_bytes), S.in(motion, count * sizeof(PyrMotionPixel)), width, height, params, S.out(out, image_bytes), nullptr);
+}
+
+int pyr_image_lens_blur_device(const float* image_device, const PyrFeaturePixel* pixels_device, uint32_t width, uint32_t height, const PyrLensBlurParams* params,
+                               float* out_device, int device, void* hip_stream) {
+    int rc = check_lens_blur_args(image_device, pixels_device, width, height, params, out_device);
+    if (rc != PYR_OK) return rc;
+    if (((uintptr_t)pixels_device & 15u) != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "pixels_device must be 16-byte aligned"); // records are read as 16-byte vectors
+    const uint64_t pixels = (uint64_t)width * height;
+    rc = check_overlap({{out_device, pixels * 12, "out_device"}}, {{image_device, pixels * 12, "image_device"}, {pixels_device, pixels * sizeof(PyrFeaturePixel), "pixels_device"}});
+    if (int bad = use_device(rc, device)) return bad;
+    return enqueue_lens_blur(image_device, pixels_device, width, height, params, out_device, (hipStream_t)hip_stream);
+}
+
+int pyr_image_lens_blur(const float* image, const PyrFeaturePixel* pixels, uint32_t width, uint32_t height, const PyrLensBlurParams* params, float* out, int device) {
+    if (int bad = use_device(check_lens_blur_args(image, pixels, width, height, params, out), device)) return bad;
+    const size_t count = (size_t)width * height, image_bytes = count * 3 * sizeof(float);
+    Staging S;
+    return S.finish(enqueue_lens_blur, S.in(image, image_bytes), S.in(pixels, count * sizeof(PyrFeaturePixel)), width, height, params, S.out(out, image_bytes), nullptr);
 }
 
 int pyr_image_glare_device(const float* image_device, uint32_t width, uint32_t height, const PyrGlareParams* params, float* out_device, int device, void* hip_stream) {

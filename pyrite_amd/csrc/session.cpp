@@ -444,6 +444,30 @@ int pyr_session_glared(PyrSession* session, const PyrDevelopParams* develop_para
     });
 }
 
+int pyr_session_lens_blurred(PyrSession* session, const PyrDevelopParams* develop_params, const PyrFeatureParams* feature_params, const PyrLensBlurParams* blur_params,
+                             float* out) {
+    if (!session) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: session");
+    if (!develop_params) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: develop_params");
+    if (!feature_params) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: feature_params");
+    if (!out) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument: out");
+    int rc = check_lens_blur_params(blur_params, "blur_params"); // what needs no session comes first: before a device is looked for
+    if (rc != PYR_OK || (rc = check_feature_args(session, "session", nullptr, false, &session->film, feature_params, nullptr, out)) != PYR_OK) return rc;
+    if ((rc = check_linear_args(&session->film, session, develop_params, PYR_LINEAR_SRGB, out)) != PYR_OK || (rc = session_ready(session)) != PYR_OK) return rc;
+    PyrSession* s = session;
+    const size_t pixels = (size_t)s->film.width * s->film.height, image_bytes = pixels * 3 * sizeof(float);
+    DeviceBuffer records_dev, out_dev;
+    if ((rc = records_dev.alloc(pixels * sizeof(PyrFeaturePixel))) != PYR_OK || (rc = out_dev.alloc(image_bytes)) != PYR_OK) return rc;
+    return enqueue_then_sync(s, [&]() -> int {
+        int rc = session_linear(s, develop_params, PYR_LINEAR_SRGB);
+        if (rc != PYR_OK) return rc;
+        if ((rc = enqueue_features(s->scene, &s->camera, &s->film, feature_params, nullptr, (PyrFeaturePixel*)records_dev.ptr, s->stream)) != PYR_OK) return rc;
+        rc = enqueue_lens_blur((const float*)s->linear.ptr, (const PyrFeaturePixel*)records_dev.ptr, s->film.width, s->film.height, blur_params, (float*)out_dev.ptr, s->stream);
+        if (rc != PYR_OK) return rc;
+        if (hipMemcpyAsync(out, out_dev.ptr, image_bytes, hipMemcpyDeviceToHost, s->stream) != hipSuccess) return fail(PYR_ERR_DEVICE, "hipMemcpyAsync of the blurred image failed");
+        return PYR_OK;
+    });
+}
+
 int pyr_session_linear(PyrSession* session, const PyrDevelopParams* develop_params, uint32_t space, float* out) {
     if (!session) return fail(PYR_ERR_INVALID_ARGUMENT, "null argument");
     int rc = check_linear_args(&session->film, session, develop_params, space, out);

@@ -324,6 +324,45 @@ def motion_blur(image, motion, device=0, **params):
     return out
 
 
+def lens_blur_params(camera=None, focus_distance=None, aperture=None, view_plane=None, max_radius=abi.PYR_LENS_BLUR_MAX_RADIUS,
+                     depth_tolerance=abi.PYR_REPROJECT_DEPTH_TOLERANCE):
+    """abi.PyrLensBlurParams: a thin lens of `aperture` (the lens disc's radius squared, as the project file has it) focused at
+    `focus_distance` before a camera of `view_plane`; circles of confusion are clamped to `max_radius` pixels, and depths within
+    `depth_tolerance` (relative) count as one layer. With `camera` (a renderer.Camera or an abi.PyrCamera) the three lens numbers
+    are read from it, each unless given; without one all three must be given."""
+    c = getattr(camera, "c", camera)
+    given = {"focus_distance": focus_distance, "aperture": aperture, "view_plane": view_plane}
+    for name, value in given.items():
+        if value is None:
+            if c is None:
+                raise ValueError("lens_blur_params: %s is needed without a camera" % name)
+            given[name] = getattr(c, name)
+    return abi.PyrLensBlurParams(float(given["focus_distance"]), float(given["aperture"]), float(given["view_plane"]), int(max_radius), float(depth_tolerance))
+
+
+def lens_blur(image, pixels, device=0, **params):
+    """float32 [height, width, 3]: the linear image `image`, rendered through a pinhole, blurred as a thin lens would blur it
+    (pyr_image_lens_blur; include/pyrite_gpu.h has the arithmetic). `pixels`: the feature records of the same camera at the same
+    size (Features.records). `params`: lens_blur_params. Pixels in focus that no neighbour's blur reaches keep their bits."""
+    image = _linear_image(image)
+    h, w, _ = image.shape
+    pixels = np.ascontiguousarray(pixels)
+    assert pixels.nbytes == C.sizeof(abi.PyrFeaturePixel) * h * w
+    p = lens_blur_params(**params)
+    out = np.zeros(image.shape, dtype=np.float32)
+    check(lib().pyr_image_lens_blur(image.ctypes.data, pixels.ctypes.data, w, h, C.byref(p), out.ctypes.data, int(device)))
+    return out
+
+
+def lens_blur_flag_problem(lens_blur, lens_blur_radius):
+    """What is wrong with --lens-blur / --lens-blur-radius R, in the words pyrite_host_tool uses too, or None."""
+    if not lens_blur:
+        return "--lens-blur-radius needs --lens-blur" if lens_blur_radius is not None else None
+    if lens_blur_radius is not None and not 1 <= lens_blur_radius <= abi.PYR_LENS_BLUR_MOST_RADIUS:
+        return "--lens-blur-radius must be 1 to %d" % abi.PYR_LENS_BLUR_MOST_RADIUS
+    return None
+
+
 def glare_params(strength=abi.PYR_GLARE_STRENGTH, levels=abi.PYR_GLARE_LEVELS, threshold=abi.PYR_GLARE_THRESHOLD, falloff=abi.PYR_GLARE_FALLOFF):
     """abi.PyrGlareParams: `strength` of every pixel's light (of what lies above the luminance `threshold`, when that is not 0) is
     spread over `levels` blurs, each twice as wide as the one before and weighted `falloff` times as much."""

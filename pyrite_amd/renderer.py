@@ -559,6 +559,20 @@ class Session:
         del keep
         return out
 
+    def lens_blurred(self, step=2.0, filter=None, white=None, grid=1, **params):
+        """float32 [height, width, 3]: the film as it stands developed to linear sRGB and blurred by a thin lens over the records of
+        the feature pass (`grid` x `grid` sub-samples), all on the session's device (pyr_session_lens_blurred; develop.lens_blur of
+        linear() and features(grid).records gives the same floats). `params`: develop.lens_blur_params -- the lens is theirs, not
+        the session camera's, which is meant to have rendered with aperture 0. The session's film is not touched."""
+        from .develop import develop_params, lens_blur_params
+
+        p, keep = develop_params(self._film, step, filter, white)
+        fp, bp = abi.PyrFeatureParams(int(grid), 1), lens_blur_params(**params)
+        out = np.zeros((self.height, self.width, 3), dtype=np.float32)
+        check(lib().pyr_session_lens_blurred(self.handle, C.byref(p), C.byref(fp), C.byref(bp), out.ctypes.data))
+        del keep
+        return out
+
     def glared(self, step=2.0, filter=None, white=None, **params):
         """float32 [height, width, 3]: the film as it stands developed to linear sRGB with the glare added, all on the session's
         device (pyr_session_glared; develop.glare of linear() gives the same floats). `params`: develop.glare_params. The session's
