@@ -613,6 +613,67 @@ typedef struct PyrSkinUpdate {
 } PyrSkinUpdate;
 int pyr_scene_skin(PyrScene*, const PyrSkinUpdate*, void* hip_stream);
 
+/* ---- morph targets for a live scene's meshes. A skin bends a mesh over a skeleton; a face that changes expression, a muscle that
+ * bulges, a corrective shape at an elbow or a cloth cache played back between key shapes is a weighted sum of per-vertex deltas.
+ * pyr_scene_set_morphs takes the deltas once, 36 bytes per target and triangle (72 with normal deltas); pyr_scene_morph takes one
+ * weight per target per frame (and, if wanted, joint matrices and the objects' poses), computes every triangle from the rest pose on
+ * the device and runs the refit or the rebuild of pyr_scene_pose from there.
+ *   A morph belongs to one object of pyr_scene_set_objects and covers all of that object's triangles, in their order; the object's
+ * spheres are not morphed. It has T targets, each a dense array of position deltas dp[t][triangle][vertex][3], and either all of its
+ * targets have normal deltas dn of the same shape or none has. A frame supplies one weight w[t] per target. A target is ACTIVE
+ * when w[t] != 0.0f (both zeros are inactive); an inactive target is skipped and its deltas are not read (adding 0 * d is not a
+ * no-op on bits). A morph with no active target is AT REST: its triangles are the rest arrays bit for bit -- positions, normals
+ * and frames -- decided per morph on the host, as with an identity skin. Otherwise, per vertex, all f32 and unfused, over the
+ * active targets in ascending t:
+ *     positions  p = p + w[t] * dp[t]                                    per component
+ *     normals    (morph with normal deltas) m = n, then m = m + w[t] * dn[t]; s = (m.x*m.x + m.y*m.y) + m.z*m.z;
+ *                n' = normalize(m)                                       (normalize as in pyr_scene_pose)
+ *     frames     (scene that keeps frames) with dot(a,b) = (a0*b0 + a1*b1) + a2*b2, rx = q * ex, ry = q * ey:
+ *                d = dot(rx, n'); x = rx - n'*d per component; x = normalize(x);
+ *                e = dot(ry, n'); f = dot(ry, x); y = (ry - n'*e) - x*f per component; y = normalize(y);
+ *                q' = quat_from_cols(x, y, n')       -- a Gram-Schmidt of the old tangent frame against the new normal
+ * A squared length s that is normalised -- of m, of x, of y -- must lie in [1e-30, 1e30]: a lane with !(s >= 1e-30f && s <= 1e30f)
+ * raises bit 1 of the call's flag word (below). A morph without normal deltas keeps rest's normals and frames bit for bit.
+ *   The morphed vertex then takes what its object already has: the skin rule of pyr_scene_skin if the object has a skin, and the
+ * object's pose on top, each skipped bit for bit under the conventions stated there. The geometry is
+ * P_object(S(M(rest, targets, w), bindings, J)), always from rest, never from the previous frame. Weights may be negative or above
+ * 1 and are not renormalised.
+ *   pyr_scene_set_morphs needs objects to be set. It copies the deltas to the device, in morph order, keeps a device copy of the rest
+ * positions, normals and frames that the morph is written into, and sets every weight to 0; the geometry does not change at this
+ * call. num_morphs == 0 forgets the morphs. Every pyr_scene_set_objects call forgets them, and so does every
+ * pyr_scene_update[_device] that carries an array; pyr_scene_set_skins and pyr_scene_set_morphs each leave the other's state in
+ * place. Refused with PYR_ERR_INVALID_ARGUMENT, in this order, before any device is looked for (pyr_last_error names the
+ * argument): NULL morphs with a non-zero count; a NULL scene; no objects set; a non-zero reserved word; an object index out of
+ * range; an object without triangles; two morphs on one object; num_targets 0 or above 256; NULL position_deltas; a delta that is
+ * not finite. A refused call leaves the previous morphs in place.
+ *   pyr_scene_morph is pyr_scene_skin with a weight table: one call, one morph-pose-and-skin pass, one read-back of the flag word
+ * and one refit or rebuild, with pyr_scene_pose's contract and atomicity. `poses`, `joints` and `weights` may each be NULL: the
+ * scene keeps what it is in. The flag word: bit 0 (a bound beyond 1e15, which a morphed position that is not finite fails too) is
+ * PYR_ERR_UNSUPPORTED with pyr_scene_pose's message; bit 1 alone is PYR_ERR_UNSUPPORTED with a message that names a morphed normal;
+ * either way the scene renders as before, under the weights, joints and poses it was in. Argument checks: pyr_scene_pose's, in its
+ * order, with NULL poses allowed; then no morphs set; joints given on a scene without skins; for joints that are given,
+ * pyr_scene_skin's checks of the table; num_weights that is not the scene's (the morphs' num_targets summed) when weights are
+ * given; a weight that is not finite. pyr_scene_pose and pyr_scene_skin on a scene with morphs keep the weights it is in. */
+typedef struct PyrMorph {
+    uint32_t object;               /* index into the ranges of pyr_scene_set_objects */
+    uint32_t num_targets;          /* 1 .. 256 */
+    const float* position_deltas;  /* HOST, [num_targets][object's num_triangles][3][3] */
+    const float* normal_deltas;    /* HOST, same shape, or NULL: normals and frames stay rest's */
+    uint32_t reserved[4];
+} PyrMorph;
+int pyr_scene_set_morphs(PyrScene*, const PyrMorph* morphs, uint32_t num_morphs);
+typedef struct PyrMorphUpdate {
+    uint32_t mode;               /* PYR_UPDATE_REFIT | PYR_UPDATE_REBUILD */
+    uint32_t num_objects;        /* must equal the scene's */
+    const PyrObjectPose* poses;  /* HOST or NULL: keep */
+    const float* joints;         /* HOST [num_joints][16] or NULL: keep (then num_joints is not read) */
+    uint32_t num_joints;
+    const float* weights;        /* HOST [num_weights], the morphs' targets one after the other in morph order; or NULL: keep */
+    uint32_t num_weights;        /* must equal the scene's when weights is given */
+    uint32_t reserved[4];
+} PyrMorphUpdate;
+int pyr_scene_morph(PyrScene*, const PyrMorphUpdate*, void* hip_stream);
+
 /* Introspection of the kernel a render of `scene` with `params` would run (nothing is launched; only spectrum_samples is read
  * today). Results never depend on it -- every schedule is the same per-sample arithmetic as tracer.rs:208-345 -- but throughput
  * does, and a maintainer wants to see why a scene is slow: */

@@ -307,6 +307,23 @@ class World { // world.rs:31-36
     // joints and poses and a scene it makes later is built for them.
     void skin(const std::map<size_t, std::vector<float>>& joints, const std::map<size_t, ObjectPose>* poses = nullptr, Update mode = Update::Refit, int device = 0,
               void* hip_stream = nullptr);
+    // Gives meshes their morph targets (pyr_scene_set_morphs on every scene of this world): `morphs` maps an object's index in
+    // objects() to its targets -- position deltas [num_targets][T][3][3] for the object's T triangles and, if the normals are to
+    // follow, normal deltas of the same shape (empty: normals and frames stay the rest pose's). Morphs are in the order of their
+    // object indices. Every weight is zero afterwards and the geometry does not change; an empty map forgets the morphs, and so do
+    // set_objects() and an update() that carries arrays. set_skins() and set_morphs() leave each other's state alone.
+    struct Morph {
+        uint32_t num_targets = 0;
+        std::vector<float> position_deltas, normal_deltas;
+    };
+    void set_morphs(const std::map<size_t, Morph>& morphs);
+    // One frame of the morphed meshes of the scene on `device` (pyr_scene_morph): `weights` maps a morphed object's index to one
+    // weight per target; a morph it does not name stays at the weights it is in. Every vertex takes the weighted deltas of the
+    // targets whose weight is not zero, then its skin if its object has one (`joints` as for skin(), nullptr keeps the joints the
+    // world is in), then the object's pose (`poses` as for pose(), nullptr keeps them). Everything is computed from the rest pose
+    // on the GPU. flat() stays the rest pose; the world remembers weights, joints and poses for a scene it makes later.
+    void morph(const std::map<size_t, std::vector<float>>& weights, const std::map<size_t, std::vector<float>>* joints = nullptr,
+               const std::map<size_t, ObjectPose>* poses = nullptr, Update mode = Update::Refit, int device = 0, void* hip_stream = nullptr);
     // pyr_scene_geometry: the geometry of the scene on `device` as it is now (frames empty unless the scene keeps them)
     struct Geometry {
         std::vector<float> positions, normals, frames, spheres;
@@ -328,10 +345,16 @@ class World { // world.rs:31-36
     std::map<size_t, ObjectPose> poses_;            // the poses the scenes are in; identity where absent
     std::map<size_t, Skin> skins_;                  // the bindings (set_skins)
     std::map<size_t, std::vector<float>> joints_;   // the joints the scenes are in; identity where absent
+    std::map<size_t, Morph> morphs_;                // the targets (set_morphs)
+    std::map<size_t, std::vector<float>> weights_;  // the morph weights the scenes are in; zero where absent
     std::vector<PyrObjectPose> pose_records(const std::map<size_t, ObjectPose>& poses) const;
     void pose_scene(PyrScene* handle, const std::map<size_t, ObjectPose>& poses, Update mode, void* hip_stream);
     void set_skins_on(PyrScene* handle, const std::map<size_t, Skin>& skins);
     void skin_scene(PyrScene* handle, const std::map<size_t, std::vector<float>>& joints, const std::map<size_t, ObjectPose>& poses, Update mode, void* hip_stream);
+    std::vector<float> joint_table(const std::map<size_t, std::vector<float>>& joints) const;
+    void set_morphs_on(PyrScene* handle, const std::map<size_t, Morph>& morphs);
+    void morph_scene(PyrScene* handle, const std::map<size_t, std::vector<float>>& weights, const std::map<size_t, std::vector<float>>* joints,
+                     const std::map<size_t, ObjectPose>& poses, Update mode, void* hip_stream);
 };
 
 struct Camera { // cameras.rs:20-27

@@ -340,6 +340,29 @@ class PyrSkinUpdate(C.Structure):
     ]
 
 
+class PyrMorph(C.Structure):
+    _fields_ = [
+        ("object", C.c_uint32),
+        ("num_targets", C.c_uint32),
+        ("position_deltas", C.c_void_p),
+        ("normal_deltas", C.c_void_p),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
+class PyrMorphUpdate(C.Structure):
+    _fields_ = [
+        ("mode", C.c_uint32),
+        ("num_objects", C.c_uint32),
+        ("poses", C.POINTER(PyrObjectPose)),
+        ("joints", C.c_void_p),
+        ("num_joints", C.c_uint32),
+        ("weights", C.c_void_p),
+        ("num_weights", C.c_uint32),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
 class PyrPathInfo(C.Structure):
     _fields_ = [
         ("stage_scheduler", C.c_uint32),
@@ -534,6 +557,8 @@ ENTRY_POINTS = {
     "pyr_scene_geometry": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pyr_scene_set_skins": (C.c_int, [C.c_void_p, C.POINTER(PyrSkin), C.c_uint32]),
     "pyr_scene_skin": (C.c_int, [C.c_void_p, C.POINTER(PyrSkinUpdate), C.c_void_p]),
+    "pyr_scene_set_morphs": (C.c_int, [C.c_void_p, C.POINTER(PyrMorph), C.c_uint32]),
+    "pyr_scene_morph": (C.c_int, [C.c_void_p, C.POINTER(PyrMorphUpdate), C.c_void_p]),
     "pyr_scene_path_info": (C.c_int, [C.c_void_p, C.POINTER(PyrRenderParams), C.POINTER(PyrPathInfo)]),
     "pyr_scene_program_info": (C.c_int, [C.c_void_p, C.POINTER(PyrProgramInfo)]),
     "pyr_program_allocate_registers": (C.c_int, [C.POINTER(PyrInstr), C.POINTER(PyrProgram), C.POINTER(PyrInstr), C.POINTER(PyrProgram)]),

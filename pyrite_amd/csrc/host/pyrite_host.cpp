@@ -1081,7 +1081,13 @@ PyrScene* World::scene(int device, int copy, std::optional<Build> build) {
         for (const FlatScene::Object& o : flat_.objects()) ranges.push_back(o.range);
         check_status(pyr_scene_set_objects(handle, ranges.data(), (uint32_t)ranges.size()));
         if (!skins_.empty()) set_skins_on(handle, skins_);
-        if (!joints_.empty())
+        if (!morphs_.empty()) set_morphs_on(handle, morphs_);
+        bool morphed = false;
+        for (const auto& kv : weights_)
+            for (float w : kv.second) morphed = morphed || w != 0.0f;
+        if (morphed)
+            morph_scene(handle, weights_, skins_.empty() ? nullptr : &joints_, poses_, Update::Rebuild, nullptr);
+        else if (!joints_.empty())
             skin_scene(handle, joints_, poses_, Update::Rebuild, nullptr);
         else if (!poses_.empty())
             pose_scene(handle, poses_, Update::Rebuild, nullptr);
@@ -1109,17 +1115,17 @@ void World::update(const std::vector<float>& positions, const std::vector<float>
     u.spheres = spheres.empty() ? nullptr : spheres.data();
     check_status(pyr_scene_update(handle, &u));
     flat_.move_geometry(positions, normals, frames, spheres);
-    if (u.tri_positions || u.tri_normals || u.tri_frames || u.spheres) poses_.clear(), skins_.clear(), joints_.clear(); // a new geometry, not a pose of the old one: the scene forgot its objects (set_objects names them again)
+    if (u.tri_positions || u.tri_normals || u.tri_frames || u.spheres) poses_.clear(), skins_.clear(), joints_.clear(), morphs_.clear(), weights_.clear(); // a new geometry, not a pose of the old one: the scene forgot its objects (set_objects names them again)
 }
 void World::set_objects() {
-    if ((!poses_.empty() || !joints_.empty()) && !scenes_.empty()) { // every scene of this world is in the same pose: flat() follows the first
+    if ((!poses_.empty() || !joints_.empty() || !weights_.empty()) && !scenes_.empty()) { // every scene of this world is in the same pose: flat() follows the first
         const Geometry g = geometry(scenes_.begin()->first.first);
         flat_.move_geometry(g.positions, g.normals, g.frames, g.spheres);
     }
     std::vector<PyrObjectRange> ranges;
     for (const FlatScene::Object& o : flat_.objects()) ranges.push_back(o.range);
     for (auto& kv : scenes_) check_status(pyr_scene_set_objects(kv.second, ranges.data(), (uint32_t)ranges.size()));
-    poses_.clear(), skins_.clear(), joints_.clear(); // skins hang on objects: pyr_scene_set_objects forgot them
+    poses_.clear(), skins_.clear(), joints_.clear(), morphs_.clear(), weights_.clear(); // skins and morphs hang on objects: pyr_scene_set_objects forgot them
 }
 std::vector<PyrObjectPose> World::pose_records(const std::map<size_t, ObjectPose>& poses) const {
     std::vector<PyrObjectPose> records(flat_.objects().size());
@@ -1167,7 +1173,7 @@ void World::set_skins(const std::map<size_t, Skin>& skins) {
     skins_ = skins;
     joints_.clear();
 }
-void World::skin_scene(PyrScene* handle, const std::map<size_t, std::vector<float>>& joints, const std::map<size_t, ObjectPose>& poses, Update mode, void* hip_stream) {
+std::vector<float> World::joint_table(const std::map<size_t, std::vector<float>>& joints) const {
     static const float identity[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     std::vector<float> table;
     for (const auto& kv : skins_) {
@@ -1177,6 +1183,10 @@ void World::skin_scene(PyrScene* handle, const std::map<size_t, std::vector<floa
         else
             for (uint32_t j = 0; j < kv.second.num_joints; ++j) table.insert(table.end(), identity, identity + 16);
     }
+    return table;
+}
+void World::skin_scene(PyrScene* handle, const std::map<size_t, std::vector<float>>& joints, const std::map<size_t, ObjectPose>& poses, Update mode, void* hip_stream) {
+    const std::vector<float> table = joint_table(joints);
     const std::vector<PyrObjectPose> records = pose_records(poses);
     PyrSkinUpdate u{};
     u.mode = mode == Update::Rebuild ? PYR_UPDATE_REBUILD : PYR_UPDATE_REFIT;
@@ -1198,6 +1208,77 @@ void World::skin(const std::map<size_t, std::vector<float>>& joints, const std::
     const std::map<size_t, ObjectPose> named = poses ? *poses : poses_;
     skin_scene(scene(device), joints, named, mode, hip_stream);
     poses_ = named, joints_ = joints;
+}
+void World::set_morphs_on(PyrScene* handle, const std::map<size_t, Morph>& morphs) {
+    std::vector<PyrMorph> records;
+    for (const auto& kv : morphs) {
+        PyrMorph m{};
+        m.object = (uint32_t)kv.first, m.num_targets = kv.second.num_targets;
+        m.position_deltas = kv.second.position_deltas.data();
+        m.normal_deltas = kv.second.normal_deltas.empty() ? nullptr : kv.second.normal_deltas.data();
+        records.push_back(m);
+    }
+    check_status(pyr_scene_set_morphs(handle, records.data(), (uint32_t)records.size()));
+}
+void World::set_morphs(const std::map<size_t, Morph>& morphs) {
+    for (const auto& kv : morphs) {
+        if (kv.first >= flat_.objects().size()) throw ProjectError("set_morphs: no object " + std::to_string(kv.first));
+        if (kv.second.num_targets == 0 || kv.second.num_targets > 256) throw ProjectError("set_morphs: object " + std::to_string(kv.first) + " needs 1 to 256 targets");
+        const size_t words = 9 * (size_t)flat_.objects()[kv.first].range.num_triangles * kv.second.num_targets;
+        if (kv.second.position_deltas.size() != words || (!kv.second.normal_deltas.empty() && kv.second.normal_deltas.size() != words))
+            throw ProjectError("set_morphs: object " + std::to_string(kv.first) + " needs three deltas for each vertex of each of its triangles in each target");
+    }
+    for (auto& kv : scenes_) set_morphs_on(kv.second, morphs);
+    morphs_ = morphs;
+    weights_.clear();
+}
+void World::morph_scene(PyrScene* handle, const std::map<size_t, std::vector<float>>& weights, const std::map<size_t, std::vector<float>>* joints,
+                        const std::map<size_t, ObjectPose>& poses, Update mode, void* hip_stream) {
+    std::vector<float> table, joint_rows;
+    for (const auto& kv : morphs_) {
+        const auto it = weights.find(kv.first);
+        if (it != weights.end())
+            table.insert(table.end(), it->second.begin(), it->second.end());
+        else
+            table.insert(table.end(), kv.second.num_targets, 0.0f);
+    }
+    if (joints) joint_rows = joint_table(*joints);
+    const std::vector<PyrObjectPose> records = pose_records(poses);
+    PyrMorphUpdate u{};
+    u.mode = mode == Update::Rebuild ? PYR_UPDATE_REBUILD : PYR_UPDATE_REFIT;
+    u.num_objects = (uint32_t)records.size();
+    u.poses = records.data();
+    u.joints = joints ? joint_rows.data() : nullptr;
+    u.num_joints = (uint32_t)(joint_rows.size() / 16);
+    u.weights = table.data();
+    u.num_weights = (uint32_t)table.size();
+    check_status(pyr_scene_morph(handle, &u, hip_stream));
+}
+void World::morph(const std::map<size_t, std::vector<float>>& weights, const std::map<size_t, std::vector<float>>* joints, const std::map<size_t, ObjectPose>* poses, Update mode,
+                  int device, void* hip_stream) {
+    if (morphs_.empty()) throw ProjectError("morph: the world has no morphs (set_morphs gives them)");
+    std::map<size_t, std::vector<float>> merged = weights_;
+    for (const auto& kv : weights) {
+        const auto it = morphs_.find(kv.first);
+        if (it == morphs_.end()) throw ProjectError("morph: no morph on object " + std::to_string(kv.first));
+        if (kv.second.size() != it->second.num_targets) throw ProjectError("morph: object " + std::to_string(kv.first) + " needs one weight for each of its targets");
+        merged[kv.first] = kv.second;
+    }
+    if (joints) {
+        if (skins_.empty()) throw ProjectError("morph: joints are given, and the world has no skins");
+        for (const auto& kv : *joints) {
+            const auto it = skins_.find(kv.first);
+            if (it == skins_.end()) throw ProjectError("morph: no skin on object " + std::to_string(kv.first));
+            if (kv.second.size() != 16 * (size_t)it->second.num_joints) throw ProjectError("morph: object " + std::to_string(kv.first) + " needs 16 floats for each of its joints");
+        }
+    }
+    if (poses)
+        for (const auto& kv : *poses)
+            if (kv.first >= flat_.objects().size()) throw ProjectError("morph: no object " + std::to_string(kv.first));
+    const std::map<size_t, ObjectPose> named = poses ? *poses : poses_;
+    morph_scene(scene(device), merged, joints, named, mode, hip_stream);
+    weights_ = merged, poses_ = named;
+    if (joints) joints_ = *joints;
 }
 World::Geometry World::geometry(int device) {
     PyrScene* handle = scene(device);

@@ -510,6 +510,41 @@ int main(int argc, char** argv) {
             std::printf("object %u skinned to %u joints\n", head[0], head[1]);
             return 0;
         }
+        if (argc >= 7 && std::string(argv[1]) == "morph") { // morph <scene> <data_dir> <targets> <weights.f32> <geometry.f32> [rebuild] (tests)
+            // targets: u32 object, num_targets, has_normals; f32 position_deltas[num_targets][T][3][3]; f32 normal_deltas of the same
+            // shape if has_normals, for the object's T triangles. weights.f32: one float a target.
+            Project project = make_scene(argv[2], argv[3]);
+            std::unique_ptr<World> world = World::from_project(project.world, argv[3]);
+            const auto slurp = [](const char* path) {
+                std::ifstream in(path, std::ios::binary);
+                return std::vector<char>((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+            };
+            const std::vector<char> targets = slurp(argv[4]), table = slurp(argv[5]);
+            uint32_t head[3] = {0, 0, 0};
+            if (targets.size() < 12) throw ProjectError("morph: the targets file is too short");
+            std::memcpy(head, targets.data(), 12);
+            if (head[0] >= world->objects().size()) throw ProjectError("morph: no such object");
+            const size_t words = 9 * (size_t)world->objects()[head[0]].range.num_triangles * head[1];
+            if (targets.size() != 12 + words * 4 * (head[2] ? 2 : 1)) throw ProjectError("morph: the targets file does not hold the object's triangles");
+            if (table.size() != (size_t)head[1] * 4) throw ProjectError("morph: the weights file does not hold one float for each target");
+            World::Morph morph;
+            morph.num_targets = head[1];
+            morph.position_deltas.resize(words);
+            if (words) std::memcpy(morph.position_deltas.data(), targets.data() + 12, words * 4);
+            if (head[2]) {
+                morph.normal_deltas.resize(words);
+                if (words) std::memcpy(morph.normal_deltas.data(), targets.data() + 12 + words * 4, words * 4);
+            }
+            std::vector<float> weights(table.size() / 4);
+            if (!weights.empty()) std::memcpy(weights.data(), table.data(), table.size());
+            world->set_morphs({{head[0], morph}});
+            world->morph({{head[0], weights}}, nullptr, nullptr, argc >= 8 && std::string(argv[7]) == "rebuild" ? World::Update::Rebuild : World::Update::Refit);
+            const World::Geometry g = world->geometry();
+            std::ofstream out(argv[6], std::ios::binary);
+            for (const std::vector<float>* a : {&g.positions, &g.normals, &g.frames, &g.spheres}) out.write(reinterpret_cast<const char*>(a->data()), (std::streamsize)(a->size() * 4));
+            std::printf("object %u morphed over %u targets\n", head[0], head[1]);
+            return 0;
+        }
         if (argc >= 6 && std::string(argv[1]) == "intersect") { // intersect <scene> <data_dir> <rays.f32> <hits.bin>
             Project project = make_scene(argv[2], argv[3]);
             std::unique_ptr<World> world = World::from_project(project.world, argv[3]);

@@ -1,5 +1,5 @@
-// pose.hip -- posing a live scene's objects and skinning its meshes on the device (DESIGN.md sections 9g and 9h), a unit of its own: every primitive of an object
-// is computed from the rest pose by pose_rules.h and written to the scene's staging arrays, from where the refit of section 9f
+// pose.hip -- posing a live scene's objects, skinning its meshes and morphing them on the device (DESIGN.md sections 9g, 9h and 9p), a unit of its own: every primitive of an object
+// is computed from the rest pose (where the scene has morphs: from the morphed rest, which the morph kernel writes first) by pose_rules.h and written to the scene's staging arrays, from where the refit of section 9f
 // (kernels/refit.hip) rewrites the records and the boxes; the records of shape lamps follow from the staging arrays too. Nothing
 // here touches a record the render kernels read except the lamp records, and those only after the host has seen the flag clear.
 //
@@ -168,6 +168,78 @@ __global__ __launch_bounds__(kBlock) void skin_triangles_kernel(Ctx c) {
     raise_flag(bad, &block_flag, c.beyond_range);
 }
 
+// ---- one lane per triangle of a morph: the triangle from rest into the morphed rest, which the two kernels
+// above then read as their rest pose. Positions accumulate over the morph's active targets in nine registers; normals and frame go
+// a vertex at a time through pose_rules.h morph_normal_frame. The host has packed the active targets as (target, weight) pairs, so
+// no inactive target's deltas are read, and a wave that lies inside one morph walks the pairs uniformly. A pair's target is
+// compared against the morph's count and its row against the buffer's rows before any delta is read (pyr_scene_set_morphs and the
+// host's packing make both hold: bit 0 of the flag otherwise, and the target is left out). A morph with no active target is
+// copied from rest, and so are normals and frames of a morph without normal deltas.
+__global__ __launch_bounds__(kBlock) void morph_triangles_kernel(MorphCtx c) {
+    __shared__ uint32_t block_flag;
+    if (threadIdx.x == 0) block_flag = 0u;
+    __syncthreads();
+    const uint32_t lane = blockIdx.x * kBlock + threadIdx.x;
+    uint32_t bad = 0u;
+    if (lane < c.morphed_triangles && c.num_morphs != 0u) {
+        const DevMorph& morph = c.morphs[object_of<DevMorph, &DevMorph::lane>(c.morphs, c.num_morphs, lane)];
+        const uint32_t within = lane - morph.lane, index = morph.first_triangle + within;
+        const uint32_t first_active = morph.first_active, num_active = morph.num_active, num_targets = morph.num_targets, rows = morph.num_triangles;
+        const bool pairs_inside = first_active <= c.num_active && num_active <= c.num_active - first_active;
+        if (within < rows && index >= morph.first_triangle && index < c.num_triangles && pairs_inside) {
+            const ActiveTarget* active = c.active + first_active;
+            const uint64_t position_row = morph.position_row + within, normal_row = morph.normal_row + within;
+            const bool with_normals = morph.has_normals != 0u && num_active != 0u;
+            const float* rest_p = c.rest_positions + 9 * (size_t)index;
+            const float* rest_n = c.rest_normals + 9 * (size_t)index;
+            float* out_p = c.positions + 9 * (size_t)index;
+            float* out_n = c.normals + 9 * (size_t)index;
+            float p[9];
+            for (int k = 0; k < 9; ++k) p[k] = rest_p[k];
+            for (uint32_t a = 0; a < num_active; ++a) {
+                const uint32_t target = active[a].target;
+                const float w = active[a].weight;
+                const uint64_t row = position_row + (uint64_t)target * rows;
+                if (target >= num_targets || row >= c.position_rows) {
+                    bad |= 1u;
+                    continue;
+                }
+                const float* d = c.position_deltas + 9 * row;
+                for (int k = 0; k < 9; ++k) p[k] = p[k] + w * d[k];
+            }
+            for (int k = 0; k < 9; ++k) out_p[k] = p[k];
+            for (int v = 0; v < 3; ++v) {
+                float n[3] = {rest_n[3 * v], rest_n[3 * v + 1], rest_n[3 * v + 2]};
+                float q[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                if (c.rest_frames) {
+                    const float4_t f = load4(c.rest_frames + 12 * (size_t)index + 4 * v);
+                    q[0] = f.x, q[1] = f.y, q[2] = f.z, q[3] = f.w;
+                }
+                if (with_normals) {
+                    for (uint32_t a = 0; a < num_active; ++a) {
+                        const uint32_t target = active[a].target;
+                        const float w = active[a].weight;
+                        const uint64_t row = normal_row + (uint64_t)target * rows;
+                        if (target >= num_targets || row >= c.normal_rows) {
+                            bad |= 1u;
+                            continue;
+                        }
+                        const float* d = c.normal_deltas + 9 * row + 3 * v;
+                        for (int k = 0; k < 3; ++k) n[k] = n[k] + w * d[k];
+                    }
+                    const bool outside = c.rest_frames ? pose::morph_normal_frame(n, q) : pose::morph_normal_frame(n, nullptr);
+                    if (outside) bad |= 2u;
+                }
+                if (c.rest_frames) store4(c.frames + 12 * (size_t)index + 4 * v, float4_t{q[0], q[1], q[2], q[3]});
+                out_n[3 * v] = n[0], out_n[3 * v + 1] = n[1], out_n[3 * v + 2] = n[2];
+            }
+        }
+    }
+    if (bad) atomicOr(&block_flag, bad);
+    __syncthreads();
+    if (threadIdx.x == 0 && block_flag != 0u) atomicOr(c.flag, block_flag);
+}
+
 // ---- one lane per sphere of an object
 __global__ __launch_bounds__(kBlock) void pose_spheres_kernel(Ctx c) {
     __shared__ uint32_t block_flag;
@@ -222,6 +294,11 @@ __global__ __launch_bounds__(kBlock) void pose_lamps_kernel(Ctx c) {
 uint32_t blocks_for(uint32_t n) { return (n + kBlock - 1) / kBlock; }
 
 } // namespace
+
+hipError_t launch_morph(const MorphCtx& c, hipStream_t stream) {
+    if (c.morphed_triangles) hipLaunchKernelGGL(morph_triangles_kernel, dim3(blocks_for(c.morphed_triangles)), dim3(kBlock), 0, stream, c);
+    return hipGetLastError();
+}
 
 hipError_t launch_pose(const Ctx& c, hipStream_t stream) {
     if (c.posed_triangles) hipLaunchKernelGGL(pose_triangles_kernel, dim3(blocks_for(c.posed_triangles)), dim3(kBlock), 0, stream, c);

@@ -57,7 +57,45 @@ struct Ctx {
     const uint16_t* skin_joints;  // [skinned_triangles][3][4], relative to the skin's first joint
 };
 
+// One morph on the device: its object's triangles, where its lanes begin in the launch over all morphed
+// triangles, where its targets begin in the two delta buffers -- in rows of nine floats, a target being num_triangles rows and a
+// morph's targets lying one after the other -- and its active targets of this frame in the pair table. 48 bytes.
+struct DevMorph {
+    uint32_t first_triangle, num_triangles, lane;
+    uint32_t num_targets, has_normals;
+    uint32_t first_active, num_active; // none active: the morph is at rest and its triangles are copied from rest
+    uint32_t unused;
+    uint64_t position_row, normal_row;
+};
+// One active target of a frame: the host packs every morph's targets whose weight is not zero, in ascending order.
+struct ActiveTarget {
+    uint32_t target;
+    float weight;
+};
+
+// What the morph kernel reads and writes: the rest pose, the morphed rest (which the pose and skin kernels then take for their
+// rest pose), the morphs, the frame's pairs and the deltas as uploaded, [target][triangle][3][3]. The kernel compares a triangle
+// index against num_triangles and a target's row against the buffer's row count before it uses either.
+struct MorphCtx {
+    const float* rest_positions; // [num_triangles][3][3]
+    const float* rest_normals;
+    const float* rest_frames;    // or nullptr: the scene keeps none
+    float* positions;            // the morphed rest, the same shapes
+    float* normals;
+    float* frames;
+    const DevMorph* morphs;
+    const ActiveTarget* active;
+    const float* position_deltas; // [position_rows][3][3]
+    const float* normal_deltas;   // [normal_rows][3][3]
+    uint64_t position_rows, normal_rows;
+    uint32_t num_morphs, num_active;
+    uint32_t num_triangles;     // the scene's count
+    uint32_t morphed_triangles; // lanes: the morphs' triangle counts summed
+    uint32_t* flag; // the pose kernels' word: bit 0 as there; bit 1 (value 2): a morphed normal or tangent that cannot be normalised
+};
+
 // Each enqueues on `stream` and returns hipGetLastError().
+hipError_t launch_morph(const MorphCtx& c, hipStream_t stream); // every morph's triangles from rest into the morphed rest
 hipError_t launch_pose(const Ctx& c, hipStream_t stream);  // triangles and spheres of every object, skinned or posed, into the staging arrays
 hipError_t launch_lamps(const Ctx& c, hipStream_t stream); // the records of shape lamps from the staging arrays
 

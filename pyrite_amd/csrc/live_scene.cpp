@@ -1,5 +1,5 @@
 // live_scene.cpp -- everything that moves a scene after creation: pyr_scene_update[_device], pyr_scene_set_objects,
-// pyr_scene_pose, pyr_scene_set_skins, pyr_scene_skin, pyr_scene_geometry, pyr_scene_update_info -- and pyr_scene_keep_previous,
+// pyr_scene_pose, pyr_scene_set_skins, pyr_scene_skin, pyr_scene_set_morphs, pyr_scene_morph, pyr_scene_geometry, pyr_scene_update_info -- and pyr_scene_keep_previous,
 // which copies where the geometry is now for the motion pass (api.cpp enqueues that one). LiveGeometry
 // (scene_internal.h) says where the geometry is and which copies are valid; rebuild_from and refit_from are the two ways new
 // arrays reach the records and trees on the device.
@@ -50,9 +50,18 @@ void LiveGeometry::forget_skins() {
     for (const devpose::DevObject& o : pose_table) posed_triangles += o.num_triangles;
 }
 
+void LiveGeometry::forget_morphs() {
+    morphs.clear(), morph_weights.clear();
+    morphed_triangles = 0;
+    morph_position_rows = morph_normal_rows = 0;
+    for (DeviceBuffer* b : {&morph_table, &morph_active, &morph_positions, &morph_normals}) b->release();
+    for (DeviceBuffer& b : morphed_rest) b.release();
+}
+
 void LiveGeometry::forget_objects() {
     pose_table.clear();
     forget_skins();
+    forget_morphs();
     posed_triangles = posed_spheres = 0;
     for (LiveArray& a : arrays) a.rest.release();
     pose_objects.release();
@@ -131,6 +140,20 @@ int check_pose_args(const PyrScene* scene, const PyrPoseUpdate* u) {
     return check_move(scene, u, "PyrPoseUpdate", "pose", [&]() { return check_poses(scene, u, "PyrPoseUpdate", false); });
 }
 
+// What pyr_scene_skin and pyr_scene_morph refuse of a joint table that is given (`name`: the update's struct).
+template <class Update>
+int check_joints(const LiveGeometry& live, const Update* u, const std::string& name) {
+    if ((size_t)u->num_joints * 16 != live.skin_joints.size()) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".num_joints is not the scene's");
+    if (!u->joints) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".joints is null");
+    for (size_t k = 0; k < live.skin_joints.size(); ++k)
+        if (!std::isfinite(u->joints[k])) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".joints has an entry that is not finite");
+    for (uint32_t j = 0; j < u->num_joints; ++j) {
+        const float* m = u->joints + 16 * (size_t)j;
+        if (!(m[3] == 0.0f && m[7] == 0.0f && m[11] == 0.0f && m[15] == 1.0f)) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".joints: the last row must be 0, 0, 0, 1");
+    }
+    return (int)PYR_OK;
+}
+
 // What pyr_scene_skin adds to that: the joint table.
 int check_skin_args(const PyrScene* scene, const PyrSkinUpdate* u) {
     if (!u) return fail(PYR_ERR_INVALID_ARGUMENT, "null update");
@@ -138,15 +161,29 @@ int check_skin_args(const PyrScene* scene, const PyrSkinUpdate* u) {
     return check_move(scene, u, "PyrSkinUpdate", "skin", [&]() {
         const int rc = check_poses(scene, u, "PyrSkinUpdate", true);
         if (rc != PYR_OK) return rc;
+        if (scene->live.skins.empty()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSkinUpdate.num_joints: the scene has no skins (pyr_scene_set_skins binds them)");
+        return check_joints(scene->live, u, "PyrSkinUpdate");
+    });
+}
+
+// What pyr_scene_morph adds to pyr_scene_pose's checks: morphs must be set; a joint table is pyr_scene_skin's, but may be NULL (the
+// scene keeps its joints); then the weight table, which may be NULL too.
+int check_morph_args(const PyrScene* scene, const PyrMorphUpdate* u) {
+    if (!u) return fail(PYR_ERR_INVALID_ARGUMENT, "null update");
+    if (!scene) return fail(PYR_ERR_INVALID_ARGUMENT, "null scene");
+    return check_move(scene, u, "PyrMorphUpdate", "morph", [&]() {
+        int rc = check_poses(scene, u, "PyrMorphUpdate", true);
+        if (rc != PYR_OK) return rc;
         const LiveGeometry& live = scene->live;
-        if (live.skins.empty()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSkinUpdate.num_joints: the scene has no skins (pyr_scene_set_skins binds them)");
-        if ((size_t)u->num_joints * 16 != live.skin_joints.size()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSkinUpdate.num_joints is not the scene's");
-        if (!u->joints) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSkinUpdate.joints is null");
-        for (size_t k = 0; k < live.skin_joints.size(); ++k)
-            if (!std::isfinite(u->joints[k])) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSkinUpdate.joints has an entry that is not finite");
-        for (uint32_t j = 0; j < u->num_joints; ++j) {
-            const float* m = u->joints + 16 * (size_t)j;
-            if (!(m[3] == 0.0f && m[7] == 0.0f && m[11] == 0.0f && m[15] == 1.0f)) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSkinUpdate.joints: the last row must be 0, 0, 0, 1");
+        if (live.morphs.empty()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrMorphUpdate.num_weights: the scene has no morphs (pyr_scene_set_morphs sets them)");
+        if (u->joints) {
+            if (live.skins.empty()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrMorphUpdate.joints: the scene has no skins (pyr_scene_set_skins binds them)");
+            if ((rc = check_joints(live, u, "PyrMorphUpdate")) != PYR_OK) return rc;
+        }
+        if (u->weights) {
+            if (u->num_weights != live.morph_weights.size()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrMorphUpdate.num_weights is not the scene's");
+            for (uint32_t k = 0; k < u->num_weights; ++k)
+                if (!std::isfinite(u->weights[k])) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrMorphUpdate.weights has a weight that is not finite");
         }
         return (int)PYR_OK;
     });
@@ -343,7 +380,8 @@ void set_pose(devpose::DevObject& o, const float* transform, float scale) {
 
 devpose::Ctx pose_context(PyrScene* s) {
     const LiveGeometry& live = s->live;
-    const auto rest = [&](int k) { return live.arrays[k].kept ? (const float*)live.arrays[k].rest.ptr : nullptr; };
+    // (while morphs are set, the rest pose of the pose and skin kernels is what the morph kernel wrote)
+    const auto rest = [&](int k) { return !live.arrays[k].kept ? nullptr : !live.morphs.empty() && k < 3 ? (const float*)live.morphed_rest[k].ptr : (const float*)live.arrays[k].rest.ptr; };
     const auto staging = [&](int k) { return (float*)live.arrays[k].staging.ptr; };
     devpose::Ctx c{};
     c.rest_positions = rest(POSITIONS), c.rest_normals = rest(NORMALS), c.rest_frames = rest(FRAMES), c.rest_spheres = rest(SPHERES);
@@ -360,11 +398,43 @@ devpose::Ctx pose_context(PyrScene* s) {
     return c;
 }
 
-// Every object's primitives from the rest pose into the staging arrays under `table` and, where the scene has skins, under
-// `joints` ([joints][16]), and the flag back: the one wait. A skinned object's triangles have their lanes in the skin kernel's
-// launch, so the table the pose kernels read gives that object none.
-int run_pose(PyrScene* s, const std::vector<devpose::DevObject>& table, const std::vector<float>& joints, hipStream_t stream, uint32_t& beyond_range) {
+devpose::MorphCtx morph_context(PyrScene* s, uint32_t num_active) {
     const LiveGeometry& live = s->live;
+    devpose::MorphCtx c{};
+    c.rest_positions = (const float*)live.arrays[POSITIONS].rest.ptr, c.rest_normals = (const float*)live.arrays[NORMALS].rest.ptr;
+    c.rest_frames = live.arrays[FRAMES].kept ? (const float*)live.arrays[FRAMES].rest.ptr : nullptr;
+    c.positions = (float*)live.morphed_rest[POSITIONS].ptr, c.normals = (float*)live.morphed_rest[NORMALS].ptr;
+    c.frames = live.arrays[FRAMES].kept ? (float*)live.morphed_rest[FRAMES].ptr : nullptr;
+    c.morphs = (const devpose::DevMorph*)live.morph_table.ptr, c.active = (const devpose::ActiveTarget*)live.morph_active.ptr;
+    c.position_deltas = (const float*)live.morph_positions.ptr, c.normal_deltas = (const float*)live.morph_normals.ptr;
+    c.position_rows = live.morph_position_rows, c.normal_rows = live.morph_normal_rows;
+    c.num_morphs = (uint32_t)live.morphs.size(), c.num_active = num_active;
+    c.num_triangles = live.num_triangles, c.morphed_triangles = live.morphed_triangles;
+    c.flag = (uint32_t*)live.pose_flag.ptr;
+    return c;
+}
+
+// Every object's primitives from the rest pose into the staging arrays under `table` and, where the scene has skins, under
+// `joints` ([joints][16]), and the flag back: the one wait. Where the scene has morphs, their triangles go from the rest pose into
+// the morphed rest under `weights` first (the morphs' targets one after the other), and the other kernels start from there. A skinned object's triangles have their lanes in the skin kernel's
+// launch, so the table the pose kernels read gives that object none.
+int run_pose(PyrScene* s, const std::vector<devpose::DevObject>& table, const std::vector<float>& joints, const std::vector<float>& weights, hipStream_t stream,
+             uint32_t& beyond_range) {
+    const LiveGeometry& live = s->live;
+    std::vector<devpose::DevMorph> morphs(live.morphs.size()); // (these two live until the wait below as well)
+    std::vector<devpose::ActiveTarget> active;
+    for (size_t k = 0; k < morphs.size(); ++k) {
+        const LiveGeometry::Morph& from = live.morphs[k];
+        devpose::DevMorph& to = morphs[k];
+        to.first_triangle = table[from.object].first_triangle, to.num_triangles = table[from.object].num_triangles, to.lane = from.lane;
+        to.num_targets = from.num_targets, to.has_normals = from.has_normals ? 1u : 0u;
+        to.first_active = (uint32_t)active.size();
+        for (uint32_t t = 0; t < from.num_targets; ++t)
+            if (weights[from.first_weight + t] != 0.0f) active.push_back({t, weights[from.first_weight + t]});
+        to.num_active = (uint32_t)active.size() - to.first_active;
+        to.unused = 0;
+        to.position_row = from.position_row, to.normal_row = from.normal_row;
+    }
     std::vector<devpose::DevObject> unskinned; // (these three live until the wait below)
     std::vector<devpose::DevSkin> skins(live.skins.size());
     std::vector<float> rows(joints.size() / 16 * 12);
@@ -393,6 +463,12 @@ int run_pose(PyrScene* s, const std::vector<devpose::DevObject>& table, const st
     const std::vector<devpose::DevObject>& objects = live.skins.empty() ? table : unskinned;
     HIP_TRY(hipMemcpyAsync(s->live.pose_objects.ptr, objects.data(), objects.size() * sizeof(devpose::DevObject), hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemsetAsync(s->live.pose_flag.ptr, 0, 4, stream));
+    if (!morphs.empty()) {
+        HIP_TRY(hipMemcpyAsync(live.morph_table.ptr, morphs.data(), morphs.size() * sizeof(devpose::DevMorph), hipMemcpyHostToDevice, stream));
+        if (!active.empty()) HIP_TRY(hipMemcpyAsync(live.morph_active.ptr, active.data(), active.size() * sizeof(devpose::ActiveTarget), hipMemcpyHostToDevice, stream));
+        const hipError_t em = devpose::launch_morph(morph_context(s, (uint32_t)active.size()), stream);
+        if (em != hipSuccess) return hip_fail(em, "morph kernel");
+    }
     const hipError_t e = devpose::launch_pose(pose_context(s), stream);
     if (e != hipSuccess) return hip_fail(e, "pose kernels");
     HIP_TRY(hipMemcpyAsync(&beyond_range, s->live.pose_flag.ptr, 4, hipMemcpyDeviceToHost, stream));
@@ -400,8 +476,13 @@ int run_pose(PyrScene* s, const std::vector<devpose::DevObject>& table, const st
     return PYR_OK;
 }
 
-// pyr_scene_pose and pyr_scene_skin: `poses` nullptr keeps the poses the scene is in, `new_joints` nullptr its joints.
-int scene_pose(PyrScene* s, uint32_t mode, const PyrObjectPose* poses, const float* new_joints, hipStream_t stream) {
+// Bit 0 of the flag word: a bound beyond the coordinate range; bit 1 alone: a morphed normal that cannot be normalised.
+const char* const kMorphedNormalMessage =
+    "a morphed normal or the tangent frame rebuilt against it has a squared length outside 1e-30 .. 1e30 and cannot be normalised (pyrite_gpu.h, pyr_scene_morph)";
+
+// pyr_scene_pose, pyr_scene_skin and pyr_scene_morph: `poses` nullptr keeps the poses the scene is in, `new_joints` nullptr its
+// joints, `new_weights` nullptr its morph weights.
+int scene_pose(PyrScene* s, uint32_t mode, const PyrObjectPose* poses, const float* new_joints, const float* new_weights, hipStream_t stream) {
     const auto t_start = Clock::now();
     HIP_TRY(hipSetDevice(s->device));
     LiveGeometry& live = s->live;
@@ -412,13 +493,16 @@ int scene_pose(PyrScene* s, uint32_t mode, const PyrObjectPose* poses, const flo
         for (size_t i = 0; i < table.size(); ++i) set_pose(table[i], poses[i].transform, poses[i].scale);
     std::vector<float> joints = live.skin_joints;
     if (new_joints) joints.assign(new_joints, new_joints + joints.size());
+    std::vector<float> weights = live.morph_weights;
+    if (new_weights) weights.assign(new_weights, new_weights + weights.size());
     uint32_t beyond_range = 0;
-    if ((rc = run_pose(s, table, joints, stream, beyond_range)) != PYR_OK) return rc;
-    const auto refused = [&](int why) { // no record has been touched: the staging arrays go back to the poses and joints the scene is in
-        const int back = run_pose(s, live.pose_table, live.skin_joints, stream, beyond_range);
+    if ((rc = run_pose(s, table, joints, weights, stream, beyond_range)) != PYR_OK) return rc;
+    const auto refused = [&](int why) { // no record has been touched: the staging arrays go back to the poses, joints and weights the scene is in
+        const int back = run_pose(s, live.pose_table, live.skin_joints, live.morph_weights, stream, beyond_range);
         return back != PYR_OK ? back : why;
     };
-    if (beyond_range != 0) return refused(fail(PYR_ERR_UNSUPPORTED, kCoordinateRangeMessage));
+    if (beyond_range & 1u) return refused(fail(PYR_ERR_UNSUPPORTED, kCoordinateRangeMessage));
+    if (beyond_range != 0) return refused(fail(PYR_ERR_UNSUPPORTED, kMorphedNormalMessage));
     PyrUpdateInfo info{};
     info.mode_used = mode;
     info.area_ratio = 1.0;
@@ -433,12 +517,12 @@ int scene_pose(PyrScene* s, uint32_t mode, const PyrObjectPose* poses, const flo
             live.posed();
             return refused(rc);
         }
-        live.pose_table.swap(table), live.skin_joints.swap(joints);
+        live.pose_table.swap(table), live.skin_joints.swap(joints), live.morph_weights.swap(weights);
         return PYR_OK;
     }
 
     // ---- refit: every record and box from the staging arrays, as the host form of pyr_scene_update given all four arrays
-    live.pose_table.swap(table), live.skin_joints.swap(joints);
+    live.pose_table.swap(table), live.skin_joints.swap(joints), live.morph_weights.swap(weights);
     live.posed();
     const float* source[NUM_ARRAYS];
     for (int k = 0; k < NUM_ARRAYS; ++k) source[k] = live.kept_floats(k) ? (const float*)live.arrays[k].staging.ptr : nullptr;
@@ -479,6 +563,32 @@ int check_skins(const LiveGeometry& live, const PyrSkin* skins, uint32_t n) {
             const float sum = ((w[0] + w[1]) + w[2]) + w[3];
             if (!(std::fabs(sum - 1.0f) <= 1.0e-3f)) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSkin.weights: a vertex's weights do not sum to 1 within 1e-3");
         }
+    return PYR_OK;
+}
+
+// What pyr_scene_set_morphs refuses of the morphs themselves, in the order pyrite_gpu.h gives.
+int check_morphs(const LiveGeometry& live, const PyrMorph* morphs, uint32_t n) {
+    for (uint32_t k = 0; k < n; ++k)
+        for (uint32_t word : morphs[k].reserved)
+            if (word != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrMorph.reserved must be zero");
+    for (uint32_t k = 0; k < n; ++k)
+        if (morphs[k].object >= live.pose_table.size()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrMorph.object is not one of the scene's objects");
+    for (uint32_t k = 0; k < n; ++k)
+        if (live.pose_table[morphs[k].object].num_triangles == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrMorph.object: the object has no triangles");
+    std::vector<uint32_t> taken;
+    for (uint32_t k = 0; k < n; ++k) taken.push_back(morphs[k].object);
+    std::sort(taken.begin(), taken.end());
+    if (std::adjacent_find(taken.begin(), taken.end()) != taken.end()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrMorph.object: two morphs on one object");
+    for (uint32_t k = 0; k < n; ++k)
+        if (morphs[k].num_targets == 0 || morphs[k].num_targets > 256u) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrMorph.num_targets must be 1 to 256");
+    for (uint32_t k = 0; k < n; ++k)
+        if (!morphs[k].position_deltas) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrMorph.position_deltas is null");
+    for (uint32_t k = 0; k < n; ++k) {
+        const size_t words = 9 * (size_t)live.pose_table[morphs[k].object].num_triangles * morphs[k].num_targets;
+        for (const float* deltas : {morphs[k].position_deltas, morphs[k].normal_deltas})
+            for (size_t i = 0; deltas && i < words; ++i)
+                if (!std::isfinite(deltas[i])) return fail(PYR_ERR_INVALID_ARGUMENT, deltas == morphs[k].position_deltas ? "PyrMorph.position_deltas has a delta that is not finite" : "PyrMorph.normal_deltas has a delta that is not finite");
+    }
     return PYR_OK;
 }
 
@@ -543,7 +653,7 @@ int pyr_scene_set_objects(PyrScene* scene, const PyrObjectRange* ranges, uint32_
 int pyr_scene_pose(PyrScene* scene, const PyrPoseUpdate* update, void* hip_stream) {
     int rc = check_pose_args(scene, update);
     if (rc != PYR_OK) return rc;
-    return scene_pose(scene, update->mode, update->poses, nullptr, (hipStream_t)hip_stream);
+    return scene_pose(scene, update->mode, update->poses, nullptr, nullptr, (hipStream_t)hip_stream);
 }
 
 int pyr_scene_set_skins(PyrScene* scene, const PyrSkin* skins, uint32_t num_skins) {
@@ -592,7 +702,59 @@ int pyr_scene_set_skins(PyrScene* scene, const PyrSkin* skins, uint32_t num_skin
 int pyr_scene_skin(PyrScene* scene, const PyrSkinUpdate* update, void* hip_stream) {
     int rc = check_skin_args(scene, update);
     if (rc != PYR_OK) return rc;
-    return scene_pose(scene, update->mode, update->poses, update->joints, (hipStream_t)hip_stream);
+    return scene_pose(scene, update->mode, update->poses, update->joints, nullptr, (hipStream_t)hip_stream);
+}
+
+int pyr_scene_set_morphs(PyrScene* scene, const PyrMorph* morphs, uint32_t num_morphs) {
+    if (num_morphs != 0 && !morphs) return fail(PYR_ERR_INVALID_ARGUMENT, "null morphs with a non-zero num_morphs");
+    if (!scene) return fail(PYR_ERR_INVALID_ARGUMENT, "null scene");
+    LiveGeometry& live = scene->live;
+    if (live.pose_table.empty()) return fail(PYR_ERR_INVALID_ARGUMENT, "pyr_scene_set_morphs: the scene has no objects (pyr_scene_set_objects names them)");
+    int rc = check_morphs(live, morphs, num_morphs);
+    if (rc != PYR_OK) return rc;
+    if (num_morphs == 0 && live.morphs.empty()) return PYR_OK;
+    HIP_TRY(hipSetDevice(scene->device));
+    HIP_TRY(hipDeviceSynchronize()); // an earlier call's kernels may still read the deltas and the morphed rest
+    if (num_morphs == 0) {
+        live.forget_morphs();
+        return PYR_OK;
+    }
+    // the deltas one morph after the other, on the device before anything of the old morphs is let go
+    std::vector<LiveGeometry::Morph> table(num_morphs);
+    std::vector<float> positions, normals;
+    uint32_t lane = 0, weight = 0;
+    for (uint32_t k = 0; k < num_morphs; ++k) {
+        const uint32_t triangles = live.pose_table[morphs[k].object].num_triangles;
+        const size_t words = 9 * (size_t)triangles * morphs[k].num_targets;
+        table[k] = {morphs[k].object, morphs[k].num_targets, weight, lane, positions.size() / 9, normals.size() / 9, morphs[k].normal_deltas != nullptr};
+        positions.insert(positions.end(), morphs[k].position_deltas, morphs[k].position_deltas + words);
+        if (morphs[k].normal_deltas) normals.insert(normals.end(), morphs[k].normal_deltas, morphs[k].normal_deltas + words);
+        lane += triangles, weight += morphs[k].num_targets; // disjoint ranges: below 2^28; at most 256 a morph
+    }
+    DeviceBuffer fresh[7]; // position deltas, normal deltas, DevMorph records, a frame's pairs, the morphed rest
+    if ((rc = fresh[0].upload(positions.data(), positions.size() * 4)) != PYR_OK) return rc;
+    if (!normals.empty() && (rc = fresh[1].upload(normals.data(), normals.size() * 4)) != PYR_OK) return rc;
+    if ((rc = fresh[2].alloc((size_t)num_morphs * sizeof(devpose::DevMorph))) != PYR_OK) return rc;
+    if ((rc = fresh[3].alloc((size_t)weight * sizeof(devpose::ActiveTarget))) != PYR_OK) return rc;
+    for (int k = 0; k < 3; ++k) {
+        const size_t bytes = live.kept_floats(k) * 4;
+        if (!bytes) continue;
+        if ((rc = fresh[4 + k].alloc(bytes)) != PYR_OK) return rc;
+        HIP_TRY(hipMemcpy(fresh[4 + k].ptr, live.arrays[k].rest.ptr, bytes, hipMemcpyDeviceToDevice));
+    }
+    DeviceBuffer* const own[7] = {&live.morph_positions, &live.morph_normals, &live.morph_table, &live.morph_active, &live.morphed_rest[0], &live.morphed_rest[1], &live.morphed_rest[2]};
+    for (int k = 0; k < 7; ++k) std::swap(own[k]->ptr, fresh[k].ptr), std::swap(own[k]->bytes, fresh[k].bytes);
+    live.morphs.swap(table);
+    live.morph_weights.assign(weight, 0.0f);
+    live.morphed_triangles = lane;
+    live.morph_position_rows = positions.size() / 9, live.morph_normal_rows = normals.size() / 9;
+    return PYR_OK;
+}
+
+int pyr_scene_morph(PyrScene* scene, const PyrMorphUpdate* update, void* hip_stream) {
+    int rc = check_morph_args(scene, update);
+    if (rc != PYR_OK) return rc;
+    return scene_pose(scene, update->mode, update->poses, update->joints, update->weights, (hipStream_t)hip_stream);
 }
 
 int pyr_scene_geometry(PyrScene* scene, float* tri_positions, float* tri_normals, float* tri_frames, float* spheres) {

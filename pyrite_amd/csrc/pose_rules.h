@@ -1,5 +1,5 @@
-// pose_rules.h -- what a pose does to one vertex, one sphere and one lamp and how a skin blends a vertex's
-// matrix (section 9h), as functions of one record: the
+// pose_rules.h -- what a pose does to one vertex, one sphere and one lamp, how a skin blends a vertex's
+// matrix (section 9h) and what a morphed normal does to its tangent frame (section 9p), as functions of one record: the
 // pose kernels (kernels/pose.hip) and the host rehearsal (tests/probes/pose_check.cpp) both compile these, so what they compute
 // can differ only in the square root and the reciprocal -- sqrt32 / rcp32 of exact_math.h on the device, std::sqrt and 1.0f / x on
 // the host, bit-identical in the ranges exact_math.h names.
@@ -152,6 +152,34 @@ PYR_POSE_HD void blend_joints(const float* joints, const uint32_t* j, const floa
     }
     b.scale = 1.0f;
     b.identity = 0u;
+}
+
+// ---- the morph rule: what a vertex normal and its tangent frame become once the active targets' normal
+// deltas have been added to the normal (`n` comes in as m = n + sum w[t] * dn[t], the caller's loop over the active targets in
+// ascending t, and leaves as normalize(m)). `frame` nullptr: the scene keeps none; otherwise the old tangent frame is
+// Gram-Schmidt'ed against the new normal, x first, which keeps it orthonormal and its handedness. Returns whether a squared
+// length that is normalised lies outside [1e-30, 1e30] -- the range in which sqrt32 and rcp32 are the host's bits (exact_math.h);
+// the caller raises bit 1 of the flag word then, and what is written is not used.
+PYR_POSE_HD bool morph_normal_frame(float* n, float* frame) {
+    const auto outside = [](float s) { return !(s >= 1.0e-30f && s <= 1.0e30f); };
+    bool bad = outside((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
+    normalize(n);
+    if (!frame) return bad;
+    const float ex[3] = {1.0f, 0.0f, 0.0f}, ey[3] = {0.0f, 1.0f, 0.0f};
+    float rx[3], ry[3], x[3], y[3];
+    quat_rotate(frame, ex, rx);
+    quat_rotate(frame, ey, ry);
+    const float d = (rx[0] * n[0] + rx[1] * n[1]) + rx[2] * n[2];
+    for (int a = 0; a < 3; ++a) x[a] = rx[a] - n[a] * d;
+    bad = bad || outside((x[0] * x[0] + x[1] * x[1]) + x[2] * x[2]);
+    normalize(x);
+    const float e = (ry[0] * n[0] + ry[1] * n[1]) + ry[2] * n[2];
+    const float f = (ry[0] * x[0] + ry[1] * x[1]) + ry[2] * x[2];
+    for (int a = 0; a < 3; ++a) y[a] = (ry[a] - n[a] * e) - x[a] * f;
+    bad = bad || outside((y[0] * y[0] + y[1] * y[1]) + y[2] * y[2]);
+    normalize(y);
+    quat_from_cols(x, y, n, frame);
+    return bad;
 }
 
 // ---- the per-sphere rule: radius *= scale; centre *= scale; centre = transform_point(centre)

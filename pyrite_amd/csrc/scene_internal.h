@@ -109,6 +109,21 @@ struct LiveGeometry {
     std::vector<float> skin_joints;
     uint32_t skinned_triangles = 0;
     DeviceBuffer skin_table, skin_weights, skin_indices, joint_table; // DevSkin records, the two binding arrays, twelve floats a joint
+    // the morphs in morph order (pyr_scene_set_morphs): whose triangles, how many targets, where its weights begin in the weight
+    // table, its lanes in the morph kernel's launch and its targets in the two delta buffers (rows of nine floats); and the weights
+    // the scene is in, the morphs' targets one after the other (zero when the morphs are set). `morphed_rest`: positions, normals
+    // and frames after the morph, which the pose and skin kernels read as their rest pose while morphs are set.
+    struct Morph {
+        uint32_t object, num_targets, first_weight, lane;
+        uint64_t position_row, normal_row;
+        bool has_normals;
+    };
+    std::vector<Morph> morphs;
+    std::vector<float> morph_weights;
+    uint32_t morphed_triangles = 0;
+    uint64_t morph_position_rows = 0, morph_normal_rows = 0;
+    DeviceBuffer morph_table, morph_active, morph_positions, morph_normals; // DevMorph records, a frame's pairs, the deltas as uploaded
+    DeviceBuffer morphed_rest[3];
     // the previous frame (pyr_scene_keep_previous): positions and spheres as they were when it was called, the description's order.
     // Nothing that moves the scene touches them -- counts and indices never change -- and only the motion pass reads them.
     DeviceBuffer previous_positions, previous_spheres;
@@ -118,8 +133,9 @@ struct LiveGeometry {
     size_t kept_floats(int k) const { return arrays[k].kept ? floats(k) : 0; }
     void keep(const PyrSceneDesc* d); // scene creation: the description's geometry
     PyrSceneDesc view(const float* const with[NUM_ARRAYS] = nullptr) const; // what pack_geometry and pack_lamp read; `with`: arrays in place of the scene's own
-    void forget_objects(); // (adopted() does it: new arrays are a new geometry, not a pose of the old one); forgets the skins too
+    void forget_objects(); // (adopted() does it: new arrays are a new geometry, not a pose of the old one); forgets the skins and the morphs too
     void forget_skins();
+    void forget_morphs();
     bool host_current() const { return host_current_; }
     bool positions_staged() const { return positions_staged_; }
     bool schedule_current() const { return schedule_current_; }

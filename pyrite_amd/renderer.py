@@ -29,6 +29,8 @@ class World:
         self._poses = {}  # object index -> (float32[16] column-major, scale): the poses the scenes are in; identity where absent
         self._skins = {}  # object index -> dict(joints uint16 [T,3,4], weights float32 [T,3,4], num_joints): the bindings (World.set_skins)
         self._joints = {}  # object index -> float32 [J,16] column-major: the joints the scenes are in; identity where absent
+        self._morphs = {}  # object index -> dict(positions float32 [T,n,3,3], normals float32 [T,n,3,3] | None): the targets (World.set_morphs)
+        self._weights = {}  # object index -> float32 [T]: the weights the scenes are in; zero where absent
 
     @classmethod
     def from_project(cls, world, base_dir="."):
@@ -61,7 +63,11 @@ class World:
                 self._set_objects(handle)
                 if self._skins:
                     self._set_skins(handle, self._skins)
-                if self._joints:
+                if self._morphs:
+                    self._set_morphs(handle, self._morphs)
+                if any(np.any(w != 0) for w in self._weights.values()):
+                    self._morph(handle, self._weights, self._joints if self._skins else None, self._poses, "rebuild", 0)
+                elif self._joints:
                     self._skin(handle, self._joints, self._poses, "rebuild", 0)
                 elif self._poses:
                     self._pose(handle, self._poses, "rebuild", 0)
@@ -100,13 +106,14 @@ class World:
     def set_objects(self, objects=None):
         """Names other primitive ranges as the objects (pyr_scene_set_objects on every scene of this world; None: the records of
         the description again). The geometry as it is now becomes the rest pose, and every pose is the identity again."""
-        if (self._poses or self._joints) and self._scenes:  # every scene of this world is in the same pose: `flat` follows the first
+        if (self._poses or self._joints or self._weights) and self._scenes:  # every scene of this world is in the same pose: `flat` follows the first
             self._follow(self._geometry(next(iter(self._scenes.values()))))
         objects = [dict(o) for o in (self.flat.objects if objects is None else objects)]
         for handle in self._scenes.values():
             self._set_objects(handle, objects)
         self._objects, self._poses = objects, {}
         self._skins, self._joints = {}, {}  # skins hang on objects: pyr_scene_set_objects forgot them
+        self._morphs, self._weights = {}, {}  # and so do morphs
 
     def _follow(self, arrays):
         for name, attr in (("positions", "tri_positions"), ("normals", "tri_normals"), ("frames", "tri_frames"), ("spheres", "spheres")):
@@ -220,6 +227,77 @@ class World:
         self._skin(self.scene(device), tables, named, mode, stream)
         self._poses, self._joints = named, tables
 
+    def _set_morphs(self, handle, morphs):
+        order = sorted(morphs)
+        records = (abi.PyrMorph * max(1, len(order)))()
+        for k, index in enumerate(order):
+            m = morphs[index]
+            records[k] = abi.PyrMorph(object=index, num_targets=len(m["positions"]), position_deltas=m["positions"].ctypes.data,
+                                      normal_deltas=None if m["normals"] is None else m["normals"].ctypes.data)
+        check(lib().pyr_scene_set_morphs(handle, records, len(order)))
+
+    def set_morphs(self, morphs):
+        """Gives meshes their morph targets (pyr_scene_set_morphs on every scene of this world): `morphs` maps an object's index in
+        `World.objects` to dict(positions=float32 [T,n,3,3], normals=None | float32 [T,n,3,3]) for T targets (1 to 256) over that
+        object's n triangles -- position deltas and, if the normals are to follow, normal deltas. Morphs are in the order of their
+        object indices. Every weight is zero afterwards and the geometry does not change; an empty dict forgets the morphs."""
+        held = {}
+        for index, m in morphs.items():
+            if not 0 <= int(index) < len(self._objects):
+                raise ValueError("no object %r: the world has %d" % (index, len(self._objects)))
+            positions = np.asarray(m["positions"])
+            normals = None if m.get("normals") is None else np.asarray(m["normals"])
+            n = self._objects[int(index)].get("num_triangles", 0)
+            if positions.ndim != 4 or positions.shape[1:] != (n, 3, 3) or not 1 <= positions.shape[0] <= 256:
+                raise ValueError("the morph of object %r needs positions of shape [1..256, %d, 3, 3], not %r" % (index, n, positions.shape))
+            if normals is not None and normals.shape != positions.shape:
+                raise ValueError("the morph of object %r needs normals of shape %r, not %r" % (index, positions.shape, normals.shape))
+            held[int(index)] = dict(positions=np.ascontiguousarray(positions, dtype=np.float32), normals=None if normals is None else np.ascontiguousarray(normals, dtype=np.float32))
+        for handle in self._scenes.values():
+            self._set_morphs(handle, held)
+        self._morphs, self._weights = held, {}
+
+    def _morph(self, handle, weights, tables, poses, mode, stream):
+        rows = [weights[index] if index in weights else np.zeros(len(self._morphs[index]["positions"]), dtype=np.float32) for index in sorted(self._morphs)]
+        table = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros(0), dtype=np.float32)
+        u = abi.PyrMorphUpdate(mode=self.UPDATE_MODES[mode], num_objects=len(self._objects), poses=self._pose_records(poses), weights=table.ctypes.data, num_weights=len(table))
+        if tables is not None:
+            joints = [tables[index] if index in tables else np.tile(self.IDENTITY, (self._skins[index]["num_joints"], 1)) for index in sorted(self._skins)]
+            joints = np.ascontiguousarray(np.concatenate(joints) if joints else np.zeros((0, 16)), dtype=np.float32)
+            u.joints, u.num_joints = joints.ctypes.data, len(joints)
+        check(lib().pyr_scene_morph(handle, C.byref(u), C.c_void_p(int(stream))))
+
+    def morph(self, weights, joints=None, poses=None, mode="refit", device=0, stream=0):
+        """One frame of the morphed meshes of the scene on `device` (pyr_scene_morph): `weights` maps a morphed object's index to
+        one weight per target, [T]; a morph it does not name stays at the weights it is in. Every vertex takes the weighted deltas
+        of the targets whose weight is not zero, then its skin if the object has one -- `joints` as for `skin`, None keeps the
+        joints the world is in -- then the object's pose: `poses` as for `pose`, None keeps the poses. Everything is computed from
+        the rest pose on the GPU; mode as for `update`. `World.flat` stays the rest pose, and the world remembers weights, joints
+        and poses for scenes it creates later."""
+        if mode not in self.UPDATE_MODES:
+            raise ValueError("mode must be 'refit' or 'rebuild', not %r" % (mode,))
+        for k in ({} if poses is None else poses):
+            if not 0 <= int(k) < len(self._objects):
+                raise ValueError("no object %r: the world has %d" % (k, len(self._objects)))
+        merged = dict(self._weights)
+        for index, w in weights.items():
+            if int(index) not in self._morphs:
+                raise ValueError("no morph on object %r" % (index,))
+            w = np.ascontiguousarray(w, dtype=np.float32)
+            if w.shape != (len(self._morphs[int(index)]["positions"]),):
+                raise ValueError("the morph of object %r has %d targets, not %r weights" % (index, len(self._morphs[int(index)]["positions"]), w.shape))
+            merged[int(index)] = w
+        if not self._morphs:
+            raise ValueError("the world has no morphs (set_morphs gives them)")
+        if joints is not None and not self._skins:
+            raise ValueError("joints are given, and the world has no skins")
+        tables = None if joints is None else self._joint_tables(joints)
+        named = self._poses if poses is None else {int(k): (None if v[0] is None else np.array(v[0], dtype=np.float32), float(v[1])) for k, v in poses.items()}
+        self._morph(self.scene(device), merged, tables, named, mode, stream)
+        self._weights, self._poses = merged, named
+        if tables is not None:
+            self._joints = tables
+
     def geometry(self, device=0):
         """The geometry of the scene on `device` as it is now (pyr_scene_geometry): a dict of float32 arrays `positions` [n,9],
         `normals` [n,9], `frames` [n,12] (None unless the scene keeps frames) and `spheres` [n,4]."""
@@ -279,6 +357,7 @@ class World:
         if u.tri_positions or u.tri_normals or u.tri_frames or u.spheres:
             self._poses = {}  # new arrays are a new geometry, not a pose of the old one: the scene forgot its objects (set_objects names them again)
             self._skins, self._joints = {}, {}
+            self._morphs, self._weights = {}, {}
         for name, attr in (("positions", "tri_positions"), ("normals", "tri_normals"), ("frames", "tri_frames"), ("spheres", "spheres")):
             if name in host:
                 setattr(self.flat, attr, [host[name].copy()])
