@@ -674,6 +674,54 @@ typedef struct PyrMorphUpdate {
 } PyrMorphUpdate;
 int pyr_scene_morph(PyrScene*, const PyrMorphUpdate*, void* hip_stream);
 
+/* ---- smooth normals for a live scene's meshes. A pose, a joint matrix and a morph carry the rest pose's shading normals along:
+ * normalize(M3 n) under a matrix (no inverse transpose), rest's own bits under a morph without normal deltas. Neither is the normal
+ * of the surface where it now is: a sheared, bulged or non-uniformly scaled mesh is shaded as if it still had its rest shape.
+ * pyr_scene_set_smoothing takes, once, which corners of an object share a vertex; from then on every pyr_scene_pose, pyr_scene_skin
+ * and pyr_scene_morph recomputes that object's vertex normals on the device from the positions the call has just computed, and
+ * rebuilds the tangent frames against them. There is no per-frame call of its own and nothing crosses the bus per frame.
+ *   A smoothing belongs to one object of pyr_scene_set_objects and covers all of that object's triangles, in their order; the
+ * object's spheres are not touched. vertex_ids gives one label per corner, [triangle][3], arbitrary uint32_t values: the corners
+ * of the object with equal labels form a GROUP and share one normal. Groups never cross objects (equal labels in two objects are
+ * two groups). A crease is kept by giving its two sides different labels.
+ *   Orientation, decided once at pyr_scene_set_smoothing from the rest pose (the arrays pyr_scene_set_objects captured, not a
+ * morphed rest), all f32 and unfused: per triangle c = cross(p1 - p0, p2 - p0) with cross(a, b) = (a1*b2 - a2*b1, a2*b0 - a0*b2,
+ * a0*b1 - a1*b0); per component r = (n0 + n1) + n2 over its three rest normals; d = (c.x*r.x + c.y*r.y) + c.z*r.z. The triangle
+ * is NEGATED iff d < 0 (a d of zero or NaN does not negate): it is wound against its normals.
+ *   Per frame, after the morph, the skin and the pose have written the positions P of the call:
+ *     face vector  c = cross(p1 - p0, p2 - p0) from the triangle's final positions, every component negated (-c) if the triangle
+ *                  is negated; its length is twice the triangle's area, so the sum below is area-weighted
+ *     group sum    over the group's corners in ascending corner index 3*triangle + k: m = c of the first corner's triangle (not
+ *                  0 + c: 0 + (-0) loses a sign bit), then m = m + c per component for each further corner. A triangle that has
+ *                  two corners in one group counts twice.
+ *     normal       every corner of the group gets n' = normalize(m)           (normalize as in pyr_scene_pose)
+ *     frames       (scene that keeps frames) the corner's frame as the call computed it -- morphed, skinned and posed -- is
+ *                  Gram-Schmidt'ed against n' exactly as pyr_scene_set_morphs states for a morphed normal: x first, then y,
+ *                  q' = quat_from_cols(x, y, n')
+ * A squared length s that is normalised -- of m, of x, of y -- must lie in [1e-30, 1e30]: a lane with !(s >= 1e-30f && s <= 1e30f)
+ * raises bit 2 (value 4) of the call's flag word.
+ *   A smoothed object's normals and frames are ALWAYS N(final positions) after any pyr_scene_pose, pyr_scene_skin or
+ * pyr_scene_morph, also under an identity pose, an identity skin and a morph at rest: positions are rest's bits there, normals the
+ * recomputed ones. The geometry is N(P_object(S(M(rest)))). An object without a smoothing keeps those calls' own normals in
+ * every word. pyr_scene_set_smoothing itself moves nothing: the geometry does not change at this call.
+ *   pyr_scene_set_smoothing needs objects to be set. It packs the groups (4 bytes per corner and 4 per group on the device).
+ * num_smoothings == 0 forgets the smoothing. Every pyr_scene_set_objects call forgets it, and so does every
+ * pyr_scene_update[_device] that carries an array; pyr_scene_set_skins, pyr_scene_set_morphs and pyr_scene_set_smoothing leave each
+ * other's state in place. Refused with PYR_ERR_INVALID_ARGUMENT, in this order, before any device is looked for (pyr_last_error
+ * names the argument): NULL smoothings with a non-zero count; a NULL scene; no objects set; a non-zero reserved word; an object
+ * index out of range; an object without triangles; two smoothings on one object; NULL vertex_ids. A refused call leaves the
+ * previous smoothing in place.
+ *   The flag word of pyr_scene_pose, pyr_scene_skin and pyr_scene_morph: bit 0 keeps its message and comes first; bit 1 keeps its
+ * message; bit 2 without either is PYR_ERR_UNSUPPORTED with a message that names a recomputed normal (a group whose face vectors
+ * cancel or vanish, as under a pose of scale 0). In every case the scene renders as before. */
+typedef struct PyrSmoothing {
+    uint32_t object;              /* index into the ranges of pyr_scene_set_objects */
+    uint32_t reserved0;
+    const uint32_t* vertex_ids;   /* HOST, [object's num_triangles][3]; equal labels share a normal */
+    uint32_t reserved[4];
+} PyrSmoothing;
+int pyr_scene_set_smoothing(PyrScene*, const PyrSmoothing*, uint32_t num_smoothings);
+
 /* Introspection of the kernel a render of `scene` with `params` would run (nothing is launched; only spectrum_samples is read
  * today). Results never depend on it -- every schedule is the same per-sample arithmetic as tracer.rs:208-345 -- but throughput
  * does, and a maintainer wants to see why a scene is slow: */

@@ -259,6 +259,11 @@ class FlatScene {
     std::unique_ptr<Impl> impl_;
 };
 
+// Corner labels for World::set_smoothing from a mesh's own arrays, [num_triangles][3][3] each: two corners get the same label
+// exactly when the bits of their positions and of their normals agree in all six words, so a mesh keeps the creases its normals
+// already have. A label is the index of the first corner of its group.
+std::vector<uint32_t> weld(const float* positions, const float* normals, size_t num_triangles);
+
 class World { // world.rs:31-36
   public:
     static std::unique_ptr<World> from_project(const WorldProject& world, const std::string& base_dir = ".");
@@ -324,6 +329,13 @@ class World { // world.rs:31-36
     // on the GPU. flat() stays the rest pose; the world remembers weights, joints and poses for a scene it makes later.
     void morph(const std::map<size_t, std::vector<float>>& weights, const std::map<size_t, std::vector<float>>* joints = nullptr,
                const std::map<size_t, ObjectPose>* poses = nullptr, Update mode = Update::Refit, int device = 0, void* hip_stream = nullptr);
+    // Has the normals of meshes recomputed from where their surface is (pyr_scene_set_smoothing on every scene of this world):
+    // `smoothing` maps an object's index in objects() to one label per corner of the object's T triangles, [T][3] -- corners with
+    // equal labels share a vertex normal, the area-weighted sum of their triangles' face vectors -- or to an empty vector: weld()
+    // of the object's rest positions and rest normals. From then on every pose(), skin() and morph() recomputes those objects'
+    // normals and tangent frames on the GPU from the frame's positions, also under the identity. The geometry does not change at
+    // this call; an empty map forgets the smoothing, and so do set_objects() and an update() that carries arrays.
+    void set_smoothing(const std::map<size_t, std::vector<uint32_t>>& smoothing);
     // pyr_scene_geometry: the geometry of the scene on `device` as it is now (frames empty unless the scene keeps them)
     struct Geometry {
         std::vector<float> positions, normals, frames, spheres;
@@ -347,12 +359,15 @@ class World { // world.rs:31-36
     std::map<size_t, std::vector<float>> joints_;   // the joints the scenes are in; identity where absent
     std::map<size_t, Morph> morphs_;                // the targets (set_morphs)
     std::map<size_t, std::vector<float>> weights_;  // the morph weights the scenes are in; zero where absent
+    std::map<size_t, std::vector<uint32_t>> smoothing_; // the corner labels (set_smoothing)
+    bool smooth_frame_ = false;                     // a pose, skin or morph has run since: the scenes hold recomputed normals
     std::vector<PyrObjectPose> pose_records(const std::map<size_t, ObjectPose>& poses) const;
     void pose_scene(PyrScene* handle, const std::map<size_t, ObjectPose>& poses, Update mode, void* hip_stream);
     void set_skins_on(PyrScene* handle, const std::map<size_t, Skin>& skins);
     void skin_scene(PyrScene* handle, const std::map<size_t, std::vector<float>>& joints, const std::map<size_t, ObjectPose>& poses, Update mode, void* hip_stream);
     std::vector<float> joint_table(const std::map<size_t, std::vector<float>>& joints) const;
     void set_morphs_on(PyrScene* handle, const std::map<size_t, Morph>& morphs);
+    void set_smoothing_on(PyrScene* handle, const std::map<size_t, std::vector<uint32_t>>& smoothing);
     void morph_scene(PyrScene* handle, const std::map<size_t, std::vector<float>>& weights, const std::map<size_t, std::vector<float>>* joints,
                      const std::map<size_t, ObjectPose>& poses, Update mode, void* hip_stream);
 };

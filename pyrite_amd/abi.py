@@ -363,6 +363,15 @@ class PyrMorphUpdate(C.Structure):
     ]
 
 
+class PyrSmoothing(C.Structure):
+    _fields_ = [
+        ("object", C.c_uint32),
+        ("reserved0", C.c_uint32),
+        ("vertex_ids", C.c_void_p),
+        ("reserved", C.c_uint32 * 4),
+    ]
+
+
 class PyrPathInfo(C.Structure):
     _fields_ = [
         ("stage_scheduler", C.c_uint32),
@@ -559,6 +568,7 @@ ENTRY_POINTS = {
     "pyr_scene_skin": (C.c_int, [C.c_void_p, C.POINTER(PyrSkinUpdate), C.c_void_p]),
     "pyr_scene_set_morphs": (C.c_int, [C.c_void_p, C.POINTER(PyrMorph), C.c_uint32]),
     "pyr_scene_morph": (C.c_int, [C.c_void_p, C.POINTER(PyrMorphUpdate), C.c_void_p]),
+    "pyr_scene_set_smoothing": (C.c_int, [C.c_void_p, C.POINTER(PyrSmoothing), C.c_uint32]),
     "pyr_scene_path_info": (C.c_int, [C.c_void_p, C.POINTER(PyrRenderParams), C.POINTER(PyrPathInfo)]),
     "pyr_scene_program_info": (C.c_int, [C.c_void_p, C.POINTER(PyrProgramInfo)]),
     "pyr_program_allocate_registers": (C.c_int, [C.POINTER(PyrInstr), C.POINTER(PyrProgram), C.POINTER(PyrInstr), C.POINTER(PyrProgram)]),

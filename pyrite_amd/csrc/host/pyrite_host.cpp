@@ -1082,6 +1082,7 @@ PyrScene* World::scene(int device, int copy, std::optional<Build> build) {
         check_status(pyr_scene_set_objects(handle, ranges.data(), (uint32_t)ranges.size()));
         if (!skins_.empty()) set_skins_on(handle, skins_);
         if (!morphs_.empty()) set_morphs_on(handle, morphs_);
+        if (!smoothing_.empty()) set_smoothing_on(handle, smoothing_);
         bool morphed = false;
         for (const auto& kv : weights_)
             for (float w : kv.second) morphed = morphed || w != 0.0f;
@@ -1089,7 +1090,7 @@ PyrScene* World::scene(int device, int copy, std::optional<Build> build) {
             morph_scene(handle, weights_, skins_.empty() ? nullptr : &joints_, poses_, Update::Rebuild, nullptr);
         else if (!joints_.empty())
             skin_scene(handle, joints_, poses_, Update::Rebuild, nullptr);
-        else if (!poses_.empty())
+        else if (!poses_.empty() || smooth_frame_) // (a smoothed object's normals are recomputed under the identity too)
             pose_scene(handle, poses_, Update::Rebuild, nullptr);
     }
     return handle;
@@ -1115,17 +1116,17 @@ void World::update(const std::vector<float>& positions, const std::vector<float>
     u.spheres = spheres.empty() ? nullptr : spheres.data();
     check_status(pyr_scene_update(handle, &u));
     flat_.move_geometry(positions, normals, frames, spheres);
-    if (u.tri_positions || u.tri_normals || u.tri_frames || u.spheres) poses_.clear(), skins_.clear(), joints_.clear(), morphs_.clear(), weights_.clear(); // a new geometry, not a pose of the old one: the scene forgot its objects (set_objects names them again)
+    if (u.tri_positions || u.tri_normals || u.tri_frames || u.spheres) poses_.clear(), skins_.clear(), joints_.clear(), morphs_.clear(), weights_.clear(), smoothing_.clear(), smooth_frame_ = false; // a new geometry, not a pose of the old one: the scene forgot its objects (set_objects names them again)
 }
 void World::set_objects() {
-    if ((!poses_.empty() || !joints_.empty() || !weights_.empty()) && !scenes_.empty()) { // every scene of this world is in the same pose: flat() follows the first
+    if ((!poses_.empty() || !joints_.empty() || !weights_.empty() || smooth_frame_) && !scenes_.empty()) { // every scene of this world is in the same pose: flat() follows the first
         const Geometry g = geometry(scenes_.begin()->first.first);
         flat_.move_geometry(g.positions, g.normals, g.frames, g.spheres);
     }
     std::vector<PyrObjectRange> ranges;
     for (const FlatScene::Object& o : flat_.objects()) ranges.push_back(o.range);
     for (auto& kv : scenes_) check_status(pyr_scene_set_objects(kv.second, ranges.data(), (uint32_t)ranges.size()));
-    poses_.clear(), skins_.clear(), joints_.clear(), morphs_.clear(), weights_.clear(); // skins and morphs hang on objects: pyr_scene_set_objects forgot them
+    poses_.clear(), skins_.clear(), joints_.clear(), morphs_.clear(), weights_.clear(), smoothing_.clear(), smooth_frame_ = false; // skins, morphs and the smoothing hang on objects: pyr_scene_set_objects forgot them
 }
 std::vector<PyrObjectPose> World::pose_records(const std::map<size_t, ObjectPose>& poses) const {
     std::vector<PyrObjectPose> records(flat_.objects().size());
@@ -1151,6 +1152,7 @@ void World::pose(const std::map<size_t, ObjectPose>& poses, Update mode, int dev
         if (kv.first >= flat_.objects().size()) throw ProjectError("pose: no object " + std::to_string(kv.first));
     pose_scene(scene(device), poses, mode, hip_stream);
     poses_ = poses;
+    smooth_frame_ = !smoothing_.empty();
 }
 void World::set_skins_on(PyrScene* handle, const std::map<size_t, Skin>& skins) {
     std::vector<PyrSkin> records;
@@ -1208,6 +1210,7 @@ void World::skin(const std::map<size_t, std::vector<float>>& joints, const std::
     const std::map<size_t, ObjectPose> named = poses ? *poses : poses_;
     skin_scene(scene(device), joints, named, mode, hip_stream);
     poses_ = named, joints_ = joints;
+    smooth_frame_ = !smoothing_.empty();
 }
 void World::set_morphs_on(PyrScene* handle, const std::map<size_t, Morph>& morphs) {
     std::vector<PyrMorph> records;
@@ -1278,7 +1281,49 @@ void World::morph(const std::map<size_t, std::vector<float>>& weights, const std
     const std::map<size_t, ObjectPose> named = poses ? *poses : poses_;
     morph_scene(scene(device), merged, joints, named, mode, hip_stream);
     weights_ = merged, poses_ = named;
+    smooth_frame_ = !smoothing_.empty();
     if (joints) joints_ = *joints;
+}
+std::vector<uint32_t> weld(const float* positions, const float* normals, size_t num_triangles) {
+    struct Key {
+        uint32_t w[6];
+        bool operator<(const Key& o) const { return std::lexicographical_compare(w, w + 6, o.w, o.w + 6); }
+    };
+    std::map<Key, uint32_t> first;
+    std::vector<uint32_t> ids(3 * num_triangles);
+    for (size_t c = 0; c < ids.size(); ++c) {
+        Key key;
+        std::memcpy(key.w, positions + 3 * c, 12);
+        std::memcpy(key.w + 3, normals + 3 * c, 12);
+        ids[c] = first.emplace(key, (uint32_t)c).first->second;
+    }
+    return ids;
+}
+void World::set_smoothing_on(PyrScene* handle, const std::map<size_t, std::vector<uint32_t>>& smoothing) {
+    std::vector<PyrSmoothing> records;
+    for (const auto& kv : smoothing) {
+        PyrSmoothing s{};
+        s.object = (uint32_t)kv.first, s.vertex_ids = kv.second.data();
+        records.push_back(s);
+    }
+    check_status(pyr_scene_set_smoothing(handle, records.data(), (uint32_t)records.size()));
+}
+void World::set_smoothing(const std::map<size_t, std::vector<uint32_t>>& smoothing) {
+    std::map<size_t, std::vector<uint32_t>> held;
+    for (const auto& kv : smoothing) {
+        if (kv.first >= flat_.objects().size()) throw ProjectError("set_smoothing: no object " + std::to_string(kv.first));
+        const PyrObjectRange& r = flat_.objects()[kv.first].range;
+        if (r.num_triangles == 0) throw ProjectError("set_smoothing: object " + std::to_string(kv.first) + " has no triangles");
+        if (kv.second.empty()) // flat() stays the rest pose: welded by its positions and normals
+            held[kv.first] = weld(flat_.desc().tri_positions + 9 * (size_t)r.first_triangle, flat_.desc().tri_normals + 9 * (size_t)r.first_triangle, r.num_triangles);
+        else if (kv.second.size() != 3 * (size_t)r.num_triangles)
+            throw ProjectError("set_smoothing: object " + std::to_string(kv.first) + " needs one label for each vertex of each of its triangles");
+        else
+            held[kv.first] = kv.second;
+    }
+    for (auto& kv : scenes_) set_smoothing_on(kv.second, held);
+    smoothing_.swap(held);
+    if (smoothing_.empty()) smooth_frame_ = false;
 }
 World::Geometry World::geometry(int device) {
     PyrScene* handle = scene(device);

@@ -545,6 +545,36 @@ int main(int argc, char** argv) {
             std::printf("object %u morphed over %u targets\n", head[0], head[1]);
             return 0;
         }
+        if (argc >= 7 && std::string(argv[1]) == "smooth") { // smooth <scene> <data_dir> <labels> <pose.f32> <geometry.f32> [rebuild] (tests)
+            // labels: u32 object, has_labels; u32 vertex_ids[T][3] for the object's T triangles if has_labels, else the object is
+            // welded by its rest positions and normals. pose.f32: transform[16] column-major and the scale, for that object.
+            Project project = make_scene(argv[2], argv[3]);
+            std::unique_ptr<World> world = World::from_project(project.world, argv[3]);
+            const auto slurp = [](const char* path) {
+                std::ifstream in(path, std::ios::binary);
+                return std::vector<char>((std::istreambuf_iterator<char>(in)), std::istreambuf_iterator<char>());
+            };
+            const std::vector<char> labels = slurp(argv[4]), posed = slurp(argv[5]);
+            uint32_t head[2] = {0, 0};
+            if (labels.size() < 8) throw ProjectError("smooth: the labels file is too short");
+            std::memcpy(head, labels.data(), 8);
+            if (head[0] >= world->objects().size()) throw ProjectError("smooth: no such object");
+            const size_t corners = 3 * (size_t)world->objects()[head[0]].range.num_triangles;
+            if (labels.size() != 8 + (head[1] ? corners * 4 : 0)) throw ProjectError("smooth: the labels file does not hold the object's corners");
+            if (posed.size() != 17 * 4) throw ProjectError("smooth: the pose file does not hold 17 floats");
+            std::vector<uint32_t> ids(head[1] ? corners : 0);
+            if (!ids.empty()) std::memcpy(ids.data(), labels.data() + 8, corners * 4);
+            World::ObjectPose pose;
+            std::memcpy(pose.transform, posed.data(), 64);
+            std::memcpy(&pose.scale, posed.data() + 64, 4);
+            world->set_smoothing({{head[0], ids}});
+            world->pose({{head[0], pose}}, argc >= 8 && std::string(argv[7]) == "rebuild" ? World::Update::Rebuild : World::Update::Refit);
+            const World::Geometry g = world->geometry();
+            std::ofstream out(argv[6], std::ios::binary);
+            for (const std::vector<float>* a : {&g.positions, &g.normals, &g.frames, &g.spheres}) out.write(reinterpret_cast<const char*>(a->data()), (std::streamsize)(a->size() * 4));
+            std::printf("object %u smoothed over %zu corners\n", head[0], corners);
+            return 0;
+        }
         if (argc >= 6 && std::string(argv[1]) == "intersect") { // intersect <scene> <data_dir> <rays.f32> <hits.bin>
             Project project = make_scene(argv[2], argv[3]);
             std::unique_ptr<World> world = World::from_project(project.world, argv[3]);

@@ -1,9 +1,10 @@
-// pose.hip -- posing a live scene's objects, skinning its meshes and morphing them on the device (DESIGN.md sections 9g, 9h and 9p), a unit of its own: every primitive of an object
+// pose.hip -- posing a live scene's objects, skinning its meshes, morphing them and recomputing their normals on the device (DESIGN.md sections 9g, 9h, 9p and 9q), a unit of its own: every primitive of an object
 // is computed from the rest pose (where the scene has morphs: from the morphed rest, which the morph kernel writes first) by pose_rules.h and written to the scene's staging arrays, from where the refit of section 9f
 // (kernels/refit.hip) rewrites the records and the boxes; the records of shape lamps follow from the staging arrays too. Nothing
 // here touches a record the render kernels read except the lamp records, and those only after the host has seen the flag clear.
 //
-// One lane per primitive of an object, each lane stores to its own primitive only; the only word two lanes share is the flag,
+// One lane per primitive of an object, each lane stores to its own primitive only (the smoothing kernel, which runs after them:
+// one lane per group of corners, each lane stores to its own group's corners only); the only word two lanes share is the flag,
 // which is an OR. No kernel waits for another workgroup.
 #include "pose_launch.h"
 
@@ -240,6 +241,69 @@ __global__ __launch_bounds__(kBlock) void morph_triangles_kernel(MorphCtx c) {
     if (threadIdx.x == 0 && block_flag != 0u) atomicOr(c.flag, block_flag);
 }
 
+// raise_flag for a kernel whose lanes raise more than bit 0: the workgroup's OR of `mine` in LDS, then one atomic on the scene's word
+__device__ __forceinline__ void raise_flag_bits(uint32_t mine, uint32_t* block_flag, uint32_t* flag) {
+    if (mine) atomicOr(block_flag, mine);
+    __syncthreads();
+    if (threadIdx.x == 0 && *block_flag != 0u) atomicOr(flag, *block_flag);
+}
+
+// ---- one lane per group of a smoothing, after the kernels above have written the staging arrays: the lane
+// walks its row of the corner table twice. First it sums the signed face vectors of the corners' triangles (pose_rules.h
+// signed_face_vector over the triangle's nine staged position dwords), in the row's order, starting from the first one. Then it
+// gives every corner of the row the normalised sum -- three dwords into the corner's slot of the staged normals -- and, where the
+// scene keeps frames, rebuilds the corner's 16-byte staged frame against it (morph_normal_frame). A lane stores to the corners of
+// its own group only and reads positions only, which this kernel does not write; sums are in a fixed order, so there is no float
+// atomic. The row is compared against the table's size and every corner's triangle against the scene's count before either is
+// used (the host's packing makes both hold: bit 0 of the flag otherwise, and the corner is left out).
+__global__ __launch_bounds__(kBlock) void smooth_normals_kernel(SmoothCtx c) {
+    __shared__ uint32_t block_flag;
+    if (threadIdx.x == 0) block_flag = 0u;
+    __syncthreads();
+    const uint32_t lane = blockIdx.x * kBlock + threadIdx.x;
+    uint32_t bad = 0u;
+    if (lane < c.num_groups) {
+        const uint32_t begin = c.group_begin[lane], end = c.group_begin[lane + 1];
+        if (begin <= end && end <= c.num_corners) {
+            float m[3] = {0.0f, 0.0f, 0.0f};
+            bool any = false;
+            for (uint32_t k = begin; k < end; ++k) {
+                const uint32_t word = c.group_corners[k], triangle = (word & ~kNegated) / 3u;
+                if (triangle >= c.num_triangles) {
+                    bad |= 1u;
+                    continue;
+                }
+                const float* from = c.positions + 9 * (size_t)triangle;
+                float p[9], f[3];
+                for (int a = 0; a < 9; ++a) p[a] = from[a];
+                pose::signed_face_vector(p, (word & kNegated) != 0u, f);
+                if (any)
+                    m[0] = m[0] + f[0], m[1] = m[1] + f[1], m[2] = m[2] + f[2];
+                else
+                    m[0] = f[0], m[1] = f[1], m[2] = f[2], any = true;
+            }
+            float shared[3] = {m[0], m[1], m[2]}; // a scene without frames: every corner gets the same three words
+            if (any && !c.frames && pose::morph_normal_frame(shared, nullptr)) bad |= 4u;
+            for (uint32_t k = begin; any && k < end; ++k) {
+                const uint32_t corner = c.group_corners[k] & ~kNegated;
+                if (corner / 3u >= c.num_triangles) continue;
+                float n[3] = {shared[0], shared[1], shared[2]};
+                if (c.frames) {
+                    const float4_t q4 = load4(c.frames + 4 * (size_t)corner);
+                    float q[4] = {q4.x, q4.y, q4.z, q4.w};
+                    if (pose::morph_normal_frame(n, q)) bad |= 4u;
+                    store4(c.frames + 4 * (size_t)corner, float4_t{q[0], q[1], q[2], q[3]});
+                }
+                float* out = c.normals + 3 * (size_t)corner;
+                out[0] = n[0], out[1] = n[1], out[2] = n[2];
+            }
+        } else {
+            bad |= 1u;
+        }
+    }
+    raise_flag_bits(bad, &block_flag, c.flag);
+}
+
 // ---- one lane per sphere of an object
 __global__ __launch_bounds__(kBlock) void pose_spheres_kernel(Ctx c) {
     __shared__ uint32_t block_flag;
@@ -304,6 +368,11 @@ hipError_t launch_pose(const Ctx& c, hipStream_t stream) {
     if (c.posed_triangles) hipLaunchKernelGGL(pose_triangles_kernel, dim3(blocks_for(c.posed_triangles)), dim3(kBlock), 0, stream, c);
     if (c.skinned_triangles) hipLaunchKernelGGL(skin_triangles_kernel, dim3(blocks_for(c.skinned_triangles)), dim3(kBlock), 0, stream, c);
     if (c.posed_spheres) hipLaunchKernelGGL(pose_spheres_kernel, dim3(blocks_for(c.posed_spheres)), dim3(kBlock), 0, stream, c);
+    return hipGetLastError();
+}
+
+hipError_t launch_smooth(const SmoothCtx& c, hipStream_t stream) {
+    if (c.num_groups) hipLaunchKernelGGL(smooth_normals_kernel, dim3(blocks_for(c.num_groups)), dim3(kBlock), 0, stream, c);
     return hipGetLastError();
 }
 

@@ -94,9 +94,27 @@ struct MorphCtx {
     uint32_t* flag; // the pose kernels' word: bit 0 as there; bit 1 (value 2): a morphed normal or tangent that cannot be normalised
 };
 
+// What the smoothing kernel reads and writes: the staged positions as the morph, skin and pose kernels left
+// them, the staged normals and frames it rewrites for the corners of smoothed objects, and the groups as a CSR -- group g's corners
+// are group_corners[group_begin[g] .. group_begin[g + 1]), ascending. A corner is 3 * triangle + vertex over the scene's triangles,
+// with bit 31 set where the triangle's face vector is negated (kNegated). The kernel compares a row against num_corners and a
+// corner's triangle against num_triangles before it uses either.
+constexpr uint32_t kNegated = 0x80000000u;
+struct SmoothCtx {
+    const float* positions; // staging, [num_triangles][3][3]
+    float* normals;         // staging, the same shape
+    float* frames;          // staging, [num_triangles][3][4], or nullptr: the scene keeps none
+    const uint32_t* group_begin;   // [num_groups + 1]
+    const uint32_t* group_corners; // [num_corners]
+    uint32_t num_groups, num_corners;
+    uint32_t num_triangles; // the scene's count
+    uint32_t* flag; // the pose kernels' word: bit 0 as there; bit 2 (value 4): a recomputed normal or tangent that cannot be normalised
+};
+
 // Each enqueues on `stream` and returns hipGetLastError().
 hipError_t launch_morph(const MorphCtx& c, hipStream_t stream); // every morph's triangles from rest into the morphed rest
 hipError_t launch_pose(const Ctx& c, hipStream_t stream);  // triangles and spheres of every object, skinned or posed, into the staging arrays
+hipError_t launch_smooth(const SmoothCtx& c, hipStream_t stream); // the normals and frames of every smoothed object from the staged positions
 hipError_t launch_lamps(const Ctx& c, hipStream_t stream); // the records of shape lamps from the staging arrays
 
 } // namespace devpose

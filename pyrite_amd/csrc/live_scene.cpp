@@ -1,11 +1,12 @@
 // live_scene.cpp -- everything that moves a scene after creation: pyr_scene_update[_device], pyr_scene_set_objects,
-// pyr_scene_pose, pyr_scene_set_skins, pyr_scene_skin, pyr_scene_set_morphs, pyr_scene_morph, pyr_scene_geometry, pyr_scene_update_info -- and pyr_scene_keep_previous,
+// pyr_scene_pose, pyr_scene_set_skins, pyr_scene_skin, pyr_scene_set_morphs, pyr_scene_morph, pyr_scene_set_smoothing, pyr_scene_geometry, pyr_scene_update_info -- and pyr_scene_keep_previous,
 // which copies where the geometry is now for the motion pass (api.cpp enqueues that one). LiveGeometry
 // (scene_internal.h) says where the geometry is and which copies are valid; rebuild_from and refit_from are the two ways new
 // arrays reach the records and trees on the device.
 #include <algorithm>
 #include <cmath>
 #include <cstring>
+#include <unordered_map>
 
 #include "bvh_level.h"
 #include "kernels/refit_launch.h"
@@ -58,10 +59,17 @@ void LiveGeometry::forget_morphs() {
     for (DeviceBuffer& b : morphed_rest) b.release();
 }
 
+void LiveGeometry::forget_smoothing() {
+    smoothed_objects.clear();
+    smooth_groups = smooth_corners = 0;
+    smooth_begin.release(), smooth_corners_table.release();
+}
+
 void LiveGeometry::forget_objects() {
     pose_table.clear();
     forget_skins();
     forget_morphs();
+    forget_smoothing();
     posed_triangles = posed_spheres = 0;
     for (LiveArray& a : arrays) a.rest.release();
     pose_objects.release();
@@ -414,10 +422,23 @@ devpose::MorphCtx morph_context(PyrScene* s, uint32_t num_active) {
     return c;
 }
 
+devpose::SmoothCtx smooth_context(PyrScene* s) {
+    const LiveGeometry& live = s->live;
+    devpose::SmoothCtx c{};
+    c.positions = (const float*)live.arrays[POSITIONS].staging.ptr, c.normals = (float*)live.arrays[NORMALS].staging.ptr;
+    c.frames = live.arrays[FRAMES].kept ? (float*)live.arrays[FRAMES].staging.ptr : nullptr;
+    c.group_begin = (const uint32_t*)live.smooth_begin.ptr, c.group_corners = (const uint32_t*)live.smooth_corners_table.ptr;
+    c.num_groups = live.smooth_groups, c.num_corners = live.smooth_corners;
+    c.num_triangles = live.num_triangles;
+    c.flag = (uint32_t*)live.pose_flag.ptr;
+    return c;
+}
+
 // Every object's primitives from the rest pose into the staging arrays under `table` and, where the scene has skins, under
 // `joints` ([joints][16]), and the flag back: the one wait. Where the scene has morphs, their triangles go from the rest pose into
 // the morphed rest under `weights` first (the morphs' targets one after the other), and the other kernels start from there. A skinned object's triangles have their lanes in the skin kernel's
-// launch, so the table the pose kernels read gives that object none.
+// launch, so the table the pose kernels read gives that object none. Where the scene has a smoothing, the normals and frames of
+// its objects are recomputed from the staged positions last.
 int run_pose(PyrScene* s, const std::vector<devpose::DevObject>& table, const std::vector<float>& joints, const std::vector<float>& weights, hipStream_t stream,
              uint32_t& beyond_range) {
     const LiveGeometry& live = s->live;
@@ -471,14 +492,22 @@ int run_pose(PyrScene* s, const std::vector<devpose::DevObject>& table, const st
     }
     const hipError_t e = devpose::launch_pose(pose_context(s), stream);
     if (e != hipSuccess) return hip_fail(e, "pose kernels");
+    if (live.smooth_groups) {
+        const hipError_t es = devpose::launch_smooth(smooth_context(s), stream);
+        if (es != hipSuccess) return hip_fail(es, "smoothing kernel");
+    }
     HIP_TRY(hipMemcpyAsync(&beyond_range, s->live.pose_flag.ptr, 4, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return PYR_OK;
 }
 
-// Bit 0 of the flag word: a bound beyond the coordinate range; bit 1 alone: a morphed normal that cannot be normalised.
+// Bit 0 of the flag word: a bound beyond the coordinate range; bit 1 without it: a morphed normal that cannot be normalised; bit 2
+// without either: a recomputed normal that cannot be.
 const char* const kMorphedNormalMessage =
     "a morphed normal or the tangent frame rebuilt against it has a squared length outside 1e-30 .. 1e30 and cannot be normalised (pyrite_gpu.h, pyr_scene_morph)";
+
+const char* const kRecomputedNormalMessage =
+    "a recomputed normal or the tangent frame rebuilt against it has a squared length outside 1e-30 .. 1e30 and cannot be normalised (pyrite_gpu.h, pyr_scene_set_smoothing)";
 
 // pyr_scene_pose, pyr_scene_skin and pyr_scene_morph: `poses` nullptr keeps the poses the scene is in, `new_joints` nullptr its
 // joints, `new_weights` nullptr its morph weights.
@@ -502,7 +531,8 @@ int scene_pose(PyrScene* s, uint32_t mode, const PyrObjectPose* poses, const flo
         return back != PYR_OK ? back : why;
     };
     if (beyond_range & 1u) return refused(fail(PYR_ERR_UNSUPPORTED, kCoordinateRangeMessage));
-    if (beyond_range != 0) return refused(fail(PYR_ERR_UNSUPPORTED, kMorphedNormalMessage));
+    if (beyond_range & 2u) return refused(fail(PYR_ERR_UNSUPPORTED, kMorphedNormalMessage));
+    if (beyond_range != 0) return refused(fail(PYR_ERR_UNSUPPORTED, kRecomputedNormalMessage));
     PyrUpdateInfo info{};
     info.mode_used = mode;
     info.area_ratio = 1.0;
@@ -589,6 +619,26 @@ int check_morphs(const LiveGeometry& live, const PyrMorph* morphs, uint32_t n) {
             for (size_t i = 0; deltas && i < words; ++i)
                 if (!std::isfinite(deltas[i])) return fail(PYR_ERR_INVALID_ARGUMENT, deltas == morphs[k].position_deltas ? "PyrMorph.position_deltas has a delta that is not finite" : "PyrMorph.normal_deltas has a delta that is not finite");
     }
+    return PYR_OK;
+}
+
+// What pyr_scene_set_smoothing refuses of the smoothings themselves, in the order pyrite_gpu.h gives.
+int check_smoothings(const LiveGeometry& live, const PyrSmoothing* smoothings, uint32_t n) {
+    for (uint32_t k = 0; k < n; ++k) {
+        if (smoothings[k].reserved0 != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSmoothing.reserved must be zero");
+        for (uint32_t word : smoothings[k].reserved)
+            if (word != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSmoothing.reserved must be zero");
+    }
+    for (uint32_t k = 0; k < n; ++k)
+        if (smoothings[k].object >= live.pose_table.size()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSmoothing.object is not one of the scene's objects");
+    for (uint32_t k = 0; k < n; ++k)
+        if (live.pose_table[smoothings[k].object].num_triangles == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSmoothing.object: the object has no triangles");
+    std::vector<uint32_t> taken;
+    for (uint32_t k = 0; k < n; ++k) taken.push_back(smoothings[k].object);
+    std::sort(taken.begin(), taken.end());
+    if (std::adjacent_find(taken.begin(), taken.end()) != taken.end()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSmoothing.object: two smoothings on one object");
+    for (uint32_t k = 0; k < n; ++k)
+        if (!smoothings[k].vertex_ids) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSmoothing.vertex_ids is null");
     return PYR_OK;
 }
 
@@ -755,6 +805,58 @@ int pyr_scene_morph(PyrScene* scene, const PyrMorphUpdate* update, void* hip_str
     int rc = check_morph_args(scene, update);
     if (rc != PYR_OK) return rc;
     return scene_pose(scene, update->mode, update->poses, update->joints, update->weights, (hipStream_t)hip_stream);
+}
+
+int pyr_scene_set_smoothing(PyrScene* scene, const PyrSmoothing* smoothings, uint32_t num_smoothings) {
+    if (num_smoothings != 0 && !smoothings) return fail(PYR_ERR_INVALID_ARGUMENT, "null smoothings with a non-zero num_smoothings");
+    if (!scene) return fail(PYR_ERR_INVALID_ARGUMENT, "null scene");
+    LiveGeometry& live = scene->live;
+    if (live.pose_table.empty()) return fail(PYR_ERR_INVALID_ARGUMENT, "pyr_scene_set_smoothing: the scene has no objects (pyr_scene_set_objects names them)");
+    int rc = check_smoothings(live, smoothings, num_smoothings);
+    if (rc != PYR_OK) return rc;
+    if (num_smoothings == 0 && live.smoothed_objects.empty()) return PYR_OK;
+    HIP_TRY(hipSetDevice(scene->device));
+    HIP_TRY(hipDeviceSynchronize()); // an earlier call's kernels may still read the groups
+    if (num_smoothings == 0) {
+        live.forget_smoothing();
+        return PYR_OK;
+    }
+    // the groups one smoothing after the other: a group's number is its rank by first corner within its object, so neighbouring
+    // lanes touch neighbouring triangles whatever the caller's labels are; rows are filled in ascending corner order
+    std::vector<uint32_t> objects, begin(1, 0u), corners;
+    std::vector<float> rest_p, rest_n;
+    for (uint32_t k = 0; k < num_smoothings; ++k) {
+        const devpose::DevObject& o = live.pose_table[smoothings[k].object];
+        const size_t words = 9 * (size_t)o.num_triangles, count = 3 * (size_t)o.num_triangles;
+        rest_p.resize(words), rest_n.resize(words); // the orientation is the rest pose's: the device copy taken when objects were named
+        HIP_TRY(hipMemcpy(rest_p.data(), (const float*)live.arrays[POSITIONS].rest.ptr + 9 * (size_t)o.first_triangle, words * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(rest_n.data(), (const float*)live.arrays[NORMALS].rest.ptr + 9 * (size_t)o.first_triangle, words * 4, hipMemcpyDeviceToHost));
+        const uint32_t* ids = smoothings[k].vertex_ids;
+        std::unordered_map<uint32_t, uint32_t> group_of; // label -> group within this object, numbered by first appearance
+        std::vector<uint32_t> group(count), size;
+        for (size_t i = 0; i < count; ++i) {
+            const auto found = group_of.emplace(ids[i], (uint32_t)size.size());
+            if (found.second) size.push_back(0u);
+            group[i] = found.first->second, ++size[group[i]];
+        }
+        std::vector<uint32_t> fill(size.size());
+        for (size_t g = 0; g < size.size(); ++g) fill[g] = begin.back(), begin.push_back(begin.back() + size[g]);
+        corners.resize(begin.back());
+        for (size_t i = 0; i < count; ++i) {
+            const size_t t = i / 3;
+            const bool negated = pose::face_negated(&rest_p[9 * t], &rest_n[9 * t]);
+            corners[fill[group[i]]++] = (3u * o.first_triangle + (uint32_t)i) | (negated ? devpose::kNegated : 0u); // below 3 * 2^28
+        }
+        objects.push_back(smoothings[k].object);
+    }
+    DeviceBuffer fresh[2]; // on the device before anything of the old smoothing is let go
+    if ((rc = fresh[0].upload(begin.data(), begin.size() * 4)) != PYR_OK) return rc;
+    if ((rc = fresh[1].upload(corners.data(), corners.size() * 4)) != PYR_OK) return rc;
+    DeviceBuffer* const own[2] = {&live.smooth_begin, &live.smooth_corners_table};
+    for (int k = 0; k < 2; ++k) std::swap(own[k]->ptr, fresh[k].ptr), std::swap(own[k]->bytes, fresh[k].bytes);
+    live.smoothed_objects.swap(objects);
+    live.smooth_groups = (uint32_t)begin.size() - 1u, live.smooth_corners = (uint32_t)corners.size();
+    return PYR_OK;
 }
 
 int pyr_scene_geometry(PyrScene* scene, float* tri_positions, float* tri_normals, float* tri_frames, float* spheres) {

@@ -1,5 +1,6 @@
 // pose_rules.h -- what a pose does to one vertex, one sphere and one lamp, how a skin blends a vertex's
-// matrix (section 9h) and what a morphed normal does to its tangent frame (section 9p), as functions of one record: the
+// matrix (section 9h), what a morphed normal does to its tangent frame (section 9p) and the face vector a recomputed normal
+// sums (section 9q), as functions of one record: the
 // pose kernels (kernels/pose.hip) and the host rehearsal (tests/probes/pose_check.cpp) both compile these, so what they compute
 // can differ only in the square root and the reciprocal -- sqrt32 / rcp32 of exact_math.h on the device, std::sqrt and 1.0f / x on
 // the host, bit-identical in the ranges exact_math.h names.
@@ -180,6 +181,29 @@ PYR_POSE_HD bool morph_normal_frame(float* n, float* frame) {
     normalize(y);
     quat_from_cols(x, y, n, frame);
     return bad;
+}
+
+// ---- the smoothing rule: a vertex normal recomputed from where the surface is, as the sum of the face
+// vectors of the triangles that share the vertex. A face vector is cross(p1 - p0, p2 - p0) -- twice the triangle's area along its
+// geometric normal, so the sum is area-weighted -- and a triangle wound against its rest normals has its face vector negated:
+// face_negated decides that once, from the rest pose (d of zero or NaN does not negate). The caller sums a group's face vectors
+// in ascending corner order, starting from the first one (not from zero: 0 + (-0) loses a sign bit), and hands the sum to
+// morph_normal_frame above, which normalises it, rebuilds the corner's tangent frame against it and range-checks what it
+// normalises (bit 2 of the flag word here).
+PYR_POSE_HD void face_vector(const float* p, float* c) {
+    const float a[3] = {p[3] - p[0], p[4] - p[1], p[5] - p[2]}, b[3] = {p[6] - p[0], p[7] - p[1], p[8] - p[2]};
+    cross(a, b, c);
+}
+PYR_POSE_HD bool face_negated(const float* rest_p, const float* rest_n) {
+    float c[3];
+    face_vector(rest_p, c);
+    const float r[3] = {(rest_n[0] + rest_n[3]) + rest_n[6], (rest_n[1] + rest_n[4]) + rest_n[7], (rest_n[2] + rest_n[5]) + rest_n[8]};
+    const float d = (c[0] * r[0] + c[1] * r[1]) + c[2] * r[2];
+    return d < 0.0f;
+}
+PYR_POSE_HD void signed_face_vector(const float* p, bool negated, float* c) {
+    face_vector(p, c);
+    if (negated) c[0] = -c[0], c[1] = -c[1], c[2] = -c[2];
 }
 
 // ---- the per-sphere rule: radius *= scale; centre *= scale; centre = transform_point(centre)

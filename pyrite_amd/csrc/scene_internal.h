@@ -124,6 +124,12 @@ struct LiveGeometry {
     uint64_t morph_position_rows = 0, morph_normal_rows = 0;
     DeviceBuffer morph_table, morph_active, morph_positions, morph_normals; // DevMorph records, a frame's pairs, the deltas as uploaded
     DeviceBuffer morphed_rest[3];
+    // the smoothing (pyr_scene_set_smoothing): which objects have their normals recomputed, and the groups of their corners as a
+    // CSR on the device -- smooth_begin [smooth_groups + 1], smooth_corners_table [smooth_corners], a corner being 3 * triangle +
+    // vertex over the scene's triangles with devpose::kNegated set where the triangle's face vector is negated
+    std::vector<uint32_t> smoothed_objects;
+    uint32_t smooth_groups = 0, smooth_corners = 0;
+    DeviceBuffer smooth_begin, smooth_corners_table;
     // the previous frame (pyr_scene_keep_previous): positions and spheres as they were when it was called, the description's order.
     // Nothing that moves the scene touches them -- counts and indices never change -- and only the motion pass reads them.
     DeviceBuffer previous_positions, previous_spheres;
@@ -133,9 +139,10 @@ struct LiveGeometry {
     size_t kept_floats(int k) const { return arrays[k].kept ? floats(k) : 0; }
     void keep(const PyrSceneDesc* d); // scene creation: the description's geometry
     PyrSceneDesc view(const float* const with[NUM_ARRAYS] = nullptr) const; // what pack_geometry and pack_lamp read; `with`: arrays in place of the scene's own
-    void forget_objects(); // (adopted() does it: new arrays are a new geometry, not a pose of the old one); forgets the skins and the morphs too
+    void forget_objects(); // (adopted() does it: new arrays are a new geometry, not a pose of the old one); forgets the skins, the morphs and the smoothing too
     void forget_skins();
     void forget_morphs();
+    void forget_smoothing();
     bool host_current() const { return host_current_; }
     bool positions_staged() const { return positions_staged_; }
     bool schedule_current() const { return schedule_current_; }

@@ -17,6 +17,22 @@ from .compiler import FlatScene, camera_from_project, renderer_from_project
 from .film import Film
 
 
+def weld(positions, normals):
+    """Corner labels for `World.set_smoothing` from a mesh's own arrays: `positions` and `normals` are [n,3,3] or [n,9] float32,
+    and two corners get the same label exactly when all six words -- the bits of position and normal -- agree. Returns uint32
+    [n,3]; a label is the index of the first corner of its group. A mesh whose rest normals break along an edge keeps that
+    crease, since the corners on its two sides differ in their normals."""
+    p = np.ascontiguousarray(positions, dtype=np.float32).reshape(-1, 3)
+    n = np.ascontiguousarray(normals, dtype=np.float32).reshape(-1, 3)
+    if p.shape != n.shape or len(p) % 3:
+        raise ValueError("weld needs positions and normals of one shape [n,3,3], not %r and %r" % (np.shape(positions), np.shape(normals)))
+    if len(p) == 0:
+        return np.zeros((0, 3), dtype=np.uint32)
+    words = np.concatenate([p, n], axis=1).view(np.uint32)
+    _, first, inverse = np.unique(words, axis=0, return_index=True, return_inverse=True)
+    return first[inverse.reshape(-1)].astype(np.uint32).reshape(-1, 3)
+
+
 class World:
     """World::from_project (world.rs:39-271) result. Device scenes are created lazily, one per device."""
 
@@ -31,6 +47,8 @@ class World:
         self._joints = {}  # object index -> float32 [J,16] column-major: the joints the scenes are in; identity where absent
         self._morphs = {}  # object index -> dict(positions float32 [T,n,3,3], normals float32 [T,n,3,3] | None): the targets (World.set_morphs)
         self._weights = {}  # object index -> float32 [T]: the weights the scenes are in; zero where absent
+        self._smoothing = {}  # object index -> uint32 [n,3]: the corner labels (World.set_smoothing)
+        self._smooth_frame = False  # a pose, skin or morph has run since the smoothing was set: the scenes hold recomputed normals
 
     @classmethod
     def from_project(cls, world, base_dir="."):
@@ -65,11 +83,13 @@ class World:
                     self._set_skins(handle, self._skins)
                 if self._morphs:
                     self._set_morphs(handle, self._morphs)
+                if self._smoothing:
+                    self._set_smoothing(handle, self._smoothing)
                 if any(np.any(w != 0) for w in self._weights.values()):
                     self._morph(handle, self._weights, self._joints if self._skins else None, self._poses, "rebuild", 0)
                 elif self._joints:
                     self._skin(handle, self._joints, self._poses, "rebuild", 0)
-                elif self._poses:
+                elif self._poses or self._smooth_frame:  # (a smoothed object's normals are recomputed under the identity too)
                     self._pose(handle, self._poses, "rebuild", 0)
         elif build is not None and build != self._builders[key]:
             raise ValueError("the scene on device %r was created with build=%r" % (device, self._builders[key]))
@@ -106,7 +126,7 @@ class World:
     def set_objects(self, objects=None):
         """Names other primitive ranges as the objects (pyr_scene_set_objects on every scene of this world; None: the records of
         the description again). The geometry as it is now becomes the rest pose, and every pose is the identity again."""
-        if (self._poses or self._joints or self._weights) and self._scenes:  # every scene of this world is in the same pose: `flat` follows the first
+        if (self._poses or self._joints or self._weights or self._smooth_frame) and self._scenes:  # every scene of this world is in the same pose: `flat` follows the first
             self._follow(self._geometry(next(iter(self._scenes.values()))))
         objects = [dict(o) for o in (self.flat.objects if objects is None else objects)]
         for handle in self._scenes.values():
@@ -114,6 +134,7 @@ class World:
         self._objects, self._poses = objects, {}
         self._skins, self._joints = {}, {}  # skins hang on objects: pyr_scene_set_objects forgot them
         self._morphs, self._weights = {}, {}  # and so do morphs
+        self._smoothing, self._smooth_frame = {}, False  # and the smoothing
 
     def _follow(self, arrays):
         for name, attr in (("positions", "tri_positions"), ("normals", "tri_normals"), ("frames", "tri_frames"), ("spheres", "spheres")):
@@ -154,6 +175,7 @@ class World:
         named = {int(k): (None if v[0] is None else np.array(v[0], dtype=np.float32), float(v[1])) for k, v in poses.items()}
         self._pose(self.scene(device), named, mode, stream)
         self._poses = named
+        self._smooth_frame = bool(self._smoothing)
 
     def keep_previous(self, keep=True, device=0):
         """Keeps the geometry of the scene on `device` as it is now as the previous frame's (pyr_scene_keep_previous): the
@@ -226,6 +248,7 @@ class World:
         named = self._poses if poses is None else {int(k): (None if v[0] is None else np.array(v[0], dtype=np.float32), float(v[1])) for k, v in poses.items()}
         self._skin(self.scene(device), tables, named, mode, stream)
         self._poses, self._joints = named, tables
+        self._smooth_frame = bool(self._smoothing)
 
     def _set_morphs(self, handle, morphs):
         order = sorted(morphs)
@@ -295,8 +318,50 @@ class World:
         named = self._poses if poses is None else {int(k): (None if v[0] is None else np.array(v[0], dtype=np.float32), float(v[1])) for k, v in poses.items()}
         self._morph(self.scene(device), merged, tables, named, mode, stream)
         self._weights, self._poses = merged, named
+        self._smooth_frame = bool(self._smoothing)
         if tables is not None:
             self._joints = tables
+
+    def _set_smoothing(self, handle, smoothing):
+        order = sorted(smoothing)
+        records = (abi.PyrSmoothing * max(1, len(order)))()
+        for k, index in enumerate(order):
+            records[k] = abi.PyrSmoothing(object=index, vertex_ids=smoothing[index].ctypes.data)
+        check(lib().pyr_scene_set_smoothing(handle, records, len(order)))
+
+    def _rest_of(self, index):
+        """(positions [n,9], normals [n,9]) of an object's triangles in the rest pose, which `World.flat` stays."""
+        o = self._objects[index]
+        t0, n = o.get("first_triangle", 0), o.get("num_triangles", 0)
+        cat = lambda rows: np.concatenate([np.asarray(r, dtype=np.float32).reshape(-1, 9) for r in rows]) if len(rows) else np.zeros((0, 9), dtype=np.float32)  # noqa: E731
+        return cat(self.flat.tri_positions)[t0:t0 + n], cat(self.flat.tri_normals)[t0:t0 + n]
+
+    def set_smoothing(self, smoothing):
+        """Has the normals of meshes recomputed from where their surface is (pyr_scene_set_smoothing on every scene of this
+        world): `smoothing` maps an object's index in `World.objects` to one label per corner of that object's n triangles,
+        integers [n,3] -- corners with equal labels share a vertex normal, the area-weighted sum of their triangles' face
+        vectors -- or to None: `weld` of the object's rest positions and rest normals, which keeps the creases the rest normals
+        already have. From then on every `pose`, `skin` and `morph` recomputes those objects' normals and tangent frames on the
+        GPU from the positions of the frame, also under the identity. The geometry does not change at this call; an empty dict
+        forgets the smoothing, and so do `set_objects` and an `update` that carries arrays."""
+        held = {}
+        for index, ids in smoothing.items():
+            if not 0 <= int(index) < len(self._objects):
+                raise ValueError("no object %r: the world has %d" % (index, len(self._objects)))
+            n = self._objects[int(index)].get("num_triangles", 0)
+            if n == 0:
+                raise ValueError("object %r has no triangles to smooth" % (index,))
+            if ids is None:
+                ids = weld(*self._rest_of(int(index)))
+            ids = np.asarray(ids)
+            if ids.shape != (n, 3) or ids.dtype.kind not in "iu" or (ids.size and (ids.min() < 0 or ids.max() > 0xFFFFFFFF)):
+                raise ValueError("the smoothing of object %r needs uint32 labels of shape (%d, 3), not %s %r" % (index, n, ids.dtype, ids.shape))
+            held[int(index)] = np.ascontiguousarray(ids, dtype=np.uint32)
+        for handle in self._scenes.values():
+            self._set_smoothing(handle, held)
+        self._smoothing = held
+        if not held:
+            self._smooth_frame = False
 
     def geometry(self, device=0):
         """The geometry of the scene on `device` as it is now (pyr_scene_geometry): a dict of float32 arrays `positions` [n,9],
@@ -358,6 +423,7 @@ class World:
             self._poses = {}  # new arrays are a new geometry, not a pose of the old one: the scene forgot its objects (set_objects names them again)
             self._skins, self._joints = {}, {}
             self._morphs, self._weights = {}, {}
+            self._smoothing, self._smooth_frame = {}, False
         for name, attr in (("positions", "tri_positions"), ("normals", "tri_normals"), ("frames", "tri_frames"), ("spheres", "spheres")):
             if name in host:
                 setattr(self.flat, attr, [host[name].copy()])
