@@ -362,14 +362,17 @@ class World { // world.rs:31-36
     std::map<size_t, std::vector<uint32_t>> smoothing_; // the corner labels (set_smoothing)
     bool smooth_frame_ = false;                     // a pose, skin or morph has run since: the scenes hold recomputed normals
     std::vector<PyrObjectPose> pose_records(const std::map<size_t, ObjectPose>& poses) const;
-    void pose_scene(PyrScene* handle, const std::map<size_t, ObjectPose>& poses, Update mode, void* hip_stream);
     void set_skins_on(PyrScene* handle, const std::map<size_t, Skin>& skins);
-    void skin_scene(PyrScene* handle, const std::map<size_t, std::vector<float>>& joints, const std::map<size_t, ObjectPose>& poses, Update mode, void* hip_stream);
     std::vector<float> joint_table(const std::map<size_t, std::vector<float>>& joints) const;
     void set_morphs_on(PyrScene* handle, const std::map<size_t, Morph>& morphs);
     void set_smoothing_on(PyrScene* handle, const std::map<size_t, std::vector<uint32_t>>& smoothing);
-    void morph_scene(PyrScene* handle, const std::map<size_t, std::vector<float>>& weights, const std::map<size_t, std::vector<float>>* joints,
-                     const std::map<size_t, ObjectPose>& poses, Update mode, void* hip_stream);
+    // pose, skin and morph are one frame: `entry` says which of pyr_scene_pose, pyr_scene_skin and pyr_scene_morph runs and names the
+    // errors; a table the entry has not, or a nullptr, keeps what the world is in. send_frame fills the widest update the entry has.
+    enum class Entry { Pose, Skin, Morph };
+    using Tables = std::map<size_t, std::vector<float>>;
+    void frame(Entry entry, const Tables* weights, const Tables* joints, const std::map<size_t, ObjectPose>* poses, Update mode, int device, void* hip_stream);
+    void send_frame(PyrScene* handle, Entry entry, const Tables& weights, const Tables* joints, const std::map<size_t, ObjectPose>& poses, Update mode, void* hip_stream);
+    void forget(); // every pose is the identity again, and what hangs on objects is gone
 };
 
 struct Camera { // cameras.rs:20-27

@@ -28,6 +28,7 @@ struct DeviceBuffer {
     int upload(const void* src, size_t n); // (over an earlier allocation: that one is freed -- a rebuild uploads into the scene's buffers again)
     int alloc(size_t n);
     int reserve(size_t n); // holds `n` bytes afterwards: allocated once, kept while it is large enough
+    void swap(DeviceBuffer& other) { std::swap(ptr, other.ptr), std::swap(bytes, other.bytes); }
 };
 
 // Device a scene was created on.

@@ -1087,11 +1087,11 @@ PyrScene* World::scene(int device, int copy, std::optional<Build> build) {
         for (const auto& kv : weights_)
             for (float w : kv.second) morphed = morphed || w != 0.0f;
         if (morphed)
-            morph_scene(handle, weights_, skins_.empty() ? nullptr : &joints_, poses_, Update::Rebuild, nullptr);
+            send_frame(handle, Entry::Morph, weights_, skins_.empty() ? nullptr : &joints_, poses_, Update::Rebuild, nullptr);
         else if (!joints_.empty())
-            skin_scene(handle, joints_, poses_, Update::Rebuild, nullptr);
+            send_frame(handle, Entry::Skin, weights_, &joints_, poses_, Update::Rebuild, nullptr);
         else if (!poses_.empty() || smooth_frame_) // (a smoothed object's normals are recomputed under the identity too)
-            pose_scene(handle, poses_, Update::Rebuild, nullptr);
+            send_frame(handle, Entry::Pose, weights_, nullptr, poses_, Update::Rebuild, nullptr);
     }
     return handle;
 }
@@ -1116,8 +1116,9 @@ void World::update(const std::vector<float>& positions, const std::vector<float>
     u.spheres = spheres.empty() ? nullptr : spheres.data();
     check_status(pyr_scene_update(handle, &u));
     flat_.move_geometry(positions, normals, frames, spheres);
-    if (u.tri_positions || u.tri_normals || u.tri_frames || u.spheres) poses_.clear(), skins_.clear(), joints_.clear(), morphs_.clear(), weights_.clear(), smoothing_.clear(), smooth_frame_ = false; // a new geometry, not a pose of the old one: the scene forgot its objects (set_objects names them again)
+    if (u.tri_positions || u.tri_normals || u.tri_frames || u.spheres) forget(); // a new geometry, not a pose of the old one: the scene forgot its objects (set_objects names them again)
 }
+void World::forget() { poses_.clear(), skins_.clear(), joints_.clear(), morphs_.clear(), weights_.clear(), smoothing_.clear(), smooth_frame_ = false; }
 void World::set_objects() {
     if ((!poses_.empty() || !joints_.empty() || !weights_.empty() || smooth_frame_) && !scenes_.empty()) { // every scene of this world is in the same pose: flat() follows the first
         const Geometry g = geometry(scenes_.begin()->first.first);
@@ -1126,7 +1127,7 @@ void World::set_objects() {
     std::vector<PyrObjectRange> ranges;
     for (const FlatScene::Object& o : flat_.objects()) ranges.push_back(o.range);
     for (auto& kv : scenes_) check_status(pyr_scene_set_objects(kv.second, ranges.data(), (uint32_t)ranges.size()));
-    poses_.clear(), skins_.clear(), joints_.clear(), morphs_.clear(), weights_.clear(), smoothing_.clear(), smooth_frame_ = false; // skins, morphs and the smoothing hang on objects: pyr_scene_set_objects forgot them
+    forget(); // skins, morphs and the smoothing hang on objects: pyr_scene_set_objects forgot them
 }
 std::vector<PyrObjectPose> World::pose_records(const std::map<size_t, ObjectPose>& poses) const {
     std::vector<PyrObjectPose> records(flat_.objects().size());
@@ -1139,21 +1140,63 @@ std::vector<PyrObjectPose> World::pose_records(const std::map<size_t, ObjectPose
     }
     return records;
 }
-void World::pose_scene(PyrScene* handle, const std::map<size_t, ObjectPose>& poses, Update mode, void* hip_stream) {
+void World::send_frame(PyrScene* handle, Entry entry, const Tables& weights, const Tables* joints, const std::map<size_t, ObjectPose>& poses, Update mode, void* hip_stream) {
     const std::vector<PyrObjectPose> records = pose_records(poses);
-    PyrPoseUpdate u{};
+    const std::vector<float> joint_rows = joints ? joint_table(*joints) : std::vector<float>();
+    std::vector<float> table;
+    for (const auto& kv : morphs_) {
+        const auto it = weights.find(kv.first);
+        if (it != weights.end())
+            table.insert(table.end(), it->second.begin(), it->second.end());
+        else
+            table.insert(table.end(), kv.second.num_targets, 0.0f);
+    }
+    PyrMorphUpdate u{}; // the widest of the three updates; each entry takes what it has of it
     u.mode = mode == Update::Rebuild ? PYR_UPDATE_REBUILD : PYR_UPDATE_REFIT;
-    u.num_objects = (uint32_t)records.size();
-    u.poses = records.data();
-    check_status(pyr_scene_pose(handle, &u, hip_stream));
+    u.num_objects = (uint32_t)records.size(), u.poses = records.data();
+    u.joints = joints ? joint_rows.data() : nullptr, u.num_joints = (uint32_t)(joint_rows.size() / 16);
+    u.weights = table.data(), u.num_weights = (uint32_t)table.size();
+    if (entry == Entry::Pose) {
+        PyrPoseUpdate p{};
+        p.mode = u.mode, p.num_objects = u.num_objects, p.poses = u.poses;
+        check_status(pyr_scene_pose(handle, &p, hip_stream));
+    } else if (entry == Entry::Skin) {
+        PyrSkinUpdate k{};
+        k.mode = u.mode, k.num_objects = u.num_objects, k.poses = u.poses, k.joints = u.joints, k.num_joints = u.num_joints;
+        check_status(pyr_scene_skin(handle, &k, hip_stream));
+    } else {
+        check_status(pyr_scene_morph(handle, &u, hip_stream));
+    }
 }
-void World::pose(const std::map<size_t, ObjectPose>& poses, Update mode, int device, void* hip_stream) {
-    for (const auto& kv : poses)
-        if (kv.first >= flat_.objects().size()) throw ProjectError("pose: no object " + std::to_string(kv.first));
-    pose_scene(scene(device), poses, mode, hip_stream);
-    poses_ = poses;
+void World::frame(Entry entry, const Tables* weights, const Tables* joints, const std::map<size_t, ObjectPose>* poses, Update mode, int device, void* hip_stream) {
+    const std::string name = entry == Entry::Pose ? "pose" : entry == Entry::Skin ? "skin" : "morph";
+    Tables merged = weights_;
+    if (entry == Entry::Morph) {
+        if (morphs_.empty()) throw ProjectError("morph: the world has no morphs (set_morphs gives them)");
+        for (const auto& kv : *weights) {
+            const auto it = morphs_.find(kv.first);
+            if (it == morphs_.end()) throw ProjectError("morph: no morph on object " + std::to_string(kv.first));
+            if (kv.second.size() != it->second.num_targets) throw ProjectError("morph: object " + std::to_string(kv.first) + " needs one weight for each of its targets");
+            merged[kv.first] = kv.second;
+        }
+        if (joints && skins_.empty()) throw ProjectError("morph: joints are given, and the world has no skins");
+    }
+    if (joints)
+        for (const auto& kv : *joints) {
+            const auto it = skins_.find(kv.first);
+            if (it == skins_.end()) throw ProjectError(name + ": no skin on object " + std::to_string(kv.first));
+            if (kv.second.size() != 16 * (size_t)it->second.num_joints) throw ProjectError(name + ": object " + std::to_string(kv.first) + " needs 16 floats for each of its joints");
+        }
+    if (poses)
+        for (const auto& kv : *poses)
+            if (kv.first >= flat_.objects().size()) throw ProjectError(name + ": no object " + std::to_string(kv.first));
+    const std::map<size_t, ObjectPose> named = poses ? *poses : poses_;
+    send_frame(scene(device), entry, merged, joints, named, mode, hip_stream);
+    weights_ = merged, poses_ = named;
+    if (joints) joints_ = *joints;
     smooth_frame_ = !smoothing_.empty();
 }
+void World::pose(const std::map<size_t, ObjectPose>& poses, Update mode, int device, void* hip_stream) { frame(Entry::Pose, nullptr, nullptr, &poses, mode, device, hip_stream); }
 void World::set_skins_on(PyrScene* handle, const std::map<size_t, Skin>& skins) {
     std::vector<PyrSkin> records;
     for (const auto& kv : skins) {
@@ -1187,30 +1230,8 @@ std::vector<float> World::joint_table(const std::map<size_t, std::vector<float>>
     }
     return table;
 }
-void World::skin_scene(PyrScene* handle, const std::map<size_t, std::vector<float>>& joints, const std::map<size_t, ObjectPose>& poses, Update mode, void* hip_stream) {
-    const std::vector<float> table = joint_table(joints);
-    const std::vector<PyrObjectPose> records = pose_records(poses);
-    PyrSkinUpdate u{};
-    u.mode = mode == Update::Rebuild ? PYR_UPDATE_REBUILD : PYR_UPDATE_REFIT;
-    u.num_objects = (uint32_t)records.size();
-    u.poses = records.data();
-    u.num_joints = (uint32_t)(table.size() / 16);
-    u.joints = table.data();
-    check_status(pyr_scene_skin(handle, &u, hip_stream));
-}
 void World::skin(const std::map<size_t, std::vector<float>>& joints, const std::map<size_t, ObjectPose>* poses, Update mode, int device, void* hip_stream) {
-    for (const auto& kv : joints) {
-        const auto it = skins_.find(kv.first);
-        if (it == skins_.end()) throw ProjectError("skin: no skin on object " + std::to_string(kv.first));
-        if (kv.second.size() != 16 * (size_t)it->second.num_joints) throw ProjectError("skin: object " + std::to_string(kv.first) + " needs 16 floats for each of its joints");
-    }
-    if (poses)
-        for (const auto& kv : *poses)
-            if (kv.first >= flat_.objects().size()) throw ProjectError("skin: no object " + std::to_string(kv.first));
-    const std::map<size_t, ObjectPose> named = poses ? *poses : poses_;
-    skin_scene(scene(device), joints, named, mode, hip_stream);
-    poses_ = named, joints_ = joints;
-    smooth_frame_ = !smoothing_.empty();
+    frame(Entry::Skin, nullptr, &joints, poses, mode, device, hip_stream);
 }
 void World::set_morphs_on(PyrScene* handle, const std::map<size_t, Morph>& morphs) {
     std::vector<PyrMorph> records;
@@ -1235,54 +1256,9 @@ void World::set_morphs(const std::map<size_t, Morph>& morphs) {
     morphs_ = morphs;
     weights_.clear();
 }
-void World::morph_scene(PyrScene* handle, const std::map<size_t, std::vector<float>>& weights, const std::map<size_t, std::vector<float>>* joints,
-                        const std::map<size_t, ObjectPose>& poses, Update mode, void* hip_stream) {
-    std::vector<float> table, joint_rows;
-    for (const auto& kv : morphs_) {
-        const auto it = weights.find(kv.first);
-        if (it != weights.end())
-            table.insert(table.end(), it->second.begin(), it->second.end());
-        else
-            table.insert(table.end(), kv.second.num_targets, 0.0f);
-    }
-    if (joints) joint_rows = joint_table(*joints);
-    const std::vector<PyrObjectPose> records = pose_records(poses);
-    PyrMorphUpdate u{};
-    u.mode = mode == Update::Rebuild ? PYR_UPDATE_REBUILD : PYR_UPDATE_REFIT;
-    u.num_objects = (uint32_t)records.size();
-    u.poses = records.data();
-    u.joints = joints ? joint_rows.data() : nullptr;
-    u.num_joints = (uint32_t)(joint_rows.size() / 16);
-    u.weights = table.data();
-    u.num_weights = (uint32_t)table.size();
-    check_status(pyr_scene_morph(handle, &u, hip_stream));
-}
 void World::morph(const std::map<size_t, std::vector<float>>& weights, const std::map<size_t, std::vector<float>>* joints, const std::map<size_t, ObjectPose>* poses, Update mode,
                   int device, void* hip_stream) {
-    if (morphs_.empty()) throw ProjectError("morph: the world has no morphs (set_morphs gives them)");
-    std::map<size_t, std::vector<float>> merged = weights_;
-    for (const auto& kv : weights) {
-        const auto it = morphs_.find(kv.first);
-        if (it == morphs_.end()) throw ProjectError("morph: no morph on object " + std::to_string(kv.first));
-        if (kv.second.size() != it->second.num_targets) throw ProjectError("morph: object " + std::to_string(kv.first) + " needs one weight for each of its targets");
-        merged[kv.first] = kv.second;
-    }
-    if (joints) {
-        if (skins_.empty()) throw ProjectError("morph: joints are given, and the world has no skins");
-        for (const auto& kv : *joints) {
-            const auto it = skins_.find(kv.first);
-            if (it == skins_.end()) throw ProjectError("morph: no skin on object " + std::to_string(kv.first));
-            if (kv.second.size() != 16 * (size_t)it->second.num_joints) throw ProjectError("morph: object " + std::to_string(kv.first) + " needs 16 floats for each of its joints");
-        }
-    }
-    if (poses)
-        for (const auto& kv : *poses)
-            if (kv.first >= flat_.objects().size()) throw ProjectError("morph: no object " + std::to_string(kv.first));
-    const std::map<size_t, ObjectPose> named = poses ? *poses : poses_;
-    morph_scene(scene(device), merged, joints, named, mode, hip_stream);
-    weights_ = merged, poses_ = named;
-    smooth_frame_ = !smoothing_.empty();
-    if (joints) joints_ = *joints;
+    frame(Entry::Morph, &weights, joints, poses, mode, device, hip_stream);
 }
 std::vector<uint32_t> weld(const float* positions, const float* normals, size_t num_triangles) {
     struct Key {

@@ -1,7 +1,13 @@
-// pose.hip -- posing a live scene's objects, skinning its meshes, morphing them and recomputing their normals on the device (DESIGN.md sections 9g, 9h, 9p and 9q), a unit of its own: every primitive of an object
-// is computed from the rest pose (where the scene has morphs: from the morphed rest, which the morph kernel writes first) by pose_rules.h and written to the scene's staging arrays, from where the refit of section 9f
-// (kernels/refit.hip) rewrites the records and the boxes; the records of shape lamps follow from the staging arrays too. Nothing
-// here touches a record the render kernels read except the lamp records, and those only after the host has seen the flag clear.
+// pose.hip -- a live scene's deformation pipeline on the device, morph -> skin -> pose -> smooth -> lamps (DESIGN.md sections 9g,
+// 9h, 9p, 9q and 9r), a unit of its own: every primitive of an object is computed from the rest pose (where the scene has morphs:
+// from the morphed rest, which the morph kernel writes first) and written to the scene's staging arrays, from where the refit of
+// section 9f (kernels/refit.hip) rewrites the records and the boxes; the records of shape lamps follow from the staging arrays
+// too. Nothing here touches a record the render kernels read except the lamp records, and those only after the host has seen
+// the flag clear.
+//
+// What a lane computes is pose_rules.h's "one lane's walk", which the host rehearsal compiles too. This unit keeps what is the
+// kernels' own: lane -> record -> index and its range checks, the loads and stores with their widths, the bounds checks on tables
+// in memory, and the flag reduction.
 //
 // One lane per primitive of an object, each lane stores to its own primitive only (the smoothing kernel, which runs after them:
 // one lane per group of corners, each lane stores to its own group's corners only); the only word two lanes share is the flag,
@@ -49,71 +55,82 @@ __device__ __forceinline__ pose::Pose load_pose(const pose::Pose& from) {
     return p;
 }
 
-__device__ __forceinline__ bool box_beyond_range(const float* lo, const float* hi) {
-    bool bad = false;
-    for (int a = 0; a < 3; ++a) bad = bad || pose::beyond_range(lo[a]) || pose::beyond_range(hi[a]);
-    return bad;
-}
-
-// the workgroup's OR in LDS, then one atomic of the workgroup on the scene's word (every lane of the workgroup arrives here)
-__device__ __forceinline__ void raise_flag(bool mine, uint32_t* block_flag, uint32_t* flag) {
-    if (mine) atomicOr(block_flag, 1u);
+// the workgroup's OR of `mine` in LDS, then one atomic of the workgroup on the scene's word (every lane of the workgroup arrives here)
+__device__ __forceinline__ void raise_flag(uint32_t mine, uint32_t* block_flag, uint32_t* flag) {
+    if (mine) atomicOr(block_flag, mine);
     __syncthreads();
-    if (threadIdx.x == 0 && *block_flag != 0u) atomicOr(flag, 1u);
+    if (threadIdx.x == 0 && *block_flag != 0u) atomicOr(flag, *block_flag);
 }
 
-// ---- one lane per triangle of an object. 36 bytes a triangle, so only every fourth starts on a 16-byte boundary: dword loads
-// and stores for positions and normals; a triangle's frames are 48 bytes: 16-byte loads and stores.
+// ---- what the three triangle kernels share (Ctx and MorphCtx name these arrays alike). 36 bytes a triangle, so only every fourth
+// starts on a 16-byte boundary: dword loads and stores for positions and normals; a triangle's frames are 48 bytes: 16-byte loads
+// and stores. A scene that keeps no frames gives a vertex a frame of zeros, which nothing reads.
+template <class C>
+__device__ __forceinline__ void load_positions(const C& c, uint32_t index, float* p) {
+    const float* rest_p = c.rest_positions + 9 * (size_t)index;
+    for (int k = 0; k < 9; ++k) p[k] = rest_p[k];
+}
+template <class C>
+__device__ __forceinline__ void load_normal_frame(const C& c, uint32_t index, int v, float* n, float* q) {
+    const float* rest_n = c.rest_normals + 9 * (size_t)index + 3 * v;
+    n[0] = rest_n[0], n[1] = rest_n[1], n[2] = rest_n[2];
+    q[0] = q[1] = q[2] = q[3] = 0.0f;
+    if (c.rest_frames) {
+        const float4_t f = load4(c.rest_frames + 12 * (size_t)index + 4 * v);
+        q[0] = f.x, q[1] = f.y, q[2] = f.z, q[3] = f.w;
+    }
+}
+template <class C>
+__device__ __forceinline__ void store_normal_frame(const C& c, uint32_t index, int v, const float* n, const float* q) {
+    if (c.rest_frames) store4(c.frames + 12 * (size_t)index + 4 * v, float4_t{q[0], q[1], q[2], q[3]});
+    float* out_n = c.normals + 9 * (size_t)index + 3 * v;
+    out_n[0] = n[0], out_n[1] = n[1], out_n[2] = n[2];
+}
+// the triangle's positions out, and the coordinate check on its box
+template <class C>
+__device__ __forceinline__ uint32_t store_positions(const C& c, uint32_t index, const float* p) {
+    float* out_p = c.positions + 9 * (size_t)index;
+    for (int k = 0; k < 9; ++k) out_p[k] = p[k];
+    float lo[3], hi[3];
+    lvl::triangle_bounds(p, lo, hi);
+    return pose::bounds_flag(lo, hi);
+}
+
+// ---- one lane per triangle of an object: a vertex at a time through pose_rules.h pose_vertex
 __global__ __launch_bounds__(kBlock) void pose_triangles_kernel(Ctx c) {
     __shared__ uint32_t block_flag;
     if (threadIdx.x == 0) block_flag = 0u;
     __syncthreads();
     const uint32_t lane = blockIdx.x * kBlock + threadIdx.x;
-    bool bad = false;
+    uint32_t bad = 0u;
     if (lane < c.posed_triangles && c.num_objects != 0u) {
         const DevObject& object = c.objects[object_of<DevObject, &DevObject::triangle_lane>(c.objects, c.num_objects, lane)];
         const uint32_t within = lane - object.triangle_lane, index = object.first_triangle + within;
         if (within < object.num_triangles && index >= object.first_triangle && index < c.num_triangles) {
             const pose::Pose pose = load_pose(object.pose);
-            const float* rest_p = c.rest_positions + 9 * (size_t)index;
-            const float* rest_n = c.rest_normals + 9 * (size_t)index;
-            float* out_p = c.positions + 9 * (size_t)index;
-            float* out_n = c.normals + 9 * (size_t)index;
             float p[9];
-            for (int k = 0; k < 9; ++k) p[k] = rest_p[k];
-            if (!pose.identity)
-                for (int v = 0; v < 3; ++v) pose::pose_point(pose, p + 3 * v);
-            for (int k = 0; k < 9; ++k) out_p[k] = p[k];
-            float lo[3], hi[3];
-            lvl::triangle_bounds(p, lo, hi);
-            bad = box_beyond_range(lo, hi);
-            for (int v = 0; v < 3; ++v) { // a vertex at a time: its normal and, where the scene keeps them, its frame
-                float n[3] = {rest_n[3 * v], rest_n[3 * v + 1], rest_n[3 * v + 2]};
-                if (c.rest_frames) {
-                    const float4_t f = load4(c.rest_frames + 12 * (size_t)index + 4 * v);
-                    float q[4] = {f.x, f.y, f.z, f.w};
-                    if (!pose.identity) pose::pose_normal_frame(pose, n, q);
-                    store4(c.frames + 12 * (size_t)index + 4 * v, float4_t{q[0], q[1], q[2], q[3]});
-                } else if (!pose.identity) {
-                    pose::pose_normal(pose, n);
-                }
-                out_n[3 * v] = n[0], out_n[3 * v + 1] = n[1], out_n[3 * v + 2] = n[2];
+            load_positions(c, index, p);
+            for (int v = 0; v < 3; ++v) {
+                float n[3], q[4];
+                load_normal_frame(c, index, v, n, q);
+                pose::pose_vertex(pose, p + 3 * v, n, q, c.rest_frames != nullptr);
+                store_normal_frame(c, index, v, n, q);
             }
+            bad = store_positions(c, index, p);
         }
     }
     raise_flag(bad, &block_flag, c.beyond_range);
 }
 
-// ---- one lane per triangle of a skin: a vertex at a time, its matrix blended from the joints its binding
-// names (pose_rules.h blend_joints), the per-vertex rule with that matrix, then the object's own pose as above. A triangle's
-// weights are 48 bytes: 16-byte loads; its joint indices are 24 bytes: 8-byte loads. The binding row is the lane. A joint index is
-// compared against the skin's count before it is used (pyr_scene_set_skins has refused such a binding: the flag, and joint 0).
+// ---- one lane per triangle of a skin: a vertex at a time through pose_rules.h skin_vertex. A triangle's
+// weights are 48 bytes: 16-byte loads; its joint indices are 24 bytes: 8-byte loads. The binding row is the lane. A skin at rest
+// reads no binding.
 __global__ __launch_bounds__(kBlock) void skin_triangles_kernel(Ctx c) {
     __shared__ uint32_t block_flag;
     if (threadIdx.x == 0) block_flag = 0u;
     __syncthreads();
     const uint32_t lane = blockIdx.x * kBlock + threadIdx.x;
-    bool bad = false;
+    uint32_t bad = 0u;
     if (lane < c.skinned_triangles && c.num_skins != 0u) {
         const DevSkin& skin = c.skins[object_of<DevSkin, &DevSkin::lane>(c.skins, c.num_skins, lane)];
         const uint32_t within = lane - skin.lane, index = skin.first_triangle + within;
@@ -122,48 +139,22 @@ __global__ __launch_bounds__(kBlock) void skin_triangles_kernel(Ctx c) {
             const pose::Pose pose = load_pose(skin.pose);
             const uint32_t num_joints = skin.num_joints, rest_skin = skin.identity;
             const float* joints = c.joints + 12 * (size_t)skin.first_joint;
-            const float* rest_p = c.rest_positions + 9 * (size_t)index;
-            const float* rest_n = c.rest_normals + 9 * (size_t)index;
-            float* out_p = c.positions + 9 * (size_t)index;
-            float* out_n = c.normals + 9 * (size_t)index;
             float p[9];
+            load_positions(c, index, p);
             for (int v = 0; v < 3; ++v) {
-                float n[3] = {rest_n[3 * v], rest_n[3 * v + 1], rest_n[3 * v + 2]};
-                float q[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-                for (int a = 0; a < 3; ++a) p[3 * v + a] = rest_p[3 * v + a];
-                if (c.rest_frames) {
-                    const float4_t f = load4(c.rest_frames + 12 * (size_t)index + 4 * v);
-                    q[0] = f.x, q[1] = f.y, q[2] = f.z, q[3] = f.w;
-                }
+                float n[3], q[4], w[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                uint32_t j[4] = {0u, 0u, 0u, 0u};
+                load_normal_frame(c, index, v, n, q);
                 if (!rest_skin) {
                     const float4_t wv = load4(c.skin_weights + 12 * (size_t)lane + 4 * v);
                     const uint2_t jv = *(const uint2_t*)(c.skin_joints + 12 * (size_t)lane + 4 * v);
-                    const float w[4] = {wv.x, wv.y, wv.z, wv.w};
-                    uint32_t j[4] = {jv.x & 0xFFFFu, jv.x >> 16, jv.y & 0xFFFFu, jv.y >> 16};
-                    for (int k = 0; k < 4; ++k)
-                        if (j[k] >= num_joints) j[k] = 0u, bad = true;
-                    pose::Pose blended;
-                    pose::blend_joints(joints, j, w, blended);
-                    pose::pose_point(blended, p + 3 * v);
-                    if (c.rest_frames)
-                        pose::pose_normal_frame(blended, n, q);
-                    else
-                        pose::pose_normal(blended, n);
+                    w[0] = wv.x, w[1] = wv.y, w[2] = wv.z, w[3] = wv.w;
+                    j[0] = jv.x & 0xFFFFu, j[1] = jv.x >> 16, j[2] = jv.y & 0xFFFFu, j[3] = jv.y >> 16;
                 }
-                if (!pose.identity) {
-                    pose::pose_point(pose, p + 3 * v);
-                    if (c.rest_frames)
-                        pose::pose_normal_frame(pose, n, q);
-                    else
-                        pose::pose_normal(pose, n);
-                }
-                if (c.rest_frames) store4(c.frames + 12 * (size_t)index + 4 * v, float4_t{q[0], q[1], q[2], q[3]});
-                out_n[3 * v] = n[0], out_n[3 * v + 1] = n[1], out_n[3 * v + 2] = n[2];
+                bad |= pose::skin_vertex(joints, num_joints, rest_skin != 0u, j, w, pose, p + 3 * v, n, q, c.rest_frames != nullptr);
+                store_normal_frame(c, index, v, n, q);
             }
-            for (int k = 0; k < 9; ++k) out_p[k] = p[k];
-            float lo[3], hi[3];
-            lvl::triangle_bounds(p, lo, hi);
-            bad = bad || box_beyond_range(lo, hi);
+            bad |= store_positions(c, index, p);
         }
     }
     raise_flag(bad, &block_flag, c.beyond_range);
@@ -171,11 +162,11 @@ __global__ __launch_bounds__(kBlock) void skin_triangles_kernel(Ctx c) {
 
 // ---- one lane per triangle of a morph: the triangle from rest into the morphed rest, which the two kernels
 // above then read as their rest pose. Positions accumulate over the morph's active targets in nine registers; normals and frame go
-// a vertex at a time through pose_rules.h morph_normal_frame. The host has packed the active targets as (target, weight) pairs, so
-// no inactive target's deltas are read, and a wave that lies inside one morph walks the pairs uniformly. A pair's target is
-// compared against the morph's count and its row against the buffer's rows before any delta is read (pyr_scene_set_morphs and the
-// host's packing make both hold: bit 0 of the flag otherwise, and the target is left out). A morph with no active target is
-// copied from rest, and so are normals and frames of a morph without normal deltas.
+// a vertex at a time (pose_rules.h add_delta and morphed_normal). The host has packed the active targets as (target, weight)
+// pairs, so no inactive target's deltas are read, and a wave that lies inside one morph walks the pairs uniformly. A pair's target
+// is compared against the morph's count and its row against the buffer's rows before any delta is read (pyr_scene_set_morphs and
+// the host's packing make both hold: kBeyondRange otherwise, and the target is left out). The morphed rest is no moved primitive:
+// its box is not checked here.
 __global__ __launch_bounds__(kBlock) void morph_triangles_kernel(MorphCtx c) {
     __shared__ uint32_t block_flag;
     if (threadIdx.x == 0) block_flag = 0u;
@@ -190,72 +181,52 @@ __global__ __launch_bounds__(kBlock) void morph_triangles_kernel(MorphCtx c) {
         if (within < rows && index >= morph.first_triangle && index < c.num_triangles && pairs_inside) {
             const ActiveTarget* active = c.active + first_active;
             const uint64_t position_row = morph.position_row + within, normal_row = morph.normal_row + within;
-            const bool with_normals = morph.has_normals != 0u && num_active != 0u;
-            const float* rest_p = c.rest_positions + 9 * (size_t)index;
-            const float* rest_n = c.rest_normals + 9 * (size_t)index;
-            float* out_p = c.positions + 9 * (size_t)index;
-            float* out_n = c.normals + 9 * (size_t)index;
+            const bool with_normals = pose::morph_moves_normals(morph.has_normals, num_active);
             float p[9];
-            for (int k = 0; k < 9; ++k) p[k] = rest_p[k];
+            load_positions(c, index, p);
             for (uint32_t a = 0; a < num_active; ++a) {
                 const uint32_t target = active[a].target;
                 const float w = active[a].weight;
                 const uint64_t row = position_row + (uint64_t)target * rows;
                 if (target >= num_targets || row >= c.position_rows) {
-                    bad |= 1u;
+                    bad |= pose::kBeyondRange;
                     continue;
                 }
-                const float* d = c.position_deltas + 9 * row;
-                for (int k = 0; k < 9; ++k) p[k] = p[k] + w * d[k];
+                pose::add_delta(p, w, c.position_deltas + 9 * row, 9);
             }
+            float* out_p = c.positions + 9 * (size_t)index;
             for (int k = 0; k < 9; ++k) out_p[k] = p[k];
             for (int v = 0; v < 3; ++v) {
-                float n[3] = {rest_n[3 * v], rest_n[3 * v + 1], rest_n[3 * v + 2]};
-                float q[4] = {0.0f, 0.0f, 0.0f, 0.0f};
-                if (c.rest_frames) {
-                    const float4_t f = load4(c.rest_frames + 12 * (size_t)index + 4 * v);
-                    q[0] = f.x, q[1] = f.y, q[2] = f.z, q[3] = f.w;
-                }
+                float n[3], q[4];
+                load_normal_frame(c, index, v, n, q);
                 if (with_normals) {
                     for (uint32_t a = 0; a < num_active; ++a) {
                         const uint32_t target = active[a].target;
                         const float w = active[a].weight;
                         const uint64_t row = normal_row + (uint64_t)target * rows;
                         if (target >= num_targets || row >= c.normal_rows) {
-                            bad |= 1u;
+                            bad |= pose::kBeyondRange;
                             continue;
                         }
-                        const float* d = c.normal_deltas + 9 * row + 3 * v;
-                        for (int k = 0; k < 3; ++k) n[k] = n[k] + w * d[k];
+                        pose::add_delta(n, w, c.normal_deltas + 9 * row + 3 * v, 3);
                     }
-                    const bool outside = c.rest_frames ? pose::morph_normal_frame(n, q) : pose::morph_normal_frame(n, nullptr);
-                    if (outside) bad |= 2u;
+                    bad |= pose::morphed_normal(n, q, c.rest_frames != nullptr);
                 }
-                if (c.rest_frames) store4(c.frames + 12 * (size_t)index + 4 * v, float4_t{q[0], q[1], q[2], q[3]});
-                out_n[3 * v] = n[0], out_n[3 * v + 1] = n[1], out_n[3 * v + 2] = n[2];
+                store_normal_frame(c, index, v, n, q);
             }
         }
     }
-    if (bad) atomicOr(&block_flag, bad);
-    __syncthreads();
-    if (threadIdx.x == 0 && block_flag != 0u) atomicOr(c.flag, block_flag);
-}
-
-// raise_flag for a kernel whose lanes raise more than bit 0: the workgroup's OR of `mine` in LDS, then one atomic on the scene's word
-__device__ __forceinline__ void raise_flag_bits(uint32_t mine, uint32_t* block_flag, uint32_t* flag) {
-    if (mine) atomicOr(block_flag, mine);
-    __syncthreads();
-    if (threadIdx.x == 0 && *block_flag != 0u) atomicOr(flag, *block_flag);
+    raise_flag(bad, &block_flag, c.flag);
 }
 
 // ---- one lane per group of a smoothing, after the kernels above have written the staging arrays: the lane
-// walks its row of the corner table twice. First it sums the signed face vectors of the corners' triangles (pose_rules.h
-// signed_face_vector over the triangle's nine staged position dwords), in the row's order, starting from the first one. Then it
-// gives every corner of the row the normalised sum -- three dwords into the corner's slot of the staged normals -- and, where the
-// scene keeps frames, rebuilds the corner's 16-byte staged frame against it (morph_normal_frame). A lane stores to the corners of
-// its own group only and reads positions only, which this kernel does not write; sums are in a fixed order, so there is no float
-// atomic. The row is compared against the table's size and every corner's triangle against the scene's count before either is
-// used (the host's packing makes both hold: bit 0 of the flag otherwise, and the corner is left out).
+// walks its row of the corner table twice. First it sums the signed face vectors of the corners' triangles (pose_rules.h add_face
+// over the triangle's nine staged position dwords), in the row's order. Then it gives every corner of the row the normalised sum
+// -- three dwords into the corner's slot of the staged normals -- and, where the scene keeps frames, rebuilds the corner's 16-byte
+// staged frame against it (finish_corner; a scene without frames finishes the sum once, every corner getting the same three
+// words). A lane stores to the corners of its own group only and reads positions only, which this kernel does not write; sums are
+// in a fixed order, so there is no float atomic. The row is compared against the table's size and every corner's triangle against
+// the scene's count before either is used (the host's packing makes both hold: kBeyondRange otherwise, and the corner is left out).
 __global__ __launch_bounds__(kBlock) void smooth_normals_kernel(SmoothCtx c) {
     __shared__ uint32_t block_flag;
     if (threadIdx.x == 0) block_flag = 0u;
@@ -270,20 +241,16 @@ __global__ __launch_bounds__(kBlock) void smooth_normals_kernel(SmoothCtx c) {
             for (uint32_t k = begin; k < end; ++k) {
                 const uint32_t word = c.group_corners[k], triangle = (word & ~kNegated) / 3u;
                 if (triangle >= c.num_triangles) {
-                    bad |= 1u;
+                    bad |= pose::kBeyondRange;
                     continue;
                 }
                 const float* from = c.positions + 9 * (size_t)triangle;
-                float p[9], f[3];
+                float p[9];
                 for (int a = 0; a < 9; ++a) p[a] = from[a];
-                pose::signed_face_vector(p, (word & kNegated) != 0u, f);
-                if (any)
-                    m[0] = m[0] + f[0], m[1] = m[1] + f[1], m[2] = m[2] + f[2];
-                else
-                    m[0] = f[0], m[1] = f[1], m[2] = f[2], any = true;
+                pose::add_face(p, (word & kNegated) != 0u, m, any);
             }
-            float shared[3] = {m[0], m[1], m[2]}; // a scene without frames: every corner gets the same three words
-            if (any && !c.frames && pose::morph_normal_frame(shared, nullptr)) bad |= 4u;
+            float shared[3] = {m[0], m[1], m[2]};
+            if (any && !c.frames) bad |= pose::finish_corner(m, shared, nullptr, false);
             for (uint32_t k = begin; any && k < end; ++k) {
                 const uint32_t corner = c.group_corners[k] & ~kNegated;
                 if (corner / 3u >= c.num_triangles) continue;
@@ -291,17 +258,17 @@ __global__ __launch_bounds__(kBlock) void smooth_normals_kernel(SmoothCtx c) {
                 if (c.frames) {
                     const float4_t q4 = load4(c.frames + 4 * (size_t)corner);
                     float q[4] = {q4.x, q4.y, q4.z, q4.w};
-                    if (pose::morph_normal_frame(n, q)) bad |= 4u;
+                    bad |= pose::finish_corner(m, n, q, true);
                     store4(c.frames + 4 * (size_t)corner, float4_t{q[0], q[1], q[2], q[3]});
                 }
                 float* out = c.normals + 3 * (size_t)corner;
                 out[0] = n[0], out[1] = n[1], out[2] = n[2];
             }
         } else {
-            bad |= 1u;
+            bad |= pose::kBeyondRange;
         }
     }
-    raise_flag_bits(bad, &block_flag, c.flag);
+    raise_flag(bad, &block_flag, c.flag);
 }
 
 // ---- one lane per sphere of an object
@@ -310,7 +277,7 @@ __global__ __launch_bounds__(kBlock) void pose_spheres_kernel(Ctx c) {
     if (threadIdx.x == 0) block_flag = 0u;
     __syncthreads();
     const uint32_t lane = blockIdx.x * kBlock + threadIdx.x;
-    bool bad = false;
+    uint32_t bad = 0u;
     if (lane < c.posed_spheres && c.num_objects != 0u) {
         const DevObject& object = c.objects[object_of<DevObject, &DevObject::sphere_lane>(c.objects, c.num_objects, lane)];
         const uint32_t within = lane - object.sphere_lane, index = object.first_sphere + within;
@@ -318,11 +285,11 @@ __global__ __launch_bounds__(kBlock) void pose_spheres_kernel(Ctx c) {
             const pose::Pose pose = load_pose(object.pose);
             const float4_t r = load4(c.rest_spheres + 4 * (size_t)index);
             float s[4] = {r.x, r.y, r.z, r.w};
-            if (!pose.identity) pose::pose_sphere(pose, s);
+            pose::pose_sphere(pose, s);
             store4(c.spheres + 4 * (size_t)index, float4_t{s[0], s[1], s[2], s[3]});
             float lo[3], hi[3];
             lvl::sphere_bounds(s, lo, hi);
-            bad = box_beyond_range(lo, hi);
+            bad = pose::bounds_flag(lo, hi);
         }
     }
     raise_flag(bad, &block_flag, c.beyond_range);

@@ -1,4 +1,7 @@
-// pose_launch.h -- what the pose kernels (kernels/pose.hip) and their host driver (live_scene.cpp pyr_scene_pose) share.
+// pose_launch.h -- what the kernels of a live scene's deformation pipeline (kernels/pose.hip: morph, skin, pose, smooth, lamps) and
+// their host driver (live_scene.cpp scene_pose) share: the records and contexts on the device, and the launchers. The bits of the
+// flag word all of them raise are pose_rules.h's Flag -- that header states which failure raises which, and it is compiled where
+// this one cannot be (the host rehearsal) -- named here as devpose::Flag for the two sides of the bus.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -9,6 +12,7 @@ struct DevLamp;
 namespace devpose {
 
 constexpr uint32_t kBlock = 256;
+using Flag = pose::Flag; // kBeyondRange, kMorphedNormal, kSmoothedNormal
 
 // One object on the device: its pose, its primitive ranges, and where its lanes begin in the launches over all objects'
 // triangles and spheres (the running sums of the counts, in object order). 96 bytes.
@@ -44,7 +48,7 @@ struct Ctx {
     uint32_t num_objects;
     uint32_t num_triangles, num_spheres;         // the scene's counts
     uint32_t posed_triangles, posed_spheres;     // lanes: the objects' counts summed
-    uint32_t* beyond_range; // one word, zeroed before the call: set when a bound of a moved primitive fails the coordinate check
+    uint32_t* beyond_range; // the flag word, zeroed before the call: kBeyondRange when a bound of a moved primitive fails the coordinate check
     DevLamp* lamps;
     uint32_t num_lamps;
     // the skins (none: num_skins 0 and the rest unused)
@@ -91,7 +95,7 @@ struct MorphCtx {
     uint32_t num_morphs, num_active;
     uint32_t num_triangles;     // the scene's count
     uint32_t morphed_triangles; // lanes: the morphs' triangle counts summed
-    uint32_t* flag; // the pose kernels' word: bit 0 as there; bit 1 (value 2): a morphed normal or tangent that cannot be normalised
+    uint32_t* flag; // the pose kernels' word: kBeyondRange as there; kMorphedNormal: a morphed normal or tangent that cannot be normalised
 };
 
 // What the smoothing kernel reads and writes: the staged positions as the morph, skin and pose kernels left
@@ -108,7 +112,7 @@ struct SmoothCtx {
     const uint32_t* group_corners; // [num_corners]
     uint32_t num_groups, num_corners;
     uint32_t num_triangles; // the scene's count
-    uint32_t* flag; // the pose kernels' word: bit 0 as there; bit 2 (value 4): a recomputed normal or tangent that cannot be normalised
+    uint32_t* flag; // the pose kernels' word: kBeyondRange as there; kSmoothedNormal: a recomputed normal or tangent that cannot be normalised
 };
 
 // Each enqueues on `stream` and returns hipGetLastError().

@@ -1,8 +1,10 @@
-// live_scene.cpp -- everything that moves a scene after creation: pyr_scene_update[_device], pyr_scene_set_objects,
-// pyr_scene_pose, pyr_scene_set_skins, pyr_scene_skin, pyr_scene_set_morphs, pyr_scene_morph, pyr_scene_set_smoothing, pyr_scene_geometry, pyr_scene_update_info -- and pyr_scene_keep_previous,
-// which copies where the geometry is now for the motion pass (api.cpp enqueues that one). LiveGeometry
-// (scene_internal.h) says where the geometry is and which copies are valid; rebuild_from and refit_from are the two ways new
-// arrays reach the records and trees on the device.
+// live_scene.cpp -- everything that moves a scene after creation: pyr_scene_update[_device], pyr_scene_set_objects, pyr_scene_pose,
+// pyr_scene_set_skins, pyr_scene_skin, pyr_scene_set_morphs, pyr_scene_morph, pyr_scene_set_smoothing, pyr_scene_geometry,
+// pyr_scene_update_info -- and pyr_scene_keep_previous, which copies where the geometry is now for the motion pass (api.cpp
+// enqueues that one). LiveGeometry (scene_internal.h) says where the geometry is and which copies are valid; rebuild_from and
+// refit_from are the two ways new arrays reach the records and trees on the device. The three calls that give a frame -- pose, skin,
+// morph -- are one frame (Frame), one check (check_frame) and one run (scene_pose); the three that attach something to objects --
+// skins, morphs, a smoothing -- are one check of the attachment (check_attachments) and one skeleton (set_attachments).
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -43,26 +45,21 @@ PyrSceneDesc LiveGeometry::view(const float* const with[NUM_ARRAYS]) const {
 }
 
 // (the description is current: whoever forgets the objects has fetched it)
-void LiveGeometry::forget_skins() {
-    skins.clear(), skin_joints.clear();
-    skinned_triangles = 0;
-    for (DeviceBuffer* b : {&skin_table, &skin_weights, &skin_indices, &joint_table}) b->release();
-    posed_triangles = 0; // the launch over the objects' triangles has every object's again
-    for (const devpose::DevObject& o : pose_table) posed_triangles += o.num_triangles;
+void LiveGeometry::recount_lanes() {
+    posed_triangles = posed_spheres = 0;
+    for (const devpose::DevObject& o : pose_table) posed_triangles += o.num_triangles, posed_spheres += o.num_spheres;
+    posed_triangles -= skin.triangles; // a skinned object's triangles have their lanes in the skin kernel's launch
 }
 
-void LiveGeometry::forget_morphs() {
-    morphs.clear(), morph_weights.clear();
-    morphed_triangles = 0;
-    morph_position_rows = morph_normal_rows = 0;
-    for (DeviceBuffer* b : {&morph_table, &morph_active, &morph_positions, &morph_normals}) b->release();
-    for (DeviceBuffer& b : morphed_rest) b.release();
+void LiveGeometry::forget_skins() {
+    skin.clear();
+    recount_lanes(); // the launch over the objects' triangles has every object's again
 }
+
+void LiveGeometry::forget_morphs() { morph.clear(); }
 
 void LiveGeometry::forget_smoothing() {
-    smoothed_objects.clear();
-    smooth_groups = smooth_corners = 0;
-    smooth_begin.release(), smooth_corners_table.release();
+    smooth.clear();
 }
 
 void LiveGeometry::forget_objects() {
@@ -70,7 +67,6 @@ void LiveGeometry::forget_objects() {
     forget_skins();
     forget_morphs();
     forget_smoothing();
-    posed_triangles = posed_spheres = 0;
     for (LiveArray& a : arrays) a.rest.release();
     pose_objects.release();
 }
@@ -117,81 +113,66 @@ int check_update_args(const PyrScene* scene, const PyrGeometryUpdate* u) {
     });
 }
 
-// What pyr_scene_pose and pyr_scene_skin refuse of the objects' poses (`name`: the update's struct; `may_keep`: NULL poses keep
-// the poses the scene is in), in the order pyrite_gpu.h gives.
+// One frame of a live scene as pyr_scene_pose, pyr_scene_skin and pyr_scene_morph give it: the mode, and the three tables of which a
+// NULL one keeps what the scene is in. An entry point fills what its update has and leaves the rest null.
+struct Frame {
+    uint32_t mode = 0;
+    const PyrObjectPose* poses = nullptr;
+    uint32_t num_objects = 0;
+    const float* joints = nullptr;
+    uint32_t num_joints = 0;
+    const float* weights = nullptr;
+    uint32_t num_weights = 0;
+};
+// What an entry point's update has of the three tables: none at all, one it must give, or one it may leave NULL. `name`: the
+// update's struct in the messages; `noun`: what the session's message calls the call.
+enum Part { ABSENT, REQUIRED, MAY_KEEP };
+struct FrameRules {
+    const char *name, *noun;
+    Part poses, joints, weights;
+};
+const FrameRules kPoseFrame{"PyrPoseUpdate", "pose", REQUIRED, ABSENT, ABSENT}, kSkinFrame{"PyrSkinUpdate", "skin", MAY_KEEP, REQUIRED, ABSENT},
+    kMorphFrame{"PyrMorphUpdate", "morph", MAY_KEEP, MAY_KEEP, MAY_KEEP};
+
+bool affine(const float* m) { return m[3] == 0.0f && m[7] == 0.0f && m[11] == 0.0f && m[15] == 1.0f; }
+
+// What the three refuse before any device is looked for, in the order pyrite_gpu.h gives: the poses; that the scene has morphs,
+// where the update has weights; the joint table where it must be or is given; the weight table where it is given.
 template <class Update>
-int check_poses(const PyrScene* scene, const Update* u, const std::string& name, bool may_keep) {
-    if (u->poses)
-        for (uint32_t i = 0; i < u->num_objects; ++i)
-            for (uint32_t word : u->poses[i].reserved)
-                if (word != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectPose.reserved must be zero");
-    if (scene->live.pose_table.empty()) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".num_objects: the scene has no objects (pyr_scene_set_objects names them)");
-    if (u->num_objects != scene->live.pose_table.size()) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".num_objects is not the scene's");
-    if (!u->poses) return may_keep ? (int)PYR_OK : fail(PYR_ERR_INVALID_ARGUMENT, name + ".poses is null");
-    for (uint32_t i = 0; i < u->num_objects; ++i) {
-        const PyrObjectPose& p = u->poses[i];
-        for (float x : p.transform)
-            if (!std::isfinite(x)) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectPose.transform has an entry that is not finite");
-        if (!std::isfinite(p.scale)) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectPose.scale is not finite");
-    }
-    for (uint32_t i = 0; i < u->num_objects; ++i) {
-        const float* m = u->poses[i].transform;
-        if (!(m[3] == 0.0f && m[7] == 0.0f && m[11] == 0.0f && m[15] == 1.0f)) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectPose.transform: the last row must be 0, 0, 0, 1");
-    }
-    return (int)PYR_OK;
-}
-
-// What pyr_scene_pose refuses before any device is looked for, in the order pyrite_gpu.h gives.
-int check_pose_args(const PyrScene* scene, const PyrPoseUpdate* u) {
+int check_frame(const PyrScene* scene, const Update* u, const Frame& f, const FrameRules& r) {
     if (!u) return fail(PYR_ERR_INVALID_ARGUMENT, "null update");
     if (!scene) return fail(PYR_ERR_INVALID_ARGUMENT, "null scene");
-    return check_move(scene, u, "PyrPoseUpdate", "pose", [&]() { return check_poses(scene, u, "PyrPoseUpdate", false); });
-}
-
-// What pyr_scene_skin and pyr_scene_morph refuse of a joint table that is given (`name`: the update's struct).
-template <class Update>
-int check_joints(const LiveGeometry& live, const Update* u, const std::string& name) {
-    if ((size_t)u->num_joints * 16 != live.skin_joints.size()) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".num_joints is not the scene's");
-    if (!u->joints) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".joints is null");
-    for (size_t k = 0; k < live.skin_joints.size(); ++k)
-        if (!std::isfinite(u->joints[k])) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".joints has an entry that is not finite");
-    for (uint32_t j = 0; j < u->num_joints; ++j) {
-        const float* m = u->joints + 16 * (size_t)j;
-        if (!(m[3] == 0.0f && m[7] == 0.0f && m[11] == 0.0f && m[15] == 1.0f)) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".joints: the last row must be 0, 0, 0, 1");
-    }
-    return (int)PYR_OK;
-}
-
-// What pyr_scene_skin adds to that: the joint table.
-int check_skin_args(const PyrScene* scene, const PyrSkinUpdate* u) {
-    if (!u) return fail(PYR_ERR_INVALID_ARGUMENT, "null update");
-    if (!scene) return fail(PYR_ERR_INVALID_ARGUMENT, "null scene");
-    return check_move(scene, u, "PyrSkinUpdate", "skin", [&]() {
-        const int rc = check_poses(scene, u, "PyrSkinUpdate", true);
-        if (rc != PYR_OK) return rc;
-        if (scene->live.skins.empty()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSkinUpdate.num_joints: the scene has no skins (pyr_scene_set_skins binds them)");
-        return check_joints(scene->live, u, "PyrSkinUpdate");
-    });
-}
-
-// What pyr_scene_morph adds to pyr_scene_pose's checks: morphs must be set; a joint table is pyr_scene_skin's, but may be NULL (the
-// scene keeps its joints); then the weight table, which may be NULL too.
-int check_morph_args(const PyrScene* scene, const PyrMorphUpdate* u) {
-    if (!u) return fail(PYR_ERR_INVALID_ARGUMENT, "null update");
-    if (!scene) return fail(PYR_ERR_INVALID_ARGUMENT, "null scene");
-    return check_move(scene, u, "PyrMorphUpdate", "morph", [&]() {
-        int rc = check_poses(scene, u, "PyrMorphUpdate", true);
-        if (rc != PYR_OK) return rc;
+    const std::string name = r.name;
+    return check_move(scene, u, name, r.noun, [&]() {
         const LiveGeometry& live = scene->live;
-        if (live.morphs.empty()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrMorphUpdate.num_weights: the scene has no morphs (pyr_scene_set_morphs sets them)");
-        if (u->joints) {
-            if (live.skins.empty()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrMorphUpdate.joints: the scene has no skins (pyr_scene_set_skins binds them)");
-            if ((rc = check_joints(live, u, "PyrMorphUpdate")) != PYR_OK) return rc;
+        if (f.poses)
+            for (uint32_t i = 0; i < f.num_objects; ++i)
+                for (uint32_t word : f.poses[i].reserved)
+                    if (word != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectPose.reserved must be zero");
+        if (live.pose_table.empty()) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".num_objects: the scene has no objects (pyr_scene_set_objects names them)");
+        if (f.num_objects != live.pose_table.size()) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".num_objects is not the scene's");
+        if (!f.poses && r.poses == REQUIRED) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".poses is null");
+        for (uint32_t i = 0; f.poses && i < f.num_objects; ++i) {
+            for (float x : f.poses[i].transform)
+                if (!std::isfinite(x)) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectPose.transform has an entry that is not finite");
+            if (!std::isfinite(f.poses[i].scale)) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectPose.scale is not finite");
         }
-        if (u->weights) {
-            if (u->num_weights != live.morph_weights.size()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrMorphUpdate.num_weights is not the scene's");
-            for (uint32_t k = 0; k < u->num_weights; ++k)
-                if (!std::isfinite(u->weights[k])) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrMorphUpdate.weights has a weight that is not finite");
+        for (uint32_t i = 0; f.poses && i < f.num_objects; ++i)
+            if (!affine(f.poses[i].transform)) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrObjectPose.transform: the last row must be 0, 0, 0, 1");
+        if (r.weights != ABSENT && !live.morph.set()) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".num_weights: the scene has no morphs (pyr_scene_set_morphs sets them)");
+        if (r.joints == REQUIRED || f.joints) {
+            if (!live.skin.set()) return fail(PYR_ERR_INVALID_ARGUMENT, name + (r.joints == REQUIRED ? ".num_joints" : ".joints") + ": the scene has no skins (pyr_scene_set_skins binds them)");
+            if ((size_t)f.num_joints * 16 != live.skin.joints.size()) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".num_joints is not the scene's");
+            if (!f.joints) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".joints is null");
+            for (size_t k = 0; k < live.skin.joints.size(); ++k)
+                if (!std::isfinite(f.joints[k])) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".joints has an entry that is not finite");
+            for (uint32_t j = 0; j < f.num_joints; ++j)
+                if (!affine(f.joints + 16 * (size_t)j)) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".joints: the last row must be 0, 0, 0, 1");
+        }
+        if (f.weights) {
+            if (f.num_weights != live.morph.weights.size()) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".num_weights is not the scene's");
+            for (uint32_t k = 0; k < f.num_weights; ++k)
+                if (!std::isfinite(f.weights[k])) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".weights has a weight that is not finite");
         }
         return (int)PYR_OK;
     });
@@ -389,7 +370,7 @@ void set_pose(devpose::DevObject& o, const float* transform, float scale) {
 devpose::Ctx pose_context(PyrScene* s) {
     const LiveGeometry& live = s->live;
     // (while morphs are set, the rest pose of the pose and skin kernels is what the morph kernel wrote)
-    const auto rest = [&](int k) { return !live.arrays[k].kept ? nullptr : !live.morphs.empty() && k < 3 ? (const float*)live.morphed_rest[k].ptr : (const float*)live.arrays[k].rest.ptr; };
+    const auto rest = [&](int k) { return !live.arrays[k].kept ? nullptr : live.morph.set() && k < 3 ? (const float*)live.morph.rest[k].ptr : (const float*)live.arrays[k].rest.ptr; };
     const auto staging = [&](int k) { return (float*)live.arrays[k].staging.ptr; };
     devpose::Ctx c{};
     c.rest_positions = rest(POSITIONS), c.rest_normals = rest(NORMALS), c.rest_frames = rest(FRAMES), c.rest_spheres = rest(SPHERES);
@@ -399,10 +380,10 @@ devpose::Ctx pose_context(PyrScene* s) {
     c.posed_triangles = live.posed_triangles, c.posed_spheres = live.posed_spheres;
     c.beyond_range = (uint32_t*)live.pose_flag.ptr;
     c.lamps = (DevLamp*)s->lamps.ptr, c.num_lamps = (uint32_t)live.lamps.size();
-    c.skins = (const devpose::DevSkin*)live.skin_table.ptr, c.num_skins = (uint32_t)live.skins.size();
-    c.skinned_triangles = live.skinned_triangles, c.num_joints = (uint32_t)(live.skin_joints.size() / 16);
-    c.joints = (const float*)live.joint_table.ptr;
-    c.skin_weights = (const float*)live.skin_weights.ptr, c.skin_joints = (const uint16_t*)live.skin_indices.ptr;
+    c.skins = (const devpose::DevSkin*)live.skin.records.ptr, c.num_skins = (uint32_t)live.skin.table.size();
+    c.skinned_triangles = live.skin.triangles, c.num_joints = (uint32_t)(live.skin.joints.size() / 16);
+    c.joints = (const float*)live.skin.rows.ptr;
+    c.skin_weights = (const float*)live.skin.weights.ptr, c.skin_joints = (const uint16_t*)live.skin.indices.ptr;
     return c;
 }
 
@@ -411,13 +392,13 @@ devpose::MorphCtx morph_context(PyrScene* s, uint32_t num_active) {
     devpose::MorphCtx c{};
     c.rest_positions = (const float*)live.arrays[POSITIONS].rest.ptr, c.rest_normals = (const float*)live.arrays[NORMALS].rest.ptr;
     c.rest_frames = live.arrays[FRAMES].kept ? (const float*)live.arrays[FRAMES].rest.ptr : nullptr;
-    c.positions = (float*)live.morphed_rest[POSITIONS].ptr, c.normals = (float*)live.morphed_rest[NORMALS].ptr;
-    c.frames = live.arrays[FRAMES].kept ? (float*)live.morphed_rest[FRAMES].ptr : nullptr;
-    c.morphs = (const devpose::DevMorph*)live.morph_table.ptr, c.active = (const devpose::ActiveTarget*)live.morph_active.ptr;
-    c.position_deltas = (const float*)live.morph_positions.ptr, c.normal_deltas = (const float*)live.morph_normals.ptr;
-    c.position_rows = live.morph_position_rows, c.normal_rows = live.morph_normal_rows;
-    c.num_morphs = (uint32_t)live.morphs.size(), c.num_active = num_active;
-    c.num_triangles = live.num_triangles, c.morphed_triangles = live.morphed_triangles;
+    c.positions = (float*)live.morph.rest[POSITIONS].ptr, c.normals = (float*)live.morph.rest[NORMALS].ptr;
+    c.frames = live.arrays[FRAMES].kept ? (float*)live.morph.rest[FRAMES].ptr : nullptr;
+    c.morphs = (const devpose::DevMorph*)live.morph.records.ptr, c.active = (const devpose::ActiveTarget*)live.morph.active.ptr;
+    c.position_deltas = (const float*)live.morph.positions.ptr, c.normal_deltas = (const float*)live.morph.normals.ptr;
+    c.position_rows = live.morph.position_rows, c.normal_rows = live.morph.normal_rows;
+    c.num_morphs = (uint32_t)live.morph.table.size(), c.num_active = num_active;
+    c.num_triangles = live.num_triangles, c.morphed_triangles = live.morph.triangles;
     c.flag = (uint32_t*)live.pose_flag.ptr;
     return c;
 }
@@ -427,8 +408,8 @@ devpose::SmoothCtx smooth_context(PyrScene* s) {
     devpose::SmoothCtx c{};
     c.positions = (const float*)live.arrays[POSITIONS].staging.ptr, c.normals = (float*)live.arrays[NORMALS].staging.ptr;
     c.frames = live.arrays[FRAMES].kept ? (float*)live.arrays[FRAMES].staging.ptr : nullptr;
-    c.group_begin = (const uint32_t*)live.smooth_begin.ptr, c.group_corners = (const uint32_t*)live.smooth_corners_table.ptr;
-    c.num_groups = live.smooth_groups, c.num_corners = live.smooth_corners;
+    c.group_begin = (const uint32_t*)live.smooth.begin.ptr, c.group_corners = (const uint32_t*)live.smooth.corner_table.ptr;
+    c.num_groups = live.smooth.groups, c.num_corners = live.smooth.corners;
     c.num_triangles = live.num_triangles;
     c.flag = (uint32_t*)live.pose_flag.ptr;
     return c;
@@ -440,12 +421,12 @@ devpose::SmoothCtx smooth_context(PyrScene* s) {
 // launch, so the table the pose kernels read gives that object none. Where the scene has a smoothing, the normals and frames of
 // its objects are recomputed from the staged positions last.
 int run_pose(PyrScene* s, const std::vector<devpose::DevObject>& table, const std::vector<float>& joints, const std::vector<float>& weights, hipStream_t stream,
-             uint32_t& beyond_range) {
+             uint32_t& flag) {
     const LiveGeometry& live = s->live;
-    std::vector<devpose::DevMorph> morphs(live.morphs.size()); // (these two live until the wait below as well)
+    std::vector<devpose::DevMorph> morphs(live.morph.table.size()); // (these two live until the wait below as well)
     std::vector<devpose::ActiveTarget> active;
     for (size_t k = 0; k < morphs.size(); ++k) {
-        const LiveGeometry::Morph& from = live.morphs[k];
+        const LiveGeometry::Morph& from = live.morph.table[k];
         devpose::DevMorph& to = morphs[k];
         to.first_triangle = table[from.object].first_triangle, to.num_triangles = table[from.object].num_triangles, to.lane = from.lane;
         to.num_targets = from.num_targets, to.has_normals = from.has_normals ? 1u : 0u;
@@ -457,12 +438,12 @@ int run_pose(PyrScene* s, const std::vector<devpose::DevObject>& table, const st
         to.position_row = from.position_row, to.normal_row = from.normal_row;
     }
     std::vector<devpose::DevObject> unskinned; // (these three live until the wait below)
-    std::vector<devpose::DevSkin> skins(live.skins.size());
+    std::vector<devpose::DevSkin> skins(live.skin.table.size());
     std::vector<float> rows(joints.size() / 16 * 12);
-    if (!live.skins.empty()) {
+    if (live.skin.set()) {
         unskinned = table;
         for (size_t k = 0; k < skins.size(); ++k) {
-            const LiveGeometry::Skin& from = live.skins[k];
+            const LiveGeometry::Skin& from = live.skin.table[k];
             devpose::DevSkin& to = skins[k];
             to.pose = table[from.object].pose;
             to.first_triangle = table[from.object].first_triangle, to.num_triangles = table[from.object].num_triangles, to.lane = from.lane;
@@ -478,61 +459,62 @@ int run_pose(PyrScene* s, const std::vector<devpose::DevObject>& table, const st
         for (size_t j = 0; j < rows.size() / 12; ++j)
             for (int col = 0; col < 4; ++col)
                 for (int row = 0; row < 3; ++row) rows[12 * j + 3 * col + row] = joints[16 * j + 4 * col + row];
-        HIP_TRY(hipMemcpyAsync(live.skin_table.ptr, skins.data(), skins.size() * sizeof(devpose::DevSkin), hipMemcpyHostToDevice, stream));
-        HIP_TRY(hipMemcpyAsync(live.joint_table.ptr, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(live.skin.records.ptr, skins.data(), skins.size() * sizeof(devpose::DevSkin), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(live.skin.rows.ptr, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, stream));
     }
-    const std::vector<devpose::DevObject>& objects = live.skins.empty() ? table : unskinned;
+    const std::vector<devpose::DevObject>& objects = !live.skin.set() ? table : unskinned;
     HIP_TRY(hipMemcpyAsync(s->live.pose_objects.ptr, objects.data(), objects.size() * sizeof(devpose::DevObject), hipMemcpyHostToDevice, stream));
     HIP_TRY(hipMemsetAsync(s->live.pose_flag.ptr, 0, 4, stream));
     if (!morphs.empty()) {
-        HIP_TRY(hipMemcpyAsync(live.morph_table.ptr, morphs.data(), morphs.size() * sizeof(devpose::DevMorph), hipMemcpyHostToDevice, stream));
-        if (!active.empty()) HIP_TRY(hipMemcpyAsync(live.morph_active.ptr, active.data(), active.size() * sizeof(devpose::ActiveTarget), hipMemcpyHostToDevice, stream));
+        HIP_TRY(hipMemcpyAsync(live.morph.records.ptr, morphs.data(), morphs.size() * sizeof(devpose::DevMorph), hipMemcpyHostToDevice, stream));
+        if (!active.empty()) HIP_TRY(hipMemcpyAsync(live.morph.active.ptr, active.data(), active.size() * sizeof(devpose::ActiveTarget), hipMemcpyHostToDevice, stream));
         const hipError_t em = devpose::launch_morph(morph_context(s, (uint32_t)active.size()), stream);
         if (em != hipSuccess) return hip_fail(em, "morph kernel");
     }
     const hipError_t e = devpose::launch_pose(pose_context(s), stream);
     if (e != hipSuccess) return hip_fail(e, "pose kernels");
-    if (live.smooth_groups) {
+    if (live.smooth.groups) {
         const hipError_t es = devpose::launch_smooth(smooth_context(s), stream);
         if (es != hipSuccess) return hip_fail(es, "smoothing kernel");
     }
-    HIP_TRY(hipMemcpyAsync(&beyond_range, s->live.pose_flag.ptr, 4, hipMemcpyDeviceToHost, stream));
+    HIP_TRY(hipMemcpyAsync(&flag, s->live.pose_flag.ptr, 4, hipMemcpyDeviceToHost, stream));
     HIP_TRY(hipStreamSynchronize(stream));
     return PYR_OK;
 }
 
-// Bit 0 of the flag word: a bound beyond the coordinate range; bit 1 without it: a morphed normal that cannot be normalised; bit 2
-// without either: a recomputed normal that cannot be.
-const char* const kMorphedNormalMessage =
-    "a morphed normal or the tangent frame rebuilt against it has a squared length outside 1e-30 .. 1e30 and cannot be normalised (pyrite_gpu.h, pyr_scene_morph)";
-
-const char* const kRecomputedNormalMessage =
-    "a recomputed normal or the tangent frame rebuilt against it has a squared length outside 1e-30 .. 1e30 and cannot be normalised (pyrite_gpu.h, pyr_scene_set_smoothing)";
-
-// pyr_scene_pose, pyr_scene_skin and pyr_scene_morph: `poses` nullptr keeps the poses the scene is in, `new_joints` nullptr its
-// joints, `new_weights` nullptr its morph weights.
-int scene_pose(PyrScene* s, uint32_t mode, const PyrObjectPose* poses, const float* new_joints, const float* new_weights, hipStream_t stream) {
+// pyr_scene_pose, pyr_scene_skin and pyr_scene_morph, after check_frame: a table the frame leaves null stays as the scene has it.
+int scene_pose(PyrScene* s, const Frame& f, hipStream_t stream) {
     const auto t_start = Clock::now();
     HIP_TRY(hipSetDevice(s->device));
     LiveGeometry& live = s->live;
+    const uint32_t mode = f.mode;
     int rc;
     if (mode == PYR_UPDATE_REFIT && (rc = prepare_refit(s)) != PYR_OK) return rc;
     std::vector<devpose::DevObject> table = live.pose_table;
-    if (poses)
-        for (size_t i = 0; i < table.size(); ++i) set_pose(table[i], poses[i].transform, poses[i].scale);
-    std::vector<float> joints = live.skin_joints;
-    if (new_joints) joints.assign(new_joints, new_joints + joints.size());
-    std::vector<float> weights = live.morph_weights;
-    if (new_weights) weights.assign(new_weights, new_weights + weights.size());
-    uint32_t beyond_range = 0;
-    if ((rc = run_pose(s, table, joints, weights, stream, beyond_range)) != PYR_OK) return rc;
+    if (f.poses)
+        for (size_t i = 0; i < table.size(); ++i) set_pose(table[i], f.poses[i].transform, f.poses[i].scale);
+    std::vector<float> joints = live.skin.joints;
+    if (f.joints) joints.assign(f.joints, f.joints + joints.size());
+    std::vector<float> weights = live.morph.weights;
+    if (f.weights) weights.assign(f.weights, f.weights + weights.size());
+    uint32_t flag = 0;
+    if ((rc = run_pose(s, table, joints, weights, stream, flag)) != PYR_OK) return rc;
     const auto refused = [&](int why) { // no record has been touched: the staging arrays go back to the poses, joints and weights the scene is in
-        const int back = run_pose(s, live.pose_table, live.skin_joints, live.morph_weights, stream, beyond_range);
+        const int back = run_pose(s, live.pose_table, live.skin.joints, live.morph.weights, stream, flag);
         return back != PYR_OK ? back : why;
     };
-    if (beyond_range & 1u) return refused(fail(PYR_ERR_UNSUPPORTED, kCoordinateRangeMessage));
-    if (beyond_range & 2u) return refused(fail(PYR_ERR_UNSUPPORTED, kMorphedNormalMessage));
-    if (beyond_range != 0) return refused(fail(PYR_ERR_UNSUPPORTED, kRecomputedNormalMessage));
+    const struct { // what each bit of the flag word refuses the frame with; the first one raised decides
+        uint32_t bit;
+        const char* message;
+    } raised[] = {
+        {devpose::Flag::kBeyondRange, kCoordinateRangeMessage},
+        {devpose::Flag::kMorphedNormal,
+         "a morphed normal or the tangent frame rebuilt against it has a squared length outside 1e-30 .. 1e30 and cannot be normalised (pyrite_gpu.h, pyr_scene_morph)"},
+        {devpose::Flag::kSmoothedNormal,
+         "a recomputed normal or the tangent frame rebuilt against it has a squared length outside 1e-30 .. 1e30 and cannot be normalised (pyrite_gpu.h, pyr_scene_set_smoothing)"},
+    };
+    for (const auto& r : raised)
+        if (flag & r.bit) return refused(fail(PYR_ERR_UNSUPPORTED, r.message));
     PyrUpdateInfo info{};
     info.mode_used = mode;
     info.area_ratio = 1.0;
@@ -547,12 +529,12 @@ int scene_pose(PyrScene* s, uint32_t mode, const PyrObjectPose* poses, const flo
             live.posed();
             return refused(rc);
         }
-        live.pose_table.swap(table), live.skin_joints.swap(joints), live.morph_weights.swap(weights);
+        live.pose_table.swap(table), live.skin.joints.swap(joints), live.morph.weights.swap(weights);
         return PYR_OK;
     }
 
     // ---- refit: every record and box from the staging arrays, as the host form of pyr_scene_update given all four arrays
-    live.pose_table.swap(table), live.skin_joints.swap(joints), live.morph_weights.swap(weights);
+    live.pose_table.swap(table), live.skin.joints.swap(joints), live.morph.weights.swap(weights);
     live.posed();
     const float* source[NUM_ARRAYS];
     for (int k = 0; k < NUM_ARRAYS; ++k) source[k] = live.kept_floats(k) ? (const float*)live.arrays[k].staging.ptr : nullptr;
@@ -561,20 +543,33 @@ int scene_pose(PyrScene* s, uint32_t mode, const PyrObjectPose* poses, const flo
     return refit_from(s, source, live.num_triangles != 0, live.num_spheres != 0, false, stream, t_start, &t_posed, info);
 }
 
+// What every attachment to an object refuses first -- a skin, a morph, a smoothing: reserved words, the object, an object without
+// triangles, two on one object. `name`: the struct; `plural`: what two of them are called.
+inline bool reserved_clear(const PyrSmoothing& s) { return s.reserved0 == 0 && std::all_of(std::begin(s.reserved), std::end(s.reserved), [](uint32_t w) { return w == 0; }); }
+template <class T>
+bool reserved_clear(const T& t) {
+    return std::all_of(std::begin(t.reserved), std::end(t.reserved), [](uint32_t w) { return w == 0; });
+}
+template <class T>
+int check_attachments(const LiveGeometry& live, const T* items, uint32_t n, const std::string& name, const char* plural) {
+    for (uint32_t k = 0; k < n; ++k)
+        if (!reserved_clear(items[k])) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".reserved must be zero");
+    for (uint32_t k = 0; k < n; ++k)
+        if (items[k].object >= live.pose_table.size()) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".object is not one of the scene's objects");
+    for (uint32_t k = 0; k < n; ++k)
+        if (live.pose_table[items[k].object].num_triangles == 0) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".object: the object has no triangles");
+    std::vector<uint32_t> taken;
+    for (uint32_t k = 0; k < n; ++k) taken.push_back(items[k].object);
+    std::sort(taken.begin(), taken.end());
+    if (std::adjacent_find(taken.begin(), taken.end()) != taken.end()) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".object: two " + plural + " on one object");
+    return PYR_OK;
+}
+
 // What pyr_scene_set_skins refuses of the skins themselves, in the order pyrite_gpu.h gives.
 int check_skins(const LiveGeometry& live, const PyrSkin* skins, uint32_t n) {
     const auto triangles_of = [&](const PyrSkin& s) { return (size_t)live.pose_table[s.object].num_triangles; };
-    for (uint32_t k = 0; k < n; ++k)
-        for (uint32_t word : skins[k].reserved)
-            if (word != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSkin.reserved must be zero");
-    for (uint32_t k = 0; k < n; ++k)
-        if (skins[k].object >= live.pose_table.size()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSkin.object is not one of the scene's objects");
-    for (uint32_t k = 0; k < n; ++k)
-        if (triangles_of(skins[k]) == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSkin.object: the object has no triangles");
-    std::vector<uint32_t> taken;
-    for (uint32_t k = 0; k < n; ++k) taken.push_back(skins[k].object);
-    std::sort(taken.begin(), taken.end());
-    if (std::adjacent_find(taken.begin(), taken.end()) != taken.end()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSkin.object: two skins on one object");
+    const int rc = check_attachments(live, skins, n, "PyrSkin", "skins");
+    if (rc != PYR_OK) return rc;
     for (uint32_t k = 0; k < n; ++k)
         if (skins[k].num_joints == 0 || skins[k].num_joints > 65536u) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSkin.num_joints must be 1 to 65,536");
     for (uint32_t k = 0; k < n; ++k) {
@@ -598,17 +593,8 @@ int check_skins(const LiveGeometry& live, const PyrSkin* skins, uint32_t n) {
 
 // What pyr_scene_set_morphs refuses of the morphs themselves, in the order pyrite_gpu.h gives.
 int check_morphs(const LiveGeometry& live, const PyrMorph* morphs, uint32_t n) {
-    for (uint32_t k = 0; k < n; ++k)
-        for (uint32_t word : morphs[k].reserved)
-            if (word != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrMorph.reserved must be zero");
-    for (uint32_t k = 0; k < n; ++k)
-        if (morphs[k].object >= live.pose_table.size()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrMorph.object is not one of the scene's objects");
-    for (uint32_t k = 0; k < n; ++k)
-        if (live.pose_table[morphs[k].object].num_triangles == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrMorph.object: the object has no triangles");
-    std::vector<uint32_t> taken;
-    for (uint32_t k = 0; k < n; ++k) taken.push_back(morphs[k].object);
-    std::sort(taken.begin(), taken.end());
-    if (std::adjacent_find(taken.begin(), taken.end()) != taken.end()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrMorph.object: two morphs on one object");
+    const int rc = check_attachments(live, morphs, n, "PyrMorph", "morphs");
+    if (rc != PYR_OK) return rc;
     for (uint32_t k = 0; k < n; ++k)
         if (morphs[k].num_targets == 0 || morphs[k].num_targets > 256u) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrMorph.num_targets must be 1 to 256");
     for (uint32_t k = 0; k < n; ++k)
@@ -624,22 +610,136 @@ int check_morphs(const LiveGeometry& live, const PyrMorph* morphs, uint32_t n) {
 
 // What pyr_scene_set_smoothing refuses of the smoothings themselves, in the order pyrite_gpu.h gives.
 int check_smoothings(const LiveGeometry& live, const PyrSmoothing* smoothings, uint32_t n) {
-    for (uint32_t k = 0; k < n; ++k) {
-        if (smoothings[k].reserved0 != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSmoothing.reserved must be zero");
-        for (uint32_t word : smoothings[k].reserved)
-            if (word != 0) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSmoothing.reserved must be zero");
-    }
-    for (uint32_t k = 0; k < n; ++k)
-        if (smoothings[k].object >= live.pose_table.size()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSmoothing.object is not one of the scene's objects");
-    for (uint32_t k = 0; k < n; ++k)
-        if (live.pose_table[smoothings[k].object].num_triangles == 0) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSmoothing.object: the object has no triangles");
-    std::vector<uint32_t> taken;
-    for (uint32_t k = 0; k < n; ++k) taken.push_back(smoothings[k].object);
-    std::sort(taken.begin(), taken.end());
-    if (std::adjacent_find(taken.begin(), taken.end()) != taken.end()) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSmoothing.object: two smoothings on one object");
+    const int rc = check_attachments(live, smoothings, n, "PyrSmoothing", "smoothings");
+    if (rc != PYR_OK) return rc;
     for (uint32_t k = 0; k < n; ++k)
         if (!smoothings[k].vertex_ids) return fail(PYR_ERR_INVALID_ARGUMENT, "PyrSmoothing.vertex_ids is null");
     return PYR_OK;
+}
+
+// pyr_scene_set_skins, once it has skins to set: the bindings one skin after the other.
+int install_skins(LiveGeometry& live, const PyrSkin* skins, uint32_t num_skins) {
+    int rc;
+    // the bindings one skin after the other, on the device before anything of the old skins is let go
+    std::vector<LiveGeometry::Skin> table(num_skins);
+    std::vector<float> weights;
+    std::vector<uint16_t> indices;
+    uint32_t lane = 0, joint = 0;
+    for (uint32_t k = 0; k < num_skins; ++k) {
+        const size_t words = 12 * (size_t)live.pose_table[skins[k].object].num_triangles;
+        table[k] = {skins[k].object, skins[k].num_joints, joint, lane};
+        weights.insert(weights.end(), skins[k].weights, skins[k].weights + words);
+        indices.insert(indices.end(), skins[k].joints, skins[k].joints + words);
+        lane += live.pose_table[skins[k].object].num_triangles, joint += skins[k].num_joints; // disjoint ranges: below 2^28; at most 2^16 a skin
+    }
+    LiveGeometry::Skins fresh;
+    if ((rc = fresh.weights.upload(weights.data(), weights.size() * 4)) != PYR_OK) return rc;
+    if ((rc = fresh.indices.upload(indices.data(), indices.size() * 2)) != PYR_OK) return rc;
+    if ((rc = fresh.records.alloc((size_t)num_skins * sizeof(devpose::DevSkin))) != PYR_OK) return rc;
+    if ((rc = fresh.rows.alloc((size_t)joint * 48)) != PYR_OK) return rc;
+    fresh.table.swap(table);
+    for (uint32_t j = 0; j < joint; ++j) fresh.joints.insert(fresh.joints.end(), kIdentity, kIdentity + 16);
+    fresh.triangles = lane;
+    live.skin.swap(fresh);
+    live.recount_lanes();
+    return PYR_OK;
+}
+
+// pyr_scene_set_morphs, once it has morphs to set: the deltas one morph after the other, and the morphed rest as a copy of rest.
+int install_morphs(LiveGeometry& live, const PyrMorph* morphs, uint32_t num_morphs) {
+    int rc;
+    // the deltas one morph after the other, on the device before anything of the old morphs is let go
+    std::vector<LiveGeometry::Morph> table(num_morphs);
+    std::vector<float> positions, normals;
+    uint32_t lane = 0, weight = 0;
+    for (uint32_t k = 0; k < num_morphs; ++k) {
+        const uint32_t triangles = live.pose_table[morphs[k].object].num_triangles;
+        const size_t words = 9 * (size_t)triangles * morphs[k].num_targets;
+        table[k] = {morphs[k].object, morphs[k].num_targets, weight, lane, positions.size() / 9, normals.size() / 9, morphs[k].normal_deltas != nullptr};
+        positions.insert(positions.end(), morphs[k].position_deltas, morphs[k].position_deltas + words);
+        if (morphs[k].normal_deltas) normals.insert(normals.end(), morphs[k].normal_deltas, morphs[k].normal_deltas + words);
+        lane += triangles, weight += morphs[k].num_targets; // disjoint ranges: below 2^28; at most 256 a morph
+    }
+    LiveGeometry::Morphs fresh;
+    if ((rc = fresh.positions.upload(positions.data(), positions.size() * 4)) != PYR_OK) return rc;
+    if (!normals.empty() && (rc = fresh.normals.upload(normals.data(), normals.size() * 4)) != PYR_OK) return rc;
+    if ((rc = fresh.records.alloc((size_t)num_morphs * sizeof(devpose::DevMorph))) != PYR_OK) return rc;
+    if ((rc = fresh.active.alloc((size_t)weight * sizeof(devpose::ActiveTarget))) != PYR_OK) return rc;
+    for (int k = 0; k < 3; ++k) {
+        const size_t bytes = live.kept_floats(k) * 4;
+        if (!bytes) continue;
+        if ((rc = fresh.rest[k].alloc(bytes)) != PYR_OK) return rc;
+        HIP_TRY(hipMemcpy(fresh.rest[k].ptr, live.arrays[k].rest.ptr, bytes, hipMemcpyDeviceToDevice));
+    }
+    fresh.table.swap(table);
+    fresh.weights.assign(weight, 0.0f);
+    fresh.triangles = lane;
+    fresh.position_rows = positions.size() / 9, fresh.normal_rows = normals.size() / 9;
+    live.morph.swap(fresh);
+    return PYR_OK;
+}
+
+// pyr_scene_set_smoothing, once it has smoothings to set: the groups of corners as a CSR.
+int install_smoothings(LiveGeometry& live, const PyrSmoothing* smoothings, uint32_t num_smoothings) {
+    int rc;
+    // the groups one smoothing after the other: a group's number is its rank by first corner within its object, so neighbouring
+    // lanes touch neighbouring triangles whatever the caller's labels are; rows are filled in ascending corner order
+    std::vector<uint32_t> objects, begin(1, 0u), corners;
+    std::vector<float> rest_p, rest_n;
+    for (uint32_t k = 0; k < num_smoothings; ++k) {
+        const devpose::DevObject& o = live.pose_table[smoothings[k].object];
+        const size_t words = 9 * (size_t)o.num_triangles, count = 3 * (size_t)o.num_triangles;
+        rest_p.resize(words), rest_n.resize(words); // the orientation is the rest pose's: the device copy taken when objects were named
+        HIP_TRY(hipMemcpy(rest_p.data(), (const float*)live.arrays[POSITIONS].rest.ptr + 9 * (size_t)o.first_triangle, words * 4, hipMemcpyDeviceToHost));
+        HIP_TRY(hipMemcpy(rest_n.data(), (const float*)live.arrays[NORMALS].rest.ptr + 9 * (size_t)o.first_triangle, words * 4, hipMemcpyDeviceToHost));
+        const uint32_t* ids = smoothings[k].vertex_ids;
+        std::unordered_map<uint32_t, uint32_t> group_of; // label -> group within this object, numbered by first appearance
+        std::vector<uint32_t> group(count), size;
+        for (size_t i = 0; i < count; ++i) {
+            const auto found = group_of.emplace(ids[i], (uint32_t)size.size());
+            if (found.second) size.push_back(0u);
+            group[i] = found.first->second, ++size[group[i]];
+        }
+        std::vector<uint32_t> fill(size.size());
+        for (size_t g = 0; g < size.size(); ++g) fill[g] = begin.back(), begin.push_back(begin.back() + size[g]);
+        corners.resize(begin.back());
+        for (size_t i = 0; i < count; ++i) {
+            const size_t t = i / 3;
+            const bool negated = pose::face_negated(&rest_p[9 * t], &rest_n[9 * t]);
+            corners[fill[group[i]]++] = (3u * o.first_triangle + (uint32_t)i) | (negated ? devpose::kNegated : 0u); // below 3 * 2^28
+        }
+        objects.push_back(smoothings[k].object);
+    }
+    LiveGeometry::Smooth fresh; // on the device before anything of the old smoothing is let go
+    if ((rc = fresh.begin.upload(begin.data(), begin.size() * 4)) != PYR_OK) return rc;
+    if ((rc = fresh.corner_table.upload(corners.data(), corners.size() * 4)) != PYR_OK) return rc;
+    fresh.objects.swap(objects);
+    fresh.groups = (uint32_t)begin.size() - 1u, fresh.corners = (uint32_t)corners.size();
+    live.smooth.swap(fresh);
+    return PYR_OK;
+}
+
+// The skeleton of pyr_scene_set_skins, pyr_scene_set_morphs and pyr_scene_set_smoothing: what all three refuse, `check` for the
+// attachments themselves, nothing to do where none are set and none are given, the wait (an earlier call's kernels may still read
+// what is about to go), then `forget` for none or `install` for new ones -- which has everything on the device before it lets
+// anything of the old ones go. `plural`: the argument's name; `entry`: the entry point's.
+template <class T, class State, class Check, class Install>
+int set_attachments(PyrScene* scene, const T* items, uint32_t n, const std::string& plural, const char* entry, State LiveGeometry::*state, void (LiveGeometry::*forget)(), Check check,
+                    Install install) {
+    if (n != 0 && !items) return fail(PYR_ERR_INVALID_ARGUMENT, "null " + plural + " with a non-zero num_" + plural);
+    if (!scene) return fail(PYR_ERR_INVALID_ARGUMENT, "null scene");
+    LiveGeometry& live = scene->live;
+    if (live.pose_table.empty()) return fail(PYR_ERR_INVALID_ARGUMENT, std::string(entry) + ": the scene has no objects (pyr_scene_set_objects names them)");
+    const int rc = check(live, items, n);
+    if (rc != PYR_OK) return rc;
+    if (n == 0 && !(live.*state).set()) return PYR_OK;
+    HIP_TRY(hipSetDevice(scene->device));
+    HIP_TRY(hipDeviceSynchronize());
+    if (n == 0) {
+        (live.*forget)();
+        return PYR_OK;
+    }
+    return install(live, items, n);
 }
 
 // ranges inside the counts and pairwise disjoint, triangles and spheres each
@@ -696,167 +796,43 @@ int pyr_scene_set_objects(PyrScene* scene, const PyrObjectRange* ranges, uint32_
         o.triangle_lane = triangle_lane, o.sphere_lane = sphere_lane;
         triangle_lane += o.num_triangles, sphere_lane += o.num_spheres; // disjoint ranges inside the counts: below 2^28 in all
     }
-    live.posed_triangles = triangle_lane, live.posed_spheres = sphere_lane;
+    live.recount_lanes();
     return PYR_OK;
 }
 
 int pyr_scene_pose(PyrScene* scene, const PyrPoseUpdate* update, void* hip_stream) {
-    int rc = check_pose_args(scene, update);
-    if (rc != PYR_OK) return rc;
-    return scene_pose(scene, update->mode, update->poses, nullptr, nullptr, (hipStream_t)hip_stream);
+    Frame f;
+    if (update) f.mode = update->mode, f.poses = update->poses, f.num_objects = update->num_objects;
+    const int rc = check_frame(scene, update, f, kPoseFrame);
+    return rc != PYR_OK ? rc : scene_pose(scene, f, (hipStream_t)hip_stream);
 }
 
 int pyr_scene_set_skins(PyrScene* scene, const PyrSkin* skins, uint32_t num_skins) {
-    if (num_skins != 0 && !skins) return fail(PYR_ERR_INVALID_ARGUMENT, "null skins with a non-zero num_skins");
-    if (!scene) return fail(PYR_ERR_INVALID_ARGUMENT, "null scene");
-    LiveGeometry& live = scene->live;
-    if (live.pose_table.empty()) return fail(PYR_ERR_INVALID_ARGUMENT, "pyr_scene_set_skins: the scene has no objects (pyr_scene_set_objects names them)");
-    int rc = check_skins(live, skins, num_skins);
-    if (rc != PYR_OK) return rc;
-    if (num_skins == 0 && live.skins.empty()) return PYR_OK;
-    HIP_TRY(hipSetDevice(scene->device));
-    HIP_TRY(hipDeviceSynchronize()); // an earlier call's kernels may still read the bindings
-    if (num_skins == 0) {
-        live.forget_skins();
-        return PYR_OK;
-    }
-    // the bindings one skin after the other, on the device before anything of the old skins is let go
-    std::vector<LiveGeometry::Skin> table(num_skins);
-    std::vector<float> weights;
-    std::vector<uint16_t> indices;
-    uint32_t lane = 0, joint = 0;
-    for (uint32_t k = 0; k < num_skins; ++k) {
-        const size_t words = 12 * (size_t)live.pose_table[skins[k].object].num_triangles;
-        table[k] = {skins[k].object, skins[k].num_joints, joint, lane};
-        weights.insert(weights.end(), skins[k].weights, skins[k].weights + words);
-        indices.insert(indices.end(), skins[k].joints, skins[k].joints + words);
-        lane += live.pose_table[skins[k].object].num_triangles, joint += skins[k].num_joints; // disjoint ranges: below 2^28; at most 2^16 a skin
-    }
-    DeviceBuffer fresh[4]; // weights, indices, DevSkin records, joint rows
-    if ((rc = fresh[0].upload(weights.data(), weights.size() * 4)) != PYR_OK) return rc;
-    if ((rc = fresh[1].upload(indices.data(), indices.size() * 2)) != PYR_OK) return rc;
-    if ((rc = fresh[2].alloc((size_t)num_skins * sizeof(devpose::DevSkin))) != PYR_OK) return rc;
-    if ((rc = fresh[3].alloc((size_t)joint * 48)) != PYR_OK) return rc;
-    DeviceBuffer* const own[4] = {&live.skin_weights, &live.skin_indices, &live.skin_table, &live.joint_table};
-    for (int k = 0; k < 4; ++k) std::swap(own[k]->ptr, fresh[k].ptr), std::swap(own[k]->bytes, fresh[k].bytes);
-    live.skins.swap(table);
-    live.skin_joints.clear();
-    for (uint32_t j = 0; j < joint; ++j) live.skin_joints.insert(live.skin_joints.end(), kIdentity, kIdentity + 16);
-    live.skinned_triangles = lane;
-    live.posed_triangles = 0;
-    for (const devpose::DevObject& o : live.pose_table) live.posed_triangles += o.num_triangles;
-    live.posed_triangles -= lane;
-    return PYR_OK;
+    return set_attachments(scene, skins, num_skins, "skins", "pyr_scene_set_skins", &LiveGeometry::skin, &LiveGeometry::forget_skins, check_skins, install_skins);
 }
 
 int pyr_scene_skin(PyrScene* scene, const PyrSkinUpdate* update, void* hip_stream) {
-    int rc = check_skin_args(scene, update);
-    if (rc != PYR_OK) return rc;
-    return scene_pose(scene, update->mode, update->poses, update->joints, nullptr, (hipStream_t)hip_stream);
+    Frame f;
+    if (update) f.mode = update->mode, f.poses = update->poses, f.num_objects = update->num_objects, f.joints = update->joints, f.num_joints = update->num_joints;
+    const int rc = check_frame(scene, update, f, kSkinFrame);
+    return rc != PYR_OK ? rc : scene_pose(scene, f, (hipStream_t)hip_stream);
 }
 
 int pyr_scene_set_morphs(PyrScene* scene, const PyrMorph* morphs, uint32_t num_morphs) {
-    if (num_morphs != 0 && !morphs) return fail(PYR_ERR_INVALID_ARGUMENT, "null morphs with a non-zero num_morphs");
-    if (!scene) return fail(PYR_ERR_INVALID_ARGUMENT, "null scene");
-    LiveGeometry& live = scene->live;
-    if (live.pose_table.empty()) return fail(PYR_ERR_INVALID_ARGUMENT, "pyr_scene_set_morphs: the scene has no objects (pyr_scene_set_objects names them)");
-    int rc = check_morphs(live, morphs, num_morphs);
-    if (rc != PYR_OK) return rc;
-    if (num_morphs == 0 && live.morphs.empty()) return PYR_OK;
-    HIP_TRY(hipSetDevice(scene->device));
-    HIP_TRY(hipDeviceSynchronize()); // an earlier call's kernels may still read the deltas and the morphed rest
-    if (num_morphs == 0) {
-        live.forget_morphs();
-        return PYR_OK;
-    }
-    // the deltas one morph after the other, on the device before anything of the old morphs is let go
-    std::vector<LiveGeometry::Morph> table(num_morphs);
-    std::vector<float> positions, normals;
-    uint32_t lane = 0, weight = 0;
-    for (uint32_t k = 0; k < num_morphs; ++k) {
-        const uint32_t triangles = live.pose_table[morphs[k].object].num_triangles;
-        const size_t words = 9 * (size_t)triangles * morphs[k].num_targets;
-        table[k] = {morphs[k].object, morphs[k].num_targets, weight, lane, positions.size() / 9, normals.size() / 9, morphs[k].normal_deltas != nullptr};
-        positions.insert(positions.end(), morphs[k].position_deltas, morphs[k].position_deltas + words);
-        if (morphs[k].normal_deltas) normals.insert(normals.end(), morphs[k].normal_deltas, morphs[k].normal_deltas + words);
-        lane += triangles, weight += morphs[k].num_targets; // disjoint ranges: below 2^28; at most 256 a morph
-    }
-    DeviceBuffer fresh[7]; // position deltas, normal deltas, DevMorph records, a frame's pairs, the morphed rest
-    if ((rc = fresh[0].upload(positions.data(), positions.size() * 4)) != PYR_OK) return rc;
-    if (!normals.empty() && (rc = fresh[1].upload(normals.data(), normals.size() * 4)) != PYR_OK) return rc;
-    if ((rc = fresh[2].alloc((size_t)num_morphs * sizeof(devpose::DevMorph))) != PYR_OK) return rc;
-    if ((rc = fresh[3].alloc((size_t)weight * sizeof(devpose::ActiveTarget))) != PYR_OK) return rc;
-    for (int k = 0; k < 3; ++k) {
-        const size_t bytes = live.kept_floats(k) * 4;
-        if (!bytes) continue;
-        if ((rc = fresh[4 + k].alloc(bytes)) != PYR_OK) return rc;
-        HIP_TRY(hipMemcpy(fresh[4 + k].ptr, live.arrays[k].rest.ptr, bytes, hipMemcpyDeviceToDevice));
-    }
-    DeviceBuffer* const own[7] = {&live.morph_positions, &live.morph_normals, &live.morph_table, &live.morph_active, &live.morphed_rest[0], &live.morphed_rest[1], &live.morphed_rest[2]};
-    for (int k = 0; k < 7; ++k) std::swap(own[k]->ptr, fresh[k].ptr), std::swap(own[k]->bytes, fresh[k].bytes);
-    live.morphs.swap(table);
-    live.morph_weights.assign(weight, 0.0f);
-    live.morphed_triangles = lane;
-    live.morph_position_rows = positions.size() / 9, live.morph_normal_rows = normals.size() / 9;
-    return PYR_OK;
+    return set_attachments(scene, morphs, num_morphs, "morphs", "pyr_scene_set_morphs", &LiveGeometry::morph, &LiveGeometry::forget_morphs, check_morphs, install_morphs);
 }
 
 int pyr_scene_morph(PyrScene* scene, const PyrMorphUpdate* update, void* hip_stream) {
-    int rc = check_morph_args(scene, update);
-    if (rc != PYR_OK) return rc;
-    return scene_pose(scene, update->mode, update->poses, update->joints, update->weights, (hipStream_t)hip_stream);
+    Frame f;
+    if (update)
+        f.mode = update->mode, f.poses = update->poses, f.num_objects = update->num_objects, f.joints = update->joints, f.num_joints = update->num_joints, f.weights = update->weights,
+        f.num_weights = update->num_weights;
+    const int rc = check_frame(scene, update, f, kMorphFrame);
+    return rc != PYR_OK ? rc : scene_pose(scene, f, (hipStream_t)hip_stream);
 }
 
 int pyr_scene_set_smoothing(PyrScene* scene, const PyrSmoothing* smoothings, uint32_t num_smoothings) {
-    if (num_smoothings != 0 && !smoothings) return fail(PYR_ERR_INVALID_ARGUMENT, "null smoothings with a non-zero num_smoothings");
-    if (!scene) return fail(PYR_ERR_INVALID_ARGUMENT, "null scene");
-    LiveGeometry& live = scene->live;
-    if (live.pose_table.empty()) return fail(PYR_ERR_INVALID_ARGUMENT, "pyr_scene_set_smoothing: the scene has no objects (pyr_scene_set_objects names them)");
-    int rc = check_smoothings(live, smoothings, num_smoothings);
-    if (rc != PYR_OK) return rc;
-    if (num_smoothings == 0 && live.smoothed_objects.empty()) return PYR_OK;
-    HIP_TRY(hipSetDevice(scene->device));
-    HIP_TRY(hipDeviceSynchronize()); // an earlier call's kernels may still read the groups
-    if (num_smoothings == 0) {
-        live.forget_smoothing();
-        return PYR_OK;
-    }
-    // the groups one smoothing after the other: a group's number is its rank by first corner within its object, so neighbouring
-    // lanes touch neighbouring triangles whatever the caller's labels are; rows are filled in ascending corner order
-    std::vector<uint32_t> objects, begin(1, 0u), corners;
-    std::vector<float> rest_p, rest_n;
-    for (uint32_t k = 0; k < num_smoothings; ++k) {
-        const devpose::DevObject& o = live.pose_table[smoothings[k].object];
-        const size_t words = 9 * (size_t)o.num_triangles, count = 3 * (size_t)o.num_triangles;
-        rest_p.resize(words), rest_n.resize(words); // the orientation is the rest pose's: the device copy taken when objects were named
-        HIP_TRY(hipMemcpy(rest_p.data(), (const float*)live.arrays[POSITIONS].rest.ptr + 9 * (size_t)o.first_triangle, words * 4, hipMemcpyDeviceToHost));
-        HIP_TRY(hipMemcpy(rest_n.data(), (const float*)live.arrays[NORMALS].rest.ptr + 9 * (size_t)o.first_triangle, words * 4, hipMemcpyDeviceToHost));
-        const uint32_t* ids = smoothings[k].vertex_ids;
-        std::unordered_map<uint32_t, uint32_t> group_of; // label -> group within this object, numbered by first appearance
-        std::vector<uint32_t> group(count), size;
-        for (size_t i = 0; i < count; ++i) {
-            const auto found = group_of.emplace(ids[i], (uint32_t)size.size());
-            if (found.second) size.push_back(0u);
-            group[i] = found.first->second, ++size[group[i]];
-        }
-        std::vector<uint32_t> fill(size.size());
-        for (size_t g = 0; g < size.size(); ++g) fill[g] = begin.back(), begin.push_back(begin.back() + size[g]);
-        corners.resize(begin.back());
-        for (size_t i = 0; i < count; ++i) {
-            const size_t t = i / 3;
-            const bool negated = pose::face_negated(&rest_p[9 * t], &rest_n[9 * t]);
-            corners[fill[group[i]]++] = (3u * o.first_triangle + (uint32_t)i) | (negated ? devpose::kNegated : 0u); // below 3 * 2^28
-        }
-        objects.push_back(smoothings[k].object);
-    }
-    DeviceBuffer fresh[2]; // on the device before anything of the old smoothing is let go
-    if ((rc = fresh[0].upload(begin.data(), begin.size() * 4)) != PYR_OK) return rc;
-    if ((rc = fresh[1].upload(corners.data(), corners.size() * 4)) != PYR_OK) return rc;
-    DeviceBuffer* const own[2] = {&live.smooth_begin, &live.smooth_corners_table};
-    for (int k = 0; k < 2; ++k) std::swap(own[k]->ptr, fresh[k].ptr), std::swap(own[k]->bytes, fresh[k].bytes);
-    live.smoothed_objects.swap(objects);
-    live.smooth_groups = (uint32_t)begin.size() - 1u, live.smooth_corners = (uint32_t)corners.size();
-    return PYR_OK;
+    return set_attachments(scene, smoothings, num_smoothings, "smoothings", "pyr_scene_set_smoothing", &LiveGeometry::smooth, &LiveGeometry::forget_smoothing, check_smoothings, install_smoothings);
 }
 
 int pyr_scene_geometry(PyrScene* scene, float* tri_positions, float* tri_normals, float* tri_frames, float* spheres) {

@@ -1,15 +1,18 @@
-// pose_rules.h -- what a pose does to one vertex, one sphere and one lamp, how a skin blends a vertex's
-// matrix (section 9h), what a morphed normal does to its tangent frame (section 9p) and the face vector a recomputed normal
-// sums (section 9q), as functions of one record: the
-// pose kernels (kernels/pose.hip) and the host rehearsal (tests/probes/pose_check.cpp) both compile these, so what they compute
-// can differ only in the square root and the reciprocal -- sqrt32 / rcp32 of exact_math.h on the device, std::sqrt and 1.0f / x on
-// the host, bit-identical in the ranges exact_math.h names.
+// pose_rules.h -- the rules of a live scene's deformation pipeline, morph -> skin -> pose -> smooth -> lamps (DESIGN.md sections
+// 9g, 9h, 9p, 9q and 9r), stated once. Two layers: the arithmetic on one vector (pose_point, pose_normal_frame, blend_joints,
+// morph_normal_frame, signed_face_vector, ...) and, below it, what one lane of a kernel does with it over registers and plain
+// pointers ("one lane's walk": pose_vertex, skin_vertex, add_delta, morphed_normal, add_face, finish_corner, pose_sphere,
+// bounds_flag) -- which rule comes first, what an identity copies, which Flag bit a failure raises. The kernels
+// (kernels/pose.hip) keep the lane mapping, the loads and stores and the bounds checks on tables in memory, and call only the
+// second layer; the host rehearsal (tests/probes/deform_check.cpp) calls the same functions under ASan and UBSan, so what the two
+// compute can differ only in the square root and the reciprocal -- sqrt32 / rcp32 of exact_math.h on the device, std::sqrt and
+// 1.0f / x on the host, bit-identical in the ranges exact_math.h names.
 //
 // The rule is the reference's Shape::scale and Shape::transform (shapes/mod.rs:290-344) with Normal::transform (shapes/mod.rs:
 // 572-583), in f32 and in the operation order of compiler.py's _transform_point, _transform_vector, _quat_rotate, _normalize and
 // _quat_from_cols. Units that include this header are built with -ffp-contract=off. A pose's last row is 0,0,0,1 (pyr_scene_pose
 // refuses any other), so transform_point's division by w is a division by exactly 1 and is left out. It is compiled for the
-// device too: no standard container in here.
+// device and by a plain C++ compiler: no vector type and no standard container in here.
 #pragma once
 #include <cstdint>
 
@@ -35,6 +38,14 @@ struct Pose {
     float m[16];
     float scale;
     uint32_t identity;
+};
+
+// The bits of the one flag word the kernels raise and pyr_scene_pose / _skin / _morph read back; the lowest bit set decides the
+// refusal (live_scene.cpp scene_pose).
+enum Flag : uint32_t {
+    kBeyondRange = 1u,   // a bound of a moved primitive fails the coordinate check, or a table names what lies outside it
+    kMorphedNormal = 2u, // a morphed normal or the tangent rebuilt against it cannot be normalised
+    kSmoothedNormal = 4u // a recomputed normal or the tangent rebuilt against it cannot be
 };
 
 PYR_POSE_HD float root(float x) {
@@ -112,7 +123,7 @@ PYR_POSE_HD void quat_from_cols(const float* c0, const float* c1, const float* c
     }
 }
 
-// ---- the per-vertex rule
+// ---- the per-vertex arithmetic
 // Shape::scale, then Shape::transform, on a vertex position
 PYR_POSE_HD void pose_point(const Pose& pose, float* p) {
     const float s[3] = {p[0] * pose.scale, p[1] * pose.scale, p[2] * pose.scale};
@@ -160,7 +171,7 @@ PYR_POSE_HD void blend_joints(const float* joints, const uint32_t* j, const floa
 // ascending t, and leaves as normalize(m)). `frame` nullptr: the scene keeps none; otherwise the old tangent frame is
 // Gram-Schmidt'ed against the new normal, x first, which keeps it orthonormal and its handedness. Returns whether a squared
 // length that is normalised lies outside [1e-30, 1e30] -- the range in which sqrt32 and rcp32 are the host's bits (exact_math.h);
-// the caller raises bit 1 of the flag word then, and what is written is not used.
+// the caller raises its Flag bit then, and what is written is not used.
 PYR_POSE_HD bool morph_normal_frame(float* n, float* frame) {
     const auto outside = [](float s) { return !(s >= 1.0e-30f && s <= 1.0e30f); };
     bool bad = outside((n[0] * n[0] + n[1] * n[1]) + n[2] * n[2]);
@@ -189,7 +200,7 @@ PYR_POSE_HD bool morph_normal_frame(float* n, float* frame) {
 // face_negated decides that once, from the rest pose (d of zero or NaN does not negate). The caller sums a group's face vectors
 // in ascending corner order, starting from the first one (not from zero: 0 + (-0) loses a sign bit), and hands the sum to
 // morph_normal_frame above, which normalises it, rebuilds the corner's tangent frame against it and range-checks what it
-// normalises (bit 2 of the flag word here).
+// normalises (kSmoothedNormal here).
 PYR_POSE_HD void face_vector(const float* p, float* c) {
     const float a[3] = {p[3] - p[0], p[4] - p[1], p[5] - p[2]}, b[3] = {p[6] - p[0], p[7] - p[1], p[8] - p[2]};
     cross(a, b, c);
@@ -206,10 +217,70 @@ PYR_POSE_HD void signed_face_vector(const float* p, bool negated, float* c) {
     if (negated) c[0] = -c[0], c[1] = -c[1], c[2] = -c[2];
 }
 
-// ---- the per-sphere rule: radius *= scale; centre *= scale; centre = transform_point(centre)
+// ---- one lane's walk: what the kernels' lanes and the host rehearsal both call
+// One vertex under one pose: an identity pose copies bits; the normal takes its frame along where the scene keeps frames.
+PYR_POSE_HD void pose_vertex(const Pose& pose, float* p, float* n, float* frame, bool has_frames) {
+    if (pose.identity) return;
+    pose_point(pose, p);
+    if (has_frames)
+        pose_normal_frame(pose, n, frame);
+    else
+        pose_normal(pose, n);
+}
+// One skinned vertex: the skin first (a skin at rest copies), then the object's pose. `joints`: the skin's rows of the joint
+// table; `j`: the four indices of the binding, relative to it. An index at or above the skin's count uses joint 0 and raises
+// kBeyondRange (pyr_scene_set_skins has refused such a binding). Returns the bits raised.
+PYR_POSE_HD uint32_t skin_vertex(const float* joints, uint32_t num_joints, bool skin_at_rest, const uint32_t* j, const float* w, const Pose& pose, float* p, float* n,
+                                 float* frame, bool has_frames) {
+    uint32_t raised = 0u;
+    if (!skin_at_rest) {
+        uint32_t inside[4];
+        for (int k = 0; k < 4; ++k) {
+            inside[k] = j[k];
+            if (inside[k] >= num_joints) inside[k] = 0u, raised = kBeyondRange;
+        }
+        Pose blended;
+        blend_joints(joints, inside, w, blended);
+        pose_vertex(blended, p, n, frame, has_frames);
+    }
+    pose_vertex(pose, p, n, frame, has_frames);
+    return raised;
+}
+// One active target's deltas added to `count` floats of a morphed triangle: x += w * d, unfused, the caller walking the active
+// targets in ascending order. A morph with no active target adds nothing and so copies rest.
+PYR_POSE_HD void add_delta(float* x, float w, const float* d, int count) {
+    for (int k = 0; k < count; ++k) x[k] = x[k] + w * d[k];
+}
+// Whether a morph moves its normals at all (otherwise normals and frames are copied from rest), and one morphed vertex's normal
+// finished once its deltas are in. Returns the bits raised.
+PYR_POSE_HD bool morph_moves_normals(uint32_t has_normals, uint32_t num_active) { return has_normals != 0u && num_active != 0u; }
+PYR_POSE_HD uint32_t morphed_normal(float* n, float* frame, bool has_frames) { return morph_normal_frame(n, has_frames ? frame : nullptr) ? kMorphedNormal : 0u; }
+// One face added to a group's sum, from the triangle's nine final positions: the sum starts from the first face vector (`any`
+// says whether there was one). And one corner finished from the sum: its normal and, where the scene keeps frames, its frame
+// rebuilt against it. Returns the bits raised.
+PYR_POSE_HD void add_face(const float* p, bool negated, float* sum, bool& any) {
+    float f[3];
+    signed_face_vector(p, negated, f);
+    if (any)
+        sum[0] = sum[0] + f[0], sum[1] = sum[1] + f[1], sum[2] = sum[2] + f[2];
+    else
+        sum[0] = f[0], sum[1] = f[1], sum[2] = f[2], any = true;
+}
+PYR_POSE_HD uint32_t finish_corner(const float* sum, float* n, float* frame, bool has_frames) {
+    n[0] = sum[0], n[1] = sum[1], n[2] = sum[2];
+    return morph_normal_frame(n, has_frames ? frame : nullptr) ? kSmoothedNormal : 0u;
+}
+// One sphere under one pose: radius *= scale; centre *= scale; centre = transform_point(centre)
 PYR_POSE_HD void pose_sphere(const Pose& pose, float* s) {
+    if (pose.identity) return;
     s[3] = s[3] * pose.scale;
     pose_point(pose, s);
+}
+// creation's coordinate check on a moved primitive's box (bvh_level.h triangle_bounds / sphere_bounds). Returns the bits raised.
+PYR_POSE_HD uint32_t bounds_flag(const float* lo, const float* hi) {
+    bool bad = false;
+    for (int a = 0; a < 3; ++a) bad = bad || beyond_range(lo[a]) || beyond_range(hi[a]);
+    return bad ? kBeyondRange : 0u;
 }
 
 // ---- the lamp rule: what a shape lamp's record takes from its shape, with pack_lamp's arithmetic (api.cpp)

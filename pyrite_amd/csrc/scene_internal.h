@@ -105,31 +105,70 @@ struct LiveGeometry {
     struct Skin {
         uint32_t object, num_joints, first_joint, lane;
     };
-    std::vector<Skin> skins;
-    std::vector<float> skin_joints;
-    uint32_t skinned_triangles = 0;
-    DeviceBuffer skin_table, skin_weights, skin_indices, joint_table; // DevSkin records, the two binding arrays, twelve floats a joint
+    struct Skins {
+        std::vector<Skin> table;
+        std::vector<float> joints;
+        uint32_t triangles = 0;                         // lanes of the skin kernel
+        DeviceBuffer records, weights, indices, rows;   // DevSkin records, the two binding arrays, twelve floats a joint
+        bool set() const { return !table.empty(); }
+        void clear() {
+            table.clear(), joints.clear();
+            triangles = 0;
+            for (DeviceBuffer* b : {&records, &weights, &indices, &rows}) b->release();
+        }
+        void swap(Skins& o) {
+            table.swap(o.table), joints.swap(o.joints), std::swap(triangles, o.triangles);
+            records.swap(o.records), weights.swap(o.weights), indices.swap(o.indices), rows.swap(o.rows);
+        }
+    } skin;
     // the morphs in morph order (pyr_scene_set_morphs): whose triangles, how many targets, where its weights begin in the weight
     // table, its lanes in the morph kernel's launch and its targets in the two delta buffers (rows of nine floats); and the weights
-    // the scene is in, the morphs' targets one after the other (zero when the morphs are set). `morphed_rest`: positions, normals
-    // and frames after the morph, which the pose and skin kernels read as their rest pose while morphs are set.
+    // the scene is in, the morphs' targets one after the other (zero when the morphs are set). `rest`: positions, normals and
+    // frames after the morph, which the pose and skin kernels read as their rest pose while morphs are set.
     struct Morph {
         uint32_t object, num_targets, first_weight, lane;
         uint64_t position_row, normal_row;
         bool has_normals;
     };
-    std::vector<Morph> morphs;
-    std::vector<float> morph_weights;
-    uint32_t morphed_triangles = 0;
-    uint64_t morph_position_rows = 0, morph_normal_rows = 0;
-    DeviceBuffer morph_table, morph_active, morph_positions, morph_normals; // DevMorph records, a frame's pairs, the deltas as uploaded
-    DeviceBuffer morphed_rest[3];
+    struct Morphs {
+        std::vector<Morph> table;
+        std::vector<float> weights;
+        uint32_t triangles = 0; // lanes of the morph kernel
+        uint64_t position_rows = 0, normal_rows = 0;
+        DeviceBuffer records, active, positions, normals; // DevMorph records, a frame's pairs, the deltas as uploaded
+        DeviceBuffer rest[3];
+        bool set() const { return !table.empty(); }
+        void clear() {
+            table.clear(), weights.clear();
+            triangles = 0;
+            position_rows = normal_rows = 0;
+            for (DeviceBuffer* b : {&records, &active, &positions, &normals, &rest[0], &rest[1], &rest[2]}) b->release();
+        }
+        void swap(Morphs& o) {
+            table.swap(o.table), weights.swap(o.weights), std::swap(triangles, o.triangles);
+            std::swap(position_rows, o.position_rows), std::swap(normal_rows, o.normal_rows);
+            records.swap(o.records), active.swap(o.active), positions.swap(o.positions), normals.swap(o.normals);
+            for (int k = 0; k < 3; ++k) rest[k].swap(o.rest[k]);
+        }
+    } morph;
     // the smoothing (pyr_scene_set_smoothing): which objects have their normals recomputed, and the groups of their corners as a
-    // CSR on the device -- smooth_begin [smooth_groups + 1], smooth_corners_table [smooth_corners], a corner being 3 * triangle +
-    // vertex over the scene's triangles with devpose::kNegated set where the triangle's face vector is negated
-    std::vector<uint32_t> smoothed_objects;
-    uint32_t smooth_groups = 0, smooth_corners = 0;
-    DeviceBuffer smooth_begin, smooth_corners_table;
+    // CSR on the device -- begin [groups + 1], corner_table [corners], a corner being 3 * triangle + vertex over the scene's
+    // triangles with devpose::kNegated set where the triangle's face vector is negated
+    struct Smooth {
+        std::vector<uint32_t> objects;
+        uint32_t groups = 0, corners = 0;
+        DeviceBuffer begin, corner_table;
+        bool set() const { return !objects.empty(); }
+        void clear() {
+            objects.clear();
+            groups = corners = 0;
+            begin.release(), corner_table.release();
+        }
+        void swap(Smooth& o) {
+            objects.swap(o.objects), std::swap(groups, o.groups), std::swap(corners, o.corners);
+            begin.swap(o.begin), corner_table.swap(o.corner_table);
+        }
+    } smooth;
     // the previous frame (pyr_scene_keep_previous): positions and spheres as they were when it was called, the description's order.
     // Nothing that moves the scene touches them -- counts and indices never change -- and only the motion pass reads them.
     DeviceBuffer previous_positions, previous_spheres;
@@ -143,6 +182,7 @@ struct LiveGeometry {
     void forget_skins();
     void forget_morphs();
     void forget_smoothing();
+    void recount_lanes(); // the pose kernels' lanes: every object's spheres, and the triangles no skin has taken
     bool host_current() const { return host_current_; }
     bool positions_staged() const { return positions_staged_; }
     bool schedule_current() const { return schedule_current_; }

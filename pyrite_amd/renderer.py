@@ -86,11 +86,11 @@ class World:
                 if self._smoothing:
                     self._set_smoothing(handle, self._smoothing)
                 if any(np.any(w != 0) for w in self._weights.values()):
-                    self._morph(handle, self._weights, self._joints if self._skins else None, self._poses, "rebuild", 0)
+                    self._send(handle, "morph", self._poses, self._joints if self._skins else None, self._weights, "rebuild", 0)
                 elif self._joints:
-                    self._skin(handle, self._joints, self._poses, "rebuild", 0)
+                    self._send(handle, "skin", self._poses, self._joints, None, "rebuild", 0)
                 elif self._poses or self._smooth_frame:  # (a smoothed object's normals are recomputed under the identity too)
-                    self._pose(handle, self._poses, "rebuild", 0)
+                    self._send(handle, "pose", self._poses, None, None, "rebuild", 0)
         elif build is not None and build != self._builders[key]:
             raise ValueError("the scene on device %r was created with build=%r" % (device, self._builders[key]))
         return self._scenes[key]
@@ -131,10 +131,13 @@ class World:
         objects = [dict(o) for o in (self.flat.objects if objects is None else objects)]
         for handle in self._scenes.values():
             self._set_objects(handle, objects)
-        self._objects, self._poses = objects, {}
-        self._skins, self._joints = {}, {}  # skins hang on objects: pyr_scene_set_objects forgot them
-        self._morphs, self._weights = {}, {}  # and so do morphs
-        self._smoothing, self._smooth_frame = {}, False  # and the smoothing
+        self._objects = objects
+        self._forget()  # skins, morphs and the smoothing hang on objects: pyr_scene_set_objects forgot them
+
+    def _forget(self):
+        """Every pose is the identity again, and what hangs on objects is gone."""
+        self._poses, self._skins, self._joints, self._morphs, self._weights = {}, {}, {}, {}, {}
+        self._smoothing, self._smooth_frame = {}, False
 
     def _follow(self, arrays):
         for name, attr in (("positions", "tri_positions"), ("normals", "tri_normals"), ("frames", "tri_frames"), ("spheres", "spheres")):
@@ -156,10 +159,49 @@ class World:
             records[k].scale = float(scale)
         return records
 
-    def _pose(self, handle, poses, mode, stream):
-        records = self._pose_records(poses)
-        u = abi.PyrPoseUpdate(mode=self.UPDATE_MODES[mode], num_objects=len(self._objects), poses=records)
-        check(lib().pyr_scene_pose(handle, C.byref(u), C.c_void_p(int(stream))))
+    def _send(self, handle, entry, poses, tables, weights, mode, stream):
+        """pyr_scene_<entry> on one scene with the widest update that entry has: the poses; for "skin" and "morph" the joint table
+        (`tables` None: the scene keeps its joints); for "morph" the weight table."""
+        common = dict(mode=self.UPDATE_MODES[mode], num_objects=len(self._objects), poses=self._pose_records(poses))
+        u = {"pose": abi.PyrPoseUpdate, "skin": abi.PyrSkinUpdate, "morph": abi.PyrMorphUpdate}[entry](**common)
+        if tables is not None:
+            joints = [tables[index] if index in tables else np.tile(self.IDENTITY, (self._skins[index]["num_joints"], 1)) for index in sorted(self._skins)]
+            joints = np.ascontiguousarray(np.concatenate(joints) if joints else np.zeros((0, 16)), dtype=np.float32)
+            u.joints, u.num_joints = joints.ctypes.data, len(joints)
+        if entry == "morph":
+            rows = [weights[index] if index in weights else np.zeros(len(self._morphs[index]["positions"]), dtype=np.float32) for index in sorted(self._morphs)]
+            table = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros(0), dtype=np.float32)
+            u.weights, u.num_weights = table.ctypes.data, len(table)
+        check(getattr(lib(), "pyr_scene_" + entry)(handle, C.byref(u), C.c_void_p(int(stream))))
+
+    def _frame(self, entry, poses, joints, weights, mode, device, stream):
+        """One frame through pyr_scene_<entry>: checks what was given, merges it with what the world is in (None keeps), sends it to
+        the scene on `device` and remembers the result for scenes created later."""
+        if mode not in self.UPDATE_MODES:
+            raise ValueError("mode must be 'refit' or 'rebuild', not %r" % (mode,))
+        for k in ({} if poses is None else poses):
+            if not 0 <= int(k) < len(self._objects):
+                raise ValueError("no object %r: the world has %d" % (k, len(self._objects)))
+        merged = dict(self._weights)
+        if entry == "morph":
+            for index, w in weights.items():
+                if int(index) not in self._morphs:
+                    raise ValueError("no morph on object %r" % (index,))
+                w = np.ascontiguousarray(w, dtype=np.float32)
+                if w.shape != (len(self._morphs[int(index)]["positions"]),):
+                    raise ValueError("the morph of object %r has %d targets, not %r weights" % (index, len(self._morphs[int(index)]["positions"]), w.shape))
+                merged[int(index)] = w
+            if not self._morphs:
+                raise ValueError("the world has no morphs (set_morphs gives them)")
+            if joints is not None and not self._skins:
+                raise ValueError("joints are given, and the world has no skins")
+        tables = None if joints is None else self._joint_tables(joints)
+        named = self._poses if poses is None else {int(k): (None if v[0] is None else np.array(v[0], dtype=np.float32), float(v[1])) for k, v in poses.items()}
+        self._send(self.scene(device), entry, named, tables, merged, mode, stream)
+        self._poses, self._weights = named, merged
+        if tables is not None:
+            self._joints = tables
+        self._smooth_frame = bool(self._smoothing)
 
     def pose(self, poses, mode="refit", device=0, stream=0):
         """Poses the objects of the scene on `device` (pyr_scene_pose): `poses` maps an object's index in `World.objects` to
@@ -167,15 +209,7 @@ class World:
         for no transform; the uniform scale comes first. Objects it does not name keep the identity: every pose is from the
         rest pose, never from the previous one. The primitives are computed on the GPU; mode as for `update`. `World.flat`
         stays the rest pose, and the world remembers the poses for scenes it creates later."""
-        if mode not in self.UPDATE_MODES:
-            raise ValueError("mode must be 'refit' or 'rebuild', not %r" % (mode,))
-        for k in poses:
-            if not 0 <= int(k) < len(self._objects):
-                raise ValueError("no object %r: the world has %d" % (k, len(self._objects)))
-        named = {int(k): (None if v[0] is None else np.array(v[0], dtype=np.float32), float(v[1])) for k, v in poses.items()}
-        self._pose(self.scene(device), named, mode, stream)
-        self._poses = named
-        self._smooth_frame = bool(self._smoothing)
+        self._frame("pose", poses, None, None, mode, device, stream)
 
     def keep_previous(self, keep=True, device=0):
         """Keeps the geometry of the scene on `device` as it is now as the previous frame's (pyr_scene_keep_previous): the
@@ -226,29 +260,13 @@ class World:
             tables[int(index)] = t
         return tables
 
-    def _skin(self, handle, tables, poses, mode, stream):
-        rows = [tables[index] if index in tables else np.tile(self.IDENTITY, (self._skins[index]["num_joints"], 1)) for index in sorted(self._skins)]
-        table = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros((0, 16)), dtype=np.float32)
-        records = self._pose_records(poses)
-        u = abi.PyrSkinUpdate(mode=self.UPDATE_MODES[mode], num_objects=len(self._objects), poses=records, joints=table.ctypes.data, num_joints=len(table))
-        check(lib().pyr_scene_skin(handle, C.byref(u), C.c_void_p(int(stream))))
-
     def skin(self, joints, poses=None, mode="refit", device=0, stream=0):
         """One frame of the skinned meshes of the scene on `device` (pyr_scene_skin): `joints` maps a skinned object's index to its
         joint matrices, [J,4,4] as written on paper or [J,16] column-major; a skin it does not name is at the identity. Every
         vertex takes the matrix blended from its four joints by its weights, then the object's pose: `poses` as for `pose`, None
         keeps the poses the world is in. Everything is computed from the rest pose on the GPU; mode as for `update`. `World.flat`
         stays the rest pose, and the world remembers joints and poses for scenes it creates later."""
-        if mode not in self.UPDATE_MODES:
-            raise ValueError("mode must be 'refit' or 'rebuild', not %r" % (mode,))
-        for k in ({} if poses is None else poses):
-            if not 0 <= int(k) < len(self._objects):
-                raise ValueError("no object %r: the world has %d" % (k, len(self._objects)))
-        tables = self._joint_tables(joints)
-        named = self._poses if poses is None else {int(k): (None if v[0] is None else np.array(v[0], dtype=np.float32), float(v[1])) for k, v in poses.items()}
-        self._skin(self.scene(device), tables, named, mode, stream)
-        self._poses, self._joints = named, tables
-        self._smooth_frame = bool(self._smoothing)
+        self._frame("skin", poses, joints, None, mode, device, stream)
 
     def _set_morphs(self, handle, morphs):
         order = sorted(morphs)
@@ -280,16 +298,6 @@ class World:
             self._set_morphs(handle, held)
         self._morphs, self._weights = held, {}
 
-    def _morph(self, handle, weights, tables, poses, mode, stream):
-        rows = [weights[index] if index in weights else np.zeros(len(self._morphs[index]["positions"]), dtype=np.float32) for index in sorted(self._morphs)]
-        table = np.ascontiguousarray(np.concatenate(rows) if rows else np.zeros(0), dtype=np.float32)
-        u = abi.PyrMorphUpdate(mode=self.UPDATE_MODES[mode], num_objects=len(self._objects), poses=self._pose_records(poses), weights=table.ctypes.data, num_weights=len(table))
-        if tables is not None:
-            joints = [tables[index] if index in tables else np.tile(self.IDENTITY, (self._skins[index]["num_joints"], 1)) for index in sorted(self._skins)]
-            joints = np.ascontiguousarray(np.concatenate(joints) if joints else np.zeros((0, 16)), dtype=np.float32)
-            u.joints, u.num_joints = joints.ctypes.data, len(joints)
-        check(lib().pyr_scene_morph(handle, C.byref(u), C.c_void_p(int(stream))))
-
     def morph(self, weights, joints=None, poses=None, mode="refit", device=0, stream=0):
         """One frame of the morphed meshes of the scene on `device` (pyr_scene_morph): `weights` maps a morphed object's index to
         one weight per target, [T]; a morph it does not name stays at the weights it is in. Every vertex takes the weighted deltas
@@ -297,30 +305,7 @@ class World:
         joints the world is in -- then the object's pose: `poses` as for `pose`, None keeps the poses. Everything is computed from
         the rest pose on the GPU; mode as for `update`. `World.flat` stays the rest pose, and the world remembers weights, joints
         and poses for scenes it creates later."""
-        if mode not in self.UPDATE_MODES:
-            raise ValueError("mode must be 'refit' or 'rebuild', not %r" % (mode,))
-        for k in ({} if poses is None else poses):
-            if not 0 <= int(k) < len(self._objects):
-                raise ValueError("no object %r: the world has %d" % (k, len(self._objects)))
-        merged = dict(self._weights)
-        for index, w in weights.items():
-            if int(index) not in self._morphs:
-                raise ValueError("no morph on object %r" % (index,))
-            w = np.ascontiguousarray(w, dtype=np.float32)
-            if w.shape != (len(self._morphs[int(index)]["positions"]),):
-                raise ValueError("the morph of object %r has %d targets, not %r weights" % (index, len(self._morphs[int(index)]["positions"]), w.shape))
-            merged[int(index)] = w
-        if not self._morphs:
-            raise ValueError("the world has no morphs (set_morphs gives them)")
-        if joints is not None and not self._skins:
-            raise ValueError("joints are given, and the world has no skins")
-        tables = None if joints is None else self._joint_tables(joints)
-        named = self._poses if poses is None else {int(k): (None if v[0] is None else np.array(v[0], dtype=np.float32), float(v[1])) for k, v in poses.items()}
-        self._morph(self.scene(device), merged, tables, named, mode, stream)
-        self._weights, self._poses = merged, named
-        self._smooth_frame = bool(self._smoothing)
-        if tables is not None:
-            self._joints = tables
+        self._frame("morph", poses, joints, weights, mode, device, stream)
 
     def _set_smoothing(self, handle, smoothing):
         order = sorted(smoothing)
@@ -420,10 +405,7 @@ class World:
             check(lib().pyr_scene_update(self.scene(device), C.byref(u)))
         del keep
         if u.tri_positions or u.tri_normals or u.tri_frames or u.spheres:
-            self._poses = {}  # new arrays are a new geometry, not a pose of the old one: the scene forgot its objects (set_objects names them again)
-            self._skins, self._joints = {}, {}
-            self._morphs, self._weights = {}, {}
-            self._smoothing, self._smooth_frame = {}, False
+            self._forget()  # new arrays are a new geometry, not a pose of the old one: the scene forgot its objects (set_objects names them again)
         for name, attr in (("positions", "tri_positions"), ("normals", "tri_normals"), ("frames", "tri_frames"), ("spheres", "spheres")):
             if name in host:
                 setattr(self.flat, attr, [host[name].copy()])

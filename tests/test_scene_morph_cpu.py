@@ -1,6 +1,6 @@
 """pyr_scene_set_morphs / pyr_scene_morph without a GPU: the two new structs of the ABI, the argument checks
 that need no scene, the world's bookkeeping, what the cases are, and the host rehearsal of the morph kernel -- pose_rules.h, the
-header kernels/pose.hip compiles, through tests/probes/morph_check.cpp, a program of its own built with
+header kernels/pose.hip compiles, through tests/probes/deform_check.cpp, a program of its own built with
 -fsanitize=address,undefined and run as a child process -- compared as bits with the numpy restatement
 (tests/morph_restatement.py)."""
 import ctypes as C
@@ -16,6 +16,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import bvh_build_inputs as inputs  # noqa: E402
+import deform_probe  # noqa: E402
 import morph_cases  # noqa: E402
 import morph_restatement as restatement  # noqa: E402
 import pose_cases as cases  # noqa: E402
@@ -142,60 +143,13 @@ def test_the_targets_of_the_cases_are_what_the_tests_take_them_for():
 
 
 # ---------------------------------------------------------------------------------------------------------------- (d) the rehearsal
-def write_input(path, rest, ranges, poses, lamps, skins, joints, morphs, weights):
-    nt, ns = len(rest["positions"]), len(rest["spheres"])
-    with open(path, "wb") as f:
-        f.write(np.array([nt, ns, 0 if rest["frames"] is None else 1, len(ranges), len(lamps), len(skins), len(morphs)], dtype=np.uint32).tobytes())
-        for key in KEYS:
-            if rest[key] is not None:
-                f.write(np.ascontiguousarray(rest[key], dtype=np.float32).tobytes())
-        for k, r in enumerate(ranges):
-            matrix, scale = poses.get(k, (None, 1.0))
-            f.write(np.array([r["first_triangle"], r["num_triangles"], r["first_sphere"], r["num_spheres"]], dtype=np.uint32).tobytes())
-            f.write(pose_restatement.column_major(matrix).tobytes())
-            f.write(np.float32(scale).tobytes())
-        f.write(np.array(lamps, dtype=np.uint32).reshape(-1, 2).tobytes())
-        for index in sorted(skins):
-            skin = skins[index]
-            f.write(np.array([index, skin["num_joints"]], dtype=np.uint32).tobytes())
-            f.write(skin_restatement.joint_table(joints.get(index), skin["num_joints"]).tobytes())
-            f.write(np.ascontiguousarray(skin["weights"], dtype=np.float32).tobytes())
-            f.write(np.ascontiguousarray(skin["joints"], dtype=np.uint16).tobytes())
-        for index in sorted(morphs):
-            morph = morphs[index]
-            f.write(np.array([index, len(morph["positions"]), 0 if morph["normals"] is None else 1], dtype=np.uint32).tobytes())
-            f.write(restatement.weights_of(weights, index, len(morph["positions"])).tobytes())
-            f.write(np.ascontiguousarray(morph["positions"], dtype=np.float32).tobytes())
-            if morph["normals"] is not None:
-                f.write(np.ascontiguousarray(morph["normals"], dtype=np.float32).tobytes())
-
-
-def read_output(path, rest, num_lamps):
-    data = np.fromfile(path, dtype=np.float32)
-    out, at = {}, 0
-    for key in KEYS:
-        if rest[key] is None:
-            out[key] = None
-            continue
-        out[key] = data[at:at + rest[key].size].reshape(rest[key].shape)
-        at += rest[key].size
-    out["lamps"] = data[at:at + 23 * num_lamps].reshape(num_lamps, 23)
-    at += 23 * num_lamps
-    assert at + 1 == len(data)
-    out["flag"] = int(data[at:].view(np.uint32)[0])
-    return out
-
-
 def bits(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 @pytest.fixture(scope="module")
 def morph_check(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("morph_check") / "morph_check"
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-static-libasan", "-static-libubsan", "-o", str(exe), os.path.join(ROOT, "tests", "probes", "morph_check.cpp")])
-    return str(exe)
+    return deform_probe.build(tmp_path_factory.mktemp("deform_check"))
 
 
 @pytest.fixture(scope="module")
@@ -219,11 +173,7 @@ def rehearsal_inputs():
 
 
 def rehearse(morph_check, tmp_path, name, rest, ranges, poses, lamps, skins, joints, morphs, weights):
-    source, result = str(tmp_path / (name + ".in")), str(tmp_path / (name + ".out"))
-    write_input(source, rest, ranges, poses, lamps, skins, joints, morphs, weights)
-    run = subprocess.run([morph_check, source, result], capture_output=True, text=True, timeout=120)
-    assert run.returncode == 0, run.stdout + run.stderr
-    return read_output(result, rest, len(lamps))
+    return deform_probe.rehearse(morph_check, tmp_path, name, rest, ranges, lamps, poses=poses, skins=skins, joints=joints, morphs=morphs, weights=weights)
 
 
 def targets_of(rest, ranges, morphed, with_normals=True):

@@ -1,6 +1,6 @@
 """pyr_scene_pose without a GPU: the three new structs of the ABI, the argument checks that need no scene,
 the objects the description records, and the host rehearsal of the pose kernels -- pose_rules.h, the header kernels/pose.hip
-compiles, through tests/probes/pose_check.cpp, a program of its own built with -fsanitize=address,undefined and run as a child
+compiles, through tests/probes/deform_check.cpp, a program of its own built with -fsanitize=address,undefined and run as a child
 process -- compared as bits with the numpy restatement (tests/pose_restatement.py)."""
 import ctypes as C
 import os
@@ -15,6 +15,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import bvh_build_inputs as inputs  # noqa: E402
+import deform_probe  # noqa: E402
 import pose_cases as cases  # noqa: E402
 import pose_restatement as restatement  # noqa: E402
 
@@ -107,47 +108,13 @@ def test_the_cpp_front_end_records_the_same_objects(tmp_path):
 
 
 # ---------------------------------------------------------------------------------------------------------------- the rehearsal
-def write_input(path, rest, ranges, poses, lamps):
-    nt, ns = len(rest["positions"]), len(rest["spheres"])
-    with open(path, "wb") as f:
-        f.write(np.array([nt, ns, 0 if rest["frames"] is None else 1, len(ranges), len(lamps)], dtype=np.uint32).tobytes())
-        for key in ("positions", "normals", "frames", "spheres"):
-            if rest[key] is not None:
-                f.write(np.ascontiguousarray(rest[key], dtype=np.float32).tobytes())
-        for k, r in enumerate(ranges):
-            matrix, scale = poses.get(k, (None, 1.0))
-            f.write(np.array([r["first_triangle"], r["num_triangles"], r["first_sphere"], r["num_spheres"]], dtype=np.uint32).tobytes())
-            f.write(restatement.column_major(matrix).tobytes())
-            f.write(np.float32(scale).tobytes())
-        f.write(np.array(lamps, dtype=np.uint32).reshape(-1, 2).tobytes())
-
-
-def read_output(path, rest, num_lamps):
-    data = np.fromfile(path, dtype=np.float32)
-    out, at = {}, 0
-    for key in ("positions", "normals", "frames", "spheres"):
-        if rest[key] is None:
-            out[key] = None
-            continue
-        out[key] = data[at:at + rest[key].size].reshape(rest[key].shape)
-        at += rest[key].size
-    out["lamps"] = data[at:at + 23 * num_lamps].reshape(num_lamps, 23)
-    at += 23 * num_lamps
-    assert at + 1 == len(data)
-    out["beyond_range"] = int(data[at:].view(np.uint32)[0])
-    return out
-
-
 def bits(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 @pytest.fixture(scope="module")
 def pose_check(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("pose_check") / "pose_check"
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-static-libasan", "-static-libubsan", "-o", str(exe), os.path.join(ROOT, "tests", "probes", "pose_check.cpp")])
-    return str(exe)
+    return deform_probe.build(tmp_path_factory.mktemp("deform_check"))
 
 
 def rehearsal_inputs():
@@ -173,11 +140,7 @@ def test_the_host_rehearsal_of_the_pose_kernels_under_sanitizers(pose_check, tmp
     records' vertices, normals, centres and radii are the posed arrays' and their areas pack_lamp's formula restated in numpy."""
     for name, (rest, ranges, lamps) in rehearsal_inputs().items():
         poses = cases.poses_for(pose, len(ranges))
-        source, result = str(tmp_path / (name + ".in")), str(tmp_path / (name + ".out"))
-        write_input(source, rest, ranges, poses, lamps)
-        run = subprocess.run([pose_check, source, result], capture_output=True, text=True, timeout=120)
-        assert run.returncode == 0, run.stdout + run.stderr
-        got = read_output(result, rest, len(lamps))
+        got = deform_probe.rehearse(pose_check, tmp_path, name, rest, ranges, lamps, poses=poses)
         want = restatement.pose_arrays(rest, ranges, poses)
         for key in ("positions", "normals", "frames", "spheres"):
             if rest[key] is None:
@@ -189,7 +152,7 @@ def test_the_host_rehearsal_of_the_pose_kernels_under_sanitizers(pose_check, tmp
         else:
             moved = [key for key in ("positions", "spheres") if rest[key] is not None and rest[key].size and not np.array_equal(bits(got[key]), bits(rest[key]))]
             assert moved, (name, pose)
-        assert got["beyond_range"] == 0
+        assert got["flag"] == 0
         areas = restatement.lamp_areas(want, lamps)
         for k, (kind, index) in enumerate(lamps):
             record = got["lamps"][k]
@@ -204,8 +167,4 @@ def test_the_rehearsal_raises_the_flag_beyond_the_coordinate_range(pose_check, t
     rest, ranges, lamps = rehearsal_inputs()["three_spheres"]
     far = np.eye(4, dtype=np.float32)
     far[0, 3] = 1e16
-    source, result = str(tmp_path / "far.in"), str(tmp_path / "far.out")
-    write_input(source, rest, ranges, {1: (far, 1.0)}, lamps)
-    run = subprocess.run([pose_check, source, result], capture_output=True, text=True, timeout=120)
-    assert run.returncode == 0, run.stdout + run.stderr
-    assert read_output(result, rest, len(lamps))["beyond_range"] == 1
+    assert deform_probe.rehearse(pose_check, tmp_path, "far", rest, ranges, lamps, poses={1: (far, 1.0)})["flag"] == 1

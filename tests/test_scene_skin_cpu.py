@@ -1,6 +1,6 @@
 """pyr_scene_set_skins / pyr_scene_skin without a GPU: the two new structs of the ABI, the argument checks that
 need no scene, the world's bookkeeping, and the host rehearsal of the skin kernel -- pose_rules.h, the header kernels/pose.hip
-compiles, through tests/probes/skin_check.cpp, a program of its own built with -fsanitize=address,undefined and run as a child
+compiles, through tests/probes/deform_check.cpp, a program of its own built with -fsanitize=address,undefined and run as a child
 process -- compared as bits with the numpy restatement (tests/skin_restatement.py)."""
 import ctypes as C
 import os
@@ -15,6 +15,7 @@ import pytest
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import bvh_build_inputs as inputs  # noqa: E402
+import deform_probe  # noqa: E402
 import pose_cases as cases  # noqa: E402
 import pose_restatement  # noqa: E402
 import skin_cases  # noqa: E402
@@ -113,53 +114,13 @@ def test_the_bindings_of_the_cases_are_what_the_tests_take_them_for():
 
 
 # ---------------------------------------------------------------------------------------------------------------- (c) the rehearsal
-def write_input(path, rest, ranges, poses, lamps, skins, joints):
-    nt, ns = len(rest["positions"]), len(rest["spheres"])
-    with open(path, "wb") as f:
-        f.write(np.array([nt, ns, 0 if rest["frames"] is None else 1, len(ranges), len(lamps), len(skins)], dtype=np.uint32).tobytes())
-        for key in KEYS:
-            if rest[key] is not None:
-                f.write(np.ascontiguousarray(rest[key], dtype=np.float32).tobytes())
-        for k, r in enumerate(ranges):
-            matrix, scale = poses.get(k, (None, 1.0))
-            f.write(np.array([r["first_triangle"], r["num_triangles"], r["first_sphere"], r["num_spheres"]], dtype=np.uint32).tobytes())
-            f.write(pose_restatement.column_major(matrix).tobytes())
-            f.write(np.float32(scale).tobytes())
-        f.write(np.array(lamps, dtype=np.uint32).reshape(-1, 2).tobytes())
-        for index in sorted(skins):
-            skin = skins[index]
-            f.write(np.array([index, skin["num_joints"]], dtype=np.uint32).tobytes())
-            f.write(restatement.joint_table(joints.get(index), skin["num_joints"]).tobytes())
-            f.write(np.ascontiguousarray(skin["weights"], dtype=np.float32).tobytes())
-            f.write(np.ascontiguousarray(skin["joints"], dtype=np.uint16).tobytes())
-
-
-def read_output(path, rest, num_lamps):
-    data = np.fromfile(path, dtype=np.float32)
-    out, at = {}, 0
-    for key in KEYS:
-        if rest[key] is None:
-            out[key] = None
-            continue
-        out[key] = data[at:at + rest[key].size].reshape(rest[key].shape)
-        at += rest[key].size
-    out["lamps"] = data[at:at + 23 * num_lamps].reshape(num_lamps, 23)
-    at += 23 * num_lamps
-    assert at + 1 == len(data)
-    out["beyond_range"] = int(data[at:].view(np.uint32)[0])
-    return out
-
-
 def bits(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 @pytest.fixture(scope="module")
 def skin_check(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("skin_check") / "skin_check"
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-static-libasan", "-static-libubsan", "-o", str(exe), os.path.join(ROOT, "tests", "probes", "skin_check.cpp")])
-    return str(exe)
+    return deform_probe.build(tmp_path_factory.mktemp("deform_check"))
 
 
 @pytest.fixture(scope="module")
@@ -182,11 +143,7 @@ def rehearsal_inputs():
 
 
 def rehearse(skin_check, tmp_path, name, rest, ranges, poses, lamps, skins, joints):
-    source, result = str(tmp_path / (name + ".in")), str(tmp_path / (name + ".out"))
-    write_input(source, rest, ranges, poses, lamps, skins, joints)
-    run = subprocess.run([skin_check, source, result], capture_output=True, text=True, timeout=120)
-    assert run.returncode == 0, run.stdout + run.stderr
-    return read_output(result, rest, len(lamps))
+    return deform_probe.rehearse(skin_check, tmp_path, name, rest, ranges, lamps, poses=poses, skins=skins, joints=joints)
 
 
 @pytest.mark.parametrize("pose", ["identity", "rotated_and_translated"])
@@ -206,7 +163,7 @@ def test_the_host_rehearsal_of_the_skin_kernel_under_sanitizers(skin_check, rehe
             assert np.array_equal(bits(got[key]), bits(want[key])), (name, binding, pose, key, int((bits(got[key]) != bits(want[key])).sum()))
             assert np.isfinite(got[key]).all()
         assert not np.array_equal(bits(got["positions"]), bits(rest["positions"])), (name, binding)
-        assert got["beyond_range"] == 0
+        assert got["flag"] == 0
         if binding == "one_hot" and pose == "identity":  # B is J[0] exactly: the rigid pose by J[0]
             rigid = pose_restatement.pose_arrays(rest, ranges, {index: (skin_cases.THREE[0], 1.0)})
             assert all(np.array_equal(bits(got[key]), bits(rigid[key])) for key in KEYS if rest[key] is not None), name
@@ -225,7 +182,7 @@ def test_the_identity_table_gives_rest_bit_for_bit(skin_check, rehearsal_inputs,
         skins = {index: skin_cases.binding("bend", rest, ranges[index])}
         got = rehearse(skin_check, tmp_path, name, rest, ranges, {}, lamps, skins, {})
         assert all(np.array_equal(bits(got[key]), bits(rest[key])) for key in KEYS if rest[key] is not None), name
-        assert got["beyond_range"] == 0
+        assert got["flag"] == 0
 
 
 def test_the_rehearsal_raises_the_flag_beyond_the_coordinate_range(skin_check, rehearsal_inputs, tmp_path):
@@ -234,4 +191,29 @@ def test_the_rehearsal_raises_the_flag_beyond_the_coordinate_range(skin_check, r
     far = skin_cases.THREE.copy()
     far[1, 0, 3] = 1e16  # joint 1 translated out of the coordinate range
     got = rehearse(skin_check, tmp_path, "far", rest, ranges, {}, lamps, skins, {index: far})
-    assert got["beyond_range"] == 1
+    assert got["flag"] == 1
+
+
+def test_a_joint_index_at_the_skins_count_uses_joint_0_and_raises_bit_0(skin_check, rehearsal_inputs, tmp_path):
+    """The guard the skin kernel and the rehearsal share (pose_rules.h skin_vertex): a binding pyr_scene_set_skins would have refused.
+    One index equal to num_joints: the rehearsal ends clean under the sanitizers, bit 0 is set, and that vertex has the bits the
+    restatement gives with the index replaced by 0; every other word is the unbroken binding's."""
+    rest, ranges, lamps, index = rehearsal_inputs["knot"]
+    good = skin_cases.binding("bend", rest, ranges[index])
+    slot = 1  # (bend names joints 0, 1, 2, 0): the first vertex on which joint 1 weighs anything
+    triangle, vertex = (int(x) for x in np.argwhere(np.asarray(good["weights"], dtype=np.float32).reshape(-1, 3, 4)[:, :, slot] > 0.25)[0])
+    broken, replaced = (dict(good, joints=np.array(good["joints"], dtype=np.uint16).reshape(-1, 3, 4).copy()) for _ in range(2))
+    broken["joints"][triangle, vertex, slot] = good["num_joints"]
+    replaced["joints"][triangle, vertex, slot] = 0
+    joints = {index: skin_cases.THREE}
+    got = rehearse(skin_check, tmp_path, "beyond", rest, ranges, {}, lamps, {index: broken}, joints)
+    assert got["flag"] & 1
+    want = restatement.skin_arrays(rest, ranges, {index: replaced}, joints, {})
+    for key in KEYS:
+        if rest[key] is not None:
+            assert np.array_equal(bits(got[key]), bits(want[key])), key
+    unbroken = restatement.skin_arrays(rest, ranges, {index: good}, joints, {})
+    at = ranges[index]["first_triangle"] + triangle
+    assert not np.array_equal(bits(want["positions"][at]), bits(unbroken["positions"][at]))  # the replacement moved the vertex
+    others = np.arange(len(rest["positions"])) != at
+    assert np.array_equal(bits(got["positions"][others]), bits(unbroken["positions"][others]))

@@ -1,6 +1,6 @@
 """pyr_scene_set_smoothing without a GPU: the new struct of the ABI, the argument checks that need no scene,
 the world's bookkeeping and `weld`, what the cases are, the host rehearsal of the smoothing kernel -- pose_rules.h, the header
-kernels/pose.hip compiles, through tests/probes/smooth_check.cpp, a program of its own built with -fsanitize=address,undefined and
+kernels/pose.hip compiles, through tests/probes/deform_check.cpp, a program of its own built with -fsanitize=address,undefined and
 run as a child process -- compared as bits with the numpy restatement (tests/smooth_restatement.py), and what the recomputed
 normals are worth against the float64 truth of an affine deformation."""
 import ctypes as C
@@ -15,6 +15,7 @@ import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+import deform_probe  # noqa: E402
 import morph_cases  # noqa: E402
 import morph_restatement  # noqa: E402
 import pose_cases as cases  # noqa: E402
@@ -76,8 +77,10 @@ def test_a_scene_without_smoothing_launches_no_new_kernel():
     host = open(os.path.join(ROOT, "pyrite_amd", "csrc", "live_scene.cpp")).read()
     unit = open(os.path.join(ROOT, "pyrite_amd", "csrc", "kernels", "pose.hip")).read()
     assert host.count("launch_smooth(") == 1
-    assert re.search(r"if \(live\.smooth_groups\) \{\s*const hipError_t es = devpose::launch_smooth\(", host)
-    assert re.search(r"forget_smoothing\(\) \{[^}]*smooth_groups = smooth_corners = 0;", host)
+    state = open(os.path.join(ROOT, "pyrite_amd", "csrc", "scene_internal.h")).read()
+    assert re.search(r"if \(live\.smooth\.groups\) \{\s*const hipError_t es = devpose::launch_smooth\(", host)
+    assert re.search(r"forget_smoothing\(\) \{\s*smooth\.clear\(\);", host)
+    assert re.search(r"struct Smooth \{.*?void clear\(\) \{[^}]*groups = corners = 0;", state, re.S)
     assert re.search(r"launch_smooth\(const SmoothCtx& c, hipStream_t stream\) \{\s*if \(c\.num_groups\) hipLaunchKernelGGL\(smooth_normals_kernel,", unit)
     assert unit.count("smooth_normals_kernel") == 2  # its definition and that one launch
 
@@ -191,64 +194,13 @@ def moved(rest, ranges, frame):
     return skin_restatement.skin_arrays(arrays, ranges, frame.get("skins", {}), frame.get("joints", {}), frame.get("poses", {}))
 
 
-def write_input(path, rest, ranges, lamps, smoothing, frame):
-    poses, skins, joints, morphs, weights = (frame.get(k, {}) for k in ("poses", "skins", "joints", "morphs", "weights"))
-    nt, ns = len(rest["positions"]), len(rest["spheres"])
-    with open(path, "wb") as f:
-        f.write(np.array([nt, ns, 0 if rest["frames"] is None else 1, len(ranges), len(lamps), len(skins), len(morphs), len(smoothing)], dtype=np.uint32).tobytes())
-        for key in KEYS:
-            if rest[key] is not None:
-                f.write(np.ascontiguousarray(rest[key], dtype=np.float32).tobytes())
-        for k, r in enumerate(ranges):
-            matrix, scale = poses.get(k, (None, 1.0))
-            f.write(np.array([r["first_triangle"], r["num_triangles"], r["first_sphere"], r["num_spheres"]], dtype=np.uint32).tobytes())
-            f.write(pose_restatement.column_major(matrix).tobytes())
-            f.write(np.float32(scale).tobytes())
-        f.write(np.array(lamps, dtype=np.uint32).reshape(-1, 2).tobytes())
-        for index in sorted(skins):
-            skin = skins[index]
-            f.write(np.array([index, skin["num_joints"]], dtype=np.uint32).tobytes())
-            f.write(skin_restatement.joint_table(joints.get(index), skin["num_joints"]).tobytes())
-            f.write(np.ascontiguousarray(skin["weights"], dtype=np.float32).tobytes())
-            f.write(np.ascontiguousarray(skin["joints"], dtype=np.uint16).tobytes())
-        for index in sorted(morphs):
-            morph = morphs[index]
-            f.write(np.array([index, len(morph["positions"]), 0 if morph["normals"] is None else 1], dtype=np.uint32).tobytes())
-            f.write(morph_restatement.weights_of(weights, index, len(morph["positions"])).tobytes())
-            f.write(np.ascontiguousarray(morph["positions"], dtype=np.float32).tobytes())
-            if morph["normals"] is not None:
-                f.write(np.ascontiguousarray(morph["normals"], dtype=np.float32).tobytes())
-        for index in sorted(smoothing):
-            f.write(np.array([index], dtype=np.uint32).tobytes())
-            f.write(np.ascontiguousarray(smoothing[index], dtype=np.uint32).tobytes())
-
-
-def read_output(path, rest, num_lamps):
-    data = np.fromfile(path, dtype=np.float32)
-    out, at = {}, 0
-    for key in KEYS:
-        if rest[key] is None:
-            out[key] = None
-            continue
-        out[key] = data[at:at + rest[key].size].reshape(rest[key].shape)
-        at += rest[key].size
-    out["lamps"] = data[at:at + 23 * num_lamps].reshape(num_lamps, 23)
-    at += 23 * num_lamps
-    assert at + 1 == len(data)
-    out["flag"] = int(data[at:].view(np.uint32)[0])
-    return out
-
-
 def bits(a):
     return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
 
 
 @pytest.fixture(scope="module")
 def smooth_check(tmp_path_factory):
-    exe = tmp_path_factory.mktemp("smooth_check") / "smooth_check"
-    subprocess.check_call([os.environ.get("CXX", "g++"), "-std=c++17", "-O1", "-g", "-ffp-contract=off", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
-                           "-static-libasan", "-static-libubsan", "-o", str(exe), os.path.join(ROOT, "tests", "probes", "smooth_check.cpp")])
-    return str(exe)
+    return deform_probe.build(tmp_path_factory.mktemp("deform_check"))
 
 
 @pytest.fixture(scope="module")
@@ -265,11 +217,7 @@ def rehearsal_inputs():
 
 
 def rehearse(smooth_check, tmp_path, name, rest, ranges, lamps, smoothing, frame):
-    source, result = str(tmp_path / (name + ".in")), str(tmp_path / (name + ".out"))
-    write_input(source, rest, ranges, lamps, smoothing, frame)
-    run = subprocess.run([smooth_check, source, result], capture_output=True, text=True, timeout=120)
-    assert run.returncode == 0, run.stdout + run.stderr
-    return read_output(result, rest, len(lamps))
+    return deform_probe.rehearse(smooth_check, tmp_path, name, rest, ranges, lamps, smoothing=smoothing, **{k: v for k, v in frame.items() if k != "name"})
 
 
 def test_the_host_rehearsal_of_the_smoothing_kernel_under_sanitizers(smooth_check, rehearsal_inputs, tmp_path):
