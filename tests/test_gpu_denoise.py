@@ -76,8 +76,9 @@ def hdr_halves(width, height, seed):
     return a, b, albedo, records
 
 
-def gpu_denoise(a, b, albedo, records, params, want_error=True, device_entry=False):
-    """pyr_image_denoise / pyr_image_denoise_device through ctypes: (out, error or None)."""
+def gpu_denoise(a, b, albedo, records, params, want_error=True, device_entry=False, out_bits=None):
+    """pyr_image_denoise / pyr_image_denoise_device through ctypes: (out, error or None). `out_bits`: the 32 bits every float of the
+    device entry's outputs holds before the call (default: zeros)."""
     h, w, _ = a.shape
     p = develop.denoise_params(**params)
     out, error = np.full(a.shape, -7, dtype=f32), np.full(a.shape, -7, dtype=f32) if want_error else None
@@ -93,6 +94,8 @@ def gpu_denoise(a, b, albedo, records, params, want_error=True, device_entry=Fal
 
     ta, tb, talb, trec = up(a), up(b), up(albedo), up(records)
     tout, terr = torch.zeros(a.size * 4, dtype=torch.uint8, device="cuda"), torch.zeros(a.size * 4, dtype=torch.uint8, device="cuda")
+    if out_bits is not None:
+        tout, terr = (torch.full((a.size,), out_bits, dtype=torch.int32, device="cuda").view(torch.uint8) for _ in range(2))
     stream = torch.cuda.current_stream()
     rc = lib().pyr_image_denoise_device(C.c_void_p(ta.data_ptr()), C.c_void_p(tb.data_ptr()), C.c_void_p(talb.data_ptr()) if talb is not None else None,
                                         C.c_void_p(trec.data_ptr()) if trec is not None else None, w, h, C.byref(p), C.c_void_p(tout.data_ptr()),

@@ -35,12 +35,15 @@ def form(request, monkeypatch):
     return request.param
 
 
-def glare_on_device(image, **params):
+def glare_on_device(image, out_bits=None, **params):
+    """`out_bits`: the 32 bits every float of `out` holds before the call (default: those of -1.0f)."""
     import torch
 
     h, w, _ = image.shape
     image_dev = torch.from_numpy(np.ascontiguousarray(image).view(np.uint8).reshape(-1).copy()).cuda()
     out = torch.full((h * w * 3,), -1.0, dtype=torch.float32, device="cuda")
+    if out_bits is not None:
+        out = torch.full((h * w * 3,), out_bits, dtype=torch.int32, device="cuda").view(torch.float32)
     p = develop.glare_params(**params)
     stream = torch.cuda.current_stream()
     check(lib().pyr_image_glare_device(C.c_void_p(image_dev.data_ptr()), w, h, C.byref(p), C.c_void_p(out.data_ptr()), 0, C.c_void_p(stream.cuda_stream)))

@@ -36,13 +36,16 @@ def kept(got, image):
     return (got.view(np.uint32) == image.view(np.uint32)).all(axis=-1)
 
 
-def blur_on_device(image, records, **params):
+def blur_on_device(image, records, out_bits=None, **params):
+    """`out_bits`: the 32 bits every float of `out` holds before the call (default: those of -1.0f)."""
     import torch
 
     h, w, _ = image.shape
     dev = lambda a: torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()  # noqa: E731
     image_dev, records_dev = dev(image), dev(records)
     out = torch.full((h * w * 3,), -1.0, dtype=torch.float32, device="cuda")
+    if out_bits is not None:
+        out = torch.full((h * w * 3,), out_bits, dtype=torch.int32, device="cuda").view(torch.float32)
     p = develop.lens_blur_params(**params)
     stream = torch.cuda.current_stream()
     check(lib().pyr_image_lens_blur_device(C.c_void_p(image_dev.data_ptr()), C.c_void_p(records_dev.data_ptr()), w, h, C.byref(p), C.c_void_p(out.data_ptr()), 0,

@@ -275,13 +275,16 @@ def random_frame(width, height, seed):
     return current, now, history, then, counts
 
 
-def reproject_on_device(current, now, history, then, counts, **params):
+def reproject_on_device(current, now, history, then, counts, out_bits=None, **params):
+    """`out_bits`: the 32 bits every float of the two outputs holds before the call (default: 0.0f)."""
     import torch
 
     h, w, _ = current.shape
     dev = lambda a: None if a is None else torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda()  # noqa: E731
     buffers = [dev(a) for a in (current, now, history, then, counts)]
     out, count = torch.zeros(h * w * 3, dtype=torch.float32, device="cuda"), torch.zeros(h * w, dtype=torch.float32, device="cuda")
+    if out_bits is not None:
+        out, count = (torch.full((n,), out_bits, dtype=torch.int32, device="cuda").view(torch.float32) for n in (h * w * 3, h * w))
     p = abi.PyrReprojectParams(params.get("depth_tolerance", abi.PYR_REPROJECT_DEPTH_TOLERANCE), params.get("max_history", abi.PYR_REPROJECT_MAX_HISTORY))
     stream = torch.cuda.current_stream()
     ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731

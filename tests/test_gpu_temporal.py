@@ -58,7 +58,8 @@ def random_frame(width, height, seed, spread=0.15):
     return current, now, history, then, counts, noise
 
 
-def resolve_on_device(current, now, history, then, counts, noise, clip=True, **params):
+def resolve_on_device(current, now, history, then, counts, noise, clip=True, out_bits=None, **params):
+    """`out_bits`: the 32 bits every float of the three outputs holds before the call (default: 0.0f, 0.0f and -7.0f)."""
     import torch
 
     h, w, _ = current.shape
@@ -66,6 +67,8 @@ def resolve_on_device(current, now, history, then, counts, noise, clip=True, **p
     buffers = [dev(a) for a in (current, now, noise, history, then, counts)]
     out = torch.zeros(h * w * 3, dtype=torch.float32, device="cuda")
     count, clipped = torch.zeros(h * w, dtype=torch.float32, device="cuda"), torch.full((h * w,), -7.0, dtype=torch.float32, device="cuda")
+    if out_bits is not None:
+        out, count, clipped = (torch.full((n,), out_bits, dtype=torch.int32, device="cuda").view(torch.float32) for n in (h * w * 3, h * w, h * w))
     p = develop.temporal_params(**params)
     stream = torch.cuda.current_stream()
     ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())  # noqa: E731

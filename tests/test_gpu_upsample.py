@@ -31,13 +31,16 @@ def assert_same_image(got, want, what):
         what, len(differs), got.size, tuple(differs[0]), got[tuple(differs[0])], want[tuple(differs[0])])
 
 
-def upsample_on_device(low, scale, albedo=None, pixels=None, low_albedo=None, low_pixels=None, **params):
+def upsample_on_device(low, scale, albedo=None, pixels=None, low_albedo=None, low_pixels=None, out_bits=None, **params):
+    """`out_bits`: the 32 bits every float of `out` holds before the call (default: those of -1.0f)."""
     import torch
 
     h, w, _ = low.shape
     keep = [None if a is None else torch.from_numpy(np.ascontiguousarray(a).view(np.uint8).reshape(-1).copy()).cuda() for a in (low, low_albedo, low_pixels, albedo, pixels)]
     at = [None if t is None else C.c_void_p(t.data_ptr()) for t in keep]
     out = torch.full((h * scale * w * scale * 3,), -1.0, dtype=torch.float32, device="cuda")
+    if out_bits is not None:
+        out = torch.full((h * scale * w * scale * 3,), out_bits, dtype=torch.int32, device="cuda").view(torch.float32)
     p = develop.upsample_params(**params)
     stream = torch.cuda.current_stream()
     check(lib().pyr_image_upsample_device(at[0], at[1], at[2], w, h, scale, at[3], at[4], C.byref(p), C.c_void_p(out.data_ptr()), 0, C.c_void_p(stream.cuda_stream)))
