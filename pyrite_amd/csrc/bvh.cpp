@@ -688,12 +688,22 @@ BuiltBvh build_bvh_levelwise(const std::vector<PrimBounds>& prims, bool leaves_t
 
     std::vector<uint32_t> level{0}, following;
     uint32_t levels = 0;
+    LevelBuildStats paths; // which paths of the device builder this input takes; nothing below reads them
+    {
+        const lvl::Box3 root = lvl::box_of_keys(tasks[0].cbox);
+        for (int a = 0; a < 3; ++a) paths.root_centroid_extent[a] = root.hi[a] - root.lo[a];
+    }
     while (!level.empty()) {
         ++levels;
         following.clear();
+        uint32_t large_nodes = 0;
         for (const uint32_t ti : level) {
             lvl::Task t = tasks[ti];
             const uint32_t count = t.end - t.begin;
+            if (count > kLevelSmallNode) {
+                paths.most_large_nodes = std::max(paths.most_large_nodes, ++large_nodes);
+                paths.most_chunks = std::max(paths.most_chunks, (count + kLevelChunk - 1) / kLevelChunk);
+            }
             const lvl::Box3 box = lvl::box_of_keys(t.box), cbox = lvl::box_of_keys(t.cbox);
             // bin phase
             Bins bins;
@@ -710,6 +720,19 @@ BuiltBvh build_bvh_levelwise(const std::vector<PrimBounds>& prims, bool leaves_t
                 for (uint32_t i = t.begin; i < t.end; ++i) leaf_shapes[i] = cur[i].shape;
                 tasks[ti] = t;
                 continue;
+            }
+            if (d.kind == lvl::KIND_MEDIAN) {
+                const float extent = cbox.hi[d.axis] - cbox.lo[d.axis];
+                paths.largest_median = std::max(paths.largest_median, count);
+                if (extent > 0.0f) {
+                    (count > kLevelSmallNode ? paths.medians_positive_large : paths.medians_positive_small)++;
+                    if (lvl::bin_scale(extent) == lvl::pos_inf()) paths.medians_infinite_scale++;
+                }
+                if (lvl::force_median(count, t.depth, depth_bound)) paths.largest_forced_median = std::max(paths.largest_forced_median, count);
+            } else if (count > kLevelSmallNode) {
+                int degenerate = 0;
+                for (int a = 0; a < 3; ++a) degenerate += !(cbox.hi[a] - cbox.lo[a] > 0.0f);
+                paths.degenerate_axis_splits += degenerate > 0;
             }
             // partition phase
             t.child0 = (uint32_t)tasks.size();
@@ -746,7 +769,7 @@ BuiltBvh build_bvh_levelwise(const std::vector<PrimBounds>& prims, bool leaves_t
         level.swap(following);
     }
     BuiltBvh out;
-    LevelBuildStats st;
+    LevelBuildStats st = paths;
     if (!finish_levelwise(tasks, leaf_shapes, bvh_padding(prims), out, &st)) return BuiltBvh{};
     st.levels = levels;
     if (stats) *stats = st;

@@ -66,9 +66,23 @@ BuiltBvh build_bvh(const std::vector<PrimBounds>& prims, bool leaves_tested_in_p
 // build_bvh's (tree_digest below is equal); where one does, the count / 2 references smallest by (centroid, shape code) go to
 // slot 0, which may break ties differently from build_bvh's nth_element. `depth_bound` stands in for kMaxBvhDepth in the depth
 // rule (tests lower it to reach the forced median on small inputs).
+// How the device builder divides a level's nodes (kernels/build_launch.h takes them from here): a node of at most
+// kLevelSmallNode references is one wave's; a larger one is shared out in chunks of kLevelChunk references.
+constexpr uint32_t kLevelSmallNode = 64;
+constexpr uint32_t kLevelChunk = 2048;
 struct LevelBuildStats {
     uint32_t levels = 0;        // iterations of the level loop
     uint32_t median_splits = 0; // nodes split by the median rule
+    // which paths of the device builder the input takes (tools/bvh_quality.cpp `level` prints them; no builder reads them)
+    uint32_t largest_median = 0;           // references of the largest node split by the median rule
+    uint32_t medians_positive_small = 0;   // median splits whose centroid extent on the chosen axis is positive: nodes of at most
+    uint32_t medians_positive_large = 0;   // kLevelSmallNode references, and larger ones
+    uint32_t medians_infinite_scale = 0;   // of both, those whose extent is so small that bin_scale(extent) is infinite
+    uint32_t largest_forced_median = 0;    // references of the largest node the depth rule (force_median) sent to the median rule
+    uint32_t most_large_nodes = 0;         // nodes of more than kLevelSmallNode references in one level, at most
+    uint32_t most_chunks = 0;              // chunks of kLevelChunk references of one such node, at most
+    uint32_t degenerate_axis_splits = 0;   // SAH splits of such nodes with a zero centroid extent on one or two axes
+    float root_centroid_extent[3] = {0, 0, 0};
 };
 BuiltBvh build_bvh_levelwise(const std::vector<PrimBounds>& prims, bool leaves_tested_in_pairs = false, uint32_t depth_bound = kMaxBvhDepth,
                              LevelBuildStats* stats = nullptr);

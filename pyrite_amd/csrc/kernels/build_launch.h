@@ -10,8 +10,8 @@ namespace devbuild {
 
 // A node of more than kSmallNode references is binned and partitioned by many workgroups, kChunk references each, through
 // global atomics; one of at most kSmallNode -- a wave's worth -- by one wave, from bins to children, without any.
-constexpr uint32_t kSmallNode = 64;
-constexpr uint32_t kChunk = 2048;
+constexpr uint32_t kSmallNode = kLevelSmallNode;
+constexpr uint32_t kChunk = kLevelChunk;
 constexpr uint32_t kBlock = 256;
 // the largest node one workgroup splits by the median rule (its keys live in LDS: 8 bytes each); a larger one ends the device build
 constexpr uint32_t kMedianMax = 2048;

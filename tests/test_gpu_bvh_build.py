@@ -1,9 +1,15 @@
 """The BVH built on the device (pyr_scene_create_with, PYR_BUILD_DEVICE) against the host builder's -- run
 with `-m gpu` on an MI355X. The inputs are those of tests/test_bvh_device_cpu.py (tests/bvh_build_inputs.py).
 
-Tie-free inputs: the device builds the host's tree -- equal digest (the one tests/golden/bvh_digests.json pins), equal PyrBvhInfo, hits equal bit for bit, equal traversal
+Every tree the device builds is the rehearsal's (build_bvh_levelwise), medians included: its digest, median splits and levels are
+the ones tests/golden/bvh_digests.json pins, and tests/test_bvh_device_cpu.py proves on the CPU which path of the builder each
+input reaches (the median over distinct centroids in either kernel, the depth rule, chunk and wave edges, a level of more large
+nodes than one workgroup chooses, degenerate axes, signed zeros, huge and subnormal coordinates).
+Tie-free inputs: that is the host's tree too -- equal PyrBvhInfo, hits equal bit for bit, equal traversal
 counts. Fallback inputs (a node needs the median rule, where the two builders may break ties differently): equal hit distances bit
 for bit, and equal shapes except where the oracle's own intersection routine says both primitives are hit at that very distance.
+The inputs at the builder's edges are held to the oracle's hits as well, and the deep trees of the depth rule to the oracle's
+films, with the traversal stack spilled past its LDS part by real depth.
 The command lines compare PNG files byte for byte: the 8-bit image of a fixed seed does not move with the order of the film's
 float atomics in any test of this suite (tests/test_gpu_session.py compares the same way), and here the trees are equal too."""
 import json
@@ -16,7 +22,8 @@ import pytest
 
 sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 import bvh_build_inputs as inputs  # noqa: E402
-from test_gpu_parity import TOL, primitive_distance, rel_l2  # noqa: E402
+import oracle  # noqa: E402
+from test_gpu_parity import TOL, assert_parity, assert_same_hits, primitive_distance, rel_l2  # noqa: E402
 
 from pyrite_amd import abi, scenes  # noqa: E402
 from pyrite_amd import build as gpu_build  # noqa: E402
@@ -30,22 +37,30 @@ with open(os.path.join(ROOT, "tests", "golden", "bvh_digests.json")) as f:
     PINS = json.load(f)
 
 
-def world_of(spheres, tris):
+def world_of(spheres, tris, sky=None):
     flat = FlatScene()
     grey = {"surface": material.diffuse(color=0.8)}
-    flat.add_world({"objects": [shape.sphere(position=vector(float(s[0]), float(s[1]), float(s[2])), radius=float(s[3]), material=grey) for s in spheres]})
+    flat.add_world({"sky": sky, "objects": [shape.sphere(position=vector(float(s[0]), float(s[1]), float(s[2])), radius=float(s[3]), material=grey) for s in spheres]})
     if len(tris):
         mat, _ = flat.add_material(grey)
         t = tris.reshape(-1, 3, 3)
-        n = np.cross(t[:, 1] - t[:, 0], t[:, 2] - t[:, 0])
-        n /= np.maximum(np.linalg.norm(n, axis=1, keepdims=True), 1e-30)
-        flat.add_triangles(t, np.repeat(n[:, None, :], 3, axis=1), mat)
+        e = t.astype(np.float64)  # (the cross product of a triangle of 1e-30 underflows in float32)
+        n = np.cross(e[:, 1] - e[:, 0], e[:, 2] - e[:, 0])
+        n /= np.maximum(np.linalg.norm(n, axis=1, keepdims=True), 1e-300)
+        flat.add_triangles(t, np.repeat(n[:, None, :], 3, axis=1).astype(np.float32), mat)
     return World(flat)
 
 
-def rays_into(spheres, tris, n, seed=9):
-    o, d, _ = inputs.rays_for(spheres, tris, n=n, seed=seed)
-    return np.concatenate([o[:n], d[:n]], axis=1).astype(np.float32)
+rays_into = inputs.rays_into
+
+
+def assert_the_rehearsals_tree(info, name):
+    """The device built it, and it is build_bvh_levelwise's tree: the pinned digest, median splits and levels (both builders count the
+    iterations of their level loop; none for a scene that is a single leaf)."""
+    group = "level_tie_free" if name in inputs.TIE_FREE else "level_fallback" if name in inputs.FALLBACK else "level_depth_rule"
+    assert info["builder_asked"] == info["builder_used"] == abi.PYR_BUILD_DEVICE and info["fallback_reason"] == 0
+    assert "%016x" % info["tree_digest"] == PINS[group][name]["levelwise"]
+    assert {"medians": info["median_splits"], "levels": info["levels"]} == PINS["level_counts"][name]
 
 
 def built_pair(name, group):
@@ -66,6 +81,7 @@ def test_tie_free_inputs_get_the_host_builders_tree(gpu_lib, name):
     assert d["builder_asked"] == d["builder_used"] == abi.PYR_BUILD_DEVICE and d["fallback_reason"] == 0 and d["median_splits"] == 0
     assert d["tree_digest"] == h["tree_digest"]
     assert "%016x" % d["tree_digest"] == PINS["level_tie_free"][name]["levelwise"]
+    assert_the_rehearsals_tree(d, name)
     assert device.bvh_info() == host.bvh_info()
     rays = rays_into(spheres, tris, 20000)
     hh, _, hc = host.intersect(rays, want_counters=True)
@@ -83,11 +99,12 @@ def test_fallback_inputs_get_a_tree_with_the_same_hits(gpu_lib, name):
     d = device.build_info()
     assert d["builder_used"] == abi.PYR_BUILD_DEVICE and d["fallback_reason"] == 0
     assert d["median_splits"] > 0 and host.build_info()["median_splits"] > 0
+    assert_the_rehearsals_tree(d, name)  # both rank by median_before: the rehearsal's tree, digest for digest
     rays = rays_into(spheres, tris, 20000)
     hh, _, _ = host.intersect(rays)
     dh, _, _ = device.intersect(rays)
     assert np.array_equal(hh["distance"].view(np.uint32), dh["distance"].view(np.uint32))
-    assert (hh["shape"] != 0xFFFFFFFF).sum() > 100
+    assert (hh["shape"] != 0xFFFFFFFF).sum() > 100 or name in inputs.UNHITTABLE
     assert_shapes_equal_up_to_ties(host, hh, dh, rays)
 
 
@@ -123,6 +140,151 @@ def test_a_median_node_too_large_for_the_device_is_built_on_the_host(gpu_lib):
     hh, _, _ = host.intersect(rays)
     dh, _, _ = device.intersect(rays)
     assert hh.tobytes() == dh.tobytes() and (hh["shape"] != 0xFFFFFFFF).sum() > 100
+
+
+# ------------------------------------------------------------------------------------------------- the builder's edges
+@pytest.mark.parametrize("name", [n for n in inputs.EDGES if n not in inputs.DEPTH_RULE and n != "tri40000"])
+def test_edge_inputs_answer_like_the_oracle_on_a_device_built_scene(gpu_lib, name):
+    """The host-built scene is not the only witness: closest hits of 20,000 rays against the oracle's, ties proven."""
+    spheres, tris = inputs.group_of(name)[name]()
+    world = world_of(spheres, tris)
+    world.scene(0, build="device")
+    assert_the_rehearsals_tree(world.build_info(), name)
+    rays = inputs.rays_of(name, spheres, tris)
+    ohits, _ = oracle.OracleScene(world).intersect(rays)
+    ghits, _, _ = world.intersect(rays)
+    ties = assert_same_hits(ohits, ghits, world, rays)
+    print("%s: %d of %d rays hit, %d ties" % (name, (ohits["shape"] != 0xFFFFFFFF).sum(), len(rays), ties))
+    assert (ghits["shape"] != 0xFFFFFFFF).sum() >= 1000 or name in inputs.UNHITTABLE
+    world.close()
+
+
+def test_forty_thousand_triangles_are_chosen_by_more_than_one_workgroup(gpu_lib):
+    """tri40000 has levels of several hundred large nodes (choose_large_kernel decides 64 per workgroup) and a root of 20 chunks:
+    the rehearsal's tree, and the host-built scene's hits and traversal counts on rays that hit."""
+    spheres, tris, host, device = built_pair("tri40000", inputs.TIE_FREE)
+    assert_the_rehearsals_tree(device.build_info(), "tri40000")
+    assert device.bvh_info() == host.bvh_info()
+    rays = inputs.rays_of("tri40000", spheres, tris)
+    hh, _, hc = host.intersect(rays, want_counters=True)
+    dh, _, dc = device.intersect(rays, want_counters=True)
+    assert hh.tobytes() == dh.tobytes() and (hh["shape"] != 0xFFFFFFFF).sum() >= 1000
+    assert (hc["box_tests"], hc["triangle_tests"], hc["sphere_tests"]) == (dc["box_tests"], dc["triangle_tests"], dc["sphere_tests"])
+
+
+# ------------------------------------------------------------------------------------------------- the depth rule
+def chain_world(name, build, sky=None):
+    spheres, tris = inputs.DEPTH_RULE[name]()
+    world = world_of(spheres, tris, sky=sky)
+    world.scene(0, build=build)
+    return spheres, tris, world
+
+
+def assert_chain_tree(world, name):
+    """chain300, chain300_r4: the device's median kernel ranked distinct centroids at the depth rule's node; the scene walks its
+    four-wide tree. chain3000: that node is larger than the kernel ranks, the host built, and the four-wide tree, whose stack need
+    is beyond the kernels', is dropped for the binary one."""
+    info, bvh = world.build_info(), world.bvh_info()
+    assert bvh["max_depth"] == 39
+    if name == "chain3000":
+        assert info["builder_asked"] == abi.PYR_BUILD_DEVICE and info["builder_used"] == abi.PYR_BUILD_HOST
+        assert info["fallback_reason"] == abi.PYR_BUILD_FALLBACK_MEDIAN_TOO_LARGE and info["levels"] == 0
+        assert bvh["num_wide_nodes"] == bvh["num_pair_records"] == 0 and bvh["wide_node_bytes"] == 0 and bvh["num_nodes"] > 1000
+    else:
+        assert_the_rehearsals_tree(info, name)
+        assert bvh["num_wide_nodes"] > 0
+    return info
+
+
+@pytest.mark.parametrize("name", sorted(inputs.DEPTH_RULE))
+def test_deep_trees_answer_like_the_oracle_whatever_part_of_the_stack_is_in_lds(gpu_lib, name, monkeypatch):
+    """20,000 rays aimed at the triangles a ray can hit and 2,000 through the small end, which every padded box of the chain holds:
+    a walk 39 levels down pushes past the LDS part of its stack with real depth. One LDS level, and the default: the same bits."""
+    spheres, tris, world = chain_world(name, "device")
+    info = assert_chain_tree(world, name)
+    rays = inputs.rays_of(name, spheres, tris)
+    assert len(rays) == 22000
+    ohits, _ = oracle.OracleScene(world).intersect(rays)
+    ghits, _, _ = world.intersect(rays)
+    ties = assert_same_hits(ohits, ghits, world, rays)
+    print("%s: %d of %d rays hit, %d ties, build_info %r" % (name, (ohits["shape"] != 0xFFFFFFFF).sum(), len(rays), ties, info))
+    assert (ghits["shape"] != 0xFFFFFFFF).sum() >= 1000
+    monkeypatch.setenv("PYRITE_LDS_STACK", "1")
+    short, _, _ = world.intersect(rays)
+    assert short.tobytes() == ghits.tobytes()
+    monkeypatch.delenv("PYRITE_LDS_STACK")
+    host = world_of(spheres, tris)
+    host.scene(0, build="host")
+    assert host.build_info()["tree_digest"] == info["tree_digest"]  # distinct centroids: nth_element has no tie to break its own way
+    hh, _, _ = host.intersect(rays)
+    assert hh.tobytes() == ghits.tobytes()
+    host.close(), world.close()
+
+
+def chain_view(tris):
+    """Straight at the chain's triangle of a size nearest 100, from 1.5 sizes off its plane: it fills a good part of the view, the
+    sky the rest, and every ray runs inside the padded boxes of all the smaller links and of the cluster (the padding, 16 ulps of
+    the chain's top, is 2e6)."""
+    from pyrite_amd.project import camera, transform
+    from pyrite_amd.renderer import Camera
+
+    t = tris.reshape(-1, 3, 3).astype(np.float64)
+    size = np.linalg.norm(t.max(axis=1) - t.min(axis=1), axis=1)
+    k = int(np.argmin(np.abs(np.log(size / 100.0))))
+    n = np.cross(t[k, 1] - t[k, 0], t[k, 2] - t[k, 0])
+    centre, eye = t[k].mean(axis=0), t[k].mean(axis=0) + 1.5 * size[k] * n / np.linalg.norm(n)
+    up = np.cross(n, [1.0, 0.3, 0.2])
+    return Camera.from_project(camera.perspective(fov=40.0, transform=transform.look_at(**{"from": vector(*eye), "to": vector(*centre), "up": vector(*(up / np.linalg.norm(up)))})))
+
+
+@pytest.mark.parametrize("name", sorted(inputs.DEPTH_RULE))
+def test_a_render_of_a_deep_tree_matches_the_oracles_film(gpu_lib, name):
+    from pyrite_amd.project import renderer as project_renderer
+    from pyrite_amd.renderer import Renderer
+
+    _, tris, world = chain_world(name, "device", sky=1.0)
+    assert_chain_tree(world, name)
+    r, cam = Renderer.from_project(project_renderer.simple(pixel_samples=4), seed=3), chain_view(tris)
+    gfilm, cfilm = r.new_film(32, 24), r.new_film(32, 24)
+    ccount = oracle.OracleScene(world).render(r, cam, cfilm, threads=8)
+    gcount = r.render(gfilm, cam, world, counters=True)
+    assert_parity(gfilm, cfilm)
+    for key in ("samples", "extension_rays", "shadow_rays", "shaded_hits", "exposures"):
+        assert gcount[key] == ccount[key], key
+    assert 100 < ccount["shaded_hits"] and ccount["samples"] == 32 * 24 * 4  # paths bounce off the chain under the sky
+    world.close()
+
+
+def test_feature_and_motion_passes_of_a_deep_tree_are_the_host_built_scenes(gpu_lib):
+    """features_kernel and motion_kernel carry scratch stacks of their own."""
+    from pyrite_amd.project import renderer as project_renderer
+    from pyrite_amd.renderer import Renderer
+
+    r, cam = Renderer.from_project(project_renderer.simple(pixel_samples=4), seed=3), chain_view(inputs.DEPTH_RULE["chain300"]()[1])
+    seen = {}
+    for build in ("host", "device"):
+        _, _, world = chain_world("chain300", build, sky=1.0)
+        f = r.features((32, 24), cam, world)
+        seen[build] = (f.albedo.grains.tobytes(), f.records.tobytes(), r.motion((32, 24), cam, world).tobytes())
+        if build == "device":
+            assert_chain_tree(world, "chain300")
+            assert 0 < (f.records["shape"] != 0xFFFFFFFF).sum() < f.records["shape"].size  # the view holds triangles and sky
+        world.close()
+    assert seen["host"] == seen["device"]
+
+
+def test_an_identity_refit_of_the_binary_tree_of_chain3000_changes_nothing(gpu_lib):
+    from test_gpu_scene_update import counts_of, same_bits, update_world
+
+    spheres, tris, world = chain_world("chain3000", "device")
+    assert_chain_tree(world, "chain3000")
+    rays = inputs.rays_of("chain3000", spheres, tris)
+    h0, _, c0 = world.intersect(rays, want_counters=True)
+    update_world(world, spheres, tris)
+    h1, _, c1 = world.intersect(rays, want_counters=True)
+    assert same_bits(h0, h1) and counts_of(c0) == counts_of(c1) and (h0["shape"] != 0xFFFFFFFF).sum() >= 1000
+    assert world.update_info()["mode_used"] == abi.PYR_UPDATE_REFIT and world.update_info()["area_ratio"] == 1.0
+    world.close()
 
 
 def test_a_render_on_a_device_built_scene_is_the_host_built_scenes(gpu_lib):

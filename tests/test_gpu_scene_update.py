@@ -34,9 +34,9 @@ def counts_of(counters):
 
 
 def normals_of(tris):
-    t = tris.reshape(-1, 3, 3)
+    t = tris.reshape(-1, 3, 3).astype(np.float64)  # (as world_of: a cross product of 1e21 squared overflows float32)
     n = np.cross(t[:, 1] - t[:, 0], t[:, 2] - t[:, 0])
-    n /= np.maximum(np.linalg.norm(n, axis=1, keepdims=True), 1e-30)
+    n /= np.maximum(np.linalg.norm(n, axis=1, keepdims=True), 1e-300)
     return np.repeat(n[:, None, :], 3, axis=1).astype(np.float32)
 
 
@@ -62,15 +62,7 @@ def moved(spheres, tris, move):
     return new_spheres, (tris + rng.uniform(-amplitude, amplitude, size=tris.shape).astype(np.float32)).astype(np.float32)
 
 
-def aimed_rays(spheres, tris, n, seed=3):
-    """rays_for's set and as many rays aimed at primitives from points around them, so that small inputs are hit often too."""
-    centres = np.concatenate([tris.reshape(-1, 3, 3).mean(axis=1), spheres[:, :3]]).astype(np.float64)
-    rng = np.random.RandomState(seed)
-    target = centres[rng.randint(len(centres), size=n // 2)]
-    origin = target + rng.normal(size=target.shape) * 6.0
-    d = target - origin
-    d /= np.linalg.norm(d, axis=1, keepdims=True)
-    return np.concatenate([rays_into(spheres, tris, n - n // 2), np.concatenate([origin, d], axis=1).astype(np.float32)])
+aimed_rays = inputs.aimed_rays
 
 
 def update_world(world, spheres, tris, mode="refit", form="host"):
@@ -155,6 +147,29 @@ def test_a_rebuilt_scene_is_the_scene_created_from_the_moved_arrays(gpu_lib, nam
     ha, _, ca = a.intersect(rays, want_counters=True)
     hb, _, cb = b.intersect(rays, want_counters=True)
     assert same_bits(ha, hb) and counts_of(ca) == counts_of(cb)  # the same builder on the same arrays: the same tree, ties included
+    assert (hb["shape"] != 0xFFFFFFFF).sum() > 1000
+    info = a.update_info()
+    assert info["mode_used"] == abi.PYR_UPDATE_REBUILD and info["updates"] == 0 and info["area_ratio"] == 1.0
+    a.close(), b.close()
+
+
+@pytest.mark.parametrize("name", ["tri2049", "chain300"])
+def test_a_device_rebuild_at_the_builders_edges_is_the_scene_created_from_the_moved_arrays(gpu_lib, name):
+    """tri2049: a root of two chunks. chain300: the depth rule's median in the median kernel (moved rigidly, its small end collapses
+    onto one point: the medians of the rebuilt tree rank equal centroids as well as distinct ones)."""
+    spheres, tris = inputs.group_of(name)[name]()
+    new_spheres, new_tris = moved(spheres, tris, "rigid")
+    a, b = world_of(spheres, tris), world_of(new_spheres, new_tris)
+    a.scene(0, build="device"), b.scene(0, build="device")
+    update_world(a, new_spheres, new_tris, mode="rebuild")
+    ia, ib = a.build_info(), b.build_info()
+    for key in ("builder_asked", "builder_used", "fallback_reason", "levels", "median_splits", "tree_digest"):
+        assert ia[key] == ib[key], key
+    assert ib["builder_used"] == abi.PYR_BUILD_DEVICE and a.bvh_info() == b.bvh_info()
+    rays = inputs.aimed_rays_at_scale(new_spheres, new_tris, 20000) if name in inputs.AT_SCALE else aimed_rays(new_spheres, new_tris, 20000)
+    ha, _, ca = a.intersect(rays, want_counters=True)
+    hb, _, cb = b.intersect(rays, want_counters=True)
+    assert same_bits(ha, hb) and counts_of(ca) == counts_of(cb)
     assert (hb["shape"] != 0xFFFFFFFF).sum() > 1000
     info = a.update_info()
     assert info["mode_used"] == abi.PYR_UPDATE_REBUILD and info["updates"] == 0 and info["area_ratio"] == 1.0
