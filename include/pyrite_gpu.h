@@ -603,6 +603,44 @@ typedef struct PyrSkin {
     uint32_t reserved[4];
 } PyrSkin;
 int pyr_scene_set_skins(PyrScene*, const PyrSkin* skins, uint32_t num_skins);
+/* ---- dual quaternion skinning, chosen per skin. Where two joints twist against each other the linear blend above is no rotation
+ * and the mesh loses volume (the "candy wrapper": joints 170 degrees apart about the bone leave the ring between them 9 % of its
+ * radius). A dual-quaternion skin (Kavan et al. 2007) blends its joints as rigid motions instead; only how the vertex's matrix B is
+ * made changes, and everything after B is the rule above. All f32 and unfused; normalize, sqrt and 1/x as in pyr_scene_pose;
+ * dot4(a,b) = ((a0*b0 + a1*b1) + a2*b2) + a3*b3.
+ *   Per joint, once per frame, on the host: r = quat_from_cols(c0, c1, c2) of the joint's upper 3x3 columns, (s,x,y,z);
+ * k = 1/sqrt(dot4(r,r)); r = r*k per component. With t the translation column, the dual part d = 0.5 * (0,t) * r:
+ *     d0 = -0.5f*((t0*r1 + t1*r2) + t2*r3)        d1 = 0.5f*((t0*r0 + t1*r3) - t2*r2)
+ *     d2 =  0.5f*((t1*r0 + t2*r1) - t0*r3)        d3 = 0.5f*((t0*r2 + t2*r0) - t1*r1)
+ * Q[j] = (r, d), eight floats, in a device table beside the twelve-float one, allocated and uploaded only while some skin is
+ * dual-quaternion: a scene without such a skin allocates, uploads and launches nothing for it.
+ *   Per vertex, on the device, with the binding's j0..j3 and w0..w3: the pivot is joint j0; for k = 1..3
+ * wk' = dot4(r[j0], r[jk]) < 0 ? -wk : wk (a dot of zero or NaN does not negate), w0' = w0;
+ *     b[e] = ((w0'*Q[j0][e] + w1'*Q[j1][e]) + w2'*Q[j2][e]) + w3'*Q[j3][e]          for the eight entries
+ * s = dot4(b[0..4], b[0..4]); a lane with !(s >= 1e-30f && s <= 1e30f) raises bit 3 (value 8) of the call's flag word;
+ * k = 1/sqrt(s); r = b[0..4]*k, d = b[4..8]*k; the translation t = 2 * (d * conj(r)):
+ *     t0 = 2.0f*(((d1*r0 - d0*r1) - d2*r3) + d3*r2)
+ *     t1 = 2.0f*(((d2*r0 - d0*r2) + d1*r3) - d3*r1)
+ *     t2 = 2.0f*(((d3*r0 - d0*r3) - d1*r2) + d2*r1)
+ * B's upper 3x3 is cgmath's Matrix3::from(Quaternion) of r = (s,x,y,z): with x2=x+x, y2=y+y, z2=z+z, xx2=x2*x, xy2=x2*y, xz2=x2*z,
+ * yy2=y2*y, yz2=y2*z, zz2=z2*z, sx2=x2*s, sy2=y2*s, sz2=z2*s the columns are (1-yy2-zz2, xy2+sz2, xz2-sy2),
+ * (xy2-sz2, 1-xx2-zz2, yz2+sx2), (xz2+sy2, yz2-sx2, 1-xx2-yy2); the fourth column is t, the last row 0,0,0,1. The vertex then takes
+ * exactly what a linearly blended vertex takes: the per-vertex rule with transform B and scale 1.0f, then the object's pose. As
+ * above: a skin whose joint matrices are all exactly the identity copies rest bit for bit, weights are not renormalised, an index
+ * at or above the skin's count uses joint 0 and raises bit 0, and the geometry is always computed from rest.
+ *   pyr_scene_set_skin_blend gives one mode per skin, in skin order. It needs skins to be set, sets every joint to the identity as
+ * pyr_scene_set_skins does, and the geometry does not change at this call. pyr_scene_set_skins makes every skin linear again, and
+ * whatever forgets the skins forgets the modes. Refused with PYR_ERR_INVALID_ARGUMENT, in this order, before any device is looked
+ * for: NULL modes; a NULL scene; no skins set; num_skins that is not the scene's; an unknown mode. A refused call leaves the modes
+ * as they were.
+ *   pyr_scene_skin and pyr_scene_morph add one check, after "a last row that is not 0,0,0,1": a joint of a dual-quaternion skin whose
+ * upper 3x3 is not a rotation is refused. A rotation here: |dot(ci,ci) - 1| <= 1e-3f for each column, |dot(ci,cj)| <= 1e-3f for
+ * each pair, dot(cross(c0,c1), c2) > 0, with dot(a,b) = (a0*b0 + a1*b1) + a2*b2. The flag word: bits 0, 1 and 2 keep their order
+ * and messages; bit 3 without any of them is PYR_ERR_UNSUPPORTED with a message that names a blended joint rotation (the rotations
+ * of a vertex's joints cancel, as two antipodal ones under equal weights). The scene renders as before. */
+#define PYR_SKIN_LINEAR 0u
+#define PYR_SKIN_DUAL_QUATERNION 1u
+int pyr_scene_set_skin_blend(PyrScene*, const uint32_t* modes, uint32_t num_skins);
 typedef struct PyrSkinUpdate {
     uint32_t mode;               /* PYR_UPDATE_REFIT | PYR_UPDATE_REBUILD */
     uint32_t num_objects;        /* must equal the scene's */

@@ -299,10 +299,14 @@ class World { // world.rs:31-36
     // bindings -- four joint indices below num_joints and four weights for each of the three vertices of each of the object's
     // triangles ([T][3][4] each). Skins are in the order of their object indices. Every joint is the identity afterwards and the
     // geometry does not change; an empty map forgets the skins, and so do set_objects() and an update() that carries arrays.
+    // `blend`: PYR_SKIN_LINEAR (the vertex's matrix is the weighted sum of its joints' matrices) or PYR_SKIN_DUAL_QUATERNION
+    // (pyr_scene_set_skin_blend: the joints are blended as rigid motions, which keeps the volume of a twisting mesh; the joints of
+    // such a skin must be rotations and translations).
     struct Skin {
         uint32_t num_joints = 0;
         std::vector<uint16_t> joints;
         std::vector<float> weights;
+        uint32_t blend = PYR_SKIN_LINEAR;
     };
     void set_skins(const std::map<size_t, Skin>& skins);
     // One frame of the skinned meshes of the scene on `device` (pyr_scene_skin): `joints` maps a skinned object's index to its joint

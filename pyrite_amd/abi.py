@@ -264,6 +264,8 @@ class PyrBuildInfo(C.Structure):
 
 PYR_UPDATE_REFIT = 0
 PYR_UPDATE_REBUILD = 1
+PYR_SKIN_LINEAR = 0
+PYR_SKIN_DUAL_QUATERNION = 1
 
 
 class PyrGeometryUpdate(C.Structure):
@@ -565,6 +567,7 @@ ENTRY_POINTS = {
     "pyr_scene_pose": (C.c_int, [C.c_void_p, C.POINTER(PyrPoseUpdate), C.c_void_p]),
     "pyr_scene_geometry": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "pyr_scene_set_skins": (C.c_int, [C.c_void_p, C.POINTER(PyrSkin), C.c_uint32]),
+    "pyr_scene_set_skin_blend": (C.c_int, [C.c_void_p, C.POINTER(C.c_uint32), C.c_uint32]),
     "pyr_scene_skin": (C.c_int, [C.c_void_p, C.POINTER(PyrSkinUpdate), C.c_void_p]),
     "pyr_scene_set_morphs": (C.c_int, [C.c_void_p, C.POINTER(PyrMorph), C.c_uint32]),
     "pyr_scene_morph": (C.c_int, [C.c_void_p, C.POINTER(PyrMorphUpdate), C.c_void_p]),

@@ -1206,6 +1206,10 @@ void World::set_skins_on(PyrScene* handle, const std::map<size_t, Skin>& skins) 
         records.push_back(s);
     }
     check_status(pyr_scene_set_skins(handle, records.data(), (uint32_t)records.size()));
+    std::vector<uint32_t> modes;
+    for (const auto& kv : skins) modes.push_back(kv.second.blend);
+    if (std::any_of(modes.begin(), modes.end(), [](uint32_t m) { return m != PYR_SKIN_LINEAR; })) // (pyr_scene_set_skins has made every skin linear)
+        check_status(pyr_scene_set_skin_blend(handle, modes.data(), (uint32_t)modes.size()));
 }
 void World::set_skins(const std::map<size_t, Skin>& skins) {
     for (const auto& kv : skins) {
@@ -1213,6 +1217,8 @@ void World::set_skins(const std::map<size_t, Skin>& skins) {
         const size_t words = 12 * (size_t)flat_.objects()[kv.first].range.num_triangles;
         if (kv.second.joints.size() != words || kv.second.weights.size() != words)
             throw ProjectError("set_skins: object " + std::to_string(kv.first) + " needs four joints and four weights for each vertex of each of its triangles");
+        if (kv.second.blend != PYR_SKIN_LINEAR && kv.second.blend != PYR_SKIN_DUAL_QUATERNION)
+            throw ProjectError("set_skins: the blend of object " + std::to_string(kv.first) + " is neither PYR_SKIN_LINEAR nor PYR_SKIN_DUAL_QUATERNION");
     }
     for (auto& kv : scenes_) set_skins_on(kv.second, skins);
     skins_ = skins;

@@ -480,7 +480,7 @@ int main(int argc, char** argv) {
             std::printf("%zu objects posed\n", poses.size());
             return 0;
         }
-        if (argc >= 7 && std::string(argv[1]) == "skin") { // skin <scene> <data_dir> <bindings> <joints.f32> <geometry.f32> [rebuild] (tests)
+        if (argc >= 7 && std::string(argv[1]) == "skin") { // skin <scene> <data_dir> <bindings> <joints.f32> <geometry.f32> [refit|rebuild [dual_quaternion]] (tests)
             // bindings: u32 object, num_joints; u16 joints[T][3][4]; f32 weights[T][3][4] for the object's T triangles. joints.f32: 16 floats a joint.
             Project project = make_scene(argv[2], argv[3]);
             std::unique_ptr<World> world = World::from_project(project.world, argv[3]);
@@ -498,6 +498,7 @@ int main(int argc, char** argv) {
             if (table.size() != (size_t)head[1] * 64) throw ProjectError("skin: the joints file does not hold 16 floats for each joint");
             World::Skin skin;
             skin.num_joints = head[1];
+            if (argc >= 9 && std::string(argv[8]) == "dual_quaternion") skin.blend = PYR_SKIN_DUAL_QUATERNION;
             skin.joints.resize(words), skin.weights.resize(words);
             if (words) std::memcpy(skin.joints.data(), bindings.data() + 8, words * 2), std::memcpy(skin.weights.data(), bindings.data() + 8 + words * 2, words * 4);
             std::vector<float> joints(table.size() / 4);

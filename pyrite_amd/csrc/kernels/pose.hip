@@ -1,5 +1,5 @@
 // pose.hip -- a live scene's deformation pipeline on the device, morph -> skin -> pose -> smooth -> lamps (DESIGN.md sections 9g,
-// 9h, 9p, 9q and 9r), a unit of its own: every primitive of an object is computed from the rest pose (where the scene has morphs:
+// 9h, 9p, 9q, 9r and 9s), a unit of its own: every primitive of an object is computed from the rest pose (where the scene has morphs:
 // from the morphed rest, which the morph kernel writes first) and written to the scene's staging arrays, from where the refit of
 // section 9f (kernels/refit.hip) rewrites the records and the boxes; the records of shape lamps follow from the staging arrays
 // too. Nothing here touches a record the render kernels read except the lamp records, and those only after the host has seen
@@ -152,6 +152,46 @@ __global__ __launch_bounds__(kBlock) void skin_triangles_kernel(Ctx c) {
                     j[0] = jv.x & 0xFFFFu, j[1] = jv.x >> 16, j[2] = jv.y & 0xFFFFu, j[3] = jv.y >> 16;
                 }
                 bad |= pose::skin_vertex(joints, num_joints, rest_skin != 0u, j, w, pose, p + 3 * v, n, q, c.rest_frames != nullptr);
+                store_normal_frame(c, index, v, n, q);
+            }
+            bad |= store_positions(c, index, p);
+        }
+    }
+    raise_flag(bad, &block_flag, c.beyond_range);
+}
+
+// ---- the same lanes for the dual-quaternion skins, through pose_rules.h skin_vertex_dual: a kernel of its
+// own, not a branch in the one above, whose code and registers stay what they were. The two read the same bindings and each its
+// own skin table (Ctx::skins, Ctx::dual_skins), in which a skin of the other kind has no triangles, so that its lanes do nothing;
+// each is launched only when a skin of its kind exists. A joint's dual quaternion is eight floats read as two 16-byte loads: 128
+// bytes a vertex against the 192 of four linear joints.
+__global__ __launch_bounds__(kBlock) void skin_triangles_dual_kernel(Ctx c) {
+    __shared__ uint32_t block_flag;
+    if (threadIdx.x == 0) block_flag = 0u;
+    __syncthreads();
+    const uint32_t lane = blockIdx.x * kBlock + threadIdx.x;
+    uint32_t bad = 0u;
+    if (lane < c.skinned_triangles && c.num_skins != 0u) {
+        const DevSkin& skin = c.dual_skins[object_of<DevSkin, &DevSkin::lane>(c.dual_skins, c.num_skins, lane)];
+        const uint32_t within = lane - skin.lane, index = skin.first_triangle + within;
+        const bool joints_inside = skin.num_joints != 0u && skin.first_joint < c.num_joints && skin.num_joints <= c.num_joints - skin.first_joint;
+        if (within < skin.num_triangles && index >= skin.first_triangle && index < c.num_triangles && joints_inside) {
+            const pose::Pose pose = load_pose(skin.pose);
+            const uint32_t num_joints = skin.num_joints, rest_skin = skin.identity;
+            const float* quats = c.joint_quats + 8 * (size_t)skin.first_joint;
+            float p[9];
+            load_positions(c, index, p);
+            for (int v = 0; v < 3; ++v) {
+                float n[3], q[4], w[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+                uint32_t j[4] = {0u, 0u, 0u, 0u};
+                load_normal_frame(c, index, v, n, q);
+                if (!rest_skin) {
+                    const float4_t wv = load4(c.skin_weights + 12 * (size_t)lane + 4 * v);
+                    const uint2_t jv = *(const uint2_t*)(c.skin_joints + 12 * (size_t)lane + 4 * v);
+                    w[0] = wv.x, w[1] = wv.y, w[2] = wv.z, w[3] = wv.w;
+                    j[0] = jv.x & 0xFFFFu, j[1] = jv.x >> 16, j[2] = jv.y & 0xFFFFu, j[3] = jv.y >> 16;
+                }
+                bad |= pose::skin_vertex_dual(quats, num_joints, rest_skin != 0u, j, w, pose, p + 3 * v, n, q, c.rest_frames != nullptr);
                 store_normal_frame(c, index, v, n, q);
             }
             bad |= store_positions(c, index, p);
@@ -333,7 +373,8 @@ hipError_t launch_morph(const MorphCtx& c, hipStream_t stream) {
 
 hipError_t launch_pose(const Ctx& c, hipStream_t stream) {
     if (c.posed_triangles) hipLaunchKernelGGL(pose_triangles_kernel, dim3(blocks_for(c.posed_triangles)), dim3(kBlock), 0, stream, c);
-    if (c.skinned_triangles) hipLaunchKernelGGL(skin_triangles_kernel, dim3(blocks_for(c.skinned_triangles)), dim3(kBlock), 0, stream, c);
+    if (c.skinned_triangles && c.skins) hipLaunchKernelGGL(skin_triangles_kernel, dim3(blocks_for(c.skinned_triangles)), dim3(kBlock), 0, stream, c);
+    if (c.skinned_triangles && c.dual_skins) hipLaunchKernelGGL(skin_triangles_dual_kernel, dim3(blocks_for(c.skinned_triangles)), dim3(kBlock), 0, stream, c);
     if (c.posed_spheres) hipLaunchKernelGGL(pose_spheres_kernel, dim3(blocks_for(c.posed_spheres)), dim3(kBlock), 0, stream, c);
     return hipGetLastError();
 }

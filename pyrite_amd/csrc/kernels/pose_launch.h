@@ -12,7 +12,7 @@ struct DevLamp;
 namespace devpose {
 
 constexpr uint32_t kBlock = 256;
-using Flag = pose::Flag; // kBeyondRange, kMorphedNormal, kSmoothedNormal
+using Flag = pose::Flag; // kBeyondRange, kMorphedNormal, kSmoothedNormal, kBlendedRotation
 
 // One object on the device: its pose, its primitive ranges, and where its lanes begin in the launches over all objects'
 // triangles and spheres (the running sums of the counts, in object order). 96 bytes.
@@ -59,6 +59,11 @@ struct Ctx {
     const float* joints;          // [num_joints][12]: a joint's upper three rows, column by column
     const float* skin_weights;    // [skinned_triangles][3][4]
     const uint16_t* skin_joints;  // [skinned_triangles][3][4], relative to the skin's first joint
+    // the dual-quaternion skins (none: dual_skins nullptr and joint_quats unused). Each of the two skin kernels
+    // has a table of its own with num_skins records and the same lanes: a skin of the other kind has no triangles in it, so its
+    // lanes do nothing there, as a skinned object's do in the launch over the objects' triangles.
+    const DevSkin* dual_skins;
+    const float* joint_quats;     // [num_joints][8]: a joint's unit dual quaternion (r, d), parallel to `joints`
 };
 
 // One morph on the device: its object's triangles, where its lanes begin in the launch over all morphed

@@ -1,6 +1,6 @@
 // live_scene.cpp -- everything that moves a scene after creation: pyr_scene_update[_device], pyr_scene_set_objects, pyr_scene_pose,
-// pyr_scene_set_skins, pyr_scene_skin, pyr_scene_set_morphs, pyr_scene_morph, pyr_scene_set_smoothing, pyr_scene_geometry,
-// pyr_scene_update_info -- and pyr_scene_keep_previous, which copies where the geometry is now for the motion pass (api.cpp
+// pyr_scene_set_skins, pyr_scene_set_skin_blend, pyr_scene_skin, pyr_scene_set_morphs, pyr_scene_morph, pyr_scene_set_smoothing,
+// pyr_scene_geometry, pyr_scene_update_info -- and pyr_scene_keep_previous, which copies where the geometry is now for the motion pass (api.cpp
 // enqueues that one). LiveGeometry (scene_internal.h) says where the geometry is and which copies are valid; rebuild_from and
 // refit_from are the two ways new arrays reach the records and trees on the device. The three calls that give a frame -- pose, skin,
 // morph -- are one frame (Frame), one check (check_frame) and one run (scene_pose); the three that attach something to objects --
@@ -168,6 +168,10 @@ int check_frame(const PyrScene* scene, const Update* u, const Frame& f, const Fr
                 if (!std::isfinite(f.joints[k])) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".joints has an entry that is not finite");
             for (uint32_t j = 0; j < f.num_joints; ++j)
                 if (!affine(f.joints + 16 * (size_t)j)) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".joints: the last row must be 0, 0, 0, 1");
+            for (const LiveGeometry::Skin& skin : live.skin.table)
+                for (uint32_t j = skin.first_joint; skin.blend == PYR_SKIN_DUAL_QUATERNION && j < skin.first_joint + skin.num_joints; ++j)
+                    if (!pose::joint_is_rotation(f.joints + 16 * (size_t)j))
+                        return fail(PYR_ERR_INVALID_ARGUMENT, name + ".joints: a joint of a dual-quaternion skin must have a rotation for its upper 3x3 (orthonormal columns within 1e-3, right-handed)");
         }
         if (f.weights) {
             if (f.num_weights != live.morph.weights.size()) return fail(PYR_ERR_INVALID_ARGUMENT, name + ".num_weights is not the scene's");
@@ -380,7 +384,10 @@ devpose::Ctx pose_context(PyrScene* s) {
     c.posed_triangles = live.posed_triangles, c.posed_spheres = live.posed_spheres;
     c.beyond_range = (uint32_t*)live.pose_flag.ptr;
     c.lamps = (DevLamp*)s->lamps.ptr, c.num_lamps = (uint32_t)live.lamps.size();
-    c.skins = (const devpose::DevSkin*)live.skin.records.ptr, c.num_skins = (uint32_t)live.skin.table.size();
+    // (each skin kernel is launched only where a skin of its kind exists: the table of the other one is null)
+    c.skins = live.skin.any(PYR_SKIN_LINEAR) ? (const devpose::DevSkin*)live.skin.records.ptr : nullptr, c.num_skins = (uint32_t)live.skin.table.size();
+    c.dual_skins = live.skin.any(PYR_SKIN_DUAL_QUATERNION) ? (const devpose::DevSkin*)live.skin.dual_records.ptr : nullptr;
+    c.joint_quats = (const float*)live.skin.quats.ptr;
     c.skinned_triangles = live.skin.triangles, c.num_joints = (uint32_t)(live.skin.joints.size() / 16);
     c.joints = (const float*)live.skin.rows.ptr;
     c.skin_weights = (const float*)live.skin.weights.ptr, c.skin_joints = (const uint16_t*)live.skin.indices.ptr;
@@ -440,6 +447,8 @@ int run_pose(PyrScene* s, const std::vector<devpose::DevObject>& table, const st
     std::vector<devpose::DevObject> unskinned; // (these three live until the wait below)
     std::vector<devpose::DevSkin> skins(live.skin.table.size());
     std::vector<float> rows(joints.size() / 16 * 12);
+    std::vector<devpose::DevSkin> dual_skins; // (and these two, which only a scene with a dual-quaternion skin fills)
+    std::vector<float> quats;
     if (live.skin.set()) {
         unskinned = table;
         for (size_t k = 0; k < skins.size(); ++k) {
@@ -459,8 +468,25 @@ int run_pose(PyrScene* s, const std::vector<devpose::DevObject>& table, const st
         for (size_t j = 0; j < rows.size() / 12; ++j)
             for (int col = 0; col < 4; ++col)
                 for (int row = 0; row < 3; ++row) rows[12 * j + 3 * col + row] = joints[16 * j + 4 * col + row];
-        HIP_TRY(hipMemcpyAsync(live.skin.records.ptr, skins.data(), skins.size() * sizeof(devpose::DevSkin), hipMemcpyHostToDevice, stream));
         HIP_TRY(hipMemcpyAsync(live.skin.rows.ptr, rows.data(), rows.size() * 4, hipMemcpyHostToDevice, stream));
+        if (live.skin.any(PYR_SKIN_DUAL_QUATERNION)) {
+            // Each kernel its own table over the same lanes: a skin of the other kind has no triangles there. The joints of the
+            // dual-quaternion skins as unit dual quaternions, eight floats a joint, parallel to `rows`.
+            dual_skins = skins;
+            quats.assign(joints.size() / 16 * 8, 0.0f);
+            for (size_t k = 0; k < skins.size(); ++k) {
+                const LiveGeometry::Skin& from = live.skin.table[k];
+                if (from.blend != PYR_SKIN_DUAL_QUATERNION) {
+                    dual_skins[k].num_triangles = 0;
+                    continue;
+                }
+                skins[k].num_triangles = 0;
+                for (size_t j = from.first_joint; j < (size_t)from.first_joint + from.num_joints; ++j) pose::joint_dual_quaternion(&joints[16 * j], &quats[8 * j]);
+            }
+            HIP_TRY(hipMemcpyAsync(live.skin.dual_records.ptr, dual_skins.data(), dual_skins.size() * sizeof(devpose::DevSkin), hipMemcpyHostToDevice, stream));
+            HIP_TRY(hipMemcpyAsync(live.skin.quats.ptr, quats.data(), quats.size() * 4, hipMemcpyHostToDevice, stream));
+        }
+        HIP_TRY(hipMemcpyAsync(live.skin.records.ptr, skins.data(), skins.size() * sizeof(devpose::DevSkin), hipMemcpyHostToDevice, stream));
     }
     const std::vector<devpose::DevObject>& objects = !live.skin.set() ? table : unskinned;
     HIP_TRY(hipMemcpyAsync(s->live.pose_objects.ptr, objects.data(), objects.size() * sizeof(devpose::DevObject), hipMemcpyHostToDevice, stream));
@@ -512,6 +538,8 @@ int scene_pose(PyrScene* s, const Frame& f, hipStream_t stream) {
          "a morphed normal or the tangent frame rebuilt against it has a squared length outside 1e-30 .. 1e30 and cannot be normalised (pyrite_gpu.h, pyr_scene_morph)"},
         {devpose::Flag::kSmoothedNormal,
          "a recomputed normal or the tangent frame rebuilt against it has a squared length outside 1e-30 .. 1e30 and cannot be normalised (pyrite_gpu.h, pyr_scene_set_smoothing)"},
+        {devpose::Flag::kBlendedRotation,
+         "a blended joint rotation of a dual-quaternion skin has a squared length outside 1e-30 .. 1e30 and cannot be normalised: the rotations of a vertex's joints cancel (pyrite_gpu.h, pyr_scene_set_skin_blend)"},
     };
     for (const auto& r : raised)
         if (flag & r.bit) return refused(fail(PYR_ERR_UNSUPPORTED, r.message));
@@ -809,6 +837,29 @@ int pyr_scene_pose(PyrScene* scene, const PyrPoseUpdate* update, void* hip_strea
 
 int pyr_scene_set_skins(PyrScene* scene, const PyrSkin* skins, uint32_t num_skins) {
     return set_attachments(scene, skins, num_skins, "skins", "pyr_scene_set_skins", &LiveGeometry::skin, &LiveGeometry::forget_skins, check_skins, install_skins);
+}
+
+int pyr_scene_set_skin_blend(PyrScene* scene, const uint32_t* modes, uint32_t num_skins) {
+    if (!modes) return fail(PYR_ERR_INVALID_ARGUMENT, "null modes");
+    if (!scene) return fail(PYR_ERR_INVALID_ARGUMENT, "null scene");
+    LiveGeometry::Skins& skin = scene->live.skin;
+    if (!skin.set()) return fail(PYR_ERR_INVALID_ARGUMENT, "pyr_scene_set_skin_blend: the scene has no skins (pyr_scene_set_skins binds them)");
+    if (num_skins != skin.table.size()) return fail(PYR_ERR_INVALID_ARGUMENT, "pyr_scene_set_skin_blend: num_skins is not the scene's");
+    bool dual = false;
+    for (uint32_t k = 0; k < num_skins; ++k) {
+        if (modes[k] != PYR_SKIN_LINEAR && modes[k] != PYR_SKIN_DUAL_QUATERNION) return fail(PYR_ERR_INVALID_ARGUMENT, "pyr_scene_set_skin_blend: a mode is neither PYR_SKIN_LINEAR nor PYR_SKIN_DUAL_QUATERNION");
+        dual = dual || modes[k] == PYR_SKIN_DUAL_QUATERNION;
+    }
+    HIP_TRY(hipSetDevice(scene->device));
+    HIP_TRY(hipDeviceSynchronize()); // an earlier call's kernels may still read the tables that go
+    DeviceBuffer records, quats; // on the device before anything of the scene changes; a scene without such a skin holds neither
+    int rc;
+    if (dual && (rc = records.alloc(skin.table.size() * sizeof(devpose::DevSkin))) != PYR_OK) return rc;
+    if (dual && (rc = quats.alloc(skin.joints.size() / 16 * 32)) != PYR_OK) return rc;
+    skin.dual_records.swap(records), skin.quats.swap(quats);
+    for (uint32_t k = 0; k < num_skins; ++k) skin.table[k].blend = modes[k];
+    for (size_t j = 0; j < skin.joints.size(); j += 16) std::copy(kIdentity, kIdentity + 16, skin.joints.begin() + j);
+    return PYR_OK;
 }
 
 int pyr_scene_skin(PyrScene* scene, const PyrSkinUpdate* update, void* hip_stream) {

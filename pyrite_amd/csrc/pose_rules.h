@@ -1,10 +1,10 @@
 // pose_rules.h -- the rules of a live scene's deformation pipeline, morph -> skin -> pose -> smooth -> lamps (DESIGN.md sections
-// 9g, 9h, 9p, 9q and 9r), stated once. Two layers: the arithmetic on one vector (pose_point, pose_normal_frame, blend_joints,
-// morph_normal_frame, signed_face_vector, ...) and, below it, what one lane of a kernel does with it over registers and plain
-// pointers ("one lane's walk": pose_vertex, skin_vertex, add_delta, morphed_normal, add_face, finish_corner, pose_sphere,
-// bounds_flag) -- which rule comes first, what an identity copies, which Flag bit a failure raises. The kernels
+// 9g, 9h, 9p, 9q, 9r and 9s), stated once. Two layers: the arithmetic on one vector (pose_point, pose_normal_frame, blend_joints,
+// blend_dual_quaternions, morph_normal_frame, signed_face_vector, ...) and, below it, what one lane of a kernel does with it over
+// registers and plain pointers ("one lane's walk": pose_vertex, skin_vertex, skin_vertex_dual, add_delta, morphed_normal, add_face,
+// finish_corner, pose_sphere, bounds_flag) -- which rule comes first, what an identity copies, which Flag bit a failure raises. The kernels
 // (kernels/pose.hip) keep the lane mapping, the loads and stores and the bounds checks on tables in memory, and call only the
-// second layer; the host rehearsal (tests/probes/deform_check.cpp) calls the same functions under ASan and UBSan, so what the two
+// second layer; the host rehearsals (tests/probes/deform_check.cpp, dq_skin_check.cpp) call the same functions under ASan and UBSan, so what the two
 // compute can differ only in the square root and the reciprocal -- sqrt32 / rcp32 of exact_math.h on the device, std::sqrt and
 // 1.0f / x on the host, bit-identical in the ranges exact_math.h names.
 //
@@ -23,6 +23,12 @@
 #define PYR_POSE_HD __host__ __device__ __forceinline__
 #else
 #define PYR_POSE_HD inline
+#endif
+// a row of a device table that starts on a 16-byte boundary (the host rehearsal's tables are plain vectors: no promise there)
+#if defined(__HIP_DEVICE_COMPILE__)
+#define PYR_POSE_ROW16(p) ((const float*)__builtin_assume_aligned((p), 16))
+#else
+#define PYR_POSE_ROW16(p) (p)
 #endif
 #if !defined(__HIP_DEVICE_COMPILE__)
 #include <cmath>
@@ -45,7 +51,8 @@ struct Pose {
 enum Flag : uint32_t {
     kBeyondRange = 1u,   // a bound of a moved primitive fails the coordinate check, or a table names what lies outside it
     kMorphedNormal = 2u, // a morphed normal or the tangent rebuilt against it cannot be normalised
-    kSmoothedNormal = 4u // a recomputed normal or the tangent rebuilt against it cannot be
+    kSmoothedNormal = 4u, // a recomputed normal or the tangent rebuilt against it cannot be
+    kBlendedRotation = 8u // a vertex's blended dual quaternion cannot be normalised (its joints' rotations cancel)
 };
 
 PYR_POSE_HD float root(float x) {
@@ -73,6 +80,7 @@ PYR_POSE_HD void normalize(float* v) {
     const float k = reciprocal(mag);
     v[0] = v[0] * k, v[1] = v[1] * k, v[2] = v[2] * k;
 }
+PYR_POSE_HD float dot4(const float* a, const float* b) { return ((a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]) + a[3] * b[3]; }
 PYR_POSE_HD void cross(const float* a, const float* b, float* o) {
     o[0] = a[1] * b[2] - a[2] * b[1];
     o[1] = a[2] * b[0] - a[0] * b[2];
@@ -166,6 +174,64 @@ PYR_POSE_HD void blend_joints(const float* joints, const uint32_t* j, const floa
     b.identity = 0u;
 }
 
+// ---- the dual quaternion skin rule (Kavan et al. 2007): a rigid joint as a unit dual quaternion (r, d),
+// eight floats -- r the rotation (s, x, y, z) of the upper 3x3, renormalised, d = 0.5 * (0, t) * r with t the translation column --
+// made once per joint and frame on the host from the joint's matrix `m` (column-major, 16 floats, its upper 3x3 a rotation:
+// pyr_scene_skin refuses any other for such a skin, joint_is_rotation below).
+PYR_POSE_HD void joint_dual_quaternion(const float* m, float* q) {
+    float r[4];
+    quat_from_cols(m, m + 4, m + 8, r);
+    const float k = reciprocal(root(dot4(r, r)));
+    r[0] = r[0] * k, r[1] = r[1] * k, r[2] = r[2] * k, r[3] = r[3] * k;
+    const float* t = m + 12;
+    q[0] = r[0], q[1] = r[1], q[2] = r[2], q[3] = r[3];
+    q[4] = -0.5f * ((t[0] * r[1] + t[1] * r[2]) + t[2] * r[3]);
+    q[5] = 0.5f * ((t[0] * r[0] + t[1] * r[3]) - t[2] * r[2]);
+    q[6] = 0.5f * ((t[1] * r[0] + t[2] * r[1]) - t[0] * r[3]);
+    q[7] = 0.5f * ((t[0] * r[2] + t[2] * r[0]) - t[1] * r[1]);
+}
+// What pyr_scene_skin takes for a rotation in a dual-quaternion skin's joint: columns of length 1 and pairwise orthogonal within
+// 1e-3, right-handed.
+PYR_POSE_HD bool joint_is_rotation(const float* m) {
+    const float *c0 = m, *c1 = m + 4, *c2 = m + 8;
+    const auto dot = [](const float* a, const float* b) { return (a[0] * b[0] + a[1] * b[1]) + a[2] * b[2]; };
+    if (!(magnitude(dot(c0, c0) - 1.0f) <= 1.0e-3f) || !(magnitude(dot(c1, c1) - 1.0f) <= 1.0e-3f) || !(magnitude(dot(c2, c2) - 1.0f) <= 1.0e-3f)) return false;
+    if (!(magnitude(dot(c0, c1)) <= 1.0e-3f) || !(magnitude(dot(c0, c2)) <= 1.0e-3f) || !(magnitude(dot(c1, c2)) <= 1.0e-3f)) return false;
+    float x[3];
+    cross(c0, c1, x);
+    return dot(x, c2) > 0.0f;
+}
+// One vertex's matrix from four joints' dual quaternions, `table` holding eight floats a joint and j0..j3 already compared against
+// the skin's joint count. The pivot is joint j0: a joint whose rotation lies in the other hemisphere (dot4 < 0; zero or NaN does
+// not) has its weight negated, so that q and -q, the same motion, blend the short way. Every entry of the blend is
+// ((w0'*Q0 + w1'*Q1) + w2'*Q2) + w3'*Q3, unfused; it is normalised by its rotation part, t = 2 * (d * conj(r)) is the translation
+// and cgmath's Matrix3::from(Quaternion) the upper 3x3; the last row is 0,0,0,1. The vertex then takes the per-vertex rule above
+// with Pose{B, 1.0f, not identity}, exactly as after blend_joints. Returns whether the squared length that is normalised lies
+// outside [1e-30, 1e30] (kBlendedRotation; what is written then is not used).
+PYR_POSE_HD bool blend_dual_quaternions(const float* table, const uint32_t* j, const float* w, Pose& b) {
+    const float *q0 = PYR_POSE_ROW16(table + 8 * (size_t)j[0]), *q1 = PYR_POSE_ROW16(table + 8 * (size_t)j[1]), *q2 = PYR_POSE_ROW16(table + 8 * (size_t)j[2]),
+                *q3 = PYR_POSE_ROW16(table + 8 * (size_t)j[3]);
+    const float w1 = dot4(q0, q1) < 0.0f ? -w[1] : w[1], w2 = dot4(q0, q2) < 0.0f ? -w[2] : w[2], w3 = dot4(q0, q3) < 0.0f ? -w[3] : w[3];
+    float e[8];
+    for (int i = 0; i < 8; ++i) e[i] = ((w[0] * q0[i] + w1 * q1[i]) + w2 * q2[i]) + w3 * q3[i];
+    const float s = dot4(e, e);
+    const bool bad = !(s >= 1.0e-30f && s <= 1.0e30f);
+    const float k = reciprocal(root(s));
+    const float r0 = e[0] * k, r1 = e[1] * k, r2 = e[2] * k, r3 = e[3] * k, d0 = e[4] * k, d1 = e[5] * k, d2 = e[6] * k, d3 = e[7] * k;
+    const float x2 = r1 + r1, y2 = r2 + r2, z2 = r3 + r3;
+    const float xx2 = x2 * r1, xy2 = x2 * r2, xz2 = x2 * r3, yy2 = y2 * r2, yz2 = y2 * r3, zz2 = z2 * r3, sx2 = x2 * r0, sy2 = y2 * r0, sz2 = z2 * r0;
+    b.m[0] = 1.0f - yy2 - zz2, b.m[1] = xy2 + sz2, b.m[2] = xz2 - sy2, b.m[3] = 0.0f;
+    b.m[4] = xy2 - sz2, b.m[5] = 1.0f - xx2 - zz2, b.m[6] = yz2 + sx2, b.m[7] = 0.0f;
+    b.m[8] = xz2 + sy2, b.m[9] = yz2 - sx2, b.m[10] = 1.0f - xx2 - yy2, b.m[11] = 0.0f;
+    b.m[12] = 2.0f * (((d1 * r0 - d0 * r1) - d2 * r3) + d3 * r2);
+    b.m[13] = 2.0f * (((d2 * r0 - d0 * r2) + d1 * r3) - d3 * r1);
+    b.m[14] = 2.0f * (((d3 * r0 - d0 * r3) - d1 * r2) + d2 * r1);
+    b.m[15] = 1.0f;
+    b.scale = 1.0f;
+    b.identity = 0u;
+    return bad;
+}
+
 // ---- the morph rule: what a vertex normal and its tangent frame become once the active targets' normal
 // deltas have been added to the normal (`n` comes in as m = n + sum w[t] * dn[t], the caller's loop over the active targets in
 // ascending t, and leaves as normalize(m)). `frame` nullptr: the scene keeps none; otherwise the old tangent frame is
@@ -241,6 +307,24 @@ PYR_POSE_HD uint32_t skin_vertex(const float* joints, uint32_t num_joints, bool 
         }
         Pose blended;
         blend_joints(joints, inside, w, blended);
+        pose_vertex(blended, p, n, frame, has_frames);
+    }
+    pose_vertex(pose, p, n, frame, has_frames);
+    return raised;
+}
+// One vertex of a dual-quaternion skin: skin_vertex with blend_dual_quaternions in place of blend_joints.
+// `table`: the skin's rows of the dual quaternion table. Returns the bits raised: kBeyondRange as there, kBlendedRotation.
+PYR_POSE_HD uint32_t skin_vertex_dual(const float* table, uint32_t num_joints, bool skin_at_rest, const uint32_t* j, const float* w, const Pose& pose, float* p, float* n,
+                                      float* frame, bool has_frames) {
+    uint32_t raised = 0u;
+    if (!skin_at_rest) {
+        uint32_t inside[4];
+        for (int k = 0; k < 4; ++k) {
+            inside[k] = j[k];
+            if (inside[k] >= num_joints) inside[k] = 0u, raised = kBeyondRange;
+        }
+        Pose blended;
+        if (blend_dual_quaternions(table, inside, w, blended)) raised |= kBlendedRotation;
         pose_vertex(blended, p, n, frame, has_frames);
     }
     pose_vertex(pose, p, n, frame, has_frames);

@@ -101,24 +101,33 @@ struct LiveGeometry {
     uint32_t posed_triangles = 0, posed_spheres = 0;
     DeviceBuffer pose_objects, pose_flag;
     // the skins in skin order (pyr_scene_set_skins): whose triangles, which rows of the joint table, where the lanes and bindings
-    // begin; and the joint matrices the scene is in, [joints][16] (identity when the skins are set)
+    // begin, and how its joints are blended (PYR_SKIN_*: linear when the skins are set, pyr_scene_set_skin_blend says otherwise); and
+    // the joint matrices the scene is in, [joints][16] (identity when the skins are set). `dual_records` and `quats` exist only
+    // while some skin is dual-quaternion.
     struct Skin {
-        uint32_t object, num_joints, first_joint, lane;
+        uint32_t object, num_joints, first_joint, lane, blend;
     };
     struct Skins {
         std::vector<Skin> table;
         std::vector<float> joints;
-        uint32_t triangles = 0;                         // lanes of the skin kernel
+        uint32_t triangles = 0;                         // lanes of the skin kernels
         DeviceBuffer records, weights, indices, rows;   // DevSkin records, the two binding arrays, twelve floats a joint
+        DeviceBuffer dual_records, quats;               // the dual-quaternion kernel's DevSkin records, eight floats a joint
         bool set() const { return !table.empty(); }
+        bool any(uint32_t blend) const {
+            for (const Skin& s : table)
+                if (s.blend == blend) return true;
+            return false;
+        }
         void clear() {
             table.clear(), joints.clear();
             triangles = 0;
-            for (DeviceBuffer* b : {&records, &weights, &indices, &rows}) b->release();
+            for (DeviceBuffer* b : {&records, &weights, &indices, &rows, &dual_records, &quats}) b->release();
         }
         void swap(Skins& o) {
             table.swap(o.table), joints.swap(o.joints), std::swap(triangles, o.triangles);
             records.swap(o.records), weights.swap(o.weights), indices.swap(o.indices), rows.swap(o.rows);
+            dual_records.swap(o.dual_records), quats.swap(o.quats);
         }
     } skin;
     // the morphs in morph order (pyr_scene_set_morphs): whose triangles, how many targets, where its weights begin in the weight

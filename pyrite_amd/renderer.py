@@ -224,12 +224,20 @@ class World:
             s = skins[index]
             records[k] = abi.PyrSkin(object=index, num_joints=s["num_joints"], joints=s["joints"].ctypes.data, weights=s["weights"].ctypes.data)
         check(lib().pyr_scene_set_skins(handle, records, len(order)))
+        if any(skins[index]["blend"] != "linear" for index in order):  # (pyr_scene_set_skins has made every skin linear)
+            modes = (C.c_uint32 * len(order))(*[self.SKIN_BLENDS[skins[index]["blend"]] for index in order])
+            check(lib().pyr_scene_set_skin_blend(handle, modes, len(order)))
+
+    SKIN_BLENDS = {"linear": abi.PYR_SKIN_LINEAR, "dual_quaternion": abi.PYR_SKIN_DUAL_QUATERNION}
 
     def set_skins(self, skins):
         """Binds meshes to joints (pyr_scene_set_skins on every scene of this world): `skins` maps an object's index in
         `World.objects` to dict(joints=uint16 [T,3,4], weights=float32 [T,3,4], num_joints=J) for that object's T triangles --
-        four joint indices below J and four weights per vertex. Skins are in the order of their object indices. Every joint is
-        the identity afterwards and the geometry does not change; an empty dict forgets the skins."""
+        four joint indices below J and four weights per vertex -- and, if wanted, blend="linear" (the default: the vertex's
+        matrix is the weighted sum of its joints' matrices) or "dual_quaternion" (pyr_scene_set_skin_blend: the joints are blended
+        as rigid motions, which keeps the volume of a twisting mesh; the joints of such a skin must be rotations and
+        translations). Skins are in the order of their object indices. Every joint is the identity afterwards and the geometry
+        does not change; an empty dict forgets the skins."""
         bound = {}
         for index, s in skins.items():
             if not 0 <= int(index) < len(self._objects):
@@ -240,7 +248,11 @@ class World:
                 raise ValueError("the skin of object %r needs joints and weights of shape %r, not %r and %r" % (index, shape, joints.shape, weights.shape))
             if joints.size and (joints.min() < 0 or joints.max() > 0xFFFF):
                 raise ValueError("the skin of object %r names a joint index that is no uint16" % (index,))
-            bound[int(index)] = dict(joints=np.ascontiguousarray(joints, dtype=np.uint16), weights=np.ascontiguousarray(weights, dtype=np.float32), num_joints=int(s["num_joints"]))
+            blend = s.get("blend", "linear")
+            if blend not in self.SKIN_BLENDS:
+                raise ValueError("the skin of object %r has blend %r: it must be 'linear' or 'dual_quaternion'" % (index, blend))
+            bound[int(index)] = dict(joints=np.ascontiguousarray(joints, dtype=np.uint16), weights=np.ascontiguousarray(weights, dtype=np.float32), num_joints=int(s["num_joints"]),
+                                     blend=blend)
         for handle in self._scenes.values():
             self._set_skins(handle, bound)
         self._skins, self._joints = bound, {}

@@ -8,8 +8,9 @@ One process, one GPU. Two meshes: C3's (scenes.c3_flat) and the 160 x 160 torus 
 joints placed along its parameter (the closed curve the tube follows): a vertex of segment s lies between joints floor(64 s / S)
 and the next one, and its two weights fall linearly between them. Per mesh one warm-up and `repeats` (default 7) rounds; in a round
 every joint turns about the vertical axis through the knot's centre and rises or sinks, by amounts that vary along the knot and grow
-from round to round, in three ways on three live scenes, alternating:
+from round to round, in four ways on four live scenes, alternating:
   skin       World.skin: 64 matrices, the triangles computed on the device (pyr_scene_skin, refit)
+  skin-dq    the same frame with the skin dual-quaternion (pyr_scene_set_skin_blend); its row comes last
   update     World.update(mode="refit") from host arrays (pyr_scene_update) of the same deformed geometry
   update-dev World.update(mode="refit") from torch tensors on the device (pyr_scene_update_device), uploaded beforehand
 The arrays of the last two are computed by the numpy restatement of the skin rule (tests/skin_restatement.py) before the clock starts;
@@ -27,6 +28,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 sys.path.insert(0, os.path.join(ROOT, "tests"))
 
+import dq_skin_restatement  # noqa: E402
 import skin_restatement as restatement  # noqa: E402
 
 from pyrite_amd import scenes  # noqa: E402
@@ -85,7 +87,7 @@ def report(title, runs):
 def timings(title, mesh):
     import torch
 
-    live = {way: World(scenes.c3_flat(**mesh)) for way in ("skin", "update", "update-dev")}
+    live = {way: World(scenes.c3_flat(**mesh)) for way in ("skin", "update", "update-dev", "skin-dq")}
     rest = rest_of(live["skin"])
     ranges = live["skin"].objects
     knot = [k for k, o in enumerate(ranges) if o["first_triangle"] == BOX_TRIANGLES]
@@ -97,6 +99,8 @@ def timings(title, mesh):
     for world in live.values():
         world.scene(0, build="device")
     live["skin"].set_skins(skins)
+    dual = {index: dict(skin, blend="dual_quaternion") for index, skin in skins.items()}
+    live["skin-dq"].set_skins(dual)
     runs = {way: [] for way in live}
     host_ms = []
     for i in range(REPEATS + 1):
@@ -109,7 +113,8 @@ def timings(title, mesh):
         row = {}
         for way, call in (("skin", lambda: live["skin"].skin(joints)),
                           ("update", lambda: live["update"].update(positions=p, normals=n, mode="refit")),
-                          ("update-dev", lambda: live["update-dev"].update(positions=tp, normals=tn, mode="refit"))):
+                          ("update-dev", lambda: live["update-dev"].update(positions=tp, normals=tn, mode="refit")),
+                          ("skin-dq", lambda: live["skin-dq"].skin(joints))):
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             call()
@@ -130,6 +135,12 @@ def timings(title, mesh):
     got = live["skin"].geometry()
     differ = sum(int((got[key].view(np.uint32) != want[key].view(np.uint32)).sum()) for key in ("positions", "normals"))
     print("    words of the skinned positions and normals that differ from the restatement's: %d" % differ, flush=True)
+    report("skin-dq    (World.skin with the skin dual-quaternion, refit)", runs["skin-dq"])
+    print("    total_ms medians: skin-dq / skin = %.2f; wall_ms medians: skin-dq / skin = %.2f"
+          % (statistics.median(r["total_ms"] for r in runs["skin-dq"]) / med["skin"], statistics.median(r["wall_ms"] for r in runs["skin-dq"]) / wall["skin"]))
+    got, want = live["skin-dq"].geometry(), dq_skin_restatement.dq_skin_arrays(rest, ranges, dual, joints)
+    differ = sum(int((got[key].view(np.uint32) != want[key].view(np.uint32)).sum()) for key in ("positions", "normals"))
+    print("    words of its positions and normals that differ from the dual quaternion restatement's: %d" % differ, flush=True)
     for world in live.values():
         world.close()
 
