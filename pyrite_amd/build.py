@@ -13,8 +13,8 @@ KERNELS = os.path.join(CSRC, "kernels")  # the units that instantiate the kernel
 KERNEL_UNITS = ["main.hip", "interp.hip", "product.hip", "wide.hip", "film.hip", "features.hip", "features_wide.hip", "tone.hip", "denoise.hip", "build.hip", "refit.hip", "pose.hip", "motion.hip", "reproject.hip", "motion_blur.hip", "temporal.hip", "glare.hip", "upsample.hip", "despeckle.hip", "lens_blur.hip"]
 PROFILE_UNIT = "profile.hip"  # -DPYR_PHASE_PROFILE builds: main, interp and product in one unit, no wide build
 PLAIN_UNITS = ["film.hip", "features.hip", "features_wide.hip", "tone.hip", "denoise.hip", "build.hip", "refit.hip", "pose.hip", "motion.hip", "reproject.hip", "motion_blur.hip", "temporal.hip", "glare.hip", "upsample.hip", "despeckle.hip", "lens_blur.hip"]  # units without phase counters: every build has them
-SOURCES = ["api.cpp", "live_scene.cpp", "session.cpp", "image_ops.cpp", "multi.cpp", "bvh.cpp", "bvh_device.cpp", "program_regs.cpp"]
-HEADERS = ["kernels.hip", "bvh.h", "bvh_level.h", "bvh_device.h", "device_scene.h", "api_internal.h", "scene_internal.h", "image_internal.h", "exact_math.h", "pose_rules.h", "program_regs.h", os.path.join("..", "..", "include", "pyrite_gpu.h")]
+SOURCES = ["api.cpp", "scene_create.cpp", "scene_pack.cpp", "error.cpp", "live_scene.cpp", "session.cpp", "image_ops.cpp", "multi.cpp", "bvh.cpp", "bvh_device.cpp", "program_regs.cpp"]
+HEADERS = ["kernels.hip", "bvh.h", "bvh_level.h", "bvh_device.h", "device_scene.h", "api_internal.h", "error.h", "scene_internal.h", "scene_pack.h", "image_internal.h", "exact_math.h", "pose_rules.h", "program_regs.h", os.path.join("..", "..", "include", "pyrite_gpu.h")]
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 FLAGS = [
     "-O3", "-std=c++17", "--offload-arch=gfx950", "-fPIC", "-shared",

@@ -1,18 +1,17 @@
-// api_internal.h -- what the host-side translation units of libpyrite_gpu.so and the launchers under kernels/ share besides the
-// public ABI: the one error channel, and a device allocation that frees itself.
+// api_internal.h -- what the host-side translation units of libpyrite_gpu.so that talk to the device and the launchers under
+// kernels/ share besides the public ABI: the one error channel (error.h) with HIP's errors on it, and a device allocation that
+// frees itself (scene_create.cpp defines its methods).
 #pragma once
 #include <hip/hip_runtime.h>
 
 #include <string>
 
 #include "../../include/pyrite_gpu.h"
+#include "error.h"
 
 namespace pyr {
 
-// Records the thread-local message pyr_last_error() returns and hands `code` back. Everything that refuses or fails reports
-// here -- entry points, checks, the kernels' launchers -- so whoever gets a code back passes it on and the message is the failure's.
-int fail(int code, const std::string& message);
-int hip_fail(hipError_t e, const char* what);
+int hip_fail(hipError_t e, const char* what); // fail(PYR_ERR_DEVICE, what + ": " + HIP's words for e)
 
 #define HIP_TRY(expr)                                          \
     do {                                                       \

@@ -1,4 +1,4 @@
-// device_scene.h -- layout of the frozen scene in HBM, shared by the host packer (api.cpp) and the kernels.
+// device_scene.h -- layout of the frozen scene in HBM, shared by the host packer (scene_pack.cpp), the uploader (scene_create.cpp) and the kernels.
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -75,7 +75,7 @@ enum FastProgram : uint32_t {
 //              (kernels.hip lambda_eval) -- and the record names it;
 //   PRODUCT    the program's value is a chain of products ((l * h1) * h2) ... with ONE factor l that depends on the wavelength alone in
 //              LAMBDA's sense and up to three factors that depend on the hit alone (a mono texture times a spectrum times a number: the
-//              textured lamps of the fuzz scenes and of the generated textures scene, a tinted mask): api.cpp splits it into two programs
+//              textured lamps of the fuzz scenes and of the generated textures scene, a tinted mask): scene_pack.cpp splits it into two programs
 //              of its own instructions -- the hit side (HIT_VALUE) and the wavelength side (DIRECT or LAMBDA, with a value slot) -- the
 //              interpreter runs the hit side once per hit, and records carry h1 to the slot's value, h2 ... to that product and the
 //              contribution's factor to the result: the products the interpreter and `contribute` form, in their order;
@@ -94,7 +94,7 @@ struct DevProgram {
     uint32_t reads_wavelength; // some executed operand is Input(Wavelength): ProbabilityInput::wavelength_used
     uint32_t tape_form;        // TapeForm
     // HIT_RGB: the rgb register the closing RgbSpectrumValue reads. PRODUCT (one word, so that the record stays twelve: three more were 8 % of
-    // the example scenes' throughput): bits 0-7 / 8-15 the two programs api.cpp made of this one's instructions, the hit side and the
+    // the example scenes' throughput): bits 0-7 / 8-15 the two programs scene_pack.cpp made of this one's instructions, the hit side and the
     // wavelength side; bits 16-19 the number of hit-side factors (1-3), bits 20-23, 24-27, 28-31 their number registers, innermost product first
     uint32_t tape_rgb_reg;
 };

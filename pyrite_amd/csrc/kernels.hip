@@ -37,7 +37,7 @@
 // pick_product_kernel(); wide.hip: the wide interpreter build; profile.hip: the first three in one piece for -DPYR_PHASE_PROFILE
 // builds, whose device-side counters must live in one translation unit). pyrite_amd/build.py compiles the four side by side.
 // Its one parameter is PYR_WIDE_VM, which wide.hip defines: the online interpreter builds of render_kernel_sm (no tape) whose register
-// files (struct Vm) hold PYR_WIDE_*_REGISTERS, for scenes with a program that needs more than the in-register file even after api.cpp's
+// files (struct Vm) hold PYR_WIDE_*_REGISTERS, for scenes with a program that needs more than the in-register file even after scene_pack.cpp's
 // register allocation (program_regs.h). Everything of that unit lives in a namespace of its own, pyr::wide: the same templates with
 // another Vm under the same names would break the one-definition rule.
 #ifdef PYR_WIDE_VM
@@ -2505,7 +2505,7 @@ struct Walker {
                 const DevProgram colour = S.programs[c_color];
                 // (PRODUCT is a build of its own: the three conditions it adds here, compiled into every interpreter kernel, cost the reference's
                 // example scenes 5-11 % -- these kernels sit on the edge of their register budget)
-                const bool product = PRODUCT && colour.tape_form == TAPE_FORM_PRODUCT; // its hit side is a program of its own (api.cpp split_product)
+                const bool product = PRODUCT && colour.tape_form == TAPE_FORM_PRODUCT; // its hit side is a program of its own (scene_pack.cpp split_product)
                 const bool run_colour = colour.tape_form == TAPE_FORM_HIT_VALUE || colour.tape_form == TAPE_FORM_HIT_RGB || product; // the interpreter runs its hit part; everything else is looked up by the replay
                 // job 0: the probability program in full (it is evaluated for the hero wavelength only); job 1: the colour program's
                 // instructions that do not depend on the wavelength -- all of a HIT_VALUE program, all but the closing one of a HIT_RGB
@@ -2537,7 +2537,7 @@ struct Walker {
                     tape_push_raw(L, flags | (kTapeOneSlot << TAPE_EAGER_SLOT_SHIFT), hit_value * factor); // value * factor is the product contribute forms
                 } else if (product) { // t = value[slot of the wavelength side] * h1, t = t * h2 ...: the program's products in its order; then t * factor
                     const uint32_t packed = colour.tape_rgb_reg;
-                    const uint32_t slot = tape_prepared != nullptr ? tape_prepared[8 * ((packed >> 8) & 255u) + 7] : kTapeOneSlot; // (a hit-tape scene always replays eagerly: api.cpp)
+                    const uint32_t slot = tape_prepared != nullptr ? tape_prepared[8 * ((packed >> 8) & 255u) + 7] : kTapeOneSlot; // (a hit-tape scene always replays eagerly: scene_pack.cpp pack_tables)
                     const uint32_t hero = c_companions ? 0u : TAPE_HERO_ONLY, factors = (packed >> 16) & 15u;
                     tape_push_raw(L, hero | TAPE_RGB_FIRST | (slot << TAPE_EAGER_SLOT_SHIFT), vm.num[(packed >> 20) & 15u]);
                     for (uint32_t k = 1; k < factors; ++k)
@@ -2842,7 +2842,7 @@ DEV float lambda_eval(const DevScene& S, const DevProgram& p, float wavelength) 
             r = ins.operator_ == PYR_BIN_ADD ? l + rr : (ins.operator_ == PYR_BIN_SUB ? l - rr : (ins.operator_ == PYR_BIN_MUL ? l * rr : l / rr));
             break;
         }
-        default: { // PYR_OP_CLAMP (api.cpp admits no other opcode into a LAMBDA program)
+        default: { // PYR_OP_CLAMP (scene_pack.cpp pack_program admits no other opcode into a LAMBDA program)
             const float v = value(ins.x), mn = value(ins.y), mx = value(ins.z);
             r = fmaxf(fminf(v, mx), mn);
             break;
@@ -3259,7 +3259,7 @@ DEV uint32_t prepare_tape_tables(const DevScene& S0, const DevScene& S, const Re
     // The value rows (the last one holds 1.0; a scene with HIT_RGB programs keeps the RGB basis in three of them, behind the
     // programs' slots): too many spectrum-reading programs for them and the replay looks values up record by record. A scene
     // without any such program has nothing to look up eagerly -- unless it records hit-tape forms, which only the eager replay knows
-    // (api.cpp makes sure they fit).
+    // (scene_pack.cpp pack_tables makes sure they fit).
     eager = L.tape_programs_lds != 0 && (paired || (PAIRS ? tape_packed_rows(n_spectral) : tape_rows_needed(n_spectral, S0.rgb_records != 0)) <= S0.tape_value_rows) &&
             (n_spectral != 0 || S0.hit_tape != 0);
     return eager ? n_spectral : 0u;
@@ -3330,7 +3330,7 @@ __global__ __launch_bounds__(BLOCK, sm_waves(INTERP)) void render_kernel_sm(DevS
         if (eager) w.tape_prepared = prepared_lds;
         w.rgb_slot = tape_rgb_row(n_spectral);
         w.tape_column = blockIdx.x * BLOCK + threadIdx.x;
-        if (HIT_TAPE && !eager) *L.tape_overflow = 1u; // api.cpp only marks a scene hit_tape when its value slots fit: never taken
+        if (HIT_TAPE && !eager) *L.tape_overflow = 1u; // scene_pack.cpp pack_tables only marks a scene hit_tape when its value slots fit: never taken
     }
 
     // the scene record as the phases see it (table pointers at the staged copies), rebuilt where a phase starts

@@ -210,7 +210,7 @@ static size_t render_lds_bytes(const DevScene& scene, const RenderLaunch& launch
 }
 
 
-// A scene staged in LDS never has its tables staged too (api.cpp: lds_table_floats is only set for scenes that do not live in
+// A scene staged in LDS never has its tables staged too (scene_pack.cpp pack_records: lds_table_floats is only set for scenes that do not live in
 // LDS), so that combination is never instantiated.
 static RenderKernel pick_kernel(bool sm, bool with_counters, bool interp, bool lds_scene, bool lds_tables, bool hit_tape, bool product, bool wide_vm) {
     if (interp && wide_vm) return pick_wide_kernel(with_counters, lds_scene, lds_tables);

@@ -262,12 +262,8 @@ int refit_from(PyrScene* s, const float* const sources[NUM_ARRAYS], bool write_t
 // arrays (and so forgets the objects, if there is one), the refit starts over, and `info` becomes the scene's.
 int rebuild_from(PyrScene* s, const float* const arrays[NUM_ARRAYS], Clock::time_point t_start, PyrUpdateInfo info) {
     const PyrSceneDesc d = s->live.view(arrays);
-    const PyrBuildInfo build_before = s->build_info;
     const int rc = pack_geometry(&d, s, s->builder);
-    if (rc != PYR_OK) {
-        s->build_info = build_before;
-        return rc;
-    }
+    if (rc != PYR_OK) return rc;
     s->live.adopted(arrays, false);
     s->live.built();
     info.updates = 0;

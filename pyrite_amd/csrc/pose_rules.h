@@ -367,7 +367,7 @@ PYR_POSE_HD uint32_t bounds_flag(const float* lo, const float* hi) {
     return bad ? kBeyondRange : 0u;
 }
 
-// ---- the lamp rule: what a shape lamp's record takes from its shape, with pack_lamp's arithmetic (api.cpp)
+// ---- the lamp rule: what a shape lamp's record takes from its shape, with pack_lamp's arithmetic (scene_pack.cpp)
 struct LampShape {
     float v[3], width; // sphere: centre and radius
     float p[9], n[9];  // triangle: vertices and vertex normals

@@ -1,37 +1,20 @@
-// scene_internal.h -- what api.cpp (creation, renders, feature passes), live_scene.cpp (everything that moves a scene after
-// creation) and session.cpp (progressive sessions) all see of a PyrScene. Declarations, but for the coordinate test: api.cpp
-// defines what is not said to live elsewhere.
+// scene_internal.h -- what scene_create.cpp (creation), api.cpp (renders, feature passes), live_scene.cpp (everything that moves
+// a scene after creation) and session.cpp (progressive sessions) all see of a PyrScene. Declarations only; what packs a scene
+// on the host -- pack_lamp and the coordinate test among it -- comes with scene_pack.h.
 #pragma once
 #include <hip/hip_runtime.h>
 
-#include <chrono>
-#include <cmath>
 #include <memory>
 #include <string>
 #include <vector>
 
 #include "api_internal.h"
-#include "bvh.h"
-#include "device_scene.h"
 #include "kernels/pose_launch.h"
+#include "scene_pack.h"
 
 namespace pyr {
 
-double ms_between(std::chrono::steady_clock::time_point a, std::chrono::steady_clock::time_point b);
-
-// pyrite_gpu.h "Coordinates": what pack_geometry, pyr_scene_update and pyr_scene_pose refuse, in the same words. The test runs
-// once per primitive of every creation and update, so it is the one body here: a call into another unit costs a millisecond
-// per million triangles.
-constexpr float kMaxCoordinate = 1.0e15f;
-extern const char* const kCoordinateRangeMessage;
-inline bool within_coordinate_range(const PrimBounds& b) {
-    for (int a = 0; a < 3; ++a)
-        if (!(std::fabs(b.lo[a]) <= kMaxCoordinate && std::fabs(b.hi[a]) <= kMaxCoordinate)) return false;
-    return true;
-}
-
-// One DevLamp from the description, and the geometry part of scene creation (api.cpp): `d` needs its geometry fields and lamps.
-DevLamp pack_lamp(const PyrSceneDesc* d, uint32_t i);
+// The geometry part of scene creation, once more over a scene that exists (scene_create.cpp): `d` needs its geometry fields and lamps.
 int pack_geometry(const PyrSceneDesc* d, PyrScene* s, uint32_t builder);
 
 // The render side, for the units that enqueue renders and feature passes of a scene (api.cpp defines it, session.cpp calls it).

@@ -119,7 +119,7 @@ def pose_arrays(rest, ranges, poses):
 
 
 def lamp_areas(arrays, lamps):
-    """pack_lamp's surface areas (api.cpp) for shape lamps, unfused f32: 0.5 * sqrt(|a x b|^2) and r*r*4*pi. `lamps`: a list of
+    """pack_lamp's surface areas (scene_pack.cpp) for shape lamps, unfused f32: 0.5 * sqrt(|a x b|^2) and r*r*4*pi. `lamps`: a list of
     (shape_kind, shape_index) with shape_kind 0 = sphere, 1 = triangle (PYR_SHAPE_*)."""
     areas = []
     for kind, index in lamps:

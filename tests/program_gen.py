@@ -2,7 +2,7 @@
 what a caller of pyr_scene_create may hand over, not only what compiler.py and lua_project.py happen to emit. Test infrastructure.
 
 `Gen.program()` is the generator tests/test_program_registers.py has always used (its draws are unchanged). The families on top of
-it each draw from a random stream of their own and aim at one decision of api.cpp's pack_program / split_product or at one corner
+it each draw from a random stream of their own and aim at one decision of scene_pack.cpp's pack_program / split_product or at one corner
 of the interpreters (kernels.hip Vm::step, lambda_eval, the tape replay, the wide build). Every instruction carries its transitive
 dependencies. No family emits a program whose memoised re-run differs from its full run (include/pyrite_gpu.h, PyrInstr::deps)."""
 import zlib

@@ -6,7 +6,7 @@ A. Every instruction, bit for bit, through the feature pass: with grid 1 and a m
    (tests/program_restatement.py), run on the oracle's first-hit surface data, gives the expected bit pattern of every grain; inf and
    NaN included. The in-register build and the wide build both run (features_kernel<true>, wide::features_kernel<true>).
 B. Every program form through the render kernels: scenes whose colour programs are all of one family, so that
-   pyr_scene_path_info's `tape` tells what api.cpp's pack_program / split_product made of them, rendered with and without the hit
+   pyr_scene_path_info's `tape` tells what scene_pack.cpp's pack_program / split_product made of them, rendered with and without the hit
    tape at 1, 4 and 7 wavelengths a path, staged in LDS and on a mesh walked from memory, against the oracle's film as
    tests/test_gpu_parity.py states parity.
 
@@ -69,20 +69,25 @@ def grey():
 A_SIZE = (32, 20)
 
 
-def feature_world(cases, normal_maps=()):
+def feature_flat(cases, normal_maps=()):
     """A plane and seven spheres, one diffuse component each: object k is coloured by cases[k] (grey where there is none) and bent
-    by normal_maps[k]. Returns (World, the cases by material index, the normal maps by material index)."""
+    by normal_maps[k]. Cases past the eighth are programs of the scene that colour nothing (tests/test_scene_pack_cpu.py packs the
+    whole corpus that way). Returns the FlatScene."""
     flat = tables_flat()
     assert not flat.components and not flat.materials
     flat.add_world({"objects": [plane(grey())] + [sphere(k, grey()) for k in range(len(SPHERES))]})
     assert len(flat.components) == len(flat.materials) == 1 + len(SPHERES)
     ids = append_programs(flat, list(cases) + list(normal_maps))
-    for k in range(len(cases)):
+    for k in range(min(len(cases), len(flat.components))):
         flat.components[k]["color"] = ids[k]
     for k in range(len(normal_maps)):
         m = flat.materials[k]
         flat.materials[k] = (m[0], m[1], m[2], m[3], ids[len(cases) + k])
-    return World(flat)
+    return flat
+
+
+def feature_world(cases, normal_maps=()):
+    return World(feature_flat(cases, normal_maps))
 
 
 def feature_renderer():

@@ -240,7 +240,7 @@ def test_the_families_fill_their_quotas():
 def test_the_families_are_what_they_claim():
     """The structural claims of the generator, checked on the instructions: dependencies are transitive and true; hit_value and
     normal_map read no wavelength; lambda is number-only without hit inputs; hit_rgb has exactly one dependent instruction, its
-    last; every near miss is named after a condition of api.cpp."""
+    last; every near miss is named after a condition of scene_pack.cpp."""
     hit = abi.DEP_NORMAL | abi.DEP_INCIDENT | abi.DEP_TEXTURE
     for case in corpus():
         deps_of = {"n": {}, "v": {}, "c": {}}
